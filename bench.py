@@ -18,10 +18,17 @@ Multi-GPU: the grid's LPs are independent, so the path shards with no data-path 
 A committed event is one increment of the reference's `total_events_processed`
 (happysimulator/core/simulation.py:493) -- the same number the CPU reference reports for the same seed.
 
-The default invocation (`--workload grid`, one GPU) also times the other two BASELINE workloads for the same --steps / --warmup
--- the 65 536-station ring (configs[2]) and the consistent-hash load balancer (configs[4]) -- and the 8-GPU strong shard of the
-grid (8 192 LPs), and prints them INSIDE the one JSON line as `workloads.{ring,lb}` (each with its own value, ms_per_step,
-roofline and cpu_baseline) and `strong_shard`; `--extras 0` leaves them out.
+A plain run sets up, warms up, times the --steps steps and prints the line: its `value`, `ms_per_step` and `roofline` (the
+HBM figures of the timed steps, and the committed profiles' counters while they describe the kernels that ran).  `--full` adds
+everything else the benchmark measures, each with runs of its own: the CPU-port baselines (`cpu_baseline`, --cpu-sample-s), the
+user-visible `hs.Simulation(...).run()` at the same size (--api-run) and, with `--workload grid` on one GPU, the other two
+BASELINE workloads for the same --steps / --warmup -- the 65 536-station ring (configs[2]) and the consistent-hash load balancer
+(configs[4]) -- and the 8-GPU strong shard of the grid (8 192 LPs), printed INSIDE the one JSON line as `workloads.{ring,lb}`
+(each with its own value, ms_per_step, roofline and cpu_baseline) and `strong_shard`; `--full --extras 0` leaves those out.
+
+`--dump-outputs DIR`: after the timed steps, what the last step computed -- the arrays a caller of the engine reads back (the
+summary, the per-LP / per-backend statistics, the Sink records; a fixed seeded sample of at most DUMP_RECORDS records) -- as
+DIR/<name>.npy in float64.  The inputs are a function of the arguments alone, so two builds can be compared output for output.
 
 `--fake-ranks R`: R ranks as R PROCESSES ON ONE GPU (all on device 0, torch.distributed over gloo, exchange tensors staged through
 host memory because RCCL refuses two ranks on one device).  Not a performance figure -- the ranks share one device -- but it runs
@@ -132,6 +139,45 @@ def reference_python():
     return d
 
 
+DUMP_RECORDS = 1 << 20      # --dump-outputs: Sink records written (a fixed seeded sample when there are more)
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (counts and nanosecond times are exact below 2**53)."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), np.asarray(a, np.float64))
+
+
+def summary_outputs(s):
+    return {"summary": [s.events_processed, s.events_cancelled, s.final_time_ns, s.requests_completed, s.sink_records],
+            "events_by_kind": s.events_by_kind}
+
+
+def record_sample(t, cr):
+    """Sink records (completion ns, created_at ns) in record order: all of them, or a fixed seeded sample of DUMP_RECORDS."""
+    import numpy as np
+
+    if len(t) > DUMP_RECORDS:
+        idx = np.sort(np.random.default_rng(0).integers(0, len(t), DUMP_RECORDS))
+        t, cr = t[idx], cr[idx]
+    return {"sink_t_ns": t, "sink_created_ns": cr}
+
+
+def station_outputs(eng, network=False):
+    """What a caller of a StationEngine reads back after a run: the summary, every LP's statistics, the Sink records."""
+    out = summary_outputs(eng.summary())
+    out.update({f"lp_{k}": v for k, v in eng.lp_stats().items()})
+    if network:
+        out.update({f"net_{k}": v for k, v in eng.net_stats().items()})
+    counts, t, cr = eng.read_sinks()
+    out["sink_counts"] = counts
+    out.update(record_sample(t, cr))
+    return out
+
+
 def api_run(args, device):
     """Wall time of the user-visible call: build the 3 x n_lp reference-API objects, `hs.Simulation(...).run()` (lowering, the
     engine run, the read-back of every statistic and Sink record into the Python objects)."""
@@ -240,8 +286,13 @@ def parse():
     ap.add_argument("--rate", type=float, default=8.0)
     ap.add_argument("--mean", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--cpu-sample-s", type=float, default=20.0,
-                    help="simulated seconds of the same 65 536-LP workload timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU-port baselines, the API run and (grid, "
+                         "1 GPU) the ring, the load balancer, the strong shard and the graph replicas (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-sample-s", type=float, default=None,
+                    help="--full: simulated seconds of the same 65 536-LP workload timed on the CPU oracle (default 20; 0 = skip)")
     ap.add_argument("--workload", choices=("grid", "ring", "lb"), default="grid",
                     help="grid = the headline metric (independent M/M/1 chains, weak scaling); ring = BASELINE configs[2]/[3]: "
                          "ONE 65 536-station ring network, sharded over the GPUs (strong scaling, RCCL exchange + GVT); "
@@ -252,8 +303,9 @@ def parse():
                          "GPUs, SURVEY 8(d) 2b: the default with --gpus > 1; each GPU then runs the K-lanes-per-LP kernel, "
                          "csrc/hs_kernels_wide.hpp); weak = every GPU its own n_lp chains.  With --gpus > 1 the other one is "
                          "timed as well and printed as `other_scaling`.")
-    ap.add_argument("--api-run", type=int, default=1,
-                    help="grid, 1 GPU: also time the user-visible hs.Simulation(...).run() at this size (config.api_run_s)")
+    ap.add_argument("--api-run", type=int, default=None,
+                    help="--full, grid, 1 GPU: also time the user-visible hs.Simulation(...).run() at this size (config.api_run_s; "
+                         "default 1)")
     ap.add_argument("--lb-backends", type=int, default=32768)
     ap.add_argument("--lb-sources", type=int, default=32768)
     ap.add_argument("--lb-rate", type=float, default=6.0, help="lb: Poisson rate per source (mean backend load = rate * S / B)")
@@ -265,15 +317,20 @@ def parse():
                     help="ring, N > 1: exchanges between host synchronisations (0 = 4 rounds / 256 windows)")
     ap.add_argument("--fake-ranks", type=int, default=0,
                     help="R > 1: run R ranks as R processes on ONE GPU over gloo (see the module docstring); implies --gpus 1")
-    ap.add_argument("--extras", type=int, default=1,
-                    help="grid, 1 GPU: also time the ring, the load balancer and the 8 192-LP strong shard and print them inside the "
-                         "line (workloads / strong_shard)")
+    ap.add_argument("--extras", type=int, default=None,
+                    help="--full, grid, 1 GPU: also time the ring, the load balancer and the 8 192-LP strong shard and print them "
+                         "inside the line (workloads / strong_shard; default 1)")
     ap.add_argument("--ring-exchange", choices=("live", "device", "collective"), default="live",
                     help="--workload ring on several ranks: how the shards exchange (live: one launch per rank and run; device / collective: "
                          "asynchronous rounds)")
     ap.add_argument("--ring-windows", action="store_true",
                     help="ring, N > 1: the windowed protocol (one exchange per 1 ms window) instead of asynchronous rounds")
-    return ap.parse_args()
+    args = ap.parse_args()
+    # what only --full measures is off in a plain run unless asked for by name
+    for name, full_default in (("cpu_sample_s", 20.0), ("api_run", 1), ("extras", 1)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    return args
 
 
 def ring_description(args):
@@ -324,8 +381,9 @@ class Ctx:
         return float(t.item())
 
 
-def ring_main(args, ctx):
-    """One step = one complete run of the ring network (bootstrap + every window + the overshoot).  Returns the line (rank 0)."""
+def ring_main(args, ctx, dump=False):
+    """One step = one complete run of the ring network (bootstrap + every window + the overshoot).  Returns the line (rank 0).
+    `dump`: write the last step's outputs to --dump-outputs."""
     import numpy as np
     import torch
 
@@ -353,6 +411,8 @@ def ring_main(args, ctx):
         s = eng.summary()
         events, requests, windows, window_ns = s.events_processed, s.requests_completed, s.launches, s.window_ns
         info["device_ms_per_step"] = float(np.mean(kernel_ms))
+        if dump:
+            write_outputs(args.dump_outputs, station_outputs(eng, network=True))
         eng.close()
     else:
         rounds = not args.ring_windows
@@ -374,6 +434,8 @@ def ring_main(args, ctx):
         barrier()
         elapsed = time.perf_counter() - t0
         events, requests, windows, window_ns = s.events_processed, s.requests_completed, s.windows, s.window_ns
+        if dump and rank == 0:
+            write_outputs(args.dump_outputs, {"summary": [events, requests]})
         sn.close()
     elapsed = ctx.reduce(elapsed, "MAX")
     out = None
@@ -447,9 +509,10 @@ def lb_traffic():
     return d.get("hbm_bytes_per_launch") if d and d.get("current") else None
 
 
-def lb_main(args, ctx):
+def lb_main(args, ctx, dump=False):
     """BASELINE configs[4].  One step = one complete run of the load-balancer topology: every Source's ticks, the
-    (backend, time) sort, every backend's queue protocol, the shared Sink's merge, the overshoot election.  Returns the line."""
+    (backend, time) sort, every backend's queue protocol, the shared Sink's merge, the overshoot election.  Returns the line.
+    `dump`: write the last step's outputs to --dump-outputs."""
     import numpy as np
 
     from happy_simulator_amd import _native as N
@@ -477,6 +540,12 @@ def lb_main(args, ctx):
     elapsed = time.perf_counter() - t0
     s = eng.summary()
     st = eng.stats()
+    if dump and rank == 0:
+        got = summary_outputs(s)
+        got.update({f"lb_{k}": v for k, v in st.items()})
+        got["latency_stats"] = list(eng.latency_stats().values())
+        got.update(record_sample(*eng.read_sink(0)))
+        write_outputs(args.dump_outputs, got)
     elapsed = ctx.reduce(elapsed, "MAX")
     total_events = ctx.reduce(s.events_processed, "SUM")
     out = None
@@ -608,8 +677,9 @@ def cpu_baseline_ring(args):
     }
 
 
-def grid_main(args, ctx, headline=True):
-    """The headline workload.  One step = hs_station_reset + hs_station_run on this rank's LPs.  Returns the line (rank 0)."""
+def grid_main(args, ctx, headline=True, dump=False):
+    """The headline workload.  One step = hs_station_reset + hs_station_run on this rank's LPs.  Returns the line (rank 0).
+    `dump`: write the last step's outputs to --dump-outputs."""
     import numpy as np
 
     from happy_simulator_amd import _native as N
@@ -647,6 +717,8 @@ def grid_main(args, ctx, headline=True):
     eng, elapsed, total_events_per_step, kernel_ms, dev_total_ms, s, n_mine = timed(scaling)
     events_per_step = s.events_processed
     requests_per_step = s.requests_completed
+    if dump and rank == 0:
+        write_outputs(args.dump_outputs, station_outputs(eng))
     eng.close()
     if rank != 0:
         return None
@@ -781,12 +853,13 @@ def main():
     assert world == (args.fake_ranks if fake else args.gpus), f"--gpus {args.gpus} / --fake-ranks {args.fake_ranks} but WORLD_SIZE={world}"
     ctx = Ctx(rank, local_rank, world, dist, fake)
 
+    dump = args.dump_outputs is not None
     if args.workload == "lb":
-        out = lb_main(args, ctx)
+        out = lb_main(args, ctx, dump=dump)
     elif args.workload == "ring":
-        out = ring_main(args, ctx)
+        out = ring_main(args, ctx, dump=dump)
     else:
-        out = grid_main(args, ctx)
+        out = grid_main(args, ctx, dump=dump)
         if world == 1 and args.extras:
             # the other BASELINE workloads and the 8-GPU strong shard on the same driver-timed line (same --steps / --warmup;
             # shorter CPU-port samples so that the whole command stays well under a minute)

@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "live_reference: needs /root/reference (build container only)")
+    config.addinivalue_line("markers", "live_reference: against the upstream reference's recorded results (tests/golden/live_reference/)")
 
 
 def _has_gpu() -> bool:

@@ -1,5 +1,5 @@
 """GPU: the driver-facing contract of bench.py -- one JSON line on stdout with the metric, the whole-job value, the
-roofline object and the CPU baseline -- on small instances of the three workloads."""
+roofline object and (--full) the CPU baseline -- on small instances of the three workloads; the plain line and --dump-outputs."""
 import json
 import os
 import subprocess
@@ -29,7 +29,7 @@ def _run(*args):
     ("--workload", "lb", "--lb-sources", "512", "--lb-backends", "512", "--end-s", "10", "--cpu-sample-s", "2"),
 ], ids=["grid", "ring", "lb"])
 def test_bench_prints_one_contract_line(args):
-    d = _run("--steps", "3", "--warmup", "1", *args)
+    d = _run("--full", "--steps", "3", "--warmup", "1", *args)
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
@@ -71,7 +71,7 @@ def test_bench_strong_scaling_and_self_launch_flags():
 def test_default_line_carries_ring_lb_and_the_strong_shard():
     """The default invocation (grid, one GPU) times the ring, the load balancer and the 8-GPU strong shard with the same
     --steps / --warmup and prints them inside the ONE line -- each workload with its own roofline and CPU-port baseline."""
-    d = _run("--steps", "3", "--warmup", "1", "--n-lp", "4096", "--end-s", "10", "--cpu-sample-s", "2", "--lb-sources", "512",
+    d = _run("--full", "--steps", "3", "--warmup", "1", "--n-lp", "4096", "--end-s", "10", "--cpu-sample-s", "2", "--lb-sources", "512",
              "--lb-backends", "512", "--api-run", "0")
     for name, metric in (("ring", "ring network"), ("lb", "load balancer")):
         w = d["workloads"][name]
@@ -115,3 +115,31 @@ def test_fake_ranks_run_the_multi_rank_bench_paths_on_one_gpu():
                  "--fake-ranks", "2", "--ring-exchange", "device")
     assert "gloo" in ring3["config"]["parallelism"] and "peers' buffers" in ring3["config"]["parallelism"]
     assert ring3["config"]["events_per_step"] == ring1["config"]["events_per_step"] and ring3["config"]["launches_per_step"] >= 1
+
+
+@pytest.mark.parametrize("args", [
+    ("--n-lp", "4096", "--end-s", "20"),
+    ("--workload", "ring", "--n-lp", "2048", "--end-s", "5"),
+    ("--workload", "lb", "--lb-sources", "512", "--lb-backends", "512", "--end-s", "10"),
+], ids=["grid", "ring", "lb"])
+def test_plain_line_times_only_the_steps_and_dumps_the_last_steps_outputs(args, tmp_path):
+    """A plain run measures only its headline (no CPU baseline, API run or other workloads: those are --full's) and
+    --dump-outputs writes the last step's outputs as float64 .npy files -- the same ones for the same arguments."""
+    import numpy as np
+
+    d = _run("--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / "a"), *args)
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 1e6
+    for k in ("metric", "unit", "higher_is_better", "dtype", "roofline"):
+        assert k in d, k
+    assert "cpu_baseline" not in d and "workloads" not in d and "strong_shard" not in d and "api_run_s" not in d["config"]
+    _run("--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / "b"), *args)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert "summary.npy" in names and any(n.startswith("sink_t_ns") for n in names) and names == sorted(os.listdir(tmp_path / "b"))
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64, n
+        np.testing.assert_array_equal(a, b, err_msg=n)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "summary.npy")[0] == (d["config"].get("events_per_step_per_gpu") or d["config"]["events_per_step"])

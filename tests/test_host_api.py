@@ -476,44 +476,44 @@ def test_parallel_summary_formulas_and_layout():
     assert "Windows" not in str(quiet) and quiet.speedup == 2.0 and quiet.parallelism_efficiency == 1.0
 
 
-@pytest.mark.live_reference
-def test_parallel_summary_mirror_equals_the_live_reference_class():
-    """Same constructor keywords, `to_dict()` and `__str__` as happysimulator/parallel/summary.py, field for field."""
-    import os
-    import sys
-
-    if not os.path.isdir("/root/reference/happysimulator"):
-        pytest.skip("needs /root/reference (build container only)")
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import refshim
-
-    refshim.install()
-    from happysimulator.instrumentation.summary import SimulationSummary as RefSS
-    from happysimulator.parallel.summary import ParallelSimulationSummary as Ref
-
-    from happy_simulator_amd.parallel import ParallelSimulationSummary as Mine
-    from happy_simulator_amd.summary import SimulationSummary as MySS
-
+def _summaries(Par, SS, ES, QS, par_defaults):
+    """to_dict() and str() of the same ParallelSimulationSummary / SimulationSummary constructions, built from the given classes
+    (the mirror's or the reference's); `par_defaults`: a ParallelSimulationSummary built with the defaults."""
     kw = dict(duration_s=12.5, total_events_processed=1234, events_per_second=98.72, wall_clock_seconds=0.25,
               partition_wall_times={"p0": 0.1, "p1": 0.12}, speedup=0.88, parallelism_efficiency=0.44, total_windows=125,
               total_cross_partition_events=77, window_size_s=0.1, barrier_overhead_seconds=0.01, coordination_efficiency=0.96)
-    ref = Ref(partitions={"p0": RefSS(12.5, 600, 0, 48.0, 0.1), "p1": RefSS(12.4, 634, 0, 51.1, 0.12)}, **kw)
-    mine = Mine(partitions={"p0": MySS(12.5, 600, 0, 48.0, 0.1), "p1": MySS(12.4, 634, 0, 51.1, 0.12)}, **kw)
-    assert mine.to_dict() == ref.to_dict()
-    assert str(mine) == str(ref)
-    assert str(Mine(duration_s=1.0, total_events_processed=3)) == str(Ref(1.0, 3, 0.0, 0.0))       # defaults, no windows
+    par = Par(partitions={"p0": SS(12.5, 600, 0, 48.0, 0.1), "p1": SS(12.4, 634, 0, 51.1, 0.12)}, **kw)
     # ... and the per-run summary with its entity / queue lines (instrumentation/summary.py:14-87)
-    from happysimulator.instrumentation.summary import EntitySummary as RefES, QueueStats as RefQS
+    one = SS(duration_s=60.000000001, total_events_processed=4321, events_cancelled=2, events_per_second=72.016,
+             wall_clock_seconds=0.0123, entities={"srv": ES("srv", "Server", 0, QS(0, 480, 3)), "Sink": ES("Sink", "Sink", 477)})
+    return {"parallel": (par.to_dict(), str(par)), "parallel_defaults": str(par_defaults), "run": (one.to_dict(), str(one)),
+            "run_keys": list(one.to_dict()), "run_short": (str(SS(1.5, 10)), SS(1.5, 10).to_dict())}
 
-    from happy_simulator_amd.summary import EntitySummary as MyES, QueueStats as MyQS
 
-    def build(SS, ES, QS):
-        return SS(duration_s=60.000000001, total_events_processed=4321, events_cancelled=2, events_per_second=72.016,
-                  wall_clock_seconds=0.0123, entities={"srv": ES("srv", "Server", 0, QS(0, 480, 3)), "Sink": ES("Sink", "Sink", 477)})
-    a, b = build(MySS, MyES, MyQS), build(RefSS, RefES, RefQS)
-    assert a.to_dict() == b.to_dict() and list(a.to_dict()) == list(b.to_dict())
-    assert str(a) == str(b)
-    assert str(MySS(1.5, 10)) == str(RefSS(1.5, 10)) and MySS(1.5, 10).to_dict() == RefSS(1.5, 10).to_dict()
+@pytest.mark.live_reference
+def test_parallel_summary_mirror_equals_the_live_reference_class():
+    """Same constructor keywords, `to_dict()` and `__str__` as happysimulator/parallel/summary.py, field for field (the reference's
+    side as recorded from the live classes: tests/reference_runs.py)."""
+    from reference_runs import REF
+
+    from happy_simulator_amd.parallel import ParallelSimulationSummary as Mine
+    from happy_simulator_amd.summary import EntitySummary as MyES, QueueStats as MyQS, SimulationSummary as MySS
+
+    def reference():
+        from happysimulator.instrumentation.summary import EntitySummary, QueueStats, SimulationSummary
+        from happysimulator.parallel.summary import ParallelSimulationSummary
+
+        return _summaries(ParallelSimulationSummary, SimulationSummary, EntitySummary, QueueStats,
+                          ParallelSimulationSummary(1.0, 3, 0.0, 0.0))
+
+    ref = REF.value("summary_classes", reference)
+    mine = _summaries(Mine, MySS, MyES, MyQS, Mine(duration_s=1.0, total_events_processed=3))
+    assert mine["parallel"][0] == ref["parallel"][0]
+    assert mine["parallel"][1] == ref["parallel"][1]
+    assert mine["parallel_defaults"] == ref["parallel_defaults"]       # defaults, no windows
+    assert mine["run"][0] == ref["run"][0] and mine["run_keys"] == ref["run_keys"]
+    assert mine["run"][1] == ref["run"][1]
+    assert mine["run_short"] == ref["run_short"]
 
 
 def test_scheduled_requests_carry_their_construction_rank():

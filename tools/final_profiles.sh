@@ -29,13 +29,16 @@ python profiles/derive_valu_floor.py $R grid "hs_station_run<1, false, true, tru
 python profiles/derive_valu_floor.py $R ring "hs_net_async<1, false, true>" 1 profiles/${R}_valu_classes_ring.txt profiles/${R}_valu_rates.json >> gpurun_out/final/derive.log 2>&1
 python profiles/derive_valu_floor.py $R wave8192 "hs_station_wave<16, true>" 8 profiles/${R}_valu_classes_wave_8192lp.txt profiles/${R}_valu_rates.json >> gpurun_out/final/derive.log 2>&1
 cp profiles/${R}_valu_* gpurun_out/final/ 2>/dev/null
-# the driver's own command (default flags: grid + ring + LB + strong shard in one line), kernel trace only
-(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof_${R}default -o ${R}default -- python $GRAFT_REPO_ROOT/bench.py > $GRAFT_REPO_ROOT/gpurun_out/prof_${R}default.log 2>&1)
-f=$(ls gpurun_out/prof_${R}default/*_results.db 2>/dev/null | head -1)
+# the full line (bench.py --full: grid + ring + LB + strong shard in one line), kernel trace only; raw output under $RAW
+HERE=$(pwd)
+RAW=${RAW:-$HERE/profiles/raw}
+mkdir -p $RAW
+(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $RAW/prof_${R}default -o ${R}default -- python $HERE/bench.py --full > $RAW/prof_${R}default.log 2>&1)
+f=$(ls $RAW/prof_${R}default/*_results.db 2>/dev/null | head -1)
 [ -n "$f" ] && python profiles/summarize_rocprof.py $f > profiles/${R}default_trace.txt 2>&1
-grep -h '"metric"' gpurun_out/prof_${R}default.log | tail -1 > profiles/${R}default_bench_line_under_rocprof.json
+grep -h '"metric"' $RAW/prof_${R}default.log | tail -1 > profiles/${R}default_bench_line_under_rocprof.json
 cp profiles/${R}default_trace.txt profiles/${R}default_bench_line_under_rocprof.json gpurun_out/final/ 2>/dev/null
-rm -rf gpurun_out/prof_${R}default
+rm -rf $RAW/prof_${R}default
 echo "grid profile done $(( $(date +%s) - T0 )) s"
 STEPS=3 BENCH_ARGS="--workload ring" bash profiles/collect.sh ${R}ring > gpurun_out/collect_${R}ring.log 2>&1
 for k in trace fetch write sq; do cp gpurun_out/prof_${R}ring/${R}ring_$k.txt profiles/; done
@@ -50,7 +53,7 @@ echo "lb profile done $(( $(date +%s) - T0 )) s"
 cp profiles/${R}*_roofline_*.json gpurun_out/final/ 2>/dev/null
 for k in trace fetch write sq; do cp profiles/${R}_$k.txt profiles/${R}ring_$k.txt profiles/${R}lb_$k.txt gpurun_out/final/ 2>/dev/null; done
 cp profiles/${R}*_bench_line_under_rocprof.json gpurun_out/final/ 2>/dev/null
-python bench.py --steps 20 --warmup 5 2> gpurun_out/final/bench_default.err | tail -1 > gpurun_out/final/${R}_bench_default.json
+python bench.py --full --steps 20 --warmup 5 2> $RAW/bench_default.err | tail -1 > $RAW/${R}_bench_default.json
 python bench.py --workload ring --cpu-sample-s 6 2> gpurun_out/final/bench_ring.err | tail -1 > gpurun_out/final/${R}_bench_ring.json
 python bench.py --workload lb --cpu-sample-s 6 2> gpurun_out/final/bench_lb.err | tail -1 > gpurun_out/final/${R}_bench_lb.json
 python bench.py --n-lp 8192 --cpu-sample-s 0 --extras 0 --api-run 0 2> gpurun_out/final/bench_8192.err | tail -1 > gpurun_out/final/${R}_bench_8192.json
@@ -65,7 +68,7 @@ python tools/ring_fullsize.py > gpurun_out/final/${R}_ring_fullsize.log 2>&1
 python tools/ring_fullsize.py --n 131072 >> gpurun_out/final/${R}_ring_fullsize.log 2>&1
 python tools/api_profile.py 2>&1 | grep "^pass" > gpurun_out/final/${R}_api_profile.log
 echo "bench done $(( $(date +%s) - T0 )) s"
-cut -c1-400 gpurun_out/final/${R}_bench_default.json
+cut -c1-400 $RAW/${R}_bench_default.json
 tail -3 gpurun_out/final/derive.log
 # round 6: windows over the ring -- continued from the last state against repeated from the start against one run
 python - <<'PY' > profiles/${R}_ring_windows.json 2> gpurun_out/final/ring_windows.err
