@@ -87,7 +87,8 @@ struct GRequest {                              // 32 bytes: the payload Event's 
     double service_s;                          // service_time_s of the generator frame (server/server.py:246-247)
     int64_t client;                            // context["metadata"]["client_id"] (-1: none)
     int32_t next;                              // FIFO / free list
-    int32_t hook;                              // LoadBalancer whose `_lb_response` hook rides on the Event (-1: none)
+    int32_t hook : 31;                         // LoadBalancer whose `_lb_response` hook rides on the Event (-1: none)
+    uint32_t pre : 1;                          // `idx` came from the process-wide counter (GEvent::pad), set where the payload is queued
 };
 
 enum : int { kRunning = 0, kDone = 1, kGrowHeap = 2, kGrowReq = 4, kGrowRec = 8, kBadKind = 16, kGrowTicks = 32, kUndecided = 64 };
@@ -310,7 +311,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             else { status |= kGrowReq; break; }
             const int node = c.sched_node[V.sched_done];
             const int64_t t = c.sched_t[V.sched_done];
-            GRequest q; q.created = t; q.idx = V.global_counter; q.service_s = 0.0; q.client = -1; q.next = -1; q.hook = -1;
+            GRequest q; q.created = t; q.idx = V.global_counter; q.service_s = 0.0; q.client = -1; q.next = -1; q.hook = -1; q.pre = 1;
             c.reqs[r] = q;
             H.push(mk_pre(t, V.global_counter++, arrival_kind(c.P, node), node, r));
             V.sched_done++;
@@ -368,7 +369,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     r = req_free;
                     if (r >= 0) req_free = c.reqs[r].next; else r = req_len++;
                     idx_p = G++;
-                    GRequest q; q.created = t; q.idx = idx_p; q.service_s = 0.0; q.client = -1; q.next = -1; q.hook = -1;
+                    GRequest q; q.created = t; q.idx = idx_p; q.service_s = 0.0; q.client = -1; q.next = -1; q.hook = -1; q.pre = 0;
                     if (p.conc > 0) {                                               // chash_example.py:83: one client id per Request
                         const double u = uniform_at(c.seed, stream_id(p.stream_base, kStreamKey), s.svc_draws);
                         s.svc_draws += 1;
@@ -391,6 +392,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     c.reqs[e.req].next = req_free; req_free = e.req;
                 } else {
                     c.reqs[e.req].idx = e.idx;              // the queued payload IS this Event object
+                    c.reqs[e.req].pre = e.pad & 1u;         // ... and its index keeps its origin (WORK re-uses it)
                     c.reqs[e.req].next = -1;
                     if (s.qtail >= 0) c.reqs[s.qtail].next = e.req; else s.qhead = e.req;
                     s.qtail = e.req;
@@ -414,9 +416,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 s.qlen -= 1;
                 H.push(mk(t, G++, HS_EV_DELIVER, n, r));
             } break;
-            case HS_EV_DELIVER:                                                     // queue_driver.py:66-90: same payload, ORIGINAL index
-                H.push(mk(t, c.reqs[e.req].idx, HS_EV_WORK, n, e.req));
-                break;
+            case HS_EV_DELIVER: {                                                   // queue_driver.py:66-90: same payload, ORIGINAL index
+                const GRequest &q = c.reqs[e.req];                                  // (a schedule()d Request's: a pre-run index)
+                H.push(q.pre ? mk_pre(t, q.idx, HS_EV_WORK, n, e.req) : mk(t, q.idx, HS_EV_WORK, n, e.req));
+            } break;
             case HS_EV_WORK: {
                 // Server.handle_queued_event up to its yield (server/server.py:202-250) via Event._start_process
                 // (core/event.py:313-325): one continuation is built and invoked at once, the pushed one is the second
@@ -1110,7 +1113,6 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
     HSG_HIP(g0, hipSetDevice(g0->cfg.device));
     { const int rc = ensure_stream(g0); if (rc) return rc; }
     for (int i = 0; i < n; ++i) {
-        gs[i]->ctl.part = part;
         const int rc = prepare_run(gs[i], end_ns);
         if (rc) { if (gs[i] != g0) gfail(g0, rc, "graph %d: %s", i, gs[i]->error.c_str()); return rc; }
     }
@@ -1125,7 +1127,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
     hipError_t he = hipEventRecord(g0->ev_a, g0->stream);
     while (he == hipSuccess && rc == HS_OK && !pending.empty()) {
         h_ctl.clear();
-        for (int i : pending) h_ctl.push_back(gs[i]->ctl);
+        for (int i : pending) {
+            h_ctl.push_back(gs[i]->ctl);
+            h_ctl.back().part = part;              // (the handles themselves never keep part semantics: no early return can leave it set)
+        }
         if ((he = hipMemcpy(d_ctl, h_ctl.data(), h_ctl.size() * sizeof(GCtl), hipMemcpyHostToDevice)) != hipSuccess) break;
         hipLaunchKernelGGL(hs_graph_run_batch, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         if ((he = hipGetLastError()) != hipSuccess) break;
@@ -1152,7 +1157,6 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
             for (int i = 0; i < n; ++i) gs[i]->last_run_ms = ms;          // (the batch's wall time: the heaps ran side by side)
     }
     (void)hipFree(d_ctl);
-    for (int i = 0; i < n; ++i) gs[i]->ctl.part = 0;
     if (rc) return rc;
     if (he != hipSuccess) return gfail(g0, HS_E_HIP, "batch launch: %s", hipGetErrorString(he));
     return HS_OK;
@@ -1197,11 +1201,10 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         bool done = false;
         const int rc = after_launch(g, &done);       // (enlarges what the one event needed)
         if (rc) { if (g != g0) gfail(g0, rc, "%s", g->error.c_str()); return rc; }
+        if (g->undecided) return 1;                  // (the popped event was dropped: the handle's state is no answer any more)
         GVars now;
         HSG_HIP(g0, hipMemcpy(&now, g->ctl.V, sizeof now, hipMemcpyDeviceToHost));
-        if (now.processed > before.processed || now.heap_len <= 0) {
-            return g->undecided ? 1 : HS_OK;      // (a neighbour of the other origin on the event's own nanosecond: the device's check)
-        }
+        if (now.processed > before.processed || now.heap_len <= 0) return HS_OK;
     }
     return gfail(g0, HS_E_OVERFLOW, "the event beyond the end could not be processed");
 }

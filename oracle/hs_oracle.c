@@ -21,6 +21,7 @@ typedef struct {
     int32_t node;   /* target node                                            */
     int32_t req;    /* request slot (payload / context), -1 if none           */
     int32_t aux;    /* per-kind scratch (service slot ...)                    */
+    int32_t pre;    /* 1: the index came from the process-wide counter (hso_params.part_check) */
 #ifdef HSO_LINEAGE  /* analysis build only (tools/election_rules.py): when was it created, and its creator, and that one's */
     int64_t crt, crt2, crt3;
     /* ... and its place in the FIFO that the heap is among events of one nanosecond: how many steps after the root of the group
@@ -41,6 +42,7 @@ typedef struct {
     int32_t next_free;
     int64_t client_id;  /* context["metadata"]["client_id"] (as an int; the key string is its decimal form), -1 = none */
     int32_t lb_hook;    /* LB node whose `on_complete` hook rides on this Event (load_balancer.py:413-431), -1 = none */
+    int32_t pre;        /* origin of `idx` (hso_event::pre), set where the payload is queued */
 } hso_request;
 
 /* ConsistentHash ring point (strategies.py:336-433): md5 digest as a big-endian 128-bit integer + backend node */
@@ -93,6 +95,8 @@ struct hso_sim {
     hsr_mt19937 mt_coord;                 /* the coordinator's random.Random(seed) (hso_graph.ploss) */
     /* trace */
     int64_t *tr_t; int32_t *tr_kind; int32_t *tr_node; int64_t *tr_idx; int64_t tr_len;
+    /* part_check: pops so far, the first flagged one (0: none) and what hso_part_check reports of it */
+    int64_t pops, pc_pop, pc_out[5];
 #ifdef HSO_LINEAGE
     int cur_valid; int64_t cur_crt, cur_crt2;      /* the event being processed (creator of what is pushed now) */
     int64_t cur_rsrc;                              /* ... and the tick its children descend from (hso_event::rsrc) */
@@ -402,13 +406,13 @@ static void on_source(hso_sim *s, const hso_event *e) {
         s->reqs[r].idx = payload.idx;
         payload.node = s->g.target[n];
         payload.kind = arrival_kind_for(s, payload.node);
-        payload.req = r; payload.aux = 0;
+        payload.req = r; payload.aux = 0; payload.pre = 0;
     }
     nd->generated++;                                                /* :159 */
     hso_event tick;
     tick.time = next_arrival(s, n);                                 /* :170 */
     tick.idx = next_index(s);                                       /* SourceEvent constructed second (:171) */
-    tick.kind = HSO_EV_SOURCE; tick.node = n; tick.req = -1; tick.aux = 0;
+    tick.kind = HSO_EV_SOURCE; tick.node = n; tick.req = -1; tick.aux = 0; tick.pre = 0;
     if (has_payload) heap_push(s, payload);                         /* return [*payload_events, next_tick] (:174) */
     heap_push(s, tick);
 }
@@ -418,12 +422,12 @@ static void on_source(hso_sim *s, const hso_event *e) {
 static void on_probe_tick(hso_sim *s, const hso_event *e) {
     int32_t n = e->node;
     hso_node *nd = &s->nodes[n];
-    hso_event pe = {e->time, next_index(s), HSO_EV_PROBE, n, -1, 0};
+    hso_event pe = {e->time, next_index(s), HSO_EV_PROBE, n, -1, 0, 0};
     nd->generated++;
     hso_event tick;
     tick.time = next_arrival(s, n);
     tick.idx = next_index(s);
-    tick.kind = HSO_EV_PROBE_TICK; tick.node = n; tick.req = -1; tick.aux = 0;
+    tick.kind = HSO_EV_PROBE_TICK; tick.node = n; tick.req = -1; tick.aux = 0; tick.pre = 0;
     heap_push(s, pe);
     heap_push(s, tick);
 }
@@ -465,17 +469,18 @@ static void on_enqueue(hso_sim *s, const hso_event *e) {
         req_release(s, e->req);
     } else {
         s->reqs[e->req].idx = e->idx;   /* the queued payload IS this Event object (a forwarded request is a new Event) */
+        s->reqs[e->req].pre = e->pre;   /* ... and its index keeps its origin */
         fifo_push(&nd->fifo, e->req);
         nd->accepted++;                                             /* queue.py:138 */
         if (was_empty) {                                            /* queue.py:144-146 */
-            hso_event nf = {e->time, next_index(s), HSO_EV_NOTIFY, n, -1, 0};
+            hso_event nf = {e->time, next_index(s), HSO_EV_NOTIFY, n, -1, 0, 0};
             heap_push(s, nf);
         }
     }
     /* Event.invoke (core/event.py:277-283): the handler returned a plain list, so the completion hooks run NOW --
      * after the handler's own events were constructed -- and their events are appended: the LB's `_lb_response`. */
     if (hook >= 0) {
-        hso_event rs = {e->time, next_index(s), HSO_EV_LB_RESP, hook, -1, 0};
+        hso_event rs = {e->time, next_index(s), HSO_EV_LB_RESP, hook, -1, 0, 0};
         heap_push(s, rs);
     }
 }
@@ -484,7 +489,7 @@ static void on_enqueue(hso_sim *s, const hso_event *e) {
 static void on_notify(hso_sim *s, const hso_event *e) {
     int32_t n = e->node;
     if (!(s->nodes[n].active < s->g.concurrency[n])) return;        /* has_capacity, concurrency.py:122-131 */
-    hso_event pl = {e->time, next_index(s), HSO_EV_POLL, n, -1, 0};
+    hso_event pl = {e->time, next_index(s), HSO_EV_POLL, n, -1, 0, 0};
     heap_push(s, pl);
 }
 
@@ -494,7 +499,7 @@ static void on_poll(hso_sim *s, const hso_event *e) {
     hso_node *nd = &s->nodes[n];
     if (nd->fifo.len == 0) return;                                  /* :151-154 */
     int32_t r = fifo_pop(&nd->fifo);
-    hso_event dv = {e->time, next_index(s), HSO_EV_DELIVER, n, r, 0};
+    hso_event dv = {e->time, next_index(s), HSO_EV_DELIVER, n, r, 0, 0};
     heap_push(s, dv);
 }
 
@@ -502,7 +507,8 @@ static void on_poll(hso_sim *s, const hso_event *e) {
  * the SAME payload object is re-timed, re-targeted and re-pushed with its
  * original sort index; the schedule_poll completion hook is attached. */
 static void on_deliver(hso_sim *s, const hso_event *e) {
-    hso_event wk = {e->time, s->reqs[e->req].idx, HSO_EV_WORK, e->node, e->req, 0};
+    hso_event wk = {e->time, s->reqs[e->req].idx, HSO_EV_WORK, e->node, e->req, 0, 0};
+    wk.pre = s->p.part_check == 2 ? 0 : s->reqs[e->req].pre;       /* (2: the rule before the origin was carried) */
     heap_push(s, wk);
 }
 
@@ -523,7 +529,7 @@ static void on_work(hso_sim *s, const hso_event *e) {
     double service_s = sample_latency_s(s, n, HS_STREAM_SERVICE, &nd->svc_draws); /* :246-247 */
     s->reqs[e->req].service_s = service_s;
     /* `yield service_time_s` -> resume_time = self.time + delay (event.py:499) = ns + int(delay*1e9) (temporal.py:222) */
-    hso_event ct = {e->time + hsr_ns_from_seconds(service_s), next_index(s), HSO_EV_CONTINUATION, n, e->req, 0};
+    hso_event ct = {e->time + hsr_ns_from_seconds(service_s), next_index(s), HSO_EV_CONTINUATION, n, e->req, 0, 0};
     heap_push(s, ct);
 }
 
@@ -538,13 +544,13 @@ static void on_continuation(hso_sim *s, const hso_event *e) {
     nd->total_service_s += s->reqs[e->req].service_s;               /* :256-257 */
     int32_t dn = s->g.target[n];
     if (dn >= 0) {                                                  /* forward(event, downstream), :271-272 */
-        hso_event fw = {e->time, next_index(s), arrival_kind_for(s, dn), dn, e->req, 0};
+        hso_event fw = {e->time, next_index(s), arrival_kind_for(s, dn), dn, e->req, 0, 0};
         heap_push(s, fw);
     } else {
         req_release(s, e->req);
     }
     if (nd->active < s->g.concurrency[n]) {                         /* schedule_poll hook */
-        hso_event pl = {e->time, next_index(s), HSO_EV_POLL, n, -1, 0};
+        hso_event pl = {e->time, next_index(s), HSO_EV_POLL, n, -1, 0, 0};
         heap_push(s, pl);
     }
 }
@@ -564,7 +570,7 @@ static void on_sink(hso_sim *s, const hso_event *e) {
     s->reqs[e->req].lb_hook = -1;
     req_release(s, e->req);
     if (hook >= 0) {
-        hso_event rs = {e->time, next_index(s), HSO_EV_LB_RESP, hook, -1, 0};
+        hso_event rs = {e->time, next_index(s), HSO_EV_LB_RESP, hook, -1, 0, 0};
         heap_push(s, rs);
     }
 }
@@ -580,7 +586,7 @@ static void on_route(hso_sim *s, const hso_event *e) {
     double u = draw_uniform(s, n, HS_STREAM_ROUTE, &nd->route_draws);
     int32_t idx = (int32_t)(u * (double)cnt);
     int32_t tgt = s->g.rt_targets[s->g.rt_off[n] + idx];
-    hso_event ev = {e->time, next_index(s), arrival_kind_for(s, tgt), tgt, e->req, 0};
+    hso_event ev = {e->time, next_index(s), arrival_kind_for(s, tgt), tgt, e->req, 0, 0};
     heap_push(s, ev);
 }
 
@@ -617,7 +623,7 @@ static void on_link(hso_sim *s, const hso_event *e) {
         delay = delay + hsr_seconds_from_ns(hsr_ns_from_seconds(s->g.lat_mean[n])); /* jitter = ConstantLatency(lat_mean): no draw */
     }
     if (!(delay > 0.0)) delay = 0.0;                                /* max(0.0, delay) */
-    hso_event ct = {e->time + hsr_ns_from_seconds(delay), next_index(s), HSO_EV_LINK_CONT, n, e->req, 0};
+    hso_event ct = {e->time + hsr_ns_from_seconds(delay), next_index(s), HSO_EV_LINK_CONT, n, e->req, 0, 0};
     heap_push(s, ct);
 }
 
@@ -628,7 +634,7 @@ static void on_link_cont(hso_sim *s, const hso_event *e) {
     nd->packets_sent++;
     int32_t eg = s->g.target[n];
     if (eg < 0) { req_release(s, e->req); return; }
-    hso_event fw = {e->time, next_index(s), arrival_kind_for(s, eg), eg, e->req, 0};
+    hso_event fw = {e->time, next_index(s), arrival_kind_for(s, eg), eg, e->req, 0, 0};
     heap_push(s, fw);
 }
 
@@ -765,7 +771,7 @@ static void on_lb(hso_sim *s, const hso_event *e) {
     nd->lb_forwarded++;                                             /* :388 */
     /* a NEW Event for the backend, same context (created_at survives), + the response hook (:398-431) */
     s->reqs[e->req].lb_hook = n;
-    hso_event fw = {e->time, next_index(s), arrival_kind_for(s, be), be, e->req, 0};
+    hso_event fw = {e->time, next_index(s), arrival_kind_for(s, be), be, e->req, 0, 0};
     heap_push(s, fw);
 }
 /* LoadBalancer._handle_response, load_balancer.py:435-473: bookkeeping only */
@@ -847,7 +853,7 @@ hso_sim *hso_create(const hso_graph *g, const hso_params *p) {
         hso_event tick;
         tick.time = next_arrival(s, i);
         tick.idx = next_index(s);
-        tick.kind = HSO_EV_SOURCE; tick.node = i; tick.req = -1; tick.aux = 0;
+        tick.kind = HSO_EV_SOURCE; tick.node = i; tick.req = -1; tick.aux = 0; tick.pre = 1;
         heap_push(s, tick);
     }
     /* then the probes, in list order (core/simulation.py:156-160) */
@@ -858,7 +864,7 @@ hso_sim *hso_create(const hso_graph *g, const hso_params *p) {
         tick.time = next_arrival(s, i);
         if (tick.time == INT64_MAX) continue;                       /* "Rate is zero indefinitely. Source will not start." */
         tick.idx = next_index(s);
-        tick.kind = HSO_EV_PROBE_TICK; tick.node = i; tick.req = -1; tick.aux = 0;
+        tick.kind = HSO_EV_PROBE_TICK; tick.node = i; tick.req = -1; tick.aux = 0; tick.pre = 1;
         heap_push(s, tick);
     }
     /* run(): _active_sim_context switches Event construction to the per-heap
@@ -883,55 +889,90 @@ int hso_schedule(hso_sim *s, int32_t node, int64_t time_ns) {
     s->reqs[r].service_s = 0.0;
     s->reqs[r].client_id = -1;
     s->reqs[r].lb_hook = -1;
-    hso_event ev = {time_ns, s->global_counter++, k, node, r, 0};
+    hso_event ev = {time_ns, s->global_counter++, k, node, r, 0, 1};
     s->reqs[r].idx = ev.idx;
+    s->reqs[r].pre = 1;
     heap_push(s, ev);
     return 0;
 }
 
-/* Simulation._execute_until, core/simulation.py:449-505 (no cancellation on this path) */
-int hso_run_until(hso_sim *s, int64_t end_ns) {
-    while (s->heap_len > 0 && s->current_ns <= end_ns) {            /* :472 tests the PREVIOUS event's time */
-        hso_event e = heap_pop(s);
-        if (e.time < s->current_ns) continue;                       /* time travel drop, :480-489 */
-#ifdef HSO_LINEAGE
-        if (e.time > end_ns && s->dump == NULL) {
-            s->dump = (hso_event *)malloc((size_t)(s->heap_len + 1) * sizeof(hso_event));
-            s->dump[0] = e;
-            memcpy(s->dump + 1, s->heap, (size_t)s->heap_len * sizeof(hso_event));
-            s->dump_len = s->heap_len + 1;
-        }
-        s->cur_valid = 1; s->cur_crt = e.crt; s->cur_crt2 = e.crt2; s->cur_rsrc = e.rsrc;
-        if (e.crt < e.time) {          /* created earlier: the root of a chain of this nanosecond's group */
-            s->g_depth = 0; s->g_rcrt = e.crt; s->g_rcdepth = e.cdepth; s->g_r2crt = e.rcrt; s->g_r2cdepth = e.rcdepth;
-        } else {                       /* created in this very nanosecond: it carries its group's context */
-            s->g_depth = e.cdepth; s->g_rcrt = e.rcrt; s->g_rcdepth = e.rcdepth; s->g_r2crt = e.r2crt; s->g_r2cdepth = e.r2cdepth;
-        }
-#endif
-        s->current_ns = e.time;
-        s->processed++;
-        s->by_kind[e.kind]++;
-        trace(s, &e);
-        switch (e.kind) {
-            case HSO_EV_SOURCE: on_source(s, &e); break;
-            case HSO_EV_ENQUEUE: on_enqueue(s, &e); break;
-            case HSO_EV_NOTIFY: on_notify(s, &e); break;
-            case HSO_EV_POLL: on_poll(s, &e); break;
-            case HSO_EV_DELIVER: on_deliver(s, &e); break;
-            case HSO_EV_WORK: on_work(s, &e); break;
-            case HSO_EV_CONTINUATION: on_continuation(s, &e); break;
-            case HSO_EV_SINK: on_sink(s, &e); break;
-            case HSO_EV_LINK: on_link(s, &e); break;
-            case HSO_EV_LINK_CONT: on_link_cont(s, &e); break;
-            case HSO_EV_ROUTE: on_route(s, &e); break;
-            case HSO_EV_LB: on_lb(s, &e); break;
-            case HSO_EV_LB_RESP: on_lb_resp(s, &e); break;
-            case HSO_EV_PROBE_TICK: on_probe_tick(s, &e); break;
-            case HSO_EV_PROBE: on_probe_event(s, &e); break;
-            default: return -1;
+/* one pop of Simulation._execute_until's loop, core/simulation.py:472-505 */
+static int pop_and_process(hso_sim *s, int64_t end_ns) {
+    hso_event e = heap_pop(s);
+    s->pops++;
+    if (s->p.part_check && s->pc_pop == 0 && s->heap_len > 0) {
+        /* the device's check (hs_graph.hip, part runs): the popped event and the next pending one on one nanosecond, their indices
+         * from different counters -- their order depends on how many events the WHOLE Simulation had created */
+        const hso_event *nx = &s->heap[0];
+        if (nx->time == e.time && nx->pre != e.pre) {
+            s->pc_pop = s->pops;
+            s->pc_out[0] = e.time; s->pc_out[1] = e.kind; s->pc_out[2] = e.pre; s->pc_out[3] = nx->kind; s->pc_out[4] = nx->pre;
         }
     }
+    if (e.time < s->current_ns) return 0;                           /* time travel drop, :480-489 */
+#ifdef HSO_LINEAGE
+    if (e.time > end_ns && s->dump == NULL) {
+        s->dump = (hso_event *)malloc((size_t)(s->heap_len + 1) * sizeof(hso_event));
+        s->dump[0] = e;
+        memcpy(s->dump + 1, s->heap, (size_t)s->heap_len * sizeof(hso_event));
+        s->dump_len = s->heap_len + 1;
+    }
+    s->cur_valid = 1; s->cur_crt = e.crt; s->cur_crt2 = e.crt2; s->cur_rsrc = e.rsrc;
+    if (e.crt < e.time) {          /* created earlier: the root of a chain of this nanosecond's group */
+        s->g_depth = 0; s->g_rcrt = e.crt; s->g_rcdepth = e.cdepth; s->g_r2crt = e.rcrt; s->g_r2cdepth = e.rcdepth;
+    } else {                       /* created in this very nanosecond: it carries its group's context */
+        s->g_depth = e.cdepth; s->g_rcrt = e.rcrt; s->g_rcdepth = e.rcdepth; s->g_r2crt = e.r2crt; s->g_r2cdepth = e.r2cdepth;
+    }
+#else
+    (void)end_ns;
+#endif
+    s->current_ns = e.time;
+    s->processed++;
+    s->by_kind[e.kind]++;
+    trace(s, &e);
+    switch (e.kind) {
+        case HSO_EV_SOURCE: on_source(s, &e); break;
+        case HSO_EV_ENQUEUE: on_enqueue(s, &e); break;
+        case HSO_EV_NOTIFY: on_notify(s, &e); break;
+        case HSO_EV_POLL: on_poll(s, &e); break;
+        case HSO_EV_DELIVER: on_deliver(s, &e); break;
+        case HSO_EV_WORK: on_work(s, &e); break;
+        case HSO_EV_CONTINUATION: on_continuation(s, &e); break;
+        case HSO_EV_SINK: on_sink(s, &e); break;
+        case HSO_EV_LINK: on_link(s, &e); break;
+        case HSO_EV_LINK_CONT: on_link_cont(s, &e); break;
+        case HSO_EV_ROUTE: on_route(s, &e); break;
+        case HSO_EV_LB: on_lb(s, &e); break;
+        case HSO_EV_LB_RESP: on_lb_resp(s, &e); break;
+        case HSO_EV_PROBE_TICK: on_probe_tick(s, &e); break;
+        case HSO_EV_PROBE: on_probe_event(s, &e); break;
+        default: return -1;
+    }
     return 0;
+}
+
+/* Simulation._execute_until, core/simulation.py:449-505 (no cancellation on this path).  part_check: a part of a Simulation stops
+ * in front of the first event beyond the end instead (hs_graph.hip's part loop). */
+int hso_run_until(hso_sim *s, int64_t end_ns) {
+    while (s->heap_len > 0 && (s->p.part_check ? s->heap[0].time <= end_ns : s->current_ns <= end_ns)) {   /* :472 tests the PREVIOUS event's time */
+        if (pop_and_process(s, end_ns) != 0) return -1;
+    }
+    return 0;
+}
+
+int hso_step(hso_sim *s) {
+    if (s->heap_len == 0) return 1;
+    return pop_and_process(s, INT64_MAX);
+}
+
+int64_t hso_pending(const hso_sim *s, int64_t *next_ns) {
+    if (next_ns && s->heap_len > 0) *next_ns = s->heap[0].time;
+    return s->heap_len;
+}
+
+int64_t hso_part_check(const hso_sim *s, int64_t out[5]) {
+    if (out) memcpy(out, s->pc_out, sizeof s->pc_out);
+    return s->pc_pop;
 }
 
 #ifdef HSO_LINEAGE

@@ -79,6 +79,7 @@ class _Params(C.Structure):
         ("mt_seed_np", C.c_uint32),
         ("trace_cap", C.c_int64),
         ("coord_seed", C.c_uint32),
+        ("part_check", C.c_int32),
     ]
 
 
@@ -106,6 +107,12 @@ def lib():
         L.hso_schedule.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
         L.hso_run_until.restype = C.c_int
         L.hso_run_until.argtypes = [C.c_void_p, C.c_int64]
+        L.hso_step.restype = C.c_int
+        L.hso_step.argtypes = [C.c_void_p]
+        L.hso_pending.restype = C.c_int64
+        L.hso_pending.argtypes = [C.c_void_p, C.c_void_p]
+        L.hso_part_check.restype = C.c_int64
+        L.hso_part_check.argtypes = [C.c_void_p, C.c_void_p]
         L.hso_get_summary.argtypes = [C.c_void_p, C.POINTER(_Summary)]
         L.hso_get_node_stats.argtypes = [C.c_void_p] + [C.c_void_p] * 9
         L.hso_get_net_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -253,7 +260,7 @@ class Result:
 
 
 def _create(g: Graph, end_ns: int, start_ns: int, seed: int, rng_mode: int, mt_seed_py: int, mt_seed_np: int,
-            trace_cap: int, coord_seed: int = 42):
+            trace_cap: int, coord_seed: int = 42, part_check: int = 0):
     """hso_create for a Graph; returns the handle (the C side copies every array)."""
     L = lib()
     n = len(g)
@@ -285,20 +292,23 @@ def _create(g: Graph, end_ns: int, start_ns: int, seed: int, rng_mode: int, mt_s
         setattr(G, name, a.ctypes.data_as(ftype))
     G.names = names_blob
     G.name_off = name_off.ctypes.data_as(C.POINTER(C.c_int32))
-    P = _Params(start_ns, end_ns, seed, rng_mode, mt_seed_py, mt_seed_np, trace_cap, coord_seed)
+    P = _Params(start_ns, end_ns, seed, rng_mode, mt_seed_py, mt_seed_np, trace_cap, coord_seed, part_check)
     return L.hso_create(C.byref(G), C.byref(P))
 
 
 def run(g: Graph, end_ns: int, start_ns: int = 0, seed: int = 42, rng_mode: int = RNG_PHILOX,
         mt_seed_py: int = 42, mt_seed_np: int = 42, trace_cap: int = 0, windows: list | None = None,
-        lb_probe: int = 0, schedule: list | None = None, coord_seed: int = 42) -> Result:
+        lb_probe: int = 0, schedule: list | None = None, coord_seed: int = 42, part_check: int = 0, step: bool = False) -> Result:
     """Run the oracle once; returns a Result with summary, per-node stats, sink records, trace.
-    schedule: [(node, time_ns), ...] = Simulation.schedule(Event(time, "Request", target=node)) calls before run()."""
+    schedule: [(node, time_ns), ...] = Simulation.schedule(Event(time, "Request", target=node)) calls before run().
+    part_check (hso_params.part_check): run as one part of a Simulation -- stop in front of the first event beyond end_ns, take that one
+    too when `step`, and report the first pop that met a mixed-origin pair on one nanosecond as r.part_check = None | dict(pop, ns,
+    kinds=(popped, next), pre=(popped, next)).  r.next_ns: the earliest pending event's time after the run (None: nothing pending)."""
     L = lib()
     n = len(g)
     import time as _time
 
-    h = _create(g, end_ns, start_ns, seed, rng_mode, mt_seed_py, mt_seed_np, trace_cap, coord_seed)
+    h = _create(g, end_ns, start_ns, seed, rng_mode, mt_seed_py, mt_seed_np, trace_cap, coord_seed, part_check)
     try:
         for node, t_ns in (schedule or []):
             if L.hso_schedule(h, int(node), int(t_ns)) != 0:
@@ -307,6 +317,8 @@ def run(g: Graph, end_ns: int, start_ns: int = 0, seed: int = 42, rng_mode: int 
         for w_end in (windows or []):
             L.hso_run_until(h, int(w_end))
         rc = L.hso_run_until(h, int(end_ns))
+        if rc == 0 and step:
+            rc = min(L.hso_step(h), 0)
         run_seconds = _time.perf_counter() - t0
         if rc != 0:
             raise RuntimeError("oracle: unsupported event kind")
@@ -318,6 +330,14 @@ def run(g: Graph, end_ns: int, start_ns: int = 0, seed: int = 42, rng_mode: int 
         r.events_by_kind = np.array(list(S.events_by_kind), np.int64)
         r.final_time_ns = S.final_time_ns
         r.heap_peak = S.heap_peak
+        nx = C.c_int64(0)
+        r.next_ns = int(nx.value) if L.hso_pending(h, C.byref(nx)) > 0 else None
+        r.part_check = None
+        if part_check:
+            pc = np.zeros(5, np.int64)
+            pop = int(L.hso_part_check(h, pc.ctypes.data))
+            if pop:
+                r.part_check = dict(pop=pop, ns=int(pc[0]), kinds=(int(pc[1]), int(pc[3])), pre=(int(pc[2]), int(pc[4])))
         names = ["generated", "accepted", "dropped", "completed", "rejected", "total_service_s",
                  "received", "depth", "active"]
         bufs = {nm: np.zeros(n, np.float64 if nm == "total_service_s" else np.int64) for nm in names}

@@ -317,16 +317,18 @@ def oracle_ring_graph(spec):
 
 def oracle_graph(spec):
     """Oracle nodes of a graph golden (tests/golden/make_golden.py run_graph_case): sources in list order first, then sinks, servers,
-    links, routers.  Returns (graph, {"source": [...], "sink": [...], "server": [...], "link": [...], "router": [...]})."""
+    links, routers, then the Probes of spec["probes"] ([[[kind, index], metric, interval], ...], after every Source: they start after
+    them).  A Server with svc="const" serves in a constant `mean`.  Returns (graph, {"source": [...], "sink": [...], "server": [...],
+    "link": [...], "router": [...], "lb": [...], "probe": [...]})."""
     g = O.Graph()
-    nodes = {"source": [], "sink": [], "server": [], "link": [], "router": [None] * len(spec["routers"]), "lb": []}
+    nodes = {"source": [], "sink": [], "server": [], "link": [], "router": [None] * len(spec["routers"]), "lb": [], "probe": []}
     for k, sc in enumerate(spec["sources"]):
         nodes["source"].append(g.source(O.ARR_POISSON if sc["kind"] == "poisson" else O.ARR_CONSTANT, sc["rate"], stream_base=k,
                                         n_clients=sc.get("n_clients", 0)))
     for _ in range(spec["n_sinks"]):
         nodes["sink"].append(g.sink())
     for i, sv in enumerate(spec["servers"]):
-        nodes["server"].append(g.server(O.LAT_EXP, sv["mean"], concurrency=sv.get("c", 1),
+        nodes["server"].append(g.server(O.LAT_CONST if sv.get("svc") == "const" else O.LAT_EXP, sv["mean"], concurrency=sv.get("c", 1),
                                         queue_cap=-1 if sv.get("cap") is None else sv["cap"], stream_base=i, name=f"srv{i}"))
     for lb in spec.get("lbs") or []:                # strategy by the vnodes field (hs_oracle.c on_lb): > 0 ConsistentHash, 0 RoundRobin, -1 Random
         vn = {"chash": lb.get("vnodes", 100), "round_robin": 0, "random": -1}[lb["strategy"]]
@@ -349,6 +351,8 @@ def oracle_graph(spec):
             g.target[nodes["server"][i]] = nodes[sv["out"][0]][sv["out"][1]]
     for l, lk in enumerate(spec["links"]):
         g.target[nodes["link"][l]] = nodes["server"][lk["to"]]
+    for (kind, idx), metric, interval in spec.get("probes") or []:
+        nodes["probe"].append(g.probe(nodes[kind][idx], PROBE_METRICS[metric][1], interval))
     return g, nodes
 
 

@@ -226,12 +226,12 @@ def union_spec(specs, name="union"):
     Sources of all of them in one list (spec by spec), one end and one seed (the first spec's)."""
     import copy
 
-    out = dict(name=name, topology="graph", n_sinks=0, servers=[], links=[], routers=[], lbs=[], sources=[], schedule=[],
+    out = dict(name=name, topology="graph", n_sinks=0, servers=[], links=[], routers=[], lbs=[], sources=[], schedule=[], probes=[],
                end_s=specs[0]["end_s"], seed=specs[0]["seed"])
     for sp in specs:
         sp = copy.deepcopy(sp)
         off = {"sink": out["n_sinks"], "server": len(out["servers"]), "link": len(out["links"]), "router": len(out["routers"]),
-               "lb": len(out["lbs"])}
+               "lb": len(out["lbs"]), "source": len(out["sources"])}
 
         def sh(ref):
             return None if ref is None else [ref[0], ref[1] + off[ref[0]]]
@@ -248,6 +248,8 @@ def union_spec(specs, name="union"):
             sc["to"] = sc["to"] + off["server"] if isinstance(sc["to"], int) else sh(sc["to"])
         for ref, t in sp.get("schedule") or []:
             out["schedule"].append([sh(ref), min(t, out["end_s"] + 0.5)])
+        for ref, metric, interval in sp.get("probes") or []:
+            out["probes"].append([sh(ref), metric, interval])
         out["n_sinks"] += sp["n_sinks"]
         for k in ("servers", "links", "routers", "sources"):
             out[k].extend(sp[k])
@@ -376,4 +378,79 @@ def lb_strategy_spec(k):
     spec["vnodes"], spec["n_clients"] = 1, (1 if k % 2 == 0 else spec["n_backends"])
     if spec.get("probes"):                        # (a Source with stop_after is not probed: its ticks without Requests are not logged)
         spec["probes"] = [pr for pr in spec["probes"] if not (pr[0] == "source" and spec.get("stop_after_s") is not None)]
+    return spec
+
+
+def _station_part(sources, mean, c=1, cap=None, svc="const", sched=(), probes=()):
+    """One component in the graph-spec format: Sources -> one Server -> one Sink; sched: [(kind, seconds)] with kind "server" | "sink";
+    probes: [(kind, metric, interval)] on the Server / the Sink / the first Source."""
+    return dict(topology="graph", n_sinks=1, links=[], routers=[], lbs=[],
+                servers=[dict(mean=float(mean), c=int(c), cap=cap, out=["sink", 0], svc=svc)],
+                sources=[dict(kind=kind, rate=float(rate), to=0) for kind, rate in sources],
+                schedule=[[[kind, 0], float(t)] for kind, t in sched], probes=[[[kind, 0], metric, float(iv)] for kind, metric, iv in probes])
+
+
+def part_order_spec(k):
+    """A Simulation of 2 to 8 disconnected components built to meet, on purpose, the timestamp groups whose order a part run cannot
+    decide alone (tests/part_model.py), next to one or two ballast components -- 50 to 2 000 low-rate Poisson Sources on a Server of
+    c = 33 -- that drive the process-wide counter and the run's own far from each part's.  k % 5 picks the hazard:
+    (A) Requests schedule()d on a busy constant-service Server, queued, their WORK on the nanosecond of a tick, sample or completion;
+    (B) a first tick on the nanosecond of an event of the run (two constant Sources of one rate or of rates 1 : 2, a Probe);
+    (C) Requests schedule()d on Source tick times; (D) constant Sources of one rate in different components, idle at the end: their
+    first events beyond it tie; (E) controls, constant and Poisson components whose ticks never meet: the parts decide.
+    Periods are binary fractions of a second, service times divide them, queue capacities 0 to 2, c = 1 / 2 / 33."""
+    rng = np.random.default_rng(57_000 + k)
+    cls = "ABCDE"[k % 5]
+    period = float(rng.choice([0.0625, 0.125, 0.25, 0.5]))
+    rate = 1.0 / period
+    m = int(rng.integers(4, 13))
+    end = m * period + (0.37 if cls == "E" else 0.5) * period
+    n_ballast = 1 if rng.random() < 0.7 else 2
+    n_hazard = int(rng.integers(max(1, 2 - n_ballast), 9 - n_ballast))
+    if cls == "D":
+        n_hazard = max(n_hazard, 2)
+    server_metrics = ["depth", "active_requests", "stats_accepted", "stats_dropped", "requests_completed"]
+    comps = []
+    e_rates = list(rng.permutation([3.0, 7.0, 11.0, 13.0, 17.0, 19.0, 23.0, 29.0]))
+    for _ in range(n_hazard):
+        cap = [None, 0, 1, 2][int(rng.choice([0, 0, 1, 2, 2, 3]))]
+        if cls == "A":
+            # (a busy Server: c Requests in service, each for c periods; the Requests schedule()d between two ticks wait in the queue
+            #  and start on a later tick's nanosecond, next to that tick, its payload and the completion that frees the Server)
+            c = int(rng.choice([1, 1, 1, 2]))
+            sched = [("server", (int(rng.integers(1, m)) + float(rng.choice([0.25, 0.5, 0.75]))) * period)
+                     for _ in range(int(rng.integers(1, 4)))]
+            comps.append(_station_part([("constant", rate)], c * period, c, None if cap == 0 else cap, sched=sched))
+        elif cls == "B":
+            c = int(rng.choice([1, 2, 33]))
+            srcs = [("constant", rate)]
+            probes = []
+            what = int(rng.integers(0, 3))
+            if what == 0:
+                srcs.append(("constant", rate))
+            elif what == 1:
+                srcs.append(("constant", 2.0 * rate))
+            else:
+                probes.append(("server", str(rng.choice(server_metrics)), period) if rng.random() < 0.5 else ("sink", "events_received", period))
+            comps.append(_station_part(srcs, period / float(rng.choice([1, 2, 4])), c, cap, probes=probes))
+        elif cls == "C":
+            c = int(rng.choice([1, 2, 33]))
+            sched = [(str(rng.choice(["server", "server", "sink"])), int(rng.integers(1, m + 1)) * period)
+                     for _ in range(int(rng.integers(1, 4)))]
+            comps.append(_station_part([("constant", rate)], period / float(rng.choice([2, 4])), c, cap, sched=sched))
+        elif cls == "D":
+            comps.append(_station_part([("constant", rate)], period / 4.0, int(rng.choice([1, 2, 33])), None))
+        else:
+            srcs = [(str(rng.choice(["constant", "poisson"])), float(e_rates.pop()))]
+            comps.append(_station_part(srcs, float(rng.choice([0.01, 0.02])), int(rng.choice([1, 2, 33])), cap,
+                                       svc=str(rng.choice(["const", "exp"]))))
+    for _ in range(n_ballast):
+        n = int(round(float(np.exp(rng.uniform(np.log(50.0), np.log(2000.0))))))
+        r = 0.0005 if cls == "D" else float(rng.choice([0.02, 0.05, 0.2])) * 50.0 / n * float(rng.choice([1.0, 4.0]))
+        comps.append(_station_part([("poisson", r)] * n, 0.05, 33, None, svc="exp"))
+    order = rng.permutation(len(comps))
+    seed = int(rng.integers(1, 10_000))
+    comps = [dict(comps[i], end_s=end, seed=seed) for i in order]
+    spec = union_spec(comps, name=f"part_order_{k}")
+    spec["part_class"] = cls
     return spec

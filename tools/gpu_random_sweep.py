@@ -173,11 +173,16 @@ def _general(spec):
 
     sim, ents = GS.build(spec)
     if not isinstance(sim.lowered(), GeneralGraph):          # (a draw the station engines take: their families' ground)
-        return
+        return None
     g_o, nodes = H.oracle_graph(spec)
     r = O.run(g_o, H.ns_from_seconds(spec["end_s"]), seed=spec["seed"], schedule=H.oracle_graph_schedule(spec, nodes))
     sim.run()
     _compare_with_oracle(spec, sim, ents, r, nodes)
+    for (pr, data), nd in zip(ents["probes"], nodes["probe"]):
+        t, v = r.sinks[nd]
+        np.testing.assert_array_equal(data._t_ns, t, err_msg=pr.name)
+        np.testing.assert_array_equal(data._v, v, err_msg=pr.name)
+    return sim
 
 
 def graph(k):                  # round 6: several senders per link, any fan-out, Server -> Server next to links, many Sources per Server
@@ -215,7 +220,18 @@ def graph_union(k):             # round 6: several disconnected graphs in ONE Si
     _general(spec)
 
 
-FAMILIES = [graph, lb_graph, graph_probes, graph_union, station, tie, multi_source, ring_async, ring_windowed, jitter_ring_async, jitter_ring_windowed, multi_source_ring_async,
+def part_order(k):              # unions built to meet the timestamp groups a part cannot order alone: one heap exactly when the CPU
+    import part_model as PM    # model of the device's rule (tests/part_model.py) says undecided, parts otherwise; == the oracle
+
+    spec = RS.part_order_spec(k)
+    model = PM.spec_model(spec)[0]
+    sim = _general(spec)
+    if sim is not None:
+        want = model.n_parts if model.decided else 1
+        assert sim._graph_parts == want, f"heaps {sim._graph_parts}, the model's rule: {want} ({model})"
+
+
+FAMILIES = [graph, lb_graph, graph_probes, graph_union, part_order, station, tie, multi_source, ring_async, ring_windowed, jitter_ring_async, jitter_ring_windowed, multi_source_ring_async,
             multi_source_ring_windowed, ring_windows_async, ring_windows_windowed, jitter_ring_windows_async,
             multi_source_ring_windows_async, lb,
             lb_probes, lb_profiles, lb_strategies, lb_workers, tandem, tandem_fan_in, tandem_probes]
