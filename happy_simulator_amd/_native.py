@@ -38,6 +38,11 @@ EV_NAMES = ("source", "enqueue", "notify", "poll", "deliver", "work", "continuat
 PROBE_METRICS = {"depth": 0, "active_requests": 1, "stats_accepted": 2, "stats_dropped": 3, "requests_completed": 4,
                  "_requests_completed": 4, "events_received": 5, "generated_count": 6}
 PROBE_NONE = 255
+# hs_engine_run_path / hs_lb_run_path: which side of the host-side gates the last run landed on (include/hs_engine.h)
+RUN_ONE_LANE, RUN_ONE_LANE_UNI, RUN_WIDE, RUN_WAVE, RUN_TANDEM, RUN_SINGLE_HEAP = 1, 2, 4, 8, 16, 32
+RUN_F64_TIMES, RUN_NET_ASYNC, RUN_NET_ASYNC_UNI, RUN_NET_WINDOWED, RUN_NET_SEGMENTED = 64, 128, 256, 512, 1024
+RUN_LANES_SHIFT = 16        # bits 16..23: lanes per LP (RUN_WIDE) or LPs per workgroup (RUN_WAVE)
+LB_RUN_F64_TIMES, LB_RUN_MARGIN, LB_RUN_LEAN, LB_RUN_SCAN, LB_RUN_SINK_PACKED, LB_RUN_SINK_GATHER = 1, 2, 4, 8, 16, 32
 ABI_VERSION = 16
 IPC_HANDLE_BYTES = 64
 
@@ -362,6 +367,10 @@ def lib():
     L.hs_engine_prologue_path.argtypes = [C.c_void_p]
     L.hs_engine_window_path.restype = C.c_int
     L.hs_engine_window_path.argtypes = [C.c_void_p]
+    L.hs_engine_run_path.restype = C.c_int
+    L.hs_engine_run_path.argtypes = [C.c_void_p]
+    L.hs_lb_run_path.restype = C.c_int
+    L.hs_lb_run_path.argtypes = [C.c_void_p]
     L.hs_engine_synchronize.restype = C.c_int
     L.hs_engine_synchronize.argtypes = [C.c_void_p]
     L.hs_engine_bench_runs.restype = C.c_int
@@ -394,6 +403,8 @@ def lib():
                                  C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_debug_const_div.restype = C.c_int
     L.hs_debug_const_div.argtypes = [C.c_int32, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hs_debug_time_ops.restype = C.c_int
+    L.hs_debug_time_ops.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_engine_set_profile_budget.restype = C.c_int
     L.hs_engine_set_profile_budget.argtypes = [C.c_void_p, C.c_int64]
     L.hs_lb_set_profile_budget.restype = C.c_int
@@ -477,12 +488,13 @@ EXPORTED_SYMBOLS = (
     "hs_engine_shard_ipc_buffers", "hs_engine_shard_peers_local", "hs_engine_shard_push", "hs_engine_shard_inject_ipc",
     "hs_engine_shard_live_export", "hs_engine_shard_live_attach",
     "hs_engine_shard_live_run", "hs_engine_shard_live_wait", "hs_engine_reset",
-    "hs_engine_run_until", "hs_engine_run_until_async", "hs_engine_synchronize", "hs_engine_tandem_path", "hs_engine_prologue_path", "hs_engine_window_path", "hs_engine_bench_runs",
+    "hs_engine_run_until", "hs_engine_run_until_async", "hs_engine_synchronize", "hs_engine_tandem_path", "hs_engine_prologue_path", "hs_engine_window_path", "hs_engine_run_path",
+    "hs_engine_bench_runs",
     "hs_engine_get_summary", "hs_engine_get_lp_stats", "hs_engine_read_sink", "hs_engine_read_sinks", "hs_engine_read_probe",
     "hs_engine_read_probe_slot", "hs_engine_read_source_generated",
     "hs_last_error", "hs_last_global_error", "hs_engine_destroy", "hs_debug_draws", "hs_debug_set_flags",
-    "hs_debug_const_div", "hs_debug_async_counters",
-    "hs_lb_create", "hs_lb_run", "hs_lb_bench_runs", "hs_lb_get_summary", "hs_lb_get_stats", "hs_lb_read_sink",
+    "hs_debug_const_div", "hs_debug_time_ops", "hs_debug_async_counters",
+    "hs_lb_create", "hs_lb_run", "hs_lb_run_path", "hs_lb_bench_runs", "hs_lb_get_summary", "hs_lb_get_stats", "hs_lb_read_sink",
     "hs_lb_set_probes", "hs_lb_read_probe",
     "hs_lb_latency_stats",
     "hs_lb_ring", "hs_lb_select", "hs_lb_last_error", "hs_lb_destroy", "hs_md5", "hs_debug_radix_sort", "hs_merge_sink_records",

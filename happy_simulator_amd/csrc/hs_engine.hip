@@ -91,6 +91,7 @@ struct hs_engine {
     bool net_resume = false;            // ... and this run_until continues from the state that run left (hs_net_resume first)
     int64_t net_resume_from = 0;        // ... whose end_ns this was
     int net_window_path = 0;            // hs_engine_window_path
+    int run_path = 0;                   // hs_engine_run_path: HS_RUN_* bits of what the last run launched
     int xs_phase_seen = 0;              // ... and the prologue's phase (XState::phase)
     Totals tot_seen{};                  // the totals hs_engine_run_until read behind the last run (valid until the next launch):
     bool tot_seen_valid = false;        //   the next window's decision without another round trip to the device
@@ -236,12 +237,14 @@ int upload(hs_engine *h, const T **dst, const T *src, size_t n, T dflt) {
 template <int C>
 void launch_run(hs_engine *h, int64_t end_ns, int mode, int flags) {
     if (h->n_pass > 0) {      // tandem queues: the general-path instantiation, one pass (hs_station.hpp `trk`)
+        h->run_path |= HS_RUN_TANDEM;
         hipLaunchKernelGGL((hs_station_run<C, true>), dim3(h->n_blocks), dim3(kBlock), 0, h->stream, h->P, h->X, h->L, h->tot,
                            h->cands, h->cfg.n_lp, end_ns, mode, flags);
         return;
     }
     if constexpr (C == 1) {
         if (!h->any_profile && !(flags & 512)) {     // producer / consumer wavefronts (debug flag 512: the one-role kernel)
+            h->run_path |= (h->uni_grid && (flags & (1 << 20)) == 0) ? HS_RUN_ONE_LANE_UNI : HS_RUN_ONE_LANE;
             if (h->uni_grid && (flags & (1 << 20)) == 0)   // uniform entity kinds: compile-time predicates (hs_station.hpp HSG)
                 hipLaunchKernelGGL((hs_station_run<1, false, true, true>), dim3(h->n_blocks), dim3(2 * kBlock), 0, h->stream, h->P,
                                    h->X, h->L, h->tot, h->cands, h->cfg.n_lp, end_ns, mode, flags);
@@ -251,6 +254,7 @@ void launch_run(hs_engine *h, int64_t end_ns, int mode, int flags) {
             return;
         }
     }
+    h->run_path |= HS_RUN_ONE_LANE;
     if (h->any_profile)
         hipLaunchKernelGGL((hs_station_run<C, true>), dim3(h->n_blocks), dim3(kBlock), 0, h->stream, h->P, h->X, h->L, h->tot,
                            h->cands, h->cfg.n_lp, end_ns, mode, flags);
@@ -298,6 +302,7 @@ int wide_lanes(const hs_engine *h) {
 template <int K>
 void launch_wide(hs_engine *h, int64_t end_ns) {
     const int n = h->cfg.n_lp, G = 64 / K, nb = (n + G - 1) / G;
+    h->run_path |= HS_RUN_WIDE | (K << 16);
     hipLaunchKernelGGL(hs_station_wide<K>, dim3(nb), dim3(kWideBlock), 0, h->stream, h->P, h->X, h->L, h->tot, h->cands, h->wide_ctl,
                        h->wide_bail, n, end_ns, h->flags);
     hipLaunchKernelGGL(hs_station_wide_finish, dim3(1), dim3(kBlock), 0, h->stream, h->P, h->X, h->L, h->tot, h->cands, nb, h->wide_ctl,
@@ -306,6 +311,7 @@ void launch_wide(hs_engine *h, int64_t end_ns) {
 template <int NW>
 void launch_wave(hs_engine *h, int64_t end_ns) {
     const int n = h->cfg.n_lp, nb = (n + NW - 1) / NW;
+    h->run_path |= HS_RUN_WAVE | (NW << 16);
     const bool fresh = h->reset_pending;                      // the bootstrap inside the kernel, no hs_station_reset launch
     h->reset_pending = false;
     if (fresh)
@@ -374,6 +380,10 @@ void launch_net_resume(hs_engine *h, const NetState &NX, int send_idx) {
     h->launches++;
 }
 
+// the uniform-kind instantiation of hs_net_async (debug flag 1 << 20 keeps the generic one)
+bool async_uni(const hs_engine *h, int lanes) {
+    return h->C == 1 && h->net_uni && !h->net_pf && !h->net_global && (h->flags & ((1 << 20) | 1 | 32)) == 0 && h->round_iters == 0 && lanes == 64;
+}
 template <int C>
 hipError_t launch_async(hs_engine *h, int64_t end_ns, NetState NX) {
     int n = h->cfg.n_lp, flags = h->flags & (1 | 64 | 128 | 1024 | 0xff00 | (1 << 21)), lanes = h->async_lanes;
@@ -382,8 +392,7 @@ hipError_t launch_async(hs_engine *h, int64_t end_ns, NetState NX) {
     void *args[] = {&h->P, &h->NP, &h->X, &NX, &h->L, &h->tot, &n, &end_ns, &flags, &h->SC, &lanes, &max_iters};
     const void *fn = h->net_pf ? (const void *)hs_net_async<C, true> : (const void *)hs_net_async<C, false>;
     if constexpr (C == 1) {    // uniform entity kinds: the specialised instantiation (debug flag 1 << 20 keeps the generic one)
-        if (h->net_uni && !h->net_pf && !h->net_global && (h->flags & ((1 << 20) | 1 | 32)) == 0 && h->round_iters == 0 && lanes == 64)
-            fn = (const void *)hs_net_async<1, false, true>;
+        if (async_uni(h, lanes)) fn = (const void *)hs_net_async<1, false, true>;
     }
     // LIVE exchange: the ranks' kernels wait for one another, and several of them may share this device (shards of one process, or
     // of several processes) -- a plain launch each: what makes them co-resident is that together they have no more workgroups than
@@ -468,6 +477,7 @@ int try_run_net_whole(hs_engine *h, int64_t end_ns) {
         NetState NXs = h->NX;
         NXs.aq_on = 1;
         if (h->net_resume) launch_net_resume(h, NXs, 0);
+        h->run_path |= HS_RUN_NET_SEGMENTED;
         const int rc = run_net_segments(h, end_ns, NXs, h->async_resident_blocks);
         if (rc) return rc;
         const NetState keep = h->NX;
@@ -489,6 +499,7 @@ int try_run_net_whole(hs_engine *h, int64_t end_ns) {
         if (h->net_resume) return fail(h, HS_E_HIP, "the cooperative launch of a resumed window failed: %s", hipGetErrorString(e));
         return 0;               // ... windows
     }
+    h->run_path |= HS_RUN_NET_ASYNC | (async_uni(h, h->async_lanes) ? HS_RUN_NET_ASYNC_UNI : 0);
     const NetState keep = h->NX;
     h->NX = NX;
     launch_net_dispatch(h, end_ns, 1, (h->flags & 1) | 2 | 8);       // FINAL: leftover queue entries, overshoot
@@ -509,6 +520,7 @@ int run_net_async(hs_engine *h, int64_t end_ns) {
     const int64_t W = h->window_ns;
     int64_t t0 = h->cfg.start_ns;
     int win = 0;
+    h->run_path |= HS_RUN_NET_WINDOWED;
     if (h->net_resume) {
         // windows: the conservative windows continue behind the last end (everything at or before it has happened); what the
         // finished group sends waits in the incoming bags the first window merges (parity 1)
@@ -603,6 +615,7 @@ int launch_prologue(hs_engine *h, int64_t end_ns) {
     if (h->lazy_prologue) h->P.sched_idx = lazy_active(h) ? nullptr : h->XI.sched_idx;   // (the prologue writes them)
     if (lazy_active(h)) return HS_OK;
     h->XI.no_handover = h->exact_only ? 1 : 0;
+    if (h->exact_only) h->run_path |= HS_RUN_SINGLE_HEAP;
     hipLaunchKernelGGL(hs_exact_run, dim3(h->XI.per_lp ? (unsigned)((h->cfg.n_lp + 63) / 64) : 1u), dim3(64), 0, h->stream, h->P, h->NP, h->X, h->NX, h->L, h->tot, h->xs, h->XI,
                        h->cfg.n_lp, h->C, h->is_net ? 1 : 0, h->is_net ? h->NP.n_links : 0, h->cfg.start_ns, end_ns);
     HS_HIP(h, hipGetLastError());
@@ -647,6 +660,8 @@ int hs_engine_create(const hs_config *cfg, hs_engine **out) {
         return fail(nullptr, HS_E_INVALID, "hs_engine_create: unknown mode %d", cfg->mode);
     if (cfg->horizon_ns < cfg->start_ns)
         return fail(nullptr, HS_E_INVALID, "hs_engine_create: horizon_ns precedes start_ns");
+    if (cfg->start_ns < 0)      // (the Sinks' merged records and the packed link bounds hold non-negative times)
+        return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, HS_E_NO_DEVICE, "no HIP device visible: the engine has no CPU fallback");
@@ -680,6 +695,7 @@ int hs_engine_set_stations(hs_engine *h, const hs_stations *st) {
     // ---- validation (mirrors the reference constructors' ValueErrors) and sizing
     int maxc = 1;
     double max_mean_records = 0.0;
+    double reach_s = 0.0;        // the longest single step of any entity, in seconds (reach_fits_int64)
     bool any_source = false;
     const double horizon_s = (double)(h->cfg.horizon_ns - h->cfg.start_ns) / 1e9;
     // several Sources feeding one Server: slots 1 .. kMaxXSrc of an LP (include/hs_engine.h `src_more_kind`)
@@ -704,6 +720,7 @@ int hs_engine_set_stations(hs_engine *h, const hs_stations *st) {
             if (!(r > 0.0) || !std::isfinite(r)) return fail(h, HS_E_INVALID, "LP %d: source rate must be > 0 (got %g)", i, r);
             if (r > 1e8) return fail(h, HS_E_UNSUPPORTED, "LP %d: source rate %g above 1e8/s is not supported", i, r);
             xk[o] = (uint8_t)k; xr[o] = r; xsum[(size_t)i] += r;
+            reach_s = std::max(reach_s, 36.8 / r);
             if (st->src_more_stop_after_ns) xstop[o] = st->src_more_stop_after_ns[o];
             ++n_xsrc_total;
         }
@@ -736,6 +753,7 @@ int hs_engine_set_stations(hs_engine *h, const hs_stations *st) {
             if (r > 1e8) return fail(h, HS_E_UNSUPPORTED, "LP %d: source rate %g above 1e8/s is not supported", i, r);
             const double m = (r + xsum[(size_t)i]) * horizon_s;
             if (m > max_mean_records) max_mean_records = m;
+            reach_s = std::max(reach_s, 36.8 / r);                   // (the longest draw: -log(2^-53) = 36.7 inter-arrival means)
         }
         const int c = st->concurrency ? st->concurrency[i] : 1;
         if (c < 1) return fail(h, HS_E_INVALID, "LP %d: max_concurrent must be >= 1, got %d", i, c);
@@ -750,6 +768,7 @@ int hs_engine_set_stations(hs_engine *h, const hs_stations *st) {
         if (!(mean >= 0.0) || !std::isfinite(mean)) return fail(h, HS_E_INVALID, "LP %d: bad service mean %g", i, mean);
         if (vk == HS_LAT_EXPONENTIAL && !(mean > 0.0))
             return fail(h, HS_E_INVALID, "LP %d: exponential service needs mean > 0", i);
+        if (vk != HS_LAT_NO_SERVER) reach_s = std::max(reach_s, vk == HS_LAT_EXPONENTIAL ? 36.8 * mean : mean);
         const int eg = st->egress ? st->egress[i] : HS_EGRESS_SINK;
         if (eg != HS_EGRESS_NONE && eg != HS_EGRESS_SINK && eg != HS_EGRESS_SERVER)
             return fail(h, HS_E_UNSUPPORTED, "LP %d: egress kind %d is not lowered", i, eg);
@@ -853,6 +872,7 @@ int hs_engine_set_stations(hs_engine *h, const hs_stations *st) {
             if (!(iv > 0.0) || !std::isfinite(iv)) return fail(h, HS_E_INVALID, "Probe interval must be positive.");   // probe.py:29-30
             pm[(size_t)j * n + i] = (uint8_t)m;
             prate[(size_t)j * n + i] = 1.0 / iv;
+            reach_s = std::max(reach_s, iv);
             if (min_interval == 0.0 || iv < min_interval) min_interval = iv;
             h->any_probe = true;
             if (j + 1 > h->n_probe_slots) h->n_probe_slots = j + 1;
@@ -860,6 +880,10 @@ int hs_engine_set_stations(hs_engine *h, const hs_stations *st) {
         }
     }
     if (h->any_probe) h->any_profile = true;                        // probes run on the general-path instantiation
+    if (!reach_fits_int64(h->cfg.horizon_ns, reach_s))
+        return fail(h, HS_E_UNSUPPORTED, "the horizon (%lld ns) plus one longest step (%.6g s: 36.8 / the smallest rate, 36.8 x the largest "
+                    "exponential mean, the largest constant service or probe interval) leaves int64 nanoseconds -- refused, never "
+                    "wrapped", (long long)h->cfg.horizon_ns, reach_s);
     // Requests injected with Simulation.schedule(): validated here, run by the general-path instantiation too
     int64_t n_sched = 0, max_sched = 0;
     if (st->sched_off) {
@@ -1284,6 +1308,14 @@ int hs_engine_set_network(hs_engine *h, const hs_network *net) {
         const double lm = net->link_lat_min_s[l];
         if (!(lm > 0.0) || !std::isfinite(lm))
             return fail(h, HS_E_INVALID, "link %d: min latency must be > 0 (conservative windows need lookahead), got %g", l, lm);
+        {   // (before any conversion of the latency to int64 nanoseconds)
+            const int jk0 = net->link_jitter_kind ? net->link_jitter_kind[l] : HS_LAT_CONSTANT;
+            const double jm = net->link_jitter_mean_s ? net->link_jitter_mean_s[l] : 0.0;
+            const double delay_s = lm + (jk0 == HS_LAT_EXPONENTIAL ? 36.8 * jm : jm);
+            if (!reach_fits_int64(h->cfg.horizon_ns, delay_s))
+                return fail(h, HS_E_UNSUPPORTED, "link %d: the horizon (%lld ns) plus its longest delay (%.6g s: latency + 36.8 x the jitter "
+                            "mean) leaves int64 nanoseconds -- refused, never wrapped", l, (long long)h->cfg.horizon_ns, delay_s);
+        }
         const double lc = (double)(int64_t)(lm * 1e9) / 1e9;
         const int64_t w = (int64_t)(lc * 1e9);
         if (w <= 0) return fail(h, HS_E_INVALID, "link %d: min latency %g s truncates to 0 ns", l, lm);
@@ -2059,6 +2091,7 @@ int hs_engine_run_until_async(hs_engine *h, int64_t end_ns) {
                     (long long)h->cfg.horizon_ns);
     HS_HIP(h, hipSetDevice(h->cfg.device));
     h->launches = 0;
+    h->run_path = 0;
     const bool seen_valid = h->tot_seen_valid && !h->pending_async;
     h->tot_seen_valid = false;
     h->net_resume = false;
@@ -2278,6 +2311,7 @@ int hs_engine_prologue_path(const hs_engine *h) {
 }
 int hs_engine_window_path(const hs_engine *h) { return h ? h->net_window_path : 0; }
 int hs_engine_tandem_path(const hs_engine *h) { return !h || h->n_pass == 0 ? 0 : h->exact_only ? 2 : 1; }
+int hs_engine_run_path(const hs_engine *h) { return !h ? 0 : h->run_path | (h->f64_times ? HS_RUN_F64_TIMES : 0); }
 
 int hs_engine_synchronize(hs_engine *h) {
     if (!h) return fail(h, HS_E_INVALID, "null handle");
@@ -2348,6 +2382,7 @@ int hs_engine_bench_runs(hs_engine *h, int64_t end_ns, int32_t repeats, float *k
     if (!h || !h->have_stations) return fail(h, HS_E_STATE, "hs_engine_bench_runs: stations not set");
     if (repeats <= 0) return fail(h, HS_E_INVALID, "repeats must be > 0");
     HS_HIP(h, hipSetDevice(h->cfg.device));
+    h->run_path = 0;
     std::vector<hipEvent_t> ev((size_t)repeats * 2 + 2);
     for (auto &e : ev) HS_HIP(h, hipEventCreate(&e));
     // Round 6: the kernel duration is SAMPLED on every eighth repeat instead of bracketed on every one.  An event pair is two barrier
@@ -2671,6 +2706,33 @@ int hs_debug_const_div(int32_t device, double b, int64_t n, const double *a, dou
     HS_HIP(nullptr, hipMemcpy(q_ieee, d[2], (size_t)n * 8, hipMemcpyDeviceToHost));
     HS_HIP(nullptr, hipMemcpy(q_ns, d[3], (size_t)n * 8, hipMemcpyDeviceToHost));
     for (auto &p : d) hipFree(p);
+    return HS_OK;
+}
+
+int hs_debug_time_ops(int32_t device, int64_t n, const int64_t *ns, const double *secs, double *out_f64, int64_t *out_i64) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, HS_E_NO_DEVICE, "no HIP device visible: the engine has no CPU fallback");
+    if (n <= 0 || !ns || !secs || !out_f64 || !out_i64) return fail(nullptr, HS_E_INVALID, "hs_debug_time_ops: bad arguments");
+    if (device < 0 || device >= ndev) return fail(nullptr, HS_E_INVALID, "device ordinal %d out of range (%d devices)", device, ndev);
+    HS_HIP(nullptr, hipSetDevice(device));
+    void *d[4] = {nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[4] = {(size_t)n * 8, (size_t)n * 8, (size_t)n * 24, (size_t)n * 16};
+    for (int k = 0; k < 4; ++k) {
+        const hipError_t e = hipMalloc(&d[k], bytes[k]);
+        if (e != hipSuccess) { for (auto &p : d) if (p) hipFree(p); return fail(nullptr, HS_E_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
+    }
+    hipError_t e = hipMemcpy(d[0], ns, bytes[0], hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d[1], secs, bytes[1], hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(hs_debug_time_ops_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, (const int64_t *)d[0],
+                           (const double *)d[1], (double *)d[2], (int64_t *)d[3]);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out_f64, d[2], bytes[2], hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_i64, d[3], bytes[3], hipMemcpyDeviceToHost);
+    for (auto &p : d) hipFree(p);
+    if (e != hipSuccess) return fail(nullptr, HS_E_HIP, "hs_debug_time_ops: %s", hipGetErrorString(e));
     return HS_OK;
 }
 

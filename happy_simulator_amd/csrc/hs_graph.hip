@@ -601,6 +601,7 @@ using namespace hs::graph;
 struct hs_graph {
     hs_graph_config cfg{};
     int n = 0, n_rt = 0;
+    double reach_s = 0.0;          // the longest single step of any node, in seconds: end + this must stay inside int64 (reach_fits_int64)
     GCtl ctl{};
     std::vector<GParam> params;
     std::vector<int32_t> sched_node; std::vector<int64_t> sched_t;
@@ -725,6 +726,8 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count < 1)
         return gfail(nullptr, HS_E_NO_DEVICE, "no HIP device is visible (the engine has no CPU fallback)");
     if (cfg->device < 0 || cfg->device >= dev_count) return gfail(nullptr, HS_E_INVALID, "device %d out of range", cfg->device);
+    if (cfg->start_ns < 0)        // (the Sinks' merged records hold non-negative times)
+        return gfail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
     auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB; };
     int64_t kmax = 0;                                  // client ids any Source hands out: [0, kmax)
     for (int i = 0; i < n; ++i)
@@ -878,6 +881,14 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     }
     hs_graph *g = new hs_graph();
     g->cfg = *cfg; g->n = n; g->n_rt = nd->n_rt; g->params = P; g->rows = rows; g->row_rate = row_rate;
+    for (int i = 0; i < n; ++i) {
+        const GParam &p = P[(size_t)i];
+        const double draw = p.sub == HS_LAT_EXPONENTIAL ? 36.8 * p.mean : p.mean;       // (-log(2^-53) = 36.7 means at most)
+        if (p.kind == HS_NODE_SOURCE) g->reach_s = std::max(g->reach_s, 36.8 / p.mean);
+        else if (p.kind == HS_NODE_SERVER) g->reach_s = std::max(g->reach_s, draw);
+        else if (p.kind == HS_NODE_LINK) g->reach_s = std::max(g->reach_s, p.lat_min + draw);
+        else if (p.kind == HS_NODE_PROBE) g->reach_s = std::max(g->reach_s, 1.0 / row_rate[(size_t)p.rt_off]);
+    }
 #define HSG_TRY(expr) do { int rc_ = (expr); if (rc_) { g_graph_error = g->error; hs_graph_destroy(g); return rc_; } } while (0)
 #define HSG_HIPD(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { gfail(g, HS_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); g_graph_error = g->error; hs_graph_destroy(g); return HS_E_HIP; } } while (0)
     HSG_HIPD(hipSetDevice(cfg->device));
@@ -997,6 +1008,10 @@ static int build_tables(hs_graph *g, int64_t horizon) {
 // What a run needs before its first launch: tick tables up to the end, the schedule()d entries on the device.
 static int prepare_run(hs_graph *g, int64_t end_ns) {
     GCtl &c = g->ctl;
+    if (!hs::reach_fits_int64(end_ns, g->reach_s))
+        return gfail(g, HS_E_UNSUPPORTED, "the end (%lld ns) plus one longest step (%.6g s: 36.8 / the smallest rate, 36.8 x the largest "
+                     "exponential mean, a constant service, a link's delay or a probe interval) leaves int64 nanoseconds -- refused, "
+                     "never wrapped", (long long)end_ns, g->reach_s);
     // table-driven streams: up to this end when it is a real horizon, else (an auto-terminating run) a minute at a time
     int64_t table_h = end_ns;
     if (!g->rows.empty()) {

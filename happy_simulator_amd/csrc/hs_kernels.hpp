@@ -2069,6 +2069,18 @@ __global__ void hs_debug_const_div_kernel(double b, int64_t n, const double *a, 
     q_ieee[i] = __ddiv_rn(a[i], b);
     q_ns[i] = seconds_from_ns((int64_t)a[i]);
 }
+// the time algebra of hs_device.hpp, one input per thread (hs_debug_time_ops)
+__global__ void hs_debug_time_ops_kernel(int64_t n, const int64_t *ns, const double *secs, double *out_f64, int64_t *out_i64) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t t = ns[i];
+    const double x = secs[i];
+    out_f64[3 * i] = seconds_from_ns(t);
+    out_f64[3 * i + 1] = seconds_from_ns_d(__ll2double_rn(t));
+    out_f64[3 * i + 2] = ns_from_seconds_d(x);
+    out_i64[2 * i] = ns_from_seconds(x);
+    out_i64[2 * i + 1] = i64_from_whole_d(__ll2double_rn(t));
+}
 #endif  // HS_KERNELS_MAIN
 
 #include "hs_kernels_wide.hpp"

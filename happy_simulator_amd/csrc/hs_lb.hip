@@ -1757,7 +1757,8 @@ struct hs_lb {
     int src_lanes_run = 64;                            // Sources per wavefront of the last run's Source kernel (hs_lb_finalize reads one candidate per workgroup)
     bool lean_off = false, lean_ran = false;           // hs_lbk_sources_lean: switched off after a run it could not cover; used by the last run
     int n_simd = 1024;                                 // SIMDs of the device (4 per CU): lb_lanes()
-    bool f64_times = false;                            // every time of a run is a whole ns in [0, 2^51): exact in binary64
+    bool f64_times = false;                            // every time of a run is a whole ns in [0, 2^52): exact in binary64
+    int run_path = 0;                                  // hs_lb_run_path: HS_LB_RUN_* bits of the last run
     uint64_t *kA = nullptr, *vA = nullptr, *kB = nullptr, *vB = nullptr;   // dense ping-pong buffers [n_slots]
     uint64_t *skey = nullptr, *sval = nullptr;        // where the sorted arrivals ended up
     uint64_t *mkey = nullptr, *mslot = nullptr;       // where the merged Sink order ended up
@@ -2071,6 +2072,10 @@ int run_async(hs_lb *h, int64_t end_ns) {
                            h->skey, h->off, h->adm, h->sink_t, h->out_t, h->n_done, 1, 1, h->tot, h->keys0, h->PS.count, S);
         h->launches += 1;
     }
+    // (binary64 times: the Sources' kernels whenever f64_times holds and no Source has a profile; the scan unless debug flag 128)
+    const bool f64_ran = h->f64_times && (!h->any_src_profile || (scan && (h->flags & 128) == 0));
+    h->run_path = (f64_ran ? HS_LB_RUN_F64_TIMES : 0) | (margin > 0.0 ? HS_LB_RUN_MARGIN : 0) | (h->lean_ran ? HS_LB_RUN_LEAN : 0) |
+                  (scan ? HS_LB_RUN_SCAN : 0) | (h->cfg.shared_sink ? (h->slot_bits ? HS_LB_RUN_SINK_PACKED : HS_LB_RUN_SINK_GATHER) : 0);
     {
         const int sl = h->src_lanes_run * (kLbBlock / 64), bl = lb_lanes(h, B) * (kLbBlock / 64);
         hipLaunchKernelGGL(hs_lb_finalize, dim3(1), dim3(kLbBlock), 0, h->stream, h->PS, h->PB, S, B, h->cfg.start_ns, h->tot, h->Q,
@@ -2140,7 +2145,8 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     if (cfg->strategy < HS_LB_CONSISTENT_HASH || cfg->strategy > HS_LB_RANDOM) return lfail(nullptr, HS_E_UNSUPPORTED, "load-balancing strategy %d is not lowered", cfg->strategy);
     const bool chash = cfg->strategy == HS_LB_CONSISTENT_HASH;
     if (chash && cfg->virtual_nodes < 1) return lfail(nullptr, HS_E_INVALID, "virtual_nodes must be >= 1, got %d", cfg->virtual_nodes);
-    if (cfg->horizon_ns < cfg->start_ns || cfg->start_ns < 0) return lfail(nullptr, HS_E_INVALID, "hs_lb_create: bad start / horizon");
+    if (cfg->start_ns < 0) return lfail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
+    if (cfg->horizon_ns < cfg->start_ns) return lfail(nullptr, HS_E_INVALID, "hs_lb_create: horizon_ns precedes start_ns");
     if (!src->src_rate || (chash && !src->n_clients)) return lfail(nullptr, HS_E_INVALID, "src_rate and n_clients are required");
     if (!be->names || !be->name_off) return lfail(nullptr, HS_E_INVALID, "backend names are required (the ring hashes them)");
     int ndev = 0;
@@ -2172,6 +2178,7 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     if (kmax > (1ll << 26)) return lfail(nullptr, HS_E_UNSUPPORTED, "n_clients above 2^26 is not supported (client -> backend table)");
     int maxc = 1;
     bool any_no_sink = false;
+    double svc_step_s = 0.0;        // the longest service one request can draw: 36.8 exponential means or a constant
     for (int j = 0; j < B; ++j) {
         const int c = be->concurrency ? be->concurrency[j] : 1;
         if (c < 1) return lfail(nullptr, HS_E_INVALID, "backend %d: max_concurrent must be >= 1, got %d", j, c);
@@ -2182,12 +2189,17 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
         const double mean = be->svc_mean_s ? be->svc_mean_s[j] : 0.01;
         if (!(mean >= 0.0) || !std::isfinite(mean) || (vk == HS_LAT_EXPONENTIAL && !(mean > 0.0)))
             return lfail(nullptr, HS_E_INVALID, "backend %d: bad service mean %g", j, mean);
+        svc_step_s = std::max(svc_step_s, vk == HS_LAT_EXPONENTIAL ? 36.8 * mean : mean);
         const int eg = be->egress ? be->egress[j] : HS_EGRESS_SINK;
         if (eg != HS_EGRESS_NONE && eg != HS_EGRESS_SINK) return lfail(nullptr, HS_E_UNSUPPORTED, "backend %d: egress kind %d is not lowered", j, eg);
         if (eg == HS_EGRESS_NONE) any_no_sink = true;
         if (be->name_off[j + 1] < be->name_off[j] || be->name_off[j + 1] - be->name_off[j] > 200)
             return lfail(nullptr, HS_E_INVALID, "backend %d: bad name", j);
     }
+    if (!reach_fits_int64(cfg->horizon_ns, std::max(svc_step_s, 36.8 / min_rate)))
+        return lfail(nullptr, HS_E_UNSUPPORTED, "the horizon (%lld ns) plus one longest step (%.6g s: 36.8 / the smallest rate, 36.8 x the "
+                     "largest exponential mean or the largest constant service) leaves int64 nanoseconds -- refused, never wrapped",
+                     (long long)cfg->horizon_ns, std::max(svc_step_s, 36.8 / min_rate));
     hs_lb *h = new (std::nothrow) hs_lb();
     if (!h) return lfail(nullptr, HS_E_INVALID, "out of host memory");
     h->cfg = *cfg;
@@ -2202,7 +2214,10 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     // reach past cap * roundup64(S) slots when S > 64), so a tick_capacity that is no multiple of 16 rounds DOWN; the rest is self-drawn
     h->n_pre = std::min<int64_t>(cap & ~(int64_t)15, ((int64_t)(max_ticks + 5.0 * std::sqrt(max_ticks + 1.0) + 16.0) + 15) & ~(int64_t)15);
     h->n_slots = cap * (int64_t)S;
-    h->f64_times = cfg->start_ns >= 0 && cfg->horizon_ns < (1ll << 50) && min_rate > 1e-3;   // (one increment <= 36.8 / rate seconds)
+    // (one increment <= 36.8 / rate seconds; a started request's departure S + service, S <= horizon, is the pending event beyond the
+    // end: hs_lbk_scan<true> converts it with i64_from_whole_d, exact below 2^52 only)
+    h->f64_times = cfg->start_ns >= 0 && cfg->horizon_ns < (1ll << 50) && min_rate > 1e-3 &&
+                   (double)cfg->horizon_ns + svc_step_s * 1e9 < 4503599627370496.0;
     if ((double)h->n_slots * 88.0 > 200e9) { delete h; return lfail(nullptr, HS_E_INVALID, "buffers would need %.1f GB", (double)h->n_slots * 88.0 / 1e9); }
     {   // rows of the [k][backend] layout: three times the mean load of a backend (consistent hashing with >= 100 virtual
         // nodes keeps the busiest backend below ~2x); capped so that the five transposed arrays stay within ~4x n_slots
@@ -2384,6 +2399,8 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     *out = h;
     return HS_OK;
 }
+
+int hs_lb_run_path(const hs_lb *h) { return h ? h->run_path : 0; }
 
 int hs_lb_run(hs_lb *h, int64_t end_ns) {
     if (!h) return lfail(h, HS_E_INVALID, "hs_lb_run: null handle");

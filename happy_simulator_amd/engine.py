@@ -356,6 +356,11 @@ class StationEngine:
         left; 2 nothing moved; 3 repeated from the start (include/hs_engine.h hs_engine_window_path)."""
         return int(self._lib.hs_engine_window_path(self._h))
 
+    def run_path(self) -> int:
+        """Which kernels the last run_until launched: _native.RUN_* bits, the lanes per LP / LPs per workgroup of the wide and
+        wavefront kernels in bits 16..23 (include/hs_engine.h hs_engine_run_path).  Read-only; results do not depend on it."""
+        return int(self._lib.hs_engine_run_path(self._h))
+
     def synchronize(self):
         self._check(self._lib.hs_engine_synchronize(self._h))
 
@@ -472,3 +477,21 @@ def debug_const_div(a: np.ndarray, b: float, device: int = 0):
     if rc < 0:
         raise N.EngineError(rc, L.hs_last_global_error().decode())
     return qf, qi, qn
+
+
+def debug_time_ops(ns: np.ndarray, secs: np.ndarray, device: int = 0) -> dict:
+    """The device time algebra (csrc/hs_device.hpp) on int64 ns and binary64 seconds -- test hook (include/hs_engine.h
+    hs_debug_time_ops)."""
+    L = N.lib()
+    ns = np.ascontiguousarray(ns, np.int64)
+    secs = np.ascontiguousarray(secs, np.float64)
+    assert len(ns) == len(secs) > 0
+    f = np.zeros((len(ns), 3), np.float64)
+    i = np.zeros((len(ns), 2), np.int64)
+    rc = L.hs_debug_time_ops(device, len(ns), ns.ctypes.data, secs.ctypes.data, f.ctypes.data, i.ctypes.data)
+    if rc == N.HS_E_NO_DEVICE:
+        raise N.EngineUnavailable(L.hs_last_global_error().decode())
+    if rc < 0:
+        raise N.EngineError(rc, L.hs_last_global_error().decode())
+    return dict(seconds_from_ns=f[:, 0], seconds_from_ns_d=f[:, 1], ns_from_seconds_d=f[:, 2], ns_from_seconds=i[:, 0],
+                i64_from_whole_d=i[:, 1])

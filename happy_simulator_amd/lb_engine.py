@@ -133,6 +133,10 @@ class LoadBalancerEngine:
         """`Simulation.__init__` + `run()` to end_ns (one-event overshoot included)."""
         self._check(self._lib.hs_lb_run(self._h, int(end_ns)))
 
+    def run_path(self) -> int:
+        """Which paths the last run took: _native.LB_RUN_* bits (include/hs_engine.h hs_lb_run_path).  Read-only."""
+        return int(self._lib.hs_lb_run_path(self._h))
+
     def set_probes(self, target_kind, target_index, metric, interval_s) -> None:
         """Probe.on(<backend Server> | <Sink>, metric, interval) (include/hs_engine.h `hs_lb_set_probes`): target_kind 0 =
         backend Server, 1 = Sink; metric = N.PROBE_METRICS id; once, before the first run."""

@@ -207,6 +207,9 @@ class Simulation:
                 # the primary count above zero for ever, exactly like a Source's
                 raise UnsupportedTopology("end_time = Infinity with Probes never terminates either (a Probe's ticks are primary events: "
                                           "only its probe_event samples are daemons, load/source_event.py:27); pass end_time/duration")
+        if self._start_time.nanoseconds < 0:
+            # the reference accepts it; every engine keeps its Sinks' records and its links' packed bounds as non-negative times
+            raise UnsupportedTopology(f"start_time {self._start_time!r} is negative: not lowered (the engines refuse it too)")
         wall0 = _time.monotonic()
         import gc
 

@@ -340,6 +340,23 @@ int hs_engine_prologue_path(const hs_engine *h);
  * Diagnostics only; results are identical. */
 int hs_engine_window_path(const hs_engine *h);
 
+/* Which kernels the last hs_engine_run_until ran (everything since it started, the repetitions hs_engine_synchronize makes
+ * included), as HS_RUN_* bits; bits 16..23 hold the lanes per LP of the wide kernel or the LPs per workgroup of the wavefront-per-LP
+ * kernel.  HS_RUN_F64_TIMES: the engine keeps whole nanoseconds as binary64 on its uniform paths (start >= 0, horizon < 2^51,
+ * rates > 1e-3, means < 1e4).  Read-only, for tests that must know which side of a host-side gate a configuration landed on. */
+#define HS_RUN_ONE_LANE        (1 << 0)    /* hs_station_run, one lane per LP, general entity kinds */
+#define HS_RUN_ONE_LANE_UNI    (1 << 1)    /* hs_station_run, uniform entity kinds (binary64 times) */
+#define HS_RUN_WIDE            (1 << 2)    /* hs_station_wide<K>, K lanes per LP */
+#define HS_RUN_WAVE            (1 << 3)    /* hs_station_wave<NW>, one wavefront per LP */
+#define HS_RUN_TANDEM          (1 << 4)    /* passes of the station kernel, upstream Servers first */
+#define HS_RUN_SINGLE_HEAP     (1 << 5)    /* the single-heap loop held the whole run (csrc/hs_exact.hpp) */
+#define HS_RUN_F64_TIMES       (1 << 6)
+#define HS_RUN_NET_ASYNC       (1 << 7)    /* hs_net_async, one cooperative launch */
+#define HS_RUN_NET_ASYNC_UNI   (1 << 8)    /* ... its uniform-kind instantiation */
+#define HS_RUN_NET_WINDOWED    (1 << 9)    /* conservative windows of hs_net_window */
+#define HS_RUN_NET_SEGMENTED   (1 << 10)   /* segments of hs_net_async taking turns */
+int hs_engine_run_path(const hs_engine *h);
+
 int hs_engine_create(const hs_config *cfg, hs_engine **out);
 int hs_engine_set_stations(hs_engine *h, const hs_stations *st);
 /* Optional, after hs_engine_set_stations and before the first run: connect stations with links / routers.
@@ -542,6 +559,14 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
  * last one is the state of one run to e_k -- which is what the reference's windows leave (one global event order, every call stops
  * behind the first event beyond its end): tests/test_gpu_lb.py::test_lb_windows_equal_one_run. */
 int hs_lb_run(hs_lb *h, int64_t end_ns);
+/* Which paths the last hs_lb_run took, as HS_LB_RUN_* bits (read-only, for tests). */
+#define HS_LB_RUN_F64_TIMES    (1 << 0)    /* Sources and the scan keep whole nanoseconds as binary64 */
+#define HS_LB_RUN_MARGIN       (1 << 1)    /* speculated whole-ns arrival steps (lb_step_encode; horizon < 2^40) */
+#define HS_LB_RUN_LEAN         (1 << 2)    /* hs_lbk_sources_lean */
+#define HS_LB_RUN_SCAN         (1 << 3)    /* the backends as (max, +) scans (hs_lbk_scan) */
+#define HS_LB_RUN_SINK_PACKED  (1 << 4)    /* shared Sink merge: created_at << slot_bits | slot in one word */
+#define HS_LB_RUN_SINK_GATHER  (1 << 5)    /* shared Sink merge: created_at gathered by slot */
+int hs_lb_run_path(const hs_lb *h);
 /* `repeats` complete runs back to back on the engine's stream; per-run device time of the whole pipeline and of the
  * sort passes alone (HIP events on that stream). */
 int hs_lb_bench_runs(hs_lb *h, int64_t end_ns, int32_t repeats, float *run_ms_out, float *sort_ms_out);
@@ -651,6 +676,10 @@ int64_t hs_debug_tick_table(int32_t device, const double *profile, int32_t poiss
  * division, q_ns[i] = seconds_from_ns((int64)a[i]) (compare with a[i] / 1e9). */
 int hs_debug_const_div(int32_t device, double b, int64_t n, const double *a, double *q_fast, double *q_ieee,
                        double *q_ns);
+/* Debug: the device time algebra (csrc/hs_device.hpp) on n inputs: out_f64[3 i] = seconds_from_ns(ns[i]),
+ * out_f64[3 i + 1] = seconds_from_ns_d((double)ns[i]), out_f64[3 i + 2] = ns_from_seconds_d(secs[i]),
+ * out_i64[2 i] = ns_from_seconds(secs[i]), out_i64[2 i + 1] = i64_from_whole_d((double)ns[i]). */
+int hs_debug_time_ops(int32_t device, int64_t n, const int64_t *ns, const double *secs, double *out_f64, int64_t *out_i64);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * General entity graphs (ABI 15; LoadBalancer nodes: ABI 16).

@@ -262,6 +262,8 @@ class Result:
 def _create(g: Graph, end_ns: int, start_ns: int, seed: int, rng_mode: int, mt_seed_py: int, mt_seed_np: int,
             trace_cap: int, coord_seed: int = 42, part_check: int = 0):
     """hso_create for a Graph; returns the handle (the C side copies every array)."""
+    if start_ns < 0:        # (the reference accepts it and this port does not reproduce it; the engines refuse it too)
+        raise ValueError(f"start_time {start_ns} ns is negative: not lowered")
     L = lib()
     n = len(g)
     arrs = {

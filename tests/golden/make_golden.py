@@ -251,7 +251,7 @@ def build_chains(spec, chain_ids, seed):
         # (include/hs_engine.h `src_more_kind`).  Several Sources feeding one Server are entities of their own.
         made = []
         for slot, (sa, sr, is_first) in enumerate(slot_plan[i]):
-            stop_instant = None if stop is None else Instant.from_seconds(stop)
+            stop_instant = None if stop is None else _at(spec, stop)
             if spec["rng"] != "philox":
                 factory = Source.poisson if sa == "poisson" else Source.constant
                 made.append(factory(rate=sr, target=server, name=f"src{i}" + ("" if is_first else f"_{slot}"), stop_after=stop))
@@ -304,6 +304,19 @@ def classify(ev, node_of):
 
 
 
+def _at(spec, t_s):
+    """The absolute Instant `t_s` seconds after the spec's start: spec["start_ns"] (integer nanoseconds, default 0) plus
+    Instant.from_seconds(t_s) -- ends, stop_after, window ends and scheduled times move with the start."""
+    return Instant(int(spec.get("start_ns", 0)) + Instant.from_seconds(t_s).nanoseconds)
+
+
+def _start(spec):
+    """Simulation(start_time=...) of a spec: the integer spec["start_ns"], else the float spec["start_s"], else the default."""
+    if "start_ns" in spec:
+        return Instant(int(spec["start_ns"]))
+    return Instant.from_seconds(spec["start_s"]) if spec.get("start_s") else None
+
+
 def run_sim_windows(sim, spec):
     """`sim.run()`, or -- spec["windows"] = [t_1, ..., t_k] seconds -- the reference's own windowed execution (core/simulation.py:527-541
     `_run_window`, what ParallelSimulation's coordinator drives) to every t_i and then to end_s; the summary as run() builds it."""
@@ -311,7 +324,7 @@ def run_sim_windows(sim, spec):
     if not w:
         return sim.run()
     for t in list(w) + [spec["end_s"]]:
-        sim._run_window(Instant.from_seconds(t))
+        sim._run_window(_at(spec, t))
     sim._is_running = False
     return sim._build_summary()
 
@@ -345,8 +358,7 @@ def run_sim(spec, chain_ids, seed, want_trace):
             data.add_stat = add_stat
             probes.append((c, probe))
             probe_data[(c, j)] = data
-    sim = Simulation(start_time=Instant.from_seconds(spec.get("start_s", 0)) if spec.get("start_s") else None,
-                     end_time=Instant.from_seconds(spec["end_s"]), sources=sources, entities=entities,
+    sim = Simulation(start_time=_start(spec), end_time=_at(spec, spec["end_s"]), sources=sources, entities=entities,
                      probes=[p for _, p in probes])
     sim._probe_data = probe_data
     # chain-local node numbering: chain c -> (source=c, server=c, sink=c); kinds disambiguate
@@ -388,7 +400,7 @@ def run_sim(spec, chain_ids, seed, want_trace):
     # Simulation.schedule(): one-off Requests built by the caller AFTER the Simulation (core/simulation.py:195-206)
     for c, t_s in spec.get("schedule") or []:
         if c in chain_ids:
-            sim.schedule(Event(time=Instant.from_seconds(t_s), event_type="Request",
+            sim.schedule(Event(time=_at(spec, t_s), event_type="Request",
                                target=handles[chain_ids.index(c)][1]))
     summary = run_sim_windows(sim, spec)
     return sim, summary, handles, trace
@@ -725,7 +737,7 @@ def run_ring_case(spec):
             data.add_stat = add_stat
             probes.append((i, probe))
             probe_data[(i, j)] = data
-    sim = Simulation(end_time=Instant.from_seconds(spec["end_s"]), sources=listed,
+    sim = Simulation(start_time=_start(spec), end_time=_at(spec, spec["end_s"]), sources=listed,
                      entities=servers + routers + links + sinks, probes=[p for _, p in probes])
     node_of = {}
     for i in range(n):
@@ -753,7 +765,7 @@ def run_ring_case(spec):
 
         heap.pop = pop
     for i, t_s in spec.get("schedule") or []:          # Simulation.schedule(): Requests for station i's Server, before run()
-        sim.schedule(Event(time=Instant.from_seconds(t_s), event_type="Request", target=servers[i]))
+        sim.schedule(Event(time=_at(spec, t_s), event_type="Request", target=servers[i]))
     summary = run_sim_windows(sim, spec)
     out = {}
     meta = dict(spec=spec, total_events=[summary.total_events_processed], final_ns=[sim._current_time.nanoseconds],
@@ -872,9 +884,10 @@ def run_graph_case(spec):
         else:
             ep = SimpleEventProvider(to, "Request", None)
         sources.append(Source(f"src{k}", ep, prov))
-    sim = Simulation(end_time=Instant.from_seconds(spec["end_s"]), sources=sources, entities=servers + lbs + routers + links + sinks)
+    sim = Simulation(start_time=_start(spec), end_time=_at(spec, spec["end_s"]), sources=sources,
+                     entities=servers + lbs + routers + links + sinks)
     for ref, t_s in spec.get("schedule") or []:      # Simulation.schedule() before run(), in this order (core/simulation.py:195-206)
-        sim.schedule(Event(time=Instant.from_seconds(t_s), event_type="Request", target=entity(ref)))
+        sim.schedule(Event(time=_at(spec, t_s), event_type="Request", target=entity(ref)))
     summary = sim.run()
     out = {}
     meta = dict(spec=spec, total_events=[summary.total_events_processed], final_ns=[sim._current_time.nanoseconds],
@@ -942,7 +955,7 @@ def run_lb_case(spec):
         lb = LoadBalancer("lb", backends=servers, strategy=ConsistentHash(virtual_nodes=spec["vnodes"]))
     rate = _per_chain(spec["rate"], S)
     stop = spec.get("stop_after_s")
-    stop_instant = None if stop is None else Instant.from_seconds(stop)
+    stop_instant = None if stop is None else _at(spec, stop)
     sources = []
     profiles = spec.get("profile") or [None] * S              # per source: None | ["ramp", d, s, e] | ["spike", b, s, w, d]
     for i in range(S):
@@ -967,7 +980,7 @@ def run_lb_case(spec):
         data.add_stat = add_stat
         probes.append(probe)
         probe_data.append(data)
-    sim = Simulation(end_time=Instant.from_seconds(spec["end_s"]), sources=sources, entities=[lb, *servers, *sinks],
+    sim = Simulation(start_time=_start(spec), end_time=_at(spec, spec["end_s"]), sources=sources, entities=[lb, *servers, *sinks],
                      probes=probes)
     node_of = {id(lb): S}
     for j, probe in enumerate(probes):

@@ -7,9 +7,10 @@ import numpy as np
 import happy_simulator_amd as hs
 
 
-def build(spec, extra_schedule=None):
+def build(spec, extra_schedule=None, start_ns=0):
     """Returns (Simulation, dict(sources, servers, links, routers, sinks, lbs, probes)); probes: [(Probe, Data), ...] of spec["probes"]
-    ([[[kind, index], metric, interval], ...]).  A Server with svc="const" serves in a constant `mean`."""
+    ([[[kind, index], metric, interval], ...]).  A Server with svc="const" serves in a constant `mean`.  start_ns: an integer
+    `Simulation(start_time=...)`; the end and the scheduled times move with it."""
     sinks = [hs.Sink(f"sink{j}") for j in range(spec["n_sinks"])]
     servers = [hs.Server(f"srv{i}", concurrency=sv.get("c", 1), service_time=hs.ConstantLatency(sv["mean"]) if sv.get("svc") == "const" else hs.ExponentialLatency(sv["mean"]),
                          queue_capacity=sv.get("cap")) for i, sv in enumerate(spec["servers"])]
@@ -48,13 +49,17 @@ def build(spec, extra_schedule=None):
             sources.append(make(rate=sc["rate"], target=to, name=f"src{k}"))
     pools["source"] = sources
     probes = [hs.Probe.on(pools[kind][idx], metric, interval=interval) for (kind, idx), metric, interval in spec.get("probes") or []]
-    end = None if spec.get("end_s") is None else hs.Instant.from_seconds(spec["end_s"])      # None: auto-termination
+    def at(t_s):
+        return hs.Instant(start_ns + hs.Instant.from_seconds(t_s).nanoseconds)
+
+    end = None if spec.get("end_s") is None else at(spec["end_s"])      # None: auto-termination
     sim = hs.Simulation(end_time=end, sources=sources, entities=servers + lbs + routers + links + sinks, seed=spec["seed"],
+                        **({"start_time": hs.Instant(start_ns)} if start_ns else {}),
                         **({"probes": [p for p, _ in probes]} if probes else {}))
     for (kind, idx), t_s in spec.get("schedule") or []:
-        sim.schedule(hs.Event(time=hs.Instant.from_seconds(t_s), event_type="Request", target=pools[kind][idx]))
+        sim.schedule(hs.Event(time=at(t_s), event_type="Request", target=pools[kind][idx]))
     for kind, idx, t_s in (extra_schedule or []):
-        sim.schedule(hs.Event(time=hs.Instant.from_seconds(t_s), event_type="Request", target=pools[kind][idx]))
+        sim.schedule(hs.Event(time=at(t_s), event_type="Request", target=pools[kind][idx]))
     return sim, dict(sources=sources, servers=servers, links=links, routers=routers, sinks=sinks, lbs=lbs, probes=probes)
 
 

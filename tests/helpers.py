@@ -72,6 +72,16 @@ def ns_from_seconds(x: float) -> int:
     return int(x * 1_000_000_000)
 
 
+def spec_start_ns(spec) -> int:
+    """A spec's start (Simulation(start_time=Instant(ns))): the integer spec["start_ns"], default 0."""
+    return int(spec.get("start_ns", 0))
+
+
+def spec_ns(spec, t_s) -> int:
+    """The absolute nanosecond `t_s` seconds after the spec's start (tests/golden/make_golden.py `_at`)."""
+    return spec_start_ns(spec) + ns_from_seconds(t_s)
+
+
 def _probe_lists(spec, n):
     """spec["probes"][c] is None, one [metric, interval] pair, or a list of pairs (several probes on one chain)."""
     out = []
@@ -94,14 +104,14 @@ def spec_chain_params(spec):
         mean=[float(m) for m in per_chain(spec["mean"], n)],
         conc=per_chain(spec.get("concurrency", 1), n),
         qcap=[-1 if q is None else int(q) for q in per_chain(spec.get("queue_cap"), n)],
-        stop_ns=-1 if spec.get("stop_after_s") is None else ns_from_seconds(spec["stop_after_s"]),
+        stop_ns=-1 if spec.get("stop_after_s") is None else spec_ns(spec, spec["stop_after_s"]),
         downstream=spec.get("downstream", True),
-        end_ns=ns_from_seconds(spec["end_s"]),
+        start_ns=spec_start_ns(spec), end_ns=spec_ns(spec, spec["end_s"]),
         profile=[None if pr is None else tuple(pr) for pr in (spec.get("profile") or [None] * n)],
         probes=[None if pr is None else (pr[0], float(pr[1])) for pr in _first_probes(spec, n)],
         probe_list=[[(m, float(iv)) for m, iv in prs] for prs in _probe_lists(spec, n)],       # every probe of a chain, in order
         # Simulation.schedule(): (chain, time ns) in the caller's construction order; a chain with rate 0 has no Source
-        schedule=[(int(c), ns_from_seconds(float(t))) for c, t in (spec.get("schedule") or [])],
+        schedule=[(int(c), spec_ns(spec, float(t))) for c, t in (spec.get("schedule") or [])],
         no_source=[float(r) == 0.0 and pr is None
                    for r, pr in zip(per_chain(spec["rate"], n), spec.get("profile") or [None] * n)],
         # several Sources feeding one Server: per chain [(arrival kind, rate)] of the further ones
@@ -233,7 +243,7 @@ def run_oracle_for_spec(spec, trace_cap=0):
         groups = [([i], spec["seed"] + i, [0]) for i in range(n)]
     for chain_ids, seed, bases in groups:
         g, nodes = oracle_graph_for(spec, chain_ids, bases)
-        r = O.run(g, p["end_ns"], seed=seed, rng_mode=rng, mt_seed_py=seed & 0xFFFFFFFF,
+        r = O.run(g, p["end_ns"], start_ns=p["start_ns"], seed=seed, rng_mode=rng, mt_seed_py=seed & 0xFFFFFFFF,
                   mt_seed_np=seed & 0xFFFFFFFF, trace_cap=trace_cap,
                   schedule=[(nodes[c][1], t) for c, t in p["schedule"] if c in nodes])
         r.probe_nodes, r.probe_nodes_all, r.xsrc_nodes = g.probe_nodes, g.probe_nodes_all, g.xsrc_nodes
@@ -246,7 +256,8 @@ def ring_params(spec):
     return dict(
         n=n, ext_rate=[float(r) for r in per_chain(spec["ext_rate"], n)], mean=float(spec["mean"]),
         conc=int(spec.get("concurrency", 1)), qcap=-1 if spec.get("queue_cap") is None else int(spec["queue_cap"]),
-        lat_min=float(spec["lat_min"]), jitter_mean=spec.get("jitter_mean"), end_ns=ns_from_seconds(spec["end_s"]),
+        lat_min=float(spec["lat_min"]), jitter_mean=spec.get("jitter_mean"), start_ns=spec_start_ns(spec),
+        end_ns=spec_ns(spec, spec["end_s"]),
         # per link: (kind, mean) with kind "exp" | "const" | None -- spec["jitter_kind"] (default "exp") and spec["jitter_mean"] may be lists
         jitter=[(None, 0.0) if (m is None or k is None) else (k, float(m))
                 for k, m in zip(per_chain(spec.get("jitter_kind", "exp"), n), per_chain(spec.get("jitter_mean"), n))],
@@ -254,7 +265,7 @@ def ring_params(spec):
         probes=[None if pr is None else (pr[0], float(pr[1])) for pr in _first_probes(spec, n)],
         probe_list=[[(m, float(iv)) for m, iv in prs] for prs in _probe_lists(spec, n)],
         profile=[None if pr is None else tuple(pr) for pr in (spec.get("profile") or [None] * n)],
-        schedule=[(int(c), ns_from_seconds(float(t))) for c, t in (spec.get("schedule") or [])])
+        schedule=[(int(c), spec_ns(spec, float(t))) for c, t in (spec.get("schedule") or [])])
 
 
 def ring_source_plan(spec):
@@ -358,7 +369,7 @@ def oracle_graph(spec):
 
 def oracle_graph_schedule(spec, nodes):
     """spec["schedule"] = [[[kind, index], seconds], ...] -> hso_schedule's (node, ns) list, in call order."""
-    return [(nodes[ref[0]][ref[1]], ns_from_seconds(t)) for ref, t in spec.get("schedule") or []]
+    return [(nodes[ref[0]][ref[1]], spec_ns(spec, t)) for ref, t in spec.get("schedule") or []]
 
 
 def lb_params(spec):
@@ -368,8 +379,8 @@ def lb_params(spec):
         conc=[int(c) for c in per_chain(spec.get("concurrency", 1), B)],
         qcap=[-1 if q is None else int(q) for q in per_chain(spec.get("queue_cap"), B)],
         vnodes=int(spec["vnodes"]), n_clients=int(spec["n_clients"]),
-        stop_ns=-1 if spec.get("stop_after_s") is None else ns_from_seconds(spec["stop_after_s"]),
-        shared_sink=bool(spec.get("shared_sink", True)), end_ns=ns_from_seconds(spec["end_s"]),
+        stop_ns=-1 if spec.get("stop_after_s") is None else spec_ns(spec, spec["stop_after_s"]),
+        shared_sink=bool(spec.get("shared_sink", True)), start_ns=spec_start_ns(spec), end_ns=spec_ns(spec, spec["end_s"]),
         strategy=spec.get("strategy", "chash"))
 
 
@@ -416,7 +427,7 @@ def sched_arrays(n, schedule, per_station=False):
 # HIP engine side (GPU tests only)
 # ----------------------------------------------------------------------------------------------
 def engine_for_spec(spec, log_capacity=0, horizon_ns=None, flags=0):
-    """Build a StationEngine for a golden spec (all chains resident, one LP per chain)."""
+    """Build a StationEngine for a golden spec (all chains resident, one LP per chain), from the spec's start (spec_start_ns)."""
     from happy_simulator_amd import _native as N
     from happy_simulator_amd.engine import StationArrays, StationEngine
 
@@ -468,7 +479,8 @@ def engine_for_spec(spec, log_capacity=0, horizon_ns=None, flags=0):
         seed = 0
         st.seed = np.array([spec["seed"] + i for i in range(n)], np.uint64)
         st.stream_base = np.zeros(n, np.uint64)
-    eng = StationEngine(st, mode=mode, horizon_ns=horizon_ns or p["end_ns"], seed=seed, log_capacity=log_capacity)
+    eng = StationEngine(st, mode=mode, horizon_ns=horizon_ns or p["end_ns"], seed=seed, log_capacity=log_capacity,
+                        start_ns=p["start_ns"])
     if flags:
         eng.set_debug_flags(flags)
     return eng, p
@@ -569,7 +581,7 @@ def ring_arrays(spec, bag_capacity=0, log_capacity=0):
         bag_capacity=bag_capacity,
     )
     # external rate 4/s + forwarded 4/s per station: size the logs for the total admission rate
-    horizon_s = p["end_ns"] / 1e9
+    horizon_s = (p["end_ns"] - p["start_ns"]) / 1e9
     lam = 2.0 * float(max(rates.max(), (st.src_rate * (st.src_kind != N.SRC_NONE)).max())) + 1.0   # (src_rate: a profile's peak)
     cap = log_capacity or int(lam * horizon_s + 10 * (lam * horizon_s) ** 0.5 + 64)
     return st, net, cap, p
@@ -581,7 +593,8 @@ def ring_engine_for_spec(spec, flags=0, bag_capacity=0, log_capacity=0):
     from happy_simulator_amd.engine import StationEngine
 
     st, net, cap, p = ring_arrays(spec, bag_capacity, log_capacity)
-    eng = StationEngine(st, mode=N.MODE_SINGLE, horizon_ns=p["end_ns"], seed=spec["seed"], log_capacity=cap, network=net)
+    eng = StationEngine(st, mode=N.MODE_SINGLE, horizon_ns=p["end_ns"], start_ns=p["start_ns"], seed=spec["seed"], log_capacity=cap,
+                        network=net)
     if flags:
         eng.set_debug_flags(flags)
     return eng, p
@@ -613,7 +626,7 @@ def lb_engine_for_spec(spec, flags=0, tick_capacity=0):
         svc_kind=np.array([N.LAT_EXPONENTIAL if k == "exp" else N.LAT_CONSTANT for k in per_chain(svc, B)], np.uint8),
         svc_mean_s=np.array(p["mean"], np.float64), queue_cap=np.array(p["qcap"], np.int64),
         egress=np.full(B, N.EGRESS_SINK, np.uint8))
-    eng = LoadBalancerEngine(src, be, virtual_nodes=p["vnodes"], horizon_ns=p["end_ns"], shared_sink=p["shared_sink"],
+    eng = LoadBalancerEngine(src, be, virtual_nodes=p["vnodes"], horizon_ns=p["end_ns"], start_ns=p["start_ns"], shared_sink=p["shared_sink"],
                              seed=spec["seed"], tick_capacity=tick_capacity,
                              strategy={"chash": N.LB_CONSISTENT_HASH, "round_robin": N.LB_ROUND_ROBIN, "random": N.LB_RANDOM}[p["strategy"]])
     if flags:

@@ -135,6 +135,12 @@ class _Recorded:
         """Write every result recorded in this session, merged over the stored ones, into files of at most PART_BYTES."""
         if not self._fresh:
             return
+        stored = self._store()
+        if not any(key in stored for key in self._fresh):
+            # only new results: new part files behind the stored ones, which stay byte for byte as they are
+            n0 = len(glob.glob(os.path.join(REC_DIR, "*.npz")))
+            self._write_parts(self._fresh, n0)
+            return
         cases = {}
         for key, (skeleton, arrays) in self._store().items():
             cases[key] = (skeleton, arrays)
@@ -142,7 +148,13 @@ class _Recorded:
         os.makedirs(REC_DIR, exist_ok=True)
         for path in glob.glob(os.path.join(REC_DIR, "*.npz")):
             os.remove(path)
-        part, index, size, n = {}, {}, 0, 0
+        self._write_parts(cases, 0)
+
+    @staticmethod
+    def _write_parts(cases, first):
+        """cases -> part_<first>.npz, part_<first + 1>.npz, ... of at most PART_BYTES each."""
+        os.makedirs(REC_DIR, exist_ok=True)
+        part, index, size, n = {}, {}, 0, first
 
         def flush():
             nonlocal part, index, size, n

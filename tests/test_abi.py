@@ -32,6 +32,19 @@ def test_header_symbols_are_exported(lib):
     assert set(N.EXPORTED_SYMBOLS) <= declared
 
 
+def test_run_path_bits_match_the_header(lib):
+    """hs_engine_run_path / hs_lb_run_path (the path a run took, for tests that target one side of a gate) and hs_debug_time_ops are
+    exported, and the bit constants of _native are the header's."""
+    for sym in ("hs_engine_run_path", "hs_lb_run_path", "hs_debug_time_ops"):
+        assert sym in N.EXPORTED_SYMBOLS and hasattr(lib, sym)
+    hdr = open(os.path.join(ROOT, "include", "hs_engine.h")).read()
+    bits = {m: 1 << int(v) for m, v in re.findall(r"^#define (HS_(?:LB_)?RUN_[A-Z0-9_]+)\s+\(1 << (\d+)\)", hdr, re.M)}
+    assert len(bits) == 17
+    for name, v in bits.items():
+        assert getattr(N, name[3:]) == v, name
+    assert lib.hs_engine_run_path(None) == 0 and lib.hs_lb_run_path(None) == 0
+
+
 def test_abi_version_and_struct_sizes(lib):
     assert lib.hs_abi_version() == N.ABI_VERSION == 16
     assert C.sizeof(N.Config) == 56

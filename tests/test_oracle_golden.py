@@ -28,7 +28,7 @@ def check_oracle_against_station_golden(gold):
     assert [r.final_time_ns for _, _, r in runs] == gold.meta["final_ns"]
     for (chain_ids, nodes, r), dur in zip(runs, gold.meta["duration_s"]):
         # duration_s = (t_last - t_start).to_seconds()  (core/simulation.py:546)
-        assert float(r.final_time_ns) / 1e9 == dur
+        assert float(r.final_time_ns - H.spec_start_ns(spec)) / 1e9 == dur
         for c in chain_ids:
             src, srv, snk = nodes[c]
             assert (r.generated[src] if src >= 0 else 0) == gold.generated[c]
@@ -101,7 +101,8 @@ def check_oracle_against_graph_golden(gold):
     Sink record (time and latency), bit for bit."""
     spec = gold.spec
     g, nodes = H.oracle_graph(spec)
-    r = O.run(g, H.ns_from_seconds(spec["end_s"]), seed=spec["seed"], schedule=H.oracle_graph_schedule(spec, nodes))
+    r = O.run(g, H.spec_ns(spec, spec["end_s"]), start_ns=H.spec_start_ns(spec), seed=spec["seed"],
+              schedule=H.oracle_graph_schedule(spec, nodes))
     assert [r.events_processed] == gold.meta["total_events"]
     assert [r.final_time_ns] == gold.meta["final_ns"]
     np.testing.assert_array_equal(r.generated[nodes["source"]], gold.generated)
@@ -130,7 +131,7 @@ def check_oracle_against_ring_golden(gold):
     spec = gold.spec
     want_trace = "trace" in gold.arrays
     g, nodes = H.oracle_ring_graph(spec)
-    r = O.run(g, H.ns_from_seconds(spec["end_s"]), seed=spec["seed"],
+    r = O.run(g, H.spec_ns(spec, spec["end_s"]), start_ns=H.spec_start_ns(spec), seed=spec["seed"],
               trace_cap=(len(gold.trace) + 16) if want_trace else 0,
               schedule=[(nodes[c]["srv"], t) for c, t in H.ring_params(spec)["schedule"]])
     assert [r.events_processed] == gold.meta["total_events"]
@@ -187,7 +188,7 @@ def check_oracle_against_lb_golden(gold):
     g, p = H.oracle_lb_graph(spec)
     S, B = p["S"], p["B"]
     chash = spec.get("strategy", "chash") == "chash"          # (RoundRobin / Random: no ring to compare)
-    r = O.run(g, p["end_ns"], seed=spec["seed"], trace_cap=(len(gold.trace) + 16) if want_trace else 0,
+    r = O.run(g, p["end_ns"], start_ns=p["start_ns"], seed=spec["seed"], trace_cap=(len(gold.trace) + 16) if want_trace else 0,
               lb_probe=len(gold.client_backend) if chash else 0)
     assert [r.events_processed] == gold.meta["total_events"]
     assert [r.final_time_ns] == gold.meta["final_ns"]

@@ -352,3 +352,64 @@ def test_the_reference_in_windows_equals_the_reference_in_one_run(kind, k):
     assert meta1["total_events"] == meta2["total_events"] and meta1["final_ns"] == meta2["final_ns"]
     assert sum(meta1["total_events"]) > 20
     _same_results(one, win, f"{kind} {k}")
+
+
+# ---- the same configurations far from the epoch: Simulation(start_time=Instant(ns)) with an integer start ------------------------
+# The engines choose their exact arithmetic by absolute time (tests/test_gpu_time_range.py runs them against the oracle at these
+# offsets); here the oracle is held to the reference at the same offsets: 2^39 (the wavefront kernel's bound), 2^51 (binary64 whole
+# ns) and 2^53 + 1 (float(ns) rounds).  Every absolute time of a spec -- the end, stop_after, window ends, scheduled Requests -- moves
+# with the start; profiles keep their absolute definition, as in the reference.  A negative start: the reference accepts it, the
+# oracle and the engines refuse it by name (test_a_negative_start_is_refused_by_the_oracle).
+START_OFFSETS = pytest.mark.parametrize("start_ns", [1 << 39, 1 << 51, (1 << 53) + 1], ids=["2^39", "2^51", "2^53+1"])
+
+
+def test_a_negative_start_is_refused_by_the_oracle():
+    from oracle import hs_oracle as O
+
+    out, meta = REF.run_case(dict(_station_spec(0), start_ns=-(1 << 31) - 7))     # the reference runs it ...
+    assert sum(meta["total_events"]) > 0
+    with pytest.raises(ValueError, match="start_time"):                          # ... the oracle does not guess
+        H.run_oracle_for_spec(dict(_station_spec(0), start_ns=-(1 << 31) - 7))
+
+
+@START_OFFSETS
+@pytest.mark.parametrize("k", [0, 3])
+def test_oracle_equals_live_reference_on_station_specs_at_an_offset(k, start_ns):
+    spec = dict(_station_spec(k), start_ns=start_ns)
+    spec["trace"] = spec["mode"] != "replicas" and spec.get("trace", False)
+    out, meta = REF.run_case(spec)
+    gold = H.Golden.from_results(out, meta)
+    assert sum(gold.meta["total_events"]) > 0
+    assert min(gold.meta["final_ns"]) > start_ns
+    check_oracle_against_station_golden(gold)
+
+
+@START_OFFSETS
+@pytest.mark.parametrize("k", [1])
+def test_oracle_equals_live_reference_on_ring_specs_at_an_offset(k, start_ns):
+    spec = dict(_ring_spec(k), start_ns=start_ns)
+    out, meta = REF.run_ring_case(spec)
+    gold = H.Golden.from_results(out, meta)
+    assert gold.meta["total_events"][0] > 100 and gold.meta["final_ns"][0] > start_ns
+    check_oracle_against_ring_golden(gold)
+
+
+@START_OFFSETS
+@pytest.mark.parametrize("make,k", [(_lb_spec, 2), (lb_profile_spec, 1), (lb_probe_spec, 0), (lb_strategy_spec, 1)],
+                         ids=["lb", "profile", "probes", "strategy"])
+def test_oracle_equals_live_reference_on_load_balancers_at_an_offset(make, k, start_ns):
+    spec = dict(make(k), start_ns=start_ns)
+    out, meta = REF.run_lb_case(spec)
+    gold = H.Golden.from_results(out, meta)
+    assert gold.meta["total_events"][0] > 50 and gold.meta["final_ns"][0] > start_ns
+    check_oracle_against_lb_golden(gold)
+
+
+@START_OFFSETS
+@pytest.mark.parametrize("make,k", [(graph_spec, 0), (lb_graph_spec, 0)], ids=["graph", "lb_graph"])
+def test_oracle_equals_live_reference_on_graphs_at_an_offset(make, k, start_ns):
+    spec = dict(make(k), start_ns=start_ns)
+    out, meta = REF.run_graph_case(spec)
+    gold = H.Golden.from_results(out, meta)
+    assert gold.meta["total_events"][0] > 50 and gold.meta["final_ns"][0] > start_ns
+    check_oracle_against_graph_golden(gold)
