@@ -26,6 +26,7 @@ constexpr int64_t kInfNs = INT64_MAX;  // Instant.Infinity (core/temporal.py:298
 // engines refuse such a configuration by name before any launch: the station, network and load-balancer engines at construction,
 // the graph engine (whose end comes with each run) before the run's first launch.  (2^63 = 9.22e18 ns, less the sum's rounding.)
 constexpr double kMaxReachNs = 9.0e18;
+constexpr double kLongestExpDraw = 36.8;   // the longest exponential draw, in means: -log(2^-53) = 36.7 (the messages say "36.8")
 inline bool reach_fits_int64(int64_t horizon_ns, double step_s) { return (double)horizon_ns + step_s * 1e9 < kMaxReachNs; }
 
 enum StreamKind : uint32_t { kStreamArrival = 0, kStreamService = 1, kStreamLink = 2, kStreamRoute = 3, kStreamKey = 4, kStreamLoss = 5 };

@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,12 +20,12 @@
 #define HS_KERNELS_MAIN
 #include "hs_kernels.hpp"
 #include "hs_tables_api.hpp"
+#include "hs_host.hpp"
+#include "hs_plan.hpp"
 
 // =============================================================================================
 // host side
 // =============================================================================================
-static thread_local std::string g_global_error;
-
 struct hs_engine {
     bool pending_async = false;   // hs_engine_run_until_async enqueued a run whose results hs_engine_synchronize has not finalised yet
 
@@ -52,6 +51,7 @@ struct hs_engine {
     bool net_on_heap = false;     // ... a network that moved there behind an undecided election (tandem_fallback); hs_engine_reset moves it back
     std::vector<int32_t> h_src_lp;     // the Sources in `sources=[...]` order (hs_engine_set_stations), kept for setup_exact_plain
     std::vector<uint8_t> h_src_slot;
+    std::vector<uint64_t> h_stream_base;   // the stations' effective stream_base (hs_engine_set_network: the default of routers and links)
     bool tandem_fan_in = false;   // some Server is the downstream of several Servers: no passes, the single heap from the start
     bool exact_prologue = false;   // the prologue takes part in ordinary runs (pre-run events whose indices run-time events can pass)
     // ... but only where a pre-run event shares its nanosecond with another event of its LP, or while the run has created fewer
@@ -153,37 +153,6 @@ struct hs_engine {
 
 namespace {
 
-int fail(hs_engine *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->error = buf;
-    g_global_error = buf;
-    return code;
-}
-
-#define HS_HIP(h, expr)                                                                                \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(h, HS_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
-
-template <typename T>
-int dev_alloc(hs_engine *h, T **p, size_t count) {
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(T) ? count * sizeof(T) : sizeof(T));
-    if (e != hipSuccess) return fail(h, HS_E_HIP, "hipMalloc(%zu B): %s", count * sizeof(T), hipGetErrorString(e));
-    h->allocs.push_back(q);
-    *p = (T *)q;
-    // debug: HS_POISON_ALLOC=<byte> fills every device allocation with that byte -- nothing may depend on what hipMalloc hands out
-    // (memory of an engine destroyed earlier in the process): tests/test_gpu_sharded.py::test_nothing_depends_on_what_the_allocator_hands_out
-    static const char *poison = getenv("HS_POISON_ALLOC");
-    if (poison && *poison) (void)hipMemset(q, (int)strtol(poison, nullptr, 0) & 0xff, count * sizeof(T) ? count * sizeof(T) : sizeof(T));
-    return HS_OK;
-}
-
 // Uncached device memory (hipExtMallocWithFlags(hipDeviceMallocUncached): the buffers other ranks' kernels write into while this
 // rank's kernel runs) comes from a process-wide pool and is never handed back to the runtime while the process lives.  Measured
 // (round 6, tests/test_gpu_sharded.py in one process): after ~50 engines that each freed five such buffers, ordinary hipMalloc'ed
@@ -219,19 +188,6 @@ void uncached_release(hs_engine *h) {
     std::lock_guard<std::mutex> g(P.m);
     for (auto &b : h->uncached) P.idle.emplace(b.second, b.first);
     h->uncached.clear();
-}
-
-template <typename T>
-int upload(hs_engine *h, const T **dst, const T *src, size_t n, T dflt) {
-    T *d = nullptr;
-    int rc = dev_alloc(h, &d, n);
-    if (rc) return rc;
-    std::vector<T> tmp;
-    if (!src) { tmp.assign(n, dflt); src = tmp.data(); }
-    hipError_t e = hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(h, HS_E_HIP, "hipMemcpy H2D: %s", hipGetErrorString(e));
-    *dst = d;
-    return HS_OK;
 }
 
 template <int C>
@@ -638,6 +594,250 @@ int ipc_set_peers(hs_engine *h, const std::vector<int64_t *> &pin, const std::ve
 
 }  // namespace
 
+// =============================================================================================
+// set-up: plan_stations / plan_network (hs_plan.hpp) decide, these two allocate and upload what was decided
+// =============================================================================================
+namespace {
+
+template <typename T>
+int upload_vec(hs_engine *h, const T **dst, const std::vector<T> &v) { return upload<T>(h, dst, v.data(), v.size(), T{}); }
+template <typename T>
+int upload_col(hs_engine *h, const T **dst, const Col<T> &c) { return upload<T>(h, dst, c.p, (size_t)h->cfg.n_lp, c.dflt); }
+// (inside the apply functions: `h`, the plan `p` and `int rc` are in scope)
+#define DA(ptr, count) if ((rc = dev_alloc(h, &(ptr), count))) return rc
+#define UPV(dst, vec) if ((rc = upload_vec(h, &(dst), p.vec))) return rc
+#define UPC(dst, col) if ((rc = upload_col(h, &(dst), p.col))) return rc
+template <typename T>
+int alloc_zeroed(hs_engine *h, T **p, size_t count) {
+    const int rc = dev_alloc(h, p, count);
+    if (rc) return rc;
+    HS_HIP(h, hipMemset(*p, 0, (count ? count : 1) * sizeof(T)));     // (dev_alloc hands out at least one element)
+    return HS_OK;
+}
+
+// the buffers of the prologue / the single heap (hs_exact.hpp XState), sized by the plan
+int alloc_xstate(hs_engine *h, const StationPlan &p) {
+    const size_t n = (size_t)h->cfg.n_lp;
+    int rc;
+    h->xs_host = p.xs;
+    DA(h->xs_host.heap, p.xs_heap); DA(h->xs_host.qhead, n); DA(h->xs_host.qtail, n);
+    DA(h->xs_host.pnext, p.xs_pool); DA(h->xs_host.pidx, p.xs_pool); DA(h->xs_host.init_t, p.xs_init);
+    return dev_alloc(h, &h->xs, p.xs_count);
+}
+
+// the tick tables and the arrays that travel with them (hs_tables.hpp TickTables)
+int apply_tick_tables(hs_engine *h, const StationPlan &p) {
+    const size_t n = (size_t)h->cfg.n_lp, cap = (size_t)p.log_cap;
+    int rc;
+    if (!p.rows.empty()) {
+        DA(h->tab_rows, p.rows.size());
+        HS_HIP(h, hipMemcpy(h->tab_rows, p.rows.data(), p.rows.size() * sizeof(TickRow), hipMemcpyHostToDevice));
+        DA(h->tab_times, p.rows.size() * (size_t)p.tab_cap); DA(h->tab_count, p.rows.size());
+        if ((rc = alloc_zeroed(h, &h->tab_status, 2))) return rc;
+    }
+    TickTables tt{};
+    tt.times = h->tab_times; tt.cap = p.tab_cap; tt.t_start = h->cfg.start_ns;
+    if (!p.tandem.empty()) {                                      // tandem queues: hs_tables.hpp TickTables::tandem
+        UPV(tt.tandem, tandem);
+        if ((rc = alloc_zeroed(h, &tt.inj_i, (size_t)kMaxUp * n))) return rc;
+        for (int64_t **col : {&tt.fw_rc, &tt.fw_rrc, &tt.fw_rdr, &tt.fw_dep}) DA(*col, n * cap);
+        for (int64_t **col : {&tt.q_rrc, &tt.q_rdr, &tt.q_pay}) DA(*col, n * (size_t)kQCap);
+    }
+    if (p.cand_key && (rc = alloc_zeroed(h, &tt.cand_key, n * 4))) return rc;
+    tt.standin_sched = p.standin_sched ? 1 : 0;
+    if (p.lineage_src) {
+        DA(tt.rs_dep, n * (size_t)p.C); DA(tt.rs_q, n * (size_t)kQCap);
+        HS_HIP(h, hipMemset(tt.rs_dep, 0xff, n * (size_t)p.C));
+        HS_HIP(h, hipMemset(tt.rs_q, 0xff, n * (size_t)kQCap));
+    }
+    UPV(tt.src_row, src_row); UPV(tt.probe_row, probe_row);
+    return upload<TickTables>(h, &h->P.tabs, &tt, 1, TickTables{});
+}
+
+// the pre-run events in construction order and the prologue's state (hs_exact.hpp XInit / XState)
+int apply_prologue(hs_engine *h, const StationPlan &p) {
+    int rc;
+    if (p.XI.per_lp) {
+        UPV(h->XI.lp_src_slots, lp_src_slots); UPV(h->XI.sched_rank, sched_rank); UPV(h->XI.sched_entry, sched_entry);
+    } else {
+        UPV(h->XI.sched_rank, sched_rank); UPV(h->XI.src_lp, src_lp); UPV(h->XI.src_slot, src_slot); UPV(h->XI.probe_lp, probe_lp);
+        UPV(h->XI.probe_slot, probe_slot); UPV(h->XI.sched_lp, sched_lp); UPV(h->XI.sched_entry, sched_entry);
+    }
+    if ((rc = alloc_zeroed(h, &h->XI.sched_idx, (size_t)p.n_sched))) return rc;
+    h->P.sched_idx = h->XI.sched_idx;
+    return alloc_xstate(h, p);
+}
+
+int apply_stations(hs_engine *h, const StationPlan &p) {
+    const int n = h->cfg.n_lp;
+    // ---- the plan's facts
+    h->any_xsrc = p.any_xsrc; h->uni_stations = p.uni_stations; h->uni_grid = p.uni_grid; h->f64_times = p.f64_times;
+    h->any_profile = p.any_profile; h->any_timevarying = p.any_timevarying; h->any_sched = p.any_sched; h->any_probe = p.any_probe;
+    h->n_pass = p.n_pass; h->tandem_fan_in = p.tandem_fan_in; h->n_probe_slots = p.n_probe_slots; h->C = p.C;
+    h->exact = p.exact; h->exact_prologue = p.exact_prologue; h->exact_only = p.exact_only; h->lazy_prologue = p.lazy_prologue;
+    h->n_init = p.n_init; h->XI = p.XI;
+    h->L.cap = p.log_cap; h->L.pcap = p.probe_cap; h->tab_cap = p.tab_cap; h->n_tab_rows = (int)p.rows.size();
+    h->h_src_lp = p.src_lp; h->h_src_slot = p.src_slot;      // (setup_exact_plain: the single-heap machinery built on demand)
+    h->h_stream_base = p.stream_base;                        // (hs_engine_set_network: the routers' and links' default streams)
+    // ---- the stations' columns
+    int rc;
+    UPC(h->P.src_kind, cols.src_kind); UPC(h->P.src_rate, cols.src_rate); UPC(h->P.src_stop, cols.src_stop); UPC(h->P.conc, cols.conc);
+    UPC(h->P.svc_kind, cols.svc_kind); UPC(h->P.svc_mean, cols.svc_mean); UPC(h->P.qcap, cols.qcap); UPC(h->P.egress, cols.egress);
+    UPC(h->P.seed, cols.seed); UPV(h->P.stream_base, stream_base);
+    UPV(h->P.prof_kind, prof_kind); UPV(h->P.prof_p, prof_p); UPV(h->P.probe_metric, probe_metric); UPV(h->P.probe_rate, probe_rate);
+    h->P.tabs = nullptr;
+    if (p.want_tabs && (rc = apply_tick_tables(h, p))) return rc;
+    h->P.xsrc_kind = nullptr; h->P.xsrc_rate = nullptr; h->P.xsrc_stop = nullptr;
+    if (p.any_xsrc) { UPV(h->P.xsrc_kind, xsrc_kind); UPV(h->P.xsrc_rate, xsrc_rate); UPV(h->P.xsrc_stop, xsrc_stop); }
+    h->P.sched_off = nullptr; h->P.sched_t = nullptr;
+    if (p.n_sched > 0) {
+        if ((rc = upload<int64_t>(h, &h->P.sched_off, p.sched_off, (size_t)n + 1, 0))) return rc;
+        if ((rc = upload<int64_t>(h, &h->P.sched_t, p.sched_time_ns, (size_t)p.n_sched, 0))) return rc;
+    }
+    h->P.tie_rank = nullptr;
+    if (!p.tie_rank.empty()) UPV(h->P.tie_rank, tie_rank);
+    h->P.sched_idx = nullptr;
+    if (p.exact && (rc = apply_prologue(h, p))) return rc;
+    // ---- the stations' state, the logs, the totals
+    const size_t N = (size_t)n, NC = (size_t)n * (size_t)h->C, cap = (size_t)p.log_cap;
+#define AL(field, count) DA(h->X.field, count)
+    AL(A, N); AL(seqA, N); AL(crtA, N); AL(arr_k, N); AL(arr_time, N); AL(svc_k, N);
+    AL(D, NC); AL(seqD, NC); AL(crtD, NC); AL(svc_s, NC); AL(crt, NC);
+    AL(seq, N); AL(buf, N); AL(active, N);
+    AL(generated, N); AL(accepted, N); AL(dropped, N); AL(completed, N); AL(rejected, N); AL(started, N);
+    AL(received, N); AL(sink_w, N); AL(total_service, N); AL(q, N); AL(grp_time, N); AL(last_time, N);
+    AL(events, N); AL(ev_kind, N * 11);
+    AL(dpA, N); AL(rcA, N); AL(dpD, NC); AL(rcD, NC); AL(wkD, NC); AL(qdep, N * kQCap); AL(qrc, N * kQCap);   // lineage (hs_station.hpp)
+    if (h->any_profile) {      // the general-path instantiation of the run kernel loads / stores the probe state of every LP
+        AL(PA, N * kMaxProbes); AL(seqP, N * kMaxProbes); AL(crtP, N * kMaxProbes); AL(p_arr, N * kMaxProbes);
+        AL(p_n, N * kMaxProbes); AL(ev_probe, N * 2); AL(sched_i, N); AL(rcP, N * kMaxProbes);
+    }
+    if (h->any_xsrc) {
+        AL(XA, N * kMaxXSrc); AL(crtX, N * kMaxXSrc); AL(x_arr, N * kMaxXSrc); AL(x_n, N * kMaxXSrc); AL(seqX, N * kMaxXSrc);
+        AL(x_k, N * kMaxXSrc); AL(dpX, N * kMaxXSrc); AL(rcX, N * kMaxXSrc);
+    }
+#undef AL
+    if (h->any_probe) {
+        DA(h->L.probe_t, N * (size_t)h->L.pcap * (size_t)h->n_probe_slots); DA(h->L.probe_v, N * (size_t)h->L.pcap * (size_t)h->n_probe_slots);
+    }
+    DA(h->L.adm, N * cap); DA(h->L.sink_t, N * cap);
+    if (h->C > 1) DA(h->L.sink_created_own, N * cap);   // explicit created_at column: completions leave in a different order than admissions
+    h->L.sink_created = (h->C > 1) ? h->L.sink_created_own : h->L.adm;
+    if ((rc = alloc_zeroed(h, &h->tot, 1))) return rc;
+    DA(h->cands, std::max<size_t>((size_t)h->n_blocks, (size_t)(n + 1) / 2));   // (the wide kernel: one per >= 2 LPs)
+    if (p.wide) {
+        if ((rc = alloc_zeroed(h, &h->wide_ctl, 1))) return rc;
+        DA(h->wide_bail, (size_t)n); DA(h->wave_parts, ((size_t)n + 7) / 8);
+    }
+    // (the uploads and fills above went through the NULL stream; the engine's launches use a non-blocking stream, which does not
+    //  wait for it: everything is in place before the caller can enqueue a run)
+    HS_HIP(h, hipDeviceSynchronize());
+    h->have_stations = true;
+    return HS_OK;
+}
+
+// the link queues of hs_net_async and what goes with them
+int apply_link_queues(hs_engine *h, const NetworkPlan &p) {
+    const size_t n = (size_t)h->cfg.n_lp, NL = p.NL, NQ = NL * (size_t)p.aq_cap;
+    int rc;
+#define ALN(field, count) DA(h->NX.field, count)
+    if (p.global) {
+        // a shard: the link queues other ranks may write into while this rank's kernel runs (LIVE exchange) -- uncached device
+        // memory, exportable with hipIpcGetMemHandle: a peer's stores arrive in HBM past this device's L2
+        void *a = nullptr, *b = nullptr, *c = nullptr;
+        if ((rc = uncached_alloc(h, &a, NQ * 4 * sizeof(int64_t)))) return rc;
+        if ((rc = uncached_alloc(h, &b, NL * sizeof(unsigned long long)))) return rc;
+        if ((rc = uncached_alloc(h, &c, NL * sizeof(int64_t)))) return rc;
+        h->NX.aq_rec = (int64_t *)a; h->NX.aq_head = (unsigned long long *)b; h->NX.aq_ea = (int64_t *)c;
+        HS_HIP(h, hipMemset(a, 0, NQ * 4 * sizeof(int64_t)));
+        HS_HIP(h, hipMemset(b, 0, NL * sizeof(unsigned long long)));
+        HS_HIP(h, hipMemset(c, 0, NL * sizeof(int64_t)));
+        ALN(aq_tail, NL);
+    } else {
+        ALN(aq_rec, NQ * 4); ALN(aq_tail, NL); ALN(aq_head, NL); ALN(aq_ea, NL);
+    }
+    ALN(early_upto, n); ALN(d_pre, n);
+#undef ALN
+    return HS_OK;
+}
+
+#ifndef HS_NO_LOSS_TABLES
+// table-decided losses (hs_network.link_drop_capacity): the bit tables, all clear, and the send log
+int apply_loss_tables(hs_engine *h, const NetworkPlan &p) {
+    int rc;
+    LossTables lt{};
+    uint32_t *bits = nullptr;
+    UPV(lt.drop_off, drop_off);
+    if ((rc = alloc_zeroed(h, &bits, (size_t)(p.drop_total / 32)))) return rc;
+    lt.drop_bits = bits;
+    h->drop_bits_dev = bits;
+    DA(lt.send_log, (size_t)p.drop_total * 3);
+    if ((rc = alloc_zeroed(h, &lt.send_log_n, 1))) return rc;
+    lt.send_log_cap = p.drop_total;
+    lt.overflow_word = &h->tot->overflow;
+    h->loss_host = lt;
+    return upload<LossTables>(h, &h->NP.loss_tables, &lt, 1, lt);
+}
+#endif
+
+int apply_network(hs_engine *h, const NetworkPlan &p) {
+    const int n = h->cfg.n_lp;
+    // ---- the plan's facts
+    h->window_ns = p.window_ns;
+    h->drop_off_host = p.drop_off;
+    h->net_global = p.global; h->n_global_lp = (int32_t)p.n_all; h->n_gid = p.n_gid;
+    h->SC = ShardCtl{};
+    h->SC.lp_base = p.lo;
+    h->h_link_dst = p.link_dst; h->h_link_src = p.link_src; h->h_gid2local = p.gid2local;
+    h->async_ok = p.async_ok; h->net_pf = p.net_pf; h->net_uni = p.net_uni;
+    h->NP.n_links = p.nl;
+    h->NX.bag_cap = p.bag_cap; h->NX.aq_cap = p.aq_cap; h->NX.aq_on = 0; h->NX.pk_base = h->cfg.start_ns;
+    // ---- routers and links
+    int rc;
+    UPC(h->NP.egress, egress); UPV(h->NP.rt0, rt0); UPV(h->NP.rt1, rt1); UPV(h->NP.rt2, rt2); UPV(h->NP.rt3, rt3); UPV(h->NP.rt_cnt, rt_cnt);
+    UPV(h->NP.link_of, link_of); UPV(h->NP.route_base, route_base);
+    UPV(h->NP.link_dst, link_dst); UPV(h->NP.link_lat_min, lat_min); UPV(h->NP.link_jit_kind, jit_kind); UPV(h->NP.link_jit_mean, jit_mean);
+    UPV(h->NP.link_base, link_base);
+#ifndef HS_NO_LOSS_TABLES    // (scratch build: plan_network has refused a network that needs them)
+    h->NP.loss_tables = nullptr;
+    if (p.drop_total > 0 && (rc = apply_loss_tables(h, p))) return rc;
+#endif
+    UPV(h->NP.link_loss, loss); UPV(h->NP.in_off, in_off); UPV(h->NP.in_links, in_links); UPV(h->NP.link_lat_ns, lat_ns);
+    h->NP.link_gid = nullptr;
+    if (p.have_gid) {
+        const int32_t *g2l_dev = nullptr;
+        UPV(h->NP.link_gid, gid); UPV(g2l_dev, gid2local);
+        h->gid2local = const_cast<int32_t *>(g2l_dev);
+    }
+    // ---- the network's state
+    const size_t N = (size_t)n, NL = p.NL, NB = (size_t)n * (size_t)p.bag_cap;
+#define ALN(field, count) DA(h->NX.field, count)
+    ALN(route_k, N); ALN(routed, N); ALN(link_k, NL); ALN(link_in, NL); ALN(link_sent, NL); ALN(link_packets, NL); ALN(next_time, N);
+    ALN(pend_pay, N);
+    ALN(bag_cnt, N); ALN(bag_t, NB); ALN(bag_ts, NB); ALN(bag_cr, NB); ALN(bag_link, NB); ALN(bag_lin, NB);
+    ALN(in_cnt, 2 * N); ALN(in_t, 2 * NB); ALN(in_ts, 2 * NB); ALN(in_cr, 2 * NB); ALN(in_link, 2 * NB); ALN(in_lin, 2 * NB);
+#undef ALN
+    DA(h->X.enqpay, N * (size_t)kEnqPay);    // hs_net_async's ENQ payloads (general path)
+    if (p.nl > 0 && (rc = apply_link_queues(h, p))) return rc;
+    if (!h->L.sink_created_own) DA(h->L.sink_created_own, N * (size_t)h->L.cap);   // not every completion reaches the Sink any more: explicit created_at column
+    h->L.sink_created = h->L.sink_created_own;
+#ifndef HS_LOGS_ROW_MAJOR   // (scratch build: the [cap][n_lp] logs the network engines had until round 5)
+    h->L.lp_major = 1;          // an LP's records contiguous (hs_station.hpp RecordLogs::lp_major); nothing has been logged yet
+#endif
+    if (p.pool_want > 0) {      // (the single heap's list cells for a whole run: plan_net_paths)
+        DA(h->xs_host.pnext, (size_t)p.pool_want); DA(h->xs_host.pidx, (size_t)p.pool_want);
+        h->xs_host.pool_cap = p.pool_want;
+    }
+    HS_HIP(h, hipDeviceSynchronize());      // (null-stream uploads and fills, as in apply_stations)
+    h->is_net = true;
+    return HS_OK;
+}
+#undef DA
+#undef UPV
+#undef UPC
+
+}  // namespace
+
 extern "C" {
 
 int hs_abi_version(void) { return HS_ABI_VERSION; }
@@ -648,8 +848,8 @@ int hs_device_count(void) {
     return n;
 }
 
-const char *hs_last_error(const hs_engine *h) { return h ? h->error.c_str() : g_global_error.c_str(); }
-const char *hs_last_global_error(void) { return g_global_error.c_str(); }
+const char *hs_last_error(const hs_engine *h) { return h ? h->error.c_str() : g_last_error.c_str(); }
+const char *hs_last_global_error(void) { return g_last_error.c_str(); }
 
 int hs_engine_create(const hs_config *cfg, hs_engine **out) {
     if (!cfg || !out) return fail(nullptr, HS_E_INVALID, "hs_engine_create: null argument");
@@ -691,592 +891,11 @@ int hs_engine_set_stations(hs_engine *h, const hs_stations *st) {
     if (!h || !st) return fail(h, HS_E_INVALID, "hs_engine_set_stations: null argument");
     if (h->have_stations) return fail(h, HS_E_STATE, "stations already set");
     HS_HIP(h, hipSetDevice(h->cfg.device));
-    const int n = h->cfg.n_lp;
-    // ---- validation (mirrors the reference constructors' ValueErrors) and sizing
-    int maxc = 1;
-    double max_mean_records = 0.0;
-    double reach_s = 0.0;        // the longest single step of any entity, in seconds (reach_fits_int64)
-    bool any_source = false;
-    const double horizon_s = (double)(h->cfg.horizon_ns - h->cfg.start_ns) / 1e9;
-    // several Sources feeding one Server: slots 1 .. kMaxXSrc of an LP (include/hs_engine.h `src_more_kind`)
-    std::vector<uint8_t> xk((size_t)n * kMaxXSrc, (uint8_t)0);
-    std::vector<double> xr((size_t)n * kMaxXSrc, 1.0), xsum((size_t)n, 0.0);
-    std::vector<int64_t> xstop((size_t)n * kMaxXSrc, (int64_t)-1);
-    int64_t n_xsrc_total = 0;
-    for (int j = 0; j < kMaxXSrc && st->src_more_kind; ++j)
-        for (int i = 0; i < n; ++i) {
-            const size_t o = (size_t)j * n + i;
-            const int k = st->src_more_kind[o];
-            if (k == HS_SRC_NONE) continue;
-            if (k != HS_SRC_POISSON && k != HS_SRC_CONSTANT) return fail(h, HS_E_INVALID, "LP %d: unknown source kind %d in slot %d", i, k, j + 1);
-            const bool prev = j == 0 ? (st->src_kind ? st->src_kind[i] : HS_SRC_POISSON) != HS_SRC_NONE : xk[(size_t)(j - 1) * n + i] != 0;
-            if (!prev) return fail(h, HS_E_INVALID, "LP %d: source slots must be filled from 0", i);
-            if ((st->svc_kind ? st->svc_kind[i] : HS_LAT_CONSTANT) == HS_LAT_NO_SERVER)
-                return fail(h, HS_E_UNSUPPORTED, "LP %d: several Sources need a Server to feed", i);
-            if (st->src_profile_kind && st->src_profile_kind[i] != 0)
-                return fail(h, HS_E_UNSUPPORTED, "LP %d: a time-varying Source next to further Sources is not lowered", i);
-            if (!st->src_more_rate) return fail(h, HS_E_INVALID, "src_more_rate is required with src_more_kind");
-            const double r = st->src_more_rate[o];
-            if (!(r > 0.0) || !std::isfinite(r)) return fail(h, HS_E_INVALID, "LP %d: source rate must be > 0 (got %g)", i, r);
-            if (r > 1e8) return fail(h, HS_E_UNSUPPORTED, "LP %d: source rate %g above 1e8/s is not supported", i, r);
-            xk[o] = (uint8_t)k; xr[o] = r; xsum[(size_t)i] += r;
-            reach_s = std::max(reach_s, 36.8 / r);
-            if (st->src_more_stop_after_ns) xstop[o] = st->src_more_stop_after_ns[o];
-            ++n_xsrc_total;
-        }
-    h->any_xsrc = n_xsrc_total > 0;
-    // every LP is Source.poisson -> Server(Exp, c = 1, unbounded queue), nothing stops: half of what the specialised network
-    // kernel (NetStation<.., UNI>) assumes; hs_engine_set_network checks the routers and links
-    h->uni_stations = true;
-    for (int i = 0; i < n; ++i) {
-        if ((st->src_kind ? st->src_kind[i] : HS_SRC_POISSON) != HS_SRC_POISSON || (st->concurrency ? st->concurrency[i] : 1) != 1 ||
-            (st->svc_kind ? st->svc_kind[i] : HS_LAT_CONSTANT) != HS_LAT_EXPONENTIAL || (st->queue_cap ? st->queue_cap[i] : -1) >= 0 ||
-            (st->src_stop_after_ns ? st->src_stop_after_ns[i] : -1) >= 0) { h->uni_stations = false; break; }
-    }
-    h->uni_grid = h->uni_stations;
-    for (int i = 0; i < n && h->uni_grid; ++i) if ((st->egress ? st->egress[i] : HS_EGRESS_SINK) != HS_EGRESS_SINK) h->uni_grid = false;
-    // (the uniform-kind kernels keep times as exact binary64 integers: whole ns in [0, 2^51), hs_device.hpp ns_from_seconds_d)
-    h->f64_times = h->cfg.start_ns >= 0 && h->cfg.horizon_ns < (1ll << 51);
-    for (int i = 0; i < n && h->f64_times; ++i)     // (one draw is at most 36.8 means / inter-arrival times: everything stays below 2^52 ns)
-        if (!((st->svc_mean_s ? st->svc_mean_s[i] : 0.01) < 1e4) || !((st->src_rate ? st->src_rate[i] : 1.0) > 1e-3)) h->f64_times = false;
-    if (!h->f64_times) h->uni_grid = false;
-    if (h->any_xsrc) h->any_profile = true;                         // such LPs run on the general-path instantiation
-    for (int i = 0; i < n; ++i) {
-        const int sk = st->src_kind ? st->src_kind[i] : HS_SRC_POISSON;
-        if (sk < 0 || sk > 2) return fail(h, HS_E_INVALID, "LP %d: unknown source kind %d", i, sk);
-        if (sk != HS_SRC_NONE) {
-            any_source = true;
-            if (!st->src_rate) return fail(h, HS_E_INVALID, "src_rate is required when sources exist");
-            const double r = st->src_rate[i];
-            if (!(r > 0.0) || !std::isfinite(r))
-                return fail(h, HS_E_INVALID, "LP %d: source rate must be > 0 (got %g)", i, r);
-            if (r > 1e8) return fail(h, HS_E_UNSUPPORTED, "LP %d: source rate %g above 1e8/s is not supported", i, r);
-            const double m = (r + xsum[(size_t)i]) * horizon_s;
-            if (m > max_mean_records) max_mean_records = m;
-            reach_s = std::max(reach_s, 36.8 / r);                   // (the longest draw: -log(2^-53) = 36.7 inter-arrival means)
-        }
-        const int c = st->concurrency ? st->concurrency[i] : 1;
-        if (c < 1) return fail(h, HS_E_INVALID, "LP %d: max_concurrent must be >= 1, got %d", i, c);
-        if (c > 32) return fail(h, HS_E_UNSUPPORTED, "LP %d: concurrency %d > 32 is not lowered yet", i, c);
-        if (c > maxc) maxc = c;
-        const int vk = st->svc_kind ? st->svc_kind[i] : HS_LAT_CONSTANT;
-        if (vk != HS_LAT_EXPONENTIAL && vk != HS_LAT_CONSTANT && vk != HS_LAT_NO_SERVER)
-            return fail(h, HS_E_UNSUPPORTED, "LP %d: service distribution kind %d is not lowered", i, vk);
-        if (vk == HS_LAT_NO_SERVER && sk == HS_SRC_NONE)
-            return fail(h, HS_E_INVALID, "LP %d: neither a Source nor a Server", i);
-        const double mean = st->svc_mean_s ? st->svc_mean_s[i] : 0.01;
-        if (!(mean >= 0.0) || !std::isfinite(mean)) return fail(h, HS_E_INVALID, "LP %d: bad service mean %g", i, mean);
-        if (vk == HS_LAT_EXPONENTIAL && !(mean > 0.0))
-            return fail(h, HS_E_INVALID, "LP %d: exponential service needs mean > 0", i);
-        if (vk != HS_LAT_NO_SERVER) reach_s = std::max(reach_s, vk == HS_LAT_EXPONENTIAL ? 36.8 * mean : mean);
-        const int eg = st->egress ? st->egress[i] : HS_EGRESS_SINK;
-        if (eg != HS_EGRESS_NONE && eg != HS_EGRESS_SINK && eg != HS_EGRESS_SERVER)
-            return fail(h, HS_E_UNSUPPORTED, "LP %d: egress kind %d is not lowered", i, eg);
-    }
-    // Tandem queues: Server(downstream=<Server>) (components/server/server.py:271-272).  up[d] = the LP that forwards to LP d;
-    // an LP's pass = its distance from the head of its chain (hs_station.hpp `trk`).
-    std::vector<int32_t> tandem;                     // hs_tables.hpp TickTables::tandem: kMaxUp upstream rows, the pass, the downstream LP
-    const size_t rowP = (size_t)kMaxUp * n, rowD = (size_t)(kMaxUp + 1) * n;
-    bool fan_in = false;                             // more than kMaxUp Servers forward to one: no passes, the single-heap loop
-    for (int i = 0; i < n; ++i) {
-        if ((st->egress ? st->egress[i] : HS_EGRESS_SINK) != HS_EGRESS_SERVER) continue;
-        if (tandem.empty()) { tandem.assign((size_t)(kMaxUp + 2) * n, -1); for (int k = 0; k < n; ++k) tandem[rowP + k] = 0; }
-        if (!st->downstream_lp) return fail(h, HS_E_INVALID, "downstream_lp is required with HS_EGRESS_SERVER");
-        const int d = st->downstream_lp[i];
-        if (d < 0 || d >= n || d == i) return fail(h, HS_E_INVALID, "LP %d: downstream_lp %d is not another LP of this engine", i, d);
-        if ((st->svc_kind ? st->svc_kind[i] : HS_LAT_CONSTANT) == HS_LAT_NO_SERVER || (st->svc_kind ? st->svc_kind[d] : HS_LAT_CONSTANT) == HS_LAT_NO_SERVER)
-            return fail(h, HS_E_INVALID, "LP %d: HS_EGRESS_SERVER connects two Servers", i);
-        int u = 0;
-        while (u < kMaxUp && tandem[(size_t)u * n + d] >= 0) ++u;
-        if (u == kMaxUp) fan_in = true;
-        else tandem[(size_t)u * n + d] = i;
-        tandem[rowD + i] = d;
-    }
-    if (!tandem.empty()) {
-        if (h->cfg.mode != HS_MODE_SINGLE) return fail(h, HS_E_UNSUPPORTED, "tandem queues (HS_EGRESS_SERVER) need HS_MODE_SINGLE: the LPs of a chain are one Simulation");
-        for (int i = 0; i < n; ++i) {                                   // no cycles of Servers (zero-length services would never end)
-            int steps = 0;
-            for (int d = tandem[rowD + i]; d >= 0; d = tandem[rowD + d])
-                if (++steps > n) return fail(h, HS_E_UNSUPPORTED, "LP %d: a cycle of Servers (downstream of downstream ... of itself) is not lowered", i);
-        }
-        // an LP's pass = the longest chain of Servers above it (acyclic: relax until nothing moves)
-        int max_pass = 0;
-        for (int round = 0; round < n; ++round) {
-            bool changed = false;
-            for (int i = 0; i < n; ++i) {
-                const int d = tandem[rowD + i];
-                if (d >= 0 && tandem[rowP + d] < tandem[rowP + i] + 1) { tandem[rowP + d] = tandem[rowP + i] + 1; changed = true; }
-            }
-            if (!changed) break;
-        }
-        for (int i = 0; i < n; ++i) max_pass = std::max(max_pass, (int)tandem[rowP + i]);
-        if (max_pass > 6) {
-            if (!fan_in) return fail(h, HS_E_UNSUPPORTED, "more than 7 Servers in a row are not lowered");
-            max_pass = 6;                                                // (fan-in beyond kMaxUp runs on the single heap anyway)
-        }
-        h->n_pass = max_pass + 1;
-        h->tandem_fan_in = fan_in;
-        // what a Server behind Servers can admit: its own Sources' ticks plus everything upstream (sizes the record logs)
-        std::vector<double> flow((size_t)n, 0.0);
-        for (int i = 0; i < n; ++i)
-            flow[(size_t)i] = ((st->src_kind ? st->src_kind[i] : HS_SRC_POISSON) != HS_SRC_NONE ? st->src_rate[i] : 0.0) + xsum[(size_t)i];
-        for (int round = 0; round < n; ++round) {                       // (acyclic: settles after as many rounds as the longest chain)
-            std::vector<double> in((size_t)n, 0.0);
-            for (int i = 0; i < n; ++i) { const int d = tandem[rowD + i]; if (d >= 0) in[(size_t)d] += flow[(size_t)i]; }
-            bool changed = false;
-            for (int i = 0; i < n; ++i) {
-                const double f = ((st->src_kind ? st->src_kind[i] : HS_SRC_POISSON) != HS_SRC_NONE ? st->src_rate[i] : 0.0) + xsum[(size_t)i] + in[(size_t)i];
-                if (f != flow[(size_t)i]) { flow[(size_t)i] = f; changed = true; }
-            }
-            if (!changed) break;
-        }
-        for (int i = 0; i < n; ++i) if (flow[(size_t)i] * horizon_s > max_mean_records) max_mean_records = flow[(size_t)i] * horizon_s;
-        h->any_profile = true;                                       // the general-path instantiation
-        h->uni_grid = false;
-    }
-    (void)any_source;
-    // time-varying profiles (load/profile.py:52-113); src_rate of such a source is its PEAK rate (it sizes the logs)
-    std::vector<uint8_t> pk((size_t)n, (uint8_t)0);
-    std::vector<double> pp((size_t)n * 4, 0.0);
-    for (int i = 0; i < n && st->src_profile_kind; ++i) {
-        const int k = st->src_profile_kind[i];
-        if (k == 0) continue;
-        if (k != 1 && k != 2) return fail(h, HS_E_UNSUPPORTED, "LP %d: profile kind %d is not lowered", i, k);
-        if (!st->src_profile_params) return fail(h, HS_E_INVALID, "src_profile_params is required with src_profile_kind");
-        const double *q = st->src_profile_params + 4 * (size_t)i;
-        for (int j = 0; j < 4; ++j) {
-            if (!std::isfinite(q[j]) || q[j] < 0.0) return fail(h, HS_E_INVALID, "LP %d: bad profile parameter %g", i, q[j]);
-            pp[(size_t)j * n + i] = q[j];
-        }
-        if (k == 1 && !(q[0] > 0.0)) return fail(h, HS_E_INVALID, "LP %d: LinearRampProfile needs duration_s > 0", i);
-        pk[(size_t)i] = (uint8_t)k;
-        h->any_profile = true;
-        h->any_timevarying = true;
-    }
-    // Probes (instrumentation/probe.py:81-164): up to kMaxProbes per LP (slot 0 = probe_metric, slots 1.. = probe_metric_more);
-    // rate = 1.0 / interval as the reference computes it
-    std::vector<uint8_t> pm((size_t)n * kMaxProbes, (uint8_t)255);
-    std::vector<double> prate((size_t)n * kMaxProbes, 1.0);
-    double min_interval = 0.0;
-    int64_t n_prb_total = 0;
-    for (int j = 0; j < kMaxProbes; ++j) {
-        const uint8_t *pmj = j == 0 ? st->probe_metric : (st->probe_metric_more ? st->probe_metric_more + (size_t)(j - 1) * n : nullptr);
-        const double *pij = j == 0 ? st->probe_interval_s : (st->probe_interval_more ? st->probe_interval_more + (size_t)(j - 1) * n : nullptr);
-        for (int i = 0; i < n && pmj; ++i) {
-            const int m = pmj[i];
-            if (m == 255) continue;
-            if (m < 0 || m > 6) return fail(h, HS_E_UNSUPPORTED, "LP %d: probe metric %d is not lowered", i, m);
-            if (j > 0 && pm[(size_t)(j - 1) * n + i] == 255) return fail(h, HS_E_INVALID, "LP %d: probe slots must be filled from 0", i);
-            if (!pij) return fail(h, HS_E_INVALID, "probe_interval_s is required with probe_metric");
-            const double iv = pij[i];
-            if (!(iv > 0.0) || !std::isfinite(iv)) return fail(h, HS_E_INVALID, "Probe interval must be positive.");   // probe.py:29-30
-            pm[(size_t)j * n + i] = (uint8_t)m;
-            prate[(size_t)j * n + i] = 1.0 / iv;
-            reach_s = std::max(reach_s, iv);
-            if (min_interval == 0.0 || iv < min_interval) min_interval = iv;
-            h->any_probe = true;
-            if (j + 1 > h->n_probe_slots) h->n_probe_slots = j + 1;
-            ++n_prb_total;
-        }
-    }
-    if (h->any_probe) h->any_profile = true;                        // probes run on the general-path instantiation
-    if (!reach_fits_int64(h->cfg.horizon_ns, reach_s))
-        return fail(h, HS_E_UNSUPPORTED, "the horizon (%lld ns) plus one longest step (%.6g s: 36.8 / the smallest rate, 36.8 x the largest "
-                    "exponential mean, the largest constant service or probe interval) leaves int64 nanoseconds -- refused, never "
-                    "wrapped", (long long)h->cfg.horizon_ns, reach_s);
-    // Requests injected with Simulation.schedule(): validated here, run by the general-path instantiation too
-    int64_t n_sched = 0, max_sched = 0;
-    if (st->sched_off) {
-        if (st->sched_off[0] != 0) return fail(h, HS_E_INVALID, "sched_off[0] must be 0");
-        for (int i = 0; i < n; ++i) {
-            const int64_t a = st->sched_off[i], b = st->sched_off[i + 1];
-            if (b < a) return fail(h, HS_E_INVALID, "sched_off must not decrease (LP %d)", i);
-            if (b > a && !st->sched_time_ns) return fail(h, HS_E_INVALID, "sched_time_ns is required with sched_off");
-            if (b > a && (st->svc_kind ? st->svc_kind[i] : HS_LAT_CONSTANT) == HS_LAT_NO_SERVER)
-                return fail(h, HS_E_UNSUPPORTED, "LP %d: scheduled Requests need a Server to receive them", i);
-            for (int64_t k = a; k < b; ++k) {
-                if (st->sched_time_ns[k] < h->cfg.start_ns)
-                    return fail(h, HS_E_INVALID, "LP %d: scheduled time %lld ns lies before start_ns", i, (long long)st->sched_time_ns[k]);
-                if (k > a && st->sched_time_ns[k] < st->sched_time_ns[k - 1])
-                    return fail(h, HS_E_INVALID, "LP %d: scheduled times must be ascending", i);
-            }
-            if (b - a > max_sched) max_sched = b - a;
-        }
-        n_sched = st->sched_off[n];
-        if (n_sched > 0) { h->any_profile = true; h->any_sched = true; }
-    }
-    h->C = maxc <= 1 ? 1 : maxc <= 2 ? 2 : maxc <= 4 ? 4 : maxc <= 8 ? 8 : maxc <= 16 ? 16 : 32;
-    // (C == 1 reads a sink record's created_at from the admission log: the m-th completion is the m-th admission.  A Server that can
-    // receive TWO Requests in one nanosecond while idle -- a forward beside its own Source's Request, two injected Requests, two
-    // Sources in lock step -- delivers both and REJECTS the second at the worker (server.py:223-234), after which that shortcut is
-    // off by one: explicit column, C >= 2.  Found by the tandem + probes sweep on a chain WITHOUT tandem queues: two Requests
-    // injected at one instant into an idle Server.)
-    if ((!tandem.empty() || n_sched > 0 || h->any_xsrc) && h->C == 1) h->C = 2;
-    int64_t cap = h->cfg.log_capacity;
-    if (cap <= 0) {
-        const double c = max_mean_records + 10.0 * std::sqrt(max_mean_records + 1.0) + 64.0 + (double)max_sched;
-        cap = ((int64_t)c + 15) & ~(int64_t)15;
-    }
-    const double log_bytes = (double)n * (double)cap * 8.0 * (h->C > 1 ? 3.0 : 2.0);
-    if (log_bytes > 200e9)
-        return fail(h, HS_E_INVALID, "record logs would need %.1f GB (n_lp=%d, capacity=%lld)", log_bytes / 1e9, n,
-                    (long long)cap);
-    h->L.cap = cap;
-    int rc;
-    std::vector<uint64_t> dflt_base((size_t)n);
-    for (int i = 0; i < n; ++i) dflt_base[(size_t)i] = h->cfg.lp_base + (uint64_t)i;
-#define UP(field, src, T, d) if ((rc = upload<T>(h, &h->P.field, src, (size_t)n, d))) return rc
-    UP(src_kind, st->src_kind, uint8_t, (uint8_t)HS_SRC_POISSON);
-    UP(src_rate, st->src_rate, double, 1.0);
-    UP(src_stop, st->src_stop_after_ns, int64_t, (int64_t)-1);
-    UP(conc, st->concurrency, int32_t, 1);
-    UP(svc_kind, st->svc_kind, uint8_t, (uint8_t)HS_LAT_CONSTANT);
-    UP(svc_mean, st->svc_mean_s, double, 0.01);
-    UP(qcap, st->queue_cap, int64_t, (int64_t)-1);
-    UP(egress, st->egress, uint8_t, (uint8_t)HS_EGRESS_SINK);
-    UP(seed, st->seed, uint64_t, h->cfg.seed);
-    if ((rc = upload<uint64_t>(h, &h->P.stream_base, st->stream_base ? st->stream_base : dflt_base.data(), (size_t)n, 0)))
-        return rc;
-#undef UP
-    if ((rc = upload<uint8_t>(h, &h->P.prof_kind, pk.data(), (size_t)n, 0))) return rc;
-    if ((rc = upload<double>(h, &h->P.prof_p, pp.data(), (size_t)n * 4, 0.0))) return rc;
-    if ((rc = upload<uint8_t>(h, &h->P.probe_metric, pm.data(), (size_t)n * kMaxProbes, 255))) return rc;
-    if ((rc = upload<double>(h, &h->P.probe_rate, prate.data(), (size_t)n * kMaxProbes, 1.0))) return rc;
-    h->P.tabs = nullptr;
-    const bool sched_single = h->any_sched && h->cfg.mode == HS_MODE_SINGLE;      // (the election's tie check: TickTables::standin_sched)
-    if (h->any_timevarying || h->any_probe || !tandem.empty() || h->any_xsrc || sched_single) {
-        // Tick tables (hs_tables.hpp): one row per time-varying Source (Poisson ones draw from their own arrival stream;
-        // deterministic ones with equal parameters share a row) and one per distinct Probe interval (a Probe's tick times are a
-        // property of (interval, start) alone).
-        std::vector<TickRow> rows;
-        std::vector<int32_t> srow((size_t)n, -1), prow((size_t)n * kMaxProbes, -1);
-        for (int i = 0; i < n; ++i) {
-            if (pk[(size_t)i] == 0) continue;
-            TickRow r{};
-            r.kind = pk[(size_t)i];
-            r.poisson = (st->src_kind ? st->src_kind[i] : HS_SRC_POISSON) == HS_SRC_POISSON ? 1u : 0u;
-            r.p0 = pp[(size_t)i]; r.p1 = pp[(size_t)n + i]; r.p2 = pp[(size_t)2 * n + i]; r.p3 = pp[(size_t)3 * n + i];
-            r.owner = i;
-            if (r.poisson) {
-                r.seed = st->seed ? st->seed[i] : h->cfg.seed;
-                r.sid = stream_id(st->stream_base ? st->stream_base[i] : dflt_base[(size_t)i], kStreamArrival);
-            }
-            int32_t found = -1;
-            if (!r.poisson)
-                for (size_t q = 0; q < rows.size() && found < 0; ++q)
-                    if (!rows[q].poisson && rows[q].kind == r.kind && rows[q].p0 == r.p0 && rows[q].p1 == r.p1 && rows[q].p2 == r.p2 &&
-                        rows[q].p3 == r.p3) found = (int32_t)q;
-            if (found < 0) { found = (int32_t)rows.size(); rows.push_back(r); }
-            srow[(size_t)i] = found;
-        }
-        {
-            std::vector<std::pair<double, int32_t>> seen;          // (rate, row) of the probe rows so far
-            for (int j = 0; j < kMaxProbes; ++j)
-                for (int i = 0; i < n; ++i) {
-                    const size_t o = (size_t)j * n + i;
-                    if (pm[o] == 255) continue;
-                    int32_t found = -1;
-                    for (const auto &pr : seen) if (pr.first == prate[o]) { found = pr.second; break; }
-                    if (found < 0) {
-                        TickRow r{};
-                        r.kind = kProfGeneralConstant; r.poisson = 0; r.p0 = prate[o]; r.owner = i;
-                        found = (int32_t)rows.size();
-                        rows.push_back(r);
-                        seen.emplace_back(prate[o], found);
-                    }
-                    prow[o] = found;
-                }
-        }
-        // capacity: what a Source's logs are sized for (its peak rate) / the fastest Probe's ticks, + the two beyond the horizon
-        int64_t tcap = h->any_timevarying ? cap + 2 : 0;
-        if (h->any_probe) tcap = std::max<int64_t>(tcap, (int64_t)(horizon_s / min_interval) + 8 + 2);
-        h->tab_cap = tcap;
-        h->n_tab_rows = (int)rows.size();
-        if ((double)rows.size() * (double)tcap * 8.0 > 100e9)
-            return fail(h, HS_E_INVALID, "tick tables would need %.1f GB", (double)rows.size() * (double)tcap * 8.0 / 1e9);
-        if (!rows.empty()) {
-            if ((rc = dev_alloc(h, &h->tab_rows, rows.size()))) return rc;
-            HS_HIP(h, hipMemcpy(h->tab_rows, rows.data(), rows.size() * sizeof(TickRow), hipMemcpyHostToDevice));
-            if ((rc = dev_alloc(h, &h->tab_times, rows.size() * (size_t)tcap))) return rc;
-            if ((rc = dev_alloc(h, &h->tab_count, rows.size()))) return rc;
-            if ((rc = dev_alloc(h, &h->tab_status, 2))) return rc;
-            HS_HIP(h, hipMemset(h->tab_status, 0, 2 * sizeof(unsigned long long)));
-        }
-        TickTables tt{};
-        tt.times = h->tab_times; tt.cap = tcap; tt.t_start = h->cfg.start_ns;
-        if (!tandem.empty()) {                                      // tandem queues: hs_tables.hpp TickTables::tandem
-            if ((double)n * (double)cap * 32.0 > 100e9)
-                return fail(h, HS_E_INVALID, "the forward logs of the tandem queues would need %.1f GB", (double)n * (double)cap * 32.0 / 1e9);
-            if ((rc = upload<int32_t>(h, &tt.tandem, tandem.data(), tandem.size(), -1))) return rc;
-            if ((rc = dev_alloc(h, &tt.inj_i, (size_t)kMaxUp * (size_t)n))) return rc;
-            HS_HIP(h, hipMemset(tt.inj_i, 0, (size_t)kMaxUp * (size_t)n * sizeof(int64_t)));
-            for (int64_t **col : {&tt.fw_rc, &tt.fw_rrc, &tt.fw_rdr, &tt.fw_dep}) if ((rc = dev_alloc(h, col, (size_t)n * (size_t)cap))) return rc;
-            for (int64_t **col : {&tt.q_rrc, &tt.q_rdr, &tt.q_pay}) if ((rc = dev_alloc(h, col, (size_t)n * (size_t)kQCap))) return rc;
-            if ((rc = dev_alloc(h, &tt.cand_key, (size_t)n * 4))) return rc;
-            HS_HIP(h, hipMemset(tt.cand_key, 0, (size_t)n * 4 * sizeof(int64_t)));
-        }
-        if (tandem.empty() && !h->any_xsrc && sched_single) {
-            // injected Requests only: the same tie check, every departure / injected Request a stand-in (TickTables::standin_sched)
-            if ((rc = dev_alloc(h, &tt.cand_key, (size_t)n * 4))) return rc;
-            HS_HIP(h, hipMemset(tt.cand_key, 0, (size_t)n * 4 * sizeof(int64_t)));
-        }
-        tt.standin_sched = sched_single ? 1 : 0;
-        if (tandem.empty() && h->any_xsrc && h->cfg.mode == HS_MODE_SINGLE) {
-            // several Sources per Server: a pending DEPARTURE's last election key is the construction rank of the Source its lineage
-            // goes back to, which the engine does not carry -- cand_rank() uses the LP's first-listed Source.  When the election of
-            // the event beyond end_ns comes down to that key for such a candidate (every other key ties with another LP's), the run
-            // is repeated on the single heap (Totals::undecided bit 1, tandem_fallback) instead of guessing.  Found by
-            // tools/gpu_random_sweep.py, multi_source case 22522: two lock-step constant Sources in different LPs, the other LP's
-            // first-listed Source a Poisson one constructed earlier.
-            if ((rc = dev_alloc(h, &tt.cand_key, (size_t)n * 4))) return rc;
-            HS_HIP(h, hipMemset(tt.cand_key, 0, (size_t)n * 4 * sizeof(int64_t)));
-            // ... and the engine carries the lineage's Source with every pending departure (TickTables::rs_dep): the stand-in is then
-            // only used for departures whose lineage starts at an injected Request
-            if ((rc = dev_alloc(h, &tt.rs_dep, (size_t)n * (size_t)h->C))) return rc;
-            if ((rc = dev_alloc(h, &tt.rs_q, (size_t)n * (size_t)kQCap))) return rc;
-            HS_HIP(h, hipMemset(tt.rs_dep, 0xff, (size_t)n * (size_t)h->C));
-            HS_HIP(h, hipMemset(tt.rs_q, 0xff, (size_t)n * (size_t)kQCap));
-        }
-        if ((rc = upload<int32_t>(h, &tt.src_row, srow.data(), srow.size(), -1))) return rc;
-        if ((rc = upload<int32_t>(h, &tt.probe_row, prow.data(), prow.size(), -1))) return rc;
-        if ((rc = upload<TickTables>(h, &h->P.tabs, &tt, 1, TickTables{}))) return rc;
-    }
-    h->P.xsrc_kind = nullptr; h->P.xsrc_rate = nullptr; h->P.xsrc_stop = nullptr;
-    if (h->any_xsrc) {
-        if ((rc = upload<uint8_t>(h, &h->P.xsrc_kind, xk.data(), xk.size(), 0))) return rc;
-        if ((rc = upload<double>(h, &h->P.xsrc_rate, xr.data(), xr.size(), 1.0))) return rc;
-        if ((rc = upload<int64_t>(h, &h->P.xsrc_stop, xstop.data(), xstop.size(), (int64_t)-1))) return rc;
-    }
-    h->P.sched_off = nullptr; h->P.sched_t = nullptr;
-    if (n_sched > 0) {
-        if ((rc = upload<int64_t>(h, &h->P.sched_off, st->sched_off, (size_t)n + 1, 0))) return rc;
-        if ((rc = upload<int64_t>(h, &h->P.sched_t, st->sched_time_ns, (size_t)n_sched, 0))) return rc;
-    }
-    h->P.tie_rank = nullptr;
-    // the Sources in `sources=[...]` order: (LP, slot) pairs; default = LP-major, slot-minor
-    std::vector<int32_t> so;
-    std::vector<uint8_t> sslot;
-    {
-        auto has_src = [&](int lp, int slot) {
-            return slot == 0 ? (st->src_kind ? st->src_kind[lp] : HS_SRC_POISSON) != HS_SRC_NONE : xk[(size_t)(slot - 1) * n + lp] != 0;
-        };
-        int64_t n_src_total = n_xsrc_total;
-        for (int i = 0; i < n; ++i) if (has_src(i, 0)) ++n_src_total;
-        if (st->source_order) {
-            std::vector<uint8_t> taken((size_t)n * (kMaxXSrc + 1), (uint8_t)0);
-            for (int64_t k = 0; k < n_src_total; ++k) {
-                const int lp = st->source_order[k], slot = st->source_slot_order ? st->source_slot_order[k] : 0;
-                if (lp < 0 || lp >= n || slot < 0 || slot > kMaxXSrc || !has_src(lp, slot) || taken[(size_t)slot * n + lp])
-                    return fail(h, HS_E_INVALID, "source_order / source_slot_order must list every Source exactly once");
-                taken[(size_t)slot * n + lp] = 1;
-                so.push_back(lp); sslot.push_back((uint8_t)slot);
-            }
-        } else {
-            for (int i = 0; i < n; ++i)
-                for (int j = 0; j <= kMaxXSrc; ++j) if (has_src(i, j)) { so.push_back(i); sslot.push_back((uint8_t)j); }
-        }
-    }
-    h->h_src_lp = so; h->h_src_slot = sslot;      // (setup_exact_plain: the single-heap machinery built on demand)
-    // the Probes in `probes=[...]` order: (LP, slot) pairs; default = LP-major, slot-minor
-    std::vector<int32_t> po;
-    std::vector<uint8_t> pslot;
-    {
-        std::vector<uint8_t> taken((size_t)n * kMaxProbes, (uint8_t)0);
-        if (st->probe_order) {
-            for (int64_t k = 0; k < n_prb_total; ++k) {
-                const int lp = st->probe_order[k], slot = st->probe_slot_order ? st->probe_slot_order[k] : 0;
-                if (lp < 0 || lp >= n || slot < 0 || slot >= kMaxProbes || pm[(size_t)slot * n + lp] == 255 || taken[(size_t)slot * n + lp])
-                    return fail(h, HS_E_INVALID, "probe_order / probe_slot_order must list every probe exactly once");
-                taken[(size_t)slot * n + lp] = 1;
-                po.push_back(lp); pslot.push_back((uint8_t)slot);
-            }
-        } else {
-            for (int i = 0; i < n && n_prb_total > 0; ++i)
-                for (int j = 0; j < kMaxProbes; ++j) if (pm[(size_t)j * n + i] != 255) { po.push_back(i); pslot.push_back((uint8_t)j); }
-        }
-    }
-    if (((double)so.size() + (double)n + (double)po.size() + 1.0) * 8.0 >= 2147483647.0)
-        return fail(h, HS_E_UNSUPPORTED, "too many Sources / stations / Probes for the 32-bit construction ranks of the election key");
-    if (st->source_order || st->probe_order || !tandem.empty()) {   // cross-LP ties go to the entity the reference constructed first (cand_rank, hs_station.hpp)
-        std::vector<int32_t> tr((size_t)n * (kMaxXSrc + 2) + 1 + (size_t)n * kMaxProbes, -1);
-        int32_t *sr = tr.data() + n;
-        for (size_t q = 0; q < so.size(); ++q) {
-            sr[(size_t)sslot[q] * n + (size_t)so[q]] = (int32_t)q;               // a tick: its own Source's position
-            if (tr[(size_t)so[q]] < 0) tr[(size_t)so[q]] = (int32_t)q;           // anything else: the LP's first-listed Source
-        }
-        if (!tandem.empty())                                                     // a Server behind a Server: what reaches it descends
-            for (int i = 0; i < n; ++i) {                                        // from the Sources of its chain's head
-                int head = i;                                                    // (its first-listed upstream, all the way up)
-                while (tandem[(size_t)head] >= 0) head = tandem[(size_t)head];
-                if (head != i && tr[(size_t)i] < 0 && tr[(size_t)head] >= 0) tr[(size_t)i] = tr[(size_t)head];
-            }
-        for (int i = 0; i < n; ++i) if (tr[(size_t)i] < 0) tr[(size_t)i] = (int32_t)so.size() + i;   // sourceless LPs after them
-        tr[(size_t)n * (kMaxXSrc + 2)] = (int32_t)so.size() + n;                 // Probes behind all of them ...
-        int32_t *pr = tr.data() + (size_t)n * (kMaxXSrc + 2) + 1;                // ... each by its own position in `probes=[...]`
-        for (size_t q = 0; q < po.size(); ++q) pr[(size_t)pslot[q] * n + (size_t)po[q]] = (int32_t)so.size() + n + (int32_t)q;
-        if (!tandem.empty())     // ... and where every other key ties between two Servers of a chain, the upstream one's event was created first
-            for (size_t q = 0; q < tr.size(); ++q) {                             // (ranks only compare: room for the pass below them)
-                const size_t lp = q < (size_t)n * (kMaxXSrc + 2) ? q % (size_t)n : (q - (size_t)n * (kMaxXSrc + 2) - 1) % (size_t)n;
-                // (3 bits for the pass: clamped -- a chain deeper than 7 behind a fan-in beyond kMaxUp runs on the single heap, which
-                //  does not read this key; unclamped, a pass >= 8 spilled into the construction rank above it: ADVICE r3)
-                if (q == (size_t)n * (kMaxXSrc + 2)) { tr[q] = tr[q] * 8; continue; }
-                const int32_t ps = tandem[(size_t)kMaxUp * n + lp];
-                tr[q] = tr[q] * 8 + (ps > 7 ? 7 : ps < 0 ? 0 : ps);
-            }
-        if ((rc = upload<int32_t>(h, &h->P.tie_rank, tr.data(), tr.size(), 0))) return rc;
-    }
-    h->P.sched_idx = nullptr;
-    if (h->cfg.mode == HS_MODE_REPLICAS && (n_sched > 0 || h->any_probe || h->any_xsrc)) {
-        {   // every LP's Sources in its own construction order: slots, 255-terminated
-            std::vector<uint8_t> lso((size_t)n * (kMaxXSrc + 1), (uint8_t)255);
-            std::vector<int> cnt((size_t)n, 0);
-            for (size_t q = 0; q < so.size(); ++q) lso[(size_t)cnt[(size_t)so[q]]++ * n + (size_t)so[q]] = sslot[q];
-            if ((rc = upload<uint8_t>(h, &h->XI.lp_src_slots, lso.data(), lso.size(), 255))) return rc;
-        }
-        // One prologue per LP (every LP is its own Simulation): its Events sorted by construction rank inside the LP
-        std::vector<int64_t> se((size_t)n_sched), sr((size_t)n_sched);
-        int64_t span = 0;
-        for (int i = 0; i < n && n_sched > 0; ++i) {
-            const int64_t a = st->sched_off[i], b = st->sched_off[i + 1];
-            for (int64_t k = a; k < b; ++k) se[(size_t)k] = k;
-            if (st->sched_rank) {
-                std::sort(se.begin() + a, se.begin() + b, [&](int64_t x, int64_t y) { return st->sched_rank[x] < st->sched_rank[y]; });
-                for (int64_t k = a; k < b; ++k) {
-                    const int64_t r = st->sched_rank[se[(size_t)k]];
-                    if (r < 0 || (k > a && r == st->sched_rank[se[(size_t)k - 1]]))
-                        return fail(h, HS_E_INVALID, "LP %d: sched_rank must hold distinct positions >= 0", i);
-                }
-            }
-            for (int64_t k = a; k < b; ++k) {
-                sr[(size_t)k] = st->sched_rank ? st->sched_rank[se[(size_t)k]] : k - a;
-                if (sr[(size_t)k] + 1 > span) span = sr[(size_t)k] + 1;
-            }
-        }
-        if (span > max_sched + (1 << 16)) return fail(h, HS_E_INVALID, "sched_rank positions are implausibly sparse");
-        if ((rc = upload<int64_t>(h, &h->XI.sched_rank, sr.data(), sr.size(), 0))) return rc;
-        if ((rc = upload<int64_t>(h, &h->XI.sched_entry, se.data(), se.size(), 0))) return rc;
-        h->XI.n_src = 0; h->XI.n_probe = 0; h->XI.n_sched = n_sched; h->XI.per_lp = 1;
-        if ((rc = dev_alloc(h, &h->XI.sched_idx, (size_t)n_sched))) return rc;
-        HS_HIP(h, hipMemset(h->XI.sched_idx, 0, (size_t)(n_sched > 0 ? n_sched : 1) * sizeof(uint32_t)));
-        h->P.sched_idx = h->XI.sched_idx;
-        const int64_t n_init_lp = 1 + kMaxXSrc + kMaxProbes + span;
-        h->XI.init_cap_lp = n_init_lp;
-        h->XI.heap_cap_lp = n_init_lp + h->C + 32;
-        h->XI.pool_cap_lp = 2 * n_init_lp + 64;
-        h->xs_host = XState{};
-        if ((rc = dev_alloc(h, &h->xs_host.heap, (size_t)n * (size_t)h->XI.heap_cap_lp))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.qhead, (size_t)n))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.qtail, (size_t)n))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.pnext, (size_t)n * (size_t)h->XI.pool_cap_lp))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.pidx, (size_t)n * (size_t)h->XI.pool_cap_lp))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.init_t, (size_t)n * (size_t)n_init_lp))) return rc;
-        if ((rc = dev_alloc(h, &h->xs, (size_t)n + 1))) return rc;
-        h->exact = true;
-        h->exact_prologue = true;
-    }
-    if (h->cfg.mode == HS_MODE_SINGLE && (n_sched > 0 || h->any_probe || h->any_xsrc || !tandem.empty())) {
-        // The prologue (hs_exact.hpp): the reference's pre-run events in the order it constructs them.  (Tandem queues: the same
-        // loop as the engine's exact path for whole runs -- `exact_only`.)
-        h->exact_prologue = n_sched > 0 || h->any_probe || h->any_xsrc;
-        // (more upstream Servers than the passes merge: one heap from the start.  Tandem queues next to pre-run events start on the
-        // passes like any lazy_prologue engine and move to the single heap -- which IS the prologue's loop -- on the first hazard)
-        h->exact_only = !tandem.empty() && h->tandem_fan_in;
-        std::vector<int32_t> sl((size_t)n_sched);
-        std::vector<int64_t> se((size_t)n_sched);
-        std::vector<int32_t> lp_of((size_t)n_sched);
-        for (int i = 0; i < n && n_sched > 0; ++i)
-            for (int64_t k = st->sched_off[i]; k < st->sched_off[i + 1]; ++k) lp_of[(size_t)k] = i;
-        std::vector<int64_t> sr((size_t)n_sched);
-        for (int64_t j = 0; j < n_sched; ++j) se[(size_t)j] = j;
-        if (st->sched_rank) {
-            std::sort(se.begin(), se.end(), [&](int64_t a, int64_t b) { return st->sched_rank[a] < st->sched_rank[b]; });
-            for (int64_t j = 0; j < n_sched; ++j) {
-                const int64_t r = st->sched_rank[se[(size_t)j]];
-                if (r < 0 || (j > 0 && r == st->sched_rank[se[(size_t)j - 1]]))
-                    return fail(h, HS_E_INVALID, "sched_rank must hold distinct positions >= 0");
-            }
-        }
-        for (int64_t j = 0; j < n_sched; ++j) {
-            sl[(size_t)j] = lp_of[(size_t)se[(size_t)j]];
-            sr[(size_t)j] = st->sched_rank ? st->sched_rank[se[(size_t)j]] : j;
-        }
-        if ((rc = upload<int64_t>(h, &h->XI.sched_rank, sr.data(), sr.size(), 0))) return rc;
-        if ((rc = upload<int32_t>(h, &h->XI.src_lp, so.data(), so.size(), 0))) return rc;
-        if ((rc = upload<uint8_t>(h, &h->XI.src_slot, sslot.data(), sslot.size(), 0))) return rc;
-        if ((rc = upload<int32_t>(h, &h->XI.probe_lp, po.data(), po.size(), 0))) return rc;
-        if ((rc = upload<uint8_t>(h, &h->XI.probe_slot, pslot.data(), pslot.size(), 0))) return rc;
-        if ((rc = upload<int32_t>(h, &h->XI.sched_lp, sl.data(), sl.size(), 0))) return rc;
-        if ((rc = upload<int64_t>(h, &h->XI.sched_entry, se.data(), se.size(), 0))) return rc;
-        h->XI.n_src = (int32_t)so.size(); h->XI.n_probe = (int32_t)po.size(); h->XI.n_sched = n_sched;
-        if ((rc = dev_alloc(h, &h->XI.sched_idx, (size_t)n_sched))) return rc;
-        HS_HIP(h, hipMemset(h->XI.sched_idx, 0, (size_t)(n_sched > 0 ? n_sched : 1) * sizeof(uint32_t)));
-        h->P.sched_idx = h->XI.sched_idx;
-        int64_t rank_span = 0;                                  // positions 0 .. rank_span-1 (cancelled Events leave gaps)
-        for (int64_t j = 0; j < n_sched; ++j) if (sr[(size_t)j] + 1 > rank_span) rank_span = sr[(size_t)j] + 1;
-        if (rank_span > n_sched + (1 << 20)) return fail(h, HS_E_INVALID, "sched_rank positions are implausibly sparse");
-        const int64_t n_init = (int64_t)so.size() + (int64_t)po.size() + rank_span;
-        h->n_init = n_init;
-        h->lazy_prologue = h->exact_prologue;
-        h->xs_host = XState{};
-        h->xs_host.heap_cap = n_init + (int64_t)n * (h->C + 16) + 1024;
-        h->xs_host.pool_cap = 2 * n_init + 16 * (int64_t)n + 1024;
-        if (!tandem.empty() || h->any_xsrc || h->any_sched)       // a whole run (tandem queues; several Sources per Server after an undecided election): one list cell per admitted Request
-            h->xs_host.pool_cap = std::min<int64_t>(h->xs_host.pool_cap + (int64_t)n * cap, (int64_t)1 << 30);
-        if ((rc = dev_alloc(h, &h->xs_host.heap, (size_t)h->xs_host.heap_cap))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.qhead, (size_t)n))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.qtail, (size_t)n))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.pnext, (size_t)h->xs_host.pool_cap))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.pidx, (size_t)h->xs_host.pool_cap))) return rc;
-        if ((rc = dev_alloc(h, &h->xs_host.init_t, (size_t)n_init))) return rc;
-        if ((rc = dev_alloc(h, &h->xs, 1))) return rc;
-        h->exact = true;
-    }
-    const size_t N = (size_t)n, NC = (size_t)n * (size_t)h->C;
-#define AL(field, count) if ((rc = dev_alloc(h, &h->X.field, count))) return rc
-    AL(A, N); AL(seqA, N); AL(crtA, N); AL(arr_k, N); AL(arr_time, N); AL(svc_k, N);
-    AL(D, NC); AL(seqD, NC); AL(crtD, NC); AL(svc_s, NC); AL(crt, NC);
-    AL(seq, N); AL(buf, N); AL(active, N);
-    AL(generated, N); AL(accepted, N); AL(dropped, N); AL(completed, N); AL(rejected, N); AL(started, N);
-    AL(received, N); AL(sink_w, N); AL(total_service, N); AL(q, N); AL(grp_time, N); AL(last_time, N);
-    AL(events, N); AL(ev_kind, N * 11);
-    AL(dpA, N); AL(rcA, N); AL(dpD, NC); AL(rcD, NC); AL(wkD, NC); AL(qdep, N * kQCap); AL(qrc, N * kQCap);   // lineage (hs_station.hpp)
-    if (h->any_profile) {      // the general-path instantiation of the run kernel loads / stores the probe state of every LP
-        AL(PA, N * kMaxProbes); AL(seqP, N * kMaxProbes); AL(crtP, N * kMaxProbes); AL(p_arr, N * kMaxProbes);
-        AL(p_n, N * kMaxProbes); AL(ev_probe, N * 2); AL(sched_i, N); AL(rcP, N * kMaxProbes);
-    }
-    if (h->any_xsrc) {
-        AL(XA, N * kMaxXSrc); AL(crtX, N * kMaxXSrc); AL(x_arr, N * kMaxXSrc); AL(x_n, N * kMaxXSrc); AL(seqX, N * kMaxXSrc);
-        AL(x_k, N * kMaxXSrc); AL(dpX, N * kMaxXSrc); AL(rcX, N * kMaxXSrc);
-    }
-    if (h->any_probe) {
-        h->L.pcap = (int64_t)(horizon_s / min_interval) + 8;
-        if ((double)h->L.pcap * (double)n * 16.0 > 50e9) return fail(h, HS_E_INVALID, "probe logs would need %.1f GB", (double)h->L.pcap * n * 16.0 / 1e9);
-        if ((rc = dev_alloc(h, &h->L.probe_t, N * (size_t)h->L.pcap * (size_t)h->n_probe_slots))) return rc;
-        if ((rc = dev_alloc(h, &h->L.probe_v, N * (size_t)h->L.pcap * (size_t)h->n_probe_slots))) return rc;
-    }
-#undef AL
-    if ((rc = dev_alloc(h, &h->L.adm, N * (size_t)cap))) return rc;
-    if ((rc = dev_alloc(h, &h->L.sink_t, N * (size_t)cap))) return rc;
-    if (h->C > 1) {
-        // explicit created_at column: completions leave in a different order than admissions
-        if ((rc = dev_alloc(h, &h->L.sink_created_own, N * (size_t)cap))) return rc;
-    }
-    h->L.sink_created = (h->C > 1) ? h->L.sink_created_own : h->L.adm;
-    if ((rc = dev_alloc(h, &h->tot, 1))) return rc;
-    HS_HIP(h, hipMemset(h->tot, 0, sizeof(Totals)));
-    if ((rc = dev_alloc(h, &h->cands, std::max<size_t>((size_t)h->n_blocks, (size_t)(n + 1) / 2)))) return rc;   // (the wide kernel: one per >= 2 LPs)
-    if (h->C == 1 && h->uni_grid && !h->any_profile && h->cfg.mode == HS_MODE_SINGLE) {
-        if ((rc = dev_alloc(h, &h->wide_ctl, 1))) return rc;
-        if ((rc = dev_alloc(h, &h->wide_bail, (size_t)n))) return rc;
-        if ((rc = dev_alloc(h, &h->wave_parts, ((size_t)n + 7) / 8))) return rc;
-        HS_HIP(h, hipMemset(h->wide_ctl, 0, sizeof(WideCtl)));
-    }
-    HS_HIP(h, hipMemset(h->tot, 0, sizeof(Totals)));
-    // (the uploads and fills above went through the NULL stream; the engine's launches use a non-blocking stream, which does not
-    //  wait for it: everything is in place before the caller can enqueue a run)
-    HS_HIP(h, hipDeviceSynchronize());
-    h->have_stations = true;
-    return HS_OK;
+    StationPlan plan;
+    std::string err;
+    const int rc = plan_stations(h->cfg, *st, plan, err);
+    if (rc) return fail(h, rc, "%s", err.c_str());       // (refused: the engine is as it was before the call)
+    return apply_stations(h, plan);
 }
 
 int hs_engine_set_network(hs_engine *h, const hs_network *net) {
@@ -1288,291 +907,16 @@ int hs_engine_set_network(hs_engine *h, const hs_network *net) {
     if (h->C > 4) return fail(h, HS_E_UNSUPPORTED, "networked stations support concurrency <= 4 for now");
     HS_HIP(h, hipSetDevice(h->cfg.device));
     { const int rcr = ensure_reset(h); if (rcr) return rcr; }     // (a bootstrap deferred for a station engine this no longer is)
-    const int n = h->cfg.n_lp, nl = net->n_links;
-    if (nl < 0) return fail(h, HS_E_INVALID, "n_links < 0");
-    // A shard of a larger network: link endpoints are network-wide station indices, this engine owns
-    // [lp_base, lp_base + n_lp).  Otherwise the engine holds the whole network and endpoints are its own indices.
-    const bool global = net->n_global_lp > 0;
-    const int64_t lo = global ? (int64_t)h->cfg.lp_base : 0;
-    const int64_t n_all = global ? net->n_global_lp : n;
-    if (global && (lo + n > n_all)) return fail(h, HS_E_INVALID, "shard [%lld, %lld) exceeds the %lld stations of the network",
-                                                (long long)lo, (long long)(lo + n), (long long)n_all);
-    if (global && !net->link_gid) return fail(h, HS_E_INVALID, "a shard needs link_gid (network-wide link ids)");
-    if (!net->egress_kind) return fail(h, HS_E_INVALID, "egress_kind is required");
-    if (nl > 0 && (!net->link_dst || !net->link_lat_min_s || !net->link_src))
-        return fail(h, HS_E_INVALID, "link_dst, link_src and link_lat_min_s are required");
-    // lookahead W = min over links of int(to_seconds(from_seconds(lat_min)) * 1e9) -- the same truncations the
-    // device applies (core/temporal.py:62,66)
-    int64_t W = INT64_MAX;
-    for (int l = 0; l < nl; ++l) {
-        const double lm = net->link_lat_min_s[l];
-        if (!(lm > 0.0) || !std::isfinite(lm))
-            return fail(h, HS_E_INVALID, "link %d: min latency must be > 0 (conservative windows need lookahead), got %g", l, lm);
-        {   // (before any conversion of the latency to int64 nanoseconds)
-            const int jk0 = net->link_jitter_kind ? net->link_jitter_kind[l] : HS_LAT_CONSTANT;
-            const double jm = net->link_jitter_mean_s ? net->link_jitter_mean_s[l] : 0.0;
-            const double delay_s = lm + (jk0 == HS_LAT_EXPONENTIAL ? 36.8 * jm : jm);
-            if (!reach_fits_int64(h->cfg.horizon_ns, delay_s))
-                return fail(h, HS_E_UNSUPPORTED, "link %d: the horizon (%lld ns) plus its longest delay (%.6g s: latency + 36.8 x the jitter "
-                            "mean) leaves int64 nanoseconds -- refused, never wrapped", l, (long long)h->cfg.horizon_ns, delay_s);
-        }
-        const double lc = (double)(int64_t)(lm * 1e9) / 1e9;
-        const int64_t w = (int64_t)(lc * 1e9);
-        if (w <= 0) return fail(h, HS_E_INVALID, "link %d: min latency %g s truncates to 0 ns", l, lm);
-        if (w < W) W = w;
-        if (net->link_dst[l] < 0 || net->link_dst[l] >= n_all || net->link_src[l] < 0 || net->link_src[l] >= n_all)
-            return fail(h, HS_E_INVALID, "link %d: endpoint out of range", l);
-        const bool src_here = net->link_src[l] >= lo && net->link_src[l] < lo + n;
-        const bool dst_here = net->link_dst[l] >= lo && net->link_dst[l] < lo + n;
-        if (!src_here && !dst_here) return fail(h, HS_E_INVALID, "link %d touches no station of this shard", l);
-        const int jk = net->link_jitter_kind ? net->link_jitter_kind[l] : HS_LAT_CONSTANT;
-        if (jk == HS_LAT_EXPONENTIAL && !(net->link_jitter_mean_s && net->link_jitter_mean_s[l] > 0.0))
-            return fail(h, HS_E_INVALID, "link %d: exponential jitter needs mean > 0", l);
-        if (jk != HS_LAT_EXPONENTIAL && jk != HS_LAT_CONSTANT)
-            return fail(h, HS_E_UNSUPPORTED, "link %d: jitter kind %d is not lowered", l, jk);
-        if (jk == HS_LAT_CONSTANT && net->link_jitter_mean_s && !(net->link_jitter_mean_s[l] >= 0.0 && net->link_jitter_mean_s[l] < 1e6))
-            return fail(h, HS_E_INVALID, "link %d: constant jitter %g s", l, net->link_jitter_mean_s[l]);
-    }
-    std::vector<int32_t> rt0((size_t)n, -1), rt1((size_t)n, -1), rt2((size_t)n, -1), rt3((size_t)n, -1), lof((size_t)n, -1);
-    std::vector<uint8_t> rtk((size_t)n, (uint8_t)2);
-    std::vector<uint8_t> link_used((size_t)(nl > 0 ? nl : 1), 0);
-    auto use_link = [&](int lp, int l) -> int {
-        if (l < 0 || l >= nl) return fail(h, HS_E_INVALID, "LP %d: link index %d out of range", lp, l);
-        if (net->link_src[l] != lo + lp) return fail(h, HS_E_INVALID, "LP %d uses link %d whose source is station %d", lp, l, net->link_src[l]);
-        if (link_used[(size_t)l]) return fail(h, HS_E_INVALID, "link %d is referenced twice", l);
-        link_used[(size_t)l] = 1;
-        return HS_OK;
-    };
-    for (int i = 0; i < n; ++i) {
-        const int ek = net->egress_kind[i];
-        int rc2;
-        if (ek == HS_EGRESS_ROUTER) {
-            if (!net->router_target0 || !net->router_target1) return fail(h, HS_E_INVALID, "router targets are required");
-            const int k = net->router_n_targets ? net->router_n_targets[i] : 2;
-            if (k < 1 || k > 4) return fail(h, HS_E_UNSUPPORTED, "LP %d: RandomRouter with %d targets (1..4 are lowered)", i, k);
-            if ((k > 2 && !net->router_target2) || (k > 3 && !net->router_target3))
-                return fail(h, HS_E_INVALID, "router_target2 / router_target3 are required for routers with that many targets");
-            rtk[(size_t)i] = (uint8_t)k;
-            const int32_t tg[4] = {net->router_target0[i], net->router_target1[i], k > 2 ? net->router_target2[i] : -1,
-                                   k > 3 ? net->router_target3[i] : -1};
-            int n_link = 0;
-            for (int q = 0; q < k; ++q) {
-                if (tg[q] < -1) return fail(h, HS_E_INVALID, "LP %d: bad router target", i);
-                if (tg[q] >= 0) { if ((rc2 = use_link(i, tg[q]))) return rc2; ++n_link; }
-            }
-            if (n_link > 2) return fail(h, HS_E_UNSUPPORTED, "LP %d: a router with more than two NetworkLink targets is not lowered", i);
-            rt0[(size_t)i] = tg[0]; rt1[(size_t)i] = tg[1]; rt2[(size_t)i] = tg[2]; rt3[(size_t)i] = tg[3];
-        } else if (ek == HS_EGRESS_LINK) {
-            if (!net->link_of) return fail(h, HS_E_INVALID, "link_of is required");
-            lof[(size_t)i] = net->link_of[i];
-            if ((rc2 = use_link(i, lof[(size_t)i]))) return rc2;
-        } else if (ek != HS_EGRESS_NONE && ek != HS_EGRESS_SINK) {
-            return fail(h, HS_E_UNSUPPORTED, "LP %d: egress kind %d is not lowered", i, ek);
-        }
-    }
-    if (nl == 0) W = h->cfg.horizon_ns - h->cfg.start_ns + 1;   // no links: one window
-    h->window_ns = W;
-    int rc;
-    std::vector<uint64_t> rbase((size_t)n), lbase((size_t)(nl > 0 ? nl : 1));
-    std::vector<uint64_t> sbase((size_t)n);
-    HS_HIP(h, hipMemcpy(sbase.data(), h->P.stream_base, (size_t)n * 8, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; ++i) rbase[(size_t)i] = net->router_stream_base ? net->router_stream_base[i] : sbase[(size_t)i];
-    for (int l = 0; l < nl; ++l) {
-        const int64_t sl = net->link_src[l] - lo;   // incoming links of a shard (remote source) are never drawn from here
-        lbase[(size_t)l] = net->link_stream_base ? net->link_stream_base[l]
-                                                 : (sl >= 0 && sl < n ? sbase[(size_t)sl] : 0);
-    }
-    const size_t NL = (size_t)(nl > 0 ? nl : 1);
-    std::vector<uint8_t> jk(NL, (uint8_t)HS_LAT_CONSTANT);
-    std::vector<double> jm(NL, 0.0), lmin(NL, 1.0), lloss(NL, 0.0);
-    std::vector<int32_t> ldst(NL, 0);
-    for (int l = 0; l < nl; ++l) {
-        jk[(size_t)l] = net->link_jitter_kind ? net->link_jitter_kind[l] : (uint8_t)HS_LAT_CONSTANT;
-        jm[(size_t)l] = net->link_jitter_mean_s ? net->link_jitter_mean_s[l] : 0.0;
-        lmin[(size_t)l] = net->link_lat_min_s[l];
-        ldst[(size_t)l] = net->link_dst[l];
-        if (net->link_loss_rate) {
-            const double pl = net->link_loss_rate[l];
-            if (!(pl >= 0.0 && pl <= 1.0))                       // components/network/link.py:71-72
-                return fail(h, HS_E_INVALID, "link %d: packet_loss_rate must be in [0, 1], got %g", l, pl);
-            lloss[(size_t)l] = pl;
-        }
-    }
-    if ((rc = upload<uint8_t>(h, &h->NP.egress, net->egress_kind, (size_t)n, 0))) return rc;
-    if ((rc = upload<int32_t>(h, &h->NP.rt0, rt0.data(), (size_t)n, -1))) return rc;
-    if ((rc = upload<int32_t>(h, &h->NP.rt1, rt1.data(), (size_t)n, -1))) return rc;
-    if ((rc = upload<int32_t>(h, &h->NP.rt2, rt2.data(), (size_t)n, -1))) return rc;
-    if ((rc = upload<int32_t>(h, &h->NP.rt3, rt3.data(), (size_t)n, -1))) return rc;
-    if ((rc = upload<uint8_t>(h, &h->NP.rt_cnt, rtk.data(), (size_t)n, 2))) return rc;
-    if ((rc = upload<int32_t>(h, &h->NP.link_of, lof.data(), (size_t)n, -1))) return rc;
-    if ((rc = upload<uint64_t>(h, &h->NP.route_base, rbase.data(), (size_t)n, 0))) return rc;
-    h->NP.n_links = nl;
-    if ((rc = upload<int32_t>(h, &h->NP.link_dst, ldst.data(), NL, 0))) return rc;
-    if ((rc = upload<double>(h, &h->NP.link_lat_min, lmin.data(), NL, 0.0))) return rc;
-    if ((rc = upload<uint8_t>(h, &h->NP.link_jit_kind, jk.data(), NL, 1))) return rc;
-    if ((rc = upload<double>(h, &h->NP.link_jit_mean, jm.data(), NL, 0.0))) return rc;
-    if ((rc = upload<uint64_t>(h, &h->NP.link_base, lbase.data(), NL, 0))) return rc;
-    {   // table-decided losses (hs_network.link_drop_capacity): the bit tables, all clear, and the send log
-        std::vector<int64_t> doff(NL + 1, 0);
-        int64_t total = 0;
-        for (int l = 0; l < nl; ++l) {
-            const int64_t c = net->link_drop_capacity ? net->link_drop_capacity[l] : 0;
-            if (c < 0) return fail(h, HS_E_INVALID, "link %d: link_drop_capacity < 0", l);
-            if (c > 0 && lloss[(size_t)l] != 0.0)
-                return fail(h, HS_E_INVALID, "link %d: a link with a loss table must have link_loss_rate 0", l);
-            doff[(size_t)l] = total;
-            if (c > 0) { lloss[(size_t)l] = kLossTable; total += (c + 31) / 32 * 32; }
-        }
-        for (size_t l = (size_t)(nl > 0 ? nl : 0); l <= NL; ++l) doff[l] = total;
-        h->drop_off_host = doff;
-#ifdef HS_NO_LOSS_TABLES
-        if (total > 0) return fail(h, HS_E_UNSUPPORTED, "built without loss tables");
-#else
-        h->NP.loss_tables = nullptr;
-        if (total > 0) {
-            LossTables lt{};
-            uint32_t *bits = nullptr;
-            if ((rc = upload<int64_t>(h, &lt.drop_off, doff.data(), NL + 1, 0))) return rc;
-            if ((rc = dev_alloc(h, &bits, (size_t)(total / 32)))) return rc;
-            HS_HIP(h, hipMemset(bits, 0, (size_t)(total / 32) * sizeof(uint32_t)));
-            lt.drop_bits = bits;
-            h->drop_bits_dev = bits;
-            if ((rc = dev_alloc(h, &lt.send_log, (size_t)total * 3))) return rc;
-            if ((rc = dev_alloc(h, &lt.send_log_n, 1))) return rc;
-            HS_HIP(h, hipMemset(lt.send_log_n, 0, sizeof(unsigned long long)));
-            lt.send_log_cap = total;
-            lt.overflow_word = &h->tot->overflow;
-            h->loss_host = lt;
-            if ((rc = upload<LossTables>(h, &h->NP.loss_tables, &lt, 1, lt))) return rc;
-        }
-#endif
-    }
-    if ((rc = upload<double>(h, &h->NP.link_loss, lloss.data(), NL, 0.0))) return rc;
-    std::vector<int32_t> in_deg_h;
-    {   // incoming links per LP (CSR) and the transit floor of every link, for the asynchronous engine
-        std::vector<int32_t> in_off((size_t)n + 1, 0), in_links(NL, 0);
-        std::vector<int64_t> lat_ns(NL, 1);
-        {   // (a shard: only the links that END here, indexed by the local station)
-            auto here = [&](int l) { return net->link_dst[l] >= lo && net->link_dst[l] < lo + n; };
-            for (int l = 0; l < nl; ++l) if (here(l)) in_off[(size_t)(net->link_dst[l] - lo) + 1]++;
-            for (int i = 0; i < n; ++i) in_off[(size_t)i + 1] += in_off[(size_t)i];
-            std::vector<int32_t> cur(in_off.begin(), in_off.end() - 1);
-            for (int l = 0; l < nl; ++l) if (here(l)) in_links[(size_t)cur[(size_t)(net->link_dst[l] - lo)]++] = l;
-        }
-        for (int l = 0; l < nl; ++l) {
-            const double lc = (double)(int64_t)(net->link_lat_min_s[l] * 1e9) / 1e9;   // ConstantLatency.get_latency().to_seconds()
-            lat_ns[(size_t)l] = (int64_t)(lc * 1e9);
-        }
-        in_deg_h.resize((size_t)n);
-        for (int i = 0; i < n; ++i) in_deg_h[(size_t)i] = in_off[(size_t)i + 1] - in_off[(size_t)i];
-        if ((rc = upload<int32_t>(h, &h->NP.in_off, in_off.data(), (size_t)n + 1, 0))) return rc;
-        if ((rc = upload<int32_t>(h, &h->NP.in_links, in_links.data(), NL, 0))) return rc;
-        if ((rc = upload<int64_t>(h, &h->NP.link_lat_ns, lat_ns.data(), NL, 1))) return rc;
-    }
-    h->NP.link_gid = nullptr;
-    if (net->link_gid && nl > 0) {
-        std::vector<int32_t> gid((size_t)nl);
-        int64_t gmax = -1;
-        for (int l = 0; l < nl; ++l) {
-            if (net->link_gid[l] < 0 || net->link_gid[l] > 0x7fffffffll) return fail(h, HS_E_INVALID, "link %d: bad link_gid", l);
-            gid[(size_t)l] = (int32_t)net->link_gid[l];
-            if (net->link_gid[l] > gmax) gmax = net->link_gid[l];
-        }
-        h->n_gid = net->n_global_links > gmax + 1 ? net->n_global_links : gmax + 1;
-        std::vector<int32_t> g2l((size_t)h->n_gid, -1);
-        for (int l = 0; l < nl; ++l) {
-            if (g2l[(size_t)gid[(size_t)l]] >= 0) return fail(h, HS_E_INVALID, "link_gid %d appears twice", gid[(size_t)l]);
-            g2l[(size_t)gid[(size_t)l]] = l;
-        }
-        if ((rc = upload<int32_t>(h, &h->NP.link_gid, gid.data(), (size_t)nl, 0))) return rc;
-        const int32_t *g2l_dev = nullptr;
-        if ((rc = upload<int32_t>(h, &g2l_dev, g2l.data(), (size_t)h->n_gid, -1))) return rc;
-        h->h_gid2local = g2l;
-        h->gid2local = const_cast<int32_t *>(g2l_dev);
-    }
-    h->net_global = global;
-    h->n_global_lp = (int32_t)n_all;
-    h->SC = ShardCtl{};
-    h->SC.lp_base = lo;
-    h->h_link_dst.assign(ldst.begin(), ldst.end());
-    h->h_link_src.assign(net->link_src, net->link_src + nl);
-    const int bag = net->bag_capacity > 0 ? net->bag_capacity : 16;
-    h->NX.bag_cap = bag;
-    const size_t N = (size_t)n, NB = (size_t)n * (size_t)bag;
-#define ALN(field, count) if ((rc = dev_alloc(h, &h->NX.field, count))) return rc
-    ALN(route_k, N); ALN(routed, N); ALN(link_k, NL); ALN(link_in, NL); ALN(link_sent, NL); ALN(link_packets, NL); ALN(next_time, N);
-    ALN(pend_pay, N);
-    ALN(bag_cnt, N); ALN(bag_t, NB); ALN(bag_ts, NB); ALN(bag_cr, NB); ALN(bag_link, NB); ALN(bag_lin, NB);
-    ALN(in_cnt, 2 * N); ALN(in_t, 2 * NB); ALN(in_ts, 2 * NB); ALN(in_cr, 2 * NB); ALN(in_link, 2 * NB); ALN(in_lin, 2 * NB);
-    if ((rc = dev_alloc(h, &h->X.enqpay, N * (size_t)kEnqPay))) return rc;    // hs_net_async's ENQ payloads (general path)
-    int aqc = 1;
-    while (aqc < bag) aqc <<= 1;      // a power of two: queue slots are addressed with a mask, not a 64-bit modulo
-#ifndef HS_AQ_MIN
-#define HS_AQ_MIN 64
-#endif
-    if (aqc < HS_AQ_MIN) aqc = HS_AQ_MIN;   // pre-sent messages (hs_netstation.hpp `early_upto`) sit in the queue for a whole backlog
-    if (global && aqc < 256) aqc = 256; // a shard's incoming cross links are filled a whole exchange round at a time
-    h->NX.aq_cap = aqc;
-    h->NX.aq_on = 0;
-    h->NX.pk_base = h->cfg.start_ns;
-    if (nl > 0) {
-        const size_t NQ = NL * (size_t)aqc;
-        if (global) {
-            // a shard: the link queues other ranks may write into while this rank's kernel runs (LIVE exchange) -- uncached device
-            // memory, exportable with hipIpcGetMemHandle: a peer's stores arrive in HBM past this device's L2
-            void *a = nullptr, *b = nullptr, *c = nullptr;
-            if ((rc = uncached_alloc(h, &a, NQ * 4 * sizeof(int64_t)))) return rc;
-            if ((rc = uncached_alloc(h, &b, NL * sizeof(unsigned long long)))) return rc;
-            if ((rc = uncached_alloc(h, &c, NL * sizeof(int64_t)))) return rc;
-            h->NX.aq_rec = (int64_t *)a; h->NX.aq_head = (unsigned long long *)b; h->NX.aq_ea = (int64_t *)c;
-            HS_HIP(h, hipMemset(a, 0, NQ * 4 * sizeof(int64_t)));
-            HS_HIP(h, hipMemset(b, 0, NL * sizeof(unsigned long long)));
-            HS_HIP(h, hipMemset(c, 0, NL * sizeof(int64_t)));
-            ALN(aq_tail, NL);
-        } else {
-            ALN(aq_rec, NQ * 4); ALN(aq_tail, NL); ALN(aq_head, NL); ALN(aq_ea, NL);
-        }
-        ALN(early_upto, (size_t)n); ALN(d_pre, (size_t)n);
-        // the whole network in one cooperative launch (shards: hs_engine_shard_round); with probes, time-varying profiles
-        // or scheduled Requests the PF instantiation of the kernel (a profile's next arrival and the next scheduled Request
-        // are part of next_admission() / next_time(), which is all the bounds are made of)
-        // (the links' packed (bound, tail) words hold 44 bits of nanoseconds: 4.9 hours of simulated time)
-        const bool fits = h->cfg.horizon_ns - h->cfg.start_ns < (int64_t)kPkNever - 2 && aqc < (1 << (kPkTailBits - 2));
-        h->async_ok = !global && fits;
-        h->net_pf = h->any_probe || h->any_timevarying || h->any_sched || h->any_xsrc;
-        // the network's entity kinds are uniform: the specialised instantiation (hs_netstation.hpp HSU)
-        h->net_uni = h->uni_stations && h->f64_times && !global && !h->net_pf && h->C == 1;
-        for (int i = 0; i < n && h->net_uni; ++i) {
-            if (net->egress_kind[i] != HS_EGRESS_ROUTER) { h->net_uni = false; break; }
-            int n_link = 0, l1 = -1;
-            const int32_t tg[4] = {rt0[(size_t)i], rt1[(size_t)i], rt2[(size_t)i], rt3[(size_t)i]};
-            for (int q = 0; q < (int)rtk[(size_t)i]; ++q) if (tg[q] >= 0) { ++n_link; l1 = tg[q]; }
-            if (n_link != 1 || jk[(size_t)l1] != HS_LAT_EXPONENTIAL || lloss[(size_t)l1] != 0.0) h->net_uni = false;
-            if (h->net_uni && !(net->link_lat_min_s[l1] < 1e4 && (net->link_jitter_mean_s ? net->link_jitter_mean_s[l1] : 0.0) < 1e4)) h->net_uni = false;
-            if (h->net_uni && in_deg_h[(size_t)i] != 1) h->net_uni = false;        // exactly one incoming link per station
-        }
-    }
-#undef ALN
-    if (!h->L.sink_created_own) {   // not every completion reaches the Sink any more: explicit created_at column
-        if ((rc = dev_alloc(h, &h->L.sink_created_own, N * (size_t)h->L.cap))) return rc;
-    }
-    h->L.sink_created = h->L.sink_created_own;
-#ifndef HS_LOGS_ROW_MAJOR   // (scratch build: the [cap][n_lp] logs the network engines had until round 5)
-    h->L.lp_major = 1;          // an LP's records contiguous (hs_station.hpp RecordLogs::lp_major); nothing has been logged yet
-#endif
-    if (h->exact && h->cfg.mode == HS_MODE_SINGLE && !global) {
-        // a whole run on the single heap (an election the lineage key does not decide: tandem_fallback) takes one list cell per
-        // admitted Request, like tandem queues
-        const int64_t want = std::min<int64_t>(h->xs_host.pool_cap + (int64_t)n * h->L.cap, (int64_t)1 << 28);
-        if (want > h->xs_host.pool_cap) {
-            if ((rc = dev_alloc(h, &h->xs_host.pnext, (size_t)want))) return rc;
-            if ((rc = dev_alloc(h, &h->xs_host.pidx, (size_t)want))) return rc;
-            h->xs_host.pool_cap = want;
-        }
-    }
-    HS_HIP(h, hipDeviceSynchronize());      // (null-stream uploads and fills, as in hs_engine_set_stations)
-    h->is_net = true;
-    return HS_OK;
+    NetStationFacts sf;
+    sf.C = h->C; sf.uni_stations = h->uni_stations; sf.f64_times = h->f64_times;
+    sf.net_pf = h->any_probe || h->any_timevarying || h->any_sched || h->any_xsrc;
+    sf.exact = h->exact; sf.pool_cap = h->xs_host.pool_cap; sf.log_cap = h->L.cap;
+    sf.stream_base = h->h_stream_base.data();
+    NetworkPlan plan;
+    std::string err;
+    const int rc = plan_network(h->cfg, sf, *net, plan, err);
+    if (rc) return fail(h, rc, "%s", err.c_str());       // (refused: the engine is as it was before the call)
+    return apply_network(h, plan);
 }
 
 int hs_engine_set_stream(hs_engine *h, void *hip_stream, int external) {

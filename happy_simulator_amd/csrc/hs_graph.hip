@@ -23,7 +23,6 @@
 #include <algorithm>
 #include <mutex>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -624,24 +623,7 @@ struct hs_graph {
     std::string error;
 };
 
-static thread_local std::string g_graph_error;
-
-static int gfail(hs_graph *g, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (g) g->error = buf;
-    g_graph_error = buf;
-    return code;
-}
-
-#define HSG_HIP(g, expr)                                                                               \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return gfail(g, HS_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));       \
-    } while (0)
+#include "hs_host.hpp"
 
 // Slabs of destroyed handles wait here for the next handle of about their size: a Simulation spread over thousands of parts, or a sweep of
 // thousands of replicas, creates and frees as many handles back to back, and hipFree synchronises the device every time (0.2 ms).
@@ -680,24 +662,24 @@ static bool in_slab(const hs_graph *g, const void *p) {
 template <typename T>
 static int grow(hs_graph *g, T **buf, long long old_n, long long new_n) {
     T *nb = nullptr;
-    HSG_HIP(g, hipMalloc(&nb, (size_t)new_n * sizeof(T)));
-    if (*buf && old_n > 0) HSG_HIP(g, hipMemcpy(nb, *buf, (size_t)old_n * sizeof(T), hipMemcpyDeviceToDevice));
-    if (*buf && !in_slab(g, *buf)) HSG_HIP(g, hipFree(*buf));
+    HS_HIP(g, hipMalloc(&nb, (size_t)new_n * sizeof(T)));
+    if (*buf && old_n > 0) HS_HIP(g, hipMemcpy(nb, *buf, (size_t)old_n * sizeof(T), hipMemcpyDeviceToDevice));
+    if (*buf && !in_slab(g, *buf)) HS_HIP(g, hipFree(*buf));
     *buf = nb;
     return HS_OK;
 }
 
 static int ensure_stream(hs_graph *g) {
     if (g->stream) return HS_OK;
-    HSG_HIP(g, hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    HSG_HIP(g, hipEventCreate(&g->ev_a));
-    HSG_HIP(g, hipEventCreate(&g->ev_b));
+    HS_HIP(g, hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    HS_HIP(g, hipEventCreate(&g->ev_a));
+    HS_HIP(g, hipEventCreate(&g->ev_b));
     return HS_OK;
 }
 
 extern "C" {
 
-const char *hs_graph_last_error(const hs_graph *g) { return g ? g->error.c_str() : g_graph_error.c_str(); }
+const char *hs_graph_last_error(const hs_graph *g) { return g ? g->error.c_str() : g_last_error.c_str(); }
 
 void hs_graph_destroy(hs_graph *g) {
     if (!g) return;
@@ -715,24 +697,24 @@ void hs_graph_destroy(hs_graph *g) {
 }
 
 int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_graph **out) {
-    if (!cfg || !nd || !out) return gfail(nullptr, HS_E_INVALID, "hs_graph_create: null argument");
+    if (!cfg || !nd || !out) return fail(nullptr, HS_E_INVALID, "hs_graph_create: null argument");
     *out = nullptr;
-    if (cfg->struct_size != sizeof(hs_graph_config)) return gfail(nullptr, HS_E_INVALID, "hs_graph_config.struct_size mismatch (ABI)");
+    if (cfg->struct_size != sizeof(hs_graph_config)) return fail(nullptr, HS_E_INVALID, "hs_graph_config.struct_size mismatch (ABI)");
     const int n = nd->n_nodes;
-    if (n < 1) return gfail(nullptr, HS_E_INVALID, "n_nodes must be >= 1");
-    if (!nd->kind || !nd->target) return gfail(nullptr, HS_E_INVALID, "kind and target are required");
-    if (nd->n_rt < 0 || (nd->n_rt > 0 && !nd->rt_targets)) return gfail(nullptr, HS_E_INVALID, "rt_targets is required with n_rt > 0");
+    if (n < 1) return fail(nullptr, HS_E_INVALID, "n_nodes must be >= 1");
+    if (!nd->kind || !nd->target) return fail(nullptr, HS_E_INVALID, "kind and target are required");
+    if (nd->n_rt < 0 || (nd->n_rt > 0 && !nd->rt_targets)) return fail(nullptr, HS_E_INVALID, "rt_targets is required with n_rt > 0");
     int dev_count = 0;
     if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count < 1)
-        return gfail(nullptr, HS_E_NO_DEVICE, "no HIP device is visible (the engine has no CPU fallback)");
-    if (cfg->device < 0 || cfg->device >= dev_count) return gfail(nullptr, HS_E_INVALID, "device %d out of range", cfg->device);
+        return fail(nullptr, HS_E_NO_DEVICE, "no HIP device is visible (the engine has no CPU fallback)");
+    if (cfg->device < 0 || cfg->device >= dev_count) return fail(nullptr, HS_E_INVALID, "device %d out of range", cfg->device);
     if (cfg->start_ns < 0)        // (the Sinks' merged records hold non-negative times)
-        return gfail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
+        return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
     auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB; };
     int64_t kmax = 0;                                  // client ids any Source hands out: [0, kmax)
     for (int i = 0; i < n; ++i)
         if (nd->kind[i] == HS_NODE_SOURCE && nd->src_n_clients && nd->src_n_clients[i] > kmax) kmax = nd->src_n_clients[i];
-    if (kmax > (1ll << 26)) return gfail(nullptr, HS_E_UNSUPPORTED, "n_clients above 2^26 is not supported (client -> backend table)");
+    if (kmax > (1ll << 26)) return fail(nullptr, HS_E_UNSUPPORTED, "n_clients above 2^26 is not supported (client -> backend table)");
     std::vector<int32_t> key_table;
     std::vector<GParam> P((size_t)n);
     std::vector<hs::TickRow> rows;
@@ -747,37 +729,37 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
         p.stream_base = nd->stream_base ? nd->stream_base[i] : (uint64_t)i;
         p.conc = 1; p.lim = -1; p.rt_off = 0; p.rt_cnt = 0; p.mean = 0.0; p.lat_min = 0.0; p.loss = 0.0;
         p.rt_off = -1;
-        if (p.target < -1 || p.target >= n) return gfail(nullptr, HS_E_INVALID, "node %d: target %d out of range", i, p.target);
+        if (p.target < -1 || p.target >= n) return fail(nullptr, HS_E_INVALID, "node %d: target %d out of range", i, p.target);
         if (p.kind != HS_NODE_PROBE && p.target >= 0 && !takes_requests(p.target))
-            return gfail(nullptr, HS_E_INVALID, "node %d: its target %d takes no Requests (a Source or a Probe)", i, p.target);
+            return fail(nullptr, HS_E_INVALID, "node %d: its target %d takes no Requests (a Source or a Probe)", i, p.target);
         if (p.kind == HS_NODE_SOURCE && (seen_other || seen_probe))
-            return gfail(nullptr, HS_E_INVALID, "node %d: SOURCE nodes come first, in sources=[...] order", i);
+            return fail(nullptr, HS_E_INVALID, "node %d: SOURCE nodes come first, in sources=[...] order", i);
         if (p.kind == HS_NODE_PROBE && seen_other)
-            return gfail(nullptr, HS_E_INVALID, "node %d: PROBE nodes come behind the SOURCE nodes, in probes=[...] order", i);
+            return fail(nullptr, HS_E_INVALID, "node %d: PROBE nodes come behind the SOURCE nodes, in probes=[...] order", i);
         if (p.kind == HS_NODE_PROBE) seen_probe = true;
         else if (p.kind != HS_NODE_SOURCE) seen_other = true;
         switch (p.kind) {
         case HS_NODE_SOURCE: {
-            if (!nd->src_rate) return gfail(nullptr, HS_E_INVALID, "src_rate is required");
+            if (!nd->src_rate) return fail(nullptr, HS_E_INVALID, "src_rate is required");
             p.sub = nd->src_kind ? nd->src_kind[i] : (uint8_t)HS_SRC_POISSON;
-            if (p.sub != HS_SRC_POISSON && p.sub != HS_SRC_CONSTANT) return gfail(nullptr, HS_E_UNSUPPORTED, "node %d: source kind %d is not lowered", i, (int)p.sub);
+            if (p.sub != HS_SRC_POISSON && p.sub != HS_SRC_CONSTANT) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: source kind %d is not lowered", i, (int)p.sub);
             p.mean = nd->src_rate[i];
-            if (!(p.mean > 0.0) || !std::isfinite(p.mean)) return gfail(nullptr, HS_E_INVALID, "node %d: source rate must be > 0, got %g", i, p.mean);
+            if (!(p.mean > 0.0) || !std::isfinite(p.mean)) return fail(nullptr, HS_E_INVALID, "node %d: source rate must be > 0, got %g", i, p.mean);
             p.lim = nd->src_stop_after_ns ? nd->src_stop_after_ns[i] : -1;
-            if (p.target < 0) return gfail(nullptr, HS_E_INVALID, "node %d: a Source needs a target", i);
+            if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a Source needs a target", i);
             {
                 const int64_t nc = nd->src_n_clients ? nd->src_n_clients[i] : 0;
-                if (nc < 0) return gfail(nullptr, HS_E_INVALID, "node %d: src_n_clients < 0", i);
+                if (nc < 0) return fail(nullptr, HS_E_INVALID, "node %d: src_n_clients < 0", i);
                 p.conc = (int32_t)nc;
             }
             rate_sum += p.mean;
             ++n_src;
             const int pk = nd->src_profile_kind ? nd->src_profile_kind[i] : 0;
             if (pk != HS_PROF_CONSTANT) {
-                if (pk != HS_PROF_LINEAR_RAMP && pk != HS_PROF_SPIKE) return gfail(nullptr, HS_E_UNSUPPORTED, "node %d: profile kind %d is not lowered", i, pk);
-                if (!nd->src_profile_params) return gfail(nullptr, HS_E_INVALID, "src_profile_params is required with src_profile_kind");
+                if (pk != HS_PROF_LINEAR_RAMP && pk != HS_PROF_SPIKE) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: profile kind %d is not lowered", i, pk);
+                if (!nd->src_profile_params) return fail(nullptr, HS_E_INVALID, "src_profile_params is required with src_profile_kind");
                 const double *q = nd->src_profile_params + 4 * (size_t)i;
-                for (int j = 0; j < 4; ++j) if (!std::isfinite(q[j]) || q[j] < 0.0) return gfail(nullptr, HS_E_INVALID, "node %d: bad profile parameter %g", i, q[j]);
+                for (int j = 0; j < 4; ++j) if (!std::isfinite(q[j]) || q[j] < 0.0) return fail(nullptr, HS_E_INVALID, "node %d: bad profile parameter %g", i, q[j]);
                 hs::TickRow r{};
                 r.kind = (uint32_t)pk; r.poisson = p.sub == HS_SRC_POISSON ? 1u : 0u;
                 r.p0 = q[0]; r.p1 = q[1]; r.p2 = q[2]; r.p3 = q[3];
@@ -788,15 +770,15 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             }
         } break;
         case HS_NODE_PROBE: {
-            if (!nd->probe_metric || !nd->probe_interval_s) return gfail(nullptr, HS_E_INVALID, "probe_metric and probe_interval_s are required for probes");
+            if (!nd->probe_metric || !nd->probe_interval_s) return fail(nullptr, HS_E_INVALID, "probe_metric and probe_interval_s are required for probes");
             p.sub = nd->probe_metric[i];
             const double iv = nd->probe_interval_s[i];
-            if (!(iv > 0.0) || !std::isfinite(iv)) return gfail(nullptr, HS_E_INVALID, "node %d: Probe interval must be positive", i);   // probe.py:29-30
-            if (p.target < 0) return gfail(nullptr, HS_E_INVALID, "node %d: a Probe needs a target", i);
+            if (!(iv > 0.0) || !std::isfinite(iv)) return fail(nullptr, HS_E_INVALID, "node %d: Probe interval must be positive", i);   // probe.py:29-30
+            if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a Probe needs a target", i);
             const int tk = nd->kind[p.target];
             const bool ok = p.sub == HS_PROBE_GENERATED ? tk == HS_NODE_SOURCE : p.sub == HS_PROBE_RECEIVED ? tk == HS_NODE_SINK
                             : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
-            if (!ok) return gfail(nullptr, HS_E_UNSUPPORTED, "node %d: metric %d is not an attribute of its target (node kind %d)", i, (int)p.sub, tk);
+            if (!ok) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: metric %d is not an attribute of its target (node kind %d)", i, (int)p.sub, tk);
             const double rate = 1.0 / iv;                           // _ProbeProfile.rate (probe.py:31)
             int found = -1;
             for (size_t q = 0; q < rows.size() && found < 0; ++q)
@@ -812,57 +794,57 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
         } break;
         case HS_NODE_SERVER: {
             p.conc = nd->concurrency ? nd->concurrency[i] : 1;
-            if (p.conc < 1) return gfail(nullptr, HS_E_INVALID, "node %d: max_concurrent must be >= 1, got %d", i, p.conc);
+            if (p.conc < 1) return fail(nullptr, HS_E_INVALID, "node %d: max_concurrent must be >= 1, got %d", i, p.conc);
             p.sub = nd->lat_kind ? nd->lat_kind[i] : (uint8_t)HS_LAT_CONSTANT;
-            if (p.sub != HS_LAT_EXPONENTIAL && p.sub != HS_LAT_CONSTANT) return gfail(nullptr, HS_E_UNSUPPORTED, "node %d: service distribution kind %d is not lowered", i, (int)p.sub);
+            if (p.sub != HS_LAT_EXPONENTIAL && p.sub != HS_LAT_CONSTANT) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: service distribution kind %d is not lowered", i, (int)p.sub);
             p.mean = nd->lat_mean_s ? nd->lat_mean_s[i] : 0.0;
-            if (!(p.mean >= 0.0) || !std::isfinite(p.mean)) return gfail(nullptr, HS_E_INVALID, "node %d: bad service mean %g", i, p.mean);
-            if (p.sub == HS_LAT_EXPONENTIAL && !(p.mean > 0.0)) return gfail(nullptr, HS_E_INVALID, "node %d: exponential service needs mean > 0", i);
+            if (!(p.mean >= 0.0) || !std::isfinite(p.mean)) return fail(nullptr, HS_E_INVALID, "node %d: bad service mean %g", i, p.mean);
+            if (p.sub == HS_LAT_EXPONENTIAL && !(p.mean > 0.0)) return fail(nullptr, HS_E_INVALID, "node %d: exponential service needs mean > 0", i);
             p.lim = nd->queue_cap ? nd->queue_cap[i] : -1;
         } break;
         case HS_NODE_SINK: break;
         case HS_NODE_LINK: {
             p.sub = nd->lat_kind ? nd->lat_kind[i] : (uint8_t)HS_LAT_CONSTANT;
-            if (p.sub != HS_LAT_EXPONENTIAL && p.sub != HS_LAT_CONSTANT) return gfail(nullptr, HS_E_UNSUPPORTED, "node %d: jitter kind %d is not lowered", i, (int)p.sub);
+            if (p.sub != HS_LAT_EXPONENTIAL && p.sub != HS_LAT_CONSTANT) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: jitter kind %d is not lowered", i, (int)p.sub);
             p.mean = nd->lat_mean_s ? nd->lat_mean_s[i] : 0.0;
-            if (p.sub == HS_LAT_EXPONENTIAL && !(p.mean > 0.0)) return gfail(nullptr, HS_E_INVALID, "node %d: exponential jitter needs mean > 0", i);
-            if (!(p.mean >= 0.0) || !std::isfinite(p.mean)) return gfail(nullptr, HS_E_INVALID, "node %d: bad jitter mean %g", i, p.mean);
+            if (p.sub == HS_LAT_EXPONENTIAL && !(p.mean > 0.0)) return fail(nullptr, HS_E_INVALID, "node %d: exponential jitter needs mean > 0", i);
+            if (!(p.mean >= 0.0) || !std::isfinite(p.mean)) return fail(nullptr, HS_E_INVALID, "node %d: bad jitter mean %g", i, p.mean);
             p.lat_min = nd->link_lat_min_s ? nd->link_lat_min_s[i] : 0.0;
-            if (!(p.lat_min >= 0.0) || !std::isfinite(p.lat_min)) return gfail(nullptr, HS_E_INVALID, "node %d: bad link latency %g", i, p.lat_min);
+            if (!(p.lat_min >= 0.0) || !std::isfinite(p.lat_min)) return fail(nullptr, HS_E_INVALID, "node %d: bad link latency %g", i, p.lat_min);
             p.loss = nd->link_loss_rate ? nd->link_loss_rate[i] : 0.0;
-            if (!(p.loss >= 0.0 && p.loss <= 1.0)) return gfail(nullptr, HS_E_INVALID, "node %d: packet_loss_rate must be in [0, 1], got %g", i, p.loss);   // link.py:71-72
+            if (!(p.loss >= 0.0 && p.loss <= 1.0)) return fail(nullptr, HS_E_INVALID, "node %d: packet_loss_rate must be in [0, 1], got %g", i, p.loss);   // link.py:71-72
         } break;
         case HS_NODE_ROUTER: {
-            if (!nd->rt_off || !nd->rt_cnt) return gfail(nullptr, HS_E_INVALID, "rt_off and rt_cnt are required for routers");
+            if (!nd->rt_off || !nd->rt_cnt) return fail(nullptr, HS_E_INVALID, "rt_off and rt_cnt are required for routers");
             p.rt_off = nd->rt_off[i]; p.rt_cnt = nd->rt_cnt[i];
-            if (p.rt_cnt < 1) return gfail(nullptr, HS_E_INVALID, "node %d: a RandomRouter needs at least one target", i);
-            if (p.rt_off < 0 || (long long)p.rt_off + p.rt_cnt > nd->n_rt) return gfail(nullptr, HS_E_INVALID, "node %d: router targets out of range", i);
+            if (p.rt_cnt < 1) return fail(nullptr, HS_E_INVALID, "node %d: a RandomRouter needs at least one target", i);
+            if (p.rt_off < 0 || (long long)p.rt_off + p.rt_cnt > nd->n_rt) return fail(nullptr, HS_E_INVALID, "node %d: router targets out of range", i);
             for (int q = 0; q < p.rt_cnt; ++q) {
                 const int t = nd->rt_targets[p.rt_off + q];
-                if (t < 0 || t >= n || !takes_requests(t)) return gfail(nullptr, HS_E_INVALID, "node %d: router target %d takes no Requests", i, t);
+                if (t < 0 || t >= n || !takes_requests(t)) return fail(nullptr, HS_E_INVALID, "node %d: router target %d takes no Requests", i, t);
             }
         } break;
         case HS_NODE_LB: {
-            if (!nd->rt_off || !nd->rt_cnt) return gfail(nullptr, HS_E_INVALID, "rt_off and rt_cnt are required for LoadBalancers");
+            if (!nd->rt_off || !nd->rt_cnt) return fail(nullptr, HS_E_INVALID, "rt_off and rt_cnt are required for LoadBalancers");
             p.rt_off = nd->rt_off[i]; p.rt_cnt = nd->rt_cnt[i];
-            if (p.rt_cnt < 0 || p.rt_off < 0 || (long long)p.rt_off + p.rt_cnt > nd->n_rt) return gfail(nullptr, HS_E_INVALID, "node %d: backends out of range", i);
+            if (p.rt_cnt < 0 || p.rt_off < 0 || (long long)p.rt_off + p.rt_cnt > nd->n_rt) return fail(nullptr, HS_E_INVALID, "node %d: backends out of range", i);
             p.sub = nd->lb_strategy ? nd->lb_strategy[i] : (uint8_t)HS_LB_ROUND_ROBIN;                  // load_balancer.py:112: the default
-            if (p.sub > HS_LB_RANDOM) return gfail(nullptr, HS_E_UNSUPPORTED, "node %d: load-balancing strategy %d is not lowered", i, (int)p.sub);
+            if (p.sub > HS_LB_RANDOM) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: load-balancing strategy %d is not lowered", i, (int)p.sub);
             for (int q = 0; q < p.rt_cnt; ++q) {
                 const int t = nd->rt_targets[p.rt_off + q];
-                if (t < 0 || t >= n || nd->kind[t] != HS_NODE_SERVER) return gfail(nullptr, HS_E_UNSUPPORTED, "node %d: backend %d is not a Server (only Server backends are lowered)", i, t);
+                if (t < 0 || t >= n || nd->kind[t] != HS_NODE_SERVER) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: backend %d is not a Server (only Server backends are lowered)", i, t);
             }
             p.lim = -1; p.conc = 0;
             if (p.sub == HS_LB_CONSISTENT_HASH && p.rt_cnt > 0) {
                 const int V = nd->lb_vnodes ? nd->lb_vnodes[i] : 100;
-                if (V < 1) return gfail(nullptr, HS_E_INVALID, "node %d: virtual_nodes must be >= 1, got %d", i, V);   // strategies.py:355-356
-                if (!nd->names || !nd->name_off) return gfail(nullptr, HS_E_INVALID, "names / name_off are required for a ConsistentHash LoadBalancer");
+                if (V < 1) return fail(nullptr, HS_E_INVALID, "node %d: virtual_nodes must be >= 1, got %d", i, V);   // strategies.py:355-356
+                if (!nd->names || !nd->name_off) return fail(nullptr, HS_E_INVALID, "names / name_off are required for a ConsistentHash LoadBalancer");
                 std::string names;
                 std::vector<int32_t> off(1, 0);
                 for (int q = 0; q < p.rt_cnt; ++q) {
                     const int t = nd->rt_targets[p.rt_off + q];
                     const int nl = nd->name_off[t + 1] - nd->name_off[t];
-                    if (nl < 1 || nl > 200) return gfail(nullptr, HS_E_INVALID, "node %d: backend %d needs a name (1 .. 200 bytes)", i, t);
+                    if (nl < 1 || nl > 200) return fail(nullptr, HS_E_INVALID, "node %d: backend %d needs a name (1 .. 200 bytes)", i, t);
                     names.append(nd->names + nd->name_off[t], (size_t)nl);
                     off.push_back((int32_t)names.size());
                 }
@@ -875,7 +857,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
                 }
             }
         } break;
-        default: return gfail(nullptr, HS_E_UNSUPPORTED, "node %d: kind %d is not lowered", i, (int)p.kind);
+        default: return fail(nullptr, HS_E_UNSUPPORTED, "node %d: kind %d is not lowered", i, (int)p.kind);
         }
         P[(size_t)i] = p;
     }
@@ -883,14 +865,14 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     g->cfg = *cfg; g->n = n; g->n_rt = nd->n_rt; g->params = P; g->rows = rows; g->row_rate = row_rate;
     for (int i = 0; i < n; ++i) {
         const GParam &p = P[(size_t)i];
-        const double draw = p.sub == HS_LAT_EXPONENTIAL ? 36.8 * p.mean : p.mean;       // (-log(2^-53) = 36.7 means at most)
-        if (p.kind == HS_NODE_SOURCE) g->reach_s = std::max(g->reach_s, 36.8 / p.mean);
+        const double draw = p.sub == HS_LAT_EXPONENTIAL ? hs::kLongestExpDraw * p.mean : p.mean;       // (-log(2^-53) = 36.7 means at most)
+        if (p.kind == HS_NODE_SOURCE) g->reach_s = std::max(g->reach_s, hs::kLongestExpDraw / p.mean);
         else if (p.kind == HS_NODE_SERVER) g->reach_s = std::max(g->reach_s, draw);
         else if (p.kind == HS_NODE_LINK) g->reach_s = std::max(g->reach_s, p.lat_min + draw);
         else if (p.kind == HS_NODE_PROBE) g->reach_s = std::max(g->reach_s, 1.0 / row_rate[(size_t)p.rt_off]);
     }
-#define HSG_TRY(expr) do { int rc_ = (expr); if (rc_) { g_graph_error = g->error; hs_graph_destroy(g); return rc_; } } while (0)
-#define HSG_HIPD(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { gfail(g, HS_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); g_graph_error = g->error; hs_graph_destroy(g); return HS_E_HIP; } } while (0)
+#define HSG_TRY(expr) do { int rc_ = (expr); if (rc_) { g_last_error = g->error; hs_graph_destroy(g); return rc_; } } while (0)
+#define HSG_HIPD(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fail(g, HS_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); g_last_error = g->error; hs_graph_destroy(g); return HS_E_HIP; } } while (0)
     HSG_HIPD(hipSetDevice(cfg->device));
     GCtl &c = g->ctl;
     c.n = n; c.seed = cfg->seed; c.start_ns = cfg->start_ns; c.budget = kBudget;
@@ -953,10 +935,10 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
 }
 
 int hs_graph_schedule(hs_graph *g, int32_t node, int64_t time_ns) {
-    if (!g) return gfail(g, HS_E_INVALID, "null handle");
-    if (node < 0 || node >= g->n) return gfail(g, HS_E_INVALID, "schedule: node %d out of range", node);
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "schedule: node %d out of range", node);
     if (g->params[(size_t)node].kind == HS_NODE_SOURCE)
-        return gfail(g, HS_E_UNSUPPORTED, "schedule: node %d is a Source (only Requests for a Server, Sink, link or router are lowered)", node);
+        return fail(g, HS_E_UNSUPPORTED, "schedule: node %d is a Source (only Requests for a Server, Sink, link or router are lowered)", node);
     g->sched_node.push_back(node);
     g->sched_t.push_back(time_ns);
     return HS_OK;
@@ -973,26 +955,26 @@ static int build_tables(hs_graph *g, int64_t horizon) {
     for (double r : g->row_rate) {
         const double mean = r * (span_s > 0 ? span_s : 0.0);
         const double want = mean + 10.0 * std::sqrt(mean + 1.0) + 72.0;
-        if (want > 4e9) return gfail(g, HS_E_INVALID, "a tick table up to %lld ns would need %.3g ticks", (long long)horizon, want);
+        if (want > 4e9) return fail(g, HS_E_INVALID, "a tick table up to %lld ns would need %.3g ticks", (long long)horizon, want);
         if ((int64_t)want > cap) cap = (int64_t)want;
     }
     const long long budget = g->cfg.profile_budget > 0 ? g->cfg.profile_budget : hs::kDefaultLaneBudget;
     for (int attempt = 0; attempt < 8; ++attempt) {
-        if ((double)g->rows.size() * (double)cap * 8.0 > 64e9) return gfail(g, HS_E_INVALID, "tick tables would need %.1f GB", (double)g->rows.size() * (double)cap * 8.0 / 1e9);
+        if ((double)g->rows.size() * (double)cap * 8.0 > 64e9) return fail(g, HS_E_INVALID, "tick tables would need %.1f GB", (double)g->rows.size() * (double)cap * 8.0 / 1e9);
         if (cap != g->tick_cap || !g->d_ticks) {
-            if (g->d_ticks) HSG_HIP(g, hipFree(g->d_ticks));
+            if (g->d_ticks) HS_HIP(g, hipFree(g->d_ticks));
             g->d_ticks = nullptr;
-            HSG_HIP(g, hipMalloc(&g->d_ticks, g->rows.size() * (size_t)cap * sizeof(int64_t)));
+            HS_HIP(g, hipMalloc(&g->d_ticks, g->rows.size() * (size_t)cap * sizeof(int64_t)));
             g->tick_cap = cap;
         }
         { const int rc = ensure_stream(g); if (rc) return rc; }
-        HSG_HIP(g, hs::tick_tables_launch(g->stream, g->d_rows, (int)g->rows.size(), g->cfg.start_ns, horizon, cap, g->d_ticks, g->d_tick_count,
+        HS_HIP(g, hs::tick_tables_launch(g->stream, g->d_rows, (int)g->rows.size(), g->cfg.start_ns, horizon, cap, g->d_ticks, g->d_tick_count,
                                           g->d_tick_status, budget, false));
-        HSG_HIP(g, hipStreamSynchronize(g->stream));
+        HS_HIP(g, hipStreamSynchronize(g->stream));
         unsigned long long st[2] = {0ull, 0ull};
-        HSG_HIP(g, hipMemcpy(st, g->d_tick_status, sizeof st, hipMemcpyDeviceToHost));
+        HS_HIP(g, hipMemcpy(st, g->d_tick_status, sizeof st, hipMemcpyDeviceToHost));
         if (st[0] != 0ull)
-            return gfail(g, HS_E_UNSUPPORTED, "node %lld: one tick of its time-varying Source / Probe needs more than 64 x %lld adaptive-Simpson "
+            return fail(g, HS_E_UNSUPPORTED, "node %lld: one tick of its time-varying Source / Probe needs more than 64 x %lld adaptive-Simpson "
                          "intervals (hs_graph_config.profile_budget raises the limit) -- refused instead of stalling the device",
                          (long long)st[0] - 2, budget);
         if (st[1] == 0ull) {
@@ -1002,14 +984,14 @@ static int build_tables(hs_graph *g, int64_t horizon) {
         }
         cap *= 2;                                           // (a Poisson stream that ran ahead of its mean: a longer table)
     }
-    return gfail(g, HS_E_OVERFLOW, "a tick table overflowed after eight doublings");
+    return fail(g, HS_E_OVERFLOW, "a tick table overflowed after eight doublings");
 }
 
 // What a run needs before its first launch: tick tables up to the end, the schedule()d entries on the device.
 static int prepare_run(hs_graph *g, int64_t end_ns) {
     GCtl &c = g->ctl;
     if (!hs::reach_fits_int64(end_ns, g->reach_s))
-        return gfail(g, HS_E_UNSUPPORTED, "the end (%lld ns) plus one longest step (%.6g s: 36.8 / the smallest rate, 36.8 x the largest "
+        return fail(g, HS_E_UNSUPPORTED, "the end (%lld ns) plus one longest step (%.6g s: 36.8 / the smallest rate, 36.8 x the largest "
                      "exponential mean, a constant service, a link's delay or a probe interval) leaves int64 nanoseconds -- refused, "
                      "never wrapped", (long long)end_ns, g->reach_s);
     // table-driven streams: up to this end when it is a real horizon, else (an auto-terminating run) a minute at a time
@@ -1022,16 +1004,16 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
     }
     const long long ns = (long long)g->sched_node.size();
     if (ns > g->d_sched_cap) {
-        if (g->d_sched_node) HSG_HIP(g, hipFree(g->d_sched_node));
-        if (g->d_sched_t) HSG_HIP(g, hipFree(g->d_sched_t));
+        if (g->d_sched_node) HS_HIP(g, hipFree(g->d_sched_node));
+        if (g->d_sched_t) HS_HIP(g, hipFree(g->d_sched_t));
         g->d_sched_node = nullptr; g->d_sched_t = nullptr;
         g->d_sched_cap = ns + ns / 2 + 16;
-        HSG_HIP(g, hipMalloc(&g->d_sched_node, (size_t)g->d_sched_cap * sizeof(int32_t)));
-        HSG_HIP(g, hipMalloc(&g->d_sched_t, (size_t)g->d_sched_cap * sizeof(int64_t)));
+        HS_HIP(g, hipMalloc(&g->d_sched_node, (size_t)g->d_sched_cap * sizeof(int32_t)));
+        HS_HIP(g, hipMalloc(&g->d_sched_t, (size_t)g->d_sched_cap * sizeof(int64_t)));
     }
     if (ns > 0) {
-        HSG_HIP(g, hipMemcpy(g->d_sched_node, g->sched_node.data(), (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice));
-        HSG_HIP(g, hipMemcpy(g->d_sched_t, g->sched_t.data(), (size_t)ns * sizeof(int64_t), hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(g->d_sched_node, g->sched_node.data(), (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(g->d_sched_t, g->sched_t.data(), (size_t)ns * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     c.sched_node = g->d_sched_node; c.sched_t = g->d_sched_t; c.n_sched = ns;
     c.end_ns = end_ns;
@@ -1043,16 +1025,16 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
 static int after_launch_with(hs_graph *g, int status, long long processed, bool *done);
 static int after_launch(hs_graph *g, bool *done) {
     GVars v;
-    HSG_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+    HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
     return after_launch_with(g, v.status, v.processed, done);
 }
 static int after_launch_with(hs_graph *g, int status, long long processed, bool *done) {
     GCtl &c = g->ctl;
     g->launches++;
     struct { int status; long long processed; } v{status, processed};
-    if (v.status & kBadKind) return gfail(g, HS_E_INVALID, "an event of unknown kind reached the loop (internal error)");
+    if (v.status & kBadKind) return fail(g, HS_E_INVALID, "an event of unknown kind reached the loop (internal error)");
     if (g->cfg.max_events > 0 && v.processed > g->cfg.max_events)
-        return gfail(g, HS_E_UNSUPPORTED, "the run exceeds max_events = %lld events on the single-heap path (one lane, ~2.4 us per event); "
+        return fail(g, HS_E_UNSUPPORTED, "the run exceeds max_events = %lld events on the single-heap path (one lane, ~2.4 us per event); "
                      "raise max_events, or bring the graph into the shape the station engines take", (long long)g->cfg.max_events);
     if (v.status & kGrowHeap) {
         const long long nc = c.heap_cap * 2;
@@ -1060,7 +1042,7 @@ static int after_launch_with(hs_graph *g, int status, long long processed, bool 
         c.heap_cap = nc;
     }
     if (v.status & kGrowReq) {
-        if (c.req_cap >= (1 << 30)) return gfail(g, HS_E_OVERFLOW, "more than 2^30 Requests alive at once");
+        if (c.req_cap >= (1 << 30)) return fail(g, HS_E_OVERFLOW, "more than 2^30 Requests alive at once");
         const int nc = c.req_cap * 2;
         int rc = grow(g, &c.reqs, c.req_cap, nc); if (rc) return rc;
         c.req_cap = nc;
@@ -1070,7 +1052,7 @@ static int after_launch_with(hs_graph *g, int status, long long processed, bool 
         // ticks every table holds beyond its horizon)
         const int64_t span = g->tick_horizon - g->cfg.start_ns;
         int64_t nh = g->cfg.start_ns + (span > 0 ? 2 * span : 1000000000ll);
-        if (nh <= g->tick_horizon) return gfail(g, HS_E_OVERFLOW, "the tick tables cannot grow any further");
+        if (nh <= g->tick_horizon) return fail(g, HS_E_OVERFLOW, "the tick tables cannot grow any further");
         const int rc = build_tables(g, nh);
         if (rc) return rc;
     }
@@ -1090,23 +1072,23 @@ static int after_launch_with(hs_graph *g, int status, long long processed, bool 
 extern "C" {
 
 int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
-    if (!g) return gfail(g, HS_E_INVALID, "null handle");
-    HSG_HIP(g, hipSetDevice(g->cfg.device));
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
     {
         const int rc = prepare_run(g, end_ns);
         if (rc) return rc;
     }
     { const int rc = ensure_stream(g); if (rc) return rc; }
-    HSG_HIP(g, hipEventRecord(g->ev_a, g->stream));
+    HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
         hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        HSG_HIP(g, hipGetLastError());
-        HSG_HIP(g, hipStreamSynchronize(g->stream));
+        HS_HIP(g, hipGetLastError());
+        HS_HIP(g, hipStreamSynchronize(g->stream));
         const int rc = after_launch(g, &done);
         if (rc) return rc;
     }
-    HSG_HIP(g, hipEventRecord(g->ev_b, g->stream));
-    HSG_HIP(g, hipStreamSynchronize(g->stream));
+    HS_HIP(g, hipEventRecord(g->ev_b, g->stream));
+    HS_HIP(g, hipStreamSynchronize(g->stream));
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, g->ev_a, g->ev_b) == hipSuccess) g->last_run_ms = ms;
     g->ran = true;
@@ -1114,25 +1096,25 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
 }
 
 static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
-    if (!gs || n < 1) return gfail(nullptr, HS_E_INVALID, "no handles");
+    if (!gs || n < 1) return fail(nullptr, HS_E_INVALID, "no handles");
     for (int i = 0; i < n; ++i) {
-        if (!gs[i]) return gfail(nullptr, HS_E_INVALID, "handle %d is null", i);
-        if (gs[i]->cfg.device != gs[0]->cfg.device) return gfail(gs[i], HS_E_INVALID, "handle %d lives on another device", i);
+        if (!gs[i]) return fail(nullptr, HS_E_INVALID, "handle %d is null", i);
+        if (gs[i]->cfg.device != gs[0]->cfg.device) return fail(gs[i], HS_E_INVALID, "handle %d lives on another device", i);
     }
     {   // (a handle listed twice would run on one heap from two workgroups)
         std::vector<hs_graph *> sorted(gs, gs + n);
         std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return gfail(gs[0], HS_E_INVALID, "a handle is listed twice");
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(gs[0], HS_E_INVALID, "a handle is listed twice");
     }
     hs_graph *g0 = gs[0];
-    HSG_HIP(g0, hipSetDevice(g0->cfg.device));
+    HS_HIP(g0, hipSetDevice(g0->cfg.device));
     { const int rc = ensure_stream(g0); if (rc) return rc; }
     for (int i = 0; i < n; ++i) {
         const int rc = prepare_run(gs[i], end_ns);
-        if (rc) { if (gs[i] != g0) gfail(g0, rc, "graph %d: %s", i, gs[i]->error.c_str()); return rc; }
+        if (rc) { if (gs[i] != g0) fail(g0, rc, "graph %d: %s", i, gs[i]->error.c_str()); return rc; }
     }
     GCtl *d_ctl = nullptr;
-    HSG_HIP(g0, hipMalloc(&d_ctl, (size_t)n * (sizeof(GCtl) + kBatchStat * sizeof(long long))));
+    HS_HIP(g0, hipMalloc(&d_ctl, (size_t)n * (sizeof(GCtl) + kBatchStat * sizeof(long long))));
     long long *d_stat = reinterpret_cast<long long *>(d_ctl + n);
     std::vector<long long> h_stat;
     std::vector<int> pending((size_t)n);
@@ -1159,7 +1141,7 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
             const long long *st = &h_stat[(size_t)kBatchStat * slot++];
             rc = after_launch_with(gs[i], (int)st[0], st[1], &done);
             gs[i]->pending_events = st[2]; gs[i]->earliest_ns = st[3];
-            if (rc) { if (gs[i] != g0) gfail(g0, rc, "graph %d: %s", i, gs[i]->error.c_str()); break; }
+            if (rc) { if (gs[i] != g0) fail(g0, rc, "graph %d: %s", i, gs[i]->error.c_str()); break; }
             if (done) gs[i]->ran = true; else left.push_back(i);
         }
         pending.swap(left);
@@ -1173,7 +1155,7 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
     }
     (void)hipFree(d_ctl);
     if (rc) return rc;
-    if (he != hipSuccess) return gfail(g0, HS_E_HIP, "batch launch: %s", hipGetErrorString(he));
+    if (he != hipSuccess) return fail(g0, HS_E_HIP, "batch launch: %s", hipGetErrorString(he));
     return HS_OK;
 }
 
@@ -1200,35 +1182,35 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
     hs_graph *g = gs[best];
     {
         const int rc = ensure_stream(g);
-        if (rc) { gfail(g0, rc, "%s", g->error.c_str()); return rc; }
+        if (rc) { fail(g0, rc, "%s", g->error.c_str()); return rc; }
     }
     GCtl one = g->ctl;
     one.part = 1; one.budget = 1; one.end_ns = INT64_MAX;
     GVars before;
-    HSG_HIP(g0, hipMemcpy(&before, g->ctl.V, sizeof before, hipMemcpyDeviceToHost));
+    HS_HIP(g0, hipMemcpy(&before, g->ctl.V, sizeof before, hipMemcpyDeviceToHost));
     for (int attempt = 0; attempt < 64; ++attempt) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count;
         hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, one);
-        HSG_HIP(g0, hipGetLastError());
-        HSG_HIP(g0, hipStreamSynchronize(g->stream));
+        HS_HIP(g0, hipGetLastError());
+        HS_HIP(g0, hipStreamSynchronize(g->stream));
         bool done = false;
         const int rc = after_launch(g, &done);       // (enlarges what the one event needed)
-        if (rc) { if (g != g0) gfail(g0, rc, "%s", g->error.c_str()); return rc; }
+        if (rc) { if (g != g0) fail(g0, rc, "%s", g->error.c_str()); return rc; }
         if (g->undecided) return 1;                  // (the popped event was dropped: the handle's state is no answer any more)
         GVars now;
-        HSG_HIP(g0, hipMemcpy(&now, g->ctl.V, sizeof now, hipMemcpyDeviceToHost));
+        HS_HIP(g0, hipMemcpy(&now, g->ctl.V, sizeof now, hipMemcpyDeviceToHost));
         if (now.processed > before.processed || now.heap_len <= 0) return HS_OK;
     }
-    return gfail(g0, HS_E_OVERFLOW, "the event beyond the end could not be processed");
+    return fail(g0, HS_E_OVERFLOW, "the event beyond the end could not be processed");
 }
 
 int hs_graph_get_summary(hs_graph *g, hs_summary *out) {
-    if (!g || !out) return gfail(g, HS_E_INVALID, "null argument");
-    HSG_HIP(g, hipSetDevice(g->cfg.device));
+    if (!g || !out) return fail(g, HS_E_INVALID, "null argument");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
     GVars v;
-    HSG_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+    HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
     std::memset(out, 0, sizeof *out);
     out->events_processed = v.processed;
     for (int k = 0; k < HS_EV_KINDS; ++k) out->events_by_kind[k] = v.by_kind[k];
@@ -1242,10 +1224,10 @@ int hs_graph_get_summary(hs_graph *g, hs_summary *out) {
 }
 
 int hs_graph_get_stats(hs_graph *g, hs_graph_stats *o) {
-    if (!g || !o) return gfail(g, HS_E_INVALID, "null argument");
-    HSG_HIP(g, hipSetDevice(g->cfg.device));
+    if (!g || !o) return fail(g, HS_E_INVALID, "null argument");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
     std::vector<GState> S((size_t)g->n);
-    HSG_HIP(g, hipMemcpy(S.data(), g->ctl.S, (size_t)g->n * sizeof(GState), hipMemcpyDeviceToHost));
+    HS_HIP(g, hipMemcpy(S.data(), g->ctl.S, (size_t)g->n * sizeof(GState), hipMemcpyDeviceToHost));
     for (int i = 0; i < g->n; ++i) {
         const GState &s = S[(size_t)i];
         const int k = g->params[(size_t)i].kind;
@@ -1272,20 +1254,20 @@ int hs_graph_get_stats(hs_graph *g, hs_graph_stats *o) {
         }
     }
     if (o->rt_taken && g->n_rt > 0)
-        HSG_HIP(g, hipMemcpy(o->rt_taken, g->ctl.rt_taken, (size_t)g->n_rt * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HS_HIP(g, hipMemcpy(o->rt_taken, g->ctl.rt_taken, (size_t)g->n_rt * sizeof(int64_t), hipMemcpyDeviceToHost));
     return HS_OK;
 }
 
 int64_t hs_graph_read_records(hs_graph *g, int32_t *node, int64_t *t_ns, int64_t *created_ns, int64_t cap) {
-    if (!g) return gfail(g, HS_E_INVALID, "null handle");
-    if (hipSetDevice(g->cfg.device) != hipSuccess) return gfail(g, HS_E_HIP, "hipSetDevice failed");
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (hipSetDevice(g->cfg.device) != hipSuccess) return fail(g, HS_E_HIP, "hipSetDevice failed");
     GVars v;
-    if (hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return gfail(g, HS_E_HIP, "reading the run's scalars failed");
+    if (hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return fail(g, HS_E_HIP, "reading the run's scalars failed");
     const long long m = std::min<long long>(v.rec_n, cap > 0 ? cap : 0);
     if (m > 0) {
-        if (node && hipMemcpy(node, g->ctl.rec_node, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return gfail(g, HS_E_HIP, "record copy failed");
-        if (t_ns && hipMemcpy(t_ns, g->ctl.rec_t, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return gfail(g, HS_E_HIP, "record copy failed");
-        if (created_ns && hipMemcpy(created_ns, g->ctl.rec_cr, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return gfail(g, HS_E_HIP, "record copy failed");
+        if (node && hipMemcpy(node, g->ctl.rec_node, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return fail(g, HS_E_HIP, "record copy failed");
+        if (t_ns && hipMemcpy(t_ns, g->ctl.rec_t, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return fail(g, HS_E_HIP, "record copy failed");
+        if (created_ns && hipMemcpy(created_ns, g->ctl.rec_cr, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return fail(g, HS_E_HIP, "record copy failed");
     }
     return v.rec_n;
 }

@@ -27,7 +27,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -1734,9 +1733,9 @@ __global__ void hs_lb_clear(LbTotals *tot) {
 
 using hs::ring::Md5; using hs::ring::RingPoint; using hs::ring::md5_u128; using hs::ring::ring_select;   // (hs_ring.hpp)
 
-thread_local std::string g_lb_error;
-
 }  // namespace
+
+#include "hs_host.hpp"
 
 struct hs_lb {
     hs_lb_config cfg{};
@@ -1794,45 +1793,6 @@ struct hs_lb {
 
 namespace {
 
-int lfail(hs_lb *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->error = buf;
-    g_lb_error = buf;
-    return code;
-}
-
-#define LB_HIP(h, expr)                                                                                  \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return lfail(h, HS_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
-
-template <typename T>
-int lalloc(hs_lb *h, T **p, size_t count) {
-    void *q = nullptr;
-    const size_t bytes = count * sizeof(T) ? count * sizeof(T) : sizeof(T);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return lfail(h, HS_E_HIP, "hipMalloc(%zu B): %s", bytes, hipGetErrorString(e));
-    h->allocs.push_back(q);
-    *p = (T *)q;
-    return HS_OK;
-}
-template <typename T>
-int lupload(hs_lb *h, const T **dst, const T *src, size_t n, T dflt) {
-    T *d = nullptr;
-    int rc = lalloc(h, &d, n);
-    if (rc) return rc;
-    std::vector<T> tmp;
-    if (!src) { tmp.assign(n, dflt); src = tmp.data(); }
-    if (hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return lfail(h, HS_E_HIP, "hipMemcpy H2D failed");
-    *dst = d;
-    return HS_OK;
-}
-
 int bit_length(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b < 1 ? 1 : b; }
 
 
@@ -1853,8 +1813,8 @@ void radix_sort_async(hs_lb *h, const uint64_t *k_in, const uint64_t *v_in, cons
     uint64_t *ko = startB ? h->kB : h->kA, *vo = startB ? h->vB : h->vA;
     const uint64_t *ki = k_in, *vi = v_in;
     if (h->ghist == nullptr) {       // (the one-off sorts of hs_debug_radix_sort / hs_merge_sink_records / the latency statistics)
-        if (lalloc(h, &h->ghist, (size_t)kRadixMaxPasses * kRadixBins) || lalloc(h, &h->tickets, (size_t)kRadixMaxPasses + 1) ||
-            lalloc(h, &h->radix_err, (size_t)1)) h->ghist = nullptr;
+        if (dev_alloc(h, &h->ghist, (size_t)kRadixMaxPasses * kRadixBins) || dev_alloc(h, &h->tickets, (size_t)kRadixMaxPasses + 1) ||
+            dev_alloc(h, &h->radix_err, (size_t)1)) h->ghist = nullptr;
         else { hipMemset(h->tickets, 0, (kRadixMaxPasses + 1) * sizeof(uint32_t)); hipMemset(h->radix_err, 0, sizeof(int)); }
     }
     if ((h->flags & 16) != 0 && passes <= kRadixMaxPasses && h->ghist != nullptr) {
@@ -1937,7 +1897,7 @@ int run_async(hs_lb *h, int64_t end_ns) {
     h->launches = 0;
     hipLaunchKernelGGL(hs_lb_clear, dim3(1), dim3(1), 0, h->stream, h->tot);
     if (h->any_src_profile && !h->tables_built) {      // the time-varying Sources' tick tables: once (hs_tables.hpp)
-        LB_HIP(h, tick_tables_launch(h->stream, h->tab_rows, h->n_tab_rows, h->cfg.start_ns, h->cfg.horizon_ns, h->PS.tab_cap,
+        HS_HIP(h, tick_tables_launch(h->stream, h->tab_rows, h->n_tab_rows, h->cfg.start_ns, h->cfg.horizon_ns, h->PS.tab_cap,
                                      h->tab_times, h->tab_count, h->tab_status, h->lane_budget, false));
         h->tables_built = true;
     }
@@ -2082,7 +2042,7 @@ int run_async(hs_lb *h, int64_t end_ns) {
                            (S + sl - 1) / sl, (B + bl - 1) / bl, h->scan_cand + n_scan_blocks, scan ? 1 : 0);
     }
     h->launches += 6;
-    LB_HIP(h, hipGetLastError());
+    HS_HIP(h, hipGetLastError());
     h->ran = true;
     return HS_OK;
 }
@@ -2098,29 +2058,29 @@ bool lean_gave_up(hs_lb *h) {
 
 int check_flags(hs_lb *h) {
     LbTotals t;
-    LB_HIP(h, hipMemcpy(&t, h->tot, sizeof t, hipMemcpyDeviceToHost));
-    if (t.qoverflow) return lfail(h, HS_E_UNSUPPORTED, "a same-timestamp event cascade exceeded the in-group queue");
+    HS_HIP(h, hipMemcpy(&t, h->tot, sizeof t, hipMemcpyDeviceToHost));
+    if (t.qoverflow) return fail(h, HS_E_UNSUPPORTED, "a same-timestamp event cascade exceeded the in-group queue");
     if (h->radix_err != nullptr) {
         int re = 0;
-        LB_HIP(h, hipMemcpy(&re, h->radix_err, sizeof re, hipMemcpyDeviceToHost));
-        if (re) return lfail(h, HS_E_HIP, "the radix sort's look-back (debug flag 16) gave up waiting for an earlier tile (bounded spin)");
+        HS_HIP(h, hipMemcpy(&re, h->radix_err, sizeof re, hipMemcpyDeviceToHost));
+        if (re) return fail(h, HS_E_HIP, "the radix sort's look-back (debug flag 16) gave up waiting for an earlier tile (bounded spin)");
     }
-    if (t.bad_client & 1) return lfail(h, HS_E_INVALID, "a client id fell outside the client table");
+    if (t.bad_client & 1) return fail(h, HS_E_INVALID, "a client id fell outside the client table");
     if (h->any_src_profile) {          // a Source whose inversion gave up would simply stop ticking: never silently
         unsigned long long st[2] = {0ull, 0ull};
-        LB_HIP(h, hipMemcpy(st, h->tab_status, sizeof st, hipMemcpyDeviceToHost));
+        HS_HIP(h, hipMemcpy(st, h->tab_status, sizeof st, hipMemcpyDeviceToHost));
         if (st[0] != 0ull)
-            return lfail(h, HS_E_UNSUPPORTED, "Source %lld: one arrival of its time-varying profile needs more than 64 x %lld adaptive-Simpson "
+            return fail(h, HS_E_UNSUPPORTED, "Source %lld: one arrival of its time-varying profile needs more than 64 x %lld adaptive-Simpson "
                          "intervals (csrc/hs_tables.hpp; hs_lb_set_profile_budget raises the limit) -- refused instead of stalling the device",
                          (long long)st[0] - 2, (long long)h->lane_budget);
         if (st[1] != 0ull)
-            return lfail(h, HS_E_OVERFLOW, "Source %lld: its tick table overflowed (capacity %lld ticks); raise tick_capacity",
+            return fail(h, HS_E_OVERFLOW, "Source %lld: its tick table overflowed (capacity %lld ticks); raise tick_capacity",
                          (long long)st[1] - 2, (long long)h->PS.tab_cap);
     }
-    if (t.bad_client & 2) return lfail(h, HS_E_OVERFLOW, "a source's tick log overflowed (capacity %lld ticks); raise tick_capacity", (long long)h->cap);
-    if (t.probe_tie & 1) return lfail(h, HS_E_UNSUPPORTED, "a probe sample fell on the nanosecond of an event of its target: on load-balancer "
+    if (t.bad_client & 2) return fail(h, HS_E_OVERFLOW, "a source's tick log overflowed (capacity %lld ticks); raise tick_capacity", (long long)h->cap);
+    if (t.probe_tie & 1) return fail(h, HS_E_UNSUPPORTED, "a probe sample fell on the nanosecond of an event of its target: on load-balancer "
                                       "graphs that order (the reference's sort indices) is not lowered");
-    if (t.probe_tie & 2) return lfail(h, HS_E_UNSUPPORTED, "a probed backend rejected deliveries (no free worker): its queue is not "
+    if (t.probe_tie & 2) return fail(h, HS_E_UNSUPPORTED, "a probed backend rejected deliveries (no free worker): its queue is not "
                                       "work-conserving and the samples cannot be read off the logs");
     return HS_OK;
 }
@@ -2129,7 +2089,7 @@ int check_flags(hs_lb *h) {
 
 extern "C" {
 
-const char *hs_lb_last_error(const hs_lb *h) { return h ? h->error.c_str() : g_lb_error.c_str(); }
+const char *hs_lb_last_error(const hs_lb *h) { return h ? h->error.c_str() : g_last_error.c_str(); }
 
 void hs_md5(const char *msg, int64_t len, uint8_t out[16]) {
     Md5 m;
@@ -2137,37 +2097,37 @@ void hs_md5(const char *msg, int64_t len, uint8_t out[16]) {
 }
 
 int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_backends *be, hs_lb **out) {
-    if (!cfg || !src || !be || !out) return lfail(nullptr, HS_E_INVALID, "hs_lb_create: null argument");
-    if (cfg->struct_size != sizeof(hs_lb_config)) return lfail(nullptr, HS_E_INVALID, "hs_lb_create: hs_lb_config size mismatch (ABI %d)", HS_ABI_VERSION);
+    if (!cfg || !src || !be || !out) return fail(nullptr, HS_E_INVALID, "hs_lb_create: null argument");
+    if (cfg->struct_size != sizeof(hs_lb_config)) return fail(nullptr, HS_E_INVALID, "hs_lb_create: hs_lb_config size mismatch (ABI %d)", HS_ABI_VERSION);
     const int S = cfg->n_sources, B = cfg->n_backends;
-    if (S <= 0) return lfail(nullptr, HS_E_INVALID, "hs_lb_create: n_sources must be > 0");
-    if (B <= 0) return lfail(nullptr, HS_E_INVALID, "hs_lb_create: n_backends must be > 0 (the reference rejects every request otherwise)");
-    if (cfg->strategy < HS_LB_CONSISTENT_HASH || cfg->strategy > HS_LB_RANDOM) return lfail(nullptr, HS_E_UNSUPPORTED, "load-balancing strategy %d is not lowered", cfg->strategy);
+    if (S <= 0) return fail(nullptr, HS_E_INVALID, "hs_lb_create: n_sources must be > 0");
+    if (B <= 0) return fail(nullptr, HS_E_INVALID, "hs_lb_create: n_backends must be > 0 (the reference rejects every request otherwise)");
+    if (cfg->strategy < HS_LB_CONSISTENT_HASH || cfg->strategy > HS_LB_RANDOM) return fail(nullptr, HS_E_UNSUPPORTED, "load-balancing strategy %d is not lowered", cfg->strategy);
     const bool chash = cfg->strategy == HS_LB_CONSISTENT_HASH;
-    if (chash && cfg->virtual_nodes < 1) return lfail(nullptr, HS_E_INVALID, "virtual_nodes must be >= 1, got %d", cfg->virtual_nodes);
-    if (cfg->start_ns < 0) return lfail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
-    if (cfg->horizon_ns < cfg->start_ns) return lfail(nullptr, HS_E_INVALID, "hs_lb_create: horizon_ns precedes start_ns");
-    if (!src->src_rate || (chash && !src->n_clients)) return lfail(nullptr, HS_E_INVALID, "src_rate and n_clients are required");
-    if (!be->names || !be->name_off) return lfail(nullptr, HS_E_INVALID, "backend names are required (the ring hashes them)");
+    if (chash && cfg->virtual_nodes < 1) return fail(nullptr, HS_E_INVALID, "virtual_nodes must be >= 1, got %d", cfg->virtual_nodes);
+    if (cfg->start_ns < 0) return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
+    if (cfg->horizon_ns < cfg->start_ns) return fail(nullptr, HS_E_INVALID, "hs_lb_create: horizon_ns precedes start_ns");
+    if (!src->src_rate || (chash && !src->n_clients)) return fail(nullptr, HS_E_INVALID, "src_rate and n_clients are required");
+    if (!be->names || !be->name_off) return fail(nullptr, HS_E_INVALID, "backend names are required (the ring hashes them)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return lfail(nullptr, HS_E_NO_DEVICE, "no HIP device visible: the engine has no CPU fallback");
-    if (cfg->device < 0 || cfg->device >= ndev) return lfail(nullptr, HS_E_INVALID, "device ordinal %d out of range (%d devices)", cfg->device, ndev);
+        return fail(nullptr, HS_E_NO_DEVICE, "no HIP device visible: the engine has no CPU fallback");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, HS_E_INVALID, "device ordinal %d out of range (%d devices)", cfg->device, ndev);
     // ---- validation + sizing
     const double horizon_s = (double)(cfg->horizon_ns - cfg->start_ns) / 1e9;
     double max_ticks = 0.0, total_rate = 0.0, min_rate = 1e300;
     int64_t kmax = 0;
     for (int i = 0; i < S; ++i) {
         const int sk = src->src_kind ? src->src_kind[i] : HS_SRC_POISSON;
-        if (sk != HS_SRC_POISSON && sk != HS_SRC_CONSTANT) return lfail(nullptr, HS_E_INVALID, "source %d: unknown source kind %d", i, sk);
+        if (sk != HS_SRC_POISSON && sk != HS_SRC_CONSTANT) return fail(nullptr, HS_E_INVALID, "source %d: unknown source kind %d", i, sk);
         const double r = src->src_rate[i];
-        if (!(r > 0.0) || !std::isfinite(r)) return lfail(nullptr, HS_E_INVALID, "source %d: rate must be > 0 (got %g)", i, r);
-        if (r > 1e8) return lfail(nullptr, HS_E_UNSUPPORTED, "source %d: rate %g above 1e8/s is not supported", i, r);
+        if (!(r > 0.0) || !std::isfinite(r)) return fail(nullptr, HS_E_INVALID, "source %d: rate must be > 0 (got %g)", i, r);
+        if (r > 1e8) return fail(nullptr, HS_E_UNSUPPORTED, "source %d: rate %g above 1e8/s is not supported", i, r);
         max_ticks = std::max(max_ticks, r * horizon_s);
         min_rate = std::min(min_rate, r);
         total_rate += r;
         if (chash) {
-            if (src->n_clients[i] < 1) return lfail(nullptr, HS_E_INVALID, "source %d: n_clients must be >= 1", i);
+            if (src->n_clients[i] < 1) return fail(nullptr, HS_E_INVALID, "source %d: n_clients must be >= 1", i);
             kmax = std::max(kmax, src->n_clients[i]);
         }
     }
@@ -2175,38 +2135,38 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     // a placeholder (0), the assignment follows the global arrival order (hs_lb_rr_assign)
     if (cfg->strategy == HS_LB_RANDOM) kmax = B;
     if (cfg->strategy == HS_LB_ROUND_ROBIN) kmax = 1;
-    if (kmax > (1ll << 26)) return lfail(nullptr, HS_E_UNSUPPORTED, "n_clients above 2^26 is not supported (client -> backend table)");
+    if (kmax > (1ll << 26)) return fail(nullptr, HS_E_UNSUPPORTED, "n_clients above 2^26 is not supported (client -> backend table)");
     int maxc = 1;
     bool any_no_sink = false;
     double svc_step_s = 0.0;        // the longest service one request can draw: 36.8 exponential means or a constant
     for (int j = 0; j < B; ++j) {
         const int c = be->concurrency ? be->concurrency[j] : 1;
-        if (c < 1) return lfail(nullptr, HS_E_INVALID, "backend %d: max_concurrent must be >= 1, got %d", j, c);
-        if (c > 32) return lfail(nullptr, HS_E_UNSUPPORTED, "backend %d: concurrency %d > 32 is not lowered yet", j, c);
+        if (c < 1) return fail(nullptr, HS_E_INVALID, "backend %d: max_concurrent must be >= 1, got %d", j, c);
+        if (c > 32) return fail(nullptr, HS_E_UNSUPPORTED, "backend %d: concurrency %d > 32 is not lowered yet", j, c);
         maxc = std::max(maxc, c);
         const int vk = be->svc_kind ? be->svc_kind[j] : HS_LAT_CONSTANT;
-        if (vk != HS_LAT_EXPONENTIAL && vk != HS_LAT_CONSTANT) return lfail(nullptr, HS_E_UNSUPPORTED, "backend %d: service distribution kind %d is not lowered", j, vk);
+        if (vk != HS_LAT_EXPONENTIAL && vk != HS_LAT_CONSTANT) return fail(nullptr, HS_E_UNSUPPORTED, "backend %d: service distribution kind %d is not lowered", j, vk);
         const double mean = be->svc_mean_s ? be->svc_mean_s[j] : 0.01;
         if (!(mean >= 0.0) || !std::isfinite(mean) || (vk == HS_LAT_EXPONENTIAL && !(mean > 0.0)))
-            return lfail(nullptr, HS_E_INVALID, "backend %d: bad service mean %g", j, mean);
-        svc_step_s = std::max(svc_step_s, vk == HS_LAT_EXPONENTIAL ? 36.8 * mean : mean);
+            return fail(nullptr, HS_E_INVALID, "backend %d: bad service mean %g", j, mean);
+        svc_step_s = std::max(svc_step_s, vk == HS_LAT_EXPONENTIAL ? kLongestExpDraw * mean : mean);
         const int eg = be->egress ? be->egress[j] : HS_EGRESS_SINK;
-        if (eg != HS_EGRESS_NONE && eg != HS_EGRESS_SINK) return lfail(nullptr, HS_E_UNSUPPORTED, "backend %d: egress kind %d is not lowered", j, eg);
+        if (eg != HS_EGRESS_NONE && eg != HS_EGRESS_SINK) return fail(nullptr, HS_E_UNSUPPORTED, "backend %d: egress kind %d is not lowered", j, eg);
         if (eg == HS_EGRESS_NONE) any_no_sink = true;
         if (be->name_off[j + 1] < be->name_off[j] || be->name_off[j + 1] - be->name_off[j] > 200)
-            return lfail(nullptr, HS_E_INVALID, "backend %d: bad name", j);
+            return fail(nullptr, HS_E_INVALID, "backend %d: bad name", j);
     }
-    if (!reach_fits_int64(cfg->horizon_ns, std::max(svc_step_s, 36.8 / min_rate)))
-        return lfail(nullptr, HS_E_UNSUPPORTED, "the horizon (%lld ns) plus one longest step (%.6g s: 36.8 / the smallest rate, 36.8 x the "
+    if (!reach_fits_int64(cfg->horizon_ns, std::max(svc_step_s, kLongestExpDraw / min_rate)))
+        return fail(nullptr, HS_E_UNSUPPORTED, "the horizon (%lld ns) plus one longest step (%.6g s: 36.8 / the smallest rate, 36.8 x the "
                      "largest exponential mean or the largest constant service) leaves int64 nanoseconds -- refused, never wrapped",
-                     (long long)cfg->horizon_ns, std::max(svc_step_s, 36.8 / min_rate));
+                     (long long)cfg->horizon_ns, std::max(svc_step_s, kLongestExpDraw / min_rate));
     hs_lb *h = new (std::nothrow) hs_lb();
-    if (!h) return lfail(nullptr, HS_E_INVALID, "out of host memory");
+    if (!h) return fail(nullptr, HS_E_INVALID, "out of host memory");
     h->cfg = *cfg;
     h->C = maxc <= 1 ? 1 : maxc <= 2 ? 2 : maxc <= 4 ? 4 : maxc <= 8 ? 8 : maxc <= 16 ? 16 : 32;
     h->tb = bit_length((uint64_t)cfg->horizon_ns);
     h->bb = bit_length((uint64_t)(B - 1));
-    if (h->tb + h->bb > 64 || h->tb > 56) { delete h; return lfail(nullptr, HS_E_UNSUPPORTED, "horizon x backends do not fit the 64-bit sort key"); }
+    if (h->tb + h->bb > 64 || h->tb > 56) { delete h; return fail(nullptr, HS_E_UNSUPPORTED, "horizon x backends do not fit the 64-bit sort key"); }
     int64_t cap = cfg->tick_capacity;
     if (cap <= 0) cap = ((int64_t)(max_ticks + 10.0 * std::sqrt(max_ticks + 1.0) + 64.0) + 15) & ~(int64_t)15;
     h->cap = cap;
@@ -2218,7 +2178,7 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     // end: hs_lbk_scan<true> converts it with i64_from_whole_d, exact below 2^52 only)
     h->f64_times = cfg->start_ns >= 0 && cfg->horizon_ns < (1ll << 50) && min_rate > 1e-3 &&
                    (double)cfg->horizon_ns + svc_step_s * 1e9 < 4503599627370496.0;
-    if ((double)h->n_slots * 88.0 > 200e9) { delete h; return lfail(nullptr, HS_E_INVALID, "buffers would need %.1f GB", (double)h->n_slots * 88.0 / 1e9); }
+    if ((double)h->n_slots * 88.0 > 200e9) { delete h; return fail(nullptr, HS_E_INVALID, "buffers would need %.1f GB", (double)h->n_slots * 88.0 / 1e9); }
     {   // rows of the [k][backend] layout: three times the mean load of a backend (consistent hashing with >= 100 virtual
         // nodes keeps the busiest backend below ~2x); capped so that the five transposed arrays stay within ~4x n_slots
         const double mean_be = total_rate * horizon_s / (double)B;
@@ -2283,39 +2243,39 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) h->n_simd = 4 * cus; }
     hipEvent_t *evs[6] = {&h->ev0, &h->ev1, &h->evs0, &h->evs1, &h->evs2, &h->evs3};
     for (auto pe : evs) if (e == hipSuccess) e = hipEventCreate(pe);
-    if (e != hipSuccess) { int rc = lfail(nullptr, HS_E_HIP, "device setup: %s", hipGetErrorString(e)); hs_lb_destroy(h); return rc; }
+    if (e != hipSuccess) { int rc = fail(nullptr, HS_E_HIP, "device setup: %s", hipGetErrorString(e)); hs_lb_destroy(h); return rc; }
     int rc = HS_OK;
     std::vector<uint64_t> sbase((size_t)S), bbase((size_t)B);
     for (int i = 0; i < S; ++i) sbase[(size_t)i] = (uint64_t)i;
     for (int j = 0; j < B; ++j) bbase[(size_t)j] = (uint64_t)S + (uint64_t)j;
-#define TRY(x) do { if ((rc = (x))) { g_lb_error = h->error; hs_lb_destroy(h); return rc; } } while (0)
-    TRY(lupload<uint8_t>(h, &h->PS.kind, src->src_kind, (size_t)S, (uint8_t)HS_SRC_POISSON));
-    TRY(lupload<double>(h, &h->PS.rate, src->src_rate, (size_t)S, 1.0));
-    TRY(lupload<int64_t>(h, &h->PS.stop, src->src_stop_after_ns, (size_t)S, (int64_t)-1));
+#define TRY(x) do { if ((rc = (x))) { g_last_error = h->error; hs_lb_destroy(h); return rc; } } while (0)
+    TRY(upload<uint8_t>(h, &h->PS.kind, src->src_kind, (size_t)S, (uint8_t)HS_SRC_POISSON));
+    TRY(upload<double>(h, &h->PS.rate, src->src_rate, (size_t)S, 1.0));
+    TRY(upload<int64_t>(h, &h->PS.stop, src->src_stop_after_ns, (size_t)S, (int64_t)-1));
     h->src_stop_h.assign((size_t)S, (int64_t)-1);
     if (src->src_stop_after_ns) h->src_stop_h.assign(src->src_stop_after_ns, src->src_stop_after_ns + S);
     for (int i = 0; i < S && src->src_stop_after_ns; ++i) if (src->src_stop_after_ns[i] >= 0) h->any_stop = true;
-    if (chash) TRY(lupload<int64_t>(h, &h->PS.n_clients, src->n_clients, (size_t)S, (int64_t)1));
-    else TRY(lupload<int64_t>(h, &h->PS.n_clients, (const int64_t *)nullptr, (size_t)S, (int64_t)kmax));
+    if (chash) TRY(upload<int64_t>(h, &h->PS.n_clients, src->n_clients, (size_t)S, (int64_t)1));
+    else TRY(upload<int64_t>(h, &h->PS.n_clients, (const int64_t *)nullptr, (size_t)S, (int64_t)kmax));
     {   // time-varying profiles (load/profile.py:52-113): src_rate of such a Source is its PEAK rate (it sizes the tick log)
         std::vector<uint8_t> pk((size_t)S, (uint8_t)0);
         std::vector<double> pp((size_t)S * 4, 0.0);
         for (int i = 0; i < S && src->src_profile_kind; ++i) {
             const int k = src->src_profile_kind[i];
             if (k == 0) continue;
-            if (k != 1 && k != 2) { rc = lfail(nullptr, HS_E_UNSUPPORTED, "source %d: profile kind %d is not lowered", i, k); hs_lb_destroy(h); return rc; }
-            if (!src->src_profile_params) { rc = lfail(nullptr, HS_E_INVALID, "src_profile_params is required with src_profile_kind"); hs_lb_destroy(h); return rc; }
+            if (k != 1 && k != 2) { rc = fail(nullptr, HS_E_UNSUPPORTED, "source %d: profile kind %d is not lowered", i, k); hs_lb_destroy(h); return rc; }
+            if (!src->src_profile_params) { rc = fail(nullptr, HS_E_INVALID, "src_profile_params is required with src_profile_kind"); hs_lb_destroy(h); return rc; }
             const double *q = src->src_profile_params + 4 * (size_t)i;
             for (int j = 0; j < 4; ++j) {
-                if (!std::isfinite(q[j]) || q[j] < 0.0) { rc = lfail(nullptr, HS_E_INVALID, "source %d: bad profile parameter %g", i, q[j]); hs_lb_destroy(h); return rc; }
+                if (!std::isfinite(q[j]) || q[j] < 0.0) { rc = fail(nullptr, HS_E_INVALID, "source %d: bad profile parameter %g", i, q[j]); hs_lb_destroy(h); return rc; }
                 pp[(size_t)j * S + i] = q[j];
             }
-            if (k == 1 && !(q[0] > 0.0)) { rc = lfail(nullptr, HS_E_INVALID, "source %d: LinearRampProfile needs duration_s > 0", i); hs_lb_destroy(h); return rc; }
+            if (k == 1 && !(q[0] > 0.0)) { rc = fail(nullptr, HS_E_INVALID, "source %d: LinearRampProfile needs duration_s > 0", i); hs_lb_destroy(h); return rc; }
             pk[(size_t)i] = (uint8_t)k;
             h->any_src_profile = true;
         }
-        TRY(lupload<uint8_t>(h, &h->PS.prof_kind, pk.data(), (size_t)S, (uint8_t)0));
-        TRY(lupload<double>(h, &h->PS.prof_p, pp.data(), (size_t)S * 4, 0.0));
+        TRY(upload<uint8_t>(h, &h->PS.prof_kind, pk.data(), (size_t)S, (uint8_t)0));
+        TRY(upload<double>(h, &h->PS.prof_p, pp.data(), (size_t)S * 4, 0.0));
         if (h->any_src_profile) {
             // one tick-table row per time-varying Source (hs_tables.hpp); a table holds cap + 2 ticks: everything the tick
             // log can take plus the two beyond the horizon
@@ -2335,66 +2295,66 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
             }
             h->n_tab_rows = (int)rows.size();
             h->PS.tab_cap = h->cap + 2;
-            TRY(lalloc(h, &h->tab_rows, rows.size()));
+            TRY(dev_alloc(h, &h->tab_rows, rows.size()));
             if (hipMemcpy(h->tab_rows, rows.data(), rows.size() * sizeof(TickRow), hipMemcpyHostToDevice) != hipSuccess) {
-                rc = lfail(nullptr, HS_E_HIP, "memcpy"); hs_lb_destroy(h); return rc;
+                rc = fail(nullptr, HS_E_HIP, "memcpy"); hs_lb_destroy(h); return rc;
             }
-            TRY(lupload<int32_t>(h, &h->PS.tab_row, row_of.data(), (size_t)S, -1));
-            TRY(lalloc(h, &h->tab_times, rows.size() * (size_t)h->PS.tab_cap));
-            TRY(lalloc(h, &h->tab_count, rows.size()));
-            TRY(lalloc(h, &h->tab_status, 2));
+            TRY(upload<int32_t>(h, &h->PS.tab_row, row_of.data(), (size_t)S, -1));
+            TRY(dev_alloc(h, &h->tab_times, rows.size() * (size_t)h->PS.tab_cap));
+            TRY(dev_alloc(h, &h->tab_count, rows.size()));
+            TRY(dev_alloc(h, &h->tab_status, 2));
             h->PS.tab_times = h->tab_times;
         }
     }
-    TRY(lupload<uint64_t>(h, &h->PS.base, src->stream_base ? src->stream_base : sbase.data(), (size_t)S, 0));
-    TRY(lalloc(h, &h->PS.count, (size_t)S)); TRY(lalloc(h, &h->PS.generated, (size_t)S)); TRY(lalloc(h, &h->PS.cand, (size_t)S));
-    TRY(lupload<int32_t>(h, &h->PB.conc, be->concurrency, (size_t)B, 1));
-    TRY(lupload<uint8_t>(h, &h->PB.svc_kind, be->svc_kind, (size_t)B, (uint8_t)HS_LAT_CONSTANT));
-    TRY(lupload<double>(h, &h->PB.svc_mean, be->svc_mean_s, (size_t)B, 0.01));
-    TRY(lupload<int64_t>(h, &h->PB.qcap, be->queue_cap, (size_t)B, (int64_t)-1));
-    TRY(lupload<uint8_t>(h, &h->PB.egress, be->egress, (size_t)B, (uint8_t)HS_EGRESS_SINK));
-    TRY(lupload<uint64_t>(h, &h->PB.base, be->stream_base ? be->stream_base : bbase.data(), (size_t)B, 0));
-    TRY(lalloc(h, &h->PB.accepted, (size_t)B)); TRY(lalloc(h, &h->PB.dropped, (size_t)B)); TRY(lalloc(h, &h->PB.completed, (size_t)B));
-    TRY(lalloc(h, &h->PB.rejected, (size_t)B)); TRY(lalloc(h, &h->PB.received, (size_t)B)); TRY(lalloc(h, &h->PB.depth, (size_t)B));
-    TRY(lalloc(h, &h->PB.active, (size_t)B)); TRY(lalloc(h, &h->PB.total_service, (size_t)B)); TRY(lalloc(h, &h->PB.cand, (size_t)B));
+    TRY(upload<uint64_t>(h, &h->PS.base, src->stream_base ? src->stream_base : sbase.data(), (size_t)S, 0));
+    TRY(dev_alloc(h, &h->PS.count, (size_t)S)); TRY(dev_alloc(h, &h->PS.generated, (size_t)S)); TRY(dev_alloc(h, &h->PS.cand, (size_t)S));
+    TRY(upload<int32_t>(h, &h->PB.conc, be->concurrency, (size_t)B, 1));
+    TRY(upload<uint8_t>(h, &h->PB.svc_kind, be->svc_kind, (size_t)B, (uint8_t)HS_LAT_CONSTANT));
+    TRY(upload<double>(h, &h->PB.svc_mean, be->svc_mean_s, (size_t)B, 0.01));
+    TRY(upload<int64_t>(h, &h->PB.qcap, be->queue_cap, (size_t)B, (int64_t)-1));
+    TRY(upload<uint8_t>(h, &h->PB.egress, be->egress, (size_t)B, (uint8_t)HS_EGRESS_SINK));
+    TRY(upload<uint64_t>(h, &h->PB.base, be->stream_base ? be->stream_base : bbase.data(), (size_t)B, 0));
+    TRY(dev_alloc(h, &h->PB.accepted, (size_t)B)); TRY(dev_alloc(h, &h->PB.dropped, (size_t)B)); TRY(dev_alloc(h, &h->PB.completed, (size_t)B));
+    TRY(dev_alloc(h, &h->PB.rejected, (size_t)B)); TRY(dev_alloc(h, &h->PB.received, (size_t)B)); TRY(dev_alloc(h, &h->PB.depth, (size_t)B));
+    TRY(dev_alloc(h, &h->PB.active, (size_t)B)); TRY(dev_alloc(h, &h->PB.total_service, (size_t)B)); TRY(dev_alloc(h, &h->PB.cand, (size_t)B));
     {
         const int32_t *dt = nullptr;
-        TRY(lupload<int32_t>(h, &dt, table.data(), (size_t)kmax, 0));
+        TRY(upload<int32_t>(h, &dt, table.data(), (size_t)kmax, 0));
         h->client_be = const_cast<int32_t *>(dt);
     }
     const size_t NS = (size_t)h->n_slots;
-    TRY(lalloc(h, &h->keys0, NS)); TRY(lalloc(h, &h->vals0, NS));
+    TRY(dev_alloc(h, &h->keys0, NS)); TRY(dev_alloc(h, &h->vals0, NS));
     // (kA / vA also hold hs_lb_source_draws' tiled output before the first sort: whole wavefronts of Sources, lb_draw_index)
     const size_t NSP = (size_t)h->cap * (((size_t)S + 63) & ~(size_t)63);
-    TRY(lalloc(h, &h->kA, NSP)); TRY(lalloc(h, &h->vA, NSP)); TRY(lalloc(h, &h->kB, NS)); TRY(lalloc(h, &h->vB, NS));
-    TRY(lalloc(h, &h->off, (size_t)B + 1));
+    TRY(dev_alloc(h, &h->kA, NSP)); TRY(dev_alloc(h, &h->vA, NSP)); TRY(dev_alloc(h, &h->kB, NS)); TRY(dev_alloc(h, &h->vB, NS));
+    TRY(dev_alloc(h, &h->off, (size_t)B + 1));
     const size_t NL = (size_t)h->n_layout;
-    TRY(lalloc(h, &h->adm, NS)); TRY(lalloc(h, &h->sink_t, NL)); TRY(lalloc(h, &h->sink_created, NL)); TRY(lalloc(h, &h->sink_S, NL));
+    TRY(dev_alloc(h, &h->adm, NS)); TRY(dev_alloc(h, &h->sink_t, NL)); TRY(dev_alloc(h, &h->sink_created, NL)); TRY(dev_alloc(h, &h->sink_S, NL));
     if (h->LY.rows > 0) {
-        TRY(lalloc(h, &h->LY.tkey, (size_t)h->LY.rows * (size_t)B));
-        TRY(lalloc(h, &h->LY.tsv, (size_t)h->LY.rows * (size_t)B));
+        TRY(dev_alloc(h, &h->LY.tkey, (size_t)h->LY.rows * (size_t)B));
+        TRY(dev_alloc(h, &h->LY.tsv, (size_t)h->LY.rows * (size_t)B));
     }
-    TRY(lalloc(h, &h->n_merge, 1));
-    TRY(lalloc(h, &h->bev, (size_t)3 * (size_t)B)); TRY(lalloc(h, &h->blast, (size_t)B)); TRY(lalloc(h, &h->redo, (size_t)B));
-    TRY(lalloc(h, &h->scan_cand, (size_t)(B + kLbBlock / 64 - 1) / (kLbBlock / 64) + 1));
-    TRY(lalloc(h, &h->scan_part, (size_t)kScanParts)); TRY(lalloc(h, &h->scan_ticket, (size_t)1));
-    LB_HIP(h, hipMemset(h->scan_ticket, 0, sizeof(unsigned)));
-    if (cfg->shared_sink) { TRY(lalloc(h, &h->out_t, NS)); TRY(lalloc(h, &h->out_created, NS)); }
+    TRY(dev_alloc(h, &h->n_merge, 1));
+    TRY(dev_alloc(h, &h->bev, (size_t)3 * (size_t)B)); TRY(dev_alloc(h, &h->blast, (size_t)B)); TRY(dev_alloc(h, &h->redo, (size_t)B));
+    TRY(dev_alloc(h, &h->scan_cand, (size_t)(B + kLbBlock / 64 - 1) / (kLbBlock / 64) + 1));
+    TRY(dev_alloc(h, &h->scan_part, (size_t)kScanParts)); TRY(dev_alloc(h, &h->scan_ticket, (size_t)1));
+    HS_HIP(h, hipMemset(h->scan_ticket, 0, sizeof(unsigned)));
+    if (cfg->shared_sink) { TRY(dev_alloc(h, &h->out_t, NS)); TRY(dev_alloc(h, &h->out_created, NS)); }
     for (int j = 0; j < B; ++j)
         if ((be->concurrency ? be->concurrency[j] : 1) == 1 && (be->queue_cap ? be->queue_cap[j] : -1) < 0) h->any_simple = true;
     h->any_no_sink = any_no_sink;
-    TRY(lalloc(h, &h->svdraw, (h->C == 1 && h->any_simple) ? NS : (size_t)1));
-    TRY(lalloc(h, &h->n_slots_dev, 1)); TRY(lalloc(h, &h->n_arr, 1)); TRY(lalloc(h, &h->n_done, 1)); TRY(lalloc(h, &h->n_tmp, 1));
-    TRY(lalloc(h, &h->hist, (size_t)kRadixBins * (size_t)h->n_tiles)); TRY(lalloc(h, &h->row_total, (size_t)kRadixBins));
-    TRY(lalloc(h, &h->digit_base, (size_t)kRadixBins));
-    TRY(lalloc(h, &h->ghist, (size_t)kRadixMaxPasses * kRadixBins)); TRY(lalloc(h, &h->tickets, (size_t)kRadixMaxPasses + 1));
-    TRY(lalloc(h, &h->radix_err, (size_t)1));
-    LB_HIP(h, hipMemset(h->tickets, 0, (kRadixMaxPasses + 1) * sizeof(uint32_t)));
-    LB_HIP(h, hipMemset(h->radix_err, 0, sizeof(int)));
-    TRY(lalloc(h, &h->tot, 1));
+    TRY(dev_alloc(h, &h->svdraw, (h->C == 1 && h->any_simple) ? NS : (size_t)1));
+    TRY(dev_alloc(h, &h->n_slots_dev, 1)); TRY(dev_alloc(h, &h->n_arr, 1)); TRY(dev_alloc(h, &h->n_done, 1)); TRY(dev_alloc(h, &h->n_tmp, 1));
+    TRY(dev_alloc(h, &h->hist, (size_t)kRadixBins * (size_t)h->n_tiles)); TRY(dev_alloc(h, &h->row_total, (size_t)kRadixBins));
+    TRY(dev_alloc(h, &h->digit_base, (size_t)kRadixBins));
+    TRY(dev_alloc(h, &h->ghist, (size_t)kRadixMaxPasses * kRadixBins)); TRY(dev_alloc(h, &h->tickets, (size_t)kRadixMaxPasses + 1));
+    TRY(dev_alloc(h, &h->radix_err, (size_t)1));
+    HS_HIP(h, hipMemset(h->tickets, 0, (kRadixMaxPasses + 1) * sizeof(uint32_t)));
+    HS_HIP(h, hipMemset(h->radix_err, 0, sizeof(int)));
+    TRY(dev_alloc(h, &h->tot, 1));
 #undef TRY
     if (hipMemcpy(h->n_slots_dev, &h->n_slots, 8, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = lfail(nullptr, HS_E_HIP, "hipMemcpy failed"); hs_lb_destroy(h); return rc;
+        rc = fail(nullptr, HS_E_HIP, "hipMemcpy failed"); hs_lb_destroy(h); return rc;
     }
     *out = h;
     return HS_OK;
@@ -2403,14 +2363,14 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
 int hs_lb_run_path(const hs_lb *h) { return h ? h->run_path : 0; }
 
 int hs_lb_run(hs_lb *h, int64_t end_ns) {
-    if (!h) return lfail(h, HS_E_INVALID, "hs_lb_run: null handle");
-    if (end_ns < h->cfg.start_ns || end_ns > h->cfg.horizon_ns) return lfail(h, HS_E_INVALID, "end_ns outside [start_ns, horizon_ns]");
-    LB_HIP(h, hipSetDevice(h->cfg.device));
-    LB_HIP(h, hipEventRecord(h->ev0, h->stream));
+    if (!h) return fail(h, HS_E_INVALID, "hs_lb_run: null handle");
+    if (end_ns < h->cfg.start_ns || end_ns > h->cfg.horizon_ns) return fail(h, HS_E_INVALID, "end_ns outside [start_ns, horizon_ns]");
+    HS_HIP(h, hipSetDevice(h->cfg.device));
+    HS_HIP(h, hipEventRecord(h->ev0, h->stream));
     int rc = run_async(h, end_ns);
     if (rc) return rc;
-    LB_HIP(h, hipEventRecord(h->ev1, h->stream));
-    LB_HIP(h, hipStreamSynchronize(h->stream));
+    HS_HIP(h, hipEventRecord(h->ev1, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
     float ms = 0, s1 = 0, s2 = 0;
     hipEventElapsedTime(&ms, h->ev0, h->ev1);
     hipEventElapsedTime(&s1, h->evs0, h->evs1);
@@ -2421,24 +2381,24 @@ int hs_lb_run(hs_lb *h, int64_t end_ns) {
 }
 
 int hs_lb_bench_runs(hs_lb *h, int64_t end_ns, int32_t repeats, float *run_ms_out, float *sort_ms_out) {
-    if (!h || repeats <= 0) return lfail(h, HS_E_INVALID, "hs_lb_bench_runs: bad argument");
-    if (end_ns < h->cfg.start_ns || end_ns > h->cfg.horizon_ns) return lfail(h, HS_E_INVALID, "end_ns outside [start_ns, horizon_ns]");
-    LB_HIP(h, hipSetDevice(h->cfg.device));
+    if (!h || repeats <= 0) return fail(h, HS_E_INVALID, "hs_lb_bench_runs: bad argument");
+    if (end_ns < h->cfg.start_ns || end_ns > h->cfg.horizon_ns) return fail(h, HS_E_INVALID, "end_ns outside [start_ns, horizon_ns]");
+    HS_HIP(h, hipSetDevice(h->cfg.device));
     // `repeats` complete runs enqueued back to back (every count lives in device memory: a run needs no host synchronisation), each
     // bracketed by its own HIP events on the engine's stream; ONE synchronisation at the end, as hs_engine_bench_runs does
     std::vector<hipEvent_t> ev((size_t)repeats * 6);
-    for (auto &e : ev) LB_HIP(h, hipEventCreate(&e));
+    for (auto &e : ev) HS_HIP(h, hipEventCreate(&e));
     hipEvent_t keep[4] = {h->evs0, h->evs1, h->evs2, h->evs3};
     int rc = HS_OK;
     for (int r = 0; r < repeats && rc == HS_OK; ++r) {
         hipEvent_t *e = &ev[(size_t)r * 6];
         h->evs0 = e[2]; h->evs1 = e[3]; h->evs2 = e[4]; h->evs3 = e[5];
-        if (hipEventRecord(e[0], h->stream) != hipSuccess) rc = lfail(h, HS_E_HIP, "hipEventRecord failed");
+        if (hipEventRecord(e[0], h->stream) != hipSuccess) rc = fail(h, HS_E_HIP, "hipEventRecord failed");
         if (rc == HS_OK) rc = run_async(h, end_ns);
-        if (rc == HS_OK && hipEventRecord(e[1], h->stream) != hipSuccess) rc = lfail(h, HS_E_HIP, "hipEventRecord failed");
+        if (rc == HS_OK && hipEventRecord(e[1], h->stream) != hipSuccess) rc = fail(h, HS_E_HIP, "hipEventRecord failed");
     }
     h->evs0 = keep[0]; h->evs1 = keep[1]; h->evs2 = keep[2]; h->evs3 = keep[3];
-    if (rc == HS_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = lfail(h, HS_E_HIP, "hipStreamSynchronize failed");
+    if (rc == HS_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, HS_E_HIP, "hipStreamSynchronize failed");
     for (int r = 0; r < repeats && rc == HS_OK; ++r) {
         hipEvent_t *e = &ev[(size_t)r * 6];
         float ms = 0, s1 = 0, s2 = 0;
@@ -2453,12 +2413,12 @@ int hs_lb_bench_runs(hs_lb *h, int64_t end_ns, int32_t repeats, float *run_ms_ou
 }
 
 int hs_lb_get_summary(hs_lb *h, hs_summary *out) {
-    if (!h || !out) return lfail(h, HS_E_INVALID, "hs_lb_get_summary: null argument");
-    if (!h->ran) return lfail(h, HS_E_STATE, "hs_lb_run has not been called");
-    LB_HIP(h, hipSetDevice(h->cfg.device));
-    LB_HIP(h, hipStreamSynchronize(h->stream));
+    if (!h || !out) return fail(h, HS_E_INVALID, "hs_lb_get_summary: null argument");
+    if (!h->ran) return fail(h, HS_E_STATE, "hs_lb_run has not been called");
+    HS_HIP(h, hipSetDevice(h->cfg.device));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
     LbTotals t;
-    LB_HIP(h, hipMemcpy(&t, h->tot, sizeof t, hipMemcpyDeviceToHost));
+    HS_HIP(h, hipMemcpy(&t, h->tot, sizeof t, hipMemcpyDeviceToHost));
     memset(out, 0, sizeof *out);
     int64_t total = 0;
     for (int k = 0; k < HS_EV_KINDS; ++k) { out->events_by_kind[k] = (int64_t)t.ev[k]; total += (int64_t)t.ev[k]; }
@@ -2473,20 +2433,20 @@ int hs_lb_get_summary(hs_lb *h, hs_summary *out) {
 }
 
 int hs_lb_get_stats(hs_lb *h, const hs_lb_stats *o) {
-    if (!h || !o) return lfail(h, HS_E_INVALID, "hs_lb_get_stats: null argument");
-    if (!h->ran) return lfail(h, HS_E_STATE, "hs_lb_run has not been called");
-    LB_HIP(h, hipSetDevice(h->cfg.device));
-    LB_HIP(h, hipStreamSynchronize(h->stream));
+    if (!h || !o) return fail(h, HS_E_INVALID, "hs_lb_get_stats: null argument");
+    if (!h->ran) return fail(h, HS_E_STATE, "hs_lb_run has not been called");
+    HS_HIP(h, hipSetDevice(h->cfg.device));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
     const size_t S = (size_t)h->cfg.n_sources, B = (size_t)h->cfg.n_backends;
-    if (o->generated) LB_HIP(h, hipMemcpy(o->generated, h->PS.generated, S * 8, hipMemcpyDeviceToHost));
-#define DL(dst, srcp, T) if (o->dst) LB_HIP(h, hipMemcpy(o->dst, h->PB.srcp, B * sizeof(T), hipMemcpyDeviceToHost))
+    if (o->generated) HS_HIP(h, hipMemcpy(o->generated, h->PS.generated, S * 8, hipMemcpyDeviceToHost));
+#define DL(dst, srcp, T) if (o->dst) HS_HIP(h, hipMemcpy(o->dst, h->PB.srcp, B * sizeof(T), hipMemcpyDeviceToHost))
     DL(accepted, accepted, int64_t); DL(dropped, dropped, int64_t); DL(completed, completed, int64_t);
     DL(rejected, rejected, int64_t); DL(total_service_s, total_service, double); DL(queue_depth, depth, int64_t);
     DL(active, active, int32_t); DL(sink_received, received, int64_t);
 #undef DL
     if (o->total_requests || o->lb) {
         std::vector<int64_t> off(B + 1);
-        LB_HIP(h, hipMemcpy(off.data(), h->off, (B + 1) * 8, hipMemcpyDeviceToHost));
+        HS_HIP(h, hipMemcpy(off.data(), h->off, (B + 1) * 8, hipMemcpyDeviceToHost));
         if (o->total_requests) for (size_t j = 0; j < B; ++j) o->total_requests[j] = off[j + 1] - off[j];
         if (o->lb) { o->lb[0] = off[B]; o->lb[1] = off[B]; o->lb[2] = 0; o->lb[3] = 0; o->lb[4] = 0; }
     }
@@ -2495,53 +2455,53 @@ int hs_lb_get_stats(hs_lb *h, const hs_lb_stats *o) {
 
 int hs_lb_set_probes(hs_lb *h, int32_t n_probes, const int32_t *target_kind, const int32_t *target_index,
                      const uint8_t *metric, const double *interval_s) {
-    if (!h) return lfail(h, HS_E_INVALID, "hs_lb_set_probes: null handle");
-    if (h->Q.n > 0) return lfail(h, HS_E_STATE, "probes already set");
+    if (!h) return fail(h, HS_E_INVALID, "hs_lb_set_probes: null handle");
+    if (h->Q.n > 0) return fail(h, HS_E_STATE, "probes already set");
     if (n_probes <= 0) return HS_OK;
-    if (!target_kind || !target_index || !metric || !interval_s) return lfail(h, HS_E_INVALID, "hs_lb_set_probes: null argument");
-    LB_HIP(h, hipSetDevice(h->cfg.device));
+    if (!target_kind || !target_index || !metric || !interval_s) return fail(h, HS_E_INVALID, "hs_lb_set_probes: null argument");
+    HS_HIP(h, hipSetDevice(h->cfg.device));
     const int B = h->cfg.n_backends;
     std::vector<double> rate((size_t)n_probes);
     double min_iv = 0.0;
     for (int j = 0; j < n_probes; ++j) {
         const int k = target_kind[j], i = target_index[j], m = metric[j];
-        if (k < 0 || k > 2) return lfail(h, HS_E_UNSUPPORTED, "probe %d: target kind %d (0 = backend Server, 1 = Sink, 2 = Source)", j, k);
+        if (k < 0 || k > 2) return fail(h, HS_E_UNSUPPORTED, "probe %d: target kind %d (0 = backend Server, 1 = Sink, 2 = Source)", j, k);
         if (k == 2) {
-            if (i < 0 || i >= h->cfg.n_sources) return lfail(h, HS_E_INVALID, "probe %d: source %d out of range", j, i);
-            if (m != HS_PROBE_GENERATED) return lfail(h, HS_E_UNSUPPORTED, "probe %d: metric %d is not an attribute of a Source", j, m);
+            if (i < 0 || i >= h->cfg.n_sources) return fail(h, HS_E_INVALID, "probe %d: source %d out of range", j, i);
+            if (m != HS_PROBE_GENERATED) return fail(h, HS_E_UNSUPPORTED, "probe %d: metric %d is not an attribute of a Source", j, m);
             if (h->src_stop_h[(size_t)i] >= 0)
-                return lfail(h, HS_E_UNSUPPORTED, "probe %d: a Source with stop_after keeps ticking without Requests, which its log does not hold", j);
+                return fail(h, HS_E_UNSUPPORTED, "probe %d: a Source with stop_after keeps ticking without Requests, which its log does not hold", j);
         }
-        if (k == 0 && (i < 0 || i >= B)) return lfail(h, HS_E_INVALID, "probe %d: backend %d out of range", j, i);
-        if (k == 1 && (i < 0 || i >= (h->cfg.shared_sink ? 1 : B))) return lfail(h, HS_E_INVALID, "probe %d: sink %d out of range", j, i);
+        if (k == 0 && (i < 0 || i >= B)) return fail(h, HS_E_INVALID, "probe %d: backend %d out of range", j, i);
+        if (k == 1 && (i < 0 || i >= (h->cfg.shared_sink ? 1 : B))) return fail(h, HS_E_INVALID, "probe %d: sink %d out of range", j, i);
         if (k == 0 && !(m == HS_PROBE_DEPTH || m == HS_PROBE_ACTIVE || m == HS_PROBE_ACCEPTED || m == HS_PROBE_DROPPED ||
                         m == HS_PROBE_COMPLETED))
-            return lfail(h, HS_E_UNSUPPORTED, "probe %d: metric %d is not an attribute of a Server", j, m);
-        if (k == 1 && m != HS_PROBE_RECEIVED) return lfail(h, HS_E_UNSUPPORTED, "probe %d: metric %d is not an attribute of a Sink", j, m);
-        if (h->any_no_sink) return lfail(h, HS_E_UNSUPPORTED, "probes on a load-balancer graph need the backends' completion logs (a Sink downstream)");
+            return fail(h, HS_E_UNSUPPORTED, "probe %d: metric %d is not an attribute of a Server", j, m);
+        if (k == 1 && m != HS_PROBE_RECEIVED) return fail(h, HS_E_UNSUPPORTED, "probe %d: metric %d is not an attribute of a Sink", j, m);
+        if (h->any_no_sink) return fail(h, HS_E_UNSUPPORTED, "probes on a load-balancer graph need the backends' completion logs (a Sink downstream)");
         const double iv = interval_s[j];
-        if (!(iv > 0.0) || !std::isfinite(iv)) return lfail(h, HS_E_INVALID, "Probe interval must be positive.");   // probe.py:29-30
+        if (!(iv > 0.0) || !std::isfinite(iv)) return fail(h, HS_E_INVALID, "Probe interval must be positive.");   // probe.py:29-30
         rate[(size_t)j] = 1.0 / iv;
         if (min_iv == 0.0 || iv < min_iv) min_iv = iv;
     }
     const double horizon_s = (double)(h->cfg.horizon_ns - h->cfg.start_ns) / 1e9;
     const int64_t pcap = (int64_t)(horizon_s / min_iv) + 8;
-    if ((double)pcap * n_probes * 16.0 > 8e9) return lfail(h, HS_E_INVALID, "probe logs would need %.1f GB", (double)pcap * n_probes * 16.0 / 1e9);
+    if ((double)pcap * n_probes * 16.0 > 8e9) return fail(h, HS_E_INVALID, "probe logs would need %.1f GB", (double)pcap * n_probes * 16.0 / 1e9);
     LbProbes Q{};
     Q.n = n_probes; Q.pcap = pcap;
     int32_t *dk = nullptr, *di = nullptr; uint8_t *dm = nullptr; double *dr = nullptr;
     int rc;
 #define PTRY(x) do { if ((rc = (x))) return rc; } while (0)
-    PTRY(lalloc(h, &dk, (size_t)n_probes)); PTRY(lalloc(h, &di, (size_t)n_probes)); PTRY(lalloc(h, &dm, (size_t)n_probes));
-    PTRY(lalloc(h, &dr, (size_t)n_probes));
-    PTRY(lalloc(h, &Q.tick, (size_t)n_probes * (size_t)pcap)); PTRY(lalloc(h, &Q.val, (size_t)n_probes * (size_t)pcap));
-    PTRY(lalloc(h, &Q.n_tick, (size_t)n_probes)); PTRY(lalloc(h, &Q.cnt, (size_t)n_probes)); PTRY(lalloc(h, &Q.cand, (size_t)n_probes));
+    PTRY(dev_alloc(h, &dk, (size_t)n_probes)); PTRY(dev_alloc(h, &di, (size_t)n_probes)); PTRY(dev_alloc(h, &dm, (size_t)n_probes));
+    PTRY(dev_alloc(h, &dr, (size_t)n_probes));
+    PTRY(dev_alloc(h, &Q.tick, (size_t)n_probes * (size_t)pcap)); PTRY(dev_alloc(h, &Q.val, (size_t)n_probes * (size_t)pcap));
+    PTRY(dev_alloc(h, &Q.n_tick, (size_t)n_probes)); PTRY(dev_alloc(h, &Q.cnt, (size_t)n_probes)); PTRY(dev_alloc(h, &Q.cand, (size_t)n_probes));
 #undef PTRY
-    LB_HIP(h, hipMemcpy(dk, target_kind, (size_t)n_probes * 4, hipMemcpyHostToDevice));
-    LB_HIP(h, hipMemcpy(di, target_index, (size_t)n_probes * 4, hipMemcpyHostToDevice));
-    LB_HIP(h, hipMemcpy(dm, metric, (size_t)n_probes, hipMemcpyHostToDevice));
-    LB_HIP(h, hipMemcpy(dr, rate.data(), (size_t)n_probes * 8, hipMemcpyHostToDevice));
-    LB_HIP(h, hipMemset(Q.cnt, 0, (size_t)n_probes * 8));
+    HS_HIP(h, hipMemcpy(dk, target_kind, (size_t)n_probes * 4, hipMemcpyHostToDevice));
+    HS_HIP(h, hipMemcpy(di, target_index, (size_t)n_probes * 4, hipMemcpyHostToDevice));
+    HS_HIP(h, hipMemcpy(dm, metric, (size_t)n_probes, hipMemcpyHostToDevice));
+    HS_HIP(h, hipMemcpy(dr, rate.data(), (size_t)n_probes * 8, hipMemcpyHostToDevice));
+    HS_HIP(h, hipMemset(Q.cnt, 0, (size_t)n_probes * 8));
     Q.kind = dk; Q.idx = di; Q.metric = dm; Q.rate = dr;
     // the tick times do not depend on the run: once, from the tick-table kernel (hs_tables.hpp: _ProbeProfile goes through
     // the reference's numerical path), Q.tick IS the table (row j, pcap entries), up to the second tick beyond the horizon
@@ -2554,15 +2514,15 @@ int hs_lb_set_probes(hs_lb *h, int32_t n_probes, const int32_t *target_kind, con
         }
         TickRow *drows = nullptr;
         unsigned long long *dstat = nullptr;
-        if ((rc = lalloc(h, &drows, (size_t)n_probes))) return rc;
-        if ((rc = lalloc(h, &dstat, 2))) return rc;
-        LB_HIP(h, hipMemcpy(drows, rows.data(), rows.size() * sizeof(TickRow), hipMemcpyHostToDevice));
-        LB_HIP(h, tick_tables_launch(h->stream, drows, n_probes, h->cfg.start_ns, h->cfg.horizon_ns, pcap, Q.tick, Q.n_tick, dstat,
+        if ((rc = dev_alloc(h, &drows, (size_t)n_probes))) return rc;
+        if ((rc = dev_alloc(h, &dstat, 2))) return rc;
+        HS_HIP(h, hipMemcpy(drows, rows.data(), rows.size() * sizeof(TickRow), hipMemcpyHostToDevice));
+        HS_HIP(h, tick_tables_launch(h->stream, drows, n_probes, h->cfg.start_ns, h->cfg.horizon_ns, pcap, Q.tick, Q.n_tick, dstat,
                                      h->lane_budget, false));
-        LB_HIP(h, hipStreamSynchronize(h->stream));
+        HS_HIP(h, hipStreamSynchronize(h->stream));
         unsigned long long st[2] = {0ull, 0ull};
-        LB_HIP(h, hipMemcpy(st, dstat, sizeof st, hipMemcpyDeviceToHost));
-        if (st[0] != 0ull) return lfail(h, HS_E_UNSUPPORTED, "probe %lld: a tick needs more than 64 x %lld adaptive-Simpson intervals", (long long)st[0] - 2, (long long)h->lane_budget);
+        HS_HIP(h, hipMemcpy(st, dstat, sizeof st, hipMemcpyDeviceToHost));
+        if (st[0] != 0ull) return fail(h, HS_E_UNSUPPORTED, "probe %lld: a tick needs more than 64 x %lld adaptive-Simpson intervals", (long long)st[0] - 2, (long long)h->lane_budget);
         // (a table that ends before `pcap` entries simply has fewer ticks; one that fills it ends on its last entry, as before)
     }
     h->Q = Q;
@@ -2570,51 +2530,51 @@ int hs_lb_set_probes(hs_lb *h, int32_t n_probes, const int32_t *target_kind, con
 }
 
 int hs_lb_set_profile_budget(hs_lb *h, int64_t intervals_per_lane) {
-    if (!h) return lfail(h, HS_E_INVALID, "hs_lb_set_profile_budget: null handle");
-    if (intervals_per_lane < 1) return lfail(h, HS_E_INVALID, "hs_lb_set_profile_budget: the budget must be >= 1");
+    if (!h) return fail(h, HS_E_INVALID, "hs_lb_set_profile_budget: null handle");
+    if (intervals_per_lane < 1) return fail(h, HS_E_INVALID, "hs_lb_set_profile_budget: the budget must be >= 1");
     h->lane_budget = (long long)intervals_per_lane;
     h->tables_built = false;
     return HS_OK;
 }
 
 int64_t hs_lb_read_probe(hs_lb *h, int32_t probe, int64_t *t_ns, int64_t *values, int64_t cap) {
-    if (!h || !h->ran) return lfail(h, HS_E_STATE, "hs_lb_read_probe before hs_lb_run");
-    if (probe < 0 || probe >= h->Q.n) return lfail(h, HS_E_INVALID, "probe %d out of range", probe);
-    if (hipSetDevice(h->cfg.device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return lfail(h, HS_E_HIP, "device synchronisation failed");
+    if (!h || !h->ran) return fail(h, HS_E_STATE, "hs_lb_read_probe before hs_lb_run");
+    if (probe < 0 || probe >= h->Q.n) return fail(h, HS_E_INVALID, "probe %d out of range", probe);
+    if (hipSetDevice(h->cfg.device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, HS_E_HIP, "device synchronisation failed");
     int64_t cnt = 0;
-    if (hipMemcpy(&cnt, h->Q.cnt + probe, 8, hipMemcpyDeviceToHost) != hipSuccess) return lfail(h, HS_E_HIP, "memcpy");
+    if (hipMemcpy(&cnt, h->Q.cnt + probe, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, HS_E_HIP, "memcpy");
     if (cnt > cap) cnt = cap;
     if (cnt > 0) {
         const size_t o = (size_t)probe * (size_t)h->Q.pcap;
-        if (t_ns && hipMemcpy(t_ns, h->Q.tick + o, (size_t)cnt * 8, hipMemcpyDeviceToHost) != hipSuccess) return lfail(h, HS_E_HIP, "memcpy");
-        if (values && hipMemcpy(values, h->Q.val + o, (size_t)cnt * 8, hipMemcpyDeviceToHost) != hipSuccess) return lfail(h, HS_E_HIP, "memcpy");
+        if (t_ns && hipMemcpy(t_ns, h->Q.tick + o, (size_t)cnt * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, HS_E_HIP, "memcpy");
+        if (values && hipMemcpy(values, h->Q.val + o, (size_t)cnt * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, HS_E_HIP, "memcpy");
     }
     return cnt;
 }
 
 int64_t hs_lb_read_sink(hs_lb *h, int32_t sink, int64_t *t_ns, int64_t *created_ns, int64_t cap) {
-    if (!h || !h->ran) return lfail(h, HS_E_STATE, "hs_lb_run has not been called");
+    if (!h || !h->ran) return fail(h, HS_E_STATE, "hs_lb_run has not been called");
     if (hipSetDevice(h->cfg.device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
-        return lfail(h, HS_E_HIP, "device synchronisation failed");
+        return fail(h, HS_E_HIP, "device synchronisation failed");
     const int B = h->cfg.n_backends;
     int64_t cnt = 0;
     const int64_t *src_t, *src_c;
     if (h->cfg.shared_sink) {
-        if (sink != 0) return lfail(h, HS_E_INVALID, "shared sink: the only sink index is 0");
-        if (hipMemcpy(&cnt, h->n_done, 8, hipMemcpyDeviceToHost) != hipSuccess) return lfail(h, HS_E_HIP, "memcpy");
+        if (sink != 0) return fail(h, HS_E_INVALID, "shared sink: the only sink index is 0");
+        if (hipMemcpy(&cnt, h->n_done, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, HS_E_HIP, "memcpy");
         src_t = h->out_t; src_c = h->out_created;
     } else {
-        if (sink < 0 || sink >= B) return lfail(h, HS_E_INVALID, "sink index %d out of range", sink);
+        if (sink < 0 || sink >= B) return fail(h, HS_E_INVALID, "sink index %d out of range", sink);
         int64_t o = 0;
         LbTotals tt;
         if (hipMemcpy(&cnt, h->PB.received + sink, 8, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(&o, h->off + sink, 8, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(&tt, h->tot, sizeof tt, hipMemcpyDeviceToHost) != hipSuccess) return lfail(h, HS_E_HIP, "memcpy");
+            hipMemcpy(&tt, h->tot, sizeof tt, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, HS_E_HIP, "memcpy");
         if (tt.use_t) {                      // [m][backend] logs: gather the backend's column
             if (cnt > cap) cnt = cap;
             if (cnt <= 0) return 0;
             int64_t *tmp = nullptr;
-            if (hipMalloc(&tmp, (size_t)cnt * 8) != hipSuccess) return lfail(h, HS_E_HIP, "hipMalloc of the read-back staging buffer failed");
+            if (hipMalloc(&tmp, (size_t)cnt * 8) != hipSuccess) return fail(h, HS_E_HIP, "hipMalloc of the read-back staging buffer failed");
             const int64_t *cols[2] = {h->sink_t + sink, h->sink_created + sink};
             int64_t *dsts[2] = {t_ns, created_ns};
             for (int c = 0; c < 2; ++c) {
@@ -2624,7 +2584,7 @@ int64_t hs_lb_read_sink(hs_lb *h, int32_t sink, int64_t *t_ns, int64_t *created_
                 if (hipStreamSynchronize(h->stream) != hipSuccess ||
                     hipMemcpy(dsts[c], tmp, (size_t)cnt * 8, hipMemcpyDeviceToHost) != hipSuccess) {
                     hipFree(tmp);
-                    return lfail(h, HS_E_HIP, "sink read-back failed");
+                    return fail(h, HS_E_HIP, "sink read-back failed");
                 }
             }
             hipFree(tmp);
@@ -2634,17 +2594,17 @@ int64_t hs_lb_read_sink(hs_lb *h, int32_t sink, int64_t *t_ns, int64_t *created_
     }
     if (cnt > cap) cnt = cap;
     if (cnt > 0) {
-        if (t_ns && hipMemcpy(t_ns, src_t, (size_t)cnt * 8, hipMemcpyDeviceToHost) != hipSuccess) return lfail(h, HS_E_HIP, "memcpy");
-        if (created_ns && hipMemcpy(created_ns, src_c, (size_t)cnt * 8, hipMemcpyDeviceToHost) != hipSuccess) return lfail(h, HS_E_HIP, "memcpy");
+        if (t_ns && hipMemcpy(t_ns, src_t, (size_t)cnt * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, HS_E_HIP, "memcpy");
+        if (created_ns && hipMemcpy(created_ns, src_c, (size_t)cnt * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, HS_E_HIP, "memcpy");
     }
     return cnt;
 }
 
 int hs_lb_latency_stats(hs_lb *h, double out[6]) {
-    if (!h || !out) return lfail(h, HS_E_INVALID, "hs_lb_latency_stats: null argument");
-    if (!h->ran) return lfail(h, HS_E_STATE, "hs_lb_run has not been called");
-    if (!h->cfg.shared_sink) return lfail(h, HS_E_INVALID, "hs_lb_latency_stats is for the shared Sink; per-backend Sinks are small: read them");
-    LB_HIP(h, hipSetDevice(h->cfg.device));
+    if (!h || !out) return fail(h, HS_E_INVALID, "hs_lb_latency_stats: null argument");
+    if (!h->ran) return fail(h, HS_E_STATE, "hs_lb_run has not been called");
+    if (!h->cfg.shared_sink) return fail(h, HS_E_INVALID, "hs_lb_latency_stats is for the shared Sink; per-backend Sinks are small: read them");
+    HS_HIP(h, hipSetDevice(h->cfg.device));
     // the sort buffers are free between runs: keys0 <- latencies, sorted in the ping-pong buffers
     hipLaunchKernelGGL(hs_lb_latency_keys, dim3((unsigned)((h->n_slots + 255) / 256)), dim3(256), 0, h->stream, h->out_t,
                        h->out_created, h->n_done, h->keys0);
@@ -2654,7 +2614,7 @@ int hs_lb_latency_stats(hs_lb *h, double out[6]) {
                      h->tb > kRadixBits ? g : 0);
     (void)vr;
     double *d_out = nullptr;
-    LB_HIP(h, hipMalloc(&d_out, 6 * sizeof(double)));
+    HS_HIP(h, hipMalloc(&d_out, 6 * sizeof(double)));
     if (h->tb > kRadixBits && g) {
         // the ragged low bits were skipped: finish short runs in place (keys only) with the segment kernel's fix-up
         hipLaunchKernelGGL(hs_lb_fix_runs, dim3((unsigned)((h->n_slots + 255) / 256)), dim3(256), 0, h->stream, kr, h->n_done, g);
@@ -2663,20 +2623,20 @@ int hs_lb_latency_stats(hs_lb *h, double out[6]) {
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) e = hipMemcpy(out, d_out, 6 * sizeof(double), hipMemcpyDeviceToHost);
     hipFree(d_out);
-    if (e != hipSuccess) return lfail(h, HS_E_HIP, "latency statistics failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(h, HS_E_HIP, "latency statistics failed: %s", hipGetErrorString(e));
     return HS_OK;
 }
 
 int hs_lb_ring(hs_lb *h, int32_t *ring_backend) {
-    if (!h || !ring_backend) return lfail(h, HS_E_INVALID, "hs_lb_ring: null argument");
-    if (h->cfg.strategy != HS_LB_CONSISTENT_HASH) return lfail(h, HS_E_STATE, "hs_lb_ring: this LoadBalancer has no ConsistentHash ring");
+    if (!h || !ring_backend) return fail(h, HS_E_INVALID, "hs_lb_ring: null argument");
+    if (h->cfg.strategy != HS_LB_CONSISTENT_HASH) return fail(h, HS_E_STATE, "hs_lb_ring: this LoadBalancer has no ConsistentHash ring");
     for (size_t i = 0; i < h->ring.size(); ++i) ring_backend[i] = h->ring[i].backend;
     return HS_OK;
 }
 
 int32_t hs_lb_select(hs_lb *h, const char *key) {
-    if (!h || !key) return lfail(h, HS_E_INVALID, "hs_lb_select: null argument");
-    if (h->cfg.strategy != HS_LB_CONSISTENT_HASH) return lfail(h, HS_E_STATE, "hs_lb_select: this LoadBalancer has no ConsistentHash ring");
+    if (!h || !key) return fail(h, HS_E_INVALID, "hs_lb_select: null argument");
+    if (h->cfg.strategy != HS_LB_CONSISTENT_HASH) return fail(h, HS_E_STATE, "hs_lb_select: this LoadBalancer has no ConsistentHash ring");
     return ring_select(h->ring, key, strlen(key));
 }
 
@@ -2700,24 +2660,24 @@ int hs_debug_lb_flags(hs_lb *h, int flags) {
 int hs_debug_radix_sort(int32_t device, int64_t n, int32_t key_bits, const uint64_t *keys_in, const uint64_t *vals_in,
                         uint64_t *keys_out, uint64_t *vals_out, float *device_ms) {
     if (n <= 0 || key_bits < 1 || key_bits > 64 || !keys_in || !vals_in || !keys_out || !vals_out)
-        return lfail(nullptr, HS_E_INVALID, "hs_debug_radix_sort: bad argument");
+        return fail(nullptr, HS_E_INVALID, "hs_debug_radix_sort: bad argument");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return lfail(nullptr, HS_E_NO_DEVICE, "no HIP device visible");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, HS_E_NO_DEVICE, "no HIP device visible");
     hs_lb h;
     h.cfg.device = device;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking) != hipSuccess)
-        return lfail(nullptr, HS_E_HIP, "device setup failed");
+        return fail(nullptr, HS_E_HIP, "device setup failed");
     hipEventCreate(&h.ev0); hipEventCreate(&h.ev1);
     h.n_slots = n;
     h.n_tiles = (int)((n + kRadixTile - 1) / kRadixTile);
     uint64_t *k0 = nullptr, *v0 = nullptr;
     int rc = HS_OK;
     const size_t N = (size_t)n;
-    if ((rc = lalloc(&h, &k0, N)) || (rc = lalloc(&h, &v0, N)) || (rc = lalloc(&h, &h.kA, N)) || (rc = lalloc(&h, &h.vA, N)) ||
-        (rc = lalloc(&h, &h.kB, N)) || (rc = lalloc(&h, &h.vB, N)) || (rc = lalloc(&h, &h.n_slots_dev, 1)) ||
-        (rc = lalloc(&h, &h.n_arr, 1)) || (rc = lalloc(&h, &h.hist, (size_t)kRadixBins * (size_t)h.n_tiles)) ||
-        (rc = lalloc(&h, &h.row_total, (size_t)kRadixBins)) || (rc = lalloc(&h, &h.digit_base, (size_t)kRadixBins))) {
-        g_lb_error = h.error;
+    if ((rc = dev_alloc(&h, &k0, N)) || (rc = dev_alloc(&h, &v0, N)) || (rc = dev_alloc(&h, &h.kA, N)) || (rc = dev_alloc(&h, &h.vA, N)) ||
+        (rc = dev_alloc(&h, &h.kB, N)) || (rc = dev_alloc(&h, &h.vB, N)) || (rc = dev_alloc(&h, &h.n_slots_dev, 1)) ||
+        (rc = dev_alloc(&h, &h.n_arr, 1)) || (rc = dev_alloc(&h, &h.hist, (size_t)kRadixBins * (size_t)h.n_tiles)) ||
+        (rc = dev_alloc(&h, &h.row_total, (size_t)kRadixBins)) || (rc = dev_alloc(&h, &h.digit_base, (size_t)kRadixBins))) {
+        g_last_error = h.error;
     } else {
         hipMemcpy(k0, keys_in, N * 8, hipMemcpyHostToDevice);
         hipMemcpy(v0, vals_in, N * 8, hipMemcpyHostToDevice);
@@ -2726,7 +2686,7 @@ int hs_debug_radix_sort(int32_t device, int64_t n, int32_t key_bits, const uint6
         hipEventRecord(h.ev0, h.stream);
         radix_sort_async(&h, k0, v0, h.n_slots_dev, h.n_arr, key_bits, RadixAll{}, NoVal{}, &kr, &vr);
         hipEventRecord(h.ev1, h.stream);
-        if (hipStreamSynchronize(h.stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = lfail(nullptr, HS_E_HIP, "radix sort failed");
+        if (hipStreamSynchronize(h.stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = fail(nullptr, HS_E_HIP, "radix sort failed");
         else {
             hipMemcpy(keys_out, kr, N * 8, hipMemcpyDeviceToHost);
             hipMemcpy(vals_out, vr, N * 8, hipMemcpyDeviceToHost);
@@ -2748,11 +2708,11 @@ int hs_debug_radix_sort(int32_t device, int64_t n, int32_t key_bits, const uint6
 // records of one station keep their order and equal timestamps of different stations come in station order (the
 // reference orders those by event creation: DESIGN.md "known deviations" (i)).  In place.
 int hs_merge_sink_records(int32_t device, int64_t n, int64_t *t_ns, int64_t *created_ns) {
-    if (n < 0 || (n > 0 && (!t_ns || !created_ns))) return lfail(nullptr, HS_E_INVALID, "hs_merge_sink_records: bad argument");
+    if (n < 0 || (n > 0 && (!t_ns || !created_ns))) return fail(nullptr, HS_E_INVALID, "hs_merge_sink_records: bad argument");
     if (n < 2) return HS_OK;
     int64_t tmax = 0;
     for (int64_t i = 0; i < n; ++i) {
-        if (t_ns[i] < 0) return lfail(nullptr, HS_E_INVALID, "hs_merge_sink_records: negative timestamp");
+        if (t_ns[i] < 0) return fail(nullptr, HS_E_INVALID, "hs_merge_sink_records: negative timestamp");
         if (t_ns[i] > tmax) tmax = t_ns[i];
     }
     int bits = 1;
@@ -2768,7 +2728,7 @@ int hs_merge_sink_records(int32_t device, int64_t n, int64_t *t_ns, int64_t *cre
 
 // Sink.latency_stats() (components/common.py:59-76, instrumentation/data.py:197-210) of any Sink's records on the device:
 int hs_set_float_sum_mode(int compensated) {
-    if (compensated != 0 && compensated != 1) return lfail(nullptr, HS_E_INVALID, "hs_set_float_sum_mode: 0 (left to right) or 1 (Neumaier, CPython >= 3.12)");
+    if (compensated != 0 && compensated != 1) return fail(nullptr, HS_E_INVALID, "hs_set_float_sum_mode: 0 (left to right) or 1 (Neumaier, CPython >= 3.12)");
     g_float_sum_mode = compensated;
     return HS_OK;
 }
@@ -2777,13 +2737,13 @@ int hs_set_float_sum_mode(int compensated) {
 // routine of the load-balancer engine (hs_lb_latency_stats) for the station engines' Sinks.  out = {count, avg, min, max,
 // p50, p99}.  Host buffers in, six doubles out.
 int hs_sink_latency_stats(int32_t device, int64_t n, const int64_t *t_ns, const int64_t *created_ns, double out[6]) {
-    if (n < 0 || !out || (n > 0 && (!t_ns || !created_ns))) return lfail(nullptr, HS_E_INVALID, "hs_sink_latency_stats: bad argument");
+    if (n < 0 || !out || (n > 0 && (!t_ns || !created_ns))) return fail(nullptr, HS_E_INVALID, "hs_sink_latency_stats: bad argument");
     for (int k = 0; k < 6; ++k) out[k] = 0.0;
     if (n == 0) return HS_OK;
     std::vector<uint64_t> lat((size_t)n), zero((size_t)n, 0ull), ko((size_t)n), vo((size_t)n);
     uint64_t lmax = 0;
     for (int64_t i = 0; i < n; ++i) {
-        if (t_ns[i] < created_ns[i]) return lfail(nullptr, HS_E_INVALID, "hs_sink_latency_stats: a record completes before it was created");
+        if (t_ns[i] < created_ns[i]) return fail(nullptr, HS_E_INVALID, "hs_sink_latency_stats: a record completes before it was created");
         lat[(size_t)i] = (uint64_t)(t_ns[i] - created_ns[i]);
         if (lat[(size_t)i] > lmax) lmax = lat[(size_t)i];
     }
@@ -2791,7 +2751,7 @@ int hs_sink_latency_stats(int32_t device, int64_t n, const int64_t *t_ns, const 
     while (bits < 63 && (lmax >> bits) != 0) ++bits;
     int rc = hs_debug_radix_sort(device, n, bits, lat.data(), zero.data(), ko.data(), vo.data(), nullptr);
     if (rc != HS_OK) return rc;
-    if (hipSetDevice(device) != hipSuccess) return lfail(nullptr, HS_E_HIP, "hipSetDevice failed");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, HS_E_HIP, "hipSetDevice failed");
     uint64_t *d_sorted = nullptr; int64_t *d_n = nullptr; double *d_out = nullptr;
     hipError_t e = hipMalloc(&d_sorted, (size_t)n * 8);
     if (e == hipSuccess) e = hipMalloc(&d_n, 8);
@@ -2804,7 +2764,7 @@ int hs_sink_latency_stats(int32_t device, int64_t n, const int64_t *t_ns, const 
     }
     if (e == hipSuccess) e = hipMemcpy(out, d_out, 6 * sizeof(double), hipMemcpyDeviceToHost);
     hipFree(d_sorted); hipFree(d_n); hipFree(d_out);
-    if (e != hipSuccess) return lfail(nullptr, HS_E_HIP, "hs_sink_latency_stats: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(nullptr, HS_E_HIP, "hs_sink_latency_stats: %s", hipGetErrorString(e));
     return HS_OK;
 }
 

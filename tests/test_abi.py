@@ -115,6 +115,15 @@ def test_product_never_imports_the_oracle():
                     "oracle/ ", ""), f
 
 
+def test_the_setup_plan_stays_on_the_host():
+    """csrc/hs_plan.hpp decides an engine's set-up before any device call: it calls nothing of the HIP runtime and never sees
+    the engine handle, so a refused request cannot leave a handle half configured."""
+    text = open(os.path.join(N.CSRC, "hs_plan.hpp")).read()
+    assert "plan_stations(" in text and "plan_network(" in text
+    assert re.findall(r"hip[A-Z]\w*\(", text) == []
+    assert "hs_engine *" not in text and "hs_engine*" not in text
+
+
 def test_library_is_loaded_after_torch():
     """One HIP runtime per process: PyTorch-ROCm bundles its own libamdhip64.so.7, and a process that maps this library's
     copy first leaves torch without a device (seen on MI355X).  _native.lib() therefore imports torch before dlopen --
