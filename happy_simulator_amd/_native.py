@@ -31,6 +31,9 @@ PROF_CONSTANT, PROF_LINEAR_RAMP, PROF_SPIKE = 0, 1, 2
 LAT_EXPONENTIAL, LAT_CONSTANT, LAT_NO_SERVER = 0, 1, 2
 EGRESS_NONE, EGRESS_SINK, EGRESS_LINK, EGRESS_ROUTER, EGRESS_SERVER = 0, 1, 2, 3, 4
 LB_CONSISTENT_HASH, LB_ROUND_ROBIN, LB_RANDOM = 0, 1, 2
+LB_WEIGHTED_ROUND_ROBIN, LB_IP_HASH, LB_LEAST_CONNECTIONS, LB_WEIGHTED_LEAST_CONNECTIONS = 3, 4, 5, 6
+GRAPH_DEBUG_LANE_SERIAL, GRAPH_DEBUG_COOPERATIVE = 1, 2     # hs_debug_graph_flags: where least-loaded selections run
+GRAPH_COOP_MIN_BACKENDS = 32                                # csrc/hs_graph.hip kCoopMinBackends (tests/test_lb_strategies_host.py compares)
 NODE_SOURCE, NODE_SERVER, NODE_SINK, NODE_LINK, NODE_ROUTER, NODE_PROBE, NODE_LB = 0, 1, 2, 3, 4, 5, 6
 EV_KINDS = 15
 EV_NAMES = ("source", "enqueue", "notify", "poll", "deliver", "work", "continuation", "sink", "link", "link_cont",
@@ -455,6 +458,18 @@ def lib():
     L.hs_graph_create.argtypes = [P(GraphConfig), P(GraphNodes), P(C.c_void_p)]
     L.hs_graph_schedule.restype = C.c_int
     L.hs_graph_schedule.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
+    L.hs_graph_set_lb_weights.restype = C.c_int
+    L.hs_graph_set_lb_weights.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+    L.hs_graph_coop_selects.restype = C.c_int64
+    L.hs_graph_coop_selects.argtypes = [C.c_void_p]
+    L.hs_debug_graph_flags.restype = C.c_int
+    L.hs_debug_graph_flags.argtypes = [C.c_void_p, C.c_int]
+    L.hs_lb_set_weights.restype = C.c_int
+    L.hs_lb_set_weights.argtypes = [C.c_void_p, C.c_void_p]
+    L.hs_lb_wrr_table.restype = C.c_int64
+    L.hs_lb_wrr_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+    L.hs_lb_ip_hash_select.restype = C.c_int32
+    L.hs_lb_ip_hash_select.argtypes = [C.c_char_p, C.c_int32]
     L.hs_graph_run_until.restype = C.c_int
     L.hs_graph_run_until.argtypes = [C.c_void_p, C.c_int64]
     L.hs_graph_run_many.restype = C.c_int
@@ -502,4 +517,5 @@ EXPORTED_SYMBOLS = (
     "hs_debug_lb_flags", "hs_engine_set_profile_budget", "hs_lb_set_profile_budget", "hs_debug_tick_table",
     "hs_graph_create", "hs_graph_schedule", "hs_graph_run_until", "hs_graph_run_many", "hs_graph_run_parts", "hs_graph_get_summary", "hs_graph_get_stats", "hs_graph_read_records",
     "hs_graph_last_error", "hs_graph_destroy",
+    "hs_graph_set_lb_weights", "hs_graph_coop_selects", "hs_debug_graph_flags", "hs_lb_set_weights", "hs_lb_wrr_table", "hs_lb_ip_hash_select",
 )

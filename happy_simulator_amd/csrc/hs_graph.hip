@@ -32,6 +32,7 @@
 #include "hs_device.hpp"
 #include "hs_tables_api.hpp"
 #include "hs_ring.hpp"
+#include "hs_wrr.hpp"
 
 namespace hs {
 namespace graph {
@@ -41,6 +42,12 @@ constexpr int kLdsNodes = 192, kLdsNodesBatch = 48;   // nodes whose parameters 
 constexpr int kLdsHeapBatch = 1024;            // ... of each of the heaps hs_graph_run_many runs side by side
 constexpr int kLdsHeap = 4096;                 // heap entries in LDS: 4 096 x 32 B = 128 KB of the CU's 160 (+ 24 KB of nodes)
 constexpr long long kBudget = 1ll << 21;       // events per launch (~2 s)
+// LeastConnections / WeightedLeastConnections: from this many backends on, all 64 lanes take the selection (graph_loop's outer loop);
+// below it the lone lane scans them itself.  NOT MEASURED YET -- an estimate: the hand-over costs two workgroup barriers, an LDS
+// round trip and six cross-lane steps on a (binary64, int32) pair, a few hundred cycles of the lone wavefront, i.e. a few dozen of
+// the lane-serial scan's dependent load pairs.  tools/lb_strategies_profile.py measures both sides at 8 .. 32 768 backends
+// (hs_debug_graph_flags); the crossover it finds belongs here.  Either side leaves the same bits, so the value is a matter of time only.
+constexpr int kCoopMinBackends = 32;
 
 struct GEvent {                                // 32 bytes
     int64_t t;                                 // Event.time
@@ -59,7 +66,8 @@ struct GParam {                                // 64 bytes, read-only
     int64_t lim;                               // Source: stop_after ns (< 0 never); Server: queue capacity (< 0 unbounded)
     int32_t target;
     int32_t conc;                              // Server: max_concurrent; Source: n_clients of its ClientKeyEventProvider (0: none);
-                                               // LoadBalancer: entries of its client -> backend-slot table (lim = its offset)
+                                               // LoadBalancer: entries of its client -> backend-slot table (lim = its offset);
+                                               // WeightedRoundRobin: the total weight W = entries of its selection table (lim = its offset)
     int32_t rt_off, rt_cnt;                    // router / LoadBalancer: its targets; Source / Probe: rt_off = row of its tick table (-1: none)
     uint8_t kind, sub;                         // sub: Source arrival kind (hs_source_kind); Server / link latency kind; Probe metric; LB strategy
     uint8_t pad[6];
@@ -72,7 +80,8 @@ struct GState {                                // 64 bytes
     // router: a = stats_routed (= route draws);  Sink: a = events_received
     // Probe:  a = ticks taken from its table, c = samples
     // LoadBalancer: a = requests_received, b = requests_forwarded, c = requests_failed (= no_backend_available), d = in flight,
-    //               svc_draws = RoundRobin._index (ConsistentHash: its fallback's, the key-less Requests);  Source: svc_draws = KEY draws
+    //               svc_draws = RoundRobin._index (ConsistentHash / IPHash: their fallback's, the key-less Requests; WeightedRoundRobin:
+    //               its selections);  Source: svc_draws = KEY draws
     int64_t a, b, c, d;
     double total_service;                      // Server._total_service_time
     uint64_t svc_draws;
@@ -106,6 +115,7 @@ struct GVars {                                 // device scalars
     int status;
     long long sched_done;                      // scheduled entries already pushed
     long long heap_peak;
+    long long coop_selects;                    // least-loaded selections all 64 lanes took (hs_graph_coop_selects)
 };
 
 struct GCtl {                                  // kernel argument
@@ -118,7 +128,12 @@ struct GCtl {                                  // kernel argument
     // tick tables (hs_tables.hpp) of the time-varying Sources and the Probes: tick k of row r at ticks[r * tick_cap + k]; a row
     // holds tick_count[r] ticks -- up to two beyond the horizon it was computed for, or up to the stream's end (kInfNs)
     const int64_t *ticks; long long tick_cap; const int64_t *tick_count;
-    const int32_t *key_table;                  // ConsistentHash.select(str(client id)) as a backend slot, per LoadBalancer (GParam::lim)
+    const int32_t *key_table;                  // ConsistentHash / IPHash .select(str(client id)) as a backend slot, per LoadBalancer (GParam::lim);
+                                               // WeightedRoundRobin: one period of its selection sequence
+    const int32_t *lb_w;                       // [n_rt] the weighted strategies' weight of every backend slot (strategy._weights; default 1)
+    int coop_reset;                            // 1: the first launch of a run -- the lone lane zeroes GVars::coop_selects (the host clears it after the launch)
+    int coop_min;                              // least-loaded selections over >= this many backends go to all 64 lanes; 0: never (no such
+                                               // LoadBalancer in the graph, or the lane-serial scan is forced)
     GVars *V;
     uint64_t seed;
     int64_t start_ns, end_ns;
@@ -251,11 +266,20 @@ __device__ inline int64_t next_arrival(const GCtl &c, int n) {
     return a2;
 }
 
+// LeastConnections._get_connections (strategies.py:163-177: Server.active_requests) / WeightedLeastConnections._get_score (:227-231:
+// connections / weight, a true division of two ints = the correctly rounded binary64 quotient)
+__device__ __forceinline__ double lb_score(const GCtl &c, const GParam &p, int slot) {
+    const int be = c.rt_targets[p.rt_off + slot];
+    const double act = (double)c.S[be].active;
+    return p.sub == HS_LB_WEIGHTED_LEAST_CONNECTIONS ? __ddiv_rn(act, (double)c.lb_w[p.rt_off + slot]) : act;
+}
+
 // NL: graphs of up to NL nodes keep their nodes' parameters and state in LDS for the launch (the loop's dependent chain goes
 // through them several times per event: 64-cycle LDS round trips instead of L2's) -- `lnodes`: NL x (GParam + GState).
 template <int W, int NL>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     __shared__ unsigned long long s_by_kind[HS_EV_KINDS];
+    __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
     GCtl c = c0;
     GVars &V = *c.V;
     const int lane = threadIdx.x;
@@ -277,11 +301,15 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         for (long long i = lane; i < n8; i += 64) dst[i] = src[i];
     }
     __syncthreads();
+    // The lone lane's registers live across the outer loop below (the other 63 lanes carry copies they never use).
+    int req_free = V.req_free, req_len = V.req_len;                         // (registers for the launch)
+    Heap<W> H{(lds_u32x4 *)lheap, c.heap, V.heap_len};
+    unsigned long long G = V.counter;
+    int status = kRunning;
+    int sel = -1, sel_node = -1;               // a selection the wavefront made for the LoadBalancer event on top of the heap
+    long long cur = V.cur, processed = 0, n_completed = 0, n_received = 0, rec_n = V.rec_n, n_coop = 0;
+    long long peak = V.heap_peak;
     if (lane == 0) {
-        int req_free = V.req_free, req_len = V.req_len;                     // (registers for the launch)
-        Heap<W> H{(lds_u32x4 *)lheap, c.heap, V.heap_len};
-        unsigned long long G = V.counter;
-        int status = kRunning;
         if (!V.booted) {
             // Simulation.__init__ (core/simulation.py:145-154) + Source.start (load/source.py:120-140): the Sources in list order,
             // their first SourceEvents numbered by the process-wide counter
@@ -315,8 +343,13 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             H.push(mk_pre(t, V.global_counter++, arrival_kind(c.P, node), node, r));
             V.sched_done++;
         }
-        long long cur = V.cur, processed = 0, n_completed = 0, n_received = 0, rec_n = V.rec_n;
-        long long peak = V.heap_peak;
+        cur = V.cur;
+    }
+    // Wave-uniform outer loop: the lone lane walks the event loop until it ends or until the event on top of the heap is a least-loaded
+    // selection over many backends; that one all 64 lanes take (an O(B) scan is no work for one lane), then the lone lane goes on.
+    for (;;) {
+      int want = -1;
+      if (lane == 0) {
         while (status == kRunning) {
             // core/simulation.py:472 tests the PREVIOUS event's time; a PART of a Simulation stops in front of the first event beyond
             // the end (which of the parts' first events the reference still processes is decided across all of them)
@@ -337,6 +370,13 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                             status |= kGrowTicks; break;
                         }
                     }
+                }
+            }
+            if (c.coop_min > 0 && sel < 0) {                                       // (a graph without such a LoadBalancer: one uniform test)
+                const GEvent top = H.get(0);
+                if (top.kind == HS_EV_LB && top.t >= cur) {
+                    const GParam &tp = c.P[top.node];
+                    if (tp.sub >= HS_LB_LEAST_CONNECTIONS && tp.rt_cnt >= c.coop_min) { want = top.node; break; }
                 }
             }
             if (H.len > peak) peak = H.len;
@@ -498,12 +538,26 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 }
                 const int64_t client = c.reqs[e.req].client;
                 int slot = 0;
-                if (p.sub == HS_LB_CONSISTENT_HASH) {
-                    if (client >= 0 && client < (int64_t)p.conc) slot = c.key_table[p.lim + client];   // ConsistentHash.select(str(client_id))
+                if (p.sub == HS_LB_CONSISTENT_HASH || p.sub == HS_LB_IP_HASH) {
+                    if (client >= 0 && client < (int64_t)p.conc) slot = c.key_table[p.lim + client];   // .select(str(client_id)): a table
                     else {                                                          // no key: `self._fallback.select(...)`, a RoundRobin of
-                        slot = (int)(s.svc_draws % (uint64_t)p.rt_cnt);             // the strategy's own (strategies.py:362,420-421)
+                        slot = (int)(s.svc_draws % (uint64_t)p.rt_cnt);             // the strategy's own (strategies.py:309,326-328,362,420-421)
                         s.svc_draws += 1;
                     }
+                } else if (p.sub == HS_LB_WEIGHTED_ROUND_ROBIN) {                   // strategies.py:111-134: periodic in the total weight
+                    slot = c.key_table[p.lim + (int64_t)(s.svc_draws % (uint64_t)p.conc)];
+                    s.svc_draws += 1;
+                } else if (p.sub >= HS_LB_LEAST_CONNECTIONS) {
+                    // min(backends, key=...) (strategies.py:179-186,233-237): the FIRST backend with the smallest score
+                    if (sel >= 0 && sel_node == n) { slot = sel; n_coop++; }        // (the wavefront took it, below)
+                    else {
+                        double best = lb_score(c, p, 0);
+                        for (int q = 1; q < p.rt_cnt; ++q) {
+                            const double sc = lb_score(c, p, q);
+                            if (sc < best) { best = sc; slot = q; }
+                        }
+                    }
+                    sel = -1;
                 } else if (p.sub == HS_LB_ROUND_ROBIN) {
                     slot = (int)(s.svc_draws % (uint64_t)p.rt_cnt);                 // backends[_index % len], _index += 1 (strategies.py:66-67)
                     s.svc_draws += 1;
@@ -548,11 +602,38 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             default: status |= kBadKind; break;
             }
         }
+        s_want = want;
+      }
+      __syncthreads();
+      const int wn = s_want;
+      if (wn < 0) break;
+      {
+        // The selection of LoadBalancer `wn` by all 64 lanes: lane l scores slots l, l + 64, ... (ascending, so a lane keeps its first
+        // minimum), then a butterfly over the lanes keeps the smaller (score, slot) pair -- the first minimum in add_backend order.  The
+        // nodes' state is the lone lane's, visible behind the barrier (LDS, or HBM written by this very wavefront).
+        const GParam wp = c.P[wn];
+        double best = __longlong_as_double(0x7ff0000000000000ll);
+        int bslot = 0x7fffffff;
+        for (int q = lane; q < wp.rt_cnt; q += 64) {
+            const double sc = lb_score(c, wp, q);
+            if (sc < best) { best = sc; bslot = q; }
+        }
+        for (int m = 32; m >= 1; m >>= 1) {
+            const double ob = __shfl_xor(best, m, 64);
+            const int os = __shfl_xor(bslot, m, 64);
+            if (ob < best || (ob == best && os < bslot)) { best = ob; bslot = os; }
+        }
+        sel = bslot; sel_node = wn;
+      }
+      __syncthreads();
+    }
+    if (lane == 0) {
         V.heap_len = H.len; V.counter = G; V.cur = cur; V.processed += processed; V.rec_n = rec_n;
         for (int k = 0; k < HS_EV_KINDS; ++k) V.by_kind[k] += (long long)s_by_kind[k];
         V.req_free = req_free; V.req_len = req_len;
         V.completed += n_completed; V.received += n_received;
         V.heap_peak = peak;
+        V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
     __syncthreads();
@@ -607,6 +688,10 @@ struct hs_graph {
     int32_t *d_sched_node = nullptr; int64_t *d_sched_t = nullptr; long long d_sched_cap = 0;
     int32_t *d_rt_targets = nullptr;
     int32_t *d_key_table = nullptr;
+    std::vector<int32_t> key_table;            // host image of d_key_table (hs_graph_set_lb_weights appends a WeightedRoundRobin's new table)
+    std::vector<int32_t> lb_w;                 // [n_rt] host image of ctl.lb_w
+    bool has_least_loaded = false;             // a LeastConnections / WeightedLeastConnections LoadBalancer among the nodes
+    int debug_flags = 0;                       // hs_debug_graph_flags
     // tick tables: one row per time-varying Source and per distinct Probe interval, computed up to `tick_horizon`
     std::vector<hs::TickRow> rows;
     std::vector<double> row_rate;              // ticks per second a row may reach (sizes the table)
@@ -686,7 +771,7 @@ void hs_graph_destroy(hs_graph *g) {
     (void)hipSetDevice(g->cfg.device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *bufs[] = {g->ctl.heap, g->ctl.reqs, g->ctl.rec_node, g->ctl.rec_t, g->ctl.rec_cr, (void *)g->ctl.P, g->ctl.S,
-                    g->d_rt_targets, g->d_key_table, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
+                    g->d_rt_targets, g->d_key_table, (void *)g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
                     g->d_tick_status};
     for (void *b : bufs) if (b && !in_slab(g, b)) (void)hipFree(b);
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
@@ -721,6 +806,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     std::vector<double> row_rate;
     double rate_sum = 0.0;
     int n_src = 0;
+    bool has_ll = false;
     bool seen_other = false, seen_probe = false;      // node order: Sources, then Probes (the pre-run sort indices), then the rest
     for (int i = 0; i < n; ++i) {
         GParam p{};
@@ -829,7 +915,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             p.rt_off = nd->rt_off[i]; p.rt_cnt = nd->rt_cnt[i];
             if (p.rt_cnt < 0 || p.rt_off < 0 || (long long)p.rt_off + p.rt_cnt > nd->n_rt) return fail(nullptr, HS_E_INVALID, "node %d: backends out of range", i);
             p.sub = nd->lb_strategy ? nd->lb_strategy[i] : (uint8_t)HS_LB_ROUND_ROBIN;                  // load_balancer.py:112: the default
-            if (p.sub > HS_LB_RANDOM) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: load-balancing strategy %d is not lowered", i, (int)p.sub);
+            if (p.sub > HS_LB_WEIGHTED_LEAST_CONNECTIONS) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: load-balancing strategy %d is not lowered", i, (int)p.sub);
             for (int q = 0; q < p.rt_cnt; ++q) {
                 const int t = nd->rt_targets[p.rt_off + q];
                 if (t < 0 || t >= n || nd->kind[t] != HS_NODE_SERVER) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: backend %d is not a Server (only Server backends are lowered)", i, t);
@@ -856,6 +942,19 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
                     key_table.push_back(hs::ring::ring_select(ring, key, (size_t)len));
                 }
             }
+            if (p.sub == HS_LB_IP_HASH && p.rt_cnt > 0) {                           // IPHash.select for key str(id) (strategies.py:330-333)
+                p.lim = (int64_t)key_table.size(); p.conc = (int32_t)kmax;
+                char key[32];
+                for (int64_t cid = 0; cid < kmax; ++cid) {
+                    const int len = snprintf(key, sizeof key, "%lld", (long long)cid);
+                    key_table.push_back(hs::wrr::ip_hash_select(key, (size_t)len, p.rt_cnt));
+                }
+            }
+            if (p.sub == HS_LB_WEIGHTED_ROUND_ROBIN && p.rt_cnt > 0) {              // every weight 1 (the default): RoundRobin's sequence
+                p.lim = (int64_t)key_table.size(); p.conc = p.rt_cnt;
+                for (int q = 0; q < p.rt_cnt; ++q) key_table.push_back(q);
+            }
+            if (p.sub >= HS_LB_LEAST_CONNECTIONS) has_ll = true;
         } break;
         default: return fail(nullptr, HS_E_UNSUPPORTED, "node %d: kind %d is not lowered", i, (int)p.kind);
         }
@@ -863,6 +962,8 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     }
     hs_graph *g = new hs_graph();
     g->cfg = *cfg; g->n = n; g->n_rt = nd->n_rt; g->params = P; g->rows = rows; g->row_rate = row_rate;
+    g->key_table = key_table; g->has_least_loaded = has_ll;
+    g->lb_w.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
     for (int i = 0; i < n; ++i) {
         const GParam &p = P[(size_t)i];
         const double draw = p.sub == HS_LAT_EXPONENTIAL ? hs::kLongestExpDraw * p.mean : p.mean;       // (-log(2^-53) = 36.7 means at most)
@@ -886,7 +987,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
     const size_t o_P = take((size_t)n * sizeof(GParam)), o_S = take((size_t)n * sizeof(GState)), o_rt = take(nrt * sizeof(int32_t)),
-                 o_key = take(key_table.size() * sizeof(int32_t)), o_taken = take(nrt * sizeof(long long)),
+                 o_key = take(key_table.size() * sizeof(int32_t)), o_w = take(nrt * sizeof(int32_t)), o_taken = take(nrt * sizeof(long long)),
                  o_rows = take(rows.size() * sizeof(hs::TickRow)), o_V = take(sizeof(GVars));
     const size_t image_bytes = off;
     const size_t o_tcount = take(rows.size() * sizeof(int64_t)), o_tstatus = take(rows.empty() ? 0 : 2 * sizeof(unsigned long long)),
@@ -903,6 +1004,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
         for (int i = 0; i < n; ++i) { S0[i].qhead = -1; S0[i].qtail = -1; }
         if (nd->n_rt > 0) std::memcpy(image.data() + o_rt, nd->rt_targets, (size_t)nd->n_rt * sizeof(int32_t));
         if (!key_table.empty()) std::memcpy(image.data() + o_key, key_table.data(), key_table.size() * sizeof(int32_t));
+        std::memcpy(image.data() + o_w, g->lb_w.data(), nrt * sizeof(int32_t));
         if (!rows.empty()) std::memcpy(image.data() + o_rows, rows.data(), rows.size() * sizeof(hs::TickRow));
         GVars v{};
         v.req_free = -1; v.cur = cfg->start_ns;
@@ -915,6 +1017,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     c.rt_targets = g->d_rt_targets;
     g->d_key_table = key_table.empty() ? nullptr : reinterpret_cast<int32_t *>(g->slab + o_key);
     c.key_table = g->d_key_table;
+    c.lb_w = reinterpret_cast<const int32_t *>(g->slab + o_w);
     c.rt_taken = reinterpret_cast<long long *>(g->slab + o_taken);
     c.V = reinterpret_cast<GVars *>(g->slab + o_V);
     if (!rows.empty()) {
@@ -932,6 +1035,76 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
 #undef HSG_HIPD
     *out = g;
     return HS_OK;
+}
+
+int hs_graph_set_lb_weights(hs_graph *g, int32_t node, const int32_t *weights, int32_t n) {
+    if (!g || !weights) return fail(g, HS_E_INVALID, "null argument");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_LB)
+        return fail(g, HS_E_INVALID, "set_lb_weights: node %d is not a LoadBalancer", node);
+    if (g->ran || g->launches > 0) return fail(g, HS_E_STATE, "set_lb_weights: the weights are set before the first run");
+    GParam &p = g->params[(size_t)node];
+    if (n != p.rt_cnt) return fail(g, HS_E_INVALID, "set_lb_weights: node %d has %d backends, got %d weights", node, p.rt_cnt, n);
+    for (int q = 0; q < n; ++q)
+        if (weights[q] < 1) return fail(g, HS_E_INVALID, "weight must be >= 1, got %d", weights[q]);     // strategies.py:103-104,205-206
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (p.sub == HS_LB_WEIGHTED_ROUND_ROBIN && n > 0) {
+        long long W = 0;
+        for (int q = 0; q < n; ++q) W += weights[q];
+        if (W > hs::wrr::kMaxTotalWeight)
+            return fail(g, HS_E_UNSUPPORTED, "WeightedRoundRobin: a total weight of %lld needs a selection table beyond 2^24 entries", W);
+        std::vector<int32_t> table;
+        hs::wrr::build_table(weights, n, table);
+        // the new table goes behind everything the other LoadBalancers keep; the device copy moves into an allocation of its own
+        const size_t at = g->key_table.size();
+        g->key_table.insert(g->key_table.end(), table.begin(), table.end());
+        int32_t *nk = nullptr;
+        HS_HIP(g, hipMalloc(&nk, g->key_table.size() * sizeof(int32_t)));
+        hipError_t e = hipMemcpy(nk, g->key_table.data(), g->key_table.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(nk); return fail(g, HS_E_HIP, "copying the selection table: %s", hipGetErrorString(e)); }
+        if (g->d_key_table && !in_slab(g, g->d_key_table)) (void)hipFree(g->d_key_table);
+        g->d_key_table = nk; g->ctl.key_table = nk;
+        p.lim = (int64_t)at; p.conc = (int32_t)W;
+        HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    }
+    if (n > 0) {
+        std::copy(weights, weights + n, g->lb_w.begin() + p.rt_off);
+        HS_HIP(g, hipMemcpy(const_cast<int32_t *>(g->ctl.lb_w) + p.rt_off, weights, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    return HS_OK;
+}
+
+int hs_debug_graph_flags(hs_graph *g, int flags) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    g->debug_flags = flags;
+    return HS_OK;
+}
+
+int64_t hs_graph_coop_selects(const hs_graph *g) {
+    if (!g) return HS_E_INVALID;
+    if (hipSetDevice(g->cfg.device) != hipSuccess) return HS_E_HIP;
+    GVars v;
+    if (hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return HS_E_HIP;
+    return v.coop_selects;
+}
+
+int64_t hs_lb_wrr_table(const int32_t *weights, int32_t n, int32_t *out, int64_t cap) {
+    if (!weights || n < 1) return fail(nullptr, HS_E_INVALID, "hs_lb_wrr_table: weights of at least one backend are required");
+    long long W = 0;
+    for (int q = 0; q < n; ++q) {
+        if (weights[q] < 1) return fail(nullptr, HS_E_INVALID, "weight must be >= 1, got %d", weights[q]);
+        W += weights[q];
+    }
+    if (W > hs::wrr::kMaxTotalWeight)
+        return fail(nullptr, HS_E_UNSUPPORTED, "WeightedRoundRobin: a total weight of %lld needs a selection table beyond 2^24 entries", W);
+    std::vector<int32_t> table;
+    hs::wrr::build_table(weights, n, table);
+    if (out) std::copy(table.begin(), table.begin() + std::min<long long>(W, cap > 0 ? cap : 0), out);
+    return W;
+}
+
+int32_t hs_lb_ip_hash_select(const char *key, int32_t n_backends) {
+    if (!key || n_backends < 1) return fail(nullptr, HS_E_INVALID, "hs_lb_ip_hash_select: a key and at least one backend are required");
+    return hs::wrr::ip_hash_select(key, strlen(key), n_backends);
 }
 
 int hs_graph_schedule(hs_graph *g, int32_t node, int64_t time_ns) {
@@ -1017,6 +1190,8 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
     }
     c.sched_node = g->d_sched_node; c.sched_t = g->d_sched_t; c.n_sched = ns;
     c.end_ns = end_ns;
+    c.coop_min = !g->has_least_loaded || (g->debug_flags & 1) ? 0 : (g->debug_flags & 2) ? 1 : kCoopMinBackends;
+    c.coop_reset = 1;                                      // (hs_graph_coop_selects counts the LAST run: zeroed by its first launch)
     g->launches = 0;
     return HS_OK;
 }
@@ -1031,6 +1206,7 @@ static int after_launch(hs_graph *g, bool *done) {
 static int after_launch_with(hs_graph *g, int status, long long processed, bool *done) {
     GCtl &c = g->ctl;
     g->launches++;
+    c.coop_reset = 0;
     struct { int status; long long processed; } v{status, processed};
     if (v.status & kBadKind) return fail(g, HS_E_INVALID, "an event of unknown kind reached the loop (internal error)");
     if (g->cfg.max_events > 0 && v.processed > g->cfg.max_events)

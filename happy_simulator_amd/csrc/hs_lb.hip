@@ -35,6 +35,7 @@
 
 #include "../../include/hs_engine.h"
 #include "hs_ring.hpp"
+#include "hs_wrr.hpp"
 #include "hs_device.hpp"
 #include "hs_tables_api.hpp"
 #include "hs_radix.hpp"
@@ -569,9 +570,11 @@ __global__ void __launch_bounds__(256) hs_lb_segments(const uint64_t *__restrict
 // the run's Requests that the LoadBalancer processes before it -- earlier ns; on one ns the one whose SourceEvent chain was created
 // first (the stamp the per-backend order uses as well, LbBackend::order_arrival_run), then input order = (tick, Source) --, and
 // that place IS the RoundRobin index: the Request leaves with key (place mod B) << tb | ns for the usual (backend, ns) sort.
+// WeightedRoundRobin (strategies.py:111-134): the same place indexes one period of the smooth-weighted sequence instead --
+// key table[place mod W] << tb | ns (csrc/hs_wrr.hpp; W entries of int32 in device memory; table == nullptr: every weight 1).
 __global__ void __launch_bounds__(256) hs_lb_rr_assign(const uint64_t *__restrict__ skey, const uint64_t *__restrict__ sval,
                                                       uint64_t *__restrict__ fkey, uint64_t *__restrict__ fval, const int64_t *n_ptr, int tb,
-                                                      int g, int B) {
+                                                      int g, int B, const int32_t *__restrict__ table, long long W) {
     __shared__ uint64_t lk[kSegTile + 2 * kSegHalo];
     const int64_t n = *n_ptr;
     const int64_t base = (int64_t)blockIdx.x * kSegTile;
@@ -601,7 +604,8 @@ __global__ void __launch_bounds__(256) hs_lb_rr_assign(const uint64_t *__restric
         for (int64_t j = i + 1; j < n && (key_at(j) >> g) == hi; ++j) rank += before(j) ? 1 : 0;
         const int64_t pos = lo + rank;
         const uint64_t tmask = tb >= 64 ? ~0ull : ((1ull << tb) - 1);
-        fkey[pos] = ((uint64_t)(pos % B) << tb) | (k & tmask);
+        const uint64_t be = table ? (uint64_t)table[pos % W] : (uint64_t)(pos % B);
+        fkey[pos] = (be << tb) | (k & tmask);
         fval[pos] = v;
     }
 }
@@ -1749,6 +1753,7 @@ struct hs_lb {
     LbBe PB{};
     LbTotals *tot = nullptr;
     int32_t *client_be = nullptr;
+    int32_t *wrr_table = nullptr; int64_t wrr_W = 0;  // WeightedRoundRobin: one period of its selection sequence (hs_lb_set_weights); nullptr = all ones
     int64_t n_table = 0, cap = 0, n_slots = 0;
     uint64_t *keys0 = nullptr, *vals0 = nullptr;      // [cap][S] arrival logs
     int64_t n_pre = 0;                                 // ticks per Source whose stream values hs_lb_source_draws produces
@@ -1936,7 +1941,7 @@ int run_async(hs_lb *h, int64_t end_ns) {
 #undef HS_LAUNCH_SOURCES
     hipLaunchKernelGGL(hs_lb_rows, dim3(1), dim3(1), 0, h->stream, h->tot, S, h->n_slots_dev);
     hipEventRecord(h->evs0, h->stream);
-    if (h->cfg.strategy == HS_LB_ROUND_ROBIN) {
+    if (h->cfg.strategy == HS_LB_ROUND_ROBIN || h->cfg.strategy == HS_LB_WEIGHTED_ROUND_ROBIN) {
         // the LoadBalancer's processing order first: all Requests by arrival ns (backend column 0), every Request's place in that
         // order, backend = place mod B (hs_lb_rr_assign); then the (backend, ns) sort of any other strategy over the dense result
         uint64_t *tk = nullptr, *tv = nullptr;
@@ -1944,7 +1949,7 @@ int run_async(hs_lb *h, int64_t end_ns) {
                          NoVal{}, &tk, &tv, nullptr, h->g_sink, h->n_slots);
         uint64_t *fk = tk == h->kA ? h->kB : h->kA, *fv = tk == h->kA ? h->vB : h->vA;
         hipLaunchKernelGGL(hs_lb_rr_assign, dim3((unsigned)((h->n_slots + kSegTile - 1) / kSegTile)), dim3(256), 0, h->stream, tk, tv, fk, fv,
-                           h->n_arr, h->tb, h->g_sink, B);
+                           h->n_arr, h->tb, h->g_sink, B, (const int32_t *)h->wrr_table, (long long)h->wrr_W);
         h->launches += 1;
         radix_sort_async(h, fk, fv, h->n_arr, h->n_arr, h->tb + h->bb, RadixAll{}, NoVal{}, &h->skey, &h->sval, fk, h->g_arr, h->n_slots);
     } else
@@ -2102,12 +2107,18 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     const int S = cfg->n_sources, B = cfg->n_backends;
     if (S <= 0) return fail(nullptr, HS_E_INVALID, "hs_lb_create: n_sources must be > 0");
     if (B <= 0) return fail(nullptr, HS_E_INVALID, "hs_lb_create: n_backends must be > 0 (the reference rejects every request otherwise)");
-    if (cfg->strategy < HS_LB_CONSISTENT_HASH || cfg->strategy > HS_LB_RANDOM) return fail(nullptr, HS_E_UNSUPPORTED, "load-balancing strategy %d is not lowered", cfg->strategy);
+    if (cfg->strategy == HS_LB_LEAST_CONNECTIONS || cfg->strategy == HS_LB_WEIGHTED_LEAST_CONNECTIONS)
+        return fail(nullptr, HS_E_UNSUPPORTED, "load-balancing strategy %d selects by the backends' live active_requests: a feedback from backend "
+                     "state is not feed-forward, the single-heap loop (hs_graph_create) orders it", cfg->strategy);
+    if (cfg->strategy < HS_LB_CONSISTENT_HASH || cfg->strategy > HS_LB_WEIGHTED_LEAST_CONNECTIONS) return fail(nullptr, HS_E_UNSUPPORTED, "load-balancing strategy %d is not lowered", cfg->strategy);
+    const bool ranked = cfg->strategy == HS_LB_ROUND_ROBIN || cfg->strategy == HS_LB_WEIGHTED_ROUND_ROBIN;   // by the Request's place in the arrival order
+    const bool iphash = cfg->strategy == HS_LB_IP_HASH;                 // keyed like ConsistentHash, with another client -> backend table
     const bool chash = cfg->strategy == HS_LB_CONSISTENT_HASH;
+    const bool keyed = chash || iphash;
     if (chash && cfg->virtual_nodes < 1) return fail(nullptr, HS_E_INVALID, "virtual_nodes must be >= 1, got %d", cfg->virtual_nodes);
     if (cfg->start_ns < 0) return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
     if (cfg->horizon_ns < cfg->start_ns) return fail(nullptr, HS_E_INVALID, "hs_lb_create: horizon_ns precedes start_ns");
-    if (!src->src_rate || (chash && !src->n_clients)) return fail(nullptr, HS_E_INVALID, "src_rate and n_clients are required");
+    if (!src->src_rate || (keyed && !src->n_clients)) return fail(nullptr, HS_E_INVALID, "src_rate and n_clients are required");
     if (!be->names || !be->name_off) return fail(nullptr, HS_E_INVALID, "backend names are required (the ring hashes them)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -2126,7 +2137,7 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
         max_ticks = std::max(max_ticks, r * horizon_s);
         min_rate = std::min(min_rate, r);
         total_rate += r;
-        if (chash) {
+        if (keyed) {
             if (src->n_clients[i] < 1) return fail(nullptr, HS_E_INVALID, "source %d: n_clients must be >= 1", i);
             kmax = std::max(kmax, src->n_clients[i]);
         }
@@ -2134,7 +2145,7 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     // RANDOM: the key draw IS the backend index -- int(u * B) through an identity table; ROUND_ROBIN: the Sources' backend column is
     // a placeholder (0), the assignment follows the global arrival order (hs_lb_rr_assign)
     if (cfg->strategy == HS_LB_RANDOM) kmax = B;
-    if (cfg->strategy == HS_LB_ROUND_ROBIN) kmax = 1;
+    if (ranked) kmax = 1;
     if (kmax > (1ll << 26)) return fail(nullptr, HS_E_UNSUPPORTED, "n_clients above 2^26 is not supported (client -> backend table)");
     int maxc = 1;
     bool any_no_sink = false;
@@ -2236,6 +2247,12 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
             const int m = snprintf(key, sizeof key, "%lld", (long long)c);
             table[(size_t)c] = ring_select(h->ring, key, (size_t)m);
         }
+    } else if (iphash) {                              // IPHash.select for key str(id) (strategies.py:330-333)
+        char key[32];
+        for (int64_t c = 0; c < kmax; ++c) {
+            const int m = snprintf(key, sizeof key, "%lld", (long long)c);
+            table[(size_t)c] = hs::wrr::ip_hash_select(key, (size_t)m, B);
+        }
     } else for (int64_t c = 0; c < kmax; ++c) table[(size_t)c] = (int32_t)c;
     h->n_table = kmax;
     hipError_t e = hipSetDevice(cfg->device);
@@ -2255,7 +2272,7 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
     h->src_stop_h.assign((size_t)S, (int64_t)-1);
     if (src->src_stop_after_ns) h->src_stop_h.assign(src->src_stop_after_ns, src->src_stop_after_ns + S);
     for (int i = 0; i < S && src->src_stop_after_ns; ++i) if (src->src_stop_after_ns[i] >= 0) h->any_stop = true;
-    if (chash) TRY(upload<int64_t>(h, &h->PS.n_clients, src->n_clients, (size_t)S, (int64_t)1));
+    if (keyed) TRY(upload<int64_t>(h, &h->PS.n_clients, src->n_clients, (size_t)S, (int64_t)1));
     else TRY(upload<int64_t>(h, &h->PS.n_clients, (const int64_t *)nullptr, (size_t)S, (int64_t)kmax));
     {   // time-varying profiles (load/profile.py:52-113): src_rate of such a Source is its PEAK rate (it sizes the tick log)
         std::vector<uint8_t> pk((size_t)S, (uint8_t)0);
@@ -2649,6 +2666,28 @@ void hs_lb_destroy(hs_lb *h) {
     for (auto e : evs) if (e) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
+}
+
+int hs_lb_set_weights(hs_lb *h, const int32_t *weights) {
+    if (!h || !weights) return fail(h, HS_E_INVALID, "hs_lb_set_weights: null argument");
+    if (h->ran) return fail(h, HS_E_STATE, "hs_lb_set_weights: the weights are set before the first run");
+    const int B = h->cfg.n_backends;
+    long long W = 0;
+    for (int j = 0; j < B; ++j) {
+        if (weights[j] < 1) return fail(h, HS_E_INVALID, "weight must be >= 1, got %d", weights[j]);      // strategies.py:103-104
+        W += weights[j];
+    }
+    if (h->cfg.strategy != HS_LB_WEIGHTED_ROUND_ROBIN) return HS_OK;          // (no other strategy of the pipeline reads weights)
+    if (W > hs::wrr::kMaxTotalWeight)
+        return fail(h, HS_E_UNSUPPORTED, "WeightedRoundRobin: a total weight of %lld needs a selection table beyond 2^24 entries", W);
+    std::vector<int32_t> table;
+    hs::wrr::build_table(weights, B, table);
+    HS_HIP(h, hipSetDevice(h->cfg.device));
+    int32_t *dt = nullptr;
+    { const int rc = dev_alloc(h, &dt, (size_t)W); if (rc) return rc; }
+    HS_HIP(h, hipMemcpy(dt, table.data(), (size_t)W * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->wrr_table = dt; h->wrr_W = W;
+    return HS_OK;
 }
 
 int hs_debug_lb_flags(hs_lb *h, int flags) {

@@ -725,11 +725,103 @@ class RoundRobin:
         self._index = 0
 
 
+class _Weighted:
+    """`_weights` (backend.name -> weight), `set_weight` / `get_weight` of the two weighted strategies (strategies.py:88-109,199-211).
+    `LoadBalancer.add_backend(backend, weight=)` calls `set_weight` when it registers the backend (load_balancer.py:203-205) -- so
+    `LoadBalancer(backends=[...], strategy=s)` resets the weights `s` held for them to 1, as in the reference: weights are set through
+    `add_backend(b, weight=w)` or by `set_weight` AFTER the LoadBalancer exists."""
+
+    def __init__(self):
+        self._weights: dict[str, int] = {}
+        self._default_weight = 1
+
+    def set_weight(self, backend: Entity, weight: int) -> None:
+        if weight < 1:
+            raise ValueError(f"weight must be >= 1, got {weight}")                        # strategies.py:103-104,205-206
+        self._weights[backend.name] = weight
+
+    def get_weight(self, backend: Entity) -> int:
+        return self._weights.get(backend.name, self._default_weight)
+
+
+class WeightedRoundRobin(_Weighted):
+    """Smooth weighted round robin (components/load_balancer/strategies.py:75-134): every current weight grows by its backend's
+    weight, the first maximum is taken and loses the total weight W.  The sequence is periodic in W, so the engine selects
+    table[k % W] for the k-th Request from one period built in libhs_hip.so (csrc/hs_wrr.hpp; `selection_table`).  After a run
+    `_selections` holds the number of selections and `_current_weights` what the reference's dict holds: w_i * t - W * n_i."""
+
+    MAX_TOTAL_WEIGHT = 1 << 24
+
+    def __init__(self):
+        super().__init__()
+        self._current_weights: dict[str, int] = {}
+        self._selections = 0
+
+    @staticmethod
+    def selection_table(weights) -> np.ndarray:
+        """One period of the selection sequence over backends 0 .. n-1 (hs_lb_wrr_table; host only, no device)."""
+        from . import _native as N
+        w = np.ascontiguousarray(weights, np.int32)
+        if len(w) == 0:
+            return np.zeros(0, np.int32)
+        if (w < 1).any():
+            raise ValueError(f"weight must be >= 1, got {int(w[w < 1][0])}")
+        total = int(w.astype(np.int64).sum())
+        if total > WeightedRoundRobin.MAX_TOTAL_WEIGHT:
+            raise NotImplementedError(f"WeightedRoundRobin: a total weight of {total} needs a selection table beyond 2^24 entries "
+                                      "(not lowered)")
+        out = np.zeros(total, np.int32)
+        got = N.lib().hs_lb_wrr_table(w.ctypes.data, len(w), out.ctypes.data, total)
+        if got != total:
+            raise N.EngineError(int(got), (N.lib().hs_graph_last_error(None) or b"").decode())
+        return out
+
+
+class IPHash:
+    """Hash of the client key (strategies.py:294-333): backends[int(md5(key).hexdigest(), 16) % len(backends)] with key =
+    str(metadata["client_id"]); a Request without a key takes the strategy's own RoundRobin (`_fallback`), which only such Requests
+    advance.  On the engine a client -> backend table, like ConsistentHash's."""
+
+    def __init__(self, get_key=None):
+        if get_key is not None:
+            raise NotImplementedError("a custom get_key is arbitrary Python; the engine hashes metadata['client_id']")
+        self._fallback = RoundRobin()
+
+
+class LeastConnections:
+    """The backend with the fewest active connections (strategies.py:152-186): min(backends, key=active_requests), the first
+    minimum in add_backend order; a Server's `active_requests` is the requests in service, not its queue depth.  The choice feeds
+    back from backend state, so only the single-heap loop orders it (csrc/hs_graph.hip: all 64 lanes scan the backends)."""
+
+
+class WeightedLeastConnections(_Weighted):
+    """Least connections with weights (strategies.py:189-237): min(backends, key=active_requests / weight), a true division in
+    binary64; the first minimum wins."""
+
+
 class Random:
     """Random backend selection (strategies.py:137-150: `random.choice(backends)`).  On the engine the choice is
     backends[int(u * len(backends))] with u the Request's draw from its Source's own Philox KEY stream -- the seed-matched form
     of the process-wide `random`, pinned against the reference with that plug (tests/golden/make_golden.py
     `_PerRequestChoice`)."""
+
+
+class PowerOfTwoChoices:
+    """strategies.py:436-475: `random.sample(backends, 2)` on the process-wide generator.  Constructible for API parity; a LoadBalancer
+    refuses it by name (no stream of the engine defines that draw)."""
+
+
+class LeastResponseTime:
+    """strategies.py:240-291: `random.choice` among the backends without data, fed by a host-side `record_response_time`.
+    Constructible for API parity; a LoadBalancer refuses it by name."""
+
+    def __init__(self, alpha: float = 0.3):
+        if not 0 < alpha <= 1:
+            raise ValueError(f"alpha must be in (0, 1], got {alpha}")                    # strategies.py:255-256
+        self._alpha = alpha
+
+
+LOWERED_STRATEGIES = (ConsistentHash, RoundRobin, Random, WeightedRoundRobin, IPHash, LeastConnections, WeightedLeastConnections)
 
 
 @dataclass(frozen=True)
@@ -759,7 +851,8 @@ class BackendInfo:
 
 class LoadBalancer(Entity):
     """Distributes requests over backends (components/load_balancer/load_balancer.py:83-473).  Lowered: the ConsistentHash,
-    RoundRobin (the default) and Random strategies over Server backends that all stay healthy for the whole run."""
+    RoundRobin (the default), Random, WeightedRoundRobin, IPHash, LeastConnections and WeightedLeastConnections strategies over Server
+    backends that all stay healthy for the whole run."""
 
     def __init__(self, name: str, backends: list[Entity] | None = None, strategy=None, on_no_backend: str = "reject"):
         super().__init__(name)
@@ -767,9 +860,13 @@ class LoadBalancer(Entity):
             raise ValueError(f"on_no_backend must be 'reject' or 'queue', got {on_no_backend}")   # load_balancer.py:120-121
         if strategy is None:
             strategy = RoundRobin()                                                       # load_balancer.py:112
-        if not isinstance(strategy, (ConsistentHash, RoundRobin, Random)):
-            raise NotImplementedError(f"strategy {type(strategy).__name__} is not lowered to the engine (ConsistentHash, "
-                                      "RoundRobin and Random are)")
+        if not isinstance(strategy, LOWERED_STRATEGIES):
+            why = ""
+            if type(strategy).__name__ in ("PowerOfTwoChoices", "LeastResponseTime"):
+                # random.sample / random.choice on the process-wide generator (strategies.py:289,470): no engine stream defines them
+                why = ": it draws from the process-wide random generator, which no stream of the engine defines"
+            raise NotImplementedError(f"strategy {type(strategy).__name__} is not lowered to the engine{why} (ConsistentHash, RoundRobin, "
+                                      "Random, WeightedRoundRobin, IPHash, LeastConnections and WeightedLeastConnections are)")
         self._strategy = strategy
         self._on_no_backend = on_no_backend
         self._backends: dict[str, BackendInfo] = {}
@@ -785,9 +882,11 @@ class LoadBalancer(Entity):
         if weight < 1:
             raise ValueError(f"weight must be >= 1, got {weight}")                        # load_balancer.py:207-208
         if backend.name in self._backends:
-            self._backends[backend.name].weight = weight
+            self._backends[backend.name].weight = weight                                  # (the strategy keeps its weight, :189-196)
             return
         self._backends[backend.name] = BackendInfo(backend=backend, weight=weight)
+        if hasattr(self._strategy, "set_weight"):                                         # load_balancer.py:203-205: a backend's FIRST
+            self._strategy.set_weight(backend, weight)                                    # registration sets the strategy's weight
 
     def remove_backend(self, backend: Entity) -> None:
         self._backends.pop(backend.name, None)

@@ -22,8 +22,12 @@ import numpy as np
 
 from . import _native as N
 from .entities import (ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity, ExponentialLatency,
-                       LatencyTracker, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random, RandomRouter, RoundRobin, Server,
-                       SimpleEventProvider, Sink, Source)
+                       IPHash, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random, RandomRouter,
+                       RoundRobin, Server, SimpleEventProvider, Sink, Source, WeightedLeastConnections, WeightedRoundRobin)
+
+_STRATEGY_CODE = ((ConsistentHash, N.LB_CONSISTENT_HASH), (RoundRobin, N.LB_ROUND_ROBIN), (Random, N.LB_RANDOM),
+                  (WeightedRoundRobin, N.LB_WEIGHTED_ROUND_ROBIN), (IPHash, N.LB_IP_HASH), (LeastConnections, N.LB_LEAST_CONNECTIONS),
+                  (WeightedLeastConnections, N.LB_WEIGHTED_LEAST_CONNECTIONS))
 
 _SINKS = (Sink, Counter, LatencyTracker)
 DEFAULT_MAX_EVENTS = 200_000_000          # ~ minutes on the one lane; Simulation(max_graph_events=) raises it
@@ -62,6 +66,7 @@ class GraphArrays:
         self.names = None
         self.name_off = None
         self.src_n_clients = None            # [n] int64: Sources with a ClientKeyEventProvider
+        self.lb_weights = None               # [n_rt] int32: strategy.get_weight(backend) per backend slot of the weighted strategies
 
     def struct(self) -> N.GraphNodes:
         s = N.GraphNodes()
@@ -100,6 +105,27 @@ class GraphEngine:
                 raise N.EngineUnavailable(msg)
             raise N.EngineError(rc, msg)
         self._h = h
+        if arrays.lb_weights is not None and arrays.lb_strategy is not None:
+            # WeightedRoundRobin / WeightedLeastConnections: strategy._weights, per LoadBalancer in slot order (the default is all ones)
+            w = np.ascontiguousarray(arrays.lb_weights, np.int32)
+            try:
+                for i in np.nonzero((arrays.kind == N.NODE_LB) & ((arrays.lb_strategy == N.LB_WEIGHTED_ROUND_ROBIN) |
+                                                                  (arrays.lb_strategy == N.LB_WEIGHTED_LEAST_CONNECTIONS)))[0]:
+                    off, cnt = int(arrays.rt_off[i]), int(arrays.rt_cnt[i])
+                    wi = np.ascontiguousarray(w[off:off + cnt])
+                    if cnt and (wi != 1).any():
+                        self._check(self._lib.hs_graph_set_lb_weights(self._h, int(i), _ptr(wi), cnt))
+            except BaseException:
+                self.close()
+                raise
+
+    def set_debug_flags(self, flags: int) -> None:
+        """hs_debug_graph_flags: N.GRAPH_DEBUG_LANE_SERIAL / N.GRAPH_DEBUG_COOPERATIVE force where least-loaded selections run."""
+        self._check(self._lib.hs_debug_graph_flags(self._h, int(flags)))
+
+    def coop_selects(self) -> int:
+        """Least-loaded selections of the last run that all 64 lanes took (hs_graph_coop_selects)."""
+        return int(self._check(self._lib.hs_graph_coop_selects(self._h)))
 
     def _check(self, rc: int):
         if rc < 0:
@@ -237,6 +263,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
     a = GraphArrays(n)
     counters = {Server: 0, NetworkLink: 0, RandomRouter: 0}
     rt: list[int] = []
+    weights: dict[int, list[int]] = {}                        # rt offset -> the weights of a weighted strategy's backends
     for i, ent in enumerate(nodes):
         if isinstance(ent, Source):
             ep, prov = ent._event_provider, ent._time_provider
@@ -326,11 +353,19 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
                 a.lb_vnodes = np.zeros(n, np.int32)
             st = ent.strategy
             a.kind[i] = N.NODE_LB
-            a.lb_strategy[i] = (N.LB_CONSISTENT_HASH if isinstance(st, ConsistentHash) else N.LB_ROUND_ROBIN if isinstance(st, RoundRobin)
-                                else N.LB_RANDOM)
+            code = next((c for cls, c in _STRATEGY_CODE if isinstance(st, cls)), None)
+            if code is None:
+                raise UnsupportedTopology(f"strategy {type(st).__name__} of '{ent.name}' is not lowered to the engine")
+            a.lb_strategy[i] = code
             a.lb_vnodes[i] = getattr(st, "virtual_nodes", 0)
             a.rt_off[i] = len(rt)
             a.rt_cnt[i] = len(backends)
+            if isinstance(st, (WeightedRoundRobin, WeightedLeastConnections)):
+                ws = [int(st.get_weight(b)) for b in backends]
+                if isinstance(st, WeightedRoundRobin) and sum(ws) > WeightedRoundRobin.MAX_TOTAL_WEIGHT:
+                    raise UnsupportedTopology(f"'{ent.name}': WeightedRoundRobin with a total weight of {sum(ws)} needs a selection table "
+                                              "beyond 2^24 entries (not lowered)")
+                weights[len(rt)] = ws
             rt.extend(node_of[id(b)] for b in backends)
         elif isinstance(ent, RandomRouter):
             if not ent.targets:
@@ -344,6 +379,10 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
         else:
             a.kind[i] = N.NODE_SINK
     a.rt_targets = np.array(rt, np.int32)
+    if weights:
+        a.lb_weights = np.ones(len(rt), np.int32)
+        for off, ws in weights.items():
+            a.lb_weights[off:off + len(ws)] = ws
     if a.lb_strategy is not None:
         _check_keys(nodes, node_of, a)
         blobs = [(x.name.encode() if isinstance(x, Server) else b"") for x in nodes]     # (only an LB's backends need their name)
@@ -407,6 +446,8 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
         if total:
             pos = np.repeat(rt_off[ids] - (np.cumsum(cnt) - cnt), cnt) + np.arange(total)
             b.rt_targets = new_index[rt[pos]].astype(np.int32)
+            if a.lb_weights is not None:
+                b.lb_weights = np.ascontiguousarray(a.lb_weights[pos])
         else:
             pos = np.zeros(0, np.int64)
             b.rt_targets = np.zeros(0, np.int32)
@@ -548,11 +589,19 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
              ent._in_flight_count, selections) = (int(v) for v in stats["lb"][i])
             if isinstance(ent.strategy, RoundRobin):
                 ent.strategy._index += selections                  # one select per forwarded Request (strategies.py:66-67)
-            elif isinstance(ent.strategy, ConsistentHash):
-                ent.strategy._fallback._index += selections        # ... per KEY-LESS Request (strategies.py:362,420-421)
+            elif isinstance(ent.strategy, (ConsistentHash, IPHash)):
+                ent.strategy._fallback._index += selections        # ... per KEY-LESS Request (strategies.py:309,362,420-421)
             off = int(a.rt_off[i])
             for q, b in enumerate(ent.all_backends):
                 ent._backends[b.name].total_requests = int(stats["rt_taken"][off + q])
+            if isinstance(ent.strategy, WeightedRoundRobin) and ent.all_backends:
+                # what select() leaves in `_current_weights` after t selections of which n_i went to backend i: w_i * t - W * n_i
+                # (strategies.py:125-132; a run starts from a fresh strategy, as every engine run starts from time zero)
+                st = ent.strategy
+                ws = [int(st.get_weight(b)) for b in ent.all_backends]
+                st._selections = selections
+                st._current_weights = ({b.name: w * selections - sum(ws) * int(stats["rt_taken"][off + q])
+                                        for q, (b, w) in enumerate(zip(ent.all_backends, ws))} if selections else {})
         elif isinstance(ent, Probe):
             sel = order[bounds[i]:bounds[i + 1]]                 # its samples: (time, sampled integer)
             ent.data_sink._set(rec_t[sel].copy(), rec_cr[sel].copy(), Probe.value_map(ent.metric, ent.target))

@@ -129,6 +129,13 @@ class LoadBalancerEngine:
             pass
 
     # ------------------------------------------------------------------
+    def set_weights(self, weights) -> None:
+        """hs_lb_set_weights: WeightedRoundRobin's weight per backend, before the first run."""
+        w = np.ascontiguousarray(weights, np.int32)
+        if w.shape != (self.B,):
+            raise ValueError(f"weights must have shape ({self.B},)")
+        self._check(self._lib.hs_lb_set_weights(self._h, w.ctypes.data))
+
     def run(self, end_ns: int) -> None:
         """`Simulation.__init__` + `run()` to end_ns (one-event overshoot included)."""
         self._check(self._lib.hs_lb_run(self._h, int(end_ns)))

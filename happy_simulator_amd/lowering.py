@@ -19,8 +19,9 @@ import numpy as np
 from . import _native as N
 from .engine import NetworkArrays, StationArrays
 from .entities import (ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
-                       ExponentialLatency, LatencyTracker, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random, RandomRouter,
-                       RoundRobin, Server, SimpleEventProvider, Sink, Source, _RecordSink)
+                       ExponentialLatency, IPHash, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe,
+                       Random, RandomRouter, RoundRobin, Server, SimpleEventProvider, Sink, Source, WeightedLeastConnections,
+                       WeightedRoundRobin, _RecordSink)
 
 _SINKS = (Sink, Counter, LatencyTracker)
 
@@ -845,17 +846,20 @@ def lower_lb(sources: list, entities: list, lb: LoadBalancer) -> LbGraph:
         if not isinstance(s, Source):
             raise UnsupportedTopology(f"source {type(s).__name__} is not a lowered Source")
         ep = s._event_provider
-        if isinstance(lb.strategy, ConsistentHash) and not isinstance(ep, ClientKeyEventProvider):
+        if isinstance(lb.strategy, (ConsistentHash, IPHash)) and not isinstance(ep, ClientKeyEventProvider):
             raise UnsupportedTopology(
                 f"source '{s.name}': requests for a key-based LoadBalancer must come from a ClientKeyEventProvider "
-                "(ConsistentHash falls back to RoundRobin for key-less requests: use strategy=RoundRobin() for those)")
+                f"({type(lb.strategy).__name__} falls back to RoundRobin for key-less requests: use strategy=RoundRobin() for those)")
         if not isinstance(ep, (ClientKeyEventProvider, SimpleEventProvider)):
             raise UnsupportedTopology(f"source '{s.name}': event provider {type(ep).__name__} is not lowered")
         if ep._target is not lb:
             raise UnsupportedTopology(f"source '{s.name}' does not target the LoadBalancer '{lb.name}'")
         if not (s.rate > 0):
             raise UnsupportedTopology(f"source '{s.name}': rate must be > 0")
-    if not isinstance(lb.strategy, (ConsistentHash, RoundRobin, Random)):
+    if isinstance(lb.strategy, (LeastConnections, WeightedLeastConnections)):
+        raise UnsupportedTopology(f"strategy {type(lb.strategy).__name__} selects by the backends' live active_requests: a feedback from "
+                                  "backend state is not feed-forward, so the pipeline does not take it (the single-heap loop orders it)")
+    if not isinstance(lb.strategy, (ConsistentHash, RoundRobin, Random, IPHash, WeightedRoundRobin)):
         raise UnsupportedTopology(f"strategy {type(lb.strategy).__name__} is not lowered")
     backends = lb.all_backends
     if not backends:
@@ -929,6 +933,13 @@ def write_back_lb(g: LbGraph, stats: dict, eng) -> None:
         int(v) for v in stats["lb"])
     if isinstance(lb.strategy, RoundRobin):
         lb.strategy._index += lb._requests_forwarded              # one select per forwarded Request (strategies.py:66-67)
+    if isinstance(lb.strategy, WeightedRoundRobin):
+        # one select per forwarded Request; `_current_weights` after t selections of which n_i went to backend i: w_i * t - W * n_i
+        st, t = lb.strategy, lb._requests_forwarded
+        ws = [int(st.get_weight(b)) for b in g.backends]
+        st._selections = t
+        st._current_weights = ({b.name: w * t - sum(ws) * int(stats["total_requests"][j]) for j, (b, w) in enumerate(zip(g.backends, ws))}
+                               if t else {})
     for j, b in enumerate(g.backends):
         b._queue.stats_accepted = int(stats["accepted"][j])
         b._queue.stats_dropped = int(stats["dropped"][j])

@@ -165,15 +165,19 @@ class Simulation:
 
         end_ns = self._end_time.nanoseconds
         src, be = g.engine_arrays()
-        from .entities import ConsistentHash, RoundRobin
+        from .entities import ConsistentHash, IPHash, RoundRobin, WeightedRoundRobin
 
         strat = g.lb.strategy
-        code = N.LB_CONSISTENT_HASH if isinstance(strat, ConsistentHash) else N.LB_ROUND_ROBIN if isinstance(strat, RoundRobin) else N.LB_RANDOM
+        code = (N.LB_CONSISTENT_HASH if isinstance(strat, ConsistentHash) else N.LB_ROUND_ROBIN if isinstance(strat, RoundRobin)
+                else N.LB_IP_HASH if isinstance(strat, IPHash) else N.LB_WEIGHTED_ROUND_ROBIN if isinstance(strat, WeightedRoundRobin)
+                else N.LB_RANDOM)
         with LoadBalancerEngine(src, be, virtual_nodes=getattr(strat, "virtual_nodes", 1), horizon_ns=end_ns,
                                 shared_sink=g.shared_sink, start_ns=self._start_time.nanoseconds, seed=self._seed,
                                 device=self._device, strategy=code) as eng:
             if g.probes:
                 eng.set_probes(*g.probe_arrays())
+            if isinstance(strat, WeightedRoundRobin):
+                eng.set_weights([strat.get_weight(b) for b in g.backends])
             eng.run(end_ns)
             es = eng.summary()
             write_back_lb(g, eng.stats(), eng)

@@ -513,8 +513,23 @@ typedef struct hs_lb_config {
  *                    as for any other assignment;  hs_lb_sources.n_clients and virtual_nodes are ignored;
  *   RANDOM           strategies.py:137-150: random.choice(backends) with the choice plugged like every draw of the seed-matched
  *                    definition: backends[int(u * len(backends))], u = the Request's draw from its Source's
- *                    KEY stream (the stream the client ids come from otherwise);  n_clients and virtual_nodes are ignored. */
-typedef enum hs_lb_strategy { HS_LB_CONSISTENT_HASH = 0, HS_LB_ROUND_ROBIN = 1, HS_LB_RANDOM = 2 } hs_lb_strategy;
+ *                    KEY stream (the stream the client ids come from otherwise);  n_clients and virtual_nodes are ignored.
+ *   WEIGHTED_ROUND_ROBIN  strategies.py:75-134, the smooth (nginx) algorithm: every current weight grows by its backend's weight,
+ *                    the first maximum is taken and loses the total weight W.  The sequence is periodic in W, so the engine keeps
+ *                    ONE period as a table (csrc/hs_wrr.hpp: built per weight class in exact int64 arithmetic) and the k-th
+ *                    selection is table[k % W]; W <= 2^24 entries of int32 (a longer table is refused by name, HS_E_UNSUPPORTED).
+ *                    Weights: strategy._weights (set_weight), default 1 -- hs_lb_set_weights / hs_graph_set_lb_weights.  Here the
+ *                    Requests are ranked like ROUND_ROBIN's and the rank indexes the table (hs_lb_rr_assign);
+ *   IP_HASH          strategies.py:294-333: backends[int(md5(key).hexdigest(), 16) % len(backends)], key = str(client_id) -- the
+ *                    CONSISTENT_HASH path with another client -> backend table (a Request without a key takes the strategy's own
+ *                    RoundRobin, which only such Requests advance: general entity graphs run those);
+ *   The two strategies below select by live backend state; hs_lb_create refuses them by name, general entity graphs
+ *   (HS_NODE_LB of hs_graph_nodes) run them:
+ *   LEAST_CONNECTIONS  strategies.py:152-186: min(backends, key=active_requests), the first minimum in add_backend order;
+ *                    Server.active_requests is the requests IN SERVICE (FixedConcurrency._active), not the queue depth;
+ *   WEIGHTED_LEAST_CONNECTIONS  strategies.py:189-237: min(backends, key=active_requests / weight), a binary64 quotient; first minimum. */
+typedef enum hs_lb_strategy { HS_LB_CONSISTENT_HASH = 0, HS_LB_ROUND_ROBIN = 1, HS_LB_RANDOM = 2, HS_LB_WEIGHTED_ROUND_ROBIN = 3,
+                              HS_LB_IP_HASH = 4, HS_LB_LEAST_CONNECTIONS = 5, HS_LB_WEIGHTED_LEAST_CONNECTIONS = 6 } hs_lb_strategy;
 
 typedef struct hs_lb_sources {     /* [n_sources] each; NULL = documented default */
     const uint8_t *src_kind;           /* hs_source_kind (POISSON / CONSTANT); NULL = POISSON */
@@ -559,6 +574,10 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
  * last one is the state of one run to e_k -- which is what the reference's windows leave (one global event order, every call stops
  * behind the first event beyond its end): tests/test_gpu_lb.py::test_lb_windows_equal_one_run. */
 int hs_lb_run(hs_lb *h, int64_t end_ns);
+/* WeightedRoundRobin.set_weight (strategies.py:93-105) for every backend at once: weights[n_backends], before the first run; the
+ * default is all ones (RoundRobin's sequence).  HS_E_INVALID for a weight below 1, HS_E_UNSUPPORTED for a total weight above 2^24,
+ * HS_E_STATE after a run.  A strategy that reads no weights ignores them (as the reference ignores BackendInfo.weight). */
+int hs_lb_set_weights(hs_lb *h, const int32_t *weights);
 /* Which paths the last hs_lb_run took, as HS_LB_RUN_* bits (read-only, for tests). */
 #define HS_LB_RUN_F64_TIMES    (1 << 0)    /* Sources and the scan keep whole nanoseconds as binary64 */
 #define HS_LB_RUN_MARGIN       (1 << 1)    /* speculated whole-ns arrival steps (lb_step_encode; horizon < 2^40) */
@@ -605,6 +624,12 @@ const char *hs_lb_last_error(const hs_lb *h);
 void hs_lb_destroy(hs_lb *h);
 /* md5 digest of a byte string (the ring's hash function), exported so tests can check it against RFC 1321. */
 void hs_md5(const char *msg, int64_t len, uint8_t out[16]);
+/* WeightedRoundRobin.select (strategies.py:111-134) over backends 0 .. n-1 as ONE period of its selection sequence: out[k] = the
+ * backend of selection k for k < min(W, cap); returns the total weight W = the period.  Host only (no device).  HS_E_INVALID for a
+ * weight below 1 (`set_weight` raises ValueError, :103-104), HS_E_UNSUPPORTED for W > 2^24. */
+int64_t hs_lb_wrr_table(const int32_t *weights, int32_t n, int32_t *out, int64_t cap);
+/* IPHash.select for a key string (strategies.py:330-333): int(md5(key).hexdigest(), 16) % n_backends.  Host only. */
+int32_t hs_lb_ip_hash_select(const char *key, int32_t n_backends);
 
 /* Debug: bit 0 routes every timestamp group of every backend through the general in-group FIFO path; bit 1 disables the
  * request-order loop of single-worker unbounded backends (event-order loop with its single-event fast path instead);
@@ -756,8 +781,9 @@ typedef struct hs_graph_nodes {
      * ConsistentHash (strategies.py:336-433): lb_vnodes ring points md5("<backend name>:<i>") per backend (names / name_off), the key
      * of a Request is str(client_id); RoundRobin (strategies.py:50-73); Random (strategies.py:137-150) with random.choice plugged by
      * the Request's key draw: backends[client_id].  A Source with src_n_clients > 0 builds its Requests like a
-     * ClientKeyEventProvider (examples/visual/chash_example.py:69-88): client_id = int(u * n_clients), u from its KEY stream.  A
-     * Request WITHOUT a client_id (a scheduled one, one of a plain Source) at a ConsistentHash LoadBalancer takes the strategy's own
+     * ClientKeyEventProvider (examples/visual/chash_example.py:69-88): client_id = int(u * n_clients), u from its KEY stream.
+     * WeightedRoundRobin / IPHash / LeastConnections / WeightedLeastConnections: see hs_lb_strategy; weights: hs_graph_set_lb_weights.
+     * A Request WITHOUT a client_id (a scheduled one, one of a plain Source) at a ConsistentHash or IPHash LoadBalancer takes the strategy's own
      * fallback RoundRobin, which only such Requests advance (strategies.py:362,420-421); it must not reach a Random LoadBalancer
      * (the reference draws from the process-wide generator): the caller refuses such graphs; the device sends it to backend 0.  Every forwarded Request carries the `_lb_response` completion hook
      * (load_balancer.py:413-431): one more event behind the backend's enqueue.  NULL = no LoadBalancer. */
@@ -784,8 +810,9 @@ typedef struct hs_graph_stats {      /* host arrays [n_nodes] (rt_taken: [n_rt])
                                       * a LoadBalancer's slots: BackendInfo.total_requests       load_balancer.py:385-386 */
     int64_t *lb;                     /* [n][6] LoadBalancer: requests_received, requests_forwarded, requests_failed,
                                       * no_backend_available, len(_in_flight)                    load_balancer.py:349-388
-                                      * and the selections of the strategy's RoundRobin: RoundRobin._index, or the index of
-                                      * ConsistentHash's key-less fallback                         strategies.py:66-67,362 */
+                                      * and the selections of the strategy's RoundRobin: RoundRobin._index, the index of
+                                      * ConsistentHash's / IPHash's key-less fallback, or WeightedRoundRobin's selections
+                                      *                                                            strategies.py:66-67,309,362 */
 } hs_graph_stats;
 
 int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nodes, hs_graph **out);
@@ -794,6 +821,18 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nodes, hs_
  * its own time.  Calls in the order the caller constructed the Events.  `node`: a Server, Sink, link, router or
  * LoadBalancer. */
 int hs_graph_schedule(hs_graph *g, int32_t node, int64_t time_ns);
+/* WeightedRoundRobin.set_weight / WeightedLeastConnections.set_weight (strategies.py:93-105,203-207) for every backend of the
+ * LoadBalancer `node` at once: weights[n] in slot (add_backend) order, n = its backend count.  Before the first run; the default is
+ * all ones.  HS_E_INVALID for a weight below 1 or a node that is no LoadBalancer (a strategy that reads no weights ignores them, as
+ * the reference ignores BackendInfo.weight), HS_E_UNSUPPORTED for a WeightedRoundRobin total weight above 2^24, HS_E_STATE after a run. */
+int hs_graph_set_lb_weights(hs_graph *g, int32_t node, const int32_t *weights, int32_t n);
+/* How many LeastConnections / WeightedLeastConnections selections of the last run all 64 lanes of the wavefront took (min() over the
+ * backends, strategies.py:186,237, as a strided scan + cross-lane reduction) instead of the lone lane (read-only, for tests).
+ * Negative: an hs_status. */
+int64_t hs_graph_coop_selects(const hs_graph *g);
+/* Debug: bit 0 keeps every least-loaded selection on the lone lane, bit 1 hands every one to the wavefront (default: from
+ * 32 backends on -- csrc/hs_graph.hip kCoopMinBackends, an estimate until tools/lb_strategies_profile.py has been run).  Takes effect at the next run; both give bit-identical results (tests/test_gpu_lb_strategies.py). */
+int hs_debug_graph_flags(hs_graph *g, int flags);
 /* `_execute_until(end)`: pops while the PREVIOUS event's time <= end_ns (so exactly one event beyond the end is processed,
  * core/simulation.py:472); may be called again with a later end (windows, :527-541). */
 int hs_graph_run_until(hs_graph *g, int64_t end_ns);
