@@ -35,11 +35,16 @@ LB_WEIGHTED_ROUND_ROBIN, LB_IP_HASH, LB_LEAST_CONNECTIONS, LB_WEIGHTED_LEAST_CON
 GRAPH_DEBUG_LANE_SERIAL, GRAPH_DEBUG_COOPERATIVE = 1, 2     # hs_debug_graph_flags: where least-loaded selections run
 GRAPH_COOP_MIN_BACKENDS = 32                                # csrc/hs_graph.hip kCoopMinBackends (tests/test_lb_strategies_host.py compares)
 NODE_SOURCE, NODE_SERVER, NODE_SINK, NODE_LINK, NODE_ROUTER, NODE_PROBE, NODE_LB = 0, 1, 2, 3, 4, 5, 6
+NODE_RATE_LIMITER = 7
+# hs_limiter_policy / hs_limiter_outcome (the third column of a limiter's records)
+LIMITER_TOKEN_BUCKET, LIMITER_LEAKY_BUCKET, LIMITER_SLIDING_WINDOW, LIMITER_FIXED_WINDOW, LIMITER_NONE = 0, 1, 2, 3, 255
+LIMITER_FORWARDED, LIMITER_QUEUED, LIMITER_DROPPED, LIMITER_DRAINED = 0, 1, 2, 3
+LIMITER_MAX_SLIDING_LOG = 1 << 20                           # csrc/hs_graph.hip kMaxSlidingLog
 EV_KINDS = 15
 EV_NAMES = ("source", "enqueue", "notify", "poll", "deliver", "work", "continuation", "sink", "link", "link_cont",
             "route", "lb", "lb_resp", "probe_tick", "probe")
 PROBE_METRICS = {"depth": 0, "active_requests": 1, "stats_accepted": 2, "stats_dropped": 3, "requests_completed": 4,
-                 "_requests_completed": 4, "events_received": 5, "generated_count": 6}
+                 "_requests_completed": 4, "events_received": 5, "generated_count": 6, "queue_depth": 7}
 PROBE_NONE = 255
 # hs_engine_run_path / hs_lb_run_path: which side of the host-side gates the last run landed on (include/hs_engine.h)
 RUN_ONE_LANE, RUN_ONE_LANE_UNI, RUN_WIDE, RUN_WAVE, RUN_TANDEM, RUN_SINGLE_HEAP = 1, 2, 4, 8, 16, 32
@@ -144,6 +149,17 @@ class GraphNodes(C.Structure):
 
 GRAPH_STATS = ("generated", "payloads", "accepted", "dropped", "completed", "rejected", "total_service_s", "queue_depth", "active",
                "received", "entered", "packets_sent", "packets_dropped", "routed", "rt_taken", "lb")
+
+
+class LimiterPolicyParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("policy", C.c_int32), ("p0", C.c_double), ("p1", C.c_double), ("p2", C.c_double),
+                ("count", C.c_int64)]
+
+
+class LimiterState(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("policy", C.c_int32)] + [(n, C.c_int64) for n in (
+        "received", "forwarded", "queued", "dropped", "queue_depth", "poll_scheduled", "requests_handled", "polls_handled", "has_time",
+        "time_ns")] + [("tokens", C.c_double), ("count", C.c_int64)]
 
 
 class GraphStats(C.Structure):
@@ -460,6 +476,12 @@ def lib():
     L.hs_graph_schedule.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
     L.hs_graph_set_lb_weights.restype = C.c_int
     L.hs_graph_set_lb_weights.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+    L.hs_graph_set_limiter_policy.restype = C.c_int
+    L.hs_graph_set_limiter_policy.argtypes = [C.c_void_p, C.c_int32, P(LimiterPolicyParams)]
+    L.hs_graph_get_limiter.restype = C.c_int
+    L.hs_graph_get_limiter.argtypes = [C.c_void_p, C.c_int32, P(LimiterState), C.c_void_p, C.c_int64]
+    L.hs_debug_window_start.restype = C.c_int
+    L.hs_debug_window_start.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_graph_coop_selects.restype = C.c_int64
     L.hs_graph_coop_selects.argtypes = [C.c_void_p]
     L.hs_debug_graph_flags.restype = C.c_int
@@ -518,4 +540,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_create", "hs_graph_schedule", "hs_graph_run_until", "hs_graph_run_many", "hs_graph_run_parts", "hs_graph_get_summary", "hs_graph_get_stats", "hs_graph_read_records",
     "hs_graph_last_error", "hs_graph_destroy",
     "hs_graph_set_lb_weights", "hs_graph_coop_selects", "hs_debug_graph_flags", "hs_lb_set_weights", "hs_lb_wrr_table", "hs_lb_ip_hash_select",
+    "hs_graph_set_limiter_policy", "hs_graph_get_limiter", "hs_debug_window_start",
 )

@@ -79,6 +79,9 @@ struct GState {                                // 64 bytes
     // link:   a = entered, b = packets_sent, c = packets_dropped, d = jitter draws
     // router: a = stats_routed (= route draws);  Sink: a = events_received
     // Probe:  a = ticks taken from its table, c = samples
+    // limiter: a = received (= Requests handled), b = dropped, c = queued, d = polls handled; forwarded = a - b - qlen;
+    //          active = kLimPollScheduled | kLimHasTime; svc_draws = _last_refill_time / _last_leak_time / _current_window_start ns
+    //          (SlidingWindow: the ring's head); total_service = tokens (the windows: their count, as int64 bits)
     // LoadBalancer: a = requests_received, b = requests_forwarded, c = requests_failed (= no_backend_available), d = in flight,
     //               svc_draws = RoundRobin._index (ConsistentHash / IPHash: their fallback's, the key-less Requests; WeightedRoundRobin:
     //               its selections);  Source: svc_draws = KEY draws
@@ -99,6 +102,12 @@ struct GRequest {                              // 32 bytes: the payload Event's 
     uint32_t pre : 1;                          // `idx` came from the process-wide counter (GEvent::pad), set where the payload is queued
 };
 
+// RateLimitedEntity's two handlers: heap-entry kinds of this loop only, beyond the public fifteen (hs_summary.events_by_kind keeps its
+// meaning; they are counted per node: GState::a Requests, GState::d polls)
+constexpr uint32_t kEvLimRequest = HS_EV_KINDS, kEvLimPoll = HS_EV_KINDS + 1, kEvAllKinds = HS_EV_KINDS + 2;
+constexpr int kLimPollScheduled = 1, kLimHasTime = 2;   // GState::active of a limiter: _poll_scheduled; _last_*_time / _current_window_start is set
+constexpr long long kMaxSlidingLog = 1ll << 20;          // SlidingWindowPolicy.max_requests the ring is sized for
+
 enum : int { kRunning = 0, kDone = 1, kGrowHeap = 2, kGrowReq = 4, kGrowRec = 8, kBadKind = 16, kGrowTicks = 32, kUndecided = 64 };
 
 struct GVars {                                 // device scalars
@@ -116,6 +125,7 @@ struct GVars {                                 // device scalars
     long long sched_done;                      // scheduled entries already pushed
     long long heap_peak;
     long long coop_selects;                    // least-loaded selections all 64 lanes took (hs_graph_coop_selects)
+    long long polls_pending;                   // the limiters' poll Events in the heap
 };
 
 struct GCtl {                                  // kernel argument
@@ -132,6 +142,8 @@ struct GCtl {                                  // kernel argument
                                                // WeightedRoundRobin: one period of its selection sequence
     const int32_t *lb_w;                       // [n_rt] the weighted strategies' weight of every backend slot (strategy._weights; default 1)
     int coop_reset;                            // 1: the first launch of a run -- the lone lane zeroes GVars::coop_selects (the host clears it after the launch)
+    int64_t *lim_ring;                         // SlidingWindowPolicy._request_log of every such limiter: a ring at GParam::rt_off of GParam::rt_cnt entries
+    int auto_term;                             // 1: end_ns = 2^61 (end_time = Infinity) -- the run ends when only the limiters' daemon polls are pending
     int coop_min;                              // least-loaded selections over >= this many backends go to all 64 lanes; 0: never (no such
                                                // LoadBalancer in the graph, or the lane-serial scan is forced)
     GVars *V;
@@ -228,6 +240,7 @@ __device__ __forceinline__ uint32_t arrival_kind(const GParam *P, int node) {
         case HS_NODE_LINK: return HS_EV_LINK;
         case HS_NODE_ROUTER: return HS_EV_ROUTE;
         case HS_NODE_LB: return HS_EV_LB;
+        case HS_NODE_RATE_LIMITER: return kEvLimRequest;
         default: return 0xffffffffu;
     }
 }
@@ -274,11 +287,127 @@ __device__ __forceinline__ double lb_score(const GCtl &c, const GParam &p, int s
     return p.sub == HS_LB_WEIGHTED_LEAST_CONNECTIONS ? __ddiv_rn(act, (double)c.lb_w[p.rt_off + slot]) : act;
 }
 
+// ---- rate limiter policies (components/rate_limiter/policy.py), the reference's binary64 operations one by one --------------------
+// GParam of a limiter: sub = hs_limiter_policy, lim = FIFO capacity, conc = max_requests / requests_per_window,
+//   TokenBucket: lat_min = capacity, mean = refill_rate;  LeakyBucket: mean = leak_rate, lat_min = _leak_interval;
+//   SlidingWindow / FixedWindow: mean = the window in seconds; SlidingWindow: rt_off / rt_cnt = its ring in GCtl::lim_ring.
+
+// fmod(x, y) for finite x >= 0 and normal y > 0, exactly (the remainder of the two significands as integers, one binary digit of the
+// quotient per step): the C library's result, which CPython's float floor division starts from (Objects/floatobject.c float_divmod)
+__device__ inline double exact_fmod_pos(double x, double y) {
+    if (x < y) return x;
+    const uint64_t bx = (uint64_t)__double_as_longlong(x), by = (uint64_t)__double_as_longlong(y);
+    const int ex = (int)(bx >> 52), ey = (int)(by >> 52);                      // (x >= y > 0 normal: both biased exponents >= 1)
+    const uint64_t mx = (bx & 0xfffffffffffffull) | (1ull << 52), my = (by & 0xfffffffffffffull) | (1ull << 52);
+    uint64_t r = mx % my;
+    for (int i = ex - ey; i > 0; --i) { r <<= 1; if (r >= my) r -= my; }      // (r < my < 2^53: no overflow)
+    return ldexp((double)r, ey - 1075);                                       // r < my: at most y's own digits, exact
+}
+// Python's `v // w` on floats for v >= 0, w > 0 (float_floor_div: fmod, the exact quotient of the rest, floor with its half-way fix-up)
+__device__ inline double py_floordiv_pos(double v, double w) {
+    const double mod = exact_fmod_pos(v, w);
+    const double div = __ddiv_rn(__dsub_rn(v, mod), w);
+    if (div == 0.0) return 0.0;
+    double fl = floor(div);
+    if (__dsub_rn(div, fl) > 0.5) fl = __dadd_rn(fl, 1.0);
+    return fl;
+}
+__device__ __forceinline__ int64_t &lim_count(GState &s) { return *reinterpret_cast<int64_t *>(&s.total_service); }
+__device__ inline void lim_token_refill(const GParam &p, GState &s, int64_t now) {           // TokenBucketPolicy._refill
+    if (!(s.active & kLimHasTime)) { s.active |= kLimHasTime; s.svc_draws = (uint64_t)now; return; }
+    const double elapsed = seconds_from_ns(now - (int64_t)s.svc_draws);
+    if (elapsed <= 0.0) return;
+    const double x = __dadd_rn(s.total_service, __dmul_rn(elapsed, p.mean));
+    s.total_service = x < p.lat_min ? x : p.lat_min;                                          // min(capacity, x)
+    s.svc_draws = (uint64_t)now;
+}
+__device__ inline void lim_sliding_prune(const GCtl &c, const GParam &p, GState &s, int64_t now) {   // SlidingWindowPolicy._prune
+    const int64_t cutoff = now - ns_from_seconds(p.mean);
+    int64_t &cnt = lim_count(s);
+    while (cnt > 0 && c.lim_ring[p.rt_off + (int64_t)s.svc_draws] < cutoff) {
+        s.svc_draws = s.svc_draws + 1 == (uint64_t)p.rt_cnt ? 0 : s.svc_draws + 1;
+        cnt -= 1;
+    }
+}
+__device__ inline void lim_fixed_reset(const GParam &p, GState &s, int64_t now) {             // FixedWindowPolicy._maybe_reset
+    const int64_t ws = ns_from_seconds(__dmul_rn(py_floordiv_pos(seconds_from_ns(now), p.mean), p.mean));
+    if (!(s.active & kLimHasTime) || ws > (int64_t)s.svc_draws) { s.active |= kLimHasTime; s.svc_draws = (uint64_t)ws; lim_count(s) = 0; }
+}
+// FixedWindowPolicy._get_window_start, one input per thread (hs_debug_window_start)
+__global__ void hs_debug_window_start_kernel(int64_t n, const int64_t *now_ns, const double *w, double *out_div, int64_t *out_start) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double div = py_floordiv_pos(seconds_from_ns(now_ns[i]), w[i]);
+    out_div[i] = div;
+    out_start[i] = ns_from_seconds(__dmul_rn(div, w[i]));
+}
+__device__ inline bool lim_try_acquire(const GCtl &c, const GParam &p, GState &s, int64_t now) {
+    switch (p.sub) {
+    case HS_LIMITER_TOKEN_BUCKET:
+        lim_token_refill(p, s, now);
+        if (s.total_service >= 1.0) { s.total_service = __dsub_rn(s.total_service, 1.0); return true; }
+        return false;
+    case HS_LIMITER_LEAKY_BUCKET:
+        if (!(s.active & kLimHasTime)) { s.active |= kLimHasTime; s.svc_draws = (uint64_t)now; return true; }
+        if (seconds_from_ns(now - (int64_t)s.svc_draws) >= p.lat_min) { s.svc_draws = (uint64_t)now; return true; }
+        return false;
+    case HS_LIMITER_SLIDING_WINDOW: {
+        lim_sliding_prune(c, p, s, now);
+        int64_t &cnt = lim_count(s);
+        if (cnt < (int64_t)p.conc) {
+            int64_t at = (int64_t)s.svc_draws + cnt;
+            if (at >= p.rt_cnt) at -= p.rt_cnt;
+            c.lim_ring[p.rt_off + at] = now;
+            cnt += 1;
+            return true;
+        }
+        return false;
+    }
+    default: {
+        lim_fixed_reset(p, s, now);
+        int64_t &cnt = lim_count(s);
+        if (cnt < (int64_t)p.conc) { cnt += 1; return true; }
+        return false;
+    }
+    }
+}
+// policy.time_until_available(now) in nanoseconds, with the three `wait == Duration.ZERO -> Duration(1)` guards (and LeakyBucket's)
+__device__ inline int64_t lim_wait_ns(const GCtl &c, const GParam &p, GState &s, int64_t now) {
+    int64_t wait;
+    switch (p.sub) {
+    case HS_LIMITER_TOKEN_BUCKET:
+        lim_token_refill(p, s, now);
+        if (s.total_service >= 1.0) return 0;
+        wait = ns_from_seconds(__ddiv_rn(__dsub_rn(1.0, s.total_service), p.mean));
+        break;
+    case HS_LIMITER_LEAKY_BUCKET: {
+        if (!(s.active & kLimHasTime)) return 0;
+        const double remaining = __dsub_rn(p.lat_min, seconds_from_ns(now - (int64_t)s.svc_draws));
+        if (remaining <= 0.0) return 0;
+        wait = ns_from_seconds(remaining);
+    } break;
+    case HS_LIMITER_SLIDING_WINDOW: {
+        lim_sliding_prune(c, p, s, now);
+        if (lim_count(s) < (int64_t)p.conc) return 0;
+        const int64_t expires = c.lim_ring[p.rt_off + (int64_t)s.svc_draws] + ns_from_seconds(p.mean);
+        wait = ns_from_seconds(seconds_from_ns(expires - now));
+    } break;
+    default: {
+        lim_fixed_reset(p, s, now);
+        if (lim_count(s) < (int64_t)p.conc) return 0;
+        const double remaining = seconds_from_ns((int64_t)s.svc_draws + ns_from_seconds(p.mean) - now);
+        if (remaining <= 0.0) return 0;
+        wait = ns_from_seconds(remaining);
+    } break;
+    }
+    return wait == 0 ? 1 : wait;
+}
+
 // NL: graphs of up to NL nodes keep their nodes' parameters and state in LDS for the launch (the loop's dependent chain goes
 // through them several times per event: 64-cycle LDS round trips instead of L2's) -- `lnodes`: NL x (GParam + GState).
 template <int W, int NL>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
-    __shared__ unsigned long long s_by_kind[HS_EV_KINDS];
+    __shared__ unsigned long long s_by_kind[kEvAllKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
     GCtl c = c0;
     GVars &V = *c.V;
@@ -293,7 +422,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         c.P = reinterpret_cast<const GParam *>(lnodes);
         c.S = reinterpret_cast<GState *>(lnodes + (size_t)NL * sizeof(GParam));
     }
-    if (lane < HS_EV_KINDS) s_by_kind[lane] = 0ull;
+    if (lane < (int)kEvAllKinds) s_by_kind[lane] = 0ull;
     {   // the heap's head comes into LDS (all 64 lanes copy; 8 bytes per lane and step)
         const long long n8 = (V.heap_len < W ? V.heap_len : (long long)W) * (long long)(sizeof(GEvent) / 8);
         const uint64_t *src = reinterpret_cast<const uint64_t *>(c.heap);
@@ -309,6 +438,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
     int sel = -1, sel_node = -1;               // a selection the wavefront made for the LoadBalancer event on top of the heap
     long long cur = V.cur, processed = 0, n_completed = 0, n_received = 0, rec_n = V.rec_n, n_coop = 0;
     long long peak = V.heap_peak;
+    long long polls_pending = V.polls_pending;   // daemon polls in the heap: they do not keep an auto-terminating run alive
     if (lane == 0) {
         if (!V.booted) {
             // Simulation.__init__ (core/simulation.py:145-154) + Source.start (load/source.py:120-140): the Sources in list order,
@@ -353,7 +483,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         while (status == kRunning) {
             // core/simulation.py:472 tests the PREVIOUS event's time; a PART of a Simulation stops in front of the first event beyond
             // the end (which of the parts' first events the reference still processes is decided across all of them)
-            if (!(H.len > 0 && (c.part ? H.get(0).t <= c.end_ns : cur <= c.end_ns))) { status = kDone; break; }
+            if (!(H.len > (c.auto_term ? polls_pending : 0) && (c.part ? H.get(0).t <= c.end_ns : cur <= c.end_ns))) { status = kDone; break; }
             if (processed >= c.budget) break;
             // room for whatever this event constructs (at most two pushes, one Request, one record)
             if (H.len + 2 > c.heap_cap) { status |= kGrowHeap; break; }
@@ -393,7 +523,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             processed++;
             const int n = e.node;
             const int64_t t = e.t;
-            if (e.kind >= (uint32_t)HS_EV_KINDS) { status |= kBadKind; break; }
+            if (e.kind >= kEvAllKinds) { status |= kBadKind; break; }
             s_by_kind[e.kind] += 1ull;
             const GParam p = c.P[n];
             GState &s = c.S[n];
@@ -593,11 +723,63 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     case HS_PROBE_COMPLETED: v = tg.c; break;
                     case HS_PROBE_RECEIVED: v = tg.a; break;                        // Sink.events_received
                     case HS_PROBE_GENERATED: v = tg.c; break;                       // Source.generated_count
+                    case HS_PROBE_LIMITER_DEPTH: v = tg.qlen; break;                // RateLimitedEntity.queue_depth
                     default: break;
                 }
                 c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = v;
                 rec_n++;
                 s.c += 1;
+            } break;
+            case kEvLimRequest: {
+                // RateLimitedEntity._handle_request (rate_limited_entity.py:114-142): count, try_acquire, forward or queue or drop
+                s.a += 1;
+                int64_t outcome;
+                if (lim_try_acquire(c, p, s, t)) {
+                    // _forward (:164-178): a NEW Event for the downstream at `now` with a copy of the context, no completion hook
+                    outcome = HS_LIMITER_FORWARDED;
+                    H.push(mk(t, G++, arrival_kind(c.P, p.target), p.target, e.req));
+                } else if (!(p.lim >= 0 && s.qlen >= p.lim)) {                     // FIFOQueue.push (queue_policy.py:94-98)
+                    outcome = HS_LIMITER_QUEUED;
+                    c.reqs[e.req].next = -1;
+                    if (s.qtail >= 0) c.reqs[s.qtail].next = e.req; else s.qhead = e.req;
+                    s.qtail = e.req;
+                    s.qlen += 1;
+                    s.c += 1;
+                    if (!(s.active & kLimPollScheduled)) {                          // _ensure_poll_scheduled (:180-193): ONE daemon Event
+                        s.active |= kLimPollScheduled;
+                        H.push(mk(t + lim_wait_ns(c, p, s, t), G++, kEvLimPoll, n, -1));
+                        polls_pending += 1;
+                    }
+                } else {
+                    outcome = HS_LIMITER_DROPPED;
+                    s.b += 1;
+                    c.reqs[e.req].next = req_free; req_free = e.req;
+                }
+                c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = outcome;
+                rec_n++;
+            } break;
+            case kEvLimPoll: {
+                // RateLimitedEntity._handle_poll (:144-162)
+                s.d += 1;
+                s.active &= ~kLimPollScheduled;
+                polls_pending -= 1;
+                if (s.qlen == 0) break;
+                bool again = true;
+                if (lim_try_acquire(c, p, s, t)) {
+                    const int r = s.qhead;
+                    s.qhead = c.reqs[r].next;
+                    if (s.qhead < 0) s.qtail = -1;
+                    s.qlen -= 1;
+                    c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = HS_LIMITER_DRAINED;
+                    rec_n++;
+                    H.push(mk(t, G++, arrival_kind(c.P, p.target), p.target, r));
+                    again = s.qlen > 0;
+                }
+                if (again) {
+                    s.active |= kLimPollScheduled;
+                    H.push(mk(t + lim_wait_ns(c, p, s, t), G++, kEvLimPoll, n, -1));
+                    polls_pending += 1;
+                }
             } break;
             default: status |= kBadKind; break;
             }
@@ -632,7 +814,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         for (int k = 0; k < HS_EV_KINDS; ++k) V.by_kind[k] += (long long)s_by_kind[k];
         V.req_free = req_free; V.req_len = req_len;
         V.completed += n_completed; V.received += n_received;
-        V.heap_peak = peak;
+        V.heap_peak = peak; V.polls_pending = polls_pending;
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
@@ -690,6 +872,11 @@ struct hs_graph {
     int32_t *d_key_table = nullptr;
     std::vector<int32_t> key_table;            // host image of d_key_table (hs_graph_set_lb_weights appends a WeightedRoundRobin's new table)
     std::vector<int32_t> lb_w;                 // [n_rt] host image of ctl.lb_w
+    std::vector<hs_limiter_policy_params> lim_policy;   // per node (policy = HS_LIMITER_NONE until hs_graph_set_limiter_policy)
+    int n_limiters = 0;
+    long long lim_ring_len = 0;                // entries of ctl.lim_ring handed out so far
+    std::vector<GState> state_cache; bool state_cache_valid = false;   // hs_graph_get_limiter: one copy of the nodes' state per run
+    std::vector<int64_t> ring_cache;           // ... and of ctl.lim_ring
     bool has_least_loaded = false;             // a LeastConnections / WeightedLeastConnections LoadBalancer among the nodes
     int debug_flags = 0;                       // hs_debug_graph_flags
     // tick tables: one row per time-varying Source and per distinct Probe interval, computed up to `tick_horizon`
@@ -772,7 +959,7 @@ void hs_graph_destroy(hs_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *bufs[] = {g->ctl.heap, g->ctl.reqs, g->ctl.rec_node, g->ctl.rec_t, g->ctl.rec_cr, (void *)g->ctl.P, g->ctl.S,
                     g->d_rt_targets, g->d_key_table, (void *)g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
-                    g->d_tick_status};
+                    g->d_tick_status, g->ctl.lim_ring};
     for (void *b : bufs) if (b && !in_slab(g, b)) (void)hipFree(b);
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
     if (g->ev_a) (void)hipEventDestroy(g->ev_a);
@@ -795,7 +982,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     if (cfg->device < 0 || cfg->device >= dev_count) return fail(nullptr, HS_E_INVALID, "device %d out of range", cfg->device);
     if (cfg->start_ns < 0)        // (the Sinks' merged records hold non-negative times)
         return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
-    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB; };
+    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER; };
     int64_t kmax = 0;                                  // client ids any Source hands out: [0, kmax)
     for (int i = 0; i < n; ++i)
         if (nd->kind[i] == HS_NODE_SOURCE && nd->src_n_clients && nd->src_n_clients[i] > kmax) kmax = nd->src_n_clients[i];
@@ -863,7 +1050,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a Probe needs a target", i);
             const int tk = nd->kind[p.target];
             const bool ok = p.sub == HS_PROBE_GENERATED ? tk == HS_NODE_SOURCE : p.sub == HS_PROBE_RECEIVED ? tk == HS_NODE_SINK
-                            : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
+                            : p.sub == HS_PROBE_LIMITER_DEPTH ? tk == HS_NODE_RATE_LIMITER : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
             if (!ok) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: metric %d is not an attribute of its target (node kind %d)", i, (int)p.sub, tk);
             const double rate = 1.0 / iv;                           // _ProbeProfile.rate (probe.py:31)
             int found = -1;
@@ -956,6 +1143,11 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             }
             if (p.sub >= HS_LB_LEAST_CONNECTIONS) has_ll = true;
         } break;
+        case HS_NODE_RATE_LIMITER: {
+            if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a RateLimitedEntity needs a downstream", i);
+            p.lim = nd->queue_cap ? nd->queue_cap[i] : 1000;                        // rate_limited_entity.py:60
+            p.sub = (uint8_t)HS_LIMITER_NONE; p.conc = 0; p.rt_off = 0; p.rt_cnt = 0;
+        } break;
         default: return fail(nullptr, HS_E_UNSUPPORTED, "node %d: kind %d is not lowered", i, (int)p.kind);
         }
         P[(size_t)i] = p;
@@ -964,6 +1156,12 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     g->cfg = *cfg; g->n = n; g->n_rt = nd->n_rt; g->params = P; g->rows = rows; g->row_rate = row_rate;
     g->key_table = key_table; g->has_least_loaded = has_ll;
     g->lb_w.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
+    {
+        hs_limiter_policy_params none{};
+        none.struct_size = sizeof none; none.policy = HS_LIMITER_NONE;
+        g->lim_policy.assign((size_t)n, none);
+        for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_RATE_LIMITER) g->n_limiters++;
+    }
     for (int i = 0; i < n; ++i) {
         const GParam &p = P[(size_t)i];
         const double draw = p.sub == HS_LAT_EXPONENTIAL ? hs::kLongestExpDraw * p.mean : p.mean;       // (-log(2^-53) = 36.7 means at most)
@@ -1073,6 +1271,126 @@ int hs_graph_set_lb_weights(hs_graph *g, int32_t node, const int32_t *weights, i
     return HS_OK;
 }
 
+int hs_graph_set_limiter_policy(hs_graph *g, int32_t node, const hs_limiter_policy_params *q) {
+    if (!g || !q) return fail(g, HS_E_INVALID, "null argument");
+    if (q->struct_size != sizeof(hs_limiter_policy_params)) return fail(g, HS_E_INVALID, "hs_limiter_policy_params.struct_size mismatch (ABI)");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_RATE_LIMITER)
+        return fail(g, HS_E_INVALID, "set_limiter_policy: node %d is not a RateLimitedEntity", node);
+    if (g->ran || g->launches > 0) return fail(g, HS_E_STATE, "set_limiter_policy: the policy is set before the first run");
+    if (g->lim_policy[(size_t)node].policy != HS_LIMITER_NONE) return fail(g, HS_E_STATE, "set_limiter_policy: node %d has its policy already", node);
+    GParam p = g->params[(size_t)node];                    // (a copy: a refused policy leaves the node as it was)
+    GState s0{};
+    s0.qhead = -1; s0.qtail = -1;
+    auto finite = [](double v) { return std::isfinite(v); };
+    double reach = 0.0;
+    switch (q->policy) {
+    case HS_LIMITER_TOKEN_BUCKET:
+        if (!finite(q->p0) || !finite(q->p1) || !finite(q->p2)) return fail(g, HS_E_INVALID, "TokenBucketPolicy: parameters must be finite");
+        if (!(q->p1 > 0.0)) return fail(g, HS_E_INVALID, "TokenBucketPolicy: refill_rate must be > 0, got %g (the reference divides by it)", q->p1);
+        p.lat_min = q->p0; p.mean = q->p1; s0.total_service = q->p2;
+        reach = (1.0 + (q->p2 < 0.0 ? -q->p2 : 0.0)) / q->p1;
+        break;
+    case HS_LIMITER_LEAKY_BUCKET:
+        if (!finite(q->p0) || !(q->p0 > 0.0)) return fail(g, HS_E_INVALID, "LeakyBucketPolicy: leak_rate must be > 0, got %g", q->p0);
+        if (!finite(q->p1) || !(q->p1 > 0.0)) return fail(g, HS_E_INVALID, "LeakyBucketPolicy: bad leak interval %g", q->p1);
+        p.mean = q->p0; p.lat_min = q->p1;
+        reach = q->p1;
+        break;
+    case HS_LIMITER_SLIDING_WINDOW:
+    case HS_LIMITER_FIXED_WINDOW: {
+        const char *nm = q->policy == HS_LIMITER_SLIDING_WINDOW ? "SlidingWindowPolicy" : "FixedWindowPolicy";
+        if (!finite(q->p0) || !(q->p0 >= 1e-9)) return fail(g, HS_E_INVALID, "%s: a window of %g s is below one nanosecond", nm, q->p0);
+        if (q->count < 1) return fail(g, HS_E_INVALID, "%s: at least one request per window, got %lld", nm, (long long)q->count);
+        if (q->policy == HS_LIMITER_SLIDING_WINDOW && q->count > kMaxSlidingLog)
+            return fail(g, HS_E_UNSUPPORTED, "SlidingWindowPolicy: max_requests = %lld needs a log beyond 2^20 entries", (long long)q->count);
+        if (q->count > INT32_MAX) return fail(g, HS_E_UNSUPPORTED, "%s: %lld requests per window is beyond 2^31", nm, (long long)q->count);
+        p.mean = q->p0; p.conc = (int32_t)q->count;
+        reach = q->p0;
+        if (q->policy == HS_LIMITER_SLIDING_WINDOW) {
+            if (g->lim_ring_len + q->count > (1ll << 30)) return fail(g, HS_E_UNSUPPORTED, "the SlidingWindowPolicy logs of this graph exceed 2^30 entries");
+            p.rt_off = (int32_t)g->lim_ring_len; p.rt_cnt = (int32_t)q->count;                // (the ring itself: prepare_run, once)
+        }
+    } break;
+    default: return fail(g, HS_E_UNSUPPORTED, "rate limiter policy %d is not lowered", (int)q->policy);
+    }
+    p.sub = (uint8_t)q->policy;
+    g->reach_s = std::max(g->reach_s, reach);
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    HS_HIP(g, hipMemcpy(g->ctl.S + node, &s0, sizeof s0, hipMemcpyHostToDevice));
+    g->params[(size_t)node] = p;
+    if (q->policy == HS_LIMITER_SLIDING_WINDOW) g->lim_ring_len += q->count;
+    g->lim_policy[(size_t)node] = *q;
+    return HS_OK;
+}
+
+int hs_debug_window_start(int32_t device, int64_t n, const int64_t *now_ns, const double *window_s, double *out_div, int64_t *out_start_ns) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, HS_E_NO_DEVICE, "no HIP device visible: the engine has no CPU fallback");
+    if (n <= 0 || !now_ns || !window_s || !out_div || !out_start_ns) return fail(nullptr, HS_E_INVALID, "hs_debug_window_start: bad arguments");
+    if (device < 0 || device >= ndev) return fail(nullptr, HS_E_INVALID, "device ordinal %d out of range (%d devices)", device, ndev);
+    for (int64_t i = 0; i < n; ++i)
+        if (now_ns[i] < 0 || !(window_s[i] >= 2.2250738585072014e-308) || !std::isfinite(window_s[i]))
+            return fail(nullptr, HS_E_INVALID, "hs_debug_window_start: entry %lld is outside now >= 0, window normal and > 0", (long long)i);
+    HS_HIP(nullptr, hipSetDevice(device));
+    void *d[4] = {nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes = (size_t)n * 8;
+    for (int k = 0; k < 4; ++k) {
+        const hipError_t e = hipMalloc(&d[k], bytes);
+        if (e != hipSuccess) { for (auto &p : d) if (p) hipFree(p); return fail(nullptr, HS_E_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
+    }
+    hipError_t e = hipMemcpy(d[0], now_ns, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d[1], window_s, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(hs_debug_window_start_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, (const int64_t *)d[0],
+                           (const double *)d[1], (double *)d[2], (int64_t *)d[3]);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out_div, d[2], bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_start_ns, d[3], bytes, hipMemcpyDeviceToHost);
+    for (auto &p : d) hipFree(p);
+    if (e != hipSuccess) return fail(nullptr, HS_E_HIP, "hs_debug_window_start: %s", hipGetErrorString(e));
+    return HS_OK;
+}
+
+int hs_graph_get_limiter(hs_graph *g, int32_t node, hs_limiter_state *out, int64_t *log, int64_t log_cap) {
+    if (!g || !out) return fail(g, HS_E_INVALID, "null argument");
+    if (out->struct_size != sizeof(hs_limiter_state)) return fail(g, HS_E_INVALID, "hs_limiter_state.struct_size mismatch (ABI)");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_RATE_LIMITER)
+        return fail(g, HS_E_INVALID, "get_limiter: node %d is not a RateLimitedEntity", node);
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (!g->state_cache_valid) {
+        g->state_cache.resize((size_t)g->n);
+        HS_HIP(g, hipMemcpy(g->state_cache.data(), g->ctl.S, (size_t)g->n * sizeof(GState), hipMemcpyDeviceToHost));
+        g->ring_cache.resize((size_t)g->lim_ring_len);    // ... and every sliding-window log with it: one copy per run, not one per limiter
+        if (g->lim_ring_len > 0 && g->ctl.lim_ring)
+            HS_HIP(g, hipMemcpy(g->ring_cache.data(), g->ctl.lim_ring, (size_t)g->lim_ring_len * sizeof(int64_t), hipMemcpyDeviceToHost));
+        g->state_cache_valid = true;
+    }
+    const GState &s = g->state_cache[(size_t)node];
+    const GParam &p = g->params[(size_t)node];
+    int64_t bits;
+    std::memcpy(&bits, &s.total_service, sizeof bits);
+    const bool window = p.sub == HS_LIMITER_SLIDING_WINDOW || p.sub == HS_LIMITER_FIXED_WINDOW;
+    out->policy = p.sub;
+    out->received = s.a; out->dropped = s.b; out->queued = s.c; out->forwarded = s.a - s.b - s.qlen;
+    out->queue_depth = s.qlen;
+    out->poll_scheduled = (s.active & kLimPollScheduled) ? 1 : 0;
+    out->requests_handled = s.a; out->polls_handled = s.d;
+    out->has_time = p.sub != HS_LIMITER_SLIDING_WINDOW && (s.active & kLimHasTime) ? 1 : 0;
+    out->time_ns = out->has_time ? (int64_t)s.svc_draws : 0;
+    out->tokens = p.sub == HS_LIMITER_TOKEN_BUCKET ? s.total_service : 0.0;
+    out->count = window ? bits : 0;
+    if (p.sub == HS_LIMITER_SLIDING_WINDOW && log && log_cap > 0 && bits > 0) {
+        const int64_t m = std::min<int64_t>(bits, log_cap), head = (int64_t)s.svc_draws, first = std::min<int64_t>(m, p.rt_cnt - head);
+        const int64_t *ring = g->ring_cache.data() + p.rt_off;
+        std::copy(ring + head, ring + head + first, log);
+        if (m > first) std::copy(ring, ring + (m - first), log + first);
+    }
+    return HS_OK;
+}
+
 int hs_debug_graph_flags(hs_graph *g, int flags) {
     if (!g) return fail(g, HS_E_INVALID, "null handle");
     g->debug_flags = flags;
@@ -1163,9 +1481,18 @@ static int build_tables(hs_graph *g, int64_t horizon) {
 // What a run needs before its first launch: tick tables up to the end, the schedule()d entries on the device.
 static int prepare_run(hs_graph *g, int64_t end_ns) {
     GCtl &c = g->ctl;
+    g->state_cache_valid = false;
+    if (g->n_limiters > 0)
+        for (int i = 0; i < g->n; ++i)
+            if (g->params[(size_t)i].kind == HS_NODE_RATE_LIMITER && g->lim_policy[(size_t)i].policy == HS_LIMITER_NONE)
+                return fail(g, HS_E_STATE, "node %d: a RateLimitedEntity without a policy (hs_graph_set_limiter_policy comes before the run)", i);
+    if (g->lim_ring_len > 0 && !c.lim_ring) {              // the SlidingWindowPolicy logs of all such limiters, sized once (every policy is set)
+        HS_HIP(g, hipSetDevice(g->cfg.device));
+        HS_HIP(g, hipMalloc(&c.lim_ring, (size_t)g->lim_ring_len * sizeof(int64_t)));
+    }
     if (!hs::reach_fits_int64(end_ns, g->reach_s))
         return fail(g, HS_E_UNSUPPORTED, "the end (%lld ns) plus one longest step (%.6g s: 36.8 / the smallest rate, 36.8 x the largest "
-                     "exponential mean, a constant service, a link's delay or a probe interval) leaves int64 nanoseconds -- refused, "
+                     "exponential mean, a constant service, a link's delay, a probe interval or a rate limiter's longest wait) leaves int64 nanoseconds -- refused, "
                      "never wrapped", (long long)end_ns, g->reach_s);
     // table-driven streams: up to this end when it is a real horizon, else (an auto-terminating run) a minute at a time
     int64_t table_h = end_ns;
@@ -1190,6 +1517,7 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
     }
     c.sched_node = g->d_sched_node; c.sched_t = g->d_sched_t; c.n_sched = ns;
     c.end_ns = end_ns;
+    c.auto_term = end_ns == (1ll << 61);                   // end_time = Infinity: the limiters' polls are daemons (core/simulation.py:306-322)
     c.coop_min = !g->has_least_loaded || (g->debug_flags & 1) ? 0 : (g->debug_flags & 2) ? 1 : kCoopMinBackends;
     c.coop_reset = 1;                                      // (hs_graph_coop_selects counts the LAST run: zeroed by its first launch)
     g->launches = 0;
@@ -1210,8 +1538,15 @@ static int after_launch_with(hs_graph *g, int status, long long processed, bool 
     struct { int status; long long processed; } v{status, processed};
     if (v.status & kBadKind) return fail(g, HS_E_INVALID, "an event of unknown kind reached the loop (internal error)");
     if (g->cfg.max_events > 0 && v.processed > g->cfg.max_events)
+    {
+        bool fixed_window = false;                         // (the reference's own livelock, README "Admission control": name it)
+        for (const auto &q : g->lim_policy) fixed_window |= q.policy == HS_LIMITER_FIXED_WINDOW;
         return fail(g, HS_E_UNSUPPORTED, "the run exceeds max_events = %lld events on the single-heap path (one lane, ~2.4 us per event); "
-                     "raise max_events, or bring the graph into the shape the station engines take", (long long)g->cfg.max_events);
+                     "raise max_events, or bring the graph into the shape the station engines take%s", (long long)g->cfg.max_events,
+                     fixed_window ? "; likely cause in this graph: a FixedWindowPolicy whose window_size is no exact binary fraction of a "
+                                    "second (0.1, 0.3, 1/3 ...) can reschedule its poll for the same nanosecond for ever, as the "
+                                    "reference does -- use a window such as 0.125, 0.25 or 0.5" : "");
+    }
     if (v.status & kGrowHeap) {
         const long long nc = c.heap_cap * 2;
         int rc = grow(g, &c.heap, c.heap_cap, nc); if (rc) return rc;

@@ -928,6 +928,230 @@ class LoadBalancer(Entity):
                                  self._no_backend_available, 0, 0)
 
 
+# ---- rate limiting -------------------------------------------------------------------------------
+# components/rate_limiter/policy.py and rate_limited_entity.py.  Inside a Simulation the policies run on the device
+# (csrc/hs_graph.hip lim_try_acquire / lim_wait_ns); `try_acquire` / `time_until_available` here are the same arithmetic in host
+# Python -- binary64, `Instant - Instant` exact, `Instant +- float` truncating float * 1e9 -- so the classes work on their own, and
+# the two implementations check each other against the recorded reference (tests/test_rate_limiter_host.py).
+class TokenBucketPolicy:
+    """Token bucket (policy.py:65-127): `refill_rate` tokens per second up to `capacity`, one token per request."""
+
+    def __init__(self, capacity: float = 10.0, refill_rate: float = 1.0, initial_tokens: float | None = None):
+        self._capacity = float(capacity)
+        self._refill_rate = float(refill_rate)
+        self._tokens = self._capacity if initial_tokens is None else float(initial_tokens)
+        self._last_refill_time: Instant | None = None
+
+    capacity = property(lambda self: self._capacity)
+    refill_rate = property(lambda self: self._refill_rate)
+    tokens = property(lambda self: self._tokens)
+
+    def _refill(self, now: Instant) -> None:
+        last = self._last_refill_time
+        if last is None:                      # the first call only starts the clock
+            self._last_refill_time = now
+            return
+        elapsed = (now - last).to_seconds()
+        if elapsed > 0:
+            self._tokens = min(self._capacity, self._tokens + elapsed * self._refill_rate)
+            self._last_refill_time = now
+
+    def try_acquire(self, now: Instant) -> bool:
+        self._refill(now)
+        if self._tokens >= 1.0:
+            self._tokens -= 1.0
+            return True
+        return False
+
+    def time_until_available(self, now: Instant) -> Duration:
+        self._refill(now)
+        if self._tokens >= 1.0:
+            return Duration.ZERO
+        wait = Duration.from_seconds((1.0 - self._tokens) / self._refill_rate)
+        return Duration(1) if wait == Duration.ZERO else wait       # progress guard (policy.py:124-126)
+
+    def _engine_params(self):
+        return N_LIMITER["token"], self._capacity, self._refill_rate, self._tokens, 0
+
+    def _pristine(self) -> bool:
+        return self._last_refill_time is None
+
+
+class LeakyBucketPolicy:
+    """Leaky bucket (policy.py:130-170): one request per 1 / leak_rate seconds, no bursts."""
+
+    def __init__(self, leak_rate: float = 1.0):
+        self._leak_rate = float(leak_rate)
+        self._leak_interval = 1.0 / leak_rate if leak_rate > 0 else float("inf")
+        self._last_leak_time: Instant | None = None
+
+    leak_rate = property(lambda self: self._leak_rate)
+
+    def try_acquire(self, now: Instant) -> bool:
+        last = self._last_leak_time
+        if last is None or (now - last).to_seconds() >= self._leak_interval:
+            self._last_leak_time = now
+            return True
+        return False
+
+    def time_until_available(self, now: Instant) -> Duration:
+        last = self._last_leak_time
+        if last is None:
+            return Duration.ZERO
+        remaining = self._leak_interval - (now - last).to_seconds()
+        if remaining <= 0:
+            return Duration.ZERO
+        wait = Duration.from_seconds(remaining)
+        return Duration(1) if wait == Duration.ZERO else wait       # policy.py:167-169
+
+    def _engine_params(self):
+        return N_LIMITER["leaky"], self._leak_rate, self._leak_interval, 0.0, 0
+
+    def _pristine(self) -> bool:
+        return self._last_leak_time is None
+
+
+class SlidingWindowPolicy:
+    """Sliding window log (policy.py:173-222): at most `max_requests` grants inside any window of `window_size_seconds`."""
+
+    def __init__(self, window_size_seconds: float = 1.0, max_requests: int = 10):
+        self._window_size = float(window_size_seconds)
+        self._max_requests = int(max_requests)
+        self._request_log: list[Instant] = []
+
+    window_size_seconds = property(lambda self: self._window_size)
+    max_requests = property(lambda self: self._max_requests)
+
+    def _prune(self, now: Instant) -> None:
+        cutoff = now - self._window_size
+        log = self._request_log
+        k = 0
+        while k < len(log) and log[k] < cutoff:
+            k += 1
+        if k:
+            del log[:k]
+
+    def try_acquire(self, now: Instant) -> bool:
+        self._prune(now)
+        if len(self._request_log) < self._max_requests:
+            self._request_log.append(now)
+            return True
+        return False
+
+    def time_until_available(self, now: Instant) -> Duration:
+        self._prune(now)
+        if len(self._request_log) < self._max_requests:
+            return Duration.ZERO
+        expires_at = self._request_log[0] + self._window_size      # the oldest grant leaves the window then
+        wait = Duration.from_seconds((expires_at - now).to_seconds())
+        return Duration(1) if wait == Duration.ZERO else wait       # policy.py:219-221
+
+    def _engine_params(self):
+        return N_LIMITER["sliding"], self._window_size, 0.0, 0.0, self._max_requests
+
+    def _pristine(self) -> bool:
+        return not self._request_log
+
+
+class FixedWindowPolicy:
+    """Fixed window counter (policy.py:225-289): `requests_per_window` grants per window; windows start at multiples of
+    `window_size`, computed as `(now_s // window_size) * window_size` in floats."""
+
+    def __init__(self, requests_per_window: int, window_size: float = 1.0):
+        if requests_per_window < 1:
+            raise ValueError(f"requests_per_window must be >= 1, got {requests_per_window}")
+        if window_size <= 0:
+            raise ValueError(f"window_size must be > 0, got {window_size}")
+        self._requests_per_window = requests_per_window
+        self._window_size = window_size
+        self._current_window_start: Instant | None = None
+        self._current_window_count: int = 0
+
+    requests_per_window = property(lambda self: self._requests_per_window)
+    window_size = property(lambda self: self._window_size)
+
+    def _get_window_start(self, now: Instant) -> Instant:
+        return Instant.from_seconds((now.to_seconds() // self._window_size) * self._window_size)
+
+    def _maybe_reset(self, now: Instant) -> None:
+        start = self._get_window_start(now)
+        if self._current_window_start is None or start > self._current_window_start:
+            self._current_window_start = start
+            self._current_window_count = 0
+
+    def try_acquire(self, now: Instant) -> bool:
+        self._maybe_reset(now)
+        if self._current_window_count < self._requests_per_window:
+            self._current_window_count += 1
+            return True
+        return False
+
+    def time_until_available(self, now: Instant) -> Duration:
+        self._maybe_reset(now)
+        if self._current_window_count < self._requests_per_window:
+            return Duration.ZERO
+        remaining = ((self._current_window_start + self._window_size) - now).to_seconds()
+        if remaining <= 0:
+            return Duration.ZERO
+        wait = Duration.from_seconds(remaining)
+        return Duration(1) if wait == Duration.ZERO else wait       # policy.py:286-288
+
+    def _engine_params(self):
+        return N_LIMITER["fixed"], float(self._window_size), 0.0, 0.0, int(self._requests_per_window)
+
+    def _pristine(self) -> bool:
+        return self._current_window_start is None and self._current_window_count == 0
+
+
+N_LIMITER = {"token": 0, "leaky": 1, "sliding": 2, "fixed": 3}      # hs_limiter_policy (include/hs_engine.h)
+LIMITER_POLICIES = (TokenBucketPolicy, LeakyBucketPolicy, SlidingWindowPolicy, FixedWindowPolicy)
+
+
+@dataclass(frozen=True)
+class RateLimitedEntityStats:
+    received: int = 0
+    forwarded: int = 0
+    queued: int = 0
+    dropped: int = 0
+
+
+class RateLimitedEntity(Entity):
+    """Admission control in front of `downstream` (rate_limited_entity.py:40-193): a Request the policy grants is forwarded at once,
+    one it denies waits in a FIFO of `queue_capacity` places that a self-scheduled daemon poll drains at the moment the policy
+    reports capacity; only a full queue drops.  Runs on the single-heap loop (csrc/hs_graph.hip kEvLimRequest / kEvLimPoll)."""
+
+    def __init__(self, name: str, downstream: Entity, policy, queue_capacity: int = 1000):
+        super().__init__(name)
+        self._downstream = downstream
+        self._policy = policy
+        self._queue = FIFOQueue(capacity=queue_capacity)
+        self._queue_depth = 0
+        self._poll_scheduled = False
+        self._received = self._forwarded = self._queued = self._dropped = 0
+        self.received_times: list[Instant] = []
+        self.forwarded_times: list[Instant] = []
+        self.dropped_times: list[Instant] = []
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._downstream]
+
+    @property
+    def downstream(self) -> Entity:
+        return self._downstream
+
+    @property
+    def policy(self):
+        return self._policy
+
+    @property
+    def queue_depth(self) -> int:
+        return self._queue_depth
+
+    @property
+    def stats(self) -> RateLimitedEntityStats:
+        return RateLimitedEntityStats(received=self._received, forwarded=self._forwarded, queued=self._queued, dropped=self._dropped)
+
+
 # ---- probes --------------------------------------------------------------------------------------
 class Data:
     """Time-series container of a Probe (instrumentation/data.py:20-110): `values` = [(time_s, value), ...]."""
@@ -996,10 +1220,10 @@ class Data:
 class Probe(Entity):
     """Periodic metric sampler (instrumentation/probe.py:81-164): a daemon Source that reads `getattr(target, metric)`
     every `interval` seconds into a Data container.  Lowered metrics: Server.depth / active_requests / utilization / available_capacity / has_capacity /
-    stats_accepted / stats_dropped / requests completed, Sink.events_received, Source.generated_count."""
+    stats_accepted / stats_dropped / requests completed, Sink.events_received, Source.generated_count, RateLimitedEntity.queue_depth."""
 
     _LOWERED = {"depth", "active_requests", "utilization", "available_capacity", "has_capacity", "stats_accepted", "stats_dropped",
-                "requests_completed", "_requests_completed", "events_received", "generated_count", "_generated_count"}
+                "requests_completed", "_requests_completed", "events_received", "generated_count", "_generated_count", "queue_depth"}
     # Server attributes that are functions of `active_requests` and the (fixed) concurrency: the engine samples the integer,
     # the Data container applies the reference's expression (components/server/server.py:153-173,191-200, concurrency.py:117-131)
     _ON_ACTIVE = ("utilization", "available_capacity", "has_capacity")
@@ -1024,7 +1248,7 @@ class Probe(Entity):
     def __init__(self, target: Entity, metric: str, data: Data, interval: float = 1.0, start_time: Instant | None = None):
         if interval <= 0:
             raise ValueError("Probe interval must be positive.")                  # probe.py:29-30
-        if metric not in self._LOWERED:
+        if metric not in self._LOWERED or (metric == "queue_depth" and not isinstance(target, RateLimitedEntity)):
             raise NotImplementedError(f"probe metric '{metric}' is an arbitrary attribute; lowered: {sorted(self._LOWERED)}")
         super().__init__(f"Probe_{target.name}_{metric}")
         self.target = target

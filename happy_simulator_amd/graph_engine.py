@@ -21,9 +21,11 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from .core.temporal import Instant
 from .entities import (ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity, ExponentialLatency,
-                       IPHash, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random, RandomRouter,
-                       RoundRobin, Server, SimpleEventProvider, Sink, Source, WeightedLeastConnections, WeightedRoundRobin)
+                       IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random,
+                       RandomRouter, RateLimitedEntity, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source,
+                       TokenBucketPolicy, WeightedLeastConnections, WeightedRoundRobin)
 
 _STRATEGY_CODE = ((ConsistentHash, N.LB_CONSISTENT_HASH), (RoundRobin, N.LB_ROUND_ROBIN), (Random, N.LB_RANDOM),
                   (WeightedRoundRobin, N.LB_WEIGHTED_ROUND_ROBIN), (IPHash, N.LB_IP_HASH), (LeastConnections, N.LB_LEAST_CONNECTIONS),
@@ -67,6 +69,9 @@ class GraphArrays:
         self.name_off = None
         self.src_n_clients = None            # [n] int64: Sources with a ClientKeyEventProvider
         self.lb_weights = None               # [n_rt] int32: strategy.get_weight(backend) per backend slot of the weighted strategies
+        self.lim_policy = None               # [n] uint8 hs_limiter_policy / [n, 3] float64 / [n] int64: RATE_LIMITER nodes
+        self.lim_params = None               #   (hs_limiter_policy_params: p0, p1, p2 and count), set through
+        self.lim_count = None                #   hs_graph_set_limiter_policy once the handle exists
 
     def struct(self) -> N.GraphNodes:
         s = N.GraphNodes()
@@ -119,6 +124,26 @@ class GraphEngine:
                 self.close()
                 raise
 
+        if arrays.lim_policy is not None:
+            try:
+                for i in np.nonzero(arrays.kind == N.NODE_RATE_LIMITER)[0]:
+                    q = N.LimiterPolicyParams(C.sizeof(N.LimiterPolicyParams), int(arrays.lim_policy[i]), *(float(v) for v in arrays.lim_params[i]),
+                                              int(arrays.lim_count[i]))
+                    self._check(self._lib.hs_graph_set_limiter_policy(self._h, int(i), C.byref(q)))
+            except BaseException:
+                self.close()
+                raise
+
+    def limiter(self, node: int) -> dict:
+        """hs_graph_get_limiter: counters, queue depth, the two event counts and the policy's state of limiter `node`."""
+        st = N.LimiterState(struct_size=C.sizeof(N.LimiterState))
+        sliding = self.arrays.lim_policy is not None and self.arrays.lim_policy[node] == N.LIMITER_SLIDING_WINDOW
+        log = np.zeros(int(self.arrays.lim_count[node]) if sliding else 0, np.int64)      # (max_requests bounds the log)
+        self._check(self._lib.hs_graph_get_limiter(self._h, int(node), C.byref(st), _ptr(log) if len(log) else None, len(log)))
+        out = {name: getattr(st, name) for name, _ in N.LimiterState._fields_[1:]}
+        out["log"] = log[:st.count] if sliding else log
+        return out
+
     def set_debug_flags(self, flags: int) -> None:
         """hs_debug_graph_flags: N.GRAPH_DEBUG_LANE_SERIAL / N.GRAPH_DEBUG_COOPERATIVE force where least-loaded selections run."""
         self._check(self._lib.hs_debug_graph_flags(self._h, int(flags)))
@@ -161,6 +186,7 @@ class GraphEngine:
             setattr(st, k, _ptr(a))
         self._check(self._lib.hs_graph_get_stats(self._h, C.byref(st)))
         out["rt_taken"] = out["rt_taken"][:len(self.arrays.rt_targets)]
+        out["limiters"] = {int(i): self.limiter(int(i)) for i in np.nonzero(self.arrays.kind == N.NODE_RATE_LIMITER)[0]}
         return out
 
     def records(self):
@@ -226,7 +252,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             raise UnsupportedTopology(f"probe '{pr.name}' is listed twice")
         add(pr)
     n_front = len(nodes)
-    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer) + _SINKS
+    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity) + _SINKS
 
     def check(ent, where):
         if isinstance(ent, Source):
@@ -264,6 +290,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
     counters = {Server: 0, NetworkLink: 0, RandomRouter: 0}
     rt: list[int] = []
     weights: dict[int, list[int]] = {}                        # rt offset -> the weights of a weighted strategy's backends
+    policies_seen: dict[int, str] = {}                        # id(policy) -> the limiter that holds it
     for i, ent in enumerate(nodes):
         if isinstance(ent, Source):
             ep, prov = ent._event_provider, ent._time_provider
@@ -305,7 +332,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             tgt = ent.target
             if id(tgt) not in node_of:
                 raise UnsupportedTopology(f"probe '{ent.name}': its target is not an entity of this Simulation")
-            want = Source if m == "generated_count" else _SINKS if m == "events_received" else Server
+            want = Source if m == "generated_count" else _SINKS if m == "events_received" else RateLimitedEntity if m == "queue_depth" else Server
             if not isinstance(tgt, want):
                 raise UnsupportedTopology(f"probe '{ent.name}': metric '{ent.metric}' is not an attribute of {type(tgt).__name__}")
             if a.probe_metric is None:
@@ -367,6 +394,41 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
                                               "beyond 2^24 entries (not lowered)")
                 weights[len(rt)] = ws
             rt.extend(node_of[id(b)] for b in backends)
+        elif isinstance(ent, RateLimitedEntity):
+            pol = ent.policy
+            if type(pol) not in LIMITER_POLICIES:
+                raise UnsupportedTopology(f"limiter '{ent.name}': policy {type(pol).__name__} is not lowered to the engine (lowered: "
+                                          "TokenBucketPolicy, LeakyBucketPolicy, SlidingWindowPolicy, FixedWindowPolicy)")
+            if id(pol) in policies_seen:
+                raise UnsupportedTopology(f"limiter '{ent.name}' shares its policy object with '{policies_seen[id(pol)]}': one policy per "
+                                          "limiter is lowered")
+            policies_seen[id(pol)] = ent.name
+            if not pol._pristine():
+                raise UnsupportedTopology(f"limiter '{ent.name}': its policy has been used already (a run starts from the policy as constructed)")
+            kind, p0, p1, p2, count = pol._engine_params()
+            if isinstance(pol, TokenBucketPolicy) and not (p1 > 0):
+                raise UnsupportedTopology(f"limiter '{ent.name}': refill_rate must be > 0, got {p1} (the reference divides by it in mid-run)")
+            if kind == N.LIMITER_LEAKY_BUCKET and not (p0 > 0):
+                raise UnsupportedTopology(f"limiter '{ent.name}': leak_rate must be > 0, got {p0} (the reference never lets a queued Request go)")
+            if isinstance(pol, SlidingWindowPolicy):
+                if count < 1:
+                    raise UnsupportedTopology(f"limiter '{ent.name}': max_requests must be >= 1, got {count} (the reference fails in mid-run)")
+                if count > N.LIMITER_MAX_SLIDING_LOG:
+                    raise UnsupportedTopology(f"limiter '{ent.name}': a SlidingWindowPolicy log of {count} entries is beyond the "
+                                              f"{N.LIMITER_MAX_SLIDING_LOG} the engine keeps")
+            if not all(np.isfinite((p0, p1, p2))):
+                raise UnsupportedTopology(f"limiter '{ent.name}': the policy's parameters must be finite")
+            if kind in (N.LIMITER_SLIDING_WINDOW, N.LIMITER_FIXED_WINDOW) and not (p0 >= 1e-9):
+                raise UnsupportedTopology(f"limiter '{ent.name}': a window of {p0} s is below one nanosecond")
+            cap = ent._queue.capacity
+            if a.lim_policy is None:
+                a.lim_policy = np.full(n, N.LIMITER_NONE, np.uint8)
+                a.lim_params = np.zeros((n, 3), np.float64)
+                a.lim_count = np.zeros(n, np.int64)
+            a.kind[i] = N.NODE_RATE_LIMITER
+            a.target[i] = node_of[id(ent.downstream)]
+            a.queue_cap[i] = -1 if cap == float("inf") else int(cap)
+            a.lim_policy[i], a.lim_params[i], a.lim_count[i] = kind, (p0, p1, p2), count
         elif isinstance(ent, RandomRouter):
             if not ent.targets:
                 raise UnsupportedTopology(f"router '{ent.name}' has no targets")
@@ -427,7 +489,8 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
     new_index = np.empty(n, np.int64)
     per_node = [nm for nm in ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s",
                               "link_lat_min_s", "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric",
-                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients") if getattr(a, nm) is not None]
+                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count")
+                if getattr(a, nm) is not None]
     names = None if a.names is None else [a.names[a.name_off[i]:a.name_off[i + 1]] for i in range(n)]
     parts = []
     for p in range(k):
@@ -495,7 +558,9 @@ class PartRun:
         for (ids, pos, _b), e in zip(self.parts, self.engines):
             st = e.stats()
             for k, v in st.items():
-                if k == "rt_taken":
+                if k == "limiters":
+                    out.setdefault(k, {}).update({int(ids[i]): x for i, x in v.items()})
+                elif k == "rt_taken":
                     out[k][pos] = v
                 else:
                     out[k][ids] = v
@@ -602,6 +667,25 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
                 st._selections = selections
                 st._current_weights = ({b.name: w * selections - sum(ws) * int(stats["rt_taken"][off + q])
                                         for q, (b, w) in enumerate(zip(ent.all_backends, ws))} if selections else {})
+        elif isinstance(ent, RateLimitedEntity):
+            st = stats["limiters"][i]
+            ent._received, ent._forwarded, ent._queued, ent._dropped = (int(st[k]) for k in ("received", "forwarded", "queued", "dropped"))
+            ent._queue_depth, ent._poll_scheduled = int(st["queue_depth"]), bool(st["poll_scheduled"])
+            ent._events = (int(st["requests_handled"]), int(st["polls_handled"]))
+            sel = order[bounds[i]:bounds[i + 1]]                 # its records: (time, hs_limiter_outcome), in processing order
+            tt, code = rec_t[sel], rec_cr[sel]
+            ent.received_times = [Instant(int(t)) for t in tt[code != N.LIMITER_DRAINED]]
+            ent.forwarded_times = [Instant(int(t)) for t in tt[(code == N.LIMITER_FORWARDED) | (code == N.LIMITER_DRAINED)]]
+            ent.dropped_times = [Instant(int(t)) for t in tt[code == N.LIMITER_DROPPED]]
+            pol, when = ent.policy, (Instant(int(st["time_ns"])) if st["has_time"] else None)
+            if st["policy"] == N.LIMITER_TOKEN_BUCKET:
+                pol._tokens, pol._last_refill_time = float(st["tokens"]), when
+            elif st["policy"] == N.LIMITER_LEAKY_BUCKET:
+                pol._last_leak_time = when
+            elif st["policy"] == N.LIMITER_SLIDING_WINDOW:
+                pol._request_log = [Instant(int(t)) for t in st["log"]]
+            else:
+                pol._current_window_start, pol._current_window_count = when, int(st["count"])
         elif isinstance(ent, Probe):
             sel = order[bounds[i]:bounds[i + 1]]                 # its samples: (time, sampled integer)
             ent.data_sink._set(rec_t[sel].copy(), rec_cr[sel].copy(), Probe.value_map(ent.metric, ent.target))

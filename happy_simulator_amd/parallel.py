@@ -551,6 +551,13 @@ class ParallelSimulation:
         self._bounds = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
 
     def run(self) -> ParallelSimulationSummary:
+        from .entities import RateLimitedEntity
+
+        for p in self._partitions:                    # partitions run on the station and sharded engines, which have no limiter
+            for e in p.entities:
+                if isinstance(e, RateLimitedEntity):
+                    raise UnsupportedTopology(f"partition '{p.name}': RateLimitedEntity '{e.name}' is not lowered inside ParallelSimulation "
+                                              "partitions (the single-heap loop of a plain Simulation runs it)")
         if self._links:
             return self._run_linked()
         wall0 = _time.monotonic()

@@ -310,7 +310,10 @@ class Simulation:
         end_ns, start_ns, sched, cancelled_ns = self._general_prepare(g, auto)
         # (one component per heap while there are at most MAX_PARTS: components that SHARE a heap are checked as one -- two Probes of one
         #  interval, two constant Sources of one rate in different components then look like a mixed timestamp group: undecided)
-        parts = None if cancelled_ns else split_parts(g.arrays, MAX_PARTS)
+        # an auto-terminating run with limiters ends when no PRIMARY event is pending anywhere (their polls are daemons,
+        # core/simulation.py:311-322): a part cannot know that of the others, so such a run stays on one heap
+        daemons = auto and bool((g.arrays.kind == N.NODE_RATE_LIMITER).any())
+        parts = None if cancelled_ns or daemons else split_parts(g.arrays, MAX_PARTS)
         try:
             self._refuse_long_run(1 if parts is None else len(parts))
         except UnsupportedTopology:
@@ -371,8 +374,8 @@ class Simulation:
                 continue
             i = g.node_of.get(id(ev.target))
             if i is None or a.kind[i] == N.NODE_SOURCE:
-                raise UnsupportedTopology(f"scheduled event {ev!r}: only Requests for a Server / Sink / NetworkLink / RandomRouter of "
-                                          "this Simulation are lowered")
+                raise UnsupportedTopology(f"scheduled event {ev!r}: only Requests for a Server / Sink / NetworkLink / RandomRouter / "
+                                          "RateLimitedEntity of this Simulation are lowered")
             if ev.on_complete:
                 raise UnsupportedTopology(f"scheduled event {ev!r}: completion hooks are host Python (not lowered)")
             if ev.context.get("created_at") != ev.time:

@@ -188,6 +188,7 @@ typedef enum hs_probe_metric {
     HS_PROBE_COMPLETED = 4,    /* Server._requests_completed */
     HS_PROBE_RECEIVED = 5,     /* Sink.events_received */
     HS_PROBE_GENERATED = 6,    /* Source.generated_count */
+    HS_PROBE_LIMITER_DEPTH = 7,/* RateLimitedEntity.queue_depth (general graphs only) */
     HS_PROBE_NONE = 255
 } hs_probe_metric;
 typedef enum hs_profile_kind { HS_PROF_CONSTANT = 0, HS_PROF_LINEAR_RAMP = 1, HS_PROF_SPIKE = 2 } hs_profile_kind;
@@ -728,7 +729,9 @@ int hs_debug_time_ops(int32_t device, int64_t n, const int64_t *ns, const double
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct hs_graph hs_graph;
 
-typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK = 2, HS_NODE_LINK = 3, HS_NODE_ROUTER = 4, HS_NODE_PROBE = 5, HS_NODE_LB = 6 } hs_node_kind;
+typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK = 2, HS_NODE_LINK = 3, HS_NODE_ROUTER = 4, HS_NODE_PROBE = 5, HS_NODE_LB = 6,
+                             HS_NODE_RATE_LIMITER = 7 /* RateLimitedEntity: `target` = its downstream, `queue_cap` = its FIFO capacity; policy: hs_graph_set_limiter_policy */
+} hs_node_kind;
 
 typedef struct hs_graph_config {
     uint32_t struct_size;            /* sizeof(hs_graph_config) */
@@ -826,6 +829,57 @@ int hs_graph_schedule(hs_graph *g, int32_t node, int64_t time_ns);
  * all ones.  HS_E_INVALID for a weight below 1 or a node that is no LoadBalancer (a strategy that reads no weights ignores them, as
  * the reference ignores BackendInfo.weight), HS_E_UNSUPPORTED for a WeightedRoundRobin total weight above 2^24, HS_E_STATE after a run. */
 int hs_graph_set_lb_weights(hs_graph *g, int32_t node, const int32_t *weights, int32_t n);
+
+/* HS_NODE_RATE_LIMITER: RateLimitedEntity(name, downstream, policy, queue_capacity) (components/rate_limiter/rate_limited_entity.py)
+ * -- admission control in front of any node that takes Requests.  A Request is forwarded at once when policy.try_acquire(now)
+ * grants it (a NEW Event for the downstream at `now`, run-time sort index, same context, no completion hook), else queued in a FIFO
+ * of `queue_cap` places and drained by ONE self-scheduled daemon poll Event at now + policy.time_until_available(now), else dropped.
+ * The two handlers are internal heap-entry kinds beyond HS_EV_KINDS: they count in hs_summary.events_processed but not in
+ * events_by_kind; hs_graph_get_limiter reports them per node (events_processed == sum(events_by_kind) + sum(requests + polls)).
+ * The policies (components/rate_limiter/policy.py), binary64 operation for operation: */
+typedef enum hs_limiter_policy {
+    HS_LIMITER_TOKEN_BUCKET = 0,   /* TokenBucketPolicy(capacity, refill_rate, initial_tokens): p0 = capacity, p1 = refill_rate > 0,
+                                    * p2 = the tokens the bucket starts with */
+    HS_LIMITER_LEAKY_BUCKET = 1,   /* LeakyBucketPolicy(leak_rate): p0 = leak_rate > 0, p1 = its _leak_interval = 1.0 / leak_rate */
+    HS_LIMITER_SLIDING_WINDOW = 2, /* SlidingWindowPolicy(window_size_seconds, max_requests): p0 = the window, count = max_requests in
+                                    * [1, 2^20]: the log is a ring of that many timestamps */
+    HS_LIMITER_FIXED_WINDOW = 3,   /* FixedWindowPolicy(requests_per_window, window_size): p0 = window_size, count = requests_per_window
+                                    * >= 1; the window's start is Python's float floor division (now_s // window_size) * window_size */
+    HS_LIMITER_NONE = 255
+} hs_limiter_policy;
+typedef struct hs_limiter_policy_params {
+    uint32_t struct_size;            /* sizeof(hs_limiter_policy_params) */
+    int32_t policy;                  /* hs_limiter_policy */
+    double p0, p1, p2;
+    int64_t count;
+} hs_limiter_policy_params;
+/* The policy of limiter `node`, between hs_graph_create and the first run (HS_E_STATE afterwards).  A run of a graph that holds a
+ * limiter without a policy returns HS_E_STATE.  HS_E_INVALID: no limiter, a rate <= 0, a count < 1, a window below one nanosecond;
+ * HS_E_UNSUPPORTED: a sliding-window log beyond 2^20 entries. */
+int hs_graph_set_limiter_policy(hs_graph *g, int32_t node, const hs_limiter_policy_params *params);
+typedef struct hs_limiter_state {
+    uint32_t struct_size;            /* sizeof(hs_limiter_state), set by the caller */
+    int32_t policy;
+    int64_t received, forwarded, queued, dropped;   /* RateLimitedEntity.stats */
+    int64_t queue_depth;
+    int64_t poll_scheduled;          /* _poll_scheduled */
+    int64_t requests_handled, polls_handled;        /* events of the two internal kinds this node processed */
+    int64_t has_time;                /* 0: _last_refill_time / _last_leak_time / _current_window_start is None */
+    int64_t time_ns;                 /* ... else its nanoseconds */
+    double tokens;                   /* TokenBucketPolicy.tokens */
+    int64_t count;                   /* _current_window_count; SlidingWindowPolicy: len(_request_log) */
+} hs_limiter_state;
+/* One limiter's state after a run; `log` (capacity `log_cap`, may be NULL) receives min(count, log_cap) timestamps of a
+ * SlidingWindowPolicy's _request_log, oldest first.  Outcome of every Request and every drained one, in processing order:
+ * hs_graph_read_records with node = the limiter, t = the time, created = hs_limiter_outcome. */
+int hs_graph_get_limiter(hs_graph *g, int32_t node, hs_limiter_state *out, int64_t *log, int64_t log_cap);
+typedef enum hs_limiter_outcome { HS_LIMITER_FORWARDED = 0, HS_LIMITER_QUEUED = 1, HS_LIMITER_DROPPED = 2, HS_LIMITER_DRAINED = 3 } hs_limiter_outcome;
+/* Auto-termination (core/simulation.py:306-322, end_time = Infinity): a run to end_ns = 2^61 ends in front of a pop when only daemon
+ * events -- the limiters' polls -- are pending.  A run with any other end processes polls like any event. */
+/* Debug / tests only (no engine path calls it; the null stream, its own allocations): FixedWindowPolicy._get_window_start on the device, one (now_ns, window_s) pair per thread: out_div[i] = Python's float
+ * `to_seconds(now_ns[i]) // window_s[i]` (now_ns >= 0, window_s normal and > 0), out_start_ns[i] = from_seconds(out_div[i] * window_s[i]).
+ * Tests compare both with CPython. */
+int hs_debug_window_start(int32_t device, int64_t n, const int64_t *now_ns, const double *window_s, double *out_div, int64_t *out_start_ns);
 /* How many LeastConnections / WeightedLeastConnections selections of the last run all 64 lanes of the wavefront took (min() over the
  * backends, strategies.py:186,237, as a strided scan + cross-lane reduction) instead of the lone lane (read-only, for tests).
  * Negative: an hs_status. */
