@@ -305,7 +305,7 @@ def run(g: Graph, end_ns: int, start_ns: int = 0, seed: int = 42, rng_mode: int 
     schedule: [(node, time_ns), ...] = Simulation.schedule(Event(time, "Request", target=node)) calls before run().
     part_check (hso_params.part_check): run as one part of a Simulation -- stop in front of the first event beyond end_ns, take that one
     too when `step`, and report the first pop that met a mixed-origin pair on one nanosecond as r.part_check = None | dict(pop, ns,
-    kinds=(popped, next), pre=(popped, next)).  r.next_ns: the earliest pending event's time after the run (None: nothing pending)."""
+    kinds=(popped, next), pre=(popped, next)).  r.next_ns: the earliest pending event's time after the run (None: nothing pending), r.pending: how many are pending."""
     L = lib()
     n = len(g)
     import time as _time
@@ -333,7 +333,8 @@ def run(g: Graph, end_ns: int, start_ns: int = 0, seed: int = 42, rng_mode: int 
         r.final_time_ns = S.final_time_ns
         r.heap_peak = S.heap_peak
         nx = C.c_int64(0)
-        r.next_ns = int(nx.value) if L.hso_pending(h, C.byref(nx)) > 0 else None
+        r.pending = int(L.hso_pending(h, C.byref(nx)))     # the heap's length where the run stopped
+        r.next_ns = int(nx.value) if r.pending > 0 else None
         r.part_check = None
         if part_check:
             pc = np.zeros(5, np.int64)

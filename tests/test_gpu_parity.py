@@ -83,6 +83,44 @@ def test_constant_divisor_quotients_are_ieee():
             np.testing.assert_array_equal(qi, a / b)
 
 
+def test_constant_divisor_quotients_are_ieee_for_random_divisors():
+    """The engines build a ConstDiv from every user rate and every 1 / mean: ~1 500 divisors -- log-uniform rates, reciprocals of
+    log-uniform means, significands within 256 ulp below all-ones (the all-ones significand itself takes the `fast = false` branch)
+    and within 256 ulp above a power of two at exponents -10 .. 10 -- times 2 048 numerators each (the range of E = -log(1 - u),
+    values down to 2^-61, whole nanoseconds up to 2^52), against numpy's division, exactly."""
+    from happy_simulator_amd.engine import debug_const_div
+
+    rng = np.random.default_rng(20)
+    ones = np.uint64(0x000fffffffffffff)
+    exps = np.arange(-10, 11)
+
+    def with_significand(e, frac):                     # 2^e x (1 + frac / 2^52)
+        return ((1023 + e).astype(np.uint64) << np.uint64(52) | frac).view(np.float64)
+
+    e_hi, e_lo = np.repeat(exps, 11), np.repeat(exps, 10)
+    below_ones = np.concatenate([np.zeros(len(exps), np.uint64), rng.integers(1, 257, 10 * len(exps)).astype(np.uint64)])
+    divisors = np.concatenate([
+        np.exp(rng.uniform(np.log(1e-3), np.log(1e8), 600)),
+        1.0 / np.exp(rng.uniform(np.log(1e-6), np.log(1e4), 400)),
+        with_significand(np.concatenate([exps, e_lo]), ones - below_ones),
+        with_significand(e_hi, rng.integers(0, 257, len(e_hi)).astype(np.uint64)),
+    ])
+    all_ones = (divisors.view(np.uint64) & ones) == ones
+    assert 1400 <= len(divisors) <= 1600 and all_ones.sum() == len(exps) and np.isfinite(divisors).all() and (divisors > 0).all()
+    n = 2048
+    for b in divisors:
+        a = np.concatenate([
+            -np.log1p(-rng.random(683)),
+            np.ldexp(rng.random(683) + 0.5, rng.integers(-60, 8, 683)),
+            np.floor(np.ldexp(rng.random(682), rng.integers(1, 53, 682))),
+        ])
+        assert len(a) == n
+        qf, qi, _ = debug_const_div(a, float(b))
+        want = a / b
+        np.testing.assert_array_equal(qf, want, err_msg=f"q_fast, b={float(b)!r}")
+        np.testing.assert_array_equal(qi, want, err_msg=f"q_ieee, b={float(b)!r}")
+
+
 @pytest.mark.parametrize("name", H.golden_names())
 def test_engine_matches_reference_golden(name):
     gold = H.Golden(name)

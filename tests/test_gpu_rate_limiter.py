@@ -68,6 +68,22 @@ def test_named_fixture_equals_the_reference(name):
             S.MAX_PARTS = old
         assert one_sim._graph_parts == 1
         _compare(spec, one_sim, one_pools, RR.get("case", spec))
+        # ... and on the side-by-side kernel, around ITS 48 LDS node rows (hs_graph_run_batch; test_graph_host.py pins the constant):
+        # 6 heaps of 48 / 44 nodes (the last sizes whose rows stay in LDS), 5 heaps of 56 and 2 heaps of 140 (rows in HBM).  Every
+        # heap holds all four policies; a fall-back to one heap would leave _graph_parts == 1
+        from happy_simulator_amd.graph_engine import split_parts
+
+        for max_parts, sizes in ((6, {44, 48}), (5, {56}), (2, {140})):
+            heaps = [b for _ids, _pos, b in split_parts(sim._graph.arrays, max_parts)]
+            assert {b.n for b in heaps} == sizes
+            assert all(len(set(b.lim_policy[b.kind == N.NODE_RATE_LIMITER].tolist())) == 4 for b in heaps)
+            old, S.MAX_PARTS = S.MAX_PARTS, max_parts
+            try:
+                few_sim, few_pools = _run(spec)
+            finally:
+                S.MAX_PARTS = old
+            assert few_sim._graph_parts == max_parts
+            _compare(spec, few_sim, few_pools, RR.get("case", spec))
 
 
 @pytest.mark.parametrize("k", range(RS.N_RANDOM))

@@ -211,3 +211,15 @@ def test_split_parts_partitions_the_graph_without_cutting_an_edge(k):
     chain = hs.Simulation(duration=1.0, sources=[hs.Source.poisson(rate=5.0, target=(sv := hs.Server("s", concurrency=64, downstream=hs.Sink("k"))))],
                           entities=[sv, sv.downstream])
     assert split_parts(chain.lowered().arrays) is None                                # one component: the one heap
+
+
+def test_the_side_by_side_kernels_lds_windows_are_the_sizes_the_gpu_tests_cross():
+    """tests/test_gpu_graph_batch_windows.py and test_gpu_rate_limiter.py hold the windows of hs_graph_run_batch as literals (heaps
+    around 1 024 entries, 48 / 49 nodes) and the capacity a handle starts with (a heap must outgrow it to grow with its tail in HBM):
+    when one of them moves, this test fails instead of those tests silently crossing nothing."""
+    import os
+
+    text = open(os.path.join(N.CSRC, "hs_graph.hip")).read()
+    assert "kLdsHeapBatch = 1024" in text and "kLdsNodesBatch = 48" in text
+    assert "graph_loop<kLdsHeapBatch, kLdsNodesBatch>" in text             # ... and it is these two the batch kernel is built with
+    assert "(long long)n * 4 + 1024);" in text                             # hs_graph_create: the smallest heap_cap of a handle
