@@ -129,20 +129,29 @@ __device__ __forceinline__ double seconds_from_ns_ieee(int64_t ns) { return __dd
 // second makes it exact).  The theorem excludes divisors whose significand is all ones and needs the
 // intermediates to stay normal; `fast` is false for such divisors and the hardware division is used.
 // tests/test_gpu_parity.py::test_constant_divisor_quotients_are_ieee compares 10^7 quotients per divisor.
+// The divisors the multiply + FMA sequence is exact for.  One definition for the device (ConstDiv::init) and the host: the set-up
+// plan (hs_plan.hpp) sends a grid to the uniform-kind kernel only if every LP's two divisors pass, and that kernel then runs
+// the sequence without testing (ConstDiv::div_fast).
+__host__ __device__ inline bool const_div_fast(double divisor) {
+    const uint64_t bits = __builtin_bit_cast(uint64_t, divisor);
+    const uint32_t ex = (uint32_t)(bits >> 52) & 0x7ffu;
+    const bool all_ones = (bits & 0x000fffffffffffffull) == 0x000fffffffffffffull;
+    return !all_ones && ex > 1023u - 200u && ex < 1023u + 200u && (bits >> 63) == 0;
+}
 struct ConstDiv {
     double b, y;
     bool fast;
     __device__ __forceinline__ void init(double divisor) {
         b = divisor;
         y = __ddiv_rn(1.0, divisor);
-        const uint64_t bits = (uint64_t)__double_as_longlong(divisor);
-        const uint32_t ex = (uint32_t)(bits >> 52) & 0x7ffu;
-        const bool all_ones = (bits & 0x000fffffffffffffull) == 0x000fffffffffffffull;
-        fast = !all_ones && ex > 1023u - 200u && ex < 1023u + 200u && (bits >> 63) == 0;
+        fast = const_div_fast(divisor);
     }
     // a must be finite and either 0 or of magnitude in [2^-300, 2^300] (every caller: event times, -log(1-u))
     __device__ __forceinline__ double div(double a) const {
         if (!fast) return __ddiv_rn(a, b);
+        return div_fast(a);
+    }
+    __device__ __forceinline__ double div_fast(double a) const {   // (only where `fast` is known to hold)
         const double q0 = __dmul_rn(a, y);
         const double r0 = __fma_rn(-b, q0, a);
         const double q1 = __fma_rn(r0, y, q0);

@@ -1828,6 +1828,27 @@ int hs_engine_get_lp_stats(hs_engine *h, const hs_lp_stats *o) {
     return HS_OK;
 }
 
+// C == 1 reads created_at from the admission log, where the entries of Requests the worker rejected stay in place, marked
+// (hs_station.hpp log_time): the m-th Sink record's created_at is the m-th UNMARKED entry.  `created` holds the first `cnt` entries
+// of LP `lp`'s log; with `rej` rejected Requests the records lie within the first cnt + rej.
+static int skip_rejected_admissions(hs_engine *h, int32_t lp, int64_t cnt, int64_t rej, int64_t *created) {
+    int64_t want = cnt + rej;
+    if (want > h->L.cap) want = h->L.cap;
+    int64_t *tmp = nullptr;
+    if (hipMalloc(&tmp, (size_t)want * 8) != hipSuccess) return fail(h, HS_E_HIP, "hipMalloc of the read-back staging buffer failed");
+    std::vector<int64_t> all((size_t)want);
+    hipLaunchKernelGGL(hs_gather_one, dim3((unsigned)((want + 255) / 256)), dim3(256), 0, h->stream, h->L.adm, tmp, h->cfg.n_lp, lp, want,
+                       h->L.lp_major ? h->L.cap : (int64_t)0);
+    const bool ok = hipStreamSynchronize(h->stream) == hipSuccess &&
+                    hipMemcpy(all.data(), tmp, (size_t)want * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    hipFree(tmp);
+    if (!ok) return fail(h, HS_E_HIP, "sink read-back failed");
+    int64_t m = 0;
+    for (int64_t k = 0; k < want && m < cnt; ++k) if (all[(size_t)k] >= 0) created[m++] = all[(size_t)k];
+    return HS_OK;
+}
+static bool created_is_the_admission_log(const hs_engine *h) { return h->L.sink_created == h->L.adm; }
+
 int64_t hs_engine_read_sink(hs_engine *h, int32_t lp, int64_t *t_ns, int64_t *created_ns, int64_t cap) {
     if (!h || !h->have_stations) return fail(h, HS_E_STATE, "stations not set");
     if (lp < 0 || lp >= h->cfg.n_lp) return fail(h, HS_E_INVALID, "LP index %d out of range", lp);
@@ -1854,6 +1875,11 @@ int64_t hs_engine_read_sink(hs_engine *h, int32_t lp, int64_t *t_ns, int64_t *cr
             }
         }
         hipFree(tmp);
+        if (created_ns && created_is_the_admission_log(h)) {
+            int64_t rej = 0;
+            if (hipMemcpy(&rej, h->X.rejected + lp, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, HS_E_HIP, "memcpy");
+            if (rej > 0) { const int rc = skip_rejected_admissions(h, lp, cnt, rej, created_ns); if (rc) return rc; }
+        }
     }
     return cnt;
 }
@@ -1897,6 +1923,16 @@ int64_t hs_engine_read_sinks(hs_engine *h, int64_t *counts, int64_t *t_ns, int64
     hipFree(d_off);
     hipFree(d_out);
     if (!ok) return fail(h, HS_E_HIP, "sink read-back failed");
+    if (created_ns && created_is_the_admission_log(h)) {     // (rare: LPs whose worker rejected a Request are read again, one by one)
+        std::vector<int64_t> rej(n);
+        if (hipMemcpy(rej.data(), h->X.rejected, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, HS_E_HIP, "memcpy");
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t c = counts[i] > cap ? cap : counts[i];
+            if (rej[i] <= 0 || c <= 0) continue;
+            const int rc = skip_rejected_admissions(h, (int32_t)i, c, rej[i], created_ns + off[i]);
+            if (rc) return rc;
+        }
+    }
     return total;
 }
 

@@ -508,10 +508,17 @@ __global__ void __launch_bounds__(PC ? 2 * kBlock : kBlock) hs_station_run(Stati
     if constexpr (PC) {
         if (producer) {
             // ---- producer wavefront: stream values for LP `tid`, as long as its consumer is in the request-order loop
+            // Value k of a stream lives in ring slot k % kRing, and a refill is kRefill / 2 whole Philox blocks that start at a
+            // multiple of kRefill: no half block, no wrap inside a refill.  The first refill therefore starts at or below the
+            // stream's position; the values before the position land in the slots behind the consumer's head -- free, nothing is
+            // outstanding when the launch begins -- and are not counted as produced (prod_* starts below zero, mod 2^32).
+            static_assert(kRing % kRefill == 0 && kRefill % 2 == 0,
+                          "HS_KRING must be a multiple of HS_KREFILL and HS_KREFILL even: a refill is whole Philox blocks that do not wrap");
             const int w = tid >> 6;
             bool wants_a = false, wants_s = false;
+            bool first_a = true, first_s = true;    // nothing generated yet: the rings are empty, the first refill always fits
             uint64_t gen_a = 0, gen_s = 0;          // absolute index of the next value to generate
-            uint32_t prod_a = 0, prod_s = 0;        // values written to the rings so far
+            uint32_t prod_a = 0, prod_s = 0;        // values at or beyond the position written to the rings so far
             int slot_a = 0, slot_s = 0;
             if (lp < n) {
                 S.tid = tid;
@@ -521,41 +528,46 @@ __global__ void __launch_bounds__(PC ? 2 * kBlock : kBlock) hs_station_run(Stati
                 S.init_streams(P.seed[lp], P.stream_base[lp], X.arr_k[lp], X.svc_k[lp], ring_a, ring_s);
                 wants_a = P.src_kind[lp] == 1 && X.A[lp] != kInfNs;
                 wants_s = P.svc_kind[lp] == 0;
-                gen_a = S.arr_k; gen_s = S.svc_k;
+                // (a stream nobody draws from keeps its count at zero: the first pass refills every wanted stream before it publishes)
+                const uint32_t back_a = wants_a ? (uint32_t)(S.arr_k % (uint64_t)kRefill) : 0u;
+                const uint32_t back_s = wants_s ? (uint32_t)(S.svc_k % (uint64_t)kRefill) : 0u;
+                gen_a = S.arr_k - back_a; gen_s = S.svc_k - back_s;
+                prod_a = 0u - back_a; prod_s = 0u - back_s;
+                slot_a = (int)(gen_a % (uint64_t)kRing); slot_s = (int)(gen_s % (uint64_t)kRing);
             }
             for (;;) {
                 if (__hip_atomic_load(&pc_done[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
                 const uint32_t c = __hip_atomic_load(&pc_cons[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 const uint32_t out_a = (prod_a - (c & 0xffffu)) & 0xffffu, out_s = (prod_s - (c >> 16)) & 0xffffu;
-                const bool do_a = wants_a && out_a + (uint32_t)kRefill <= (uint32_t)kRing;
-                const bool do_s = wants_s && out_s + (uint32_t)kRefill <= (uint32_t)kRing;
+                const bool do_a = wants_a && (first_a || out_a + (uint32_t)kRefill <= (uint32_t)kRing);
+                const bool do_s = wants_s && (first_s || out_s + (uint32_t)kRefill <= (uint32_t)kRing);
                 if (!__any(do_a || do_s)) { __builtin_amdgcn_s_sleep(HS_PC_SLEEP_P); continue; }
                 if (__any(do_a)) {
                     if (do_a) {
                         const uint64_t b0 = gen_a >> 1;
-                        const bool odd = (gen_a & 1) != 0;
 #pragma unroll
                         for (int i = 0; i < kRefill / 2; ++i) {
                             const uint64_t b = b0 + (uint64_t)i;
                             const U4 o = philox4x32_10((uint32_t)b, (uint32_t)(b >> 32), S.asid0, S.asid1, S.key0, S.key1);
-                            const double v0 = S.arr_value(res53(o.x, o.y)), v1 = S.arr_value(res53(o.z, o.w));
-                            if (!(i == 0 && odd)) { ring_a[slot_a][tid] = v0; slot_a = slot_a + 1 == kRing ? 0 : slot_a + 1; ++prod_a; ++gen_a; }
-                            ring_a[slot_a][tid] = v1; slot_a = slot_a + 1 == kRing ? 0 : slot_a + 1; ++prod_a; ++gen_a;
+                            ring_a[slot_a + 2 * i][tid] = S.arr_value(res53(o.x, o.y));
+                            ring_a[slot_a + 2 * i + 1][tid] = S.arr_value(res53(o.z, o.w));
                         }
+                        slot_a = slot_a + kRefill == kRing ? 0 : slot_a + kRefill;
+                        prod_a += (uint32_t)kRefill; gen_a += (uint64_t)kRefill; first_a = false;
                     }
                 }
                 if (__any(do_s)) {
                     if (do_s) {
                         const uint64_t b0 = gen_s >> 1;
-                        const bool odd = (gen_s & 1) != 0;
 #pragma unroll
                         for (int i = 0; i < kRefill / 2; ++i) {
                             const uint64_t b = b0 + (uint64_t)i;
                             const U4 o = philox4x32_10((uint32_t)b, (uint32_t)(b >> 32), S.ssid0, S.ssid1, S.key0, S.key1);
-                            const double v0 = S.svc_value(res53(o.x, o.y)), v1 = S.svc_value(res53(o.z, o.w));
-                            if (!(i == 0 && odd)) { ring_s[slot_s][tid] = v0; slot_s = slot_s + 1 == kRing ? 0 : slot_s + 1; ++prod_s; ++gen_s; }
-                            ring_s[slot_s][tid] = v1; slot_s = slot_s + 1 == kRing ? 0 : slot_s + 1; ++prod_s; ++gen_s;
+                            ring_s[slot_s + 2 * i][tid] = S.svc_value(res53(o.x, o.y));
+                            ring_s[slot_s + 2 * i + 1][tid] = S.svc_value(res53(o.z, o.w));
                         }
+                        slot_s = slot_s + kRefill == kRing ? 0 : slot_s + kRefill;
+                        prod_s += (uint32_t)kRefill; gen_s += (uint64_t)kRefill; first_s = false;
                     }
                 }
                 // the values first, then the counters (release: the ring stores are complete before the count moves)
@@ -597,6 +609,11 @@ __global__ void __launch_bounds__(PC ? 2 * kBlock : kBlock) hs_station_run(Stati
 #endif
             uint32_t seen = 0;                   // PC: produced counters as last read (arrival | service << 16)
             const uint64_t ak0 = S.arr_k, sk0 = S.svc_k;
+            if constexpr (PC) {                  // value k of a stream is in slot k % kRing (the producer above)
+                if (live) { S.ra.head = (int)(ak0 % (uint64_t)kRing); S.rs.head = (int)(sk0 % (uint64_t)kRing); }
+            }
+            uint32_t ca = 0, cs = 0;             // PC: values consumed so far (mod 2^16), what pc_cons publishes
+            uint32_t n_int = 0;                  // interior iterations of this lane not yet in rc / arr_k / svc_k (req_fold_interior)
             for (;;) {
                 const bool act = elig && !rc.bail && !rc.done;
                 if (!__any(act)) break;
@@ -606,7 +623,6 @@ __global__ void __launch_bounds__(PC ? 2 * kBlock : kBlock) hs_station_run(Stati
                 if constexpr (PC) {
                     // every lane that may consume needs one value of each stream; the producer runs ahead, so this rarely waits
                     const bool need_a = act && S.src_kind == 1 && S.A != kInfNs, need_s = act && S.svc_kind == 0;
-                    const uint32_t ca = (uint32_t)(S.arr_k - ak0) & 0xffffu, cs = (uint32_t)(S.svc_k - sk0) & 0xffffu;
                     unsigned spins = 0;
                     while (__any((need_a && (seen & 0xffffu) == ca) || (need_s && (seen >> 16) == cs))) {
                         seen = __hip_atomic_load(&pc_prod[tid], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -623,12 +639,23 @@ __global__ void __launch_bounds__(PC ? 2 * kBlock : kBlock) hs_station_run(Stati
 #ifdef HS_CYCLES
                 const unsigned long long c1 = __builtin_readcyclecounter();
 #endif
-                S.req_step(rc, act);
-                if constexpr (PC) {
-                    __hip_atomic_store(&pc_cons[tid], ((uint32_t)(S.arr_k - ak0) & 0xffffu) | ((uint32_t)(S.svc_k - sk0) << 16),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    seen = __hip_atomic_load(&pc_prod[tid], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if constexpr (PC && UNI) {
+                    // between the edges of the window every active lane's request arrives, starts and departs inside it: the
+                    // wavefront then takes the lean body, and today's req_step whenever one active lane is not provably there
+                    const auto e = S.req_eval(rc);
+                    if (!__any(act && !S.req_interior(rc, e))) {
+                        if (act) { S.req_step_interior(rc, e); ++n_int; ++ca; ++cs; }
+                    } else {
+                        S.req_step(rc, act, e);
+                        ca = (uint32_t)(S.arr_k - ak0) + n_int; cs = (uint32_t)(S.svc_k - sk0) + n_int;
+                    }
+                    ca &= 0xffffu; cs &= 0xffffu;
+                } else {
+                    S.req_step(rc, act);
+                    if constexpr (PC) { ca = (uint32_t)(S.arr_k - ak0) & 0xffffu; cs = (uint32_t)(S.svc_k - sk0) & 0xffffu; }
                 }
+                // (the produced counts are read again at the top, and only when the local copy says a ring is empty)
+                if constexpr (PC) __hip_atomic_store(&pc_cons[tid], ca | (cs << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #ifdef HS_CYCLES
                 const unsigned long long c2 = __builtin_readcyclecounter();
                 cyc_top += c1 - c0; cyc_step += c2 - c1; ++n_it;
@@ -643,6 +670,7 @@ __global__ void __launch_bounds__(PC ? 2 * kBlock : kBlock) hs_station_run(Stati
             if constexpr (PC) {
                 if ((tid & 63) == 0) __hip_atomic_store(&pc_done[tid >> 6], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
+            if constexpr (PC && UNI) S.req_fold_interior(rc, n_int);
             if (elig && !rc.bail) { S.req_finish(rc); event_order = false; }
             bail_reload = elig && rc.bail;     // same-timestamp hazard: start over in event order
         }

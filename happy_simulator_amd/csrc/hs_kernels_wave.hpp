@@ -128,12 +128,12 @@ __device__ __forceinline__ void wave_fold(const StationParams &P, StationState &
             seqA = seq + (d_first ? 1u : 0u); seqD = seq + (d_first ? 0u : 1u); seq += 2u;
         }
         // lineage of what is pending now (Station::req_finish)
-        if (c_tick) { dpA = 1; rcA = acc2 >= 2 ? (c_tick >= 2 ? to_i64(a_last2) : L.adm[(size_t)(acc2 - 2) * n + lp]) : crtA0; }
+        if (c_tick) { dpA = 1; rcA = acc2 >= 2 ? (c_tick >= 2 ? to_i64(a_last2) : log_time(L.adm[(size_t)(acc2 - 2) * n + lp])) : crtA0; }
         if (pend && pend_new) {
             const int64_t m = st2 - 1;                   // the request in service: it started at pendS
             if (pendS == to_i64(pendA_d)) {              // ... on arrival: six steps from its tick, which was created at the tick before
                 dpD = 6;
-                rcD = m >= 1 ? (pend_i >= 1 ? to_i64(pendAp_d) : (m - 1 < L.cap ? L.adm[(size_t)(m - 1) * n + lp] : 0)) : crtA0;
+                rcD = m >= 1 ? (pend_i >= 1 ? to_i64(pendAp_d) : (m - 1 < L.cap ? log_time(L.adm[(size_t)(m - 1) * n + lp]) : 0)) : crtA0;
             } else {                                     // ... when request m - 1 left: four steps from that continuation, created when IT started
                 dpD = 4; rcD = to_i64(pendSp_d);         // (= pendS - its service time: Station::req_finish draws that again)
             }

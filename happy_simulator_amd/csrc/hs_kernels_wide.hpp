@@ -399,11 +399,11 @@ __global__ void __launch_bounds__(kWideBlock) __attribute__((amdgpu_waves_per_eu
         // lineage of what is pending now (Station::req_finish)
         int32_t dpA = X.dpA[lp], dpD = X.dpD[lp];
         int64_t rcA = X.rcA[lp], rcD = X.rcD[lp];
-        if (c_tick) { dpA = 1; rcA = acc2 >= 2 ? (c_tick >= 2 ? (int64_t)a_last2 : L.adm[(size_t)(acc2 - 2) * n + lp]) : crtA0; X.dpA[lp] = (uint8_t)dpA; X.rcA[lp] = rcA; }
+        if (c_tick) { dpA = 1; rcA = acc2 >= 2 ? (c_tick >= 2 ? (int64_t)a_last2 : log_time(L.adm[(size_t)(acc2 - 2) * n + lp])) : crtA0; X.dpA[lp] = (uint8_t)dpA; X.rcA[lp] = rcA; }
         if (pend && pn) {
             const int64_t m = st2 - 1;
-            const int64_t a_m = m < L.cap ? L.adm[(size_t)m * n + lp] : 0;
-            if (pendS == a_m) { dpD = 6; rcD = m >= 1 ? L.adm[(size_t)(m - 1) * n + lp] : crtA0; }
+            const int64_t a_m = m < L.cap ? log_time(L.adm[(size_t)m * n + lp]) : 0;
+            if (pendS == a_m) { dpD = 6; rcD = m >= 1 ? log_time(L.adm[(size_t)(m - 1) * n + lp]) : crtA0; }
             else {
                 Stream st;
                 st.init(((uint64_t)key1 << 32) | key0, ((uint64_t)ssid1 << 32) | ssid0, (uint64_t)(m - 1));

@@ -136,6 +136,10 @@ inline int plan_entities(const hs_config &cfg, const hs_stations *st, StationPla
     for (int i = 0; i < n && p.f64_times; ++i)     // (one draw is at most kLongestExpDraw means / inter-arrival times: everything stays below 2^52 ns)
         if (!(c.svc_mean[i] < 1e4) || !(c.src_rate[i] > 1e-3)) p.f64_times = false;
     if (!p.f64_times) p.uni_grid = false;
+    // (... and divide by the rate and by lambda = 1 / mean with the multiply + FMA sequence, untested: hs_device.hpp const_div_fast.
+    // The f64_times limits keep the exponents in range; what this excludes is an all-ones significand.)
+    for (int i = 0; i < n && p.uni_grid; ++i)
+        if (!const_div_fast(c.src_rate[i]) || !const_div_fast(1.0 / c.svc_mean[i])) p.uni_grid = false;
     if (p.any_xsrc) p.any_profile = true;                         // such LPs run on the general-path instantiation
     for (int i = 0; i < n; ++i) {
         const int sk = c.src_kind[i];

@@ -195,6 +195,12 @@ struct RecordLogs {
     // against 1.05 GB of records on the headline ring).  LP-major, the line an LP appends to stays in the L2 until it is full.
     int32_t lp_major;
 };
+// C == 1 keeps no created_at column of its own: Sink record m reads adm[m], the m-th completion being the m-th admission.  A
+// Request that the worker REJECTS (two Requests of one nanosecond delivered to it, server.py:223-234 -- at nanosecond-scale rates a
+// Source's next tick truncates onto the current one) is admitted and never completes; its entry stays in place, so that adm[k] remains
+// the time of tick k for the lineage, and is MARKED by complementing it (times are >= 0: hs_engine_create refuses a negative start).
+// Who reads a time from the log takes the mark off (log_time); who reads created_at values skips marked entries (hs_engine_read_sink*).
+__device__ __forceinline__ int64_t log_time(int64_t v) { return v < 0 ? ~v : v; }
 __device__ __forceinline__ size_t log_at(const RecordLogs &L, int64_t k, int lp, int n) {
     return L.lp_major ? (size_t)lp * (size_t)L.cap + (size_t)k : (size_t)k * (size_t)n + (size_t)lp;
 }
@@ -413,11 +419,14 @@ struct Station {
     }
     // value of arrival draw k: E / rate with E = -log(1 - u)          (providers/poisson_arrival.py:31,
     //                                                                   load/arrival_time_provider.py:76)
-    __device__ __forceinline__ double arr_value(double u) const { return div_rate.div(exp1_from_uniform(u)); }
+    // (UNI: the host has checked both divisors, hs_plan.hpp plan_entities)
+    __device__ __forceinline__ double arr_value(double u) const {
+        return UNI ? div_rate.div_fast(exp1_from_uniform(u)) : div_rate.div(exp1_from_uniform(u));
+    }
     // value of service draw k: get_latency(...).to_seconds() of random.expovariate(lambda)
     //                                         (distributions/exponential.py:43, server/server.py:246-247)
     __device__ __forceinline__ double svc_value(double u) const {
-        const double sample = div_lambda.div(exp1_from_uniform(u));
+        const double sample = UNI ? div_lambda.div_fast(exp1_from_uniform(u)) : div_lambda.div(exp1_from_uniform(u));
         if constexpr (UNI) return seconds_from_ns_d(ns_from_seconds_d(sample));   // (times below 2^51 ns: hs_engine uni_grid)
         return seconds_from_ns(ns_from_seconds(sample));      // Duration.from_seconds(sample).to_seconds()
     }
@@ -538,7 +547,11 @@ struct Station {
         ev[4]++;
         ev[5]++;
         const int64_t k = started++;
-        if (active >= conc) { rejected++; return 0; }                    // acquire() failed (server.py:223-234)
+        if (active >= conc) {                                            // acquire() failed (server.py:223-234)
+            if (C == 1 && k < cap && adm[k * ls] >= 0) adm[k * ls] = ~adm[k * ls];   // (no Sink record will read this entry: log_time)
+            rejected++;
+            return 0;
+        }
         active++;
         double s; int64_t dur;
         sample_service(s, dur);
@@ -1131,6 +1144,10 @@ struct Station {
         bool pend, blocked, bail, done;
         int64_t crtA0;              // creation time of the tick that was pending when the window began (lineage, req_finish)
         double arr_d;               // UNI: ArrivalTimeProvider.current_time as a binary64 (whole ns below 2^52: exact)
+        // where the next admission / Sink record goes and how many still fit: adm + (accepted + n_tick) * ls and
+        // cap - (accepted + n_tick), sink_t + (sink_w + n_dep) * ls and cap - (sink_w + n_dep), carried instead of recomputed
+        int64_t *pa, *ps;
+        int64_t room_a, room_s;
         // PF, an LP with ONE Probe (slot 0): its ticks inside the window, sampled from the request sequence (req_probe_*).  A sample
         // needs generated(T) -- known once an arrival beyond T is seen -- and completed(T) -- known once a departure beyond T is
         // seen; the two become known in either order, so each has its own pointer into the tick table and a third one finalises.
@@ -1208,9 +1225,10 @@ struct Station {
     __device__ __forceinline__ void req_count_departure(ReqCursor &c, bool p, int64_t d, double s) {
         total_service = p ? __dadd_rn(total_service, s) : total_service;
         if (p && HSG(egress == 1, true)) {
-            const int64_t w = sink_w + (int64_t)c.n_dep;
-            if (w < cap) sink_t[w * ls] = d; else overflow = 1;
+            if (c.room_s > 0) *c.ps = d; else overflow = 1;
         }
+        c.ps += p ? ls : 0;                               // (only read where the LP has a Sink)
+        c.room_s -= p ? 1 : 0;
         c.n_dep += p ? 1u : 0u;
         c.lt = (p && d > c.lt) ? d : c.lt;
     }
@@ -1218,6 +1236,8 @@ struct Station {
         c.T = T; c.nb = buf; c.lt = last_time; c.crtA0 = crtA; c.arr_d = (double)arr_time;
         c.n_tick = c.n_notify = c.n_poll = c.n_start = c.n_dep = 0;
         c.blocked = c.bail = c.done = false;
+        c.pa = adm + accepted * ls; c.room_a = cap - accepted;
+        c.ps = sink_t + sink_w * ls; c.room_s = cap - sink_w;
         const bool busy = active > 0;
         c.Sprev = busy ? crtD[0] : INT64_MIN;
         c.Dprev = busy ? D[0] : INT64_MIN;
@@ -1233,23 +1253,75 @@ struct Station {
             }
         }
     }
-    __device__ __forceinline__ void req_step(ReqCursor &c, bool act) {
+    // What one iteration works with whichever way the request goes: the tick after A, the service time the next start
+    // draws, and where the request starts and departs if it is the next ARRIVAL (nobody waiting from an earlier launch).
+    struct ReqEval {
+        double a2d, s_new;
+        int64_t a2, dur, Sk, Dk;
+    };
+    __device__ __forceinline__ ReqEval req_eval(const ReqCursor &c) const {
+        ReqEval e;
+        const double inc = HSG(src_kind == 1, true) ? ra.peek() : inc_const;
+        e.a2d = UNI ? ns_from_seconds_d(__dadd_rn(seconds_from_ns_d(c.arr_d), inc)) : 0.0;
+        e.a2 = UNI ? i64_from_whole_d(e.a2d) : ns_from_seconds(__dadd_rn(seconds_from_ns(arr_time), inc));
+        e.s_new = HSG(svc_kind == 0, true) ? rs.peek() : svc_const_s;
+        e.dur = UNI ? i64_from_whole_d(ns_from_seconds_d(e.s_new)) : (HSG(svc_kind == 0, true) ? ns_from_seconds(e.s_new) : svc_const_ns);
+        e.Sk = A > c.Dprev ? A : c.Dprev;
+        e.Dk = (int64_t)((uint64_t)e.Sk + (uint64_t)e.dur);   // (Sk may be kInfNs: wraps, and req_interior / req_step look at Sk first)
+        return e;
+    }
+    // INTERIOR: the request arrives, starts and departs inside the window, nobody was waiting before it, and nothing shares
+    // a nanosecond in a way that makes req_step bail.  For such a lane req_step runs with bk = false, arr = st = dp = true
+    // and bail = false, and req_step_interior below leaves exactly the state req_step would.
+    __device__ __forceinline__ bool req_interior(const ReqCursor &c, const ReqEval &e) const {
+        // (Sk <= T covers A <= T.  It is not implied by Dk <= T: after a request that could not start Dprev is kInfNs, and
+        // kInfNs + dur wraps)
+        return c.nb == 0 && e.Sk <= c.T && e.Dk <= c.T && A != c.Sprev && A != c.Dprev && e.a2 > A && e.dur != 0;
+    }
+    // (UNI, no Probe.)  Call it for the active lanes only: every statement is req_step's with the predicates above folded in.
+    // The three event counters n_tick / n_start / n_dep, arr_k and svc_k all move by one: the caller counts the interior
+    // iterations of a lane instead and adds them with req_fold_interior.  c.pendD / pendS / pend_s are not written: they are
+    // read only while c.pend holds, and whoever sets c.pend writes all three (req_begin, req_step).
+    __device__ __forceinline__ void req_step_interior(ReqCursor &c, const ReqEval &e) {
+        static_assert(UNI && !PF, "the interior step assumes Source.poisson -> Server(Exp) -> Sink and no Probe");
+        if (c.room_a > 0) *c.pa = A; else overflow = 1;
+        c.pa += ls; c.room_a -= 1;
+        c.n_notify += c.Sprev < A ? 1u : 0u;
+        c.n_poll += c.Dprev < A ? 1u : 0u;
+        crtA = A;
+        arr_time = e.a2;
+        c.arr_d = e.a2d;
+        ra.advance_if(true);
+        rs.advance_if(true);
+        total_service = __dadd_rn(total_service, e.s_new);
+        if (c.room_s > 0) *c.ps = e.Dk; else overflow = 1;
+        c.ps += ls; c.room_s -= 1;
+        c.lt = e.Dk > c.lt ? e.Dk : c.lt;                // (A <= Sk < Dk: the departure is the latest of the three)
+        c.pend = false;
+        c.Sprev = e.Sk; c.Dprev = e.Dk;
+        A = e.a2;
+    }
+    __device__ __forceinline__ void req_fold_interior(ReqCursor &c, uint32_t n_int) {
+        c.n_tick += n_int; c.n_start += n_int; c.n_dep += n_int;
+        arr_k += n_int; svc_k += n_int;
+    }
+    __device__ __forceinline__ void req_step(ReqCursor &c, bool act) { req_step(c, act, req_eval(c)); }
+    __device__ __forceinline__ void req_step(ReqCursor &c, bool act, const ReqEval &e) {
         const int64_t T = c.T;
         const bool bk = c.nb > 0 && !c.blocked;          // next in FIFO order: a request that is already waiting
         const bool arr = !bk && A <= T;                  // ... or the next arrival
         const bool fin = !bk && !arr;
         // arrival part at a_k = A
-        const double inc = HSG(src_kind == 1, true) ? ra.peek() : inc_const;
-        const double a2d = UNI ? ns_from_seconds_d(__dadd_rn(seconds_from_ns_d(c.arr_d), inc)) : 0.0;
-        const int64_t a2 = UNI ? i64_from_whole_d(a2d) : ns_from_seconds(__dadd_rn(seconds_from_ns(arr_time), inc));
+        const double a2d = e.a2d;
+        const int64_t a2 = e.a2;
         const bool tie_a = arr && (A == c.Sprev || A == c.Dprev || a2 <= A);
         const bool notify = arr && c.Sprev < A;
         const bool idle = arr && c.Dprev < A;
         // start part at S_k
-        const int64_t Sk = bk ? c.Dprev : (A > c.Dprev ? A : c.Dprev);
+        const int64_t Sk = bk ? c.Dprev : e.Sk;
         const bool st = (bk || arr) && Sk <= T;
-        const double s_new = HSG(svc_kind == 0, true) ? rs.peek() : svc_const_s;
-        const int64_t dur = UNI ? i64_from_whole_d(ns_from_seconds_d(s_new)) : (HSG(svc_kind == 0, true) ? ns_from_seconds(s_new) : svc_const_ns);
+        const double s_new = e.s_new;
+        const int64_t dur = e.dur;
         const int64_t Dk = Sk + dur;
         const bool dp = st && Dk <= T;                   // departure part at D_k
         bool tie_p = false;
@@ -1268,9 +1340,10 @@ struct Station {
         const bool arr_g = go && arr, st_g = go && st, dp_g = go && dp;
         // Source.handle_event + Queue._handle_enqueue (+ notify / poll when the buffer is empty / the worker idle)
         if (arr_g) {
-            const int64_t w = accepted + (int64_t)c.n_tick;
-            if (w < cap) adm[w * ls] = A; else overflow = 1;
+            if (c.room_a > 0) *c.pa = A; else overflow = 1;
         }
+        c.pa += arr_g ? ls : 0;
+        c.room_a -= arr_g ? 1 : 0;
         c.n_tick += arr_g ? 1u : 0u;
         c.n_notify += (go && notify) ? 1u : 0u;
         c.n_poll += (go && idle) ? 1u : 0u;
@@ -1362,14 +1435,14 @@ struct Station {
         // (a tie made the lane bail), and in this regime every tick is admitted: adm[k] is the time of tick k.
         if (c.n_tick != 0u) {       // the pending tick was created by tick number accepted - 1, itself created at tick accepted - 2
             dpA = 1;
-            rcA = accepted >= 2 ? adm[(accepted - 2) * ls] : c.crtA0;
+            rcA = accepted >= 2 ? (accepted - 2 < cap ? log_time(adm[(accepted - 2) * ls]) : 0) : c.crtA0;   // (a full log: the run is refused)
         }
         if (c.pend && c.n_start != 0u) {      // the request in service is number m = started - 1; it started at pendS
             const int64_t m = started - 1;
-            const int64_t a_m = m < cap ? adm[m * ls] : 0;
+            const int64_t a_m = m < cap ? log_time(adm[m * ls]) : 0;
             if (c.pendS == a_m) {             // ... on arrival: six steps from tick m, which was created at tick m - 1
                 dpD[0] = 6;
-                rcD[0] = m >= 1 ? adm[(m - 1) * ls] : c.crtA0;
+                rcD[0] = m >= 1 ? log_time(adm[(m - 1) * ls]) : c.crtA0;
             } else {                          // ... when request m - 1 left: four steps from that continuation, created when IT started
                 double s_prev = svc_const_s;
                 if (HSG(svc_kind == 0, true)) {
