@@ -482,6 +482,10 @@ def lib():
     L.hs_graph_get_limiter.argtypes = [C.c_void_p, C.c_int32, P(LimiterState), C.c_void_p, C.c_int64]
     L.hs_debug_window_start.restype = C.c_int
     L.hs_debug_window_start.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hs_graph_add_fault.restype = C.c_int
+    L.hs_graph_add_fault.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
+    L.hs_graph_get_faults.restype = C.c_int
+    L.hs_graph_get_faults.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64)]
     L.hs_graph_coop_selects.restype = C.c_int64
     L.hs_graph_coop_selects.argtypes = [C.c_void_p]
     L.hs_debug_graph_flags.restype = C.c_int
@@ -541,4 +545,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_last_error", "hs_graph_destroy",
     "hs_graph_set_lb_weights", "hs_graph_coop_selects", "hs_debug_graph_flags", "hs_lb_set_weights", "hs_lb_wrr_table", "hs_lb_ip_hash_select",
     "hs_graph_set_limiter_policy", "hs_graph_get_limiter", "hs_debug_window_start",
+    "hs_graph_add_fault", "hs_graph_get_faults",
 )

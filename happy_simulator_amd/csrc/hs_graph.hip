@@ -70,7 +70,8 @@ struct GParam {                                // 64 bytes, read-only
                                                // WeightedRoundRobin: the total weight W = entries of its selection table (lim = its offset)
     int32_t rt_off, rt_cnt;                    // router / LoadBalancer: its targets; Source / Probe: rt_off = row of its tick table (-1: none)
     uint8_t kind, sub;                         // sub: Source arrival kind (hs_source_kind); Server / link latency kind; Probe metric; LB strategy
-    uint8_t pad[6];
+    uint8_t crashed;                           // entity._crashed (faults/node_faults.py:46-62): the one byte of a row a run writes -- kFaultOn / kFaultOff
+    uint8_t pad[5];
 };
 
 struct GState {                                // 64 bytes
@@ -104,7 +105,19 @@ struct GRequest {                              // 32 bytes: the payload Event's 
 
 // RateLimitedEntity's two handlers: heap-entry kinds of this loop only, beyond the public fifteen (hs_summary.events_by_kind keeps its
 // meaning; they are counted per node: GState::a Requests, GState::d polls)
-constexpr uint32_t kEvLimRequest = HS_EV_KINDS, kEvLimPoll = HS_EV_KINDS + 1, kEvAllKinds = HS_EV_KINDS + 2;
+constexpr uint32_t kEvLimRequest = HS_EV_KINDS, kEvLimPoll = HS_EV_KINDS + 1;
+// CrashNode / PauseNode (faults/node_faults.py): the two daemon Events of a node fault, two more internal kinds.  GEvent::node is the
+// entity whose flag they set / clear; GEvent::pad bit 1: the Event was cancelled before the run (popped and skipped,
+// core/simulation.py:475-477).  They count in events_processed and per graph (GVars::faults_processed), not in events_by_kind.
+constexpr uint32_t kEvFaultOn = HS_EV_KINDS + 2, kEvFaultOff = HS_EV_KINDS + 3, kEvAllKinds = HS_EV_KINDS + 4;
+constexpr uint32_t kPadPre = 1u, kPadCancelled = 2u;
+// Event.invoke drops an Event whose TARGET has `_crashed` set (core/event.py:261); ProcessContinuation.invoke (:465) does not look.
+// These kinds are aimed at the entity itself; NOTIFY / POLL / DELIVER / WORK / PROBE go to its driver, queue, worker adapter or the
+// probe's callback, the two continuations resume a generator: never dropped.
+constexpr uint32_t kDropKinds = (1u << HS_EV_SOURCE) | (1u << HS_EV_PROBE_TICK) | (1u << HS_EV_ENQUEUE) | (1u << HS_EV_SINK) | (1u << HS_EV_LINK) |
+                                (1u << HS_EV_ROUTE) | (1u << HS_EV_LB) | (1u << HS_EV_LB_RESP) | (1u << kEvLimRequest) | (1u << kEvLimPoll);
+static_assert(kEvAllKinds <= 32, "kDropKinds is one word");
+struct GFault { int64_t t; int32_t node; uint32_t flags; };   // hs_graph_add_fault: flags bit 0 = on, bit 1 = cancelled
 constexpr int kLimPollScheduled = 1, kLimHasTime = 2;   // GState::active of a limiter: _poll_scheduled; _last_*_time / _current_window_start is set
 constexpr long long kMaxSlidingLog = 1ll << 20;          // SlidingWindowPolicy.max_requests the ring is sized for
 
@@ -125,7 +138,10 @@ struct GVars {                                 // device scalars
     long long sched_done;                      // scheduled entries already pushed
     long long heap_peak;
     long long coop_selects;                    // least-loaded selections all 64 lanes took (hs_graph_coop_selects)
-    long long polls_pending;                   // the limiters' poll Events in the heap
+    long long polls_pending;                   // daemon Events in the heap: the limiters' polls and the fault Events
+    long long internal_by_kind[4];             // the four internal kinds as events_by_kind counts the public ones (hs_graph_get_faults)
+    long long faults_cancelled;                // cancelled fault Events popped
+    const GFault *faults; long long n_faults;  // the fault Events in the order FaultSchedule.start constructed them: read once, at boot
 };
 
 struct GCtl {                                  // kernel argument
@@ -143,7 +159,7 @@ struct GCtl {                                  // kernel argument
     const int32_t *lb_w;                       // [n_rt] the weighted strategies' weight of every backend slot (strategy._weights; default 1)
     int coop_reset;                            // 1: the first launch of a run -- the lone lane zeroes GVars::coop_selects (the host clears it after the launch)
     int64_t *lim_ring;                         // SlidingWindowPolicy._request_log of every such limiter: a ring at GParam::rt_off of GParam::rt_cnt entries
-    int auto_term;                             // 1: end_ns = 2^61 (end_time = Infinity) -- the run ends when only the limiters' daemon polls are pending
+    int auto_term;                             // 1: end_ns = 2^61 (end_time = Infinity) -- the run ends when only daemon Events (polls, faults) are pending
     int coop_min;                              // least-loaded selections over >= this many backends go to all 64 lanes; 0: never (no such
                                                // LoadBalancer in the graph, or the lane-serial scan is forced)
     GVars *V;
@@ -405,9 +421,12 @@ __device__ inline int64_t lim_wait_ns(const GCtl &c, const GParam &p, GState &s,
 
 // NL: graphs of up to NL nodes keep their nodes' parameters and state in LDS for the launch (the loop's dependent chain goes
 // through them several times per event: 64-cycle LDS round trips instead of L2's) -- `lnodes`: NL x (GParam + GState).
-template <int W, int NL>
+// F: the graph has fault Events.  A graph without any runs the instantiation that holds none of their code (the lone lane's loop is
+// bound by its own instruction count and register allocation: the two tests per event were measurable).
+template <int W, int NL, bool F = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
-    __shared__ unsigned long long s_by_kind[kEvAllKinds];
+    constexpr uint32_t kKinds = F ? kEvAllKinds : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
+    __shared__ unsigned long long s_by_kind[kKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
     GCtl c = c0;
     GVars &V = *c.V;
@@ -422,7 +441,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         c.P = reinterpret_cast<const GParam *>(lnodes);
         c.S = reinterpret_cast<GState *>(lnodes + (size_t)NL * sizeof(GParam));
     }
-    if (lane < (int)kEvAllKinds) s_by_kind[lane] = 0ull;
+    if (lane < (int)kKinds) s_by_kind[lane] = 0ull;
     {   // the heap's head comes into LDS (all 64 lanes copy; 8 bytes per lane and step)
         const long long n8 = (V.heap_len < W ? V.heap_len : (long long)W) * (long long)(sizeof(GEvent) / 8);
         const uint64_t *src = reinterpret_cast<const uint64_t *>(c.heap);
@@ -438,7 +457,8 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
     int sel = -1, sel_node = -1;               // a selection the wavefront made for the LoadBalancer event on top of the heap
     long long cur = V.cur, processed = 0, n_completed = 0, n_received = 0, rec_n = V.rec_n, n_coop = 0;
     long long peak = V.heap_peak;
-    long long polls_pending = V.polls_pending;   // daemon polls in the heap: they do not keep an auto-terminating run alive
+    long long polls_pending = V.polls_pending;   // daemon Events in the heap: they do not keep an auto-terminating run alive
+    long long n_cancelled = 0;
     if (lane == 0) {
         if (!V.booted) {
             // Simulation.__init__ (core/simulation.py:145-154) + Source.start (load/source.py:120-140): the Sources in list order,
@@ -456,6 +476,18 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 const int64_t t = c.ticks[(size_t)c.P[i].rt_off * (size_t)c.tick_cap];
                 if (t == kInfNs) continue;
                 H.push(mk_pre(t, g++, HS_EV_PROBE_TICK, i, -1));
+            }
+            // then the fault Events (FaultSchedule.start, core/simulation.py:162-169): daemons, in add() order
+            if constexpr (F) {
+                const GFault *faults = V.faults;
+                const long long n_faults = V.n_faults;
+                for (long long i = 0; i < n_faults; ++i) {      // (heap_cap >= n + n_faults: prepare_run)
+                    const GFault f = faults[i];
+                    GEvent fe = mk_pre(f.t, g++, (f.flags & 1u) ? kEvFaultOn : kEvFaultOff, f.node, -1);
+                    if (f.flags & 2u) fe.pad |= kPadCancelled;
+                    H.push(fe);
+                    polls_pending += 1;
+                }
             }
             V.global_counter = g; V.booted = 1; G = 0; V.cur = c.start_ns;
         }
@@ -506,7 +538,8 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 const GEvent top = H.get(0);
                 if (top.kind == HS_EV_LB && top.t >= cur) {
                     const GParam &tp = c.P[top.node];
-                    if (tp.sub >= HS_LB_LEAST_CONNECTIONS && tp.rt_cnt >= c.coop_min) { want = top.node; break; }
+                    // (a crashed LoadBalancer makes no selection: its Event is dropped below)
+                    if (tp.sub >= HS_LB_LEAST_CONNECTIONS && tp.rt_cnt >= c.coop_min && !(F && tp.crashed)) { want = top.node; break; }
                 }
             }
             if (H.len > peak) peak = H.len;
@@ -518,15 +551,38 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 const GEvent nx = H.get(0);
                 if (nx.t == e.t && ((nx.pad ^ e.pad) & 1u)) { status |= kUndecided; break; }
             }
+            if constexpr (F) {
+                if (e.kind >= kEvFaultOn && e.kind < kEvAllKinds) {                // a daemon leaves the heap; a cancelled one is skipped
+                    polls_pending -= 1;                                            // before anything else (core/simulation.py:475-477)
+                    if (e.pad & kPadCancelled) { n_cancelled++; continue; }
+                }
+            }
             if (e.t < cur) continue;                                               // time-travel drop, core/simulation.py:480-489
             cur = e.t;
             processed++;
             const int n = e.node;
             const int64_t t = e.t;
-            if (e.kind >= kEvAllKinds) { status |= kBadKind; break; }
+            if (e.kind >= kKinds) { status |= kBadKind; break; }
             s_by_kind[e.kind] += 1ull;
             const GParam p = c.P[n];
             GState &s = c.S[n];
+            if constexpr (F) {
+                if (p.crashed && ((kDropKinds >> e.kind) & 1u)) {
+                    // Event.invoke returns [] (core/event.py:261-262): no handler, no completion hooks, nothing constructed.  A
+                    // Source's or Probe's one pending tick ends there for good, a limiter keeps _poll_scheduled without a poll.
+                    if (e.kind == kEvLimPoll) polls_pending -= 1;
+                    if (e.req >= 0) { c.reqs[e.req].next = req_free; req_free = e.req; }
+                    continue;
+                }
+                if (e.kind >= kEvFaultOn) {
+                    // crash / restart, pause / resume (faults/node_faults.py:46-62,103-109): a flag, not a count.  The row may be the
+                    // launch's LDS copy: the byte goes to its place in HBM as well, nothing else of a row is ever written.
+                    const uint8_t v = e.kind == kEvFaultOn ? 1 : 0;
+                    const_cast<GParam *>(c.P)[n].crashed = v;
+                    if (nodes_in_lds) const_cast<GParam *>(c0.P)[n].crashed = v;
+                    continue;
+                }
+            }
             switch (e.kind) {
             case HS_EV_SOURCE: {
                 // Source.handle_event (load/source.py:142-180): the payload is constructed first, then the next SourceEvent;
@@ -815,6 +871,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         V.req_free = req_free; V.req_len = req_len;
         V.completed += n_completed; V.received += n_received;
         V.heap_peak = peak; V.polls_pending = polls_pending;
+        if constexpr (F) {
+            for (int k = 0; k < 4; ++k) V.internal_by_kind[k] += (long long)s_by_kind[HS_EV_KINDS + k];
+            V.faults_cancelled += n_cancelled;
+        }
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
@@ -838,21 +898,37 @@ __global__ void __launch_bounds__(64) hs_graph_run(GCtl c) {
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
     graph_loop<kLdsHeap, kLdsNodes>(c, lheap, lnodes);
 }
+__global__ void __launch_bounds__(64) hs_graph_run_faults(GCtl c) {           // ... of a graph with fault Events
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true>(c, lheap, lnodes);
+}
 
 // Independent graphs -- the replicas / sweep points of parallel/runner.py:82-142 -- side by side: one workgroup (one heap) each, one
 // with a quarter of the lone run's LDS window (32 KB + 6 KB of nodes: four workgroups per CU, 1 024 heaps on the device at once; a heap that outgrows
 // the window continues in HBM as it does behind the large one -- the window's size changes nothing the loop computes).
-__global__ void __launch_bounds__(64) hs_graph_run_batch(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch>(c, lheap, lnodes);
+__device__ __forceinline__ void batch_report(const GCtl &c, long long *stat) {
     __syncthreads();
     if (threadIdx.x == 0) {                    // what the host decides on, in ONE array for the whole batch
         long long *o = stat + kBatchStat * blockIdx.x;
         o[0] = c.V->status; o[1] = c.V->processed; o[2] = c.V->heap_len;
         o[3] = c.V->heap_len > 0 ? c.heap[0].t : 0;                // (the earliest pending event: hs_graph_run_parts elects across parts)
     }
+}
+__global__ void __launch_bounds__(64) hs_graph_run_batch(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
+// ... of a batch in which at least one handle has fault Events (a handle without any computes the same either way)
+__global__ void __launch_bounds__(64) hs_graph_run_batch_faults(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true>(c, lheap, lnodes);
+    batch_report(c, stat);
 }
 
 }  // namespace graph
@@ -868,6 +944,7 @@ struct hs_graph {
     std::vector<GParam> params;
     std::vector<int32_t> sched_node; std::vector<int64_t> sched_t;
     int32_t *d_sched_node = nullptr; int64_t *d_sched_t = nullptr; long long d_sched_cap = 0;
+    std::vector<GFault> faults; GFault *d_faults = nullptr;   // hs_graph_add_fault, in call order; on the device with the first run
     int32_t *d_rt_targets = nullptr;
     int32_t *d_key_table = nullptr;
     std::vector<int32_t> key_table;            // host image of d_key_table (hs_graph_set_lb_weights appends a WeightedRoundRobin's new table)
@@ -959,7 +1036,7 @@ void hs_graph_destroy(hs_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *bufs[] = {g->ctl.heap, g->ctl.reqs, g->ctl.rec_node, g->ctl.rec_t, g->ctl.rec_cr, (void *)g->ctl.P, g->ctl.S,
                     g->d_rt_targets, g->d_key_table, (void *)g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
-                    g->d_tick_status, g->ctl.lim_ring};
+                    g->d_tick_status, g->ctl.lim_ring, g->d_faults};
     for (void *b : bufs) if (b && !in_slab(g, b)) (void)hipFree(b);
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
     if (g->ev_a) (void)hipEventDestroy(g->ev_a);
@@ -1425,6 +1502,42 @@ int32_t hs_lb_ip_hash_select(const char *key, int32_t n_backends) {
     return hs::wrr::ip_hash_select(key, strlen(key), n_backends);
 }
 
+int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, int32_t cancelled) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "add_fault: node %d out of range", node);
+    if (g->ran || g->launches > 0 || g->d_faults) return fail(g, HS_E_STATE, "add_fault: fault Events are constructed before the first run");
+    if (g->faults.size() >= (size_t)1 << 24) return fail(g, HS_E_OVERFLOW, "more than 2^24 fault Events");
+    g->faults.push_back(GFault{time_ns, node, (on ? 1u : 0u) | (cancelled ? 2u : 0u)});
+    return HS_OK;
+}
+
+int hs_graph_get_faults(hs_graph *g, uint8_t *crashed, int64_t *internal_by_kind, int64_t *cancelled) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (crashed) {
+        std::vector<GParam> P((size_t)g->n);
+        HS_HIP(g, hipMemcpy(P.data(), g->ctl.P, (size_t)g->n * sizeof(GParam), hipMemcpyDeviceToHost));
+        for (int i = 0; i < g->n; ++i) crashed[i] = P[(size_t)i].crashed;
+    }
+    GVars v;
+    HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+    if (internal_by_kind) {
+        for (int k = 0; k < 4; ++k) internal_by_kind[k] = v.internal_by_kind[k];
+        if (g->faults.empty()) {
+            // A graph without fault Events: its own loop does not count the internal kinds, the batch loop of a launch it shares with
+            // a graph that has some does -- so the device's counts are not taken.  Nothing is ever dropped there: a limiter's Events
+            // are exactly the ones its two handlers counted.
+            for (int k = 0; k < 4; ++k) internal_by_kind[k] = 0;
+            std::vector<GState> S((size_t)g->n);
+            HS_HIP(g, hipMemcpy(S.data(), g->ctl.S, (size_t)g->n * sizeof(GState), hipMemcpyDeviceToHost));
+            for (int i = 0; i < g->n; ++i)
+                if (g->params[(size_t)i].kind == HS_NODE_RATE_LIMITER) { internal_by_kind[0] += S[(size_t)i].a; internal_by_kind[1] += S[(size_t)i].d; }
+        }
+    }
+    if (cancelled) *cancelled = v.faults_cancelled;
+    return HS_OK;
+}
+
 int hs_graph_schedule(hs_graph *g, int32_t node, int64_t time_ns) {
     if (!g) return fail(g, HS_E_INVALID, "null handle");
     if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "schedule: node %d out of range", node);
@@ -1501,6 +1614,20 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         if (end_ns - g->cfg.start_ns > 64 * minute) table_h = std::max<int64_t>(g->tick_horizon, g->cfg.start_ns + minute);
         const int rc = build_tables(g, table_h);
         if (rc) return rc;
+    }
+    if (!g->faults.empty() && !g->d_faults) {              // the fault Events: read once, by the launch that boots the heap
+        const long long need = (long long)g->n + (long long)g->faults.size() + 16;
+        if (c.heap_cap < need) {
+            const int rc = grow(g, &c.heap, 0, need);
+            if (rc) return rc;
+            c.heap_cap = need;
+        }
+        HS_HIP(g, hipMalloc(&g->d_faults, g->faults.size() * sizeof(GFault)));
+        HS_HIP(g, hipMemcpy(g->d_faults, g->faults.data(), g->faults.size() * sizeof(GFault), hipMemcpyHostToDevice));
+        const GFault *df = g->d_faults;
+        const long long nf = (long long)g->faults.size();
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, faults), &df, sizeof df, hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, n_faults), &nf, sizeof nf, hipMemcpyHostToDevice));
     }
     const long long ns = (long long)g->sched_node.size();
     if (ns > g->d_sched_cap) {
@@ -1592,7 +1719,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
         HS_HIP(g, hipGetLastError());
         HS_HIP(g, hipStreamSynchronize(g->stream));
         const int rc = after_launch(g, &done);
@@ -1640,7 +1768,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
             h_ctl.back().part = part;              // (the handles themselves never keep part semantics: no early return can leave it set)
         }
         if ((he = hipMemcpy(d_ctl, h_ctl.data(), h_ctl.size() * sizeof(GCtl), hipMemcpyHostToDevice)) != hipSuccess) break;
-        hipLaunchKernelGGL(hs_graph_run_batch, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_faults = false;
+        for (int i : pending) any_faults |= !gs[i]->faults.empty();
+        if (!any_faults) hipLaunchKernelGGL(hs_graph_run_batch, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else hipLaunchKernelGGL(hs_graph_run_batch_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         if ((he = hipGetLastError()) != hipSuccess) break;
         if ((he = hipStreamSynchronize(g0->stream)) != hipSuccess) break;
         h_stat.resize((size_t)kBatchStat * pending.size());
@@ -1703,7 +1834,8 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count;
-        hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, one);
+        if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, one);
+        else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, one);
         HS_HIP(g0, hipGetLastError());
         HS_HIP(g0, hipStreamSynchronize(g->stream));
         bool done = false;

@@ -160,6 +160,18 @@ class GraphEngine:
     def schedule(self, node: int, time_ns: int) -> None:
         self._check(self._lib.hs_graph_schedule(self._h, int(node), int(time_ns)))
 
+    def add_fault(self, node: int, time_ns: int, on: bool, cancelled: bool = False) -> None:
+        """hs_graph_add_fault: one fault Event (set / clear the crashed flag of `node`), numbered in call order."""
+        self._check(self._lib.hs_graph_add_fault(self._h, int(node), int(time_ns), int(bool(on)), int(bool(cancelled))))
+
+    def faults(self):
+        """hs_graph_get_faults: (crashed flag per node, the four internal kinds' event counts -- limiter Requests, limiter polls,
+        fault set, fault clear --, cancelled fault Events popped)."""
+        crashed, internal = np.zeros(self.arrays.n, np.uint8), np.zeros(4, np.int64)
+        cancelled = C.c_int64(0)
+        self._check(self._lib.hs_graph_get_faults(self._h, _ptr(crashed), _ptr(internal), C.byref(cancelled)))
+        return crashed, internal, int(cancelled.value)
+
     def run_until(self, end_ns: int) -> None:
         self._check(self._lib.hs_graph_run_until(self._h, int(end_ns)))
 
@@ -565,6 +577,15 @@ class PartRun:
                 else:
                     out[k][ids] = v
         return out
+
+    def faults(self):
+        crashed, internal, cancelled = np.zeros(self.arrays.n, np.uint8), np.zeros(4, np.int64), 0
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            c, p, k = e.faults()
+            crashed[ids] = c
+            internal += p
+            cancelled += k
+        return crashed, internal, cancelled
 
     def records(self):
         node, t, cr = [], [], []

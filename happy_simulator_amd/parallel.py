@@ -269,6 +269,7 @@ class SimulationPartition:
     entities: list = field(default_factory=list)
     sources: list = field(default_factory=list)
     probes: list = field(default_factory=list)
+    fault_schedule: Any = None           # parallel/partition.py:37 -- refused by ParallelSimulation: faults run on the single heap
 
 
 @dataclass
@@ -428,6 +429,11 @@ class ParallelSimulation:
         self._links = list(links or [])
         self._window_size = window_size
         self._validate(partitions, self._links, window_size)
+        for p in partitions:
+            if p.fault_schedule is not None:
+                from .lowering import UnsupportedTopology
+                raise UnsupportedTopology(f"partition '{p.name}': a fault schedule on a ParallelSimulation partition is not lowered "
+                                          "(node faults run on the single-heap loop: pass it to a Simulation)")
         self._partitions = partitions
         self._seed = seed
         self._device = device

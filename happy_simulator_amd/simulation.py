@@ -15,6 +15,7 @@ from .engine import StationEngine
 from .graph_engine import (DEFAULT_MAX_EVENTS, MAX_PARTS, GeneralGraph, GraphEngine, PartRun, keyless_hazard, lower_general, split_parts,
                            write_back_general)
 from .entities import Entity, Server
+from .faults import FaultSchedule
 from .lowering import (LazyRecords, LbGraph, LoweredGraph, UnsupportedTopology, attach_lb_probes, attach_probes, find_load_balancer, lower,
                        plain_probe_arrays, write_back_plain_probes,
                        lower_lb, write_back, write_back_lb, write_back_plain, write_back_probes, write_back_shared_sink_probes)
@@ -52,8 +53,12 @@ class Simulation:
         self._probes = list(probes or [])
         if trace_recorder is not None:
             raise UnsupportedTopology("trace recorders force the reference's slow loop; profile with rocprofv3 instead")
-        if fault_schedule is not None:
-            raise UnsupportedTopology("fault schedules are not lowered")
+        # FaultSchedule.start (core/simulation.py:162-169): the fault Events come into being HERE, behind the Sources' and the
+        # Probes' first Events -- names resolve now (KeyError), a handle cancelled from now on cancels them
+        self._fault_schedule = fault_schedule
+        if fault_schedule is not None and not isinstance(fault_schedule, FaultSchedule):
+            raise UnsupportedTopology(f"fault schedule {type(fault_schedule).__name__} is not a lowered FaultSchedule")
+        self._faults = fault_schedule._start(self) if fault_schedule is not None else []
         self._seed = _DEFAULT_SEED if seed is None else int(seed)
         self._device = device
         # engine capacities (records per station log / in-flight messages per station / messages per exchange row); None =
@@ -120,6 +125,10 @@ class Simulation:
         return self._summary
 
     def lowered(self) -> "LoweredGraph | LbGraph | GeneralGraph":
+        if self._graph is None and self._faults:
+            # node faults run where every Event is popped one by one: the single-heap loop
+            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._station_refusal = "the station, network and pipeline engines do not lower fault schedules"
         if self._graph is None:
             plain = plain_chains(self._sources, self._entities)      # (n plain chains: no LoadBalancer among them, one pass less)
             if plain is not None:
@@ -312,8 +321,10 @@ class Simulation:
         #  interval, two constant Sources of one rate in different components then look like a mixed timestamp group: undecided)
         # an auto-terminating run with limiters ends when no PRIMARY event is pending anywhere (their polls are daemons,
         # core/simulation.py:311-322): a part cannot know that of the others, so such a run stays on one heap
-        daemons = auto and bool((g.arrays.kind == N.NODE_RATE_LIMITER).any())
-        parts = None if cancelled_ns or daemons else split_parts(g.arrays, MAX_PARTS)
+        daemons = auto and bool((g.arrays.kind == N.NODE_RATE_LIMITER).any() or self._faults)
+        faults = self._general_faults(g)
+        # (a cancelled fault Event stays in its heap, as in the reference's: it is no candidate for the one Event beyond the end)
+        parts = None if cancelled_ns or daemons or any(c for _n, _t, _on, c in faults) else split_parts(g.arrays, MAX_PARTS)
         try:
             self._refuse_long_run(1 if parts is None else len(parts))
         except UnsupportedTopology:
@@ -334,6 +345,8 @@ class Simulation:
                 for p, (ids, _pos, b) in enumerate(parts):
                     engines.append(GraphEngine(b, seed=self._seed, start_ns=start_ns, device=self._device, max_events=self._max_graph_events,
                                                record_capacity=4096))
+                for node, t, on, cancelled in faults:              # (a fault Event lives in the part of the entity it names)
+                    engines[int(part_of[node])].add_fault(int(local[node]), t, on, cancelled)
                 for node, t in sched:                              # (call order: each part keeps the order of its own)
                     engines[int(part_of[node])].schedule(int(local[node]), t)
                 run = PartRun(g.arrays, parts, engines)
@@ -397,12 +410,18 @@ class Simulation:
         eng = GraphEngine(g.arrays, seed=self._seed, start_ns=start_ns, device=self._device, max_events=self._max_graph_events,
                           record_capacity=record_capacity)
         try:
+            for node, t, on, cancelled in self._general_faults(g):
+                eng.add_fault(node, t, on, cancelled)
             for node, t in sched:
                 eng.schedule(node, t)
         except BaseException:
             eng.close()
             raise
         return eng
+
+    def _general_faults(self, g: GeneralGraph) -> list[tuple[int, int, bool, bool]]:
+        """The fault Events as (node, ns, on, cancelled by now), in the order Simulation.__init__ constructed them."""
+        return [(g.node_of[id(ent)], ev.time.nanoseconds, on, ev.cancelled) for ent, ev, on in self._faults]
 
     def _general_finish(self, g: GeneralGraph, eng: GraphEngine, end_ns: int, cancelled_ns, wall_s: float) -> SimulationSummary:
         """The run's results off the engine onto the user's objects (the engine may have run alone or in a batch)."""
@@ -412,6 +431,13 @@ class Simulation:
         write_back_general(g, stats, *rec, device=self._device)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
+        if self._faults:
+            crashed, internal, popped_cancelled = eng.faults()
+            self._internal_by_kind = internal                      # (limiter Requests, limiter polls, fault set, fault clear)
+            self._fault_events_processed = int(internal[2] + internal[3])
+            self._events_cancelled += popped_cancelled
+            for ent, _ev, _on in self._faults:                     # the flag every named entity is left with (faults/node_faults.py:46-62)
+                ent._crashed = bool(crashed[g.node_of[id(ent)]])
         self._engine_summary = es
         self._events_processed = es.events_processed
         self._current_time = Instant(es.final_time_ns)

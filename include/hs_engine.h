@@ -874,6 +874,22 @@ typedef struct hs_limiter_state {
  * hs_graph_read_records with node = the limiter, t = the time, created = hs_limiter_outcome. */
 int hs_graph_get_limiter(hs_graph *g, int32_t node, hs_limiter_state *out, int64_t *log, int64_t log_cap);
 typedef enum hs_limiter_outcome { HS_LIMITER_FORWARDED = 0, HS_LIMITER_QUEUED = 1, HS_LIMITER_DROPPED = 2, HS_LIMITER_DRAINED = 3 } hs_limiter_outcome;
+/* Node faults: CrashNode / PauseNode of a FaultSchedule (faults/node_faults.py, faults/schedule.py:68-100).  One call per fault
+ * Event, in the order FaultSchedule.start constructs them (add() order, crash before restart): at `time_ns` (absolute) the
+ * `_crashed` flag of `node` is set (`on` != 0) or cleared.  The Events are daemon pre-run Events: they take the next values of the
+ * process-wide counter behind the Sources' and Probes' first ticks and before every hs_graph_schedule entry, count in
+ * hs_summary.events_processed (not in events_by_kind: two more internal kinds) and do not keep a run to end_ns = 2^61 alive.
+ * While a node's flag is set, every Event aimed at the entity itself is popped, counted and dropped (core/event.py:261): SOURCE,
+ * PROBE_TICK, ENQUEUE, SINK, LINK, ROUTE, LB, LB_RESP and a limiter's two kinds -- its Request returns to the pool, no completion
+ * hook runs; NOTIFY / POLL / DELIVER / WORK / PROBE and the two continuations are not (other targets; ProcessContinuation.invoke
+ * does not look).  `cancelled` != 0: the Event was cancelled after its construction; it keeps its counter value, is popped, skipped
+ * and not processed.  Before the first run (HS_E_STATE afterwards). */
+int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, int32_t cancelled);
+/* After a run: crashed[n_nodes] = every node's flag as the run left it; internal_by_kind[4] = the graph's Events of the four
+ * internal kinds, counted like events_by_kind counts the public ones (an Event dropped at a crashed target included): a limiter's
+ * Requests, its polls, fault Events that set a flag, fault Events that clear one -- events_processed == sum(events_by_kind) +
+ * sum(internal_by_kind); *cancelled = cancelled fault Events popped.  Any of the three may be NULL. */
+int hs_graph_get_faults(hs_graph *g, uint8_t *crashed, int64_t *internal_by_kind, int64_t *cancelled);
 /* Auto-termination (core/simulation.py:306-322, end_time = Infinity): a run to end_ns = 2^61 ends in front of a pop when only daemon
  * events -- the limiters' polls -- are pending.  A run with any other end processes polls like any event. */
 /* Debug / tests only (no engine path calls it; the null stream, its own allocations): FixedWindowPolicy._get_window_start on the device, one (now_ns, window_s) pair per thread: out_div[i] = Python's float
