@@ -273,7 +273,7 @@ void launch_wave(hs_engine *h, int64_t end_ns) {
     if (fresh)
         hipLaunchKernelGGL((hs_station_wave<NW, true>), dim3(nb), dim3(NW * 64), 0, h->stream, h->P, h->X, h->L, h->tot, h->cands, h->wide_ctl,
                            h->wide_bail, h->wave_parts, n, end_ns, h->flags, h->cfg.start_ns);
-    else
+    else    // (wide_lanes() needs `fresh`: also this one only ever starts at ak0 = 1, sk0 = 0 -- its `ds` and `!da` branches are unreachable from here)
         hipLaunchKernelGGL((hs_station_wave<NW, false>), dim3(nb), dim3(NW * 64), 0, h->stream, h->P, h->X, h->L, h->tot, h->cands, h->wide_ctl,
                            h->wide_bail, h->wave_parts, n, end_ns, h->flags, h->cfg.start_ns);
     hipLaunchKernelGGL(hs_station_wide_finish, dim3(1), dim3(kBlock), 0, h->stream, h->P, h->X, h->L, h->tot, h->cands, nb, h->wide_ctl,

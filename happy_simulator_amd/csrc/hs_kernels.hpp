@@ -526,8 +526,13 @@ __global__ void __launch_bounds__(PC ? 2 * kBlock : kBlock) hs_station_run(Stati
                 S.svc_lambda = __ddiv_rn(1.0, P.svc_mean[lp]);
                 S.prof_kind = kProfConstant;
                 S.init_streams(P.seed[lp], P.stream_base[lp], X.arr_k[lp], X.svc_k[lp], ring_a, ring_s);
-                wants_a = P.src_kind[lp] == 1 && X.A[lp] != kInfNs;
-                wants_s = P.svc_kind[lp] == 0;
+                // An LP the election left inside a group (q != 0) is not in the request-order loop of this launch: its consumer lane
+                // finishes the group in event order while this wavefront runs, drawing through slots 0, 1 of the same two columns.
+                // Values are addressed by draw index here and from slot 0 there, so a refill would overwrite a value between that
+                // lane's push and pop: nothing is produced for such an LP.
+                const bool in_loop = (X.q[lp] >> 16) == 0;
+                wants_a = in_loop && P.src_kind[lp] == 1 && X.A[lp] != kInfNs;
+                wants_s = in_loop && P.svc_kind[lp] == 0;
                 // (a stream nobody draws from keeps its count at zero: the first pass refills every wanted stream before it publishes)
                 const uint32_t back_a = wants_a ? (uint32_t)(S.arr_k % (uint64_t)kRefill) : 0u;
                 const uint32_t back_s = wants_s ? (uint32_t)(S.svc_k % (uint64_t)kRefill) : 0u;

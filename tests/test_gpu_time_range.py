@@ -31,6 +31,8 @@ from oracle import hs_oracle as O
 
 import helpers as H
 from test_gpu_ring import _check_against_oracle as check_ring
+# hs_engine.hip wide_lanes for a fresh uniform grid: shared with tests/test_gpu_wide.py and tests/test_gpu_uniform_kernels_oracle.py
+from uniform_cases import device_lanes as _device_lanes, expected_uniform_kernel as _expected_uniform_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -131,28 +133,6 @@ def test_uniform_grid_at_offset(n, start, end, kernel, lanes, f64):
     assert path & KERNELS == kernel, hex(path)
     assert _lanes(path) == lanes, hex(path)
     assert bool(path & N.RUN_F64_TIMES) == f64, hex(path)
-
-
-def _device_lanes():
-    import torch
-
-    return torch.cuda.get_device_properties(0).multi_processor_count * 4 * 64
-
-
-def _expected_uniform_kernel(n, horizon, lanes, f64):
-    """hs_engine.hip wide_lanes for a fresh uniform grid: (kernel bit, lanes per LP or LPs per workgroup)."""
-    if not f64:
-        return ONE, 0
-    wave_ok = horizon < (1 << 39)
-    if wave_ok and n * 16 <= lanes:
-        return WAVE, 8
-    if wave_ok and n * 3 <= lanes * 2:
-        return WAVE, 16
-    if n * 16 <= lanes:
-        return WIDE, 8
-    if n * 4 <= lanes:
-        return WIDE, 4
-    return UNI, 0
 
 
 def test_uniform_grid_windows_across_2_39_and_2_51():

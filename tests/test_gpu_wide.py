@@ -9,6 +9,7 @@ import hashlib
 import numpy as np
 import pytest
 
+import uniform_cases as U
 from oracle import hs_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -29,8 +30,11 @@ def _run(n, end_ns, flags, seed=42, rate=8.0, mean=0.1, second_end=None, start_n
     with StationEngine(st, mode=N.MODE_SINGLE, horizon_ns=second_end or end_ns, seed=seed, start_ns=start_ns) as eng:
         eng.set_debug_flags(flags)
         eng.run_until(end_ns)
+        # the kernel the flags ask for is the kernel that ran: otherwise the file compares the one-lane kernel with itself
+        U.check_path(eng.run_path(), flags, n, second_end or end_ns, True, f"n {n} end {end_ns}")
         if second_end:
             eng.run_until(second_end)        # (not fresh any more: the one-lane kernel continues from the state the first left)
+            U.check_path(eng.run_path(), flags, n, second_end, False, f"n {n} second end {second_end}")
         s = eng.summary()
         out = {"tot_events": s.events_processed, "tot_final": s.final_time_ns, "tot_completed": s.requests_completed,
                "tot_sink_records": s.sink_records, "by_kind": s.events_by_kind.copy()}
@@ -44,6 +48,19 @@ def _same(a, b, what):
     assert a.keys() == b.keys()
     for k in a:
         np.testing.assert_array_equal(np.asarray(a[k]), np.asarray(b[k]), err_msg=f"{what}: {k}")
+
+
+def _same_or_verdict(got, ref, what, n, end, kw):
+    """_same; when the two kernels differ, the oracle says which of them left it, and in which fields."""
+    try:
+        _same(got, ref, what)
+    except AssertionError as e:
+        ends = (end, kw["second_end"]) if kw["second_end"] else (end,)
+        want = U.oracle_outputs(n, U.oracle_run(n, kw["rate"], kw["mean"], ends, kw["start_ns"], kw["seed"]))
+        v = U.verdict(U.from_run(got), "the run that began on the kernel under test", U.from_run(ref), "the run on the one-lane kernel", want)
+        if kw["second_end"]:
+            v += "  (the second window of BOTH runs is the one-lane kernel)"
+        raise AssertionError(f"{e}\nORACLE: {v}") from None
 
 
 @pytest.mark.parametrize("n,end_s", [(1, 5.0), (7, 3.0), (64, 10.0), (300, 2.5), (4096, 6.0), (8192, 60.0), (32768, 12.0), (43000, 5.0)])
@@ -141,5 +158,6 @@ def test_wave_kernel_on_random_uniform_grids():
         kw = dict(seed=seed, rate=rate, mean=mean, second_end=second, start_ns=start)
         ref = _run(n, end, ONE_LANE, **kw)
         for k in (64, 65):
-            _same(_run(n, end, _force(k), **kw), ref, f"case {case}: n {n} end {end} K {k} {kw}")
-        _same(_run(n, end, _force(64) | (1 << 29), **kw), ref, f"case {case} (reset kernel + the loading instantiation): n {n} end {end} {kw}")
+            _same_or_verdict(_run(n, end, _force(k), **kw), ref, f"case {case}: n {n} end {end} K {k} {kw}", n, end, kw)
+        _same_or_verdict(_run(n, end, _force(64) | (1 << 29), **kw), ref,
+                         f"case {case} (reset kernel + the loading instantiation): n {n} end {end} {kw}", n, end, kw)
