@@ -36,6 +36,7 @@ GRAPH_DEBUG_LANE_SERIAL, GRAPH_DEBUG_COOPERATIVE = 1, 2     # hs_debug_graph_fla
 GRAPH_COOP_MIN_BACKENDS = 32                                # csrc/hs_graph.hip kCoopMinBackends (tests/test_lb_strategies_host.py compares)
 NODE_SOURCE, NODE_SERVER, NODE_SINK, NODE_LINK, NODE_ROUTER, NODE_PROBE, NODE_LB = 0, 1, 2, 3, 4, 5, 6
 NODE_RATE_LIMITER = 7
+NODE_HEALTH_CHECKER = 8
 # hs_limiter_policy / hs_limiter_outcome (the third column of a limiter's records)
 LIMITER_TOKEN_BUCKET, LIMITER_LEAKY_BUCKET, LIMITER_SLIDING_WINDOW, LIMITER_FIXED_WINDOW, LIMITER_NONE = 0, 1, 2, 3, 255
 LIMITER_FORWARDED, LIMITER_QUEUED, LIMITER_DROPPED, LIMITER_DRAINED = 0, 1, 2, 3
@@ -486,6 +487,14 @@ def lib():
     L.hs_graph_add_fault.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
     L.hs_graph_get_faults.restype = C.c_int
     L.hs_graph_get_faults.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64)]
+    L.hs_graph_set_health_checker.restype = C.c_int
+    L.hs_graph_set_health_checker.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32]
+    L.hs_graph_set_lb_health.restype = C.c_int
+    L.hs_graph_set_lb_health.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+    L.hs_graph_get_health.restype = C.c_int
+    L.hs_graph_get_health.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hs_graph_get_lb_current_weights.restype = C.c_int64
+    L.hs_graph_get_lb_current_weights.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
     L.hs_graph_coop_selects.restype = C.c_int64
     L.hs_graph_coop_selects.argtypes = [C.c_void_p]
     L.hs_debug_graph_flags.restype = C.c_int
@@ -546,4 +555,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_set_lb_weights", "hs_graph_coop_selects", "hs_debug_graph_flags", "hs_lb_set_weights", "hs_lb_wrr_table", "hs_lb_ip_hash_select",
     "hs_graph_set_limiter_policy", "hs_graph_get_limiter", "hs_debug_window_start",
     "hs_graph_add_fault", "hs_graph_get_faults",
+    "hs_graph_set_health_checker", "hs_graph_set_lb_health", "hs_graph_get_health", "hs_graph_get_lb_current_weights",
 )

@@ -68,6 +68,8 @@ struct GParam {                                // 64 bytes, read-only
     int32_t conc;                              // Server: max_concurrent; Source: n_clients of its ClientKeyEventProvider (0: none);
                                                // LoadBalancer: entries of its client -> backend-slot table (lim = its offset);
                                                // WeightedRoundRobin: the total weight W = entries of its selection table (lim = its offset)
+                                               // HealthChecker: mean = interval, lat_min = timeout (seconds), conc = healthy_threshold,
+                                               // lim = unhealthy_threshold, sub = _is_running, target = its LoadBalancer
     int32_t rt_off, rt_cnt;                    // router / LoadBalancer: its targets; Source / Probe: rt_off = row of its tick table (-1: none)
     uint8_t kind, sub;                         // sub: Source arrival kind (hs_source_kind); Server / link latency kind; Probe metric; LB strategy
     uint8_t crashed;                           // entity._crashed (faults/node_faults.py:46-62): the one byte of a row a run writes -- kFaultOn / kFaultOff
@@ -86,6 +88,9 @@ struct GState {                                // 64 bytes
     // LoadBalancer: a = requests_received, b = requests_forwarded, c = requests_failed (= no_backend_available), d = in flight,
     //               svc_draws = RoundRobin._index (ConsistentHash / IPHash: their fallback's, the key-less Requests; WeightedRoundRobin:
     //               its selections);  Source: svc_draws = KEY draws
+    //               a graph with health state (GCtl::health): qlen = healthy_count, qhead / qtail = backends_marked_unhealthy / _healthy
+    // HealthChecker: a = checks_performed, b = checks_passed, c = checks_failed (= checks_timed_out), d = _next_check_id,
+    //                qlen = backends_marked_healthy, active = backends_marked_unhealthy
     int64_t a, b, c, d;
     double total_service;                      // Server._total_service_time
     uint64_t svc_draws;
@@ -109,15 +114,31 @@ constexpr uint32_t kEvLimRequest = HS_EV_KINDS, kEvLimPoll = HS_EV_KINDS + 1;
 // CrashNode / PauseNode (faults/node_faults.py): the two daemon Events of a node fault, two more internal kinds.  GEvent::node is the
 // entity whose flag they set / clear; GEvent::pad bit 1: the Event was cancelled before the run (popped and skipped,
 // core/simulation.py:475-477).  They count in events_processed and per graph (GVars::faults_processed), not in events_by_kind.
-constexpr uint32_t kEvFaultOn = HS_EV_KINDS + 2, kEvFaultOff = HS_EV_KINDS + 3, kEvAllKinds = HS_EV_KINDS + 4;
+constexpr uint32_t kEvFaultOn = HS_EV_KINDS + 2, kEvFaultOff = HS_EV_KINDS + 3;
+// HealthChecker (components/load_balancer/health_check.py:253-444): its three handlers, three more internal kinds, aimed at the checker
+// itself.  GEvent::node is the checker; a response / timeout carries the backend's slot in its LoadBalancer as req = -2 - slot (negative:
+// no Request) and the check id in GEvent::pad above the two flag bits.  They count in events_processed and per graph
+// (GVars::health_by_kind), not in events_by_kind.
+constexpr uint32_t kEvHcCycle = HS_EV_KINDS + 4, kEvHcResp = HS_EV_KINDS + 5, kEvHcTimeout = HS_EV_KINDS + 6, kEvAllKinds = HS_EV_KINDS + 7;
 constexpr uint32_t kPadPre = 1u, kPadCancelled = 2u;
+constexpr int kPadIdShift = 2;                 // a check id in GEvent::pad (its low 30 bits: only the one pending id of a backend and ids
+                                               // at most one timeout older are ever compared)
 // Event.invoke drops an Event whose TARGET has `_crashed` set (core/event.py:261); ProcessContinuation.invoke (:465) does not look.
 // These kinds are aimed at the entity itself; NOTIFY / POLL / DELIVER / WORK / PROBE go to its driver, queue, worker adapter or the
 // probe's callback, the two continuations resume a generator: never dropped.
 constexpr uint32_t kDropKinds = (1u << HS_EV_SOURCE) | (1u << HS_EV_PROBE_TICK) | (1u << HS_EV_ENQUEUE) | (1u << HS_EV_SINK) | (1u << HS_EV_LINK) |
-                                (1u << HS_EV_ROUTE) | (1u << HS_EV_LB) | (1u << HS_EV_LB_RESP) | (1u << kEvLimRequest) | (1u << kEvLimPoll);
+                                (1u << HS_EV_ROUTE) | (1u << HS_EV_LB) | (1u << HS_EV_LB_RESP) | (1u << kEvLimRequest) | (1u << kEvLimPoll) |
+                                (1u << kEvHcCycle) | (1u << kEvHcResp) | (1u << kEvHcTimeout);
 static_assert(kEvAllKinds <= 32, "kDropKinds is one word");
 struct GFault { int64_t t; int32_t node; uint32_t flags; };   // hs_graph_add_fault: flags bit 0 = on, bit 1 = cancelled
+// HealthChecker._backend_states / _pending_checks of one backend, at its slot of the LoadBalancer's targets (one checker per LoadBalancer)
+struct GHc {                                   // 32 bytes
+    int64_t succ, fail;                        // consecutive_successes / consecutive_failures
+    int64_t last_time;                         // last_check_time (has_time)
+    int32_t pending;                           // _pending_checks[backend.name] (0: none; ids count from 1)
+    int8_t is_checking, last_passed, has_time;        // last_check_passed: -1 = None
+    int8_t wrr_seen;                           // WeightedRoundRobin._current_weights has an entry for the backend: it was in a list select() saw
+};
 constexpr int kLimPollScheduled = 1, kLimHasTime = 2;   // GState::active of a limiter: _poll_scheduled; _last_*_time / _current_window_start is set
 constexpr long long kMaxSlidingLog = 1ll << 20;          // SlidingWindowPolicy.max_requests the ring is sized for
 
@@ -142,6 +163,7 @@ struct GVars {                                 // device scalars
     long long internal_by_kind[4];             // the four internal kinds as events_by_kind counts the public ones (hs_graph_get_faults)
     long long faults_cancelled;                // cancelled fault Events popped
     const GFault *faults; long long n_faults;  // the fault Events in the order FaultSchedule.start constructed them: read once, at boot
+    long long health_by_kind[3];               // the checkers' cycle / response / timeout Events (hs_graph_get_health)
 };
 
 struct GCtl {                                  // kernel argument
@@ -167,6 +189,13 @@ struct GCtl {                                  // kernel argument
     int64_t start_ns, end_ns;
     long long budget;
     int part;                                  // 1: this heap holds PART of a Simulation (hs_graph_run_parts)
+    // Backend health (LoadBalancer.mark_unhealthy / mark_healthy, load_balancer.py:244-297): only a graph with a HealthChecker or a
+    // backend marked unhealthy before the run has these (health = 1); every array is indexed like rt_targets
+    int health;
+    uint8_t *hl_flag;                          // BackendInfo.is_healthy of every backend slot
+    int32_t *hl_list;                          // per LoadBalancer at its rt_off: its healthy slots, ascending (= `healthy_backends`); GState::qlen of them
+    long long *wrr_cur;                        // WeightedRoundRobin._current_weights of every backend slot (they persist while a backend is out)
+    GHc *hc;                                   // the checker's state of every backend slot
 };
 
 __device__ __forceinline__ bool ev_lt(const GEvent &a, const GEvent &b) {   // Event.__lt__, core/event.py:337-344
@@ -419,13 +448,41 @@ __device__ inline int64_t lim_wait_ns(const GCtl &c, const GParam &p, GState &s,
     return wait == 0 ? 1 : wait;
 }
 
+// LoadBalancer.mark_healthy / mark_unhealthy (load_balancer.py:244-297) of backend `slot`: the flag, the mark counter and the list of
+// healthy slots, kept ascending (marks are rare, selections are not).  A plain method call in the reference: it takes effect whatever
+// the LoadBalancer's own `_crashed` flag says.  Returns false when the backend was in that state already.
+__device__ inline bool lb_mark(const GCtl &c, int lb, int slot, bool healthy) {
+    const GParam &lp = c.P[lb];
+    GState &ls = c.S[lb];
+    uint8_t &flag = c.hl_flag[lp.rt_off + slot];
+    if ((flag != 0) == healthy) return false;
+    flag = healthy ? 1 : 0;
+    int32_t *hl = c.hl_list + lp.rt_off;
+    int nh = ls.qlen;
+    if (healthy) {
+        int i = nh;
+        while (i > 0 && hl[i - 1] > slot) { hl[i] = hl[i - 1]; --i; }
+        hl[i] = slot;
+        ls.qlen = nh + 1; ls.qtail += 1;
+    } else {
+        int i = 0;
+        while (i < nh && hl[i] != slot) ++i;
+        for (; i + 1 < nh; ++i) hl[i] = hl[i + 1];
+        ls.qlen = nh - 1; ls.qhead += 1;
+    }
+    return true;
+}
+
 // NL: graphs of up to NL nodes keep their nodes' parameters and state in LDS for the launch (the loop's dependent chain goes
 // through them several times per event: 64-cycle LDS round trips instead of L2's) -- `lnodes`: NL x (GParam + GState).
 // F: the graph has fault Events.  A graph without any runs the instantiation that holds none of their code (the lone lane's loop is
 // bound by its own instruction count and register allocation: the two tests per event were measurable).
-template <int W, int NL, bool F = false>
+// HC: the graph (or one of a batch) has a HealthChecker or an unhealthy backend -- a third instantiation, so that the two above keep
+// their code: the fault-only loop is as sensitive to what it carries as the plain one.  HC implies F.
+template <int W, int NL, bool F = false, bool HC = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
-    constexpr uint32_t kKinds = F ? kEvAllKinds : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
+    static_assert(F || !HC, "the health instantiation carries the fault code");
+    constexpr uint32_t kKinds = HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
     __shared__ unsigned long long s_by_kind[kKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
     GCtl c = c0;
@@ -494,6 +551,15 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         // Simulation.schedule (core/simulation.py:195-206): Events constructed outside the run
         while (status == kRunning && V.sched_done < c.n_sched) {
             if (H.len + 1 > c.heap_cap) { status |= kGrowHeap; break; }
+            if constexpr (HC) {
+                // HealthChecker.start() (health_check.py:201-216): the first _health_check_cycle Event, no Request
+                const int hn = c.sched_node[V.sched_done];
+                if (c.P[hn].kind == HS_NODE_HEALTH_CHECKER) {
+                    H.push(mk_pre(c.sched_t[V.sched_done], V.global_counter++, kEvHcCycle, hn, -1));
+                    V.sched_done++;
+                    continue;
+                }
+            }
             int r = req_free;
             if (r >= 0) req_free = c.reqs[r].next;
             else if (req_len < c.req_cap) r = req_len++;
@@ -534,12 +600,29 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     }
                 }
             }
+            if constexpr (HC) {
+                const GEvent top = H.get(0);
+                if (top.kind == kEvHcCycle && top.t >= cur) {                      // a cycle constructs two Events and one Request per backend
+                    const long long nb = c.P[c.P[top.node].target].rt_cnt;
+                    if (H.len + 2 * nb + 1 > c.heap_cap) { status |= kGrowHeap; break; }
+                    long long room = (long long)c.req_cap - (long long)req_len;    // never-used entries, then as much of the free list as it takes
+                    for (int r = req_free; r >= 0 && room < nb; r = c.reqs[r].next) room += 1;
+                    if (room < nb) { status |= kGrowReq; break; }
+                }
+            }
             if (c.coop_min > 0 && sel < 0) {                                       // (a graph without such a LoadBalancer: one uniform test)
                 const GEvent top = H.get(0);
                 if (top.kind == HS_EV_LB && top.t >= cur) {
                     const GParam &tp = c.P[top.node];
                     // (a crashed LoadBalancer makes no selection: its Event is dropped below)
-                    if (tp.sub >= HS_LB_LEAST_CONNECTIONS && tp.rt_cnt >= c.coop_min && !(F && tp.crashed)) { want = top.node; break; }
+                    bool coop = tp.sub >= HS_LB_LEAST_CONNECTIONS && tp.rt_cnt >= c.coop_min;
+                    if constexpr (HC) {
+                        // ... over the healthy list; the live WeightedRoundRobin adds, takes the first maximum and subtracts the same way.
+                        // Every test that could stop the loop in front of this Event has passed above and passes again unchanged
+                        // behind the hand-over, so the selection the wavefront makes (and, for WeightedRoundRobin, applies) is consumed.
+                        if (c.health) coop = (tp.sub >= HS_LB_LEAST_CONNECTIONS || tp.sub == HS_LB_WEIGHTED_ROUND_ROBIN) && c.S[top.node].qlen >= c.coop_min;
+                    }
+                    if (coop && !(F && tp.crashed)) { want = top.node; break; }
                 }
             }
             if (H.len > peak) peak = H.len;
@@ -552,7 +635,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if (nx.t == e.t && ((nx.pad ^ e.pad) & 1u)) { status |= kUndecided; break; }
             }
             if constexpr (F) {
-                if (e.kind >= kEvFaultOn && e.kind < kEvAllKinds) {                // a daemon leaves the heap; a cancelled one is skipped
+                if (e.kind >= kEvFaultOn && e.kind < kEvHcCycle) {                 // a daemon leaves the heap; a cancelled one is skipped
                     polls_pending -= 1;                                            // before anything else (core/simulation.py:475-477)
                     if (e.pad & kPadCancelled) { n_cancelled++; continue; }
                 }
@@ -574,12 +657,61 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     if (e.req >= 0) { c.reqs[e.req].next = req_free; req_free = e.req; }
                     continue;
                 }
-                if (e.kind >= kEvFaultOn) {
+                if (e.kind >= kEvFaultOn && (!HC || e.kind < kEvHcCycle)) {
                     // crash / restart, pause / resume (faults/node_faults.py:46-62,103-109): a flag, not a count.  The row may be the
                     // launch's LDS copy: the byte goes to its place in HBM as well, nothing else of a row is ever written.
                     const uint8_t v = e.kind == kEvFaultOn ? 1 : 0;
                     const_cast<GParam *>(c.P)[n].crashed = v;
                     if (nodes_in_lds) const_cast<GParam *>(c0.P)[n].crashed = v;
+                    continue;
+                }
+            }
+            if constexpr (HC) {
+                if (e.kind == kEvHcCycle) {
+                    // HealthChecker._run_check_cycle / _check_backend (health_check.py:253-349): per backend of `all_backends` that is not
+                    // being checked the probe -- a Request of the backend in every respect -- and its timeout, then the next cycle
+                    if (!p.sub) continue;                                           // `if not self._is_running: return []`
+                    const GParam &lp = c.P[p.target];
+                    for (int q = 0; q < lp.rt_cnt; ++q) {
+                        GHc &h = c.hc[lp.rt_off + q];
+                        if (h.is_checking) continue;
+                        h.is_checking = 1; h.last_time = t; h.has_time = 1;
+                        s.d += 1;                                                   // _next_check_id
+                        const int64_t id = s.d;
+                        h.pending = (int32_t)id;
+                        s.a += 1;
+                        int r = req_free;
+                        if (r >= 0) req_free = c.reqs[r].next; else r = req_len++;  // (room: tested in front of the pop)
+                        const unsigned long long idx_p = G++;
+                        GRequest rq; rq.created = t; rq.idx = idx_p; rq.service_s = 0.0; rq.client = (id << 32) | (int64_t)q; rq.next = -1; rq.hook = n; rq.pre = 0;
+                        c.reqs[r] = rq;
+                        const int be = c.rt_targets[lp.rt_off + q];
+                        H.push(mk(t, idx_p, arrival_kind(c.P, be), be, r));
+                        GEvent te = mk(t + ns_from_seconds(p.lat_min), G++, kEvHcTimeout, n, -2 - q);
+                        te.pad = (uint32_t)id << kPadIdShift;
+                        H.push(te);
+                    }
+                    H.push(mk(t + ns_from_seconds(p.mean), G++, kEvHcCycle, n, -1));  // self.now + Duration.from_seconds(interval)
+                    continue;
+                }
+                if (e.kind > kEvHcCycle) {
+                    // _handle_response / _handle_timeout (health_check.py:351-444)
+                    const int q = -2 - e.req;
+                    const GParam &lp = c.P[p.target];
+                    GHc &h = c.hc[lp.rt_off + q];
+                    if (h.pending == 0 || ((uint32_t)h.pending << kPadIdShift) != (e.pad & ~3u)) continue;   // stale: a processed no-op
+                    h.pending = 0;
+                    h.is_checking = 0;
+                    const bool healthy = c.hl_flag[lp.rt_off + q] != 0;
+                    if (e.kind == kEvHcResp) {
+                        h.last_passed = 1; h.succ += 1; h.fail = 0;
+                        s.b += 1;
+                        if (!healthy && h.succ >= (int64_t)p.conc) { lb_mark(c, p.target, q, true); s.qlen += 1; }
+                    } else {
+                        h.last_passed = 0; h.fail += 1; h.succ = 0;
+                        s.c += 1;
+                        if (healthy && h.fail >= p.lim) { lb_mark(c, p.target, q, false); s.active += 1; }
+                    }
                     continue;
                 }
             }
@@ -612,6 +744,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 // QueuedResource.handle_event -> Queue._handle_enqueue (components/queue.py:122-147)
                 const int hook = c.reqs[e.req].hook;                               // Event.on_complete of THIS Event: one-shot (core/event.py:290-311)
                 c.reqs[e.req].hook = -1;
+                int64_t probe_tag = -1;                                            // a health probe: (check id << 32) | backend slot rode in `client`
+                if constexpr (HC) {
+                    if (hook >= 0 && c.P[hook].kind == HS_NODE_HEALTH_CHECKER) { probe_tag = c.reqs[e.req].client; c.reqs[e.req].client = -1; }
+                }
                 if (p.lim >= 0 && s.qlen >= p.lim) {                               // FIFOQueue.push refuses (queue_policy.py:94-98)
                     s.b += 1;
                     c.reqs[e.req].next = req_free; req_free = e.req;
@@ -628,7 +764,12 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 }
                 // Event.invoke (core/event.py:277-283): the handler returned a plain list, so the completion hooks run now, behind
                 // the handler's own events: the LoadBalancer's `_lb_response`
-                if (hook >= 0) H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
+                if (HC && probe_tag >= 0) {
+                    // ... or the checker's _health_check_response (health_check.py:321-334): a probe the queue refused passes as well
+                    GEvent re = mk(t, G++, kEvHcResp, hook, -2 - (int)(probe_tag & 0xffffffffll));
+                    re.pad = (uint32_t)(probe_tag >> 32) << kPadIdShift;
+                    H.push(re);
+                } else if (hook >= 0) H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
             } break;
             case HS_EV_NOTIFY:                                                      // QueueDriver._handle_notify (queue_driver.py:92-99)
                 if (s.active < p.conc) H.push(mk(t, G++, HS_EV_POLL, n, -1));
@@ -715,16 +856,62 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 else { c.reqs[e.req].next = req_free; req_free = e.req; }
                 break;
             case HS_EV_LB: {
-                // LoadBalancer._forward_request (load_balancer.py:347-433), every backend healthy
+                // LoadBalancer._forward_request (load_balancer.py:347-433); without health state every backend is healthy
                 s.a += 1;                                                           // :349
-                if (p.rt_cnt == 0) {                                                // no healthy backends, :352-366
+                int slot = 0;
+                bool picked = false;
+                if constexpr (HC) {
+                    // `backends = self.healthy_backends`: the registration order, filtered (the three hashed / random strategies are
+                    // refused over a changing list: with health state their backends all stay healthy, the tables below hold)
+                    if (c.health && (p.sub == HS_LB_ROUND_ROBIN || p.sub == HS_LB_WEIGHTED_ROUND_ROBIN || p.sub >= HS_LB_LEAST_CONNECTIONS)) {
+                        const int nh = s.qlen;
+                        if (nh == 0) {                                              // :352-366
+                            s.c += 1;
+                            c.reqs[e.req].next = req_free; req_free = e.req;
+                            break;
+                        }
+                        const int32_t *hl = c.hl_list + p.rt_off;
+                        if (p.sub == HS_LB_ROUND_ROBIN) {
+                            slot = hl[(int)(s.svc_draws % (uint64_t)nh)];          // healthy[_index % len(healthy)]
+                            s.svc_draws += 1;
+                        } else if (sel >= 0 && sel_node == n) {                    // (the wavefront took it, below)
+                            slot = sel; n_coop++;
+                            if (p.sub == HS_LB_WEIGHTED_ROUND_ROBIN) s.svc_draws += 1;
+                        } else if (p.sub == HS_LB_WEIGHTED_ROUND_ROBIN) {
+                            // the live smooth weighted round robin (strategies.py:111-134): every healthy backend's current weight grows
+                            // by its weight, the first maximum in list order is taken and loses the healthy total
+                            long long total = 0, best = 0;
+                            for (int q = 0; q < nh; ++q) {
+                                const int sl = hl[q];
+                                const long long w = c.lb_w[p.rt_off + sl];
+                                const long long cw = c.wrr_cur[p.rt_off + sl] + w;
+                                c.wrr_cur[p.rt_off + sl] = cw;
+                                c.hc[p.rt_off + sl].wrr_seen = 1;
+                                total += w;
+                                if (q == 0 || cw > best) { best = cw; slot = sl; }
+                            }
+                            c.wrr_cur[p.rt_off + slot] = best - total;
+                            s.svc_draws += 1;
+                        } else {
+                            slot = hl[0];
+                            double best = lb_score(c, p, slot);
+                            for (int q = 1; q < nh; ++q) {
+                                const double sc = lb_score(c, p, hl[q]);
+                                if (sc < best) { best = sc; slot = hl[q]; }
+                            }
+                        }
+                        sel = -1;
+                        picked = true;
+                    }
+                }
+                if (!picked && p.rt_cnt == 0) {                                     // no healthy backends, :352-366
                     s.c += 1;
                     c.reqs[e.req].next = req_free; req_free = e.req;
                     break;
                 }
                 const int64_t client = c.reqs[e.req].client;
-                int slot = 0;
-                if (p.sub == HS_LB_CONSISTENT_HASH || p.sub == HS_LB_IP_HASH) {
+                if (picked) {
+                } else if (p.sub == HS_LB_CONSISTENT_HASH || p.sub == HS_LB_IP_HASH) {
                     if (client >= 0 && client < (int64_t)p.conc) slot = c.key_table[p.lim + client];   // .select(str(client_id)): a table
                     else {                                                          // no key: `self._fallback.select(...)`, a RoundRobin of
                         slot = (int)(s.svc_draws % (uint64_t)p.rt_cnt);             // the strategy's own (strategies.py:309,326-328,362,420-421)
@@ -850,6 +1037,51 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         // minimum), then a butterfly over the lanes keeps the smaller (score, slot) pair -- the first minimum in add_backend order.  The
         // nodes' state is the lone lane's, visible behind the barrier (LDS, or HBM written by this very wavefront).
         const GParam wp = c.P[wn];
+        bool taken = false;
+        if constexpr (HC) {
+            if (c.health) {
+                // ... over the LoadBalancer's healthy list (ascending slots: a lane's first extremum is its smallest slot, and the smaller
+                // slot wins a tie across lanes -- the first one in list order)
+                const int nh = c.S[wn].qlen;
+                const int32_t *hl = c.hl_list + wp.rt_off;
+                int bslot = 0x7fffffff;
+                if (wp.sub == HS_LB_WEIGHTED_ROUND_ROBIN) {
+                    long long best = INT64_MIN, total = 0;
+                    for (int q = lane; q < nh; q += 64) {
+                        const int sl = hl[q];
+                        const long long w = c.lb_w[wp.rt_off + sl];
+                        const long long cw = c.wrr_cur[wp.rt_off + sl] + w;
+                        c.wrr_cur[wp.rt_off + sl] = cw;
+                        c.hc[wp.rt_off + sl].wrr_seen = 1;
+                        total += w;
+                        if (cw > best) { best = cw; bslot = sl; }
+                    }
+                    for (int m = 32; m >= 1; m >>= 1) {
+                        const long long ob = __shfl_xor(best, m, 64), ot = __shfl_xor(total, m, 64);
+                        const int os = __shfl_xor(bslot, m, 64);
+                        total += ot;
+                        if (ob > best || (ob == best && os < bslot)) { best = ob; bslot = os; }
+                    }
+                    __syncthreads();                                               // (every lane's store before the winner's)
+                    if (lane == 0) c.wrr_cur[wp.rt_off + bslot] = best - total;
+                } else {
+                    double best = __longlong_as_double(0x7ff0000000000000ll);
+                    for (int q = lane; q < nh; q += 64) {
+                        const int sl = hl[q];
+                        const double sc = lb_score(c, wp, sl);
+                        if (sc < best) { best = sc; bslot = sl; }
+                    }
+                    for (int m = 32; m >= 1; m >>= 1) {
+                        const double ob = __shfl_xor(best, m, 64);
+                        const int os = __shfl_xor(bslot, m, 64);
+                        if (ob < best || (ob == best && os < bslot)) { best = ob; bslot = os; }
+                    }
+                }
+                sel = bslot; sel_node = wn;
+                taken = true;
+            }
+        }
+        if (!taken) {
         double best = __longlong_as_double(0x7ff0000000000000ll);
         int bslot = 0x7fffffff;
         for (int q = lane; q < wp.rt_cnt; q += 64) {
@@ -862,6 +1094,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             if (ob < best || (ob == best && os < bslot)) { best = ob; bslot = os; }
         }
         sel = bslot; sel_node = wn;
+        }
       }
       __syncthreads();
     }
@@ -874,6 +1107,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         if constexpr (F) {
             for (int k = 0; k < 4; ++k) V.internal_by_kind[k] += (long long)s_by_kind[HS_EV_KINDS + k];
             V.faults_cancelled += n_cancelled;
+        }
+        if constexpr (HC) {
+            for (int k = 0; k < 3; ++k) V.health_by_kind[k] += (long long)s_by_kind[kEvHcCycle + k];
         }
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
@@ -904,6 +1140,12 @@ __global__ void __launch_bounds__(64) hs_graph_run_faults(GCtl c) {           //
     graph_loop<kLdsHeap, kLdsNodes, true>(c, lheap, lnodes);
 }
 
+__global__ void __launch_bounds__(64) hs_graph_run_health(GCtl c) {           // ... with a HealthChecker or an unhealthy backend
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true, true>(c, lheap, lnodes);
+}
+
 // Independent graphs -- the replicas / sweep points of parallel/runner.py:82-142 -- side by side: one workgroup (one heap) each, one
 // with a quarter of the lone run's LDS window (32 KB + 6 KB of nodes: four workgroups per CU, 1 024 heaps on the device at once; a heap that outgrows
 // the window continues in HBM as it does behind the large one -- the window's size changes nothing the loop computes).
@@ -928,6 +1170,14 @@ __global__ void __launch_bounds__(64) hs_graph_run_batch_faults(const GCtl *cs, 
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
     const GCtl c = cs[blockIdx.x];
     graph_loop<kLdsHeapBatch, kLdsNodesBatch, true>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
+// ... of a batch in which at least one handle has health state
+__global__ void __launch_bounds__(64) hs_graph_run_batch_health(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true>(c, lheap, lnodes);
     batch_report(c, stat);
 }
 
@@ -955,6 +1205,14 @@ struct hs_graph {
     std::vector<GState> state_cache; bool state_cache_valid = false;   // hs_graph_get_limiter: one copy of the nodes' state per run
     std::vector<int64_t> ring_cache;           // ... and of ctl.lim_ring
     bool has_least_loaded = false;             // a LeastConnections / WeightedLeastConnections LoadBalancer among the nodes
+    // backend health: hs_graph_set_health_checker / hs_graph_set_lb_health make the graph one with health state (the third instantiation
+    // of the loop); the device arrays come with the first run, in one allocation
+    bool health = false, has_wrr = false;
+    int n_checkers = 0;                        // HS_NODE_HEALTH_CHECKER nodes: every one is configured before a run
+    std::vector<uint8_t> hl_flag;              // [n_rt] the initial BackendInfo.is_healthy of every backend slot
+    std::vector<int32_t> checker_of;           // [n] the configured checker of a LoadBalancer node (-1: none)
+    std::vector<uint8_t> checker_set;          // [n] hs_graph_set_health_checker has been called for the node
+    char *d_health = nullptr;
     int debug_flags = 0;                       // hs_debug_graph_flags
     // tick tables: one row per time-varying Source and per distinct Probe interval, computed up to `tick_horizon`
     std::vector<hs::TickRow> rows;
@@ -1036,7 +1294,7 @@ void hs_graph_destroy(hs_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *bufs[] = {g->ctl.heap, g->ctl.reqs, g->ctl.rec_node, g->ctl.rec_t, g->ctl.rec_cr, (void *)g->ctl.P, g->ctl.S,
                     g->d_rt_targets, g->d_key_table, (void *)g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
-                    g->d_tick_status, g->ctl.lim_ring, g->d_faults};
+                    g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health};
     for (void *b : bufs) if (b && !in_slab(g, b)) (void)hipFree(b);
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
     if (g->ev_a) (void)hipEventDestroy(g->ev_a);
@@ -1059,6 +1317,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     if (cfg->device < 0 || cfg->device >= dev_count) return fail(nullptr, HS_E_INVALID, "device %d out of range", cfg->device);
     if (cfg->start_ns < 0)        // (the Sinks' merged records hold non-negative times)
         return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
+    bool has_wrr = false;
     auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER; };
     int64_t kmax = 0;                                  // client ids any Source hands out: [0, kmax)
     for (int i = 0; i < n; ++i)
@@ -1219,6 +1478,12 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
                 for (int q = 0; q < p.rt_cnt; ++q) key_table.push_back(q);
             }
             if (p.sub >= HS_LB_LEAST_CONNECTIONS) has_ll = true;
+            if (p.sub == HS_LB_WEIGHTED_ROUND_ROBIN) has_wrr = true;
+        } break;
+        case HS_NODE_HEALTH_CHECKER: {
+            // HealthChecker (health_check.py:83-154); its LoadBalancer and parameters: hs_graph_set_health_checker
+            if (p.target >= 0 && nd->kind[p.target] != HS_NODE_LB) return fail(nullptr, HS_E_INVALID, "node %d: a HealthChecker's target %d is not a LoadBalancer", i, p.target);
+            p.sub = 0; p.conc = 2; p.lim = 3; p.mean = 10.0; p.lat_min = 5.0; p.rt_off = 0; p.rt_cnt = 0;
         } break;
         case HS_NODE_RATE_LIMITER: {
             if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a RateLimitedEntity needs a downstream", i);
@@ -1231,13 +1496,16 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     }
     hs_graph *g = new hs_graph();
     g->cfg = *cfg; g->n = n; g->n_rt = nd->n_rt; g->params = P; g->rows = rows; g->row_rate = row_rate;
-    g->key_table = key_table; g->has_least_loaded = has_ll;
+    g->key_table = key_table; g->has_least_loaded = has_ll; g->has_wrr = has_wrr;
+    g->hl_flag.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
+    g->checker_of.assign((size_t)n, -1); g->checker_set.assign((size_t)n, 0);
     g->lb_w.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
     {
         hs_limiter_policy_params none{};
         none.struct_size = sizeof none; none.policy = HS_LIMITER_NONE;
         g->lim_policy.assign((size_t)n, none);
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_RATE_LIMITER) g->n_limiters++;
+        for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_HEALTH_CHECKER) g->n_checkers++;
     }
     for (int i = 0; i < n; ++i) {
         const GParam &p = P[(size_t)i];
@@ -1502,6 +1770,121 @@ int32_t hs_lb_ip_hash_select(const char *key, int32_t n_backends) {
     return hs::wrr::ip_hash_select(key, strlen(key), n_backends);
 }
 
+int hs_graph_set_health_checker(hs_graph *g, int32_t node, int32_t lb_node, double interval_s, double timeout_s, int32_t healthy_threshold,
+                                int32_t unhealthy_threshold, int32_t running) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_HEALTH_CHECKER)
+        return fail(g, HS_E_INVALID, "set_health_checker: node %d is not a HealthChecker", node);
+    if (lb_node < 0 || lb_node >= g->n || g->params[(size_t)lb_node].kind != HS_NODE_LB)
+        return fail(g, HS_E_INVALID, "set_health_checker: node %d is not a LoadBalancer", lb_node);
+    if (g->ran || g->launches > 0 || g->d_health) return fail(g, HS_E_STATE, "set_health_checker: a checker is configured before the first run");
+    if (g->checker_set[(size_t)node]) return fail(g, HS_E_STATE, "set_health_checker: node %d is configured already", node);
+    if (g->checker_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has HealthChecker node %d already: one checker per LoadBalancer is lowered", lb_node,
+                    g->checker_of[(size_t)lb_node]);
+    const uint8_t strat = g->params[(size_t)lb_node].sub;
+    if (strat == HS_LB_CONSISTENT_HASH || strat == HS_LB_IP_HASH || strat == HS_LB_RANDOM)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: strategy %d is not lowered over a changing backend list (under a HealthChecker)", lb_node, (int)strat);
+    // the reference's own checks (health_check.py:109-118)
+    if (!std::isfinite(interval_s) || !(interval_s > 0.0)) return fail(g, HS_E_INVALID, "interval must be > 0, got %g", interval_s);
+    if (!std::isfinite(timeout_s) || !(timeout_s > 0.0)) return fail(g, HS_E_INVALID, "timeout must be > 0, got %g", timeout_s);
+    if (timeout_s >= interval_s) return fail(g, HS_E_INVALID, "timeout (%g) must be < interval (%g)", timeout_s, interval_s);
+    if (healthy_threshold < 1) return fail(g, HS_E_INVALID, "healthy_threshold must be >= 1, got %d", healthy_threshold);
+    if (unhealthy_threshold < 1) return fail(g, HS_E_INVALID, "unhealthy_threshold must be >= 1, got %d", unhealthy_threshold);
+    if (!(interval_s * 1e9 >= 1.0)) return fail(g, HS_E_UNSUPPORTED, "an interval of %g s is below one nanosecond (the cycle would never advance)", interval_s);
+    GParam &p = g->params[(size_t)node];
+    p.target = lb_node; p.mean = interval_s; p.lat_min = timeout_s; p.conc = healthy_threshold; p.lim = unhealthy_threshold; p.sub = running ? 1 : 0;
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    g->checker_of[(size_t)lb_node] = node; g->checker_set[(size_t)node] = 1;
+    g->reach_s = std::max(g->reach_s, interval_s);
+    g->health = true;
+    return HS_OK;
+}
+
+int hs_graph_set_lb_health(hs_graph *g, int32_t node, const uint8_t *healthy, int32_t n) {
+    if (!g || !healthy) return fail(g, HS_E_INVALID, "null argument");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_LB)
+        return fail(g, HS_E_INVALID, "set_lb_health: node %d is not a LoadBalancer", node);
+    if (g->ran || g->launches > 0 || g->d_health) return fail(g, HS_E_STATE, "set_lb_health: the initial health flags are set before the first run");
+    const GParam &p = g->params[(size_t)node];
+    if (n != p.rt_cnt) return fail(g, HS_E_INVALID, "set_lb_health: node %d has %d backends, got %d flags", node, p.rt_cnt, n);
+    bool all = true;
+    for (int q = 0; q < n; ++q) all &= healthy[q] != 0;
+    if (!all && (p.sub == HS_LB_CONSISTENT_HASH || p.sub == HS_LB_IP_HASH || p.sub == HS_LB_RANDOM))
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: strategy %d is not lowered with an unhealthy backend", node, (int)p.sub);
+    for (int q = 0; q < n; ++q) g->hl_flag[(size_t)p.rt_off + (size_t)q] = healthy[q] ? 1 : 0;
+    g->health = true;
+    return HS_OK;
+}
+
+int hs_graph_get_health(hs_graph *g, int32_t node, int64_t *checker_stats, int64_t *backend_states, uint8_t *healthy, int64_t *marks, int64_t *events) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node == -1 && !checker_stats && !backend_states && !healthy && !marks) {          // the graph's event counts alone
+        if (events) {
+            HS_HIP(g, hipSetDevice(g->cfg.device));
+            GVars v;
+            HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+            for (int k = 0; k < 3; ++k) events[k] = v.health_by_kind[k];
+        }
+        return HS_OK;
+    }
+    if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "get_health: node %d out of range", node);
+    const GParam &np = g->params[(size_t)node];
+    if (np.kind != HS_NODE_LB && np.kind != HS_NODE_HEALTH_CHECKER) return fail(g, HS_E_INVALID, "get_health: node %d is neither a LoadBalancer nor a HealthChecker", node);
+    if (np.kind == HS_NODE_HEALTH_CHECKER && !g->checker_set[(size_t)node]) return fail(g, HS_E_STATE, "get_health: HealthChecker node %d was never configured", node);
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    const int lb = np.kind == HS_NODE_LB ? node : np.target;
+    const GParam &lp = g->params[(size_t)lb];
+    GState cs{}, ls{};
+    HS_HIP(g, hipMemcpy(&ls, g->ctl.S + lb, sizeof ls, hipMemcpyDeviceToHost));
+    if (np.kind == HS_NODE_HEALTH_CHECKER) HS_HIP(g, hipMemcpy(&cs, g->ctl.S + node, sizeof cs, hipMemcpyDeviceToHost));
+    if (checker_stats) {                       // HealthCheckStats (health_check.py:44-53) in field order
+        checker_stats[0] = cs.a; checker_stats[1] = cs.b; checker_stats[2] = cs.c; checker_stats[3] = cs.c;
+        checker_stats[4] = cs.qlen; checker_stats[5] = cs.active;
+    }
+    if (backend_states && lp.rt_cnt > 0) {
+        std::vector<GHc> h((size_t)lp.rt_cnt);
+        for (auto &x : h) { x = GHc{}; x.last_passed = -1; }
+        if (g->ctl.hc) HS_HIP(g, hipMemcpy(h.data(), g->ctl.hc + lp.rt_off, h.size() * sizeof(GHc), hipMemcpyDeviceToHost));
+        for (int q = 0; q < lp.rt_cnt; ++q) {
+            int64_t *o = backend_states + 6 * (size_t)q;
+            o[0] = h[(size_t)q].succ; o[1] = h[(size_t)q].fail; o[2] = h[(size_t)q].has_time ? h[(size_t)q].last_time : -1;
+            o[3] = h[(size_t)q].last_passed; o[4] = h[(size_t)q].is_checking; o[5] = h[(size_t)q].pending;
+        }
+    }
+    if (healthy && lp.rt_cnt > 0) {
+        if (g->ctl.hl_flag) HS_HIP(g, hipMemcpy(healthy, g->ctl.hl_flag + lp.rt_off, (size_t)lp.rt_cnt, hipMemcpyDeviceToHost));
+        else std::copy(g->hl_flag.begin() + lp.rt_off, g->hl_flag.begin() + lp.rt_off + lp.rt_cnt, healthy);
+    }
+    if (marks) { marks[0] = g->d_health ? ls.qhead : 0; marks[1] = g->d_health ? ls.qtail : 0; }
+    if (events) {
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 3; ++k) events[k] = v.health_by_kind[k];
+    }
+    return HS_OK;
+}
+
+int64_t hs_graph_get_lb_current_weights(hs_graph *g, int32_t node, int64_t *out, uint8_t *present, int32_t n) {
+    if (!g || !out) return fail(g, HS_E_INVALID, "null argument");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_LB)
+        return fail(g, HS_E_INVALID, "get_lb_current_weights: node %d is not a LoadBalancer", node);
+    const GParam &p = g->params[(size_t)node];
+    if (n != p.rt_cnt) return fail(g, HS_E_INVALID, "get_lb_current_weights: node %d has %d backends, got room for %d", node, p.rt_cnt, n);
+    if (!g->ctl.wrr_cur) return 0;             // (no health state: the periodic table ran, the weights follow from the counts)
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (n > 0) {
+        HS_HIP(g, hipMemcpy(out, g->ctl.wrr_cur + p.rt_off, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (present) {
+            std::vector<GHc> h((size_t)n);
+            HS_HIP(g, hipMemcpy(h.data(), g->ctl.hc + p.rt_off, h.size() * sizeof(GHc), hipMemcpyDeviceToHost));
+            for (int q = 0; q < n; ++q) present[q] = h[(size_t)q].wrr_seen ? 1 : 0;
+        }
+    }
+    return 1;
+}
+
 int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, int32_t cancelled) {
     if (!g) return fail(g, HS_E_INVALID, "null handle");
     if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "add_fault: node %d out of range", node);
@@ -1629,6 +2012,38 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, faults), &df, sizeof df, hipMemcpyHostToDevice));
         HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, n_faults), &nf, sizeof nf, hipMemcpyHostToDevice));
     }
+    if (g->n_checkers > 0 && !g->d_health)
+        for (int i = 0; i < g->n; ++i)
+            if (g->params[(size_t)i].kind == HS_NODE_HEALTH_CHECKER && !g->checker_set[(size_t)i])
+                return fail(g, HS_E_STATE, "node %d: a HealthChecker without its LoadBalancer (hs_graph_set_health_checker comes before the run)", i);
+    if (g->health && !g->d_health) {
+        // health state, once: flags, healthy lists, current weights and the checkers' per-backend state in one allocation; the
+        // LoadBalancers' rows get their healthy count and their two mark counters
+        const size_t nrt = (size_t)(g->n_rt > 0 ? g->n_rt : 1);
+        const size_t o_cur = 0, o_hc = o_cur + nrt * sizeof(long long), o_list = o_hc + nrt * sizeof(GHc), o_flag = o_list + nrt * sizeof(int32_t);
+        std::vector<char> image(o_flag + nrt, 0);
+        GHc *hc0 = reinterpret_cast<GHc *>(image.data() + o_hc);
+        int32_t *list0 = reinterpret_cast<int32_t *>(image.data() + o_list);
+        for (size_t q = 0; q < nrt; ++q) hc0[q].last_passed = -1;
+        std::memcpy(image.data() + o_flag, g->hl_flag.data(), nrt);
+        HS_HIP(g, hipSetDevice(g->cfg.device));
+        HS_HIP(g, hipMalloc((void **)&g->d_health, image.size()));
+        for (int i = 0; i < g->n; ++i) {
+            const GParam &p = g->params[(size_t)i];
+            if (p.kind != HS_NODE_LB) continue;
+            int nh = 0;
+            for (int q = 0; q < p.rt_cnt; ++q) if (g->hl_flag[(size_t)p.rt_off + (size_t)q]) list0[p.rt_off + nh++] = q;
+            GState s0{};
+            s0.qhead = 0; s0.qtail = 0; s0.qlen = nh;
+            HS_HIP(g, hipMemcpy(c.S + i, &s0, sizeof s0, hipMemcpyHostToDevice));
+        }
+        HS_HIP(g, hipMemcpy(g->d_health, image.data(), image.size(), hipMemcpyHostToDevice));
+        c.wrr_cur = reinterpret_cast<long long *>(g->d_health + o_cur);
+        c.hc = reinterpret_cast<GHc *>(g->d_health + o_hc);
+        c.hl_list = reinterpret_cast<int32_t *>(g->d_health + o_list);
+        c.hl_flag = reinterpret_cast<uint8_t *>(g->d_health + o_flag);
+        c.health = 1;
+    }
     const long long ns = (long long)g->sched_node.size();
     if (ns > g->d_sched_cap) {
         if (g->d_sched_node) HS_HIP(g, hipFree(g->d_sched_node));
@@ -1645,7 +2060,7 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
     c.sched_node = g->d_sched_node; c.sched_t = g->d_sched_t; c.n_sched = ns;
     c.end_ns = end_ns;
     c.auto_term = end_ns == (1ll << 61);                   // end_time = Infinity: the limiters' polls are daemons (core/simulation.py:306-322)
-    c.coop_min = !g->has_least_loaded || (g->debug_flags & 1) ? 0 : (g->debug_flags & 2) ? 1 : kCoopMinBackends;
+    c.coop_min = !(g->has_least_loaded || (g->health && g->has_wrr)) || (g->debug_flags & 1) ? 0 : (g->debug_flags & 2) ? 1 : kCoopMinBackends;
     c.coop_reset = 1;                                      // (hs_graph_coop_selects counts the LAST run: zeroed by its first launch)
     g->launches = 0;
     return HS_OK;
@@ -1719,7 +2134,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
         HS_HIP(g, hipGetLastError());
         HS_HIP(g, hipStreamSynchronize(g->stream));
@@ -1768,9 +2184,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
             h_ctl.back().part = part;              // (the handles themselves never keep part semantics: no early return can leave it set)
         }
         if ((he = hipMemcpy(d_ctl, h_ctl.data(), h_ctl.size() * sizeof(GCtl), hipMemcpyHostToDevice)) != hipSuccess) break;
-        bool any_faults = false;
-        for (int i : pending) any_faults |= !gs[i]->faults.empty();
-        if (!any_faults) hipLaunchKernelGGL(hs_graph_run_batch, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_faults = false, any_health = false;
+        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; }
+        if (any_health) hipLaunchKernelGGL(hs_graph_run_batch_health, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else if (!any_faults) hipLaunchKernelGGL(hs_graph_run_batch, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else hipLaunchKernelGGL(hs_graph_run_batch_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         if ((he = hipGetLastError()) != hipSuccess) break;
         if ((he = hipStreamSynchronize(g0->stream)) != hipSuccess) break;
@@ -1834,7 +2251,8 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count;
-        if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, one);
+        if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, one);
+        else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, one);
         else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, one);
         HS_HIP(g0, hipGetLastError());
         HS_HIP(g0, hipStreamSynchronize(g->stream));

@@ -838,7 +838,8 @@ class LoadBalancerStats:
 
 @dataclass
 class BackendInfo:
-    """load_balancer.py:61-80 (health bookkeeping is host-side state the engine never changes)."""
+    """load_balancer.py:61-80.  `is_healthy` is what mark_unhealthy / mark_healthy left, before a run on the host and during one
+    on the device (a HealthChecker's marks); the consecutive counters are host-side bookkeeping the engine does not keep."""
 
     backend: Entity
     weight: int = 1
@@ -852,7 +853,9 @@ class BackendInfo:
 class LoadBalancer(Entity):
     """Distributes requests over backends (components/load_balancer/load_balancer.py:83-473).  Lowered: the ConsistentHash,
     RoundRobin (the default), Random, WeightedRoundRobin, IPHash, LeastConnections and WeightedLeastConnections strategies over Server
-    backends that all stay healthy for the whole run."""
+    backends.  Backends marked unhealthy -- by mark_unhealthy before the run or by a HealthChecker during it -- leave the routing
+    pool (`healthy_backends`: registration order, filtered); that is lowered for RoundRobin, WeightedRoundRobin and the two
+    LeastConnections strategies, on the single-heap loop."""
 
     def __init__(self, name: str, backends: list[Entity] | None = None, strategy=None, on_no_backend: str = "reject"):
         super().__init__(name)
@@ -876,7 +879,25 @@ class LoadBalancer(Entity):
         self._requests_forwarded = 0
         self._requests_failed = 0
         self._no_backend_available = 0
+        self._backends_marked_unhealthy = 0
+        self._backends_marked_healthy = 0
         self._in_flight_count = 0
+
+    def mark_unhealthy(self, backend: Entity) -> None:
+        """load_balancer.py:244-270: out of the routing pool until marked healthy again (an unknown backend: a no-op)."""
+        info = self._backends.get(backend.name)
+        if info is not None and info.is_healthy:
+            info.is_healthy = False
+            info.consecutive_successes = 0
+            self._backends_marked_unhealthy += 1
+
+    def mark_healthy(self, backend: Entity) -> None:
+        """load_balancer.py:272-297."""
+        info = self._backends.get(backend.name)
+        if info is not None and not info.is_healthy:
+            info.is_healthy = True
+            info.consecutive_failures = 0
+            self._backends_marked_healthy += 1
 
     def add_backend(self, backend: Entity, weight: int = 1) -> None:
         if weight < 1:
@@ -899,11 +920,13 @@ class LoadBalancer(Entity):
     def all_backends(self) -> list[Entity]:
         return [i.backend for i in self._backends.values()]
 
-    healthy_backends = all_backends
+    @property
+    def healthy_backends(self) -> list[Entity]:
+        return [i.backend for i in self._backends.values() if i.is_healthy]
 
     @property
     def unhealthy_backends(self) -> list[Entity]:
-        return []
+        return [i.backend for i in self._backends.values() if not i.is_healthy]
 
     @property
     def backend_count(self) -> int:
@@ -911,7 +934,7 @@ class LoadBalancer(Entity):
 
     @property
     def healthy_count(self) -> int:
-        return len(self._backends)
+        return len(self.healthy_backends)
 
     def downstream_entities(self) -> list[Entity]:
         return self.all_backends
@@ -925,7 +948,124 @@ class LoadBalancer(Entity):
     @property
     def stats(self) -> LoadBalancerStats:
         return LoadBalancerStats(self._requests_received, self._requests_forwarded, self._requests_failed,
-                                 self._no_backend_available, 0, 0)
+                                 self._no_backend_available, self._backends_marked_unhealthy, self._backends_marked_healthy)
+
+
+@dataclass(frozen=True)
+class HealthCheckStats:
+    """components/load_balancer/health_check.py:44-53."""
+
+    checks_performed: int = 0
+    checks_passed: int = 0
+    checks_failed: int = 0
+    checks_timed_out: int = 0
+    backends_marked_healthy: int = 0
+    backends_marked_unhealthy: int = 0
+
+
+@dataclass
+class BackendHealthState:
+    """health_check.py:56-64."""
+
+    consecutive_successes: int = 0
+    consecutive_failures: int = 0
+    last_check_time: Instant | None = None
+    last_check_passed: bool | None = None
+    is_checking: bool = False
+
+
+class HealthChecker(Entity):
+    """Periodic health checks of a LoadBalancer's backends (components/load_balancer/health_check.py:67-448).  Every `interval`
+    seconds a probe -- an ordinary Event aimed at the backend, queued and served like a Request -- goes to every backend that is
+    not being checked, with a timeout Event `timeout` seconds later; the probe's completion hook (it fires when the backend's
+    enqueue handler returns) is the response.  `unhealthy_threshold` consecutive timeouts mark a backend unhealthy at the
+    LoadBalancer, `healthy_threshold` consecutive responses mark it healthy again.  The three handlers run on the device
+    (csrc/hs_graph.hip kEvHcCycle / kEvHcResp / kEvHcTimeout); this class carries the parameters in and the statistics and
+    per-backend states back out.  `sim.schedule(checker.start())` begins the cycle, as in the reference."""
+
+    def __init__(self, name: str, load_balancer: LoadBalancer, interval: float = 10.0, timeout: float = 5.0, healthy_threshold: int = 2,
+                 unhealthy_threshold: int = 3, check_event_type: str = "health_check"):
+        super().__init__(name)
+        if interval <= 0:                                                                 # health_check.py:109-118
+            raise ValueError(f"interval must be > 0, got {interval}")
+        if timeout <= 0:
+            raise ValueError(f"timeout must be > 0, got {timeout}")
+        if timeout >= interval:
+            raise ValueError(f"timeout ({timeout}) must be < interval ({interval})")
+        if healthy_threshold < 1:
+            raise ValueError(f"healthy_threshold must be >= 1, got {healthy_threshold}")
+        if unhealthy_threshold < 1:
+            raise ValueError(f"unhealthy_threshold must be >= 1, got {unhealthy_threshold}")
+        self._load_balancer = load_balancer
+        self._interval = interval
+        self._timeout = timeout
+        self._healthy_threshold = healthy_threshold
+        self._unhealthy_threshold = unhealthy_threshold
+        self._check_event_type = check_event_type
+        self._backend_states: dict[str, BackendHealthState] = {}
+        self._pending_checks: dict[str, int] = {}
+        self._next_check_id = 0
+        self._checks_performed = 0
+        self._checks_passed = 0
+        self._checks_failed = 0
+        self._checks_timed_out = 0
+        self._backends_marked_healthy = 0
+        self._backends_marked_unhealthy = 0
+        self._is_running = False
+        self._sim_start: Instant | None = None           # the clock a Simulation hands to its entities: `now` before run() is its start
+        self._events = (0, 0, 0)                         # after a run: its cycle / response / timeout Events processed (dropped ones included)
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._load_balancer]
+
+    @property
+    def stats(self) -> HealthCheckStats:
+        return HealthCheckStats(self._checks_performed, self._checks_passed, self._checks_failed, self._checks_timed_out,
+                                self._backends_marked_healthy, self._backends_marked_unhealthy)
+
+    @property
+    def load_balancer(self) -> LoadBalancer:
+        return self._load_balancer
+
+    @property
+    def interval(self) -> float:
+        return self._interval
+
+    @property
+    def timeout(self) -> float:
+        return self._timeout
+
+    @property
+    def healthy_threshold(self) -> int:
+        return self._healthy_threshold
+
+    @property
+    def unhealthy_threshold(self) -> int:
+        return self._unhealthy_threshold
+
+    @property
+    def is_running(self) -> bool:
+        return self._is_running
+
+    def start(self):
+        """health_check.py:201-216: the first `_health_check_cycle` Event, for `sim.schedule(...)`; its time is the Simulation's
+        start once the checker is one of its entities, Instant.Epoch before."""
+        from .core.event import Event
+
+        self._is_running = True
+        return Event(time=self._sim_start if self._sim_start is not None else Instant.Epoch, event_type="_health_check_cycle",
+                     target=self, context={})
+
+    def stop(self) -> None:
+        self._is_running = False
+
+    def get_backend_state(self, backend: Entity) -> BackendHealthState:
+        if backend.name not in self._backend_states:
+            self._backend_states[backend.name] = BackendHealthState()
+        return self._backend_states[backend.name]
+
+    def get_backend_state_by_name(self, name: str) -> BackendHealthState | None:
+        return self._backend_states.get(name)
 
 
 # ---- rate limiting -------------------------------------------------------------------------------

@@ -22,8 +22,8 @@ import numpy as np
 
 from . import _native as N
 from .core.temporal import Instant
-from .entities import (ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity, ExponentialLatency,
-                       IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random,
+from .entities import (BackendHealthState, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
+                       ExponentialLatency, HealthChecker, IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random,
                        RandomRouter, RateLimitedEntity, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source,
                        TokenBucketPolicy, WeightedLeastConnections, WeightedRoundRobin)
 
@@ -72,6 +72,14 @@ class GraphArrays:
         self.lim_policy = None               # [n] uint8 hs_limiter_policy / [n, 3] float64 / [n] int64: RATE_LIMITER nodes
         self.lim_params = None               #   (hs_limiter_policy_params: p0, p1, p2 and count), set through
         self.lim_count = None                #   hs_graph_set_limiter_policy once the handle exists
+        self.hc_params = None                # [n, 5] float64: HEALTH_CHECKER nodes -- interval, timeout, the two thresholds, _is_running
+                                             #   (their LoadBalancer: `target`), set through hs_graph_set_health_checker
+        self.lb_healthy = None               # [n_rt] uint8: BackendInfo.is_healthy per backend slot when the run begins (None: all healthy
+                                             #   and no checker -- the graph has no health state)
+
+    @property
+    def has_health(self) -> bool:
+        return self.hc_params is not None or self.lb_healthy is not None
 
     def struct(self) -> N.GraphNodes:
         s = N.GraphNodes()
@@ -133,6 +141,44 @@ class GraphEngine:
             except BaseException:
                 self.close()
                 raise
+
+        if arrays.has_health:
+            try:
+                if arrays.lb_healthy is not None:
+                    fl = np.ascontiguousarray(arrays.lb_healthy, np.uint8)
+                    for i in np.nonzero(arrays.kind == N.NODE_LB)[0]:
+                        off, cnt = int(arrays.rt_off[i]), int(arrays.rt_cnt[i])
+                        fi = np.ascontiguousarray(fl[off:off + cnt])
+                        self._check(self._lib.hs_graph_set_lb_health(self._h, int(i), _ptr(fi) if cnt else _ptr(np.zeros(1, np.uint8)), cnt))
+                for i in np.nonzero(arrays.kind == N.NODE_HEALTH_CHECKER)[0]:
+                    iv, to, ht, ut, running = arrays.hc_params[i]
+                    self._check(self._lib.hs_graph_set_health_checker(self._h, int(i), int(arrays.target[i]), float(iv), float(to), int(ht), int(ut),
+                                                                      int(running)))
+            except BaseException:
+                self.close()
+                raise
+
+    def health(self, node: int) -> dict:
+        """hs_graph_get_health of a HealthChecker or LoadBalancer node: checker stats, per-backend states, the LoadBalancer's health
+        flags and mark counts, the graph's three health event counts -- and the live WeightedRoundRobin current weights (None without
+        health state)."""
+        a = self.arrays
+        lb = int(node) if a.kind[node] == N.NODE_LB else int(a.target[node])
+        cnt = int(a.rt_cnt[lb])
+        stats, states, flags = np.zeros(6, np.int64), np.zeros((max(cnt, 1), 6), np.int64), np.ones(max(cnt, 1), np.uint8)
+        marks, events, cur = np.zeros(2, np.int64), np.zeros(3, np.int64), np.zeros(max(cnt, 1), np.int64)
+        self._check(self._lib.hs_graph_get_health(self._h, int(node), _ptr(stats), _ptr(states), _ptr(flags), _ptr(marks), _ptr(events)))
+        seen = np.zeros(max(cnt, 1), np.uint8)
+        live = self._check(self._lib.hs_graph_get_lb_current_weights(self._h, lb, _ptr(cur), _ptr(seen), cnt))
+        # current_weights: {backend slot: weight} of the slots the reference's dict has an entry for (None without health state)
+        return dict(stats=stats, states=states[:cnt], healthy=flags[:cnt], marks=marks, events=events,
+                    current_weights={q: int(cur[q]) for q in range(cnt) if seen[q]} if live else None)
+
+    def health_events(self) -> np.ndarray:
+        """The graph's cycle / response / timeout Events of the run (hs_graph_get_health, node = -1)."""
+        events = np.zeros(3, np.int64)
+        self._check(self._lib.hs_graph_get_health(self._h, -1, None, None, None, None, _ptr(events)))
+        return events
 
     def limiter(self, node: int) -> dict:
         """hs_graph_get_limiter: counters, queue depth, the two event counts and the policy's state of limiter `node`."""
@@ -264,11 +310,13 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             raise UnsupportedTopology(f"probe '{pr.name}' is listed twice")
         add(pr)
     n_front = len(nodes)
-    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity) + _SINKS
+    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker) + _SINKS
 
     def check(ent, where):
         if isinstance(ent, Source):
             raise UnsupportedTopology(f"{where}: a Source takes no Requests")
+        if isinstance(ent, HealthChecker) and where != "entities":
+            raise UnsupportedTopology(f"{where}: the HealthChecker '{ent.name}' takes no Requests")
         if not isinstance(ent, lowered):
             raise UnsupportedTopology(f"{where}: {type(ent).__name__} '{getattr(ent, 'name', ent)}' is not lowered to the engine")
 
@@ -286,7 +334,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
     while k < len(nodes):
         ent = nodes[k]
         k += 1
-        if isinstance(ent, Probe):
+        if isinstance(ent, (Probe, HealthChecker)):             # (a checker's LoadBalancer has to be part of the Simulation by itself)
             continue
         for d in ent.downstream_entities():
             if d is None:
@@ -303,6 +351,8 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
     rt: list[int] = []
     weights: dict[int, list[int]] = {}                        # rt offset -> the weights of a weighted strategy's backends
     policies_seen: dict[int, str] = {}                        # id(policy) -> the limiter that holds it
+    checked: dict[int, str] = {}                              # id(LoadBalancer) -> its HealthChecker
+    unhealthy: dict[int, list[int]] = {}                      # rt offset -> is_healthy of a LoadBalancer's backends, one of them unhealthy
     for i, ent in enumerate(nodes):
         if isinstance(ent, Source):
             ep, prov = ent._event_provider, ent._time_provider
@@ -405,7 +455,33 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
                     raise UnsupportedTopology(f"'{ent.name}': WeightedRoundRobin with a total weight of {sum(ws)} needs a selection table "
                                               "beyond 2^24 entries (not lowered)")
                 weights[len(rt)] = ws
+            flags = [int(ent.get_backend_info(b).is_healthy) for b in backends]
+            if not all(flags):
+                if isinstance(st, (ConsistentHash, IPHash, Random)):
+                    raise UnsupportedTopology(f"'{ent.name}': strategy {type(st).__name__} with an unhealthy backend ('"
+                                              f"{ent.unhealthy_backends[0].name}') is not lowered (its selection over a changing backend list "
+                                              "is a follow-up)")
+                unhealthy[len(rt)] = flags
             rt.extend(node_of[id(b)] for b in backends)
+        elif isinstance(ent, HealthChecker):
+            lb = ent.load_balancer
+            if not isinstance(lb, LoadBalancer) or id(lb) not in node_of:
+                raise UnsupportedTopology(f"health checker '{ent.name}': its LoadBalancer is not an entity of this Simulation")
+            if id(lb) in checked:
+                raise UnsupportedTopology(f"health checker '{ent.name}': LoadBalancer '{lb.name}' has the checker '{checked[id(lb)]}' already "
+                                          "(one HealthChecker per LoadBalancer is lowered)")
+            checked[id(lb)] = ent.name
+            if isinstance(lb.strategy, (ConsistentHash, IPHash, Random)):
+                raise UnsupportedTopology(f"health checker '{ent.name}': strategy {type(lb.strategy).__name__} of '{lb.name}' is not lowered "
+                                          "under a HealthChecker (its selection over a changing backend list is a follow-up: RoundRobin, "
+                                          "WeightedRoundRobin, LeastConnections and WeightedLeastConnections are)")
+            if not (ent.interval * 1e9 >= 1.0):
+                raise UnsupportedTopology(f"health checker '{ent.name}': an interval of {ent.interval} s is below one nanosecond")
+            if a.hc_params is None:
+                a.hc_params = np.zeros((n, 5), np.float64)
+            a.kind[i] = N.NODE_HEALTH_CHECKER
+            a.target[i] = node_of[id(lb)]
+            a.hc_params[i] = (ent.interval, ent.timeout, ent.healthy_threshold, ent.unhealthy_threshold, 1.0 if ent.is_running else 0.0)
         elif isinstance(ent, RateLimitedEntity):
             pol = ent.policy
             if type(pol) not in LIMITER_POLICIES:
@@ -457,6 +533,10 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
         a.lb_weights = np.ones(len(rt), np.int32)
         for off, ws in weights.items():
             a.lb_weights[off:off + len(ws)] = ws
+    if unhealthy or a.hc_params is not None:
+        a.lb_healthy = np.ones(len(rt), np.uint8)
+        for off, flags in unhealthy.items():
+            a.lb_healthy[off:off + len(flags)] = flags
     if a.lb_strategy is not None:
         _check_keys(nodes, node_of, a)
         blobs = [(x.name.encode() if isinstance(x, Server) else b"") for x in nodes]     # (only an LB's backends need their name)
@@ -501,7 +581,7 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
     new_index = np.empty(n, np.int64)
     per_node = [nm for nm in ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s",
                               "link_lat_min_s", "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric",
-                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count")
+                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params")
                 if getattr(a, nm) is not None]
     names = None if a.names is None else [a.names[a.name_off[i]:a.name_off[i + 1]] for i in range(n)]
     parts = []
@@ -523,9 +603,15 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
             b.rt_targets = new_index[rt[pos]].astype(np.int32)
             if a.lb_weights is not None:
                 b.lb_weights = np.ascontiguousarray(a.lb_weights[pos])
+            if a.lb_healthy is not None:
+                b.lb_healthy = np.ascontiguousarray(a.lb_healthy[pos])
         else:
             pos = np.zeros(0, np.int64)
             b.rt_targets = np.zeros(0, np.int32)
+        if b.hc_params is not None and not (b.kind == N.NODE_HEALTH_CHECKER).any():
+            b.hc_params = None                                             # (a part without a checker: no health state unless a flag says so)
+        if b.lb_healthy is not None and b.hc_params is None and b.lb_healthy.all():
+            b.lb_healthy = None
         if names is not None:
             blobs = [names[i] for i in ids]
             b.names = b"".join(blobs)
@@ -586,6 +672,16 @@ class PartRun:
             internal += p
             cancelled += k
         return crashed, internal, cancelled
+
+    def health_events(self) -> np.ndarray:
+        return np.sum([e.health_events() for e in self.engines], axis=0).astype(np.int64)
+
+    def health(self, node: int) -> dict:
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            at = np.searchsorted(ids, node)
+            if at < len(ids) and ids[at] == node:
+                return e.health(int(at))
+        raise KeyError(node)
 
     def records(self):
         node, t, cr = [], [], []
@@ -648,9 +744,10 @@ def keyless_hazard(g: "GeneralGraph", target) -> str | None:
     return None
 
 
-def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t: np.ndarray, rec_cr: np.ndarray, device: int = 0) -> None:
+def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t: np.ndarray, rec_cr: np.ndarray, device: int = 0,
+                       health=None) -> None:
     """The run's per-node results onto the user's objects, under the attribute names the reference uses (lowering.write_back's
-    counterpart)."""
+    counterpart).  `health`: node -> GraphEngine.health(node) of a graph with health state."""
     a = g.arrays
     order = np.argsort(rec_node, kind="stable")              # per Sink, still in processing order
     bounds = np.searchsorted(rec_node[order], np.arange(a.n + 1))
@@ -680,6 +777,18 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
             off = int(a.rt_off[i])
             for q, b in enumerate(ent.all_backends):
                 ent._backends[b.name].total_requests = int(stats["rt_taken"][off + q])
+            if health is not None:
+                h = health(i)
+                for q, b in enumerate(ent.all_backends):
+                    ent._backends[b.name].is_healthy = bool(h["healthy"][q])
+                ent._backends_marked_unhealthy += int(h["marks"][0])
+                ent._backends_marked_healthy += int(h["marks"][1])
+                if isinstance(ent.strategy, WeightedRoundRobin) and h["current_weights"] is not None:
+                    # the live algorithm ran (csrc/hs_graph.hip): what it left, for every backend a select() ever saw (strategies.py:117-119)
+                    ent.strategy._selections = selections
+                    ent.strategy._current_weights = {b.name: h["current_weights"][q] for q, b in enumerate(ent.all_backends)
+                                                     if q in h["current_weights"]}
+                    continue
             if isinstance(ent.strategy, WeightedRoundRobin) and ent.all_backends:
                 # what select() leaves in `_current_weights` after t selections of which n_i went to backend i: w_i * t - W * n_i
                 # (strategies.py:125-132; a run starts from a fresh strategy, as every engine run starts from time zero)
@@ -688,6 +797,18 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
                 st._selections = selections
                 st._current_weights = ({b.name: w * selections - sum(ws) * int(stats["rt_taken"][off + q])
                                         for q, (b, w) in enumerate(zip(ent.all_backends, ws))} if selections else {})
+        elif isinstance(ent, HealthChecker):
+            h = health(i)
+            (ent._checks_performed, ent._checks_passed, ent._checks_failed, ent._checks_timed_out, ent._backends_marked_healthy,
+             ent._backends_marked_unhealthy) = (int(v) for v in h["stats"])
+            ent._next_check_id = ent._checks_performed               # one id per check performed (health_check.py:293-297)
+            ent._backend_states, ent._pending_checks = {}, {}
+            for b, (succ, fail, last_ns, passed, checking, pending) in zip(ent.load_balancer.all_backends, h["states"].tolist()):
+                if last_ns < 0:
+                    continue                                          # (never checked: the reference has no entry for it)
+                ent._backend_states[b.name] = BackendHealthState(succ, fail, Instant(last_ns), None if passed < 0 else bool(passed), bool(checking))
+                if pending:
+                    ent._pending_checks[b.name] = pending
         elif isinstance(ent, RateLimitedEntity):
             st = stats["limiters"][i]
             ent._received, ent._forwarded, ent._queued, ent._dropped = (int(st[k]) for k in ("received", "forwarded", "queued", "dropped"))

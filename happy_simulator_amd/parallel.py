@@ -21,7 +21,7 @@ import numpy as np
 from . import _native as N
 from .core.temporal import Instant
 from .engine import StationArrays, StationEngine
-from .entities import Probe
+from .entities import HealthChecker, Probe
 from .graph_engine import GeneralGraph, GraphEngine
 from .lowering import UnsupportedTopology, write_back, write_back_probes
 from .simulation import Simulation, entity_summaries
@@ -431,9 +431,12 @@ class ParallelSimulation:
         self._validate(partitions, self._links, window_size)
         for p in partitions:
             if p.fault_schedule is not None:
-                from .lowering import UnsupportedTopology
                 raise UnsupportedTopology(f"partition '{p.name}': a fault schedule on a ParallelSimulation partition is not lowered "
                                           "(node faults run on the single-heap loop: pass it to a Simulation)")
+            for ent in p.entities:
+                if isinstance(ent, HealthChecker):
+                    raise UnsupportedTopology(f"partition '{p.name}': the HealthChecker '{ent.name}' on a ParallelSimulation partition is not "
+                                              "lowered (health checks run on the single-heap loop: pass it to a Simulation)")
         self._partitions = partitions
         self._seed = seed
         self._device = device

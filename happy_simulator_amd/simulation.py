@@ -14,7 +14,7 @@ from .core.temporal import Instant
 from .engine import StationEngine
 from .graph_engine import (DEFAULT_MAX_EVENTS, MAX_PARTS, GeneralGraph, GraphEngine, PartRun, keyless_hazard, lower_general, split_parts,
                            write_back_general)
-from .entities import Entity, Server
+from .entities import Entity, HealthChecker, LoadBalancer, Server
 from .faults import FaultSchedule
 from .lowering import (LazyRecords, LbGraph, LoweredGraph, UnsupportedTopology, attach_lb_probes, attach_probes, find_load_balancer, lower,
                        plain_probe_arrays, write_back_plain_probes,
@@ -59,6 +59,9 @@ class Simulation:
         if fault_schedule is not None and not isinstance(fault_schedule, FaultSchedule):
             raise UnsupportedTopology(f"fault schedule {type(fault_schedule).__name__} is not a lowered FaultSchedule")
         self._faults = fault_schedule._start(self) if fault_schedule is not None else []
+        for ent in self._entities:                 # the clock every listed entity is handed (core/simulation.py:118-135): a
+            if isinstance(ent, HealthChecker):     # checker's start() reads `now` from it
+                ent._sim_start = self._start_time
         self._seed = _DEFAULT_SEED if seed is None else int(seed)
         self._device = device
         # engine capacities (records per station log / in-flight messages per station / messages per exchange row); None =
@@ -124,7 +127,15 @@ class Simulation:
     def summary(self) -> SimulationSummary | None:
         return self._summary
 
+    def _has_health(self) -> bool:
+        """A HealthChecker among the entities, or a LoadBalancer with a backend marked unhealthy: the backend list changes (or is
+        not the full one), which only the single-heap loop follows."""
+        return any(isinstance(e, HealthChecker) or (isinstance(e, LoadBalancer) and e.unhealthy_backends) for e in self._entities)
+
     def lowered(self) -> "LoweredGraph | LbGraph | GeneralGraph":
+        if self._graph is None and not self._faults and self._has_health():
+            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._station_refusal = "the station, network and pipeline engines do not lower health checks or unhealthy backends"
         if self._graph is None and self._faults:
             # node faults run where every Event is popped one by one: the single-heap loop
             self._graph = lower_general(self._sources, self._entities, self._probes)
@@ -214,6 +225,10 @@ class Simulation:
             if self._sources:
                 raise UnsupportedTopology("end_time = Infinity with Sources never terminates (their ticks are primary events, in "
                                           "the reference too); pass end_time/duration")
+            if any(isinstance(e, HealthChecker) and e.is_running for e in self._entities):
+                # the cycle Event is no daemon (health_check.py:266-271): a running checker keeps the primary count above zero for ever
+                raise UnsupportedTopology("end_time = Infinity with a running HealthChecker never terminates (its cycle Events are primary "
+                                          "events, in the reference too); pass end_time/duration")
             if self._probes:
                 # a Probe IS a Source (instrumentation/probe.py:81): its ticks are SourceEvents built with daemon=False
                 # (load/source.py:136,171; load/source_event.py:27) -- only the probe_event samples are daemons -- so they keep
@@ -376,6 +391,9 @@ class Simulation:
         end_ns = self._end_time.nanoseconds if not auto else (1 << 61)
         start_ns = self._start_time.nanoseconds
         a = g.arrays
+        if auto and any(isinstance(e, HealthChecker) and e.is_running for e in g.nodes):
+            raise UnsupportedTopology("end_time = Infinity with a running HealthChecker never terminates (its cycle Events are primary "
+                                      "events, in the reference too); pass end_time/duration")
         # ~8 reference events per Request that is served and ~2 per hop: refuse up front what would take the one lane minutes
         horizon_s = 0.0 if auto else (end_ns - start_ns) / 1e9
         self._general_est = 12.0 * float(a.src_rate[a.kind == N.NODE_SOURCE].sum()) * horizon_s
@@ -386,6 +404,8 @@ class Simulation:
                 cancelled_ns.append(ev.time.nanoseconds)
                 continue
             i = g.node_of.get(id(ev.target))
+            if i is not None and a.kind[i] == N.NODE_HEALTH_CHECKER and ev.event_type != "_health_check_cycle":
+                raise UnsupportedTopology(f"scheduled event {ev!r}: only the Event start() returns is lowered for a HealthChecker")
             if i is None or a.kind[i] == N.NODE_SOURCE:
                 raise UnsupportedTopology(f"scheduled event {ev!r}: only Requests for a Server / Sink / NetworkLink / RandomRouter / "
                                           "RateLimitedEntity of this Simulation are lowered")
@@ -393,7 +413,7 @@ class Simulation:
                 raise UnsupportedTopology(f"scheduled event {ev!r}: completion hooks are host Python (not lowered)")
             if ev.context.get("created_at") != ev.time:
                 raise UnsupportedTopology(f"scheduled event {ev!r}: a custom created_at is not lowered")
-            lb_name = keyless_hazard(g, ev.target)
+            lb_name = None if a.kind[i] == N.NODE_HEALTH_CHECKER else keyless_hazard(g, ev.target)
             if lb_name is not None:
                 raise UnsupportedTopology(f"scheduled event {ev!r} carries no client id and can reach the Random LoadBalancer "
                                           f"'{lb_name}' (the reference would ask the process-wide random generator): not lowered")
@@ -428,9 +448,16 @@ class Simulation:
         es = eng.summary()
         stats = eng.stats()
         rec = eng.records()
-        write_back_general(g, stats, *rec, device=self._device)
+        health = g.arrays.has_health
+        write_back_general(g, stats, *rec, device=self._device, health=eng.health if health else None)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
+        if health:
+            # the checkers' cycle / response / timeout Events: internal kinds like the limiters' and the faults' (events_processed
+            # counts them, events_by_kind does not)
+            self._health_by_kind = eng.health_events()
+        if health and not self._faults:
+            self._internal_by_kind = eng.faults()[1]
         if self._faults:
             crashed, internal, popped_cancelled = eng.faults()
             self._internal_by_kind = internal                      # (limiter Requests, limiter polls, fault set, fault clear)

@@ -730,7 +730,8 @@ int hs_debug_time_ops(int32_t device, int64_t n, const int64_t *ns, const double
 typedef struct hs_graph hs_graph;
 
 typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK = 2, HS_NODE_LINK = 3, HS_NODE_ROUTER = 4, HS_NODE_PROBE = 5, HS_NODE_LB = 6,
-                             HS_NODE_RATE_LIMITER = 7 /* RateLimitedEntity: `target` = its downstream, `queue_cap` = its FIFO capacity; policy: hs_graph_set_limiter_policy */
+                             HS_NODE_RATE_LIMITER = 7, /* RateLimitedEntity: `target` = its downstream, `queue_cap` = its FIFO capacity; policy: hs_graph_set_limiter_policy */
+                             HS_NODE_HEALTH_CHECKER = 8 /* HealthChecker: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_health_checker */
 } hs_node_kind;
 
 typedef struct hs_graph_config {
@@ -890,6 +891,39 @@ int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, i
  * Requests, its polls, fault Events that set a flag, fault Events that clear one -- events_processed == sum(events_by_kind) +
  * sum(internal_by_kind); *cancelled = cancelled fault Events popped.  Any of the three may be NULL. */
 int hs_graph_get_faults(hs_graph *g, uint8_t *crashed, int64_t *internal_by_kind, int64_t *cancelled);
+/* Backend health: HealthChecker (components/load_balancer/health_check.py) and LoadBalancer.mark_unhealthy / mark_healthy
+ * (load_balancer.py:244-297).  A graph with a configured checker, or with initial health flags, runs an instantiation of the loop of
+ * its own; `_forward_request` then selects over the healthy backends in registration order (RoundRobin, LeastConnections,
+ * WeightedLeastConnections; WeightedRoundRobin as the live smooth-weighted algorithm with per-backend current weights that persist
+ * while a backend is out, strategies.py:111-134).  ConsistentHash, IPHash and Random are refused (HS_E_UNSUPPORTED) under a checker or
+ * with an unhealthy backend.
+ *
+ * hs_graph_set_health_checker: node `node` (HS_NODE_HEALTH_CHECKER) checks the backends of LoadBalancer `lb_node` every `interval_s`
+ * with `timeout_s` per check; the reference's own ValueErrors as HS_E_INVALID with its texts; a second checker on one LoadBalancer:
+ * HS_E_UNSUPPORTED.  `running`: `_is_running` when the run begins (start() sets it, stop() clears it).  hs_graph_schedule on the
+ * checker node is the `_health_check_cycle` Event start() returns, numbered in call order with the other scheduled entries.  Three
+ * more internal kinds -- the cycle, a check's response, its timeout -- are aimed at the checker itself (dropped while it is crashed,
+ * after which its cycle chain has ended and the backends stay `is_checking`); a probe is a Request of the backend in every respect
+ * (queue capacity, stats_accepted, service draw, downstream, Sink record with created_at = its own time), its response is pushed when
+ * the backend's enqueue handler returns, a probe at a crashed backend is dropped and only its timeout comes.
+ * hs_graph_set_lb_health: healthy[n] = BackendInfo.is_healthy of the LoadBalancer's `n` backends when the run begins.
+ * Both before the first run (HS_E_STATE afterwards). */
+int hs_graph_set_health_checker(hs_graph *g, int32_t node, int32_t lb_node, double interval_s, double timeout_s, int32_t healthy_threshold,
+                                int32_t unhealthy_threshold, int32_t running);
+int hs_graph_set_lb_health(hs_graph *g, int32_t node, const uint8_t *healthy, int32_t n);
+/* After a run, for `node` a HealthChecker or a LoadBalancer (any output may be NULL):
+ *   checker_stats[6]  HealthCheckStats in field order: performed, passed, failed, timed out, marked healthy, marked unhealthy (zeros for a LoadBalancer node);
+ *   backend_states[6 * n_backends]  per backend of the LoadBalancer: consecutive_successes, consecutive_failures, last_check_time ns (-1: None),
+ *                     last_check_passed (-1: None), is_checking, the pending check id (0: none);
+ *   healthy[n_backends]  BackendInfo.is_healthy;  marks[2]  the LoadBalancer's backends_marked_unhealthy / _healthy of the run;
+ *   events[3]         the graph's cycle / response / timeout Events, counted like events_by_kind counts the public kinds:
+ *                     events_processed == sum(events_by_kind) + sum(internal_by_kind of hs_graph_get_faults) + sum(events).
+ * node = -1 with every other output NULL: the event counts alone. */
+int hs_graph_get_health(hs_graph *g, int32_t node, int64_t *checker_stats, int64_t *backend_states, uint8_t *healthy, int64_t *marks, int64_t *events);
+/* WeightedRoundRobin._current_weights of the LoadBalancer's `n` backends after a run with health state: returns 1 and fills `out`
+ * and, if not NULL, present[n] = the dict has an entry for the backend (it was healthy at one selection at least, strategies.py:117-119);
+ * 0 when the graph has none (the periodic table ran: the weights follow from the selection counts); negative: an hs_status. */
+int64_t hs_graph_get_lb_current_weights(hs_graph *g, int32_t node, int64_t *out, uint8_t *present, int32_t n);
 /* Auto-termination (core/simulation.py:306-322, end_time = Infinity): a run to end_ns = 2^61 ends in front of a pop when only daemon
  * events -- the limiters' polls -- are pending.  A run with any other end processes polls like any event. */
 /* Debug / tests only (no engine path calls it; the null stream, its own allocations): FixedWindowPolicy._get_window_start on the device, one (now_ns, window_s) pair per thread: out_div[i] = Python's float
