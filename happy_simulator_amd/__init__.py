@@ -26,6 +26,7 @@ from .entities import (cross_region_network, datacenter_network, internet_networ
 from .entities import (FixedWindowPolicy, LeakyBucketPolicy, RateLimitedEntity, RateLimitedEntityStats,  # noqa: F401
                        SlidingWindowPolicy, TokenBucketPolicy)
 from .entities import BackendHealthState, HealthChecker, HealthCheckStats  # noqa: F401
+from .entities import Bulkhead, BulkheadStats, TimeoutStats, TimeoutWrapper  # noqa: F401
 from .faults import CrashNode, FaultHandle, FaultSchedule, FaultStats, PauseNode  # noqa: F401
 from .lowering import UnsupportedTopology  # noqa: F401
 from .parallel import (ParallelResult, ParallelRunner, ParallelSimulation, ParallelSimulationSummary,  # noqa: F401

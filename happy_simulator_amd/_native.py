@@ -37,6 +37,9 @@ GRAPH_COOP_MIN_BACKENDS = 32                                # csrc/hs_graph.hip 
 NODE_SOURCE, NODE_SERVER, NODE_SINK, NODE_LINK, NODE_ROUTER, NODE_PROBE, NODE_LB = 0, 1, 2, 3, 4, 5, 6
 NODE_RATE_LIMITER = 7
 NODE_HEALTH_CHECKER = 8
+NODE_BULKHEAD, NODE_TIMEOUT_WRAPPER = 9, 10
+BULKHEAD_MAX_CONCURRENT = 65536                             # include/hs_engine.h HS_BULKHEAD_MAX_CONCURRENT
+WRAPPER_COUNTERS = 12                                       # HS_WRAPPER_COUNTERS
 # hs_limiter_policy / hs_limiter_outcome (the third column of a limiter's records)
 LIMITER_TOKEN_BUCKET, LIMITER_LEAKY_BUCKET, LIMITER_SLIDING_WINDOW, LIMITER_FIXED_WINDOW, LIMITER_NONE = 0, 1, 2, 3, 255
 LIMITER_FORWARDED, LIMITER_QUEUED, LIMITER_DROPPED, LIMITER_DRAINED = 0, 1, 2, 3
@@ -46,6 +49,8 @@ EV_NAMES = ("source", "enqueue", "notify", "poll", "deliver", "work", "continuat
             "route", "lb", "lb_resp", "probe_tick", "probe")
 PROBE_METRICS = {"depth": 0, "active_requests": 1, "stats_accepted": 2, "stats_dropped": 3, "requests_completed": 4,
                  "_requests_completed": 4, "events_received": 5, "generated_count": 6, "queue_depth": 7}
+# ... of a Bulkhead / TimeoutWrapper (general graphs only; a Bulkhead's queue_depth is its own metric)
+PROBE_WRAPPER_METRICS = {"active_count": 8, "queue_depth": 9, "available_permits": 10, "in_flight_count": 11}
 PROBE_NONE = 255
 # hs_engine_run_path / hs_lb_run_path: which side of the host-side gates the last run landed on (include/hs_engine.h)
 RUN_ONE_LANE, RUN_ONE_LANE_UNI, RUN_WIDE, RUN_WAVE, RUN_TANDEM, RUN_SINGLE_HEAP = 1, 2, 4, 8, 16, 32
@@ -495,6 +500,10 @@ def lib():
     L.hs_graph_get_health.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_graph_get_lb_current_weights.restype = C.c_int64
     L.hs_graph_get_lb_current_weights.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+    L.hs_graph_set_wrapper.restype = C.c_int
+    L.hs_graph_set_wrapper.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32]
+    L.hs_graph_get_wrapper.restype = C.c_int
+    L.hs_graph_get_wrapper.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     L.hs_graph_coop_selects.restype = C.c_int64
     L.hs_graph_coop_selects.argtypes = [C.c_void_p]
     L.hs_debug_graph_flags.restype = C.c_int
@@ -556,4 +565,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_set_limiter_policy", "hs_graph_get_limiter", "hs_debug_window_start",
     "hs_graph_add_fault", "hs_graph_get_faults",
     "hs_graph_set_health_checker", "hs_graph_set_lb_health", "hs_graph_get_health", "hs_graph_get_lb_current_weights",
+    "hs_graph_set_wrapper", "hs_graph_get_wrapper",
 )

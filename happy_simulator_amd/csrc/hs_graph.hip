@@ -70,6 +70,8 @@ struct GParam {                                // 64 bytes, read-only
                                                // WeightedRoundRobin: the total weight W = entries of its selection table (lim = its offset)
                                                // HealthChecker: mean = interval, lat_min = timeout (seconds), conc = healthy_threshold,
                                                // lim = unhealthy_threshold, sub = _is_running, target = its LoadBalancer
+                                               // Bulkhead: conc = max_concurrent, lim = max_wait_queue, lat_min = max_wait_time (sub = 1: it has one),
+                                               // rt_off / rt_cnt = its table in GCtl::rs_tab;  TimeoutWrapper: lat_min = timeout, rt_off / rt_cnt likewise
     int32_t rt_off, rt_cnt;                    // router / LoadBalancer: its targets; Source / Probe: rt_off = row of its tick table (-1: none)
     uint8_t kind, sub;                         // sub: Source arrival kind (hs_source_kind); Server / link latency kind; Probe metric; LB strategy
     uint8_t crashed;                           // entity._crashed (faults/node_faults.py:46-62): the one byte of a row a run writes -- kFaultOn / kFaultOff
@@ -91,6 +93,10 @@ struct GState {                                // 64 bytes
     //               a graph with health state (GCtl::health): qlen = healthy_count, qhead / qtail = backends_marked_unhealthy / _healthy
     // HealthChecker: a = checks_performed, b = checks_passed, c = checks_failed (= checks_timed_out), d = _next_check_id,
     //                qlen = backends_marked_healthy, active = backends_marked_unhealthy
+    // Bulkhead: a = total, b = accepted, c = rejected, d = timed_out, svc_draws = _next_request_id (queued = svc_draws - b: every forward
+    //           and every enqueue takes one id), total_service = peak_concurrent | peak_queue_depth (two int32), active = _active_count
+    //           (= len(_in_flight)), qhead / qtail / qlen = _wait_queue through Request::next (Request::idx = enqueue time, service_s = id)
+    // TimeoutWrapper: a = total, b = successful, c = timed_out, svc_draws = _next_request_id, qlen = len(_in_flight)
     int64_t a, b, c, d;
     double total_service;                      // Server._total_service_time
     uint64_t svc_draws;
@@ -101,10 +107,11 @@ struct GState {                                // 64 bytes
 struct GRequest {                              // 32 bytes: the payload Event's identity + its context
     int64_t created;                           // context["created_at"] (load/source.py:76-79; forwarded unchanged, core/entity.py:100-105)
     uint64_t idx;                              // sort index of the queued payload Event (kept on retarget, queue_driver.py:86-90)
-    double service_s;                          // service_time_s of the generator frame (server/server.py:246-247)
+    double service_s;                          // service_time_s of the generator frame (server/server.py:246-247); dead until WORK: while a
+                                               // wrapper's hook rides on the Event (and in a Bulkhead's queue) the wrapper's request id, as bits
     int64_t client;                            // context["metadata"]["client_id"] (-1: none)
     int32_t next;                              // FIFO / free list
-    int32_t hook : 31;                         // LoadBalancer whose `_lb_response` hook rides on the Event (-1: none)
+    int32_t hook : 31;                         // LoadBalancer / checker / wrapper whose completion hook rides on the Event (-1: none)
     uint32_t pre : 1;                          // `idx` came from the process-wide counter (GEvent::pad), set where the payload is queued
 };
 
@@ -120,6 +127,13 @@ constexpr uint32_t kEvFaultOn = HS_EV_KINDS + 2, kEvFaultOff = HS_EV_KINDS + 3;
 // no Request) and the check id in GEvent::pad above the two flag bits.  They count in events_processed and per graph
 // (GVars::health_by_kind), not in events_by_kind.
 constexpr uint32_t kEvHcCycle = HS_EV_KINDS + 4, kEvHcResp = HS_EV_KINDS + 5, kEvHcTimeout = HS_EV_KINDS + 6, kEvAllKinds = HS_EV_KINDS + 7;
+// Bulkhead / TimeoutWrapper (components/resilience/bulkhead.py, timeout.py): a Request at the wrapper, the `_bh_response` /
+// `_tw_response` Event its completion hook constructs, and the `_bh_timeout` / `_tw_timeout` Event -- six more internal kinds, aimed at
+// the wrapper itself.  A response / timeout carries no Request: its per-wrapper request id rides in GEvent::pad above the two flag bits
+// (the low 30 bits) and in GEvent::req (-2 - the bits above them).  They count in events_processed and per graph
+// (GVars::resil_by_kind), not in events_by_kind.
+constexpr uint32_t kEvBhReq = kEvAllKinds, kEvBhResp = kEvAllKinds + 1, kEvBhTimeout = kEvAllKinds + 2, kEvTwReq = kEvAllKinds + 3,
+                   kEvTwResp = kEvAllKinds + 4, kEvTwTimeout = kEvAllKinds + 5, kEvResKinds = kEvAllKinds + 6;
 constexpr uint32_t kPadPre = 1u, kPadCancelled = 2u;
 constexpr int kPadIdShift = 2;                 // a check id in GEvent::pad (its low 30 bits: only the one pending id of a backend and ids
                                                // at most one timeout older are ever compared)
@@ -129,7 +143,12 @@ constexpr int kPadIdShift = 2;                 // a check id in GEvent::pad (its
 constexpr uint32_t kDropKinds = (1u << HS_EV_SOURCE) | (1u << HS_EV_PROBE_TICK) | (1u << HS_EV_ENQUEUE) | (1u << HS_EV_SINK) | (1u << HS_EV_LINK) |
                                 (1u << HS_EV_ROUTE) | (1u << HS_EV_LB) | (1u << HS_EV_LB_RESP) | (1u << kEvLimRequest) | (1u << kEvLimPoll) |
                                 (1u << kEvHcCycle) | (1u << kEvHcResp) | (1u << kEvHcTimeout);
-static_assert(kEvAllKinds <= 32, "kDropKinds is one word");
+// ... and all six kinds of the two wrappers (the instantiation that dispatches them tests this word; the others keep theirs)
+constexpr uint32_t kDropKindsRes = kDropKinds | (1u << kEvBhReq) | (1u << kEvBhResp) | (1u << kEvBhTimeout) | (1u << kEvTwReq) |
+                                   (1u << kEvTwResp) | (1u << kEvTwTimeout);
+static_assert(kEvResKinds <= 32, "kDropKinds is one word");
+constexpr int kMaxBulkheadConcurrent = HS_BULKHEAD_MAX_CONCURRENT;         // Bulkhead.max_concurrent the in-flight table is sized for (include/hs_engine.h)
+constexpr int kDefaultTimeoutTable = 256;                // ids a TimeoutWrapper's table holds before it first grows
 struct GFault { int64_t t; int32_t node; uint32_t flags; };   // hs_graph_add_fault: flags bit 0 = on, bit 1 = cancelled
 // HealthChecker._backend_states / _pending_checks of one backend, at its slot of the LoadBalancer's targets (one checker per LoadBalancer)
 struct GHc {                                   // 32 bytes
@@ -142,7 +161,7 @@ struct GHc {                                   // 32 bytes
 constexpr int kLimPollScheduled = 1, kLimHasTime = 2;   // GState::active of a limiter: _poll_scheduled; _last_*_time / _current_window_start is set
 constexpr long long kMaxSlidingLog = 1ll << 20;          // SlidingWindowPolicy.max_requests the ring is sized for
 
-enum : int { kRunning = 0, kDone = 1, kGrowHeap = 2, kGrowReq = 4, kGrowRec = 8, kBadKind = 16, kGrowTicks = 32, kUndecided = 64 };
+enum : int { kRunning = 0, kDone = 1, kGrowHeap = 2, kGrowReq = 4, kGrowRec = 8, kBadKind = 16, kGrowTicks = 32, kUndecided = 64, kGrowTab = 128 };
 
 struct GVars {                                 // device scalars
     long long heap_len;
@@ -164,6 +183,7 @@ struct GVars {                                 // device scalars
     long long faults_cancelled;                // cancelled fault Events popped
     const GFault *faults; long long n_faults;  // the fault Events in the order FaultSchedule.start constructed them: read once, at boot
     long long health_by_kind[3];               // the checkers' cycle / response / timeout Events (hs_graph_get_health)
+    long long resil_by_kind[6];                // the wrappers' request / response / timeout Events, Bulkhead then TimeoutWrapper (hs_graph_get_wrapper)
 };
 
 struct GCtl {                                  // kernel argument
@@ -196,6 +216,9 @@ struct GCtl {                                  // kernel argument
     int32_t *hl_list;                          // per LoadBalancer at its rt_off: its healthy slots, ascending (= `healthy_backends`); GState::qlen of them
     long long *wrr_cur;                        // WeightedRoundRobin._current_weights of every backend slot (they persist while a backend is out)
     GHc *hc;                                   // the checker's state of every backend slot
+    // Bulkhead / TimeoutWrapper `_in_flight`: the live request ids of every wrapper, unordered, GParam::rt_cnt places at GParam::rt_off
+    // (a Bulkhead holds GState::active of them, a TimeoutWrapper GState::qlen)
+    int64_t *rs_tab;
 };
 
 __device__ __forceinline__ bool ev_lt(const GEvent &a, const GEvent &b) {   // Event.__lt__, core/event.py:337-344
@@ -278,7 +301,12 @@ __device__ __forceinline__ double uniform_at(uint64_t seed, uint64_t sid, uint64
 }
 
 // a Request-carrying Event aimed at `node`: which handler it lands in (Entity.handle_event of that class)
+template <bool R = false>
 __device__ __forceinline__ uint32_t arrival_kind(const GParam *P, int node) {
+    if constexpr (R) {                         // (the wrappers exist in the one instantiation that dispatches their kinds)
+        if (P[node].kind == HS_NODE_BULKHEAD) return kEvBhReq;
+        if (P[node].kind == HS_NODE_TIMEOUT_WRAPPER) return kEvTwReq;
+    }
     switch (P[node].kind) {
         case HS_NODE_SERVER: return HS_EV_ENQUEUE;
         case HS_NODE_SINK: return HS_EV_SINK;
@@ -473,16 +501,35 @@ __device__ inline bool lb_mark(const GCtl &c, int lb, int slot, bool healthy) {
     return true;
 }
 
+// A wrapper's response / timeout Event with its request id (GEvent::pad above the flag bits, GEvent::req beyond 30 bits)
+__device__ __forceinline__ GEvent mk_id(int64_t t, uint64_t idx, uint32_t kind, int node, int64_t id) {
+    GEvent e = mk(t, idx, kind, node, -2 - (int)(id >> 30));
+    e.pad = (uint32_t)(id & 0x3fffffffll) << kPadIdShift;
+    return e;
+}
+__device__ __forceinline__ int64_t ev_id(const GEvent &e) { return ((int64_t)(-2 - e.req) << 30) | (int64_t)(e.pad >> kPadIdShift); }
+__device__ __forceinline__ int64_t req_id(const GRequest &q) { return __double_as_longlong(q.service_s); }
+// `request_id in self._in_flight` and its removal: the live ids are unordered, the last one takes the place of the one that leaves
+__device__ inline bool tab_remove(int64_t *tab, int live, int64_t id) {
+    for (int i = 0; i < live; ++i)
+        if (tab[i] == id) { tab[i] = tab[live - 1]; return true; }
+    return false;
+}
+
 // NL: graphs of up to NL nodes keep their nodes' parameters and state in LDS for the launch (the loop's dependent chain goes
 // through them several times per event: 64-cycle LDS round trips instead of L2's) -- `lnodes`: NL x (GParam + GState).
 // F: the graph has fault Events.  A graph without any runs the instantiation that holds none of their code (the lone lane's loop is
 // bound by its own instruction count and register allocation: the two tests per event were measurable).
 // HC: the graph (or one of a batch) has a HealthChecker or an unhealthy backend -- a third instantiation, so that the two above keep
 // their code: the fault-only loop is as sensitive to what it carries as the plain one.  HC implies F.
-template <int W, int NL, bool F = false, bool HC = false>
+// R: the graph (or one of a batch) has a Bulkhead or a TimeoutWrapper -- a fourth instantiation, for the same reason.  R implies HC.
+template <int W, int NL, bool F = false, bool HC = false, bool R = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     static_assert(F || !HC, "the health instantiation carries the fault code");
-    constexpr uint32_t kKinds = HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
+    static_assert(HC || !R, "the resilience instantiation carries the fault and health code");
+    constexpr uint32_t kKinds = R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
+    constexpr uint32_t kDrop = R ? kDropKindsRes : kDropKinds;
+    constexpr int kPushes = R ? 3 : 2;         // heap entries one event constructs at most (R: a limiter's forward or poll + the hook's response)
     __shared__ unsigned long long s_by_kind[kKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
     GCtl c = c0;
@@ -568,7 +615,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             const int64_t t = c.sched_t[V.sched_done];
             GRequest q; q.created = t; q.idx = V.global_counter; q.service_s = 0.0; q.client = -1; q.next = -1; q.hook = -1; q.pre = 1;
             c.reqs[r] = q;
-            H.push(mk_pre(t, V.global_counter++, arrival_kind(c.P, node), node, r));
+            H.push(mk_pre(t, V.global_counter++, arrival_kind<R>(c.P, node), node, r));
             V.sched_done++;
         }
         cur = V.cur;
@@ -584,7 +631,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             if (!(H.len > (c.auto_term ? polls_pending : 0) && (c.part ? H.get(0).t <= c.end_ns : cur <= c.end_ns))) { status = kDone; break; }
             if (processed >= c.budget) break;
             // room for whatever this event constructs (at most two pushes, one Request, one record)
-            if (H.len + 2 > c.heap_cap) { status |= kGrowHeap; break; }
+            if (H.len + kPushes > c.heap_cap) { status |= kGrowHeap; break; }
             if (req_free < 0 && req_len >= c.req_cap) { status |= kGrowReq; break; }
             if (rec_n >= c.rec_cap) { status |= kGrowRec; break; }
             if (c.ticks != nullptr) {                                              // the next tick of a table-driven stream must be in its table
@@ -609,6 +656,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     for (int r = req_free; r >= 0 && room < nb; r = c.reqs[r].next) room += 1;
                     if (room < nb) { status |= kGrowReq; break; }
                 }
+            }
+            if constexpr (R) {
+                const GEvent top = H.get(0);                                       // a TimeoutWrapper's table has a place for the id it is about to take
+                if (top.kind == kEvTwReq && c.S[top.node].qlen >= c.P[top.node].rt_cnt) { status |= kGrowTab; break; }
             }
             if (c.coop_min > 0 && sel < 0) {                                       // (a graph without such a LoadBalancer: one uniform test)
                 const GEvent top = H.get(0);
@@ -650,7 +701,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             const GParam p = c.P[n];
             GState &s = c.S[n];
             if constexpr (F) {
-                if (p.crashed && ((kDropKinds >> e.kind) & 1u)) {
+                if (p.crashed && ((kDrop >> e.kind) & 1u)) {
                     // Event.invoke returns [] (core/event.py:261-262): no handler, no completion hooks, nothing constructed.  A
                     // Source's or Probe's one pending tick ends there for good, a limiter keeps _poll_scheduled without a poll.
                     if (e.kind == kEvLimPoll) polls_pending -= 1;
@@ -686,7 +737,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         GRequest rq; rq.created = t; rq.idx = idx_p; rq.service_s = 0.0; rq.client = (id << 32) | (int64_t)q; rq.next = -1; rq.hook = n; rq.pre = 0;
                         c.reqs[r] = rq;
                         const int be = c.rt_targets[lp.rt_off + q];
-                        H.push(mk(t, idx_p, arrival_kind(c.P, be), be, r));
+                        H.push(mk(t, idx_p, arrival_kind<R>(c.P, be), be, r));
                         GEvent te = mk(t + ns_from_seconds(p.lat_min), G++, kEvHcTimeout, n, -2 - q);
                         te.pad = (uint32_t)id << kPadIdShift;
                         H.push(te);
@@ -694,7 +745,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     H.push(mk(t + ns_from_seconds(p.mean), G++, kEvHcCycle, n, -1));  // self.now + Duration.from_seconds(interval)
                     continue;
                 }
-                if (e.kind > kEvHcCycle) {
+                if (e.kind > kEvHcCycle && (!R || e.kind < kEvAllKinds)) {
                     // _handle_response / _handle_timeout (health_check.py:351-444)
                     const int q = -2 - e.req;
                     const GParam &lp = c.P[p.target];
@@ -711,6 +762,104 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         h.last_passed = 0; h.fail += 1; h.succ = 0;
                         s.c += 1;
                         if (healthy && h.fail >= p.lim) { lb_mark(c, p.target, q, false); s.active += 1; }
+                    }
+                    continue;
+                }
+            }
+            // Event.invoke (core/event.py:277-283) with a wrapper's hook on the Event: the handler returned, `_bh_response` / `_tw_response`
+            // is constructed behind the handler's own Events.  `keep`: NetworkLink copied the still-full hook list onto the Event for its
+            // egress before the hooks ran (link.py:181), so the egress' handler fires it once more.
+            [[maybe_unused]] auto fire_hook = [&](int r, bool keep) {
+                const int hook = c.reqs[r].hook;
+                if (hook < 0) return;
+                if (!keep) c.reqs[r].hook = -1;
+                const uint8_t hk = c.P[hook].kind;
+                if (hk == HS_NODE_BULKHEAD || hk == HS_NODE_TIMEOUT_WRAPPER)
+                    H.push(mk_id(t, G++, hk == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp, hook, req_id(c.reqs[r])));
+                else if (hk == HS_NODE_LB) H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
+            };
+            if constexpr (R) {
+                if (e.kind >= kEvBhReq) {
+                    int64_t *tab = c.rs_tab + p.rt_off;
+                    // Bulkhead._forward_request (bulkhead.py:231-291): a new id, the permit, a NEW Event for the target with the hook
+                    auto bh_forward = [&](int r) {
+                        s.svc_draws += 1;
+                        const int64_t id = (int64_t)s.svc_draws;
+                        s.active += 1; s.b += 1;
+                        int32_t *peaks = reinterpret_cast<int32_t *>(&s.total_service);
+                        if (s.active > peaks[0]) peaks[0] = s.active;
+                        tab[s.active - 1] = id;                                    // (active <= max_concurrent = rt_cnt)
+                        c.reqs[r].hook = n; c.reqs[r].service_s = __longlong_as_double(id);
+                        H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, r));
+                    };
+                    switch (e.kind) {
+                    case kEvBhReq: {                                               // Bulkhead.handle_event (bulkhead.py:191-229)
+                        s.a += 1;
+                        if (s.active < p.conc) bh_forward(e.req);
+                        else if ((int64_t)s.qlen < p.lim) {                        // _enqueue_request (:293-335)
+                            s.svc_draws += 1;
+                            const int64_t id = (int64_t)s.svc_draws;
+                            GRequest &q = c.reqs[e.req];
+                            q.idx = (uint64_t)t; q.service_s = __longlong_as_double(id); q.next = -1;
+                            if (s.qtail >= 0) c.reqs[s.qtail].next = e.req; else s.qhead = e.req;
+                            s.qtail = e.req;
+                            s.qlen += 1;
+                            int32_t *peaks = reinterpret_cast<int32_t *>(&s.total_service);
+                            if (s.qlen > peaks[1]) peaks[1] = s.qlen;
+                            if (p.sub) H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvBhTimeout, n, id));
+                        } else {
+                            s.c += 1;
+                            c.reqs[e.req].next = req_free; req_free = e.req;
+                        }
+                    } break;
+                    case kEvBhResp: {                                              // _handle_response (:337-362) + _try_process_queued (:384-409)
+                        if (!tab_remove(tab, s.active, ev_id(e))) break;           // an unknown id: a processed no-op
+                        s.active = s.active > 0 ? s.active - 1 : 0;
+                        while (s.qlen > 0 && s.active < p.conc) {
+                            const int r = s.qhead;
+                            s.qhead = c.reqs[r].next;
+                            if (s.qhead < 0) s.qtail = -1;
+                            s.qlen -= 1;
+                            if (p.sub && seconds_from_ns(t - (int64_t)c.reqs[r].idx) > p.lat_min) {   // expired: skipped, the next one is tried
+                                s.d += 1;
+                                c.reqs[r].next = req_free; req_free = r;
+                                continue;
+                            }
+                            bh_forward(r);
+                            break;
+                        }
+                    } break;
+                    case kEvBhTimeout: {                                           // _handle_timeout (:364-382): the entry of that id, if it still waits
+                        const int64_t id = ev_id(e);
+                        int prev = -1;
+                        for (int r = s.qhead; r >= 0; prev = r, r = c.reqs[r].next) {
+                            const int64_t rid = req_id(c.reqs[r]);
+                            if (rid > id) break;                                   // (ids ascend along the queue)
+                            if (rid != id) continue;
+                            const int nx = c.reqs[r].next;
+                            if (prev >= 0) c.reqs[prev].next = nx; else s.qhead = nx;
+                            if (nx < 0) s.qtail = prev;
+                            s.qlen -= 1;
+                            s.d += 1;
+                            c.reqs[r].next = req_free; req_free = r;
+                            break;
+                        }
+                    } break;
+                    case kEvTwReq: {                                               // TimeoutWrapper._forward_request (timeout.py:155-220)
+                        s.a += 1;
+                        s.svc_draws += 1;
+                        const int64_t id = (int64_t)s.svc_draws;
+                        tab[s.qlen] = id;                                          // (room: tested in front of the pop)
+                        s.qlen += 1;
+                        c.reqs[e.req].hook = n; c.reqs[e.req].service_s = __longlong_as_double(id);
+                        H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, e.req));
+                        H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvTwTimeout, n, id));
+                    } break;
+                    default: {                                                     // _handle_response / _handle_timeout (:222-295): whichever comes second finds nothing
+                        if (!tab_remove(tab, s.qlen, ev_id(e))) break;
+                        s.qlen -= 1;
+                        if (e.kind == kEvTwResp) s.b += 1; else s.c += 1;
+                    } break;
                     }
                     continue;
                 }
@@ -737,7 +886,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 }
                 s.c += 1;                                                           // _generated_count (:159)
                 const int64_t a2 = next_arrival(c, n);
-                if (payload) H.push(mk(t, idx_p, arrival_kind(c.P, p.target), p.target, r));
+                if (payload) H.push(mk(t, idx_p, arrival_kind<R>(c.P, p.target), p.target, r));
                 if (a2 != kInfNs) H.push(mk(a2, G++, HS_EV_SOURCE, n, -1));       // RuntimeError: the source is exhausted (:176-180)
             } break;
             case HS_EV_ENQUEUE: {
@@ -769,7 +918,16 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     GEvent re = mk(t, G++, kEvHcResp, hook, -2 - (int)(probe_tag & 0xffffffffll));
                     re.pad = (uint32_t)(probe_tag >> 32) << kPadIdShift;
                     H.push(re);
-                } else if (hook >= 0) H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
+                } else if (hook >= 0) {
+                    if constexpr (R) {                                             // (a wrapper's hook: its id stayed on the Request)
+                        const uint8_t hk = c.P[hook].kind;
+                        if (hk == HS_NODE_BULKHEAD || hk == HS_NODE_TIMEOUT_WRAPPER) {
+                            H.push(mk_id(t, G++, hk == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp, hook, req_id(c.reqs[e.req])));
+                            break;
+                        }
+                    }
+                    H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
+                }
             } break;
             case HS_EV_NOTIFY:                                                      // QueueDriver._handle_notify (queue_driver.py:92-99)
                 if (s.active < p.conc) H.push(mk(t, G++, HS_EV_POLL, n, -1));
@@ -812,7 +970,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 s.active = s.active > 0 ? s.active - 1 : 0;
                 s.c += 1; n_completed++;
                 s.total_service = __dadd_rn(s.total_service, c.reqs[e.req].service_s);
-                if (p.target >= 0) H.push(mk(t, G++, arrival_kind(c.P, p.target), p.target, e.req));
+                if (p.target >= 0) H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, e.req));
                 else { c.reqs[e.req].next = req_free; req_free = e.req; }
                 if (s.active < p.conc) H.push(mk(t, G++, HS_EV_POLL, n, -1));
             } break;
@@ -820,6 +978,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = c.reqs[e.req].created;
                 rec_n++;
                 s.a += 1; n_received++;
+                if constexpr (R) fire_hook(e.req, false);
                 c.reqs[e.req].next = req_free; req_free = e.req;
             } break;
             case HS_EV_ROUTE: {                                                     // RandomRouter.handle_event (random_router.py:32-45)
@@ -828,7 +987,15 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 const int ri = (int)__dmul_rn(u, (double)p.rt_cnt);                 // targets[int(u * len(targets))]
                 const int tg = c.rt_targets[p.rt_off + ri];
                 c.rt_taken[p.rt_off + ri] += 1;
-                H.push(mk(t, G++, arrival_kind(c.P, tg), tg, e.req));
+                if constexpr (R) {                                                  // (the router's new Event carries no hook: fired and cleared first,
+                    const int hook = c.reqs[e.req].hook;                            //  its Event constructed behind the forward's)
+                    const int64_t id = req_id(c.reqs[e.req]);
+                    c.reqs[e.req].hook = -1;
+                    H.push(mk(t, G++, arrival_kind<R>(c.P, tg), tg, e.req));
+                    if (hook >= 0) H.push(mk_id(t, G++, c.P[hook].kind == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp, hook, id));
+                    break;
+                }
+                H.push(mk(t, G++, arrival_kind<R>(c.P, tg), tg, e.req));
             } break;
             case HS_EV_LINK: {
                 // NetworkLink.handle_event up to its yield (components/network/link.py:114-154, _calculate_delay :190-216)
@@ -837,6 +1004,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 s.a = entered + 1;
                 if (p.loss > 0.0 && uniform_at(c.seed, stream_id(p.stream_base, kStreamLoss), (uint64_t)entered) < p.loss) {   // link.py:131-138
                     s.c += 1;
+                    if constexpr (R) fire_hook(e.req, false);                       // the generator ended before its first yield: the hooks run at once
                     c.reqs[e.req].next = req_free; req_free = e.req;
                     break;
                 }
@@ -852,8 +1020,13 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             } break;
             case HS_EV_LINK_CONT:                                                   // transit over (link.py:156-189): a NEW Event for the egress
                 s.b += 1;
-                if (p.target >= 0) H.push(mk(t, G++, arrival_kind(c.P, p.target), p.target, e.req));
-                else { c.reqs[e.req].next = req_free; req_free = e.req; }
+                if (p.target >= 0) {
+                    H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, e.req));
+                    if constexpr (R) fire_hook(e.req, true);                        // ... and stays on the Event for the egress (link.py:181)
+                } else {
+                    if constexpr (R) fire_hook(e.req, false);
+                    c.reqs[e.req].next = req_free; req_free = e.req;
+                }
                 break;
             case HS_EV_LB: {
                 // LoadBalancer._forward_request (load_balancer.py:347-433); without health state every backend is healthy
@@ -941,7 +1114,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 // a NEW Event for the backend with the same context (created_at survives) + the response hook (:398-431)
                 const int be = c.rt_targets[p.rt_off + slot];
                 c.reqs[e.req].hook = n;
-                H.push(mk(t, G++, arrival_kind(c.P, be), be, e.req));
+                H.push(mk(t, G++, arrival_kind<R>(c.P, be), be, e.req));
             } break;
             case HS_EV_LB_RESP:                                                     // LoadBalancer._handle_response (load_balancer.py:435-473)
                 if (s.d > 0) s.d -= 1;
@@ -969,6 +1142,18 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     case HS_PROBE_LIMITER_DEPTH: v = tg.qlen; break;                // RateLimitedEntity.queue_depth
                     default: break;
                 }
+                if constexpr (R) {                                                  // (the wrappers' metrics: this instantiation only)
+                    switch (p.sub) {
+                    case HS_PROBE_BH_ACTIVE: v = tg.active; break;                  // Bulkhead.active_count
+                    case HS_PROBE_BH_QUEUE_DEPTH: v = tg.qlen; break;               // Bulkhead.queue_depth
+                    case HS_PROBE_BH_PERMITS: {                                     // Bulkhead.available_permits: max(0, max_concurrent - active)
+                        const int left = c.P[p.target].conc - tg.active;
+                        v = left > 0 ? left : 0;
+                    } break;
+                    case HS_PROBE_TW_IN_FLIGHT: v = tg.qlen; break;                 // TimeoutWrapper.in_flight_count
+                    default: break;
+                    }
+                }
                 c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = v;
                 rec_n++;
                 s.c += 1;
@@ -977,10 +1162,13 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 // RateLimitedEntity._handle_request (rate_limited_entity.py:114-142): count, try_acquire, forward or queue or drop
                 s.a += 1;
                 int64_t outcome;
+                [[maybe_unused]] int hook = -1;                                     // a wrapper's hook on THIS Event: the limiter's own Events carry none
+                [[maybe_unused]] int64_t hook_id = 0;
+                if constexpr (R) { hook = c.reqs[e.req].hook; hook_id = req_id(c.reqs[e.req]); c.reqs[e.req].hook = -1; }
                 if (lim_try_acquire(c, p, s, t)) {
                     // _forward (:164-178): a NEW Event for the downstream at `now` with a copy of the context, no completion hook
                     outcome = HS_LIMITER_FORWARDED;
-                    H.push(mk(t, G++, arrival_kind(c.P, p.target), p.target, e.req));
+                    H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, e.req));
                 } else if (!(p.lim >= 0 && s.qlen >= p.lim)) {                     // FIFOQueue.push (queue_policy.py:94-98)
                     outcome = HS_LIMITER_QUEUED;
                     c.reqs[e.req].next = -1;
@@ -1000,6 +1188,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 }
                 c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = outcome;
                 rec_n++;
+                if constexpr (R) {
+                    if (hook >= 0) H.push(mk_id(t, G++, c.P[hook].kind == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp, hook, hook_id));
+                }
             } break;
             case kEvLimPoll: {
                 // RateLimitedEntity._handle_poll (:144-162)
@@ -1015,7 +1206,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     s.qlen -= 1;
                     c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = HS_LIMITER_DRAINED;
                     rec_n++;
-                    H.push(mk(t, G++, arrival_kind(c.P, p.target), p.target, r));
+                    H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, r));
                     again = s.qlen > 0;
                 }
                 if (again) {
@@ -1111,6 +1302,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         if constexpr (HC) {
             for (int k = 0; k < 3; ++k) V.health_by_kind[k] += (long long)s_by_kind[kEvHcCycle + k];
         }
+        if constexpr (R) {
+            for (int k = 0; k < 6; ++k) V.resil_by_kind[k] += (long long)s_by_kind[kEvBhReq + k];
+        }
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
@@ -1144,6 +1338,12 @@ __global__ void __launch_bounds__(64) hs_graph_run_health(GCtl c) {           //
     __shared__ GEvent lheap[kLdsHeap];
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
     graph_loop<kLdsHeap, kLdsNodes, true, true>(c, lheap, lnodes);
+}
+
+__global__ void __launch_bounds__(64) hs_graph_run_resilience(GCtl c) {       // ... with a Bulkhead or a TimeoutWrapper
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true, true, true>(c, lheap, lnodes);
 }
 
 // Independent graphs -- the replicas / sweep points of parallel/runner.py:82-142 -- side by side: one workgroup (one heap) each, one
@@ -1180,6 +1380,14 @@ __global__ void __launch_bounds__(64) hs_graph_run_batch_health(const GCtl *cs, 
     graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true>(c, lheap, lnodes);
     batch_report(c, stat);
 }
+// ... of a batch in which at least one handle has a wrapper
+__global__ void __launch_bounds__(64) hs_graph_run_batch_resilience(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
 
 }  // namespace graph
 }  // namespace hs
@@ -1213,6 +1421,12 @@ struct hs_graph {
     std::vector<int32_t> checker_of;           // [n] the configured checker of a LoadBalancer node (-1: none)
     std::vector<uint8_t> checker_set;          // [n] hs_graph_set_health_checker has been called for the node
     char *d_health = nullptr;
+    // Bulkhead / TimeoutWrapper: a graph that holds one runs the fourth instantiation of the loop; their in-flight tables (ctl.rs_tab)
+    // come with the first run, laid out in node order
+    int n_wrappers = 0;
+    std::vector<uint8_t> wrapper_set;          // [n] hs_graph_set_wrapper has been called for the node
+    std::vector<int32_t> tab_cap;              // [n] the table capacity the node starts with
+    long long rs_tab_len = 0;
     int debug_flags = 0;                       // hs_debug_graph_flags
     // tick tables: one row per time-varying Source and per distinct Probe interval, computed up to `tick_horizon`
     std::vector<hs::TickRow> rows;
@@ -1294,7 +1508,7 @@ void hs_graph_destroy(hs_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *bufs[] = {g->ctl.heap, g->ctl.reqs, g->ctl.rec_node, g->ctl.rec_t, g->ctl.rec_cr, (void *)g->ctl.P, g->ctl.S,
                     g->d_rt_targets, g->d_key_table, (void *)g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
-                    g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health};
+                    g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health, g->ctl.rs_tab};
     for (void *b : bufs) if (b && !in_slab(g, b)) (void)hipFree(b);
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
     if (g->ev_a) (void)hipEventDestroy(g->ev_a);
@@ -1318,7 +1532,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     if (cfg->start_ns < 0)        // (the Sinks' merged records hold non-negative times)
         return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
     bool has_wrr = false;
-    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER; };
+    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER || k == HS_NODE_BULKHEAD || k == HS_NODE_TIMEOUT_WRAPPER; };
     int64_t kmax = 0;                                  // client ids any Source hands out: [0, kmax)
     for (int i = 0; i < n; ++i)
         if (nd->kind[i] == HS_NODE_SOURCE && nd->src_n_clients && nd->src_n_clients[i] > kmax) kmax = nd->src_n_clients[i];
@@ -1386,7 +1600,9 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a Probe needs a target", i);
             const int tk = nd->kind[p.target];
             const bool ok = p.sub == HS_PROBE_GENERATED ? tk == HS_NODE_SOURCE : p.sub == HS_PROBE_RECEIVED ? tk == HS_NODE_SINK
-                            : p.sub == HS_PROBE_LIMITER_DEPTH ? tk == HS_NODE_RATE_LIMITER : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
+                            : p.sub == HS_PROBE_LIMITER_DEPTH ? tk == HS_NODE_RATE_LIMITER
+                            : (p.sub >= HS_PROBE_BH_ACTIVE && p.sub <= HS_PROBE_BH_PERMITS) ? tk == HS_NODE_BULKHEAD
+                            : p.sub == HS_PROBE_TW_IN_FLIGHT ? tk == HS_NODE_TIMEOUT_WRAPPER : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
             if (!ok) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: metric %d is not an attribute of its target (node kind %d)", i, (int)p.sub, tk);
             const double rate = 1.0 / iv;                           // _ProbeProfile.rate (probe.py:31)
             int found = -1;
@@ -1490,6 +1706,19 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             p.lim = nd->queue_cap ? nd->queue_cap[i] : 1000;                        // rate_limited_entity.py:60
             p.sub = (uint8_t)HS_LIMITER_NONE; p.conc = 0; p.rt_off = 0; p.rt_cnt = 0;
         } break;
+        case HS_NODE_BULKHEAD:
+        case HS_NODE_TIMEOUT_WRAPPER: {
+            // Bulkhead / TimeoutWrapper (components/resilience/): the parameters come with hs_graph_set_wrapper
+            const char *nm = p.kind == HS_NODE_BULKHEAD ? "Bulkhead" : "TimeoutWrapper";
+            if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a %s needs a target", i, nm);
+            // the target's handler must fire ONE hook: through any chain of links it is a Server, Sink, router or limiter
+            int t = p.target;
+            for (int hops = 0; hops <= n && t >= 0 && nd->kind[t] == HS_NODE_LINK; ++hops) t = nd->target[t];
+            if (t >= 0 && (nd->kind[t] == HS_NODE_LB || nd->kind[t] == HS_NODE_BULKHEAD || nd->kind[t] == HS_NODE_TIMEOUT_WRAPPER))
+                return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the target of a %s is (through %s) node %d, a LoadBalancer, Bulkhead or TimeoutWrapper: "
+                            "two completion hooks on one Event are not lowered", i, nm, t == p.target ? "no link" : "its links", t);
+            p.conc = 1; p.lim = 0; p.sub = 0; p.rt_off = 0; p.rt_cnt = 0;
+        } break;
         default: return fail(nullptr, HS_E_UNSUPPORTED, "node %d: kind %d is not lowered", i, (int)p.kind);
         }
         P[(size_t)i] = p;
@@ -1506,6 +1735,8 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
         g->lim_policy.assign((size_t)n, none);
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_RATE_LIMITER) g->n_limiters++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_HEALTH_CHECKER) g->n_checkers++;
+        for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_BULKHEAD || P[(size_t)i].kind == HS_NODE_TIMEOUT_WRAPPER) g->n_wrappers++;
+        g->wrapper_set.assign((size_t)n, 0); g->tab_cap.assign((size_t)n, 0);
     }
     for (int i = 0; i < n; ++i) {
         const GParam &p = P[(size_t)i];
@@ -1885,6 +2116,85 @@ int64_t hs_graph_get_lb_current_weights(hs_graph *g, int32_t node, int64_t *out,
     return 1;
 }
 
+int hs_graph_set_wrapper(hs_graph *g, int32_t node, int32_t max_concurrent, int32_t max_wait_queue, double max_wait_time_s, double timeout_s,
+                         int32_t table_capacity) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || (g->params[(size_t)node].kind != HS_NODE_BULKHEAD && g->params[(size_t)node].kind != HS_NODE_TIMEOUT_WRAPPER))
+        return fail(g, HS_E_INVALID, "set_wrapper: node %d is neither a Bulkhead nor a TimeoutWrapper", node);
+    if (g->ran || g->launches > 0 || g->ctl.rs_tab) return fail(g, HS_E_STATE, "set_wrapper: a wrapper is configured before the first run");
+    if (g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "set_wrapper: node %d is configured already", node);
+    GParam &p = g->params[(size_t)node];
+    if (p.kind == HS_NODE_BULKHEAD) {
+        // the reference's own checks (bulkhead.py:98-103)
+        if (max_concurrent < 1) return fail(g, HS_E_INVALID, "max_concurrent must be >= 1, got %d", max_concurrent);
+        if (max_wait_queue < 0) return fail(g, HS_E_INVALID, "max_wait_queue must be >= 0, got %d", max_wait_queue);
+        if (std::isnan(max_wait_time_s) || max_wait_time_s == 0.0 || std::isinf(max_wait_time_s))
+            return fail(g, HS_E_INVALID, "max_wait_time must be > 0 or None, got %g", max_wait_time_s);
+        if (max_concurrent > kMaxBulkheadConcurrent)
+            return fail(g, HS_E_UNSUPPORTED, "Bulkhead: max_concurrent = %d is beyond the %d ids its in-flight table holds", max_concurrent, kMaxBulkheadConcurrent);
+        p.conc = max_concurrent; p.lim = max_wait_queue;
+        p.sub = max_wait_time_s > 0.0 ? 1 : 0;                 // (negative: None)
+        p.lat_min = p.sub ? max_wait_time_s : 0.0;
+        g->tab_cap[(size_t)node] = max_concurrent;
+        if (p.sub) g->reach_s = std::max(g->reach_s, max_wait_time_s);
+    } else {
+        if (!std::isfinite(timeout_s) || !(timeout_s > 0.0)) return fail(g, HS_E_INVALID, "timeout must be > 0, got %g", timeout_s);   // timeout.py:76-77
+        if (table_capacity < 0 || table_capacity > (1 << 28)) return fail(g, HS_E_INVALID, "set_wrapper: table_capacity %d out of range", table_capacity);
+        p.lat_min = timeout_s;
+        g->tab_cap[(size_t)node] = table_capacity > 0 ? table_capacity : kDefaultTimeoutTable;
+        g->reach_s = std::max(g->reach_s, timeout_s);
+    }
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    g->wrapper_set[(size_t)node] = 1;
+    return HS_OK;
+}
+
+int hs_graph_get_wrapper(hs_graph *g, int32_t node, int64_t *counters, int64_t *queue_ids, int64_t queue_cap, int64_t *in_flight_ids,
+                         int64_t in_flight_cap, int64_t *events) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (events) {
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 6; ++k) events[k] = v.resil_by_kind[k];
+    }
+    if (node == -1 && !counters && !queue_ids && !in_flight_ids) return HS_OK;          // the graph's event counts alone
+    if (node < 0 || node >= g->n || (g->params[(size_t)node].kind != HS_NODE_BULKHEAD && g->params[(size_t)node].kind != HS_NODE_TIMEOUT_WRAPPER))
+        return fail(g, HS_E_INVALID, "get_wrapper: node %d is neither a Bulkhead nor a TimeoutWrapper", node);
+    if (!g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "get_wrapper: node %d was never configured", node);
+    const GParam &p = g->params[(size_t)node];
+    const bool bh = p.kind == HS_NODE_BULKHEAD;
+    GState s{};
+    HS_HIP(g, hipMemcpy(&s, g->ctl.S + node, sizeof s, hipMemcpyDeviceToHost));
+    const int64_t live = bh ? s.active : s.qlen;
+    if (counters) {
+        int32_t peaks[2];
+        std::memcpy(peaks, &s.total_service, sizeof peaks);
+        for (int k = 0; k < HS_WRAPPER_COUNTERS; ++k) counters[k] = 0;
+        counters[0] = s.a; counters[1] = s.b; counters[2] = s.c;
+        if (bh) { counters[3] = s.d; counters[4] = (int64_t)s.svc_draws - s.b; counters[5] = peaks[0]; counters[6] = peaks[1]; counters[7] = s.active; counters[8] = s.qlen; }
+        counters[9] = (int64_t)s.svc_draws; counters[10] = live; counters[11] = g->ctl.rs_tab ? p.rt_cnt : g->tab_cap[(size_t)node];
+    }
+    if (in_flight_ids && in_flight_cap > 0 && live > 0 && g->ctl.rs_tab)
+        HS_HIP(g, hipMemcpy(in_flight_ids, g->ctl.rs_tab + p.rt_off, (size_t)std::min<int64_t>(live, in_flight_cap) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (bh && queue_ids && queue_cap > 0 && s.qlen > 0) {
+        // the wait queue is a list through the Request pool: walked on a copy of the pool
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        std::vector<GRequest> pool((size_t)std::max(v.req_len, 1));
+        HS_HIP(g, hipMemcpy(pool.data(), g->ctl.reqs, (size_t)v.req_len * sizeof(GRequest), hipMemcpyDeviceToHost));
+        int64_t k = 0;
+        for (int r = s.qhead; r >= 0 && r < v.req_len && k < queue_cap && k < s.qlen; r = pool[(size_t)r].next) {
+            int64_t id;
+            std::memcpy(&id, &pool[(size_t)r].service_s, sizeof id);
+            queue_ids[k++] = id;
+        }
+        if (k != std::min<int64_t>(s.qlen, queue_cap)) return fail(g, HS_E_INVALID, "get_wrapper: the wait queue of node %d is broken (internal error)", node);
+    }
+    return HS_OK;
+}
+
 int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, int32_t cancelled) {
     if (!g) return fail(g, HS_E_INVALID, "null handle");
     if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "add_fault: node %d out of range", node);
@@ -2044,6 +2354,24 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         c.hl_flag = reinterpret_cast<uint8_t *>(g->d_health + o_flag);
         c.health = 1;
     }
+    if (g->n_wrappers > 0 && !c.rs_tab) {
+        // the wrappers' in-flight tables, once: one allocation, every wrapper's places in node order
+        long long len = 0;
+        HS_HIP(g, hipSetDevice(g->cfg.device));
+        for (int i = 0; i < g->n; ++i) {
+            GParam &p = g->params[(size_t)i];
+            if (p.kind != HS_NODE_BULKHEAD && p.kind != HS_NODE_TIMEOUT_WRAPPER) continue;
+            if (!g->wrapper_set[(size_t)i])
+                return fail(g, HS_E_STATE, "node %d: a Bulkhead / TimeoutWrapper without its parameters (hs_graph_set_wrapper comes before the run)", i);
+            if (len + g->tab_cap[(size_t)i] > (1ll << 30)) return fail(g, HS_E_UNSUPPORTED, "the wrappers' in-flight tables of this graph exceed 2^30 ids");
+            p.rt_off = (int32_t)len; p.rt_cnt = g->tab_cap[(size_t)i];
+            len += p.rt_cnt;
+            HS_HIP(g, hipMemcpy(const_cast<GParam *>(c.P) + i, &p, sizeof p, hipMemcpyHostToDevice));
+        }
+        HS_HIP(g, hipMalloc(&c.rs_tab, (size_t)len * sizeof(int64_t)));
+        HS_HIP(g, hipMemset(c.rs_tab, 0, (size_t)len * sizeof(int64_t)));
+        g->rs_tab_len = len;
+    }
     const long long ns = (long long)g->sched_node.size();
     if (ns > g->d_sched_cap) {
         if (g->d_sched_node) HS_HIP(g, hipFree(g->d_sched_node));
@@ -2063,6 +2391,33 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
     c.coop_min = !(g->has_least_loaded || (g->health && g->has_wrr)) || (g->debug_flags & 1) ? 0 : (g->debug_flags & 2) ? 1 : kCoopMinBackends;
     c.coop_reset = 1;                                      // (hs_graph_coop_selects counts the LAST run: zeroed by its first launch)
     g->launches = 0;
+    return HS_OK;
+}
+
+// A TimeoutWrapper's table was full: every TimeoutWrapper gets twice the places (a Bulkhead never holds more than max_concurrent ids).
+// The rows' rt_off / rt_cnt alone are rewritten: the `crashed` byte of a row is the run's.
+static int grow_tables(hs_graph *g) {
+    GCtl &c = g->ctl;
+    std::vector<int64_t> old((size_t)std::max<long long>(g->rs_tab_len, 1)), now;
+    HS_HIP(g, hipMemcpy(old.data(), c.rs_tab, (size_t)g->rs_tab_len * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (int i = 0; i < g->n; ++i) {
+        GParam &p = g->params[(size_t)i];
+        if (p.kind != HS_NODE_BULKHEAD && p.kind != HS_NODE_TIMEOUT_WRAPPER) continue;
+        const long long cnt = p.kind == HS_NODE_TIMEOUT_WRAPPER ? 2ll * p.rt_cnt : p.rt_cnt;
+        if ((long long)now.size() + cnt > (1ll << 30)) return fail(g, HS_E_OVERFLOW, "more than 2^30 request ids in flight at the wrappers");
+        const size_t at = now.size();
+        now.insert(now.end(), old.begin() + p.rt_off, old.begin() + p.rt_off + p.rt_cnt);
+        now.resize(at + (size_t)cnt, 0);
+        p.rt_off = (int32_t)at; p.rt_cnt = (int32_t)cnt;
+        static_assert(offsetof(GParam, rt_cnt) == offsetof(GParam, rt_off) + sizeof(int32_t), "rt_off and rt_cnt are copied together");
+        const int32_t pair[2] = {p.rt_off, p.rt_cnt};
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(const_cast<GParam *>(c.P) + i) + offsetof(GParam, rt_off), pair, sizeof pair, hipMemcpyHostToDevice));
+    }
+    int64_t *nt = nullptr;
+    HS_HIP(g, hipMalloc(&nt, now.size() * sizeof(int64_t)));
+    HS_HIP(g, hipMemcpy(nt, now.data(), now.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    HS_HIP(g, hipFree(c.rs_tab));
+    c.rs_tab = nt; g->rs_tab_len = (long long)now.size();
     return HS_OK;
 }
 
@@ -2117,6 +2472,10 @@ static int after_launch_with(hs_graph *g, int status, long long processed, bool 
         if ((rc = grow(g, &c.rec_cr, c.rec_cap, nc))) return rc;
         c.rec_cap = nc;
     }
+    if (v.status & kGrowTab) {
+        const int rc = grow_tables(g);
+        if (rc) return rc;
+    }
     if (v.status & kUndecided) { g->undecided = true; *done = true; return HS_OK; }
     *done = v.status == kDone;
     return HS_OK;
@@ -2134,7 +2493,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
         HS_HIP(g, hipGetLastError());
@@ -2184,9 +2544,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
             h_ctl.back().part = part;              // (the handles themselves never keep part semantics: no early return can leave it set)
         }
         if ((he = hipMemcpy(d_ctl, h_ctl.data(), h_ctl.size() * sizeof(GCtl), hipMemcpyHostToDevice)) != hipSuccess) break;
-        bool any_faults = false, any_health = false;
-        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; }
-        if (any_health) hipLaunchKernelGGL(hs_graph_run_batch_health, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_faults = false, any_health = false, any_wrappers = false;
+        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; }
+        if (any_wrappers) hipLaunchKernelGGL(hs_graph_run_batch_resilience, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else if (any_health) hipLaunchKernelGGL(hs_graph_run_batch_health, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (!any_faults) hipLaunchKernelGGL(hs_graph_run_batch, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else hipLaunchKernelGGL(hs_graph_run_batch_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         if ((he = hipGetLastError()) != hipSuccess) break;
@@ -2250,8 +2611,9 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
     for (int attempt = 0; attempt < 64; ++attempt) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
-        one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count;
-        if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, one);
+        one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count; one.rs_tab = g->ctl.rs_tab;
+        if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, one);
+        else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, one);
         else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, one);
         HS_HIP(g0, hipGetLastError());

@@ -1292,6 +1292,142 @@ class RateLimitedEntity(Entity):
         return RateLimitedEntityStats(received=self._received, forwarded=self._forwarded, queued=self._queued, dropped=self._dropped)
 
 
+# ---- resilience ----------------------------------------------------------------------------------
+# components/resilience/bulkhead.py and timeout.py: the two client-side guards that are pure event logic.  Their handlers run on the
+# device (csrc/hs_graph.hip kEvBhReq .. kEvTwTimeout); these classes carry the parameters in and the reference's state back out.
+# CircuitBreaker (never leaves CLOSED without a host `failure_predicate`), Fallback and Hedge (they take callables) are not mirrored.
+@dataclass(frozen=True)
+class BulkheadStats:
+    """bulkhead.py:35-45."""
+
+    total_requests: int = 0
+    accepted_requests: int = 0
+    rejected_requests: int = 0
+    timed_out_requests: int = 0
+    queued_requests: int = 0
+    peak_concurrent: int = 0
+    peak_queue_depth: int = 0
+
+
+class Bulkhead(Entity):
+    """At most `max_concurrent` Requests in flight at `target` (bulkhead.py:57-409): a Request beyond that waits in a queue of
+    `max_wait_queue` places for at most `max_wait_time` seconds (None: for ever), one beyond that is rejected.  A permit returns
+    when the completion hook of the forwarded Event fires -- when the target's handler returns, or a NetworkLink's transit ends --
+    so a Request dropped at a crashed target keeps its permit for good, as in the reference."""
+
+    MAX_CONCURRENT = 65536                    # include/hs_engine.h HS_BULKHEAD_MAX_CONCURRENT: the ids the in-flight table holds
+
+    def __init__(self, name: str, target: Entity, max_concurrent: int, max_wait_queue: int = 0, max_wait_time: float | None = None):
+        super().__init__(name)
+        if max_concurrent < 1:                                                            # bulkhead.py:98-103
+            raise ValueError(f"max_concurrent must be >= 1, got {max_concurrent}")
+        if max_wait_queue < 0:
+            raise ValueError(f"max_wait_queue must be >= 0, got {max_wait_queue}")
+        if max_wait_time is not None and max_wait_time <= 0:
+            raise ValueError(f"max_wait_time must be > 0 or None, got {max_wait_time}")
+        self._target = target
+        self._max_concurrent = max_concurrent
+        self._max_wait_queue = max_wait_queue
+        self._max_wait_time = max_wait_time
+        self._active_count = 0
+        self._wait_queue: list[int] = []          # after a run: the request ids that still wait, head first
+        self._next_request_id = 0
+        self._in_flight: dict[int, dict] = {}     # after a run: the ids in flight (the reference's values hold Events: not mirrored)
+        self._total_requests = 0
+        self._accepted_requests = 0
+        self._rejected_requests = 0
+        self._timed_out_requests = 0
+        self._queued_requests = 0
+        self._peak_concurrent = 0
+        self._peak_queue_depth = 0
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._target]
+
+    @property
+    def target(self) -> Entity:
+        return self._target
+
+    @property
+    def max_concurrent(self) -> int:
+        return self._max_concurrent
+
+    @property
+    def max_wait_queue(self) -> int:
+        return self._max_wait_queue
+
+    @property
+    def max_wait_time(self) -> float | None:
+        return self._max_wait_time
+
+    @property
+    def active_count(self) -> int:
+        return self._active_count
+
+    @property
+    def queue_depth(self) -> int:
+        return len(self._wait_queue)
+
+    @property
+    def available_permits(self) -> int:
+        return max(0, self._max_concurrent - self._active_count)
+
+    @property
+    def stats(self) -> BulkheadStats:
+        return BulkheadStats(total_requests=self._total_requests, accepted_requests=self._accepted_requests,
+                             rejected_requests=self._rejected_requests, timed_out_requests=self._timed_out_requests,
+                             queued_requests=self._queued_requests, peak_concurrent=self._peak_concurrent,
+                             peak_queue_depth=self._peak_queue_depth)
+
+
+@dataclass(frozen=True)
+class TimeoutStats:
+    """timeout.py:32-38."""
+
+    total_requests: int = 0
+    successful_requests: int = 0
+    timed_out_requests: int = 0
+
+
+class TimeoutWrapper(Entity):
+    """A deadline of `timeout` seconds on every Request forwarded to `target` (timeout.py:41-295): the response -- the forwarded
+    Event's completion hook -- and the timeout Event each resolve the request if it is still in flight, whichever comes second is a
+    no-op.  `on_timeout` is a host callable: not lowered."""
+
+    def __init__(self, name: str, target: Entity, timeout: float, on_timeout=None):
+        super().__init__(name)
+        if timeout <= 0:                                                                  # timeout.py:76-77
+            raise ValueError(f"timeout must be > 0, got {timeout}")
+        self._target = target
+        self._timeout = timeout
+        self._on_timeout = on_timeout
+        self._in_flight: dict[int, dict] = {}     # after a run: the ids in flight
+        self._next_request_id = 0
+        self._total_requests = 0
+        self._successful_requests = 0
+        self._timed_out_requests = 0
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._target]
+
+    @property
+    def target(self) -> Entity:
+        return self._target
+
+    @property
+    def timeout(self) -> float:
+        return self._timeout
+
+    @property
+    def in_flight_count(self) -> int:
+        return len(self._in_flight)
+
+    @property
+    def stats(self) -> TimeoutStats:
+        return TimeoutStats(total_requests=self._total_requests, successful_requests=self._successful_requests,
+                            timed_out_requests=self._timed_out_requests)
+
+
 # ---- probes --------------------------------------------------------------------------------------
 class Data:
     """Time-series container of a Probe (instrumentation/data.py:20-110): `values` = [(time_s, value), ...]."""
@@ -1360,10 +1496,13 @@ class Data:
 class Probe(Entity):
     """Periodic metric sampler (instrumentation/probe.py:81-164): a daemon Source that reads `getattr(target, metric)`
     every `interval` seconds into a Data container.  Lowered metrics: Server.depth / active_requests / utilization / available_capacity / has_capacity /
-    stats_accepted / stats_dropped / requests completed, Sink.events_received, Source.generated_count, RateLimitedEntity.queue_depth."""
+    stats_accepted / stats_dropped / requests completed, Sink.events_received, Source.generated_count, RateLimitedEntity.queue_depth,
+    Bulkhead.active_count / queue_depth / available_permits, TimeoutWrapper.in_flight_count."""
 
     _LOWERED = {"depth", "active_requests", "utilization", "available_capacity", "has_capacity", "stats_accepted", "stats_dropped",
-                "requests_completed", "_requests_completed", "events_received", "generated_count", "_generated_count", "queue_depth"}
+                "requests_completed", "_requests_completed", "events_received", "generated_count", "_generated_count", "queue_depth",
+                "active_count", "available_permits", "in_flight_count"}
+    _ON_WRAPPER = {"active_count": Bulkhead, "available_permits": Bulkhead, "in_flight_count": TimeoutWrapper}
     # Server attributes that are functions of `active_requests` and the (fixed) concurrency: the engine samples the integer,
     # the Data container applies the reference's expression (components/server/server.py:153-173,191-200, concurrency.py:117-131)
     _ON_ACTIVE = ("utilization", "available_capacity", "has_capacity")
@@ -1388,7 +1527,8 @@ class Probe(Entity):
     def __init__(self, target: Entity, metric: str, data: Data, interval: float = 1.0, start_time: Instant | None = None):
         if interval <= 0:
             raise ValueError("Probe interval must be positive.")                  # probe.py:29-30
-        if metric not in self._LOWERED or (metric == "queue_depth" and not isinstance(target, RateLimitedEntity)):
+        if (metric not in self._LOWERED or (metric == "queue_depth" and not isinstance(target, (RateLimitedEntity, Bulkhead)))
+                or (metric in self._ON_WRAPPER and not isinstance(target, self._ON_WRAPPER[metric]))):
             raise NotImplementedError(f"probe metric '{metric}' is an arbitrary attribute; lowered: {sorted(self._LOWERED)}")
         super().__init__(f"Probe_{target.name}_{metric}")
         self.target = target

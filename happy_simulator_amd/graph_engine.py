@@ -22,10 +22,10 @@ import numpy as np
 
 from . import _native as N
 from .core.temporal import Instant
-from .entities import (BackendHealthState, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
+from .entities import (BackendHealthState, Bulkhead, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
                        ExponentialLatency, HealthChecker, IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random,
                        RandomRouter, RateLimitedEntity, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source,
-                       TokenBucketPolicy, WeightedLeastConnections, WeightedRoundRobin)
+                       TimeoutWrapper, TokenBucketPolicy, WeightedLeastConnections, WeightedRoundRobin)
 
 _STRATEGY_CODE = ((ConsistentHash, N.LB_CONSISTENT_HASH), (RoundRobin, N.LB_ROUND_ROBIN), (Random, N.LB_RANDOM),
                   (WeightedRoundRobin, N.LB_WEIGHTED_ROUND_ROBIN), (IPHash, N.LB_IP_HASH), (LeastConnections, N.LB_LEAST_CONNECTIONS),
@@ -77,9 +77,17 @@ class GraphArrays:
         self.lb_healthy = None               # [n_rt] uint8: BackendInfo.is_healthy per backend slot when the run begins (None: all healthy
                                              #   and no checker -- the graph has no health state)
 
+        self.wrap_params = None              # [n, 5] float64: BULKHEAD nodes -- max_concurrent, max_wait_queue, max_wait_time (-1: None);
+                                             #   TIMEOUT_WRAPPER nodes -- column 3 = timeout, column 4 = the in-flight table's first capacity
+                                             #   (0: the engine's default); set through hs_graph_set_wrapper
+
     @property
     def has_health(self) -> bool:
         return self.hc_params is not None or self.lb_healthy is not None
+
+    @property
+    def has_wrappers(self) -> bool:
+        return self.wrap_params is not None
 
     def struct(self) -> N.GraphNodes:
         s = N.GraphNodes()
@@ -103,7 +111,8 @@ class GraphEngine:
     """ctypes handle of one hs_graph.  No CPU fallback: without the library or a GPU the constructor raises."""
 
     def __init__(self, arrays: GraphArrays, *, seed: int = 42, start_ns: int = 0, device: int = 0, max_events: int = 0,
-                 heap_capacity: int = 0, request_capacity: int = 0, record_capacity: int = 0, profile_budget: int = 0):
+                 heap_capacity: int = 0, request_capacity: int = 0, record_capacity: int = 0, profile_budget: int = 0,
+                 table_capacity: int = 0):
         self._lib = N.lib()
         self.arrays = arrays
         cfg = N.GraphConfig(struct_size=C.sizeof(N.GraphConfig), device=device, start_ns=start_ns, seed=seed,
@@ -157,6 +166,38 @@ class GraphEngine:
             except BaseException:
                 self.close()
                 raise
+
+        if arrays.has_wrappers:
+            try:
+                for i in np.nonzero((arrays.kind == N.NODE_BULKHEAD) | (arrays.kind == N.NODE_TIMEOUT_WRAPPER))[0]:
+                    mc, mq, mw, to, cap = arrays.wrap_params[i]
+                    self._check(self._lib.hs_graph_set_wrapper(self._h, int(i), int(mc), int(mq), float(mw), float(to),
+                                                               int(table_capacity) if table_capacity else int(cap)))
+            except BaseException:
+                self.close()
+                raise
+
+    def wrapper(self, node: int) -> dict:
+        """hs_graph_get_wrapper of a Bulkhead or TimeoutWrapper node: its counters by name, the ids of its wait queue (head first) and
+        the ids in flight (ascending)."""
+        c = np.zeros(N.WRAPPER_COUNTERS, np.int64)
+        self._check(self._lib.hs_graph_get_wrapper(self._h, int(node), _ptr(c), None, 0, None, 0, None))
+        queue, live = np.zeros(max(int(c[8]), 1), np.int64), np.zeros(max(int(c[10]), 1), np.int64)
+        self._check(self._lib.hs_graph_get_wrapper(self._h, int(node), None, _ptr(queue), int(c[8]), _ptr(live), int(c[10]), None))
+        names = ("total", "accepted", "rejected", "timed_out", "queued", "peak_concurrent", "peak_queue_depth", "active_count", "queue_depth",
+                 "next_request_id", "in_flight_count", "table_capacity")
+        if self.arrays.kind[node] == N.NODE_TIMEOUT_WRAPPER:
+            names = ("total", "successful", "timed_out") + ("",) * 6 + names[9:]
+        out = {k: int(v) for k, v in zip(names, c) if k}
+        out["queue_ids"] = queue[:int(c[8])]
+        out["in_flight_ids"] = np.sort(live[:int(c[10])])
+        return out
+
+    def wrapper_events(self) -> np.ndarray:
+        """The graph's Bulkhead request / response / timeout and TimeoutWrapper request / response / timeout Events of the run."""
+        events = np.zeros(6, np.int64)
+        self._check(self._lib.hs_graph_get_wrapper(self._h, -1, None, None, 0, None, 0, _ptr(events)))
+        return events
 
     def health(self, node: int) -> dict:
         """hs_graph_get_health of a HealthChecker or LoadBalancer node: checker stats, per-backend states, the LoadBalancer's health
@@ -310,7 +351,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             raise UnsupportedTopology(f"probe '{pr.name}' is listed twice")
         add(pr)
     n_front = len(nodes)
-    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker) + _SINKS
+    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker, Bulkhead, TimeoutWrapper) + _SINKS
 
     def check(ent, where):
         if isinstance(ent, Source):
@@ -389,12 +430,13 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
                     a.src_profile_params[i] = (pr.baseline_rate, pr.spike_rate, pr.warmup_s, pr.spike_duration_s)
         elif isinstance(ent, Probe):
             m = Probe.engine_metric(ent.metric)
-            if m not in N.PROBE_METRICS:
-                raise UnsupportedTopology(f"probe '{ent.name}': metric '{ent.metric}' is not sampled on the engine")
             tgt = ent.target
+            on_wrapper = isinstance(tgt, (Bulkhead, TimeoutWrapper)) and m in N.PROBE_WRAPPER_METRICS
+            if m not in N.PROBE_METRICS and not on_wrapper:
+                raise UnsupportedTopology(f"probe '{ent.name}': metric '{ent.metric}' is not sampled on the engine")
             if id(tgt) not in node_of:
                 raise UnsupportedTopology(f"probe '{ent.name}': its target is not an entity of this Simulation")
-            want = Source if m == "generated_count" else _SINKS if m == "events_received" else RateLimitedEntity if m == "queue_depth" else Server
+            want = (TimeoutWrapper if m == "in_flight_count" else Bulkhead) if on_wrapper else Source if m == "generated_count" else _SINKS if m == "events_received" else RateLimitedEntity if m == "queue_depth" else Server
             if not isinstance(tgt, want):
                 raise UnsupportedTopology(f"probe '{ent.name}': metric '{ent.metric}' is not an attribute of {type(tgt).__name__}")
             if a.probe_metric is None:
@@ -402,7 +444,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
                 a.probe_interval_s = np.ones(n, np.float64)
             a.kind[i] = N.NODE_PROBE
             a.target[i] = node_of[id(tgt)]
-            a.probe_metric[i] = N.PROBE_METRICS[m]
+            a.probe_metric[i] = N.PROBE_WRAPPER_METRICS[m] if on_wrapper else N.PROBE_METRICS[m]
             a.probe_interval_s[i] = ent.interval
         elif isinstance(ent, Server):
             svc = ent.service_time
@@ -482,6 +524,38 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             a.kind[i] = N.NODE_HEALTH_CHECKER
             a.target[i] = node_of[id(lb)]
             a.hc_params[i] = (ent.interval, ent.timeout, ent.healthy_threshold, ent.unhealthy_threshold, 1.0 if ent.is_running else 0.0)
+        elif isinstance(ent, (Bulkhead, TimeoutWrapper)):
+            what = f"{type(ent).__name__} '{ent.name}'"
+            tgt = ent.target
+            if isinstance(tgt, (Source, Probe, HealthChecker)) or not isinstance(tgt, Entity) or id(tgt) not in node_of:
+                raise UnsupportedTopology(f"{what}: its target {type(tgt).__name__} '{getattr(tgt, 'name', tgt)}' takes no Requests")
+            end, hops = tgt, 0
+            while isinstance(end, NetworkLink) and end.egress is not None and hops <= n:
+                end, hops = end.egress, hops + 1
+            if isinstance(end, (LoadBalancer, Bulkhead, TimeoutWrapper)):
+                via = " (through its NetworkLinks)" if end is not tgt else ""
+                raise UnsupportedTopology(f"{what}: its target{via} is the {type(end).__name__} '{end.name}' -- two completion hooks on one "
+                                          "Event are not lowered (a follow-up)")
+            if a.wrap_params is None:
+                a.wrap_params = np.zeros((n, 5), np.float64)
+            a.target[i] = node_of[id(tgt)]
+            if isinstance(ent, Bulkhead):
+                if ent.max_concurrent > Bulkhead.MAX_CONCURRENT:
+                    raise UnsupportedTopology(f"{what}: max_concurrent = {ent.max_concurrent} is beyond the {Bulkhead.MAX_CONCURRENT} request "
+                                              "ids the engine's in-flight table holds")
+                if ent.max_wait_queue > (1 << 30):
+                    raise UnsupportedTopology(f"{what}: max_wait_queue = {ent.max_wait_queue} is beyond 2^30")
+                if ent.max_wait_time is not None and not np.isfinite(ent.max_wait_time):
+                    raise UnsupportedTopology(f"{what}: max_wait_time must be finite or None")
+                a.kind[i] = N.NODE_BULKHEAD
+                a.wrap_params[i, :3] = (ent.max_concurrent, ent.max_wait_queue, -1.0 if ent.max_wait_time is None else ent.max_wait_time)
+            else:
+                if ent._on_timeout is not None:
+                    raise UnsupportedTopology(f"{what}: on_timeout= is a host callable (not lowered)")
+                if not np.isfinite(ent.timeout):
+                    raise UnsupportedTopology(f"{what}: timeout must be finite")
+                a.kind[i] = N.NODE_TIMEOUT_WRAPPER
+                a.wrap_params[i, 3] = ent.timeout
         elif isinstance(ent, RateLimitedEntity):
             pol = ent.policy
             if type(pol) not in LIMITER_POLICIES:
@@ -581,7 +655,7 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
     new_index = np.empty(n, np.int64)
     per_node = [nm for nm in ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s",
                               "link_lat_min_s", "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric",
-                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params")
+                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params")
                 if getattr(a, nm) is not None]
     names = None if a.names is None else [a.names[a.name_off[i]:a.name_off[i + 1]] for i in range(n)]
     parts = []
@@ -612,6 +686,8 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
             b.hc_params = None                                             # (a part without a checker: no health state unless a flag says so)
         if b.lb_healthy is not None and b.hc_params is None and b.lb_healthy.all():
             b.lb_healthy = None
+        if b.wrap_params is not None and not ((b.kind == N.NODE_BULKHEAD) | (b.kind == N.NODE_TIMEOUT_WRAPPER)).any():
+            b.wrap_params = None                                           # (a part without a wrapper runs the loop it would run alone)
         if names is not None:
             blobs = [names[i] for i in ids]
             b.names = b"".join(blobs)
@@ -675,6 +751,16 @@ class PartRun:
 
     def health_events(self) -> np.ndarray:
         return np.sum([e.health_events() for e in self.engines], axis=0).astype(np.int64)
+
+    def wrapper_events(self) -> np.ndarray:
+        return np.sum([e.wrapper_events() for e in self.engines], axis=0).astype(np.int64)
+
+    def wrapper(self, node: int) -> dict:
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            at = np.searchsorted(ids, node)
+            if at < len(ids) and ids[at] == node:
+                return e.wrapper(int(at))
+        raise KeyError(node)
 
     def health(self, node: int) -> dict:
         for (ids, _pos, _b), e in zip(self.parts, self.engines):
@@ -745,9 +831,10 @@ def keyless_hazard(g: "GeneralGraph", target) -> str | None:
 
 
 def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t: np.ndarray, rec_cr: np.ndarray, device: int = 0,
-                       health=None) -> None:
+                       health=None, wrapper=None) -> None:
     """The run's per-node results onto the user's objects, under the attribute names the reference uses (lowering.write_back's
-    counterpart).  `health`: node -> GraphEngine.health(node) of a graph with health state."""
+    counterpart).  `health`: node -> GraphEngine.health(node) of a graph with health state; `wrapper`: node -> GraphEngine.wrapper(node)
+    of a graph with a Bulkhead or a TimeoutWrapper."""
     a = g.arrays
     order = np.argsort(rec_node, kind="stable")              # per Sink, still in processing order
     bounds = np.searchsorted(rec_node[order], np.arange(a.n + 1))
@@ -809,6 +896,19 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
                 ent._backend_states[b.name] = BackendHealthState(succ, fail, Instant(last_ns), None if passed < 0 else bool(passed), bool(checking))
                 if pending:
                     ent._pending_checks[b.name] = pending
+        elif isinstance(ent, Bulkhead):
+            w = wrapper(i)
+            (ent._total_requests, ent._accepted_requests, ent._rejected_requests, ent._timed_out_requests, ent._queued_requests,
+             ent._peak_concurrent, ent._peak_queue_depth, ent._active_count) = (w[k] for k in (
+                 "total", "accepted", "rejected", "timed_out", "queued", "peak_concurrent", "peak_queue_depth", "active_count"))
+            ent._next_request_id = w["next_request_id"]
+            ent._wait_queue = [int(x) for x in w["queue_ids"]]
+            ent._in_flight = {int(x): {} for x in w["in_flight_ids"]}
+        elif isinstance(ent, TimeoutWrapper):
+            w = wrapper(i)
+            ent._total_requests, ent._successful_requests, ent._timed_out_requests = w["total"], w["successful"], w["timed_out"]
+            ent._next_request_id = w["next_request_id"]
+            ent._in_flight = {int(x): {} for x in w["in_flight_ids"]}
         elif isinstance(ent, RateLimitedEntity):
             st = stats["limiters"][i]
             ent._received, ent._forwarded, ent._queued, ent._dropped = (int(st[k]) for k in ("received", "forwarded", "queued", "dropped"))

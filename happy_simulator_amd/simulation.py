@@ -14,7 +14,7 @@ from .core.temporal import Instant
 from .engine import StationEngine
 from .graph_engine import (DEFAULT_MAX_EVENTS, MAX_PARTS, GeneralGraph, GraphEngine, PartRun, keyless_hazard, lower_general, split_parts,
                            write_back_general)
-from .entities import Entity, HealthChecker, LoadBalancer, Server
+from .entities import Bulkhead, Entity, HealthChecker, LoadBalancer, Server, TimeoutWrapper
 from .faults import FaultSchedule
 from .lowering import (LazyRecords, LbGraph, LoweredGraph, UnsupportedTopology, attach_lb_probes, attach_probes, find_load_balancer, lower,
                        plain_probe_arrays, write_back_plain_probes,
@@ -132,7 +132,16 @@ class Simulation:
         not the full one), which only the single-heap loop follows."""
         return any(isinstance(e, HealthChecker) or (isinstance(e, LoadBalancer) and e.unhealthy_backends) for e in self._entities)
 
+    def _has_wrappers(self) -> bool:
+        """A Bulkhead or a TimeoutWrapper among the entities or as a Source's target: completion hooks and per-request ids, which only
+        the single-heap loop follows."""
+        firsts = [getattr(getattr(s, "_event_provider", None), "_target", None) for s in self._sources]
+        return any(isinstance(e, (Bulkhead, TimeoutWrapper)) for e in self._entities + firsts)
+
     def lowered(self) -> "LoweredGraph | LbGraph | GeneralGraph":
+        if self._graph is None and self._has_wrappers():
+            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._station_refusal = "the station, network and pipeline engines do not lower Bulkhead or TimeoutWrapper"
         if self._graph is None and not self._faults and self._has_health():
             self._graph = lower_general(self._sources, self._entities, self._probes)
             self._station_refusal = "the station, network and pipeline engines do not lower health checks or unhealthy backends"
@@ -448,15 +457,19 @@ class Simulation:
         es = eng.summary()
         stats = eng.stats()
         rec = eng.records()
-        health = g.arrays.has_health
-        write_back_general(g, stats, *rec, device=self._device, health=eng.health if health else None)
+        health, wrappers = g.arrays.has_health, g.arrays.has_wrappers
+        write_back_general(g, stats, *rec, device=self._device, health=eng.health if health else None,
+                           wrapper=eng.wrapper if wrappers else None)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
         if health:
             # the checkers' cycle / response / timeout Events: internal kinds like the limiters' and the faults' (events_processed
             # counts them, events_by_kind does not)
             self._health_by_kind = eng.health_events()
-        if health and not self._faults:
+        if wrappers:
+            # the wrappers' request / response / timeout Events: six more internal kinds, counted the same way
+            self._resilience_by_kind = eng.wrapper_events()
+        if (health or wrappers) and not self._faults:
             self._internal_by_kind = eng.faults()[1]
         if self._faults:
             crashed, internal, popped_cancelled = eng.faults()

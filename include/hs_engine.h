@@ -189,6 +189,10 @@ typedef enum hs_probe_metric {
     HS_PROBE_RECEIVED = 5,     /* Sink.events_received */
     HS_PROBE_GENERATED = 6,    /* Source.generated_count */
     HS_PROBE_LIMITER_DEPTH = 7,/* RateLimitedEntity.queue_depth (general graphs only) */
+    HS_PROBE_BH_ACTIVE = 8,    /* Bulkhead.active_count (general graphs only, like the three below) */
+    HS_PROBE_BH_QUEUE_DEPTH = 9,   /* Bulkhead.queue_depth */
+    HS_PROBE_BH_PERMITS = 10,  /* Bulkhead.available_permits */
+    HS_PROBE_TW_IN_FLIGHT = 11,/* TimeoutWrapper.in_flight_count */
     HS_PROBE_NONE = 255
 } hs_probe_metric;
 typedef enum hs_profile_kind { HS_PROF_CONSTANT = 0, HS_PROF_LINEAR_RAMP = 1, HS_PROF_SPIKE = 2 } hs_profile_kind;
@@ -731,7 +735,9 @@ typedef struct hs_graph hs_graph;
 
 typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK = 2, HS_NODE_LINK = 3, HS_NODE_ROUTER = 4, HS_NODE_PROBE = 5, HS_NODE_LB = 6,
                              HS_NODE_RATE_LIMITER = 7, /* RateLimitedEntity: `target` = its downstream, `queue_cap` = its FIFO capacity; policy: hs_graph_set_limiter_policy */
-                             HS_NODE_HEALTH_CHECKER = 8 /* HealthChecker: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_health_checker */
+                             HS_NODE_HEALTH_CHECKER = 8, /* HealthChecker: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_health_checker */
+                             HS_NODE_BULKHEAD = 9,        /* Bulkhead: `target` = the entity it protects; everything else: hs_graph_set_wrapper */
+                             HS_NODE_TIMEOUT_WRAPPER = 10 /* TimeoutWrapper: `target` = the entity it wraps; everything else: hs_graph_set_wrapper */
 } hs_node_kind;
 
 typedef struct hs_graph_config {
@@ -924,6 +930,40 @@ int hs_graph_get_health(hs_graph *g, int32_t node, int64_t *checker_stats, int64
  * and, if not NULL, present[n] = the dict has an entry for the backend (it was healthy at one selection at least, strategies.py:117-119);
  * 0 when the graph has none (the periodic table ran: the weights follow from the selection counts); negative: an hs_status. */
 int64_t hs_graph_get_lb_current_weights(hs_graph *g, int32_t node, int64_t *out, uint8_t *present, int32_t n);
+/* Client-side guards: Bulkhead and TimeoutWrapper (components/resilience/bulkhead.py, timeout.py).  A graph that holds one runs a
+ * fourth instantiation of the loop (it carries the fault and health code too).  A Request at a wrapper is forwarded as a NEW Event
+ * for `target` with the wrapper's completion hook; the hook's `_bh_response` / `_tw_response` Event is constructed when the handler
+ * that receives the forwarded Event returns -- a Server's enqueue (accepted or refused), a Sink, a RandomRouter, a RateLimitedEntity's
+ * request handler, a NetworkLink at the end of transit (at once on a lost packet) -- behind that handler's own Events.  A NetworkLink
+ * leaves the hook on the Event it constructs for its egress, so the egress' handler fires it a second time (link.py:181): the second
+ * response finds no id and is a processed no-op, as in the reference.  An Event aimed at a crashed entity is dropped before any handler
+ * runs: no hook fires, a Bulkhead's permit leaks, a TimeoutWrapper's id waits for its timeout.  Six more internal kinds -- request,
+ * response, timeout of a Bulkhead, then of a TimeoutWrapper -- are aimed at the wrapper itself (dropped while it is crashed); they count
+ * in hs_summary.events_processed, not in events_by_kind.
+ * Refused (HS_E_UNSUPPORTED): a wrapper whose target is, directly or through a chain of NetworkLinks, a LoadBalancer, a Bulkhead or a
+ * TimeoutWrapper (two hooks on one Event); Bulkhead.max_concurrent above HS_BULKHEAD_MAX_CONCURRENT.
+ *
+ * hs_graph_set_wrapper: the parameters of node `node`.  A Bulkhead takes max_concurrent, max_wait_queue and max_wait_time_s (negative:
+ * None); a TimeoutWrapper takes timeout_s and table_capacity, the request ids its in-flight table holds at first (0: 256) -- a full
+ * table stops the launch in front of the Request, the host doubles it and the run goes on, nothing is ever dropped.  The reference's own
+ * ValueErrors as HS_E_INVALID with its texts.  Before the first run (HS_E_STATE afterwards); every wrapper node is configured before a
+ * run (HS_E_STATE otherwise). */
+#define HS_BULKHEAD_MAX_CONCURRENT 65536
+#define HS_WRAPPER_COUNTERS 12
+int hs_graph_set_wrapper(hs_graph *g, int32_t node, int32_t max_concurrent, int32_t max_wait_queue, double max_wait_time_s, double timeout_s,
+                         int32_t table_capacity);
+/* After a run, for `node` a Bulkhead or a TimeoutWrapper (any output may be NULL):
+ *   counters[HS_WRAPPER_COUNTERS]  Bulkhead: total, accepted, rejected, timed_out, queued requests, peak_concurrent, peak_queue_depth,
+ *                     active_count, queue_depth, _next_request_id, len(_in_flight), the table's capacity;
+ *                     TimeoutWrapper: total, successful, timed_out, five zeros, 0, _next_request_id, len(_in_flight), the table's capacity;
+ *   queue_ids[min(queue_depth, queue_cap)]  the request ids of a Bulkhead's wait queue, head first;
+ *   in_flight_ids[min(len(_in_flight), in_flight_cap)]  the ids in flight, in no particular order;
+ *   events[6]         the graph's Bulkhead request / response / timeout and TimeoutWrapper request / response / timeout Events, counted
+ *                     like events_by_kind counts the public kinds: events_processed == sum(events_by_kind) + sum(internal_by_kind of
+ *                     hs_graph_get_faults) + sum(events of hs_graph_get_health) + sum(events).
+ * node = -1 with the three node outputs NULL: the event counts alone. */
+int hs_graph_get_wrapper(hs_graph *g, int32_t node, int64_t *counters, int64_t *queue_ids, int64_t queue_cap, int64_t *in_flight_ids,
+                         int64_t in_flight_cap, int64_t *events);
 /* Auto-termination (core/simulation.py:306-322, end_time = Infinity): a run to end_ns = 2^61 ends in front of a pop when only daemon
  * events -- the limiters' polls -- are pending.  A run with any other end processes polls like any event. */
 /* Debug / tests only (no engine path calls it; the null stream, its own allocations): FixedWindowPolicy._get_window_start on the device, one (now_ns, window_s) pair per thread: out_div[i] = Python's float
