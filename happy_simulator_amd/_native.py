@@ -426,6 +426,13 @@ def lib():
     L.hs_debug_draws.restype = C.c_int
     L.hs_debug_draws.argtypes = [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_double,
                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hs_debug_log.restype = C.c_int
+    L.hs_debug_log.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hs_debug_philox.restype = C.c_int
+    L.hs_debug_philox.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    L.hs_debug_stream_walk.restype = C.c_int
+    L.hs_debug_stream_walk.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]
     L.hs_debug_const_div.restype = C.c_int
     L.hs_debug_const_div.argtypes = [C.c_int32, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_debug_time_ops.restype = C.c_int
@@ -553,6 +560,7 @@ EXPORTED_SYMBOLS = (
     "hs_engine_read_probe_slot", "hs_engine_read_source_generated",
     "hs_last_error", "hs_last_global_error", "hs_engine_destroy", "hs_debug_draws", "hs_debug_set_flags",
     "hs_debug_const_div", "hs_debug_time_ops", "hs_debug_async_counters",
+    "hs_debug_log", "hs_debug_philox", "hs_debug_stream_walk",
     "hs_lb_create", "hs_lb_run", "hs_lb_run_path", "hs_lb_bench_runs", "hs_lb_get_summary", "hs_lb_get_stats", "hs_lb_read_sink",
     "hs_lb_set_probes", "hs_lb_read_probe",
     "hs_lb_latency_stats",

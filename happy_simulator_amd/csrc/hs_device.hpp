@@ -58,7 +58,10 @@ __device__ __forceinline__ double res53(uint32_t a, uint32_t b) {
 }
 
 // Natural log for normal positive x (engine passes x in [2^-53, 1]).  Same operation sequence as
-// oracle/hs_rng_ref.h hs_log_ref and tests/golden/hs_streams_py.py hs_log.
+// oracle/hs_rng_ref.h hs_log_ref and tests/golden/hs_streams_py.py hs_log.  Pinned to them bit for bit at chosen inputs -- every
+// exponent, the two high words around the k switch (0x6a09c), all 2^20 high words of [0.5, 1), u = 0 (E = -0.0) -- together with
+// philox4x32_10, res53 and Stream::next* below: tests/test_streams_host.py (this text, compiled for the host) and
+// tests/test_gpu_streams.py (the device code, through hs_debug_log / hs_debug_philox / hs_debug_stream_walk).
 __device__ __forceinline__ double hs_log(double x) {
     constexpr double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10,
                      Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01,

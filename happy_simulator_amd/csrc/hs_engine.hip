@@ -2039,6 +2039,95 @@ int hs_debug_draws(int32_t device, uint64_t seed, uint64_t sid, uint64_t k0, int
     return HS_OK;
 }
 
+// The three hooks below share one shape: host arrays up, one launch, the results down, every device buffer freed on every path.
+namespace {
+struct DebugBuffers {
+    void *d[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~DebugBuffers() { for (void *p : d) if (p) (void)hipFree(p); }
+    hipError_t alloc(const size_t *bytes, int n) {
+        for (int k = 0; k < n; ++k) {
+            const hipError_t e = hipMalloc(&d[k], bytes[k]);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+};
+int debug_device(const char *who, int32_t device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, HS_E_NO_DEVICE, "no HIP device visible: the engine has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(nullptr, HS_E_INVALID, "%s: device ordinal %d out of range (%d devices)", who, device, ndev);
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, HS_E_HIP, "%s: hipSetDevice failed", who);
+    return HS_OK;
+}
+}  // namespace
+
+int hs_debug_log(int32_t device, int64_t n, const double *x, const double *u, double *out_log, double *out_exp1) {
+    if (n <= 0 || !x || !u || !out_log || !out_exp1) return fail(nullptr, HS_E_INVALID, "hs_debug_log: bad arguments");
+    if (const int rc = debug_device("hs_debug_log", device)) return rc;
+    const size_t b = (size_t)n * 8, bytes[4] = {b, b, b, b};
+    DebugBuffers m;
+    hipError_t e = m.alloc(bytes, 4);
+    if (e == hipSuccess) e = hipMemcpy(m.d[0], x, b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m.d[1], u, b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(hs_debug_log_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, (const double *)m.d[0],
+                           (const double *)m.d[1], (double *)m.d[2], (double *)m.d[3]);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out_log, m.d[2], b, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_exp1, m.d[3], b, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(nullptr, HS_E_HIP, "hs_debug_log: %s", hipGetErrorString(e));
+    return HS_OK;
+}
+
+int hs_debug_philox(int32_t device, int64_t n, const uint32_t *ctr_key, uint32_t *out) {
+    if (n <= 0 || !ctr_key || !out) return fail(nullptr, HS_E_INVALID, "hs_debug_philox: bad arguments");
+    if (const int rc = debug_device("hs_debug_philox", device)) return rc;
+    const size_t bytes[2] = {(size_t)n * 24, (size_t)n * 16};
+    DebugBuffers m;
+    hipError_t e = m.alloc(bytes, 2);
+    if (e == hipSuccess) e = hipMemcpy(m.d[0], ctr_key, bytes[0], hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(hs_debug_philox_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, (const uint32_t *)m.d[0],
+                           (uint32_t *)m.d[1]);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, m.d[1], bytes[1], hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(nullptr, HS_E_HIP, "hs_debug_philox: %s", hipGetErrorString(e));
+    return HS_OK;
+}
+
+int hs_debug_stream_walk(int32_t device, int64_t n_walks, const uint64_t *seed, const uint64_t *sid, const uint64_t *k0,
+                         int32_t n_steps, const uint8_t *steps, double *out, uint64_t *k_end) {
+    if (n_walks <= 0 || n_steps <= 0 || !seed || !sid || !k0 || !steps || !out || !k_end)
+        return fail(nullptr, HS_E_INVALID, "hs_debug_stream_walk: bad arguments");
+    int64_t row = 0;
+    for (int32_t j = 0; j < n_steps; ++j) {
+        if (steps[j] != 1 && steps[j] != 2 && steps[j] != 4)
+            return fail(nullptr, HS_E_INVALID, "hs_debug_stream_walk: steps[%d] = %d (each step draws 1, 2 or 4)", j, (int)steps[j]);
+        row += steps[j];
+    }
+    if (const int rc = debug_device("hs_debug_stream_walk", device)) return rc;
+    const size_t w = (size_t)n_walks * 8, bytes[6] = {w, w, w, (size_t)n_steps, w * (size_t)row, w};
+    DebugBuffers m;
+    hipError_t e = m.alloc(bytes, 6);
+    if (e == hipSuccess) e = hipMemcpy(m.d[0], seed, w, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m.d[1], sid, w, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m.d[2], k0, w, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m.d[3], steps, (size_t)n_steps, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(hs_debug_stream_walk_kernel, dim3((unsigned)((n_walks + 63) / 64)), dim3(64), 0, 0, n_walks,
+                           (const uint64_t *)m.d[0], (const uint64_t *)m.d[1], (const uint64_t *)m.d[2], n_steps,
+                           (const uint8_t *)m.d[3], row, (double *)m.d[4], (uint64_t *)m.d[5]);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, m.d[4], bytes[4], hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(k_end, m.d[5], w, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(nullptr, HS_E_HIP, "hs_debug_stream_walk: %s", hipGetErrorString(e));
+    return HS_OK;
+}
+
 // The tick table of ONE stream (csrc/hs_tables.hpp) -- `lone` = 0: the cooperative kernel the engine uses; 1: the same chain on
 // one lane with the sequential integrator (the device-side reference: tests/test_gpu_tables.py compares the two bit for bit).
 // profile: {kind, p0, p1, p2, p3}; returns the number of entries written to out_times (<= cap), or < 0.

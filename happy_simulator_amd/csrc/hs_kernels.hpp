@@ -2090,6 +2090,52 @@ __global__ void hs_debug_draws_kernel(uint64_t seed, uint64_t sid, uint64_t k0, 
     u[i] = uu; e[i] = ee;
     ns[i] = ns_from_seconds(__ddiv_rn(ee, rate));
 }
+// test hooks: the stream functions of hs_device.hpp at CHOSEN inputs (tests/test_gpu_streams.py) -- hs_log and exp1_from_uniform,
+// one input per thread ...
+__global__ void hs_debug_log_kernel(int64_t n, const double *__restrict__ x, const double *__restrict__ u, double *__restrict__ out_log,
+                                    double *__restrict__ out_exp1) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out_log[i] = hs_log(x[i]);
+    out_exp1[i] = exp1_from_uniform(u[i]);
+}
+// ... the raw Philox4x32-10 block, all 128 bits: ctr_key[6 i ..] = {c0, c1, c2, c3, k0, k1} -> out[4 i ..]
+__global__ void hs_debug_philox_kernel(int64_t n, const uint32_t *__restrict__ ctr_key, uint32_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t *c = ctr_key + 6 * i;
+    const U4 o = philox4x32_10(c[0], c[1], c[2], c[3], c[4], c[5]);
+    out[4 * i] = o.x; out[4 * i + 1] = o.y; out[4 * i + 2] = o.z; out[4 * i + 3] = o.w;
+}
+// ... and one Stream per thread walked by next_uniform / next2 / next4 as steps[] says (each 1, 2 or 4; `row` = their sum, checked
+// by the host): the values in draw order, then the stream's final k
+__global__ void hs_debug_stream_walk_kernel(int64_t n_walks, const uint64_t *__restrict__ seed, const uint64_t *__restrict__ sid,
+                                            const uint64_t *__restrict__ k0, int32_t n_steps, const uint8_t *__restrict__ steps,
+                                            int64_t row, double *__restrict__ out, uint64_t *__restrict__ k_end) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_walks) return;
+    Stream s;
+    s.init(seed[i], sid[i], k0[i]);
+    double *o = out + i * row;
+    int64_t pos = 0;
+    for (int32_t j = 0; j < n_steps; ++j) {
+        const int st = steps[j];
+        if (pos + st > row) break;
+        if (st == 4) {
+            double u[4];
+            s.next4(u);
+            o[pos] = u[0]; o[pos + 1] = u[1]; o[pos + 2] = u[2]; o[pos + 3] = u[3];
+        } else if (st == 2) {
+            double u[2];
+            s.next2(u);
+            o[pos] = u[0]; o[pos + 1] = u[1];
+        } else {
+            o[pos] = s.next_uniform();
+        }
+        pos += st;
+    }
+    k_end[i] = s.k;
+}
 
 // test hook: constant-divisor quotients (ConstDiv, seconds_from_ns) next to the IEEE division
 __global__ void hs_debug_const_div_kernel(double b, int64_t n, const double *a, double *q_fast, double *q_ieee,

@@ -466,6 +466,50 @@ def debug_draws(seed: int, sid: int, k0: int, n: int, rate: float, device: int =
     return u, e, ns
 
 
+def _debug_rc(L, rc: int) -> None:
+    if rc == N.HS_E_NO_DEVICE:
+        raise N.EngineUnavailable(L.hs_last_global_error().decode())
+    if rc < 0:
+        raise N.EngineError(rc, L.hs_last_global_error().decode())
+
+
+def debug_log(x: np.ndarray, u: np.ndarray, device: int = 0):
+    """Device-side (hs_log(x), exp1_from_uniform(u)) elementwise -- test hook (include/hs_engine.h hs_debug_log)."""
+    L = N.lib()
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    assert x.ndim == u.ndim == 1 and len(x) == len(u) > 0
+    out_log, out_exp1 = np.zeros(len(x), np.float64), np.zeros(len(x), np.float64)
+    _debug_rc(L, L.hs_debug_log(device, len(x), x.ctypes.data, u.ctypes.data, out_log.ctypes.data, out_exp1.ctypes.data))
+    return out_log, out_exp1
+
+
+def debug_philox(ctr_key: np.ndarray, device: int = 0) -> np.ndarray:
+    """Device-side raw Philox4x32-10 blocks: rows {c0, c1, c2, c3, k0, k1} of uint32 -> rows of 4 uint32 -- test hook."""
+    L = N.lib()
+    ctr_key = np.ascontiguousarray(ctr_key, np.uint32)
+    assert ctr_key.ndim == 2 and ctr_key.shape[1] == 6 and len(ctr_key) > 0
+    out = np.zeros((len(ctr_key), 4), np.uint32)
+    _debug_rc(L, L.hs_debug_philox(device, len(ctr_key), ctr_key.ctypes.data, out.ctypes.data))
+    return out
+
+
+def debug_stream_walk(seed, sid, k0, steps, device: int = 0):
+    """One device-side Stream per (seed[w], sid[w], k0[w]), walked by next_uniform / next2 / next4 as `steps` (each 1, 2 or 4,
+    shared by all walks) says -> (the draws [n_walks][sum(steps)] in draw order, the final draw index of every walk) -- test hook."""
+    L = N.lib()
+    seed = np.ascontiguousarray(seed, np.uint64)
+    sid = np.ascontiguousarray(sid, np.uint64)
+    k0 = np.ascontiguousarray(k0, np.uint64)
+    steps = np.ascontiguousarray(steps, np.uint8)
+    assert seed.ndim == 1 and seed.shape == sid.shape == k0.shape and len(seed) > 0 and steps.ndim == 1 and len(steps) > 0
+    out = np.zeros((len(seed), int(steps.sum(dtype=np.int64))), np.float64)
+    k_end = np.zeros(len(seed), np.uint64)
+    _debug_rc(L, L.hs_debug_stream_walk(device, len(seed), seed.ctypes.data, sid.ctypes.data, k0.ctypes.data, len(steps),
+                                        steps.ctypes.data, out.ctypes.data, k_end.ctypes.data))
+    return out, k_end
+
+
 def debug_const_div(a: np.ndarray, b: float, device: int = 0):
     """Device-side a / b by the constant-divisor sequence, by IEEE division, and seconds_from_ns(int(a)) -- test hook."""
     L = N.lib()

@@ -685,6 +685,17 @@ int hs_debug_async_counters(hs_engine *h, unsigned long long out[4]);
 
 int hs_debug_draws(int32_t device, uint64_t seed, uint64_t sid, uint64_t k0, int64_t n, double rate,
                    double *u, double *e, int64_t *ns);
+/* Debug: the stream functions of csrc/hs_device.hpp at CHOSEN inputs, host arrays in and out, one element per thread
+ * (tests/test_gpu_streams.py compares every bit with the oracle).
+ *   hs_debug_log          out_log[i] = hs_log(x[i]) (x normal and positive), out_exp1[i] = exp1_from_uniform(u[i])
+ *   hs_debug_philox       ctr_key[6 i ..] = {c0, c1, c2, c3, k0, k1} -> out[4 i ..] = the raw Philox4x32-10 block, all 128 bits
+ *   hs_debug_stream_walk  one thread per walk: Stream::init(seed[w], sid[w], k0[w]), then for each of the n_steps entries of
+ *                         `steps` (shared by all walks; each 1, 2 or 4) next_uniform / next2 / next4; out[w][..] = the
+ *                         sum(steps) values in draw order, k_end[w] = the stream's final draw index. */
+int hs_debug_log(int32_t device, int64_t n, const double *x, const double *u, double *out_log, double *out_exp1);
+int hs_debug_philox(int32_t device, int64_t n, const uint32_t *ctr_key, uint32_t *out);
+int hs_debug_stream_walk(int32_t device, int64_t n_walks, const uint64_t *seed, const uint64_t *sid, const uint64_t *k0,
+                         int32_t n_steps, const uint8_t *steps, double *out, uint64_t *k_end);
 
 /* Evaluation budget of the tick-table kernel (csrc/hs_tables.hpp): adaptive-Simpson intervals ONE lane may visit for ONE
  * arrival of a time-varying Source (64 lanes share an integral).  Replaces nothing in the reference -- its integrator

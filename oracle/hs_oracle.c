@@ -1070,6 +1070,16 @@ void hso_destroy(hso_sim *s) {
 double hso_uniform(uint64_t seed, uint64_t sid, uint64_t k) { return hsr_uniform(seed, sid, k); }
 double hso_log(double x) { return hs_log_ref(x); }
 void hso_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) { hsr_philox4x32_10(ctr, key, out); }
+/* the same three over arrays (one call for the 4 x 10^6 inputs of tests/stream_cases.py) */
+void hso_log_v(int64_t n, const double *x, double *out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = hs_log_ref(x[i]);
+}
+void hso_uniform_v(uint64_t seed, uint64_t sid, uint64_t k0, int64_t n, double *out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = hsr_uniform(seed, sid, k0 + (uint64_t)i);
+}
+void hso_philox_v(int64_t n, const uint32_t *ctr_key, uint32_t *out) {
+    for (int64_t i = 0; i < n; ++i) hsr_philox4x32_10(ctr_key + 6 * i, ctr_key + 6 * i + 4, out + 4 * i);
+}
 double hso_mt_py_random(uint32_t seed, int64_t n_skip) {
     hsr_mt19937 g; uint32_t key = seed; hsr_mt_init_by_array(&g, &key, 1);
     double v = 0; for (int64_t i = 0; i <= n_skip; ++i) v = hsr_mt_res53(&g);

@@ -134,6 +134,12 @@ def lib():
         L.hso_log.restype = C.c_double
         L.hso_log.argtypes = [C.c_double]
         L.hso_philox.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hso_log_v.restype = None
+        L.hso_log_v.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
+        L.hso_uniform_v.restype = None
+        L.hso_uniform_v.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p]
+        L.hso_philox_v.restype = None
+        L.hso_philox_v.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
         L.hso_mt_py_random.restype = C.c_double
         L.hso_mt_py_random.argtypes = [C.c_uint32, C.c_int64]
         L.hso_mt_np_random.restype = C.c_double
@@ -475,3 +481,27 @@ def philox(ctr, key):
     o = (C.c_uint32 * 4)()
     lib().hso_philox(c, k, o)
     return list(o)
+
+
+def log_v(x: np.ndarray) -> np.ndarray:
+    """hs_log_ref over an array (one call; `log` is one ctypes call per value)."""
+    x = np.ascontiguousarray(x, np.float64)
+    out = np.empty(x.shape, np.float64)
+    lib().hso_log_v(x.size, x.ctypes.data, out.ctypes.data)
+    return out
+
+
+def uniform_v(seed: int, sid: int, k0: int, n: int) -> np.ndarray:
+    """uniform(seed, sid, k0 + i) for i in 0 .. n-1."""
+    out = np.empty(n, np.float64)
+    lib().hso_uniform_v(seed, sid, k0, n, out.ctypes.data)
+    return out
+
+
+def philox_v(ctr_key: np.ndarray) -> np.ndarray:
+    """Rows {c0, c1, c2, c3, k0, k1} of uint32 -> rows of the 4 output words."""
+    ctr_key = np.ascontiguousarray(ctr_key, np.uint32)
+    assert ctr_key.ndim == 2 and ctr_key.shape[1] == 6
+    out = np.empty((len(ctr_key), 4), np.uint32)
+    lib().hso_philox_v(len(ctr_key), ctr_key.ctypes.data, out.ctypes.data)
+    return out

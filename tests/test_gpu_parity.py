@@ -54,12 +54,13 @@ def test_device_streams_match_oracle():
     for seed, sid, k0, rate in [(42, 0, 0, 8.0), (42, (5 << 3) | 1, 0, 10.0), (2**63 + 12345, (2**40 << 3) | 2, 10**12 + 1, 3.3)]:
         n = 20000
         u, e, ns = debug_draws(seed, sid, k0, n, rate)
-        for i in range(0, n, 7):
-            uo = O.uniform(seed, sid, k0 + i)
-            assert u[i] == uo
-            eo = -O.log(1.0 - uo)
-            assert e[i] == eo
-            assert ns[i] == int((eo / rate) * 1e9)
+        uo = O.uniform_v(seed, sid, k0, n)                         # all 20 000 draws, every bit
+        np.testing.assert_array_equal(u.view(np.uint64), uo.view(np.uint64))
+        eo = -O.log_v(1.0 - uo)
+        np.testing.assert_array_equal(e.view(np.uint64), eo.view(np.uint64))
+        np.testing.assert_array_equal(ns, np.trunc((eo / rate) * 1e9).astype(np.int64))
+        for i in range(0, n, 997):                                 # (the array entries are the scalar ones)
+            assert uo[i] == O.uniform(seed, sid, k0 + i) and eo[i] == -O.log(1.0 - uo[i]) and ns[i] == int((eo[i] / rate) * 1e9)
 
 
 def test_constant_divisor_quotients_are_ieee():
