@@ -72,6 +72,8 @@ struct GParam {                                // 64 bytes, read-only
                                                // lim = unhealthy_threshold, sub = _is_running, target = its LoadBalancer
                                                // Bulkhead: conc = max_concurrent, lim = max_wait_queue, lat_min = max_wait_time (sub = 1: it has one),
                                                // rt_off / rt_cnt = its table in GCtl::rs_tab;  TimeoutWrapper: lat_min = timeout, rt_off / rt_cnt likewise
+                                               // Client: lat_min = timeout (sub = 1: it has one), conc = max_attempts - 1 = entries of its delay
+                                               // table at GCtl::cl_delays + lim, rt_off / rt_cnt = its table in GCtl::rs_tab (two words per place)
     int32_t rt_off, rt_cnt;                    // router / LoadBalancer: its targets; Source / Probe: rt_off = row of its tick table (-1: none)
     uint8_t kind, sub;                         // sub: Source arrival kind (hs_source_kind); Server / link latency kind; Probe metric; LB strategy
     uint8_t crashed;                           // entity._crashed (faults/node_faults.py:46-62): the one byte of a row a run writes -- kFaultOn / kFaultOff
@@ -97,6 +99,7 @@ struct GState {                                // 64 bytes
     //           and every enqueue takes one id), total_service = peak_concurrent | peak_queue_depth (two int32), active = _active_count
     //           (= len(_in_flight)), qhead / qtail / qlen = _wait_queue through Request::next (Request::idx = enqueue time, service_s = id)
     // TimeoutWrapper: a = total, b = successful, c = timed_out, svc_draws = _next_request_id, qlen = len(_in_flight)
+    // Client: a = requests_sent, b = responses_received, c = timeouts, d = retries, svc_draws = failures, qlen = len(_in_flight)
     int64_t a, b, c, d;
     double total_service;                      // Server._total_service_time
     uint64_t svc_draws;
@@ -109,6 +112,7 @@ struct GRequest {                              // 32 bytes: the payload Event's 
     uint64_t idx;                              // sort index of the queued payload Event (kept on retarget, queue_driver.py:86-90)
     double service_s;                          // service_time_s of the generator frame (server/server.py:246-247); dead until WORK: while a
                                                // wrapper's hook rides on the Event (and in a Bulkhead's queue) the wrapper's request id, as bits
+                                               // (a Client's hook: its key, request_id | attempt << 30)
     int64_t client;                            // context["metadata"]["client_id"] (-1: none)
     int32_t next;                              // FIFO / free list
     int32_t hook : 31;                         // LoadBalancer / checker / wrapper whose completion hook rides on the Event (-1: none)
@@ -134,6 +138,14 @@ constexpr uint32_t kEvHcCycle = HS_EV_KINDS + 4, kEvHcResp = HS_EV_KINDS + 5, kE
 // (GVars::resil_by_kind), not in events_by_kind.
 constexpr uint32_t kEvBhReq = kEvAllKinds, kEvBhResp = kEvAllKinds + 1, kEvBhTimeout = kEvAllKinds + 2, kEvTwReq = kEvAllKinds + 3,
                    kEvTwResp = kEvAllKinds + 4, kEvTwTimeout = kEvAllKinds + 5, kEvResKinds = kEvAllKinds + 6;
+// Client (components/client/client.py): a request at the Client (a Source's or Server's Request, a schedule()d one, a retry), the
+// `_client_response` Event its completion hook constructs and the `_client_timeout` Event -- three more internal kinds, aimed at the
+// Client itself.  The key (request_id, attempt) is ONE word, request_id (30 bits, 0: None) | attempt << 30 (at most 2^16): a response, a
+// timeout, a retry and a schedule()d request carry no Request but the key like the wrappers' ids -- its low 30 bits (the request_id) in
+// GEvent::pad above the two flag bits, the attempt in GEvent::req (-2 - attempt); a request that carries a Request (req >= 0) has no
+// request_id and is attempt 1.  They count in events_processed and per graph (GVars::client_by_kind), not in events_by_kind.
+constexpr uint32_t kEvClReq = kEvResKinds, kEvClResp = kEvResKinds + 1, kEvClTimeout = kEvResKinds + 2, kEvCliKinds = kEvResKinds + 3;
+constexpr int kKeyAttemptShift = 30;
 constexpr uint32_t kPadPre = 1u, kPadCancelled = 2u;
 constexpr int kPadIdShift = 2;                 // a check id in GEvent::pad (its low 30 bits: only the one pending id of a backend and ids
                                                // at most one timeout older are ever compared)
@@ -146,9 +158,12 @@ constexpr uint32_t kDropKinds = (1u << HS_EV_SOURCE) | (1u << HS_EV_PROBE_TICK) 
 // ... and all six kinds of the two wrappers (the instantiation that dispatches them tests this word; the others keep theirs)
 constexpr uint32_t kDropKindsRes = kDropKinds | (1u << kEvBhReq) | (1u << kEvBhResp) | (1u << kEvBhTimeout) | (1u << kEvTwReq) |
                                    (1u << kEvTwResp) | (1u << kEvTwTimeout);
-static_assert(kEvResKinds <= 32, "kDropKinds is one word");
+// ... and the three of a Client
+constexpr uint32_t kDropKindsCli = kDropKindsRes | (1u << kEvClReq) | (1u << kEvClResp) | (1u << kEvClTimeout);
+static_assert(kEvCliKinds <= 32, "kDropKinds is one word");
 constexpr int kMaxBulkheadConcurrent = HS_BULKHEAD_MAX_CONCURRENT;         // Bulkhead.max_concurrent the in-flight table is sized for (include/hs_engine.h)
-constexpr int kDefaultTimeoutTable = 256;                // ids a TimeoutWrapper's table holds before it first grows
+constexpr int kDefaultTimeoutTable = 256;                // ids a TimeoutWrapper's (keys a Client's) table holds before it first grows
+constexpr int kMaxClientAttempts = HS_CLIENT_MAX_ATTEMPTS;   // the attempt of a key is 16 bits and one
 struct GFault { int64_t t; int32_t node; uint32_t flags; };   // hs_graph_add_fault: flags bit 0 = on, bit 1 = cancelled
 // HealthChecker._backend_states / _pending_checks of one backend, at its slot of the LoadBalancer's targets (one checker per LoadBalancer)
 struct GHc {                                   // 32 bytes
@@ -184,6 +199,7 @@ struct GVars {                                 // device scalars
     const GFault *faults; long long n_faults;  // the fault Events in the order FaultSchedule.start constructed them: read once, at boot
     long long health_by_kind[3];               // the checkers' cycle / response / timeout Events (hs_graph_get_health)
     long long resil_by_kind[6];                // the wrappers' request / response / timeout Events, Bulkhead then TimeoutWrapper (hs_graph_get_wrapper)
+    long long client_by_kind[3];               // the Clients' request / response / timeout Events (hs_graph_get_client)
 };
 
 struct GCtl {                                  // kernel argument
@@ -219,6 +235,9 @@ struct GCtl {                                  // kernel argument
     // Bulkhead / TimeoutWrapper `_in_flight`: the live request ids of every wrapper, unordered, GParam::rt_cnt places at GParam::rt_off
     // (a Bulkhead holds GState::active of them, a TimeoutWrapper GState::qlen)
     int64_t *rs_tab;
+    // Client: `_in_flight` lives in rs_tab as well, two words per place -- the key, then start_time in ns -- GState::qlen places in use;
+    const int64_t *cl_delays;                  // Duration.from_seconds(policy.get_delay(a)) in ns for a = 1 .. max_attempts - 1 of every Client (GParam::lim)
+    const int32_t *sched_id;                   // request_id of every scheduled entry (0: none; read for Client nodes only; null without any)
 };
 
 __device__ __forceinline__ bool ev_lt(const GEvent &a, const GEvent &b) {   // Event.__lt__, core/event.py:337-344
@@ -301,8 +320,11 @@ __device__ __forceinline__ double uniform_at(uint64_t seed, uint64_t sid, uint64
 }
 
 // a Request-carrying Event aimed at `node`: which handler it lands in (Entity.handle_event of that class)
-template <bool R = false>
+template <bool R = false, bool CL = false>
 __device__ __forceinline__ uint32_t arrival_kind(const GParam *P, int node) {
+    if constexpr (CL) {
+        if (P[node].kind == HS_NODE_CLIENT) return kEvClReq;
+    }
     if constexpr (R) {                         // (the wrappers exist in the one instantiation that dispatches their kinds)
         if (P[node].kind == HS_NODE_BULKHEAD) return kEvBhReq;
         if (P[node].kind == HS_NODE_TIMEOUT_WRAPPER) return kEvTwReq;
@@ -509,6 +531,21 @@ __device__ __forceinline__ GEvent mk_id(int64_t t, uint64_t idx, uint32_t kind, 
 }
 __device__ __forceinline__ int64_t ev_id(const GEvent &e) { return ((int64_t)(-2 - e.req) << 30) | (int64_t)(e.pad >> kPadIdShift); }
 __device__ __forceinline__ int64_t req_id(const GRequest &q) { return __double_as_longlong(q.service_s); }
+// the `_bh_response` / `_tw_response` / `_client_response` kind of a hook's owner
+template <bool CL>
+__device__ __forceinline__ uint32_t hook_resp_kind(uint8_t hk) {
+    if constexpr (CL) {
+        if (hk == HS_NODE_CLIENT) return kEvClResp;
+    }
+    return hk == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp;
+}
+template <bool CL>
+__device__ __forceinline__ bool hook_has_id(uint8_t hk) {
+    if constexpr (CL) {
+        if (hk == HS_NODE_CLIENT) return true;
+    }
+    return hk == HS_NODE_BULKHEAD || hk == HS_NODE_TIMEOUT_WRAPPER;
+}
 // `request_id in self._in_flight` and its removal: the live ids are unordered, the last one takes the place of the one that leaves
 __device__ inline bool tab_remove(int64_t *tab, int live, int64_t id) {
     for (int i = 0; i < live; ++i)
@@ -523,12 +560,14 @@ __device__ inline bool tab_remove(int64_t *tab, int live, int64_t id) {
 // HC: the graph (or one of a batch) has a HealthChecker or an unhealthy backend -- a third instantiation, so that the two above keep
 // their code: the fault-only loop is as sensitive to what it carries as the plain one.  HC implies F.
 // R: the graph (or one of a batch) has a Bulkhead or a TimeoutWrapper -- a fourth instantiation, for the same reason.  R implies HC.
-template <int W, int NL, bool F = false, bool HC = false, bool R = false>
+// CL: ... has a Client -- a fifth, for the same reason.  CL implies R.
+template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     static_assert(F || !HC, "the health instantiation carries the fault code");
     static_assert(HC || !R, "the resilience instantiation carries the fault and health code");
-    constexpr uint32_t kKinds = R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
-    constexpr uint32_t kDrop = R ? kDropKindsRes : kDropKinds;
+    static_assert(R || !CL, "the client instantiation carries the fault, health and resilience code");
+    constexpr uint32_t kKinds = CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
+    constexpr uint32_t kDrop = CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
     constexpr int kPushes = R ? 3 : 2;         // heap entries one event constructs at most (R: a limiter's forward or poll + the hook's response)
     __shared__ unsigned long long s_by_kind[kKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
@@ -607,6 +646,18 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     continue;
                 }
             }
+            if constexpr (CL) {
+                // an Event aimed at a Client (Client.send_request's, or a plain one: request_id None): its key, attempt 1, no Request
+                const int cn = c.sched_node[V.sched_done];
+                if (c.P[cn].kind == HS_NODE_CLIENT) {
+                    const int64_t id = c.sched_id ? (int64_t)c.sched_id[V.sched_done] : 0;
+                    GEvent ce = mk_id(c.sched_t[V.sched_done], V.global_counter++, kEvClReq, cn, id | (1ll << kKeyAttemptShift));
+                    ce.pad |= kPadPre;
+                    H.push(ce);
+                    V.sched_done++;
+                    continue;
+                }
+            }
             int r = req_free;
             if (r >= 0) req_free = c.reqs[r].next;
             else if (req_len < c.req_cap) r = req_len++;
@@ -615,7 +666,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             const int64_t t = c.sched_t[V.sched_done];
             GRequest q; q.created = t; q.idx = V.global_counter; q.service_s = 0.0; q.client = -1; q.next = -1; q.hook = -1; q.pre = 1;
             c.reqs[r] = q;
-            H.push(mk_pre(t, V.global_counter++, arrival_kind<R>(c.P, node), node, r));
+            H.push(mk_pre(t, V.global_counter++, arrival_kind<R, CL>(c.P, node), node, r));
             V.sched_done++;
         }
         cur = V.cur;
@@ -660,6 +711,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             if constexpr (R) {
                 const GEvent top = H.get(0);                                       // a TimeoutWrapper's table has a place for the id it is about to take
                 if (top.kind == kEvTwReq && c.S[top.node].qlen >= c.P[top.node].rt_cnt) { status |= kGrowTab; break; }
+                if constexpr (CL) {                                                // ... and a Client's for the key
+                    if (top.kind == kEvClReq && c.S[top.node].qlen >= c.P[top.node].rt_cnt) { status |= kGrowTab; break; }
+                }
             }
             if (c.coop_min > 0 && sel < 0) {                                       // (a graph without such a LoadBalancer: one uniform test)
                 const GEvent top = H.get(0);
@@ -737,7 +791,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         GRequest rq; rq.created = t; rq.idx = idx_p; rq.service_s = 0.0; rq.client = (id << 32) | (int64_t)q; rq.next = -1; rq.hook = n; rq.pre = 0;
                         c.reqs[r] = rq;
                         const int be = c.rt_targets[lp.rt_off + q];
-                        H.push(mk(t, idx_p, arrival_kind<R>(c.P, be), be, r));
+                        H.push(mk(t, idx_p, arrival_kind<R, CL>(c.P, be), be, r));
                         GEvent te = mk(t + ns_from_seconds(p.lat_min), G++, kEvHcTimeout, n, -2 - q);
                         te.pad = (uint32_t)id << kPadIdShift;
                         H.push(te);
@@ -774,10 +828,58 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if (hook < 0) return;
                 if (!keep) c.reqs[r].hook = -1;
                 const uint8_t hk = c.P[hook].kind;
-                if (hk == HS_NODE_BULKHEAD || hk == HS_NODE_TIMEOUT_WRAPPER)
-                    H.push(mk_id(t, G++, hk == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp, hook, req_id(c.reqs[r])));
+                if (hook_has_id<CL>(hk))
+                    H.push(mk_id(t, G++, hook_resp_kind<CL>(hk), hook, req_id(c.reqs[r])));
                 else if (hk == HS_NODE_LB) H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
             };
+            if constexpr (CL) {
+                if (e.kind >= kEvClReq) {
+                    int64_t *tab = c.rs_tab + p.rt_off;                            // _in_flight: (key, start_time ns) per place, unordered
+                    if (e.kind == kEvClReq) {
+                        // Client._send_request (client.py:233-317): _in_flight[(request_id, attempt)] is set (an equal key is overwritten),
+                        // a NEW Event for the target with the hook -- its context holds the metadata alone: created_at is this
+                        // attempt's send time, no client id survives -- then the timeout Event
+                        int r = e.req;
+                        int64_t key = 1ll << kKeyAttemptShift;                     // a Request that came along: no request_id, attempt 1
+                        if (r < 0) {
+                            key = ev_id(e);
+                            r = req_free;
+                            if (r >= 0) req_free = c.reqs[r].next; else r = req_len++;   // (room: tested in front of the pop)
+                        }
+                        int i = 0;
+                        while (i < s.qlen && tab[2 * i] != key) ++i;
+                        tab[2 * i] = key; tab[2 * i + 1] = t;                      // (room for a new key: tested in front of the pop)
+                        if (i == s.qlen) s.qlen += 1;
+                        s.a += 1;
+                        if ((key >> kKeyAttemptShift) > 1) s.d += 1;
+                        GRequest q; q.created = t; q.idx = 0; q.service_s = __longlong_as_double(key); q.client = -1; q.next = -1; q.hook = n; q.pre = 0;
+                        c.reqs[r] = q;
+                        H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, r));
+                        if (p.sub) H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvClTimeout, n, key));
+                        continue;
+                    }
+                    // _handle_response / _handle_timeout (:319-443): an unknown key is a processed no-op
+                    const int64_t key = ev_id(e);
+                    int i = 0;
+                    while (i < s.qlen && tab[2 * i] != key) ++i;
+                    if (i == s.qlen) continue;
+                    const int64_t start = tab[2 * i + 1];
+                    s.qlen -= 1;
+                    tab[2 * i] = tab[2 * s.qlen]; tab[2 * i + 1] = tab[2 * s.qlen + 1];    // the last entry takes the place of the one that leaves
+                    if (e.kind == kEvClResp) {
+                        s.b += 1;
+                        c.rec_node[rec_n] = n; c.rec_t[rec_n] = t - start; c.rec_cr[rec_n] = start;   // _response_times: (now - start_time)
+                        rec_n++;
+                    } else {
+                        s.c += 1;
+                        const int64_t attempt = key >> kKeyAttemptShift;
+                        if (attempt - 1 < (int64_t)p.conc)                         // policy.should_retry(attempt): attempt < max_attempts
+                            H.push(mk_id(t + c.cl_delays[p.lim + attempt - 1], G++, kEvClReq, n, key + (1ll << kKeyAttemptShift)));
+                        else s.svc_draws += 1;                                     // failures
+                    }
+                    continue;
+                }
+            }
             if constexpr (R) {
                 if (e.kind >= kEvBhReq) {
                     int64_t *tab = c.rs_tab + p.rt_off;
@@ -790,7 +892,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         if (s.active > peaks[0]) peaks[0] = s.active;
                         tab[s.active - 1] = id;                                    // (active <= max_concurrent = rt_cnt)
                         c.reqs[r].hook = n; c.reqs[r].service_s = __longlong_as_double(id);
-                        H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, r));
+                        H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, r));
                     };
                     switch (e.kind) {
                     case kEvBhReq: {                                               // Bulkhead.handle_event (bulkhead.py:191-229)
@@ -852,7 +954,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         tab[s.qlen] = id;                                          // (room: tested in front of the pop)
                         s.qlen += 1;
                         c.reqs[e.req].hook = n; c.reqs[e.req].service_s = __longlong_as_double(id);
-                        H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, e.req));
+                        H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, e.req));
                         H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvTwTimeout, n, id));
                     } break;
                     default: {                                                     // _handle_response / _handle_timeout (:222-295): whichever comes second finds nothing
@@ -886,7 +988,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 }
                 s.c += 1;                                                           // _generated_count (:159)
                 const int64_t a2 = next_arrival(c, n);
-                if (payload) H.push(mk(t, idx_p, arrival_kind<R>(c.P, p.target), p.target, r));
+                if (payload) H.push(mk(t, idx_p, arrival_kind<R, CL>(c.P, p.target), p.target, r));
                 if (a2 != kInfNs) H.push(mk(a2, G++, HS_EV_SOURCE, n, -1));       // RuntimeError: the source is exhausted (:176-180)
             } break;
             case HS_EV_ENQUEUE: {
@@ -921,8 +1023,8 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 } else if (hook >= 0) {
                     if constexpr (R) {                                             // (a wrapper's hook: its id stayed on the Request)
                         const uint8_t hk = c.P[hook].kind;
-                        if (hk == HS_NODE_BULKHEAD || hk == HS_NODE_TIMEOUT_WRAPPER) {
-                            H.push(mk_id(t, G++, hk == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp, hook, req_id(c.reqs[e.req])));
+                        if (hook_has_id<CL>(hk)) {
+                            H.push(mk_id(t, G++, hook_resp_kind<CL>(hk), hook, req_id(c.reqs[e.req])));
                             break;
                         }
                     }
@@ -970,7 +1072,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 s.active = s.active > 0 ? s.active - 1 : 0;
                 s.c += 1; n_completed++;
                 s.total_service = __dadd_rn(s.total_service, c.reqs[e.req].service_s);
-                if (p.target >= 0) H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, e.req));
+                if (p.target >= 0) H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, e.req));
                 else { c.reqs[e.req].next = req_free; req_free = e.req; }
                 if (s.active < p.conc) H.push(mk(t, G++, HS_EV_POLL, n, -1));
             } break;
@@ -991,11 +1093,11 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     const int hook = c.reqs[e.req].hook;                            //  its Event constructed behind the forward's)
                     const int64_t id = req_id(c.reqs[e.req]);
                     c.reqs[e.req].hook = -1;
-                    H.push(mk(t, G++, arrival_kind<R>(c.P, tg), tg, e.req));
-                    if (hook >= 0) H.push(mk_id(t, G++, c.P[hook].kind == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp, hook, id));
+                    H.push(mk(t, G++, arrival_kind<R, CL>(c.P, tg), tg, e.req));
+                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<CL>(c.P[hook].kind), hook, id));
                     break;
                 }
-                H.push(mk(t, G++, arrival_kind<R>(c.P, tg), tg, e.req));
+                H.push(mk(t, G++, arrival_kind<R, CL>(c.P, tg), tg, e.req));
             } break;
             case HS_EV_LINK: {
                 // NetworkLink.handle_event up to its yield (components/network/link.py:114-154, _calculate_delay :190-216)
@@ -1021,7 +1123,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             case HS_EV_LINK_CONT:                                                   // transit over (link.py:156-189): a NEW Event for the egress
                 s.b += 1;
                 if (p.target >= 0) {
-                    H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, e.req));
+                    H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, e.req));
                     if constexpr (R) fire_hook(e.req, true);                        // ... and stays on the Event for the egress (link.py:181)
                 } else {
                     if constexpr (R) fire_hook(e.req, false);
@@ -1114,7 +1216,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 // a NEW Event for the backend with the same context (created_at survives) + the response hook (:398-431)
                 const int be = c.rt_targets[p.rt_off + slot];
                 c.reqs[e.req].hook = n;
-                H.push(mk(t, G++, arrival_kind<R>(c.P, be), be, e.req));
+                H.push(mk(t, G++, arrival_kind<R, CL>(c.P, be), be, e.req));
             } break;
             case HS_EV_LB_RESP:                                                     // LoadBalancer._handle_response (load_balancer.py:435-473)
                 if (s.d > 0) s.d -= 1;
@@ -1151,6 +1253,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         v = left > 0 ? left : 0;
                     } break;
                     case HS_PROBE_TW_IN_FLIGHT: v = tg.qlen; break;                 // TimeoutWrapper.in_flight_count
+                    case HS_PROBE_CL_IN_FLIGHT: if constexpr (CL) v = tg.qlen; break;   // Client.in_flight_count
                     default: break;
                     }
                 }
@@ -1168,7 +1271,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if (lim_try_acquire(c, p, s, t)) {
                     // _forward (:164-178): a NEW Event for the downstream at `now` with a copy of the context, no completion hook
                     outcome = HS_LIMITER_FORWARDED;
-                    H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, e.req));
+                    H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, e.req));
                 } else if (!(p.lim >= 0 && s.qlen >= p.lim)) {                     // FIFOQueue.push (queue_policy.py:94-98)
                     outcome = HS_LIMITER_QUEUED;
                     c.reqs[e.req].next = -1;
@@ -1189,7 +1292,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = outcome;
                 rec_n++;
                 if constexpr (R) {
-                    if (hook >= 0) H.push(mk_id(t, G++, c.P[hook].kind == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp, hook, hook_id));
+                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<CL>(c.P[hook].kind), hook, hook_id));
                 }
             } break;
             case kEvLimPoll: {
@@ -1206,7 +1309,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     s.qlen -= 1;
                     c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = HS_LIMITER_DRAINED;
                     rec_n++;
-                    H.push(mk(t, G++, arrival_kind<R>(c.P, p.target), p.target, r));
+                    H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, r));
                     again = s.qlen > 0;
                 }
                 if (again) {
@@ -1305,6 +1408,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         if constexpr (R) {
             for (int k = 0; k < 6; ++k) V.resil_by_kind[k] += (long long)s_by_kind[kEvBhReq + k];
         }
+        if constexpr (CL) {
+            for (int k = 0; k < 3; ++k) V.client_by_kind[k] += (long long)s_by_kind[kEvClReq + k];
+        }
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
@@ -1344,6 +1450,12 @@ __global__ void __launch_bounds__(64) hs_graph_run_resilience(GCtl c) {       //
     __shared__ GEvent lheap[kLdsHeap];
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
     graph_loop<kLdsHeap, kLdsNodes, true, true, true>(c, lheap, lnodes);
+}
+
+__global__ void __launch_bounds__(64) hs_graph_run_client(GCtl c) {           // ... with a Client
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true>(c, lheap, lnodes);
 }
 
 // Independent graphs -- the replicas / sweep points of parallel/runner.py:82-142 -- side by side: one workgroup (one heap) each, one
@@ -1388,6 +1500,14 @@ __global__ void __launch_bounds__(64) hs_graph_run_batch_resilience(const GCtl *
     graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true>(c, lheap, lnodes);
     batch_report(c, stat);
 }
+// ... of a batch in which at least one handle has a Client
+__global__ void __launch_bounds__(64) hs_graph_run_batch_client(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
 
 }  // namespace graph
 }  // namespace hs
@@ -1427,6 +1547,13 @@ struct hs_graph {
     std::vector<uint8_t> wrapper_set;          // [n] hs_graph_set_wrapper has been called for the node
     std::vector<int32_t> tab_cap;              // [n] the table capacity the node starts with
     long long rs_tab_len = 0;
+    // Client: a graph that holds one runs the fifth instantiation; its in-flight table is one of rs_tab (two words per place)
+    int n_clients = 0;
+    std::vector<int64_t> cl_delays;            // every configured Client's delay table, back to back (GParam::lim = its offset)
+    int64_t *d_cl_delays = nullptr;
+    std::vector<int32_t> sched_id;             // request_id per scheduled entry (0: none)
+    int32_t *d_sched_id = nullptr;
+    bool any_sched_id = false;
     int debug_flags = 0;                       // hs_debug_graph_flags
     // tick tables: one row per time-varying Source and per distinct Probe interval, computed up to `tick_horizon`
     std::vector<hs::TickRow> rows;
@@ -1508,7 +1635,7 @@ void hs_graph_destroy(hs_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *bufs[] = {g->ctl.heap, g->ctl.reqs, g->ctl.rec_node, g->ctl.rec_t, g->ctl.rec_cr, (void *)g->ctl.P, g->ctl.S,
                     g->d_rt_targets, g->d_key_table, (void *)g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
-                    g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health, g->ctl.rs_tab};
+                    g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health, g->ctl.rs_tab, g->d_cl_delays, g->d_sched_id};
     for (void *b : bufs) if (b && !in_slab(g, b)) (void)hipFree(b);
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
     if (g->ev_a) (void)hipEventDestroy(g->ev_a);
@@ -1532,7 +1659,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     if (cfg->start_ns < 0)        // (the Sinks' merged records hold non-negative times)
         return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
     bool has_wrr = false;
-    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER || k == HS_NODE_BULKHEAD || k == HS_NODE_TIMEOUT_WRAPPER; };
+    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER || k == HS_NODE_BULKHEAD || k == HS_NODE_TIMEOUT_WRAPPER || k == HS_NODE_CLIENT; };
     int64_t kmax = 0;                                  // client ids any Source hands out: [0, kmax)
     for (int i = 0; i < n; ++i)
         if (nd->kind[i] == HS_NODE_SOURCE && nd->src_n_clients && nd->src_n_clients[i] > kmax) kmax = nd->src_n_clients[i];
@@ -1602,7 +1729,8 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             const bool ok = p.sub == HS_PROBE_GENERATED ? tk == HS_NODE_SOURCE : p.sub == HS_PROBE_RECEIVED ? tk == HS_NODE_SINK
                             : p.sub == HS_PROBE_LIMITER_DEPTH ? tk == HS_NODE_RATE_LIMITER
                             : (p.sub >= HS_PROBE_BH_ACTIVE && p.sub <= HS_PROBE_BH_PERMITS) ? tk == HS_NODE_BULKHEAD
-                            : p.sub == HS_PROBE_TW_IN_FLIGHT ? tk == HS_NODE_TIMEOUT_WRAPPER : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
+                            : p.sub == HS_PROBE_TW_IN_FLIGHT ? tk == HS_NODE_TIMEOUT_WRAPPER
+                            : p.sub == HS_PROBE_CL_IN_FLIGHT ? tk == HS_NODE_CLIENT : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
             if (!ok) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: metric %d is not an attribute of its target (node kind %d)", i, (int)p.sub, tk);
             const double rate = 1.0 / iv;                           // _ProbeProfile.rate (probe.py:31)
             int found = -1;
@@ -1706,16 +1834,18 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             p.lim = nd->queue_cap ? nd->queue_cap[i] : 1000;                        // rate_limited_entity.py:60
             p.sub = (uint8_t)HS_LIMITER_NONE; p.conc = 0; p.rt_off = 0; p.rt_cnt = 0;
         } break;
+        case HS_NODE_CLIENT:
         case HS_NODE_BULKHEAD:
         case HS_NODE_TIMEOUT_WRAPPER: {
-            // Bulkhead / TimeoutWrapper (components/resilience/): the parameters come with hs_graph_set_wrapper
-            const char *nm = p.kind == HS_NODE_BULKHEAD ? "Bulkhead" : "TimeoutWrapper";
+            // Bulkhead / TimeoutWrapper (components/resilience/) and Client (components/client/): the parameters come with
+            // hs_graph_set_wrapper / hs_graph_set_client
+            const char *nm = p.kind == HS_NODE_BULKHEAD ? "Bulkhead" : p.kind == HS_NODE_CLIENT ? "Client" : "TimeoutWrapper";
             if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a %s needs a target", i, nm);
             // the target's handler must fire ONE hook: through any chain of links it is a Server, Sink, router or limiter
             int t = p.target;
             for (int hops = 0; hops <= n && t >= 0 && nd->kind[t] == HS_NODE_LINK; ++hops) t = nd->target[t];
-            if (t >= 0 && (nd->kind[t] == HS_NODE_LB || nd->kind[t] == HS_NODE_BULKHEAD || nd->kind[t] == HS_NODE_TIMEOUT_WRAPPER))
-                return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the target of a %s is (through %s) node %d, a LoadBalancer, Bulkhead or TimeoutWrapper: "
+            if (t >= 0 && (nd->kind[t] == HS_NODE_LB || nd->kind[t] == HS_NODE_BULKHEAD || nd->kind[t] == HS_NODE_TIMEOUT_WRAPPER || nd->kind[t] == HS_NODE_CLIENT))
+                return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the target of a %s is (through %s) node %d, a LoadBalancer, Bulkhead, TimeoutWrapper or Client: "
                             "two completion hooks on one Event are not lowered", i, nm, t == p.target ? "no link" : "its links", t);
             p.conc = 1; p.lim = 0; p.sub = 0; p.rt_off = 0; p.rt_cnt = 0;
         } break;
@@ -1736,6 +1866,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_RATE_LIMITER) g->n_limiters++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_HEALTH_CHECKER) g->n_checkers++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_BULKHEAD || P[(size_t)i].kind == HS_NODE_TIMEOUT_WRAPPER) g->n_wrappers++;
+        for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_CLIENT) g->n_clients++;
         g->wrapper_set.assign((size_t)n, 0); g->tab_cap.assign((size_t)n, 0);
     }
     for (int i = 0; i < n; ++i) {
@@ -2195,6 +2326,64 @@ int hs_graph_get_wrapper(hs_graph *g, int32_t node, int64_t *counters, int64_t *
     return HS_OK;
 }
 
+int hs_graph_set_client(hs_graph *g, int32_t node, double timeout_s, const int64_t *delays_ns, int32_t n_delays, int32_t table_capacity) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_CLIENT) return fail(g, HS_E_INVALID, "set_client: node %d is not a Client", node);
+    if (g->ran || g->launches > 0 || g->ctl.rs_tab) return fail(g, HS_E_STATE, "set_client: a Client is configured before the first run");
+    if (g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "set_client: node %d is configured already", node);
+    if (std::isnan(timeout_s) || std::isinf(timeout_s)) return fail(g, HS_E_INVALID, "set_client: timeout must be finite or negative (None)");
+    if (n_delays < 0) return fail(g, HS_E_INVALID, "max_attempts must be >= 1, got %d", n_delays + 1);                  // retry.py:115-116
+    if (n_delays + 1 > kMaxClientAttempts)
+        return fail(g, HS_E_UNSUPPORTED, "Client: max_attempts = %d is beyond the %d attempts a key holds", n_delays + 1, kMaxClientAttempts);
+    if (n_delays > 0 && !delays_ns) return fail(g, HS_E_INVALID, "set_client: %d delays without a table", n_delays);
+    for (int k = 0; k < n_delays; ++k)
+        if (delays_ns[k] < 0) return fail(g, HS_E_INVALID, "delay must be >= 0, got %g", (double)delays_ns[k] / 1e9);   // retry.py:117-118
+    if (table_capacity < 0 || table_capacity > (1 << 27)) return fail(g, HS_E_INVALID, "set_client: table_capacity %d out of range", table_capacity);
+    GParam &p = g->params[(size_t)node];
+    p.sub = timeout_s >= 0.0 ? 1 : 0;                      // (negative: None; 0 is legal, client.py:89-90)
+    p.lat_min = p.sub ? timeout_s : 0.0;
+    p.conc = n_delays; p.lim = (int64_t)g->cl_delays.size();
+    g->cl_delays.insert(g->cl_delays.end(), delays_ns, delays_ns + n_delays);
+    g->tab_cap[(size_t)node] = table_capacity > 0 ? table_capacity : kDefaultTimeoutTable;
+    double reach = p.lat_min;
+    for (int k = 0; k < n_delays; ++k) reach = std::max(reach, (double)delays_ns[k] / 1e9);
+    g->reach_s = std::max(g->reach_s, reach);
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    g->wrapper_set[(size_t)node] = 1;
+    return HS_OK;
+}
+
+int hs_graph_get_client(hs_graph *g, int32_t node, int64_t *counters, int64_t *in_flight_keys, int64_t cap, int64_t *events) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (events) {
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 3; ++k) events[k] = v.client_by_kind[k];
+    }
+    if (node == -1 && !counters && !in_flight_keys) return HS_OK;                       // the graph's event counts alone
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_CLIENT) return fail(g, HS_E_INVALID, "get_client: node %d is not a Client", node);
+    if (!g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "get_client: node %d was never configured", node);
+    const GParam &p = g->params[(size_t)node];
+    GState s{};
+    HS_HIP(g, hipMemcpy(&s, g->ctl.S + node, sizeof s, hipMemcpyDeviceToHost));
+    if (counters) {
+        counters[0] = s.a; counters[1] = s.b; counters[2] = s.c; counters[3] = s.d; counters[4] = (int64_t)s.svc_draws; counters[5] = s.qlen;
+        counters[6] = g->ctl.rs_tab ? p.rt_cnt : g->tab_cap[(size_t)node];
+    }
+    const int64_t take = std::min<int64_t>(s.qlen, cap);
+    if (in_flight_keys && take > 0 && g->ctl.rs_tab) {
+        std::vector<int64_t> rows((size_t)take * 2);
+        HS_HIP(g, hipMemcpy(rows.data(), g->ctl.rs_tab + p.rt_off, rows.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (int64_t k = 0; k < take; ++k) {                                            // (request_id or 0, attempt) pairs
+            in_flight_keys[2 * k] = rows[(size_t)(2 * k)] & ((1ll << kKeyAttemptShift) - 1);
+            in_flight_keys[2 * k + 1] = rows[(size_t)(2 * k)] >> kKeyAttemptShift;
+        }
+    }
+    return HS_OK;
+}
+
 int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, int32_t cancelled) {
     if (!g) return fail(g, HS_E_INVALID, "null handle");
     if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "add_fault: node %d out of range", node);
@@ -2238,6 +2427,19 @@ int hs_graph_schedule(hs_graph *g, int32_t node, int64_t time_ns) {
         return fail(g, HS_E_UNSUPPORTED, "schedule: node %d is a Source (only Requests for a Server, Sink, link or router are lowered)", node);
     g->sched_node.push_back(node);
     g->sched_t.push_back(time_ns);
+    g->sched_id.push_back(0);
+    return HS_OK;
+}
+
+int hs_graph_schedule_client(hs_graph *g, int32_t node, int64_t time_ns, int32_t request_id) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_CLIENT) return fail(g, HS_E_INVALID, "schedule_client: node %d is not a Client", node);
+    if (request_id < 0 || request_id >= (1 << kKeyAttemptShift))
+        return fail(g, HS_E_UNSUPPORTED, "schedule_client: request_id %d is not in [0, 2^30) (0: none)", request_id);
+    g->sched_node.push_back(node);
+    g->sched_t.push_back(time_ns);
+    g->sched_id.push_back(request_id);
+    g->any_sched_id |= request_id != 0;
     return HS_OK;
 }
 
@@ -2354,23 +2556,30 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         c.hl_flag = reinterpret_cast<uint8_t *>(g->d_health + o_flag);
         c.health = 1;
     }
-    if (g->n_wrappers > 0 && !c.rs_tab) {
+    if (g->n_wrappers + g->n_clients > 0 && !c.rs_tab) {
         // the wrappers' in-flight tables, once: one allocation, every wrapper's places in node order
         long long len = 0;
         HS_HIP(g, hipSetDevice(g->cfg.device));
         for (int i = 0; i < g->n; ++i) {
             GParam &p = g->params[(size_t)i];
-            if (p.kind != HS_NODE_BULKHEAD && p.kind != HS_NODE_TIMEOUT_WRAPPER) continue;
+            if (p.kind != HS_NODE_BULKHEAD && p.kind != HS_NODE_TIMEOUT_WRAPPER && p.kind != HS_NODE_CLIENT) continue;
             if (!g->wrapper_set[(size_t)i])
-                return fail(g, HS_E_STATE, "node %d: a Bulkhead / TimeoutWrapper without its parameters (hs_graph_set_wrapper comes before the run)", i);
-            if (len + g->tab_cap[(size_t)i] > (1ll << 30)) return fail(g, HS_E_UNSUPPORTED, "the wrappers' in-flight tables of this graph exceed 2^30 ids");
+                return fail(g, HS_E_STATE, p.kind == HS_NODE_CLIENT ? "node %d: a Client without its parameters (hs_graph_set_client comes before the run)"
+                            : "node %d: a Bulkhead / TimeoutWrapper without its parameters (hs_graph_set_wrapper comes before the run)", i);
+            const long long words = p.kind == HS_NODE_CLIENT ? 2 : 1;                  // a Client's place: key + start time
+            if (len + words * g->tab_cap[(size_t)i] > (1ll << 30)) return fail(g, HS_E_UNSUPPORTED, "the wrappers' in-flight tables of this graph exceed 2^30 ids");
             p.rt_off = (int32_t)len; p.rt_cnt = g->tab_cap[(size_t)i];
-            len += p.rt_cnt;
+            len += words * p.rt_cnt;
             HS_HIP(g, hipMemcpy(const_cast<GParam *>(c.P) + i, &p, sizeof p, hipMemcpyHostToDevice));
         }
         HS_HIP(g, hipMalloc(&c.rs_tab, (size_t)len * sizeof(int64_t)));
         HS_HIP(g, hipMemset(c.rs_tab, 0, (size_t)len * sizeof(int64_t)));
         g->rs_tab_len = len;
+        if (!g->cl_delays.empty()) {
+            HS_HIP(g, hipMalloc(&g->d_cl_delays, g->cl_delays.size() * sizeof(int64_t)));
+            HS_HIP(g, hipMemcpy(g->d_cl_delays, g->cl_delays.data(), g->cl_delays.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        }
+        c.cl_delays = g->d_cl_delays;
     }
     const long long ns = (long long)g->sched_node.size();
     if (ns > g->d_sched_cap) {
@@ -2385,6 +2594,14 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         HS_HIP(g, hipMemcpy(g->d_sched_node, g->sched_node.data(), (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice));
         HS_HIP(g, hipMemcpy(g->d_sched_t, g->sched_t.data(), (size_t)ns * sizeof(int64_t), hipMemcpyHostToDevice));
     }
+    c.sched_id = nullptr;
+    if (g->any_sched_id) {                                  // (request ids: only a graph whose Client was handed one has the array)
+        if (g->d_sched_id) HS_HIP(g, hipFree(g->d_sched_id));
+        g->d_sched_id = nullptr;
+        HS_HIP(g, hipMalloc(&g->d_sched_id, (size_t)ns * sizeof(int32_t)));
+        HS_HIP(g, hipMemcpy(g->d_sched_id, g->sched_id.data(), (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice));
+        c.sched_id = g->d_sched_id;
+    }
     c.sched_node = g->d_sched_node; c.sched_t = g->d_sched_t; c.n_sched = ns;
     c.end_ns = end_ns;
     c.auto_term = end_ns == (1ll << 61);                   // end_time = Infinity: the limiters' polls are daemons (core/simulation.py:306-322)
@@ -2394,7 +2611,8 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
     return HS_OK;
 }
 
-// A TimeoutWrapper's table was full: every TimeoutWrapper gets twice the places (a Bulkhead never holds more than max_concurrent ids).
+// A TimeoutWrapper's or a Client's table was full: every one of them gets twice the places (a Bulkhead never holds more than
+// max_concurrent ids).
 // The rows' rt_off / rt_cnt alone are rewritten: the `crashed` byte of a row is the run's.
 static int grow_tables(hs_graph *g) {
     GCtl &c = g->ctl;
@@ -2402,12 +2620,13 @@ static int grow_tables(hs_graph *g) {
     HS_HIP(g, hipMemcpy(old.data(), c.rs_tab, (size_t)g->rs_tab_len * sizeof(int64_t), hipMemcpyDeviceToHost));
     for (int i = 0; i < g->n; ++i) {
         GParam &p = g->params[(size_t)i];
-        if (p.kind != HS_NODE_BULKHEAD && p.kind != HS_NODE_TIMEOUT_WRAPPER) continue;
-        const long long cnt = p.kind == HS_NODE_TIMEOUT_WRAPPER ? 2ll * p.rt_cnt : p.rt_cnt;
-        if ((long long)now.size() + cnt > (1ll << 30)) return fail(g, HS_E_OVERFLOW, "more than 2^30 request ids in flight at the wrappers");
+        if (p.kind != HS_NODE_BULKHEAD && p.kind != HS_NODE_TIMEOUT_WRAPPER && p.kind != HS_NODE_CLIENT) continue;
+        const long long cnt = p.kind == HS_NODE_BULKHEAD ? p.rt_cnt : 2ll * p.rt_cnt;
+        const long long words = p.kind == HS_NODE_CLIENT ? 2 : 1;
+        if ((long long)now.size() + words * cnt > (1ll << 30)) return fail(g, HS_E_OVERFLOW, "more than 2^30 request ids in flight at the wrappers");
         const size_t at = now.size();
-        now.insert(now.end(), old.begin() + p.rt_off, old.begin() + p.rt_off + p.rt_cnt);
-        now.resize(at + (size_t)cnt, 0);
+        now.insert(now.end(), old.begin() + p.rt_off, old.begin() + p.rt_off + words * p.rt_cnt);
+        now.resize(at + (size_t)(words * cnt), 0);
         p.rt_off = (int32_t)at; p.rt_cnt = (int32_t)cnt;
         static_assert(offsetof(GParam, rt_cnt) == offsetof(GParam, rt_off) + sizeof(int32_t), "rt_off and rt_cnt are copied together");
         const int32_t pair[2] = {p.rt_off, p.rt_cnt};
@@ -2493,7 +2712,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
@@ -2544,9 +2764,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
             h_ctl.back().part = part;              // (the handles themselves never keep part semantics: no early return can leave it set)
         }
         if ((he = hipMemcpy(d_ctl, h_ctl.data(), h_ctl.size() * sizeof(GCtl), hipMemcpyHostToDevice)) != hipSuccess) break;
-        bool any_faults = false, any_health = false, any_wrappers = false;
-        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; }
-        if (any_wrappers) hipLaunchKernelGGL(hs_graph_run_batch_resilience, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_faults = false, any_health = false, any_wrappers = false, any_clients = false;
+        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; any_clients |= gs[i]->n_clients > 0; }
+        if (any_clients) hipLaunchKernelGGL(hs_graph_run_batch_client, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else if (any_wrappers) hipLaunchKernelGGL(hs_graph_run_batch_resilience, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_health) hipLaunchKernelGGL(hs_graph_run_batch_health, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (!any_faults) hipLaunchKernelGGL(hs_graph_run_batch, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else hipLaunchKernelGGL(hs_graph_run_batch_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
@@ -2612,7 +2833,8 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count; one.rs_tab = g->ctl.rs_tab;
-        if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, one);
+        if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, one);
+        else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, one);
         else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, one);

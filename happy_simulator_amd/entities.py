@@ -17,10 +17,12 @@ lives in csrc/).  Names, argument meaning, defaults and error behaviour follow t
 """
 from __future__ import annotations
 
+import random as _random
 from dataclasses import dataclass
 
 import numpy as np
 
+from .core.event import Event
 from .core.temporal import Duration, Instant
 
 
@@ -1428,6 +1430,236 @@ class TimeoutWrapper(Entity):
                             timed_out_requests=self._timed_out_requests)
 
 
+# ---- client --------------------------------------------------------------------------------------
+# components/client/retry.py and client.py: the caller that answers a timeout by sending again.  The policies are host Python like the
+# limiter policies (they work on their own); the Client's three handlers run on the device (csrc/hs_graph.hip kEvClReq .. kEvClTimeout)
+# from a table of delays the host evaluates.  PooledClient / ConnectionPool are not mirrored.
+class NoRetry:
+    """retry.py:62-90: never retry."""
+
+    def should_retry(self, attempt: int, error: Exception | None = None) -> bool:
+        return False
+
+    def get_delay(self, attempt: int) -> float:
+        return 0.0
+
+
+class FixedRetry:
+    """retry.py:93-160: the same delay before every retry, `max_attempts` attempts in all."""
+
+    def __init__(self, max_attempts: int, delay: float):
+        if max_attempts < 1:
+            raise ValueError(f"max_attempts must be >= 1, got {max_attempts}")
+        if delay < 0:
+            raise ValueError(f"delay must be >= 0, got {delay}")
+        self._max_attempts = max_attempts
+        self._delay = delay
+
+    @property
+    def max_attempts(self) -> int:
+        return self._max_attempts
+
+    @property
+    def delay(self) -> float:
+        return self._delay
+
+    def should_retry(self, attempt: int, error: Exception | None = None) -> bool:
+        return attempt < self._max_attempts
+
+    def get_delay(self, attempt: int) -> float:
+        return self._delay
+
+
+class ExponentialBackoff:
+    """retry.py:163-289: min(initial_delay * multiplier ** max(0, attempt - 2), max_delay), plus random.uniform(0, jitter) when
+    jitter > 0 (the process-wide generator: such a policy works on the host, a Client that holds one is not lowered)."""
+
+    def __init__(self, max_attempts: int, initial_delay: float, max_delay: float, multiplier: float = 2.0, jitter: float = 0.0):
+        if max_attempts < 1:
+            raise ValueError(f"max_attempts must be >= 1, got {max_attempts}")
+        if initial_delay <= 0:
+            raise ValueError(f"initial_delay must be > 0, got {initial_delay}")
+        if max_delay < initial_delay:
+            raise ValueError(f"max_delay ({max_delay}) must be >= initial_delay ({initial_delay})")
+        if multiplier < 1:
+            raise ValueError(f"multiplier must be >= 1, got {multiplier}")
+        if jitter < 0:
+            raise ValueError(f"jitter must be >= 0, got {jitter}")
+        self._max_attempts = max_attempts
+        self._initial_delay = initial_delay
+        self._max_delay = max_delay
+        self._multiplier = multiplier
+        self._jitter = jitter
+
+    @property
+    def max_attempts(self) -> int:
+        return self._max_attempts
+
+    @property
+    def initial_delay(self) -> float:
+        return self._initial_delay
+
+    @property
+    def max_delay(self) -> float:
+        return self._max_delay
+
+    @property
+    def multiplier(self) -> float:
+        return self._multiplier
+
+    @property
+    def jitter(self) -> float:
+        return self._jitter
+
+    def should_retry(self, attempt: int, error: Exception | None = None) -> bool:
+        return attempt < self._max_attempts
+
+    def get_delay(self, attempt: int) -> float:
+        exponent = max(0, attempt - 2)
+        delay = self._initial_delay * (self._multiplier**exponent)
+        delay = min(delay, self._max_delay)
+        if self._jitter > 0:
+            delay += _random.uniform(0, self._jitter)
+        return delay
+
+
+class DecorrelatedJitter:
+    """retry.py:292-395: random.uniform(base_delay, min(max_delay, previous * 3)) from the process-wide generator -- host only, a Client
+    that holds one is not lowered."""
+
+    def __init__(self, max_attempts: int, base_delay: float, max_delay: float):
+        if max_attempts < 1:
+            raise ValueError(f"max_attempts must be >= 1, got {max_attempts}")
+        if base_delay <= 0:
+            raise ValueError(f"base_delay must be > 0, got {base_delay}")
+        if max_delay < base_delay:
+            raise ValueError(f"max_delay ({max_delay}) must be >= base_delay ({base_delay})")
+        self._max_attempts = max_attempts
+        self._base_delay = base_delay
+        self._max_delay = max_delay
+        self._previous_delay = base_delay
+
+    @property
+    def max_attempts(self) -> int:
+        return self._max_attempts
+
+    @property
+    def base_delay(self) -> float:
+        return self._base_delay
+
+    @property
+    def max_delay(self) -> float:
+        return self._max_delay
+
+    def should_retry(self, attempt: int, error: Exception | None = None) -> bool:
+        return attempt < self._max_attempts
+
+    def get_delay(self, attempt: int) -> float:
+        upper = min(self._max_delay, self._previous_delay * 3)
+        delay = _random.uniform(self._base_delay, upper)
+        self._previous_delay = delay
+        return delay
+
+    def reset(self) -> None:
+        self._previous_delay = self._base_delay
+
+
+@dataclass(frozen=True)
+class ClientStats:
+    """client.py:34-42."""
+
+    requests_sent: int = 0
+    responses_received: int = 0
+    timeouts: int = 0
+    retries: int = 0
+    failures: int = 0
+
+
+class Client(Entity):
+    """Sends every Event it receives on to `target` as a NEW Event with a completion hook, waits `timeout` seconds (None: for ever)
+    for the hook's response and answers a timeout as `retry_policy` says (client.py:45-470).  Attempts are keyed
+    (request_id, attempt); a Request that did not come from `send_request` has no request_id, so all of them share the keys
+    (None, attempt), as in the reference.  `on_success` / `on_failure` are host callables: not lowered."""
+
+    MAX_ATTEMPTS = 65536                      # include/hs_engine.h HS_CLIENT_MAX_ATTEMPTS
+    MAX_REQUEST_ID = 1 << 30                  # a request_id the engine carries is a positive int below this
+
+    def __init__(self, name: str, target: Entity, timeout: float | None = None, retry_policy=None, on_success=None, on_failure=None):
+        super().__init__(name)
+        if timeout is not None and timeout < 0:                                           # client.py:89-90
+            raise ValueError(f"timeout must be >= 0, got {timeout}")
+        self._target = target
+        self._timeout = timeout
+        self._retry_policy = retry_policy or NoRetry()
+        self._on_success = on_success
+        self._on_failure = on_failure
+        self._in_flight: dict[tuple, dict] = {}    # after a run: the (request_id or None, attempt) keys in flight
+        self._next_request_id = 0
+        self._requests_sent = 0
+        self._responses_received = 0
+        self._timeouts = 0
+        self._retries = 0
+        self._failures = 0
+        self._response_times: list[float] = []
+        self._sim = None                           # the Simulation that lists it: its clock (core/simulation.py:118-135)
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._target]
+
+    @property
+    def target(self) -> Entity:
+        return self._target
+
+    @property
+    def timeout(self) -> float | None:
+        return self._timeout
+
+    @property
+    def retry_policy(self):
+        return self._retry_policy
+
+    @property
+    def in_flight_count(self) -> int:
+        return len(self._in_flight)
+
+    @property
+    def average_response_time(self) -> float:
+        if not self._response_times:
+            return 0.0
+        return sum(self._response_times) / len(self._response_times)
+
+    @property
+    def stats(self) -> ClientStats:
+        return ClientStats(requests_sent=self._requests_sent, responses_received=self._responses_received, timeouts=self._timeouts,
+                           retries=self._retries, failures=self._failures)
+
+    def send_request(self, payload=None, event_type: str = "request", on_success=None, on_failure=None) -> Event:
+        """client.py:163-204: the next request id and an Event aimed at this Client, ready for `Simulation.schedule()` once the caller
+        has set its time.  Its time is the clock's `now`: Instant.Epoch outside a Simulation, the Simulation's start time before
+        run(), its current time afterwards."""
+        self._next_request_id += 1
+        now = self._sim._current_time if self._sim is not None else Instant.Epoch
+        return Event(time=now, event_type=event_type, target=self,
+                     context={"metadata": {"request_id": self._next_request_id, "payload": payload, "attempt": 1, "client_name": self.name},
+                              "_on_success": on_success or self._on_success, "_on_failure": on_failure or self._on_failure})
+
+    def get_response_time_percentile(self, percentile: float) -> float:
+        """client.py:445-470."""
+        if not self._response_times:
+            return 0.0
+        sorted_times = sorted(self._response_times)
+        n = len(sorted_times)
+        if percentile <= 0:
+            return sorted_times[0]
+        if percentile >= 1:
+            return sorted_times[-1]
+        pos = percentile * (n - 1)
+        lo = int(pos)
+        hi = min(lo + 1, n - 1)
+        frac = pos - lo
+        return sorted_times[lo] * (1.0 - frac) + sorted_times[hi] * frac
+
+
 # ---- probes --------------------------------------------------------------------------------------
 class Data:
     """Time-series container of a Probe (instrumentation/data.py:20-110): `values` = [(time_s, value), ...]."""
@@ -1497,12 +1729,12 @@ class Probe(Entity):
     """Periodic metric sampler (instrumentation/probe.py:81-164): a daemon Source that reads `getattr(target, metric)`
     every `interval` seconds into a Data container.  Lowered metrics: Server.depth / active_requests / utilization / available_capacity / has_capacity /
     stats_accepted / stats_dropped / requests completed, Sink.events_received, Source.generated_count, RateLimitedEntity.queue_depth,
-    Bulkhead.active_count / queue_depth / available_permits, TimeoutWrapper.in_flight_count."""
+    Bulkhead.active_count / queue_depth / available_permits, TimeoutWrapper.in_flight_count, Client.in_flight_count."""
 
     _LOWERED = {"depth", "active_requests", "utilization", "available_capacity", "has_capacity", "stats_accepted", "stats_dropped",
                 "requests_completed", "_requests_completed", "events_received", "generated_count", "_generated_count", "queue_depth",
                 "active_count", "available_permits", "in_flight_count"}
-    _ON_WRAPPER = {"active_count": Bulkhead, "available_permits": Bulkhead, "in_flight_count": TimeoutWrapper}
+    _ON_WRAPPER = {"active_count": Bulkhead, "available_permits": Bulkhead, "in_flight_count": (TimeoutWrapper, Client)}
     # Server attributes that are functions of `active_requests` and the (fixed) concurrency: the engine samples the integer,
     # the Data container applies the reference's expression (components/server/server.py:153-173,191-200, concurrency.py:117-131)
     _ON_ACTIVE = ("utilization", "available_capacity", "has_capacity")

@@ -21,10 +21,11 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .core.temporal import Instant
-from .entities import (BackendHealthState, Bulkhead, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
+from .core.temporal import Duration, Instant
+from .entities import (BackendHealthState, Bulkhead, Client, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
                        ExponentialLatency, HealthChecker, IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random,
                        RandomRouter, RateLimitedEntity, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source,
+                       DecorrelatedJitter, ExponentialBackoff, FixedRetry, NoRetry,
                        TimeoutWrapper, TokenBucketPolicy, WeightedLeastConnections, WeightedRoundRobin)
 
 _STRATEGY_CODE = ((ConsistentHash, N.LB_CONSISTENT_HASH), (RoundRobin, N.LB_ROUND_ROBIN), (Random, N.LB_RANDOM),
@@ -80,6 +81,16 @@ class GraphArrays:
         self.wrap_params = None              # [n, 5] float64: BULKHEAD nodes -- max_concurrent, max_wait_queue, max_wait_time (-1: None);
                                              #   TIMEOUT_WRAPPER nodes -- column 3 = timeout, column 4 = the in-flight table's first capacity
                                              #   (0: the engine's default); set through hs_graph_set_wrapper
+
+        self.cl_params = None                # [n, 2] float64: CLIENT nodes -- timeout (-1: None), the in-flight table's first capacity
+                                             #   (0: the engine's default); set through hs_graph_set_client with ...
+        self.cl_delay_off = None             # [n + 1] int64 and
+        self.cl_delays_ns = None             # int64: Duration.from_seconds(policy.get_delay(a)) for a = 1 .. max_attempts - 1 of every
+                                             #   Client, back to back
+
+    @property
+    def has_clients(self) -> bool:
+        return self.cl_params is not None
 
     @property
     def has_health(self) -> bool:
@@ -177,6 +188,36 @@ class GraphEngine:
                 self.close()
                 raise
 
+        if arrays.has_clients:
+            try:
+                for i in np.nonzero(arrays.kind == N.NODE_CLIENT)[0]:
+                    timeout, cap = arrays.cl_params[i]
+                    delays = np.ascontiguousarray(arrays.cl_delays_ns[arrays.cl_delay_off[i]:arrays.cl_delay_off[i + 1]], np.int64)
+                    self._check(self._lib.hs_graph_set_client(self._h, int(i), float(timeout), _ptr(delays) if len(delays) else None, len(delays),
+                                                              int(table_capacity) if table_capacity else int(cap)))
+            except BaseException:
+                self.close()
+                raise
+
+    def client(self, node: int) -> dict:
+        """hs_graph_get_client of a Client node: its counters by name and the keys in flight as sorted (request_id or 0, attempt) rows."""
+        c = np.zeros(N.CLIENT_COUNTERS, np.int64)
+        self._check(self._lib.hs_graph_get_client(self._h, int(node), _ptr(c), None, 0, None))
+        live = int(c[5])
+        keys = np.zeros((max(live, 1), 2), np.int64)
+        self._check(self._lib.hs_graph_get_client(self._h, int(node), None, _ptr(keys), live, None))
+        keys = keys[:live]
+        out = {k: int(v) for k, v in zip(("requests_sent", "responses_received", "timeouts", "retries", "failures", "in_flight_count",
+                                           "table_capacity"), c)}
+        out["in_flight_keys"] = keys[np.lexsort((keys[:, 1], keys[:, 0]))]
+        return out
+
+    def client_events(self) -> np.ndarray:
+        """The graph's Client request / response / timeout Events of the run."""
+        events = np.zeros(3, np.int64)
+        self._check(self._lib.hs_graph_get_client(self._h, -1, None, None, 0, _ptr(events)))
+        return events
+
     def wrapper(self, node: int) -> dict:
         """hs_graph_get_wrapper of a Bulkhead or TimeoutWrapper node: its counters by name, the ids of its wait queue (head first) and
         the ids in flight (ascending)."""
@@ -244,8 +285,12 @@ class GraphEngine:
             raise N.EngineError(rc, (self._lib.hs_graph_last_error(self._h) or b"").decode())
         return rc
 
-    def schedule(self, node: int, time_ns: int) -> None:
-        self._check(self._lib.hs_graph_schedule(self._h, int(node), int(time_ns)))
+    def schedule(self, node: int, time_ns: int, request_id: int | None = None) -> None:
+        """hs_graph_schedule; with a `request_id` (0: none) hs_graph_schedule_client: Client.send_request's Event."""
+        if request_id is None:
+            self._check(self._lib.hs_graph_schedule(self._h, int(node), int(time_ns)))
+        else:
+            self._check(self._lib.hs_graph_schedule_client(self._h, int(node), int(time_ns), int(request_id)))
 
     def add_fault(self, node: int, time_ns: int, on: bool, cancelled: bool = False) -> None:
         """hs_graph_add_fault: one fault Event (set / clear the crashed flag of `node`), numbered in call order."""
@@ -323,6 +368,36 @@ class GeneralGraph:
         self.node_of = node_of          # id(entity) -> node id
 
 
+def client_delay_table(policy, what: str) -> np.ndarray:
+    """Duration.from_seconds(policy.get_delay(a)) in whole nanoseconds for a = 1 .. max_attempts - 1: what a Client's timeout handler
+    adds to `now` for the retry of attempt a (client.py:393-410).  The device never evaluates a policy."""
+    from .lowering import UnsupportedTopology
+
+    if type(policy) is NoRetry:
+        return np.zeros(0, np.int64)
+    if type(policy) is DecorrelatedJitter:
+        raise UnsupportedTopology(f"{what}: DecorrelatedJitter draws from the process-wide random generator (not lowered; a follow-up)")
+    if type(policy) not in (FixedRetry, ExponentialBackoff):
+        raise UnsupportedTopology(f"{what}: retry policy {type(policy).__name__} is not lowered (NoRetry, FixedRetry, ExponentialBackoff are)")
+    if type(policy) is ExponentialBackoff and policy.jitter > 0:
+        raise UnsupportedTopology(f"{what}: ExponentialBackoff(jitter={policy.jitter}) draws from the process-wide random generator "
+                                  "(not lowered; a follow-up)")
+    if policy.max_attempts > Client.MAX_ATTEMPTS:
+        raise UnsupportedTopology(f"{what}: max_attempts = {policy.max_attempts} is beyond the {Client.MAX_ATTEMPTS} attempts the engine's "
+                                  "key holds")
+    out = np.zeros(policy.max_attempts - 1, np.int64)
+    for k in range(len(out)):
+        try:
+            ns = Duration.from_seconds(policy.get_delay(k + 1)).nanoseconds
+            if not 0 <= ns < (1 << 62):
+                raise OverflowError(ns)
+        except (OverflowError, ValueError, TypeError) as e:
+            raise UnsupportedTopology(f"{what}: the delay of attempt {k + 1} cannot be evaluated as a Duration "
+                                      f"({type(e).__name__}: {e})") from None
+        out[k] = ns
+    return out
+
+
 def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
     """`sources` / `entities` of a Simulation -> the node arrays of the single-heap engine.  Refuses by name what that engine
     does not run either (lowering.UnsupportedTopology)."""
@@ -351,7 +426,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             raise UnsupportedTopology(f"probe '{pr.name}' is listed twice")
         add(pr)
     n_front = len(nodes)
-    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker, Bulkhead, TimeoutWrapper) + _SINKS
+    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker, Bulkhead, TimeoutWrapper, Client) + _SINKS
 
     def check(ent, where):
         if isinstance(ent, Source):
@@ -394,6 +469,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
     policies_seen: dict[int, str] = {}                        # id(policy) -> the limiter that holds it
     checked: dict[int, str] = {}                              # id(LoadBalancer) -> its HealthChecker
     unhealthy: dict[int, list[int]] = {}                      # rt offset -> is_healthy of a LoadBalancer's backends, one of them unhealthy
+    client_delays: list = []                                  # per node: a Client's delay table in ns
     for i, ent in enumerate(nodes):
         if isinstance(ent, Source):
             ep, prov = ent._event_provider, ent._time_provider
@@ -432,11 +508,12 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             m = Probe.engine_metric(ent.metric)
             tgt = ent.target
             on_wrapper = isinstance(tgt, (Bulkhead, TimeoutWrapper)) and m in N.PROBE_WRAPPER_METRICS
-            if m not in N.PROBE_METRICS and not on_wrapper:
+            on_client = isinstance(tgt, Client) and m in N.PROBE_CLIENT_METRICS
+            if m not in N.PROBE_METRICS and not on_wrapper and not on_client:
                 raise UnsupportedTopology(f"probe '{ent.name}': metric '{ent.metric}' is not sampled on the engine")
             if id(tgt) not in node_of:
                 raise UnsupportedTopology(f"probe '{ent.name}': its target is not an entity of this Simulation")
-            want = (TimeoutWrapper if m == "in_flight_count" else Bulkhead) if on_wrapper else Source if m == "generated_count" else _SINKS if m == "events_received" else RateLimitedEntity if m == "queue_depth" else Server
+            want = Client if on_client else (TimeoutWrapper if m == "in_flight_count" else Bulkhead) if on_wrapper else Source if m == "generated_count" else _SINKS if m == "events_received" else RateLimitedEntity if m == "queue_depth" else Server
             if not isinstance(tgt, want):
                 raise UnsupportedTopology(f"probe '{ent.name}': metric '{ent.metric}' is not an attribute of {type(tgt).__name__}")
             if a.probe_metric is None:
@@ -444,7 +521,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
                 a.probe_interval_s = np.ones(n, np.float64)
             a.kind[i] = N.NODE_PROBE
             a.target[i] = node_of[id(tgt)]
-            a.probe_metric[i] = N.PROBE_WRAPPER_METRICS[m] if on_wrapper else N.PROBE_METRICS[m]
+            a.probe_metric[i] = N.PROBE_CLIENT_METRICS[m] if on_client else N.PROBE_WRAPPER_METRICS[m] if on_wrapper else N.PROBE_METRICS[m]
             a.probe_interval_s[i] = ent.interval
         elif isinstance(ent, Server):
             svc = ent.service_time
@@ -532,6 +609,10 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             end, hops = tgt, 0
             while isinstance(end, NetworkLink) and end.egress is not None and hops <= n:
                 end, hops = end.egress, hops + 1
+            if isinstance(end, Client):
+                via = " (through its NetworkLinks)" if end is not tgt else ""
+                raise UnsupportedTopology(f"{what}: its target{via} is the Client '{end.name}' -- two completion hooks on one Event are not "
+                                          "lowered (a follow-up)")
             if isinstance(end, (LoadBalancer, Bulkhead, TimeoutWrapper)):
                 via = " (through its NetworkLinks)" if end is not tgt else ""
                 raise UnsupportedTopology(f"{what}: its target{via} is the {type(end).__name__} '{end.name}' -- two completion hooks on one "
@@ -556,6 +637,30 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
                     raise UnsupportedTopology(f"{what}: timeout must be finite")
                 a.kind[i] = N.NODE_TIMEOUT_WRAPPER
                 a.wrap_params[i, 3] = ent.timeout
+        elif isinstance(ent, Client):
+            what = f"Client '{ent.name}'"
+            tgt = ent.target
+            if isinstance(tgt, (Source, Probe, HealthChecker)) or not isinstance(tgt, Entity) or id(tgt) not in node_of:
+                raise UnsupportedTopology(f"{what}: its target {type(tgt).__name__} '{getattr(tgt, 'name', tgt)}' takes no Requests")
+            end, hops = tgt, 0
+            while isinstance(end, NetworkLink) and end.egress is not None and hops <= n:
+                end, hops = end.egress, hops + 1
+            if isinstance(end, (LoadBalancer, Bulkhead, TimeoutWrapper, Client)):
+                via = " (through its NetworkLinks)" if end is not tgt else ""
+                raise UnsupportedTopology(f"{what}: its target{via} is the {type(end).__name__} '{end.name}' -- two completion hooks on one "
+                                          "Event are not lowered (a follow-up)")
+            if ent._on_success is not None or ent._on_failure is not None:
+                raise UnsupportedTopology(f"{what}: on_success= / on_failure= are host callables (not lowered)")
+            if ent.timeout is not None and not np.isfinite(ent.timeout):
+                raise UnsupportedTopology(f"{what}: timeout must be finite or None")
+            delays = client_delay_table(ent.retry_policy, what)
+            if a.cl_params is None:
+                a.cl_params = np.zeros((n, 2), np.float64)
+                client_delays = [np.zeros(0, np.int64) for _ in range(n)]
+            a.kind[i] = N.NODE_CLIENT
+            a.target[i] = node_of[id(tgt)]
+            a.cl_params[i, 0] = -1.0 if ent.timeout is None else float(ent.timeout)
+            client_delays[i] = delays
         elif isinstance(ent, RateLimitedEntity):
             pol = ent.policy
             if type(pol) not in LIMITER_POLICIES:
@@ -603,6 +708,10 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
         else:
             a.kind[i] = N.NODE_SINK
     a.rt_targets = np.array(rt, np.int32)
+    if a.cl_params is not None:
+        a.cl_delay_off = np.zeros(n + 1, np.int64)
+        a.cl_delay_off[1:] = np.cumsum([len(d) for d in client_delays])
+        a.cl_delays_ns = np.concatenate(client_delays).astype(np.int64)
     if weights:
         a.lb_weights = np.ones(len(rt), np.int32)
         for off, ws in weights.items():
@@ -655,7 +764,7 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
     new_index = np.empty(n, np.int64)
     per_node = [nm for nm in ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s",
                               "link_lat_min_s", "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric",
-                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params")
+                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params", "cl_params")
                 if getattr(a, nm) is not None]
     names = None if a.names is None else [a.names[a.name_off[i]:a.name_off[i + 1]] for i in range(n)]
     parts = []
@@ -688,6 +797,13 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
             b.lb_healthy = None
         if b.wrap_params is not None and not ((b.kind == N.NODE_BULKHEAD) | (b.kind == N.NODE_TIMEOUT_WRAPPER)).any():
             b.wrap_params = None                                           # (a part without a wrapper runs the loop it would run alone)
+        if b.cl_params is not None and not (b.kind == N.NODE_CLIENT).any():
+            b.cl_params = None                                             # (a part without a Client likewise)
+        if b.cl_params is not None:
+            tables = [a.cl_delays_ns[a.cl_delay_off[i]:a.cl_delay_off[i + 1]] for i in ids]
+            b.cl_delay_off = np.zeros(m + 1, np.int64)
+            b.cl_delay_off[1:] = np.cumsum([len(x) for x in tables])
+            b.cl_delays_ns = np.concatenate(tables).astype(np.int64)
         if names is not None:
             blobs = [names[i] for i in ids]
             b.names = b"".join(blobs)
@@ -754,6 +870,16 @@ class PartRun:
 
     def wrapper_events(self) -> np.ndarray:
         return np.sum([e.wrapper_events() for e in self.engines], axis=0).astype(np.int64)
+
+    def client_events(self) -> np.ndarray:
+        return np.sum([e.client_events() for e in self.engines], axis=0).astype(np.int64)
+
+    def client(self, node: int) -> dict:
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            at = np.searchsorted(ids, node)
+            if at < len(ids) and ids[at] == node:
+                return e.client(int(at))
+        raise KeyError(node)
 
     def wrapper(self, node: int) -> dict:
         for (ids, _pos, _b), e in zip(self.parts, self.engines):
@@ -831,10 +957,10 @@ def keyless_hazard(g: "GeneralGraph", target) -> str | None:
 
 
 def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t: np.ndarray, rec_cr: np.ndarray, device: int = 0,
-                       health=None, wrapper=None) -> None:
+                       health=None, wrapper=None, client=None) -> None:
     """The run's per-node results onto the user's objects, under the attribute names the reference uses (lowering.write_back's
     counterpart).  `health`: node -> GraphEngine.health(node) of a graph with health state; `wrapper`: node -> GraphEngine.wrapper(node)
-    of a graph with a Bulkhead or a TimeoutWrapper."""
+    of a graph with a Bulkhead or a TimeoutWrapper; `client`: node -> GraphEngine.client(node) of a graph with a Client."""
     a = g.arrays
     order = np.argsort(rec_node, kind="stable")              # per Sink, still in processing order
     bounds = np.searchsorted(rec_node[order], np.arange(a.n + 1))
@@ -904,6 +1030,14 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
             ent._next_request_id = w["next_request_id"]
             ent._wait_queue = [int(x) for x in w["queue_ids"]]
             ent._in_flight = {int(x): {} for x in w["in_flight_ids"]}
+        elif isinstance(ent, Client):
+            w = client(i)
+            (ent._requests_sent, ent._responses_received, ent._timeouts, ent._retries, ent._failures) = (w[k] for k in (
+                "requests_sent", "responses_received", "timeouts", "retries", "failures"))
+            ent._in_flight = {(int(rid) or None, int(att)): {} for rid, att in w["in_flight_keys"]}
+            # _response_times: (now - start_time).to_seconds() of every response, in order -- the rows hold both in nanoseconds
+            rows = order[bounds[i]:bounds[i + 1]]
+            ent._response_times = [Duration(int(ns)).to_seconds() for ns in rec_t[rows]]
         elif isinstance(ent, TimeoutWrapper):
             w = wrapper(i)
             ent._total_requests, ent._successful_requests, ent._timed_out_requests = w["total"], w["successful"], w["timed_out"]

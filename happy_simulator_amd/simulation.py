@@ -14,7 +14,7 @@ from .core.temporal import Instant
 from .engine import StationEngine
 from .graph_engine import (DEFAULT_MAX_EVENTS, MAX_PARTS, GeneralGraph, GraphEngine, PartRun, keyless_hazard, lower_general, split_parts,
                            write_back_general)
-from .entities import Bulkhead, Entity, HealthChecker, LoadBalancer, Server, TimeoutWrapper
+from .entities import Bulkhead, Client, Entity, HealthChecker, LoadBalancer, Server, TimeoutWrapper
 from .faults import FaultSchedule
 from .lowering import (LazyRecords, LbGraph, LoweredGraph, UnsupportedTopology, attach_lb_probes, attach_probes, find_load_balancer, lower,
                        plain_probe_arrays, write_back_plain_probes,
@@ -62,6 +62,8 @@ class Simulation:
         for ent in self._entities:                 # the clock every listed entity is handed (core/simulation.py:118-135): a
             if isinstance(ent, HealthChecker):     # checker's start() reads `now` from it
                 ent._sim_start = self._start_time
+            if isinstance(ent, Client):            # ... and a Client's send_request()
+                ent._sim = self
         self._seed = _DEFAULT_SEED if seed is None else int(seed)
         self._device = device
         # engine capacities (records per station log / in-flight messages per station / messages per exchange row); None =
@@ -138,7 +140,15 @@ class Simulation:
         firsts = [getattr(getattr(s, "_event_provider", None), "_target", None) for s in self._sources]
         return any(isinstance(e, (Bulkhead, TimeoutWrapper)) for e in self._entities + firsts)
 
+    def _has_clients(self) -> bool:
+        """A Client among the entities or as a Source's target: retries, which only the single-heap loop follows."""
+        firsts = [getattr(getattr(s, "_event_provider", None), "_target", None) for s in self._sources]
+        return any(isinstance(e, Client) for e in self._entities + firsts)
+
     def lowered(self) -> "LoweredGraph | LbGraph | GeneralGraph":
+        if self._graph is None and self._has_clients():
+            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._station_refusal = "the station, network and pipeline engines do not lower a Client"
         if self._graph is None and self._has_wrappers():
             self._graph = lower_general(self._sources, self._entities, self._probes)
             self._station_refusal = "the station, network and pipeline engines do not lower Bulkhead or TimeoutWrapper"
@@ -371,8 +381,8 @@ class Simulation:
                                                record_capacity=4096))
                 for node, t, on, cancelled in faults:              # (a fault Event lives in the part of the entity it names)
                     engines[int(part_of[node])].add_fault(int(local[node]), t, on, cancelled)
-                for node, t in sched:                              # (call order: each part keeps the order of its own)
-                    engines[int(part_of[node])].schedule(int(local[node]), t)
+                for node, t, *rid in sched:                        # (call order: each part keeps the order of its own)
+                    engines[int(part_of[node])].schedule(int(local[node]), t, *rid)
                 run = PartRun(g.arrays, parts, engines)
                 if run.run(end_ns):
                     self._graph_parts = len(parts)
@@ -420,7 +430,24 @@ class Simulation:
                                           "RateLimitedEntity of this Simulation are lowered")
             if ev.on_complete:
                 raise UnsupportedTopology(f"scheduled event {ev!r}: completion hooks are host Python (not lowered)")
-            if ev.context.get("created_at") != ev.time:
+            rid = None
+            if a.kind[i] == N.NODE_CLIENT:
+                # Client.send_request's Event or a plain one: the Client reads metadata request_id / attempt and never passes
+                # created_at on (client.py:233-282)
+                md = ev.context.get("metadata") or {}
+                if ev.event_type in ("_client_timeout", "_client_response"):
+                    raise UnsupportedTopology(f"scheduled event {ev!r}: a Client's own '{ev.event_type}' Event is not lowered")
+                if ev.context.get("_on_success") is not None or ev.context.get("_on_failure") is not None:
+                    raise UnsupportedTopology(f"scheduled event {ev!r}: on_success= / on_failure= are host callables (not lowered)")
+                if md.get("attempt", 1) != 1 or isinstance(md.get("attempt", 1), bool):
+                    raise UnsupportedTopology(f"scheduled event {ev!r}: attempt = {md.get('attempt')!r} is not lowered (a scheduled request is "
+                                              "attempt 1)")
+                rid = md.get("request_id")
+                if rid is not None and (type(rid) is not int or not 0 < rid < Client.MAX_REQUEST_ID):
+                    raise UnsupportedTopology(f"scheduled event {ev!r}: request_id = {rid!r} is not lowered (None or a positive int below "
+                                              "2^30)")
+                rid = 0 if rid is None else rid
+            elif ev.context.get("created_at") != ev.time:
                 raise UnsupportedTopology(f"scheduled event {ev!r}: a custom created_at is not lowered")
             lb_name = None if a.kind[i] == N.NODE_HEALTH_CHECKER else keyless_hazard(g, ev.target)
             if lb_name is not None:
@@ -432,7 +459,7 @@ class Simulation:
             if ev.time.nanoseconds < start_ns:     # "time travel": the loop skips it without counting (simulation.py:480-489)
                 warnings.warn(f"Time travel detected: {ev!r} lies before the simulation start; skipping event", stacklevel=3)
                 continue
-            sched.append((i, ev.time.nanoseconds))
+            sched.append((i, ev.time.nanoseconds) if rid is None else (i, ev.time.nanoseconds, rid))
         return end_ns, start_ns, sched, cancelled_ns
 
     def _general_engine(self, g: GeneralGraph, start_ns: int, sched, record_capacity: int = 0) -> GraphEngine:
@@ -441,8 +468,8 @@ class Simulation:
         try:
             for node, t, on, cancelled in self._general_faults(g):
                 eng.add_fault(node, t, on, cancelled)
-            for node, t in sched:
-                eng.schedule(node, t)
+            for node, t, *rid in sched:
+                eng.schedule(node, t, *rid)
         except BaseException:
             eng.close()
             raise
@@ -457,9 +484,9 @@ class Simulation:
         es = eng.summary()
         stats = eng.stats()
         rec = eng.records()
-        health, wrappers = g.arrays.has_health, g.arrays.has_wrappers
+        health, wrappers, clients = g.arrays.has_health, g.arrays.has_wrappers, g.arrays.has_clients
         write_back_general(g, stats, *rec, device=self._device, health=eng.health if health else None,
-                           wrapper=eng.wrapper if wrappers else None)
+                           wrapper=eng.wrapper if wrappers else None, client=eng.client if clients else None)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
         if health:
@@ -469,7 +496,10 @@ class Simulation:
         if wrappers:
             # the wrappers' request / response / timeout Events: six more internal kinds, counted the same way
             self._resilience_by_kind = eng.wrapper_events()
-        if (health or wrappers) and not self._faults:
+        if clients:
+            # the Clients' request / response / timeout Events: three more internal kinds, counted the same way
+            self._client_by_kind = eng.client_events()
+        if (health or wrappers or clients) and not self._faults:
             self._internal_by_kind = eng.faults()[1]
         if self._faults:
             crashed, internal, popped_cancelled = eng.faults()

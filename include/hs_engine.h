@@ -193,6 +193,7 @@ typedef enum hs_probe_metric {
     HS_PROBE_BH_QUEUE_DEPTH = 9,   /* Bulkhead.queue_depth */
     HS_PROBE_BH_PERMITS = 10,  /* Bulkhead.available_permits */
     HS_PROBE_TW_IN_FLIGHT = 11,/* TimeoutWrapper.in_flight_count */
+    HS_PROBE_CL_IN_FLIGHT = 12,/* Client.in_flight_count (general graphs only) */
     HS_PROBE_NONE = 255
 } hs_probe_metric;
 typedef enum hs_profile_kind { HS_PROF_CONSTANT = 0, HS_PROF_LINEAR_RAMP = 1, HS_PROF_SPIKE = 2 } hs_profile_kind;
@@ -748,7 +749,8 @@ typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK
                              HS_NODE_RATE_LIMITER = 7, /* RateLimitedEntity: `target` = its downstream, `queue_cap` = its FIFO capacity; policy: hs_graph_set_limiter_policy */
                              HS_NODE_HEALTH_CHECKER = 8, /* HealthChecker: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_health_checker */
                              HS_NODE_BULKHEAD = 9,        /* Bulkhead: `target` = the entity it protects; everything else: hs_graph_set_wrapper */
-                             HS_NODE_TIMEOUT_WRAPPER = 10 /* TimeoutWrapper: `target` = the entity it wraps; everything else: hs_graph_set_wrapper */
+                             HS_NODE_TIMEOUT_WRAPPER = 10, /* TimeoutWrapper: `target` = the entity it wraps; everything else: hs_graph_set_wrapper */
+                             HS_NODE_CLIENT = 11          /* Client: `target` = the entity it sends to; everything else: hs_graph_set_client */
 } hs_node_kind;
 
 typedef struct hs_graph_config {
@@ -975,6 +977,40 @@ int hs_graph_set_wrapper(hs_graph *g, int32_t node, int32_t max_concurrent, int3
  * node = -1 with the three node outputs NULL: the event counts alone. */
 int hs_graph_get_wrapper(hs_graph *g, int32_t node, int64_t *counters, int64_t *queue_ids, int64_t queue_cap, int64_t *in_flight_ids,
                          int64_t in_flight_cap, int64_t *events);
+/* Client with timeouts and retry policies (components/client/client.py, retry.py).  A graph that holds one runs a fifth
+ * instantiation of the loop (it carries the fault, health and wrapper code too).  Every Event that reaches a Client and is neither its
+ * `_client_response` nor its `_client_timeout` is an outgoing request: `_in_flight[(request_id, attempt)]` is set (an equal key is
+ * overwritten), a NEW Event for `target` is constructed -- its context is the metadata alone, so `created_at` downstream is the send
+ * time of THIS attempt and no client id survives -- with the Client's completion hook, then the timeout Event at now + timeout.  The
+ * hook fires where a wrapper's fires (see above; twice behind a NetworkLink, never at a crashed target).  A response of a key in
+ * flight removes it and appends now - start_time to the response times; a timeout of a key in flight removes it and, while
+ * attempt < max_attempts, constructs the retry -- a request at the Client with attempt + 1 -- at now + delays_ns[attempt - 1];
+ * otherwise it counts a failure.  A Request from a Source, a Server, a link, a router, a limiter or hs_graph_schedule has no request_id:
+ * all of them share the keys (None, attempt), as in the reference.  Three more internal kinds -- request, response, timeout -- are
+ * aimed at the Client itself (dropped while it is crashed); they count in hs_summary.events_processed, not in events_by_kind.
+ * Refused (HS_E_UNSUPPORTED): a Client whose target is, directly or through a chain of NetworkLinks, a LoadBalancer, a Bulkhead, a
+ * TimeoutWrapper or a Client, and a wrapper whose target is a Client (two hooks on one Event); more than HS_CLIENT_MAX_ATTEMPTS
+ * attempts.
+ *
+ * hs_graph_set_client: timeout_s (negative: None; 0 is legal), the policy's delays in whole nanoseconds for attempt 1 ..
+ * max_attempts - 1 (n_delays = max_attempts - 1; NoRetry: 0) -- the host evaluates Duration.from_seconds(policy.get_delay(a)), the
+ * device never does -- and table_capacity, the keys the in-flight table holds at first (0: 256; it doubles on demand like a
+ * TimeoutWrapper's, nothing is ever dropped).  The reference's own ValueErrors as HS_E_INVALID with its texts.  Before the first run
+ * (HS_E_STATE afterwards); every Client node is configured before a run (HS_E_STATE otherwise). */
+#define HS_CLIENT_MAX_ATTEMPTS 65536
+#define HS_CLIENT_COUNTERS 7
+int hs_graph_set_client(hs_graph *g, int32_t node, double timeout_s, const int64_t *delays_ns, int32_t n_delays, int32_t table_capacity);
+/* An Event aimed at Client `node` with metadata request_id = `request_id` (1 .. 2^30 - 1; 0: none, which is what hs_graph_schedule on a
+ * Client node schedules) and attempt 1 -- Client.send_request's Event.  Numbered in call order with the other scheduled entries. */
+int hs_graph_schedule_client(hs_graph *g, int32_t node, int64_t time_ns, int32_t request_id);
+/* After a run, for `node` a Client (any output may be NULL):
+ *   counters[HS_CLIENT_COUNTERS]  requests_sent, responses_received, timeouts, retries, failures, len(_in_flight), the table's capacity;
+ *   in_flight_keys[2 * min(len(_in_flight), cap)]  (request_id or 0, attempt) of every key in flight, in no particular order;
+ *   events[3]         the graph's Client request / response / timeout Events: events_processed == sum(events_by_kind) + the internal
+ *                     kinds of hs_graph_get_faults, hs_graph_get_health, hs_graph_get_wrapper + sum(events).
+ * node = -1 with the two node outputs NULL: the event counts alone.  The response times are rows of the record log
+ * (hs_graph_read_records): node = the Client, t = the response time in ns, value = start_time in ns, in the order they were appended. */
+int hs_graph_get_client(hs_graph *g, int32_t node, int64_t *counters, int64_t *in_flight_keys, int64_t cap, int64_t *events);
 /* Auto-termination (core/simulation.py:306-322, end_time = Infinity): a run to end_ns = 2^61 ends in front of a pop when only daemon
  * events -- the limiters' polls -- are pending.  A run with any other end processes polls like any event. */
 /* Debug / tests only (no engine path calls it; the null stream, its own allocations): FixedWindowPolicy._get_window_start on the device, one (now_ns, window_s) pair per thread: out_div[i] = Python's float
