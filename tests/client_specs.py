@@ -8,8 +8,8 @@
      "again"   the Event object scheduled last, scheduled once more (its own time);
      "cancel"  a send_request() Event that is cancelled after it was scheduled (only behind every live one).
 
-tests/golden/make_golden_client.py runs the LIVE reference on every spec listed here (tests/client_reference.py reads the recordings
-back); `build()` wires the product's objects the same way.  Entities: servers + lbs + routers + links + limiters + sinks + wrappers +
+tests/golden/make_golden_client.py runs the LIVE reference on every spec listed here (tests/recorded.py CLIENT reads the recordings
+back); tests/graph_family.py `build()` wires the product's objects the same way.  Entities: servers + lbs + routers + links + limiters + sinks + wrappers +
 clients + checkers.  Every case stays small: 2 - 20 requests, or a few seconds of a Source of rate ~10.
 
   FIXTURES        named cases; TRACED: recorded with their full event trace
@@ -21,7 +21,6 @@ nanosecond the timeout's index is the smaller one, so it pops first (`timeout_ze
 import numpy as np
 
 import fault_specs as FS
-import happy_simulator_amd as hs
 import health_specs as HS
 import rate_limiter_specs as RS
 import resilience_specs as XS
@@ -308,104 +307,6 @@ def union_spec(names, name="client_union"):
     return out, members
 
 
-# ---- wiring, shared by the product (build) and the reference (make_golden_client.run_case) ------------------------------------------
-def wire(spec, F, ns, bulkhead_cls, timeout_cls, checker_cls):
-    """resilience_specs.wire with the Clients (`ns`: where Client and the policies come from): pools by kind, every reference
-    resolved once its object exists."""
-    sinks = [F.sink(j) for j in range(spec["n_sinks"])]
-    servers = [F.server(i, sv) for i, sv in enumerate(spec["servers"])]
-    limiters = [F.limiter(i, lm) for i, lm in enumerate(spec.get("limiters") or [])]
-    pools = {"sink": sinks, "server": servers, "limiter": limiters}
-    links = pools["link"] = [F.link(l, lk) for l, lk in enumerate(spec["links"])]
-    lbs = pools["lb"] = [F.lb(j, lb, [servers[b] for b in lb["backends"]]) for j, lb in enumerate(spec.get("lbs") or [])]
-    routers = pools["router"] = [None] * len(spec["routers"])
-    wrappers = pools["wrapper"] = [None] * len(spec["wrappers"])
-    clients = pools["client"] = [None] * len(spec["clients"])
-
-    def ref(r):
-        return servers[r] if isinstance(r, int) else pools[r[0]][r[1]]
-
-    def ready(r):
-        return isinstance(r, int) or pools[r[0]][r[1]] is not None
-
-    pending = [("router", r) for r in range(len(routers))] + [("wrapper", i) for i in range(len(wrappers))] + [("client", i) for i in range(len(clients))]
-    while pending:
-        progressed = False
-        for kind, i in list(pending):
-            if kind == "router" and all(ready(t) for t in spec["routers"][i]["targets"]):
-                routers[i] = F.router(i, [ref(t) for t in spec["routers"][i]["targets"]])
-            elif kind == "wrapper" and ready(spec["wrappers"][i]["to"]):
-                w = spec["wrappers"][i]
-                wrappers[i] = (bulkhead_cls(f"bh{i}", ref(w["to"]), max_concurrent=w["mc"], max_wait_queue=w["mq"], max_wait_time=w["mw"])
-                               if w["kind"] == "bulkhead" else timeout_cls(f"tw{i}", ref(w["to"]), timeout=w["timeout"]))
-            elif kind == "client" and ready(spec["clients"][i]["to"]):
-                c = spec["clients"][i]
-                clients[i] = ns.Client(f"cl{i}", ref(c["to"]), timeout=c["timeout"], retry_policy=make_policy(ns, c["policy"]))
-            else:
-                continue
-            pending.remove((kind, i))
-            progressed = True
-        assert progressed, "routers, wrappers and clients form a cycle"
-    for l, lk in enumerate(spec["links"]):
-        links[l].egress = None if lk["to"] is None else ref(lk["to"])
-    for i, lm in enumerate(spec.get("limiters") or []):
-        limiters[i]._downstream = ref(lm["out"])
-    for i, sv in enumerate(spec["servers"]):
-        if sv.get("out") is not None:
-            servers[i].downstream = ref(sv["out"])
-    sources = pools["source"] = [F.source(k, sc, ref(sc["to"])) for k, sc in enumerate(spec["sources"])]
-    probes = pools["probe"] = [F.probe(ref(on), metric, interval) for on, metric, interval in spec.get("probes") or []]
-    pools["checker"] = [checker_cls(f"hc{i}", lbs[ck["lb"]], interval=ck["interval"], timeout=ck["timeout"], healthy_threshold=ck["ht"],
-                                    unhealthy_threshold=ck["ut"]) for i, ck in enumerate(spec.get("checkers") or [])]
-    entities = servers + lbs + routers + links + limiters + sinks + wrappers + clients + pools["checker"]
-    return pools, sources, probes, entities
-
-
-def schedule_all(spec, pools, sim, event_cls, at):
-    """The spec's `schedule` list on `sim`, for either library (see the module docstring for the three modes)."""
-    last, cancel = None, []
-    for on, t_s, *mode in spec.get("schedule") or []:
-        target = pools[on[0]][on[1]]
-        mode = mode[0] if mode else "plain"
-        if mode == "again":
-            sim.schedule(last)
-            continue
-        if mode == "plain":
-            last = event_cls(time=at(t_s), event_type="Request", target=target)
-        else:
-            last = target.send_request()
-            last.time = at(t_s)
-        sim.schedule(last)
-        if mode == "cancel":
-            cancel.append(last)
-    for ev in cancel:
-        ev.cancel()
-
-
-def fault_targets(pools):
-    return FS.fault_targets(pools) + list(pools["wrapper"]) + list(pools["client"]) + list(pools["checker"])
-
-
-def build(spec, seed=None):
-    """(Simulation, entities by pool) of the product, wired like the recorded reference run."""
-    pools, sources, probes, entities = wire(spec, RS._Product, hs, hs.Bulkhead, hs.TimeoutWrapper, hs.HealthChecker)
-    start_ns = int(spec.get("start_ns", 0))
-
-    def at(t_s):
-        return hs.Instant(start_ns + hs.Instant.from_seconds(t_s).nanoseconds)
-
-    fs, handles = FS.make_schedule(hs, spec, pools)
-    sim = hs.Simulation(sources=sources, entities=entities, seed=spec["seed"] if seed is None else seed, max_graph_events=400_000,
-                        fault_schedule=fs, **({} if spec.get("auto") else {"end_time": at(spec["end_s"])}),
-                        **({"start_time": hs.Instant(start_ns)} if start_ns else {}), **({"probes": [p for p, _ in probes]} if probes else {}))
-    FS.cancel_after(spec, handles)
-    schedule_all(spec, pools, sim, hs.Event, at)
-    HS.start_checkers(spec, pools, sim, [[] for _ in pools["checker"]])
-    pools["probes"] = probes
-    pools["fault_schedule"], pools["handles"] = fs, handles
-    return sim, pools
-
-
 def client_results(pools):
     """What both libraries' Clients show after a run.  cl_stats rows: requests_sent, responses_received, timeouts, retries, failures,
     in_flight_count, _next_request_id; cl_keys: sorted (request_id or 0, attempt) rows of `_in_flight`; cl_response_times: the floats
@@ -420,20 +321,3 @@ def client_results(pools):
         toff.append(len(times))
     return dict(cl_stats=np.asarray(rows, np.int64).reshape(-1, 7), cl_keys=np.asarray(keys, np.int64).reshape(-1, 2), cl_keys_off=np.asarray(koff, np.int64),
                 cl_response_times=np.asarray(times, np.float64), cl_response_times_off=np.asarray(toff, np.int64))
-
-
-def results(spec, sim, pools):
-    """Everything make_golden_client.run_case records except the trace, read off the product's objects after run()."""
-    out = RS.results(spec, sim, pools)
-    out.pop("lb_current_weights", None)
-    out.update(FS.fault_results(pools["fault_schedule"], fault_targets(pools)))
-    out.update(HS.health_results(spec, pools))
-    out.update(XS.wrapper_results(pools))
-    out.update(client_results(pools))
-    out["fault_events"] = int(getattr(sim, "_fault_events_processed", 0))
-    out["internal_by_kind"] = np.asarray(sim._internal_by_kind, np.int64)            # limiter Requests, limiter polls, fault set, fault clear
-    out["health_by_kind"] = np.asarray(getattr(sim, "_health_by_kind", np.zeros(3)), np.int64)
-    out["resilience_by_kind"] = np.asarray(getattr(sim, "_resilience_by_kind", np.zeros(6)), np.int64)
-    out["client_by_kind"] = np.asarray(sim._client_by_kind, np.int64)                # Client request / response / timeout
-    out["events_cancelled"] = int(sim.summary.events_cancelled)
-    return out

@@ -9,15 +9,14 @@
   names = [[[pool, index], name]]: entities renamed after wiring (a duplicate name resolves to the last such object,
       faults/schedule.py:121-124).
 
-tests/golden/make_golden_faults.py runs the LIVE reference on every spec listed here (tests/fault_reference.py reads the recordings
-back); `build()` wires the product's objects the same way (rate_limiter_specs.wire is shared by both).
+tests/golden/make_golden_faults.py runs the LIVE reference on every spec listed here (tests/recorded.py FAULTS reads the recordings
+back); tests/graph_family.py `build()` wires the product's objects the same way (its `wire()` is shared by both).
 
   FIXTURES        named cases; TRACED: recorded with their full event trace
   random_spec(k)  N_RANDOM seeded graphs of rate_limiter_specs.random_spec with 1 .. 4 node faults over every entity kind
 """
 import numpy as np
 
-import happy_simulator_amd as hs
 import rate_limiter_specs as RS
 
 N_RANDOM = 120
@@ -162,82 +161,7 @@ def all_specs():
     return list(FIXTURES.values()) + [random_spec(k) for k in range(N_RANDOM)]
 
 
-# ---- wiring ------------------------------------------------------------------------------------------------------------------------
-def apply_names(spec, pools):
-    for (pool, idx), name in spec.get("names") or []:
-        pools[pool][idx].name = name
-
-
-def target_name(spec, pools, on):
-    if isinstance(on, str):
-        return on
-    x = pools[on[0]][on[1]]
-    return (x[0] if isinstance(x, tuple) else x).name           # (the product's Probe.on returns (probe, data))
-
-
-def make_schedule(ns, spec, pools):
-    """(FaultSchedule, handles) of the spec from the namespace `ns` (the product or the reference's faults package); handles marked
-    cancel="before" are cancelled here."""
-    fs = ns.FaultSchedule()
-    handles = []
-    for ft in spec.get("faults") or []:
-        name = target_name(spec, pools, ft["on"])
-        fault = ns.CrashNode(name, at=ft["at"], restart_at=ft.get("restart")) if ft["kind"] == "crash" else ns.PauseNode(name, start=ft["at"], end=ft["end"])
-        h = fs.add(fault)
-        if ft.get("cancel") == "before":
-            h.cancel()
-        handles.append(h)
-    return fs, handles
-
-
-def cancel_after(spec, handles):
-    for ft, h in zip(spec.get("faults") or [], handles):
-        if ft.get("cancel") == "after":
-            h.cancel()
-
-
-def fault_targets(pools):
-    """Every object a fault can name, in one order for both libraries: Sources, Probes, then the entities."""
-    probes = [p[0] if isinstance(p, tuple) else p for p in pools["probe"]]
-    return (list(pools["source"]) + probes + list(pools["server"]) + list(pools["lb"]) + list(pools["router"]) + list(pools["link"]) +
-            list(pools["limiter"]) + list(pools["sink"]))
-
-
-def build(spec, seed=None):
-    """(Simulation, entities by pool) of the product, wired like the recorded reference run."""
-    pools, sources, probes, entities = RS.wire(spec, RS._Product)
-    pools["probe"] = probes
-    apply_names(spec, pools)
-    start_ns = int(spec.get("start_ns", 0))
-
-    def at(t_s):
-        return hs.Instant(start_ns + hs.Instant.from_seconds(t_s).nanoseconds)
-
-    fs, handles = make_schedule(hs, spec, pools)
-    sim = hs.Simulation(sources=sources, entities=entities, seed=spec["seed"] if seed is None else seed, max_graph_events=400_000,
-                        fault_schedule=fs,
-                        **({} if spec.get("auto") else {"end_time": at(spec["end_s"])}),
-                        **({"start_time": hs.Instant(start_ns)} if start_ns else {}),
-                        **({"probes": [p for p, _ in probes]} if probes else {}))
-    cancel_after(spec, handles)
-    for (kind, idx), t_s in spec.get("schedule") or []:
-        sim.schedule(hs.Event(time=at(t_s), event_type="Request", target=pools[kind][idx]))
-    pools["probes"] = probes
-    pools["fault_schedule"], pools["handles"] = fs, handles
-    return sim, pools
-
-
 def fault_results(fs, targets):
     st = fs.stats
     return dict(crashed=np.array([bool(getattr(x, "_crashed", False)) for x in targets], np.int64),
                 fault_stats=np.array([st.faults_scheduled, st.faults_activated, st.faults_deactivated, st.faults_cancelled], np.int64))
-
-
-def results(spec, sim, pools):
-    """Everything make_golden_faults.run_case records except the trace, read off the product's objects after run()."""
-    out = RS.results(spec, sim, pools)
-    out.update(fault_results(pools["fault_schedule"], fault_targets(pools)))
-    out["fault_events"] = int(getattr(sim, "_fault_events_processed", 0))
-    out["internal_by_kind"] = np.asarray(sim._internal_by_kind, np.int64)      # limiter Requests, limiter polls, fault set, fault clear
-    out["events_cancelled"] = int(sim.summary.events_cancelled)
-    return out

@@ -5,52 +5,30 @@ HS_REFERENCE_ROOT):
 
     python tests/golden/make_golden_client.py          # writes tests/golden/live_client/part_*.npz
 
-Recorded (tests/client_reference.py reads them back):
+Recorded (tests/recorded.py CLIENT reads them back; record_family.run_case is the run):
   * constructor defaults, properties, stats objects and the ValueError texts of Client and the four policies, and
     get_delay(1 .. max_attempts) of FixedRetry and ExponentialBackoff over a parameter grid that includes the max_delay cap;
   * every spec of client_specs.all_specs(): the reference's own event loop over its own components, with the Philox stream plugs of
-    make_golden.py choosing the random numbers -- everything make_golden_resilience.run_case records (this run_case is that one with the
-    Clients wired in), plus per Client its statistics, its keys in flight and its response times, and the Clients' Events processed
+    make_golden.py choosing the random numbers -- everything the resilience family records, plus per Client its statistics, its keys in flight and its response times, and the Clients' Events processed
     (kinds 28 / 29 / 30 = a request at a Client, its `_client_response`, its `_client_timeout`, in by_kind and in the trace); the
     fixtures of client_specs.TRACED with their full trace.
 The recorder asserts that every spec is one the product accepts (its host-side lowering, no device needed): no case is left out.
 """
 from __future__ import annotations
 
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))        # (the product: the recorder asserts that it takes every spec)
-
+import record_family as RF  # (puts tests/ and the repository root on sys.path; installs the reference's import path)
 import client_specs as CS  # noqa: E402
-import fault_specs as FS  # noqa: E402
-import health_specs as HS  # noqa: E402
-import rate_limiter_specs as RS  # noqa: E402
-import resilience_specs as XS  # noqa: E402
-import make_golden as MG  # noqa: E402  (installs the reference's import path; the stream plugs and the trace classifier)
-import make_golden_rate_limiter as MGR  # noqa: E402
-import make_golden_faults as MGF  # noqa: E402
-import make_golden_health as MGH  # noqa: E402
-import make_golden_resilience as MGX  # noqa: E402
-import happysimulator.faults as ref_faults  # noqa: E402
+import graph_family as GF  # noqa: E402
 import happysimulator.components.client as ref_client  # noqa: E402
-from happysimulator import Server, Simulation, Sink  # noqa: E402
+from happysimulator import Sink  # noqa: E402
 from happysimulator.components.client import Client, DecorrelatedJitter, ExponentialBackoff, FixedRetry, NoRetry  # noqa: E402
 from happysimulator.components.client.client import ClientStats  # noqa: E402
-from happysimulator.components.load_balancer import HealthChecker  # noqa: E402
-from happysimulator.components.rate_limiter.rate_limited_entity import RateLimitedEntity  # noqa: E402
-from happysimulator.components.resilience import Bulkhead, TimeoutWrapper  # noqa: E402
-from happysimulator.core.event import Event  # noqa: E402
 from happysimulator.core.temporal import Duration  # noqa: E402
+from recorded import CLIENT as CR  # noqa: E402
 
-EV_CL_REQ = MGX.EV_TW_TIMEOUT + 1
-EV_CL_RESP, EV_CL_TIMEOUT = EV_CL_REQ + 1, EV_CL_REQ + 2
-assert EV_CL_REQ == 28
+EV_CL_REQ, EV_CL_RESP = RF.EV["cl_req"], RF.EV["cl_resp"]
 FIXED_GRID = [(1, 0.0), (3, 0.25), (5, 0), (2, 1), (4, 1e-9)]
 EXP_GRID = [(6, 0.1, 1.0, 2.0), (1, 0.1, 0.1, 2.0), (5, 0.05, 0.05, 3.0), (8, 0.001, 10.0, 10.0), (4, 0.3, 0.5, 1.0), (6, 0.1, 0.25, 2.0), (12, 1, 60, 1.5)]
 CLIENT_ERRORS = (dict(timeout=-1), dict(timeout=-0.5), dict(timeout=0), dict(timeout=None), dict(timeout=0.0))
@@ -110,148 +88,14 @@ def defaults():
     return out
 
 
-def run_case(spec, want_trace=False):
-    """The reference's run of one spec.  Trace nodes: Sources, Probes, then the entities (servers + lbs + routers + links + limiters
-    + sinks + wrappers + clients + checkers); trace kinds: make_golden_resilience's (0 .. 27), then 28 .. 30 = the Clients' three."""
-    import happysimulator.components.network.link as link_mod
-
-    link_mod.random = MG._PerLinkRandom
-    F = MGX._Reference(spec)                                  # (its probe() takes `in_flight_count` by name, of a Client too)
-    pools, sources, probes, entities = CS.wire(spec, F, ref_client, Bulkhead, TimeoutWrapper, HealthChecker)
-    FS.apply_names(spec, pools)
-    servers, sinks, links, routers, lbs, lims = (pools[k] for k in ("server", "sink", "link", "router", "lb", "limiter"))
-    fs, handles = FS.make_schedule(ref_faults, spec, pools)
-    sim = Simulation(start_time=MG._start(spec), sources=sources, entities=entities, fault_schedule=fs,
-                     **({} if spec.get("auto") else {"end_time": MG._at(spec, spec["end_s"])}), **({"probes": probes} if probes else {}))
-    FS.cancel_after(spec, handles)
-    node_of = {}
-    for i, x in enumerate(sources + probes):
-        node_of[id(x)] = i
-    first = len(sources) + len(probes)
-    lim_index = {}
-    for i, x in enumerate(entities):
-        node_of[id(x)] = first + i
-        if isinstance(x, Server):
-            for part in (x._queue, x._driver, x._worker):
-                node_of[id(part)] = first + i
-        if isinstance(x, RateLimitedEntity):
-            lim_index[id(x)] = len(lim_index)
-    by_name = {x.name: node_of[id(x)] for x in entities + sources + probes}
-    cb_probe = {id(p._event_provider.data_sink): len(sources) + j for j, p in enumerate(probes)}
-    by_kind = np.zeros(EV_CL_TIMEOUT + 1, np.int64)
-    lim_events = np.zeros((len(lims), 2), np.int64)
-    trace = []
-    heap = sim._event_heap
-    orig_pop = heap.pop
-    state = dict(cur=sim._start_time, cancelled=0, skipped=0)
-
-    def pop():
-        e = orig_pop()
-        if by_kind.sum() >= MGR.MAX_EVENTS:
-            raise MGR.Livelock(spec["name"])
-        if e.cancelled:
-            state["cancelled"] += 1
-            return e
-        if e.time < state["cur"]:
-            state["skipped"] += 1
-            return e
-        state["cur"] = e.time
-        et = e.event_type
-        if et.startswith(MGF._ON) or et.startswith(MGF._OFF):
-            k, nd = (MGF.EV_FAULT_ON if et.startswith(MGF._ON) else MGF.EV_FAULT_OFF), by_name[et.split(":", 1)[1]]
-        elif isinstance(e.target, Client):
-            k, nd = {"_client_response": EV_CL_RESP, "_client_timeout": EV_CL_TIMEOUT}.get(et, EV_CL_REQ), node_of[id(e.target)]
-        elif isinstance(e.target, Bulkhead):
-            k, nd = {"_bh_response": MGX.EV_BH_RESP, "_bh_timeout": MGX.EV_BH_TIMEOUT}.get(et, MGX.EV_BH_REQ), node_of[id(e.target)]
-        elif isinstance(e.target, TimeoutWrapper):
-            k, nd = {"_tw_response": MGX.EV_TW_RESP, "_tw_timeout": MGX.EV_TW_TIMEOUT}.get(et, MGX.EV_TW_REQ), node_of[id(e.target)]
-        elif isinstance(e.target, HealthChecker):
-            k, nd = MGH._HC_KIND[et], node_of[id(e.target)]
-        elif isinstance(e.target, RateLimitedEntity):
-            poll = et == f"rate_limit_poll::{e.target.name}"
-            k, nd = (MGR.EV_LIM_POLL if poll else MGR.EV_LIM_REQUEST), node_of[id(e.target)]
-            if not getattr(e.target, "_crashed", False):
-                lim_events[lim_index[id(e.target)], int(poll)] += 1
-        else:
-            k, nd = MG.classify(e, node_of)
-        if k == MG.EV["probe"]:
-            fn = e.target._fn if hasattr(e.target, "_fn") else e.target.fn
-            cells = {id(cell.cell_contents) for cell in (fn.__closure__ or ())}
-            nd = next(c for key, c in cb_probe.items() if key in cells)
-        by_kind[k] += 1
-        if want_trace:
-            trace.append((e.time.nanoseconds, k, nd, e._sort_index))
-        return e
-
-    heap.pop = pop
-    CS.schedule_all(spec, pools, sim, Event, lambda t_s: MG._at(spec, t_s))
-    HS.start_checkers(spec, pools, sim, [[] for _ in pools["checker"]])
-    summary = MG.run_sim_windows(sim, spec)
-    out = dict(total_events=int(summary.total_events_processed), final_ns=int(sim._current_time.nanoseconds), by_kind=by_kind)
-    assert int(by_kind.sum()) == out["total_events"], (spec["name"], int(by_kind.sum()), out["total_events"])
-    assert state["cancelled"] == int(sim._events_cancelled)
-    out["pending_events"] = int(heap.size())
-    out["time_travel"] = int(state["skipped"])
-    out["generated"] = np.array([s.generated_count for s in sources], np.int64)
-    out["accepted"] = np.array([s.stats_accepted for s in servers], np.int64)
-    out["dropped"] = np.array([s.stats_dropped for s in servers], np.int64)
-    out["completed"] = np.array([s._requests_completed for s in servers], np.int64)
-    out["rejected"] = np.array([s._requests_rejected for s in servers], np.int64)
-    out["depth"] = np.array([s.depth for s in servers], np.int64)
-    out["active"] = np.array([s.active_requests for s in servers], np.int64)
-    out["total_service_s"] = np.array([s._total_service_time for s in servers], np.float64)
-    out["received"] = np.array([k.events_received for k in sinks], np.int64)
-    out["routed"] = np.array([r.stats_routed for r in routers], np.int64)
-    out["packets_sent"] = np.array([l.packets_sent for l in links], np.int64)
-    out["packets_dropped"] = np.array([l.packets_dropped for l in links], np.int64)
-    out["lb_stats"] = np.array([[lb.stats.requests_received, lb.stats.requests_forwarded, lb.stats.requests_failed,
-                                 lb.stats.no_backend_available, len(lb._in_flight)] for lb in lbs], np.int64).reshape(-1, 5)
-    tot, toff, index = [], [0], []
-    for j, lb in enumerate(lbs):
-        tot.extend(lb.get_backend_info(servers[b]).total_requests for b in spec["lbs"][j]["backends"])
-        toff.append(len(tot))
-        st = lb.strategy
-        index.append(st._fallback._index if hasattr(st, "_fallback") else getattr(st, "_index", -1))
-    out["lb_backend_total_requests"] = np.asarray(tot, np.int64)
-    out["lb_backend_off"] = np.asarray(toff, np.int64)
-    out["lb_rr_index"] = np.asarray(index, np.int64)
-    sink_t, sink_lat, off = [], [], [0]
-    for k in sinks:
-        sink_t.extend(t.nanoseconds for t in k.completion_times)
-        sink_lat.extend(k.latencies_s)
-        off.append(len(sink_t))
-    out["sink_t_ns"] = np.asarray(sink_t, np.int64)
-    out["sink_latency_s"] = np.asarray(sink_lat, np.float64)
-    out["sink_off"] = np.asarray(off, np.int64)
-    pt, pv, poff = [], [], [0]
-    for d in F.probe_data:
-        pt.extend(t for t, _ in d._ns)
-        pv.extend(int(v) for _, v in d._ns)
-        poff.append(len(pt))
-    out["probe_t_ns"], out["probe_v"], out["probe_off"] = np.asarray(pt, np.int64), np.asarray(pv, np.int64), np.asarray(poff, np.int64)
-    out.update(RS.limiter_results(lims))
-    out["lim_events"] = lim_events
-    out.update(FS.fault_results(fs, CS.fault_targets(pools)))
-    out.update(HS.health_results(spec, pools))
-    out.update(XS.wrapper_results(pools))
-    out.update(CS.client_results(pools))
-    out["fault_events"] = int(by_kind[MGF.EV_FAULT_ON] + by_kind[MGF.EV_FAULT_OFF])
-    out["events_cancelled"] = int(summary.events_cancelled)
-    if want_trace:
-        out["trace"] = np.asarray(trace, np.int64).reshape(-1, 4)
-    return out
-
-
 def main():
-    import client_reference as CR
-
     cases = {CR.key("defaults"): defaults()}
     for spec in CS.all_specs():
-        sim, _pools = CS.build(spec)
+        sim, _pools = GF.build(spec)
         sim.lowered()                                      # the product takes this graph (host-side lowering; raises otherwise)
         assert sim._graph.arrays.has_clients, spec["name"]
         sim._general_prepare(sim._graph, bool(spec.get("auto")))     # ... and every scheduled Event of it
-        res = cases[CR.key("case", spec)] = run_case(spec, want_trace=spec["name"] in CS.TRACED)
+        res = cases[CR.key("case", spec)] = RF.run_case(spec, "client", want_trace=spec["name"] in CS.TRACED)
         assert res["total_events"] <= 40_000, (spec["name"], res["total_events"])
         print(spec["name"], res["total_events"], res["by_kind"][EV_CL_REQ:].tolist(), res["cl_stats"].tolist(), res["crashed"].sum(), flush=True)
     # what the issue states about the reference, pinned on the recordings

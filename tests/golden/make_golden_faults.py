@@ -5,10 +5,10 @@ HS_REFERENCE_ROOT):
 
     python tests/golden/make_golden_faults.py          # writes tests/golden/live_faults/part_*.npz
 
-Recorded (tests/fault_reference.py reads them back):
+Recorded (tests/recorded.py FAULTS reads them back; record_family.run_case is the run):
   * constructor defaults, properties, the stats quirks and the KeyError texts of the classes;
   * every spec of fault_specs.all_specs(): the reference's own event loop over its own components, with the Philox stream plugs of
-    make_golden.py choosing the random numbers -- everything make_golden_rate_limiter.run_case records, plus the final `_crashed`
+    make_golden.py choosing the random numbers -- everything the rate_limiter family records, plus the final `_crashed`
     flag of every Source, Probe and entity, FaultSchedule.stats, events_cancelled and the fault Events processed (kinds 17 = a
     crash / pause, 18 = a restart / resume in by_kind and in the trace); the fixtures of fault_specs.TRACED with their full trace.
     by_kind counts every processed Event, one dropped at a crashed target included; lim_events counts per limiter the Events its
@@ -17,28 +17,13 @@ The recorder asserts that every spec is one the product accepts (its host-side l
 """
 from __future__ import annotations
 
-import os
-import sys
-
-import numpy as np
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))        # (the product: the recorder asserts that it takes every spec)
-
+import record_family as RF  # (puts tests/ and the repository root on sys.path; installs the reference's import path)
 import fault_specs as FS  # noqa: E402
+import graph_family as GF  # noqa: E402
 import rate_limiter_specs as RS  # noqa: E402
-import make_golden as MG  # noqa: E402  (installs the reference's import path; the stream plugs and the trace classifier)
-import make_golden_rate_limiter as MGR  # noqa: E402
 import happysimulator.faults as ref_faults  # noqa: E402
 from happysimulator import Instant, Server, Simulation, Sink, Source  # noqa: E402
-from happysimulator.components.rate_limiter.rate_limited_entity import RateLimitedEntity  # noqa: E402
-from happysimulator.core.event import Event  # noqa: E402
-
-EV_FAULT_ON, EV_FAULT_OFF = MGR.EV_LIM_POLL + 1, MGR.EV_LIM_POLL + 2
-_ON = ("fault.crash:", "fault.pause:")
-_OFF = ("fault.restart:", "fault.resume:")
+from recorded import FAULTS as FR  # noqa: E402
 
 
 def defaults():
@@ -96,139 +81,14 @@ def defaults():
     return out
 
 
-def run_case(spec, want_trace=False):
-    """The reference's run of one spec.  Trace nodes: Sources, Probes, then the entities (servers + lbs + routers + links + limiters
-    + sinks); trace kinds: make_golden.EV, 15 / 16 = a limiter's two handlers, 17 / 18 = a fault Event that sets / clears the flag
-    (node: the entity it names)."""
-    import happysimulator.components.network.link as link_mod
-
-    link_mod.random = MG._PerLinkRandom
-    F = MGR._Reference(spec)
-    pools, sources, probes, entities = RS.wire(spec, F)
-    pools["probe"] = probes
-    FS.apply_names(spec, pools)
-    servers, sinks, links, routers, lbs, lims = (pools[k] for k in ("server", "sink", "link", "router", "lb", "limiter"))
-    fs, handles = FS.make_schedule(ref_faults, spec, pools)
-    sim = Simulation(start_time=MG._start(spec), sources=sources, entities=entities, fault_schedule=fs,
-                     **({} if spec.get("auto") else {"end_time": MG._at(spec, spec["end_s"])}), **({"probes": probes} if probes else {}))
-    FS.cancel_after(spec, handles)
-    node_of = {}
-    for i, x in enumerate(sources + probes):
-        node_of[id(x)] = i
-    first = len(sources) + len(probes)
-    lim_index = {}
-    for i, x in enumerate(entities):
-        node_of[id(x)] = first + i
-        if isinstance(x, Server):
-            for part in (x._queue, x._driver, x._worker):
-                node_of[id(part)] = first + i
-        if isinstance(x, RateLimitedEntity):
-            lim_index[id(x)] = len(lim_index)
-    by_name = {x.name: node_of[id(x)] for x in entities + sources + probes}        # (the schedule's own dict order: the last wins)
-    cb_probe = {id(p._event_provider.data_sink): len(sources) + j for j, p in enumerate(probes)}
-    by_kind = np.zeros(EV_FAULT_OFF + 1, np.int64)
-    lim_events = np.zeros((len(lims), 2), np.int64)
-    trace = []
-    heap = sim._event_heap
-    orig_pop = heap.pop
-    state = dict(cur=sim._start_time, cancelled=0, skipped=0)
-
-    def pop():
-        e = orig_pop()
-        if by_kind.sum() >= MGR.MAX_EVENTS:
-            raise MGR.Livelock(spec["name"])
-        if e.cancelled:                                   # skipped, counted in events_cancelled (core/simulation.py:475-477)
-            state["cancelled"] += 1
-            return e
-        if e.time < state["cur"]:                         # time travel: skipped, not counted (:480-489)
-            state["skipped"] += 1
-            return e
-        state["cur"] = e.time
-        et = e.event_type
-        if et.startswith(_ON) or et.startswith(_OFF):
-            k, nd = (EV_FAULT_ON if et.startswith(_ON) else EV_FAULT_OFF), by_name[et.split(":", 1)[1]]
-        elif isinstance(e.target, RateLimitedEntity):
-            poll = et == f"rate_limit_poll::{e.target.name}"
-            k, nd = (MGR.EV_LIM_POLL if poll else MGR.EV_LIM_REQUEST), node_of[id(e.target)]
-            if not getattr(e.target, "_crashed", False):       # (popped and counted, but its handler never ran: core/event.py:261)
-                lim_events[lim_index[id(e.target)], int(poll)] += 1
-        else:
-            k, nd = MG.classify(e, node_of)
-        if k == MG.EV["probe"]:
-            fn = e.target._fn if hasattr(e.target, "_fn") else e.target.fn
-            cells = {id(cell.cell_contents) for cell in (fn.__closure__ or ())}
-            nd = next(c for key, c in cb_probe.items() if key in cells)
-        by_kind[k] += 1
-        if want_trace:
-            trace.append((e.time.nanoseconds, k, nd, e._sort_index))
-        return e
-
-    heap.pop = pop
-    for (kind, idx), t_s in spec.get("schedule") or []:
-        sim.schedule(Event(time=MG._at(spec, t_s), event_type="Request", target=pools[kind][idx]))
-    summary = MG.run_sim_windows(sim, spec)
-    out = dict(total_events=int(summary.total_events_processed), final_ns=int(sim._current_time.nanoseconds), by_kind=by_kind)
-    assert int(by_kind.sum()) == out["total_events"], (spec["name"], int(by_kind.sum()), out["total_events"])
-    assert state["cancelled"] == int(sim._events_cancelled)
-    out["pending_events"] = int(heap.size())
-    out["time_travel"] = int(state["skipped"])
-    out["generated"] = np.array([s.generated_count for s in sources], np.int64)
-    out["accepted"] = np.array([s.stats_accepted for s in servers], np.int64)
-    out["dropped"] = np.array([s.stats_dropped for s in servers], np.int64)
-    out["completed"] = np.array([s._requests_completed for s in servers], np.int64)
-    out["rejected"] = np.array([s._requests_rejected for s in servers], np.int64)
-    out["depth"] = np.array([s.depth for s in servers], np.int64)
-    out["active"] = np.array([s.active_requests for s in servers], np.int64)
-    out["total_service_s"] = np.array([s._total_service_time for s in servers], np.float64)
-    out["received"] = np.array([k.events_received for k in sinks], np.int64)
-    out["routed"] = np.array([r.stats_routed for r in routers], np.int64)
-    out["packets_sent"] = np.array([l.packets_sent for l in links], np.int64)
-    out["packets_dropped"] = np.array([l.packets_dropped for l in links], np.int64)
-    out["lb_stats"] = np.array([[lb.stats.requests_received, lb.stats.requests_forwarded, lb.stats.requests_failed,
-                                 lb.stats.no_backend_available, len(lb._in_flight)] for lb in lbs], np.int64).reshape(-1, 5)
-    tot, toff, index = [], [0], []
-    for j, lb in enumerate(lbs):
-        tot.extend(lb.get_backend_info(servers[b]).total_requests for b in spec["lbs"][j]["backends"])
-        toff.append(len(tot))
-        st = lb.strategy
-        index.append(st._fallback._index if hasattr(st, "_fallback") else getattr(st, "_index", -1))
-    out["lb_backend_total_requests"] = np.asarray(tot, np.int64)
-    out["lb_backend_off"] = np.asarray(toff, np.int64)
-    out["lb_rr_index"] = np.asarray(index, np.int64)
-    sink_t, sink_lat, off = [], [], [0]
-    for k in sinks:
-        sink_t.extend(t.nanoseconds for t in k.completion_times)
-        sink_lat.extend(k.latencies_s)
-        off.append(len(sink_t))
-    out["sink_t_ns"] = np.asarray(sink_t, np.int64)
-    out["sink_latency_s"] = np.asarray(sink_lat, np.float64)
-    out["sink_off"] = np.asarray(off, np.int64)
-    pt, pv, poff = [], [], [0]
-    for d in F.probe_data:
-        pt.extend(t for t, _ in d._ns)
-        pv.extend(int(v) for _, v in d._ns)
-        poff.append(len(pt))
-    out["probe_t_ns"], out["probe_v"], out["probe_off"] = np.asarray(pt, np.int64), np.asarray(pv, np.int64), np.asarray(poff, np.int64)
-    out.update(RS.limiter_results(lims))
-    out["lim_events"] = lim_events
-    out.update(FS.fault_results(fs, FS.fault_targets(pools)))
-    out["fault_events"] = int(by_kind[EV_FAULT_ON] + by_kind[EV_FAULT_OFF])
-    out["events_cancelled"] = int(summary.events_cancelled)
-    if want_trace:
-        out["trace"] = np.asarray(trace, np.int64).reshape(-1, 4)
-    return out
-
-
 def main():
-    import fault_reference as FR
-
     cases = {FR.key("defaults"): defaults()}
     kinds_hit, grid_hit = set(), 0
     for spec in FS.all_specs():
-        sim, _pools = FS.build(spec)
+        sim, _pools = GF.build(spec)
         sim.lowered()                                      # the product takes this graph (host-side lowering; raises otherwise)
         assert sim._faults, spec["name"]
-        res = cases[FR.key("case", spec)] = run_case(spec, want_trace=spec["name"] in FS.TRACED)
+        res = cases[FR.key("case", spec)] = RF.run_case(spec, "faults", want_trace=spec["name"] in FS.TRACED)
         for ft in spec["faults"]:
             if not isinstance(ft["on"], str):
                 kinds_hit.add(ft["on"][0])

@@ -5,7 +5,7 @@ tests/test_gpu_lb_strategies.py.  Run by hand where the reference is installed (
 
     python tests/golden/make_golden_strategies.py            # writes tests/golden/live_strategies/part_*.npz
 
-Recorded (tests/strategy_reference.py reads them back):
+Recorded (tests/recorded.py STRATEGIES reads them back):
   * constructor defaults and `set_weight` errors of the four classes;
   * selection sequences of the live WeightedRoundRobin (strategy_specs.WEIGHT_VECTORS, 2 W + 3 selections each);
   * the live IPHash.select for clients 0 .. n - 1 (strategy_specs.IP_HASH_TABLES);
@@ -16,30 +16,21 @@ Recorded (tests/strategy_reference.py reads them back):
 """
 from __future__ import annotations
 
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.dirname(HERE))
-
+import record_family as RF  # (puts tests/ and the repository root on sys.path; installs the reference's import path)
 import strategy_specs as SS  # noqa: E402
-import make_golden as MG  # noqa: E402  (installs the reference's import path; the stream plugs and the trace classifier)
+import make_golden as MG  # noqa: E402  (the stream plugs and the trace classifier)
 import hs_streams_py as hs  # noqa: E402
 from happysimulator import ConstantLatency, Instant, Server, Simulation, Sink, Source  # noqa: E402
 from happysimulator.components.load_balancer import strategies as ref_strategies  # noqa: E402
 from happysimulator.components.load_balancer.load_balancer import LoadBalancer  # noqa: E402
 from happysimulator.components.network.link import NetworkLink  # noqa: E402
 from happysimulator.core.event import Event  # noqa: E402
-from happysimulator.instrumentation.probe import Probe  # noqa: E402
 from happysimulator.load.profile import ConstantRateProfile  # noqa: E402
 from happysimulator.load.providers.constant_arrival import ConstantArrivalTimeProvider  # noqa: E402
 from happysimulator.load.source import SimpleEventProvider  # noqa: E402
-
-REF_CLASS = {"wrr": "WeightedRoundRobin", "ip_hash": "IPHash", "least_conn": "LeastConnections", "wlc": "WeightedLeastConnections",
-             "round_robin": "RoundRobin", "chash": "ConsistentHash", "random": "Random"}
+from recorded import STRATEGIES as SR  # noqa: E402
 
 
 class _Named:
@@ -51,7 +42,7 @@ def strategy_defaults():
     """Constructor state and error messages of the four classes."""
     out = {}
     for kind in ("wrr", "wlc"):
-        st = getattr(ref_strategies, REF_CLASS[kind])()
+        st = getattr(ref_strategies, RF.REF_STRATEGY[kind])()
         a, b = _Named("a"), _Named("b")
         st.set_weight(a, 4)
         errors = []
@@ -107,16 +98,6 @@ def ip_hash_table(n_clients, n_backends):
     return dict(table=tab, keyless=keyless, fallback_index=st._fallback._index)
 
 
-def _strategy(lb):
-    kind = lb["strategy"]
-    if kind == "chash":
-        return ref_strategies.ConsistentHash(virtual_nodes=lb["vnodes"])
-    if kind == "random":
-        ref_strategies.random = MG._PerRequestChoice
-        return ref_strategies.Random()
-    return getattr(ref_strategies, REF_CLASS[kind])()
-
-
 def run_strategy_case(spec, want_trace=False):
     """make_golden.run_graph_case's wiring (`entities=servers + lbs + routers + links + sinks`; streams: Source k ARRIVAL / KEY base k,
     Server s SERVICE base s (+ spec["server_stream_offset"]), link l LINK / LOSS base l, router r ROUTE base r) with the strategies of strategy_specs, constant
@@ -145,7 +126,7 @@ def run_strategy_case(spec, want_trace=False):
     lbs = []
     for j, lb in enumerate(spec.get("lbs") or []):
         backends = [servers[b] for b in lb["backends"]]
-        lbs.append(SS.make_lb(LoadBalancer, j, lb, backends, _strategy(lb)))
+        lbs.append(SS.make_lb(LoadBalancer, j, lb, backends, RF.ref_strategy(lb)))
     pools = {"sink": sinks, "link": links, "router": routers, "server": servers, "lb": lbs}
     pending = list(range(len(routers)))
     while pending:
@@ -173,14 +154,7 @@ def run_strategy_case(spec, want_trace=False):
     pools["source"] = sources
     probes, probe_data = [], []
     for (kind, idx), metric, interval in spec.get("probes") or []:
-        probe, data = Probe.on(pools[kind][idx], MG.PROBE_METRICS[metric][1], interval=interval)
-        data._ns = []
-
-        def add_stat(value, time, _orig=data.add_stat, _d=data):
-            _d._ns.append((time.nanoseconds, value))
-            _orig(value, time)
-
-        data.add_stat = add_stat
+        probe, data = RF.recording_probe(pools[kind][idx], MG.PROBE_METRICS[metric][1], interval)
         probes.append(probe)
         probe_data.append(data)
     entities = servers + lbs + routers + links + sinks
@@ -265,8 +239,6 @@ def run_strategy_case(spec, want_trace=False):
 
 
 def main():
-    import strategy_reference as SR
-
     cases = {SR.key("defaults"): strategy_defaults()}
     for name, w in SS.WEIGHT_VECTORS.items():
         cases[SR.key("wrr_sequence", w)] = wrr_sequence(w)

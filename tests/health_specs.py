@@ -6,8 +6,8 @@
   unhealthy = [[<LoadBalancer index>, <position among its backends>]]: LoadBalancer.mark_unhealthy before the run
   faults may name ["checker", i].
 
-tests/golden/make_golden_health.py runs the LIVE reference on every spec listed here (tests/health_reference.py reads the
-recordings back); `build()` wires the product's objects the same way.  Entities: servers + lbs + routers + links + limiters +
+tests/golden/make_golden_health.py runs the LIVE reference on every spec listed here (tests/recorded.py HEALTH reads the
+recordings back); tests/graph_family.py `build()` wires the product's objects the same way.  Entities: servers + lbs + routers + links + limiters +
 sinks + checkers.
 
   FIXTURES        named cases; TRACED: recorded with their full event trace
@@ -17,8 +17,6 @@ sinks + checkers.
 import numpy as np
 
 import fault_specs as FS
-import happy_simulator_amd as hs
-import rate_limiter_specs as RS
 
 N_RANDOM = 120
 STRATEGIES = ("round_robin", "wrr", "least_conn", "wlc")
@@ -180,58 +178,6 @@ def groups_spec(n_groups, name="groups", end_s=4.0):
                 sources=sources, faults=faults, checkers=checkers, unhealthy=[])
 
 
-# ---- wiring ------------------------------------------------------------------------------------------------------------------------
-def wire(spec, F, checker_cls):
-    """rate_limiter_specs.wire plus the checkers (`checker_cls`: the product's or the reference's HealthChecker) and the marks."""
-    pools, sources, probes, entities = RS.wire(spec, F)
-    pools["probe"] = probes
-    pools["checker"] = [checker_cls(f"hc{i}", pools["lb"][ck["lb"]], interval=ck["interval"], timeout=ck["timeout"], healthy_threshold=ck["ht"],
-                                    unhealthy_threshold=ck["ut"]) for i, ck in enumerate(spec.get("checkers") or [])]
-    for j, q in spec.get("unhealthy") or []:
-        pools["lb"][j].mark_unhealthy(pools["server"][spec["lbs"][j]["backends"][q]])
-    return pools, sources, probes, entities + pools["checker"]
-
-
-def start_checkers(spec, pools, sim, early_events):
-    """sim.schedule(checker.start()) as the spec says; `early_events`: the Events of the checkers with early=True, made by
-    early_starts() before the Simulation existed."""
-    for ck, hc, early in zip(spec.get("checkers") or [], pools["checker"], early_events):
-        for ev in early:
-            sim.schedule(ev)
-        for _ in range(0 if ck.get("early") else ck.get("starts", 1)):
-            sim.schedule(hc.start())
-        if ck.get("stop"):
-            hc.stop()
-
-
-def early_starts(spec, pools):
-    return [[hc.start() for _ in range(ck.get("starts", 1))] if ck.get("early") else []
-            for ck, hc in zip(spec.get("checkers") or [], pools["checker"])]
-
-
-def fault_targets(pools):
-    return FS.fault_targets(pools) + list(pools["checker"])
-
-
-def build(spec, seed=None):
-    """(Simulation, entities by pool) of the product, wired like the recorded reference run."""
-    pools, sources, probes, entities = wire(spec, RS._Product, hs.HealthChecker)
-    start_ns = int(spec.get("start_ns", 0))
-
-    def at(t_s):
-        return hs.Instant(start_ns + hs.Instant.from_seconds(t_s).nanoseconds)
-
-    fs, handles = FS.make_schedule(hs, spec, pools)
-    early = early_starts(spec, pools)
-    sim = hs.Simulation(sources=sources, entities=entities, seed=spec["seed"] if seed is None else seed, max_graph_events=400_000,
-                        fault_schedule=fs, end_time=at(spec["end_s"]), **({"start_time": hs.Instant(start_ns)} if start_ns else {}),
-                        **({"probes": [p for p, _ in probes]} if probes else {}))
-    start_checkers(spec, pools, sim, early)
-    pools["probes"] = probes
-    pools["fault_schedule"], pools["handles"] = fs, handles
-    return sim, pools
-
-
 def health_results(spec, pools):
     """What both libraries' LoadBalancers and checkers show after a run."""
     out = {}
@@ -264,16 +210,4 @@ def health_results(spec, pools):
     out["checker_stats"] = np.asarray(stats, np.int64).reshape(-1, 8)
     out["checker_states"] = np.asarray(states, np.int64).reshape(-1, 5)
     out["checker_pending"] = np.asarray(pend, np.int64)
-    return out
-
-
-def results(spec, sim, pools):
-    """Everything make_golden_health.run_case records except the trace, read off the product's objects after run()."""
-    out = RS.results(spec, sim, pools)
-    out.pop("lb_current_weights", None)
-    out.update(FS.fault_results(pools["fault_schedule"], fault_targets(pools)))
-    out.update(health_results(spec, pools))
-    out["internal_by_kind"] = np.asarray(sim._internal_by_kind, np.int64)      # limiter Requests, limiter polls, fault set, fault clear
-    out["health_by_kind"] = np.asarray(sim._health_by_kind, np.int64)          # cycle, response, timeout
-    out["events_cancelled"] = int(sim.summary.events_cancelled)
     return out

@@ -8,7 +8,8 @@ and ["limiter", i] wherever a Request can be aimed: a Source's `to`, a Server's 
 target, another limiter's `out`.  `auto=True`: no end time (the run ends when only daemon events are pending); `windows`: the
 reference driven by `_run_window` with these ends before `end_s`; `start_ns`: Simulation(start_time=).
 tests/golden/make_golden_rate_limiter.py runs the LIVE reference on every spec listed here and records what it computed
-(tests/rate_limiter_reference.py); `build()` wires the product's objects the same way (`wire()` is shared by both).
+(tests/recorded.py RATE_LIMITER reads it back); tests/graph_family.py `build()` wires the product's objects the same way (its `wire()`
+is shared by both).
 
   FIXTURES        named cases, recorded with their full event trace
   random_spec(k)  N_RANDOM seeded general graphs (random_specs.graph_spec / lb_graph_spec) with limiters put on their edges
@@ -255,110 +256,8 @@ def replay(pol, calls):
 replay.instant = hs.Instant       # (make_golden_rate_limiter.py sets the reference's Instant)
 
 
-# ---- wiring, shared by the product (build) and the reference (make_golden_rate_limiter.run_case) -----------------------------------
-def wire(spec, F):
-    """The spec's objects from the factory `F` (sink, server, link, lb, router, limiter, source, probe): pools by kind, limiters'
-    downstreams and links' egresses resolved once everything exists.  Entities: servers + lbs + routers + links + limiters + sinks."""
-    sinks = [F.sink(j) for j in range(spec["n_sinks"])]
-    servers = [F.server(i, sv) for i, sv in enumerate(spec["servers"])]
-    limiters = [F.limiter(i, lm) for i, lm in enumerate(spec.get("limiters") or [])]
-    pools = {"sink": sinks, "server": servers, "limiter": limiters}
-
-    def ref(r):
-        return servers[r] if isinstance(r, int) else pools[r[0]][r[1]]
-
-    links = pools["link"] = [F.link(l, lk) for l, lk in enumerate(spec["links"])]
-    lbs = pools["lb"] = [F.lb(j, lb, [servers[b] for b in lb["backends"]]) for j, lb in enumerate(spec.get("lbs") or [])]
-    routers = pools["router"] = [None] * len(spec["routers"])
-    pending = list(range(len(routers)))
-    while pending:
-        progressed = False
-        for r in list(pending):
-            tg = spec["routers"][r]["targets"]
-            if all(k != "router" or routers[i] is not None for k, i in tg):
-                routers[r] = F.router(r, [pools[k][i] for k, i in tg])
-                pending.remove(r)
-                progressed = True
-        assert progressed, "router targets form a cycle of routers"
-    for l, lk in enumerate(spec["links"]):
-        links[l].egress = ref(lk["to"])
-    for i, lm in enumerate(spec.get("limiters") or []):
-        limiters[i]._downstream = ref(lm["out"])
-    for i, sv in enumerate(spec["servers"]):
-        if sv.get("out") is not None:
-            servers[i].downstream = ref(sv["out"])
-    sources = pools["source"] = [F.source(k, sc, ref(sc["to"])) for k, sc in enumerate(spec["sources"])]
-    probes = [F.probe(pools[kind][idx], metric, interval) for (kind, idx), metric, interval in spec.get("probes") or []]
-    entities = servers + lbs + routers + links + limiters + sinks
-    return pools, sources, probes, entities
-
-
-class _Product:
-    @staticmethod
-    def sink(j):
-        return hs.Sink(f"sink{j}")
-
-    @staticmethod
-    def server(i, sv):
-        return hs.Server(f"srv{i}", concurrency=sv.get("c", 1), queue_capacity=sv.get("cap"),
-                         service_time=hs.ConstantLatency(sv["mean"]) if sv.get("svc") == "const" else hs.ExponentialLatency(sv["mean"]))
-
-    @staticmethod
-    def limiter(i, lm):
-        return hs.RateLimitedEntity(f"lim{i}", None, make_policy(hs, lm["policy"]), queue_capacity=lm["cap"])
-
-    @staticmethod
-    def link(l, lk):
-        jit = None
-        if lk.get("jm") is not None and lk.get("jk") == "exp":
-            jit = hs.ExponentialLatency(lk["jm"])
-        elif lk.get("jm") is not None and lk.get("jk") == "const":
-            jit = hs.ConstantLatency(lk["jm"])
-        return hs.NetworkLink(f"link{l}", latency=hs.ConstantLatency(lk["lat"]), jitter=jit, packet_loss_rate=lk.get("loss", 0.0), egress=None)
-
-    @staticmethod
-    def lb(j, lb, backends):
-        import strategy_specs as SS
-
-        return SS.make_lb(hs.LoadBalancer, j, lb, backends, SS.make_strategy(lb))
-
-    @staticmethod
-    def router(r, targets):
-        return hs.RandomRouter(f"router{r}", targets=targets)
-
-    @staticmethod
-    def source(k, sc, to):
-        make = hs.Source.poisson if sc["kind"] == "poisson" else hs.Source.constant
-        if sc.get("n_clients"):
-            return make(rate=sc["rate"], event_provider=hs.ClientKeyEventProvider(to, n_clients=sc["n_clients"]), name=f"src{k}")
-        return make(rate=sc["rate"], target=to, name=f"src{k}")
-
-    @staticmethod
-    def probe(target, metric, interval):
-        return hs.Probe.on(target, metric, interval=interval)
-
-
-def build(spec, seed=None):
-    """(Simulation, entities by pool) of the product, wired like the recorded reference run."""
-    pools, sources, probes, entities = wire(spec, _Product)
-    start_ns = int(spec.get("start_ns", 0))
-
-    def at(t_s):
-        return hs.Instant(start_ns + hs.Instant.from_seconds(t_s).nanoseconds)
-
-    # (max_graph_events: a run that never ends -- see _fixtures on FixedWindowPolicy -- is refused after 400 000 events, not minutes)
-    sim = hs.Simulation(sources=sources, entities=entities, seed=spec["seed"] if seed is None else seed, max_graph_events=400_000,
-                        **({} if spec.get("auto") else {"end_time": at(spec["end_s"])}),
-                        **({"start_time": hs.Instant(start_ns)} if start_ns else {}),
-                        **({"probes": [p for p, _ in probes]} if probes else {}))
-    for (kind, idx), t_s in spec.get("schedule") or []:
-        sim.schedule(hs.Event(time=at(t_s), event_type="Request", target=pools[kind][idx]))
-    pools["probes"] = probes
-    return sim, pools
-
-
 def limiter_results(lims):
-    """What both libraries' limiters show after a run (the recorded keys of make_golden_rate_limiter.run_case)."""
+    """What both libraries' limiters show after a run (recorded keys of the rate_limiter family and of every later one)."""
     out = dict(lim_stats=np.array([[x.stats.received, x.stats.forwarded, x.stats.queued, x.stats.dropped, x.queue_depth,
                                     int(x._poll_scheduled)] for x in lims], np.int64).reshape(-1, 6))
     for name in ("received_times", "forwarded_times", "dropped_times"):
@@ -376,17 +275,4 @@ def limiter_results(lims):
         loff.append(len(logs))
     out["lim_policy_state"] = np.asarray(state, np.float64).reshape(-1, 3)
     out["lim_log"], out["lim_log_off"] = np.asarray(logs, np.int64), np.asarray(loff, np.int64)
-    return out
-
-
-def results(spec, sim, pools):
-    """Everything make_golden_rate_limiter.run_case records except the trace, read off the product's objects after run()."""
-    import strategy_specs as SS
-
-    ents = dict(sources=pools["source"], servers=pools["server"], links=pools["link"], routers=pools["router"], sinks=pools["sink"],
-                lbs=pools["lb"], probes=pools["probes"])
-    out = SS.results(spec, sim, ents)
-    out.pop("sink_created_ns")
-    out.update(limiter_results(pools["limiter"]))
-    out["lim_events"] = np.array([x._events for x in pools["limiter"]], np.int64).reshape(-1, 2)
     return out

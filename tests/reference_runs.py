@@ -17,56 +17,14 @@ from __future__ import annotations
 
 import atexit
 import glob
-import hashlib
-import json
 import os
 import sys
-import zlib
 
-import numpy as np
+from recorded import GOLDEN_DIR, _decode, _encode, _key, read_parts, write_parts
 
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 REC_DIR = os.path.join(GOLDEN_DIR, "live_reference")
 RECORD = os.environ.get("HS_RECORD_REFERENCE") == "1"
 PART_BYTES = 900 * 1024                 # compressed bytes per file (every committed file stays under 1 MiB)
-
-
-def _key(name, args):
-    blob = json.dumps([name, list(args)], sort_keys=True, default=repr)
-    return hashlib.sha256(blob.encode()).hexdigest()[:20]
-
-
-def _encode(obj, arrays):
-    """obj -> a JSON value; numpy arrays go to `arrays` and are referenced by index (dict keys, tuples and scalar types kept)."""
-    if isinstance(obj, np.ndarray):
-        arrays.append(obj)
-        return {"nd": len(arrays) - 1}
-    if isinstance(obj, dict):
-        return {"dict": [[_encode(k, arrays), _encode(v, arrays)] for k, v in obj.items()]}
-    if isinstance(obj, tuple):
-        return {"tuple": [_encode(v, arrays) for v in obj]}
-    if isinstance(obj, list):
-        return [_encode(v, arrays) for v in obj]
-    if isinstance(obj, np.generic):
-        arrays.append(np.asarray(obj))
-        return {"np": len(arrays) - 1}
-    if obj is None or isinstance(obj, (bool, int, float, str)):
-        return obj
-    raise TypeError(f"cannot record a {type(obj).__name__}")
-
-
-def _decode(v, arrays):
-    if isinstance(v, list):
-        return [_decode(x, arrays) for x in v]
-    if isinstance(v, dict):
-        if "nd" in v:
-            return arrays[v["nd"]]
-        if "np" in v:
-            return arrays[v["np"]][()]
-        if "tuple" in v:
-            return tuple(_decode(x, arrays) for x in v["tuple"])
-        return {_decode(k, arrays): _decode(x, arrays) for k, x in v["dict"]}
-    return v
 
 
 def _make_golden():
@@ -85,12 +43,7 @@ class _Recorded:
 
     def _store(self):
         if self._loaded is None:
-            self._loaded = {}
-            for path in sorted(glob.glob(os.path.join(REC_DIR, "*.npz"))):
-                with np.load(path, allow_pickle=False) as z:
-                    index = json.loads(bytes(z["index"]).decode())
-                    for key, (skeleton, names) in index.items():
-                        self._loaded[key] = (skeleton, [z[n] for n in names])
+            self._loaded = read_parts(REC_DIR)
         return self._loaded
 
     def _lookup(self, key, what):
@@ -138,44 +91,9 @@ class _Recorded:
         stored = self._store()
         if not any(key in stored for key in self._fresh):
             # only new results: new part files behind the stored ones, which stay byte for byte as they are
-            n0 = len(glob.glob(os.path.join(REC_DIR, "*.npz")))
-            self._write_parts(self._fresh, n0)
+            write_parts(REC_DIR, self._fresh, PART_BYTES, first=len(glob.glob(os.path.join(REC_DIR, "*.npz"))))
             return
-        cases = {}
-        for key, (skeleton, arrays) in self._store().items():
-            cases[key] = (skeleton, arrays)
-        cases.update(self._fresh)
-        os.makedirs(REC_DIR, exist_ok=True)
-        for path in glob.glob(os.path.join(REC_DIR, "*.npz")):
-            os.remove(path)
-        self._write_parts(cases, 0)
-
-    @staticmethod
-    def _write_parts(cases, first):
-        """cases -> part_<first>.npz, part_<first + 1>.npz, ... of at most PART_BYTES each."""
-        os.makedirs(REC_DIR, exist_ok=True)
-        part, index, size, n = {}, {}, 0, first
-
-        def flush():
-            nonlocal part, index, size, n
-            if index:
-                part["index"] = np.frombuffer(json.dumps(index, separators=(",", ":")).encode(), np.uint8)
-                np.savez_compressed(os.path.join(REC_DIR, f"part_{n:03d}.npz"), **part)
-                n += 1
-            part, index, size = {}, {}, 0
-
-        for key in sorted(cases):
-            skeleton, arrays = cases[key]
-            est = len(zlib.compress(json.dumps(skeleton).encode())) + sum(
-                len(zlib.compress(np.ascontiguousarray(a).tobytes())) for a in arrays) + 256 * (len(arrays) + 1)
-            if index and size + est > PART_BYTES:
-                flush()
-            names = [f"{key}_{i}" for i in range(len(arrays))]
-            for nm, a in zip(names, arrays):
-                part[nm] = np.asarray(a)
-            index[key] = (skeleton, names)
-            size += est
-        flush()
+        write_parts(REC_DIR, {**stored, **self._fresh}, PART_BYTES)
 
 
 REF = _Recorded()

@@ -5,8 +5,8 @@
   every <ref> of the format may be ["wrapper", i]; faults and probes may name ["wrapper", i]; `checkers` / `unhealthy` as in
   tests/health_specs.py.
 
-tests/golden/make_golden_resilience.py runs the LIVE reference on every spec listed here (tests/resilience_reference.py reads the
-recordings back); `build()` wires the product's objects the same way.  Entities: servers + lbs + routers + links + limiters + sinks +
+tests/golden/make_golden_resilience.py runs the LIVE reference on every spec listed here (tests/recorded.py RESILIENCE reads the
+recordings back); tests/graph_family.py `build()` wires the product's objects the same way.  Entities: servers + lbs + routers + links + limiters + sinks +
 wrappers + checkers.  Every case stays small: at most 20 s of simulated time at 100 Requests/s or less.
 
   FIXTURES        named cases; TRACED: recorded with their full event trace
@@ -266,79 +266,6 @@ def groups_spec(n_groups, name="groups", end_s=3.0, paused=True):
     return _g(name, wrappers, servers=servers, links=links, sources=sources, n_sinks=n_groups, faults=faults, end_s=end_s, seed=23)
 
 
-# ---- wiring, shared by the product (build) and the reference (make_golden_resilience.run_case) ------------------------------------
-def wire(spec, F, bulkhead_cls, timeout_cls, checker_cls):
-    """rate_limiter_specs.wire with the wrappers: pools by kind, every reference resolved once its object exists."""
-    sinks = [F.sink(j) for j in range(spec["n_sinks"])]
-    servers = [F.server(i, sv) for i, sv in enumerate(spec["servers"])]
-    limiters = [F.limiter(i, lm) for i, lm in enumerate(spec.get("limiters") or [])]
-    pools = {"sink": sinks, "server": servers, "limiter": limiters}
-    links = pools["link"] = [F.link(l, lk) for l, lk in enumerate(spec["links"])]
-    lbs = pools["lb"] = [F.lb(j, lb, [servers[b] for b in lb["backends"]]) for j, lb in enumerate(spec.get("lbs") or [])]
-    routers = pools["router"] = [None] * len(spec["routers"])
-    wrappers = pools["wrapper"] = [None] * len(spec["wrappers"])
-
-    def ref(r):
-        return servers[r] if isinstance(r, int) else pools[r[0]][r[1]]
-
-    def ready(r):
-        return isinstance(r, int) or pools[r[0]][r[1]] is not None
-
-    pending = [("router", r) for r in range(len(routers))] + [("wrapper", i) for i in range(len(wrappers))]
-    while pending:
-        progressed = False
-        for kind, i in list(pending):
-            if kind == "router" and all(ready(t) for t in spec["routers"][i]["targets"]):
-                routers[i] = F.router(i, [ref(t) for t in spec["routers"][i]["targets"]])
-            elif kind == "wrapper" and ready(spec["wrappers"][i]["to"]):
-                w = spec["wrappers"][i]
-                wrappers[i] = (bulkhead_cls(f"bh{i}", ref(w["to"]), max_concurrent=w["mc"], max_wait_queue=w["mq"], max_wait_time=w["mw"])
-                               if w["kind"] == "bulkhead" else timeout_cls(f"tw{i}", ref(w["to"]), timeout=w["timeout"]))
-            else:
-                continue
-            pending.remove((kind, i))
-            progressed = True
-        assert progressed, "routers and wrappers form a cycle"
-    for l, lk in enumerate(spec["links"]):
-        links[l].egress = None if lk["to"] is None else ref(lk["to"])
-    for i, lm in enumerate(spec.get("limiters") or []):
-        limiters[i]._downstream = ref(lm["out"])
-    for i, sv in enumerate(spec["servers"]):
-        if sv.get("out") is not None:
-            servers[i].downstream = ref(sv["out"])
-    sources = pools["source"] = [F.source(k, sc, ref(sc["to"])) for k, sc in enumerate(spec["sources"])]
-    probes = pools["probe"] = [F.probe(ref(on), metric, interval) for on, metric, interval in spec.get("probes") or []]
-    pools["checker"] = [checker_cls(f"hc{i}", lbs[ck["lb"]], interval=ck["interval"], timeout=ck["timeout"], healthy_threshold=ck["ht"],
-                                    unhealthy_threshold=ck["ut"]) for i, ck in enumerate(spec.get("checkers") or [])]
-    entities = servers + lbs + routers + links + limiters + sinks + wrappers + pools["checker"]
-    return pools, sources, probes, entities
-
-
-def fault_targets(pools):
-    return FS.fault_targets(pools) + list(pools["wrapper"]) + list(pools["checker"])
-
-
-def build(spec, seed=None):
-    """(Simulation, entities by pool) of the product, wired like the recorded reference run."""
-    pools, sources, probes, entities = wire(spec, RS._Product, hs.Bulkhead, hs.TimeoutWrapper, hs.HealthChecker)
-    start_ns = int(spec.get("start_ns", 0))
-
-    def at(t_s):
-        return hs.Instant(start_ns + hs.Instant.from_seconds(t_s).nanoseconds)
-
-    fs, handles = FS.make_schedule(hs, spec, pools)
-    sim = hs.Simulation(sources=sources, entities=entities, seed=spec["seed"] if seed is None else seed, max_graph_events=400_000,
-                        fault_schedule=fs, **({} if spec.get("auto") else {"end_time": at(spec["end_s"])}),
-                        **({"start_time": hs.Instant(start_ns)} if start_ns else {}), **({"probes": [p for p, _ in probes]} if probes else {}))
-    FS.cancel_after(spec, handles)
-    for on, t_s in spec.get("schedule") or []:
-        sim.schedule(hs.Event(time=at(t_s), event_type="Request", target=pools[on[0]][on[1]]))
-    HS.start_checkers(spec, pools, sim, [[] for _ in pools["checker"]])
-    pools["probes"] = probes
-    pools["fault_schedule"], pools["handles"] = fs, handles
-    return sim, pools
-
-
 def wrapper_results(pools):
     """What both libraries' wrappers show after a run.  wrap_stats rows -- Bulkhead: total, accepted, rejected, timed_out, queued,
     peak_concurrent, peak_queue_depth, active_count, queue_depth, available_permits, _next_request_id, len(_in_flight);
@@ -357,18 +284,3 @@ def wrapper_results(pools):
         qoff.append(len(queue))
     return dict(wrap_stats=np.asarray(rows, np.int64).reshape(-1, 12), wrap_in_flight=np.asarray(live, np.int64), wrap_in_flight_off=np.asarray(loff, np.int64),
                 wrap_queue=np.asarray(queue, np.int64), wrap_queue_off=np.asarray(qoff, np.int64))
-
-
-def results(spec, sim, pools):
-    """Everything make_golden_resilience.run_case records except the trace, read off the product's objects after run()."""
-    out = RS.results(spec, sim, pools)
-    out.pop("lb_current_weights", None)
-    out.update(FS.fault_results(pools["fault_schedule"], fault_targets(pools)))
-    out.update(HS.health_results(spec, pools))
-    out.update(wrapper_results(pools))
-    out["fault_events"] = int(getattr(sim, "_fault_events_processed", 0))
-    out["internal_by_kind"] = np.asarray(sim._internal_by_kind, np.int64)            # limiter Requests, limiter polls, fault set, fault clear
-    out["health_by_kind"] = np.asarray(getattr(sim, "_health_by_kind", np.zeros(3)), np.int64)
-    out["resilience_by_kind"] = np.asarray(sim._resilience_by_kind, np.int64)        # Bulkhead request / response / timeout, then TimeoutWrapper's
-    out["events_cancelled"] = int(sim.summary.events_cancelled)
-    return out

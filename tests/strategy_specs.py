@@ -5,7 +5,7 @@ weighted ones; a Server may have svc="const"; `server_stream_offset` = n moves S
 pipeline lowering numbers its backends behind the Sources (lowering.lower_lb: backend j -> len(sources) + j), the single-heap lowering
 counts Servers from 0 (graph_engine.lower_general), and a spec is recorded with the numbering of the path `hs.Simulation` takes.
 tests/golden/make_golden_strategies.py runs the LIVE reference on every spec listed here and records what it computed
-(tests/strategy_reference.py); `build()` wires the product's objects the same way.
+(tests/recorded.py STRATEGIES reads it back); `build()` wires the product's objects the same way.
 
   FIXTURES        named cases, recorded with their full event trace
   random_spec(k)  150 seeded cases: pipeline shapes (k % 3 == 0) and general graphs (random_specs.lb_graph_spec with the

@@ -8,11 +8,12 @@ import subprocess
 import numpy as np
 import pytest
 
-import client_reference as CR
 import client_specs as CS
+import graph_family as GF
 import happy_simulator_amd as hs
 from happy_simulator_amd import _native as N
 from happy_simulator_amd.graph_engine import GeneralGraph, client_delay_table, split_parts
+from recorded import CLIENT as CR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (the grids of tests/golden/make_golden_client.py, which needs the reference to be imported: repeated here)
@@ -124,7 +125,7 @@ def test_the_lowering_accepts_every_spec():
     """Every recorded spec is one the product takes; a Client sends the Simulation to the single-heap loop whatever its shape."""
     for spec in CS.all_specs():
         CR.get("case", spec)                                   # (recorded: no case is left out)
-        sim, pools = CS.build(spec)
+        sim, pools = GF.build(spec)
         g = sim.lowered()
         assert isinstance(g, GeneralGraph) and g.arrays.has_clients and "do not lower a Client" in sim._station_refusal, spec["name"]
         a = g.arrays
@@ -137,14 +138,14 @@ def test_the_lowering_accepts_every_spec():
 
 
 def test_the_lowered_arrays_of_two_fixtures():
-    sim, pools = CS.build(CS.FIXTURES["exponential_backoff_at_its_cap"])  # srv0, sink0, cl0
+    sim, pools = GF.build(CS.FIXTURES["exponential_backoff_at_its_cap"])  # srv0, sink0, cl0
     a = sim.lowered().arrays
     assert a.kind.tolist() == [N.NODE_SERVER, N.NODE_SINK, N.NODE_CLIENT] and a.target.tolist() == [1, -1, 0]
     assert a.cl_params[2].tolist() == [0.05, 0.0] and not a.cl_params[:2].any()
     assert a.cl_delay_off.tolist() == [0, 0, 0, 5] and a.cl_delays_ns.tolist() == [100_000_000, 100_000_000, 200_000_000, 250_000_000, 250_000_000]
     sched = sim._general_prepare(sim.lowered(), False)[2]
     assert sched == [(2, 600_000_000, 1), (2, 700_000_000, 2), (2, 1_400_000_000, 3)]
-    sim, pools = CS.build(CS.FIXTURES["probe_on_in_flight_count"])        # 2 src, 2 probes, srv0, link0, link1, sink0, cl0, cl1
+    sim, pools = GF.build(CS.FIXTURES["probe_on_in_flight_count"])        # 2 src, 2 probes, srv0, link0, link1, sink0, cl0, cl1
     a = sim.lowered().arrays
     assert a.kind[2:4].tolist() == [N.NODE_PROBE] * 2 and a.probe_metric[2:4].tolist() == [12, 12] and a.target[2:4].tolist() == [8, 9]
     assert a.cl_params[8:].tolist() == [[0.3, 0.0], [-1.0, 0.0]] and a.cl_delays_ns.tolist() == [100_000_000]
@@ -281,7 +282,7 @@ def test_parts_keep_a_client_with_its_target_and_leave_the_rest_without():
     spec = CS.groups_spec(4)
     spec["servers"].append(CS.srv(0.05, out=None))
     spec["sources"].append(CS.src(4, 9.0))                                  # a fifth component without any Client
-    sim, pools = CS.build(spec)
+    sim, pools = GF.build(spec)
     a = sim.lowered().arrays
     parts = split_parts(a)
     assert len(parts) == 5
@@ -311,7 +312,7 @@ def test_what_the_issue_says_holds_in_the_recordings():
     late = [t for t in trace[trace[:, 1] == 29][:, 0].tolist() if t == 300_000_000]
     assert sends[:2] == [0, 250_000_000] and len(late) == 2 and r["cl_stats"][0, 1] == 0      # attempt 1's responses at 0.3 s, attempt 2 in flight until 0.45 s
     assert len(CS.FIXTURES) >= 40 and len(CS.TRACED) == 6 and CS.N_RANDOM >= 120
-    assert max(os.path.getsize(os.path.join(CR.REC_DIR, f)) for f in os.listdir(CR.REC_DIR)) <= 531_061       # the largest live_resilience part
+    assert max(os.path.getsize(os.path.join(CR.rec_dir, f)) for f in os.listdir(CR.rec_dir)) <= 531_061       # the largest live_resilience part
 
 
 def test_the_new_symbols_are_in_the_header_and_the_library():

@@ -8,12 +8,13 @@ import re
 import numpy as np
 import pytest
 
-import fault_reference as FR
 import fault_specs as FS
+import graph_family as GF
 import happy_simulator_amd as hs
 import rate_limiter_specs as RS
 from happy_simulator_amd import _native as N
 from happy_simulator_amd.graph_engine import GeneralGraph
+from recorded import FAULTS as FR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -103,7 +104,7 @@ def test_an_empty_schedule_behaves_as_none():
 
 def test_a_duplicate_name_resolves_to_the_last_object():
     spec = FS.FIXTURES["duplicate_name"]
-    sim, pools = FS.build(spec)
+    sim, pools = GF.build(spec)
     g = sim.lowered()
     assert pools["server"][0].name == pools["server"][1].name == "srv0"
     assert {n for n, _t, _on, _c in sim._general_faults(g)} == {g.node_of[id(pools["server"][1])]}
@@ -144,7 +145,7 @@ def test_every_spec_lowers_to_the_single_heap_loop():
     every entity kind."""
     kinds = set()
     for spec in FS.all_specs():
-        sim, _pools = FS.build(spec)
+        sim, _pools = GF.build(spec)
         g = sim.lowered()
         assert isinstance(g, GeneralGraph), spec["name"]
         faults = sim._general_faults(g)
@@ -184,5 +185,5 @@ def test_the_recordings_hold_what_the_issue_observed():
         assert r["lim_stats"][0, 5] == 1 and r["lim_stats"][0, 4] > 0
     # every fault_stats row: activated / deactivated are never incremented
     assert all(FR.get("case", s)["fault_stats"][1:3].tolist() == [0, 0] for s in FS.all_specs())
-    assert sorted(os.path.getsize(os.path.join(FR.REC_DIR, f)) for f in os.listdir(FR.REC_DIR))[-1] <= FR.MAX_PART_BYTES
+    assert sorted(os.path.getsize(os.path.join(FR.rec_dir, f)) for f in os.listdir(FR.rec_dir))[-1] <= FR.max_part_bytes
     assert np.all([len(FR.get("case", FS.FIXTURES[n])["trace"]) > 100 for n in FS.TRACED])

@@ -6,11 +6,13 @@ or excluded (test_every_recorded_case_is_compared)."""
 import numpy as np
 import pytest
 
-import client_reference as CR
 import client_specs as CS
+import family_checks as FC
+import graph_family as GF
 import happy_simulator_amd as hs
 from happy_simulator_amd import _native as N
 from happy_simulator_amd.graph_engine import GeneralGraph, GraphEngine
+from recorded import CLIENT as CR
 
 pytestmark = pytest.mark.gpu
 
@@ -18,31 +20,14 @@ pytestmark = pytest.mark.gpu
 # of its own (by_kind: the engine reports the public fifteen kinds, the internal ones per graph; trace: test_record_order_follows_the_trace)
 _NOT_COMPARED = {"trace", "by_kind", "pending_events", "time_travel"}
 _FIRST_HC, _FIRST_WRAPPER, _FIRST_CLIENT = N.EV_KINDS + 4, N.EV_KINDS + 7, N.EV_KINDS + 13
+_BY_KIND_SLICES = [("by_kind", N.EV_KINDS), ("internal_by_kind", _FIRST_HC), ("health_by_kind", _FIRST_WRAPPER), ("resilience_by_kind", _FIRST_CLIENT),
+                   ("client_by_kind", _FIRST_CLIENT + 3)]
 
 
-def _compare(spec, sim, pools, ref):
-    got = CS.results(spec, sim, pools)
-    for key, want in ref.items():
-        if key in _NOT_COMPARED:
-            continue
-        have = got[key]
-        if isinstance(want, np.ndarray):
-            have = np.asarray(have)
-            if want.dtype == np.float64:                    # bit for bit
-                assert have.dtype == np.float64 and have.shape == want.shape and have.tobytes() == want.tobytes(), (spec["name"], key, have.tolist()[:8], want.tolist()[:8])
-            else:
-                assert np.array_equal(have, want), (spec["name"], key, have.tolist()[:16], want.tolist()[:16])
-        else:
-            assert have == want, (spec["name"], key, have, want)
-    np.testing.assert_array_equal(got["by_kind"], ref["by_kind"][:N.EV_KINDS])
-    np.testing.assert_array_equal(got["internal_by_kind"], ref["by_kind"][N.EV_KINDS:_FIRST_HC])
-    np.testing.assert_array_equal(got["health_by_kind"], ref["by_kind"][_FIRST_HC:_FIRST_WRAPPER])
-    np.testing.assert_array_equal(got["resilience_by_kind"], ref["by_kind"][_FIRST_WRAPPER:_FIRST_CLIENT])
-    np.testing.assert_array_equal(got["client_by_kind"], ref["by_kind"][_FIRST_CLIENT:])
+def _equals_the_recording(spec, sim, pools, ref):
+    got = GF.results(spec, sim, pools, "client")
+    FC.compare(spec["name"], got, ref, _NOT_COMPARED, _BY_KIND_SLICES)
     assert len(ref["by_kind"]) == 31
-    # the event identity: the internal kinds count in events_processed, not in events_by_kind
-    assert got["total_events"] == (int(got["by_kind"].sum()) + int(got["internal_by_kind"].sum()) + int(got["health_by_kind"].sum()) +
-                                   int(got["resilience_by_kind"].sum()) + int(got["client_by_kind"].sum()))
     for c in pools["client"]:
         # average_response_time: the reference's expression over the list, evaluated here (sum() differs between Python versions)
         times = c._response_times
@@ -55,16 +40,10 @@ def _compare(spec, sim, pools, ref):
 
 
 def _run(spec, **kw):
-    sim, pools = CS.build(spec, **kw)
+    sim, pools = GF.build(spec, **kw)
     sim.run()
     assert isinstance(sim._graph, GeneralGraph) and "Client" in sim._station_refusal
     return sim, pools
-
-
-def _same(got, one, where=""):
-    assert set(got) == set(one)
-    for key in one:
-        assert np.array_equal(np.asarray(got[key]), np.asarray(one[key])), (where, key)
 
 
 def test_every_recorded_case_is_compared():
@@ -82,14 +61,14 @@ def test_every_recorded_case_is_compared():
 def test_named_fixture_equals_the_reference(name):
     spec = CS.FIXTURES[name]
     sim, pools = _run(spec)
-    _compare(spec, sim, pools, CR.get("case", spec))
+    _equals_the_recording(spec, sim, pools, CR.get("case", spec))
 
 
 @pytest.mark.parametrize("k", range(CS.N_RANDOM))
 def test_random_graph_equals_the_reference(k):
     spec = CS.random_spec(k)
     sim, pools = _run(spec)
-    _compare(spec, sim, pools, CR.get("case", spec))
+    _equals_the_recording(spec, sim, pools, CR.get("case", spec))
 
 
 def test_what_the_issue_says_about_the_reference():
@@ -112,29 +91,6 @@ def test_what_the_issue_says_about_the_reference():
     assert c.in_flight_count > 0 and c._crashed is True and all(k[0] is None or k[0] > 0 for k in c._in_flight)
 
 
-def _engine(spec, **caps):
-    sim, pools = CS.build(spec)
-    g = sim.lowered()
-    end_ns, start_ns, sched, cancelled = sim._general_prepare(g, bool(spec.get("auto")))
-    eng = GraphEngine(g.arrays, seed=spec["seed"], start_ns=start_ns, **caps)
-    for node, t, on, c in sim._general_faults(g):
-        eng.add_fault(node, t, on, c)
-    for entry in sched:
-        eng.schedule(*entry)
-    return sim, pools, g, eng, end_ns, start_ns, cancelled
-
-
-def _engine_run(spec, ends_s, **caps):
-    """The spec on a GraphEngine of its own, run to every end of `ends_s` in turn; the results bound like Simulation.run() binds them."""
-    sim, pools, g, eng, end_ns, start_ns, cancelled = _engine(spec, **caps)
-    with eng:
-        for t in ends_s:
-            eng.run_until(start_ns + hs.Instant.from_seconds(t).nanoseconds)
-        tables = [eng.client(int(i))["table_capacity"] for i in np.nonzero(g.arrays.kind == N.NODE_CLIENT)[0]]
-        sim._general_finish(g, eng, end_ns, cancelled, 0.0)
-    return sim, pools, tables
-
-
 @pytest.mark.parametrize("name", CS.TRACED)
 def test_record_order_follows_the_trace(name):
     """The record log against the reference's full trace (time ns, kind, node, sort index of every popped Event): every Sink event and
@@ -143,7 +99,7 @@ def test_record_order_follows_the_trace(name):
     spec = CS.FIXTURES[name]
     ref = CR.get("case", spec)
     trace = ref["trace"]
-    sim, pools, g, eng, end_ns, _start, _c = _engine(spec)
+    sim, pools, g, eng, end_ns, _start, _c = FC.engine(spec)
     with eng:
         eng.run_until(end_ns)
         node, t, v = eng.records()
@@ -153,14 +109,7 @@ def test_record_order_follows_the_trace(name):
     assert by_kind == [int((trace[:, 1] == k).sum()) for k in range(N.EV_KINDS)]
     assert internal.tolist() == [int((trace[:, 1] == N.EV_KINDS + k).sum()) for k in range(4)]
     assert events.tolist() == [int((trace[:, 1] == _FIRST_CLIENT + k).sum()) for k in range(3)] and events.sum() > 0
-    crashed, keep = set(), []
-    for row in trace:
-        if row[1] == N.EV_KINDS + 2:
-            crashed.add(int(row[2]))
-        elif row[1] == N.EV_KINDS + 3:
-            crashed.discard(int(row[2]))
-        keep.append(row[1] == N.EV_NAMES.index("sink") and int(row[2]) not in crashed)
-    want = trace[np.array(keep)]
+    want = FC.live_rows(trace)
     at_sink = g.arrays.kind[node] == N.NODE_SINK
     assert np.array_equal(np.stack([t[at_sink], node[at_sink]], axis=1), want[:, [0, 2]])
     # the Clients' rows: response time and start time in ns; start + response time is the time of a `_client_response` of the trace
@@ -171,13 +120,21 @@ def test_record_order_follows_the_trace(name):
     assert len(pools["client"]) == 1 and np.array_equal(t[at_client] / 1e9, ref["cl_response_times"])
 
 
+def _run_to_ends_with_tables(spec, ends_s, **caps):
+    """FC.engine_run and every Client's table capacity at the end."""
+    def tables(eng, g):
+        return [eng.client(int(i))["table_capacity"] for i in np.nonzero(g.arrays.kind == N.NODE_CLIENT)[0]]
+
+    return FC.engine_run(spec, ends_s, read=tables, **caps)
+
+
 def test_windows_equal_one_run():
     for name in ("fixed_retry_crash_with_restart", "source_plain_and_send_request_mixed", "probe_on_in_flight_count", "link_delay_equals_timeout",
                  "client_crash_with_restart"):
         spec = CS.FIXTURES[name]
         ends = [0.25, 0.5, 0.5, 1.2, 1.6, 1.9000001, spec["end_s"]]          # 7 uneven windows, ends on tie and fault nanoseconds among them
-        sim, pools, _ = _engine_run(spec, ends)
-        _compare(spec, sim, pools, CR.get("case", spec))
+        sim, pools, _ = _run_to_ends_with_tables(spec, ends)
+        _equals_the_recording(spec, sim, pools, CR.get("case", spec))
 
 
 def test_in_flight_table_grown_from_one_place_equals_the_reference():
@@ -185,12 +142,12 @@ def test_in_flight_table_grown_from_one_place_equals_the_reference():
     table (the keys in flight and their start times move with it) and the run goes on -- with leaked keys, a crash and retries on the way."""
     for name in ("client_crash_with_restart", "source_plain_and_send_request_mixed", "probe_on_in_flight_count", "two_clients_on_one_server"):
         spec = CS.FIXTURES[name]
-        sim, pools, tables = _engine_run(spec, [spec["end_s"]], table_capacity=1)
+        sim, pools, tables = _run_to_ends_with_tables(spec, [spec["end_s"]], table_capacity=1)
         assert tables and max(tables) >= 2, tables                          # (grown from one place)
-        got = _compare(spec, sim, pools, CR.get("case", spec))
-        roomy_sim, roomy_pools, roomy_tables = _engine_run(spec, [spec["end_s"]], table_capacity=4096)
+        got = _equals_the_recording(spec, sim, pools, CR.get("case", spec))
+        roomy_sim, roomy_pools, roomy_tables = _run_to_ends_with_tables(spec, [spec["end_s"]], table_capacity=4096)
         assert roomy_tables == [4096] * len(tables)
-        _same(got, CS.results(spec, roomy_sim, roomy_pools), name)
+        FC.same(got, GF.results(spec, roomy_sim, roomy_pools, "client"), name)
 
 
 def test_growth_from_capacities_of_one_equals_a_run_with_room():
@@ -199,12 +156,12 @@ def test_growth_from_capacities_of_one_equals_a_run_with_room():
     spec = CS._g("growth_under_a_backlog", [CS.cl(["link", 0], 0.8, CS.fixed(3, 0.05)), CS.cl(["link", 1], None)], servers=[CS.srv(0.1, cap=None)],
                  links=[CS.link(0, 0.5, "exp", 0.2), CS.link(0, 0.4, "exp", 0.3)], sources=[CS.src(["client", 1], 60.0)],
                  schedule=CS.send(CS.C0, *[round(0.01 * k, 2) for k in range(120)]), faults=[CS.pause(["server", 0], 0.5, 1.5)], end_s=3.0, seed=5)
-    grown_sim, grown_pools, tables = _engine_run(spec, [spec["end_s"]], heap_capacity=1, request_capacity=1, record_capacity=1, table_capacity=1)
-    roomy_sim, roomy_pools, _ = _engine_run(spec, [spec["end_s"]], heap_capacity=1 << 16, request_capacity=1 << 16, record_capacity=1 << 16,
-                                            table_capacity=1 << 12)
-    grown, roomy = CS.results(spec, grown_sim, grown_pools), CS.results(spec, roomy_sim, roomy_pools)
+    grown_sim, grown_pools, tables = _run_to_ends_with_tables(spec, [spec["end_s"]], heap_capacity=1, request_capacity=1, record_capacity=1, table_capacity=1)
+    roomy_sim, roomy_pools, _ = _run_to_ends_with_tables(spec, [spec["end_s"]], heap_capacity=1 << 16, request_capacity=1 << 16, record_capacity=1 << 16,
+                                                             table_capacity=1 << 12)
+    grown, roomy = GF.results(spec, grown_sim, grown_pools, "client"), GF.results(spec, roomy_sim, roomy_pools, "client")
     assert roomy["cl_stats"][0, 0] > 120 and roomy["cl_stats"][0, 1] > 0 and roomy["depth"].sum() + roomy["completed"].sum() > 50 and tables[0] >= 64
-    _same(grown, roomy)
+    FC.same(grown, roomy)
 
 
 def test_64_replicas_equal_64_single_runs():
@@ -214,7 +171,7 @@ def test_64_replicas_equal_64_single_runs():
     built = []
 
     def build_fn():
-        sim, pools = CS.build(specs[len(built)])
+        sim, pools = GF.build(specs[len(built)])
         built.append((sim, pools))
         return sim
 
@@ -223,9 +180,9 @@ def test_64_replicas_equal_64_single_runs():
     seen = set()
     for i, (sim, pools) in enumerate(built):
         assert isinstance(sim._graph, GeneralGraph) and sim._graph.arrays.has_clients
-        got = CS.results(specs[i], sim, pools)
+        got = GF.results(specs[i], sim, pools, "client")
         one_sim, one_pools = _run(specs[i], seed=700 + i)
-        _same(got, CS.results(specs[i], one_sim, one_pools), i)
+        FC.same(got, GF.results(specs[i], one_sim, one_pools, "client"), i)
         seen.add((got["total_events"], tuple(got["cl_stats"].ravel().tolist())))
     assert len(seen) > 48
 
@@ -244,8 +201,8 @@ def test_32_groups_as_parts_equal_one_heap():
     finally:
         S.MAX_PARTS = old
     assert one_sim._graph_parts == 1
-    got = CS.results(spec, sim, pools)
-    _same(got, CS.results(spec, one_sim, one_pools))
+    got = GF.results(spec, sim, pools, "client")
+    FC.same(got, GF.results(spec, one_sim, one_pools, "client"))
     assert (got["cl_stats"][:, 2] > 0).all() and (got["cl_stats"][:, 3] > 0).all() and (got["cl_stats"][:, 1] > 0).all()
 
 
@@ -258,7 +215,7 @@ def test_a_union_of_client_groups_as_parts_equals_the_recordings_of_its_members(
     spec, members = CS.union_spec(names)
     sim, pools = _run(spec)
     assert sim._graph_parts == parts and len(members) in (5, 6)
-    got = CS.results(spec, sim, pools)
+    got = GF.results(spec, sim, pools, "client")
     for name, off in members:
         ref = CR.get("case", CS.FIXTURES[name])
         c, k = off["client"], off["sink"]
@@ -286,7 +243,7 @@ def test_a_client_free_handle_in_a_batch_with_a_client_handle():
 
     def build_fn():
         k = len(built)
-        sim, pools = CS.build(with_client[k]) if k < 2 else XS.build(wrapped) if k == 2 else RS.build(plain_spec)
+        sim, pools = GF.build(with_client[k]) if k < 2 else GF.build(wrapped) if k == 2 else GF.build(plain_spec)
         built.append((sim, pools))
         return sim
 
@@ -294,20 +251,20 @@ def test_a_client_free_handle_in_a_batch_with_a_client_handle():
     assert len(results) == 4
     for i in range(2):
         one_sim, one_pools = _run(with_client[i], seed=40 + i)
-        _same(CS.results(with_client[i], *built[i]), CS.results(with_client[i], one_sim, one_pools), i)
-    one_sim, one_pools = XS.build(wrapped, seed=42)
+        FC.same(GF.results(with_client[i], *built[i], "client"), GF.results(with_client[i], one_sim, one_pools, "client"), i)
+    one_sim, one_pools = GF.build(wrapped, seed=42)
     one_sim.run()
-    _same(XS.results(wrapped, *built[2]), XS.results(wrapped, one_sim, one_pools), "wrapper")
+    FC.same(GF.results(wrapped, *built[2], "resilience"), GF.results(wrapped, one_sim, one_pools, "resilience"), "wrapper")
     sim, pools = built[3]
     assert not sim._graph.arrays.has_clients and not sim._graph.arrays.has_wrappers and not sim._faults
-    one_sim, one_pools = RS.build(plain_spec, seed=43)
+    one_sim, one_pools = GF.build(plain_spec, seed=43)
     one_sim.run()
-    _same(RS.results(plain_spec, sim, pools), RS.results(plain_spec, one_sim, one_pools), "plain")
+    FC.same(GF.results(plain_spec, sim, pools, "rate_limiter"), GF.results(plain_spec, one_sim, one_pools, "rate_limiter"), "plain")
     assert sim.summary.total_events_processed == one_sim.summary.total_events_processed
 
 
 def test_a_client_node_that_was_never_configured_is_a_state_error():
-    sim, _pools = CS.build(CS.FIXTURES["lossy_link"])
+    sim, _pools = GF.build(CS.FIXTURES["lossy_link"])
     g = sim.lowered()
     g.arrays.cl_params = None                                                  # (the handle is created without the client call)
     with GraphEngine(g.arrays, seed=1) as eng:
@@ -318,7 +275,7 @@ def test_a_client_node_that_was_never_configured_is_a_state_error():
 
 def test_the_engine_refuses_what_the_host_refuses():
     """hs_graph_create / hs_graph_set_client / hs_graph_schedule_client on hand-made arrays."""
-    sim, _pools = CS.build(CS.FIXTURES["two_links"])
+    sim, _pools = GF.build(CS.FIXTURES["two_links"])
     g = sim.lowered()
     a = g.arrays
     node = int(np.nonzero(a.kind == N.NODE_CLIENT)[0][0])

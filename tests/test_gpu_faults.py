@@ -6,12 +6,14 @@ including the fault count, the first Event beyond the end, the final `_crashed` 
 import numpy as np
 import pytest
 
-import fault_reference as FR
 import fault_specs as FS
+import family_checks as FC
+import graph_family as GF
 import happy_simulator_amd as hs
 import rate_limiter_specs as RS
 from happy_simulator_amd import _native as N
 from happy_simulator_amd.graph_engine import GeneralGraph, GraphEngine
+from recorded import FAULTS as FR
 
 pytestmark = pytest.mark.gpu
 
@@ -19,40 +21,24 @@ pytestmark = pytest.mark.gpu
 # form of its own (by_kind: the engine reports the public fifteen kinds, the four internal ones per node / per graph; trace:
 # test_record_order_follows_the_trace)
 _NOT_COMPARED = {"trace", "by_kind", "pending_events", "time_travel"}
-_FAULT_ON, _FAULT_OFF = N.EV_KINDS + 2, N.EV_KINDS + 3
+_FAULT_ON, _FAULT_OFF = FC.FAULT_ON, FC.FAULT_OFF
+# the four internal kinds are counted like the public ones (an Event dropped at a crashed limiter is counted, not handled)
+_BY_KIND_SLICES = [("by_kind", N.EV_KINDS), ("internal_by_kind", N.EV_KINDS + 4)]
 
 
-def _compare(spec, sim, pools, ref):
-    got = FS.results(spec, sim, pools)
-    for key, want in ref.items():
-        if key in _NOT_COMPARED:
-            continue
-        have = got[key]
-        if isinstance(want, np.ndarray):
-            assert np.array_equal(np.asarray(have), want), (spec["name"], key, np.asarray(have).tolist()[:12], want.tolist()[:12])
-        else:
-            assert have == want, (spec["name"], key, have, want)
-    np.testing.assert_array_equal(got["by_kind"], ref["by_kind"][:N.EV_KINDS])
-    # the four internal kinds, counted like the public ones (an Event dropped at a crashed limiter is counted, not handled)
-    np.testing.assert_array_equal(got["internal_by_kind"], ref["by_kind"][N.EV_KINDS:])
+def _equals_the_recording(spec, sim, pools, ref):
+    got = GF.results(spec, sim, pools, "faults")
+    FC.compare(spec["name"], got, ref, _NOT_COMPARED, _BY_KIND_SLICES)
     assert got["fault_events"] == int(ref["by_kind"][_FAULT_ON] + ref["by_kind"][_FAULT_OFF])
     assert np.all(got["lim_events"].sum(axis=0) <= got["internal_by_kind"][:2])
-    # the event identity: the internal kinds count in events_processed, not in events_by_kind
-    assert got["total_events"] == int(got["by_kind"].sum()) + int(got["internal_by_kind"].sum())
     return got
 
 
 def _run(spec, **kw):
-    sim, pools = FS.build(spec, **kw)
+    sim, pools = GF.build(spec, **kw)
     sim.run()
     assert isinstance(sim._graph, GeneralGraph) and "fault" in sim._station_refusal
     return sim, pools
-
-
-def _same(got, one, where=""):
-    assert set(got) == set(one)
-    for key in one:
-        assert np.array_equal(np.asarray(got[key]), np.asarray(one[key])), (where, key)
 
 
 def test_every_recorded_case_is_compared():
@@ -69,14 +55,14 @@ def test_every_recorded_case_is_compared():
 def test_named_fixture_equals_the_reference(name):
     spec = FS.FIXTURES[name]
     sim, pools = _run(spec)
-    _compare(spec, sim, pools, FR.get("case", spec))
+    _equals_the_recording(spec, sim, pools, FR.get("case", spec))
 
 
 @pytest.mark.parametrize("k", range(FS.N_RANDOM))
 def test_random_graph_with_faults_equals_the_reference(k):
     spec = FS.random_spec(k)
     sim, pools = _run(spec)
-    _compare(spec, sim, pools, FR.get("case", spec))
+    _equals_the_recording(spec, sim, pools, FR.get("case", spec))
 
 
 def test_the_reference_quirks_the_issue_lists():
@@ -98,29 +84,6 @@ def test_the_reference_quirks_the_issue_lists():
         assert lim._poll_scheduled and lim.queue_depth > 0 and lim._crashed is False
 
 
-def _engine(spec, **caps):
-    sim, pools = FS.build(spec)
-    g = sim.lowered()
-    auto = bool(spec.get("auto"))
-    end_ns, start_ns, sched, cancelled = sim._general_prepare(g, auto)
-    eng = GraphEngine(g.arrays, seed=spec["seed"], start_ns=start_ns, **caps)
-    for node, t, on, c in sim._general_faults(g):
-        eng.add_fault(node, t, on, c)
-    for node, t in sched:
-        eng.schedule(node, t)
-    return sim, pools, g, eng, end_ns, start_ns, cancelled
-
-
-def _engine_run(spec, ends_s, **caps):
-    """The spec on a GraphEngine of its own, run to every end of `ends_s` in turn; the results bound like Simulation.run() binds them."""
-    sim, pools, g, eng, end_ns, start_ns, cancelled = _engine(spec, **caps)
-    with eng:
-        for t in ends_s:
-            eng.run_until(start_ns + hs.Instant.from_seconds(t).nanoseconds)
-        sim._general_finish(g, eng, end_ns, cancelled, 0.0)
-    return sim, pools
-
-
 @pytest.mark.parametrize("name", FS.TRACED)
 def test_record_order_follows_the_trace(name):
     """The record log against the reference's full trace (time ns, kind, node, sort index of every popped Event): every Sink event and
@@ -128,7 +91,7 @@ def test_record_order_follows_the_trace(name):
     count of every kind equals the trace's."""
     spec = FS.FIXTURES[name]
     trace = FR.get("case", spec)["trace"]
-    sim, _pools, g, eng, end_ns, _start, _c = _engine(spec)
+    sim, _pools, g, eng, end_ns, _start, _c = FC.engine(spec)
     with eng:
         eng.run_until(end_ns)
         node, t, v = eng.records()
@@ -139,15 +102,8 @@ def test_record_order_follows_the_trace(name):
     assert n_fault == int((trace[:, 1] >= _FAULT_ON).sum()) >= 2
     kind = g.arrays.kind[node]
     arrivals = ((kind == N.NODE_RATE_LIMITER) & (v != N.LIMITER_DRAINED)) | (kind == N.NODE_SINK)
-    # the Events the reference popped while their target was crashed produced nothing: replay the flag along the trace
-    crashed, keep = set(), []
-    for row in trace:
-        if row[1] == _FAULT_ON:
-            crashed.add(int(row[2]))
-        elif row[1] == _FAULT_OFF:
-            crashed.discard(int(row[2]))
-        keep.append((row[1] == N.EV_KINDS or row[1] == N.EV_NAMES.index("sink")) and int(row[2]) not in crashed)
-    want = trace[np.array(keep)]
+    # the Events the reference popped while their target was crashed produced nothing
+    want = FC.live_rows(trace, (N.EV_KINDS, N.EV_NAMES.index("sink")))
     assert len(want) > 0 and np.array_equal(np.stack([t[arrivals], node[arrivals]], axis=1), want[:, [0, 2]])
 
 
@@ -155,18 +111,18 @@ def test_windows_equal_one_run():
     for name in ("server_crash_c2_bounded", "lockstep_tick_grid", "limiter_token_crash"):
         spec = FS.FIXTURES[name]
         ends = [0.7, 1.3, 1.3, 2.0, 2.6, 3.1, spec["end_s"]]             # (ends on the faults' own nanoseconds among them)
-        sim, pools = _engine_run(spec, ends)
-        _compare(spec, sim, pools, FR.get("case", spec))
+        sim, pools, _ = FC.engine_run(spec, ends)
+        _equals_the_recording(spec, sim, pools, FR.get("case", spec))
 
 
 def test_growth_from_capacities_of_one_equals_the_plain_run():
     """Heap, Request pool and record log start at one entry: a Request that a crash dropped without freeing would show here."""
     spec = FS._chain("growth", [FS.crash(["server", 0], 0.2, 0.5), FS.pause(["sink", 0], 0.7, 0.9)], rate=2000.0, mean=0.0004, end_s=1.2, seed=3)
-    grown_sim, grown_pools = _engine_run(spec, [spec["end_s"]], heap_capacity=1, request_capacity=1, record_capacity=1)
+    grown_sim, grown_pools, _ = FC.engine_run(spec, [spec["end_s"]], heap_capacity=1, request_capacity=1, record_capacity=1)
     plain_sim, plain_pools = _run(spec)
-    grown, plain = FS.results(spec, grown_sim, grown_pools), FS.results(spec, plain_sim, plain_pools)
+    grown, plain = GF.results(spec, grown_sim, grown_pools, "faults"), GF.results(spec, plain_sim, plain_pools, "faults")
     assert plain["generated"][0] - plain["accepted"][0] > 400 and plain["completed"][0] - plain["received"][0] > 200    # both drops happened
-    _same(grown, plain)
+    FC.same(grown, plain)
 
 
 def test_replicas_with_different_schedules_equal_single_runs():
@@ -176,7 +132,7 @@ def test_replicas_with_different_schedules_equal_single_runs():
     built = []
 
     def build_fn():
-        sim, pools = FS.build(specs[len(built)])
+        sim, pools = GF.build(specs[len(built)])
         built.append((sim, pools))
         return sim
 
@@ -185,9 +141,9 @@ def test_replicas_with_different_schedules_equal_single_runs():
     seen = set()
     for i, (sim, pools) in enumerate(built):
         assert isinstance(sim._graph, GeneralGraph)
-        got = FS.results(specs[i], sim, pools)
+        got = GF.results(specs[i], sim, pools, "faults")
         one_sim, one_pools = _run(specs[i], seed=700 + i)
-        _same(got, FS.results(specs[i], one_sim, one_pools), i)
+        FC.same(got, GF.results(specs[i], one_sim, one_pools, "faults"), i)
         seen.add((got["total_events"], tuple(got["crashed"].tolist())))
     assert len(seen) > 4
 
@@ -208,8 +164,8 @@ def test_600_chains_as_parts_equal_one_heap(grid):
     finally:
         S.MAX_PARTS = old
     assert one_sim._graph_parts == 1
-    got = FS.results(spec, sim, pools)
-    _same(got, FS.results(spec, one_sim, one_pools))
+    got = GF.results(spec, sim, pools, "faults")
+    FC.same(got, GF.results(spec, one_sim, one_pools, "faults"))
     assert got["fault_events"] > 200 and got["crashed"].sum() > 30
 
 
@@ -221,22 +177,22 @@ def test_flags_in_lds_and_in_hbm_give_the_same_result():
     ref = FR.get("case", spec)
     sim, pools = _run(spec)
     assert sim._graph.arrays.n > 192 and sim._graph_parts > 1
-    got = _compare(spec, sim, pools, ref)
+    got = _equals_the_recording(spec, sim, pools, ref)
     old, S.MAX_PARTS = S.MAX_PARTS, 1
     try:
         one_sim, one_pools = _run(spec)
     finally:
         S.MAX_PARTS = old
     assert one_sim._graph_parts == 1
-    _same(got, _compare(spec, one_sim, one_pools, ref))
+    FC.same(got, _equals_the_recording(spec, one_sim, one_pools, ref))
     # ... and a small graph alone on the large kernel (rows in LDS) against the side-by-side kernel (its own LDS rows)
     small = FS.FIXTURES["two_faults_two_entities"]
-    a_sim, a_pools = _engine_run(small, [small["end_s"]])
-    _compare(small, a_sim, a_pools, FR.get("case", small))
+    a_sim, a_pools, _ = FC.engine_run(small, [small["end_s"]])
+    _equals_the_recording(small, a_sim, a_pools, FR.get("case", small))
 
 
 def test_a_fault_after_the_first_run_is_a_state_error():
-    sim, _pools, _g, eng, end_ns, _s, _c = _engine(FS.FIXTURES["pause_sink"])
+    sim, _pools, _g, eng, end_ns, _s, _c = FC.engine(FS.FIXTURES["pause_sink"])
     with eng:
         eng.run_until(end_ns)
         with pytest.raises(N.EngineError) as e:

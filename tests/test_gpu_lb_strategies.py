@@ -14,33 +14,31 @@ import hashlib
 import numpy as np
 import pytest
 
+import family_checks as FC
 import happy_simulator_amd as hs
 import helpers as H
-import strategy_reference as SR
 import strategy_specs as SS
 from happy_simulator_amd import _native as N
 from happy_simulator_amd import lowering as L
 from happy_simulator_amd.graph_engine import GeneralGraph, GraphEngine
 from happy_simulator_amd.lb_engine import LbBackendArrays, LbSourceArrays, LoadBalancerEngine
+from recorded import STRATEGIES as SR
 
 pytestmark = pytest.mark.gpu
 
-RECORDED = ("total_events", "final_ns", "by_kind", "generated", "accepted", "dropped", "completed", "rejected", "depth", "active",
-            "total_service_s", "received", "routed", "packets_sent", "packets_dropped", "lb_stats", "lb_backend_total_requests",
-            "lb_backend_off", "lb_rr_index", "lb_current_weights", "sink_t_ns", "sink_latency_s", "sink_off", "probe_t_ns", "probe_v",
-            "probe_off")
+# everything recorded is compared but the trace (the fixtures' processing order: test_lb_strategies_host.py reads it)
+_NOT_COMPARED = {"trace"}
+_BY_KIND_SLICES = [("by_kind", N.EV_KINDS)]
 
 
-def _equal(got, want, keys, what):
-    for k in keys:
-        np.testing.assert_array_equal(got[k], want[k], err_msg=f"{what}: {k}")
+def _equals_the_recording(spec, sim, ents, what=None):
+    FC.compare(what or spec["name"], SS.results(spec, sim, ents), SR.get("case", spec), _NOT_COMPARED, _BY_KIND_SLICES)
 
 
 def _run_and_compare(spec):
-    rec = SR.get("case", spec)
     sim, ents = SS.build(spec)
     sim.run()
-    _equal(SS.results(spec, sim, ents), rec, RECORDED, spec["name"])
+    _equals_the_recording(spec, sim, ents)
     return sim, ents
 
 
@@ -56,7 +54,7 @@ def test_named_fixtures_equal_the_live_reference(name):
         assert isinstance(sim.lowered(), L.LbGraph)                    # the pipeline's shape ...
         sim2, ents2 = SS.build(spec)                                   # ... and the same fixture on the single-heap loop
         SS.force_single_heap(sim2, spec).run()
-        _equal(SS.results(spec, sim2, ents2), SR.get("case", spec), RECORDED, name + " (single heap)")
+        _equals_the_recording(spec, sim2, ents2, name + " (single heap)")
     for lb, lbs in zip(ents["lbs"], spec["lbs"]):
         if lbs["strategy"] == "wrr":
             assert lb.strategy._selections == lb.stats.requests_forwarded
@@ -87,7 +85,7 @@ def test_pipeline_shapes_agree_on_both_paths(k):
     assert took_pipeline == (spec["lbs"][0]["strategy"] in ("wrr", "ip_hash")), spec["name"]
     sim2, ents2 = SS.build(spec)
     SS.force_single_heap(sim2, spec).run()
-    _equal(SS.results(spec, sim2, ents2), SR.get("case", spec), RECORDED, spec["name"] + " (single heap)")
+    _equals_the_recording(spec, sim2, ents2, spec["name"] + " (single heap)")
 
 
 @pytest.mark.parametrize("strategy", ["wrr", "ip_hash"])
@@ -109,7 +107,7 @@ def test_pipeline_and_single_heap_agree_at_2048_by_2048(strategy):
     SS.force_single_heap(sim2, spec).run()
     a, b = SS.results(spec, sim, ents), SS.results(spec, sim2, ents2)
     assert a["total_events"] > 100_000
-    _equal(a, b, RECORDED + ("sink_created_ns",), spec["name"])
+    FC.same(a, b, spec["name"])
 
 
 def _pipeline_run(strategy, weights=None, S=32768, B=32768, rate=6.0, end_s=60.0, seed=42):
@@ -301,7 +299,7 @@ def test_replicas_of_a_least_connections_graph_equal_single_runs():
         alone.run()
         assert res.summary.total_events_processed == alone.summary.total_events_processed
         sim._summary = res.summary
-        _equal(SS.results(spec, sim, ents), SS.results(spec, alone, ents1), RECORDED + ("sink_created_ns",), f"replica {i}")
+        FC.same(SS.results(spec, sim, ents), SS.results(spec, alone, ents1), f"replica {i}")
         totals.add(res.summary.total_events_processed)
     assert len(totals) > 100
 
@@ -322,7 +320,7 @@ def test_disconnected_least_connections_graphs_run_as_parts(monkeypatch):
     one, ents1 = SS.build(spec)
     one.run()
     assert one._graph_parts == 1
-    _equal(SS.results(spec, sim, ents), SS.results(spec, one, ents1), RECORDED + ("sink_created_ns",), "parts against one heap")
+    FC.same(SS.results(spec, sim, ents), SS.results(spec, one, ents1), "parts against one heap")
     assert sum(lb.stats.requests_forwarded for lb in ents["lbs"]) > 500
 
 

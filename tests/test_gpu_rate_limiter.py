@@ -8,33 +8,25 @@ four policies (test_guard_cases; the recording holds the try it was found at), s
 import numpy as np
 import pytest
 
+import family_checks as FC
+import graph_family as GF
 import happy_simulator_amd as hs
-import rate_limiter_reference as RR
 import rate_limiter_specs as RS
 from happy_simulator_amd import _native as N
 from happy_simulator_amd.graph_engine import GeneralGraph, GraphEngine
+from recorded import RATE_LIMITER as RR
 
 pytestmark = pytest.mark.gpu
 
 # what the engine has no counterpart for (the reference heap's length, the wrapper's guard count) or what is compared in a form of
 # its own (by_kind: the engine reports the public fifteen kinds; the limiters' two per node; trace: test_record_order_follows_the_trace)
 _NOT_COMPARED = {"trace", "by_kind", "pending_events", "lim_guard_hits", "entity_summaries"}
+_BY_KIND_SLICES = [("by_kind", N.EV_KINDS), (lambda got: got["lim_events"].sum(axis=0), N.EV_KINDS + 2)]      # (the limiters' two kinds: per limiter)
 
 
-def _compare(spec, sim, pools, ref):
-    got = RS.results(spec, sim, pools)
-    for key, want in ref.items():
-        if key in _NOT_COMPARED:
-            continue
-        have = got[key]
-        if isinstance(want, np.ndarray):
-            assert np.array_equal(np.asarray(have), want), (spec["name"], key, np.asarray(have).tolist()[:12], want.tolist()[:12])
-        else:
-            assert have == want, (spec["name"], key, have, want)
-    np.testing.assert_array_equal(got["by_kind"], ref["by_kind"][:N.EV_KINDS])
-    assert got["lim_events"].sum(axis=0).tolist() == ref["by_kind"][N.EV_KINDS:].tolist()
-    # the event identity: the two internal kinds count in events_processed, not in events_by_kind
-    assert got["total_events"] == int(got["by_kind"].sum()) + int(got["lim_events"].sum())
+def _equals_the_recording(spec, sim, pools, ref):
+    got = GF.results(spec, sim, pools, "rate_limiter")
+    FC.compare(spec["name"], got, ref, _NOT_COMPARED, _BY_KIND_SLICES)
     es = sim.summary.entities
     assert {x.name: [es[x.name].entity_type, es[x.name].events_handled, es[x.name].queue_stats is None]
             for x in pools["limiter"]} == ref["entity_summaries"]
@@ -42,7 +34,7 @@ def _compare(spec, sim, pools, ref):
 
 
 def _run(spec, **kw):
-    sim, pools = RS.build(spec, **kw)
+    sim, pools = GF.build(spec, **kw)
     sim.run()
     assert isinstance(sim._graph, GeneralGraph)
     return sim, pools
@@ -52,7 +44,7 @@ def _run(spec, **kw):
 def test_named_fixture_equals_the_reference(name):
     spec = RS.FIXTURES[name]
     sim, pools = _run(spec)
-    got = _compare(spec, sim, pools, RR.get("case", spec))
+    got = _equals_the_recording(spec, sim, pools, RR.get("case", spec))
     if name.endswith("_constant"):
         kind = name[:-len("_constant")]
         assert tuple(got["lim_stats"][0, :4]) + (got["total_events"],) == RS.ISSUE_VALUES[kind]
@@ -67,7 +59,7 @@ def test_named_fixture_equals_the_reference(name):
         finally:
             S.MAX_PARTS = old
         assert one_sim._graph_parts == 1
-        _compare(spec, one_sim, one_pools, RR.get("case", spec))
+        _equals_the_recording(spec, one_sim, one_pools, RR.get("case", spec))
         # ... and on the side-by-side kernel, around ITS 48 LDS node rows (hs_graph_run_batch; test_graph_host.py pins the constant):
         # 6 heaps of 48 / 44 nodes (the last sizes whose rows stay in LDS), 5 heaps of 56 and 2 heaps of 140 (rows in HBM).  Every
         # heap holds all four policies; a fall-back to one heap would leave _graph_parts == 1
@@ -83,14 +75,14 @@ def test_named_fixture_equals_the_reference(name):
             finally:
                 S.MAX_PARTS = old
             assert few_sim._graph_parts == max_parts
-            _compare(spec, few_sim, few_pools, RR.get("case", spec))
+            _equals_the_recording(spec, few_sim, few_pools, RR.get("case", spec))
 
 
 @pytest.mark.parametrize("k", range(RS.N_RANDOM))
 def test_random_graph_with_limiters_equals_the_reference(k):
     spec = RS.random_spec(k)
     sim, pools = _run(spec)
-    _compare(spec, sim, pools, RR.get("case", spec))
+    _equals_the_recording(spec, sim, pools, RR.get("case", spec))
 
 
 @pytest.mark.parametrize("kind", RS.POLICIES)
@@ -101,21 +93,7 @@ def test_guard_cases(kind):
     spec = RS.guard_spec(kind, rec["tries"])
     assert int(rec["result"]["lim_guard_hits"].sum()) > 0
     sim, pools = _run(spec)
-    _compare(spec, sim, pools, rec["result"])
-
-
-def _engine_run(spec, ends_s, **caps):
-    """The spec on a GraphEngine of its own, run to every end of `ends_s` in turn; the results bound like Simulation.run() binds them."""
-    sim, pools = RS.build(spec)
-    g = sim.lowered()
-    end_ns, start_ns, sched, cancelled = sim._general_prepare(g, False)
-    with GraphEngine(g.arrays, seed=spec["seed"], start_ns=start_ns, **caps) as eng:
-        for node, t in sched:
-            eng.schedule(node, t)
-        for t in ends_s:
-            eng.run_until(start_ns + hs.Instant.from_seconds(t).nanoseconds)
-        sim._general_finish(g, eng, end_ns, cancelled, 0.0)
-    return sim, pools
+    _equals_the_recording(spec, sim, pools, rec["result"])
 
 
 _TRACED = [n for n in sorted(RS.FIXTURES) if len(RS.FIXTURES[n]["servers"]) <= 16]      # (the generator's own rule)
@@ -129,20 +107,15 @@ def test_record_order_follows_the_trace(name):
     at a poll of its limiter, in order."""
     spec = RS.FIXTURES[name]
     trace = RR.get("case", spec)["trace"]
-    sim, _pools = RS.build(spec)
-    g = sim.lowered()
-    auto = bool(spec.get("auto"))
-    end_ns, start_ns, sched, _cancelled = sim._general_prepare(g, auto)
-    with GraphEngine(g.arrays, seed=spec["seed"], start_ns=start_ns) as eng:
-        for node, t in sched:
-            eng.schedule(node, t)
+    _sim, _pools, g, eng, end_ns, _start, _c = FC.engine(spec)
+    with eng:
         eng.run_until(end_ns)
         node, t, v = eng.records()
         polls = {int(i): eng.limiter(int(i))["polls_handled"] for i in np.nonzero(g.arrays.kind == N.NODE_RATE_LIMITER)[0]}
     kind = g.arrays.kind[node]
     lim = kind == N.NODE_RATE_LIMITER
     arrivals = (lim & (v != N.LIMITER_DRAINED)) | (kind == N.NODE_SINK)
-    want = trace[(trace[:, 1] == N.EV_KINDS) | (trace[:, 1] == N.EV_NAMES.index("sink"))]
+    want = FC.live_rows(trace, (N.EV_KINDS, N.EV_NAMES.index("sink")))
     assert len(want) > 0 and np.array_equal(np.stack([t[arrivals], node[arrivals]], axis=1), want[:, [0, 2]])
     poll_rows = trace[trace[:, 1] == N.EV_KINDS + 1]
     assert {int(i): int((poll_rows[:, 2] == i).sum()) for i in polls} == polls
@@ -173,10 +146,10 @@ def test_the_kernels_window_start_is_pythons():
 def test_windows_equal_one_run_and_the_reference():
     spec = RS.FIXTURES["windows"]
     ref = RR.get("case", spec)
-    sim, pools = _engine_run(spec, list(spec["windows"]) + [spec["end_s"]])
-    got = _compare(spec, sim, pools, ref)
+    sim, pools, _ = FC.engine_run(spec, list(spec["windows"]) + [spec["end_s"]])
+    got = _equals_the_recording(spec, sim, pools, ref)
     one_sim, one_pools = _run({k: v for k, v in spec.items() if k != "windows"})
-    one = RS.results(spec, one_sim, one_pools)
+    one = GF.results(spec, one_sim, one_pools, "rate_limiter")
     for key in got:
         assert np.array_equal(np.asarray(got[key]), np.asarray(one[key])), key
 
@@ -188,9 +161,9 @@ def _overload_spec():
 
 def test_growth_from_capacities_of_one_equals_the_plain_run():
     spec = _overload_spec()
-    grown_sim, grown_pools = _engine_run(spec, [spec["end_s"]], heap_capacity=1, request_capacity=1, record_capacity=1)
+    grown_sim, grown_pools, _ = FC.engine_run(spec, [spec["end_s"]], heap_capacity=1, request_capacity=1, record_capacity=1)
     plain_sim, plain_pools = _run(spec)
-    grown, plain = RS.results(spec, grown_sim, grown_pools), RS.results(spec, plain_sim, plain_pools)
+    grown, plain = GF.results(spec, grown_sim, grown_pools, "rate_limiter"), GF.results(spec, plain_sim, plain_pools, "rate_limiter")
     assert plain["lim_stats"][0, 4] > 2000                        # the queue outgrew the initial pool (1 024 + 4 n Requests)
     for key in plain:
         assert np.array_equal(np.asarray(grown[key]), np.asarray(plain[key])), key
@@ -201,7 +174,7 @@ def test_replicas_equal_single_runs():
     built = []
 
     def build_fn():
-        sim, pools = RS.build(spec)
+        sim, pools = GF.build(spec)
         built.append((sim, pools))
         return sim
 
@@ -209,12 +182,12 @@ def test_replicas_equal_single_runs():
     assert len(results) == 64
     for i, (sim, pools) in enumerate(built):
         assert isinstance(sim._graph, GeneralGraph)
-        got = RS.results(spec, sim, pools)
+        got = GF.results(spec, sim, pools, "rate_limiter")
         one_sim, one_pools = _run(spec, seed=500 + i)
-        one = RS.results(spec, one_sim, one_pools)
+        one = GF.results(spec, one_sim, one_pools, "rate_limiter")
         for key in one:
             assert np.array_equal(np.asarray(got[key]), np.asarray(one[key])), (i, key)
-    assert len({RS.results(spec, s, p)["total_events"] for s, p in built}) > 8       # (the seeds matter)
+    assert len({GF.results(spec, s, p, "rate_limiter")["total_events"] for s, p in built}) > 8       # (the seeds matter)
 
 
 def _chains_spec(n, source, name):
@@ -240,7 +213,7 @@ def test_600_chains_as_parts_equal_one_heap(source):
     finally:
         S.MAX_PARTS = old
     assert one_sim._graph_parts == 1
-    got, one = RS.results(spec, sim, pools), RS.results(spec, one_sim, one_pools)
+    got, one = GF.results(spec, sim, pools, "rate_limiter"), GF.results(spec, one_sim, one_pools, "rate_limiter")
     for key in one:
         assert np.array_equal(np.asarray(got[key]), np.asarray(one[key])), key
     assert got["lim_stats"][:, 2].sum() > 100 and got["total_events"] == int(got["by_kind"].sum()) + int(got["lim_events"].sum())
@@ -260,7 +233,7 @@ def test_auto_terminating_run_ends_where_the_reference_ends():
 
 
 def test_a_limiter_without_a_policy_is_a_state_error():
-    sim, _pools = RS.build(RS.FIXTURES["token_constant"])
+    sim, _pools = GF.build(RS.FIXTURES["token_constant"])
     a = sim.lowered().arrays
     a.lim_policy = None                                            # (the handle is created, no policy follows)
     with GraphEngine(a, seed=1) as eng:
@@ -273,7 +246,7 @@ def test_the_max_events_refusal_names_a_fixed_window_as_the_likely_cause():
     """The run-time refusal at max_events says what a user can act on: with a FixedWindowPolicy in the graph it names the window
     that is no binary fraction (the reference's own livelock); without one the text is what it was."""
     for fixture, named in (("fixed_constant", True), ("token_constant", False)):
-        sim, _pools = RS.build(RS.FIXTURES[fixture])
+        sim, _pools = GF.build(RS.FIXTURES[fixture])
         with GraphEngine(sim.lowered().arrays, seed=1, max_events=50) as eng:
             with pytest.raises(N.EngineError, match="max_events") as e:
                 eng.run_until(5 * 10 ** 9)

@@ -7,11 +7,13 @@ import numpy as np
 import pytest
 
 import fault_specs as FS
-import resilience_reference as XR
+import family_checks as FC
+import graph_family as GF
 import resilience_specs as XS
 import happy_simulator_amd as hs
 from happy_simulator_amd import _native as N
 from happy_simulator_amd.graph_engine import GeneralGraph, GraphEngine
+from recorded import RESILIENCE as XR
 
 pytestmark = pytest.mark.gpu
 
@@ -19,39 +21,20 @@ pytestmark = pytest.mark.gpu
 # of its own (by_kind: the engine reports the public fifteen kinds, the internal ones per graph; trace: test_record_order_follows_the_trace)
 _NOT_COMPARED = {"trace", "by_kind", "pending_events", "time_travel"}
 _FIRST_HC, _FIRST_WRAPPER = N.EV_KINDS + 4, N.EV_KINDS + 7
+_BY_KIND_SLICES = [("by_kind", N.EV_KINDS), ("internal_by_kind", _FIRST_HC), ("health_by_kind", _FIRST_WRAPPER), ("resilience_by_kind", _FIRST_WRAPPER + 6)]
 
 
-def _compare(spec, sim, pools, ref):
-    got = XS.results(spec, sim, pools)
-    for key, want in ref.items():
-        if key in _NOT_COMPARED:
-            continue
-        have = got[key]
-        if isinstance(want, np.ndarray):
-            assert np.array_equal(np.asarray(have), want), (spec["name"], key, np.asarray(have).tolist()[:16], want.tolist()[:16])
-        else:
-            assert have == want, (spec["name"], key, have, want)
-    np.testing.assert_array_equal(got["by_kind"], ref["by_kind"][:N.EV_KINDS])
-    np.testing.assert_array_equal(got["internal_by_kind"], ref["by_kind"][N.EV_KINDS:_FIRST_HC])
-    np.testing.assert_array_equal(got["health_by_kind"], ref["by_kind"][_FIRST_HC:_FIRST_WRAPPER])
-    np.testing.assert_array_equal(got["resilience_by_kind"], ref["by_kind"][_FIRST_WRAPPER:])
-    # the event identity: the internal kinds count in events_processed, not in events_by_kind
-    assert got["total_events"] == (int(got["by_kind"].sum()) + int(got["internal_by_kind"].sum()) + int(got["health_by_kind"].sum()) +
-                                   int(got["resilience_by_kind"].sum()))
+def _equals_the_recording(spec, sim, pools, ref):
+    got = GF.results(spec, sim, pools, "resilience")
+    FC.compare(spec["name"], got, ref, _NOT_COMPARED, _BY_KIND_SLICES)
     return got
 
 
 def _run(spec, **kw):
-    sim, pools = XS.build(spec, **kw)
+    sim, pools = GF.build(spec, **kw)
     sim.run()
     assert isinstance(sim._graph, GeneralGraph) and "Bulkhead or TimeoutWrapper" in sim._station_refusal
     return sim, pools
-
-
-def _same(got, one, where=""):
-    assert set(got) == set(one)
-    for key in one:
-        assert np.array_equal(np.asarray(got[key]), np.asarray(one[key])), (where, key)
 
 
 def test_every_recorded_case_is_compared():
@@ -69,14 +52,14 @@ def test_every_recorded_case_is_compared():
 def test_named_fixture_equals_the_reference(name):
     spec = XS.FIXTURES[name]
     sim, pools = _run(spec)
-    _compare(spec, sim, pools, XR.get("case", spec))
+    _equals_the_recording(spec, sim, pools, XR.get("case", spec))
 
 
 @pytest.mark.parametrize("k", range(XS.N_RANDOM))
 def test_random_graph_equals_the_reference(k):
     spec = XS.random_spec(k)
     sim, pools = _run(spec)
-    _compare(spec, sim, pools, XR.get("case", spec))
+    _equals_the_recording(spec, sim, pools, XR.get("case", spec))
 
 
 def test_what_the_issue_says_about_the_reference():
@@ -93,29 +76,6 @@ def test_what_the_issue_says_about_the_reference():
     assert t.in_flight_count > 0 and t._crashed is True and t._next_request_id == t.stats.total_requests
 
 
-def _engine(spec, **caps):
-    sim, pools = XS.build(spec)
-    g = sim.lowered()
-    end_ns, start_ns, sched, cancelled = sim._general_prepare(g, bool(spec.get("auto")))
-    eng = GraphEngine(g.arrays, seed=spec["seed"], start_ns=start_ns, **caps)
-    for node, t, on, c in sim._general_faults(g):
-        eng.add_fault(node, t, on, c)
-    for node, t in sched:
-        eng.schedule(node, t)
-    return sim, pools, g, eng, end_ns, start_ns, cancelled
-
-
-def _engine_run(spec, ends_s, **caps):
-    """The spec on a GraphEngine of its own, run to every end of `ends_s` in turn; the results bound like Simulation.run() binds them."""
-    sim, pools, g, eng, end_ns, start_ns, cancelled = _engine(spec, **caps)
-    with eng:
-        for t in ends_s:
-            eng.run_until(start_ns + hs.Instant.from_seconds(t).nanoseconds)
-        tables = [eng.wrapper(int(i))["table_capacity"] for i in np.nonzero(g.arrays.kind == N.NODE_TIMEOUT_WRAPPER)[0]]
-        sim._general_finish(g, eng, end_ns, cancelled, 0.0)
-    return sim, pools, tables
-
-
 @pytest.mark.parametrize("name", XS.TRACED)
 def test_record_order_follows_the_trace(name):
     """The record log against the reference's full trace (time ns, kind, node, sort index of every popped Event): every Sink event that
@@ -123,7 +83,7 @@ def test_record_order_follows_the_trace(name):
     trace's."""
     spec = XS.FIXTURES[name]
     trace = XR.get("case", spec)["trace"]
-    sim, _pools, g, eng, end_ns, _start, _c = _engine(spec)
+    sim, _pools, g, eng, end_ns, _start, _c = FC.engine(spec)
     with eng:
         eng.run_until(end_ns)
         node, t, _v = eng.records()
@@ -133,16 +93,17 @@ def test_record_order_follows_the_trace(name):
     assert by_kind == [int((trace[:, 1] == k).sum()) for k in range(N.EV_KINDS)]
     assert internal.tolist() == [int((trace[:, 1] == N.EV_KINDS + k).sum()) for k in range(4)]
     assert events.tolist() == [int((trace[:, 1] == _FIRST_WRAPPER + k).sum()) for k in range(6)] and events.sum() > 0
-    crashed, keep = set(), []
-    for row in trace:
-        if row[1] == N.EV_KINDS + 2:
-            crashed.add(int(row[2]))
-        elif row[1] == N.EV_KINDS + 3:
-            crashed.discard(int(row[2]))
-        keep.append(row[1] == N.EV_NAMES.index("sink") and int(row[2]) not in crashed)
-    want = trace[np.array(keep)]
+    want = FC.live_rows(trace)
     at_sink = g.arrays.kind[node] == N.NODE_SINK
     assert len(want) > 0 and np.array_equal(np.stack([t[at_sink], node[at_sink]], axis=1), want[:, [0, 2]])
+
+
+def _run_to_ends_with_tables(spec, ends_s, **caps):
+    """FC.engine_run and every TimeoutWrapper's table capacity at the end."""
+    def tables(eng, g):
+        return [eng.wrapper(int(i))["table_capacity"] for i in np.nonzero(g.arrays.kind == N.NODE_TIMEOUT_WRAPPER)[0]]
+
+    return FC.engine_run(spec, ends_s, read=tables, **caps)
 
 
 def test_windows_equal_one_run():
@@ -150,8 +111,8 @@ def test_windows_equal_one_run():
                  "link_delay_equals_max_wait_time"):
         spec = XS.FIXTURES[name]
         ends = [0.25, 0.5, 0.5, 1.2, 1.9, 3.0000001, spec["end_s"]]          # 7 uneven windows, ends on tie and fault nanoseconds among them
-        sim, pools, _ = _engine_run(spec, ends)
-        _compare(spec, sim, pools, XR.get("case", spec))
+        sim, pools, _ = _run_to_ends_with_tables(spec, ends)
+        _equals_the_recording(spec, sim, pools, XR.get("case", spec))
 
 
 def test_in_flight_table_grown_from_one_place_equals_the_reference():
@@ -159,12 +120,12 @@ def test_in_flight_table_grown_from_one_place_equals_the_reference():
     doubles the table (the ids in flight move with it) and the run goes on -- with leaked ids, a crash and late responses on the way."""
     for name in ("timeout_response_after_the_wrappers_restart", "timeout_wrapper_crash_without_restart", "probes_on_the_four_metrics"):
         spec = XS.FIXTURES[name]
-        sim, pools, tables = _engine_run(spec, [spec["end_s"]], table_capacity=1)
+        sim, pools, tables = _run_to_ends_with_tables(spec, [spec["end_s"]], table_capacity=1)
         assert tables and min(tables) >= 4, tables                          # (grown from one place)
-        got = _compare(spec, sim, pools, XR.get("case", spec))
-        roomy_sim, roomy_pools, roomy_tables = _engine_run(spec, [spec["end_s"]], table_capacity=4096)
+        got = _equals_the_recording(spec, sim, pools, XR.get("case", spec))
+        roomy_sim, roomy_pools, roomy_tables = _run_to_ends_with_tables(spec, [spec["end_s"]], table_capacity=4096)
         assert roomy_tables == [4096] * len(tables)
-        _same(got, XS.results(spec, roomy_sim, roomy_pools), name)
+        FC.same(got, GF.results(spec, roomy_sim, roomy_pools, "resilience"), name)
 
 
 def test_growth_from_capacities_of_one_equals_a_run_with_room():
@@ -173,12 +134,12 @@ def test_growth_from_capacities_of_one_equals_a_run_with_room():
     spec = XS._g("growth_under_a_backlog", [XS.bh(["link", 0], 3, 400, 2.0), XS.tw(["link", 1], 0.4)], servers=[XS.srv(0.2, cap=None)],
                  links=[XS.link(0, 0.3, "exp", 0.2), XS.link(0, 0.1, "exp", 0.3)], sources=[XS.src(["wrapper", 0], 100.0), XS.src(["wrapper", 1], 100.0)],
                  faults=[XS.pause(["link", 0], 1.0, 1.3)], end_s=4.0, seed=5)
-    grown_sim, grown_pools, tables = _engine_run(spec, [spec["end_s"]], heap_capacity=1, request_capacity=1, record_capacity=1, table_capacity=1)
-    roomy_sim, roomy_pools, _ = _engine_run(spec, [spec["end_s"]], heap_capacity=1 << 16, request_capacity=1 << 16, record_capacity=1 << 16,
-                                            table_capacity=1 << 12)
-    grown, roomy = XS.results(spec, grown_sim, grown_pools), XS.results(spec, roomy_sim, roomy_pools)
+    grown_sim, grown_pools, tables = _run_to_ends_with_tables(spec, [spec["end_s"]], heap_capacity=1, request_capacity=1, record_capacity=1, table_capacity=1)
+    roomy_sim, roomy_pools, _ = _run_to_ends_with_tables(spec, [spec["end_s"]], heap_capacity=1 << 16, request_capacity=1 << 16, record_capacity=1 << 16,
+                                                             table_capacity=1 << 12)
+    grown, roomy = GF.results(spec, grown_sim, grown_pools, "resilience"), GF.results(spec, roomy_sim, roomy_pools, "resilience")
     assert roomy["wrap_stats"][0, 6] > 100 and roomy["wrap_stats"][1, 2] > 10 and roomy["depth"].sum() > 100 and tables[0] >= 32
-    _same(grown, roomy)
+    FC.same(grown, roomy)
 
 
 def test_64_replicas_equal_64_single_runs():
@@ -188,7 +149,7 @@ def test_64_replicas_equal_64_single_runs():
     built = []
 
     def build_fn():
-        sim, pools = XS.build(specs[len(built)])
+        sim, pools = GF.build(specs[len(built)])
         built.append((sim, pools))
         return sim
 
@@ -197,9 +158,9 @@ def test_64_replicas_equal_64_single_runs():
     seen = set()
     for i, (sim, pools) in enumerate(built):
         assert isinstance(sim._graph, GeneralGraph) and sim._graph.arrays.has_wrappers
-        got = XS.results(specs[i], sim, pools)
+        got = GF.results(specs[i], sim, pools, "resilience")
         one_sim, one_pools = _run(specs[i], seed=700 + i)
-        _same(got, XS.results(specs[i], one_sim, one_pools), i)
+        FC.same(got, GF.results(specs[i], one_sim, one_pools, "resilience"), i)
         seen.add((got["total_events"], tuple(got["wrap_stats"].ravel().tolist())))
     assert len(seen) > 48
 
@@ -218,8 +179,8 @@ def test_32_groups_as_parts_equal_one_heap():
     finally:
         S.MAX_PARTS = old
     assert one_sim._graph_parts == 1
-    got = XS.results(spec, sim, pools)
-    _same(got, XS.results(spec, one_sim, one_pools))
+    got = GF.results(spec, sim, pools, "resilience")
+    FC.same(got, GF.results(spec, one_sim, one_pools, "resilience"))
     assert (got["wrap_stats"][0::2, 7] > 0).all() and (got["wrap_stats"][1::2, 2] > 0).all()      # permits leaked, requests timed out
 
 
@@ -234,7 +195,7 @@ def test_a_wrapper_free_handle_in_a_batch_with_a_wrapper_handle():
 
     def build_fn():
         k = len(built)
-        sim, pools = XS.build(wrapped[k]) if k < 2 else RS.build(plain_spec)
+        sim, pools = GF.build(wrapped[k]) if k < 2 else GF.build(plain_spec)
         built.append((sim, pools))
         return sim
 
@@ -242,17 +203,17 @@ def test_a_wrapper_free_handle_in_a_batch_with_a_wrapper_handle():
     assert len(results) == 3
     for i in range(2):
         one_sim, one_pools = _run(wrapped[i], seed=40 + i)
-        _same(XS.results(wrapped[i], *built[i]), XS.results(wrapped[i], one_sim, one_pools), i)
+        FC.same(GF.results(wrapped[i], *built[i], "resilience"), GF.results(wrapped[i], one_sim, one_pools, "resilience"), i)
     sim, pools = built[2]
     assert not sim._graph.arrays.has_wrappers and not sim._faults
-    one_sim, one_pools = RS.build(plain_spec, seed=42)
+    one_sim, one_pools = GF.build(plain_spec, seed=42)
     one_sim.run()
-    _same(RS.results(plain_spec, sim, pools), RS.results(plain_spec, one_sim, one_pools), "plain")
+    FC.same(GF.results(plain_spec, sim, pools, "rate_limiter"), GF.results(plain_spec, one_sim, one_pools, "rate_limiter"), "plain")
     assert sim.summary.total_events_processed == one_sim.summary.total_events_processed
 
 
 def test_a_wrapper_node_that_was_never_configured_is_a_state_error():
-    sim, _pools = XS.build(XS.FIXTURES["bulkhead_link_constant"])
+    sim, _pools = GF.build(XS.FIXTURES["bulkhead_link_constant"])
     g = sim.lowered()
     g.arrays.wrap_params = None                                                # (the handle is created without the wrapper call)
     with GraphEngine(g.arrays, seed=1) as eng:
@@ -262,7 +223,7 @@ def test_a_wrapper_node_that_was_never_configured_is_a_state_error():
 
 
 def test_wrapper_parameters_after_the_first_run_are_a_state_error():
-    sim, _pools, g, eng, end_ns, _s, _c = _engine(XS.FIXTURES["bulkhead_link_constant"])
+    sim, _pools, g, eng, end_ns, _s, _c = FC.engine(XS.FIXTURES["bulkhead_link_constant"])
     node = int(np.nonzero(g.arrays.kind == N.NODE_BULKHEAD)[0][0])
     with eng:
         with pytest.raises(N.EngineError) as e:                                # a wrapper is configured once
@@ -277,7 +238,7 @@ def test_wrapper_parameters_after_the_first_run_are_a_state_error():
 def test_the_engine_refuses_what_the_host_refuses():
     """hs_graph_create / hs_graph_set_wrapper on hand-made arrays: a wrapper in front of a wrapper through a link, max_concurrent one
     above the bound, the reference's own ValueErrors."""
-    sim, _pools = XS.build(XS.FIXTURES["bulkhead_two_links"])
+    sim, _pools = GF.build(XS.FIXTURES["bulkhead_two_links"])
     g = sim.lowered()
     a = g.arrays
     node = int(np.nonzero(a.kind == N.NODE_BULKHEAD)[0][0])

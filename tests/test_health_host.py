@@ -6,11 +6,12 @@ import dataclasses
 import numpy as np
 import pytest
 
-import health_reference as HR
+import graph_family as GF
 import health_specs as HS
 import happy_simulator_amd as hs
 from happy_simulator_amd import _native as N
 from happy_simulator_amd.graph_engine import GeneralGraph
+from recorded import HEALTH as HR
 
 
 def _pool(strategy=None, n=2):
@@ -78,7 +79,7 @@ def test_the_lowering_accepts_every_spec():
     assert len(specs) == len(HS.FIXTURES) + HS.N_RANDOM
     for spec in specs:
         HR.get("case", spec)                                   # (recorded: a missing one raises by name)
-        sim, pools = HS.build(spec)
+        sim, pools = GF.build(spec)
         g = sim.lowered()
         assert isinstance(g, GeneralGraph) and g.arrays.has_health, spec["name"]
         a = g.arrays
@@ -177,7 +178,7 @@ def test_parts_keep_a_checker_with_its_load_balancer():
     from happy_simulator_amd.graph_engine import split_parts
 
     spec = HS.groups_spec(8)
-    sim, pools = HS.build(spec)
+    sim, pools = GF.build(spec)
     g = sim.lowered()
     parts = split_parts(g.arrays)
     assert len(parts) == 8

@@ -10,11 +10,11 @@ import numpy as np
 import pytest
 
 import happy_simulator_amd as hs
-import strategy_reference as SR
 import strategy_specs as SS
 from happy_simulator_amd import _native as N
 from happy_simulator_amd import lowering as L
 from happy_simulator_amd.graph_engine import GeneralGraph, lower_general, split_parts
+from recorded import STRATEGIES as SR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -209,8 +209,8 @@ def test_every_spec_has_a_recording():
     assert len(SS.FIXTURES) >= 8 and SS.N_RANDOM >= 150
     with pytest.raises(KeyError, match="no recorded reference result for case"):
         SR.get("case", dict(SS.FIXTURES["lc_poisson"], seed=-1))
-    for path in os.listdir(SR.REC_DIR):
-        assert os.path.getsize(os.path.join(SR.REC_DIR, path)) <= SR.PART_BYTES, path
+    for path in os.listdir(SR.rec_dir):
+        assert os.path.getsize(os.path.join(SR.rec_dir, path)) <= SR.part_bytes, path
 
 
 def test_recorded_least_connections_follow_min_active_on_the_trace():

@@ -8,11 +8,12 @@ import re
 import numpy as np
 import pytest
 
+import graph_family as GF
 import happy_simulator_amd as hs
-import rate_limiter_reference as RR
 import rate_limiter_specs as RS
 from happy_simulator_amd import _native as N
 from happy_simulator_amd.graph_engine import GeneralGraph, lower_general, split_parts
+from recorded import RATE_LIMITER as RR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -108,7 +109,7 @@ def test_the_kernels_floor_division_is_pythons():
 
 
 def _lowered(name):
-    sim, pools = RS.build(RS.FIXTURES[name])
+    sim, pools = GF.build(RS.FIXTURES[name])
     g = sim.lowered()
     assert isinstance(g, GeneralGraph)
     return sim, pools, g
@@ -162,7 +163,7 @@ def test_parts_carry_the_limiters():
                 servers=[dict(c["servers"][0], out=["sink", i]) for i, c in enumerate(chains)],
                 limiters=[dict(c["limiters"][0], out=["server", i]) for i, c in enumerate(chains)],
                 sources=[dict(c["sources"][0], to=["limiter", i]) for i, c in enumerate(chains)])
-    sim, _pools = RS.build(spec)
+    sim, _pools = GF.build(spec)
     g = sim.lowered()
     parts = split_parts(g.arrays)
     assert len(parts) == 4

@@ -8,11 +8,12 @@ import subprocess
 import numpy as np
 import pytest
 
-import resilience_reference as XR
+import graph_family as GF
 import resilience_specs as XS
 import happy_simulator_amd as hs
 from happy_simulator_amd import _native as N
 from happy_simulator_amd.graph_engine import GeneralGraph, split_parts
+from recorded import RESILIENCE as XR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _BH_ERRORS = (dict(max_concurrent=0), dict(max_concurrent=-2), dict(max_concurrent=1, max_wait_queue=-1), dict(max_concurrent=1, max_wait_time=0),
@@ -65,7 +66,7 @@ def test_the_lowering_accepts_every_spec():
     """Every recorded spec is one the product takes; a wrapper sends the Simulation to the single-heap loop whatever its shape."""
     for spec in XS.all_specs():
         XR.get("case", spec)                                   # (recorded: no case is left out)
-        sim, pools = XS.build(spec)
+        sim, pools = GF.build(spec)
         g = sim.lowered()
         assert isinstance(g, GeneralGraph) and g.arrays.has_wrappers and "Bulkhead or TimeoutWrapper" in sim._station_refusal, spec["name"]
         a = g.arrays
@@ -76,17 +77,17 @@ def test_the_lowering_accepts_every_spec():
 
 
 def test_the_lowered_arrays_of_three_fixtures():
-    sim, pools = XS.build(XS.FIXTURES["paused_server_leaks_permits"])      # src, srv0, sink0, bh0
+    sim, pools = GF.build(XS.FIXTURES["paused_server_leaks_permits"])      # src, srv0, sink0, bh0
     a = sim.lowered().arrays
     assert a.kind.tolist() == [N.NODE_SOURCE, N.NODE_SERVER, N.NODE_SINK, N.NODE_BULKHEAD] and a.target.tolist() == [3, 2, -1, 1]
     assert a.wrap_params[3].tolist() == [4.0, 3.0, 0.5, 0.0, 0.0] and not a.wrap_params[:3].any()
     assert len(sim._faults) == 2 and sim._general_faults(sim.lowered())[0][:3] == (1, 2 * 10 ** 9, True)
-    sim, pools = XS.build(XS.FIXTURES["timeout_two_links"])                # src, srv0, link0, link1, sink0, tw0
+    sim, pools = GF.build(XS.FIXTURES["timeout_two_links"])                # src, srv0, link0, link1, sink0, tw0
     a = sim.lowered().arrays
     assert a.kind.tolist() == [N.NODE_SOURCE, N.NODE_SERVER, N.NODE_LINK, N.NODE_LINK, N.NODE_SINK, N.NODE_TIMEOUT_WRAPPER]
     assert a.target.tolist() == [5, 4, 3, 1, -1, 2] and a.wrap_params[5].tolist() == [0.0, 0.0, 0.0, 0.1, 0.0]
     assert a.rt_cnt.sum() == 0 and len(a.rt_targets) == 0                  # (the in-flight tables are the engine's: no router slots)
-    sim, pools = XS.build(XS.FIXTURES["probes_on_the_four_metrics"])       # 2 src, 4 probes, srv0, link0, link1, sink0, bh0, tw1
+    sim, pools = GF.build(XS.FIXTURES["probes_on_the_four_metrics"])       # 2 src, 4 probes, srv0, link0, link1, sink0, bh0, tw1
     a = sim.lowered().arrays
     assert a.kind[2:6].tolist() == [N.NODE_PROBE] * 4 and a.probe_metric[2:6].tolist() == [8, 9, 10, 11] and a.target[2:6].tolist() == [10, 10, 10, 11]
     assert a.probe_interval_s[2:6].tolist() == [0.1, 0.1, 0.25, 0.1]
@@ -172,7 +173,7 @@ def test_parts_keep_a_wrapper_with_its_target_and_leave_the_rest_without():
     spec = XS.groups_spec(4)
     spec["servers"].append(XS.srv(0.05, out=None))
     spec["sources"].append(XS.src(4, 9.0))                                  # a fifth component without any wrapper
-    sim, pools = XS.build(spec)
+    sim, pools = GF.build(spec)
     parts = split_parts(sim.lowered().arrays)
     assert len(parts) == 5
     with_w = [b for _ids, _pos, b in parts if b.has_wrappers]
