@@ -28,6 +28,7 @@ from .entities import (FixedWindowPolicy, LeakyBucketPolicy, RateLimitedEntity, 
 from .entities import BackendHealthState, HealthChecker, HealthCheckStats  # noqa: F401
 from .entities import Bulkhead, BulkheadStats, TimeoutStats, TimeoutWrapper  # noqa: F401
 from .entities import Client, ClientStats, DecorrelatedJitter, ExponentialBackoff, FixedRetry, NoRetry  # noqa: F401
+from .entities import (BatchProcessor, BatchProcessorStats, ConveyorBelt, ConveyorStats, GateController, GateStats)  # noqa: F401
 from .faults import CrashNode, FaultHandle, FaultSchedule, FaultStats, PauseNode  # noqa: F401
 from .lowering import UnsupportedTopology  # noqa: F401
 from .parallel import (ParallelResult, ParallelRunner, ParallelSimulation, ParallelSimulationSummary,  # noqa: F401

@@ -44,6 +44,9 @@ NODE_CLIENT = 11
 CLIENT_MAX_ATTEMPTS = 65536                                 # include/hs_engine.h HS_CLIENT_MAX_ATTEMPTS
 CLIENT_COUNTERS = 7                                         # HS_CLIENT_COUNTERS
 CLIENT_MAX_REQUEST_ID = 1 << 30                             # a request_id is a positive int below this (the key's low 30 bits)
+NODE_BATCH_PROCESSOR, NODE_CONVEYOR, NODE_GATE = 12, 13, 14
+FLOW_MAX_ITEMS = 1 << 20                                    # include/hs_engine.h HS_FLOW_MAX_ITEMS: batch_size / a bounded gate queue
+FLOW_COUNTERS, FLOW_KINDS = 8, 8                            # HS_FLOW_COUNTERS, HS_FLOW_KINDS
 # hs_limiter_policy / hs_limiter_outcome (the third column of a limiter's records)
 LIMITER_TOKEN_BUCKET, LIMITER_LEAKY_BUCKET, LIMITER_SLIDING_WINDOW, LIMITER_FIXED_WINDOW, LIMITER_NONE = 0, 1, 2, 3, 255
 LIMITER_FORWARDED, LIMITER_QUEUED, LIMITER_DROPPED, LIMITER_DRAINED = 0, 1, 2, 3
@@ -56,6 +59,8 @@ PROBE_METRICS = {"depth": 0, "active_requests": 1, "stats_accepted": 2, "stats_d
 # ... of a Bulkhead / TimeoutWrapper (general graphs only; a Bulkhead's queue_depth is its own metric)
 PROBE_WRAPPER_METRICS = {"active_count": 8, "queue_depth": 9, "available_permits": 10, "in_flight_count": 11}
 PROBE_CLIENT_METRICS = {"in_flight_count": 12}              # ... of a Client
+# ... of a BatchProcessor / ConveyorBelt / GateController (a gate's queue_depth is its own metric)
+PROBE_FLOW_METRICS = {"buffer_depth": 13, "items_in_transit": 14, "queue_depth": 15}
 PROBE_NONE = 255
 # hs_engine_run_path / hs_lb_run_path: which side of the host-side gates the last run landed on (include/hs_engine.h)
 RUN_ONE_LANE, RUN_ONE_LANE_UNI, RUN_WIDE, RUN_WAVE, RUN_TANDEM, RUN_SINGLE_HEAP = 1, 2, 4, 8, 16, 32
@@ -522,6 +527,12 @@ def lib():
     L.hs_graph_schedule_client.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32]
     L.hs_graph_get_client.restype = C.c_int
     L.hs_graph_get_client.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.hs_graph_set_flow.restype = C.c_int
+    L.hs_graph_set_flow.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
+    L.hs_graph_schedule_gate.restype = C.c_int
+    L.hs_graph_schedule_gate.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32]
+    L.hs_graph_get_flow.restype = C.c_int
+    L.hs_graph_get_flow.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_graph_coop_selects.restype = C.c_int64
     L.hs_graph_coop_selects.argtypes = [C.c_void_p]
     L.hs_debug_graph_flags.restype = C.c_int
@@ -586,4 +597,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_set_health_checker", "hs_graph_set_lb_health", "hs_graph_get_health", "hs_graph_get_lb_current_weights",
     "hs_graph_set_wrapper", "hs_graph_get_wrapper",
     "hs_graph_set_client", "hs_graph_schedule_client", "hs_graph_get_client",
+    "hs_graph_set_flow", "hs_graph_schedule_gate", "hs_graph_get_flow",
 )

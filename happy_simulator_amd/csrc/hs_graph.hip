@@ -27,6 +27,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include <type_traits>
 
 #include "../../include/hs_engine.h"
 #include "hs_device.hpp"
@@ -146,6 +147,15 @@ constexpr uint32_t kEvBhReq = kEvAllKinds, kEvBhResp = kEvAllKinds + 1, kEvBhTim
 // request_id and is attempt 1.  They count in events_processed and per graph (GVars::client_by_kind), not in events_by_kind.
 constexpr uint32_t kEvClReq = kEvResKinds, kEvClResp = kEvResKinds + 1, kEvClTimeout = kEvResKinds + 2, kEvCliKinds = kEvResKinds + 3;
 constexpr int kKeyAttemptShift = 30;
+// BatchProcessor / ConveyorBelt / GateController (components/industrial/): eight more internal kinds.  An item carries its Request; a
+// `_BatchTimeout` carries the processor's timeout id in GEvent::pad above the two flag bits (GState::d holds the id of the ONE pending
+// timeout, 0: none -- an entry with another id was cancelled when its batch started, core/simulation.py:326-329); the continuation of
+// a batch carries the head of its list through Request::next in GEvent::req and its length in GEvent::pad above the flag bits, so
+// several batches of one processor are in process at once.  They count in events_processed and per graph (GVars::flow_by_kind).
+constexpr uint32_t kEvBpItem = kEvCliKinds, kEvBpTimeout = kEvCliKinds + 1, kEvBpCont = kEvCliKinds + 2, kEvCvItem = kEvCliKinds + 3,
+                   kEvCvCont = kEvCliKinds + 4, kEvGtItem = kEvCliKinds + 5, kEvGtOpen = kEvCliKinds + 6, kEvGtClose = kEvCliKinds + 7,
+                   kEvFlowKinds = kEvCliKinds + HS_FLOW_KINDS;
+constexpr int kMaxFlowItems = HS_FLOW_MAX_ITEMS;             // batch_size / a bounded gate queue: a batch's length rides in 30 bits of GEvent::pad
 constexpr uint32_t kPadPre = 1u, kPadCancelled = 2u;
 constexpr int kPadIdShift = 2;                 // a check id in GEvent::pad (its low 30 bits: only the one pending id of a backend and ids
                                                // at most one timeout older are ever compared)
@@ -161,6 +171,11 @@ constexpr uint32_t kDropKindsRes = kDropKinds | (1u << kEvBhReq) | (1u << kEvBhR
 // ... and the three of a Client
 constexpr uint32_t kDropKindsCli = kDropKindsRes | (1u << kEvClReq) | (1u << kEvClResp) | (1u << kEvClTimeout);
 static_assert(kEvCliKinds <= 32, "kDropKinds is one word");
+// ... and, beyond the 32 kinds one word holds, the six of the three flow entities that are aimed at the entity itself (the two
+// continuations resume a generator): a second constant of 64 bits, tested by the one instantiation that dispatches them
+constexpr uint64_t kDropKindsFlow = (uint64_t)kDropKindsCli | (1ull << kEvBpItem) | (1ull << kEvBpTimeout) | (1ull << kEvCvItem) |
+                                    (1ull << kEvGtItem) | (1ull << kEvGtOpen) | (1ull << kEvGtClose);
+static_assert(kEvFlowKinds <= 64, "kDropKindsFlow is two words; s_by_kind is zeroed by one lane per kind");
 constexpr int kMaxBulkheadConcurrent = HS_BULKHEAD_MAX_CONCURRENT;         // Bulkhead.max_concurrent the in-flight table is sized for (include/hs_engine.h)
 constexpr int kDefaultTimeoutTable = 256;                // ids a TimeoutWrapper's (keys a Client's) table holds before it first grows
 constexpr int kMaxClientAttempts = HS_CLIENT_MAX_ATTEMPTS;   // the attempt of a key is 16 bits and one
@@ -200,6 +215,8 @@ struct GVars {                                 // device scalars
     long long health_by_kind[3];               // the checkers' cycle / response / timeout Events (hs_graph_get_health)
     long long resil_by_kind[6];                // the wrappers' request / response / timeout Events, Bulkhead then TimeoutWrapper (hs_graph_get_wrapper)
     long long client_by_kind[3];               // the Clients' request / response / timeout Events (hs_graph_get_client)
+    long long flow_by_kind[HS_FLOW_KINDS];     // the flow entities' Events, kEvBpItem .. kEvGtClose (hs_graph_get_flow)
+    long long flow_cancelled;                  // cancelled `_BatchTimeout` Events popped
 };
 
 struct GCtl {                                  // kernel argument
@@ -224,7 +241,7 @@ struct GCtl {                                  // kernel argument
     uint64_t seed;
     int64_t start_ns, end_ns;
     long long budget;
-    int part;                                  // 1: this heap holds PART of a Simulation (hs_graph_run_parts)
+    int part;                                  // 1: this heap holds PART of a Simulation (hs_graph_run_parts); 2: ... and runs its one Event beyond the end
     // Backend health (LoadBalancer.mark_unhealthy / mark_healthy, load_balancer.py:244-297): only a graph with a HealthChecker or a
     // backend marked unhealthy before the run has these (health = 1); every array is indexed like rt_targets
     int health;
@@ -320,8 +337,13 @@ __device__ __forceinline__ double uniform_at(uint64_t seed, uint64_t sid, uint64
 }
 
 // a Request-carrying Event aimed at `node`: which handler it lands in (Entity.handle_event of that class)
-template <bool R = false, bool CL = false>
+template <bool R = false, bool CL = false, bool FL = false>
 __device__ __forceinline__ uint32_t arrival_kind(const GParam *P, int node) {
+    if constexpr (FL) {
+        if (P[node].kind == HS_NODE_BATCH_PROCESSOR) return kEvBpItem;
+        if (P[node].kind == HS_NODE_CONVEYOR) return kEvCvItem;
+        if (P[node].kind == HS_NODE_GATE) return kEvGtItem;
+    }
     if constexpr (CL) {
         if (P[node].kind == HS_NODE_CLIENT) return kEvClReq;
     }
@@ -561,13 +583,16 @@ __device__ inline bool tab_remove(int64_t *tab, int live, int64_t id) {
 // their code: the fault-only loop is as sensitive to what it carries as the plain one.  HC implies F.
 // R: the graph (or one of a batch) has a Bulkhead or a TimeoutWrapper -- a fourth instantiation, for the same reason.  R implies HC.
 // CL: ... has a Client -- a fifth, for the same reason.  CL implies R.
-template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false>
+// FL: ... has a BatchProcessor, a ConveyorBelt or a GateController -- a sixth, for the same reason.  FL implies CL.
+template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     static_assert(F || !HC, "the health instantiation carries the fault code");
     static_assert(HC || !R, "the resilience instantiation carries the fault and health code");
     static_assert(R || !CL, "the client instantiation carries the fault, health and resilience code");
-    constexpr uint32_t kKinds = CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
-    constexpr uint32_t kDrop = CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
+    static_assert(CL || !FL, "the flow instantiation carries the fault, health, resilience and client code");
+    constexpr uint32_t kKinds = FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
+    // (one word for the instantiations whose kinds fit in it, two for the flow instantiation's 39)
+    constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
     constexpr int kPushes = R ? 3 : 2;         // heap entries one event constructs at most (R: a limiter's forward or poll + the hook's response)
     __shared__ unsigned long long s_by_kind[kKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
@@ -602,6 +627,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
     long long peak = V.heap_peak;
     long long polls_pending = V.polls_pending;   // daemon Events in the heap: they do not keep an auto-terminating run alive
     long long n_cancelled = 0;
+    [[maybe_unused]] long long n_flow_cancelled = 0;
     if (lane == 0) {
         if (!V.booted) {
             // Simulation.__init__ (core/simulation.py:145-154) + Source.start (load/source.py:120-140): the Sources in list order,
@@ -658,6 +684,17 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     continue;
                 }
             }
+            if constexpr (FL) {
+                // one Event of GateController.start_events() (gate_controller.py:89-111): `_GateOpen` / `_GateClose`, a daemon, no Request
+                const int gn = c.sched_node[V.sched_done];
+                const int32_t what = c.sched_id ? c.sched_id[V.sched_done] : 0;
+                if (c.P[gn].kind == HS_NODE_GATE && what < 0) {
+                    H.push(mk_pre(c.sched_t[V.sched_done], V.global_counter++, what == -1 ? kEvGtOpen : kEvGtClose, gn, -1));
+                    polls_pending += 1;
+                    V.sched_done++;
+                    continue;
+                }
+            }
             int r = req_free;
             if (r >= 0) req_free = c.reqs[r].next;
             else if (req_len < c.req_cap) r = req_len++;
@@ -666,7 +703,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             const int64_t t = c.sched_t[V.sched_done];
             GRequest q; q.created = t; q.idx = V.global_counter; q.service_s = 0.0; q.client = -1; q.next = -1; q.hook = -1; q.pre = 1;
             c.reqs[r] = q;
-            H.push(mk_pre(t, V.global_counter++, arrival_kind<R, CL>(c.P, node), node, r));
+            H.push(mk_pre(t, V.global_counter++, arrival_kind<R, CL, FL>(c.P, node), node, r));
             V.sched_done++;
         }
         cur = V.cur;
@@ -715,6 +752,15 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     if (top.kind == kEvClReq && c.S[top.node].qlen >= c.P[top.node].rt_cnt) { status |= kGrowTab; break; }
                 }
             }
+            if constexpr (FL) {
+                // a batch that leaves its processor and a gate that opens construct one Event per item in ONE handler: the heap has
+                // room for all of them before anything changes, or the run stops in front of the Event (the items keep their Requests)
+                const GEvent top = H.get(0);
+                long long items = 0;
+                if (top.kind == kEvBpCont) items = (long long)(top.pad >> kPadIdShift);
+                else if (top.kind == kEvGtOpen) items = c.S[top.node].qlen;
+                if (H.len + items + kPushes > c.heap_cap) { status |= kGrowHeap; break; }
+            }
             if (c.coop_min > 0 && sel < 0) {                                       // (a graph without such a LoadBalancer: one uniform test)
                 const GEvent top = H.get(0);
                 if (top.kind == HS_EV_LB && top.t >= cur) {
@@ -745,7 +791,18 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     if (e.pad & kPadCancelled) { n_cancelled++; continue; }
                 }
             }
-            if (e.t < cur) continue;                                               // time-travel drop, core/simulation.py:480-489
+            if constexpr (FL) {
+                if (e.kind == kEvGtOpen || e.kind == kEvGtClose) polls_pending -= 1;   // a daemon leaves the heap
+                // a `_BatchTimeout` whose batch has started since: Event.cancel() (batch_processor.py:135-138), skipped like a cancelled fault
+                // (the one Event beyond the end of a PART run, GCtl::part = 2: a cancelled entry in front of it ends the launch -- whether the
+                //  next entry of this part or one of another part comes next is decided across all of them, hs_graph_run_parts)
+                if (e.kind == kEvBpTimeout && ((uint32_t)c.S[e.node].d << kPadIdShift) != (e.pad & ~3u)) {
+                    n_flow_cancelled++;
+                    if (c.part == 2) break;
+                    continue;
+                }
+            }
+            if (e.t < cur) continue;                                              // time-travel drop, core/simulation.py:480-489
             cur = e.t;
             processed++;
             const int n = e.node;
@@ -791,7 +848,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         GRequest rq; rq.created = t; rq.idx = idx_p; rq.service_s = 0.0; rq.client = (id << 32) | (int64_t)q; rq.next = -1; rq.hook = n; rq.pre = 0;
                         c.reqs[r] = rq;
                         const int be = c.rt_targets[lp.rt_off + q];
-                        H.push(mk(t, idx_p, arrival_kind<R, CL>(c.P, be), be, r));
+                        H.push(mk(t, idx_p, arrival_kind<R, CL, FL>(c.P, be), be, r));
                         GEvent te = mk(t + ns_from_seconds(p.lat_min), G++, kEvHcTimeout, n, -2 - q);
                         te.pad = (uint32_t)id << kPadIdShift;
                         H.push(te);
@@ -832,6 +889,93 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     H.push(mk_id(t, G++, hook_resp_kind<CL>(hk), hook, req_id(c.reqs[r])));
                 else if (hk == HS_NODE_LB) H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
             };
+            if constexpr (FL) {
+                if (e.kind >= kEvBpItem) {
+                    // BatchProcessor / ConveyorBelt / GateController (components/industrial/).  GParam: conc = batch_size / capacity /
+                    // queue_capacity, lim = process_time / transit_time in ns, stream_base = the timeout in ns (sub = 1: it has one).
+                    // GState: see hs_graph_get_flow.  No completion hook ever reaches one of them (a LoadBalancer's backends are Servers,
+                    // a wrapper's or Client's target is refused), so a handler ends with the Events it constructs.
+                    // A NEW Event for the downstream at `now` with the item's context (created_at survives), no hook:
+                    auto forward = [&](int r) { H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r)); };
+                    // BatchProcessor._process_batch up to its yield (batch_processor.py:131-141) via Event._start_process: the buffer
+                    // becomes the batch, the pending timeout is cancelled; one continuation is built and invoked at once, the pushed
+                    // one is the second.  The batch's list and length travel in the entry: any number of batches is in process.
+                    auto start_batch = [&]() {
+                        (void)G++;
+                        GEvent ce = mk(t + p.lim, G++, kEvBpCont, n, s.qhead);
+                        ce.pad = (uint32_t)s.qlen << kPadIdShift;
+                        s.qhead = -1; s.qtail = -1; s.qlen = 0;
+                        s.d = 0;
+                        H.push(ce);
+                    };
+                    auto append = [&](int r) {
+                        c.reqs[r].next = -1;
+                        if (s.qtail >= 0) c.reqs[s.qtail].next = r; else s.qhead = r;
+                        s.qtail = r;
+                        s.qlen += 1;
+                    };
+                    switch (e.kind) {
+                    case kEvBpItem:                                                 // BatchProcessor.handle_event (:104-122)
+                        append(e.req);
+                        if (s.qlen == 1 && p.sub) {                                 // the first item of an empty buffer: the timeout and nothing else
+                            s.svc_draws += 1;
+                            if ((s.svc_draws & 0x3fffffffull) == 0) s.svc_draws += 1;
+                            s.d = (int64_t)(s.svc_draws & 0x3fffffffull);
+                            GEvent te = mk(t + (int64_t)p.stream_base, G++, kEvBpTimeout, n, -1);
+                            te.pad = (uint32_t)s.d << kPadIdShift;
+                            H.push(te);
+                        } else if (s.qlen >= p.conc) start_batch();
+                        break;
+                    case kEvBpTimeout:                                              // _handle_timeout (:124-129): on an empty buffer a no-op
+                        s.d = 0;
+                        if (s.qlen == 0) break;
+                        s.c += 1;
+                        start_batch();
+                        break;
+                    case kEvBpCont:                                                 // the generator resumes (:142-157): every item, in buffer order
+                        s.a += 1;                                                   // (room in the heap: tested in front of the pop)
+                        s.b += (int64_t)(e.pad >> kPadIdShift);
+                        for (int r = e.req; r >= 0;) { const int nx = c.reqs[r].next; forward(r); r = nx; }
+                        break;
+                    case kEvCvItem:                                                 // ConveyorBelt.handle_event (conveyor.py:91-98)
+                        if (p.conc > 0 && s.active >= p.conc) {
+                            s.b += 1;
+                            c.reqs[e.req].next = req_free; req_free = e.req;
+                            break;
+                        }
+                        s.active += 1;
+                        (void)G++;                                                  // the continuation built by _start_process
+                        H.push(mk(t + p.lim, G++, kEvCvCont, n, e.req));
+                        break;
+                    case kEvCvCont:                                                 // _transport behind its yield (:100-113)
+                        s.active -= 1;
+                        s.a += 1;
+                        forward(e.req);
+                        break;
+                    case kEvGtItem:                                                 // GateController.handle_event (gate_controller.py:121-152)
+                        if (s.active) { s.a += 1; forward(e.req); break; }
+                        if (p.conc > 0 && s.qlen >= p.conc) {
+                            s.c += 1;
+                            c.reqs[e.req].next = req_free; req_free = e.req;
+                            break;
+                        }
+                        append(e.req);
+                        s.b += 1;
+                        break;
+                    case kEvGtOpen:                                                 // _do_open (:154-179): the whole queue, in FIFO order
+                        if (s.active) break;
+                        s.active = 1;
+                        s.d += 1;
+                        for (int r = s.qhead; r >= 0;) { const int nx = c.reqs[r].next; s.a += 1; forward(r); r = nx; }
+                        s.qhead = -1; s.qtail = -1; s.qlen = 0;                     // (room in the heap: tested in front of the pop)
+                        break;
+                    default:                                                        // kEvGtClose: _do_close (:181-186)
+                        s.active = 0;
+                        break;
+                    }
+                    continue;
+                }
+            }
             if constexpr (CL) {
                 if (e.kind >= kEvClReq) {
                     int64_t *tab = c.rs_tab + p.rt_off;                            // _in_flight: (key, start_time ns) per place, unordered
@@ -854,7 +998,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         if ((key >> kKeyAttemptShift) > 1) s.d += 1;
                         GRequest q; q.created = t; q.idx = 0; q.service_s = __longlong_as_double(key); q.client = -1; q.next = -1; q.hook = n; q.pre = 0;
                         c.reqs[r] = q;
-                        H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, r));
+                        H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r));
                         if (p.sub) H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvClTimeout, n, key));
                         continue;
                     }
@@ -892,7 +1036,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         if (s.active > peaks[0]) peaks[0] = s.active;
                         tab[s.active - 1] = id;                                    // (active <= max_concurrent = rt_cnt)
                         c.reqs[r].hook = n; c.reqs[r].service_s = __longlong_as_double(id);
-                        H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, r));
+                        H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r));
                     };
                     switch (e.kind) {
                     case kEvBhReq: {                                               // Bulkhead.handle_event (bulkhead.py:191-229)
@@ -954,7 +1098,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         tab[s.qlen] = id;                                          // (room: tested in front of the pop)
                         s.qlen += 1;
                         c.reqs[e.req].hook = n; c.reqs[e.req].service_s = __longlong_as_double(id);
-                        H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, e.req));
+                        H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, e.req));
                         H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvTwTimeout, n, id));
                     } break;
                     default: {                                                     // _handle_response / _handle_timeout (:222-295): whichever comes second finds nothing
@@ -988,7 +1132,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 }
                 s.c += 1;                                                           // _generated_count (:159)
                 const int64_t a2 = next_arrival(c, n);
-                if (payload) H.push(mk(t, idx_p, arrival_kind<R, CL>(c.P, p.target), p.target, r));
+                if (payload) H.push(mk(t, idx_p, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r));
                 if (a2 != kInfNs) H.push(mk(a2, G++, HS_EV_SOURCE, n, -1));       // RuntimeError: the source is exhausted (:176-180)
             } break;
             case HS_EV_ENQUEUE: {
@@ -1072,7 +1216,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 s.active = s.active > 0 ? s.active - 1 : 0;
                 s.c += 1; n_completed++;
                 s.total_service = __dadd_rn(s.total_service, c.reqs[e.req].service_s);
-                if (p.target >= 0) H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, e.req));
+                if (p.target >= 0) H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, e.req));
                 else { c.reqs[e.req].next = req_free; req_free = e.req; }
                 if (s.active < p.conc) H.push(mk(t, G++, HS_EV_POLL, n, -1));
             } break;
@@ -1093,11 +1237,11 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     const int hook = c.reqs[e.req].hook;                            //  its Event constructed behind the forward's)
                     const int64_t id = req_id(c.reqs[e.req]);
                     c.reqs[e.req].hook = -1;
-                    H.push(mk(t, G++, arrival_kind<R, CL>(c.P, tg), tg, e.req));
+                    H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, tg), tg, e.req));
                     if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<CL>(c.P[hook].kind), hook, id));
                     break;
                 }
-                H.push(mk(t, G++, arrival_kind<R, CL>(c.P, tg), tg, e.req));
+                H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, tg), tg, e.req));
             } break;
             case HS_EV_LINK: {
                 // NetworkLink.handle_event up to its yield (components/network/link.py:114-154, _calculate_delay :190-216)
@@ -1123,7 +1267,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             case HS_EV_LINK_CONT:                                                   // transit over (link.py:156-189): a NEW Event for the egress
                 s.b += 1;
                 if (p.target >= 0) {
-                    H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, e.req));
+                    H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, e.req));
                     if constexpr (R) fire_hook(e.req, true);                        // ... and stays on the Event for the egress (link.py:181)
                 } else {
                     if constexpr (R) fire_hook(e.req, false);
@@ -1216,7 +1360,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 // a NEW Event for the backend with the same context (created_at survives) + the response hook (:398-431)
                 const int be = c.rt_targets[p.rt_off + slot];
                 c.reqs[e.req].hook = n;
-                H.push(mk(t, G++, arrival_kind<R, CL>(c.P, be), be, e.req));
+                H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, be), be, e.req));
             } break;
             case HS_EV_LB_RESP:                                                     // LoadBalancer._handle_response (load_balancer.py:435-473)
                 if (s.d > 0) s.d -= 1;
@@ -1257,6 +1401,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     default: break;
                     }
                 }
+                if constexpr (FL) {                                                 // (the flow entities' metrics likewise)
+                    if (p.sub == HS_PROBE_BP_BUFFER_DEPTH || p.sub == HS_PROBE_GT_QUEUE_DEPTH) v = tg.qlen;   // buffer_depth / queue_depth
+                    else if (p.sub == HS_PROBE_CV_IN_TRANSIT) v = tg.active;        // ConveyorBelt.items_in_transit
+                }
                 c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = v;
                 rec_n++;
                 s.c += 1;
@@ -1271,7 +1419,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if (lim_try_acquire(c, p, s, t)) {
                     // _forward (:164-178): a NEW Event for the downstream at `now` with a copy of the context, no completion hook
                     outcome = HS_LIMITER_FORWARDED;
-                    H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, e.req));
+                    H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, e.req));
                 } else if (!(p.lim >= 0 && s.qlen >= p.lim)) {                     // FIFOQueue.push (queue_policy.py:94-98)
                     outcome = HS_LIMITER_QUEUED;
                     c.reqs[e.req].next = -1;
@@ -1309,7 +1457,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     s.qlen -= 1;
                     c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = HS_LIMITER_DRAINED;
                     rec_n++;
-                    H.push(mk(t, G++, arrival_kind<R, CL>(c.P, p.target), p.target, r));
+                    H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r));
                     again = s.qlen > 0;
                 }
                 if (again) {
@@ -1411,6 +1559,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         if constexpr (CL) {
             for (int k = 0; k < 3; ++k) V.client_by_kind[k] += (long long)s_by_kind[kEvClReq + k];
         }
+        if constexpr (FL) {
+            for (int k = 0; k < HS_FLOW_KINDS; ++k) V.flow_by_kind[k] += (long long)s_by_kind[kEvBpItem + k];
+            V.flow_cancelled += n_flow_cancelled;
+        }
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
@@ -1456,6 +1608,12 @@ __global__ void __launch_bounds__(64) hs_graph_run_client(GCtl c) {           //
     __shared__ GEvent lheap[kLdsHeap];
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
     graph_loop<kLdsHeap, kLdsNodes, true, true, true, true>(c, lheap, lnodes);
+}
+
+__global__ void __launch_bounds__(64) hs_graph_run_flow(GCtl c) {             // ... with a BatchProcessor, a ConveyorBelt or a GateController
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true>(c, lheap, lnodes);
 }
 
 // Independent graphs -- the replicas / sweep points of parallel/runner.py:82-142 -- side by side: one workgroup (one heap) each, one
@@ -1508,6 +1666,14 @@ __global__ void __launch_bounds__(64) hs_graph_run_batch_client(const GCtl *cs, 
     graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true>(c, lheap, lnodes);
     batch_report(c, stat);
 }
+// ... of a batch in which at least one handle has a flow entity
+__global__ void __launch_bounds__(64) hs_graph_run_batch_flow(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
 
 }  // namespace graph
 }  // namespace hs
@@ -1549,6 +1715,7 @@ struct hs_graph {
     long long rs_tab_len = 0;
     // Client: a graph that holds one runs the fifth instantiation; its in-flight table is one of rs_tab (two words per place)
     int n_clients = 0;
+    int n_flows = 0;                           // BatchProcessor / ConveyorBelt / GateController nodes: a graph that holds one runs the sixth instantiation
     std::vector<int64_t> cl_delays;            // every configured Client's delay table, back to back (GParam::lim = its offset)
     int64_t *d_cl_delays = nullptr;
     std::vector<int32_t> sched_id;             // request_id per scheduled entry (0: none)
@@ -1659,7 +1826,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     if (cfg->start_ns < 0)        // (the Sinks' merged records hold non-negative times)
         return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
     bool has_wrr = false;
-    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER || k == HS_NODE_BULKHEAD || k == HS_NODE_TIMEOUT_WRAPPER || k == HS_NODE_CLIENT; };
+    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER || k == HS_NODE_BULKHEAD || k == HS_NODE_TIMEOUT_WRAPPER || k == HS_NODE_CLIENT || k == HS_NODE_BATCH_PROCESSOR || k == HS_NODE_CONVEYOR || k == HS_NODE_GATE; };
     int64_t kmax = 0;                                  // client ids any Source hands out: [0, kmax)
     for (int i = 0; i < n; ++i)
         if (nd->kind[i] == HS_NODE_SOURCE && nd->src_n_clients && nd->src_n_clients[i] > kmax) kmax = nd->src_n_clients[i];
@@ -1730,7 +1897,10 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
                             : p.sub == HS_PROBE_LIMITER_DEPTH ? tk == HS_NODE_RATE_LIMITER
                             : (p.sub >= HS_PROBE_BH_ACTIVE && p.sub <= HS_PROBE_BH_PERMITS) ? tk == HS_NODE_BULKHEAD
                             : p.sub == HS_PROBE_TW_IN_FLIGHT ? tk == HS_NODE_TIMEOUT_WRAPPER
-                            : p.sub == HS_PROBE_CL_IN_FLIGHT ? tk == HS_NODE_CLIENT : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
+                            : p.sub == HS_PROBE_CL_IN_FLIGHT ? tk == HS_NODE_CLIENT
+                            : p.sub == HS_PROBE_BP_BUFFER_DEPTH ? tk == HS_NODE_BATCH_PROCESSOR
+                            : p.sub == HS_PROBE_CV_IN_TRANSIT ? tk == HS_NODE_CONVEYOR
+                            : p.sub == HS_PROBE_GT_QUEUE_DEPTH ? tk == HS_NODE_GATE : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
             if (!ok) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: metric %d is not an attribute of its target (node kind %d)", i, (int)p.sub, tk);
             const double rate = 1.0 / iv;                           // _ProbeProfile.rate (probe.py:31)
             int found = -1;
@@ -1844,10 +2014,20 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             // the target's handler must fire ONE hook: through any chain of links it is a Server, Sink, router or limiter
             int t = p.target;
             for (int hops = 0; hops <= n && t >= 0 && nd->kind[t] == HS_NODE_LINK; ++hops) t = nd->target[t];
+            if (t >= 0 && (nd->kind[t] == HS_NODE_BATCH_PROCESSOR || nd->kind[t] == HS_NODE_CONVEYOR || nd->kind[t] == HS_NODE_GATE))
+                return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the target of a %s is (through %s) node %d, a BatchProcessor, ConveyorBelt or GateController: "
+                            "a completion hook on an item they hold is not lowered", i, nm, t == p.target ? "no link" : "its links", t);
             if (t >= 0 && (nd->kind[t] == HS_NODE_LB || nd->kind[t] == HS_NODE_BULKHEAD || nd->kind[t] == HS_NODE_TIMEOUT_WRAPPER || nd->kind[t] == HS_NODE_CLIENT))
                 return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the target of a %s is (through %s) node %d, a LoadBalancer, Bulkhead, TimeoutWrapper or Client: "
                             "two completion hooks on one Event are not lowered", i, nm, t == p.target ? "no link" : "its links", t);
             p.conc = 1; p.lim = 0; p.sub = 0; p.rt_off = 0; p.rt_cnt = 0;
+        } break;
+        case HS_NODE_BATCH_PROCESSOR:
+        case HS_NODE_CONVEYOR:
+        case HS_NODE_GATE: {
+            // BatchProcessor / ConveyorBelt / GateController (components/industrial/): the parameters come with hs_graph_set_flow
+            if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a BatchProcessor, ConveyorBelt or GateController needs a downstream", i);
+            p.conc = 0; p.lim = 0; p.sub = 0; p.stream_base = 0; p.rt_off = 0; p.rt_cnt = 0;
         } break;
         default: return fail(nullptr, HS_E_UNSUPPORTED, "node %d: kind %d is not lowered", i, (int)p.kind);
         }
@@ -1867,6 +2047,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_HEALTH_CHECKER) g->n_checkers++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_BULKHEAD || P[(size_t)i].kind == HS_NODE_TIMEOUT_WRAPPER) g->n_wrappers++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_CLIENT) g->n_clients++;
+        for (int i = 0; i < n; ++i) if (P[(size_t)i].kind >= HS_NODE_BATCH_PROCESSOR && P[(size_t)i].kind <= HS_NODE_GATE) g->n_flows++;
         g->wrapper_set.assign((size_t)n, 0); g->tab_cap.assign((size_t)n, 0);
     }
     for (int i = 0; i < n; ++i) {
@@ -2384,6 +2565,74 @@ int hs_graph_get_client(hs_graph *g, int32_t node, int64_t *counters, int64_t *i
     return HS_OK;
 }
 
+int hs_graph_set_flow(hs_graph *g, int32_t node, int64_t count, int64_t delay_ns, int64_t aux_ns, int32_t flag) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind < HS_NODE_BATCH_PROCESSOR || g->params[(size_t)node].kind > HS_NODE_GATE)
+        return fail(g, HS_E_INVALID, "set_flow: node %d is not a BatchProcessor, ConveyorBelt or GateController", node);
+    if (g->ran || g->launches > 0) return fail(g, HS_E_STATE, "set_flow: a node is configured before the first run");
+    if (g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "set_flow: node %d is configured already", node);
+    GParam &p = g->params[(size_t)node];
+    GState s0{};
+    s0.qhead = -1; s0.qtail = -1;
+    if (delay_ns > (1ll << 61) || aux_ns > (1ll << 61)) return fail(g, HS_E_INVALID, "set_flow: a delay beyond 2^61 ns");
+    if (p.kind == HS_NODE_BATCH_PROCESSOR) {
+        if (count <= 0) return fail(g, HS_E_INVALID, "batch_size must be > 0, got %lld", (long long)count);                      // batch_processor.py:59-60
+        if (delay_ns < 0) return fail(g, HS_E_INVALID, "process_time must be >= 0, got %g", (double)delay_ns / 1e9);             // :61-62
+        if (count > kMaxFlowItems) return fail(g, HS_E_UNSUPPORTED, "BatchProcessor: batch_size = %lld is beyond the %d items of one batch", (long long)count, kMaxFlowItems);
+        p.conc = (int32_t)count; p.lim = delay_ns; p.sub = aux_ns > 0 ? 1 : 0; p.stream_base = (uint64_t)(aux_ns > 0 ? aux_ns : 0);
+    } else if (p.kind == HS_NODE_CONVEYOR) {
+        if (delay_ns < 0) return fail(g, HS_E_INVALID, "transit_time must be >= 0, got %g", (double)delay_ns / 1e9);             // conveyor.py:53-54
+        p.conc = (int32_t)std::min<int64_t>(std::max<int64_t>(count, 0), INT32_MAX); p.lim = delay_ns; p.sub = 0; p.stream_base = 0;
+    } else {
+        if (count > kMaxFlowItems) return fail(g, HS_E_UNSUPPORTED, "GateController: queue_capacity = %lld is beyond %d items (0: unbounded)", (long long)count, kMaxFlowItems);
+        p.conc = (int32_t)std::max<int64_t>(count, 0); p.lim = 0; p.sub = flag ? 1 : 0; p.stream_base = 0;
+        s0.active = flag ? 1 : 0;                           // _is_open
+        s0.d = aux_ns > 0 ? aux_ns : 0;                     // _open_cycles so far: open() on the host before the run
+        delay_ns = 0; aux_ns = 0;
+    }
+    g->reach_s = std::max(g->reach_s, (double)std::max(delay_ns, aux_ns) / 1e9);
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    HS_HIP(g, hipMemcpy(g->ctl.S + node, &s0, sizeof s0, hipMemcpyHostToDevice));
+    g->wrapper_set[(size_t)node] = 1;
+    return HS_OK;
+}
+
+int hs_graph_schedule_gate(hs_graph *g, int32_t node, int64_t time_ns, int32_t open) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_GATE) return fail(g, HS_E_INVALID, "schedule_gate: node %d is not a GateController", node);
+    g->sched_node.push_back(node);
+    g->sched_t.push_back(time_ns);
+    g->sched_id.push_back(open ? -1 : -2);                 // (negative: no request id but a gate Event)
+    g->any_sched_id = true;
+    return HS_OK;
+}
+
+int hs_graph_get_flow(hs_graph *g, int32_t node, int64_t *counters, int64_t *events, int64_t *cancelled) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (events || cancelled) {
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        if (events) for (int k = 0; k < HS_FLOW_KINDS; ++k) events[k] = v.flow_by_kind[k];
+        if (cancelled) *cancelled = v.flow_cancelled;
+    }
+    if (node == -1 && !counters) return HS_OK;
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind < HS_NODE_BATCH_PROCESSOR || g->params[(size_t)node].kind > HS_NODE_GATE)
+        return fail(g, HS_E_INVALID, "get_flow: node %d is not a BatchProcessor, ConveyorBelt or GateController", node);
+    if (!g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "get_flow: node %d was never configured", node);
+    if (!counters) return HS_OK;
+    GState s{};
+    HS_HIP(g, hipMemcpy(&s, g->ctl.S + node, sizeof s, hipMemcpyDeviceToHost));
+    for (int k = 0; k < HS_FLOW_COUNTERS; ++k) counters[k] = 0;
+    switch (g->params[(size_t)node].kind) {
+    case HS_NODE_BATCH_PROCESSOR: counters[0] = s.a; counters[1] = s.b; counters[2] = s.c; counters[3] = s.qlen; break;
+    case HS_NODE_CONVEYOR: counters[0] = s.a; counters[1] = s.b; counters[2] = s.active; break;
+    default: counters[0] = s.a; counters[1] = s.b; counters[2] = s.c; counters[3] = s.d; counters[4] = s.qlen; counters[5] = s.active; break;
+    }
+    return HS_OK;
+}
+
 int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, int32_t cancelled) {
     if (!g) return fail(g, HS_E_INVALID, "null handle");
     if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "add_fault: node %d out of range", node);
@@ -2581,6 +2830,12 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         }
         c.cl_delays = g->d_cl_delays;
     }
+    if (g->n_flows > 0)
+        for (int i = 0; i < g->n; ++i) {
+            const uint8_t k = g->params[(size_t)i].kind;
+            if (k >= HS_NODE_BATCH_PROCESSOR && k <= HS_NODE_GATE && !g->wrapper_set[(size_t)i])
+                return fail(g, HS_E_STATE, "node %d: a BatchProcessor, ConveyorBelt or GateController without its parameters (hs_graph_set_flow comes before the run)", i);
+        }
     const long long ns = (long long)g->sched_node.size();
     if (ns > g->d_sched_cap) {
         if (g->d_sched_node) HS_HIP(g, hipFree(g->d_sched_node));
@@ -2712,7 +2967,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, g->ctl);
@@ -2764,9 +3020,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
             h_ctl.back().part = part;              // (the handles themselves never keep part semantics: no early return can leave it set)
         }
         if ((he = hipMemcpy(d_ctl, h_ctl.data(), h_ctl.size() * sizeof(GCtl), hipMemcpyHostToDevice)) != hipSuccess) break;
-        bool any_faults = false, any_health = false, any_wrappers = false, any_clients = false;
-        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; any_clients |= gs[i]->n_clients > 0; }
-        if (any_clients) hipLaunchKernelGGL(hs_graph_run_batch_client, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_faults = false, any_health = false, any_wrappers = false, any_clients = false, any_flows = false;
+        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; any_clients |= gs[i]->n_clients > 0; any_flows |= gs[i]->n_flows > 0; }
+        if (any_flows) hipLaunchKernelGGL(hs_graph_run_batch_flow, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else if (any_clients) hipLaunchKernelGGL(hs_graph_run_batch_client, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_wrappers) hipLaunchKernelGGL(hs_graph_run_batch_resilience, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_health) hipLaunchKernelGGL(hs_graph_run_batch_health, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (!any_faults) hipLaunchKernelGGL(hs_graph_run_batch, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
@@ -2811,6 +3068,9 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
     for (int i = 0; i < n; ++i) if (gs[i]->undecided) return 1;
     // every part stands in front of its first event beyond end_ns: the reference processes the earliest of them (its loop tests the
     // PREVIOUS event's time, core/simulation.py:472) and nothing else
+    // A cancelled `_BatchTimeout` in front of that event is popped and counted like any cancelled Event (core/simulation.py:326-329):
+    // the part that holds the earliest entry pops it, and the election is repeated with that part's next entry.
+    for (int round = 0; round < (1 << 16); ++round) {
     int best = -1; int64_t best_t = 0; bool tie = false;
     for (int i = 0; i < n; ++i) {
         if (gs[i]->pending_events <= 0) continue;
@@ -2826,14 +3086,16 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         if (rc) { fail(g0, rc, "%s", g->error.c_str()); return rc; }
     }
     GCtl one = g->ctl;
-    one.part = 1; one.budget = 1; one.end_ns = INT64_MAX;
+    one.part = 2; one.budget = 1; one.end_ns = INT64_MAX;
     GVars before;
     HS_HIP(g0, hipMemcpy(&before, g->ctl.V, sizeof before, hipMemcpyDeviceToHost));
-    for (int attempt = 0; attempt < 64; ++attempt) {
+    bool again = false;
+    for (int attempt = 0; attempt < 64 && !again; ++attempt) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count; one.rs_tab = g->ctl.rs_tab;
-        if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, one);
+        if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, one);
+        else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, one);
@@ -2846,9 +3108,21 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         if (g->undecided) return 1;                  // (the popped event was dropped: the handle's state is no answer any more)
         GVars now;
         HS_HIP(g0, hipMemcpy(&now, g->ctl.V, sizeof now, hipMemcpyDeviceToHost));
-        if (now.processed > before.processed || now.heap_len <= 0) return HS_OK;
+        if (now.processed > before.processed) return HS_OK;
+        if (now.flow_cancelled > before.flow_cancelled) {
+            // a cancelled entry stood in front: this part's next entry (the launch wrote the heap's head back) joins the election
+            g->pending_events = now.heap_len;
+            if (now.heap_len > 0) {
+                GEvent top;
+                HS_HIP(g0, hipMemcpy(&top, g->ctl.heap, sizeof top, hipMemcpyDeviceToHost));
+                g->earliest_ns = top.t;
+            }
+            again = true;
+        } else if (now.heap_len <= 0) return HS_OK;
     }
-    return fail(g0, HS_E_OVERFLOW, "the event beyond the end could not be processed");
+    if (!again) return fail(g0, HS_E_OVERFLOW, "the event beyond the end could not be processed");
+    }
+    return 1;                                        // (tens of thousands of cancelled entries in front of the end: the one heap decides)
 }
 
 int hs_graph_get_summary(hs_graph *g, hs_summary *out) {

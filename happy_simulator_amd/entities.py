@@ -1660,6 +1660,184 @@ class Client(Entity):
         return sorted_times[lo] * (1.0 - frac) + sorted_times[hi] * frac
 
 
+# ---- stations that hold Requests back --------------------------------------------------------------
+# components/industrial/batch_processor.py, conveyor.py, gate_controller.py: the three entities that turn one Event into none now and
+# many later.  Their handlers run on the device (csrc/hs_graph.hip kEvBpItem .. kEvGtClose); the delays go there as whole nanoseconds.
+# Not mirrored from that package: ShiftedServer, RenegingQueuedResource, BalkingQueue, InspectionStation, BreakdownScheduler (the last
+# three draw from the process-wide `random`), SplitMerge (SimFuture), ConditionalRouter (callables).
+@dataclass(frozen=True)
+class BatchProcessorStats:
+    """batch_processor.py:25-31."""
+
+    batches_processed: int = 0
+    items_processed: int = 0
+    timeouts: int = 0
+
+
+class BatchProcessor(Entity):
+    """Buffers items until `batch_size` of them wait or `timeout_s` has passed since the first one arrived, takes `process_time`
+    seconds for the batch and forwards every item to `downstream` (batch_processor.py:34-157).  `timeout_s = 0` never schedules a
+    timeout; several batches may be in process at once."""
+
+    MAX_BATCH_SIZE = 1 << 20                  # include/hs_engine.h HS_FLOW_MAX_ITEMS
+
+    def __init__(self, name: str, downstream: Entity, batch_size: int = 10, process_time: float = 1.0, timeout_s: float = 0.0):
+        if batch_size <= 0:                                                               # batch_processor.py:59-62
+            raise ValueError(f"batch_size must be > 0, got {batch_size}")
+        if process_time < 0:
+            raise ValueError(f"process_time must be >= 0, got {process_time}")
+        super().__init__(name)
+        self.downstream = downstream
+        self.batch_size = batch_size
+        self.process_time = process_time
+        self.timeout_s = timeout_s
+        self._buffer_depth = 0                # after a run: len(_buffer)
+        self._batches_processed = 0
+        self._items_processed = 0
+        self._timeouts = 0
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self.downstream]
+
+    @property
+    def batches_processed(self) -> int:
+        return self._batches_processed
+
+    @property
+    def items_processed(self) -> int:
+        return self._items_processed
+
+    @property
+    def timeouts(self) -> int:
+        return self._timeouts
+
+    @property
+    def buffer_depth(self) -> int:
+        return self._buffer_depth
+
+    @property
+    def stats(self) -> BatchProcessorStats:
+        return BatchProcessorStats(batches_processed=self._batches_processed, items_processed=self._items_processed, timeouts=self._timeouts)
+
+
+@dataclass(frozen=True)
+class ConveyorStats:
+    """conveyor.py:23-29."""
+
+    items_transported: int = 0
+    items_in_transit: int = 0
+    items_rejected: int = 0
+
+
+class ConveyorBelt(Entity):
+    """Holds every item for `transit_time` seconds, then forwards it to `downstream`; with `capacity` > 0 an item that finds that many
+    in transit is rejected (conveyor.py:32-113)."""
+
+    def __init__(self, name: str, downstream: Entity, transit_time: float, capacity: int = 0):
+        if transit_time < 0:                                                              # conveyor.py:53-54
+            raise ValueError(f"transit_time must be >= 0, got {transit_time}")
+        super().__init__(name)
+        self.downstream = downstream
+        self.transit_time = transit_time
+        self._capacity = capacity             # <= 0: unlimited
+        self._items_in_transit = 0
+        self._items_transported = 0
+        self._items_rejected = 0
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self.downstream]
+
+    @property
+    def items_in_transit(self) -> int:
+        return self._items_in_transit
+
+    @property
+    def items_transported(self) -> int:
+        return self._items_transported
+
+    @property
+    def items_rejected(self) -> int:
+        return self._items_rejected
+
+    @property
+    def stats(self) -> ConveyorStats:
+        return ConveyorStats(items_transported=self._items_transported, items_in_transit=self._items_in_transit,
+                             items_rejected=self._items_rejected)
+
+    def has_capacity(self) -> bool:
+        return self._capacity <= 0 or self._items_in_transit < self._capacity
+
+
+@dataclass(frozen=True)
+class GateStats:
+    """gate_controller.py:23-31."""
+
+    passed_through: int = 0
+    queued_while_closed: int = 0
+    rejected: int = 0
+    open_cycles: int = 0
+    is_open: bool = True
+
+
+class GateController(Entity):
+    """Passes items on to `downstream` while open; while closed it queues them, or rejects them once `queue_capacity` (> 0) of them
+    wait, and forwards the whole queue when it opens (gate_controller.py:34-186).  `schedule` = [(open_at_s, close_at_s), ...]:
+    `start_events()` returns the daemon Events for `Simulation.schedule()`.  `open()` / `close()` before `run()` act on the state the
+    run starts from."""
+
+    MAX_QUEUE_CAPACITY = 1 << 20              # include/hs_engine.h HS_FLOW_MAX_ITEMS (a bounded queue; 0 is unbounded)
+
+    def __init__(self, name: str, downstream: Entity, schedule: list | None = None, initially_open: bool = True, queue_capacity: int = 0):
+        super().__init__(name)
+        self.downstream = downstream
+        self.schedule = schedule or []
+        self._is_open = initially_open
+        self._queue_capacity = queue_capacity
+        self._queue_depth = 0                 # after a run: len(_queue)
+        self._passed_through = 0
+        self._queued_while_closed = 0
+        self._rejected = 0
+        self._open_cycles = 0
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self.downstream]
+
+    @property
+    def is_open(self) -> bool:
+        return self._is_open
+
+    @property
+    def queue_depth(self) -> int:
+        return self._queue_depth
+
+    @property
+    def stats(self) -> GateStats:
+        return GateStats(passed_through=self._passed_through, queued_while_closed=self._queued_while_closed, rejected=self._rejected,
+                         open_cycles=self._open_cycles, is_open=self._is_open)
+
+    def start_events(self) -> list[Event]:
+        """gate_controller.py:89-111: one daemon `_GateOpen` and one daemon `_GateClose` Event per interval, in list order."""
+        events: list[Event] = []
+        for open_at, close_at in self.schedule:
+            events.append(Event(time=Instant.from_seconds(open_at), event_type="_GateOpen", target=self, daemon=True))
+            events.append(Event(time=Instant.from_seconds(close_at), event_type="_GateClose", target=self, daemon=True))
+        return events
+
+    def open(self) -> list[Event]:
+        """gate_controller.py:154-179 on the host: before a run the queue is empty, so nothing is forwarded."""
+        if not self._is_open:
+            if self._queue_depth:
+                raise NotImplementedError("GateController.open() after a run that left items queued: their Events live on the device")
+            self._is_open = True
+            self._open_cycles += 1
+        return []
+
+    def close(self) -> list[Event]:
+        """gate_controller.py:181-186."""
+        self._is_open = False
+        return []
+
+
 # ---- probes --------------------------------------------------------------------------------------
 class Data:
     """Time-series container of a Probe (instrumentation/data.py:20-110): `values` = [(time_s, value), ...]."""
@@ -1729,12 +1907,14 @@ class Probe(Entity):
     """Periodic metric sampler (instrumentation/probe.py:81-164): a daemon Source that reads `getattr(target, metric)`
     every `interval` seconds into a Data container.  Lowered metrics: Server.depth / active_requests / utilization / available_capacity / has_capacity /
     stats_accepted / stats_dropped / requests completed, Sink.events_received, Source.generated_count, RateLimitedEntity.queue_depth,
-    Bulkhead.active_count / queue_depth / available_permits, TimeoutWrapper.in_flight_count, Client.in_flight_count."""
+    Bulkhead.active_count / queue_depth / available_permits, TimeoutWrapper.in_flight_count, Client.in_flight_count,
+    BatchProcessor.buffer_depth, ConveyorBelt.items_in_transit, GateController.queue_depth."""
 
     _LOWERED = {"depth", "active_requests", "utilization", "available_capacity", "has_capacity", "stats_accepted", "stats_dropped",
                 "requests_completed", "_requests_completed", "events_received", "generated_count", "_generated_count", "queue_depth",
-                "active_count", "available_permits", "in_flight_count"}
-    _ON_WRAPPER = {"active_count": Bulkhead, "available_permits": Bulkhead, "in_flight_count": (TimeoutWrapper, Client)}
+                "active_count", "available_permits", "in_flight_count", "buffer_depth", "items_in_transit"}
+    _ON_WRAPPER = {"active_count": Bulkhead, "available_permits": Bulkhead, "in_flight_count": (TimeoutWrapper, Client),
+                   "buffer_depth": BatchProcessor, "items_in_transit": ConveyorBelt}
     # Server attributes that are functions of `active_requests` and the (fixed) concurrency: the engine samples the integer,
     # the Data container applies the reference's expression (components/server/server.py:153-173,191-200, concurrency.py:117-131)
     _ON_ACTIVE = ("utilization", "available_capacity", "has_capacity")
@@ -1759,7 +1939,7 @@ class Probe(Entity):
     def __init__(self, target: Entity, metric: str, data: Data, interval: float = 1.0, start_time: Instant | None = None):
         if interval <= 0:
             raise ValueError("Probe interval must be positive.")                  # probe.py:29-30
-        if (metric not in self._LOWERED or (metric == "queue_depth" and not isinstance(target, (RateLimitedEntity, Bulkhead)))
+        if (metric not in self._LOWERED or (metric == "queue_depth" and not isinstance(target, (RateLimitedEntity, Bulkhead, GateController)))
                 or (metric in self._ON_WRAPPER and not isinstance(target, self._ON_WRAPPER[metric]))):
             raise NotImplementedError(f"probe metric '{metric}' is an arbitrary attribute; lowered: {sorted(self._LOWERED)}")
         super().__init__(f"Probe_{target.name}_{metric}")

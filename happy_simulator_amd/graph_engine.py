@@ -22,7 +22,8 @@ import numpy as np
 
 from . import _native as N
 from .core.temporal import Duration, Instant
-from .entities import (BackendHealthState, Bulkhead, Client, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
+from .entities import (BatchProcessor, ConveyorBelt, GateController,
+                       BackendHealthState, Bulkhead, Client, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
                        ExponentialLatency, HealthChecker, IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random,
                        RandomRouter, RateLimitedEntity, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source,
                        DecorrelatedJitter, ExponentialBackoff, FixedRetry, NoRetry,
@@ -87,6 +88,13 @@ class GraphArrays:
         self.cl_delay_off = None             # [n + 1] int64 and
         self.cl_delays_ns = None             # int64: Duration.from_seconds(policy.get_delay(a)) for a = 1 .. max_attempts - 1 of every
                                              #   Client, back to back
+
+        self.flow_params = None              # [n, 4] int64: BATCH_PROCESSOR / CONVEYOR / GATE nodes -- hs_graph_set_flow's count, delay_ns,
+                                             #   aux_ns and flag (entities.BatchProcessor / ConveyorBelt / GateController)
+
+    @property
+    def has_flows(self) -> bool:
+        return self.flow_params is not None
 
     @property
     def has_clients(self) -> bool:
@@ -199,6 +207,33 @@ class GraphEngine:
                 self.close()
                 raise
 
+        if arrays.has_flows:
+            try:
+                for i in np.nonzero((arrays.kind >= N.NODE_BATCH_PROCESSOR) & (arrays.kind <= N.NODE_GATE))[0]:
+                    count, delay_ns, aux_ns, flag = (int(v) for v in arrays.flow_params[i])
+                    self._check(self._lib.hs_graph_set_flow(self._h, int(i), count, delay_ns, aux_ns, flag))
+            except BaseException:
+                self.close()
+                raise
+
+    _FLOW_NAMES = {N.NODE_BATCH_PROCESSOR: ("batches_processed", "items_processed", "timeouts", "buffer_depth"),
+                   N.NODE_CONVEYOR: ("items_transported", "items_rejected", "items_in_transit"),
+                   N.NODE_GATE: ("passed_through", "queued_while_closed", "rejected", "open_cycles", "queue_depth", "is_open")}
+
+    def flow(self, node: int) -> dict:
+        """hs_graph_get_flow of a BatchProcessor, ConveyorBelt or GateController node: its counters by name."""
+        c = np.zeros(N.FLOW_COUNTERS, np.int64)
+        self._check(self._lib.hs_graph_get_flow(self._h, int(node), _ptr(c), None, None))
+        return {k: int(v) for k, v in zip(self._FLOW_NAMES[int(self.arrays.kind[node])], c)}
+
+    def flow_events(self) -> np.ndarray:
+        """The graph's Events of the eight flow kinds (item / timeout / batch continuation, item / transit continuation, item / open /
+        close) and, last, the cancelled `_BatchTimeout` Events it popped."""
+        events, cancelled = np.zeros(N.FLOW_KINDS + 1, np.int64), C.c_int64(0)
+        self._check(self._lib.hs_graph_get_flow(self._h, -1, None, _ptr(events), C.byref(cancelled)))
+        events[N.FLOW_KINDS] = cancelled.value
+        return events
+
     def client(self, node: int) -> dict:
         """hs_graph_get_client of a Client node: its counters by name and the keys in flight as sorted (request_id or 0, attempt) rows."""
         c = np.zeros(N.CLIENT_COUNTERS, np.int64)
@@ -285,9 +320,12 @@ class GraphEngine:
             raise N.EngineError(rc, (self._lib.hs_graph_last_error(self._h) or b"").decode())
         return rc
 
-    def schedule(self, node: int, time_ns: int, request_id: int | None = None) -> None:
-        """hs_graph_schedule; with a `request_id` (0: none) hs_graph_schedule_client: Client.send_request's Event."""
-        if request_id is None:
+    def schedule(self, node: int, time_ns: int, request_id: int | None = None, gate_open: bool | None = None) -> None:
+        """hs_graph_schedule; with a `request_id` (0: none) hs_graph_schedule_client: Client.send_request's Event; with `gate_open`
+        hs_graph_schedule_gate: a GateController's `_GateOpen` / `_GateClose` Event."""
+        if gate_open is not None:
+            self._check(self._lib.hs_graph_schedule_gate(self._h, int(node), int(time_ns), int(bool(gate_open))))
+        elif request_id is None:
             self._check(self._lib.hs_graph_schedule(self._h, int(node), int(time_ns)))
         else:
             self._check(self._lib.hs_graph_schedule_client(self._h, int(node), int(time_ns), int(request_id)))
@@ -398,6 +436,30 @@ def client_delay_table(policy, what: str) -> np.ndarray:
     return out
 
 
+_FLOWS = (BatchProcessor, ConveyorBelt, GateController)
+_FLOW_METRIC_OF = {"buffer_depth": BatchProcessor, "items_in_transit": ConveyorBelt, "queue_depth": GateController}
+
+
+def _flow_target_refusal(what: str, end, tgt) -> str:
+    via = " (through its NetworkLinks)" if end is not tgt else ""
+    return (f"{what}: its target{via} is the {type(end).__name__} '{end.name}' -- a completion hook on an item that a BatchProcessor, "
+            "ConveyorBelt or GateController holds is not lowered (a follow-up)")
+
+
+def flow_delay_ns(seconds, what: str, name: str) -> int:
+    """int(seconds * 1_000_000_000): what `Instant + seconds` adds to `now` (core/temporal.py:213-222) -- it does not depend on `now`,
+    so the device gets whole nanoseconds."""
+    from .lowering import UnsupportedTopology
+
+    try:
+        ns = int(seconds * 1_000_000_000)
+    except (OverflowError, ValueError, TypeError) as e:
+        raise UnsupportedTopology(f"{what}: {name} = {seconds!r} cannot be added to an Instant ({type(e).__name__}: {e})") from None
+    if not 0 <= ns < (1 << 61):
+        raise UnsupportedTopology(f"{what}: {name} = {seconds!r} is outside [0, 2^61) ns")
+    return ns
+
+
 def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
     """`sources` / `entities` of a Simulation -> the node arrays of the single-heap engine.  Refuses by name what that engine
     does not run either (lowering.UnsupportedTopology)."""
@@ -426,7 +488,8 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             raise UnsupportedTopology(f"probe '{pr.name}' is listed twice")
         add(pr)
     n_front = len(nodes)
-    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker, Bulkhead, TimeoutWrapper, Client) + _SINKS
+    lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker, Bulkhead, TimeoutWrapper, Client,
+               BatchProcessor, ConveyorBelt, GateController) + _SINKS
 
     def check(ent, where):
         if isinstance(ent, Source):
@@ -509,6 +572,18 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             tgt = ent.target
             on_wrapper = isinstance(tgt, (Bulkhead, TimeoutWrapper)) and m in N.PROBE_WRAPPER_METRICS
             on_client = isinstance(tgt, Client) and m in N.PROBE_CLIENT_METRICS
+            on_flow = isinstance(tgt, _FLOW_METRIC_OF.get(m, ()))
+            if on_flow:
+                if a.probe_metric is None:
+                    a.probe_metric = np.full(n, N.PROBE_NONE, np.uint8)
+                    a.probe_interval_s = np.ones(n, np.float64)
+                if id(tgt) not in node_of:
+                    raise UnsupportedTopology(f"probe '{ent.name}': its target is not an entity of this Simulation")
+                a.kind[i] = N.NODE_PROBE
+                a.target[i] = node_of[id(tgt)]
+                a.probe_metric[i] = N.PROBE_FLOW_METRICS[m]
+                a.probe_interval_s[i] = ent.interval
+                continue
             if m not in N.PROBE_METRICS and not on_wrapper and not on_client:
                 raise UnsupportedTopology(f"probe '{ent.name}': metric '{ent.metric}' is not sampled on the engine")
             if id(tgt) not in node_of:
@@ -609,6 +684,8 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             end, hops = tgt, 0
             while isinstance(end, NetworkLink) and end.egress is not None and hops <= n:
                 end, hops = end.egress, hops + 1
+            if isinstance(end, _FLOWS):
+                raise UnsupportedTopology(_flow_target_refusal(what, end, tgt))
             if isinstance(end, Client):
                 via = " (through its NetworkLinks)" if end is not tgt else ""
                 raise UnsupportedTopology(f"{what}: its target{via} is the Client '{end.name}' -- two completion hooks on one Event are not "
@@ -645,6 +722,8 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             end, hops = tgt, 0
             while isinstance(end, NetworkLink) and end.egress is not None and hops <= n:
                 end, hops = end.egress, hops + 1
+            if isinstance(end, _FLOWS):
+                raise UnsupportedTopology(_flow_target_refusal(what, end, tgt))
             if isinstance(end, (LoadBalancer, Bulkhead, TimeoutWrapper, Client)):
                 via = " (through its NetworkLinks)" if end is not tgt else ""
                 raise UnsupportedTopology(f"{what}: its target{via} is the {type(end).__name__} '{end.name}' -- two completion hooks on one "
@@ -661,6 +740,37 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             a.target[i] = node_of[id(tgt)]
             a.cl_params[i, 0] = -1.0 if ent.timeout is None else float(ent.timeout)
             client_delays[i] = delays
+        elif isinstance(ent, _FLOWS):
+            what = f"{type(ent).__name__} '{ent.name}'"
+            d = ent.downstream
+            if isinstance(d, (Source, Probe, HealthChecker)) or not isinstance(d, Entity) or id(d) not in node_of:
+                raise UnsupportedTopology(f"{what}: its downstream {type(d).__name__} '{getattr(d, 'name', d)}' takes no Requests")
+            if a.flow_params is None:
+                a.flow_params = np.zeros((n, 4), np.int64)
+            a.target[i] = node_of[id(d)]
+            if isinstance(ent, BatchProcessor):
+                if type(ent.batch_size) is not int:
+                    raise UnsupportedTopology(f"{what}: batch_size must be an int, got {ent.batch_size!r}")
+                if ent.batch_size > BatchProcessor.MAX_BATCH_SIZE:
+                    raise UnsupportedTopology(f"{what}: batch_size = {ent.batch_size} is beyond the {BatchProcessor.MAX_BATCH_SIZE} items of "
+                                              "one batch on the engine (BatchProcessor.MAX_BATCH_SIZE)")
+                a.kind[i] = N.NODE_BATCH_PROCESSOR
+                # the generator's `yield process_time` is float(process_time) added to an Instant, `now + timeout_s` the number itself
+                a.flow_params[i] = (ent.batch_size, flow_delay_ns(float(ent.process_time), what, "process_time"),
+                                    flow_delay_ns(ent.timeout_s, what, "timeout_s") if ent.timeout_s > 0 else 0, 0)
+            elif isinstance(ent, ConveyorBelt):
+                a.kind[i] = N.NODE_CONVEYOR
+                cap = ent._capacity
+                a.flow_params[i] = (0 if not cap > 0 else min(int(cap), (1 << 31) - 1), flow_delay_ns(float(ent.transit_time), what, "transit_time"), 0, 0)
+            else:
+                cap = ent._queue_capacity
+                if cap > GateController.MAX_QUEUE_CAPACITY:
+                    raise UnsupportedTopology(f"{what}: queue_capacity = {cap} is beyond the {GateController.MAX_QUEUE_CAPACITY} items of a "
+                                              "bounded queue on the engine (GateController.MAX_QUEUE_CAPACITY; 0 is unbounded)")
+                if ent._queue_depth:
+                    raise UnsupportedTopology(f"{what}: {ent._queue_depth} items are still queued from an earlier run (not lowered)")
+                a.kind[i] = N.NODE_GATE
+                a.flow_params[i] = (max(int(cap), 0), 0, int(ent._open_cycles), 1 if ent._is_open else 0)
         elif isinstance(ent, RateLimitedEntity):
             pol = ent.policy
             if type(pol) not in LIMITER_POLICIES:
@@ -764,7 +874,8 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
     new_index = np.empty(n, np.int64)
     per_node = [nm for nm in ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s",
                               "link_lat_min_s", "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric",
-                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params", "cl_params")
+                              "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params", "cl_params",
+                              "flow_params")
                 if getattr(a, nm) is not None]
     names = None if a.names is None else [a.names[a.name_off[i]:a.name_off[i + 1]] for i in range(n)]
     parts = []
@@ -797,6 +908,8 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
             b.lb_healthy = None
         if b.wrap_params is not None and not ((b.kind == N.NODE_BULKHEAD) | (b.kind == N.NODE_TIMEOUT_WRAPPER)).any():
             b.wrap_params = None                                           # (a part without a wrapper runs the loop it would run alone)
+        if b.flow_params is not None and not ((b.kind >= N.NODE_BATCH_PROCESSOR) & (b.kind <= N.NODE_GATE)).any():
+            b.flow_params = None                                           # (a part without a flow entity likewise)
         if b.cl_params is not None and not (b.kind == N.NODE_CLIENT).any():
             b.cl_params = None                                             # (a part without a Client likewise)
         if b.cl_params is not None:
@@ -873,6 +986,16 @@ class PartRun:
 
     def client_events(self) -> np.ndarray:
         return np.sum([e.client_events() for e in self.engines], axis=0).astype(np.int64)
+
+    def flow_events(self) -> np.ndarray:
+        return np.sum([e.flow_events() for e in self.engines], axis=0).astype(np.int64)
+
+    def flow(self, node: int) -> dict:
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            at = np.searchsorted(ids, node)
+            if at < len(ids) and ids[at] == node:
+                return e.flow(int(at))
+        raise KeyError(node)
 
     def client(self, node: int) -> dict:
         for (ids, _pos, _b), e in zip(self.parts, self.engines):
@@ -957,7 +1080,7 @@ def keyless_hazard(g: "GeneralGraph", target) -> str | None:
 
 
 def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t: np.ndarray, rec_cr: np.ndarray, device: int = 0,
-                       health=None, wrapper=None, client=None) -> None:
+                       health=None, wrapper=None, client=None, flow=None) -> None:
     """The run's per-node results onto the user's objects, under the attribute names the reference uses (lowering.write_back's
     counterpart).  `health`: node -> GraphEngine.health(node) of a graph with health state; `wrapper`: node -> GraphEngine.wrapper(node)
     of a graph with a Bulkhead or a TimeoutWrapper; `client`: node -> GraphEngine.client(node) of a graph with a Client."""
@@ -1030,6 +1153,17 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
             ent._next_request_id = w["next_request_id"]
             ent._wait_queue = [int(x) for x in w["queue_ids"]]
             ent._in_flight = {int(x): {} for x in w["in_flight_ids"]}
+        elif isinstance(ent, _FLOWS):
+            w = flow(i)                       # GraphEngine.flow(node) of a graph with one of the three
+            if isinstance(ent, BatchProcessor):
+                ent._batches_processed, ent._items_processed, ent._timeouts, ent._buffer_depth = (
+                    w["batches_processed"], w["items_processed"], w["timeouts"], w["buffer_depth"])
+            elif isinstance(ent, ConveyorBelt):
+                ent._items_transported, ent._items_rejected, ent._items_in_transit = w["items_transported"], w["items_rejected"], w["items_in_transit"]
+            else:
+                ent._passed_through, ent._queued_while_closed, ent._rejected, ent._open_cycles, ent._queue_depth = (
+                    w["passed_through"], w["queued_while_closed"], w["rejected"], w["open_cycles"], w["queue_depth"])
+                ent._is_open = bool(w["is_open"])
         elif isinstance(ent, Client):
             w = client(i)
             (ent._requests_sent, ent._responses_received, ent._timeouts, ent._retries, ent._failures) = (w[k] for k in (

@@ -14,7 +14,7 @@ from .core.temporal import Instant
 from .engine import StationEngine
 from .graph_engine import (DEFAULT_MAX_EVENTS, MAX_PARTS, GeneralGraph, GraphEngine, PartRun, keyless_hazard, lower_general, split_parts,
                            write_back_general)
-from .entities import Bulkhead, Client, Entity, HealthChecker, LoadBalancer, Server, TimeoutWrapper
+from .entities import BatchProcessor, Bulkhead, Client, ConveyorBelt, Entity, GateController, HealthChecker, LoadBalancer, Server, TimeoutWrapper
 from .faults import FaultSchedule
 from .lowering import (LazyRecords, LbGraph, LoweredGraph, UnsupportedTopology, attach_lb_probes, attach_probes, find_load_balancer, lower,
                        plain_probe_arrays, write_back_plain_probes,
@@ -145,7 +145,16 @@ class Simulation:
         firsts = [getattr(getattr(s, "_event_provider", None), "_target", None) for s in self._sources]
         return any(isinstance(e, Client) for e in self._entities + firsts)
 
+    def _has_flows(self) -> bool:
+        """A BatchProcessor, ConveyorBelt or GateController among the entities or as a Source's target: stations that hold Requests
+        back and release them together, which only the single-heap loop follows."""
+        firsts = [getattr(getattr(s, "_event_provider", None), "_target", None) for s in self._sources]
+        return any(isinstance(e, (BatchProcessor, ConveyorBelt, GateController)) for e in self._entities + firsts)
+
     def lowered(self) -> "LoweredGraph | LbGraph | GeneralGraph":
+        if self._graph is None and self._has_flows():
+            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._station_refusal = "the station, network and pipeline engines do not lower BatchProcessor, ConveyorBelt or GateController"
         if self._graph is None and self._has_clients():
             self._graph = lower_general(self._sources, self._entities, self._probes)
             self._station_refusal = "the station, network and pipeline engines do not lower a Client"
@@ -355,7 +364,7 @@ class Simulation:
         #  interval, two constant Sources of one rate in different components then look like a mixed timestamp group: undecided)
         # an auto-terminating run with limiters ends when no PRIMARY event is pending anywhere (their polls are daemons,
         # core/simulation.py:311-322): a part cannot know that of the others, so such a run stays on one heap
-        daemons = auto and bool((g.arrays.kind == N.NODE_RATE_LIMITER).any() or self._faults)
+        daemons = auto and bool((g.arrays.kind == N.NODE_RATE_LIMITER).any() or self._faults or any(len(e) > 3 for e in sched))   # (... or gate Events)
         faults = self._general_faults(g)
         # (a cancelled fault Event stays in its heap, as in the reference's: it is no candidate for the one Event beyond the end)
         parts = None if cancelled_ns or daemons or any(c for _n, _t, _on, c in faults) else split_parts(g.arrays, MAX_PARTS)
@@ -431,6 +440,20 @@ class Simulation:
             if ev.on_complete:
                 raise UnsupportedTopology(f"scheduled event {ev!r}: completion hooks are host Python (not lowered)")
             rid = None
+            if a.kind[i] == N.NODE_GATE and ev.event_type in ("_GateOpen", "_GateClose"):
+                # one Event of GateController.start_events(): a daemon without a Request
+                if not ev.daemon:
+                    raise UnsupportedTopology(f"scheduled event {ev!r}: only the daemon Events start_events() returns are lowered for a "
+                                              "GateController")
+                if cancelled_ns:
+                    raise UnsupportedTopology("cancelled Events in front of live ones are not lowered on the single-heap path")
+                if ev.time.nanoseconds < start_ns:
+                    warnings.warn(f"Time travel detected: {ev!r} lies before the simulation start; skipping event", stacklevel=3)
+                    continue
+                sched.append((i, ev.time.nanoseconds, None, ev.event_type == "_GateOpen"))
+                continue
+            if a.kind[i] == N.NODE_BATCH_PROCESSOR and ev.event_type == "_BatchTimeout":
+                raise UnsupportedTopology(f"scheduled event {ev!r}: a BatchProcessor's own '_BatchTimeout' Event is not lowered")
             if a.kind[i] == N.NODE_CLIENT:
                 # Client.send_request's Event or a plain one: the Client reads metadata request_id / attempt and never passes
                 # created_at on (client.py:233-282)
@@ -484,9 +507,9 @@ class Simulation:
         es = eng.summary()
         stats = eng.stats()
         rec = eng.records()
-        health, wrappers, clients = g.arrays.has_health, g.arrays.has_wrappers, g.arrays.has_clients
+        health, wrappers, clients, flows = g.arrays.has_health, g.arrays.has_wrappers, g.arrays.has_clients, g.arrays.has_flows
         write_back_general(g, stats, *rec, device=self._device, health=eng.health if health else None,
-                           wrapper=eng.wrapper if wrappers else None, client=eng.client if clients else None)
+                           wrapper=eng.wrapper if wrappers else None, client=eng.client if clients else None, flow=eng.flow if flows else None)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
         if health:
@@ -499,7 +522,13 @@ class Simulation:
         if clients:
             # the Clients' request / response / timeout Events: three more internal kinds, counted the same way
             self._client_by_kind = eng.client_events()
-        if (health or wrappers or clients) and not self._faults:
+        if flows:
+            # the flow entities' Events: eight more internal kinds, counted the same way; a `_BatchTimeout` popped after its batch had
+            # started was cancelled (core/simulation.py:326-329)
+            fe = eng.flow_events()
+            self._flow_by_kind = fe[:N.FLOW_KINDS]
+            self._events_cancelled += int(fe[N.FLOW_KINDS])
+        if (health or wrappers or clients or flows) and not self._faults:
             self._internal_by_kind = eng.faults()[1]
         if self._faults:
             crashed, internal, popped_cancelled = eng.faults()

@@ -194,6 +194,9 @@ typedef enum hs_probe_metric {
     HS_PROBE_BH_PERMITS = 10,  /* Bulkhead.available_permits */
     HS_PROBE_TW_IN_FLIGHT = 11,/* TimeoutWrapper.in_flight_count */
     HS_PROBE_CL_IN_FLIGHT = 12,/* Client.in_flight_count (general graphs only) */
+    HS_PROBE_BP_BUFFER_DEPTH = 13, /* BatchProcessor.buffer_depth (general graphs only) */
+    HS_PROBE_CV_IN_TRANSIT = 14,   /* ConveyorBelt.items_in_transit */
+    HS_PROBE_GT_QUEUE_DEPTH = 15,  /* GateController.queue_depth */
     HS_PROBE_NONE = 255
 } hs_probe_metric;
 typedef enum hs_profile_kind { HS_PROF_CONSTANT = 0, HS_PROF_LINEAR_RAMP = 1, HS_PROF_SPIKE = 2 } hs_profile_kind;
@@ -750,7 +753,10 @@ typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK
                              HS_NODE_HEALTH_CHECKER = 8, /* HealthChecker: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_health_checker */
                              HS_NODE_BULKHEAD = 9,        /* Bulkhead: `target` = the entity it protects; everything else: hs_graph_set_wrapper */
                              HS_NODE_TIMEOUT_WRAPPER = 10, /* TimeoutWrapper: `target` = the entity it wraps; everything else: hs_graph_set_wrapper */
-                             HS_NODE_CLIENT = 11          /* Client: `target` = the entity it sends to; everything else: hs_graph_set_client */
+                             HS_NODE_CLIENT = 11,         /* Client: `target` = the entity it sends to; everything else: hs_graph_set_client */
+                             HS_NODE_BATCH_PROCESSOR = 12, /* BatchProcessor, ConveyorBelt, GateController: `target` = their downstream; */
+                             HS_NODE_CONVEYOR = 13,        /* everything else: hs_graph_set_flow */
+                             HS_NODE_GATE = 14
 } hs_node_kind;
 
 typedef struct hs_graph_config {
@@ -1011,6 +1017,46 @@ int hs_graph_schedule_client(hs_graph *g, int32_t node, int64_t time_ns, int32_t
  * node = -1 with the two node outputs NULL: the event counts alone.  The response times are rows of the record log
  * (hs_graph_read_records): node = the Client, t = the response time in ns, value = start_time in ns, in the order they were appended. */
 int hs_graph_get_client(hs_graph *g, int32_t node, int64_t *counters, int64_t *in_flight_keys, int64_t cap, int64_t *events);
+/* BatchProcessor, ConveyorBelt and GateController (components/industrial/batch_processor.py, conveyor.py, gate_controller.py): the
+ * stations that hold Requests back and release them together.  A graph that holds one runs a sixth instantiation of the loop (it
+ * carries the fault, health, wrapper and Client code too).  Eight more internal kinds, in this order: a Request at a BatchProcessor,
+ * its `_BatchTimeout`, the continuation of a batch in process; a Request at a ConveyorBelt, the continuation of its transit; a Request
+ * at a GateController, its `_GateOpen`, its `_GateClose`.  They count in hs_summary.events_processed, not in events_by_kind.  The
+ * two continuations resume a generator and are never dropped; the other six are aimed at the entity and are dropped while it is
+ * crashed or paused.  Every forwarded Event is a NEW Event with the item's context (created_at survives) and no completion hook.
+ *   BatchProcessor: an item joins the buffer; the first item of an empty buffer with a timeout constructs the `_BatchTimeout` Event at
+ *     now + timeout_ns and nothing else; otherwise len(buffer) >= batch_size starts a batch: the buffer becomes the batch, the pending
+ *     timeout is cancelled (its entry stays in the heap, is popped without being processed and counts as cancelled), and after
+ *     process_ns every item goes downstream in buffer order, in ONE handler.  Several batches may be in process at once.
+ *   ConveyorBelt: at capacity (> 0) the item is rejected; otherwise it is in transit for transit_ns, then goes downstream.
+ *   GateController: open, an item passes at once; closed, it joins the queue, or is rejected when queue_capacity (> 0) items wait.
+ *     `_GateOpen` on a closed gate forwards the whole queue in FIFO order in ONE handler.  Gate Events are daemons.
+ * A handler that releases N items is only entered once the heap has room for all N (the run stops in front of the Event and the heap
+ * grows, as for any other Event): a release is never partial.  The delays are whole nanoseconds the host computed
+ * (int(seconds * 1e9), core/temporal.py:222): they do not depend on `now`.
+ *
+ * hs_graph_set_flow, before the first run (HS_E_STATE afterwards; every such node is configured before a run):
+ *   BatchProcessor  count = batch_size (1 .. HS_FLOW_MAX_ITEMS), delay_ns = process_time, aux_ns = timeout (<= 0: none), flag unused
+ *   ConveyorBelt    count = capacity (<= 0: unlimited), delay_ns = transit_time
+ *   GateController  count = queue_capacity (<= 0: unbounded; at most HS_FLOW_MAX_ITEMS), flag = is_open when the run begins,
+ *                   aux_ns = open_cycles counted so far (GateController.open() on the host before the run), no time
+ * The reference's own ValueErrors as HS_E_INVALID with its texts. */
+#define HS_FLOW_MAX_ITEMS (1 << 20)
+#define HS_FLOW_COUNTERS 8
+#define HS_FLOW_KINDS 8
+int hs_graph_set_flow(hs_graph *g, int32_t node, int64_t count, int64_t delay_ns, int64_t aux_ns, int32_t flag);
+/* A `_GateOpen` (open != 0) or `_GateClose` Event for GateController `node` -- one Event of GateController.start_events(), a daemon --
+ * numbered in call order with the other scheduled entries. */
+int hs_graph_schedule_gate(hs_graph *g, int32_t node, int64_t time_ns, int32_t open);
+/* After a run, for `node` one of the three (any output may be NULL):
+ *   counters[HS_FLOW_COUNTERS]  BatchProcessor: batches_processed, items_processed, timeouts, buffer_depth, 0, 0, 0, 0
+ *                               ConveyorBelt:   items_transported, items_rejected, items_in_transit, 0 ...
+ *                               GateController: passed_through, queued_while_closed, rejected, open_cycles, queue_depth, is_open, 0, 0
+ *   events[HS_FLOW_KINDS]       the graph's Events of the eight kinds above; events_processed == sum(events_by_kind) + the internal kinds
+ *                               of hs_graph_get_faults, _health, _wrapper, _client + sum(events)
+ *   cancelled                   `_BatchTimeout` Events popped after their batch had started (events_cancelled counts them).
+ * node = -1 with counters NULL: the graph's counts alone. */
+int hs_graph_get_flow(hs_graph *g, int32_t node, int64_t *counters, int64_t *events, int64_t *cancelled);
 /* Auto-termination (core/simulation.py:306-322, end_time = Infinity): a run to end_ns = 2^61 ends in front of a pop when only daemon
  * events -- the limiters' polls -- are pending.  A run with any other end processes polls like any event. */
 /* Debug / tests only (no engine path calls it; the null stream, its own allocations): FixedWindowPolicy._get_window_start on the device, one (now_ns, window_s) pair per thread: out_div[i] = Python's float
