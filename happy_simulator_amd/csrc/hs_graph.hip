@@ -114,7 +114,8 @@ struct GRequest {                              // 32 bytes: the payload Event's 
     double service_s;                          // service_time_s of the generator frame (server/server.py:246-247); dead until WORK: while a
                                                // wrapper's hook rides on the Event (and in a Bulkhead's queue) the wrapper's request id, as bits
                                                // (a Client's hook: its key, request_id | attempt << 30)
-    int64_t client;                            // context["metadata"]["client_id"] (-1: none)
+    int64_t client;                            // context["metadata"]["client_id"] (-1: none; <= -2: no client_id, but the metadata of the
+                                               // Client the Request passed last: -2 - its key)
     int32_t next;                              // FIFO / free list
     int32_t hook : 31;                         // LoadBalancer / checker / wrapper whose completion hook rides on the Event (-1: none)
     uint32_t pre : 1;                          // `idx` came from the process-wide counter (GEvent::pad), set where the payload is queued
@@ -989,6 +990,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                             key = ev_id(e);
                             r = req_free;
                             if (r >= 0) req_free = c.reqs[r].next; else r = req_len++;   // (room: tested in front of the pop)
+                        } else if (c.reqs[r].client <= -2) {
+                            // the Request passed a Client before: every handler on the way forwards the context, so this Client reads
+                            // THAT Client's metadata (core/entity.py:100-105, client.py:235-237) -- its request_id and its attempt
+                            key = -2 - c.reqs[r].client;
                         }
                         int i = 0;
                         while (i < s.qlen && tab[2 * i] != key) ++i;
@@ -996,7 +1001,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         if (i == s.qlen) s.qlen += 1;
                         s.a += 1;
                         if ((key >> kKeyAttemptShift) > 1) s.d += 1;
-                        GRequest q; q.created = t; q.idx = 0; q.service_s = __longlong_as_double(key); q.client = -1; q.next = -1; q.hook = n; q.pre = 0;
+                        GRequest q; q.created = t; q.idx = 0; q.service_s = __longlong_as_double(key); q.client = -2 - key; q.next = -1; q.hook = n; q.pre = 0;
                         c.reqs[r] = q;
                         H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r));
                         if (p.sub) H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvClTimeout, n, key));

@@ -9,10 +9,10 @@
   pre = [[["flow", i], "open" | "close"], ...]: GateController.open() / close() on the host before the Simulation is built.
   a Source may hold stop_s: stop_after, in seconds.
 
-This family keeps its own `wire`, `build` and `results` (tests/graph_family.py builds its own pools and knows no seventh one);
-tests/golden/make_golden_flow.py hands `wire` the reference's classes and runs the LIVE reference on every spec listed here
+`wire`, `fault_targets` and `schedule_all` are tests/graph_family.py's; this family keeps its own `build` and `results`.
+tests/golden/make_golden_flow.py runs the LIVE reference on every spec listed here through tests/golden/record_family.py
 (tests/recorded.py-style store: FLOW below).  Entities: servers + lbs + routers + links + limiters + sinks + wrappers + clients +
-flows -- node numbers in the recorded traces and the process-wide sort counter depend on that order and on the order of the
+flows + checkers -- node numbers in the recorded traces and the process-wide sort counter depend on that order and on the order of the
 schedule() calls.  Every case stays small: a few seconds of a Source of rate ~10.
 
   FIXTURES        named cases; TRACED: recorded with their full event trace
@@ -25,7 +25,6 @@ there: the buffer is only ever emptied by `_process_batch`, which cancels the pe
 """
 import numpy as np
 
-import client_specs as CS
 import fault_specs as FS
 import graph_family as GF
 import happy_simulator_amd as hs
@@ -68,118 +67,34 @@ def plain(on, *times):
     return [[on, t] for t in times]
 
 
-def _g(name, flows, **kw):
-    return XS._g(name, [], flows=list(flows), **kw)
+def _g(name, flows, *, wrappers=(), **kw):
+    return XS._g(name, list(wrappers), flows=list(flows), **kw)
 
 
-def make_flow(ns, i, fl, to):
-    """The spec's entity from the namespace `ns` (the product, or the reference's industrial package)."""
-    if fl["kind"] == "batch":
-        return ns.BatchProcessor(f"flow{i}", to, batch_size=fl["n"], process_time=fl["pt"], timeout_s=fl["ts"])
-    if fl["kind"] == "conveyor":
-        return ns.ConveyorBelt(f"flow{i}", to, fl["tt"], capacity=fl["cap"])
-    return ns.GateController(f"flow{i}", to, schedule=[tuple(x) for x in fl["sched"]], initially_open=fl["open"], queue_capacity=fl["cap"])
+make_flow = GF.make_flow
 
 
 def wire(spec, F, ns):
-    """graph_family.wire with the `flows` pool: the spec's objects from the factory `F` and the namespace `ns`, every reference
-    resolved once its object exists."""
-    sinks = [F.sink(j) for j in range(spec["n_sinks"])]
-    servers = [F.server(i, sv) for i, sv in enumerate(spec["servers"])]
-    limiters = [F.limiter(i, lm) for i, lm in enumerate(spec.get("limiters") or [])]
-    pools = {"sink": sinks, "server": servers, "limiter": limiters}
-    links = pools["link"] = [F.link(l, lk) for l, lk in enumerate(spec["links"])]
-    lbs = pools["lb"] = [F.lb(j, lb, [servers[b] for b in lb["backends"]]) for j, lb in enumerate(spec.get("lbs") or [])]
-    routers = pools["router"] = [None] * len(spec["routers"])
-    wrappers = pools["wrapper"] = [None] * len(spec.get("wrappers") or [])
-    clients = pools["client"] = [None] * len(spec.get("clients") or [])
-    flows = pools["flow"] = [None] * len(spec.get("flows") or [])
-
-    def ref(r):
-        return servers[r] if isinstance(r, int) else pools[r[0]][r[1]]
-
-    def ready(r):
-        return isinstance(r, int) or pools[r[0]][r[1]] is not None
-
-    pending = ([("router", r) for r in range(len(routers))] + [("wrapper", i) for i in range(len(wrappers))] +
-               [("client", i) for i in range(len(clients))] + [("flow", i) for i in range(len(flows))])
-    while pending:
-        progressed = False
-        for kind, i in list(pending):
-            if kind == "router" and all(ready(t) for t in spec["routers"][i]["targets"]):
-                routers[i] = F.router(i, [ref(t) for t in spec["routers"][i]["targets"]])
-            elif kind == "wrapper" and ready(spec["wrappers"][i]["to"]):
-                w = spec["wrappers"][i]
-                wrappers[i] = (ns.Bulkhead(f"bh{i}", ref(w["to"]), max_concurrent=w["mc"], max_wait_queue=w["mq"], max_wait_time=w["mw"])
-                               if w["kind"] == "bulkhead" else ns.TimeoutWrapper(f"tw{i}", ref(w["to"]), timeout=w["timeout"]))
-            elif kind == "client" and ready(spec["clients"][i]["to"]):
-                c = spec["clients"][i]
-                clients[i] = ns.Client(f"cl{i}", ref(c["to"]), timeout=c["timeout"], retry_policy=CS.make_policy(ns, c["policy"]))
-            elif kind == "flow" and ready(spec["flows"][i]["to"]):
-                flows[i] = make_flow(ns, i, spec["flows"][i], ref(spec["flows"][i]["to"]))
-            else:
-                continue
-            pending.remove((kind, i))
-            progressed = True
-        assert progressed, "routers, wrappers, clients and flows form a cycle"
-    for l, lk in enumerate(spec["links"]):
-        links[l].egress = None if lk["to"] is None else ref(lk["to"])
-    for i, lm in enumerate(spec.get("limiters") or []):
-        limiters[i]._downstream = ref(lm["out"])
-    for i, sv in enumerate(spec["servers"]):
-        if sv.get("out") is not None:
-            servers[i].downstream = ref(sv["out"])
-    sources = pools["source"] = [F.source(k, sc, ref(sc["to"])) for k, sc in enumerate(spec["sources"])]
-    probes = pools["probe"] = [F.probe(ref(on), metric, interval) for on, metric, interval in spec.get("probes") or []]
-    pools["checker"] = []
-    for on, what in spec.get("pre") or []:
-        getattr(pools[on[0]][on[1]], what)()
-    entities = servers + lbs + routers + links + limiters + sinks + wrappers + clients + flows
-    return pools, sources, probes, entities
+    """graph_family.wire: the one wiring of every recorded family (a flow spec holds no checker)."""
+    return GF.wire(spec, F, ns)
 
 
 def fault_targets(pools):
-    """graph_family.fault_targets, then the flow entities."""
-    return GF.fault_targets(pools) + list(pools["flow"])
+    """graph_family.fault_targets: the flow entities stand behind the Clients."""
+    return GF.fault_targets(pools)
 
 
 def schedule_all(spec, pools, sim, event_cls, at):
-    """The spec's `schedule` list on `sim`, for either library: plain Requests and the gates' start_events()."""
-    for on, t_s, *mode in spec.get("schedule") or []:
-        target = pools[on[0]][on[1]]
-        if mode and mode[0] == "gate":
-            for ev in target.start_events():
-                sim.schedule(ev)
-        else:
-            sim.schedule(event_cls(time=at(t_s), event_type="Request", target=target))
+    """graph_family.schedule_all: plain Requests and the gates' start_events()."""
+    GF.schedule_all(spec, pools, sim, event_cls, at, GF.early_starts(spec, pools))
 
 
-class Product(GF.Product):
-    @staticmethod
-    def source(k, sc, to):
-        make = hs.Source.poisson if sc["kind"] == "poisson" else hs.Source.constant
-        return make(rate=sc["rate"], target=to, name=f"src{k}",
-                    **({} if sc.get("stop_s") is None else {"stop_after": hs.Instant.from_seconds(sc["stop_s"])}))
+Product = GF.Product
 
 
 def build(spec, seed=None, **sim_kw):
-    """(Simulation, entities by pool) of the product, wired like the recorded reference run."""
-    pools, sources, probes, entities = wire(spec, Product, hs)
-    start_ns = int(spec.get("start_ns", 0))
-
-    def at(t_s):
-        return hs.Instant(start_ns + hs.Instant.from_seconds(t_s).nanoseconds)
-
-    fs, handles = GF.make_schedule(hs, spec, pools)
-    sim = hs.Simulation(sources=sources, entities=entities, seed=spec["seed"] if seed is None else seed, max_graph_events=400_000,
-                        fault_schedule=fs, **({} if spec.get("auto") else {"end_time": at(spec["end_s"])}),
-                        **({"start_time": hs.Instant(start_ns)} if start_ns else {}), **({"probes": [p for p, _ in probes]} if probes else {}),
-                        **sim_kw)
-    GF.cancel_after(spec, handles)
-    schedule_all(spec, pools, sim, hs.Event, at)
-    pools["probes"] = probes
-    pools["fault_schedule"], pools["handles"] = fs, handles
-    return sim, pools
+    """graph_family.build: (Simulation, entities by pool) of the product, wired like the recorded reference run."""
+    return GF.build(spec, seed, **sim_kw)
 
 
 def flow_results(pools):

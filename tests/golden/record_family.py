@@ -1,4 +1,4 @@
-"""The one run of the LIVE upstream reference behind tests/golden/make_golden_{rate_limiter,faults,health,resilience,client}.py: the
+"""The one run of the LIVE upstream reference behind tests/golden/make_golden_{rate_limiter,faults,health,resilience,client,flow,mixed}.py: the
 reference's own event loop over its own components, wired by tests/graph_family.py's wire() like the product's, with the Philox
 stream plugs of make_golden.py choosing the random numbers.  Importing this module puts tests/, tests/golden/ and the repository
 root (the product: the recorders assert that it takes every spec) on sys.path, so a recorder starts from a clean shell.
@@ -22,6 +22,7 @@ for _p in (os.path.dirname(os.path.dirname(HERE)), os.path.dirname(HERE), HERE):
 
 import client_specs as CS  # noqa: E402
 import fault_specs as FS  # noqa: E402
+import flow_specs as FL  # noqa: E402
 import graph_family as GF  # noqa: E402
 import health_specs as HS  # noqa: E402
 import rate_limiter_specs as RS  # noqa: E402
@@ -30,6 +31,9 @@ import strategy_specs as SS  # noqa: E402
 import make_golden as MG  # noqa: E402  (installs the reference's import path; the stream plugs and the trace classifier)
 import hs_streams_py as hs  # noqa: E402
 import happysimulator.components.client as ref_client  # noqa: E402
+import happysimulator.components.industrial.batch_processor as ref_bp  # noqa: E402
+import happysimulator.components.industrial.conveyor as ref_cv  # noqa: E402
+import happysimulator.components.industrial.gate_controller as ref_gt  # noqa: E402
 import happysimulator.faults as ref_faults  # noqa: E402
 from happysimulator import ConstantLatency, Instant, Server, Simulation, Sink, Source  # noqa: E402
 from happysimulator.components.load_balancer import HealthChecker  # noqa: E402
@@ -39,13 +43,14 @@ from happysimulator.components.network.link import NetworkLink  # noqa: E402
 from happysimulator.components.rate_limiter import policy as ref_policy  # noqa: E402
 from happysimulator.components.rate_limiter.rate_limited_entity import RateLimitedEntity  # noqa: E402
 from happysimulator.components.resilience import Bulkhead, TimeoutWrapper  # noqa: E402
-from happysimulator.core.event import Event  # noqa: E402
+from happysimulator.core.event import Event, ProcessContinuation  # noqa: E402
 from happysimulator.core.temporal import Duration  # noqa: E402
 from happysimulator.instrumentation.probe import Probe  # noqa: E402
 from happysimulator.load.profile import ConstantRateProfile  # noqa: E402
 from happysimulator.load.providers.constant_arrival import ConstantArrivalTimeProvider  # noqa: E402
 from happysimulator.load.source import SimpleEventProvider  # noqa: E402
 
+BatchProcessor, ConveyorBelt, GateController = ref_bp.BatchProcessor, ref_cv.ConveyorBelt, ref_gt.GateController
 # trace / by_kind kinds: make_golden.EV (0 .. 14), then what each family added
 EV = dict(MG.EV)
 for _name in ("lim_request", "lim_poll",                                   # 15, 16: a Request at a limiter, a limiter's poll
@@ -53,11 +58,13 @@ for _name in ("lim_request", "lim_poll",                                   # 15,
               "hc_cycle", "hc_resp", "hc_timeout",                         # 19 .. 21: a checker's cycle / response / timeout
               "bh_req", "bh_resp", "bh_timeout",                           # 22 .. 24: a Request at a Bulkhead, its response, its timeout
               "tw_req", "tw_resp", "tw_timeout",                           # 25 .. 27: the same of a TimeoutWrapper
-              "cl_req", "cl_resp", "cl_timeout"):                          # 28 .. 30: the same of a Client
-    EV[_name] = len(EV)
-assert EV["lim_request"] == 15 and EV["cl_req"] == 28
+              "cl_req", "cl_resp", "cl_timeout",                           # 28 .. 30: the same of a Client
+              *FL.EV_FLOW):                                                # 31 .. 38: a Request at a BatchProcessor, its `_BatchTimeout`, the
+    EV[_name] = len(EV)                                                    # continuation of a batch; a Request at a ConveyorBelt, the continuation
+assert EV["lim_request"] == 15 and EV["cl_req"] == 28                      # of its transit; a Request at a GateController, `_GateOpen`, `_GateClose`
+assert EV["bp_item"] == FL.EV_FLOW_FIRST and len(EV) == 39
 N_KINDS = dict(rate_limiter=EV["lim_poll"] + 1, faults=EV["fault_off"] + 1, health=EV["hc_timeout"] + 1, resilience=EV["tw_timeout"] + 1,
-               client=EV["cl_timeout"] + 1)
+               client=EV["cl_timeout"] + 1, flow=len(EV), mixed=len(EV))
 _FAULT_ON = ("fault.crash:", "fault.pause:")
 _FAULT_OFF = ("fault.restart:", "fault.resume:")
 # event_type -> kind of the Events an entity sends itself; any other Event at it is a request
@@ -67,13 +74,15 @@ _OWN_KINDS = {HealthChecker: {"_health_check_cycle": EV["hc_cycle"], "_health_ch
               ref_client.Client: {"_client_response": EV["cl_resp"], "_client_timeout": EV["cl_timeout"], None: EV["cl_req"]}}
 # a Probe's metric -> the reference attribute it reads (the limiters', wrappers' and Clients' metrics go by their own names)
 REF_METRIC = dict({k: v[1] for k, v in MG.PROBE_METRICS.items()}, queue_depth="queue_depth", active_count="active_count",
-                  available_permits="available_permits", in_flight_count="in_flight_count")
+                  available_permits="available_permits", in_flight_count="in_flight_count", buffer_depth="buffer_depth",
+                  items_in_transit="items_in_transit")
 REF_STRATEGY = {"wrr": "WeightedRoundRobin", "ip_hash": "IPHash", "least_conn": "LeastConnections", "wlc": "WeightedLeastConnections",
                 "round_robin": "RoundRobin", "chash": "ConsistentHash", "random": "Random"}
 # where wire() and make_schedule() find the reference's classes
 REF_NS = types.SimpleNamespace(Bulkhead=Bulkhead, TimeoutWrapper=TimeoutWrapper, HealthChecker=HealthChecker, Client=ref_client.Client,
                                FixedRetry=ref_client.FixedRetry, ExponentialBackoff=ref_client.ExponentialBackoff,
-                               FaultSchedule=ref_faults.FaultSchedule, CrashNode=ref_faults.CrashNode, PauseNode=ref_faults.PauseNode)
+                               FaultSchedule=ref_faults.FaultSchedule, CrashNode=ref_faults.CrashNode, PauseNode=ref_faults.PauseNode,
+                               BatchProcessor=BatchProcessor, ConveyorBelt=ConveyorBelt, GateController=GateController)
 MAX_EVENTS = 60_000
 
 
@@ -155,8 +164,10 @@ class _Reference:
         prof = ConstantRateProfile(rate=sc["rate"])
         prov = (MG.PhiloxPoissonArrival(prof, Instant.Epoch, hs.Stream(self.seed, k, hs.STREAM_ARRIVAL)) if sc["kind"] == "poisson"
                 else ConstantArrivalTimeProvider(prof, start_time=Instant.Epoch))
+        if sc.get("stop_s") is not None:                   # (a Source that stops handing out Requests: tests/flow_specs.py)
+            assert sc["kind"] == "constant" and not sc.get("n_clients")
         ep = (MG.PhiloxClientProvider(to, sc["n_clients"], hs.Stream(self.seed, k, hs.STREAM_KEY)) if sc.get("n_clients")
-              else SimpleEventProvider(to, "Request", None))
+              else SimpleEventProvider(to, "Request", None if sc.get("stop_s") is None else MG._at(self.spec, sc["stop_s"])))
         return Source(f"src{k}", ep, prov)
 
     def probe(self, target, metric, interval):
@@ -171,6 +182,13 @@ def classify(e, node_of, by_name):
     et = e.event_type
     if et.startswith(_FAULT_ON) or et.startswith(_FAULT_OFF):
         return (EV["fault_on"] if et.startswith(_FAULT_ON) else EV["fault_off"]), by_name[et.split(":", 1)[1]]
+    t = e.target
+    if isinstance(t, BatchProcessor):
+        return (EV["bp_cont"] if isinstance(e, ProcessContinuation) else EV["bp_timeout"] if et == "_BatchTimeout" else EV["bp_item"]), node_of[id(t)]
+    if isinstance(t, ConveyorBelt):
+        return (EV["cv_cont"] if isinstance(e, ProcessContinuation) else EV["cv_item"]), node_of[id(t)]
+    if isinstance(t, GateController):
+        return (EV["gt_open"] if et == "_GateOpen" else EV["gt_close"] if et == "_GateClose" else EV["gt_item"]), node_of[id(t)]
     own = _OWN_KINDS.get(type(e.target))
     if own is not None:
         return own[et if et in own else None], node_of[id(e.target)]
@@ -242,8 +260,10 @@ _SECTION = dict(
     health=lambda c: HS.health_results(c.spec, c.pools),
     # probe_drops: probes a full bounded queue refused (their checks pass all the same)
     health_events=lambda c: dict(health_events=c.by_kind[EV["hc_cycle"]:].copy(), probe_drops=int(c.probe_drops)),
+    probe_drops=lambda c: dict(probe_drops=int(c.probe_drops)),
     wrappers=lambda c: XS.wrapper_results(c.pools),
     clients=lambda c: CS.client_results(c.pools),
+    flows=lambda c: FL.flow_results(c.pools),
     fault_events=lambda c: dict(fault_events=int(c.by_kind[EV["fault_on"]] + c.by_kind[EV["fault_off"]])),
     cancelled=lambda c: dict(events_cancelled=int(c.summary.events_cancelled)),
 )
@@ -253,6 +273,8 @@ SECTIONS = dict(
     health=("time_travel", "stats", "faults", "health", "health_events", "cancelled"),
     resilience=("time_travel", "stats", "probes", "limiters", "faults", "health", "wrappers", "fault_events", "cancelled"),
     client=("time_travel", "stats", "probes", "limiters", "faults", "health", "wrappers", "clients", "fault_events", "cancelled"),
+    flow=("time_travel", "stats", "probes", "limiters", "faults", "flows", "fault_events", "cancelled"),
+    mixed=("time_travel", "stats", "probes", "limiters", "faults", "health", "probe_drops", "wrappers", "clients", "flows", "fault_events", "cancelled"),
 )
 
 

@@ -7,10 +7,11 @@ client (tests/<family>_specs.py hold the specs and each family's own result read
   checkers, unhealthy                                      tests/health_specs.py
   wrappers                                                 tests/resilience_specs.py
   clients, the schedule's send / again / cancel modes      tests/client_specs.py
+  flows, pre, the schedule's gate mode, a Source's stop_s  tests/flow_specs.py
 
 and a list that a spec does not hold is an empty one.  `wire()` serves both libraries: `build()` hands it the product's classes,
 tests/golden/record_family.py the reference's, so both see the same objects in the same order.  Entities: servers + lbs + routers +
-links + limiters + sinks + wrappers + clients + checkers -- node numbers in the recorded traces and the process-wide sort counter of
+links + limiters + sinks + wrappers + clients + flows + checkers -- node numbers in the recorded traces and the process-wide sort counter of
 Events depend on that order and on the order of the schedule() calls below.
 
 Each family records what the one before it records and something more; `results(spec, sim, pools, family)` reads a family's keys
@@ -29,10 +30,19 @@ import strategy_specs as SS
 FAMILIES = ("rate_limiter", "faults", "health", "resilience", "client")
 
 
+def make_flow(ns, i, fl, to):
+    """The spec's flow entity from the namespace `ns` (the product, or the reference's industrial package)."""
+    if fl["kind"] == "batch":
+        return ns.BatchProcessor(f"flow{i}", to, batch_size=fl["n"], process_time=fl["pt"], timeout_s=fl["ts"])
+    if fl["kind"] == "conveyor":
+        return ns.ConveyorBelt(f"flow{i}", to, fl["tt"], capacity=fl["cap"])
+    return ns.GateController(f"flow{i}", to, schedule=[tuple(x) for x in fl["sched"]], initially_open=fl["open"], queue_capacity=fl["cap"])
+
+
 def wire(spec, F, ns):
     """The spec's objects from the factory `F` (sink, server, link, lb, router, limiter, source, probe) and the namespace `ns` (where
-    Bulkhead, TimeoutWrapper, Client, the retry policies and HealthChecker come from): pools by kind, every reference resolved once
-    its object exists."""
+    Bulkhead, TimeoutWrapper, Client, the retry policies, HealthChecker and the three flow entities come from): pools by kind, every
+    reference resolved once its object exists."""
     sinks = [F.sink(j) for j in range(spec["n_sinks"])]
     servers = [F.server(i, sv) for i, sv in enumerate(spec["servers"])]
     limiters = [F.limiter(i, lm) for i, lm in enumerate(spec.get("limiters") or [])]
@@ -42,6 +52,7 @@ def wire(spec, F, ns):
     routers = pools["router"] = [None] * len(spec["routers"])
     wrappers = pools["wrapper"] = [None] * len(spec.get("wrappers") or [])
     clients = pools["client"] = [None] * len(spec.get("clients") or [])
+    flows = pools["flow"] = [None] * len(spec.get("flows") or [])
 
     def ref(r):
         return servers[r] if isinstance(r, int) else pools[r[0]][r[1]]
@@ -49,7 +60,8 @@ def wire(spec, F, ns):
     def ready(r):
         return isinstance(r, int) or pools[r[0]][r[1]] is not None
 
-    pending = [("router", r) for r in range(len(routers))] + [("wrapper", i) for i in range(len(wrappers))] + [("client", i) for i in range(len(clients))]
+    pending = ([("router", r) for r in range(len(routers))] + [("wrapper", i) for i in range(len(wrappers))] +
+               [("client", i) for i in range(len(clients))] + [("flow", i) for i in range(len(flows))])
     while pending:
         progressed = False
         for kind, i in list(pending):
@@ -62,11 +74,13 @@ def wire(spec, F, ns):
             elif kind == "client" and ready(spec["clients"][i]["to"]):
                 c = spec["clients"][i]
                 clients[i] = ns.Client(f"cl{i}", ref(c["to"]), timeout=c["timeout"], retry_policy=CS.make_policy(ns, c["policy"]))
+            elif kind == "flow" and ready(spec["flows"][i]["to"]):
+                flows[i] = make_flow(ns, i, spec["flows"][i], ref(spec["flows"][i]["to"]))
             else:
                 continue
             pending.remove((kind, i))
             progressed = True
-        assert progressed, "routers, wrappers and clients form a cycle"
+        assert progressed, "routers, wrappers, clients and flows form a cycle"
     for l, lk in enumerate(spec["links"]):
         links[l].egress = None if lk["to"] is None else ref(lk["to"])
     for i, lm in enumerate(spec.get("limiters") or []):
@@ -82,7 +96,9 @@ def wire(spec, F, ns):
         lbs[j].mark_unhealthy(servers[spec["lbs"][j]["backends"][q]])
     for (pool, idx), name in spec.get("names") or []:
         pools[pool][idx].name = name
-    entities = servers + lbs + routers + links + limiters + sinks + wrappers + clients + pools["checker"]
+    for on, what in spec.get("pre") or []:
+        getattr(pools[on[0]][on[1]], what)()
+    entities = servers + lbs + routers + links + limiters + sinks + wrappers + clients + flows + pools["checker"]
     return pools, sources, probes, entities
 
 
@@ -113,7 +129,8 @@ def fault_targets(pools):
     """Every object a fault can name, in one order for both libraries: Sources, Probes, then the entities."""
     probes = [p[0] if isinstance(p, tuple) else p for p in pools["probe"]]
     return (list(pools["source"]) + probes + list(pools["server"]) + list(pools["lb"]) + list(pools["router"]) + list(pools["link"]) +
-            list(pools["limiter"]) + list(pools["sink"]) + list(pools["wrapper"]) + list(pools["client"]) + list(pools["checker"]))
+            list(pools["limiter"]) + list(pools["sink"]) + list(pools["wrapper"]) + list(pools["client"]) + list(pools["flow"]) +
+            list(pools["checker"]))
 
 
 def early_starts(spec, pools):
@@ -123,14 +140,21 @@ def early_starts(spec, pools):
 
 
 def schedule_all(spec, pools, sim, event_cls, at, early_events):
-    """The spec's `schedule` list (tests/client_specs.py has the three modes of a Client's entries), then sim.schedule(checker.start())
-    as the spec says, on `sim`, for either library."""
+    """The spec's `schedule` list (tests/client_specs.py has the three modes of a Client's entries, tests/flow_specs.py the "gate"
+    mode: every Event of the gate's start_events()), then sim.schedule(checker.start()) as the spec says, on `sim`, for either library."""
     last, cancel = None, []
     for on, t_s, *mode in spec.get("schedule") or []:
         target = pools[on[0]][on[1]]
         mode = mode[0] if mode else "plain"
         if mode == "again":
             sim.schedule(last)
+            continue
+        if mode == "gate":
+            for ev in target.start_events():
+                sim.schedule(ev)
+            continue
+        if mode == "start":                              # (tests/mixed_specs.py: a checker started in the middle of the list)
+            sim.schedule(target.start())
             continue
         if mode == "plain":
             last = event_cls(time=at(t_s), event_type="Request", target=target)
@@ -189,14 +213,15 @@ class Product:
         make = hs.Source.poisson if sc["kind"] == "poisson" else hs.Source.constant
         if sc.get("n_clients"):
             return make(rate=sc["rate"], event_provider=hs.ClientKeyEventProvider(to, n_clients=sc["n_clients"]), name=f"src{k}")
-        return make(rate=sc["rate"], target=to, name=f"src{k}")
+        return make(rate=sc["rate"], target=to, name=f"src{k}",
+                    **({} if sc.get("stop_s") is None else {"stop_after": hs.Instant.from_seconds(sc["stop_s"])}))
 
     @staticmethod
     def probe(target, metric, interval):
         return hs.Probe.on(target, metric, interval=interval)
 
 
-def build(spec, seed=None):
+def build(spec, seed=None, **sim_kw):
     """(Simulation, entities by pool) of the product, wired like the recorded reference run."""
     pools, sources, probes, entities = wire(spec, Product, hs)
     start_ns = int(spec.get("start_ns", 0))
@@ -210,7 +235,8 @@ def build(spec, seed=None):
     #  events, not minutes)
     sim = hs.Simulation(sources=sources, entities=entities, seed=spec["seed"] if seed is None else seed, max_graph_events=400_000,
                         fault_schedule=fs, **({} if spec.get("auto") else {"end_time": at(spec["end_s"])}),
-                        **({"start_time": hs.Instant(start_ns)} if start_ns else {}), **({"probes": [p for p, _ in probes]} if probes else {}))
+                        **({"start_time": hs.Instant(start_ns)} if start_ns else {}), **({"probes": [p for p, _ in probes]} if probes else {}),
+                        **sim_kw)
     cancel_after(spec, handles)
     schedule_all(spec, pools, sim, hs.Event, at, early)
     pools["probes"] = probes

@@ -11,6 +11,7 @@ import client_specs as CS
 import family_checks as FC
 import fault_specs as FS
 import health_specs as HS
+import mixed_specs as MX
 import rate_limiter_specs as RS
 import recorded
 import resilience_specs as XS
@@ -19,6 +20,7 @@ import test_gpu_client
 import test_gpu_faults
 import test_gpu_health
 import test_gpu_lb_strategies
+import test_gpu_mixed
 import test_gpu_rate_limiter
 import test_gpu_resilience
 from happy_simulator_amd import _native as N
@@ -40,6 +42,9 @@ FAMILIES = {
     "client": (test_gpu_client, recorded.CLIENT, CS.FIXTURES["retry_lands_after_the_restart"],
                {"internal_by_kind": (15, 19), "health_by_kind": (19, 22), "resilience_by_kind": (22, 28), "client_by_kind": (28, 31)},
                {"trace", "by_kind", "pending_events", "time_travel"}),
+    "mixed": (test_gpu_mixed, MX.MIXED, MX.FIXTURES["checked_backends_into_a_processor_a_client_and_a_bulkhead"],
+              {"internal_by_kind": (15, 19), "health_by_kind": (19, 22), "resilience_by_kind": (22, 28), "client_by_kind": (28, 31), "flow_by_kind": (31, 39)},
+              {"trace", "by_kind", "pending_events", "time_travel", "probe_drops"}),
 }
 
 
@@ -62,7 +67,8 @@ def _arrays(ref, not_compared, floating):
 def test_an_unmodified_copy_passes_and_the_set_is_the_literal(family):
     name, got, ref, not_compared, slices = _case(family)
     assert N.EV_KINDS == 15 and not_compared == FAMILIES[family][4]
-    assert slices[-1][1] == len(ref["by_kind"]) == {"strategies": 15, "rate_limiter": 17, "faults": 19, "health": 22, "resilience": 28, "client": 31}[family]
+    assert slices[-1][1] == len(ref["by_kind"]) == {"strategies": 15, "rate_limiter": 17, "faults": 19, "health": 22, "resilience": 28, "client": 31,
+                                                        "mixed": 39}[family]
     FC.compare(name, got, ref, not_compared, slices)
 
 
