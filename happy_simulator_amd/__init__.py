@@ -28,6 +28,8 @@ from .entities import (FixedWindowPolicy, LeakyBucketPolicy, RateLimitedEntity, 
 from .entities import BackendHealthState, HealthChecker, HealthCheckStats  # noqa: F401
 from .entities import Bulkhead, BulkheadStats, TimeoutStats, TimeoutWrapper  # noqa: F401
 from .entities import Client, ClientStats, DecorrelatedJitter, ExponentialBackoff, FixedRetry, NoRetry  # noqa: F401
+from .entities import (AdaptiveLIFO, AdaptiveLIFOStats, CoDelQueue, CoDelStats, DeadlineQueue, FairQueue, LIFOQueue, PriorityQueue,  # noqa: F401
+                       REDQueue, WeightedFairQueue)
 from .entities import (BatchProcessor, BatchProcessorStats, ConveyorBelt, ConveyorStats, GateController, GateStats)  # noqa: F401
 from .faults import CrashNode, FaultHandle, FaultSchedule, FaultStats, PauseNode  # noqa: F401
 from .lowering import UnsupportedTopology  # noqa: F401

@@ -47,6 +47,8 @@ CLIENT_MAX_REQUEST_ID = 1 << 30                             # a request_id is a 
 NODE_BATCH_PROCESSOR, NODE_CONVEYOR, NODE_GATE = 12, 13, 14
 FLOW_MAX_ITEMS = 1 << 20                                    # include/hs_engine.h HS_FLOW_MAX_ITEMS: batch_size / a bounded gate queue
 FLOW_COUNTERS, FLOW_KINDS = 8, 8                            # HS_FLOW_COUNTERS, HS_FLOW_KINDS
+QUEUE_FIFO, QUEUE_LIFO, QUEUE_ADAPTIVE_LIFO, QUEUE_CODEL = 0, 1, 2, 3   # hs_queue_policy
+QUEUE_FIELDS = 16                                           # HS_QUEUE_FIELDS
 # hs_limiter_policy / hs_limiter_outcome (the third column of a limiter's records)
 LIMITER_TOKEN_BUCKET, LIMITER_LEAKY_BUCKET, LIMITER_SLIDING_WINDOW, LIMITER_FIXED_WINDOW, LIMITER_NONE = 0, 1, 2, 3, 255
 LIMITER_FORWARDED, LIMITER_QUEUED, LIMITER_DROPPED, LIMITER_DRAINED = 0, 1, 2, 3
@@ -533,6 +535,12 @@ def lib():
     L.hs_graph_schedule_gate.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32]
     L.hs_graph_get_flow.restype = C.c_int
     L.hs_graph_get_flow.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hs_graph_set_queue_policy.restype = C.c_int
+    L.hs_graph_set_queue_policy.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double]
+    L.hs_graph_get_queue_policy.restype = C.c_int
+    L.hs_graph_get_queue_policy.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.hs_debug_codel_next.restype = C.c_int
+    L.hs_debug_codel_next.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_graph_coop_selects.restype = C.c_int64
     L.hs_graph_coop_selects.argtypes = [C.c_void_p]
     L.hs_debug_graph_flags.restype = C.c_int
@@ -598,4 +606,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_set_wrapper", "hs_graph_get_wrapper",
     "hs_graph_set_client", "hs_graph_schedule_client", "hs_graph_get_client",
     "hs_graph_set_flow", "hs_graph_schedule_gate", "hs_graph_get_flow",
+    "hs_graph_set_queue_policy", "hs_graph_get_queue_policy", "hs_debug_codel_next",
 )

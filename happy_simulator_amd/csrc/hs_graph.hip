@@ -189,6 +189,22 @@ struct GHc {                                   // 32 bytes
     int8_t is_checking, last_passed, has_time;        // last_check_passed: -1 = None
     int8_t wrr_seen;                           // WeightedRoundRobin._current_weights has an entry for the backend: it was in a list select() saw
 };
+// A Server's queue policy other than FIFOQueue (components/queue_policy.py LIFOQueue, components/queue_policies/adaptive_lifo.py,
+// codel.py): its parameters and state, one row per such Server in HBM (GVars::qp; GParam::pad[0] = hs_queue_policy, GParam::rt_cnt = its
+// row; GParam::lim = the policy's capacity).  While a Request waits in such a queue GRequest::hook is the link to its predecessor (what a
+// pop-newest needs; ENQUEUE fired and cleared the hook, a pop restores -1) and, under CoDel, GRequest::service_s its enqueue time in ns,
+// as bits (dead until WORK; the hook's id is read before it is overwritten).
+struct GQueue {                                // 112 bytes
+    double target, interval;                   // CoDelQueue: target_delay, interval (seconds)
+    int64_t threshold;                         // AdaptiveLIFO: congestion_threshold
+    int64_t first_above, drop_next;            // CoDel: _first_above_time / _drop_next in ns (kQueueNone: None)
+    int64_t count, last_count;                 // CoDel: _count, _last_count
+    int64_t enqueued, deq_a, deq_b;            // enqueued; dequeued (CoDel) / dequeued_fifo; dequeued_lifo
+    int64_t dropped, cap_rejected;             // CoDel: dropped; capacity_rejected
+    int64_t switches;                          // AdaptiveLIFO: mode_switches; CoDel: drop_intervals
+    int32_t flag, kind;                        // AdaptiveLIFO: _was_congested; CoDel: _dropping
+};
+constexpr int64_t kQueueNone = INT64_MIN;
 constexpr int kLimPollScheduled = 1, kLimHasTime = 2;   // GState::active of a limiter: _poll_scheduled; _last_*_time / _current_window_start is set
 constexpr long long kMaxSlidingLog = 1ll << 20;          // SlidingWindowPolicy.max_requests the ring is sized for
 
@@ -218,6 +234,7 @@ struct GVars {                                 // device scalars
     long long client_by_kind[3];               // the Clients' request / response / timeout Events (hs_graph_get_client)
     long long flow_by_kind[HS_FLOW_KINDS];     // the flow entities' Events, kEvBpItem .. kEvGtClose (hs_graph_get_flow)
     long long flow_cancelled;                  // cancelled `_BatchTimeout` Events popped
+    GQueue *qp;                                // the rows of the Servers with a queue policy (hs_graph_set_queue_policy; null: none)
 };
 
 struct GCtl {                                  // kernel argument
@@ -451,6 +468,16 @@ __device__ inline void lim_fixed_reset(const GParam &p, GState &s, int64_t now) 
     const int64_t ws = ns_from_seconds(__dmul_rn(py_floordiv_pos(seconds_from_ns(now), p.mean), p.mean));
     if (!(s.active & kLimHasTime) || ws > (int64_t)s.svc_draws) { s.active |= kLimHasTime; s.svc_draws = (uint64_t)ws; lim_count(s) = 0; }
 }
+// CoDelQueue._control_law (codel.py:246-250): Duration.from_seconds(interval / math.sqrt(count)) in ns -- the correctly rounded root
+// and quotient, the product with 1e9 truncated
+__device__ __forceinline__ int64_t codel_next_ns(int64_t count, double interval) {
+    return ns_from_seconds(__ddiv_rn(interval, __dsqrt_rn(__ll2double_rn(count))));
+}
+// ... one (count, interval) pair per thread (hs_debug_codel_next)
+__global__ void hs_debug_codel_next_kernel(int64_t n, const int64_t *count, const double *interval, int64_t *out_ns) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out_ns[i] = codel_next_ns(count[i], interval[i]);
+}
 // FixedWindowPolicy._get_window_start, one input per thread (hs_debug_window_start)
 __global__ void hs_debug_window_start_kernel(int64_t n, const int64_t *now_ns, const double *w, double *out_div, int64_t *out_start) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -585,12 +612,14 @@ __device__ inline bool tab_remove(int64_t *tab, int live, int64_t id) {
 // R: the graph (or one of a batch) has a Bulkhead or a TimeoutWrapper -- a fourth instantiation, for the same reason.  R implies HC.
 // CL: ... has a Client -- a fifth, for the same reason.  CL implies R.
 // FL: ... has a BatchProcessor, a ConveyorBelt or a GateController -- a sixth, for the same reason.  FL implies CL.
-template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false>
+// Q: ... has a Server with a LIFOQueue, an AdaptiveLIFO or a CoDelQueue -- a seventh, for the same reason.  Q implies FL.
+template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false, bool Q = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     static_assert(F || !HC, "the health instantiation carries the fault code");
     static_assert(HC || !R, "the resilience instantiation carries the fault and health code");
     static_assert(R || !CL, "the client instantiation carries the fault, health and resilience code");
     static_assert(CL || !FL, "the flow instantiation carries the fault, health, resilience and client code");
+    static_assert(FL || !Q, "the queue-policy instantiation carries the fault, health, resilience, client and flow code");
     constexpr uint32_t kKinds = FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
     // (one word for the instantiations whose kinds fit in it, two for the flow instantiation's 39)
     constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
@@ -1115,6 +1144,107 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     continue;
                 }
             }
+            if constexpr (Q) {
+                if (p.pad[0] != HS_QUEUE_FIFO && (e.kind == HS_EV_ENQUEUE || e.kind == HS_EV_POLL)) {
+                    // a Server whose Queue has a LIFOQueue, an AdaptiveLIFO or a CoDelQueue: Queue._handle_enqueue / _handle_poll
+                    // (components/queue.py:122-166) with that policy's push / pop.  The list runs through Request::next as the FIFO's
+                    // does and, backwards, through Request::hook.
+                    GQueue &qs = V.qp[p.rt_cnt];
+                    if (e.kind == HS_EV_ENQUEUE) {
+                        const int hook = c.reqs[e.req].hook;                       // (as the FIFO handler below: one-shot)
+                        c.reqs[e.req].hook = -1;
+                        int64_t probe_tag = -1;
+                        if (hook >= 0 && c.P[hook].kind == HS_NODE_HEALTH_CHECKER) { probe_tag = c.reqs[e.req].client; c.reqs[e.req].client = -1; }
+                        const int64_t hook_id = req_id(c.reqs[e.req]);             // a wrapper's id / a Client's key: read before the stamp
+                        if (p.lim >= 0 && s.qlen >= p.lim) {                       // push refuses at capacity
+                            s.b += 1;
+                            qs.cap_rejected += 1;
+                            c.reqs[e.req].next = req_free; req_free = e.req;
+                        } else {
+                            GRequest &q = c.reqs[e.req];
+                            q.idx = e.idx;
+                            q.pre = e.pad & 1u;
+                            q.next = -1;
+                            q.hook = s.qtail;                                      // the predecessor (-1: none)
+                            if (p.pad[0] == HS_QUEUE_CODEL) q.service_s = __longlong_as_double(t);   // _QueuedItem.enqueue_time
+                            if (s.qtail >= 0) c.reqs[s.qtail].next = e.req; else s.qhead = e.req;
+                            s.qtail = e.req;
+                            s.a += 1;
+                            qs.enqueued += 1;
+                            const bool was_empty = s.qlen == 0;
+                            s.qlen += 1;
+                            if (was_empty) H.push(mk(t, G++, HS_EV_NOTIFY, n, -1));
+                        }
+                        if (probe_tag >= 0) {
+                            GEvent re = mk(t, G++, kEvHcResp, hook, -2 - (int)(probe_tag & 0xffffffffll));
+                            re.pad = (uint32_t)(probe_tag >> 32) << kPadIdShift;
+                            H.push(re);
+                        } else if (hook >= 0) {
+                            const uint8_t hk = c.P[hook].kind;
+                            if (hook_has_id<CL>(hk)) H.push(mk_id(t, G++, hook_resp_kind<CL>(hk), hook, hook_id));
+                            else H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
+                        }
+                        continue;
+                    }
+                    if (s.qlen == 0) continue;                                      // pop() returns None: no Event
+                    auto pop_oldest = [&]() {
+                        const int r = s.qhead;
+                        s.qlen -= 1;
+                        if (s.qlen == 0) { s.qhead = -1; s.qtail = -1; } else s.qhead = c.reqs[r].next;
+                        return r;
+                    };
+                    auto pop_newest = [&]() {
+                        const int r = s.qtail;
+                        s.qlen -= 1;
+                        if (s.qlen == 0) { s.qhead = -1; s.qtail = -1; } else { s.qtail = c.reqs[r].hook; c.reqs[s.qtail].next = -1; }
+                        return r;
+                    };
+                    int r;
+                    if (p.pad[0] == HS_QUEUE_LIFO) r = pop_newest();
+                    else if (p.pad[0] == HS_QUEUE_ADAPTIVE_LIFO) {                 // AdaptiveLIFO.pop (adaptive_lifo.py:135-162)
+                        const int congested = (int64_t)s.qlen >= qs.threshold ? 1 : 0;   // before anything is removed
+                        if (congested != qs.flag) { qs.switches += 1; qs.flag = congested; }
+                        if (congested) { r = pop_newest(); qs.deq_b += 1; }
+                        else { r = pop_oldest(); qs.deq_a += 1; }
+                    } else {
+                        // CoDelQueue.pop / _codel_dequeue (codel.py:177-256), operation for operation
+                        r = pop_oldest();
+                        const double sojourn = seconds_from_ns(t - __double_as_longlong(c.reqs[r].service_s));
+                        bool ok_to_drop;                                            // _should_mark_or_drop: the head is gone already
+                        if (sojourn < qs.target || s.qlen == 0) { qs.first_above = kQueueNone; ok_to_drop = false; }
+                        else if (qs.first_above == kQueueNone) { qs.first_above = t + ns_from_seconds(qs.interval); ok_to_drop = false; }
+                        else ok_to_drop = t >= qs.first_above;
+                        auto drop = [&]() {                                         // _drop: the head goes, no handler sees it
+                            if (s.qlen == 0) return;
+                            const int d = pop_oldest();
+                            c.reqs[d].next = req_free; req_free = d;
+                            qs.dropped += 1;
+                        };
+                        auto control_law = [&]() { return t + codel_next_ns(qs.count, qs.interval); };
+                        if (qs.flag) {
+                            if (!ok_to_drop) qs.flag = 0;
+                            else while (qs.drop_next != kQueueNone && t >= qs.drop_next && s.qlen > 0) {
+                                drop();
+                                qs.count += 1;
+                                qs.drop_next = control_law();
+                            }
+                        } else if (ok_to_drop) {
+                            drop();
+                            qs.flag = 1;
+                            qs.switches += 1;                                       // drop_intervals
+                            const int64_t delta = qs.count - qs.last_count;
+                            // (delta >= 1 only behind a drop of the loop above, which set _drop_next; the difference is signed)
+                            qs.count = (delta < 1 || qs.drop_next == kQueueNone || seconds_from_ns(t - qs.drop_next) < qs.interval) ? 1 : delta;
+                            qs.last_count = qs.count;
+                            qs.drop_next = control_law();
+                        }
+                        qs.deq_a += 1;
+                    }
+                    c.reqs[r].hook = -1;                                            // every later handler reads it
+                    H.push(mk(t, G++, HS_EV_DELIVER, n, r));
+                    continue;
+                }
+            }
             switch (e.kind) {
             case HS_EV_SOURCE: {
                 // Source.handle_event (load/source.py:142-180): the payload is constructed first, then the next SourceEvent;
@@ -1621,6 +1751,12 @@ __global__ void __launch_bounds__(64) hs_graph_run_flow(GCtl c) {             //
     graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true>(c, lheap, lnodes);
 }
 
+__global__ void __launch_bounds__(64) hs_graph_run_queues(GCtl c) {           // ... with a Server whose queue policy is not the FIFO
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true>(c, lheap, lnodes);
+}
+
 // Independent graphs -- the replicas / sweep points of parallel/runner.py:82-142 -- side by side: one workgroup (one heap) each, one
 // with a quarter of the lone run's LDS window (32 KB + 6 KB of nodes: four workgroups per CU, 1 024 heaps on the device at once; a heap that outgrows
 // the window continues in HBM as it does behind the large one -- the window's size changes nothing the loop computes).
@@ -1679,6 +1815,14 @@ __global__ void __launch_bounds__(64) hs_graph_run_batch_flow(const GCtl *cs, lo
     graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true>(c, lheap, lnodes);
     batch_report(c, stat);
 }
+// ... of a batch in which at least one handle has a Server with a queue policy
+__global__ void __launch_bounds__(64) hs_graph_run_batch_queues(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
 
 }  // namespace graph
 }  // namespace hs
@@ -1720,6 +1864,8 @@ struct hs_graph {
     long long rs_tab_len = 0;
     // Client: a graph that holds one runs the fifth instantiation; its in-flight table is one of rs_tab (two words per place)
     int n_clients = 0;
+    std::vector<GQueue> qpol;                  // hs_graph_set_queue_policy: the rows of the Servers with a queue policy, in call order; a graph
+    GQueue *d_qp = nullptr;                    // that holds one runs the seventh instantiation (the rows go to the device with the first run)
     int n_flows = 0;                           // BatchProcessor / ConveyorBelt / GateController nodes: a graph that holds one runs the sixth instantiation
     std::vector<int64_t> cl_delays;            // every configured Client's delay table, back to back (GParam::lim = its offset)
     int64_t *d_cl_delays = nullptr;
@@ -1807,7 +1953,7 @@ void hs_graph_destroy(hs_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *bufs[] = {g->ctl.heap, g->ctl.reqs, g->ctl.rec_node, g->ctl.rec_t, g->ctl.rec_cr, (void *)g->ctl.P, g->ctl.S,
                     g->d_rt_targets, g->d_key_table, (void *)g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
-                    g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health, g->ctl.rs_tab, g->d_cl_delays, g->d_sched_id};
+                    g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health, g->ctl.rs_tab, g->d_cl_delays, g->d_sched_id, g->d_qp};
     for (void *b : bufs) if (b && !in_slab(g, b)) (void)hipFree(b);
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
     if (g->ev_a) (void)hipEventDestroy(g->ev_a);
@@ -2638,6 +2784,83 @@ int hs_graph_get_flow(hs_graph *g, int32_t node, int64_t *counters, int64_t *eve
     return HS_OK;
 }
 
+int hs_graph_set_queue_policy(hs_graph *g, int32_t node, int32_t policy, int64_t capacity, int64_t threshold, double target_s, double interval_s) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_SERVER) return fail(g, HS_E_INVALID, "set_queue_policy: node %d is not a Server", node);
+    if (g->ran || g->launches > 0) return fail(g, HS_E_STATE, "set_queue_policy: a Server is configured before the first run");
+    GParam &p = g->params[(size_t)node];
+    if (p.pad[0] != HS_QUEUE_FIFO) return fail(g, HS_E_STATE, "set_queue_policy: node %d is configured already", node);
+    if (policy != HS_QUEUE_LIFO && policy != HS_QUEUE_ADAPTIVE_LIFO && policy != HS_QUEUE_CODEL)
+        return fail(g, HS_E_UNSUPPORTED, "set_queue_policy: policy %d is not lowered", (int)policy);
+    GQueue q{};
+    q.kind = policy; q.first_above = kQueueNone; q.drop_next = kQueueNone;
+    if (policy != HS_QUEUE_LIFO && capacity == 0) return fail(g, HS_E_INVALID, "capacity must be >= 1 or None, got %lld", (long long)capacity);   // adaptive_lifo.py:68-69, codel.py:93-94
+    if (policy == HS_QUEUE_ADAPTIVE_LIFO) {
+        if (threshold < 1) return fail(g, HS_E_INVALID, "congestion_threshold must be >= 1, got %lld", (long long)threshold);     // adaptive_lifo.py:66-67
+        q.threshold = threshold;
+    } else if (policy == HS_QUEUE_CODEL) {
+        if (!(target_s > 0.0)) return fail(g, HS_E_INVALID, "target_delay must be > 0, got %g", target_s);                         // codel.py:89-92
+        if (!(interval_s > 0.0)) return fail(g, HS_E_INVALID, "interval must be > 0, got %g", interval_s);
+        if (!std::isfinite(target_s) || !(interval_s <= 4.0e9)) return fail(g, HS_E_UNSUPPORTED, "set_queue_policy: target_delay = %g, interval = %g: beyond 4e9 s or not finite", target_s, interval_s);
+        q.target = target_s; q.interval = interval_s;
+        g->reach_s = std::max(g->reach_s, interval_s);
+    }
+    if ((long long)g->qpol.size() >= (1ll << 30)) return fail(g, HS_E_UNSUPPORTED, "set_queue_policy: too many Servers with a policy");
+    p.lim = capacity < 0 ? -1 : capacity;                  // the policy's own capacity: the Server's queue_capacity is ignored (server.py)
+    p.pad[0] = (uint8_t)policy; p.rt_cnt = (int32_t)g->qpol.size();
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    g->qpol.push_back(q);
+    return HS_OK;
+}
+
+int hs_graph_get_queue_policy(hs_graph *g, int32_t node, int64_t *out) {
+    if (!g || !out) return fail(g, HS_E_INVALID, "null argument");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_SERVER || g->params[(size_t)node].pad[0] == HS_QUEUE_FIFO)
+        return fail(g, HS_E_INVALID, "get_queue_policy: node %d is not a Server with a queue policy", node);
+    const GParam &p = g->params[(size_t)node];
+    GQueue q = g->qpol[(size_t)p.rt_cnt];
+    GState s{};
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (g->d_qp) HS_HIP(g, hipMemcpy(&q, g->d_qp + p.rt_cnt, sizeof q, hipMemcpyDeviceToHost));
+    HS_HIP(g, hipMemcpy(&s, g->ctl.S + node, sizeof s, hipMemcpyDeviceToHost));
+    out[0] = q.kind; out[1] = s.qlen; out[2] = q.enqueued; out[3] = q.deq_a; out[4] = q.deq_b; out[5] = q.dropped; out[6] = q.cap_rejected;
+    out[7] = q.switches; out[8] = q.flag; out[9] = q.count; out[10] = q.last_count;
+    out[11] = q.first_above != kQueueNone; out[12] = q.first_above != kQueueNone ? q.first_above : 0;
+    out[13] = q.drop_next != kQueueNone; out[14] = q.drop_next != kQueueNone ? q.drop_next : 0;
+    out[15] = 0;
+    return HS_OK;
+}
+
+int hs_debug_codel_next(int32_t device, int64_t n, const int64_t *count, const double *interval_s, int64_t *out_ns) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, HS_E_NO_DEVICE, "no HIP device visible: the engine has no CPU fallback");
+    if (n <= 0 || !count || !interval_s || !out_ns) return fail(nullptr, HS_E_INVALID, "hs_debug_codel_next: bad arguments");
+    if (device < 0 || device >= ndev) return fail(nullptr, HS_E_INVALID, "device ordinal %d out of range (%d devices)", device, ndev);
+    for (int64_t i = 0; i < n; ++i)
+        if (count[i] < 1 || !(interval_s[i] > 0.0) || !(interval_s[i] <= 4.0e9))
+            return fail(nullptr, HS_E_INVALID, "hs_debug_codel_next: entry %lld is outside count >= 1, 0 < interval <= 4e9", (long long)i);
+    HS_HIP(nullptr, hipSetDevice(device));
+    void *d[3] = {nullptr, nullptr, nullptr};
+    const size_t bytes = (size_t)n * 8;
+    for (int k = 0; k < 3; ++k) {
+        const hipError_t e = hipMalloc(&d[k], bytes);
+        if (e != hipSuccess) { for (auto &p : d) if (p) hipFree(p); return fail(nullptr, HS_E_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
+    }
+    hipError_t e = hipMemcpy(d[0], count, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d[1], interval_s, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(hs_debug_codel_next_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, (const int64_t *)d[0],
+                           (const double *)d[1], (int64_t *)d[2]);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out_ns, d[2], bytes, hipMemcpyDeviceToHost);
+    for (auto &p : d) hipFree(p);
+    if (e != hipSuccess) return fail(nullptr, HS_E_HIP, "hs_debug_codel_next: %s", hipGetErrorString(e));
+    return HS_OK;
+}
+
 int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, int32_t cancelled) {
     if (!g) return fail(g, HS_E_INVALID, "null handle");
     if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "add_fault: node %d out of range", node);
@@ -2835,6 +3058,13 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         }
         c.cl_delays = g->d_cl_delays;
     }
+    if (!g->qpol.empty() && !g->d_qp) {
+        // the queue policies' rows, once (hs_graph_set_queue_policy comes before the first run): the device finds them through GVars
+        HS_HIP(g, hipSetDevice(g->cfg.device));
+        HS_HIP(g, hipMalloc(&g->d_qp, g->qpol.size() * sizeof(GQueue)));
+        HS_HIP(g, hipMemcpy(g->d_qp, g->qpol.data(), g->qpol.size() * sizeof(GQueue), hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, qp), &g->d_qp, sizeof g->d_qp, hipMemcpyHostToDevice));
+    }
     if (g->n_flows > 0)
         for (int i = 0; i < g->n; ++i) {
             const uint8_t k = g->params[(size_t)i].kind;
@@ -2972,7 +3202,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, g->ctl);
@@ -3025,9 +3256,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
             h_ctl.back().part = part;              // (the handles themselves never keep part semantics: no early return can leave it set)
         }
         if ((he = hipMemcpy(d_ctl, h_ctl.data(), h_ctl.size() * sizeof(GCtl), hipMemcpyHostToDevice)) != hipSuccess) break;
-        bool any_faults = false, any_health = false, any_wrappers = false, any_clients = false, any_flows = false;
-        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; any_clients |= gs[i]->n_clients > 0; any_flows |= gs[i]->n_flows > 0; }
-        if (any_flows) hipLaunchKernelGGL(hs_graph_run_batch_flow, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_faults = false, any_health = false, any_wrappers = false, any_clients = false, any_flows = false, any_queues = false;
+        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; any_clients |= gs[i]->n_clients > 0; any_flows |= gs[i]->n_flows > 0; any_queues |= !gs[i]->qpol.empty(); }
+        if (any_queues) hipLaunchKernelGGL(hs_graph_run_batch_queues, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else if (any_flows) hipLaunchKernelGGL(hs_graph_run_batch_flow, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_clients) hipLaunchKernelGGL(hs_graph_run_batch_client, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_wrappers) hipLaunchKernelGGL(hs_graph_run_batch_resilience, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_health) hipLaunchKernelGGL(hs_graph_run_batch_health, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
@@ -3099,7 +3331,8 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count; one.rs_tab = g->ctl.rs_tab;
-        if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, one);
+        if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, one);
+        else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, one);

@@ -70,7 +70,7 @@ class ConstantLatency(LatencyDistribution):
 
 # ---- queue policy --------------------------------------------------------------------------------
 class FIFOQueue:
-    """components/queue_policy.py:75-114 -- the only policy lowered to the engine."""
+    """components/queue_policy.py:75-114 -- the policy every engine runs (LIFOQueue, AdaptiveLIFO, CoDelQueue: the single-heap loop)."""
     __slots__ = ("_capacity",)
 
     def __init__(self, capacity: float = float("inf")):
@@ -79,6 +79,167 @@ class FIFOQueue:
     @property
     def capacity(self) -> float:
         return self._capacity
+
+
+class LIFOQueue:
+    """components/queue_policy.py:117-156: push appends and refuses at capacity, pop takes the newest item.  Runs on the single-heap
+    loop; `len()` is the depth the last run left."""
+    __slots__ = ("_capacity", "_len")
+
+    def __init__(self, capacity: float = float("inf")):
+        self._capacity = capacity
+        self._len = 0
+
+    @property
+    def capacity(self) -> float:
+        return self._capacity
+
+    def is_empty(self) -> bool:
+        return self._len == 0
+
+    def __len__(self) -> int:
+        return self._len
+
+
+@dataclass(frozen=True)
+class AdaptiveLIFOStats:
+    enqueued: int = 0
+    dequeued_fifo: int = 0
+    dequeued_lifo: int = 0
+    capacity_rejected: int = 0
+    mode_switches: int = 0
+
+
+class AdaptiveLIFO:
+    """components/queue_policies/adaptive_lifo.py: FIFO below `congestion_threshold` items, LIFO from there on; the test is made when
+    an item is popped, before it is removed.  Runs on the single-heap loop; the counters are the last run's."""
+
+    def __init__(self, congestion_threshold: int, capacity: int | None = None):
+        if congestion_threshold < 1:
+            raise ValueError(f"congestion_threshold must be >= 1, got {congestion_threshold}")
+        if capacity is not None and capacity < 1:
+            raise ValueError(f"capacity must be >= 1 or None, got {capacity}")
+        self._congestion_threshold = congestion_threshold
+        self._capacity = float("inf") if capacity is None else capacity
+        self._len = 0
+        self._was_congested = False
+        self._enqueued = 0
+        self._dequeued_fifo = 0
+        self._dequeued_lifo = 0
+        self._capacity_rejected = 0
+        self._mode_switches = 0
+
+    @property
+    def stats(self) -> AdaptiveLIFOStats:
+        return AdaptiveLIFOStats(enqueued=self._enqueued, dequeued_fifo=self._dequeued_fifo, dequeued_lifo=self._dequeued_lifo,
+                                 capacity_rejected=self._capacity_rejected, mode_switches=self._mode_switches)
+
+    @property
+    def congestion_threshold(self) -> int:
+        return self._congestion_threshold
+
+    @property
+    def capacity(self) -> float:
+        return self._capacity
+
+    @property
+    def is_congested(self) -> bool:
+        return self._len >= self._congestion_threshold
+
+    @property
+    def mode(self) -> str:
+        return "LIFO" if self.is_congested else "FIFO"
+
+    def is_empty(self) -> bool:
+        return self._len == 0
+
+    def __len__(self) -> int:
+        return self._len
+
+
+@dataclass(frozen=True)
+class CoDelStats:
+    enqueued: int = 0
+    dequeued: int = 0
+    dropped: int = 0
+    capacity_rejected: int = 0
+    drop_intervals: int = 0
+
+
+class CoDelQueue:
+    """components/queue_policies/codel.py: a FIFO that, when the sojourn time of the items it pops has stayed above `target_delay` for
+    `interval`, drops the items behind the popped one at a rate that grows with the square root of the drop count.  Runs on the
+    single-heap loop; the clock is the Simulation's, so `clock_func` / `set_clock` are accepted and ignored."""
+
+    def __init__(self, target_delay: float = 0.005, interval: float = 0.100, capacity: int | None = None, clock_func=None):
+        if target_delay <= 0:
+            raise ValueError(f"target_delay must be > 0, got {target_delay}")
+        if interval <= 0:
+            raise ValueError(f"interval must be > 0, got {interval}")
+        if capacity is not None and capacity < 1:
+            raise ValueError(f"capacity must be >= 1 or None, got {capacity}")
+        self._target_delay = target_delay
+        self._interval = interval
+        self._capacity = float("inf") if capacity is None else capacity
+        self._clock_func = clock_func
+        self._len = 0
+        self._first_above_time: Instant | None = None
+        self._drop_next: Instant | None = None
+        self._count = 0
+        self._dropping = False
+        self._last_count = 0
+        self._enqueued = 0
+        self._dequeued = 0
+        self._dropped = 0
+        self._capacity_rejected = 0
+        self._drop_intervals = 0
+
+    @property
+    def stats(self) -> CoDelStats:
+        return CoDelStats(enqueued=self._enqueued, dequeued=self._dequeued, dropped=self._dropped,
+                          capacity_rejected=self._capacity_rejected, drop_intervals=self._drop_intervals)
+
+    @property
+    def target_delay(self) -> float:
+        return self._target_delay
+
+    @property
+    def interval(self) -> float:
+        return self._interval
+
+    @property
+    def capacity(self) -> float:
+        return self._capacity
+
+    @property
+    def dropping(self) -> bool:
+        return self._dropping
+
+    def set_clock(self, clock_func) -> None:
+        self._clock_func = clock_func
+
+    def is_empty(self) -> bool:
+        return self._len == 0
+
+    def __len__(self) -> int:
+        return self._len
+
+
+QUEUE_POLICIES = (LIFOQueue, AdaptiveLIFO, CoDelQueue)          # the policies next to the FIFO that the single-heap loop runs
+
+
+def _refused_queue_policy(name: str, why: str):
+    """A reference policy that no engine runs: the class exists so that Server's refusal can name it and say why."""
+    def __init__(self, *args, **kwargs):
+        self.args, self.kwargs = args, kwargs
+    return type(name, (), {"__init__": __init__, "_refusal": why, "__doc__": f"Not lowered: {why}."})
+
+
+PriorityQueue = _refused_queue_policy("PriorityQueue", "its order comes from a host callable or the items' own comparison")
+DeadlineQueue = _refused_queue_policy("DeadlineQueue", "its deadlines come from a host callable")
+FairQueue = _refused_queue_policy("FairQueue", "its flows come from a host callable")
+WeightedFairQueue = _refused_queue_policy("WeightedFairQueue", "its flows and weights come from host callables")
+REDQueue = _refused_queue_policy("REDQueue", "it draws from the process-wide random generator")
 
 
 # ---- load ----------------------------------------------------------------------------------------
@@ -342,7 +503,7 @@ class Server(Entity):
     _active = _Stat("active")
 
     def __init__(self, name: str, concurrency: int = 1, service_time: LatencyDistribution | None = None,
-                 queue_policy: FIFOQueue | None = None, queue_capacity: int | None = None,
+                 queue_policy: "FIFOQueue | LIFOQueue | AdaptiveLIFO | CoDelQueue | None" = None, queue_capacity: int | None = None,
                  downstream: Entity | None = None):
         super().__init__(name)
         if not isinstance(concurrency, int):
@@ -351,8 +512,9 @@ class Server(Entity):
             raise ValueError(f"max_concurrent must be >= 1, got {concurrency}")   # server/concurrency.py:87-88
         if queue_policy is None:
             queue_policy = FIFOQueue(capacity=queue_capacity if queue_capacity is not None else float("inf"))
-        elif not isinstance(queue_policy, FIFOQueue):
-            raise NotImplementedError("only FIFOQueue is lowered to the engine")
+        elif not isinstance(queue_policy, (FIFOQueue,) + QUEUE_POLICIES):     # (with a policy given, queue_capacity is ignored)
+            why = getattr(queue_policy, "_refusal", "only FIFOQueue, LIFOQueue, AdaptiveLIFO and CoDelQueue are")
+            raise NotImplementedError(f"queue_policy {type(queue_policy).__name__} is not lowered to the engine: {why}")
         self._bound = None
         self._policy = queue_policy
         self._concurrency = concurrency
@@ -386,6 +548,10 @@ class Server(Entity):
     @property
     def queue(self) -> _QueueView:
         return self._queue
+
+    @property
+    def queue_policy(self):
+        return self._policy
 
     @property
     def depth(self) -> int:

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _native as N
 from .core.temporal import Duration, Instant
-from .entities import (BatchProcessor, ConveyorBelt, GateController,
+from .entities import (AdaptiveLIFO, CoDelQueue, FIFOQueue, QUEUE_POLICIES, BatchProcessor, ConveyorBelt, GateController,
                        BackendHealthState, Bulkhead, Client, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
                        ExponentialLatency, HealthChecker, IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random,
                        RandomRouter, RateLimitedEntity, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source,
@@ -91,6 +91,14 @@ class GraphArrays:
 
         self.flow_params = None              # [n, 4] int64: BATCH_PROCESSOR / CONVEYOR / GATE nodes -- hs_graph_set_flow's count, delay_ns,
                                              #   aux_ns and flag (entities.BatchProcessor / ConveyorBelt / GateController)
+
+        self.qp_params = None                # [n, 5] float64: SERVER nodes with a LIFOQueue / AdaptiveLIFO / CoDelQueue -- hs_queue_policy
+                                             #   (0: the FIFO), capacity (-1: unbounded), congestion_threshold, target_delay, interval;
+                                             #   set through hs_graph_set_queue_policy
+
+    @property
+    def has_queue_policies(self) -> bool:
+        return self.qp_params is not None
 
     @property
     def has_flows(self) -> bool:
@@ -215,6 +223,26 @@ class GraphEngine:
             except BaseException:
                 self.close()
                 raise
+
+        if arrays.has_queue_policies:
+            try:
+                for i in np.nonzero((arrays.kind == N.NODE_SERVER) & (arrays.qp_params[:, 0] != N.QUEUE_FIFO))[0]:
+                    pol, cap, thr, target, interval = arrays.qp_params[i]
+                    self._check(self._lib.hs_graph_set_queue_policy(self._h, int(i), int(pol), int(cap), int(thr), float(target), float(interval)))
+            except BaseException:
+                self.close()
+                raise
+
+    _QUEUE_NAMES = ("policy", "len", "enqueued", "dequeued_fifo", "dequeued_lifo", "dropped", "capacity_rejected", "switches", "flag",
+                    "count", "last_count", "has_first_above", "first_above_ns", "has_drop_next", "drop_next_ns")
+
+    def queue_policy(self, node: int) -> dict:
+        """hs_graph_get_queue_policy of a Server with a LIFOQueue, an AdaptiveLIFO or a CoDelQueue: its state by name (`dequeued_fifo`
+        is a CoDelQueue's `dequeued`, `switches` its `drop_intervals` / an AdaptiveLIFO's `mode_switches`, `flag` `_dropping` /
+        `_was_congested`)."""
+        out = np.zeros(N.QUEUE_FIELDS, np.int64)
+        self._check(self._lib.hs_graph_get_queue_policy(self._h, int(node), _ptr(out)))
+        return {k: int(v) for k, v in zip(self._QUEUE_NAMES, out)}
 
     _FLOW_NAMES = {N.NODE_BATCH_PROCESSOR: ("batches_processed", "items_processed", "timeouts", "buffer_depth"),
                    N.NODE_CONVEYOR: ("items_transported", "items_rejected", "items_in_transit"),
@@ -610,6 +638,29 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             a.lat_mean_s[i] = svc.mean
             cap = ent._policy.capacity
             a.queue_cap[i] = -1 if cap == float("inf") else int(cap)
+            pol = ent._policy
+            if isinstance(pol, QUEUE_POLICIES):
+                if a.qp_params is None:
+                    a.qp_params = np.zeros((n, 5), np.float64)
+                if len(pol):
+                    raise UnsupportedTopology(f"server '{ent.name}': {len(pol)} items are still queued in its {type(pol).__name__} from an "
+                                              "earlier run (not lowered)")
+                if cap != float("inf") and not (type(cap) is int and 0 <= cap < (1 << 31)):
+                    raise UnsupportedTopology(f"server '{ent.name}': the capacity {cap!r} of its {type(pol).__name__} is not an int below 2^31")
+                if isinstance(pol, AdaptiveLIFO):
+                    if type(pol.congestion_threshold) is not int:
+                        raise UnsupportedTopology(f"server '{ent.name}': congestion_threshold must be an int, got {pol.congestion_threshold!r}")
+                    a.qp_params[i] = (N.QUEUE_ADAPTIVE_LIFO, a.queue_cap[i], min(pol.congestion_threshold, 1 << 40), 0.0, 0.0)
+                elif isinstance(pol, CoDelQueue):
+                    target, interval = float(pol.target_delay), float(pol.interval)
+                    if not (target < float("inf") and interval <= 4.0e9):
+                        raise UnsupportedTopology(f"server '{ent.name}': CoDelQueue(target_delay={target!r}, interval={interval!r}) is beyond "
+                                                  "4e9 s or not finite")
+                    a.qp_params[i] = (N.QUEUE_CODEL, a.queue_cap[i], 0, target, interval)
+                else:
+                    a.qp_params[i] = (N.QUEUE_LIFO, a.queue_cap[i], 0, 0.0, 0.0)
+            elif not isinstance(pol, FIFOQueue):
+                raise UnsupportedTopology(f"server '{ent.name}': queue policy {type(pol).__name__} is not lowered")
             d = ent.downstream
             a.target[i] = -1 if d is None else node_of[id(d)]
         elif isinstance(ent, NetworkLink):
@@ -875,7 +926,7 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
     per_node = [nm for nm in ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s",
                               "link_lat_min_s", "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric",
                               "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params", "cl_params",
-                              "flow_params")
+                              "flow_params", "qp_params")
                 if getattr(a, nm) is not None]
     names = None if a.names is None else [a.names[a.name_off[i]:a.name_off[i + 1]] for i in range(n)]
     parts = []
@@ -910,6 +961,8 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
             b.wrap_params = None                                           # (a part without a wrapper runs the loop it would run alone)
         if b.flow_params is not None and not ((b.kind >= N.NODE_BATCH_PROCESSOR) & (b.kind <= N.NODE_GATE)).any():
             b.flow_params = None                                           # (a part without a flow entity likewise)
+        if b.qp_params is not None and not (b.qp_params[:, 0] != N.QUEUE_FIFO).any():
+            b.qp_params = None                                             # (a part without a policied Server likewise)
         if b.cl_params is not None and not (b.kind == N.NODE_CLIENT).any():
             b.cl_params = None                                             # (a part without a Client likewise)
         if b.cl_params is not None:
@@ -989,6 +1042,13 @@ class PartRun:
 
     def flow_events(self) -> np.ndarray:
         return np.sum([e.flow_events() for e in self.engines], axis=0).astype(np.int64)
+
+    def queue_policy(self, node: int) -> dict:
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            at = np.searchsorted(ids, node)
+            if at < len(ids) and ids[at] == node:
+                return e.queue_policy(int(at))
+        raise KeyError(node)
 
     def flow(self, node: int) -> dict:
         for (ids, _pos, _b), e in zip(self.parts, self.engines):
@@ -1080,7 +1140,7 @@ def keyless_hazard(g: "GeneralGraph", target) -> str | None:
 
 
 def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t: np.ndarray, rec_cr: np.ndarray, device: int = 0,
-                       health=None, wrapper=None, client=None, flow=None) -> None:
+                       health=None, wrapper=None, client=None, flow=None, queue=None) -> None:
     """The run's per-node results onto the user's objects, under the attribute names the reference uses (lowering.write_back's
     counterpart).  `health`: node -> GraphEngine.health(node) of a graph with health state; `wrapper`: node -> GraphEngine.wrapper(node)
     of a graph with a Bulkhead or a TimeoutWrapper; `client`: node -> GraphEngine.client(node) of a graph with a Client."""
@@ -1099,6 +1159,20 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
             ent._requests_rejected = int(stats["rejected"][i])
             ent._total_service_time = float(stats["total_service_s"][i])
             ent._active = int(stats["active"][i])
+            pol = ent._policy
+            if isinstance(pol, QUEUE_POLICIES):
+                w = queue(i)                  # GraphEngine.queue_policy(node) of a graph with such a Server
+                pol._len = w["len"]
+                if isinstance(pol, AdaptiveLIFO):
+                    (pol._enqueued, pol._dequeued_fifo, pol._dequeued_lifo, pol._capacity_rejected, pol._mode_switches) = (
+                        w["enqueued"], w["dequeued_fifo"], w["dequeued_lifo"], w["capacity_rejected"], w["switches"])
+                    pol._was_congested = bool(w["flag"])
+                elif isinstance(pol, CoDelQueue):
+                    (pol._enqueued, pol._dequeued, pol._dropped, pol._capacity_rejected, pol._drop_intervals) = (
+                        w["enqueued"], w["dequeued_fifo"], w["dropped"], w["capacity_rejected"], w["switches"])
+                    pol._dropping, pol._count, pol._last_count = bool(w["flag"]), w["count"], w["last_count"]
+                    pol._first_above_time = Instant(w["first_above_ns"]) if w["has_first_above"] else None
+                    pol._drop_next = Instant(w["drop_next_ns"]) if w["has_drop_next"] else None
         elif isinstance(ent, NetworkLink):
             ent.packets_sent = int(stats["packets_sent"][i])
             ent.packets_dropped = int(stats["packets_dropped"][i])

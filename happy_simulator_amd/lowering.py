@@ -19,7 +19,7 @@ import numpy as np
 from . import _native as N
 from .engine import NetworkArrays, StationArrays
 from .entities import (ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
-                       ExponentialLatency, IPHash, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe,
+                       ExponentialLatency, FIFOQueue, IPHash, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe,
                        Random, RandomRouter, RoundRobin, Server, SimpleEventProvider, Sink, Source, WeightedLeastConnections,
                        WeightedRoundRobin, _RecordSink)
 
@@ -102,7 +102,9 @@ def _plain_chains(sources, entities):
         pos = dict(zip(map(id, ent_servers), range(n)))
         station_of_source = np.fromiter(map(pos.__getitem__, map(id, servers)), np.int32, n)
         order = np.argsort(station_of_source, kind="stable")
-    downs, svcs, concs, caps = (list(c) for c in zip(*map(ag("_downstream", "_service_time", "_concurrency", "_policy._capacity"), servers)))
+    downs, svcs, concs, caps, pols = (list(c) for c in zip(*map(ag("_downstream", "_service_time", "_concurrency", "_policy._capacity", "_policy"), servers)))
+    if set(map(type, pols)) != {FIFOQueue}:             # (LIFOQueue, AdaptiveLIFO, CoDelQueue: lower() names it, the single-heap loop runs it)
+        return None
     if not set(map(type, downs)) <= {Sink, Counter, LatencyTracker, type(None)}:
         return None
     real = [d for d in downs if d is not None]
@@ -417,6 +419,14 @@ def write_back_shared_sink_probes(g: LoweredGraph) -> None:
         pr.data_sink._set(t, before.astype(np.int64), None)
 
 
+def refuse_queue_policy(sv: Server, what: str) -> None:
+    """The station, network and pipeline engines keep a Server's queue as a count or a ring in arrival order: any policy but the FIFO
+    is the single-heap loop's."""
+    if type(sv._policy) is not FIFOQueue:
+        raise UnsupportedTopology(f"{what} '{sv.name}': queue policy {type(sv._policy).__name__} is not lowered on the station, network and "
+                                  "pipeline engines (they keep a queue in arrival order; the single-heap loop runs it)")
+
+
 def lower(sources: list, entities: list) -> LoweredGraph:
     sources = list(sources or [])
     entities = list(entities or [])
@@ -436,6 +446,7 @@ def lower(sources: list, entities: list) -> LoweredGraph:
         used_sinks.setdefault(id(obj), len(g.stations))
 
     def check_server(sv: Server):
+        refuse_queue_policy(sv, "server")
         if not isinstance(sv.service_time, (ExponentialLatency, ConstantLatency)):
             raise UnsupportedTopology(
                 f"server '{sv.name}': service distribution {type(sv.service_time).__name__} is not lowered")
@@ -868,6 +879,7 @@ def lower_lb(sources: list, entities: list, lb: LoadBalancer) -> LbGraph:
     for b in backends:
         if not isinstance(b, Server):
             raise UnsupportedTopology(f"backend '{b.name}' is a {type(b).__name__}: only Server backends are lowered")
+        refuse_queue_policy(b, "backend")
         if not isinstance(b.service_time, (ExponentialLatency, ConstantLatency)):
             raise UnsupportedTopology(f"backend '{b.name}': service distribution {type(b.service_time).__name__} is not lowered")
         if b.concurrency > 32:

@@ -21,7 +21,7 @@ import numpy as np
 from . import _native as N
 from .core.temporal import Instant
 from .engine import StationArrays, StationEngine
-from .entities import BatchProcessor, Bulkhead, Client, ConveyorBelt, GateController, HealthChecker, Probe, TimeoutWrapper
+from .entities import BatchProcessor, Bulkhead, Client, ConveyorBelt, FIFOQueue, GateController, HealthChecker, Probe, Server, TimeoutWrapper
 from .graph_engine import GeneralGraph, GraphEngine
 from .lowering import UnsupportedTopology, write_back, write_back_probes
 from .simulation import Simulation, entity_summaries
@@ -443,6 +443,10 @@ class ParallelSimulation:
                 if isinstance(ent, (BatchProcessor, ConveyorBelt, GateController)):
                     raise UnsupportedTopology(f"partition '{p.name}': the {type(ent).__name__} '{ent.name}' on a ParallelSimulation partition "
                                               "is not lowered (it runs on the single-heap loop: pass it to a Simulation)")
+                if isinstance(ent, Server) and type(ent._policy) is not FIFOQueue:
+                    raise UnsupportedTopology(f"partition '{p.name}': the queue policy {type(ent._policy).__name__} of Server '{ent.name}' on a "
+                                              "ParallelSimulation partition is not lowered (it runs on the single-heap loop: pass it to a "
+                                              "Simulation)")
                 if isinstance(ent, Client):
                     raise UnsupportedTopology(f"partition '{p.name}': the Client '{ent.name}' on a ParallelSimulation partition is not "
                                               "lowered (a Client runs on the single-heap loop: pass it to a Simulation)")

@@ -509,7 +509,8 @@ class Simulation:
         rec = eng.records()
         health, wrappers, clients, flows = g.arrays.has_health, g.arrays.has_wrappers, g.arrays.has_clients, g.arrays.has_flows
         write_back_general(g, stats, *rec, device=self._device, health=eng.health if health else None,
-                           wrapper=eng.wrapper if wrappers else None, client=eng.client if clients else None, flow=eng.flow if flows else None)
+                           wrapper=eng.wrapper if wrappers else None, client=eng.client if clients else None, flow=eng.flow if flows else None,
+                           queue=eng.queue_policy if g.arrays.has_queue_policies else None)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
         if health:
@@ -528,7 +529,7 @@ class Simulation:
             fe = eng.flow_events()
             self._flow_by_kind = fe[:N.FLOW_KINDS]
             self._events_cancelled += int(fe[N.FLOW_KINDS])
-        if (health or wrappers or clients or flows) and not self._faults:
+        if (health or wrappers or clients or flows or g.arrays.has_queue_policies) and not self._faults:
             self._internal_by_kind = eng.faults()[1]
         if self._faults:
             crashed, internal, popped_cancelled = eng.faults()

@@ -1057,6 +1057,32 @@ int hs_graph_schedule_gate(hs_graph *g, int32_t node, int64_t time_ns, int32_t o
  *   cancelled                   `_BatchTimeout` Events popped after their batch had started (events_cancelled counts them).
  * node = -1 with counters NULL: the graph's counts alone. */
 int hs_graph_get_flow(hs_graph *g, int32_t node, int64_t *counters, int64_t *events, int64_t *cancelled);
+/* A Server's queue policy other than the FIFO (components/queue_policy.py LIFOQueue, components/queue_policies/adaptive_lifo.py
+ * AdaptiveLIFO, codel.py CoDelQueue).  A graph that holds such a Server runs a seventh instantiation of the loop (it carries the
+ * fault, health, wrapper, Client and flow code too); its other Servers keep the FIFO path.  No new Event kinds: the policy changes what
+ * HS_EV_ENQUEUE pushes and what HS_EV_POLL pops, events_by_kind and events_processed keep their meaning.
+ *   LIFO          push appends and refuses at capacity; pop takes the newest item.
+ *   AdaptiveLIFO  push likewise (capacity_rejected / enqueued); pop evaluates len >= congestion_threshold BEFORE it removes anything,
+ *                 counts a mode switch when that differs from the last pop's, then takes the newest (dequeued_lifo) or the oldest
+ *                 (dequeued_fifo) item.
+ *   CoDel         push stamps the item with `now`; pop removes the head, computes its sojourn time and runs the reference's
+ *                 `_codel_dequeue` operation for operation in binary64 (correctly rounded division and square root, from_seconds
+ *                 truncates): the popped item is always delivered, the items it drops behind it go back to the free list and reach no
+ *                 handler (their completion hook fired when they were enqueued).
+ * hs_graph_set_queue_policy, before the first run (HS_E_STATE afterwards), once per Server: capacity < 0 is unbounded and replaces the
+ * node's queue_cap; threshold is read for HS_QUEUE_ADAPTIVE_LIFO, target_s / interval_s for HS_QUEUE_CODEL.  The reference's own
+ * ValueErrors as HS_E_INVALID with its texts.
+ * hs_graph_get_queue_policy, out[HS_QUEUE_FIELDS]: policy, len, enqueued, dequeued (CoDel) / dequeued_fifo, dequeued_lifo, dropped,
+ *   capacity_rejected, mode_switches (AdaptiveLIFO) / drop_intervals (CoDel), _was_congested / _dropping, _count, _last_count,
+ *   _first_above_time is set, its ns, _drop_next is set, its ns, 0. */
+typedef enum hs_queue_policy { HS_QUEUE_FIFO = 0, HS_QUEUE_LIFO = 1, HS_QUEUE_ADAPTIVE_LIFO = 2, HS_QUEUE_CODEL = 3 } hs_queue_policy;
+#define HS_QUEUE_FIELDS 16
+int hs_graph_set_queue_policy(hs_graph *g, int32_t node, int32_t policy, int64_t capacity, int64_t threshold, double target_s, double interval_s);
+int hs_graph_get_queue_policy(hs_graph *g, int32_t node, int64_t *out);
+/* Debug / tests only (the null stream, its own allocations): CoDelQueue._control_law's step on the device, one (count, interval_s) pair
+ * per thread: out_ns[i] = Duration.from_seconds(interval_s[i] / sqrt(count[i])) in ns (count >= 1, 0 < interval <= 4e9).  Tests compare
+ * it with CPython. */
+int hs_debug_codel_next(int32_t device, int64_t n, const int64_t *count, const double *interval_s, int64_t *out_ns);
 /* Auto-termination (core/simulation.py:306-322, end_time = Infinity): a run to end_ns = 2^61 ends in front of a pop when only daemon
  * events -- the limiters' polls -- are pending.  A run with any other end processes polls like any event. */
 /* Debug / tests only (no engine path calls it; the null stream, its own allocations): FixedWindowPolicy._get_window_start on the device, one (now_ns, window_s) pair per thread: out_div[i] = Python's float
