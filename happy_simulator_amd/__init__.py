@@ -31,7 +31,8 @@ from .entities import Client, ClientStats, DecorrelatedJitter, ExponentialBackof
 from .entities import (AdaptiveLIFO, AdaptiveLIFOStats, CoDelQueue, CoDelStats, DeadlineQueue, FairQueue, LIFOQueue, PriorityQueue,  # noqa: F401
                        REDQueue, WeightedFairQueue)
 from .entities import (BatchProcessor, BatchProcessorStats, ConveyorBelt, ConveyorStats, GateController, GateStats)  # noqa: F401
-from .faults import CrashNode, FaultHandle, FaultSchedule, FaultStats, PauseNode  # noqa: F401
+from .entities import LinkStats, Network  # noqa: F401
+from .faults import CrashNode, FaultHandle, FaultSchedule, FaultStats, InjectLatency, InjectPacketLoss, PauseNode  # noqa: F401
 from .lowering import UnsupportedTopology  # noqa: F401
 from .parallel import (ParallelResult, ParallelRunner, ParallelSimulation, ParallelSimulationSummary,  # noqa: F401
                        PartitionLink, RunConfig, SimulationPartition, reduce_summaries, shard_range)

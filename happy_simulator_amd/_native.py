@@ -49,6 +49,7 @@ FLOW_MAX_ITEMS = 1 << 20                                    # include/hs_engine.
 FLOW_COUNTERS, FLOW_KINDS = 8, 8                            # HS_FLOW_COUNTERS, HS_FLOW_KINDS
 QUEUE_FIFO, QUEUE_LIFO, QUEUE_ADAPTIVE_LIFO, QUEUE_CODEL = 0, 1, 2, 3   # hs_queue_policy
 QUEUE_FIELDS = 16                                           # HS_QUEUE_FIELDS
+LINK_FAULT_LATENCY, LINK_FAULT_LOSS = 1, 2                  # hs_link_fault
 # hs_limiter_policy / hs_limiter_outcome (the third column of a limiter's records)
 LIMITER_TOKEN_BUCKET, LIMITER_LEAKY_BUCKET, LIMITER_SLIDING_WINDOW, LIMITER_FIXED_WINDOW, LIMITER_NONE = 0, 1, 2, 3, 255
 LIMITER_FORWARDED, LIMITER_QUEUED, LIMITER_DROPPED, LIMITER_DRAINED = 0, 1, 2, 3
@@ -511,6 +512,10 @@ def lib():
     L.hs_graph_add_fault.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
     L.hs_graph_get_faults.restype = C.c_int
     L.hs_graph_get_faults.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64)]
+    L.hs_graph_add_link_fault.restype = C.c_int
+    L.hs_graph_add_link_fault.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32]
+    L.hs_graph_get_link_faults.restype = C.c_int
+    L.hs_graph_get_link_faults.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_graph_set_health_checker.restype = C.c_int
     L.hs_graph_set_health_checker.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32]
     L.hs_graph_set_lb_health.restype = C.c_int
@@ -601,7 +606,7 @@ EXPORTED_SYMBOLS = (
     "hs_graph_last_error", "hs_graph_destroy",
     "hs_graph_set_lb_weights", "hs_graph_coop_selects", "hs_debug_graph_flags", "hs_lb_set_weights", "hs_lb_wrr_table", "hs_lb_ip_hash_select",
     "hs_graph_set_limiter_policy", "hs_graph_get_limiter", "hs_debug_window_start",
-    "hs_graph_add_fault", "hs_graph_get_faults",
+    "hs_graph_add_fault", "hs_graph_get_faults", "hs_graph_add_link_fault", "hs_graph_get_link_faults",
     "hs_graph_set_health_checker", "hs_graph_set_lb_health", "hs_graph_get_health", "hs_graph_get_lb_current_weights",
     "hs_graph_set_wrapper", "hs_graph_get_wrapper",
     "hs_graph_set_client", "hs_graph_schedule_client", "hs_graph_get_client",

@@ -84,7 +84,8 @@ struct GParam {                                // 64 bytes, read-only
 struct GState {                                // 64 bytes
     // Source: a = ArrivalTimeProvider.current_time, b = arrival draws, c = generated_count, d = payload Requests built
     // Server: a = stats_accepted, b = stats_dropped, c = completed, d = rejected
-    // link:   a = entered, b = packets_sent, c = packets_dropped, d = jitter draws
+    // link:   a = entered, b = packets_sent, c = packets_dropped, d = jitter draws; a graph with link faults (GVars::n_link_faults):
+    //         svc_draws = loss draws, qlen / active = the latency / loss fault in force (1 + its place in GVars::faults; 0: none)
     // router: a = stats_routed (= route draws);  Sink: a = events_received
     // Probe:  a = ticks taken from its table, c = samples
     // limiter: a = received (= Requests handled), b = dropped, c = queued, d = polls handled; forwarded = a - b - qlen;
@@ -180,7 +181,12 @@ static_assert(kEvFlowKinds <= 64, "kDropKindsFlow is two words; s_by_kind is zer
 constexpr int kMaxBulkheadConcurrent = HS_BULKHEAD_MAX_CONCURRENT;         // Bulkhead.max_concurrent the in-flight table is sized for (include/hs_engine.h)
 constexpr int kDefaultTimeoutTable = 256;                // ids a TimeoutWrapper's (keys a Client's) table holds before it first grows
 constexpr int kMaxClientAttempts = HS_CLIENT_MAX_ATTEMPTS;   // the attempt of a key is 16 bits and one
-struct GFault { int64_t t; int32_t node; uint32_t flags; };   // hs_graph_add_fault: flags bit 0 = on, bit 1 = cancelled
+// hs_graph_add_fault: flags bit 0 = on, bit 1 = cancelled.  hs_graph_add_link_fault: bits 2-3 = 1 latency / 2 loss (0: a node fault),
+// value = what an activation puts in force -- the extra latency in seconds as the Duration the reference adds, or the loss rate.  A link
+// fault's heap entry carries 1 + its place in this array in GEvent::pad above the two flag bits (0: a node fault); the link's state
+// names the entry in force, so a link's handler reads the value here: the array stays on the device for the graph's life.
+struct GFault { int64_t t; int32_t node; uint32_t flags; double value; };
+constexpr uint32_t kFaultWhatShift = 2, kFaultLatency = 1, kFaultLoss = 2;
 // HealthChecker._backend_states / _pending_checks of one backend, at its slot of the LoadBalancer's targets (one checker per LoadBalancer)
 struct GHc {                                   // 32 bytes
     int64_t succ, fail;                        // consecutive_successes / consecutive_failures
@@ -235,6 +241,7 @@ struct GVars {                                 // device scalars
     long long flow_by_kind[HS_FLOW_KINDS];     // the flow entities' Events, kEvBpItem .. kEvGtClose (hs_graph_get_flow)
     long long flow_cancelled;                  // cancelled `_BatchTimeout` Events popped
     GQueue *qp;                                // the rows of the Servers with a queue policy (hs_graph_set_queue_policy; null: none)
+    long long n_link_faults;                   // entries of `faults` that are link faults (hs_graph_add_link_fault)
 };
 
 struct GCtl {                                  // kernel argument
@@ -613,13 +620,15 @@ __device__ inline bool tab_remove(int64_t *tab, int live, int64_t id) {
 // CL: ... has a Client -- a fifth, for the same reason.  CL implies R.
 // FL: ... has a BatchProcessor, a ConveyorBelt or a GateController -- a sixth, for the same reason.  FL implies CL.
 // Q: ... has a Server with a LIFOQueue, an AdaptiveLIFO or a CoDelQueue -- a seventh, for the same reason.  Q implies FL.
-template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false, bool Q = false>
+// LF: ... has a link fault (InjectLatency / InjectPacketLoss) -- an eighth, for the same reason.  LF implies Q.
+template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false, bool Q = false, bool LF = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     static_assert(F || !HC, "the health instantiation carries the fault code");
     static_assert(HC || !R, "the resilience instantiation carries the fault and health code");
     static_assert(R || !CL, "the client instantiation carries the fault, health and resilience code");
     static_assert(CL || !FL, "the flow instantiation carries the fault, health, resilience and client code");
     static_assert(FL || !Q, "the queue-policy instantiation carries the fault, health, resilience, client and flow code");
+    static_assert(Q || !LF, "the link-fault instantiation carries the code of all the others");
     constexpr uint32_t kKinds = FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
     // (one word for the instantiations whose kinds fit in it, two for the flow instantiation's 39)
     constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
@@ -658,6 +667,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
     long long polls_pending = V.polls_pending;   // daemon Events in the heap: they do not keep an auto-terminating run alive
     long long n_cancelled = 0;
     [[maybe_unused]] long long n_flow_cancelled = 0;
+    [[maybe_unused]] const bool lf_graph = LF && V.n_link_faults > 0;   // (a handle without link faults in a batch with one: the plain link)
     if (lane == 0) {
         if (!V.booted) {
             // Simulation.__init__ (core/simulation.py:145-154) + Source.start (load/source.py:120-140): the Sources in list order,
@@ -684,6 +694,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     const GFault f = faults[i];
                     GEvent fe = mk_pre(f.t, g++, (f.flags & 1u) ? kEvFaultOn : kEvFaultOff, f.node, -1);
                     if (f.flags & 2u) fe.pad |= kPadCancelled;
+                    if constexpr (LF) {
+                        if (f.flags >> kFaultWhatShift) fe.pad |= (uint32_t)(i + 1) << kPadIdShift;   // (at most 2^24 entries)
+                    }
                     H.push(fe);
                     polls_pending += 1;
                 }
@@ -850,6 +863,18 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     continue;
                 }
                 if (e.kind >= kEvFaultOn && (!HC || e.kind < kEvHcCycle)) {
+                    if constexpr (LF) {
+                        // a link fault's activate / deactivate (faults/network_faults.py:83-100,159-176): the entry that is in force
+                        // from now on.  Every fault read the link's original when it was constructed, so a deactivation restores
+                        // the original whichever activation came last.  (The callback is no Event at the link: a crashed link's
+                        // faults fire all the same -- these two kinds are not among kDrop.)
+                        const uint32_t fi = e.pad >> kPadIdShift;
+                        if (fi) {
+                            const int32_t now_on = e.kind == kEvFaultOn ? (int32_t)fi : 0;
+                            if (((V.faults[fi - 1].flags >> kFaultWhatShift) & 3u) == kFaultLatency) s.qlen = now_on; else s.active = now_on;
+                            continue;
+                        }
+                    }
                     // crash / restart, pause / resume (faults/node_faults.py:46-62,103-109): a flag, not a count.  The row may be the
                     // launch's LDS copy: the byte goes to its place in HBM as well, nothing else of a row is ever written.
                     const uint8_t v = e.kind == kEvFaultOn ? 1 : 0;
@@ -1383,13 +1408,32 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 (void)G++;                                                          // the continuation built by _start_process
                 const int64_t entered = s.a;
                 s.a = entered + 1;
-                if (p.loss > 0.0 && uniform_at(c.seed, stream_id(p.stream_base, kStreamLoss), (uint64_t)entered) < p.loss) {   // link.py:131-138
+                double loss = p.loss;
+                uint64_t loss_k = (uint64_t)entered;                                // (the rate never changes: every Request draws, or none does)
+                [[maybe_unused]] bool extra_on = false;
+                [[maybe_unused]] double extra_s = 0.0;
+                if constexpr (LF) {
+                    if (lf_graph) {
+                        // the rate and the latency in force (an InjectPacketLoss / InjectLatency between its two Events); the LOSS stream
+                        // is read one value per draw, and a Request that meets a rate of 0 draws nothing (link.py:130)
+                        if (s.active) loss = V.faults[s.active - 1].value;
+                        if (s.qlen) { extra_on = true; extra_s = V.faults[s.qlen - 1].value; }
+                        loss_k = s.svc_draws;
+                        if (loss > 0.0) s.svc_draws = loss_k + 1;
+                    }
+                }
+                if (loss > 0.0 && uniform_at(c.seed, stream_id(p.stream_base, kStreamLoss), loss_k) < loss) {   // link.py:131-138
                     s.c += 1;
                     if constexpr (R) fire_hook(e.req, false);                       // the generator ended before its first yield: the hooks run at once
                     c.reqs[e.req].next = req_free; req_free = e.req;
                     break;
                 }
                 double delay = seconds_from_ns(ns_from_seconds(p.lat_min));
+                if constexpr (LF) {
+                    // _CompoundLatency.get_latency (network_faults.py:41-44): Duration.from_seconds over the sum of the two Durations'
+                    // seconds, taken back to seconds -- also for an extra of 0, which may move the base by a nanosecond
+                    if (extra_on) delay = seconds_from_ns(ns_from_seconds(__dadd_rn(delay, extra_s)));
+                }
                 if (p.sub == HS_LAT_EXPONENTIAL) {
                     const double u = uniform_at(c.seed, stream_id(p.stream_base, kStreamLink), (uint64_t)s.d);
                     s.d += 1;
@@ -1757,6 +1801,12 @@ __global__ void __launch_bounds__(64) hs_graph_run_queues(GCtl c) {           //
     graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true>(c, lheap, lnodes);
 }
 
+__global__ void __launch_bounds__(64) hs_graph_run_link_faults(GCtl c) {      // ... with an InjectLatency or an InjectPacketLoss
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true>(c, lheap, lnodes);
+}
+
 // Independent graphs -- the replicas / sweep points of parallel/runner.py:82-142 -- side by side: one workgroup (one heap) each, one
 // with a quarter of the lone run's LDS window (32 KB + 6 KB of nodes: four workgroups per CU, 1 024 heaps on the device at once; a heap that outgrows
 // the window continues in HBM as it does behind the large one -- the window's size changes nothing the loop computes).
@@ -1823,6 +1873,14 @@ __global__ void __launch_bounds__(64) hs_graph_run_batch_queues(const GCtl *cs, 
     graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true>(c, lheap, lnodes);
     batch_report(c, stat);
 }
+// ... of a batch in which at least one handle has a link fault
+__global__ void __launch_bounds__(64) hs_graph_run_batch_link_faults(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
 
 }  // namespace graph
 }  // namespace hs
@@ -1866,6 +1924,7 @@ struct hs_graph {
     int n_clients = 0;
     std::vector<GQueue> qpol;                  // hs_graph_set_queue_policy: the rows of the Servers with a queue policy, in call order; a graph
     GQueue *d_qp = nullptr;                    // that holds one runs the seventh instantiation (the rows go to the device with the first run)
+    long long n_link_faults = 0;               // entries of `faults` from hs_graph_add_link_fault: a graph that holds one runs the eighth instantiation
     int n_flows = 0;                           // BatchProcessor / ConveyorBelt / GateController nodes: a graph that holds one runs the sixth instantiation
     std::vector<int64_t> cl_delays;            // every configured Client's delay table, back to back (GParam::lim = its offset)
     int64_t *d_cl_delays = nullptr;
@@ -2866,7 +2925,45 @@ int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, i
     if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "add_fault: node %d out of range", node);
     if (g->ran || g->launches > 0 || g->d_faults) return fail(g, HS_E_STATE, "add_fault: fault Events are constructed before the first run");
     if (g->faults.size() >= (size_t)1 << 24) return fail(g, HS_E_OVERFLOW, "more than 2^24 fault Events");
-    g->faults.push_back(GFault{time_ns, node, (on ? 1u : 0u) | (cancelled ? 2u : 0u)});
+    g->faults.push_back(GFault{time_ns, node, (on ? 1u : 0u) | (cancelled ? 2u : 0u), 0.0});
+    return HS_OK;
+}
+
+int hs_graph_add_link_fault(hs_graph *g, int32_t link_node, int64_t time_ns, int32_t what, int32_t on, double value, int32_t cancelled) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (link_node < 0 || link_node >= g->n || g->params[(size_t)link_node].kind != HS_NODE_LINK)
+        return fail(g, HS_E_INVALID, "add_link_fault: node %d is not a NetworkLink", link_node);
+    if (g->ran || g->launches > 0 || g->d_faults) return fail(g, HS_E_STATE, "add_link_fault: fault Events are constructed before the first run");
+    if (g->faults.size() >= (size_t)1 << 24) return fail(g, HS_E_OVERFLOW, "more than 2^24 fault Events");
+    if (what != HS_LINK_FAULT_LATENCY && what != HS_LINK_FAULT_LOSS) return fail(g, HS_E_INVALID, "add_link_fault: what = %d is neither latency nor loss", what);
+    if (what == HS_LINK_FAULT_LATENCY && on && !(value >= 0.0 && value < 4.0e9))
+        return fail(g, HS_E_UNSUPPORTED, "add_link_fault: an extra latency of %.6g s is not in [0, 4e9)", value);
+    if (what == HS_LINK_FAULT_LOSS && !(value >= 0.0 && value <= 1.0))
+        return fail(g, HS_E_UNSUPPORTED, "add_link_fault: a packet loss rate of %.6g is not in [0, 1]", value);
+    if (what == HS_LINK_FAULT_LATENCY && on) {                 // one step of the link may now be this much longer
+        const GParam &p = g->params[(size_t)link_node];
+        const double draw = p.sub == HS_LAT_EXPONENTIAL ? hs::kLongestExpDraw * p.mean : p.mean;
+        g->reach_s = std::max(g->reach_s, p.lat_min + value + draw);
+    }
+    g->faults.push_back(GFault{time_ns, link_node, (on ? 1u : 0u) | (cancelled ? 2u : 0u) | ((uint32_t)what << kFaultWhatShift), on || what == HS_LINK_FAULT_LOSS ? value : 0.0});
+    g->n_link_faults += 1;
+    return HS_OK;
+}
+
+int hs_graph_get_link_faults(hs_graph *g, int32_t *active_latency, int32_t *active_loss, int64_t *loss_draws) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    std::vector<GState> S((size_t)g->n);
+    HS_HIP(g, hipMemcpy(S.data(), g->ctl.S, (size_t)g->n * sizeof(GState), hipMemcpyDeviceToHost));
+    for (int i = 0; i < g->n; ++i) {
+        const GState &s = S[(size_t)i];
+        const GParam &p = g->params[(size_t)i];
+        const bool lnk = p.kind == HS_NODE_LINK, lf = lnk && g->n_link_faults > 0;
+        if (active_latency) active_latency[i] = lf ? s.qlen - 1 : -1;
+        if (active_loss) active_loss[i] = lf ? s.active - 1 : -1;
+        // (without link faults the rate never changes: every Request that entered drew, or none did)
+        if (loss_draws) loss_draws[i] = lf ? (int64_t)s.svc_draws : lnk && p.loss > 0.0 ? s.a : 0;
+    }
     return HS_OK;
 }
 
@@ -3000,6 +3097,8 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         const long long nf = (long long)g->faults.size();
         HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, faults), &df, sizeof df, hipMemcpyHostToDevice));
         HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, n_faults), &nf, sizeof nf, hipMemcpyHostToDevice));
+        const long long nlf = g->n_link_faults;
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, n_link_faults), &nlf, sizeof nlf, hipMemcpyHostToDevice));
     }
     if (g->n_checkers > 0 && !g->d_health)
         for (int i = 0; i < g->n; ++i)
@@ -3202,7 +3301,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, g->ctl);
@@ -3258,7 +3358,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
         if ((he = hipMemcpy(d_ctl, h_ctl.data(), h_ctl.size() * sizeof(GCtl), hipMemcpyHostToDevice)) != hipSuccess) break;
         bool any_faults = false, any_health = false, any_wrappers = false, any_clients = false, any_flows = false, any_queues = false;
         for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; any_clients |= gs[i]->n_clients > 0; any_flows |= gs[i]->n_flows > 0; any_queues |= !gs[i]->qpol.empty(); }
-        if (any_queues) hipLaunchKernelGGL(hs_graph_run_batch_queues, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_link_faults = false;
+        for (int i : pending) any_link_faults |= gs[i]->n_link_faults > 0;
+        if (any_link_faults) hipLaunchKernelGGL(hs_graph_run_batch_link_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else if (any_queues) hipLaunchKernelGGL(hs_graph_run_batch_queues, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_flows) hipLaunchKernelGGL(hs_graph_run_batch_flow, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_clients) hipLaunchKernelGGL(hs_graph_run_batch_client, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_wrappers) hipLaunchKernelGGL(hs_graph_run_batch_resilience, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
@@ -3331,7 +3434,8 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count; one.rs_tab = g->ctl.rs_tab;
-        if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, one);
+        if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, one);
+        else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, one);

@@ -67,6 +67,23 @@ class ExponentialLatency(LatencyDistribution):
 class ConstantLatency(LatencyDistribution):
     __slots__ = ()
 
+    def get_latency(self, current_time=None) -> Duration:
+        return Duration.from_seconds(self._mean_latency)         # distributions/constant.py:33-35
+
+
+class _CompoundLatency(LatencyDistribution):
+    """faults/network_faults.py:27-44: what an active InjectLatency leaves in `link.latency` -- the link's original distribution
+    plus a ConstantLatency of the extra.  The engine adds the two terms the same way (csrc/hs_graph.hip, the link handler)."""
+    __slots__ = ("_base", "_extra")
+
+    def __init__(self, base: LatencyDistribution, extra: LatencyDistribution):
+        super().__init__(base._mean_latency + extra._mean_latency)
+        self._base = base
+        self._extra = extra
+
+    def get_latency(self, current_time=None) -> Duration:
+        return Duration.from_seconds(self._base.get_latency(current_time).to_seconds() + self._extra.get_latency(current_time).to_seconds())
+
 
 # ---- queue policy --------------------------------------------------------------------------------
 class FIFOQueue:
@@ -777,6 +794,8 @@ class NetworkLink(Entity):
         self.packets_sent = 0
         self.packets_dropped = 0
         self._entered = 0
+        self._loss_draws = 0              # values read from the link's LOSS stream: one per Request that met a rate > 0
+        self._reverse_of = None           # the link this one is Network.add_bidirectional_link's reverse copy of
 
     def downstream_entities(self) -> list[Entity]:
         return [self.egress] if self.egress is not None else []
@@ -788,6 +807,85 @@ class NetworkLink(Entity):
     @property
     def current_utilization(self) -> float:
         return 0.0          # bandwidth is infinite on the lowered path (link.py:93-95)
+
+
+@dataclass(frozen=True)
+class LinkStats:
+    """components/network/network.py:28-44."""
+    source: str = ""
+    destination: str = ""
+    packets_sent: int = 0
+    packets_dropped: int = 0
+    bytes_transmitted: int = 0
+
+
+class Network(Entity):
+    """components/network/network.py:82-426 as a REGISTRY: the links by (source name, destination name), where the link faults
+    (faults.InjectLatency / InjectPacketLoss) look theirs up.  Traffic goes to the links directly -- `add_link` sets `link.egress` --;
+    routing by an Event's source / destination metadata (`handle_event`, `send`) and partitions are not lowered, so the three routing
+    counters stay 0.  In `entities=[...]` a Network holds its place in the entity order and receives no Events."""
+
+    def __init__(self, name: str, default_link: "NetworkLink | None" = None):
+        super().__init__(name)
+        self.default_link = default_link
+        self._routes: dict[tuple[str, str], NetworkLink] = {}
+        self._known_entities: dict[str, Entity] = {}
+        self.events_routed = 0
+        self.events_dropped_no_route = 0
+        self.events_dropped_partition = 0
+
+    def add_link(self, source: Entity, dest: Entity, link: "NetworkLink") -> None:
+        self._known_entities[source.name] = source
+        self._known_entities[dest.name] = dest
+        link.egress = dest                                           # network.py:141-142
+        self._routes[(source.name, dest.name)] = link
+
+    def add_bidirectional_link(self, a: Entity, b: Entity, link: "NetworkLink") -> None:
+        """network.py:153-190: the reverse direction is a shallow copy named `<name>_reverse` with its stats zeroed.  The copy shares
+        the forward link's jitter object (and, in the recorded runs, its loss stream): it may be looked up and read, but a run that
+        sends traffic through it or names it in a fault is refused."""
+        import copy
+
+        link.egress = b
+        self._routes[(a.name, b.name)] = link
+        reverse = copy.copy(link)
+        reverse.name = f"{link.name}_reverse"
+        reverse.egress = a
+        reverse.bytes_transmitted = 0
+        reverse.packets_sent = 0
+        reverse.packets_dropped = 0
+        reverse._entered = 0
+        reverse._loss_draws = 0
+        reverse._reverse_of = link
+        self._routes[(b.name, a.name)] = reverse
+        self._known_entities[a.name] = a
+        self._known_entities[b.name] = b
+
+    def get_link(self, source_name: str, dest_name: str) -> "NetworkLink | None":
+        return self._routes.get((source_name, dest_name), self.default_link)
+
+    def is_partitioned(self, source_name: str, dest_name: str) -> bool:
+        return False
+
+    def traffic_matrix(self) -> list[LinkStats]:
+        return [LinkStats(source=s, destination=d, packets_sent=link.packets_sent, packets_dropped=link.packets_dropped,
+                          bytes_transmitted=link.bytes_transmitted) for (s, d), link in self._routes.items()]
+
+    @staticmethod
+    def _refuse(what: str):
+        from .lowering import UnsupportedTopology
+
+        raise UnsupportedTopology(f"Network.{what} is not lowered: it acts on traffic routed by Network.handle_event, and the lowered "
+                                  "traffic goes to the links directly")
+
+    def partition(self, group_a, group_b, *, asymmetric: bool = False):
+        self._refuse("partition")
+
+    def heal_partition(self) -> None:
+        self._refuse("heal_partition")
+
+    def send(self, source, destination, event_type, payload=None, daemon=False):
+        self._refuse("send")
 
 
 # ---- network condition presets (components/network/conditions.py:13-258): the same nine links, from one table ----------------

@@ -24,7 +24,7 @@ from . import _native as N
 from .core.temporal import Duration, Instant
 from .entities import (AdaptiveLIFO, CoDelQueue, FIFOQueue, QUEUE_POLICIES, BatchProcessor, ConveyorBelt, GateController,
                        BackendHealthState, Bulkhead, Client, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
-                       ExponentialLatency, HealthChecker, IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, NetworkLink, Probe, Random,
+                       ExponentialLatency, HealthChecker, IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, Network, NetworkLink, Probe, Random,
                        RandomRouter, RateLimitedEntity, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source,
                        DecorrelatedJitter, ExponentialBackoff, FixedRetry, NoRetry,
                        TimeoutWrapper, TokenBucketPolicy, WeightedLeastConnections, WeightedRoundRobin)
@@ -154,6 +154,7 @@ class GraphEngine:
                 raise N.EngineUnavailable(msg)
             raise N.EngineError(rc, msg)
         self._h = h
+        self._fault_tags: list = []          # per hs_graph_add_fault / hs_graph_add_link_fault call: the caller's tag of a link fault Event
         if arrays.lb_weights is not None and arrays.lb_strategy is not None:
             # WeightedRoundRobin / WeightedLeastConnections: strategy._weights, per LoadBalancer in slot order (the default is all ones)
             w = np.ascontiguousarray(arrays.lb_weights, np.int32)
@@ -361,6 +362,35 @@ class GraphEngine:
     def add_fault(self, node: int, time_ns: int, on: bool, cancelled: bool = False) -> None:
         """hs_graph_add_fault: one fault Event (set / clear the crashed flag of `node`), numbered in call order."""
         self._check(self._lib.hs_graph_add_fault(self._h, int(node), int(time_ns), int(bool(on)), int(bool(cancelled))))
+        self._fault_tags.append(None)
+
+    def add_link_fault(self, node: int, time_ns: int, what: str, on: bool, value: float, cancelled: bool = False, tag=None) -> None:
+        """hs_graph_add_link_fault: one Event of an InjectLatency (`what` = "latency") or an InjectPacketLoss ("loss") on link `node`,
+        numbered in call order with add_fault's.  `tag` comes back from link_faults() while this Event's activation is in force."""
+        if what not in ("latency", "loss"):
+            raise ValueError(f"add_link_fault: what = {what!r} is neither 'latency' nor 'loss'")
+        code = N.LINK_FAULT_LATENCY if what == "latency" else N.LINK_FAULT_LOSS
+        self._check(self._lib.hs_graph_add_link_fault(self._h, int(node), int(time_ns), code, int(bool(on)), float(value), int(bool(cancelled))))
+        self._fault_tags.append(tag)
+
+    def add_faults(self, entries) -> None:
+        """Simulation._general_faults' entries in their order: (node, ns, on, cancelled) of a node fault, (node, ns, on, cancelled,
+        LinkFaultEvent) of a link fault."""
+        for node, t, on, cancelled, *lf in entries:
+            if lf:
+                self.add_link_fault(node, t, lf[0].what, on, lf[0].value, cancelled, tag=lf[0])
+            else:
+                self.add_fault(node, t, on, cancelled)
+
+    def link_faults(self) -> dict:
+        """hs_graph_get_link_faults: {link node: (tag of the latency activation in force or None, tag of the loss activation in force
+        or None, values read from the LOSS stream)}."""
+        n = self.arrays.n
+        lat, loss, draws = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
+        self._check(self._lib.hs_graph_get_link_faults(self._h, _ptr(lat), _ptr(loss), _ptr(draws)))
+        tags = self._fault_tags
+        return {int(i): (tags[lat[i]] if lat[i] >= 0 else None, tags[loss[i]] if loss[i] >= 0 else None, int(draws[i]))
+                for i in np.nonzero(self.arrays.kind == N.NODE_LINK)[0]}
 
     def faults(self):
         """hs_graph_get_faults: (crashed flag per node, the four internal kinds' event counts -- limiter Requests, limiter polls,
@@ -522,6 +552,14 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
     def check(ent, where):
         if isinstance(ent, Source):
             raise UnsupportedTopology(f"{where}: a Source takes no Requests")
+        if isinstance(ent, Network):
+            # (routing by an Event's source / destination metadata, Network.handle_event, is not lowered: traffic goes to the links)
+            raise UnsupportedTopology(f"{where}: an Event aimed at the Network '{ent.name}' is not lowered (a Network is a registry of "
+                                      "links here: send to the link itself)")
+        if isinstance(ent, NetworkLink) and ent._reverse_of is not None:
+            raise UnsupportedTopology(f"{where}: link '{ent.name}' is the reverse copy add_bidirectional_link made of "
+                                      f"'{ent._reverse_of.name}' -- it shares its jitter object and its loss stream with the forward link "
+                                      "(not lowered)")
         if isinstance(ent, HealthChecker) and where != "entities":
             raise UnsupportedTopology(f"{where}: the HealthChecker '{ent.name}' takes no Requests")
         if not isinstance(ent, lowered):
@@ -534,6 +572,9 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             continue
         if not isinstance(ent, Entity):
             raise UnsupportedTopology(f"object {ent!r} is not an Entity")
+        if isinstance(ent, Network):
+            add(ent)                                          # its place in the entity order; nothing forwards to it (check())
+            continue
         check(ent, "entities")
         add(ent)
     # whatever is only reachable downstream (the reference never needs it listed: events carry their target), in discovery order
@@ -867,7 +908,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             a.rt_cnt[i] = len(ent.targets)
             rt.extend(node_of[id(t)] for t in ent.targets)
         else:
-            a.kind[i] = N.NODE_SINK
+            a.kind[i] = N.NODE_SINK                           # (a Network too: a node that no Event reaches)
     a.rt_targets = np.array(rt, np.int32)
     if a.cl_params is not None:
         a.cl_delay_off = np.zeros(n + 1, np.int64)
@@ -1031,6 +1072,12 @@ class PartRun:
             cancelled += k
         return crashed, internal, cancelled
 
+    def link_faults(self) -> dict:
+        out = {}
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            out.update({int(ids[i]): v for i, v in e.link_faults().items()})
+        return out
+
     def health_events(self) -> np.ndarray:
         return np.sum([e.health_events() for e in self.engines], axis=0).astype(np.int64)
 
@@ -1177,6 +1224,10 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
             ent.packets_sent = int(stats["packets_sent"][i])
             ent.packets_dropped = int(stats["packets_dropped"][i])
             ent._entered = int(stats["entered"][i])
+            # (a graph with link faults: Simulation._general_finish puts the count of the engine's own word here)
+            ent._loss_draws = ent._entered if ent.packet_loss_rate > 0 else 0
+        elif isinstance(ent, Network):
+            pass                                                   # (a registry: traffic_matrix() reads its links)
         elif isinstance(ent, LoadBalancer):
             (ent._requests_received, ent._requests_forwarded, ent._requests_failed, ent._no_backend_available,
              ent._in_flight_count, selections) = (int(v) for v in stats["lb"][i])

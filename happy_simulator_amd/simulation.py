@@ -14,8 +14,8 @@ from .core.temporal import Instant
 from .engine import StationEngine
 from .graph_engine import (DEFAULT_MAX_EVENTS, MAX_PARTS, GeneralGraph, GraphEngine, PartRun, keyless_hazard, lower_general, split_parts,
                            write_back_general)
-from .entities import BatchProcessor, Bulkhead, Client, ConveyorBelt, Entity, GateController, HealthChecker, LoadBalancer, Server, TimeoutWrapper
-from .faults import FaultSchedule
+from .entities import BatchProcessor, Bulkhead, Client, ConveyorBelt, Entity, GateController, HealthChecker, LoadBalancer, Network, Server, TimeoutWrapper
+from .faults import FaultSchedule, LinkFaultEvent
 from .lowering import (LazyRecords, LbGraph, LoweredGraph, UnsupportedTopology, attach_lb_probes, attach_probes, find_load_balancer, lower,
                        plain_probe_arrays, write_back_plain_probes,
                        lower_lb, write_back, write_back_lb, write_back_plain, write_back_probes, write_back_shared_sink_probes)
@@ -367,7 +367,7 @@ class Simulation:
         daemons = auto and bool((g.arrays.kind == N.NODE_RATE_LIMITER).any() or self._faults or any(len(e) > 3 for e in sched))   # (... or gate Events)
         faults = self._general_faults(g)
         # (a cancelled fault Event stays in its heap, as in the reference's: it is no candidate for the one Event beyond the end)
-        parts = None if cancelled_ns or daemons or any(c for _n, _t, _on, c in faults) else split_parts(g.arrays, MAX_PARTS)
+        parts = None if cancelled_ns or daemons or any(f[3] for f in faults) else split_parts(g.arrays, MAX_PARTS)
         try:
             self._refuse_long_run(1 if parts is None else len(parts))
         except UnsupportedTopology:
@@ -388,8 +388,8 @@ class Simulation:
                 for p, (ids, _pos, b) in enumerate(parts):
                     engines.append(GraphEngine(b, seed=self._seed, start_ns=start_ns, device=self._device, max_events=self._max_graph_events,
                                                record_capacity=4096))
-                for node, t, on, cancelled in faults:              # (a fault Event lives in the part of the entity it names)
-                    engines[int(part_of[node])].add_fault(int(local[node]), t, on, cancelled)
+                for node, *rest in faults:                         # (a fault Event lives in the part of the entity or link it names)
+                    engines[int(part_of[node])].add_faults([(int(local[node]), *rest)])
                 for node, t, *rid in sched:                        # (call order: each part keeps the order of its own)
                     engines[int(part_of[node])].schedule(int(local[node]), t, *rid)
                 run = PartRun(g.arrays, parts, engines)
@@ -432,6 +432,9 @@ class Simulation:
                 cancelled_ns.append(ev.time.nanoseconds)
                 continue
             i = g.node_of.get(id(ev.target))
+            if isinstance(ev.target, Network):
+                raise UnsupportedTopology(f"scheduled event {ev!r}: an Event aimed at the Network '{ev.target.name}' is not lowered (a Network "
+                                          "is a registry of links here: send to the link itself)")
             if i is not None and a.kind[i] == N.NODE_HEALTH_CHECKER and ev.event_type != "_health_check_cycle":
                 raise UnsupportedTopology(f"scheduled event {ev!r}: only the Event start() returns is lowered for a HealthChecker")
             if i is None or a.kind[i] == N.NODE_SOURCE:
@@ -489,8 +492,7 @@ class Simulation:
         eng = GraphEngine(g.arrays, seed=self._seed, start_ns=start_ns, device=self._device, max_events=self._max_graph_events,
                           record_capacity=record_capacity)
         try:
-            for node, t, on, cancelled in self._general_faults(g):
-                eng.add_fault(node, t, on, cancelled)
+            eng.add_faults(self._general_faults(g))
             for node, t, *rid in sched:
                 eng.schedule(node, t, *rid)
         except BaseException:
@@ -498,9 +500,21 @@ class Simulation:
             raise
         return eng
 
-    def _general_faults(self, g: GeneralGraph) -> list[tuple[int, int, bool, bool]]:
-        """The fault Events as (node, ns, on, cancelled by now), in the order Simulation.__init__ constructed them."""
-        return [(g.node_of[id(ent)], ev.time.nanoseconds, on, ev.cancelled) for ent, ev, on in self._faults]
+    def _general_faults(self, g: GeneralGraph) -> list[tuple]:
+        """The fault Events as (node, ns, on, cancelled by now) -- a link fault's: (link node, ns, on, cancelled by now, its
+        LinkFaultEvent) --, in the order Simulation.__init__ constructed them."""
+        out = []
+        for f in self._faults:
+            if isinstance(f, LinkFaultEvent):
+                node = g.node_of.get(id(f.link))
+                if node is None:
+                    raise UnsupportedTopology(f"link '{f.link.name}' is named by a link fault but is no entity of this Simulation: nothing "
+                                              "sends to it and `entities` does not list it (not lowered)")
+                out.append((node, f.event.time.nanoseconds, f.on, f.event.cancelled, f))
+            else:
+                ent, ev, on = f
+                out.append((g.node_of[id(ent)], ev.time.nanoseconds, on, ev.cancelled))
+        return out
 
     def _general_finish(self, g: GeneralGraph, eng: GraphEngine, end_ns: int, cancelled_ns, wall_s: float) -> SimulationSummary:
         """The run's results off the engine onto the user's objects (the engine may have run alone or in a batch)."""
@@ -536,8 +550,25 @@ class Simulation:
             self._internal_by_kind = internal                      # (limiter Requests, limiter polls, fault set, fault clear)
             self._fault_events_processed = int(internal[2] + internal[3])
             self._events_cancelled += popped_cancelled
-            for ent, _ev, _on in self._faults:                     # the flag every named entity is left with (faults/node_faults.py:46-62)
-                ent._crashed = bool(crashed[g.node_of[id(ent)]])
+            for f in self._faults:                                 # the flag every named entity is left with (faults/node_faults.py:46-62)
+                if not isinstance(f, LinkFaultEvent):
+                    f[0]._crashed = bool(crashed[g.node_of[id(f[0])]])
+            link_events = [f for f in self._faults if isinstance(f, LinkFaultEvent)]
+            if link_events:
+                # what the fault in force leaves on its link (faults/network_faults.py:83-100,159-176): the _CompoundLatency / the
+                # raised rate of the activation that came last, or the original a deactivation put back
+                state = eng.link_faults()
+                self._link_fault_state = {}                        # id(link) -> the schedule's place of the latency / loss fault in force (-1: none)
+                for f in link_events:
+                    if f.on:
+                        continue                                   # (every fault has a deactivation: it holds the original)
+                    lat, loss, draws = state[g.node_of[id(f.link)]]
+                    if f.what == "latency":
+                        f.link.latency = f.leaves if lat is None else lat.leaves
+                    else:
+                        f.link.packet_loss_rate = f.leaves if loss is None else loss.leaves
+                    f.link._loss_draws = draws
+                    self._link_fault_state[id(f.link)] = (-1 if lat is None else lat.index, -1 if loss is None else loss.index)
         self._engine_summary = es
         self._events_processed = es.events_processed
         self._current_time = Instant(es.final_time_ns)

@@ -916,6 +916,22 @@ int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, i
  * Requests, its polls, fault Events that set a flag, fault Events that clear one -- events_processed == sum(events_by_kind) +
  * sum(internal_by_kind); *cancelled = cancelled fault Events popped.  Any of the three may be NULL. */
 int hs_graph_get_faults(hs_graph *g, uint8_t *crashed, int64_t *internal_by_kind, int64_t *cancelled);
+/* Link faults: InjectLatency and InjectPacketLoss (faults/network_faults.py:27-198).  Each of a fault's two Events is one call, in the
+ * one FaultSchedule.add() order with hs_graph_add_fault's (they share the numbering, the daemon rule, `cancelled` and the two internal
+ * kinds: an activation counts as a fault Event that sets, a deactivation as one that clears).  The Events are aimed at a callback, not
+ * at the link: a crashed or paused link does not drop them.  `what`: HS_LINK_FAULT_LATENCY -- from an activation on, the base term of
+ * the link's delay is Duration.from_seconds(base.to_seconds() + value) taken back to seconds, value = the extra as the seconds of the
+ * Duration the reference's ConstantLatency(extra_ms / 1000) returns; HS_LINK_FAULT_LOSS -- from an activation on, the loss rate is
+ * `value` (min(1.0, original + loss_rate)).  A deactivation restores the node's own lat_min / loss_rate whichever activation came last
+ * (every fault read the original when it was constructed).  A Request in transit keeps its delay.  A graph with a link fault reads the
+ * link's LOSS stream one value per draw (a Request that meets a rate of 0 draws nothing) and runs an eighth instantiation of the loop
+ * (it carries the code of all the others).  Before the first run (HS_E_STATE afterwards).
+ * hs_graph_get_link_faults, per node (any may be NULL): the place -- among all hs_graph_add_fault / hs_graph_add_link_fault calls, from
+ * 0 -- of the latency / loss activation in force on a link (-1: none, or no link), and the values the link has read from its LOSS
+ * stream. */
+typedef enum hs_link_fault { HS_LINK_FAULT_LATENCY = 1, HS_LINK_FAULT_LOSS = 2 } hs_link_fault;
+int hs_graph_add_link_fault(hs_graph *g, int32_t link_node, int64_t time_ns, int32_t what, int32_t on, double value, int32_t cancelled);
+int hs_graph_get_link_faults(hs_graph *g, int32_t *active_latency, int32_t *active_loss, int64_t *loss_draws);
 /* Backend health: HealthChecker (components/load_balancer/health_check.py) and LoadBalancer.mark_unhealthy / mark_healthy
  * (load_balancer.py:244-297).  A graph with a configured checker, or with initial health flags, runs an instantiation of the loop of
  * its own; `_forward_request` then selects over the healthy backends in registration order (RoundRobin, LeastConnections,
