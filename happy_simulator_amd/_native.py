@@ -50,6 +50,9 @@ FLOW_COUNTERS, FLOW_KINDS = 8, 8                            # HS_FLOW_COUNTERS, 
 QUEUE_FIFO, QUEUE_LIFO, QUEUE_ADAPTIVE_LIFO, QUEUE_CODEL = 0, 1, 2, 3   # hs_queue_policy
 QUEUE_FIELDS = 16                                           # HS_QUEUE_FIELDS
 LINK_FAULT_LATENCY, LINK_FAULT_LOSS = 1, 2                  # hs_link_fault
+NODE_AUTO_SCALER = 15
+AUTOSCALER_TARGET_UTILIZATION, AUTOSCALER_STEP, AUTOSCALER_QUEUE_DEPTH = 0, 1, 2   # hs_autoscaler_policy
+AUTOSCALER_MAX_STEPS, AUTOSCALER_MAX_POOL, AUTOSCALER_FIELDS = 16, 4096, 12        # HS_AUTOSCALER_MAX_STEPS / _MAX_POOL / _FIELDS
 # hs_limiter_policy / hs_limiter_outcome (the third column of a limiter's records)
 LIMITER_TOKEN_BUCKET, LIMITER_LEAKY_BUCKET, LIMITER_SLIDING_WINDOW, LIMITER_FIXED_WINDOW, LIMITER_NONE = 0, 1, 2, 3, 255
 LIMITER_FORWARDED, LIMITER_QUEUED, LIMITER_DROPPED, LIMITER_DRAINED = 0, 1, 2, 3
@@ -64,6 +67,7 @@ PROBE_WRAPPER_METRICS = {"active_count": 8, "queue_depth": 9, "available_permits
 PROBE_CLIENT_METRICS = {"in_flight_count": 12}              # ... of a Client
 # ... of a BatchProcessor / ConveyorBelt / GateController (a gate's queue_depth is its own metric)
 PROBE_FLOW_METRICS = {"buffer_depth": 13, "items_in_transit": 14, "queue_depth": 15}
+PROBE_SCALER_METRICS = {"current_count": 16}                # ... of an AutoScaler
 PROBE_NONE = 255
 # hs_engine_run_path / hs_lb_run_path: which side of the host-side gates the last run landed on (include/hs_engine.h)
 RUN_ONE_LANE, RUN_ONE_LANE_UNI, RUN_WIDE, RUN_WAVE, RUN_TANDEM, RUN_SINGLE_HEAP = 1, 2, 4, 8, 16, 32
@@ -544,6 +548,11 @@ def lib():
     L.hs_graph_set_queue_policy.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double]
     L.hs_graph_get_queue_policy.restype = C.c_int
     L.hs_graph_get_queue_policy.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.hs_graph_set_auto_scaler.restype = C.c_int
+    L.hs_graph_set_auto_scaler.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32]
+    L.hs_graph_get_auto_scaler.restype = C.c_int
+    L.hs_graph_get_auto_scaler.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.hs_debug_codel_next.restype = C.c_int
     L.hs_debug_codel_next.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_graph_coop_selects.restype = C.c_int64
@@ -612,4 +621,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_set_client", "hs_graph_schedule_client", "hs_graph_get_client",
     "hs_graph_set_flow", "hs_graph_schedule_gate", "hs_graph_get_flow",
     "hs_graph_set_queue_policy", "hs_graph_get_queue_policy", "hs_debug_codel_next",
+    "hs_graph_set_auto_scaler", "hs_graph_get_auto_scaler",
 )

@@ -157,6 +157,10 @@ constexpr int kKeyAttemptShift = 30;
 constexpr uint32_t kEvBpItem = kEvCliKinds, kEvBpTimeout = kEvCliKinds + 1, kEvBpCont = kEvCliKinds + 2, kEvCvItem = kEvCliKinds + 3,
                    kEvCvCont = kEvCliKinds + 4, kEvGtItem = kEvCliKinds + 5, kEvGtOpen = kEvCliKinds + 6, kEvGtClose = kEvCliKinds + 7,
                    kEvFlowKinds = kEvCliKinds + HS_FLOW_KINDS;
+// AutoScaler (components/deployment/auto_scaler.py:321-357): its `_autoscaler_evaluate` Event, one more internal kind, a daemon aimed at
+// the scaler itself, no Request.  It counts in events_processed and per graph (GVars::as_evals).
+constexpr uint32_t kEvAsEval = kEvFlowKinds, kEvAsKinds = kEvFlowKinds + 1;
+constexpr int kMaxScalerSteps = HS_AUTOSCALER_MAX_STEPS;
 constexpr int kMaxFlowItems = HS_FLOW_MAX_ITEMS;             // batch_size / a bounded gate queue: a batch's length rides in 30 bits of GEvent::pad
 constexpr uint32_t kPadPre = 1u, kPadCancelled = 2u;
 constexpr int kPadIdShift = 2;                 // a check id in GEvent::pad (its low 30 bits: only the one pending id of a backend and ids
@@ -178,6 +182,9 @@ static_assert(kEvCliKinds <= 32, "kDropKinds is one word");
 constexpr uint64_t kDropKindsFlow = (uint64_t)kDropKindsCli | (1ull << kEvBpItem) | (1ull << kEvBpTimeout) | (1ull << kEvCvItem) |
                                     (1ull << kEvGtItem) | (1ull << kEvGtOpen) | (1ull << kEvGtClose);
 static_assert(kEvFlowKinds <= 64, "kDropKindsFlow is two words; s_by_kind is zeroed by one lane per kind");
+// ... and a scaler's evaluation, tested by the one instantiation that dispatches it
+constexpr uint64_t kDropKindsAs = kDropKindsFlow | (1ull << kEvAsEval);
+static_assert(kEvAsKinds <= 64, "kDropKindsAs is two words; s_by_kind is zeroed by one lane per kind");
 constexpr int kMaxBulkheadConcurrent = HS_BULKHEAD_MAX_CONCURRENT;         // Bulkhead.max_concurrent the in-flight table is sized for (include/hs_engine.h)
 constexpr int kDefaultTimeoutTable = 256;                // ids a TimeoutWrapper's (keys a Client's) table holds before it first grows
 constexpr int kMaxClientAttempts = HS_CLIENT_MAX_ATTEMPTS;   // the attempt of a key is 16 bits and one
@@ -211,10 +218,31 @@ struct GQueue {                                // 112 bytes
     int32_t flag, kind;                        // AdaptiveLIFO: _was_congested; CoDel: _dropping
 };
 constexpr int64_t kQueueNone = INT64_MIN;
+// An AutoScaler's policy and what its GState row has no room for, one row per scaler in HBM (GVars::as; GParam::stream_base = its row).
+// GParam of a scaler: mean = evaluation_interval, lat_min = scale_out_cooldown, loss = scale_in_cooldown (seconds), conc = min_instances,
+// lim = max_instances, target = its LoadBalancer, sub = _is_running, rt_off = the slot of instance 1 among the LoadBalancer's targets
+// (= its initial backends), rt_cnt = the pool's size P.  GState: a = evaluations, b = scale_out_count, c = scale_in_count,
+// d = cooldown_blocks.
+struct GAs {
+    double target;                             // TargetUtilization._target
+    double thr_out, thr_in;                    // QueueDepthScaling's two thresholds
+    double step_thr[kMaxScalerSteps];          // StepScaling._steps as the host sorted them
+    int32_t step_adj[kMaxScalerSteps];
+    int32_t n_steps, policy;                   // hs_autoscaler_policy
+    int64_t *hist; long long hist_cap, hist_len;   // scaling_history: (time ns, action + 4 x the instances it counted, from_count, to_count) per record
+    int64_t last_time;                         // _last_scale_time (last_action != 0)
+    int32_t last_action;                       // _last_scale_action: 0 None, 1 "scale_out", 2 "scale_in"
+    int32_t next_id;                           // _next_instance_id
+    int64_t added, removed;                    // instances_added / instances_removed
+    int32_t wanted;                            // the instance id beyond the pool a scale-out asked for (kPoolOut; 0: none)
+    int32_t pad;
+};
+constexpr int kAsOut = 1, kAsIn = 2;
 constexpr int kLimPollScheduled = 1, kLimHasTime = 2;   // GState::active of a limiter: _poll_scheduled; _last_*_time / _current_window_start is set
 constexpr long long kMaxSlidingLog = 1ll << 20;          // SlidingWindowPolicy.max_requests the ring is sized for
 
-enum : int { kRunning = 0, kDone = 1, kGrowHeap = 2, kGrowReq = 4, kGrowRec = 8, kBadKind = 16, kGrowTicks = 32, kUndecided = 64, kGrowTab = 128 };
+enum : int { kRunning = 0, kDone = 1, kGrowHeap = 2, kGrowReq = 4, kGrowRec = 8, kBadKind = 16, kGrowTicks = 32, kUndecided = 64, kGrowTab = 128,
+             kGrowHist = 256, kPoolOut = 512 };
 
 struct GVars {                                 // device scalars
     long long heap_len;
@@ -242,6 +270,9 @@ struct GVars {                                 // device scalars
     long long flow_cancelled;                  // cancelled `_BatchTimeout` Events popped
     GQueue *qp;                                // the rows of the Servers with a queue policy (hs_graph_set_queue_policy; null: none)
     long long n_link_faults;                   // entries of `faults` that are link faults (hs_graph_add_link_fault)
+    GAs *as;                                   // the rows of the AutoScalers (hs_graph_set_auto_scaler; null: none)
+    uint8_t *as_mem;                           // [n_rt] the membership word of every backend slot: the backend is in LoadBalancer._backends
+    long long as_evals;                        // the scalers' `_autoscaler_evaluate` Events (hs_graph_get_auto_scaler)
 };
 
 struct GCtl {                                  // kernel argument
@@ -621,7 +652,9 @@ __device__ inline bool tab_remove(int64_t *tab, int live, int64_t id) {
 // FL: ... has a BatchProcessor, a ConveyorBelt or a GateController -- a sixth, for the same reason.  FL implies CL.
 // Q: ... has a Server with a LIFOQueue, an AdaptiveLIFO or a CoDelQueue -- a seventh, for the same reason.  Q implies FL.
 // LF: ... has a link fault (InjectLatency / InjectPacketLoss) -- an eighth, for the same reason.  LF implies Q.
-template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false, bool Q = false, bool LF = false>
+// AS: ... has an AutoScaler -- a ninth, for the same reason.  AS implies LF.
+template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false, bool Q = false, bool LF = false,
+          bool AS = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     static_assert(F || !HC, "the health instantiation carries the fault code");
     static_assert(HC || !R, "the resilience instantiation carries the fault and health code");
@@ -629,9 +662,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
     static_assert(CL || !FL, "the flow instantiation carries the fault, health, resilience and client code");
     static_assert(FL || !Q, "the queue-policy instantiation carries the fault, health, resilience, client and flow code");
     static_assert(Q || !LF, "the link-fault instantiation carries the code of all the others");
-    constexpr uint32_t kKinds = FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
+    static_assert(LF || !AS, "the scaler instantiation carries the code of all the others");
+    constexpr uint32_t kKinds = AS ? kEvAsKinds : FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
     // (one word for the instantiations whose kinds fit in it, two for the flow instantiation's 39)
-    constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
+    constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = AS ? kDropKindsAs : FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
     constexpr int kPushes = R ? 3 : 2;         // heap entries one event constructs at most (R: a limiter's forward or poll + the hook's response)
     __shared__ unsigned long long s_by_kind[kKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
@@ -738,6 +772,16 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     continue;
                 }
             }
+            if constexpr (AS) {
+                // AutoScaler.start() (auto_scaler.py:302-315): the first `_autoscaler_evaluate` Event, a daemon, no Request
+                const int an = c.sched_node[V.sched_done];
+                if (c.P[an].kind == HS_NODE_AUTO_SCALER) {
+                    H.push(mk_pre(c.sched_t[V.sched_done], V.global_counter++, kEvAsEval, an, -1));
+                    polls_pending += 1;
+                    V.sched_done++;
+                    continue;
+                }
+            }
             int r = req_free;
             if (r >= 0) req_free = c.reqs[r].next;
             else if (req_len < c.req_cap) r = req_len++;
@@ -804,6 +848,13 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 else if (top.kind == kEvGtOpen) items = c.S[top.node].qlen;
                 if (H.len + items + kPushes > c.heap_cap) { status |= kGrowHeap; break; }
             }
+            if constexpr (AS) {
+                const GEvent top = H.get(0);                                       // an evaluation may append one record to its scaling history
+                if (top.kind == kEvAsEval && top.t >= cur) {
+                    const GAs &row = V.as[c.P[top.node].stream_base];
+                    if (row.hist_len >= row.hist_cap) { status |= kGrowHist; break; }
+                }
+            }
             if (c.coop_min > 0 && sel < 0) {                                       // (a graph without such a LoadBalancer: one uniform test)
                 const GEvent top = H.get(0);
                 if (top.kind == HS_EV_LB && top.t >= cur) {
@@ -844,6 +895,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     if (c.part == 2) break;
                     continue;
                 }
+            }
+            if constexpr (AS) {
+                if (e.kind == kEvAsEval) polls_pending -= 1;                       // a daemon leaves the heap
             }
             if (e.t < cur) continue;                                              // time-travel drop, core/simulation.py:480-489
             cur = e.t;
@@ -929,6 +983,111 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         s.c += 1;
                         if (healthy && h.fail >= p.lim) { lb_mark(c, p.target, q, false); s.active += 1; }
                     }
+                    continue;
+                }
+            }
+            if constexpr (AS) {
+                if (e.kind == kEvAsEval) {
+                    // AutoScaler._evaluate (auto_scaler.py:326-357).  `all_backends` is the LoadBalancer's member list (its initial
+                    // backends, then the live managed instances in id order: hl_list, GState::qlen of them -- under a scaler every
+                    // member is healthy).
+                    if (!p.sub) continue;                                           // `if not self._is_running: return []`
+                    s.a += 1;
+                    GAs &row = V.as[p.stream_base];
+                    const GParam &lp = c.P[p.target];
+                    GState &ls = c.S[p.target];
+                    int32_t *hl = c.hl_list + lp.rt_off;
+                    const int current = ls.qlen;
+                    const long long lo = p.conc, hi = p.lim;
+                    long long desired = current;
+                    if (row.policy == HS_AUTOSCALER_QUEUE_DEPTH) {
+                        // QueueDepthScaling.evaluate (:149-168): an integer sum
+                        long long total = 0;
+                        for (int q = 0; q < current; ++q) total += c.S[c.rt_targets[lp.rt_off + hl[q]]].qlen;
+                        if ((double)total >= row.thr_out) desired = current + 1;
+                        else if ((double)total <= row.thr_in && current > lo) desired = current - 1;
+                        desired = desired < hi ? desired : hi;
+                        desired = desired > lo ? desired : lo;
+                    } else if (current == 0) {
+                        if (row.policy == HS_AUTOSCALER_TARGET_UTILIZATION) desired = lo;   // `if not backends: return min_instances` (:81-82)
+                    } else {
+                        // sum(utilizations) / len(utilizations) (:90,132): the interpreter's plain left-to-right sum in list order, every
+                        // utilization active / limit (a true division of two ints)
+                        double sum = 0.0;
+                        for (int q = 0; q < current; ++q) {
+                            const int be = c.rt_targets[lp.rt_off + hl[q]];
+                            sum = __dadd_rn(sum, __ddiv_rn((double)c.S[be].active, (double)c.P[be].conc));
+                        }
+                        const double avg = __ddiv_rn(sum, (double)current);
+                        bool decided = true;
+                        if (row.policy == HS_AUTOSCALER_TARGET_UTILIZATION) {
+                            // int(current_count * avg_util / target + 0.5) (:94): three roundings, none fused
+                            desired = (long long)__dadd_rn(__ddiv_rn(__dmul_rn((double)current, avg), row.target), 0.5);
+                        } else {
+                            decided = false;                                        // StepScaling.evaluate (:134-139)
+                            for (int k = 0; k < row.n_steps; ++k)
+                                if (avg >= row.step_thr[k]) { desired = (long long)current + row.step_adj[k]; decided = true; break; }
+                        }
+                        if (decided) {
+                            desired = desired < hi ? desired : hi;
+                            desired = desired > lo ? desired : lo;
+                        }
+                    }
+                    // _in_cooldown (:359-367): (now - _last_scale_time).to_seconds() against the action's cooldown
+                    const double elapsed = row.last_action ? seconds_from_ns(t - row.last_time) : 0.0;
+                    if (desired > current) {
+                        // _try_scale_out (:369-414)
+                        if (row.last_action && elapsed < p.lat_min) s.d += 1;
+                        else {
+                            long long to_add = desired - current;
+                            if (hi - current < to_add) to_add = hi - current;
+                            if (to_add > 0) {
+                                if ((long long)row.next_id + to_add > (long long)p.rt_cnt) {    // the host's bound on the pool did not hold
+                                    row.wanted = row.next_id + 1;
+                                    status |= kPoolOut;
+                                    break;
+                                }
+                                for (long long k = 0; k < to_add; ++k) {
+                                    // `add_backend(new_server)` at weight 1 (set_weight: the slot's weight is 1 already), behind every
+                                    // member: pool slots ascend with the ids
+                                    row.next_id += 1;
+                                    const int slot = p.rt_off + row.next_id - 1;
+                                    V.as_mem[lp.rt_off + slot] = 1;
+                                    hl[ls.qlen] = slot;
+                                    ls.qlen += 1;
+                                }
+                                row.last_time = t; row.last_action = kAsOut;
+                                s.b += 1;
+                                row.added += to_add;
+                                int64_t *h = row.hist + 4 * row.hist_len;
+                                h[0] = t; h[1] = kAsOut + 4 * to_add; h[2] = current; h[3] = ls.qlen;
+                                row.hist_len += 1;
+                            }
+                        }
+                    } else if (desired < current) {
+                        // _try_scale_in (:416-455): the newest managed instances leave; with none managed the action still counts
+                        if (row.last_action && elapsed < p.loss) s.d += 1;
+                        else {
+                            long long to_remove = current - desired;
+                            if (current - lo < to_remove) to_remove = current - lo;
+                            if (to_remove > 0) {
+                                for (long long k = 0; k < to_remove; ++k) {
+                                    if (ls.qlen > 0 && hl[ls.qlen - 1] >= p.rt_off) {   // `if self._managed_servers:` -- the list's last member
+                                        V.as_mem[lp.rt_off + hl[ls.qlen - 1]] = 0;
+                                        ls.qlen -= 1;
+                                    }
+                                }
+                                row.last_time = t; row.last_action = kAsIn;
+                                s.c += 1;
+                                row.removed += to_remove;
+                                int64_t *h = row.hist + 4 * row.hist_len;
+                                h[0] = t; h[1] = kAsIn + 4 * to_remove; h[2] = current; h[3] = ls.qlen;
+                                row.hist_len += 1;
+                            }
+                        }
+                    }
+                    H.push(mk(t + ns_from_seconds(p.mean), G++, kEvAsEval, n, -1));   // self.now + Duration.from_seconds(evaluation_interval)
+                    polls_pending += 1;
                     continue;
                 }
             }
@@ -1580,6 +1739,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     default: break;
                     }
                 }
+                if constexpr (AS) {                                                 // AutoScaler.current_count: len(load_balancer.all_backends)
+                    if (p.sub == HS_PROBE_AS_CURRENT_COUNT) v = c.S[c.P[p.target].target].qlen;
+                }
                 if constexpr (FL) {                                                 // (the flow entities' metrics likewise)
                     if (p.sub == HS_PROBE_BP_BUFFER_DEPTH || p.sub == HS_PROBE_GT_QUEUE_DEPTH) v = tg.qlen;   // buffer_depth / queue_depth
                     else if (p.sub == HS_PROBE_CV_IN_TRANSIT) v = tg.active;        // ConveyorBelt.items_in_transit
@@ -1742,6 +1904,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             for (int k = 0; k < HS_FLOW_KINDS; ++k) V.flow_by_kind[k] += (long long)s_by_kind[kEvBpItem + k];
             V.flow_cancelled += n_flow_cancelled;
         }
+        if constexpr (AS) V.as_evals += (long long)s_by_kind[kEvAsEval];
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
@@ -1805,6 +1968,12 @@ __global__ void __launch_bounds__(64) hs_graph_run_link_faults(GCtl c) {      //
     __shared__ GEvent lheap[kLdsHeap];
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
     graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true>(c, lheap, lnodes);
+}
+
+__global__ void __launch_bounds__(64) hs_graph_run_scaler(GCtl c) {           // ... with an AutoScaler
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
 }
 
 // Independent graphs -- the replicas / sweep points of parallel/runner.py:82-142 -- side by side: one workgroup (one heap) each, one
@@ -1881,6 +2050,14 @@ __global__ void __launch_bounds__(64) hs_graph_run_batch_link_faults(const GCtl 
     graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true>(c, lheap, lnodes);
     batch_report(c, stat);
 }
+// ... of a batch in which at least one handle has an AutoScaler
+__global__ void __launch_bounds__(64) hs_graph_run_batch_scaler(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
 
 }  // namespace graph
 }  // namespace hs
@@ -1931,6 +2108,15 @@ struct hs_graph {
     std::vector<int32_t> sched_id;             // request_id per scheduled entry (0: none)
     int32_t *d_sched_id = nullptr;
     bool any_sched_id = false;
+    // AutoScaler: a graph that holds one runs the ninth instantiation; the rows, the membership words and the history buffers go to
+    // the device with the first run
+    int n_scalers = 0;
+    std::vector<GAs> as_rows;                  // hs_graph_set_auto_scaler, in call order (GParam::stream_base = the row)
+    std::vector<int32_t> as_node;              // the scaler node of every row
+    std::vector<int32_t> scaler_of;            // [n] the configured scaler of a LoadBalancer node (-1: none)
+    std::vector<uint8_t> as_member;            // [n_rt] the initial membership word of every backend slot (0: a dormant pool instance)
+    GAs *d_as = nullptr; uint8_t *d_as_mem = nullptr;
+    std::vector<int64_t *> d_as_hist;          // every row's history buffer
     int debug_flags = 0;                       // hs_debug_graph_flags
     // tick tables: one row per time-varying Source and per distinct Probe interval, computed up to `tick_horizon`
     std::vector<hs::TickRow> rows;
@@ -2012,8 +2198,9 @@ void hs_graph_destroy(hs_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *bufs[] = {g->ctl.heap, g->ctl.reqs, g->ctl.rec_node, g->ctl.rec_t, g->ctl.rec_cr, (void *)g->ctl.P, g->ctl.S,
                     g->d_rt_targets, g->d_key_table, (void *)g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
-                    g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health, g->ctl.rs_tab, g->d_cl_delays, g->d_sched_id, g->d_qp};
+                    g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health, g->d_as, g->d_as_mem, g->ctl.rs_tab, g->d_cl_delays, g->d_sched_id, g->d_qp};
     for (void *b : bufs) if (b && !in_slab(g, b)) (void)hipFree(b);
+    for (int64_t *h : g->d_as_hist) if (h) (void)hipFree(h);
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
     if (g->ev_a) (void)hipEventDestroy(g->ev_a);
     if (g->ev_b) (void)hipEventDestroy(g->ev_b);
@@ -2110,7 +2297,8 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
                             : p.sub == HS_PROBE_CL_IN_FLIGHT ? tk == HS_NODE_CLIENT
                             : p.sub == HS_PROBE_BP_BUFFER_DEPTH ? tk == HS_NODE_BATCH_PROCESSOR
                             : p.sub == HS_PROBE_CV_IN_TRANSIT ? tk == HS_NODE_CONVEYOR
-                            : p.sub == HS_PROBE_GT_QUEUE_DEPTH ? tk == HS_NODE_GATE : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
+                            : p.sub == HS_PROBE_GT_QUEUE_DEPTH ? tk == HS_NODE_GATE
+                            : p.sub == HS_PROBE_AS_CURRENT_COUNT ? tk == HS_NODE_AUTO_SCALER : (p.sub <= HS_PROBE_COMPLETED && tk == HS_NODE_SERVER);
             if (!ok) return fail(nullptr, HS_E_UNSUPPORTED, "node %d: metric %d is not an attribute of its target (node kind %d)", i, (int)p.sub, tk);
             const double rate = 1.0 / iv;                           // _ProbeProfile.rate (probe.py:31)
             int found = -1;
@@ -2239,6 +2427,11 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a BatchProcessor, ConveyorBelt or GateController needs a downstream", i);
             p.conc = 0; p.lim = 0; p.sub = 0; p.stream_base = 0; p.rt_off = 0; p.rt_cnt = 0;
         } break;
+        case HS_NODE_AUTO_SCALER: {
+            // AutoScaler (auto_scaler.py:207-263); its LoadBalancer, policy and parameters: hs_graph_set_auto_scaler
+            if (p.target >= 0 && nd->kind[p.target] != HS_NODE_LB) return fail(nullptr, HS_E_INVALID, "node %d: an AutoScaler's target %d is not a LoadBalancer", i, p.target);
+            p.sub = 0; p.conc = 1; p.lim = 10; p.mean = 10.0; p.lat_min = 30.0; p.loss = 60.0; p.rt_off = 0; p.rt_cnt = 0; p.stream_base = 0;
+        } break;
         default: return fail(nullptr, HS_E_UNSUPPORTED, "node %d: kind %d is not lowered", i, (int)p.kind);
         }
         P[(size_t)i] = p;
@@ -2248,6 +2441,9 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     g->key_table = key_table; g->has_least_loaded = has_ll; g->has_wrr = has_wrr;
     g->hl_flag.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
     g->checker_of.assign((size_t)n, -1); g->checker_set.assign((size_t)n, 0);
+    g->scaler_of.assign((size_t)n, -1);
+    g->as_member.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
+    for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_AUTO_SCALER) g->n_scalers++;
     g->lb_w.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
     {
         hs_limiter_policy_params none{};
@@ -2535,6 +2731,9 @@ int hs_graph_set_health_checker(hs_graph *g, int32_t node, int32_t lb_node, doub
     if (g->checker_of[(size_t)lb_node] >= 0)
         return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has HealthChecker node %d already: one checker per LoadBalancer is lowered", lb_node,
                     g->checker_of[(size_t)lb_node]);
+    if (g->scaler_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has AutoScaler node %d: a HealthChecker and an AutoScaler on one LoadBalancer are not lowered", lb_node,
+                    g->scaler_of[(size_t)lb_node]);
     const uint8_t strat = g->params[(size_t)lb_node].sub;
     if (strat == HS_LB_CONSISTENT_HASH || strat == HS_LB_IP_HASH || strat == HS_LB_RANDOM)
         return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: strategy %d is not lowered over a changing backend list (under a HealthChecker)", lb_node, (int)strat);
@@ -2920,6 +3119,96 @@ int hs_debug_codel_next(int32_t device, int64_t n, const int64_t *count, const d
     return HS_OK;
 }
 
+int hs_graph_set_auto_scaler(hs_graph *g, int32_t node, int32_t lb_node, int32_t policy, double p0, double p1, int32_t n_steps,
+                             const double *step_threshold, const int32_t *step_adjustment, int32_t min_instances, int32_t max_instances,
+                             double interval_s, double scale_out_cooldown_s, double scale_in_cooldown_s, int32_t n_pool, int32_t running) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_AUTO_SCALER)
+        return fail(g, HS_E_INVALID, "set_auto_scaler: node %d is not an AutoScaler", node);
+    if (lb_node < 0 || lb_node >= g->n || g->params[(size_t)lb_node].kind != HS_NODE_LB)
+        return fail(g, HS_E_INVALID, "set_auto_scaler: node %d is not a LoadBalancer", lb_node);
+    if (g->ran || g->launches > 0 || g->d_health || g->d_as) return fail(g, HS_E_STATE, "set_auto_scaler: a scaler is configured before the first run");
+    for (int32_t a : g->as_node) if (a == node) return fail(g, HS_E_STATE, "set_auto_scaler: node %d is configured already", node);
+    if (g->scaler_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has AutoScaler node %d already: one scaler per LoadBalancer is lowered", lb_node,
+                    g->scaler_of[(size_t)lb_node]);
+    if (g->checker_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has HealthChecker node %d: a HealthChecker and an AutoScaler on one LoadBalancer are not lowered",
+                    lb_node, g->checker_of[(size_t)lb_node]);
+    const GParam &lp = g->params[(size_t)lb_node];
+    if (lp.sub == HS_LB_CONSISTENT_HASH || lp.sub == HS_LB_IP_HASH || lp.sub == HS_LB_RANDOM)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: strategy %d is not lowered over a changing backend list (under an AutoScaler)", lb_node, (int)lp.sub);
+    if (policy < HS_AUTOSCALER_TARGET_UTILIZATION || policy > HS_AUTOSCALER_QUEUE_DEPTH) return fail(g, HS_E_UNSUPPORTED, "scaling policy %d is not lowered", policy);
+    if (policy == HS_AUTOSCALER_TARGET_UTILIZATION && !(p0 > 0.0 && p0 <= 1.0)) return fail(g, HS_E_INVALID, "target must be in (0, 1], got %g", p0);
+    if (policy == HS_AUTOSCALER_STEP) {
+        if (n_steps < 0 || n_steps > kMaxScalerSteps) return fail(g, HS_E_UNSUPPORTED, "StepScaling with %d steps: at most %d are lowered", n_steps, kMaxScalerSteps);
+        if (n_steps > 0 && (!step_threshold || !step_adjustment)) return fail(g, HS_E_INVALID, "set_auto_scaler: null steps");
+        for (int k = 0; k < n_steps; ++k) if (std::isnan(step_threshold[k])) return fail(g, HS_E_INVALID, "set_auto_scaler: step %d has no threshold", k);
+    }
+    if (n_pool < 0 || n_pool > HS_AUTOSCALER_MAX_POOL) return fail(g, HS_E_UNSUPPORTED, "a pool of %d instances is beyond the %d of one AutoScaler", n_pool, HS_AUTOSCALER_MAX_POOL);
+    if (n_pool > lp.rt_cnt) return fail(g, HS_E_INVALID, "set_auto_scaler: LoadBalancer node %d has %d targets, fewer than the pool's %d", lb_node, lp.rt_cnt, n_pool);
+    if (!std::isfinite(interval_s) || !(interval_s * 1e9 >= 1.0))
+        return fail(g, HS_E_UNSUPPORTED, "an evaluation_interval of %g s is below one nanosecond or not finite (the evaluation would never advance)", interval_s);
+    if (std::isnan(scale_out_cooldown_s) || std::isnan(scale_in_cooldown_s)) return fail(g, HS_E_INVALID, "set_auto_scaler: a cooldown is not a number");
+    for (int q = 0; q < lp.rt_cnt - n_pool; ++q)
+        if (!g->hl_flag[(size_t)lp.rt_off + (size_t)q])
+            return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: backend %d is marked unhealthy under an AutoScaler (not lowered)", lb_node, q);
+    GAs row{};
+    row.policy = policy;
+    row.target = policy == HS_AUTOSCALER_TARGET_UTILIZATION ? p0 : 0.7;
+    row.thr_out = p0; row.thr_in = p1;
+    row.n_steps = policy == HS_AUTOSCALER_STEP ? n_steps : 0;
+    for (int k = 0; k < row.n_steps; ++k) { row.step_thr[k] = step_threshold[k]; row.step_adj[k] = step_adjustment[k]; }
+    GParam &p = g->params[(size_t)node];
+    p.target = lb_node; p.mean = interval_s; p.lat_min = scale_out_cooldown_s; p.loss = scale_in_cooldown_s; p.conc = min_instances;
+    p.lim = max_instances; p.sub = running ? 1 : 0; p.rt_off = lp.rt_cnt - n_pool; p.rt_cnt = n_pool; p.stream_base = (uint64_t)g->as_rows.size();
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    for (int q = lp.rt_cnt - n_pool; q < lp.rt_cnt; ++q) g->as_member[(size_t)lp.rt_off + (size_t)q] = 0;
+    g->as_rows.push_back(row); g->as_node.push_back(node);
+    g->scaler_of[(size_t)lb_node] = node;
+    g->reach_s = std::max(g->reach_s, interval_s);
+    g->health = true;                          // (the member list is the healthy list of the health lowering)
+    return HS_OK;
+}
+
+int hs_graph_get_auto_scaler(hs_graph *g, int32_t node, int64_t *state, int64_t *history, int64_t history_cap, uint8_t *member, int64_t *events) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (events) {
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        *events = v.as_evals;
+    }
+    if (node == -1 && !state && !history && !member) return HS_OK;
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_AUTO_SCALER)
+        return fail(g, HS_E_INVALID, "get_auto_scaler: node %d is not an AutoScaler", node);
+    const GParam &np = g->params[(size_t)node];
+    size_t r = 0;
+    while (r < g->as_node.size() && g->as_node[r] != node) ++r;
+    if (r == g->as_node.size()) return fail(g, HS_E_STATE, "get_auto_scaler: AutoScaler node %d was never configured", node);
+    const GParam &lp = g->params[(size_t)np.target];
+    GAs row = g->as_rows[r];
+    GState cs{}, ls{};
+    if (g->d_as) {
+        HS_HIP(g, hipMemcpy(&row, g->d_as + r, sizeof row, hipMemcpyDeviceToHost));
+        HS_HIP(g, hipMemcpy(&cs, g->ctl.S + node, sizeof cs, hipMemcpyDeviceToHost));
+        HS_HIP(g, hipMemcpy(&ls, g->ctl.S + np.target, sizeof ls, hipMemcpyDeviceToHost));
+    } else ls.qlen = lp.rt_cnt - np.rt_cnt;
+    if (state) {
+        state[0] = cs.a; state[1] = cs.b; state[2] = cs.c; state[3] = row.added; state[4] = row.removed; state[5] = cs.d;
+        state[6] = row.next_id; state[7] = row.last_action; state[8] = row.last_action ? row.last_time : -1; state[9] = row.hist_len;
+        state[10] = ls.qlen; state[11] = 0;
+    }
+    if (history && history_cap > 0 && row.hist_len > 0 && g->d_as)
+        HS_HIP(g, hipMemcpy(history, row.hist, 4 * (size_t)std::min<long long>(row.hist_len, history_cap) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (member && lp.rt_cnt > 0) {
+        if (g->d_as_mem) HS_HIP(g, hipMemcpy(member, g->d_as_mem + lp.rt_off, (size_t)lp.rt_cnt, hipMemcpyDeviceToHost));
+        else std::copy(g->as_member.begin() + lp.rt_off, g->as_member.begin() + lp.rt_off + lp.rt_cnt, member);
+    }
+    return HS_OK;
+}
+
 int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, int32_t cancelled) {
     if (!g) return fail(g, HS_E_INVALID, "null handle");
     if (node < 0 || node >= g->n) return fail(g, HS_E_INVALID, "add_fault: node %d out of range", node);
@@ -3104,6 +3393,33 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         for (int i = 0; i < g->n; ++i)
             if (g->params[(size_t)i].kind == HS_NODE_HEALTH_CHECKER && !g->checker_set[(size_t)i])
                 return fail(g, HS_E_STATE, "node %d: a HealthChecker without its LoadBalancer (hs_graph_set_health_checker comes before the run)", i);
+    if (g->n_scalers > 0 && !g->d_as) {
+        // the scalers' rows, their history buffers and the membership words, once; the device finds them through GVars
+        if ((int)g->as_rows.size() != g->n_scalers)
+            return fail(g, HS_E_STATE, "an AutoScaler without its LoadBalancer (hs_graph_set_auto_scaler comes before the run)");
+        for (int i = 0; i < g->n; ++i) {
+            const GParam &p = g->params[(size_t)i];
+            if (p.kind != HS_NODE_LB || g->scaler_of[(size_t)i] < 0) continue;
+            for (int q = 0; q < p.rt_cnt; ++q)
+                if (!g->hl_flag[(size_t)p.rt_off + (size_t)q])
+                    return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: backend %d is marked unhealthy under an AutoScaler (not lowered)", i, q);
+        }
+        HS_HIP(g, hipSetDevice(g->cfg.device));
+        const long long cap0 = g->cfg.record_capacity > 0 && g->cfg.record_capacity < 64 ? g->cfg.record_capacity : 64;
+        for (GAs &row : g->as_rows) {
+            int64_t *h = nullptr;
+            HS_HIP(g, hipMalloc(&h, 4 * (size_t)cap0 * sizeof(int64_t)));
+            g->d_as_hist.push_back(h);
+            row.hist = h; row.hist_cap = cap0; row.hist_len = 0;
+        }
+        const size_t nrt = (size_t)(g->n_rt > 0 ? g->n_rt : 1);
+        HS_HIP(g, hipMalloc(&g->d_as, g->as_rows.size() * sizeof(GAs)));
+        HS_HIP(g, hipMemcpy(g->d_as, g->as_rows.data(), g->as_rows.size() * sizeof(GAs), hipMemcpyHostToDevice));
+        HS_HIP(g, hipMalloc(&g->d_as_mem, nrt));
+        HS_HIP(g, hipMemcpy(g->d_as_mem, g->as_member.data(), nrt, hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, as), &g->d_as, sizeof g->d_as, hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, as_mem), &g->d_as_mem, sizeof g->d_as_mem, hipMemcpyHostToDevice));
+    }
     if (g->health && !g->d_health) {
         // health state, once: flags, healthy lists, current weights and the checkers' per-backend state in one allocation; the
         // LoadBalancers' rows get their healthy count and their two mark counters
@@ -3120,7 +3436,7 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
             const GParam &p = g->params[(size_t)i];
             if (p.kind != HS_NODE_LB) continue;
             int nh = 0;
-            for (int q = 0; q < p.rt_cnt; ++q) if (g->hl_flag[(size_t)p.rt_off + (size_t)q]) list0[p.rt_off + nh++] = q;
+            for (int q = 0; q < p.rt_cnt; ++q) if (g->hl_flag[(size_t)p.rt_off + (size_t)q] && g->as_member[(size_t)p.rt_off + (size_t)q]) list0[p.rt_off + nh++] = q;
             GState s0{};
             s0.qhead = 0; s0.qtail = 0; s0.qlen = nh;
             HS_HIP(g, hipMemcpy(c.S + i, &s0, sizeof s0, hipMemcpyHostToDevice));
@@ -3284,6 +3600,31 @@ static int after_launch_with(hs_graph *g, int status, long long processed, bool 
         const int rc = grow_tables(g);
         if (rc) return rc;
     }
+    if (v.status & kPoolOut) {
+        std::vector<GAs> rows(g->as_rows.size());
+        HS_HIP(g, hipMemcpy(rows.data(), g->d_as, rows.size() * sizeof(GAs), hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < rows.size(); ++r)
+            if (rows[r].wanted)
+                return fail(g, HS_E_OVERFLOW, "AutoScaler node %d needs instance %d, beyond its pool of %d instances (the pool's bound did not hold)",
+                            g->as_node[r], rows[r].wanted, g->params[(size_t)g->as_node[r]].rt_cnt);
+        return fail(g, HS_E_OVERFLOW, "an AutoScaler needs an instance beyond its pool");
+    }
+    if (v.status & kGrowHist) {
+        // a scaling history was full: every full one gets twice the records
+        std::vector<GAs> rows(g->as_rows.size());
+        HS_HIP(g, hipMemcpy(rows.data(), g->d_as, rows.size() * sizeof(GAs), hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < rows.size(); ++r) {
+            if (rows[r].hist_len < rows[r].hist_cap) continue;
+            const long long nc = rows[r].hist_cap * 2;
+            int64_t *h = nullptr;
+            HS_HIP(g, hipMalloc(&h, 4 * (size_t)nc * sizeof(int64_t)));
+            HS_HIP(g, hipMemcpy(h, rows[r].hist, 4 * (size_t)rows[r].hist_len * sizeof(int64_t), hipMemcpyDeviceToDevice));
+            HS_HIP(g, hipFree(rows[r].hist));
+            g->d_as_hist[r] = h;
+            rows[r].hist = h; rows[r].hist_cap = nc;
+            HS_HIP(g, hipMemcpy(g->d_as + r, &rows[r], sizeof(GAs), hipMemcpyHostToDevice));
+        }
+    }
     if (v.status & kUndecided) { g->undecided = true; *done = true; return HS_OK; }
     *done = v.status == kDone;
     return HS_OK;
@@ -3301,7 +3642,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, g->ctl);
@@ -3360,7 +3702,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
         for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; any_clients |= gs[i]->n_clients > 0; any_flows |= gs[i]->n_flows > 0; any_queues |= !gs[i]->qpol.empty(); }
         bool any_link_faults = false;
         for (int i : pending) any_link_faults |= gs[i]->n_link_faults > 0;
-        if (any_link_faults) hipLaunchKernelGGL(hs_graph_run_batch_link_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_scalers = false;
+        for (int i : pending) any_scalers |= gs[i]->n_scalers > 0;
+        if (any_scalers) hipLaunchKernelGGL(hs_graph_run_batch_scaler, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else if (any_link_faults) hipLaunchKernelGGL(hs_graph_run_batch_link_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_queues) hipLaunchKernelGGL(hs_graph_run_batch_queues, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_flows) hipLaunchKernelGGL(hs_graph_run_batch_flow, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_clients) hipLaunchKernelGGL(hs_graph_run_batch_client, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
@@ -3434,7 +3779,8 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count; one.rs_tab = g->ctl.rs_tab;
-        if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, one);
+        if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, one);
+        else if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, one);
         else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, one);

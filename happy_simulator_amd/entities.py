@@ -2102,6 +2102,190 @@ class GateController(Entity):
         return []
 
 
+# ---- auto scaling --------------------------------------------------------------------------------
+# components/deployment/auto_scaler.py.  Inside a Simulation the policies are evaluated on the device (csrc/hs_graph.hip kEvAsEval);
+# `evaluate` here is the reference's expression over host objects, for a policy used on its own.
+class TargetUtilization:
+    """auto_scaler.py:58-98: scale to keep the backends' average utilization near `target`."""
+
+    def __init__(self, target: float = 0.7):
+        if not 0 < target <= 1.0:
+            raise ValueError(f"target must be in (0, 1], got {target}")
+        self._target = target
+
+    @property
+    def target(self) -> float:
+        return self._target
+
+    def evaluate(self, backends: list, current_count: int, min_instances: int, max_instances: int) -> int:
+        if not backends:
+            return min_instances
+        utilizations = [b.utilization for b in backends if hasattr(b, "utilization")]
+        if not utilizations:
+            return current_count
+        avg_util = sum(utilizations) / len(utilizations)
+        if self._target > 0:
+            desired = int(current_count * avg_util / self._target + 0.5)
+        else:
+            desired = current_count
+        return max(min_instances, min(max_instances, desired))
+
+
+class StepScaling:
+    """auto_scaler.py:101-139: (utilization threshold, adjustment) steps, evaluated from the highest threshold down."""
+
+    def __init__(self, steps: list):
+        self._steps = sorted(steps, key=lambda s: s[0], reverse=True)
+
+    def evaluate(self, backends: list, current_count: int, min_instances: int, max_instances: int) -> int:
+        if not backends:
+            return current_count
+        utilizations = [b.utilization for b in backends if hasattr(b, "utilization")]
+        if not utilizations:
+            return current_count
+        avg_util = sum(utilizations) / len(utilizations)
+        for threshold, adjustment in self._steps:
+            if avg_util >= threshold:
+                desired = current_count + adjustment
+                return max(min_instances, min(max_instances, desired))
+        return current_count
+
+
+class QueueDepthScaling:
+    """auto_scaler.py:142-168: one instance more or fewer by the backends' total queue depth."""
+
+    def __init__(self, scale_out_threshold: int = 100, scale_in_threshold: int = 10):
+        self._scale_out_threshold = scale_out_threshold
+        self._scale_in_threshold = scale_in_threshold
+
+    def evaluate(self, backends: list, current_count: int, min_instances: int, max_instances: int) -> int:
+        total_depth = 0
+        for b in backends:
+            if hasattr(b, "depth"):
+                total_depth += b.depth
+        if total_depth >= self._scale_out_threshold:
+            desired = current_count + 1
+        elif total_depth <= self._scale_in_threshold and current_count > min_instances:
+            desired = current_count - 1
+        else:
+            desired = current_count
+        return max(min_instances, min(max_instances, desired))
+
+
+SCALING_POLICIES = (TargetUtilization, StepScaling, QueueDepthScaling)
+
+
+@dataclass
+class ScalingEvent:
+    """auto_scaler.py:171-179."""
+
+    time: Instant
+    action: str
+    from_count: int
+    to_count: int
+    reason: str
+
+
+@dataclass(frozen=True)
+class AutoScalerStats:
+    """auto_scaler.py:182-191."""
+
+    evaluations: int = 0
+    scale_out_count: int = 0
+    scale_in_count: int = 0
+    instances_added: int = 0
+    instances_removed: int = 0
+    cooldown_blocks: int = 0
+
+
+class AutoScaler(Entity):
+    """Periodic controller that adds backends to a LoadBalancer and removes them again (components/deployment/auto_scaler.py:194-455).
+    Every `evaluation_interval` seconds the policy reads the backends' utilization or queue depth; a scale-out calls `server_factory`
+    for instances `{name}_server_{k}`, a scale-in removes the newest managed ones, and a cooldown follows either.  The handler runs on
+    the device (csrc/hs_graph.hip kEvAsEval).  The device cannot call the factory, so the Simulation calls it up front, when it
+    lowers the graph, for a pool of P instances -- a bound on what the run can create -- and lowers them as dormant
+    Servers; this class carries the parameters in and the statistics, history and membership back out."""
+
+    MAX_POOL = 4096                  # include/hs_engine.h HS_AUTOSCALER_MAX_POOL
+    MAX_STEPS = 16                   # HS_AUTOSCALER_MAX_STEPS
+
+    def __init__(self, name: str, load_balancer: LoadBalancer, server_factory, policy=None, min_instances: int = 1, max_instances: int = 10,
+                 evaluation_interval: float = 10.0, scale_out_cooldown: float = 30.0, scale_in_cooldown: float = 60.0):
+        super().__init__(name)
+        self._load_balancer = load_balancer
+        self._server_factory = server_factory
+        self._policy = policy or TargetUtilization()
+        self._min_instances = min_instances
+        self._max_instances = max_instances
+        self._evaluation_interval = evaluation_interval
+        self._scale_out_cooldown = scale_out_cooldown
+        self._scale_in_cooldown = scale_in_cooldown
+        self._is_running = False
+        self._last_scale_time: Instant | None = None
+        self._last_scale_action: str | None = None
+        self._next_instance_id = 0
+        self._managed_servers: list[Entity] = []
+        self._evaluations = 0
+        self._scale_out_count = 0
+        self._scale_in_count = 0
+        self._instances_added = 0
+        self._instances_removed = 0
+        self._cooldown_blocks = 0
+        self.scaling_history: list[ScalingEvent] = []
+        self._sim_start: Instant | None = None           # the clock a Simulation hands to its entities: `now` before run() is its start
+        self._pool: list[Entity] = []                    # the factory's results for instances 1 .. len(_pool), made when a graph is lowered
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._load_balancer] + list(self._managed_servers)
+
+    @property
+    def stats(self) -> AutoScalerStats:
+        return AutoScalerStats(self._evaluations, self._scale_out_count, self._scale_in_count, self._instances_added,
+                               self._instances_removed, self._cooldown_blocks)
+
+    @property
+    def load_balancer(self) -> LoadBalancer:
+        return self._load_balancer
+
+    @property
+    def policy(self):
+        return self._policy
+
+    @property
+    def min_instances(self) -> int:
+        return self._min_instances
+
+    @property
+    def max_instances(self) -> int:
+        return self._max_instances
+
+    @property
+    def current_count(self) -> int:
+        return len(self._load_balancer.all_backends)
+
+    @property
+    def is_running(self) -> bool:
+        return self._is_running
+
+    def start(self):
+        """auto_scaler.py:302-315: the first `_autoscaler_evaluate` Event, a daemon, for `sim.schedule(...)`; its time is the
+        Simulation's start once the scaler is one of its entities, Instant.Epoch before."""
+        from .core.event import Event
+
+        self._is_running = True
+        return Event(time=self._sim_start if self._sim_start is not None else Instant.Epoch, event_type="_autoscaler_evaluate",
+                     target=self, daemon=True, context={})
+
+    def stop(self) -> None:
+        self._is_running = False
+
+    def _instance(self, k: int) -> Entity:
+        """Instance k of the pool (1-based), from the factory the first time it is asked for."""
+        while len(self._pool) < k:
+            self._pool.append(self._server_factory(f"{self.name}_server_{len(self._pool) + 1}"))
+        return self._pool[k - 1]
+
+
 # ---- probes --------------------------------------------------------------------------------------
 class Data:
     """Time-series container of a Probe (instrumentation/data.py:20-110): `values` = [(time_s, value), ...]."""
@@ -2176,9 +2360,9 @@ class Probe(Entity):
 
     _LOWERED = {"depth", "active_requests", "utilization", "available_capacity", "has_capacity", "stats_accepted", "stats_dropped",
                 "requests_completed", "_requests_completed", "events_received", "generated_count", "_generated_count", "queue_depth",
-                "active_count", "available_permits", "in_flight_count", "buffer_depth", "items_in_transit"}
+                "active_count", "available_permits", "in_flight_count", "buffer_depth", "items_in_transit", "current_count"}
     _ON_WRAPPER = {"active_count": Bulkhead, "available_permits": Bulkhead, "in_flight_count": (TimeoutWrapper, Client),
-                   "buffer_depth": BatchProcessor, "items_in_transit": ConveyorBelt}
+                   "buffer_depth": BatchProcessor, "items_in_transit": ConveyorBelt, "current_count": AutoScaler}
     # Server attributes that are functions of `active_requests` and the (fixed) concurrency: the engine samples the integer,
     # the Data container applies the reference's expression (components/server/server.py:153-173,191-200, concurrency.py:117-131)
     _ON_ACTIVE = ("utilization", "available_capacity", "has_capacity")

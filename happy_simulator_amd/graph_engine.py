@@ -22,7 +22,9 @@ import numpy as np
 
 from . import _native as N
 from .core.temporal import Duration, Instant
-from .entities import (AdaptiveLIFO, CoDelQueue, FIFOQueue, QUEUE_POLICIES, BatchProcessor, ConveyorBelt, GateController,
+from .entities import (AutoScaler, SCALING_POLICIES, ScalingEvent, StepScaling, TargetUtilization,
+                       BackendInfo,
+                       AdaptiveLIFO, CoDelQueue, FIFOQueue, QUEUE_POLICIES, BatchProcessor, ConveyorBelt, GateController,
                        BackendHealthState, Bulkhead, Client, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
                        ExponentialLatency, HealthChecker, IPHash, LIMITER_POLICIES, LatencyTracker, LeastConnections, LinearRampProfile, LoadBalancer, Network, NetworkLink, Probe, Random,
                        RandomRouter, RateLimitedEntity, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source,
@@ -95,6 +97,14 @@ class GraphArrays:
         self.qp_params = None                # [n, 5] float64: SERVER nodes with a LIFOQueue / AdaptiveLIFO / CoDelQueue -- hs_queue_policy
                                              #   (0: the FIFO), capacity (-1: unbounded), congestion_threshold, target_delay, interval;
                                              #   set through hs_graph_set_queue_policy
+        self.as_params = None                # [n, 10] float64: AUTO_SCALER nodes -- hs_autoscaler_policy, p0, p1, min_instances, max_instances,
+                                             #   evaluation_interval, scale_out_cooldown, scale_in_cooldown, the pool's size P, _is_running
+        self.as_steps = None                 #   ... and per node its StepScaling steps as [(threshold, adjustment), ...] (a list per node);
+                                             #   set through hs_graph_set_auto_scaler (their LoadBalancer: `target`)
+
+    @property
+    def has_scalers(self) -> bool:
+        return self.as_params is not None
 
     @property
     def has_queue_policies(self) -> bool:
@@ -191,6 +201,20 @@ class GraphEngine:
                     iv, to, ht, ut, running = arrays.hc_params[i]
                     self._check(self._lib.hs_graph_set_health_checker(self._h, int(i), int(arrays.target[i]), float(iv), float(to), int(ht), int(ut),
                                                                       int(running)))
+            except BaseException:
+                self.close()
+                raise
+
+        if arrays.has_scalers:
+            try:
+                for i in np.nonzero(arrays.kind == N.NODE_AUTO_SCALER)[0]:
+                    pol, p0, p1, lo, hi, iv, cd_out, cd_in, pool, running = arrays.as_params[i]
+                    steps = arrays.as_steps[i] or []
+                    thr = np.array([t for t, _ in steps] or [0.0], np.float64)
+                    adj = np.array([a for _, a in steps] or [0], np.int32)
+                    self._check(self._lib.hs_graph_set_auto_scaler(self._h, int(i), int(arrays.target[i]), int(pol), float(p0), float(p1), len(steps),
+                                                                   _ptr(thr), _ptr(adj), int(lo), int(hi), float(iv), float(cd_out), float(cd_in),
+                                                                   int(pool), int(running)))
             except BaseException:
                 self.close()
                 raise
@@ -303,6 +327,30 @@ class GraphEngine:
         events = np.zeros(6, np.int64)
         self._check(self._lib.hs_graph_get_wrapper(self._h, -1, None, None, 0, None, 0, _ptr(events)))
         return events
+
+    _SCALER_NAMES = ("evaluations", "scale_out_count", "scale_in_count", "instances_added", "instances_removed", "cooldown_blocks",
+                     "next_instance_id", "last_action", "last_time_ns", "history_len", "members")
+
+    def scaler(self, node: int) -> dict:
+        """hs_graph_get_auto_scaler of an AutoScaler node: its state by name, `history` as rows (time ns, action, from_count, to_count,
+        the instances the action counted) and `member`, the membership word of every target of its LoadBalancer."""
+        a = self.arrays
+        cnt = int(a.rt_cnt[int(a.target[node])])
+        st, member = np.zeros(N.AUTOSCALER_FIELDS, np.int64), np.zeros(max(cnt, 1), np.uint8)
+        self._check(self._lib.hs_graph_get_auto_scaler(self._h, int(node), _ptr(st), None, 0, _ptr(member), None))
+        hist = np.zeros((max(int(st[9]), 1), 4), np.int64)
+        self._check(self._lib.hs_graph_get_auto_scaler(self._h, int(node), None, _ptr(hist), int(st[9]), None, None))
+        hist = hist[:int(st[9])]
+        out = {k: int(v) for k, v in zip(self._SCALER_NAMES, st)}
+        out["history"] = np.concatenate([hist[:, :1], hist[:, 1:2] & 3, hist[:, 2:], hist[:, 1:2] >> 2], axis=1)
+        out["member"] = member[:cnt]
+        return out
+
+    def scaler_events(self) -> int:
+        """The graph's `_autoscaler_evaluate` Events of the run (hs_graph_get_auto_scaler, node = -1)."""
+        events = C.c_int64(0)
+        self._check(self._lib.hs_graph_get_auto_scaler(self._h, -1, None, None, 0, None, C.byref(events)))
+        return int(events.value)
 
     def health(self, node: int) -> dict:
         """hs_graph_get_health of a HealthChecker or LoadBalancer node: checker stats, per-backend states, the LoadBalancer's health
@@ -462,6 +510,11 @@ class GeneralGraph:
         self.nodes = nodes              # entity objects by node id
         self.arrays = arrays
         self.node_of = node_of          # id(entity) -> node id
+        self.scaled = {}                # LoadBalancer node -> (its AutoScaler's node, its initial backends, the pool's Servers)
+        self.pool_of = {}               # pool Server node -> (its AutoScaler's node, its instance id k)
+        self.n_own = len(nodes)         # the Simulation's own nodes; the scalers' pools stand behind them
+        self.scaler_starts = 1          # the start() Events per scaler the pools were sized for
+        self.rr_base = {}               # scaled LoadBalancer node -> its RoundRobin's `_index` when the graph was lowered
 
 
 def client_delay_table(policy, what: str) -> np.ndarray:
@@ -518,9 +571,38 @@ def flow_delay_ns(seconds, what: str, name: str) -> int:
     return ns
 
 
-def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
+def scaler_pool_size(scaler: "AutoScaler", n_initial: int, start_ns: int, end_ns: int, starts: int = 1) -> int:
+    """P: a bound on the instances `scaler` can create in a run from start_ns to end_ns ("AutoScaler").  Evaluations
+    happen at the instants start + j * interval; the run processes the ones up to its end and at most one Event beyond it:
+    I = (end - start) // interval + 2 instants.  A scale-out adds at most max_instances - current and only managed instances ever
+    leave, so current >= n_initial: a run of scale-outs without a scale-in between them adds at most A = max_instances - n_initial.
+    A new such run begins only behind a scale-in, which follows the last scale-out by the scale-in cooldown and is followed by the
+    next scale-out by the scale-out cooldown: with one action per instant the runs begin at least g_in + g_out instants apart (a
+    cooldown of c > 0 seconds keeps max(1, c // interval - 1) instants free, a cooldown <= 0 none -- but one chain of evaluations acts
+    once per instant).  R = 1 + (I - 1) // (g_in + g_out) runs, P = R * A.  Several start() Events with a cooldown <= 0 act several
+    times per instant: every evaluation may then begin a run, R = I * starts."""
+    iv_ns = Duration.from_seconds(scaler._evaluation_interval).nanoseconds
+    instants = max(0, end_ns - start_ns) // iv_ns + 2
+    most = scaler._max_instances - n_initial
+    if most <= 0:
+        return 0
+
+    def gap(cooldown):
+        return 0 if not cooldown > 0 else max(1, int(cooldown * 1e9) // iv_ns - 1)
+
+    g_out, g_in = gap(scaler._scale_out_cooldown), gap(scaler._scale_in_cooldown)
+    if starts <= 1 or (g_out > 0 and g_in > 0):
+        runs = 1 + (instants - 1) // (max(g_out, 1) + max(g_in, 1))
+    else:
+        runs = instants * starts
+    return int(runs * most)
+
+
+def lower_general(sources: list, entities: list, probes=None, *, start_ns: int = 0, end_ns: int | None = None,
+                  scaler_starts: int = 1) -> GeneralGraph:
     """`sources` / `entities` of a Simulation -> the node arrays of the single-heap engine.  Refuses by name what that engine
-    does not run either (lowering.UnsupportedTopology)."""
+    does not run either (lowering.UnsupportedTopology).  `start_ns` / `end_ns` (None: Infinity) / `scaler_starts` (the start() Events
+    scheduled per scaler) size the instance pools of the AutoScalers."""
     from .lowering import UnsupportedTopology
 
     nodes: list = []
@@ -547,7 +629,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
         add(pr)
     n_front = len(nodes)
     lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker, Bulkhead, TimeoutWrapper, Client,
-               BatchProcessor, ConveyorBelt, GateController) + _SINKS
+               BatchProcessor, ConveyorBelt, GateController, AutoScaler) + _SINKS
 
     def check(ent, where):
         if isinstance(ent, Source):
@@ -562,6 +644,8 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
                                       "(not lowered)")
         if isinstance(ent, HealthChecker) and where != "entities":
             raise UnsupportedTopology(f"{where}: the HealthChecker '{ent.name}' takes no Requests")
+        if isinstance(ent, AutoScaler) and where != "entities":
+            raise UnsupportedTopology(f"{where}: the AutoScaler '{ent.name}' takes no Requests")
         if not isinstance(ent, lowered):
             raise UnsupportedTopology(f"{where}: {type(ent).__name__} '{getattr(ent, 'name', ent)}' is not lowered to the engine")
 
@@ -582,7 +666,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
     while k < len(nodes):
         ent = nodes[k]
         k += 1
-        if isinstance(ent, (Probe, HealthChecker)):             # (a checker's LoadBalancer has to be part of the Simulation by itself)
+        if isinstance(ent, (Probe, HealthChecker, AutoScaler)):   # (a checker's / scaler's LoadBalancer has to be part of the Simulation by itself)
             continue
         for d in ent.downstream_entities():
             if d is None:
@@ -593,6 +677,68 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
                 raise UnsupportedTopology(f"'{ent.name}' forwards to server '{d.name}', which is not listed in `entities` of this "
                                           "Simulation (not part of this Simulation)")
             add(d)
+    # the AutoScalers' instance pools: the factory's results for instances 1 .. P, dormant Server nodes behind all of the Simulation's
+    # own nodes (node numbers keep their meaning), targets of their LoadBalancer behind its initial backends
+    n_own = len(nodes)
+    n_own_servers = sum(isinstance(x, Server) for x in nodes)
+    scaled: dict[int, tuple] = {}                             # id(LoadBalancer) -> (scaler, its initial backends, the pool)
+    pool_of: dict[int, tuple] = {}                            # pool node -> (scaler, k)
+    for sc in [x for x in nodes if isinstance(x, AutoScaler)]:
+        what = f"auto scaler '{sc.name}'"
+        lb = sc.load_balancer
+        if not isinstance(lb, LoadBalancer) or id(lb) not in node_of:
+            raise UnsupportedTopology(f"{what}: its LoadBalancer is not an entity of this Simulation")
+        if id(lb) in scaled:
+            raise UnsupportedTopology(f"{what}: LoadBalancer '{lb.name}' has the scaler '{scaled[id(lb)][0].name}' already (one AutoScaler "
+                                      "per LoadBalancer is lowered)")
+        if isinstance(lb.strategy, (ConsistentHash, IPHash, Random)):
+            raise UnsupportedTopology(f"{what}: strategy {type(lb.strategy).__name__} of '{lb.name}' is not lowered under an AutoScaler (its "
+                                      "selection over a changing backend list is a follow-up: RoundRobin, WeightedRoundRobin, "
+                                      "LeastConnections and WeightedLeastConnections are)")
+        pol = sc.policy
+        if type(pol) not in SCALING_POLICIES:
+            raise UnsupportedTopology(f"{what}: policy {type(pol).__name__} is not lowered to the engine (lowered: TargetUtilization, "
+                                      "StepScaling, QueueDepthScaling)")
+        if isinstance(pol, StepScaling) and len(pol._steps) > AutoScaler.MAX_STEPS:
+            raise UnsupportedTopology(f"{what}: StepScaling with {len(pol._steps)} steps is beyond the {AutoScaler.MAX_STEPS} the engine "
+                                      "holds (AutoScaler.MAX_STEPS)")
+        if lb.unhealthy_backends:
+            raise UnsupportedTopology(f"{what}: backend '{lb.unhealthy_backends[0].name}' of '{lb.name}' is marked unhealthy -- health marks "
+                                      "under an AutoScaler are not lowered (a follow-up)")
+        for v, nm in ((sc._min_instances, "min_instances"), (sc._max_instances, "max_instances")):
+            if type(v) is not int or not -(1 << 30) < v < (1 << 30):
+                raise UnsupportedTopology(f"{what}: {nm} must be an int below 2^30, got {v!r}")
+        try:
+            ok = np.isfinite(sc._evaluation_interval) and sc._evaluation_interval * 1e9 >= 1.0
+            float(sc._scale_out_cooldown), float(sc._scale_in_cooldown)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok or sc._scale_out_cooldown != sc._scale_out_cooldown or sc._scale_in_cooldown != sc._scale_in_cooldown:
+            raise UnsupportedTopology(f"{what}: evaluation_interval = {sc._evaluation_interval!r} (below one nanosecond or not finite) or "
+                                      "a cooldown that is no number is not lowered")
+        if end_ns is None:
+            raise UnsupportedTopology(f"{what}: end_time = Infinity leaves no horizon to size its instance pool by; pass end_time/duration")
+        initial = lb.all_backends
+        size = scaler_pool_size(sc, len(initial), start_ns, end_ns, scaler_starts)
+        if size > AutoScaler.MAX_POOL:
+            raise UnsupportedTopology(f"{what}: the run could create up to {size} instances, beyond the pool of {AutoScaler.MAX_POOL} "
+                                      "per scaler (AutoScaler.MAX_POOL): a longer interval or cooldown, or a shorter run")
+        pool = []
+        for k in range(1, size + 1):
+            inst = sc._instance(k)
+            if not isinstance(inst, Server):
+                raise UnsupportedTopology(f"{what}: server_factory returned a {type(inst).__name__} for instance {k}: only Servers may stand "
+                                          "as a LoadBalancer's backends")
+            if id(inst) in node_of:
+                raise UnsupportedTopology(f"{what}: server_factory returned '{inst.name}' for instance {k}, which is an entity of this "
+                                          "Simulation or another instance already (one new Server per call)")
+            d = inst.downstream
+            if d is not None and (id(d) not in node_of or node_of[id(d)] >= n_own):
+                raise UnsupportedTopology(f"{what}: the downstream '{getattr(d, 'name', d)}' of instance {k} is not an entity of this "
+                                          "Simulation")
+            pool_of[add(inst)] = (sc, k)
+            pool.append(inst)
+        scaled[id(lb)] = (sc, initial, pool)
     n = len(nodes)
     a = GraphArrays(n)
     counters = {Server: 0, NetworkLink: 0, RandomRouter: 0}
@@ -642,6 +788,17 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             on_wrapper = isinstance(tgt, (Bulkhead, TimeoutWrapper)) and m in N.PROBE_WRAPPER_METRICS
             on_client = isinstance(tgt, Client) and m in N.PROBE_CLIENT_METRICS
             on_flow = isinstance(tgt, _FLOW_METRIC_OF.get(m, ()))
+            if isinstance(tgt, AutoScaler) and m in N.PROBE_SCALER_METRICS:
+                if a.probe_metric is None:
+                    a.probe_metric = np.full(n, N.PROBE_NONE, np.uint8)
+                    a.probe_interval_s = np.ones(n, np.float64)
+                if id(tgt) not in node_of:
+                    raise UnsupportedTopology(f"probe '{ent.name}': its target is not an entity of this Simulation")
+                a.kind[i] = N.NODE_PROBE
+                a.target[i] = node_of[id(tgt)]
+                a.probe_metric[i] = N.PROBE_SCALER_METRICS[m]
+                a.probe_interval_s[i] = ent.interval
+                continue
             if on_flow:
                 if a.probe_metric is None:
                     a.probe_metric = np.full(n, N.PROBE_NONE, np.uint8)
@@ -672,8 +829,11 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             if not isinstance(svc, (ExponentialLatency, ConstantLatency)):
                 raise UnsupportedTopology(f"server '{ent.name}': service distribution {type(svc).__name__} is not lowered")
             a.kind[i] = N.NODE_SERVER
-            a.stream_base[i] = counters[Server]
-            counters[Server] += 1
+            if i in pool_of:
+                a.stream_base[i] = n_own_servers + pool_of[i][1] - 1        # instance k: the Servers' numbering goes on
+            else:
+                a.stream_base[i] = counters[Server]
+                counters[Server] += 1
             a.concurrency[i] = ent.concurrency
             a.lat_kind[i] = N.LAT_EXPONENTIAL if isinstance(svc, ExponentialLatency) else N.LAT_CONSTANT
             a.lat_mean_s[i] = svc.mean
@@ -720,6 +880,8 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             a.target[i] = -1 if ent.egress is None else node_of[id(ent.egress)]
         elif isinstance(ent, LoadBalancer):
             backends = ent.all_backends
+            if id(ent) in scaled:
+                backends = scaled[id(ent)][1] + scaled[id(ent)][2]       # the candidate list: the initial backends, then the pool
             for b in backends:
                 if not isinstance(b, Server):
                     raise UnsupportedTopology(f"backend '{b.name}' of '{ent.name}' is a {type(b).__name__}: only Server backends are lowered")
@@ -736,12 +898,13 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             a.rt_off[i] = len(rt)
             a.rt_cnt[i] = len(backends)
             if isinstance(st, (WeightedRoundRobin, WeightedLeastConnections)):
-                ws = [int(st.get_weight(b)) for b in backends]
+                n_init = len(ent.all_backends)                         # (an instance joins at weight 1: add_backend's default)
+                ws = [int(st.get_weight(b)) if q < n_init else 1 for q, b in enumerate(backends)]
                 if isinstance(st, WeightedRoundRobin) and sum(ws) > WeightedRoundRobin.MAX_TOTAL_WEIGHT:
                     raise UnsupportedTopology(f"'{ent.name}': WeightedRoundRobin with a total weight of {sum(ws)} needs a selection table "
                                               "beyond 2^24 entries (not lowered)")
                 weights[len(rt)] = ws
-            flags = [int(ent.get_backend_info(b).is_healthy) for b in backends]
+            flags = [int(ent.get_backend_info(b).is_healthy) if ent.get_backend_info(b) is not None else 1 for b in backends]
             if not all(flags):
                 if isinstance(st, (ConsistentHash, IPHash, Random)):
                     raise UnsupportedTopology(f"'{ent.name}': strategy {type(st).__name__} with an unhealthy backend ('"
@@ -753,6 +916,9 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             lb = ent.load_balancer
             if not isinstance(lb, LoadBalancer) or id(lb) not in node_of:
                 raise UnsupportedTopology(f"health checker '{ent.name}': its LoadBalancer is not an entity of this Simulation")
+            if id(lb) in scaled:
+                raise UnsupportedTopology(f"health checker '{ent.name}': LoadBalancer '{lb.name}' has the AutoScaler '{scaled[id(lb)][0].name}' "
+                                          "-- a HealthChecker and an AutoScaler on one LoadBalancer are not lowered (a follow-up)")
             if id(lb) in checked:
                 raise UnsupportedTopology(f"health checker '{ent.name}': LoadBalancer '{lb.name}' has the checker '{checked[id(lb)]}' already "
                                           "(one HealthChecker per LoadBalancer is lowered)")
@@ -768,6 +934,28 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
             a.kind[i] = N.NODE_HEALTH_CHECKER
             a.target[i] = node_of[id(lb)]
             a.hc_params[i] = (ent.interval, ent.timeout, ent.healthy_threshold, ent.unhealthy_threshold, 1.0 if ent.is_running else 0.0)
+        elif isinstance(ent, AutoScaler):
+            lb, pol = ent.load_balancer, ent.policy
+            if id(lb) in checked:
+                raise UnsupportedTopology(f"auto scaler '{ent.name}': LoadBalancer '{lb.name}' has the HealthChecker '{checked[id(lb)]}' -- a "
+                                          "HealthChecker and an AutoScaler on one LoadBalancer are not lowered (a follow-up)")
+            if a.as_params is None:
+                a.as_params = np.zeros((n, 10), np.float64)
+                a.as_steps = [None] * n
+            a.kind[i] = N.NODE_AUTO_SCALER
+            a.target[i] = node_of[id(lb)]
+            if isinstance(pol, TargetUtilization):
+                code, p0, p1 = N.AUTOSCALER_TARGET_UTILIZATION, pol._target, 0.0
+            elif isinstance(pol, StepScaling):
+                code, p0, p1 = N.AUTOSCALER_STEP, 0.0, 0.0
+                try:
+                    a.as_steps[i] = [(float(t), int(d)) for t, d in pol._steps]
+                except (TypeError, ValueError):
+                    raise UnsupportedTopology(f"auto scaler '{ent.name}': StepScaling steps must be (number, int) pairs") from None
+            else:
+                code, p0, p1 = N.AUTOSCALER_QUEUE_DEPTH, pol._scale_out_threshold, pol._scale_in_threshold
+            a.as_params[i] = (code, p0, p1, ent._min_instances, ent._max_instances, ent._evaluation_interval, ent._scale_out_cooldown,
+                              ent._scale_in_cooldown, len(scaled[id(lb)][2]), 1.0 if ent.is_running else 0.0)
         elif isinstance(ent, (Bulkhead, TimeoutWrapper)):
             what = f"{type(ent).__name__} '{ent.name}'"
             tgt = ent.target
@@ -918,7 +1106,7 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
         a.lb_weights = np.ones(len(rt), np.int32)
         for off, ws in weights.items():
             a.lb_weights[off:off + len(ws)] = ws
-    if unhealthy or a.hc_params is not None:
+    if unhealthy or a.hc_params is not None or a.as_params is not None:     # (a scaled LoadBalancer's member list is the healthy list)
         a.lb_healthy = np.ones(len(rt), np.uint8)
         for off, flags in unhealthy.items():
             a.lb_healthy[off:off + len(flags)] = flags
@@ -929,7 +1117,12 @@ def lower_general(sources: list, entities: list, probes=None) -> GeneralGraph:
         a.name_off = np.zeros(n + 1, np.int32)
         a.name_off[1:] = np.cumsum([len(b) for b in blobs])
     assert all(a.kind[i] == N.NODE_SOURCE for i in range(n_src)) and all(a.kind[i] == N.NODE_PROBE for i in range(n_src, n_front))
-    return GeneralGraph(nodes, a, node_of)
+    g = GeneralGraph(nodes, a, node_of)
+    g.n_own, g.scaler_starts = n_own, scaler_starts
+    g.scaled = {node_of[lb_id]: (node_of[id(sc)], initial, pool) for lb_id, (sc, initial, pool) in scaled.items()}
+    g.pool_of = {i: (node_of[id(sc)], k) for i, (sc, k) in pool_of.items()}
+    g.rr_base = {i: nodes[i].strategy._index for i in g.scaled if isinstance(nodes[i].strategy, RoundRobin)}
+    return g
 
 
 MAX_PARTS = 2048          # heaps one Simulation is spread over (hs_graph_run_parts): components beyond that share heaps
@@ -967,7 +1160,7 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
     per_node = [nm for nm in ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s",
                               "link_lat_min_s", "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric",
                               "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params", "cl_params",
-                              "flow_params", "qp_params")
+                              "flow_params", "qp_params", "as_params")
                 if getattr(a, nm) is not None]
     names = None if a.names is None else [a.names[a.name_off[i]:a.name_off[i + 1]] for i in range(n)]
     parts = []
@@ -996,7 +1189,7 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
             b.rt_targets = np.zeros(0, np.int32)
         if b.hc_params is not None and not (b.kind == N.NODE_HEALTH_CHECKER).any():
             b.hc_params = None                                             # (a part without a checker: no health state unless a flag says so)
-        if b.lb_healthy is not None and b.hc_params is None and b.lb_healthy.all():
+        if b.lb_healthy is not None and b.hc_params is None and b.lb_healthy.all() and not (b.kind == N.NODE_AUTO_SCALER).any():
             b.lb_healthy = None
         if b.wrap_params is not None and not ((b.kind == N.NODE_BULKHEAD) | (b.kind == N.NODE_TIMEOUT_WRAPPER)).any():
             b.wrap_params = None                                           # (a part without a wrapper runs the loop it would run alone)
@@ -1004,6 +1197,11 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
             b.flow_params = None                                           # (a part without a flow entity likewise)
         if b.qp_params is not None and not (b.qp_params[:, 0] != N.QUEUE_FIFO).any():
             b.qp_params = None                                             # (a part without a policied Server likewise)
+        if b.as_params is not None:
+            if (b.kind == N.NODE_AUTO_SCALER).any():
+                b.as_steps = [a.as_steps[i] for i in ids]
+            else:
+                b.as_params = None                                         # (a part without a scaler likewise)
         if b.cl_params is not None and not (b.kind == N.NODE_CLIENT).any():
             b.cl_params = None                                             # (a part without a Client likewise)
         if b.cl_params is not None:
@@ -1118,6 +1316,16 @@ class PartRun:
                 return e.wrapper(int(at))
         raise KeyError(node)
 
+    def scaler_events(self) -> int:
+        return int(sum(e.scaler_events() for e in self.engines))
+
+    def scaler(self, node: int) -> dict:
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            at = np.searchsorted(ids, node)
+            if at < len(ids) and ids[at] == node:
+                return e.scaler(int(at))
+        raise KeyError(node)
+
     def health(self, node: int) -> dict:
         for (ids, _pos, _b), e in zip(self.parts, self.engines):
             at = np.searchsorted(ids, node)
@@ -1187,14 +1395,17 @@ def keyless_hazard(g: "GeneralGraph", target) -> str | None:
 
 
 def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t: np.ndarray, rec_cr: np.ndarray, device: int = 0,
-                       health=None, wrapper=None, client=None, flow=None, queue=None) -> None:
+                       health=None, wrapper=None, client=None, flow=None, queue=None, scaler=None) -> None:
     """The run's per-node results onto the user's objects, under the attribute names the reference uses (lowering.write_back's
     counterpart).  `health`: node -> GraphEngine.health(node) of a graph with health state; `wrapper`: node -> GraphEngine.wrapper(node)
     of a graph with a Bulkhead or a TimeoutWrapper; `client`: node -> GraphEngine.client(node) of a graph with a Client."""
     a = g.arrays
     order = np.argsort(rec_node, kind="stable")              # per Sink, still in processing order
     bounds = np.searchsorted(rec_node[order], np.arange(a.n + 1))
+    scalers = {sn: scaler(sn) for sn, _initial, _pool in g.scaled.values()} if g.scaled else {}    # GraphEngine.scaler(node) per AutoScaler
     for i, ent in enumerate(g.nodes):
+        if i in g.pool_of and g.pool_of[i][1] > scalers[g.pool_of[i][0]]["next_instance_id"]:
+            continue                                               # (an instance the run never activated: left untouched)
         if isinstance(ent, Source):
             ent._generated_count = int(stats["generated"][i])
             ent._event_provider._generated = int(stats["payloads"][i])
@@ -1236,6 +1447,29 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
             elif isinstance(ent.strategy, (ConsistentHash, IPHash)):
                 ent.strategy._fallback._index += selections        # ... per KEY-LESS Request (strategies.py:309,362,420-421)
             off = int(a.rt_off[i])
+            if i in g.scaled:
+                # a scaled LoadBalancer: `_backends` is the initial backends, then the live managed instances in id order; a removed
+                # instance has no entry any more, the strategy keeps what it learned of it (its weight, its current weight)
+                sn, initial, pool = g.scaled[i]
+                w, h = scalers[sn], health(i)
+                slots = [q for q in range(len(initial) + len(pool)) if w["member"][q]]
+                cand = initial + pool
+                old = ent._backends
+                ent._backends = {}
+                for q in slots:
+                    b = cand[q]
+                    info = old.get(b.name) if q < len(initial) else None
+                    ent._backends[b.name] = info if info is not None and info.backend is b else BackendInfo(backend=b, weight=1)
+                    ent._backends[b.name].total_requests = int(stats["rt_taken"][off + q])
+                if i in g.rr_base:
+                    ent.strategy._index = g.rr_base[i] + selections    # (bound behind every window: absolute, not added once more)
+                if hasattr(ent.strategy, "set_weight"):
+                    for b in pool[:w["next_instance_id"]]:
+                        ent.strategy._weights[b.name] = 1            # add_backend's set_weight(backend, 1)
+                if isinstance(ent.strategy, WeightedRoundRobin) and h["current_weights"] is not None:
+                    ent.strategy._selections = selections
+                    ent.strategy._current_weights = {cand[q].name: v for q, v in sorted(h["current_weights"].items())}
+                continue
             for q, b in enumerate(ent.all_backends):
                 ent._backends[b.name].total_requests = int(stats["rt_taken"][off + q])
             if health is not None:
@@ -1258,6 +1492,17 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
                 st._selections = selections
                 st._current_weights = ({b.name: w * selections - sum(ws) * int(stats["rt_taken"][off + q])
                                         for q, (b, w) in enumerate(zip(ent.all_backends, ws))} if selections else {})
+        elif isinstance(ent, AutoScaler):
+            w = scalers[i]
+            (ent._evaluations, ent._scale_out_count, ent._scale_in_count, ent._instances_added, ent._instances_removed,
+             ent._cooldown_blocks, ent._next_instance_id) = (w[k] for k in GraphEngine._SCALER_NAMES[:7])
+            ent._last_scale_action = (None, "scale_out", "scale_in")[w["last_action"]]
+            ent._last_scale_time = Instant(w["last_time_ns"]) if w["last_action"] else None
+            ent.scaling_history = [ScalingEvent(Instant(int(t)), "scale_out" if act == 1 else "scale_in", int(c0), int(c1),
+                                                f"{'Added' if act == 1 else 'Removed'} {int(cnt)} instances")
+                                   for t, act, c0, c1, cnt in w["history"].tolist()]
+            _sn, initial, pool = g.scaled[int(a.target[i])]
+            ent._managed_servers = [pool[q - len(initial)] for q in range(len(initial), len(initial) + len(pool)) if w["member"][q]]
         elif isinstance(ent, HealthChecker):
             h = health(i)
             (ent._checks_performed, ent._checks_passed, ent._checks_failed, ent._checks_timed_out, ent._backends_marked_healthy,

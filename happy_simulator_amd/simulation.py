@@ -14,7 +14,7 @@ from .core.temporal import Instant
 from .engine import StationEngine
 from .graph_engine import (DEFAULT_MAX_EVENTS, MAX_PARTS, GeneralGraph, GraphEngine, PartRun, keyless_hazard, lower_general, split_parts,
                            write_back_general)
-from .entities import BatchProcessor, Bulkhead, Client, ConveyorBelt, Entity, GateController, HealthChecker, LoadBalancer, Network, Server, TimeoutWrapper
+from .entities import AutoScaler, BatchProcessor, Bulkhead, Client, ConveyorBelt, Entity, GateController, HealthChecker, LoadBalancer, Network, Server, TimeoutWrapper
 from .faults import FaultSchedule, LinkFaultEvent
 from .lowering import (LazyRecords, LbGraph, LoweredGraph, UnsupportedTopology, attach_lb_probes, attach_probes, find_load_balancer, lower,
                        plain_probe_arrays, write_back_plain_probes,
@@ -60,7 +60,7 @@ class Simulation:
             raise UnsupportedTopology(f"fault schedule {type(fault_schedule).__name__} is not a lowered FaultSchedule")
         self._faults = fault_schedule._start(self) if fault_schedule is not None else []
         for ent in self._entities:                 # the clock every listed entity is handed (core/simulation.py:118-135): a
-            if isinstance(ent, HealthChecker):     # checker's start() reads `now` from it
+            if isinstance(ent, (HealthChecker, AutoScaler)):     # checker's (a scaler's) start() reads `now` from it
                 ent._sim_start = self._start_time
             if isinstance(ent, Client):            # ... and a Client's send_request()
                 ent._sim = self
@@ -134,6 +134,25 @@ class Simulation:
         not the full one), which only the single-heap loop follows."""
         return any(isinstance(e, HealthChecker) or (isinstance(e, LoadBalancer) and e.unhealthy_backends) for e in self._entities)
 
+    def _has_scalers(self) -> bool:
+        """An AutoScaler among the entities: a LoadBalancer whose backends join and leave during the run, which only the single-heap
+        loop follows."""
+        return any(isinstance(e, AutoScaler) for e in self._entities)
+
+    def _scaler_starts(self) -> int:
+        """The most `_autoscaler_evaluate` Events scheduled for one scaler: every one begins a chain of evaluations."""
+        per: dict[int, int] = {}
+        for ev in self._scheduled:
+            if isinstance(ev.target, AutoScaler) and not ev.cancelled:
+                per[id(ev.target)] = per.get(id(ev.target), 0) + 1
+        return max(per.values(), default=1)
+
+    def _lower_general(self) -> GeneralGraph:
+        """lower_general over this Simulation, with the horizon and the scheduled start() Events its AutoScalers' pools are sized by."""
+        end_ns = None if self._end_time == Instant.Infinity else self._end_time.nanoseconds
+        return lower_general(self._sources, self._entities, self._probes, start_ns=self._start_time.nanoseconds, end_ns=end_ns,
+                             scaler_starts=self._scaler_starts())
+
     def _has_wrappers(self) -> bool:
         """A Bulkhead or a TimeoutWrapper among the entities or as a Source's target: completion hooks and per-request ids, which only
         the single-heap loop follows."""
@@ -152,21 +171,24 @@ class Simulation:
         return any(isinstance(e, (BatchProcessor, ConveyorBelt, GateController)) for e in self._entities + firsts)
 
     def lowered(self) -> "LoweredGraph | LbGraph | GeneralGraph":
+        if self._graph is None and self._has_scalers():
+            self._graph = self._lower_general()
+            self._station_refusal = "the station, network and pipeline engines do not lower an AutoScaler"
         if self._graph is None and self._has_flows():
-            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._graph = self._lower_general()
             self._station_refusal = "the station, network and pipeline engines do not lower BatchProcessor, ConveyorBelt or GateController"
         if self._graph is None and self._has_clients():
-            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._graph = self._lower_general()
             self._station_refusal = "the station, network and pipeline engines do not lower a Client"
         if self._graph is None and self._has_wrappers():
-            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._graph = self._lower_general()
             self._station_refusal = "the station, network and pipeline engines do not lower Bulkhead or TimeoutWrapper"
         if self._graph is None and not self._faults and self._has_health():
-            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._graph = self._lower_general()
             self._station_refusal = "the station, network and pipeline engines do not lower health checks or unhealthy backends"
         if self._graph is None and self._faults:
             # node faults run where every Event is popped one by one: the single-heap loop
-            self._graph = lower_general(self._sources, self._entities, self._probes)
+            self._graph = self._lower_general()
             self._station_refusal = "the station, network and pipeline engines do not lower fault schedules"
         if self._graph is None:
             plain = plain_chains(self._sources, self._entities)      # (n plain chains: no LoadBalancer among them, one pass less)
@@ -184,7 +206,7 @@ class Simulation:
                     # classes can be wired into otherwise -- exactly, at ~2.4 us per event and heap (several LoadBalancers, a LoadBalancer
                     # behind Servers ... included)
                     try:
-                        self._graph = lower_general(self._sources, self._entities, self._probes)
+                        self._graph = self._lower_general()
                     except UnsupportedTopology as general:
                         raise UnsupportedTopology(f"{station_shape}; and not on the single-heap path either: {general}") from None
                     self._station_refusal = str(station_shape)
@@ -201,7 +223,7 @@ class Simulation:
                     # (more than four probes on a station, a further Source of a Server sampled, a probe on the LoadBalancer's
                     # Source with stop_after ...: the single heap samples anything)
                     try:
-                        self._graph = lower_general(self._sources, self._entities, self._probes)
+                        self._graph = self._lower_general()
                     except UnsupportedTopology:
                         raise station_shape from None
                     self._station_refusal = str(station_shape)
@@ -286,7 +308,7 @@ class Simulation:
                 # refused on the way (a probe the station slots do not hold, a tick on the nanosecond of a shared Sink's record ...):
                 # the single-heap loop takes it if the graph is its kind; otherwise the station engines' refusal stands
                 try:
-                    g = lower_general(self._sources, self._entities, self._probes)
+                    g = self._lower_general()
                 except UnsupportedTopology:
                     raise station_shape from None
                 self._station_refusal = str(station_shape)
@@ -427,6 +449,7 @@ class Simulation:
         self._general_est = 12.0 * float(a.src_rate[a.kind == N.NODE_SOURCE].sum()) * horizon_s
         cancelled_ns: list[int] = []
         sched: list[tuple[int, int]] = []
+        n_starts: dict[int, int] = {}
         for ev in self._scheduled:
             if ev.cancelled:                       # lazy deletion: skipped when popped, counted (simulation.py:475-477)
                 cancelled_ns.append(ev.time.nanoseconds)
@@ -443,6 +466,19 @@ class Simulation:
             if ev.on_complete:
                 raise UnsupportedTopology(f"scheduled event {ev!r}: completion hooks are host Python (not lowered)")
             rid = None
+            if a.kind[i] == N.NODE_AUTO_SCALER:
+                # the Event AutoScaler.start() returns: a daemon without a Request, at the Simulation's start
+                if ev.event_type != "_autoscaler_evaluate" or not ev.daemon or ev.time.nanoseconds != start_ns:
+                    raise UnsupportedTopology(f"scheduled event {ev!r}: only the daemon Event start() returns, at the Simulation's start, is "
+                                              "lowered for an AutoScaler")
+                if cancelled_ns:
+                    raise UnsupportedTopology("cancelled Events in front of live ones are not lowered on the single-heap path")
+                n_starts[i] = n_starts.get(i, 0) + 1
+                if n_starts[i] > g.scaler_starts:
+                    raise UnsupportedTopology(f"scheduled event {ev!r}: start() Events scheduled after the graph was lowered (the scaler's "
+                                              "instance pool was sized for fewer): schedule them before lowered()")
+                sched.append((i, ev.time.nanoseconds))
+                continue
             if a.kind[i] == N.NODE_GATE and ev.event_type in ("_GateOpen", "_GateClose"):
                 # one Event of GateController.start_events(): a daemon without a Request
                 if not ev.daemon:
@@ -522,9 +558,10 @@ class Simulation:
         stats = eng.stats()
         rec = eng.records()
         health, wrappers, clients, flows = g.arrays.has_health, g.arrays.has_wrappers, g.arrays.has_clients, g.arrays.has_flows
+        scalers = g.arrays.has_scalers
         write_back_general(g, stats, *rec, device=self._device, health=eng.health if health else None,
                            wrapper=eng.wrapper if wrappers else None, client=eng.client if clients else None, flow=eng.flow if flows else None,
-                           queue=eng.queue_policy if g.arrays.has_queue_policies else None)
+                           queue=eng.queue_policy if g.arrays.has_queue_policies else None, scaler=eng.scaler if scalers else None)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
         if health:
@@ -543,6 +580,9 @@ class Simulation:
             fe = eng.flow_events()
             self._flow_by_kind = fe[:N.FLOW_KINDS]
             self._events_cancelled += int(fe[N.FLOW_KINDS])
+        if scalers:
+            # the scalers' `_autoscaler_evaluate` Events: one more internal kind, counted the same way
+            self._autoscaler_by_kind = np.array([eng.scaler_events()], np.int64)
         if (health or wrappers or clients or flows or g.arrays.has_queue_policies) and not self._faults:
             self._internal_by_kind = eng.faults()[1]
         if self._faults:

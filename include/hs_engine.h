@@ -197,6 +197,7 @@ typedef enum hs_probe_metric {
     HS_PROBE_BP_BUFFER_DEPTH = 13, /* BatchProcessor.buffer_depth (general graphs only) */
     HS_PROBE_CV_IN_TRANSIT = 14,   /* ConveyorBelt.items_in_transit */
     HS_PROBE_GT_QUEUE_DEPTH = 15,  /* GateController.queue_depth */
+    HS_PROBE_AS_CURRENT_COUNT = 16,/* AutoScaler.current_count (general graphs only) */
     HS_PROBE_NONE = 255
 } hs_probe_metric;
 typedef enum hs_profile_kind { HS_PROF_CONSTANT = 0, HS_PROF_LINEAR_RAMP = 1, HS_PROF_SPIKE = 2 } hs_profile_kind;
@@ -756,7 +757,8 @@ typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK
                              HS_NODE_CLIENT = 11,         /* Client: `target` = the entity it sends to; everything else: hs_graph_set_client */
                              HS_NODE_BATCH_PROCESSOR = 12, /* BatchProcessor, ConveyorBelt, GateController: `target` = their downstream; */
                              HS_NODE_CONVEYOR = 13,        /* everything else: hs_graph_set_flow */
-                             HS_NODE_GATE = 14
+                             HS_NODE_GATE = 14,
+                             HS_NODE_AUTO_SCALER = 15      /* AutoScaler: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_auto_scaler */
 } hs_node_kind;
 
 typedef struct hs_graph_config {
@@ -1095,6 +1097,36 @@ typedef enum hs_queue_policy { HS_QUEUE_FIFO = 0, HS_QUEUE_LIFO = 1, HS_QUEUE_AD
 #define HS_QUEUE_FIELDS 16
 int hs_graph_set_queue_policy(hs_graph *g, int32_t node, int32_t policy, int64_t capacity, int64_t threshold, double target_s, double interval_s);
 int hs_graph_get_queue_policy(hs_graph *g, int32_t node, int64_t *out);
+/* AutoScaler (components/deployment/auto_scaler.py): a periodic controller that adds Servers to a LoadBalancer's backends and removes
+ * them again during the run.  The instances it may add are a POOL of dormant Server nodes: the last `n_pool` targets of the
+ * LoadBalancer (its initial backends stand in front of them), instance k = pool target k - 1.  A LoadBalancer with a scaler keeps a
+ * membership word per target next to the health flag; `_forward_request` selects over the members in list order (the path of the
+ * health lowering: RoundRobin, the live WeightedRoundRobin, LeastConnections, WeightedLeastConnections; the other strategies:
+ * HS_E_UNSUPPORTED).  A graph with a scaler runs an instantiation of the loop of its own.
+ *
+ * hs_graph_set_auto_scaler, before the first run (HS_E_STATE afterwards), once per scaler node: `policy` with its parameters --
+ * HS_AUTOSCALER_TARGET_UTILIZATION: p0 = target; HS_AUTOSCALER_QUEUE_DEPTH: p0 / p1 = scale_out / scale_in threshold;
+ * HS_AUTOSCALER_STEP: n_steps (at most HS_AUTOSCALER_MAX_STEPS) pairs step_threshold[k] / step_adjustment[k] in the order the
+ * reference evaluates them --, the limits, the interval and the two cooldowns in seconds, the LoadBalancer node, the pool's size and
+ * `running` (`_is_running` when the run begins).  A second scaler on one LoadBalancer, a scaler next to a HealthChecker on it and an
+ * initially unhealthy backend under a scaler: HS_E_UNSUPPORTED.  hs_graph_schedule on the scaler node is the daemon
+ * `_autoscaler_evaluate` Event start() returns.  The handler restates _evaluate / _in_cooldown / _try_scale_out / _try_scale_in; a
+ * scale-out that needs an instance beyond the pool ends the run with HS_E_OVERFLOW and a message that names the scaler.
+ *
+ * hs_graph_get_auto_scaler, after a run (any output may be NULL): state[HS_AUTOSCALER_FIELDS] = evaluations, scale_out_count,
+ * scale_in_count, instances_added, instances_removed, cooldown_blocks, _next_instance_id, _last_scale_action (0 None, 1 scale_out,
+ * 2 scale_in), _last_scale_time ns, records in the scaling history, members of the LoadBalancer, 0; history[4 * min(records,
+ * history_cap)] = (time ns, action + 4 x the instances it counted, from_count, to_count) per ScalingEvent; member[n targets of the LoadBalancer] = the membership
+ * word of every target; *events = the graph's `_autoscaler_evaluate` Events: events_processed == sum(events_by_kind) + the other
+ * internal kinds + *events.  node = -1 with every other output NULL: the event count alone. */
+typedef enum hs_autoscaler_policy { HS_AUTOSCALER_TARGET_UTILIZATION = 0, HS_AUTOSCALER_STEP = 1, HS_AUTOSCALER_QUEUE_DEPTH = 2 } hs_autoscaler_policy;
+#define HS_AUTOSCALER_MAX_STEPS 16
+#define HS_AUTOSCALER_MAX_POOL 4096
+#define HS_AUTOSCALER_FIELDS 12
+int hs_graph_set_auto_scaler(hs_graph *g, int32_t node, int32_t lb_node, int32_t policy, double p0, double p1, int32_t n_steps,
+                             const double *step_threshold, const int32_t *step_adjustment, int32_t min_instances, int32_t max_instances,
+                             double interval_s, double scale_out_cooldown_s, double scale_in_cooldown_s, int32_t n_pool, int32_t running);
+int hs_graph_get_auto_scaler(hs_graph *g, int32_t node, int64_t *state, int64_t *history, int64_t history_cap, uint8_t *member, int64_t *events);
 /* Debug / tests only (the null stream, its own allocations): CoDelQueue._control_law's step on the device, one (count, interval_s) pair
  * per thread: out_ns[i] = Duration.from_seconds(interval_s[i] / sqrt(count[i])) in ns (count >= 1, 0 < interval <= 4e9).  Tests compare
  * it with CPython. */
