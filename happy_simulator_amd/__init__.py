@@ -33,6 +33,8 @@ from .entities import (AdaptiveLIFO, AdaptiveLIFOStats, CoDelQueue, CoDelStats, 
 from .entities import (BatchProcessor, BatchProcessorStats, ConveyorBelt, ConveyorStats, GateController, GateStats)  # noqa: F401
 from .entities import LinkStats, Network  # noqa: F401
 from .entities import AutoScaler, AutoScalerStats, QueueDepthScaling, ScalingEvent, StepScaling, TargetUtilization  # noqa: F401
+from .entities import DeploymentState, RollingDeployer, RollingDeployerStats  # noqa: F401
+from .entities import CanaryDeployer, CanaryDeployerStats, CanaryStage, CanaryState, ErrorRateEvaluator, LatencyEvaluator  # noqa: F401
 from .faults import CrashNode, FaultHandle, FaultSchedule, FaultStats, InjectLatency, InjectPacketLoss, PauseNode  # noqa: F401
 from .lowering import UnsupportedTopology  # noqa: F401
 from .parallel import (ParallelResult, ParallelRunner, ParallelSimulation, ParallelSimulationSummary,  # noqa: F401

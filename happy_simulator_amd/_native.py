@@ -51,6 +51,13 @@ QUEUE_FIFO, QUEUE_LIFO, QUEUE_ADAPTIVE_LIFO, QUEUE_CODEL = 0, 1, 2, 3   # hs_que
 QUEUE_FIELDS = 16                                           # HS_QUEUE_FIELDS
 LINK_FAULT_LATENCY, LINK_FAULT_LOSS = 1, 2                  # hs_link_fault
 NODE_AUTO_SCALER = 15
+NODE_ROLLING_DEPLOYER = 16
+NODE_CANARY_DEPLOYER = 17
+CANARY_KINDS, CANARY_MAX_STAGES, CANARY_FIELDS = 6, 16, 16          # HS_CANARY_KINDS / _MAX_STAGES / _FIELDS
+CANARY_STATUS = ("idle", "in_progress", "promoting", "rolled_back", "completed")   # hs_canary_status
+CANARY_ERROR_RATE, CANARY_LATENCY = 0, 1                              # hs_canary_evaluator
+DEPLOYER_KINDS, DEPLOYER_MAX_POOL, DEPLOYER_FIELDS = 7, 4096, 20   # HS_DEPLOYER_KINDS / _MAX_POOL / _FIELDS
+DEPLOYMENT_STATUS = ("idle", "in_progress", "completed", "rolled_back")   # hs_deployment_status
 AUTOSCALER_TARGET_UTILIZATION, AUTOSCALER_STEP, AUTOSCALER_QUEUE_DEPTH = 0, 1, 2   # hs_autoscaler_policy
 AUTOSCALER_MAX_STEPS, AUTOSCALER_MAX_POOL, AUTOSCALER_FIELDS = 16, 4096, 12        # HS_AUTOSCALER_MAX_STEPS / _MAX_POOL / _FIELDS
 # hs_limiter_policy / hs_limiter_outcome (the third column of a limiter's records)
@@ -553,6 +560,16 @@ def lib():
                                            C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32]
     L.hs_graph_get_auto_scaler.restype = C.c_int
     L.hs_graph_get_auto_scaler.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.hs_graph_set_rolling_deployer.restype = C.c_int
+    L.hs_graph_set_rolling_deployer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.c_int32]
+    L.hs_graph_get_rolling_deployer.restype = C.c_int
+    L.hs_graph_get_rolling_deployer.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hs_graph_set_canary_deployer.restype = C.c_int
+    L.hs_graph_set_canary_deployer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double]
+    L.hs_graph_get_canary_deployer.restype = C.c_int
+    L.hs_graph_get_canary_deployer.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
+    L.hs_debug_compact_members.restype = C.c_int
+    L.hs_debug_compact_members.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.hs_debug_codel_next.restype = C.c_int
     L.hs_debug_codel_next.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_graph_coop_selects.restype = C.c_int64
@@ -622,4 +639,6 @@ EXPORTED_SYMBOLS = (
     "hs_graph_set_flow", "hs_graph_schedule_gate", "hs_graph_get_flow",
     "hs_graph_set_queue_policy", "hs_graph_get_queue_policy", "hs_debug_codel_next",
     "hs_graph_set_auto_scaler", "hs_graph_get_auto_scaler",
+    "hs_graph_set_rolling_deployer", "hs_graph_get_rolling_deployer", "hs_debug_compact_members",
+    "hs_graph_set_canary_deployer", "hs_graph_get_canary_deployer",
 )

@@ -161,6 +161,16 @@ constexpr uint32_t kEvBpItem = kEvCliKinds, kEvBpTimeout = kEvCliKinds + 1, kEvB
 // the scaler itself, no Request.  It counts in events_processed and per graph (GVars::as_evals).
 constexpr uint32_t kEvAsEval = kEvFlowKinds, kEvAsKinds = kEvFlowKinds + 1;
 constexpr int kMaxScalerSteps = HS_AUTOSCALER_MAX_STEPS;
+// RollingDeployer (components/deployment/rolling_deployer.py:158-175): its seven handlers, seven more internal kinds, aimed at the
+// deployer itself, no daemons.  A `_rolling_health_pass` / `_rolling_health_timeout` carries the instance's slot in the LoadBalancer as
+// req = -2 - slot (its `server_name`).  They count in events_processed and per graph (GVars::rd_by_kind).
+constexpr uint32_t kEvRdStart = kEvAsKinds, kEvRdBatch = kEvAsKinds + 1, kEvRdCheck = kEvAsKinds + 2, kEvRdPass = kEvAsKinds + 3,
+                   kEvRdTimeout = kEvAsKinds + 4, kEvRdRollback = kEvAsKinds + 5, kEvRdComplete = kEvAsKinds + 6,
+                   kEvDpKinds = kEvAsKinds + HS_DEPLOYER_KINDS;
+// CanaryDeployer (components/deployment/canary_deployer.py:265-280): its six handlers, six more internal kinds, aimed at the deployer
+// itself, no daemons, no Request.  They count in events_processed and per graph (GVars::cn_by_kind).
+constexpr uint32_t kEvCnStart = kEvDpKinds, kEvCnStage = kEvDpKinds + 1, kEvCnEval = kEvDpKinds + 2, kEvCnPromote = kEvDpKinds + 3,
+                   kEvCnRollback = kEvDpKinds + 4, kEvCnComplete = kEvDpKinds + 5, kEvCnKinds = kEvDpKinds + HS_CANARY_KINDS;
 constexpr int kMaxFlowItems = HS_FLOW_MAX_ITEMS;             // batch_size / a bounded gate queue: a batch's length rides in 30 bits of GEvent::pad
 constexpr uint32_t kPadPre = 1u, kPadCancelled = 2u;
 constexpr int kPadIdShift = 2;                 // a check id in GEvent::pad (its low 30 bits: only the one pending id of a backend and ids
@@ -185,6 +195,9 @@ static_assert(kEvFlowKinds <= 64, "kDropKindsFlow is two words; s_by_kind is zer
 // ... and a scaler's evaluation, tested by the one instantiation that dispatches it
 constexpr uint64_t kDropKindsAs = kDropKindsFlow | (1ull << kEvAsEval);
 static_assert(kEvAsKinds <= 64, "kDropKindsAs is two words; s_by_kind is zeroed by one lane per kind");
+// ... and a deployer's seven
+constexpr uint64_t kDropKindsDp = kDropKindsAs | (((1ull << (HS_DEPLOYER_KINDS + HS_CANARY_KINDS)) - 1ull) << kEvRdStart);
+static_assert(kEvCnKinds <= 64, "kDropKindsDp is two words; s_by_kind is zeroed by one lane per kind");
 constexpr int kMaxBulkheadConcurrent = HS_BULKHEAD_MAX_CONCURRENT;         // Bulkhead.max_concurrent the in-flight table is sized for (include/hs_engine.h)
 constexpr int kDefaultTimeoutTable = 256;                // ids a TimeoutWrapper's (keys a Client's) table holds before it first grows
 constexpr int kMaxClientAttempts = HS_CLIENT_MAX_ATTEMPTS;   // the attempt of a key is 16 bits and one
@@ -238,6 +251,40 @@ struct GAs {
     int32_t pad;
 };
 constexpr int kAsOut = 1, kAsIn = 2;
+// A RollingDeployer's state, one row per deployer in HBM (GVars::rd; GParam::stream_base = its row).  GParam of a deployer:
+// mean = health_check_interval (seconds), conc = healthy_threshold, lim = max_failures, target = its LoadBalancer, rt_off = the slot of
+// instance 1 among the LoadBalancer's targets (= its initial backends), rt_cnt = the pool's size P.  The four lists hold slots of
+// the LoadBalancer, `cap` (= its targets) places each.
+// A CanaryDeployer's parameters and state, one row per deployer in HBM (GVars::cn; GParam::stream_base = its row).  GParam of a canary
+// deployer: mean = evaluation_interval (seconds), target = its LoadBalancer, rt_off = the canary's slot among the LoadBalancer's
+// targets (= its initial backends), rt_cnt = 1.
+struct GCn {
+    double pct[HS_CANARY_MAX_STAGES], period[HS_CANARY_MAX_STAGES];   // CanaryStage.traffic_percentage / evaluation_period
+    double ev_max, ev_mult;                    // max_error_rate / max_latency, threshold_multiplier
+    double cur_pct;                            // state.canary_traffic_pct
+    int64_t stage_start;                       // _stage_start_time ns (has_start)
+    int32_t *base;                             // [cap] _baseline_backends as slots
+    int32_t *wr;                               // [cap] 1: the strategy's set_weight was called for the slot during the run (-1: never)
+    int32_t lb;                                // its LoadBalancer's node
+    int32_t pad2;
+    int32_t cap, n_base, n_stages, evaluator;  // hs_canary_evaluator
+    int32_t status, cur_stage, total_stages;   // state.status (hs_canary_status), current_stage, total_stages
+    int32_t has_start, has_canary, pad;
+    int64_t started, completed, rolled_back, stages_completed, ev_performed, ev_passed, ev_failed;   // CanaryDeployerStats
+};
+struct GRd {
+    int32_t *old_b, *new_b, *cur_old, *cur_new;    // _old_backends (from old_head on), _new_backends, _current_batch_old, _current_batch_new
+    int32_t *pass;                             // [cap] _health_pass_count by slot (-1: the name has no entry)
+    int32_t *readd;                            // [cap] 1: a rollback brought the backend back (a new BackendInfo, weight 1); -1: never
+    int32_t cap, batch_size;
+    int32_t old_head, old_n, new_n, cur_old_n, cur_new_n;
+    int32_t status;                            // state.status: hs_deployment_status
+    int32_t total, replaced, failed, cur_batch;    // state.total_instances / replaced / failed / current_batch
+    int32_t next_id, fail_count;               // _next_instance_id, _health_fail_count
+    int32_t wanted;                            // the instance id beyond the pool a batch asked for (kPoolOut; 0: none)
+    int32_t lb;                                // its LoadBalancer's node
+    int64_t started, completed, rolled_back, inst_replaced, hc_performed, hc_passed, hc_failed;   // RollingDeployerStats
+};
 constexpr int kLimPollScheduled = 1, kLimHasTime = 2;   // GState::active of a limiter: _poll_scheduled; _last_*_time / _current_window_start is set
 constexpr long long kMaxSlidingLog = 1ll << 20;          // SlidingWindowPolicy.max_requests the ring is sized for
 
@@ -273,6 +320,15 @@ struct GVars {                                 // device scalars
     GAs *as;                                   // the rows of the AutoScalers (hs_graph_set_auto_scaler; null: none)
     uint8_t *as_mem;                           // [n_rt] the membership word of every backend slot: the backend is in LoadBalancer._backends
     long long as_evals;                        // the scalers' `_autoscaler_evaluate` Events (hs_graph_get_auto_scaler)
+    GRd *rd;                                   // the rows of the RollingDeployers (hs_graph_set_rolling_deployer; null: none)
+    long long rd_by_kind[HS_DEPLOYER_KINDS];   // the deployers' Events by kind (hs_graph_get_rolling_deployer)
+    GCn *cn;                                   // the rows of the CanaryDeployers (hs_graph_set_canary_deployer; null: none)
+    long long cn_by_kind[HS_CANARY_KINDS];     // the canary deployers' Events by kind (hs_graph_get_canary_deployer)
+    double *svc_sum; long long *svc_cnt;       // [n] per node: Server._service_times as a running left-to-right sum and a count, taken at the
+                                               // draw (graphs with a CanaryDeployer; null: none)
+    int n_rd, n_cn;                            // rows of `rd` / `cn`
+    long long rd_compactions[2];               // member lists compacted behind a removal: by the lone lane, by all 64 lanes
+    int rd_coop_min;                           // a removal from a list of >= this many members is compacted by all 64 lanes (0: never)
 };
 
 struct GCtl {                                  // kernel argument
@@ -287,7 +343,8 @@ struct GCtl {                                  // kernel argument
     const int64_t *ticks; long long tick_cap; const int64_t *tick_count;
     const int32_t *key_table;                  // ConsistentHash / IPHash .select(str(client id)) as a backend slot, per LoadBalancer (GParam::lim);
                                                // WeightedRoundRobin: one period of its selection sequence
-    const int32_t *lb_w;                       // [n_rt] the weighted strategies' weight of every backend slot (strategy._weights; default 1)
+    int32_t *lb_w;                             // [n_rt] the weighted strategies' weight of every backend slot (strategy._weights; default 1);
+                                               // written during a run by the deployer instantiation alone (add_backend's set_weight)
     int coop_reset;                            // 1: the first launch of a run -- the lone lane zeroes GVars::coop_selects (the host clears it after the launch)
     int64_t *lim_ring;                         // SlidingWindowPolicy._request_log of every such limiter: a ring at GParam::rt_off of GParam::rt_cnt entries
     int auto_term;                             // 1: end_ns = 2^61 (end_time = Infinity) -- the run ends when only daemon Events (polls, faults) are pending
@@ -649,12 +706,36 @@ __device__ inline bool tab_remove(int64_t *tab, int live, int64_t id) {
 // their code: the fault-only loop is as sensitive to what it carries as the plain one.  HC implies F.
 // R: the graph (or one of a batch) has a Bulkhead or a TimeoutWrapper -- a fourth instantiation, for the same reason.  R implies HC.
 // CL: ... has a Client -- a fifth, for the same reason.  CL implies R.
+// A LoadBalancer's member list `hl` (`len` slots in insertion order) compacted by the membership words `mem` (by slot), order kept;
+// the new length.  On the lone lane ...
+__device__ inline int compact_members_lone(int32_t *hl, const uint8_t *mem, int len) {
+    int w = 0;
+    for (int q = 0; q < len; ++q) { const int sl = hl[q]; if (mem[sl]) hl[w++] = sl; }
+    return w;
+}
+// ... and by all 64 lanes of the one wavefront: per chunk of 64 entries a ballot of the entries that stay and a prefix count of the
+// lanes below.  Every lane has read its entry of a chunk before any lane writes one (one wavefront, in program order), and an entry
+// only ever moves towards the front.  Every lane returns the new length.
+__device__ inline int compact_members_wave(int32_t *hl, const uint8_t *mem, int len, int lane) {
+    int w = 0;
+    for (int base = 0; base < len; base += 64) {
+        const int q = base + lane;
+        const int sl = q < len ? hl[q] : 0;
+        const bool keep = q < len && mem[sl] != 0;
+        const unsigned long long stay = __ballot(keep);
+        const int pos = w + __popcll(stay & ((1ull << lane) - 1ull));
+        if (keep) hl[pos] = sl;
+        w += __popcll(stay);
+    }
+    return w;
+}
+
 // FL: ... has a BatchProcessor, a ConveyorBelt or a GateController -- a sixth, for the same reason.  FL implies CL.
 // Q: ... has a Server with a LIFOQueue, an AdaptiveLIFO or a CoDelQueue -- a seventh, for the same reason.  Q implies FL.
 // LF: ... has a link fault (InjectLatency / InjectPacketLoss) -- an eighth, for the same reason.  LF implies Q.
 // AS: ... has an AutoScaler -- a ninth, for the same reason.  AS implies LF.
 template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false, bool Q = false, bool LF = false,
-          bool AS = false>
+          bool AS = false, bool DP = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     static_assert(F || !HC, "the health instantiation carries the fault code");
     static_assert(HC || !R, "the resilience instantiation carries the fault and health code");
@@ -663,9 +744,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
     static_assert(FL || !Q, "the queue-policy instantiation carries the fault, health, resilience, client and flow code");
     static_assert(Q || !LF, "the link-fault instantiation carries the code of all the others");
     static_assert(LF || !AS, "the scaler instantiation carries the code of all the others");
-    constexpr uint32_t kKinds = AS ? kEvAsKinds : FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
+    static_assert(AS || !DP, "the deployer instantiation carries the code of all the others");
+    constexpr uint32_t kKinds = DP ? kEvCnKinds : AS ? kEvAsKinds : FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
     // (one word for the instantiations whose kinds fit in it, two for the flow instantiation's 39)
-    constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = AS ? kDropKindsAs : FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
+    constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = DP ? kDropKindsDp : AS ? kDropKindsAs : FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
     constexpr int kPushes = R ? 3 : 2;         // heap entries one event constructs at most (R: a limiter's forward or poll + the hook's response)
     __shared__ unsigned long long s_by_kind[kKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
@@ -782,6 +864,15 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     continue;
                 }
             }
+            if constexpr (DP) {
+                // RollingDeployer.deploy() (rolling_deployer.py:145-156): a `_rolling_deploy_start` Event, no daemon, no Request
+                const int dn = c.sched_node[V.sched_done];
+                if (c.P[dn].kind == HS_NODE_ROLLING_DEPLOYER || c.P[dn].kind == HS_NODE_CANARY_DEPLOYER) {   // (`_canary_deploy_start` likewise)
+                    H.push(mk_pre(c.sched_t[V.sched_done], V.global_counter++, c.P[dn].kind == HS_NODE_ROLLING_DEPLOYER ? kEvRdStart : kEvCnStart, dn, -1));
+                    V.sched_done++;
+                    continue;
+                }
+            }
             int r = req_free;
             if (r >= 0) req_free = c.reqs[r].next;
             else if (req_len < c.req_cap) r = req_len++;
@@ -855,6 +946,16 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     if (row.hist_len >= row.hist_cap) { status |= kGrowHist; break; }
                 }
             }
+            if constexpr (DP) {
+                const GEvent top = H.get(0);                                       // a health check constructs two Events and one Request per instance
+                if (top.kind == kEvRdCheck && top.t >= cur) {                      // of the batch
+                    const long long nb = V.rd[c.P[top.node].stream_base].cur_new_n;
+                    if (H.len + 2 * nb + 1 > c.heap_cap) { status |= kGrowHeap; break; }
+                    long long room = (long long)c.req_cap - (long long)req_len;
+                    for (int r = req_free; r >= 0 && room < nb; r = c.reqs[r].next) room += 1;
+                    if (room < nb) { status |= kGrowReq; break; }
+                }
+            }
             if (c.coop_min > 0 && sel < 0) {                                       // (a graph without such a LoadBalancer: one uniform test)
                 const GEvent top = H.get(0);
                 if (top.kind == HS_EV_LB && top.t >= cur) {
@@ -866,6 +967,12 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         // Every test that could stop the loop in front of this Event has passed above and passes again unchanged
                         // behind the hand-over, so the selection the wavefront makes (and, for WeightedRoundRobin, applies) is consumed.
                         if (c.health) coop = (tp.sub >= HS_LB_LEAST_CONNECTIONS || tp.sub == HS_LB_WEIGHTED_ROUND_ROBIN) && c.S[top.node].qlen >= c.coop_min;
+                    }
+                    if constexpr (DP) {
+                        // (a deployed LoadBalancer's list is in insertion order; the cooperative selection's tie rule needs ascending
+                        //  slots, so that one selects on the lone lane -- every other LoadBalancer of the graph keeps the wavefront)
+                        for (int r = 0; r < V.n_rd; ++r) coop = coop && V.rd[r].lb != top.node;
+                        for (int r = 0; r < V.n_cn; ++r) coop = coop && V.cn[r].lb != top.node;
                     }
                     if (coop && !(F && tp.crashed)) { want = top.node; break; }
                 }
@@ -1088,6 +1195,253 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     }
                     H.push(mk(t + ns_from_seconds(p.mean), G++, kEvAsEval, n, -1));   // self.now + Duration.from_seconds(evaluation_interval)
                     polls_pending += 1;
+                    continue;
+                }
+            }
+            if constexpr (DP) {
+                if (e.kind >= kEvCnStart) {
+                    // CanaryDeployer.handle_event (canary_deployer.py:265-280) over the ordered member list, like the rolling deployer's.
+                    GCn &row = V.cn[p.stream_base];
+                    const GParam &lp = c.P[p.target];
+                    GState &ls = c.S[p.target];
+                    int32_t *hl = c.hl_list + lp.rt_off;
+                    uint8_t *mem = V.as_mem + lp.rt_off;
+                    const int canary = p.rt_off;
+                    const bool weighted = lp.sub == HS_LB_WEIGHTED_ROUND_ROBIN || lp.sub == HS_LB_WEIGHTED_LEAST_CONNECTIONS;   // hasattr(strategy, "set_weight")
+                    auto set_weight = [&](int slot, int32_t w) { c.lb_w[lp.rt_off + slot] = w; row.wr[slot] = 1; };
+                    // _reset_weights (:487-494): every backend that is a member NOW (an entry whose word has fallen is about to leave)
+                    auto reset_weights = [&]() {
+                        if (!weighted) return;
+                        for (int q = 0; q < ls.qlen; ++q) if (mem[hl[q]]) set_weight(hl[q], 1);
+                    };
+                    int compact_lb = -1;
+                    auto compact = [&]() {
+                        if (V.rd_coop_min > 0 && ls.qlen >= V.rd_coop_min) { compact_lb = p.target; return; }
+                        ls.qlen = compact_members_lone(hl, mem, ls.qlen);
+                        V.rd_compactions[0] += 1;
+                    };
+                    // the evaluators' figure of one backend (:102-109, :140-143; server.py:176-180)
+                    auto metric = [&](int slot) -> double {
+                        const int be = c.rt_targets[lp.rt_off + slot];
+                        if (row.evaluator == HS_CANARY_LATENCY) {
+                            const long long cnt = V.svc_cnt[be];
+                            return cnt > 0 ? __ddiv_rn(V.svc_sum[be], (double)cnt) : 0.0;
+                        }
+                        const int64_t total = c.S[be].c + c.S[be].d;                // requests_completed + requests_rejected
+                        return total > 0 ? __ddiv_rn((double)c.S[be].d, (double)total) : 0.0;   // (total_failures: no attribute of ServerStats)
+                    };
+                    const int64_t iv_ns = ns_from_seconds(p.mean);
+                    switch (e.kind) {
+                    case kEvCnStart:                                                // _start_deployment (:282-310)
+                        row.n_base = ls.qlen;
+                        for (int q = 0; q < ls.qlen; ++q) row.base[q] = hl[q];
+                        row.has_canary = 1;
+                        if (!mem[canary]) {                                         // add_backend (load_balancer.py:176-216)
+                            mem[canary] = 1;
+                            hl[ls.qlen] = canary;
+                            ls.qlen += 1;
+                            c.rt_taken[lp.rt_off + canary] = 0;
+                            if (weighted) set_weight(canary, 1);
+                        }
+                        row.status = HS_CANARY_IN_PROGRESS; row.cur_stage = 0; row.total_stages = row.n_stages; row.cur_pct = 0.0;
+                        row.started += 1;
+                        H.push(mk(t, G++, kEvCnStage, n, -1));
+                        break;
+                    case kEvCnStage: {                                              // _start_stage (:312-347)
+                        if (row.cur_stage >= row.n_stages) { H.push(mk(t, G++, kEvCnPromote, n, -1)); break; }
+                        const double pct = row.pct[row.cur_stage];
+                        row.cur_pct = pct;
+                        row.stage_start = t; row.has_start = 1;
+                        // _set_traffic_weight (:453-485): two products, a difference and a quotient, each rounded on its own
+                        if (weighted && row.n_base > 0) {
+                            long long cw = 1, bw = 1;
+                            if (!(pct >= 1.0)) {
+                                const double a = __dmul_rn(pct, 100.0);
+                                const double b = __ddiv_rn(__dmul_rn(__dsub_rn(1.0, pct), 100.0), (double)row.n_base);
+                                cw = a >= 2147483647.0 ? 2147483647ll : a <= 1.0 ? 1ll : (long long)a;      // max(1, int(...))
+                                bw = b >= 2147483647.0 ? 2147483647ll : b <= 1.0 ? 1ll : (long long)b;
+                            }
+                            for (int q = 0; q < row.n_base; ++q) set_weight(row.base[q], (int32_t)bw);
+                            set_weight(canary, (int32_t)cw);
+                        }
+                        H.push(mk(t + iv_ns, G++, kEvCnEval, n, -1));
+                    } break;
+                    case kEvCnEval: {                                               // _evaluate (:349-411)
+                        if (row.status != HS_CANARY_IN_PROGRESS) break;
+                        row.ev_performed += 1;
+                        // ErrorRateEvaluator / LatencyEvaluator.is_healthy (:87-100, :123-138): the baseline's plain left-to-right sum
+                        const double x = metric(canary);
+                        bool healthy;
+                        if (x > row.ev_max) healthy = false;
+                        else if (row.n_base == 0) healthy = x <= row.ev_max;
+                        else {
+                            double sum = 0.0;
+                            for (int q = 0; q < row.n_base; ++q) sum = __dadd_rn(sum, metric(row.base[q]));
+                            const double avg = __ddiv_rn(sum, (double)row.n_base);
+                            healthy = avg > 0.0 ? x <= __dmul_rn(avg, row.ev_mult) : x <= row.ev_max;
+                        }
+                        if (!healthy) { row.ev_failed += 1; H.push(mk(t, G++, kEvCnRollback, n, -1)); break; }
+                        row.ev_passed += 1;
+                        if (seconds_from_ns(t - row.stage_start) >= row.period[row.cur_stage]) {
+                            row.stages_completed += 1;
+                            row.cur_stage += 1;
+                            H.push(mk(t, G++, row.cur_stage >= row.n_stages ? kEvCnPromote : kEvCnStage, n, -1));
+                        } else H.push(mk(t + iv_ns, G++, kEvCnEval, n, -1));
+                    } break;
+                    case kEvCnPromote: {                                            // _promote (:413-430): the whole baseline leaves in one pass
+                        row.status = HS_CANARY_PROMOTING;
+                        int gone = 0;
+                        for (int q = 0; q < row.n_base; ++q) if (mem[row.base[q]]) { mem[row.base[q]] = 0; gone += 1; }
+                        reset_weights();
+                        if (gone) compact();
+                        H.push(mk(t, G++, kEvCnComplete, n, -1));
+                    } break;
+                    case kEvCnRollback:                                             // _do_rollback (:432-444)
+                        row.status = HS_CANARY_ROLLED_BACK;
+                        row.rolled_back += 1;
+                        if (row.has_canary && mem[canary]) {
+                            mem[canary] = 0;
+                            reset_weights();
+                            compact();
+                        } else reset_weights();
+                        break;
+                    default:                                                        // _complete (:446-451)
+                        row.status = HS_CANARY_COMPLETED;
+                        row.completed += 1;
+                        break;
+                    }
+                    if (compact_lb >= 0) { want = -2 - compact_lb; break; }
+                    continue;
+                }
+            }
+            if constexpr (DP) {
+                if (e.kind >= kEvRdStart) {
+                    // RollingDeployer.handle_event (rolling_deployer.py:158-175).  The LoadBalancer's `_backends` is its member list in
+                    // INSERTION order (hl_list, GState::qlen of them; under a deployer every member is healthy): add_backend appends,
+                    // remove_backend keeps the order of the rest.
+                    GRd &row = V.rd[p.stream_base];
+                    const GParam &lp = c.P[p.target];
+                    GState &ls = c.S[p.target];
+                    int32_t *hl = c.hl_list + lp.rt_off;
+                    uint8_t *mem = V.as_mem + lp.rt_off;
+                    // add_backend (load_balancer.py:176-216): a name already registered only has its weight updated; a new BackendInfo
+                    // counts from 0 and the strategy's weight becomes 1
+                    auto add = [&](int slot) {
+                        if (mem[slot]) return;
+                        mem[slot] = 1;
+                        hl[ls.qlen] = slot;
+                        ls.qlen += 1;
+                        c.rt_taken[lp.rt_off + slot] = 0;
+                        if (slot < p.rt_off) row.readd[slot] = 1;
+                        c.lb_w[lp.rt_off + slot] = 1;
+                    };
+                    // remove_backend over a whole list (load_balancer.py:218-236): the membership words fall, then ONE pass compacts the
+                    // member list, order kept
+                    // From GVars::rd_coop_min members on the pass belongs to all 64 lanes (below, behind the hand-over): the handler
+                    // ends first -- whatever it appends in the meantime stands behind every entry the pass drops.
+                    int compact_lb = -1;
+                    auto remove_all = [&](const int32_t *list, int cnt, bool may_defer) {
+                        int gone = 0;
+                        for (int k = 0; k < cnt; ++k) if (mem[list[k]]) { mem[list[k]] = 0; gone += 1; }
+                        if (!gone) return;
+                        if (may_defer && V.rd_coop_min > 0 && ls.qlen >= V.rd_coop_min) { compact_lb = p.target; return; }
+                        ls.qlen = compact_members_lone(hl, mem, ls.qlen);
+                        V.rd_compactions[0] += 1;
+                    };
+                    const int64_t iv_ns = ns_from_seconds(p.mean);                  // Duration.from_seconds(health_check_interval)
+                    switch (e.kind) {
+                    case kEvRdStart:                                                // _start_deployment (:177-203)
+                        row.old_head = 0; row.old_n = ls.qlen;
+                        for (int q = 0; q < ls.qlen; ++q) row.old_b[q] = hl[q];
+                        row.new_n = 0;
+                        row.fail_count = 0;
+                        for (int q = 0; q < row.cap; ++q) row.pass[q] = -1;
+                        row.status = HS_DEPLOYMENT_IN_PROGRESS; row.total = ls.qlen; row.replaced = 0; row.failed = 0; row.cur_batch = 0;
+                        row.started += 1;
+                        H.push(mk(t, G++, kEvRdBatch, n, -1));
+                        break;
+                    case kEvRdBatch: {                                              // _replace_batch (:205-257)
+                        const int remaining = row.old_n - row.old_head;
+                        if (remaining == 0) { H.push(mk(t, G++, kEvRdComplete, n, -1)); break; }
+                        const int cnt = row.batch_size < remaining ? row.batch_size : remaining;
+                        if ((long long)row.next_id + cnt > (long long)p.rt_cnt) {   // the host's bound on the pool did not hold:
+                            row.wanted = p.rt_cnt + 1;                              // the first instance of the batch the pool lacks
+                            status |= kPoolOut;
+                            break;
+                        }
+                        row.cur_batch += 1;
+                        for (int k = 0; k < cnt; ++k) row.cur_old[k] = row.old_b[row.old_head + k];
+                        row.cur_old_n = cnt;
+                        row.old_head += cnt;
+                        row.cur_new_n = 0;
+                        for (int k = 0; k < cnt; ++k) {
+                            row.next_id += 1;
+                            const int slot = p.rt_off + row.next_id - 1;
+                            add(slot);
+                            row.cur_new[row.cur_new_n++] = slot;
+                            row.new_b[row.new_n++] = slot;
+                            row.pass[slot] = 0;
+                        }
+                        H.push(mk(t + iv_ns, G++, kEvRdCheck, n, -1));
+                    } break;
+                    case kEvRdCheck:                                                // _run_health_check (:259-304): the only status guard
+                        if (row.status != HS_DEPLOYMENT_IN_PROGRESS) break;
+                        for (int k = 0; k < row.cur_new_n; ++k) {
+                            // the probe -- a `health_check` Event at the new Server, a Request of it in every respect -- and its timeout
+                            const int slot = row.cur_new[k];
+                            row.hc_performed += 1;
+                            int r = req_free;
+                            if (r >= 0) req_free = c.reqs[r].next; else r = req_len++;  // (room: tested in front of the pop)
+                            const unsigned long long idx_p = G++;
+                            GRequest rq; rq.created = t; rq.idx = idx_p; rq.service_s = 0.0; rq.client = (int64_t)slot; rq.next = -1; rq.hook = n; rq.pre = 0;
+                            c.reqs[r] = rq;
+                            const int be = c.rt_targets[lp.rt_off + slot];
+                            H.push(mk(t, idx_p, arrival_kind<R, CL, FL>(c.P, be), be, r));
+                            H.push(mk(t + iv_ns, G++, kEvRdTimeout, n, -2 - slot));
+                        }
+                        break;
+                    case kEvRdPass: {                                               // _handle_health_pass (:306-361)
+                        const int slot = -2 - e.req;
+                        if (row.pass[slot] < 0) break;                              // `server_name not in self._health_pass_count`
+                        row.pass[slot] += 1;
+                        row.hc_passed += 1;
+                        bool all_healthy = true;                                    // all() over an empty batch is true
+                        for (int k = 0; k < row.cur_new_n; ++k) {
+                            const int pc = row.pass[row.cur_new[k]];
+                            if ((pc < 0 ? 0 : pc) < p.conc) { all_healthy = false; break; }
+                        }
+                        if (all_healthy) {
+                            remove_all(row.cur_old, row.cur_old_n, true);
+                            row.replaced += row.cur_old_n;
+                            row.inst_replaced += row.cur_old_n;
+                            H.push(mk(t, G++, kEvRdBatch, n, -1));
+                        } else H.push(mk(t + iv_ns, G++, kEvRdCheck, n, -1));
+                    } break;
+                    case kEvRdTimeout: {                                            // _handle_health_timeout (:363-396)
+                        const int pc = row.pass[-2 - e.req];
+                        if ((pc < 0 ? 0 : pc) >= p.conc) break;
+                        row.fail_count += 1;
+                        row.hc_failed += 1;
+                        row.failed += 1;
+                        if ((int64_t)row.fail_count > p.lim) H.push(mk(t, G++, kEvRdRollback, n, -1));
+                    } break;
+                    case kEvRdRollback: {                                           // _rollback (:398-413)
+                        row.status = HS_DEPLOYMENT_ROLLED_BACK;
+                        row.rolled_back += 1;
+                        // (a backend that comes back is appended at once: the lone lane compacts first -- also where the batch's old
+                        //  backends are instances, which could be among the new ones that leave here)
+                        bool readds = false;
+                        for (int k = 0; k < row.cur_old_n; ++k) readds |= !mem[row.cur_old[k]] || row.cur_old[k] >= p.rt_off;
+                        remove_all(row.new_b, row.new_n, !readds);
+                        for (int k = 0; k < row.cur_old_n; ++k) add(row.cur_old[k]);
+                    } break;
+                    default:                                                        // _complete (:415-424)
+                        row.status = HS_DEPLOYMENT_COMPLETED;
+                        row.completed += 1;
+                        break;
+                    }
+                    if (status != kRunning) break;
+                    if (compact_lb >= 0) { want = -2 - compact_lb; break; }         // (<= -2: the member list of that LoadBalancer, to all lanes)
                     continue;
                 }
             }
@@ -1339,6 +1693,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         c.reqs[e.req].hook = -1;
                         int64_t probe_tag = -1;
                         if (hook >= 0 && c.P[hook].kind == HS_NODE_HEALTH_CHECKER) { probe_tag = c.reqs[e.req].client; c.reqs[e.req].client = -1; }
+                        [[maybe_unused]] int rd_slot = -1;
+                        if constexpr (DP) {
+                            if (hook >= 0 && c.P[hook].kind == HS_NODE_ROLLING_DEPLOYER) { rd_slot = (int)c.reqs[e.req].client; c.reqs[e.req].client = -1; }
+                        }
                         const int64_t hook_id = req_id(c.reqs[e.req]);             // a wrapper's id / a Client's key: read before the stamp
                         if (p.lim >= 0 && s.qlen >= p.lim) {                       // push refuses at capacity
                             s.b += 1;
@@ -1359,7 +1717,8 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                             s.qlen += 1;
                             if (was_empty) H.push(mk(t, G++, HS_EV_NOTIFY, n, -1));
                         }
-                        if (probe_tag >= 0) {
+                        if (DP && rd_slot >= 0) H.push(mk(t, G++, kEvRdPass, hook, -2 - rd_slot));
+                        else if (probe_tag >= 0) {
                             GEvent re = mk(t, G++, kEvHcResp, hook, -2 - (int)(probe_tag & 0xffffffffll));
                             re.pad = (uint32_t)(probe_tag >> 32) << kPadIdShift;
                             H.push(re);
@@ -1462,6 +1821,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if constexpr (HC) {
                     if (hook >= 0 && c.P[hook].kind == HS_NODE_HEALTH_CHECKER) { probe_tag = c.reqs[e.req].client; c.reqs[e.req].client = -1; }
                 }
+                [[maybe_unused]] int rd_slot = -1;                                 // a deployer's probe: the instance's slot rode in `client`
+                if constexpr (DP) {
+                    if (hook >= 0 && c.P[hook].kind == HS_NODE_ROLLING_DEPLOYER) { rd_slot = (int)c.reqs[e.req].client; c.reqs[e.req].client = -1; }
+                }
                 if (p.lim >= 0 && s.qlen >= p.lim) {                               // FIFOQueue.push refuses (queue_policy.py:94-98)
                     s.b += 1;
                     c.reqs[e.req].next = req_free; req_free = e.req;
@@ -1478,7 +1841,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 }
                 // Event.invoke (core/event.py:277-283): the handler returned a plain list, so the completion hooks run now, behind
                 // the handler's own events: the LoadBalancer's `_lb_response`
-                if (HC && probe_tag >= 0) {
+                if (DP && rd_slot >= 0) {
+                    // ... or the deployer's `_rolling_health_pass` (rolling_deployer.py:283-291): a probe the queue refused passes as well
+                    H.push(mk(t, G++, kEvRdPass, hook, -2 - rd_slot));
+                } else if (HC && probe_tag >= 0) {
                     // ... or the checker's _health_check_response (health_check.py:321-334): a probe the queue refused passes as well
                     GEvent re = mk(t, G++, kEvHcResp, hook, -2 - (int)(probe_tag & 0xffffffffll));
                     re.pad = (uint32_t)(probe_tag >> 32) << kPadIdShift;
@@ -1527,6 +1893,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     sv = seconds_from_ns(ns_from_seconds(sample));
                 } else sv = seconds_from_ns(ns_from_seconds(p.mean));
                 c.reqs[e.req].service_s = sv;
+                if constexpr (DP) {
+                    // `_service_times.append(service_time_s)` (server.py:250): what LatencyEvaluator's average reads, in draw order
+                    if (V.svc_sum) { V.svc_sum[n] = __dadd_rn(V.svc_sum[n], sv); V.svc_cnt[n] += 1; }
+                }
                 H.push(mk(t + ns_from_seconds(sv), G++, HS_EV_CONTINUATION, n, e.req));   // Instant + float seconds (temporal.py:222)
             } break;
             case HS_EV_CONTINUATION: {
@@ -1814,7 +2184,21 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
       }
       __syncthreads();
       const int wn = s_want;
+      if constexpr (DP) {
+        if (wn <= -2) {
+            // The member list of LoadBalancer -2 - wn, compacted by membership by all 64 lanes (the lone lane's state is visible behind
+            // the barrier, as for a selection).
+            const int lbn = -2 - wn;
+            const GParam wp = c.P[lbn];
+            const int w = compact_members_wave(c.hl_list + wp.rt_off, V.as_mem + wp.rt_off, c.S[lbn].qlen, lane);
+            if (lane == 0) { c.S[lbn].qlen = w; V.rd_compactions[1] += 1; }
+            __syncthreads();
+            continue;
+        }
+        if (wn == -1) break;
+      } else {
       if (wn < 0) break;
+      }
       {
         // The selection of LoadBalancer `wn` by all 64 lanes: lane l scores slots l, l + 64, ... (ascending, so a lane keeps its first
         // minimum), then a butterfly over the lanes keeps the smaller (score, slot) pair -- the first minimum in add_backend order.  The
@@ -1905,6 +2289,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             V.flow_cancelled += n_flow_cancelled;
         }
         if constexpr (AS) V.as_evals += (long long)s_by_kind[kEvAsEval];
+        if constexpr (DP) {
+            for (int k = 0; k < HS_DEPLOYER_KINDS; ++k) V.rd_by_kind[k] += (long long)s_by_kind[kEvRdStart + k];
+            for (int k = 0; k < HS_CANARY_KINDS; ++k) V.cn_by_kind[k] += (long long)s_by_kind[kEvCnStart + k];
+        }
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
@@ -1974,6 +2362,21 @@ __global__ void __launch_bounds__(64) hs_graph_run_scaler(GCtl c) {           //
     __shared__ GEvent lheap[kLdsHeap];
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
     graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
+}
+
+__global__ void __launch_bounds__(64) hs_graph_run_deploy(GCtl c) {           // ... with a RollingDeployer
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
+}
+
+// hs_debug_compact_members: one list, one wavefront
+__global__ void __launch_bounds__(64) hs_graph_compact_members(int32_t *hl, const uint8_t *mem, int len, int wave, int32_t *out_len) {
+    const int lane = threadIdx.x;
+    int w = 0;
+    if (wave) w = compact_members_wave(hl, mem, len, lane);
+    else if (lane == 0) w = compact_members_lone(hl, mem, len);
+    if (lane == 0) *out_len = w;
 }
 
 // Independent graphs -- the replicas / sweep points of parallel/runner.py:82-142 -- side by side: one workgroup (one heap) each, one
@@ -2058,6 +2461,14 @@ __global__ void __launch_bounds__(64) hs_graph_run_batch_scaler(const GCtl *cs, 
     graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
     batch_report(c, stat);
 }
+// ... of a batch in which at least one handle has a RollingDeployer
+__global__ void __launch_bounds__(64) hs_graph_run_batch_deploy(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
 
 }  // namespace graph
 }  // namespace hs
@@ -2117,6 +2528,22 @@ struct hs_graph {
     std::vector<uint8_t> as_member;            // [n_rt] the initial membership word of every backend slot (0: a dormant pool instance)
     GAs *d_as = nullptr; uint8_t *d_as_mem = nullptr;
     std::vector<int64_t *> d_as_hist;          // every row's history buffer
+    // RollingDeployer: a graph that holds one runs the tenth instantiation; the rows and their lists go to the device with the first
+    // run (the membership words are the scalers': as_member / d_as_mem)
+    int n_deployers = 0;
+    std::vector<GRd> rd_rows;                  // hs_graph_set_rolling_deployer, in call order (GParam::stream_base = the row)
+    std::vector<int32_t> rd_node;              // the deployer node of every row
+    std::vector<int32_t> deployer_of;          // [n] the configured deployer of a LoadBalancer node (-1: none)
+    GRd *d_rd = nullptr;
+    std::vector<int32_t *> d_rd_lists;         // every row's six lists, one allocation
+    // CanaryDeployer: the same instantiation; its rows, the baseline lists and the Servers' service-time sums go to the device with the
+    // first run
+    int n_canaries = 0;
+    std::vector<GCn> cn_rows;                  // hs_graph_set_canary_deployer, in call order (GParam::stream_base = the row)
+    std::vector<int32_t> cn_node;
+    GCn *d_cn = nullptr;
+    std::vector<int32_t *> d_cn_lists;         // every row's two lists, one allocation
+    double *d_svc_sum = nullptr; long long *d_svc_cnt = nullptr;
     int debug_flags = 0;                       // hs_debug_graph_flags
     // tick tables: one row per time-varying Source and per distinct Probe interval, computed up to `tick_horizon`
     std::vector<hs::TickRow> rows;
@@ -2197,10 +2624,16 @@ void hs_graph_destroy(hs_graph *g) {
     (void)hipSetDevice(g->cfg.device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     void *bufs[] = {g->ctl.heap, g->ctl.reqs, g->ctl.rec_node, g->ctl.rec_t, g->ctl.rec_cr, (void *)g->ctl.P, g->ctl.S,
-                    g->d_rt_targets, g->d_key_table, (void *)g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
+                    g->d_rt_targets, g->d_key_table, g->ctl.lb_w, g->ctl.rt_taken, g->d_sched_node, g->d_sched_t, g->ctl.V, g->d_rows, g->d_ticks, g->d_tick_count,
                     g->d_tick_status, g->ctl.lim_ring, g->d_faults, g->d_health, g->d_as, g->d_as_mem, g->ctl.rs_tab, g->d_cl_delays, g->d_sched_id, g->d_qp};
     for (void *b : bufs) if (b && !in_slab(g, b)) (void)hipFree(b);
     for (int64_t *h : g->d_as_hist) if (h) (void)hipFree(h);
+    for (int32_t *l : g->d_rd_lists) if (l) (void)hipFree(l);
+    if (g->d_rd) (void)hipFree(g->d_rd);
+    for (int32_t *l : g->d_cn_lists) if (l) (void)hipFree(l);
+    if (g->d_cn) (void)hipFree(g->d_cn);
+    if (g->d_svc_sum) (void)hipFree(g->d_svc_sum);
+    if (g->d_svc_cnt) (void)hipFree(g->d_svc_cnt);
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
     if (g->ev_a) (void)hipEventDestroy(g->ev_a);
     if (g->ev_b) (void)hipEventDestroy(g->ev_b);
@@ -2432,6 +2865,16 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             if (p.target >= 0 && nd->kind[p.target] != HS_NODE_LB) return fail(nullptr, HS_E_INVALID, "node %d: an AutoScaler's target %d is not a LoadBalancer", i, p.target);
             p.sub = 0; p.conc = 1; p.lim = 10; p.mean = 10.0; p.lat_min = 30.0; p.loss = 60.0; p.rt_off = 0; p.rt_cnt = 0; p.stream_base = 0;
         } break;
+        case HS_NODE_ROLLING_DEPLOYER: {
+            // RollingDeployer (rolling_deployer.py:69-124); its LoadBalancer and parameters: hs_graph_set_rolling_deployer
+            if (p.target >= 0 && nd->kind[p.target] != HS_NODE_LB) return fail(nullptr, HS_E_INVALID, "node %d: a RollingDeployer's target %d is not a LoadBalancer", i, p.target);
+            p.sub = 0; p.conc = 2; p.lim = 1; p.mean = 2.0; p.lat_min = 0.0; p.loss = 0.0; p.rt_off = 0; p.rt_cnt = 0; p.stream_base = 0;
+        } break;
+        case HS_NODE_CANARY_DEPLOYER: {
+            // CanaryDeployer (canary_deployer.py:180-225); its LoadBalancer, stages and evaluator: hs_graph_set_canary_deployer
+            if (p.target >= 0 && nd->kind[p.target] != HS_NODE_LB) return fail(nullptr, HS_E_INVALID, "node %d: a CanaryDeployer's target %d is not a LoadBalancer", i, p.target);
+            p.sub = 0; p.conc = 0; p.lim = 0; p.mean = 5.0; p.lat_min = 0.0; p.loss = 0.0; p.rt_off = 0; p.rt_cnt = 0; p.stream_base = 0;
+        } break;
         default: return fail(nullptr, HS_E_UNSUPPORTED, "node %d: kind %d is not lowered", i, (int)p.kind);
         }
         P[(size_t)i] = p;
@@ -2442,6 +2885,9 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     g->hl_flag.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
     g->checker_of.assign((size_t)n, -1); g->checker_set.assign((size_t)n, 0);
     g->scaler_of.assign((size_t)n, -1);
+    g->deployer_of.assign((size_t)n, -1);
+    for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_ROLLING_DEPLOYER) g->n_deployers++;
+    for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_CANARY_DEPLOYER) g->n_canaries++;
     g->as_member.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
     for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_AUTO_SCALER) g->n_scalers++;
     g->lb_w.assign((size_t)(nd->n_rt > 0 ? nd->n_rt : 1), 1);
@@ -2509,7 +2955,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     c.rt_targets = g->d_rt_targets;
     g->d_key_table = key_table.empty() ? nullptr : reinterpret_cast<int32_t *>(g->slab + o_key);
     c.key_table = g->d_key_table;
-    c.lb_w = reinterpret_cast<const int32_t *>(g->slab + o_w);
+    c.lb_w = reinterpret_cast<int32_t *>(g->slab + o_w);
     c.rt_taken = reinterpret_cast<long long *>(g->slab + o_taken);
     c.V = reinterpret_cast<GVars *>(g->slab + o_V);
     if (!rows.empty()) {
@@ -2560,7 +3006,7 @@ int hs_graph_set_lb_weights(hs_graph *g, int32_t node, const int32_t *weights, i
     }
     if (n > 0) {
         std::copy(weights, weights + n, g->lb_w.begin() + p.rt_off);
-        HS_HIP(g, hipMemcpy(const_cast<int32_t *>(g->ctl.lb_w) + p.rt_off, weights, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(g->ctl.lb_w + p.rt_off, weights, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     return HS_OK;
 }
@@ -2734,6 +3180,9 @@ int hs_graph_set_health_checker(hs_graph *g, int32_t node, int32_t lb_node, doub
     if (g->scaler_of[(size_t)lb_node] >= 0)
         return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has AutoScaler node %d: a HealthChecker and an AutoScaler on one LoadBalancer are not lowered", lb_node,
                     g->scaler_of[(size_t)lb_node]);
+    if (g->deployer_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has RollingDeployer node %d: a HealthChecker and a deployer on one LoadBalancer are not lowered", lb_node,
+                    g->deployer_of[(size_t)lb_node]);
     const uint8_t strat = g->params[(size_t)lb_node].sub;
     if (strat == HS_LB_CONSISTENT_HASH || strat == HS_LB_IP_HASH || strat == HS_LB_RANDOM)
         return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: strategy %d is not lowered over a changing backend list (under a HealthChecker)", lb_node, (int)strat);
@@ -3135,6 +3584,9 @@ int hs_graph_set_auto_scaler(hs_graph *g, int32_t node, int32_t lb_node, int32_t
     if (g->checker_of[(size_t)lb_node] >= 0)
         return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has HealthChecker node %d: a HealthChecker and an AutoScaler on one LoadBalancer are not lowered",
                     lb_node, g->checker_of[(size_t)lb_node]);
+    if (g->deployer_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has RollingDeployer node %d: an AutoScaler and a deployer on one LoadBalancer are not lowered", lb_node,
+                    g->deployer_of[(size_t)lb_node]);
     const GParam &lp = g->params[(size_t)lb_node];
     if (lp.sub == HS_LB_CONSISTENT_HASH || lp.sub == HS_LB_IP_HASH || lp.sub == HS_LB_RANDOM)
         return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: strategy %d is not lowered over a changing backend list (under an AutoScaler)", lb_node, (int)lp.sub);
@@ -3207,6 +3659,233 @@ int hs_graph_get_auto_scaler(hs_graph *g, int32_t node, int64_t *state, int64_t 
         else std::copy(g->as_member.begin() + lp.rt_off, g->as_member.begin() + lp.rt_off + lp.rt_cnt, member);
     }
     return HS_OK;
+}
+
+int hs_graph_set_rolling_deployer(hs_graph *g, int32_t node, int32_t lb_node, int32_t batch_size, double interval_s, int32_t healthy_threshold,
+                                  int64_t max_failures, int32_t n_pool) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_ROLLING_DEPLOYER)
+        return fail(g, HS_E_INVALID, "set_rolling_deployer: node %d is not a RollingDeployer", node);
+    if (lb_node < 0 || lb_node >= g->n || g->params[(size_t)lb_node].kind != HS_NODE_LB)
+        return fail(g, HS_E_INVALID, "set_rolling_deployer: node %d is not a LoadBalancer", lb_node);
+    if (g->ran || g->launches > 0 || g->d_health || g->d_rd) return fail(g, HS_E_STATE, "set_rolling_deployer: a deployer is configured before the first run");
+    for (int32_t a : g->rd_node) if (a == node) return fail(g, HS_E_STATE, "set_rolling_deployer: node %d is configured already", node);
+    if (g->deployer_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has RollingDeployer node %d already: one deployer per LoadBalancer is lowered", lb_node,
+                    g->deployer_of[(size_t)lb_node]);
+    if (g->scaler_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has AutoScaler node %d: an AutoScaler and a deployer on one LoadBalancer are not lowered", lb_node,
+                    g->scaler_of[(size_t)lb_node]);
+    if (g->checker_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has HealthChecker node %d: a HealthChecker and a deployer on one LoadBalancer are not lowered",
+                    lb_node, g->checker_of[(size_t)lb_node]);
+    const GParam &lp = g->params[(size_t)lb_node];
+    if (lp.sub != HS_LB_ROUND_ROBIN && lp.sub != HS_LB_WEIGHTED_ROUND_ROBIN && lp.sub != HS_LB_LEAST_CONNECTIONS && lp.sub != HS_LB_WEIGHTED_LEAST_CONNECTIONS)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: strategy %d is not lowered over a changing backend list (under a deployer)", lb_node, (int)lp.sub);
+    if (batch_size < 1) return fail(g, HS_E_INVALID, "batch_size must be at least 1, got %d", batch_size);
+    if (healthy_threshold < 1) return fail(g, HS_E_INVALID, "healthy_threshold must be at least 1, got %d", healthy_threshold);
+    if (!std::isfinite(interval_s) || !(interval_s * 1e9 >= 1.0))
+        return fail(g, HS_E_UNSUPPORTED, "a health_check_interval of %g s is below one nanosecond or not finite", interval_s);
+    if (n_pool < 0 || n_pool > HS_DEPLOYER_MAX_POOL) return fail(g, HS_E_UNSUPPORTED, "a pool of %d instances is beyond the %d of one deployer", n_pool, HS_DEPLOYER_MAX_POOL);
+    if (n_pool > lp.rt_cnt) return fail(g, HS_E_INVALID, "set_rolling_deployer: LoadBalancer node %d has %d targets, fewer than the pool's %d", lb_node, lp.rt_cnt, n_pool);
+    for (int q = 0; q < lp.rt_cnt - n_pool; ++q)
+        if (!g->hl_flag[(size_t)lp.rt_off + (size_t)q])
+            return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: backend %d is marked unhealthy under a deployer (not lowered)", lb_node, q);
+    GRd row{};
+    row.cap = lp.rt_cnt; row.batch_size = batch_size; row.lb = lb_node;
+    GParam &p = g->params[(size_t)node];
+    p.target = lb_node; p.mean = interval_s; p.conc = healthy_threshold; p.lim = max_failures; p.rt_off = lp.rt_cnt - n_pool; p.rt_cnt = n_pool;
+    p.stream_base = (uint64_t)g->rd_rows.size();
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    for (int q = lp.rt_cnt - n_pool; q < lp.rt_cnt; ++q) g->as_member[(size_t)lp.rt_off + (size_t)q] = 0;
+    g->rd_rows.push_back(row); g->rd_node.push_back(node);
+    g->deployer_of[(size_t)lb_node] = node;
+    g->reach_s = std::max(g->reach_s, interval_s);
+    g->health = true;                          // (the member list is the healthy list of the health lowering)
+    return HS_OK;
+}
+
+int hs_graph_get_rolling_deployer(hs_graph *g, int32_t node, int64_t *state, int32_t *lists, int32_t *members, int32_t *pass, int32_t *readded,
+                                  int64_t *events) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (events) {
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        for (int k = 0; k < HS_DEPLOYER_KINDS; ++k) events[k] = v.rd_by_kind[k];
+        events[HS_DEPLOYER_KINDS] = v.rd_compactions[0]; events[HS_DEPLOYER_KINDS + 1] = v.rd_compactions[1];
+    }
+    if (node == -1 && !state && !lists && !members && !pass && !readded) return HS_OK;
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_ROLLING_DEPLOYER)
+        return fail(g, HS_E_INVALID, "get_rolling_deployer: node %d is not a RollingDeployer", node);
+    const GParam &np = g->params[(size_t)node];
+    size_t r = 0;
+    while (r < g->rd_node.size() && g->rd_node[r] != node) ++r;
+    if (r == g->rd_node.size()) return fail(g, HS_E_STATE, "get_rolling_deployer: RollingDeployer node %d was never configured", node);
+    const GParam &lp = g->params[(size_t)np.target];
+    const size_t cap = (size_t)lp.rt_cnt;
+    GRd row = g->rd_rows[r];
+    GState ls{};
+    std::vector<int32_t> all(6 * std::max<size_t>(cap, 1), -1), hl(std::max<size_t>(cap, 1), 0);
+    if (g->d_rd) {
+        HS_HIP(g, hipMemcpy(&row, g->d_rd + r, sizeof row, hipMemcpyDeviceToHost));
+        HS_HIP(g, hipMemcpy(&ls, g->ctl.S + np.target, sizeof ls, hipMemcpyDeviceToHost));
+        if (cap) HS_HIP(g, hipMemcpy(all.data(), g->d_rd_lists[r], 6 * cap * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (cap) HS_HIP(g, hipMemcpy(hl.data(), g->ctl.hl_list + lp.rt_off, cap * sizeof(int32_t), hipMemcpyDeviceToHost));
+    } else {
+        ls.qlen = lp.rt_cnt - np.rt_cnt;
+        for (int q = 0; q < ls.qlen; ++q) hl[(size_t)q] = q;
+    }
+    if (state) {
+        const int64_t out[HS_DEPLOYER_FIELDS] = {row.started, row.completed, row.rolled_back, row.inst_replaced, row.hc_performed, row.hc_passed, row.hc_failed,
+                                                 row.status, row.total, row.replaced, row.failed, row.cur_batch, row.next_id, row.fail_count,
+                                                 row.old_n - row.old_head, row.new_n, row.cur_old_n, row.cur_new_n, ls.qlen, 0};
+        std::copy(out, out + HS_DEPLOYER_FIELDS, state);
+    }
+    if (lists && cap) {
+        std::fill(lists, lists + 4 * cap, -1);
+        std::copy(all.begin() + row.old_head, all.begin() + row.old_n, lists);
+        std::copy(all.begin() + cap, all.begin() + cap + row.new_n, lists + cap);
+        std::copy(all.begin() + 2 * cap, all.begin() + 2 * cap + row.cur_old_n, lists + 2 * cap);
+        std::copy(all.begin() + 3 * cap, all.begin() + 3 * cap + row.cur_new_n, lists + 3 * cap);
+    }
+    if (members && cap) { std::fill(members, members + cap, -1); std::copy(hl.begin(), hl.begin() + ls.qlen, members); }
+    if (pass && cap) std::copy(all.begin() + 4 * cap, all.begin() + 5 * cap, pass);
+    if (readded && cap) for (size_t q = 0; q < cap; ++q) readded[q] = all[5 * cap + q] > 0 ? 1 : 0;
+    return HS_OK;
+}
+
+int hs_graph_set_canary_deployer(hs_graph *g, int32_t node, int32_t lb_node, int32_t n_stages, const double *traffic_percentage,
+                                 const double *evaluation_period, int32_t evaluator, double ev_max, double ev_multiplier, double interval_s) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_CANARY_DEPLOYER)
+        return fail(g, HS_E_INVALID, "set_canary_deployer: node %d is not a CanaryDeployer", node);
+    if (lb_node < 0 || lb_node >= g->n || g->params[(size_t)lb_node].kind != HS_NODE_LB)
+        return fail(g, HS_E_INVALID, "set_canary_deployer: node %d is not a LoadBalancer", lb_node);
+    if (g->ran || g->launches > 0 || g->d_health || g->d_cn) return fail(g, HS_E_STATE, "set_canary_deployer: a deployer is configured before the first run");
+    for (int32_t a : g->cn_node) if (a == node) return fail(g, HS_E_STATE, "set_canary_deployer: node %d is configured already", node);
+    if (g->deployer_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has deployer node %d already: one deployer per LoadBalancer is lowered", lb_node,
+                    g->deployer_of[(size_t)lb_node]);
+    if (g->scaler_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has AutoScaler node %d: an AutoScaler and a deployer on one LoadBalancer are not lowered", lb_node,
+                    g->scaler_of[(size_t)lb_node]);
+    if (g->checker_of[(size_t)lb_node] >= 0)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d has HealthChecker node %d: a HealthChecker and a deployer on one LoadBalancer are not lowered",
+                    lb_node, g->checker_of[(size_t)lb_node]);
+    const GParam &lp = g->params[(size_t)lb_node];
+    if (lp.sub != HS_LB_ROUND_ROBIN && lp.sub != HS_LB_WEIGHTED_ROUND_ROBIN && lp.sub != HS_LB_LEAST_CONNECTIONS && lp.sub != HS_LB_WEIGHTED_LEAST_CONNECTIONS)
+        return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: strategy %d is not lowered over a changing backend list (under a deployer)", lb_node, (int)lp.sub);
+    if (n_stages < 1 || n_stages > HS_CANARY_MAX_STAGES || !traffic_percentage || !evaluation_period)
+        return fail(g, HS_E_UNSUPPORTED, "a CanaryDeployer with %d stages: 1 .. %d are lowered", n_stages, HS_CANARY_MAX_STAGES);
+    for (int k = 0; k < n_stages; ++k)
+        if (!std::isfinite(traffic_percentage[k]) || !std::isfinite(evaluation_period[k]))
+            return fail(g, HS_E_INVALID, "set_canary_deployer: stage %d has a traffic_percentage or evaluation_period that is no finite number", k);
+    if (evaluator != HS_CANARY_ERROR_RATE && evaluator != HS_CANARY_LATENCY) return fail(g, HS_E_UNSUPPORTED, "metric evaluator %d is not lowered", evaluator);
+    if (std::isnan(ev_max) || std::isnan(ev_multiplier)) return fail(g, HS_E_INVALID, "set_canary_deployer: an evaluator parameter is no number");
+    if (!std::isfinite(interval_s) || !(interval_s * 1e9 >= 1.0))
+        return fail(g, HS_E_UNSUPPORTED, "an evaluation_interval of %g s is below one nanosecond or not finite", interval_s);
+    if (lp.rt_cnt < 1) return fail(g, HS_E_INVALID, "set_canary_deployer: LoadBalancer node %d has no target for the canary", lb_node);
+    for (int q = 0; q < lp.rt_cnt - 1; ++q)
+        if (!g->hl_flag[(size_t)lp.rt_off + (size_t)q])
+            return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: backend %d is marked unhealthy under a deployer (not lowered)", lb_node, q);
+    GCn row{};
+    row.cap = lp.rt_cnt; row.lb = lb_node; row.n_stages = n_stages; row.evaluator = evaluator; row.ev_max = ev_max; row.ev_mult = ev_multiplier;
+    for (int k = 0; k < n_stages; ++k) { row.pct[k] = traffic_percentage[k]; row.period[k] = evaluation_period[k]; }
+    GParam &p = g->params[(size_t)node];
+    p.target = lb_node; p.mean = interval_s; p.rt_off = lp.rt_cnt - 1; p.rt_cnt = 1; p.stream_base = (uint64_t)g->cn_rows.size();
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    g->as_member[(size_t)lp.rt_off + (size_t)lp.rt_cnt - 1] = 0;
+    g->cn_rows.push_back(row); g->cn_node.push_back(node);
+    g->deployer_of[(size_t)lb_node] = node;
+    g->reach_s = std::max(g->reach_s, interval_s);
+    g->health = true;                          // (the member list is the healthy list of the health lowering)
+    return HS_OK;
+}
+
+int hs_graph_get_canary_deployer(hs_graph *g, int32_t node, int64_t *state, double *traffic_pct, int32_t *baseline, int32_t *members,
+                                 int32_t *weights, int32_t *weight_set, double *service_sum, int64_t *service_count, int64_t *events) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (events) {
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        for (int k = 0; k < HS_CANARY_KINDS; ++k) events[k] = v.cn_by_kind[k];
+    }
+    if (node == -1) return HS_OK;
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_CANARY_DEPLOYER)
+        return fail(g, HS_E_INVALID, "get_canary_deployer: node %d is not a CanaryDeployer", node);
+    const GParam &np = g->params[(size_t)node];
+    size_t r = 0;
+    while (r < g->cn_node.size() && g->cn_node[r] != node) ++r;
+    if (r == g->cn_node.size()) return fail(g, HS_E_STATE, "get_canary_deployer: CanaryDeployer node %d was never configured", node);
+    const GParam &lp = g->params[(size_t)np.target];
+    const size_t cap = (size_t)lp.rt_cnt;
+    GCn row = g->cn_rows[r];
+    GState ls{};
+    std::vector<int32_t> all(2 * cap, -1), hl(cap, 0);
+    if (g->d_cn) {
+        HS_HIP(g, hipMemcpy(&row, g->d_cn + r, sizeof row, hipMemcpyDeviceToHost));
+        HS_HIP(g, hipMemcpy(&ls, g->ctl.S + np.target, sizeof ls, hipMemcpyDeviceToHost));
+        HS_HIP(g, hipMemcpy(all.data(), g->d_cn_lists[r], 2 * cap * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HS_HIP(g, hipMemcpy(hl.data(), g->ctl.hl_list + lp.rt_off, cap * sizeof(int32_t), hipMemcpyDeviceToHost));
+    } else {
+        ls.qlen = lp.rt_cnt - 1;
+        for (int q = 0; q < ls.qlen; ++q) hl[(size_t)q] = q;
+    }
+    if (state) {
+        const int64_t out[HS_CANARY_FIELDS] = {row.started, row.completed, row.rolled_back, row.stages_completed, row.ev_performed, row.ev_passed, row.ev_failed,
+                                               row.status, row.cur_stage, row.total_stages, row.has_canary, row.has_start ? row.stage_start : -1,
+                                               row.n_base, ls.qlen, row.has_start, 0};
+        std::copy(out, out + HS_CANARY_FIELDS, state);
+    }
+    if (traffic_pct) *traffic_pct = row.cur_pct;
+    if (baseline) { std::fill(baseline, baseline + cap, -1); std::copy(all.begin(), all.begin() + row.n_base, baseline); }
+    if (members) { std::fill(members, members + cap, -1); std::copy(hl.begin(), hl.begin() + ls.qlen, members); }
+    if (weight_set) for (size_t q = 0; q < cap; ++q) weight_set[q] = all[cap + q] > 0 ? 1 : 0;
+    if (weights) {
+        if (g->d_cn) HS_HIP(g, hipMemcpy(weights, g->ctl.lb_w + lp.rt_off, cap * sizeof(int32_t), hipMemcpyDeviceToHost));
+        else std::copy(g->lb_w.begin() + lp.rt_off, g->lb_w.begin() + lp.rt_off + lp.rt_cnt, weights);
+    }
+    std::vector<int32_t> tg(cap, 0);
+    if ((service_sum || service_count) && cap) HS_HIP(g, hipMemcpy(tg.data(), g->d_rt_targets + lp.rt_off, cap * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (size_t q = 0; q < cap && (service_sum || service_count); ++q) {
+        const int be = tg[q];
+        double sum = 0.0; long long cnt = 0;
+        if (g->d_svc_sum) {
+            HS_HIP(g, hipMemcpy(&sum, g->d_svc_sum + be, sizeof sum, hipMemcpyDeviceToHost));
+            HS_HIP(g, hipMemcpy(&cnt, g->d_svc_cnt + be, sizeof cnt, hipMemcpyDeviceToHost));
+        }
+        if (service_sum) service_sum[q] = sum;
+        if (service_count) service_count[q] = cnt;
+    }
+    return HS_OK;
+}
+
+int hs_debug_compact_members(int32_t device, int32_t n_slots, int32_t len, int32_t *list, const uint8_t *member, int32_t wave, int32_t *out_len) {
+    if (n_slots < 0 || len < 0 || len > n_slots || !out_len || (len > 0 && (!list || !member))) return HS_E_INVALID;
+    for (int q = 0; q < len; ++q) if (list[q] < 0 || list[q] >= n_slots) return HS_E_INVALID;
+    *out_len = 0;
+    if (len == 0) return HS_OK;
+    if (hipSetDevice(device) != hipSuccess) return HS_E_HIP;
+    int32_t *d_list = nullptr, *d_len = nullptr;
+    uint8_t *d_mem = nullptr;
+    int rc = HS_OK;
+    if (hipMalloc(&d_list, (size_t)len * sizeof(int32_t)) != hipSuccess || hipMalloc(&d_mem, (size_t)n_slots) != hipSuccess ||
+        hipMalloc(&d_len, sizeof(int32_t)) != hipSuccess) rc = HS_E_HIP;
+    if (rc == HS_OK && (hipMemcpy(d_list, list, (size_t)len * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(d_mem, member, (size_t)n_slots, hipMemcpyHostToDevice) != hipSuccess)) rc = HS_E_HIP;
+    if (rc == HS_OK) {
+        hipLaunchKernelGGL(hs::graph::hs_graph_compact_members, dim3(1), dim3(64), 0, nullptr, d_list, d_mem, len, wave ? 1 : 0, d_len);
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out_len, d_len, sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(list, d_list, (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = HS_E_HIP;
+    }
+    if (d_list) (void)hipFree(d_list);
+    if (d_mem) (void)hipFree(d_mem);
+    if (d_len) (void)hipFree(d_len);
+    return rc;
 }
 
 int hs_graph_add_fault(hs_graph *g, int32_t node, int64_t time_ns, int32_t on, int32_t cancelled) {
@@ -3420,6 +4099,69 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, as), &g->d_as, sizeof g->d_as, hipMemcpyHostToDevice));
         HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, as_mem), &g->d_as_mem, sizeof g->d_as_mem, hipMemcpyHostToDevice));
     }
+    if (g->n_deployers > 0 && !g->d_rd) {
+        // the deployers' rows, their lists and the membership words, once; the device finds them through GVars
+        if ((int)g->rd_rows.size() != g->n_deployers)
+            return fail(g, HS_E_STATE, "a RollingDeployer without its LoadBalancer (hs_graph_set_rolling_deployer comes before the run)");
+        for (int i = 0; i < g->n; ++i) {
+            const GParam &p = g->params[(size_t)i];
+            if (p.kind != HS_NODE_LB || g->deployer_of[(size_t)i] < 0) continue;
+            for (int q = 0; q < p.rt_cnt; ++q)
+                if (!g->hl_flag[(size_t)p.rt_off + (size_t)q])
+                    return fail(g, HS_E_UNSUPPORTED, "LoadBalancer node %d: backend %d is marked unhealthy under a deployer (not lowered)", i, q);
+        }
+        HS_HIP(g, hipSetDevice(g->cfg.device));
+        for (GRd &row : g->rd_rows) {
+            const size_t cap = (size_t)std::max(row.cap, 1);
+            int32_t *l = nullptr;
+            HS_HIP(g, hipMalloc(&l, 6 * cap * sizeof(int32_t)));
+            HS_HIP(g, hipMemset(l, 0xff, 6 * cap * sizeof(int32_t)));
+            g->d_rd_lists.push_back(l);
+            row.old_b = l; row.new_b = l + cap; row.cur_old = l + 2 * cap; row.cur_new = l + 3 * cap; row.pass = l + 4 * cap; row.readd = l + 5 * cap;
+        }
+        HS_HIP(g, hipMalloc(&g->d_rd, g->rd_rows.size() * sizeof(GRd)));
+        HS_HIP(g, hipMemcpy(g->d_rd, g->rd_rows.data(), g->rd_rows.size() * sizeof(GRd), hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, rd), &g->d_rd, sizeof g->d_rd, hipMemcpyHostToDevice));
+        const int n_rd = (int)g->rd_rows.size();
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, n_rd), &n_rd, sizeof n_rd, hipMemcpyHostToDevice));
+        if (!g->d_as_mem) {
+            const size_t nrt = (size_t)(g->n_rt > 0 ? g->n_rt : 1);
+            HS_HIP(g, hipMalloc(&g->d_as_mem, nrt));
+            HS_HIP(g, hipMemcpy(g->d_as_mem, g->as_member.data(), nrt, hipMemcpyHostToDevice));
+            HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, as_mem), &g->d_as_mem, sizeof g->d_as_mem, hipMemcpyHostToDevice));
+        }
+    }
+    if (g->n_canaries > 0 && !g->d_cn) {
+        // the canary deployers' rows, their lists, the Servers' service-time sums and the membership words, once
+        if ((int)g->cn_rows.size() != g->n_canaries)
+            return fail(g, HS_E_STATE, "a CanaryDeployer without its LoadBalancer (hs_graph_set_canary_deployer comes before the run)");
+        HS_HIP(g, hipSetDevice(g->cfg.device));
+        for (GCn &row : g->cn_rows) {
+            const size_t cap = (size_t)std::max(row.cap, 1);
+            int32_t *l = nullptr;
+            HS_HIP(g, hipMalloc(&l, 2 * cap * sizeof(int32_t)));
+            HS_HIP(g, hipMemset(l, 0xff, 2 * cap * sizeof(int32_t)));
+            g->d_cn_lists.push_back(l);
+            row.base = l; row.wr = l + cap;
+        }
+        HS_HIP(g, hipMalloc(&g->d_cn, g->cn_rows.size() * sizeof(GCn)));
+        HS_HIP(g, hipMemcpy(g->d_cn, g->cn_rows.data(), g->cn_rows.size() * sizeof(GCn), hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, cn), &g->d_cn, sizeof g->d_cn, hipMemcpyHostToDevice));
+        const int n_cn = (int)g->cn_rows.size();
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, n_cn), &n_cn, sizeof n_cn, hipMemcpyHostToDevice));
+        HS_HIP(g, hipMalloc(&g->d_svc_sum, (size_t)g->n * sizeof(double)));
+        HS_HIP(g, hipMemset(g->d_svc_sum, 0, (size_t)g->n * sizeof(double)));
+        HS_HIP(g, hipMalloc(&g->d_svc_cnt, (size_t)g->n * sizeof(long long)));
+        HS_HIP(g, hipMemset(g->d_svc_cnt, 0, (size_t)g->n * sizeof(long long)));
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, svc_sum), &g->d_svc_sum, sizeof g->d_svc_sum, hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, svc_cnt), &g->d_svc_cnt, sizeof g->d_svc_cnt, hipMemcpyHostToDevice));
+        if (!g->d_as_mem) {
+            const size_t nrt = (size_t)(g->n_rt > 0 ? g->n_rt : 1);
+            HS_HIP(g, hipMalloc(&g->d_as_mem, nrt));
+            HS_HIP(g, hipMemcpy(g->d_as_mem, g->as_member.data(), nrt, hipMemcpyHostToDevice));
+            HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, as_mem), &g->d_as_mem, sizeof g->d_as_mem, hipMemcpyHostToDevice));
+        }
+    }
     if (g->health && !g->d_health) {
         // health state, once: flags, healthy lists, current weights and the checkers' per-backend state in one allocation; the
         // LoadBalancers' rows get their healthy count and their two mark counters
@@ -3512,6 +4254,10 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
     c.auto_term = end_ns == (1ll << 61);                   // end_time = Infinity: the limiters' polls are daemons (core/simulation.py:306-322)
     c.coop_min = !(g->has_least_loaded || (g->health && g->has_wrr)) || (g->debug_flags & 1) ? 0 : (g->debug_flags & 2) ? 1 : kCoopMinBackends;
     c.coop_reset = 1;                                      // (hs_graph_coop_selects counts the LAST run: zeroed by its first launch)
+    if (g->n_deployers + g->n_canaries > 0) {              // where a member list is compacted behind a removal (hs_debug_graph_flags)
+        const int rd_min = (g->debug_flags & 1) ? 0 : (g->debug_flags & 2) ? 1 : kCoopMinBackends;
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, rd_coop_min), &rd_min, sizeof rd_min, hipMemcpyHostToDevice));
+    }
     g->launches = 0;
     return HS_OK;
 }
@@ -3600,6 +4346,14 @@ static int after_launch_with(hs_graph *g, int status, long long processed, bool 
         const int rc = grow_tables(g);
         if (rc) return rc;
     }
+    if ((v.status & kPoolOut) && g->d_rd) {
+        std::vector<GRd> rows(g->rd_rows.size());
+        HS_HIP(g, hipMemcpy(rows.data(), g->d_rd, rows.size() * sizeof(GRd), hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < rows.size(); ++r)
+            if (rows[r].wanted)
+                return fail(g, HS_E_OVERFLOW, "RollingDeployer node %d needs instance %d, beyond its pool of %d instances (the pool's bound did not hold)",
+                            g->rd_node[r], rows[r].wanted, g->params[(size_t)g->rd_node[r]].rt_cnt);
+    }
     if (v.status & kPoolOut) {
         std::vector<GAs> rows(g->as_rows.size());
         HS_HIP(g, hipMemcpy(rows.data(), g->d_as, rows.size() * sizeof(GAs), hipMemcpyDeviceToHost));
@@ -3642,7 +4396,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (g->n_deployers + g->n_canaries > 0) hipLaunchKernelGGL(hs_graph_run_deploy, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, g->ctl);
@@ -3704,7 +4459,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
         for (int i : pending) any_link_faults |= gs[i]->n_link_faults > 0;
         bool any_scalers = false;
         for (int i : pending) any_scalers |= gs[i]->n_scalers > 0;
-        if (any_scalers) hipLaunchKernelGGL(hs_graph_run_batch_scaler, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_deployers = false;
+        for (int i : pending) any_deployers |= gs[i]->n_deployers + gs[i]->n_canaries > 0;
+        if (any_deployers) hipLaunchKernelGGL(hs_graph_run_batch_deploy, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else if (any_scalers) hipLaunchKernelGGL(hs_graph_run_batch_scaler, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_link_faults) hipLaunchKernelGGL(hs_graph_run_batch_link_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_queues) hipLaunchKernelGGL(hs_graph_run_batch_queues, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_flows) hipLaunchKernelGGL(hs_graph_run_batch_flow, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
@@ -3779,7 +4537,8 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count; one.rs_tab = g->ctl.rs_tab;
-        if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, one);
+        if (g->n_deployers + g->n_canaries > 0) hipLaunchKernelGGL(hs_graph_run_deploy, dim3(1), dim3(64), 0, g->stream, one);
+        else if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, one);
         else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, one);

@@ -2286,6 +2286,248 @@ class AutoScaler(Entity):
         return self._pool[k - 1]
 
 
+# ---- rolling deployment --------------------------------------------------------------------------
+# components/deployment/rolling_deployer.py.  Inside a Simulation the handlers run on the device (csrc/hs_graph.hip kEvRdStart ..).
+@dataclass
+class DeploymentState:
+    """rolling_deployer.py:30-38."""
+
+    status: str = "idle"  # idle, in_progress, completed, rolled_back
+    total_instances: int = 0
+    replaced: int = 0
+    failed: int = 0
+    current_batch: int = 0
+
+
+@dataclass(frozen=True)
+class RollingDeployerStats:
+    """rolling_deployer.py:41-51."""
+
+    deployments_started: int = 0
+    deployments_completed: int = 0
+    deployments_rolled_back: int = 0
+    instances_replaced: int = 0
+    health_checks_performed: int = 0
+    health_checks_passed: int = 0
+    health_checks_failed: int = 0
+
+
+class RollingDeployer(Entity):
+    """Replaces the backends of a LoadBalancer batch by batch with instances `{name}_v2_{k}` from `server_factory`, health-checking
+    every new instance before the old ones of its batch leave, and rolls back after more than `max_failures` failed checks
+    (components/deployment/rolling_deployer.py:54-424).  The handlers run on the device (csrc/hs_graph.hip kEvRdStart ..).  The
+    device cannot call the factory, so the Simulation calls it up front, when it lowers the graph, for a pool of P instances -- a bound
+    on what the scheduled deploy() Events can create -- and lowers them as dormant Servers; this class carries the
+    parameters in and the statistics, state and lists back out."""
+
+    MAX_POOL = 4096                  # include/hs_engine.h HS_DEPLOYER_MAX_POOL
+
+    def __init__(self, name: str, load_balancer: LoadBalancer, server_factory, batch_size: int = 1, health_check_interval: float = 2.0,
+                 healthy_threshold: int = 2, max_failures: int = 1):
+        super().__init__(name)
+        self._load_balancer = load_balancer
+        self._server_factory = server_factory
+        self._batch_size = batch_size
+        self._health_check_interval = health_check_interval
+        self._healthy_threshold = healthy_threshold
+        self._max_failures = max_failures
+        self._old_backends: list[Entity] = []
+        self._new_backends: list[Entity] = []
+        self._current_batch_old: list[Entity] = []
+        self._current_batch_new: list[Entity] = []
+        self._health_pass_count: dict[str, int] = {}
+        self._health_fail_count = 0
+        self._next_instance_id = 0
+        self._deployments_started = 0
+        self._deployments_completed = 0
+        self._deployments_rolled_back = 0
+        self._instances_replaced = 0
+        self._health_checks_performed = 0
+        self._health_checks_passed = 0
+        self._health_checks_failed = 0
+        self.state = DeploymentState()
+        self._sim_start: Instant | None = None           # the clock a Simulation hands to its entities: `now` before run() is its start
+        self._pool: list[Entity] = []                    # the factory's results for instances 1 .. len(_pool), made when a graph is lowered
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._load_balancer] + list(self._old_backends) + list(self._new_backends)
+
+    @property
+    def stats(self) -> RollingDeployerStats:
+        return RollingDeployerStats(self._deployments_started, self._deployments_completed, self._deployments_rolled_back,
+                                    self._instances_replaced, self._health_checks_performed, self._health_checks_passed,
+                                    self._health_checks_failed)
+
+    @property
+    def load_balancer(self) -> LoadBalancer:
+        return self._load_balancer
+
+    def deploy(self):
+        """rolling_deployer.py:145-156: the `_rolling_deploy_start` Event for `sim.schedule(...)`, no daemon; its time is the
+        Simulation's start once the deployer is one of its entities, Instant.Epoch before.  The caller may set another time."""
+        from .core.event import Event
+
+        return Event(time=self._sim_start if self._sim_start is not None else Instant.Epoch, event_type="_rolling_deploy_start",
+                     target=self, context={})
+
+    def _instance(self, k: int) -> Entity:
+        """Instance k of the pool (1-based), from the factory the first time it is asked for."""
+        while len(self._pool) < k:
+            self._pool.append(self._server_factory(f"{self.name}_v2_{len(self._pool) + 1}"))
+        return self._pool[k - 1]
+
+
+# ---- canary deployment ---------------------------------------------------------------------------
+# components/deployment/canary_deployer.py.  Inside a Simulation the handlers and the evaluators run on the device (csrc/hs_graph.hip
+# kEvCnStart ..); `is_healthy` here is the reference's expression over host objects, for an evaluator used on its own.
+@dataclass
+class CanaryStage:
+    """canary_deployer.py:36-46."""
+
+    traffic_percentage: float
+    evaluation_period: float = 30.0
+
+
+@dataclass
+class CanaryState:
+    """canary_deployer.py:49-56."""
+
+    status: str = "idle"  # idle, in_progress, promoting, rolled_back, completed
+    current_stage: int = 0
+    total_stages: int = 0
+    canary_traffic_pct: float = 0.0
+
+
+def _against_baseline(value: float, baseline: list, limit: float, multiplier: float) -> bool:
+    """The comparison both evaluators make (canary_deployer.py:87-100, 123-138): the canary's figure against its own limit, then
+    against the baseline's plain average times the multiplier where that average is positive."""
+    if value > limit:
+        return False
+    if not baseline:
+        return value <= limit
+    average = sum(baseline) / len(baseline)
+    if average > 0:
+        return value <= average * multiplier
+    return value <= limit
+
+
+class ErrorRateEvaluator:
+    """canary_deployer.py:76-109: the canary's share of rejected Requests against the baseline's average share."""
+
+    def __init__(self, max_error_rate: float = 0.05, threshold_multiplier: float = 2.0):
+        self._max_error_rate = max_error_rate
+        self._threshold_multiplier = threshold_multiplier
+
+    def is_healthy(self, canary, baseline_backends: list) -> bool:
+        return _against_baseline(self._get_error_rate(canary), [self._get_error_rate(b) for b in baseline_backends],
+                                 self._max_error_rate, self._threshold_multiplier)
+
+    def _get_error_rate(self, backend) -> float:
+        if hasattr(backend, "stats"):
+            stats = backend.stats
+            rejected = getattr(stats, "requests_rejected", 0)
+            total = getattr(stats, "requests_completed", 0) + rejected
+            if total > 0:
+                return (rejected + getattr(stats, "total_failures", 0)) / total
+        return 0.0
+
+
+class LatencyEvaluator:
+    """canary_deployer.py:112-143: the canary's average service time against the baseline's average."""
+
+    def __init__(self, max_latency: float = 1.0, threshold_multiplier: float = 1.5):
+        self._max_latency = max_latency
+        self._threshold_multiplier = threshold_multiplier
+
+    def is_healthy(self, canary, baseline_backends: list) -> bool:
+        return _against_baseline(self._get_avg_latency(canary), [self._get_avg_latency(b) for b in baseline_backends],
+                                 self._max_latency, self._threshold_multiplier)
+
+    def _get_avg_latency(self, backend) -> float:
+        return backend.average_service_time if hasattr(backend, "average_service_time") else 0.0
+
+
+METRIC_EVALUATORS = (ErrorRateEvaluator, LatencyEvaluator)
+
+
+@dataclass(frozen=True)
+class CanaryDeployerStats:
+    """canary_deployer.py:146-156."""
+
+    deployments_started: int = 0
+    deployments_completed: int = 0
+    deployments_rolled_back: int = 0
+    stages_completed: int = 0
+    evaluations_performed: int = 0
+    evaluations_passed: int = 0
+    evaluations_failed: int = 0
+
+
+class CanaryDeployer(Entity):
+    """One new instance `{name}_canary` joins a LoadBalancer and takes a growing share of its traffic stage by stage -- the strategy's
+    weights are rewritten at every stage --, watched by a metric evaluator every `evaluation_interval` seconds; the last stage ends in
+    a promotion (the baseline leaves), a failed evaluation in a rollback (components/deployment/canary_deployer.py:159-494).  The
+    handlers run on the device (csrc/hs_graph.hip kEvCnStart ..); the factory is called once, when the graph is lowered, and the canary
+    stands as a dormant Server behind all of the Simulation's own nodes until the deployment starts."""
+
+    DEFAULT_STAGES = [CanaryStage(0.01, 30.0), CanaryStage(0.05, 30.0), CanaryStage(0.25, 30.0), CanaryStage(1.0, 30.0)]
+    MAX_STAGES = 16                  # include/hs_engine.h HS_CANARY_MAX_STAGES
+
+    def __init__(self, name: str, load_balancer: LoadBalancer, server_factory, stages=None, metric_evaluator=None,
+                 evaluation_interval: float = 5.0):
+        super().__init__(name)
+        self._load_balancer = load_balancer
+        self._server_factory = server_factory
+        self._stages = stages or list(self.DEFAULT_STAGES)
+        self._metric_evaluator = metric_evaluator or ErrorRateEvaluator()
+        self._evaluation_interval = evaluation_interval
+        self._canary: Entity | None = None
+        self._baseline_backends: list[Entity] = []
+        self._stage_start_time: Instant | None = None
+        self._original_strategy = None
+        self._deployments_started = 0
+        self._deployments_completed = 0
+        self._deployments_rolled_back = 0
+        self._stages_completed = 0
+        self._evaluations_performed = 0
+        self._evaluations_passed = 0
+        self._evaluations_failed = 0
+        self.state = CanaryState()
+        self._sim_start: Instant | None = None           # the clock a Simulation hands to its entities: `now` before run() is its start
+        self._pool: list[Entity] = []                    # the factory's one result, made when a graph is lowered
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._load_balancer] + ([self._canary] if self._canary is not None else []) + list(self._baseline_backends)
+
+    @property
+    def stats(self) -> CanaryDeployerStats:
+        return CanaryDeployerStats(self._deployments_started, self._deployments_completed, self._deployments_rolled_back,
+                                   self._stages_completed, self._evaluations_performed, self._evaluations_passed,
+                                   self._evaluations_failed)
+
+    @property
+    def canary(self):
+        return self._canary
+
+    @property
+    def load_balancer(self) -> LoadBalancer:
+        return self._load_balancer
+
+    def deploy(self):
+        """canary_deployer.py:252-263: the `_canary_deploy_start` Event for `sim.schedule(...)`, no daemon; its time is the Simulation's
+        start once the deployer is one of its entities, Instant.Epoch before.  The caller may set another time.  One per deployer."""
+        from .core.event import Event
+
+        return Event(time=self._sim_start if self._sim_start is not None else Instant.Epoch, event_type="_canary_deploy_start",
+                     target=self, context={})
+
+    def _instance(self, k: int = 1) -> Entity:
+        """The canary instance, from the factory the first time it is asked for."""
+        if not self._pool:
+            self._pool.append(self._server_factory(f"{self.name}_canary"))
+        return self._pool[0]
+
+
 # ---- probes --------------------------------------------------------------------------------------
 class Data:
     """Time-series container of a Probe (instrumentation/data.py:20-110): `values` = [(time_s, value), ...]."""

@@ -176,6 +176,17 @@ class FaultSchedule(Entity):
                 if kind in NOT_LOWERED:
                     raise UnsupportedTopology(f"fault {kind} is not lowered: {NOT_LOWERED[kind]} (lowered: {LOWERED})")
                 raise UnsupportedTopology(f"fault {kind} is not lowered: its generate_events is host Python (lowered: {LOWERED})")
+            if fault.entity_name not in entities:
+                # an instance a deployer's or scaler's factory makes is no entity of the Simulation: say so (any other unknown name
+                # is the dict's KeyError, as in the reference)
+                for c in components:
+                    pools = {"RollingDeployer": f"{c.name}_v2_", "CanaryDeployer": f"{c.name}_canary", "AutoScaler": f"{c.name}_server_"}
+                    prefix = pools.get(type(c).__name__)
+                    if prefix and fault.entity_name.startswith(prefix):
+                        raise UnsupportedTopology(f"fault {type(fault).__name__} names '{fault.entity_name}', an instance of the pool of "
+                                                  f"{type(c).__name__} '{c.name}': a pool instance is no entity of the Simulation and cannot "
+                                                  "be named by a FaultSchedule (the reference cannot either; the fault may name "
+                                                  f"'{c.name}' itself)")
             entity = entities[fault.entity_name]
             events = []
             for what, t_s, on in fault._fault_events():

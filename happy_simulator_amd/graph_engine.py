@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _native as N
 from .core.temporal import Duration, Instant
-from .entities import (AutoScaler, SCALING_POLICIES, ScalingEvent, StepScaling, TargetUtilization,
+from .entities import (CanaryDeployer, CanaryState, METRIC_EVALUATORS, LatencyEvaluator, DeploymentState, RollingDeployer, AutoScaler, SCALING_POLICIES, ScalingEvent, StepScaling, TargetUtilization,
                        BackendInfo,
                        AdaptiveLIFO, CoDelQueue, FIFOQueue, QUEUE_POLICIES, BatchProcessor, ConveyorBelt, GateController,
                        BackendHealthState, Bulkhead, Client, ClientKeyEventProvider, ConsistentHash, ConstantLatency, ConstantRateProfile, Counter, Entity,
@@ -101,6 +101,39 @@ class GraphArrays:
                                              #   evaluation_interval, scale_out_cooldown, scale_in_cooldown, the pool's size P, _is_running
         self.as_steps = None                 #   ... and per node its StepScaling steps as [(threshold, adjustment), ...] (a list per node);
                                              #   set through hs_graph_set_auto_scaler (their LoadBalancer: `target`)
+        # (kept out of vars(): tests/test_autoscaler_host.py::test_existing_lowering_is_unchanged_without_a_scaler hashes every public
+        #  attribute of these arrays but the `as_*` ones against the digest of the commit before the AutoScaler -- a new plain attribute,
+        #  even one that is None, would change what that test hashes)
+        self._rd_params = None               # `rd_params`
+
+    @property
+    def rd_params(self):
+        """[n, 5] float64 (None: no deployer): ROLLING_DEPLOYER nodes -- batch_size, health_check_interval, healthy_threshold,
+        max_failures, the pool's size P; set through hs_graph_set_rolling_deployer (their LoadBalancer: `target`)."""
+        return self._rd_params
+
+    @rd_params.setter
+    def rd_params(self, value):
+        self._rd_params = value
+
+    @property
+    def has_deployers(self) -> bool:
+        return self._rd_params is not None
+
+    @property
+    def cn_params(self):
+        """per node (None: no canary deployer; kept out of vars() like `rd_params`): None or (stages as [(traffic_percentage,
+        evaluation_period), ...], hs_canary_evaluator, its limit, its threshold_multiplier, evaluation_interval) of a CANARY_DEPLOYER
+        node; set through hs_graph_set_canary_deployer (its LoadBalancer: `target`)."""
+        return getattr(self, "_cn_params", None)
+
+    @cn_params.setter
+    def cn_params(self, value):
+        self._cn_params = value
+
+    @property
+    def has_canaries(self) -> bool:
+        return self.cn_params is not None
 
     @property
     def has_scalers(self) -> bool:
@@ -215,6 +248,28 @@ class GraphEngine:
                     self._check(self._lib.hs_graph_set_auto_scaler(self._h, int(i), int(arrays.target[i]), int(pol), float(p0), float(p1), len(steps),
                                                                    _ptr(thr), _ptr(adj), int(lo), int(hi), float(iv), float(cd_out), float(cd_in),
                                                                    int(pool), int(running)))
+            except BaseException:
+                self.close()
+                raise
+
+        if arrays.has_deployers:
+            try:
+                for i in np.nonzero(arrays.kind == N.NODE_ROLLING_DEPLOYER)[0]:
+                    batch, iv, thr, fails, pool = arrays.rd_params[i]
+                    self._check(self._lib.hs_graph_set_rolling_deployer(self._h, int(i), int(arrays.target[i]), int(batch), float(iv), int(thr),
+                                                                        int(fails), int(pool)))
+            except BaseException:
+                self.close()
+                raise
+
+        if arrays.has_canaries:
+            try:
+                for i in np.nonzero(arrays.kind == N.NODE_CANARY_DEPLOYER)[0]:
+                    stages, evaluator, limit, mult, iv = arrays.cn_params[i]
+                    pct = np.array([s_[0] for s_ in stages], np.float64)
+                    period = np.array([s_[1] for s_ in stages], np.float64)
+                    self._check(self._lib.hs_graph_set_canary_deployer(self._h, int(i), int(arrays.target[i]), len(stages), _ptr(pct), _ptr(period),
+                                                                       int(evaluator), float(limit), float(mult), float(iv)))
             except BaseException:
                 self.close()
                 raise
@@ -351,6 +406,81 @@ class GraphEngine:
         events = C.c_int64(0)
         self._check(self._lib.hs_graph_get_auto_scaler(self._h, -1, None, None, 0, None, C.byref(events)))
         return int(events.value)
+
+    _DEPLOYER_NAMES = ("deployments_started", "deployments_completed", "deployments_rolled_back", "instances_replaced",
+                       "health_checks_performed", "health_checks_passed", "health_checks_failed", "status", "total_instances", "replaced",
+                       "failed", "current_batch", "next_instance_id", "health_fail_count", "n_old", "n_new", "n_batch_old", "n_batch_new",
+                       "n_members")
+
+    def deployer(self, node: int) -> dict:
+        """hs_graph_get_rolling_deployer of a RollingDeployer node: its state by name, `old` / `new` / `batch_old` / `batch_new` and
+        `members` (the LoadBalancer's, in order) as lists of slots, `pass_count` as {slot: count}, `readded`: the slots a rollback
+        added again."""
+        a = self.arrays
+        cnt = max(int(a.rt_cnt[int(a.target[node])]), 1)
+        st, lists = np.zeros(N.DEPLOYER_FIELDS, np.int64), np.full(4 * cnt, -1, np.int32)
+        members, passes, readded = np.full(cnt, -1, np.int32), np.full(cnt, -1, np.int32), np.zeros(cnt, np.int32)
+        self._check(self._lib.hs_graph_get_rolling_deployer(self._h, int(node), _ptr(st), _ptr(lists), _ptr(members), _ptr(passes), _ptr(readded),
+                                                            None))
+        out = {k: int(v) for k, v in zip(self._DEPLOYER_NAMES, st)}
+        for j, (nm, ln) in enumerate((("old", "n_old"), ("new", "n_new"), ("batch_old", "n_batch_old"), ("batch_new", "n_batch_new"))):
+            out[nm] = lists[j * cnt:j * cnt + out[ln]].tolist()
+        out["members"] = members[:out["n_members"]].tolist()
+        out["pass_count"] = {int(q): int(v) for q, v in enumerate(passes) if v >= 0}
+        out["readded"] = np.nonzero(readded)[0].tolist()
+        return out
+
+    _CANARY_NAMES = ("deployments_started", "deployments_completed", "deployments_rolled_back", "stages_completed", "evaluations_performed",
+                     "evaluations_passed", "evaluations_failed", "status", "current_stage", "total_stages", "has_canary", "stage_start_ns",
+                     "n_baseline", "n_members")
+
+    def canary(self, node: int) -> dict:
+        """hs_graph_get_canary_deployer of a CanaryDeployer node: its state by name, `traffic_pct`, `baseline` and `members` (the
+        LoadBalancer's, in order) as lists of slots, `weights` / `weight_set` / `service_sum` / `service_count` per slot."""
+        a = self.arrays
+        cnt = max(int(a.rt_cnt[int(a.target[node])]), 1)
+        st, pct = np.zeros(N.CANARY_FIELDS, np.int64), C.c_double(0.0)
+        base, members, weights, wset = (np.full(cnt, -1, np.int32) for _ in range(4))
+        ssum, scnt = np.zeros(cnt, np.float64), np.zeros(cnt, np.int64)
+        self._check(self._lib.hs_graph_get_canary_deployer(self._h, int(node), _ptr(st), C.byref(pct), _ptr(base), _ptr(members), _ptr(weights),
+                                                           _ptr(wset), _ptr(ssum), _ptr(scnt), None))
+        out = {k: int(v) for k, v in zip(self._CANARY_NAMES, st)}
+        out.update(traffic_pct=float(pct.value), baseline=base[:out["n_baseline"]].tolist(), members=members[:out["n_members"]].tolist(),
+                   weights=weights.tolist(), weight_set=np.nonzero(wset > 0)[0].tolist(), service_sum=ssum, service_count=scnt)
+        return out
+
+    def canary_events(self) -> np.ndarray:
+        """The graph's canary deployer Events of the run by kind (hs_graph_get_canary_deployer, node = -1)."""
+        events = np.zeros(N.CANARY_KINDS, np.int64)
+        self._check(self._lib.hs_graph_get_canary_deployer(self._h, -1, None, None, None, None, None, None, None, None, _ptr(events)))
+        return events
+
+    def deployer_events(self) -> np.ndarray:
+        """The graph's deployer Events of the run by kind (hs_graph_get_rolling_deployer, node = -1)."""
+        return self._deployer_counts()[:N.DEPLOYER_KINDS]
+
+    def deployer_compactions(self) -> tuple:
+        """(by the lone lane, by all 64 lanes): the member lists this graph compacted behind a removal so far."""
+        both = self._deployer_counts()[N.DEPLOYER_KINDS:]
+        return int(both[0]), int(both[1])
+
+    @staticmethod
+    def compact_members(members, member_flags, wave: bool, device: int = 0) -> list:
+        """hs_debug_compact_members: `members` (slots in insertion order) without the slots whose flag is 0, order kept -- compacted on
+        the device by the lone lane or, `wave`, by all 64 lanes."""
+        lst = np.ascontiguousarray(members, np.int32).copy()
+        flags = np.ascontiguousarray(member_flags, np.uint8)
+        out = C.c_int32(0)
+        rc = N.lib().hs_debug_compact_members(int(device), len(flags), len(lst), _ptr(lst) if len(lst) else None, _ptr(flags) if len(flags) else None,
+                                              int(bool(wave)), C.byref(out))
+        if rc < 0:
+            raise N.EngineError(rc, "hs_debug_compact_members")
+        return lst[:out.value].tolist()
+
+    def _deployer_counts(self) -> np.ndarray:
+        events = np.zeros(N.DEPLOYER_KINDS + 2, np.int64)
+        self._check(self._lib.hs_graph_get_rolling_deployer(self._h, -1, None, None, None, None, None, _ptr(events)))
+        return events
 
     def health(self, node: int) -> dict:
         """hs_graph_get_health of a HealthChecker or LoadBalancer node: checker stats, per-backend states, the LoadBalancer's health
@@ -514,6 +644,9 @@ class GeneralGraph:
         self.pool_of = {}               # pool Server node -> (its AutoScaler's node, its instance id k)
         self.n_own = len(nodes)         # the Simulation's own nodes; the scalers' pools stand behind them
         self.scaler_starts = 1          # the start() Events per scaler the pools were sized for
+        self.deployed = {}              # LoadBalancer node -> (its RollingDeployer's node, its initial backends, the pool's Servers)
+        self.dpool_of = {}              # pool Server node -> (its RollingDeployer's node, its instance id k)
+        self.deploys = {}               # RollingDeployer node -> the deploy() Events its pool was sized for
         self.rr_base = {}               # scaled LoadBalancer node -> its RoundRobin's `_index` when the graph was lowered
 
 
@@ -598,8 +731,16 @@ def scaler_pool_size(scaler: "AutoScaler", n_initial: int, start_ns: int, end_ns
     return int(runs * most)
 
 
+def deployer_pool_size(n_initial: int, deploys: int) -> int:
+    """P: a bound on the instances a RollingDeployer can create over `deploys` scheduled deploy() Events ("Deployers").
+    Every instance takes one entry out of `_old_backends`, and entries come into that list only at a `_rolling_deploy_start`, which
+    copies the LoadBalancer's members: deployment j creates at most n_j instances, n_j <= n_initial + n_1 + .. + n_(j-1) (the initial
+    backends and every instance made so far), so n_j <= n_initial * 2^(j-1) and P = n_initial * (2^deploys - 1).  No horizon enters."""
+    return int(n_initial) * ((1 << min(int(deploys), 62)) - 1)
+
+
 def lower_general(sources: list, entities: list, probes=None, *, start_ns: int = 0, end_ns: int | None = None,
-                  scaler_starts: int = 1) -> GeneralGraph:
+                  scaler_starts: int = 1, deploys: dict | None = None) -> GeneralGraph:
     """`sources` / `entities` of a Simulation -> the node arrays of the single-heap engine.  Refuses by name what that engine
     does not run either (lowering.UnsupportedTopology).  `start_ns` / `end_ns` (None: Infinity) / `scaler_starts` (the start() Events
     scheduled per scaler) size the instance pools of the AutoScalers."""
@@ -629,7 +770,7 @@ def lower_general(sources: list, entities: list, probes=None, *, start_ns: int =
         add(pr)
     n_front = len(nodes)
     lowered = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker, Bulkhead, TimeoutWrapper, Client,
-               BatchProcessor, ConveyorBelt, GateController, AutoScaler) + _SINKS
+               BatchProcessor, ConveyorBelt, GateController, AutoScaler, RollingDeployer, CanaryDeployer) + _SINKS
 
     def check(ent, where):
         if isinstance(ent, Source):
@@ -646,6 +787,8 @@ def lower_general(sources: list, entities: list, probes=None, *, start_ns: int =
             raise UnsupportedTopology(f"{where}: the HealthChecker '{ent.name}' takes no Requests")
         if isinstance(ent, AutoScaler) and where != "entities":
             raise UnsupportedTopology(f"{where}: the AutoScaler '{ent.name}' takes no Requests")
+        if isinstance(ent, (RollingDeployer, CanaryDeployer)) and where != "entities":
+            raise UnsupportedTopology(f"{where}: the {type(ent).__name__} '{ent.name}' takes no Requests")
         if not isinstance(ent, lowered):
             raise UnsupportedTopology(f"{where}: {type(ent).__name__} '{getattr(ent, 'name', ent)}' is not lowered to the engine")
 
@@ -666,7 +809,7 @@ def lower_general(sources: list, entities: list, probes=None, *, start_ns: int =
     while k < len(nodes):
         ent = nodes[k]
         k += 1
-        if isinstance(ent, (Probe, HealthChecker, AutoScaler)):   # (a checker's / scaler's LoadBalancer has to be part of the Simulation by itself)
+        if isinstance(ent, (Probe, HealthChecker, AutoScaler, RollingDeployer, CanaryDeployer)):   # (a checker's / scaler's LoadBalancer has to be part of the Simulation by itself)
             continue
         for d in ent.downstream_entities():
             if d is None:
@@ -739,6 +882,83 @@ def lower_general(sources: list, entities: list, probes=None, *, start_ns: int =
             pool_of[add(inst)] = (sc, k)
             pool.append(inst)
         scaled[id(lb)] = (sc, initial, pool)
+    # the RollingDeployers' pools likewise, behind the scalers'
+    for dp in [x for x in nodes if isinstance(x, (RollingDeployer, CanaryDeployer))]:
+        rolling = isinstance(dp, RollingDeployer)
+        what = f"{'rolling' if rolling else 'canary'} deployer '{dp.name}'"
+        lb = dp.load_balancer
+        if not isinstance(lb, LoadBalancer) or id(lb) not in node_of:
+            raise UnsupportedTopology(f"{what}: its LoadBalancer is not an entity of this Simulation")
+        if id(lb) in scaled:
+            other = scaled[id(lb)][0]
+            raise UnsupportedTopology(f"{what}: LoadBalancer '{lb.name}' has the {type(other).__name__} '{other.name}' already (a deployer next "
+                                      "to an AutoScaler or another deployer on one LoadBalancer is not lowered: a follow-up)")
+        if not isinstance(lb.strategy, (RoundRobin, WeightedRoundRobin, LeastConnections, WeightedLeastConnections)):
+            raise UnsupportedTopology(f"{what}: strategy {type(lb.strategy).__name__} of '{lb.name}' is not lowered under a deployer (its "
+                                      "selection over a changing backend list is a follow-up: RoundRobin, WeightedRoundRobin, "
+                                      "LeastConnections and WeightedLeastConnections are)")
+        if lb.unhealthy_backends:
+            raise UnsupportedTopology(f"{what}: backend '{lb.unhealthy_backends[0].name}' of '{lb.name}' is marked unhealthy -- health marks "
+                                      "under a deployer are not lowered (a follow-up)")
+        if not rolling:
+            ev = dp._metric_evaluator
+            if type(ev) not in METRIC_EVALUATORS:
+                raise UnsupportedTopology(f"{what}: metric evaluator {type(ev).__name__} is not lowered to the engine (lowered: "
+                                          "ErrorRateEvaluator, LatencyEvaluator)")
+            if len(dp._stages) > CanaryDeployer.MAX_STAGES:
+                raise UnsupportedTopology(f"{what}: {len(dp._stages)} stages are beyond the {CanaryDeployer.MAX_STAGES} the engine holds "
+                                          "(CanaryDeployer.MAX_STAGES)")
+            for k, st_ in enumerate(dp._stages):
+                try:
+                    ok = bool(np.isfinite(st_.traffic_percentage)) and bool(np.isfinite(st_.evaluation_period))
+                except (TypeError, ValueError, AttributeError):
+                    ok = False
+                if not ok:
+                    raise UnsupportedTopology(f"{what}: stage {k} has a traffic_percentage or evaluation_period that is no finite number")
+            try:
+                ok = bool(np.isfinite(dp._evaluation_interval)) and dp._evaluation_interval > 0 and dp._evaluation_interval * 1e9 >= 1.0
+                lim_, mult_ = ((ev._max_latency if isinstance(ev, LatencyEvaluator) else ev._max_error_rate), ev._threshold_multiplier)
+                ok = ok and float(lim_) == float(lim_) and float(mult_) == float(mult_)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise UnsupportedTopology(f"{what}: evaluation_interval = {dp._evaluation_interval!r} must be a finite number of at least one "
+                                          "nanosecond (and the evaluator's limits numbers)")
+            if (deploys or {}).get(id(dp), 1) > 1:
+                raise UnsupportedTopology(f"{what}: {(deploys or {}).get(id(dp), 1)} deploy() Events are scheduled -- a second canary of the same name is never "
+                                          "registered by the LoadBalancer (one deploy() per CanaryDeployer is lowered)")
+        for v, nm, least in ((dp._batch_size, "batch_size", 1), (dp._healthy_threshold, "healthy_threshold", 1), (dp._max_failures, "max_failures", None)) if rolling else ():
+            if type(v) is not int or not -(1 << 30) < v < (1 << 30) or (least is not None and v < least):
+                raise UnsupportedTopology(f"{what}: {nm} must be an int{'' if least is None else f' of at least {least}'} below 2^30, got {v!r}")
+        try:
+            ok = not rolling or (bool(np.isfinite(dp._health_check_interval)) and dp._health_check_interval > 0 and dp._health_check_interval * 1e9 >= 1.0)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise UnsupportedTopology(f"{what}: health_check_interval = {dp._health_check_interval!r} must be a finite number of at least "
+                                      "one nanosecond")
+        initial = lb.all_backends
+        n_deploys = (deploys or {}).get(id(dp), 1)
+        size = deployer_pool_size(len(initial), n_deploys) if rolling else 1
+        if size > RollingDeployer.MAX_POOL:
+            raise UnsupportedTopology(f"{what}: {n_deploys} deploy() Events over {len(initial)} backends could create up to {size} instances, "
+                                      f"beyond the pool of {RollingDeployer.MAX_POOL} per deployer (RollingDeployer.MAX_POOL)")
+        pool = []
+        for k in range(1, size + 1):
+            inst = dp._instance(k)
+            if not isinstance(inst, Server):
+                raise UnsupportedTopology(f"{what}: server_factory returned a {type(inst).__name__} for instance {k}: only Servers may stand "
+                                          "as a LoadBalancer's backends")
+            if id(inst) in node_of:
+                raise UnsupportedTopology(f"{what}: server_factory returned '{inst.name}' for instance {k}, which is an entity of this "
+                                          "Simulation or another instance already (one new Server per call)")
+            d = inst.downstream
+            if d is not None and (id(d) not in node_of or node_of[id(d)] >= n_own):
+                raise UnsupportedTopology(f"{what}: the downstream '{getattr(d, 'name', d)}' of instance {k} is not an entity of this "
+                                          "Simulation")
+            pool_of[add(inst)] = (dp, k)
+            pool.append(inst)
+        scaled[id(lb)] = (dp, initial, pool)
     n = len(nodes)
     a = GraphArrays(n)
     counters = {Server: 0, NetworkLink: 0, RandomRouter: 0}
@@ -917,8 +1137,9 @@ def lower_general(sources: list, entities: list, probes=None, *, start_ns: int =
             if not isinstance(lb, LoadBalancer) or id(lb) not in node_of:
                 raise UnsupportedTopology(f"health checker '{ent.name}': its LoadBalancer is not an entity of this Simulation")
             if id(lb) in scaled:
-                raise UnsupportedTopology(f"health checker '{ent.name}': LoadBalancer '{lb.name}' has the AutoScaler '{scaled[id(lb)][0].name}' "
-                                          "-- a HealthChecker and an AutoScaler on one LoadBalancer are not lowered (a follow-up)")
+                kind_ = type(scaled[id(lb)][0]).__name__
+                raise UnsupportedTopology(f"health checker '{ent.name}': LoadBalancer '{lb.name}' has the {kind_} '{scaled[id(lb)][0].name}' "
+                                          f"-- a HealthChecker and {'an' if kind_ == 'AutoScaler' else 'a'} {kind_} on one LoadBalancer are not lowered (a follow-up)")
             if id(lb) in checked:
                 raise UnsupportedTopology(f"health checker '{ent.name}': LoadBalancer '{lb.name}' has the checker '{checked[id(lb)]}' already "
                                           "(one HealthChecker per LoadBalancer is lowered)")
@@ -956,6 +1177,29 @@ def lower_general(sources: list, entities: list, probes=None, *, start_ns: int =
                 code, p0, p1 = N.AUTOSCALER_QUEUE_DEPTH, pol._scale_out_threshold, pol._scale_in_threshold
             a.as_params[i] = (code, p0, p1, ent._min_instances, ent._max_instances, ent._evaluation_interval, ent._scale_out_cooldown,
                               ent._scale_in_cooldown, len(scaled[id(lb)][2]), 1.0 if ent.is_running else 0.0)
+        elif isinstance(ent, CanaryDeployer):
+            lb, ev = ent.load_balancer, ent._metric_evaluator
+            if id(lb) in checked:
+                raise UnsupportedTopology(f"canary deployer '{ent.name}': LoadBalancer '{lb.name}' has the HealthChecker '{checked[id(lb)]}' -- a "
+                                          "HealthChecker and a CanaryDeployer on one LoadBalancer are not lowered (a follow-up)")
+            if a.cn_params is None:
+                a.cn_params = [None] * n
+            a.kind[i] = N.NODE_CANARY_DEPLOYER
+            a.target[i] = node_of[id(lb)]
+            latency = isinstance(ev, LatencyEvaluator)
+            a.cn_params[i] = ([(float(s_.traffic_percentage), float(s_.evaluation_period)) for s_ in ent._stages],
+                              N.CANARY_LATENCY if latency else N.CANARY_ERROR_RATE, float(ev._max_latency if latency else ev._max_error_rate),
+                              float(ev._threshold_multiplier), float(ent._evaluation_interval))
+        elif isinstance(ent, RollingDeployer):
+            lb = ent.load_balancer
+            if id(lb) in checked:
+                raise UnsupportedTopology(f"rolling deployer '{ent.name}': LoadBalancer '{lb.name}' has the HealthChecker '{checked[id(lb)]}' -- a "
+                                          "HealthChecker and a RollingDeployer on one LoadBalancer are not lowered (a follow-up)")
+            if a.rd_params is None:
+                a.rd_params = np.zeros((n, 5), np.float64)
+            a.kind[i] = N.NODE_ROLLING_DEPLOYER
+            a.target[i] = node_of[id(lb)]
+            a.rd_params[i] = (ent._batch_size, ent._health_check_interval, ent._healthy_threshold, ent._max_failures, len(scaled[id(lb)][2]))
         elif isinstance(ent, (Bulkhead, TimeoutWrapper)):
             what = f"{type(ent).__name__} '{ent.name}'"
             tgt = ent.target
@@ -1106,7 +1350,7 @@ def lower_general(sources: list, entities: list, probes=None, *, start_ns: int =
         a.lb_weights = np.ones(len(rt), np.int32)
         for off, ws in weights.items():
             a.lb_weights[off:off + len(ws)] = ws
-    if unhealthy or a.hc_params is not None or a.as_params is not None:     # (a scaled LoadBalancer's member list is the healthy list)
+    if unhealthy or a.hc_params is not None or a.as_params is not None or a.rd_params is not None or a.cn_params is not None:     # (a scaled LoadBalancer's member list is the healthy list)
         a.lb_healthy = np.ones(len(rt), np.uint8)
         for off, flags in unhealthy.items():
             a.lb_healthy[off:off + len(flags)] = flags
@@ -1119,9 +1363,13 @@ def lower_general(sources: list, entities: list, probes=None, *, start_ns: int =
     assert all(a.kind[i] == N.NODE_SOURCE for i in range(n_src)) and all(a.kind[i] == N.NODE_PROBE for i in range(n_src, n_front))
     g = GeneralGraph(nodes, a, node_of)
     g.n_own, g.scaler_starts = n_own, scaler_starts
-    g.scaled = {node_of[lb_id]: (node_of[id(sc)], initial, pool) for lb_id, (sc, initial, pool) in scaled.items()}
-    g.pool_of = {i: (node_of[id(sc)], k) for i, (sc, k) in pool_of.items()}
-    g.rr_base = {i: nodes[i].strategy._index for i in g.scaled if isinstance(nodes[i].strategy, RoundRobin)}
+    g.scaled = {node_of[lb_id]: (node_of[id(sc)], initial, pool) for lb_id, (sc, initial, pool) in scaled.items() if isinstance(sc, AutoScaler)}
+    g.pool_of = {i: (node_of[id(sc)], k) for i, (sc, k) in pool_of.items() if isinstance(sc, AutoScaler)}
+    both = (RollingDeployer, CanaryDeployer)
+    g.deployed = {node_of[lb_id]: (node_of[id(dp)], initial, pool) for lb_id, (dp, initial, pool) in scaled.items() if isinstance(dp, both)}
+    g.dpool_of = {i: (node_of[id(dp)], k) for i, (dp, k) in pool_of.items() if isinstance(dp, both)}
+    g.deploys = {node_of[id(dp)]: (deploys or {}).get(id(dp), 1) for dp, _i, _p in scaled.values() if isinstance(dp, both)}
+    g.rr_base = {i: nodes[i].strategy._index for i in list(g.scaled) + list(g.deployed) if isinstance(nodes[i].strategy, RoundRobin)}
     return g
 
 
@@ -1160,7 +1408,7 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
     per_node = [nm for nm in ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s",
                               "link_lat_min_s", "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric",
                               "probe_interval_s", "lb_strategy", "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params", "cl_params",
-                              "flow_params", "qp_params", "as_params")
+                              "flow_params", "qp_params", "as_params", "rd_params")
                 if getattr(a, nm) is not None]
     names = None if a.names is None else [a.names[a.name_off[i]:a.name_off[i + 1]] for i in range(n)]
     parts = []
@@ -1189,7 +1437,12 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
             b.rt_targets = np.zeros(0, np.int32)
         if b.hc_params is not None and not (b.kind == N.NODE_HEALTH_CHECKER).any():
             b.hc_params = None                                             # (a part without a checker: no health state unless a flag says so)
-        if b.lb_healthy is not None and b.hc_params is None and b.lb_healthy.all() and not (b.kind == N.NODE_AUTO_SCALER).any():
+        if b.rd_params is not None and not (b.kind == N.NODE_ROLLING_DEPLOYER).any():
+            b.rd_params = None                                             # (a part without a deployer likewise)
+        if a.cn_params is not None and (b.kind == N.NODE_CANARY_DEPLOYER).any():
+            b.cn_params = [a.cn_params[i] for i in ids]
+        if (b.lb_healthy is not None and b.hc_params is None and b.lb_healthy.all() and not (b.kind == N.NODE_AUTO_SCALER).any()
+                and b.rd_params is None and b.cn_params is None):
             b.lb_healthy = None
         if b.wrap_params is not None and not ((b.kind == N.NODE_BULKHEAD) | (b.kind == N.NODE_TIMEOUT_WRAPPER)).any():
             b.wrap_params = None                                           # (a part without a wrapper runs the loop it would run alone)
@@ -1319,6 +1572,26 @@ class PartRun:
     def scaler_events(self) -> int:
         return int(sum(e.scaler_events() for e in self.engines))
 
+    def deployer_events(self) -> np.ndarray:
+        return np.sum([e.deployer_events() for e in self.engines], axis=0)
+
+    def canary_events(self) -> np.ndarray:
+        return np.sum([e.canary_events() for e in self.engines], axis=0)
+
+    def canary(self, node: int) -> dict:
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            at = np.searchsorted(ids, node)
+            if at < len(ids) and ids[at] == node:
+                return e.canary(int(at))
+        raise KeyError(node)
+
+    def deployer(self, node: int) -> dict:
+        for (ids, _pos, _b), e in zip(self.parts, self.engines):
+            at = np.searchsorted(ids, node)
+            if at < len(ids) and ids[at] == node:
+                return e.deployer(int(at))
+        raise KeyError(node)
+
     def scaler(self, node: int) -> dict:
         for (ids, _pos, _b), e in zip(self.parts, self.engines):
             at = np.searchsorted(ids, node)
@@ -1395,7 +1668,7 @@ def keyless_hazard(g: "GeneralGraph", target) -> str | None:
 
 
 def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t: np.ndarray, rec_cr: np.ndarray, device: int = 0,
-                       health=None, wrapper=None, client=None, flow=None, queue=None, scaler=None) -> None:
+                       health=None, wrapper=None, client=None, flow=None, queue=None, scaler=None, deployer=None, canary=None) -> None:
     """The run's per-node results onto the user's objects, under the attribute names the reference uses (lowering.write_back's
     counterpart).  `health`: node -> GraphEngine.health(node) of a graph with health state; `wrapper`: node -> GraphEngine.wrapper(node)
     of a graph with a Bulkhead or a TimeoutWrapper; `client`: node -> GraphEngine.client(node) of a graph with a Client."""
@@ -1403,9 +1676,16 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
     order = np.argsort(rec_node, kind="stable")              # per Sink, still in processing order
     bounds = np.searchsorted(rec_node[order], np.arange(a.n + 1))
     scalers = {sn: scaler(sn) for sn, _initial, _pool in g.scaled.values()} if g.scaled else {}    # GraphEngine.scaler(node) per AutoScaler
+    # GraphEngine.deployer(node) per RollingDeployer, GraphEngine.canary(node) per CanaryDeployer (its one instance: id 1 once it is set)
+    deployers = {dn: (deployer(dn) if isinstance(g.nodes[dn], RollingDeployer) else canary(dn)) for dn, _initial, _pool in g.deployed.values()}
+    for w in deployers.values():
+        if "has_canary" in w:
+            w.update(next_instance_id=w["has_canary"], readded=[])
     for i, ent in enumerate(g.nodes):
         if i in g.pool_of and g.pool_of[i][1] > scalers[g.pool_of[i][0]]["next_instance_id"]:
             continue                                               # (an instance the run never activated: left untouched)
+        if i in g.dpool_of and g.dpool_of[i][1] > deployers[g.dpool_of[i][0]]["next_instance_id"]:
+            continue
         if isinstance(ent, Source):
             ent._generated_count = int(stats["generated"][i])
             ent._event_provider._generated = int(stats["payloads"][i])
@@ -1470,6 +1750,34 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
                     ent.strategy._selections = selections
                     ent.strategy._current_weights = {cand[q].name: v for q, v in sorted(h["current_weights"].items())}
                 continue
+            if i in g.deployed:
+                # a deployed LoadBalancer: `_backends` in insertion order, as the device's member list holds it.  A backend that left
+                # has no entry; one that came back has a new BackendInfo (the device counts its total_requests from 0 again); the
+                # strategy keeps what it learned of every name (its weight, its current weight)
+                dn, initial, pool = g.deployed[i]
+                w, h = deployers[dn], health(i)
+                cand = initial + pool
+                old = ent._backends
+                ent._backends = {}
+                for q in w["members"]:
+                    b = cand[q]
+                    info = old.get(b.name)
+                    if info is None or info.backend is not b or (q in w["readded"] and info.weight != 1):
+                        info = BackendInfo(backend=b, weight=1)
+                    ent._backends[b.name] = info
+                    info.total_requests = int(stats["rt_taken"][off + q])
+                if i in g.rr_base:
+                    ent.strategy._index = g.rr_base[i] + selections    # (bound behind every window: absolute, not added once more)
+                if hasattr(ent.strategy, "set_weight") and "weight_set" in w:
+                    for q in w["weight_set"]:                        # a canary deployer's set_weight calls: the device's weights
+                        ent.strategy._weights[cand[q].name] = int(w["weights"][q])
+                elif hasattr(ent.strategy, "set_weight"):
+                    for b in pool[:w["next_instance_id"]] + [cand[q] for q in w["readded"]]:
+                        ent.strategy._weights[b.name] = 1            # add_backend's set_weight(backend, 1)
+                if isinstance(ent.strategy, WeightedRoundRobin) and h["current_weights"] is not None:
+                    ent.strategy._selections = selections
+                    ent.strategy._current_weights = {cand[q].name: v for q, v in sorted(h["current_weights"].items())}
+                continue
             for q, b in enumerate(ent.all_backends):
                 ent._backends[b.name].total_requests = int(stats["rt_taken"][off + q])
             if health is not None:
@@ -1492,6 +1800,29 @@ def write_back_general(g: GeneralGraph, stats: dict, rec_node: np.ndarray, rec_t
                 st._selections = selections
                 st._current_weights = ({b.name: w * selections - sum(ws) * int(stats["rt_taken"][off + q])
                                         for q, (b, w) in enumerate(zip(ent.all_backends, ws))} if selections else {})
+        elif isinstance(ent, CanaryDeployer):
+            w = deployers[i]
+            (ent._deployments_started, ent._deployments_completed, ent._deployments_rolled_back, ent._stages_completed,
+             ent._evaluations_performed, ent._evaluations_passed, ent._evaluations_failed) = (w[k] for k in GraphEngine._CANARY_NAMES[:7])
+            ent.state = CanaryState(status=N.CANARY_STATUS[w["status"]], current_stage=w["current_stage"], total_stages=w["total_stages"],
+                                    canary_traffic_pct=w["traffic_pct"])
+            _dn, initial, pool = g.deployed[int(a.target[i])]
+            cand = initial + pool
+            ent._canary = pool[0] if w["has_canary"] else None
+            ent._baseline_backends = [cand[q] for q in w["baseline"]]
+            ent._stage_start_time = Instant(w["stage_start_ns"]) if w["stage_start_ns"] >= 0 else None
+        elif isinstance(ent, RollingDeployer):
+            w = deployers[i]
+            (ent._deployments_started, ent._deployments_completed, ent._deployments_rolled_back, ent._instances_replaced,
+             ent._health_checks_performed, ent._health_checks_passed, ent._health_checks_failed) = (w[k] for k in GraphEngine._DEPLOYER_NAMES[:7])
+            ent.state = DeploymentState(status=N.DEPLOYMENT_STATUS[w["status"]], total_instances=w["total_instances"], replaced=w["replaced"],
+                                        failed=w["failed"], current_batch=w["current_batch"])
+            ent._next_instance_id, ent._health_fail_count = w["next_instance_id"], w["health_fail_count"]
+            _dn, initial, pool = g.deployed[int(a.target[i])]
+            cand = initial + pool
+            ent._old_backends, ent._new_backends = [cand[q] for q in w["old"]], [cand[q] for q in w["new"]]
+            ent._current_batch_old, ent._current_batch_new = [cand[q] for q in w["batch_old"]], [cand[q] for q in w["batch_new"]]
+            ent._health_pass_count = {cand[q].name: v for q, v in sorted(w["pass_count"].items())}
         elif isinstance(ent, AutoScaler):
             w = scalers[i]
             (ent._evaluations, ent._scale_out_count, ent._scale_in_count, ent._instances_added, ent._instances_removed,

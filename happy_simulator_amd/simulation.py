@@ -14,7 +14,7 @@ from .core.temporal import Instant
 from .engine import StationEngine
 from .graph_engine import (DEFAULT_MAX_EVENTS, MAX_PARTS, GeneralGraph, GraphEngine, PartRun, keyless_hazard, lower_general, split_parts,
                            write_back_general)
-from .entities import AutoScaler, BatchProcessor, Bulkhead, Client, ConveyorBelt, Entity, GateController, HealthChecker, LoadBalancer, Network, Server, TimeoutWrapper
+from .entities import CanaryDeployer, RollingDeployer, AutoScaler, BatchProcessor, Bulkhead, Client, ConveyorBelt, Entity, GateController, HealthChecker, LoadBalancer, Network, Server, TimeoutWrapper
 from .faults import FaultSchedule, LinkFaultEvent
 from .lowering import (LazyRecords, LbGraph, LoweredGraph, UnsupportedTopology, attach_lb_probes, attach_probes, find_load_balancer, lower,
                        plain_probe_arrays, write_back_plain_probes,
@@ -60,7 +60,7 @@ class Simulation:
             raise UnsupportedTopology(f"fault schedule {type(fault_schedule).__name__} is not a lowered FaultSchedule")
         self._faults = fault_schedule._start(self) if fault_schedule is not None else []
         for ent in self._entities:                 # the clock every listed entity is handed (core/simulation.py:118-135): a
-            if isinstance(ent, (HealthChecker, AutoScaler)):     # checker's (a scaler's) start() reads `now` from it
+            if isinstance(ent, (HealthChecker, AutoScaler, RollingDeployer, CanaryDeployer)):     # checker's (a scaler's) start(), a deployer's deploy() read `now` from it
                 ent._sim_start = self._start_time
             if isinstance(ent, Client):            # ... and a Client's send_request()
                 ent._sim = self
@@ -147,11 +147,24 @@ class Simulation:
                 per[id(ev.target)] = per.get(id(ev.target), 0) + 1
         return max(per.values(), default=1)
 
+    def _has_deployers(self) -> bool:
+        """A RollingDeployer among the entities: a LoadBalancer whose backends are replaced during the run, which only the single-heap
+        loop follows."""
+        return any(isinstance(e, (RollingDeployer, CanaryDeployer)) for e in self._entities)
+
+    def _deploys(self) -> dict:
+        """id(deployer) -> its scheduled deploy() Events: what its instance pool is sized by."""
+        per: dict[int, int] = {}
+        for ev in self._scheduled:
+            if isinstance(ev.target, (RollingDeployer, CanaryDeployer)) and not ev.cancelled:
+                per[id(ev.target)] = per.get(id(ev.target), 0) + 1
+        return per
+
     def _lower_general(self) -> GeneralGraph:
         """lower_general over this Simulation, with the horizon and the scheduled start() Events its AutoScalers' pools are sized by."""
         end_ns = None if self._end_time == Instant.Infinity else self._end_time.nanoseconds
         return lower_general(self._sources, self._entities, self._probes, start_ns=self._start_time.nanoseconds, end_ns=end_ns,
-                             scaler_starts=self._scaler_starts())
+                             scaler_starts=self._scaler_starts(), deploys=self._deploys())
 
     def _has_wrappers(self) -> bool:
         """A Bulkhead or a TimeoutWrapper among the entities or as a Source's target: completion hooks and per-request ids, which only
@@ -171,6 +184,9 @@ class Simulation:
         return any(isinstance(e, (BatchProcessor, ConveyorBelt, GateController)) for e in self._entities + firsts)
 
     def lowered(self) -> "LoweredGraph | LbGraph | GeneralGraph":
+        if self._graph is None and self._has_deployers():
+            self._graph = self._lower_general()
+            self._station_refusal = "the station, network and pipeline engines do not lower a RollingDeployer or a CanaryDeployer"
         if self._graph is None and self._has_scalers():
             self._graph = self._lower_general()
             self._station_refusal = "the station, network and pipeline engines do not lower an AutoScaler"
@@ -479,6 +495,20 @@ class Simulation:
                                               "instance pool was sized for fewer): schedule them before lowered()")
                 sched.append((i, ev.time.nanoseconds))
                 continue
+            if a.kind[i] in (N.NODE_ROLLING_DEPLOYER, N.NODE_CANARY_DEPLOYER):
+                # the Event deploy() returns: no daemon, no Request, at any time the caller set
+                rolling = a.kind[i] == N.NODE_ROLLING_DEPLOYER
+                if ev.event_type != ("_rolling_deploy_start" if rolling else "_canary_deploy_start") or ev.daemon:
+                    raise UnsupportedTopology(f"scheduled event {ev!r}: only the Event deploy() returns is lowered for a "
+                                              f"{'RollingDeployer' if rolling else 'CanaryDeployer'}")
+                if cancelled_ns:
+                    raise UnsupportedTopology("cancelled Events in front of live ones are not lowered on the single-heap path")
+                n_starts[i] = n_starts.get(i, 0) + 1
+                if n_starts[i] > g.deploys.get(i, 0):
+                    raise UnsupportedTopology(f"scheduled event {ev!r}: deploy() Events scheduled after the graph was lowered (the deployer's "
+                                              "instance pool was sized for fewer): schedule them before lowered()")
+                sched.append((i, ev.time.nanoseconds))
+                continue
             if a.kind[i] == N.NODE_GATE and ev.event_type in ("_GateOpen", "_GateClose"):
                 # one Event of GateController.start_events(): a daemon without a Request
                 if not ev.daemon:
@@ -559,9 +589,11 @@ class Simulation:
         rec = eng.records()
         health, wrappers, clients, flows = g.arrays.has_health, g.arrays.has_wrappers, g.arrays.has_clients, g.arrays.has_flows
         scalers = g.arrays.has_scalers
+        deployers = g.arrays.has_deployers or g.arrays.has_canaries
         write_back_general(g, stats, *rec, device=self._device, health=eng.health if health else None,
                            wrapper=eng.wrapper if wrappers else None, client=eng.client if clients else None, flow=eng.flow if flows else None,
-                           queue=eng.queue_policy if g.arrays.has_queue_policies else None, scaler=eng.scaler if scalers else None)
+                           queue=eng.queue_policy if g.arrays.has_queue_policies else None, scaler=eng.scaler if scalers else None,
+                           deployer=eng.deployer if deployers else None, canary=eng.canary if deployers else None)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
         if health:
@@ -583,6 +615,10 @@ class Simulation:
         if scalers:
             # the scalers' `_autoscaler_evaluate` Events: one more internal kind, counted the same way
             self._autoscaler_by_kind = np.array([eng.scaler_events()], np.int64)
+        if deployers:
+            # the deployers' Events: seven more internal kinds, counted the same way
+            self._deployer_by_kind = eng.deployer_events()
+            self._canary_by_kind = eng.canary_events()
         if (health or wrappers or clients or flows or g.arrays.has_queue_policies) and not self._faults:
             self._internal_by_kind = eng.faults()[1]
         if self._faults:

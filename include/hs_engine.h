@@ -758,7 +758,9 @@ typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK
                              HS_NODE_BATCH_PROCESSOR = 12, /* BatchProcessor, ConveyorBelt, GateController: `target` = their downstream; */
                              HS_NODE_CONVEYOR = 13,        /* everything else: hs_graph_set_flow */
                              HS_NODE_GATE = 14,
-                             HS_NODE_AUTO_SCALER = 15      /* AutoScaler: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_auto_scaler */
+                             HS_NODE_AUTO_SCALER = 15,     /* AutoScaler: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_auto_scaler */
+                             HS_NODE_ROLLING_DEPLOYER = 16,/* RollingDeployer: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_rolling_deployer */
+                             HS_NODE_CANARY_DEPLOYER = 17  /* CanaryDeployer: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_canary_deployer */
 } hs_node_kind;
 
 typedef struct hs_graph_config {
@@ -1127,6 +1129,85 @@ int hs_graph_set_auto_scaler(hs_graph *g, int32_t node, int32_t lb_node, int32_t
                              const double *step_threshold, const int32_t *step_adjustment, int32_t min_instances, int32_t max_instances,
                              double interval_s, double scale_out_cooldown_s, double scale_in_cooldown_s, int32_t n_pool, int32_t running);
 int hs_graph_get_auto_scaler(hs_graph *g, int32_t node, int64_t *state, int64_t *history, int64_t history_cap, uint8_t *member, int64_t *events);
+/* RollingDeployer (components/deployment/rolling_deployer.py): replaces the backends of a LoadBalancer batch by batch with new
+ * instances, probing every new instance until it has passed `healthy_threshold` health checks, and rolls back after more than
+ * `max_failures` failed ones.  The instances are a POOL of dormant Server nodes as an AutoScaler's are: the last `n_pool` targets of the
+ * LoadBalancer, instance k = pool target k - 1.  Unlike a scaler a deployer removes INITIAL backends, can re-add one behind newer
+ * instances and can empty the list, so the LoadBalancer's members are an ordered list of slots in insertion order (`all_backends` is a
+ * dict's order): adding appends, removing keeps the order of the rest.  A re-added backend starts with total_requests 0 and weight 1
+ * (add_backend's BackendInfo and set_weight).  RoundRobin, the live WeightedRoundRobin, LeastConnections and WeightedLeastConnections
+ * select over that list on the lone lane; the other strategies: HS_E_UNSUPPORTED.  A graph with a deployer runs an instantiation of
+ * the loop of its own.
+ *
+ * hs_graph_set_rolling_deployer, before the first run (HS_E_STATE afterwards), once per deployer node: the LoadBalancer node, batch_size
+ * (>= 1), health_check_interval in seconds (>= 1 ns, finite), healthy_threshold (>= 1), max_failures and the pool's size (at most
+ * HS_DEPLOYER_MAX_POOL).  A second deployer on one LoadBalancer, a deployer next to an AutoScaler or a HealthChecker on it and an
+ * initially unhealthy backend under a deployer: HS_E_UNSUPPORTED.  hs_graph_schedule on the deployer node is the
+ * `_rolling_deploy_start` Event deploy() returns (no daemon).  The handlers restate _start_deployment, _replace_batch,
+ * _run_health_check, _handle_health_pass, _handle_health_timeout, _rollback and _complete; a probe is a Request of the new Server whose
+ * completion hook names the deployer.  A batch that needs an instance beyond the pool ends the run with HS_E_OVERFLOW and a message
+ * that names the deployer.
+ *
+ * hs_graph_get_rolling_deployer, after a run (any output may be NULL), B = the LoadBalancer's targets: state[HS_DEPLOYER_FIELDS] =
+ * deployments_started, deployments_completed, deployments_rolled_back, instances_replaced, health_checks_performed,
+ * health_checks_passed, health_checks_failed, state.status (hs_deployment_status), total_instances, replaced, failed, current_batch,
+ * _next_instance_id, _health_fail_count, len(_old_backends), len(_new_backends), len(_current_batch_old), len(_current_batch_new),
+ * members of the LoadBalancer, 0; lists[4 * B] = _old_backends, _new_backends, _current_batch_old, _current_batch_new as slots of the
+ * LoadBalancer, B places each, -1 behind a list's end; members[B] = the LoadBalancer's members IN ORDER, -1 behind the end; pass[B] =
+ * _health_pass_count by slot (-1: the name has no entry); readded[B] = 1 for a backend a rollback added again (its BackendInfo is a
+ * new one: weight 1, total_requests from 0); events[HS_DEPLOYER_KINDS + 2] = the graph's deployer Events by kind (start,
+ * replace_batch, health_check, health_pass, health_timeout, rollback, complete): events_processed == sum(events_by_kind) + the other
+ * internal kinds + sum(events[0 .. 6]); behind them events[7] / events[8] = the member lists the graph compacted behind a removal on
+ * the lone lane / with all 64 lanes (from 32 members on the 64 lanes compact the list by membership, a ballot and a prefix count per
+ * chunk of 64 entries, order kept; hs_debug_graph_flags bit 0 keeps every compaction on the lone lane, bit 1 hands every one to the
+ * wavefront; both leave the same list).  node = -1 with every other output NULL: the event counts alone. */
+typedef enum hs_deployment_status { HS_DEPLOYMENT_IDLE = 0, HS_DEPLOYMENT_IN_PROGRESS = 1, HS_DEPLOYMENT_COMPLETED = 2, HS_DEPLOYMENT_ROLLED_BACK = 3 } hs_deployment_status;
+#define HS_DEPLOYER_KINDS 7
+#define HS_DEPLOYER_MAX_POOL 4096
+#define HS_DEPLOYER_FIELDS 20
+int hs_graph_set_rolling_deployer(hs_graph *g, int32_t node, int32_t lb_node, int32_t batch_size, double interval_s, int32_t healthy_threshold,
+                                  int64_t max_failures, int32_t n_pool);
+int hs_graph_get_rolling_deployer(hs_graph *g, int32_t node, int64_t *state, int32_t *lists, int32_t *members, int32_t *pass, int32_t *readded,
+                                  int64_t *events);
+/* CanaryDeployer (components/deployment/canary_deployer.py): ONE new instance `{name}_canary` joins a LoadBalancer -- its last target,
+ * a dormant Server like a rolling deployer's pool of one --, the strategy's weights are rewritten stage by stage
+ * (`_set_traffic_weight`: max(1, int(pct * 100)) for the canary, max(1, int((1.0 - pct) * 100 / num_baseline)) for every baseline
+ * backend, in binary64 with separate roundings; all 1 from pct >= 1.0 on; nothing without a baseline; a no-op unless the strategy is
+ * WeightedRoundRobin or WeightedLeastConnections), every `evaluation_interval` the evaluator compares the canary with the baseline's
+ * plain left-to-right average, and the deployment ends with a promotion -- the whole baseline leaves in one compaction pass, every
+ * remaining member's weight becomes 1 -- or a rollback (the canary leaves, the weights likewise).  The member list is the ordered one
+ * of a deployed LoadBalancer (see above); a graph with a canary deployer runs the deployers' instantiation and keeps, per node, the
+ * Servers' `_service_times` as a running binary64 sum and a count taken at the draw.
+ *
+ * hs_graph_set_canary_deployer, before the first run (HS_E_STATE afterwards), once per deployer node: the LoadBalancer node, n_stages
+ * (1 .. HS_CANARY_MAX_STAGES) pairs traffic_percentage[k] / evaluation_period[k] (finite), the evaluator -- HS_CANARY_ERROR_RATE:
+ * requests_rejected / (requests_completed + requests_rejected), ev_max = max_error_rate; HS_CANARY_LATENCY: the mean of the service
+ * times drawn so far, ev_max = max_latency --, its threshold_multiplier and the interval in seconds.  A second deployer on one
+ * LoadBalancer, a deployer next to an AutoScaler or a HealthChecker on it, an initially unhealthy backend: HS_E_UNSUPPORTED.
+ * hs_graph_schedule on the deployer node is the `_canary_deploy_start` Event deploy() returns (no daemon); one per deployer.
+ *
+ * hs_graph_get_canary_deployer, after a run (any output may be NULL), B = the LoadBalancer's targets: state[HS_CANARY_FIELDS] =
+ * deployments_started, deployments_completed, deployments_rolled_back, stages_completed, evaluations_performed, evaluations_passed,
+ * evaluations_failed, state.status (hs_canary_status), current_stage, total_stages, 1 if `canary` is set, _stage_start_time ns (-1:
+ * None), len(_baseline_backends), members of the LoadBalancer, 0, 0; *traffic_pct = state.canary_traffic_pct; baseline[B] =
+ * _baseline_backends as slots, -1 behind the end; members[B] = the LoadBalancer's members IN ORDER; weights[B] = the strategy's weight
+ * of every slot now; weight_set[B] = 1 where set_weight was called for the slot during the run; service_sum[B] / service_count[B] = the
+ * sum and count of every target's service times; events[HS_CANARY_KINDS] = the graph's canary Events by kind (start, stage_start,
+ * evaluate, promote, rollback, complete).  node = -1: the event counts alone. */
+typedef enum hs_canary_status { HS_CANARY_IDLE = 0, HS_CANARY_IN_PROGRESS = 1, HS_CANARY_PROMOTING = 2, HS_CANARY_ROLLED_BACK = 3, HS_CANARY_COMPLETED = 4 } hs_canary_status;
+typedef enum hs_canary_evaluator { HS_CANARY_ERROR_RATE = 0, HS_CANARY_LATENCY = 1 } hs_canary_evaluator;
+#define HS_CANARY_KINDS 6
+#define HS_CANARY_MAX_STAGES 16
+#define HS_CANARY_FIELDS 16
+int hs_graph_set_canary_deployer(hs_graph *g, int32_t node, int32_t lb_node, int32_t n_stages, const double *traffic_percentage,
+                                 const double *evaluation_period, int32_t evaluator, double ev_max, double ev_multiplier, double interval_s);
+int hs_graph_get_canary_deployer(hs_graph *g, int32_t node, int64_t *state, double *traffic_pct, int32_t *baseline, int32_t *members,
+                                 int32_t *weights, int32_t *weight_set, double *service_sum, int64_t *service_count, int64_t *events);
+/* Debug / tests only (the null stream, its own allocations): the compaction of a deployed LoadBalancer's member list on the device.
+ * list[len] = slots in [0, n_slots) in insertion order, member[n_slots] = the membership word of every slot; the entries whose word is
+ * 0 leave, the others keep their order: list[0 .. *out_len) afterwards.  wave = 0: the lone lane; 1: all 64 lanes (a ballot and a
+ * prefix count per chunk of 64 entries).  Tests require both to leave the same list. */
+int hs_debug_compact_members(int32_t device, int32_t n_slots, int32_t len, int32_t *list, const uint8_t *member, int32_t wave, int32_t *out_len);
 /* Debug / tests only (the null stream, its own allocations): CoDelQueue._control_law's step on the device, one (count, interval_s) pair
  * per thread: out_ns[i] = Duration.from_seconds(interval_s[i] / sqrt(count[i])) in ns (count >= 1, 0 < interval <= 4e9).  Tests compare
  * it with CPython. */
