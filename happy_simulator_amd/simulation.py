@@ -28,6 +28,30 @@ _DEFAULT_SEED = 42
 LAZY_PROBES_MIN = 256      # plain-chain runs with more Probes than this leave the samples on the device until a Data is read
 
 
+# Entity families only the single-heap loop follows, in the order their refusals win: (classes, whether a Source's target counts
+# next to the listed entities, the station engines' refusal).  Backends that join and leave, completion hooks and per-request ids,
+# retries, stations that hold Requests back and release them together.
+_NOT_ON_STATIONS = "the station, network and pipeline engines do not lower "
+_SINGLE_HEAP_ONLY = (
+    ((RollingDeployer, CanaryDeployer), False, _NOT_ON_STATIONS + "a RollingDeployer or a CanaryDeployer"),
+    (AutoScaler, False, _NOT_ON_STATIONS + "an AutoScaler"),
+    ((BatchProcessor, ConveyorBelt, GateController), True, _NOT_ON_STATIONS + "BatchProcessor, ConveyorBelt or GateController"),
+    (Client, True, _NOT_ON_STATIONS + "a Client"),
+    ((Bulkhead, TimeoutWrapper), True, _NOT_ON_STATIONS + "Bulkhead or TimeoutWrapper"),
+)
+
+# The internal Event kinds of the families (events_processed counts them, events_by_kind does not), like the limiters' and the
+# faults': (GraphArrays flags of which one is set, the Simulation's attribute, the engine's reader of the counts by kind).
+_BY_KIND = (
+    (("has_health",), "_health_by_kind", "health_events"),                   # the checkers' cycle / response / timeout Events
+    (("has_wrappers",), "_resilience_by_kind", "wrapper_events"),            # Bulkhead and TimeoutWrapper request / response / timeout
+    (("has_clients",), "_client_by_kind", "client_events"),                  # the Clients' request / response / timeout Events
+    (("has_scalers",), "_autoscaler_by_kind", "scaler_events"),              # the one `_autoscaler_evaluate` kind
+    (("has_deployers", "has_canaries"), "_deployer_by_kind", "deployer_events"),   # the deployers' seven kinds
+    (("has_deployers", "has_canaries"), "_canary_by_kind", "canary_events"),
+)
+
+
 def seed(value: int) -> None:
     """Default Philox key for Simulations created afterwards (the reference's idiom is `random.seed(42)`)."""
     global _DEFAULT_SEED
@@ -134,11 +158,6 @@ class Simulation:
         not the full one), which only the single-heap loop follows."""
         return any(isinstance(e, HealthChecker) or (isinstance(e, LoadBalancer) and e.unhealthy_backends) for e in self._entities)
 
-    def _has_scalers(self) -> bool:
-        """An AutoScaler among the entities: a LoadBalancer whose backends join and leave during the run, which only the single-heap
-        loop follows."""
-        return any(isinstance(e, AutoScaler) for e in self._entities)
-
     def _scaler_starts(self) -> int:
         """The most `_autoscaler_evaluate` Events scheduled for one scaler: every one begins a chain of evaluations."""
         per: dict[int, int] = {}
@@ -146,11 +165,6 @@ class Simulation:
             if isinstance(ev.target, AutoScaler) and not ev.cancelled:
                 per[id(ev.target)] = per.get(id(ev.target), 0) + 1
         return max(per.values(), default=1)
-
-    def _has_deployers(self) -> bool:
-        """A RollingDeployer among the entities: a LoadBalancer whose backends are replaced during the run, which only the single-heap
-        loop follows."""
-        return any(isinstance(e, (RollingDeployer, CanaryDeployer)) for e in self._entities)
 
     def _deploys(self) -> dict:
         """id(deployer) -> its scheduled deploy() Events: what its instance pool is sized by."""
@@ -166,46 +180,22 @@ class Simulation:
         return lower_general(self._sources, self._entities, self._probes, start_ns=self._start_time.nanoseconds, end_ns=end_ns,
                              scaler_starts=self._scaler_starts(), deploys=self._deploys())
 
-    def _has_wrappers(self) -> bool:
-        """A Bulkhead or a TimeoutWrapper among the entities or as a Source's target: completion hooks and per-request ids, which only
-        the single-heap loop follows."""
+    def _single_heap_only(self) -> str | None:
+        """What of this Simulation only the single-heap loop follows, as the station engines' refusal of it (None: nothing)."""
         firsts = [getattr(getattr(s, "_event_provider", None), "_target", None) for s in self._sources]
-        return any(isinstance(e, (Bulkhead, TimeoutWrapper)) for e in self._entities + firsts)
-
-    def _has_clients(self) -> bool:
-        """A Client among the entities or as a Source's target: retries, which only the single-heap loop follows."""
-        firsts = [getattr(getattr(s, "_event_provider", None), "_target", None) for s in self._sources]
-        return any(isinstance(e, Client) for e in self._entities + firsts)
-
-    def _has_flows(self) -> bool:
-        """A BatchProcessor, ConveyorBelt or GateController among the entities or as a Source's target: stations that hold Requests
-        back and release them together, which only the single-heap loop follows."""
-        firsts = [getattr(getattr(s, "_event_provider", None), "_target", None) for s in self._sources]
-        return any(isinstance(e, (BatchProcessor, ConveyorBelt, GateController)) for e in self._entities + firsts)
+        for classes, aimed_at, refusal in _SINGLE_HEAP_ONLY:
+            if any(isinstance(e, classes) for e in (self._entities + firsts if aimed_at else self._entities)):
+                return refusal
+        if self._faults:                               # (node faults run where every Event is popped one by one)
+            return _NOT_ON_STATIONS + "fault schedules"
+        return _NOT_ON_STATIONS + "health checks or unhealthy backends" if self._has_health() else None
 
     def lowered(self) -> "LoweredGraph | LbGraph | GeneralGraph":
-        if self._graph is None and self._has_deployers():
-            self._graph = self._lower_general()
-            self._station_refusal = "the station, network and pipeline engines do not lower a RollingDeployer or a CanaryDeployer"
-        if self._graph is None and self._has_scalers():
-            self._graph = self._lower_general()
-            self._station_refusal = "the station, network and pipeline engines do not lower an AutoScaler"
-        if self._graph is None and self._has_flows():
-            self._graph = self._lower_general()
-            self._station_refusal = "the station, network and pipeline engines do not lower BatchProcessor, ConveyorBelt or GateController"
-        if self._graph is None and self._has_clients():
-            self._graph = self._lower_general()
-            self._station_refusal = "the station, network and pipeline engines do not lower a Client"
-        if self._graph is None and self._has_wrappers():
-            self._graph = self._lower_general()
-            self._station_refusal = "the station, network and pipeline engines do not lower Bulkhead or TimeoutWrapper"
-        if self._graph is None and not self._faults and self._has_health():
-            self._graph = self._lower_general()
-            self._station_refusal = "the station, network and pipeline engines do not lower health checks or unhealthy backends"
-        if self._graph is None and self._faults:
-            # node faults run where every Event is popped one by one: the single-heap loop
-            self._graph = self._lower_general()
-            self._station_refusal = "the station, network and pipeline engines do not lower fault schedules"
+        if self._graph is None:
+            refusal = self._single_heap_only()
+            if refusal is not None:
+                self._graph = self._lower_general()
+                self._station_refusal = refusal
         if self._graph is None:
             plain = plain_chains(self._sources, self._entities)      # (n plain chains: no LoadBalancer among them, one pass less)
             if plain is not None:
@@ -267,11 +257,7 @@ class Simulation:
             eng.run(end_ns)
             es = eng.summary()
             write_back_lb(g, eng.stats(), eng)
-        self._engine_summary = es
-        self._events_processed = es.events_processed
-        self._current_time = Instant(es.final_time_ns)
-        self._summary = self._build_summary(_time.monotonic() - wall0)
-        return self._summary
+        return self._finish(es, _time.monotonic() - wall0)
 
     def __del__(self):
         try:                       # results this run has not bound to its entities yet (entities._PENDING) outlive the Simulation
@@ -389,14 +375,10 @@ class Simulation:
         # heap when the run ended with nothing left beyond end_time (core/simulation.py:472-477)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
-        self._engine_summary = es
-        self._events_processed = es.events_processed
-        self._current_time = Instant(es.final_time_ns)
-        self._summary = self._build_summary(_time.monotonic() - wall0)
-        return self._summary
+        return self._finish(es, _time.monotonic() - wall0)
 
     def _run_general(self, g: GeneralGraph, auto: bool, wall0: float) -> SimulationSummary:
-        """A graph outside the station shape (graph_engine.lower_general) on the device's single-heap loop."""
+        """A graph outside the station shape (graph_lowering.lower_general) on the device's single-heap loop."""
         end_ns, start_ns, sched, cancelled_ns = self._general_prepare(g, auto)
         # (one component per heap while there are at most MAX_PARTS: components that SHARE a heap are checked as one -- two Probes of one
         #  interval, two constant Sources of one rate in different components then look like a mixed timestamp group: undecided)
@@ -587,39 +569,20 @@ class Simulation:
         es = eng.summary()
         stats = eng.stats()
         rec = eng.records()
-        health, wrappers, clients, flows = g.arrays.has_health, g.arrays.has_wrappers, g.arrays.has_clients, g.arrays.has_flows
-        scalers = g.arrays.has_scalers
-        deployers = g.arrays.has_deployers or g.arrays.has_canaries
-        write_back_general(g, stats, *rec, device=self._device, health=eng.health if health else None,
-                           wrapper=eng.wrapper if wrappers else None, client=eng.client if clients else None, flow=eng.flow if flows else None,
-                           queue=eng.queue_policy if g.arrays.has_queue_policies else None, scaler=eng.scaler if scalers else None,
-                           deployer=eng.deployer if deployers else None, canary=eng.canary if deployers else None)
+        a = g.arrays
+        write_back_general(g, stats, *rec, device=self._device, engine=eng)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
-        if health:
-            # the checkers' cycle / response / timeout Events: internal kinds like the limiters' and the faults' (events_processed
-            # counts them, events_by_kind does not)
-            self._health_by_kind = eng.health_events()
-        if wrappers:
-            # the wrappers' request / response / timeout Events: six more internal kinds, counted the same way
-            self._resilience_by_kind = eng.wrapper_events()
-        if clients:
-            # the Clients' request / response / timeout Events: three more internal kinds, counted the same way
-            self._client_by_kind = eng.client_events()
-        if flows:
-            # the flow entities' Events: eight more internal kinds, counted the same way; a `_BatchTimeout` popped after its batch had
-            # started was cancelled (core/simulation.py:326-329)
+        for flags, attr, reader in _BY_KIND:
+            if any(getattr(a, f) for f in flags):
+                setattr(self, attr, np.atleast_1d(getattr(eng, reader)()))       # (scaler_events is the one count itself)
+        if a.has_flows:
+            # the flow entities' eight kinds and, last, the `_BatchTimeout` Events popped after their batch had started: those were
+            # cancelled (core/simulation.py:326-329)
             fe = eng.flow_events()
             self._flow_by_kind = fe[:N.FLOW_KINDS]
             self._events_cancelled += int(fe[N.FLOW_KINDS])
-        if scalers:
-            # the scalers' `_autoscaler_evaluate` Events: one more internal kind, counted the same way
-            self._autoscaler_by_kind = np.array([eng.scaler_events()], np.int64)
-        if deployers:
-            # the deployers' Events: seven more internal kinds, counted the same way
-            self._deployer_by_kind = eng.deployer_events()
-            self._canary_by_kind = eng.canary_events()
-        if (health or wrappers or clients or flows or g.arrays.has_queue_policies) and not self._faults:
+        if (a.has_health or a.has_wrappers or a.has_clients or a.has_flows or a.has_queue_policies) and not self._faults:
             self._internal_by_kind = eng.faults()[1]
         if self._faults:
             crashed, internal, popped_cancelled = eng.faults()
@@ -645,11 +608,7 @@ class Simulation:
                         f.link.packet_loss_rate = f.leaves if loss is None else loss.leaves
                     f.link._loss_draws = draws
                     self._link_fault_state[id(f.link)] = (-1 if lat is None else lat.index, -1 if loss is None else loss.index)
-        self._engine_summary = es
-        self._events_processed = es.events_processed
-        self._current_time = Instant(es.final_time_ns)
-        self._summary = self._build_summary(wall_s)
-        return self._summary
+        return self._finish(es, wall_s)
 
     def _run_plain(self, g: LoweredGraph, arrays, end_ns: int, wall0: float, probe_where=None) -> SimulationSummary:
         """n plain Source -> Server -> [Sink] chains (lowering.PlainChains): no per-station Python objects on the way in, Python
@@ -675,11 +634,7 @@ class Simulation:
         if probe_where:
             write_back_plain_probes(self._probes, probe_where, records, lazy=lazy_probes)
         self._events_cancelled = 0
-        self._engine_summary = es
-        self._events_processed = es.events_processed
-        self._current_time = Instant(es.final_time_ns)
-        self._summary = self._build_summary(_time.monotonic() - wall0)
-        return self._summary
+        return self._finish(es, _time.monotonic() - wall0)
 
     def _log_cap(self, g, horizon_s: float, arrays, is_net: bool) -> int:
         if self._log_capacity:
@@ -714,10 +669,14 @@ class Simulation:
         write_back_shared_sink_probes(g)
         drained = es.final_time_ns <= end_ns
         self._events_cancelled = sum(1 for t in cancelled_ns if drained or t <= es.final_time_ns)
+        return self._finish(es, _time.monotonic() - wall0)
+
+    def _finish(self, es, wall_s: float) -> SimulationSummary:
+        """What every engine's run leaves on the Simulation: its summary `es`, the clock and the SimulationSummary."""
         self._engine_summary = es
         self._events_processed = es.events_processed
         self._current_time = Instant(es.final_time_ns)
-        self._summary = self._build_summary(_time.monotonic() - wall0)
+        self._summary = self._build_summary(wall_s)
         return self._summary
 
     # core/simulation.py:543-591
