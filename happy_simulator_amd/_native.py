@@ -81,6 +81,7 @@ RUN_ONE_LANE, RUN_ONE_LANE_UNI, RUN_WIDE, RUN_WAVE, RUN_TANDEM, RUN_SINGLE_HEAP 
 RUN_F64_TIMES, RUN_NET_ASYNC, RUN_NET_ASYNC_UNI, RUN_NET_WINDOWED, RUN_NET_SEGMENTED = 64, 128, 256, 512, 1024
 RUN_LANES_SHIFT = 16        # bits 16..23: lanes per LP (RUN_WIDE) or LPs per workgroup (RUN_WAVE)
 LB_RUN_F64_TIMES, LB_RUN_MARGIN, LB_RUN_LEAN, LB_RUN_SCAN, LB_RUN_SINK_PACKED, LB_RUN_SINK_GATHER = 1, 2, 4, 8, 16, 32
+LB_RUN_DENSE = 64
 ABI_VERSION = 16
 IPC_HANDLE_BYTES = 64
 
@@ -420,6 +421,8 @@ def lib():
     L.hs_engine_run_path.argtypes = [C.c_void_p]
     L.hs_lb_run_path.restype = C.c_int
     L.hs_lb_run_path.argtypes = [C.c_void_p]
+    L.hs_lb_sort_plan.restype = C.c_int
+    L.hs_lb_sort_plan.argtypes = [C.c_void_p, C.c_void_p]
     L.hs_engine_synchronize.restype = C.c_int
     L.hs_engine_synchronize.argtypes = [C.c_void_p]
     L.hs_engine_bench_runs.restype = C.c_int
@@ -622,7 +625,7 @@ EXPORTED_SYMBOLS = (
     "hs_last_error", "hs_last_global_error", "hs_engine_destroy", "hs_debug_draws", "hs_debug_set_flags",
     "hs_debug_const_div", "hs_debug_time_ops", "hs_debug_async_counters",
     "hs_debug_log", "hs_debug_philox", "hs_debug_stream_walk",
-    "hs_lb_create", "hs_lb_run", "hs_lb_run_path", "hs_lb_bench_runs", "hs_lb_get_summary", "hs_lb_get_stats", "hs_lb_read_sink",
+    "hs_lb_create", "hs_lb_run", "hs_lb_run_path", "hs_lb_sort_plan", "hs_lb_bench_runs", "hs_lb_get_summary", "hs_lb_get_stats", "hs_lb_read_sink",
     "hs_lb_set_probes", "hs_lb_read_probe",
     "hs_lb_latency_stats",
     "hs_lb_ring", "hs_lb_select", "hs_lb_last_error", "hs_lb_destroy", "hs_md5", "hs_debug_radix_sort", "hs_merge_sink_records",

@@ -45,7 +45,10 @@ using namespace hs;
 namespace {
 
 constexpr int kLbBlock = 256;
-constexpr int kLbQCap = 48;                  // in-group FIFO depth per backend (LDS)
+// In-group FIFO depth per backend (LDS, 10 bytes x 256 lanes per entry: 150 KB of the CU's 160 KB, one workgroup per CU as with
+// the 48 entries it had -- tests/test_gpu_lb_runs.py puts 56 Requests of lock-step Sources on one nanosecond of one backend).
+// The event-order loop queues every arrival of a nanosecond before it drains: a burst beyond this depth is refused by name.
+constexpr int kLbQCap = 60;
 constexpr uint32_t kStreamKey = 4;           // stream kind of a Source's client-id draws
 constexpr uint64_t kCrtMask = (1ull << 56) - 1;
 
@@ -515,6 +518,9 @@ struct SlotVal { __device__ __forceinline__ uint64_t operator()(int64_t i) const
 // input order.  Such runs are short (the host picks g so that a bucket holds <= 1 element on average); every element
 // finds its place inside its run by counting the run's smaller (key, position) pairs -- stable -- and the list is
 // written out in full-key order to the other ping-pong buffer.  g <= tb, so a run never spans two backends.
+// "Short" holds on average, not always: one client key under ConsistentHash sends every Request to one backend while the
+// estimate still divides by B, and lock-step constant Sources put dozens of Requests on one nanosecond at a tiny total rate;
+// runs then outgrow the halo and the tile, and the walks below leave LDS for global memory (tests/test_gpu_lb_runs.py).
 // (round 4: a workgroup stages its 1 024 keys + a halo in LDS, so the walk along a run reads LDS instead of one dependent global
 //  load per step: 163 us -> see profiles/; a run that reaches past the halo continues in global memory)
 constexpr int kSegTile = 1024, kSegHalo = 32;
@@ -657,7 +663,8 @@ __global__ void hs_lb_gather_strided(const int64_t *__restrict__ src, int64_t st
     if (k < cnt) out[k] = src[(size_t)k * stride];
 }
 
-// keys-only variant of the run fix-up above (latency statistics)
+// keys-only variant of the run fix-up above (latency statistics).  One thread sorts a whole run by insertion: linear in the
+// run's length when its values are equal or already in order, quadratic when it holds many distinct values out of order.
 __global__ void hs_lb_fix_runs(uint64_t *__restrict__ keys, const int64_t *n_ptr, int g) {
     const int64_t n = *n_ptr;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2064,6 +2071,7 @@ bool lean_gave_up(hs_lb *h) {
 int check_flags(hs_lb *h) {
     LbTotals t;
     HS_HIP(h, hipMemcpy(&t, h->tot, sizeof t, hipMemcpyDeviceToHost));
+    if ((h->run_path & HS_LB_RUN_SCAN) == 0 && !t.use_t) h->run_path |= HS_LB_RUN_DENSE;    // (hs_lb_layout decided on the device)
     if (t.qoverflow) return fail(h, HS_E_UNSUPPORTED, "a same-timestamp event cascade exceeded the in-group queue");
     if (h->radix_err != nullptr) {
         int re = 0;
@@ -2203,7 +2211,9 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
         // full-key order inside those runs afterwards (hs_lb_segments / hs_lb_sink_finish).  Skip whole 8-bit digits while
         // the EXPECTED number of elements per bucket stays <= 1 (runs of two or three, rare longer ones): a bucket of the
         // arrival sort is (one backend, 2^g ns) and sees total_rate / B requests per second on average, a bucket of the
-        // Sink merge is 2^g ns of all completions.
+        // Sink merge is 2^g ns of all completions.  (An estimate: one client key under ConsistentHash or lock-step constant
+        // Sources defeat it with runs of hundreds of elements; the fix-up kernels take runs of any length and
+        // tests/test_gpu_lb_runs.py drives them there.)
         const double per_backend = total_rate / (double)B;
         const int r_arr = (h->tb + h->bb) % kRadixBits;
         h->g_arr = 0;
@@ -2378,6 +2388,12 @@ int hs_lb_create(const hs_lb_config *cfg, const hs_lb_sources *src, const hs_lb_
 }
 
 int hs_lb_run_path(const hs_lb *h) { return h ? h->run_path : 0; }
+
+int hs_lb_sort_plan(const hs_lb *h, int32_t out[6]) {
+    if (!h || !out) return fail(nullptr, HS_E_INVALID, "hs_lb_sort_plan: null argument");
+    out[0] = h->tb; out[1] = h->bb; out[2] = h->g_arr; out[3] = h->g_sink; out[4] = kSegTile; out[5] = kSegHalo;
+    return HS_OK;
+}
 
 int hs_lb_run(hs_lb *h, int64_t end_ns) {
     if (!h) return fail(h, HS_E_INVALID, "hs_lb_run: null handle");

@@ -144,6 +144,12 @@ class LoadBalancerEngine:
         """Which paths the last run took: _native.LB_RUN_* bits (include/hs_engine.h hs_lb_run_path).  Read-only."""
         return int(self._lib.hs_lb_run_path(self._h))
 
+    def sort_plan(self) -> dict:
+        """What the handle's sorts were planned with at creation (include/hs_engine.h hs_lb_sort_plan).  Read-only."""
+        out = (C.c_int32 * 6)()
+        self._check(self._lib.hs_lb_sort_plan(self._h, out))
+        return dict(zip(("tb", "bb", "g_arr", "g_sink", "seg_tile", "seg_halo"), (int(v) for v in out)))
+
     def set_probes(self, target_kind, target_index, metric, interval_s) -> None:
         """Probe.on(<backend Server> | <Sink>, metric, interval) (include/hs_engine.h `hs_lb_set_probes`): target_kind 0 =
         backend Server, 1 = Sink; metric = N.PROBE_METRICS id; once, before the first run."""

@@ -595,7 +595,14 @@ int hs_lb_set_weights(hs_lb *h, const int32_t *weights);
 #define HS_LB_RUN_SCAN         (1 << 3)    /* the backends as (max, +) scans (hs_lbk_scan) */
 #define HS_LB_RUN_SINK_PACKED  (1 << 4)    /* shared Sink merge: created_at << slot_bits | slot in one word */
 #define HS_LB_RUN_SINK_GATHER  (1 << 5)    /* shared Sink merge: created_at gathered by slot */
+#define HS_LB_RUN_DENSE        (1 << 6)    /* backends outside the scan read the dense segments, not [k][backend]: debug flag 4, no
+                                            * rows allocated, or the busiest backend had more Requests than the rows allocated */
 int hs_lb_run_path(const hs_lb *h);
+/* The sorts' plan, fixed at hs_lb_create (read-only, for tests that must cross these sizes):
+ * out = { tb, bb, g_arr, g_sink, kSegTile, kSegHalo } -- time and backend bits of the sort key, the low key bits the arrival sort
+ * and the Sink merge skip, and the LDS tile and halo of the kernels that finish the runs those bits leave.  HS_OK, or HS_E_INVALID
+ * on null. */
+int hs_lb_sort_plan(const hs_lb *h, int32_t out[6]);
 /* `repeats` complete runs back to back on the engine's stream; per-run device time of the whole pipeline and of the
  * sort passes alone (HIP events on that stream). */
 int hs_lb_bench_runs(hs_lb *h, int64_t end_ns, int32_t repeats, float *run_ms_out, float *sort_ms_out);

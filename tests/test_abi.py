@@ -39,7 +39,7 @@ def test_run_path_bits_match_the_header(lib):
         assert sym in N.EXPORTED_SYMBOLS and hasattr(lib, sym)
     hdr = open(os.path.join(ROOT, "include", "hs_engine.h")).read()
     bits = {m: 1 << int(v) for m, v in re.findall(r"^#define (HS_(?:LB_)?RUN_[A-Z0-9_]+)\s+\(1 << (\d+)\)", hdr, re.M)}
-    assert len(bits) == 17
+    assert len(bits) == 18
     for name, v in bits.items():
         assert getattr(N, name[3:]) == v, name
     assert lib.hs_engine_run_path(None) == 0 and lib.hs_lb_run_path(None) == 0
