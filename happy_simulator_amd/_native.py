@@ -75,6 +75,10 @@ PROBE_CLIENT_METRICS = {"in_flight_count": 12}              # ... of a Client
 # ... of a BatchProcessor / ConveyorBelt / GateController (a gate's queue_depth is its own metric)
 PROBE_FLOW_METRICS = {"buffer_depth": 13, "items_in_transit": 14, "queue_depth": 15}
 PROBE_SCALER_METRICS = {"current_count": 16}                # ... of an AutoScaler
+PROBE_HEDGE_METRICS = {"in_flight_count": 17}               # ... of a Hedge
+NODE_HEDGE, NODE_FALLBACK = 18, 19
+HEDGE_MAX_HEDGES, HEDGE_MAX_IN_FLIGHT = 65535, 1 << 20      # include/hs_engine.h HS_HEDGE_MAX_HEDGES / HS_HEDGE_MAX_IN_FLIGHT
+HEDGE_KINDS, HEDGE_COUNTERS, FALLBACK_COUNTERS = 7, 8, 9    # HS_HEDGE_KINDS / HS_HEDGE_COUNTERS / HS_FALLBACK_COUNTERS
 PROBE_NONE = 255
 # hs_engine_run_path / hs_lb_run_path: which side of the host-side gates the last run landed on (include/hs_engine.h)
 RUN_ONE_LANE, RUN_ONE_LANE_UNI, RUN_WIDE, RUN_WAVE, RUN_TANDEM, RUN_SINGLE_HEAP = 1, 2, 4, 8, 16, 32
@@ -571,6 +575,13 @@ def lib():
     L.hs_graph_set_canary_deployer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double]
     L.hs_graph_get_canary_deployer.restype = C.c_int
     L.hs_graph_get_canary_deployer.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
+    L.hs_graph_set_hedge.restype = C.c_int
+    L.hs_graph_set_hedge.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
+    L.hs_graph_set_fallback.restype = C.c_int
+    L.hs_graph_set_fallback.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    for name in ("hs_graph_get_hedge", "hs_graph_get_fallback"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.hs_debug_compact_members.restype = C.c_int
     L.hs_debug_compact_members.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.hs_debug_codel_next.restype = C.c_int
@@ -644,4 +655,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_set_auto_scaler", "hs_graph_get_auto_scaler",
     "hs_graph_set_rolling_deployer", "hs_graph_get_rolling_deployer", "hs_debug_compact_members",
     "hs_graph_set_canary_deployer", "hs_graph_get_canary_deployer",
+    "hs_graph_set_hedge", "hs_graph_set_fallback", "hs_graph_get_hedge", "hs_graph_get_fallback",
 )

@@ -171,7 +171,18 @@ constexpr uint32_t kEvRdStart = kEvAsKinds, kEvRdBatch = kEvAsKinds + 1, kEvRdCh
 // itself, no daemons, no Request.  They count in events_processed and per graph (GVars::cn_by_kind).
 constexpr uint32_t kEvCnStart = kEvDpKinds, kEvCnStage = kEvDpKinds + 1, kEvCnEval = kEvDpKinds + 2, kEvCnPromote = kEvDpKinds + 3,
                    kEvCnRollback = kEvDpKinds + 4, kEvCnComplete = kEvDpKinds + 5, kEvCnKinds = kEvDpKinds + HS_CANARY_KINDS;
-constexpr int kMaxFlowItems = HS_FLOW_MAX_ITEMS;             // batch_size / a bounded gate queue: a batch's length rides in 30 bits of GEvent::pad
+// Hedge / Fallback (components/resilience/hedge.py, fallback.py): a Request at a Hedge, its `_hg_response`, its `_hg_send_hedge`; a
+// Request at a Fallback, its `_fb_primary_response`, its `_fb_timeout`, its `_fb_fallback_response` -- seven more internal kinds, aimed
+// at the wrapper itself.  A response / send-hedge / timeout carries no Request but its key like the wrappers' ids (mk_id): the request
+// id in the low kHgIdBits bits, above them `hedge_number` (a send-hedge) and the flag bit -- `is_hedge` of a Hedge's response, "the
+// fallback entity's response" of a Fallback's.  They count in events_processed and per graph (GVars::hg_by_kind).
+constexpr uint32_t kEvHgReq = kEvCnKinds, kEvHgResp = kEvCnKinds + 1, kEvHgSend = kEvCnKinds + 2, kEvFbReq = kEvCnKinds + 3,
+                   kEvFbPrimResp = kEvCnKinds + 4, kEvFbTimeout = kEvCnKinds + 5, kEvFbFbResp = kEvCnKinds + 6,
+                   kEvHgKinds = kEvCnKinds + HS_HEDGE_KINDS;
+constexpr int kHgIdBits = 34, kHgFlagBit = 50;               // (a key's bits above the low 30 ride in GEvent::req: at most 31 of them)
+constexpr int64_t kHgIdMask = (1ll << kHgIdBits) - 1, kHgFlag = 1ll << kHgFlagBit;
+static_assert(HS_HEDGE_MAX_HEDGES < (1 << (kHgFlagBit - kHgIdBits)), "hedge_number fits between the id and the flag");
+constexpr int kMaxFlowItems = HS_FLOW_MAX_ITEMS;            // batch_size / a bounded gate queue: a batch's length rides in 30 bits of GEvent::pad
 constexpr uint32_t kPadPre = 1u, kPadCancelled = 2u;
 constexpr int kPadIdShift = 2;                 // a check id in GEvent::pad (its low 30 bits: only the one pending id of a backend and ids
                                                // at most one timeout older are ever compared)
@@ -198,6 +209,28 @@ static_assert(kEvAsKinds <= 64, "kDropKindsAs is two words; s_by_kind is zeroed 
 // ... and a deployer's seven
 constexpr uint64_t kDropKindsDp = kDropKindsAs | (((1ull << (HS_DEPLOYER_KINDS + HS_CANARY_KINDS)) - 1ull) << kEvRdStart);
 static_assert(kEvCnKinds <= 64, "kDropKindsDp is two words; s_by_kind is zeroed by one lane per kind");
+// ... and all seven of a Hedge and a Fallback
+constexpr uint64_t kDropKindsHg = kDropKindsDp | (((1ull << HS_HEDGE_KINDS) - 1ull) << kEvHgReq);
+static_assert(kEvHgKinds <= 64, "kDropKindsHg is two words; s_by_kind is zeroed by one lane per kind");
+constexpr int kDefaultHedgeTable = 256;                  // entries a Hedge's / Fallback's table holds before it first grows
+// One entry of a Hedge's or a Fallback's `_in_flight`: the id, start_time, the state and what a later duplicate of the Request is built
+// from -- the original Event's context as GRequest carries it (the first copy may long have been freed at a Sink).
+struct GHgEnt {                                // 40 bytes
+    int64_t id;                                // 0: the place is empty (ids count from 1)
+    int64_t start;                             // start_time ns
+    int64_t created, client;                   // GRequest::created / GRequest::client of the original Request
+    int64_t st;                                // Hedge: bit 0 completed, bits 8-31 hedges_sent, bits 32-63 responses_received; Fallback: 0 "primary", 1 "fallback"
+};
+constexpr int kHgSentShift = 8, kHgRecvShift = 32;
+// A Hedge's / Fallback's table, one row per wrapper in HBM (GVars::hg; GParam::rt_off = its row): open addressing on the id -- ids
+// ascend and are never reused, so `id & (cap - 1)` spreads the live ones evenly --, linear probing, removal by shifting the cluster's
+// tail back (no tombstones).  At most half full, so a probe for an id that has left ends after a few places however many leaked
+// entries the table holds.
+struct GHg { GHgEnt *tab; long long cap; };    // cap: a power of two
+// GParam of a Hedge: lim = hedge_delay ns, conc = max_hedges; of a Fallback: lim = timeout ns (< 0: None), conc = the fallback entity.
+// GState of a Hedge: a = total_requests, b = primary_wins, c = hedge_wins, d = hedges_sent, total_service = hedges_cancelled (as int64
+// bits), svc_draws = _next_request_id, qlen = len(_in_flight); of a Fallback: a = total_requests, b = primary_successes,
+// c = primary_failures, d = fallback_invocations, total_service = fallback_successes (as int64 bits), svc_draws, qlen likewise.
 constexpr int kMaxBulkheadConcurrent = HS_BULKHEAD_MAX_CONCURRENT;         // Bulkhead.max_concurrent the in-flight table is sized for (include/hs_engine.h)
 constexpr int kDefaultTimeoutTable = 256;                // ids a TimeoutWrapper's (keys a Client's) table holds before it first grows
 constexpr int kMaxClientAttempts = HS_CLIENT_MAX_ATTEMPTS;   // the attempt of a key is 16 bits and one
@@ -329,6 +362,8 @@ struct GVars {                                 // device scalars
     int n_rd, n_cn;                            // rows of `rd` / `cn`
     long long rd_compactions[2];               // member lists compacted behind a removal: by the lone lane, by all 64 lanes
     int rd_coop_min;                           // a removal from a list of >= this many members is compacted by all 64 lanes (0: never)
+    GHg *hg;                                   // the rows of the Hedges and Fallbacks (hs_graph_set_hedge / hs_graph_set_fallback; null: none)
+    long long hg_by_kind[HS_HEDGE_KINDS];      // their Events by kind, kEvHgReq .. kEvFbFbResp (hs_graph_get_hedge)
 };
 
 struct GCtl {                                  // kernel argument
@@ -450,8 +485,12 @@ __device__ __forceinline__ double uniform_at(uint64_t seed, uint64_t sid, uint64
 }
 
 // a Request-carrying Event aimed at `node`: which handler it lands in (Entity.handle_event of that class)
-template <bool R = false, bool CL = false, bool FL = false>
+template <bool R = false, bool CL = false, bool FL = false, bool HG = false>
 __device__ __forceinline__ uint32_t arrival_kind(const GParam *P, int node) {
+    if constexpr (HG) {
+        if (P[node].kind == HS_NODE_HEDGE) return kEvHgReq;
+        if (P[node].kind == HS_NODE_FALLBACK) return kEvFbReq;
+    }
     if constexpr (FL) {
         if (P[node].kind == HS_NODE_BATCH_PROCESSOR) return kEvBpItem;
         if (P[node].kind == HS_NODE_CONVEYOR) return kEvCvItem;
@@ -677,15 +716,23 @@ __device__ __forceinline__ GEvent mk_id(int64_t t, uint64_t idx, uint32_t kind, 
 __device__ __forceinline__ int64_t ev_id(const GEvent &e) { return ((int64_t)(-2 - e.req) << 30) | (int64_t)(e.pad >> kPadIdShift); }
 __device__ __forceinline__ int64_t req_id(const GRequest &q) { return __double_as_longlong(q.service_s); }
 // the `_bh_response` / `_tw_response` / `_client_response` kind of a hook's owner
-template <bool CL>
-__device__ __forceinline__ uint32_t hook_resp_kind(uint8_t hk) {
+// (a Fallback's two hooks differ by the flag bit of the key that rode on the Request)
+template <bool CL, bool HG = false>
+__device__ __forceinline__ uint32_t hook_resp_kind(uint8_t hk, [[maybe_unused]] int64_t key = 0) {
+    if constexpr (HG) {
+        if (hk == HS_NODE_HEDGE) return kEvHgResp;
+        if (hk == HS_NODE_FALLBACK) return (key & kHgFlag) ? kEvFbFbResp : kEvFbPrimResp;
+    }
     if constexpr (CL) {
         if (hk == HS_NODE_CLIENT) return kEvClResp;
     }
     return hk == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp;
 }
-template <bool CL>
+template <bool CL, bool HG = false>
 __device__ __forceinline__ bool hook_has_id(uint8_t hk) {
+    if constexpr (HG) {
+        if (hk == HS_NODE_HEDGE || hk == HS_NODE_FALLBACK) return true;
+    }
     if constexpr (CL) {
         if (hk == HS_NODE_CLIENT) return true;
     }
@@ -696,6 +743,36 @@ __device__ inline bool tab_remove(int64_t *tab, int live, int64_t id) {
     for (int i = 0; i < live; ++i)
         if (tab[i] == id) { tab[i] = tab[live - 1]; return true; }
     return false;
+}
+
+// A Hedge's / Fallback's table (GHg): the place of `id`, -1 when it is not there.  The table is at most half full, so every probe
+// meets an empty place.
+__device__ inline long long hg_find(const GHg &row, int64_t id) {
+    const long long mask = row.cap - 1;
+    for (long long i = id & mask;; i = (i + 1) & mask) {
+        const int64_t at = row.tab[i].id;
+        if (at == id) return i;
+        if (at == 0) return -1;
+    }
+}
+// ... a new entry (room: tested in front of the pop)
+__device__ inline void hg_insert(const GHg &row, const GHgEnt &ent) {
+    const long long mask = row.cap - 1;
+    long long i = ent.id & mask;
+    while (row.tab[i].id != 0) i = (i + 1) & mask;
+    row.tab[i] = ent;
+}
+// ... and `del self._in_flight[id]` of the entry at place `i`: every later entry of the cluster whose home place does not lie
+// cyclically in (hole, its place] moves back into the hole, so no probe sequence is ever cut
+__device__ inline void hg_remove(const GHg &row, long long i) {
+    const long long mask = row.cap - 1;
+    for (long long j = (i + 1) & mask; row.tab[j].id != 0; j = (j + 1) & mask) {
+        const long long k = row.tab[j].id & mask;
+        if (i <= j ? (i < k && k <= j) : (i < k || k <= j)) continue;
+        row.tab[i] = row.tab[j];
+        i = j;
+    }
+    row.tab[i].id = 0;
 }
 
 // NL: graphs of up to NL nodes keep their nodes' parameters and state in LDS for the launch (the loop's dependent chain goes
@@ -735,7 +812,7 @@ __device__ inline int compact_members_wave(int32_t *hl, const uint8_t *mem, int 
 // LF: ... has a link fault (InjectLatency / InjectPacketLoss) -- an eighth, for the same reason.  LF implies Q.
 // AS: ... has an AutoScaler -- a ninth, for the same reason.  AS implies LF.
 template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false, bool Q = false, bool LF = false,
-          bool AS = false, bool DP = false>
+          bool AS = false, bool DP = false, bool HG = false>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     static_assert(F || !HC, "the health instantiation carries the fault code");
     static_assert(HC || !R, "the resilience instantiation carries the fault and health code");
@@ -745,9 +822,10 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
     static_assert(Q || !LF, "the link-fault instantiation carries the code of all the others");
     static_assert(LF || !AS, "the scaler instantiation carries the code of all the others");
     static_assert(AS || !DP, "the deployer instantiation carries the code of all the others");
-    constexpr uint32_t kKinds = DP ? kEvCnKinds : AS ? kEvAsKinds : FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
+    static_assert(DP || !HG, "the hedge instantiation carries the code of all the others");
+    constexpr uint32_t kKinds = HG ? kEvHgKinds : DP ? kEvCnKinds : AS ? kEvAsKinds : FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
     // (one word for the instantiations whose kinds fit in it, two for the flow instantiation's 39)
-    constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = DP ? kDropKindsDp : AS ? kDropKindsAs : FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
+    constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = HG ? kDropKindsHg : DP ? kDropKindsDp : AS ? kDropKindsAs : FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
     constexpr int kPushes = R ? 3 : 2;         // heap entries one event constructs at most (R: a limiter's forward or poll + the hook's response)
     __shared__ unsigned long long s_by_kind[kKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
@@ -881,7 +959,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             const int64_t t = c.sched_t[V.sched_done];
             GRequest q; q.created = t; q.idx = V.global_counter; q.service_s = 0.0; q.client = -1; q.next = -1; q.hook = -1; q.pre = 1;
             c.reqs[r] = q;
-            H.push(mk_pre(t, V.global_counter++, arrival_kind<R, CL, FL>(c.P, node), node, r));
+            H.push(mk_pre(t, V.global_counter++, arrival_kind<R, CL, FL, HG>(c.P, node), node, r));
             V.sched_done++;
         }
         cur = V.cur;
@@ -928,6 +1006,12 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if (top.kind == kEvTwReq && c.S[top.node].qlen >= c.P[top.node].rt_cnt) { status |= kGrowTab; break; }
                 if constexpr (CL) {                                                // ... and a Client's for the key
                     if (top.kind == kEvClReq && c.S[top.node].qlen >= c.P[top.node].rt_cnt) { status |= kGrowTab; break; }
+                }
+            }
+            if constexpr (HG) {
+                const GEvent top = H.get(0);                                       // a Hedge's / Fallback's table stays at most half full
+                if ((top.kind == kEvHgReq || top.kind == kEvFbReq) && 2ll * ((long long)c.S[top.node].qlen + 1) > V.hg[c.P[top.node].rt_off].cap) {
+                    status |= kGrowTab; break;
                 }
             }
             if constexpr (FL) {
@@ -1064,7 +1148,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         GRequest rq; rq.created = t; rq.idx = idx_p; rq.service_s = 0.0; rq.client = (id << 32) | (int64_t)q; rq.next = -1; rq.hook = n; rq.pre = 0;
                         c.reqs[r] = rq;
                         const int be = c.rt_targets[lp.rt_off + q];
-                        H.push(mk(t, idx_p, arrival_kind<R, CL, FL>(c.P, be), be, r));
+                        H.push(mk(t, idx_p, arrival_kind<R, CL, FL, HG>(c.P, be), be, r));
                         GEvent te = mk(t + ns_from_seconds(p.lat_min), G++, kEvHcTimeout, n, -2 - q);
                         te.pad = (uint32_t)id << kPadIdShift;
                         H.push(te);
@@ -1195,6 +1279,100 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     }
                     H.push(mk(t + ns_from_seconds(p.mean), G++, kEvAsEval, n, -1));   // self.now + Duration.from_seconds(evaluation_interval)
                     polls_pending += 1;
+                    continue;
+                }
+            }
+            if constexpr (HG) {
+                if (e.kind >= kEvHgReq) {
+                    // Hedge.handle_event (hedge.py:152-174) / Fallback.handle_event (fallback.py:152-177).  No completion hook ever rides
+                    // on an Event that reaches one of them (a wrapper's or Client's target is refused, a LoadBalancer's backends are
+                    // Servers), so a handler ends with the Events it constructs.
+                    const GHg &row = V.hg[p.rt_off];
+                    int64_t &extra = *reinterpret_cast<int64_t *>(&s.total_service);   // hedges_cancelled / fallback_successes
+                    // a NEW Event for `to` at `now` with the entry's context and this wrapper's hook, its key on the Request
+                    auto send_copy = [&](const GHgEnt &en, int to, int64_t key) {
+                        int r = req_free;
+                        if (r >= 0) req_free = c.reqs[r].next; else r = req_len++;  // (room: tested in front of the pop)
+                        const unsigned long long idx_p = G++;
+                        GRequest q; q.created = en.created; q.idx = idx_p; q.service_s = __longlong_as_double(key); q.client = en.client;
+                        q.next = -1; q.hook = n; q.pre = 0;
+                        c.reqs[r] = q;
+                        H.push(mk(t, idx_p, arrival_kind<R, CL, FL, HG>(c.P, to), to, r));
+                    };
+                    // _forward_primary (hedge.py:176-217) / _forward_to_primary (fallback.py:179-248) up to the trigger / timeout: a new
+                    // id, the entry with the original's context, the Request itself travels on as the NEW Event's
+                    auto take_request = [&]() {
+                        s.a += 1;
+                        s.svc_draws += 1;
+                        const int64_t id = (int64_t)s.svc_draws;
+                        GRequest &q = c.reqs[e.req];
+                        GHgEnt en; en.id = id; en.start = t; en.created = q.created; en.client = q.client; en.st = 0;
+                        hg_insert(row, en);                                        // (room: tested in front of the pop)
+                        s.qlen += 1;
+                        q.hook = n; q.service_s = __longlong_as_double(id);
+                        H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
+                        return id;
+                    };
+                    const int64_t key = e.req >= 0 ? 0 : ev_id(e);
+                    const int64_t id = key & kHgIdMask;
+                    switch (e.kind) {
+                    case kEvHgReq: {
+                        const int64_t nid = take_request();                        // (max_hedges >= 1: the first trigger always)
+                        H.push(mk_id(t + p.lim, G++, kEvHgSend, n, nid | (1ll << kHgIdBits)));
+                    } break;
+                    case kEvHgSend: {                                              // _send_hedge (hedge.py:261-315)
+                        const long long at = hg_find(row, id);
+                        if (at < 0) break;                                         // the entry has left: a processed no-op
+                        GHgEnt &en = row.tab[at];
+                        if (en.st & 1) { extra += 1; break; }                      // completed: hedges_cancelled
+                        if (((en.st >> kHgSentShift) & 0xffffffll) >= (int64_t)p.conc) break;
+                        en.st += 1ll << kHgSentShift;
+                        s.d += 1;
+                        send_copy(en, p.target, id | kHgFlag);                     // is_hedge = True
+                        const int64_t number = (key >> kHgIdBits) & 0xffffll;
+                        if (number < (int64_t)p.conc) H.push(mk_id(t + p.lim, G++, kEvHgSend, n, id | ((number + 1) << kHgIdBits)));
+                    } break;
+                    case kEvHgResp: {                                              // _handle_response (hedge.py:317-362)
+                        const long long at = hg_find(row, id);
+                        if (at < 0) break;
+                        GHgEnt &en = row.tab[at];
+                        en.st += 1ll << kHgRecvShift;
+                        if (!(en.st & 1)) {
+                            en.st |= 1;
+                            if (key & kHgFlag) s.c += 1; else s.b += 1;            // hedge_wins / primary_wins
+                        }
+                        if ((int64_t)((uint64_t)en.st >> kHgRecvShift) >= 1 + ((en.st >> kHgSentShift) & 0xffffffll)) {
+                            hg_remove(row, at);
+                            s.qlen -= 1;
+                        }
+                    } break;
+                    case kEvFbReq: {
+                        const int64_t nid = take_request();
+                        if (p.lim >= 0) H.push(mk_id(t + p.lim, G++, kEvFbTimeout, n, nid));
+                    } break;
+                    case kEvFbPrimResp: {                                          // _handle_primary_response (fallback.py:314-355), no predicate
+                        const long long at = hg_find(row, id);
+                        if (at < 0 || row.tab[at].st != 0) break;                  // unknown, or timed out already: a processed no-op
+                        hg_remove(row, at);
+                        s.qlen -= 1;
+                        s.b += 1;
+                    } break;
+                    case kEvFbTimeout: {                                           // _handle_timeout (:357-380) + _forward_to_fallback (:250-312)
+                        const long long at = hg_find(row, id);
+                        if (at < 0 || row.tab[at].st != 0) break;
+                        s.c += 1;
+                        row.tab[at].st = 1;
+                        s.d += 1;
+                        send_copy(row.tab[at], p.conc, id | kHgFlag);              // the `_fb_fallback_response` hook
+                    } break;
+                    default: {                                                     // _handle_fallback_response (:382-410)
+                        const long long at = hg_find(row, id);
+                        if (at < 0 || row.tab[at].st != 1) break;
+                        hg_remove(row, at);
+                        s.qlen -= 1;
+                        extra += 1;
+                    } break;
+                    }
                     continue;
                 }
             }
@@ -1396,7 +1574,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                             GRequest rq; rq.created = t; rq.idx = idx_p; rq.service_s = 0.0; rq.client = (int64_t)slot; rq.next = -1; rq.hook = n; rq.pre = 0;
                             c.reqs[r] = rq;
                             const int be = c.rt_targets[lp.rt_off + slot];
-                            H.push(mk(t, idx_p, arrival_kind<R, CL, FL>(c.P, be), be, r));
+                            H.push(mk(t, idx_p, arrival_kind<R, CL, FL, HG>(c.P, be), be, r));
                             H.push(mk(t + iv_ns, G++, kEvRdTimeout, n, -2 - slot));
                         }
                         break;
@@ -1453,8 +1631,8 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if (hook < 0) return;
                 if (!keep) c.reqs[r].hook = -1;
                 const uint8_t hk = c.P[hook].kind;
-                if (hook_has_id<CL>(hk))
-                    H.push(mk_id(t, G++, hook_resp_kind<CL>(hk), hook, req_id(c.reqs[r])));
+                if (hook_has_id<CL, HG>(hk))
+                    H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(hk, req_id(c.reqs[r])), hook, req_id(c.reqs[r])));
                 else if (hk == HS_NODE_LB) H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
             };
             if constexpr (FL) {
@@ -1464,7 +1642,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     // GState: see hs_graph_get_flow.  No completion hook ever reaches one of them (a LoadBalancer's backends are Servers,
                     // a wrapper's or Client's target is refused), so a handler ends with the Events it constructs.
                     // A NEW Event for the downstream at `now` with the item's context (created_at survives), no hook:
-                    auto forward = [&](int r) { H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r)); };
+                    auto forward = [&](int r) { H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r)); };
                     // BatchProcessor._process_batch up to its yield (batch_processor.py:131-141) via Event._start_process: the buffer
                     // becomes the batch, the pending timeout is cancelled; one continuation is built and invoked at once, the pushed
                     // one is the second.  The batch's list and length travel in the entry: any number of batches is in process.
@@ -1570,7 +1748,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         if ((key >> kKeyAttemptShift) > 1) s.d += 1;
                         GRequest q; q.created = t; q.idx = 0; q.service_s = __longlong_as_double(key); q.client = -2 - key; q.next = -1; q.hook = n; q.pre = 0;
                         c.reqs[r] = q;
-                        H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r));
+                        H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r));
                         if (p.sub) H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvClTimeout, n, key));
                         continue;
                     }
@@ -1608,7 +1786,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         if (s.active > peaks[0]) peaks[0] = s.active;
                         tab[s.active - 1] = id;                                    // (active <= max_concurrent = rt_cnt)
                         c.reqs[r].hook = n; c.reqs[r].service_s = __longlong_as_double(id);
-                        H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r));
+                        H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r));
                     };
                     switch (e.kind) {
                     case kEvBhReq: {                                               // Bulkhead.handle_event (bulkhead.py:191-229)
@@ -1670,7 +1848,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         tab[s.qlen] = id;                                          // (room: tested in front of the pop)
                         s.qlen += 1;
                         c.reqs[e.req].hook = n; c.reqs[e.req].service_s = __longlong_as_double(id);
-                        H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, e.req));
+                        H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
                         H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvTwTimeout, n, id));
                     } break;
                     default: {                                                     // _handle_response / _handle_timeout (:222-295): whichever comes second finds nothing
@@ -1724,7 +1902,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                             H.push(re);
                         } else if (hook >= 0) {
                             const uint8_t hk = c.P[hook].kind;
-                            if (hook_has_id<CL>(hk)) H.push(mk_id(t, G++, hook_resp_kind<CL>(hk), hook, hook_id));
+                            if (hook_has_id<CL, HG>(hk)) H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(hk, hook_id), hook, hook_id));
                             else H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
                         }
                         continue;
@@ -1810,7 +1988,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 }
                 s.c += 1;                                                           // _generated_count (:159)
                 const int64_t a2 = next_arrival(c, n);
-                if (payload) H.push(mk(t, idx_p, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r));
+                if (payload) H.push(mk(t, idx_p, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r));
                 if (a2 != kInfNs) H.push(mk(a2, G++, HS_EV_SOURCE, n, -1));       // RuntimeError: the source is exhausted (:176-180)
             } break;
             case HS_EV_ENQUEUE: {
@@ -1852,8 +2030,8 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 } else if (hook >= 0) {
                     if constexpr (R) {                                             // (a wrapper's hook: its id stayed on the Request)
                         const uint8_t hk = c.P[hook].kind;
-                        if (hook_has_id<CL>(hk)) {
-                            H.push(mk_id(t, G++, hook_resp_kind<CL>(hk), hook, req_id(c.reqs[e.req])));
+                        if (hook_has_id<CL, HG>(hk)) {
+                            H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(hk, req_id(c.reqs[e.req])), hook, req_id(c.reqs[e.req])));
                             break;
                         }
                     }
@@ -1905,7 +2083,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 s.active = s.active > 0 ? s.active - 1 : 0;
                 s.c += 1; n_completed++;
                 s.total_service = __dadd_rn(s.total_service, c.reqs[e.req].service_s);
-                if (p.target >= 0) H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, e.req));
+                if (p.target >= 0) H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
                 else { c.reqs[e.req].next = req_free; req_free = e.req; }
                 if (s.active < p.conc) H.push(mk(t, G++, HS_EV_POLL, n, -1));
             } break;
@@ -1926,11 +2104,11 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     const int hook = c.reqs[e.req].hook;                            //  its Event constructed behind the forward's)
                     const int64_t id = req_id(c.reqs[e.req]);
                     c.reqs[e.req].hook = -1;
-                    H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, tg), tg, e.req));
-                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<CL>(c.P[hook].kind), hook, id));
+                    H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, tg), tg, e.req));
+                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(c.P[hook].kind, id), hook, id));
                     break;
                 }
-                H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, tg), tg, e.req));
+                H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, tg), tg, e.req));
             } break;
             case HS_EV_LINK: {
                 // NetworkLink.handle_event up to its yield (components/network/link.py:114-154, _calculate_delay :190-216)
@@ -1975,7 +2153,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             case HS_EV_LINK_CONT:                                                   // transit over (link.py:156-189): a NEW Event for the egress
                 s.b += 1;
                 if (p.target >= 0) {
-                    H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, e.req));
+                    H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
                     if constexpr (R) fire_hook(e.req, true);                        // ... and stays on the Event for the egress (link.py:181)
                 } else {
                     if constexpr (R) fire_hook(e.req, false);
@@ -2068,7 +2246,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 // a NEW Event for the backend with the same context (created_at survives) + the response hook (:398-431)
                 const int be = c.rt_targets[p.rt_off + slot];
                 c.reqs[e.req].hook = n;
-                H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, be), be, e.req));
+                H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, be), be, e.req));
             } break;
             case HS_EV_LB_RESP:                                                     // LoadBalancer._handle_response (load_balancer.py:435-473)
                 if (s.d > 0) s.d -= 1;
@@ -2112,6 +2290,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if constexpr (AS) {                                                 // AutoScaler.current_count: len(load_balancer.all_backends)
                     if (p.sub == HS_PROBE_AS_CURRENT_COUNT) v = c.S[c.P[p.target].target].qlen;
                 }
+                if constexpr (HG) {                                                 // Hedge.in_flight_count
+                    if (p.sub == HS_PROBE_HG_IN_FLIGHT) v = tg.qlen;
+                }
                 if constexpr (FL) {                                                 // (the flow entities' metrics likewise)
                     if (p.sub == HS_PROBE_BP_BUFFER_DEPTH || p.sub == HS_PROBE_GT_QUEUE_DEPTH) v = tg.qlen;   // buffer_depth / queue_depth
                     else if (p.sub == HS_PROBE_CV_IN_TRANSIT) v = tg.active;        // ConveyorBelt.items_in_transit
@@ -2130,7 +2311,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if (lim_try_acquire(c, p, s, t)) {
                     // _forward (:164-178): a NEW Event for the downstream at `now` with a copy of the context, no completion hook
                     outcome = HS_LIMITER_FORWARDED;
-                    H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, e.req));
+                    H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
                 } else if (!(p.lim >= 0 && s.qlen >= p.lim)) {                     // FIFOQueue.push (queue_policy.py:94-98)
                     outcome = HS_LIMITER_QUEUED;
                     c.reqs[e.req].next = -1;
@@ -2151,7 +2332,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = outcome;
                 rec_n++;
                 if constexpr (R) {
-                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<CL>(c.P[hook].kind), hook, hook_id));
+                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(c.P[hook].kind, hook_id), hook, hook_id));
                 }
             } break;
             case kEvLimPoll: {
@@ -2168,7 +2349,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     s.qlen -= 1;
                     c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = HS_LIMITER_DRAINED;
                     rec_n++;
-                    H.push(mk(t, G++, arrival_kind<R, CL, FL>(c.P, p.target), p.target, r));
+                    H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r));
                     again = s.qlen > 0;
                 }
                 if (again) {
@@ -2293,6 +2474,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             for (int k = 0; k < HS_DEPLOYER_KINDS; ++k) V.rd_by_kind[k] += (long long)s_by_kind[kEvRdStart + k];
             for (int k = 0; k < HS_CANARY_KINDS; ++k) V.cn_by_kind[k] += (long long)s_by_kind[kEvCnStart + k];
         }
+        if constexpr (HG) {
+            for (int k = 0; k < HS_HEDGE_KINDS; ++k) V.hg_by_kind[k] += (long long)s_by_kind[kEvHgReq + k];
+        }
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
@@ -2368,6 +2552,12 @@ __global__ void __launch_bounds__(64) hs_graph_run_deploy(GCtl c) {           //
     __shared__ GEvent lheap[kLdsHeap];
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
     graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
+}
+
+__global__ void __launch_bounds__(64) hs_graph_run_hedge(GCtl c) {            // ... with a Hedge or a Fallback
+    __shared__ GEvent lheap[kLdsHeap];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
+    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
 }
 
 // hs_debug_compact_members: one list, one wavefront
@@ -2469,6 +2659,14 @@ __global__ void __launch_bounds__(64) hs_graph_run_batch_deploy(const GCtl *cs, 
     graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
     batch_report(c, stat);
 }
+// ... of a batch in which at least one handle has a Hedge or a Fallback
+__global__ void __launch_bounds__(64) hs_graph_run_batch_hedge(const GCtl *cs, long long *stat) {
+    __shared__ GEvent lheap[kLdsHeapBatch];
+    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
+    const GCtl c = cs[blockIdx.x];
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
+    batch_report(c, stat);
+}
 
 }  // namespace graph
 }  // namespace hs
@@ -2544,6 +2742,12 @@ struct hs_graph {
     GCn *d_cn = nullptr;
     std::vector<int32_t *> d_cn_lists;         // every row's two lists, one allocation
     double *d_svc_sum = nullptr; long long *d_svc_cnt = nullptr;
+    // Hedge / Fallback: a graph that holds one runs the eleventh instantiation; the rows and every wrapper's table (an allocation of
+    // its own, so that one table grows without the others) go to the device with the first run
+    int n_hedges = 0;
+    std::vector<GHg> hg_rows;                  // in node order (GParam::rt_off = the row)
+    std::vector<int32_t> hg_node;              // the wrapper node of every row
+    GHg *d_hg = nullptr;
     int debug_flags = 0;                       // hs_debug_graph_flags
     // tick tables: one row per time-varying Source and per distinct Probe interval, computed up to `tick_horizon`
     std::vector<hs::TickRow> rows;
@@ -2634,11 +2838,23 @@ void hs_graph_destroy(hs_graph *g) {
     if (g->d_cn) (void)hipFree(g->d_cn);
     if (g->d_svc_sum) (void)hipFree(g->d_svc_sum);
     if (g->d_svc_cnt) (void)hipFree(g->d_svc_cnt);
+    if (g->d_hg) { for (GHg &r : g->hg_rows) if (r.tab) (void)hipFree(r.tab); (void)hipFree(g->d_hg); }
     if (g->slab && !g_slabs.give(g->cfg.device, g->slab_alloc, g->slab)) (void)hipFree(g->slab);
     if (g->ev_a) (void)hipEventDestroy(g->ev_a);
     if (g->ev_b) (void)hipEventDestroy(g->ev_b);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
+}
+
+// Why a Hedge's target / a Fallback's primary or fallback entity of this kind is refused (nullptr: it is lowered)
+static const char *hook_refused(int kind) {
+    switch (kind) {
+    case HS_NODE_LB: case HS_NODE_BULKHEAD: case HS_NODE_TIMEOUT_WRAPPER: case HS_NODE_CLIENT: case HS_NODE_HEDGE: case HS_NODE_FALLBACK:
+        return "a LoadBalancer, Bulkhead, TimeoutWrapper, Client, Hedge or Fallback: two completion hooks on one Event are not lowered";
+    case HS_NODE_BATCH_PROCESSOR: case HS_NODE_CONVEYOR: case HS_NODE_GATE:
+        return "a BatchProcessor, ConveyorBelt or GateController: a completion hook on an item they hold is not lowered";
+    default: return nullptr;
+    }
 }
 
 int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_graph **out) {
@@ -2656,7 +2872,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     if (cfg->start_ns < 0)        // (the Sinks' merged records hold non-negative times)
         return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
     bool has_wrr = false;
-    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER || k == HS_NODE_BULKHEAD || k == HS_NODE_TIMEOUT_WRAPPER || k == HS_NODE_CLIENT || k == HS_NODE_BATCH_PROCESSOR || k == HS_NODE_CONVEYOR || k == HS_NODE_GATE; };
+    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER || k == HS_NODE_BULKHEAD || k == HS_NODE_TIMEOUT_WRAPPER || k == HS_NODE_CLIENT || k == HS_NODE_BATCH_PROCESSOR || k == HS_NODE_CONVEYOR || k == HS_NODE_GATE || k == HS_NODE_HEDGE || k == HS_NODE_FALLBACK; };
     int64_t kmax = 0;                                  // client ids any Source hands out: [0, kmax)
     for (int i = 0; i < n; ++i)
         if (nd->kind[i] == HS_NODE_SOURCE && nd->src_n_clients && nd->src_n_clients[i] > kmax) kmax = nd->src_n_clients[i];
@@ -2728,6 +2944,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
                             : (p.sub >= HS_PROBE_BH_ACTIVE && p.sub <= HS_PROBE_BH_PERMITS) ? tk == HS_NODE_BULKHEAD
                             : p.sub == HS_PROBE_TW_IN_FLIGHT ? tk == HS_NODE_TIMEOUT_WRAPPER
                             : p.sub == HS_PROBE_CL_IN_FLIGHT ? tk == HS_NODE_CLIENT
+                            : p.sub == HS_PROBE_HG_IN_FLIGHT ? tk == HS_NODE_HEDGE
                             : p.sub == HS_PROBE_BP_BUFFER_DEPTH ? tk == HS_NODE_BATCH_PROCESSOR
                             : p.sub == HS_PROBE_CV_IN_TRANSIT ? tk == HS_NODE_CONVEYOR
                             : p.sub == HS_PROBE_GT_QUEUE_DEPTH ? tk == HS_NODE_GATE
@@ -2851,7 +3068,23 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             if (t >= 0 && (nd->kind[t] == HS_NODE_LB || nd->kind[t] == HS_NODE_BULKHEAD || nd->kind[t] == HS_NODE_TIMEOUT_WRAPPER || nd->kind[t] == HS_NODE_CLIENT))
                 return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the target of a %s is (through %s) node %d, a LoadBalancer, Bulkhead, TimeoutWrapper or Client: "
                             "two completion hooks on one Event are not lowered", i, nm, t == p.target ? "no link" : "its links", t);
+            if (t >= 0 && (nd->kind[t] == HS_NODE_HEDGE || nd->kind[t] == HS_NODE_FALLBACK))
+                return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the target of a %s is (through %s) node %d, a Hedge or a Fallback: "
+                            "two completion hooks on one Event are not lowered", i, nm, t == p.target ? "no link" : "its links", t);
             p.conc = 1; p.lim = 0; p.sub = 0; p.rt_off = 0; p.rt_cnt = 0;
+        } break;
+        case HS_NODE_HEDGE:
+        case HS_NODE_FALLBACK: {
+            // Hedge / Fallback (components/resilience/hedge.py, fallback.py): the parameters come with hs_graph_set_hedge /
+            // hs_graph_set_fallback (which checks the fallback entity the same way)
+            const char *nm = p.kind == HS_NODE_HEDGE ? "Hedge" : "Fallback";
+            if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a %s needs a target", i, nm);
+            int t = p.target;
+            for (int hops = 0; hops <= n && t >= 0 && nd->kind[t] == HS_NODE_LINK; ++hops) t = nd->target[t];
+            if (t >= 0 && hook_refused(nd->kind[t]))
+                return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the %s of a %s is (through %s) node %d, %s", i, p.kind == HS_NODE_HEDGE ? "target" : "primary",
+                            nm, t == p.target ? "no link" : "its links", t, hook_refused(nd->kind[t]));
+            p.conc = 1; p.lim = -1; p.sub = 0; p.rt_off = 0; p.rt_cnt = 0;
         } break;
         case HS_NODE_BATCH_PROCESSOR:
         case HS_NODE_CONVEYOR:
@@ -2899,6 +3132,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_HEALTH_CHECKER) g->n_checkers++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_BULKHEAD || P[(size_t)i].kind == HS_NODE_TIMEOUT_WRAPPER) g->n_wrappers++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_CLIENT) g->n_clients++;
+        for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_HEDGE || P[(size_t)i].kind == HS_NODE_FALLBACK) g->n_hedges++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind >= HS_NODE_BATCH_PROCESSOR && P[(size_t)i].kind <= HS_NODE_GATE) g->n_flows++;
         g->wrapper_set.assign((size_t)n, 0); g->tab_cap.assign((size_t)n, 0);
     }
@@ -3363,6 +3597,108 @@ int hs_graph_get_wrapper(hs_graph *g, int32_t node, int64_t *counters, int64_t *
         if (k != std::min<int64_t>(s.qlen, queue_cap)) return fail(g, HS_E_INVALID, "get_wrapper: the wait queue of node %d is broken (internal error)", node);
     }
     return HS_OK;
+}
+
+static int set_hedge_common(hs_graph *g, int32_t node, int kind, const char *what, int32_t table_capacity) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != kind) return fail(g, HS_E_INVALID, "%s: node %d is not a %s", what, node, kind == HS_NODE_HEDGE ? "Hedge" : "Fallback");
+    if (g->ran || g->launches > 0 || g->d_hg) return fail(g, HS_E_STATE, "%s: a wrapper is configured before the first run", what);
+    if (g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "%s: node %d is configured already", what, node);
+    if (table_capacity < 0 || table_capacity > 2 * HS_HEDGE_MAX_IN_FLIGHT) return fail(g, HS_E_INVALID, "%s: table_capacity %d out of range", what, table_capacity);
+    int cap = 1;                               // the table's places: a power of two
+    while (cap < (table_capacity > 0 ? table_capacity : kDefaultHedgeTable)) cap *= 2;
+    g->tab_cap[(size_t)node] = cap;
+    return HS_OK;
+}
+
+int hs_graph_set_hedge(hs_graph *g, int32_t node, int64_t hedge_delay_ns, int32_t max_hedges, int32_t table_capacity) {
+    { const int rc = set_hedge_common(g, node, HS_NODE_HEDGE, "set_hedge", table_capacity); if (rc) return rc; }
+    if (hedge_delay_ns < 0 || hedge_delay_ns > (1ll << 61)) return fail(g, HS_E_INVALID, "set_hedge: hedge_delay of %lld ns out of range", (long long)hedge_delay_ns);
+    if (max_hedges < 1) return fail(g, HS_E_INVALID, "max_hedges must be >= 1, got %d", max_hedges);                     // hedge.py:86-87
+    if (max_hedges > HS_HEDGE_MAX_HEDGES)
+        return fail(g, HS_E_UNSUPPORTED, "Hedge: max_hedges = %d is beyond the %d a request's entry counts", max_hedges, HS_HEDGE_MAX_HEDGES);
+    GParam &p = g->params[(size_t)node];
+    p.lim = hedge_delay_ns; p.conc = max_hedges;
+    g->reach_s = std::max(g->reach_s, (double)hedge_delay_ns * 1e-9);
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    g->wrapper_set[(size_t)node] = 1;
+    return HS_OK;
+}
+
+int hs_graph_set_fallback(hs_graph *g, int32_t node, int32_t fallback_node, int64_t timeout_ns, int32_t table_capacity) {
+    { const int rc = set_hedge_common(g, node, HS_NODE_FALLBACK, "set_fallback", table_capacity); if (rc) return rc; }
+    if (timeout_ns > (1ll << 61)) return fail(g, HS_E_INVALID, "set_fallback: timeout of %lld ns out of range", (long long)timeout_ns);
+    if (fallback_node < 0 || fallback_node >= g->n) return fail(g, HS_E_INVALID, "set_fallback: fallback node %d out of range", fallback_node);
+    {
+        const int k = g->params[(size_t)fallback_node].kind;
+        if (k == HS_NODE_SOURCE || k == HS_NODE_PROBE || k == HS_NODE_HEALTH_CHECKER || k == HS_NODE_AUTO_SCALER || k == HS_NODE_ROLLING_DEPLOYER || k == HS_NODE_CANARY_DEPLOYER)
+            return fail(g, HS_E_INVALID, "node %d: its fallback entity %d takes no Requests", node, fallback_node);
+        int t = fallback_node;
+        for (int hops = 0; hops <= g->n && t >= 0 && g->params[(size_t)t].kind == HS_NODE_LINK; ++hops) t = g->params[(size_t)t].target;
+        if (t >= 0 && hook_refused(g->params[(size_t)t].kind))
+            return fail(g, HS_E_UNSUPPORTED, "node %d: the fallback entity of a Fallback is (through %s) node %d, %s", node,
+                        t == fallback_node ? "no link" : "its links", t, hook_refused(g->params[(size_t)t].kind));
+    }
+    GParam &p = g->params[(size_t)node];
+    p.lim = timeout_ns < 0 ? -1 : timeout_ns; p.conc = fallback_node;
+    if (timeout_ns > 0) g->reach_s = std::max(g->reach_s, (double)timeout_ns * 1e-9);
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    g->wrapper_set[(size_t)node] = 1;
+    return HS_OK;
+}
+
+// hs_graph_get_hedge / hs_graph_get_fallback: the counters, then the live entries of the node's table
+static int get_hedge_common(hs_graph *g, int32_t node, int kind, const char *what, int64_t *counters, int64_t *entries, int64_t cap, int64_t *events) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (events) {
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        for (int k = 0; k < HS_HEDGE_KINDS; ++k) events[k] = v.hg_by_kind[k];
+    }
+    if (node == -1 && !counters && !entries) return HS_OK;
+    const bool hedge = kind == HS_NODE_HEDGE;
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != kind) return fail(g, HS_E_INVALID, "%s: node %d is not a %s", what, node, hedge ? "Hedge" : "Fallback");
+    if (!g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "%s: node %d was never configured", what, node);
+    const GParam &p = g->params[(size_t)node];
+    GState s{};
+    HS_HIP(g, hipMemcpy(&s, g->ctl.S + node, sizeof s, hipMemcpyDeviceToHost));
+    int64_t extra;
+    std::memcpy(&extra, &s.total_service, sizeof extra);
+    const long long tab_cap = g->d_hg ? g->hg_rows[(size_t)p.rt_off].cap : g->tab_cap[(size_t)node];
+    if (counters) {
+        int k = 0;
+        counters[k++] = s.a; counters[k++] = s.b; counters[k++] = s.c; counters[k++] = s.d; counters[k++] = extra;
+        if (!hedge) counters[k++] = 0;                     // fallback_failures: the reference never counts one
+        counters[k++] = (int64_t)s.svc_draws; counters[k++] = s.qlen; counters[k++] = tab_cap;
+    }
+    if (entries && cap > 0 && s.qlen > 0 && g->d_hg) {
+        const GHg &row = g->hg_rows[(size_t)p.rt_off];
+        std::vector<GHgEnt> tab((size_t)row.cap);
+        HS_HIP(g, hipMemcpy(tab.data(), row.tab, tab.size() * sizeof(GHgEnt), hipMemcpyDeviceToHost));
+        int64_t k = 0;
+        for (const GHgEnt &en : tab) {
+            if (en.id == 0 || k >= cap) continue;
+            if (hedge) {
+                int64_t *o = entries + 5 * k;
+                o[0] = en.id; o[1] = en.start; o[2] = en.st & 1; o[3] = (en.st >> kHgSentShift) & 0xffffffll; o[4] = (int64_t)((uint64_t)en.st >> kHgRecvShift);
+            } else {
+                int64_t *o = entries + 3 * k;
+                o[0] = en.id; o[1] = en.start; o[2] = en.st;
+            }
+            ++k;
+        }
+        if (k != std::min<int64_t>(s.qlen, cap)) return fail(g, HS_E_INVALID, "%s: the table of node %d is broken (internal error)", what, node);
+    }
+    return HS_OK;
+}
+int hs_graph_get_hedge(hs_graph *g, int32_t node, int64_t *counters, int64_t *entries, int64_t cap, int64_t *events) {
+    return get_hedge_common(g, node, HS_NODE_HEDGE, "get_hedge", counters, entries, cap, events);
+}
+int hs_graph_get_fallback(hs_graph *g, int32_t node, int64_t *counters, int64_t *entries, int64_t cap, int64_t *events) {
+    return get_hedge_common(g, node, HS_NODE_FALLBACK, "get_fallback", counters, entries, cap, events);
 }
 
 int hs_graph_set_client(hs_graph *g, int32_t node, double timeout_s, const int64_t *delays_ns, int32_t n_delays, int32_t table_capacity) {
@@ -4215,6 +4551,30 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         }
         c.cl_delays = g->d_cl_delays;
     }
+    if (g->n_hedges > 0 && !g->d_hg) {
+        // the Hedges' and Fallbacks' rows and tables, once; the device finds them through GVars
+        HS_HIP(g, hipSetDevice(g->cfg.device));
+        for (int i = 0; i < g->n; ++i) {
+            GParam &p = g->params[(size_t)i];
+            if (p.kind != HS_NODE_HEDGE && p.kind != HS_NODE_FALLBACK) continue;
+            if (!g->wrapper_set[(size_t)i])
+                return fail(g, HS_E_STATE, "node %d: a Hedge / Fallback without its parameters (hs_graph_set_hedge / hs_graph_set_fallback comes before the run)", i);
+        }
+        for (int i = 0; i < g->n; ++i) {
+            GParam &p = g->params[(size_t)i];
+            if (p.kind != HS_NODE_HEDGE && p.kind != HS_NODE_FALLBACK) continue;
+            GHg row{};
+            row.cap = g->tab_cap[(size_t)i];
+            HS_HIP(g, hipMalloc(&row.tab, (size_t)row.cap * sizeof(GHgEnt)));
+            g->hg_rows.push_back(row); g->hg_node.push_back(i);               // (owned from here on: hs_graph_destroy frees it)
+            HS_HIP(g, hipMemset(row.tab, 0, (size_t)row.cap * sizeof(GHgEnt)));
+            p.rt_off = (int32_t)g->hg_rows.size() - 1; p.rt_cnt = 0;
+            HS_HIP(g, hipMemcpy(const_cast<GParam *>(c.P) + i, &p, sizeof p, hipMemcpyHostToDevice));
+        }
+        HS_HIP(g, hipMalloc(&g->d_hg, g->hg_rows.size() * sizeof(GHg)));
+        HS_HIP(g, hipMemcpy(g->d_hg, g->hg_rows.data(), g->hg_rows.size() * sizeof(GHg), hipMemcpyHostToDevice));
+        HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, hg), &g->d_hg, sizeof g->d_hg, hipMemcpyHostToDevice));
+    }
     if (!g->qpol.empty() && !g->d_qp) {
         // the queue policies' rows, once (hs_graph_set_queue_policy comes before the first run): the device finds them through GVars
         HS_HIP(g, hipSetDevice(g->cfg.device));
@@ -4291,6 +4651,40 @@ static int grow_tables(hs_graph *g) {
     return HS_OK;
 }
 
+// A Hedge's or a Fallback's table would be more than half full with one more entry: every such table gets twice the places, its
+// entries at their new homes (ascending ids keep the probe order of the old table, which no lookup depends on).
+static int grow_hedge_tables(hs_graph *g) {
+    std::vector<GState> S((size_t)g->n);
+    HS_HIP(g, hipMemcpy(S.data(), g->ctl.S, (size_t)g->n * sizeof(GState), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < g->hg_rows.size(); ++r) {
+        GHg &row = g->hg_rows[r];
+        const int node = g->hg_node[r];
+        const long long live = S[(size_t)node].qlen;
+        if (2 * (live + 1) <= row.cap) continue;
+        if (live >= HS_HEDGE_MAX_IN_FLIGHT)
+            return fail(g, HS_E_OVERFLOW, "%s node %d: more than %d requests in flight (entries leak behind a crashed or paused target)",
+                        g->params[(size_t)node].kind == HS_NODE_HEDGE ? "Hedge" : "Fallback", node, HS_HEDGE_MAX_IN_FLIGHT);
+        std::vector<GHgEnt> old((size_t)row.cap);
+        HS_HIP(g, hipMemcpy(old.data(), row.tab, old.size() * sizeof(GHgEnt), hipMemcpyDeviceToHost));
+        long long nc = row.cap;
+        while (2 * (live + 1) > nc) nc *= 2;
+        std::vector<GHgEnt> now((size_t)nc, GHgEnt{});
+        for (const GHgEnt &en : old) {
+            if (en.id == 0) continue;
+            long long i = en.id & (nc - 1);
+            while (now[(size_t)i].id != 0) i = (i + 1) & (nc - 1);
+            now[(size_t)i] = en;
+        }
+        GHgEnt *nt = nullptr;
+        HS_HIP(g, hipMalloc(&nt, now.size() * sizeof(GHgEnt)));
+        HS_HIP(g, hipMemcpy(nt, now.data(), now.size() * sizeof(GHgEnt), hipMemcpyHostToDevice));
+        HS_HIP(g, hipFree(row.tab));
+        row.tab = nt; row.cap = nc;
+        HS_HIP(g, hipMemcpy(g->d_hg + r, &row, sizeof row, hipMemcpyHostToDevice));
+    }
+    return HS_OK;
+}
+
 // What a launch left (the device is idle): enlarge what it ran out of; *done = the run reached its end.
 static int after_launch_with(hs_graph *g, int status, long long processed, bool *done);
 static int after_launch(hs_graph *g, bool *done) {
@@ -4342,8 +4736,12 @@ static int after_launch_with(hs_graph *g, int status, long long processed, bool 
         if ((rc = grow(g, &c.rec_cr, c.rec_cap, nc))) return rc;
         c.rec_cap = nc;
     }
-    if (v.status & kGrowTab) {
+    if ((v.status & kGrowTab) && g->ctl.rs_tab) {
         const int rc = grow_tables(g);
+        if (rc) return rc;
+    }
+    if ((v.status & kGrowTab) && g->d_hg) {
+        const int rc = grow_hedge_tables(g);
         if (rc) return rc;
     }
     if ((v.status & kPoolOut) && g->d_rd) {
@@ -4396,7 +4794,8 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (g->n_deployers + g->n_canaries > 0) hipLaunchKernelGGL(hs_graph_run_deploy, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        if (g->n_hedges > 0) hipLaunchKernelGGL(hs_graph_run_hedge, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        else if (g->n_deployers + g->n_canaries > 0) hipLaunchKernelGGL(hs_graph_run_deploy, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
         else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, g->ctl);
@@ -4461,7 +4860,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
         for (int i : pending) any_scalers |= gs[i]->n_scalers > 0;
         bool any_deployers = false;
         for (int i : pending) any_deployers |= gs[i]->n_deployers + gs[i]->n_canaries > 0;
-        if (any_deployers) hipLaunchKernelGGL(hs_graph_run_batch_deploy, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        bool any_hedges = false;
+        for (int i : pending) any_hedges |= gs[i]->n_hedges > 0;
+        if (any_hedges) hipLaunchKernelGGL(hs_graph_run_batch_hedge, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        else if (any_deployers) hipLaunchKernelGGL(hs_graph_run_batch_deploy, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_scalers) hipLaunchKernelGGL(hs_graph_run_batch_scaler, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_link_faults) hipLaunchKernelGGL(hs_graph_run_batch_link_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
         else if (any_queues) hipLaunchKernelGGL(hs_graph_run_batch_queues, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
@@ -4537,7 +4939,8 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count; one.rs_tab = g->ctl.rs_tab;
-        if (g->n_deployers + g->n_canaries > 0) hipLaunchKernelGGL(hs_graph_run_deploy, dim3(1), dim3(64), 0, g->stream, one);
+        if (g->n_hedges > 0) hipLaunchKernelGGL(hs_graph_run_hedge, dim3(1), dim3(64), 0, g->stream, one);
+        else if (g->n_deployers + g->n_canaries > 0) hipLaunchKernelGGL(hs_graph_run_deploy, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, one);
         else if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, one);
         else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, one);

@@ -1561,7 +1561,8 @@ class RateLimitedEntity(Entity):
 # ---- resilience ----------------------------------------------------------------------------------
 # components/resilience/bulkhead.py and timeout.py: the two client-side guards that are pure event logic.  Their handlers run on the
 # device (csrc/hs_graph.hip kEvBhReq .. kEvTwTimeout); these classes carry the parameters in and the reference's state back out.
-# CircuitBreaker (never leaves CLOSED without a host `failure_predicate`), Fallback and Hedge (they take callables) are not mirrored.
+# Hedge and Fallback (hedge.py, fallback.py) follow below: they send a Request a second time, from a copy of its context the device keeps
+# (kEvHgReq .. kEvFbFbResp).  CircuitBreaker (never leaves CLOSED without a host `failure_predicate`) is not mirrored.
 @dataclass(frozen=True)
 class BulkheadStats:
     """bulkhead.py:35-45."""
@@ -1692,6 +1693,124 @@ class TimeoutWrapper(Entity):
     def stats(self) -> TimeoutStats:
         return TimeoutStats(total_requests=self._total_requests, successful_requests=self._successful_requests,
                             timed_out_requests=self._timed_out_requests)
+
+
+@dataclass(frozen=True)
+class HedgeStats:
+    """hedge.py:31-39."""
+
+    total_requests: int = 0
+    primary_wins: int = 0
+    hedge_wins: int = 0
+    hedges_sent: int = 0
+    hedges_cancelled: int = 0
+
+
+class Hedge(Entity):
+    """A duplicate of every Request that has no response `hedge_delay` seconds after it was forwarded to `target`, up to `max_hedges`
+    of them, `hedge_delay` apart (hedge.py:42-362).  The duplicates really flow downstream; the first response -- a forwarded
+    Event's completion hook -- decides primary_wins / hedge_wins, and a request's entry leaves `_in_flight` once as many responses have
+    come as copies were sent by then.  Behind a crashed or paused target no hook fires: the hedges go out and the entry stays."""
+
+    MAX_HEDGES = 65535                        # include/hs_engine.h HS_HEDGE_MAX_HEDGES: what a request's entry counts
+
+    def __init__(self, name: str, target: Entity, hedge_delay: float, max_hedges: int = 1):
+        super().__init__(name)
+        if hedge_delay <= 0:                                                              # hedge.py:84-87
+            raise ValueError(f"hedge_delay must be > 0, got {hedge_delay}")
+        if max_hedges < 1:
+            raise ValueError(f"max_hedges must be >= 1, got {max_hedges}")
+        self._target = target
+        self._hedge_delay = hedge_delay
+        self._max_hedges = max_hedges
+        # after a run: {id: {"start_time", "completed", "hedges_sent", "responses_received"}} (`original_event` is not mirrored)
+        self._in_flight: dict[int, dict] = {}
+        self._next_request_id = 0
+        self._total_requests = 0
+        self._primary_wins = 0
+        self._hedge_wins = 0
+        self._hedges_sent = 0
+        self._hedges_cancelled = 0
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._target]
+
+    @property
+    def target(self) -> Entity:
+        return self._target
+
+    @property
+    def hedge_delay(self) -> float:
+        return self._hedge_delay
+
+    @property
+    def max_hedges(self) -> int:
+        return self._max_hedges
+
+    @property
+    def in_flight_count(self) -> int:
+        return len(self._in_flight)
+
+    @property
+    def stats(self) -> HedgeStats:
+        return HedgeStats(total_requests=self._total_requests, primary_wins=self._primary_wins, hedge_wins=self._hedge_wins,
+                          hedges_sent=self._hedges_sent, hedges_cancelled=self._hedges_cancelled)
+
+
+@dataclass(frozen=True)
+class FallbackStats:
+    """fallback.py:31-40."""
+
+    total_requests: int = 0
+    primary_successes: int = 0
+    primary_failures: int = 0
+    fallback_invocations: int = 0
+    fallback_successes: int = 0
+    fallback_failures: int = 0
+
+
+class Fallback(Entity):
+    """Every Request goes to `primary`; one without a response after `timeout` seconds is sent again to the `fallback` entity
+    (fallback.py:43-410), and a primary response that comes later is ignored.  `timeout=None` never invokes the fallback entity.
+    `failure_predicate` and a callable `fallback` are host callables: not lowered.  `fallback_failures` stays 0, as in the reference."""
+
+    def __init__(self, name: str, primary: Entity, fallback, failure_predicate=None, timeout: float | None = None):
+        super().__init__(name)
+        if timeout is not None and timeout <= 0:                                          # fallback.py:83-84
+            raise ValueError(f"timeout must be > 0 or None, got {timeout}")
+        self._primary = primary
+        self._fallback = fallback
+        self._failure_predicate = failure_predicate
+        self._timeout = timeout
+        self._in_flight: dict[int, dict] = {}     # after a run: {id: {"start_time", "state"}} (`original_event` is not mirrored)
+        self._next_request_id = 0
+        self._total_requests = 0
+        self._primary_successes = 0
+        self._primary_failures = 0
+        self._fallback_invocations = 0
+        self._fallback_successes = 0
+        self._fallback_failures = 0
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self._primary] + ([self._fallback] if isinstance(self._fallback, Entity) else [])
+
+    @property
+    def primary(self) -> Entity:
+        return self._primary
+
+    @property
+    def fallback(self):
+        return self._fallback
+
+    @property
+    def timeout(self) -> float | None:
+        return self._timeout
+
+    @property
+    def stats(self) -> FallbackStats:
+        return FallbackStats(total_requests=self._total_requests, primary_successes=self._primary_successes,
+                             primary_failures=self._primary_failures, fallback_invocations=self._fallback_invocations,
+                             fallback_successes=self._fallback_successes, fallback_failures=self._fallback_failures)
 
 
 # ---- client --------------------------------------------------------------------------------------
@@ -2603,7 +2722,7 @@ class Probe(Entity):
     _LOWERED = {"depth", "active_requests", "utilization", "available_capacity", "has_capacity", "stats_accepted", "stats_dropped",
                 "requests_completed", "_requests_completed", "events_received", "generated_count", "_generated_count", "queue_depth",
                 "active_count", "available_permits", "in_flight_count", "buffer_depth", "items_in_transit", "current_count"}
-    _ON_WRAPPER = {"active_count": Bulkhead, "available_permits": Bulkhead, "in_flight_count": (TimeoutWrapper, Client),
+    _ON_WRAPPER = {"active_count": Bulkhead, "available_permits": Bulkhead, "in_flight_count": (TimeoutWrapper, Client, Hedge),
                    "buffer_depth": BatchProcessor, "items_in_transit": ConveyorBelt, "current_count": AutoScaler}
     # Server attributes that are functions of `active_requests` and the (fixed) concurrency: the engine samples the integer,
     # the Data container applies the reference's expression (components/server/server.py:153-173,191-200, concurrency.py:117-131)

@@ -95,6 +95,18 @@ class GraphArrays:
     def cn_params(self, value):
         self._cn_params = value
 
+    @property
+    def hg_params(self):
+        """[n, 4] int64 (None: neither a Hedge nor a Fallback; kept out of vars() like `rd_params`): HEDGE nodes -- hedge_delay in ns,
+        max_hedges, -1, the in-flight table's first capacity (0: the engine's default); FALLBACK nodes -- timeout in ns (-1: None), 0,
+        the node of the fallback entity (the node's second outgoing edge; the primary: `target`), the table's first capacity; set
+        through hs_graph_set_hedge / hs_graph_set_fallback."""
+        return getattr(self, "_hg_params", None)
+
+    @hg_params.setter
+    def hg_params(self, value):
+        self._hg_params = value
+
     # the families a graph has nodes of: what GraphEngine applies and reads, what the run's results hold
     has_deployers = property(lambda self: self._rd_params is not None)
     has_canaries = property(lambda self: self.cn_params is not None)
@@ -104,6 +116,7 @@ class GraphArrays:
     has_clients = property(lambda self: self.cl_params is not None)
     has_health = property(lambda self: self.hc_params is not None or self.lb_healthy is not None)
     has_wrappers = property(lambda self: self.wrap_params is not None)
+    has_hedges = property(lambda self: self.hg_params is not None)
 
     def struct(self) -> N.GraphNodes:
         s = N.GraphNodes()
@@ -127,7 +140,7 @@ class GraphArrays:
 _PER_NODE = ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s", "link_lat_min_s",
              "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric", "probe_interval_s", "lb_strategy",
              "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params", "cl_params", "flow_params",
-             "qp_params", "as_params", "rd_params")
+             "qp_params", "as_params", "rd_params", "hg_params")
 
 # (a family's array, which of a part's nodes are of that family): a part without one drops the array and runs the loop it would run
 # alone (without a checker: no health state unless a flag says so, below)
@@ -137,7 +150,8 @@ _FAMILY_OF = (("hc_params", lambda b: b.kind == N.NODE_HEALTH_CHECKER),
               ("flow_params", lambda b: (b.kind >= N.NODE_BATCH_PROCESSOR) & (b.kind <= N.NODE_GATE)),
               ("qp_params", lambda b: b.qp_params[:, 0] != N.QUEUE_FIFO),
               ("as_params", lambda b: b.kind == N.NODE_AUTO_SCALER),
-              ("cl_params", lambda b: b.kind == N.NODE_CLIENT))
+              ("cl_params", lambda b: b.kind == N.NODE_CLIENT),
+              ("hg_params", lambda b: (b.kind == N.NODE_HEDGE) | (b.kind == N.NODE_FALLBACK)))
 
 
 def _offsets(blobs, dtype) -> np.ndarray:
@@ -162,6 +176,9 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
         return None
     src = np.concatenate([has_t, rt_owner])
     dst = np.concatenate([a.target[has_t].astype(np.int64), rt])
+    if a.hg_params is not None:                        # a Fallback's second edge: its fallback entity
+        fb = np.nonzero(a.kind == N.NODE_FALLBACK)[0]
+        src, dst = np.concatenate([src, fb]), np.concatenate([dst, a.hg_params[fb, 2]])
     n_comp, label = connected_components(coo_matrix((np.ones(len(src), np.int8), (src, dst)), shape=(n, n)), directed=False)
     if n_comp < 2:
         return None
@@ -202,6 +219,9 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
         else:
             pos = np.zeros(0, np.int64)
             b.rt_targets = np.zeros(0, np.int32)
+        if b.hg_params is not None:
+            fb = b.kind == N.NODE_FALLBACK
+            b.hg_params[fb, 2] = new_index[b.hg_params[fb, 2]]
         for nm, of_family in _FAMILY_OF:
             if getattr(b, nm) is not None and not of_family(b).any():
                 setattr(b, nm, None)

@@ -118,6 +118,14 @@ class GraphEngine:
             self._check(self._lib.hs_graph_set_wrapper(self._h, int(i), int(mc), int(mq), float(mw), float(to),
                                                        self._table_capacity or int(cap)))
 
+    def _apply_hedges(self, a: GraphArrays) -> None:
+        for i in np.nonzero((a.kind == N.NODE_HEDGE) | (a.kind == N.NODE_FALLBACK))[0]:
+            delay_ns, max_hedges, fallback, cap = (int(v) for v in a.hg_params[i])
+            if a.kind[i] == N.NODE_HEDGE:
+                self._check(self._lib.hs_graph_set_hedge(self._h, int(i), delay_ns, max_hedges, self._table_capacity or cap))
+            else:
+                self._check(self._lib.hs_graph_set_fallback(self._h, int(i), fallback, delay_ns, self._table_capacity or cap))
+
     def _apply_clients(self, a: GraphArrays) -> None:
         for i in np.nonzero(a.kind == N.NODE_CLIENT)[0]:
             timeout, cap = a.cl_params[i]
@@ -139,7 +147,7 @@ class GraphEngine:
     # before its scaler ...
     _APPLY = ((None, _apply_lb_weights), (None, _apply_limiters), ("has_health", _apply_health), ("has_scalers", _apply_scalers),
               ("has_deployers", _apply_rolling_deployers), ("has_canaries", _apply_canary_deployers), ("has_wrappers", _apply_wrappers),
-              ("has_clients", _apply_clients), ("has_flows", _apply_flows), ("has_queue_policies", _apply_queue_policies))
+              ("has_hedges", _apply_hedges), ("has_clients", _apply_clients), ("has_flows", _apply_flows), ("has_queue_policies", _apply_queue_policies))
 
     _QUEUE_NAMES = ("policy", "len", "enqueued", "dequeued_fifo", "dequeued_lifo", "dropped", "capacity_rejected", "switches", "flag",
                     "count", "last_count", "has_first_above", "first_above_ns", "has_drop_next", "drop_next_ns")
@@ -187,6 +195,35 @@ class GraphEngine:
         """The graph's Client request / response / timeout Events of the run."""
         events = np.zeros(3, np.int64)
         self._check(self._lib.hs_graph_get_client(self._h, -1, None, None, 0, _ptr(events)))
+        return events
+
+    _HEDGE_NAMES = ("total_requests", "primary_wins", "hedge_wins", "hedges_sent", "hedges_cancelled", "next_request_id", "in_flight_count",
+                    "table_capacity")
+    _FALLBACK_NAMES = ("total_requests", "primary_successes", "primary_failures", "fallback_invocations", "fallback_successes",
+                       "fallback_failures", "next_request_id", "in_flight_count", "table_capacity")
+
+    def hedge(self, node: int) -> dict:
+        """hs_graph_get_hedge / hs_graph_get_fallback of a Hedge or Fallback node: its counters by name and `entries`, the requests in
+        flight by ascending id -- rows (id, start_time ns, completed, hedges_sent, responses_received) of a Hedge, (id, start_time ns,
+        state: 0 "primary" / 1 "fallback") of a Fallback."""
+        hedge = self.arrays.kind[node] == N.NODE_HEDGE
+        get, names, width = ((self._lib.hs_graph_get_hedge, self._HEDGE_NAMES, 5) if hedge else
+                             (self._lib.hs_graph_get_fallback, self._FALLBACK_NAMES, 3))
+        c = np.zeros(len(names), np.int64)
+        self._check(get(self._h, int(node), _ptr(c), None, 0, None))
+        out = {k: int(v) for k, v in zip(names, c)}
+        live = out["in_flight_count"]
+        rows = np.zeros((max(live, 1), width), np.int64)
+        self._check(get(self._h, int(node), None, _ptr(rows), live, None))
+        rows = rows[:live]
+        out["entries"] = rows[np.argsort(rows[:, 0], kind="stable")]
+        return out
+
+    def hedge_events(self) -> np.ndarray:
+        """The graph's Hedge request / response / send-hedge and Fallback request / primary-response / timeout / fallback-response
+        Events of the run."""
+        events = np.zeros(N.HEDGE_KINDS, np.int64)
+        self._check(self._lib.hs_graph_get_hedge(self._h, -1, None, None, 0, _ptr(events)))
         return events
 
     def wrapper(self, node: int) -> dict:
@@ -562,6 +599,7 @@ class PartRun:
         return v.astype(np.int64)
 
     queue_policy, flow, client, wrapper = _of_node("queue_policy"), _of_node("flow"), _of_node("client"), _of_node("wrapper")
+    hedge, hedge_events = _of_node("hedge"), _summed("hedge_events", _int64)
     canary, deployer, scaler, health = _of_node("canary"), _of_node("deployer"), _of_node("scaler"), _of_node("health")
     health_events, wrapper_events = _summed("health_events", _int64), _summed("wrapper_events", _int64)
     client_events, flow_events = _summed("client_events", _int64), _summed("flow_events", _int64)

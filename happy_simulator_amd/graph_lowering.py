@@ -18,7 +18,7 @@ from .core.temporal import Duration
 from .entities import (LIMITER_POLICIES, METRIC_EVALUATORS, QUEUE_POLICIES, SCALING_POLICIES, AdaptiveLIFO, AutoScaler, BatchProcessor,
                        Bulkhead, CanaryDeployer, Client, ClientKeyEventProvider, CoDelQueue, ConsistentHash, ConstantLatency,
                        ConstantRateProfile, ConveyorBelt, Counter, DecorrelatedJitter, Entity, ExponentialBackoff, ExponentialLatency,
-                       FIFOQueue, FixedRetry, GateController, HealthChecker, IPHash, LatencyEvaluator, LatencyTracker, LeastConnections,
+                       Fallback, FIFOQueue, FixedRetry, GateController, HealthChecker, Hedge, IPHash, LatencyEvaluator, LatencyTracker, LeastConnections,
                        LinearRampProfile, LoadBalancer, Network, NetworkLink, NoRetry, Probe, Random, RandomRouter, RateLimitedEntity,
                        RollingDeployer, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source, StepScaling,
                        TargetUtilization, TimeoutWrapper, TokenBucketPolicy, WeightedLeastConnections, WeightedRoundRobin)
@@ -35,7 +35,7 @@ _FLOWS = (BatchProcessor, ConveyorBelt, GateController)
 _DEPLOYERS = (RollingDeployer, CanaryDeployer)
 _FLOW_METRIC_OF = {"buffer_depth": BatchProcessor, "items_in_transit": ConveyorBelt, "queue_depth": GateController}
 _LOWERED = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker, Bulkhead, TimeoutWrapper, Client,
-            BatchProcessor, ConveyorBelt, GateController, AutoScaler, RollingDeployer, CanaryDeployer) + _SINKS
+            BatchProcessor, ConveyorBelt, GateController, AutoScaler, RollingDeployer, CanaryDeployer, Hedge, Fallback) + _SINKS
 _FIXED_LIST = (ConsistentHash, IPHash, Random)            # strategies whose selection over a changing backend list is not lowered
 
 
@@ -405,9 +405,12 @@ def _lower_probe(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
     tgt = ent.target
     on_wrapper = isinstance(tgt, (Bulkhead, TimeoutWrapper)) and m in N.PROBE_WRAPPER_METRICS
     on_client = isinstance(tgt, Client) and m in N.PROBE_CLIENT_METRICS
+    on_hedge = isinstance(tgt, Hedge) and m in N.PROBE_HEDGE_METRICS
     want = None                                       # the class whose attribute the metric is, where the metric alone does not say
     if isinstance(tgt, AutoScaler) and m in N.PROBE_SCALER_METRICS:
         codes = N.PROBE_SCALER_METRICS
+    elif on_hedge:
+        codes = N.PROBE_HEDGE_METRICS
     elif isinstance(tgt, _FLOW_METRIC_OF.get(m, ())):
         codes = N.PROBE_FLOW_METRICS
     else:
@@ -580,16 +583,23 @@ def _lower_rolling_deployer(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
         ent._batch_size, ent._health_check_interval, ent._healthy_threshold, ent._max_failures, len(cx.scaled[id(lb)][2]))
 
 
-def _hook_target(cx: _Lowering, what: str, ent) -> int:
-    """The node a Client or a wrapper sends to.  Its completion hook rides on the Event to the end of the NetworkLinks behind that
-    target: what holds the item back there, or hangs a hook of its own on it, is refused."""
-    tgt = ent.target
+def _hook_target(cx: _Lowering, what: str, ent, tgt=None, role: str = "target") -> int:
+    """The node a Client or a wrapper sends to (`tgt`: a Hedge's target, a Fallback's primary or fallback entity, named by `role`).
+    Its completion hook rides on the Event to the end of the NetworkLinks behind that target: what holds the item back there, or
+    hangs a hook of its own on it, is refused."""
+    tgt = ent.target if tgt is None else tgt
     if _takes_no_requests(cx, tgt):
-        raise UnsupportedTopology(f"{what}: its target {type(tgt).__name__} '{getattr(tgt, 'name', tgt)}' takes no Requests")
+        raise UnsupportedTopology(f"{what}: its {role} {type(tgt).__name__} '{getattr(tgt, 'name', tgt)}' takes no Requests")
     end, hops = tgt, 0
     while isinstance(end, NetworkLink) and end.egress is not None and hops <= cx.a.n:
         end, hops = end.egress, hops + 1
     via = " (through its NetworkLinks)" if end is not tgt else ""
+    if isinstance(end, (Hedge, Fallback)) or (isinstance(ent, (Hedge, Fallback)) and isinstance(end, (LoadBalancer, Bulkhead, TimeoutWrapper, Client))):
+        raise UnsupportedTopology(f"{what}: its {role}{via} is the {type(end).__name__} '{end.name}' -- two completion hooks on one Event "
+                                  "are not lowered (a follow-up)")
+    if isinstance(end, _FLOWS) and isinstance(ent, (Hedge, Fallback)):
+        raise UnsupportedTopology(f"{what}: its {role}{via} is the {type(end).__name__} '{end.name}' -- a completion hook on an item that "
+                                  "a BatchProcessor, ConveyorBelt or GateController holds is not lowered (a follow-up)")
     if isinstance(end, _FLOWS):
         raise UnsupportedTopology(f"{what}: its target{via} is the {type(end).__name__} '{end.name}' -- a completion hook on an item that "
                                   "a BatchProcessor, ConveyorBelt or GateController holds is not lowered (a follow-up)")
@@ -623,6 +633,43 @@ def _lower_wrapper(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
             raise UnsupportedTopology(f"{what}: timeout must be finite")
         a.kind[i] = N.NODE_TIMEOUT_WRAPPER
         params[i, 3] = ent.timeout
+
+
+def _wrapper_delay_ns(what: str, name: str, seconds) -> int:
+    """Duration.from_seconds(seconds) in whole nanoseconds: what a Hedge / Fallback handler adds to `now`."""
+    try:
+        ns = Duration.from_seconds(seconds).nanoseconds
+        if not 0 <= ns < (1 << 61):
+            raise OverflowError(ns)
+    except (OverflowError, ValueError, TypeError) as e:
+        raise UnsupportedTopology(f"{what}: {name} = {seconds!r} cannot be evaluated as a Duration ({type(e).__name__}: {e})") from None
+    return ns
+
+
+def _lower_hedge(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
+    what = f"Hedge '{ent.name}'"
+    target = _hook_target(cx, what, ent)
+    if type(ent.max_hedges) is not int or ent.max_hedges > Hedge.MAX_HEDGES:
+        raise UnsupportedTopology(f"{what}: max_hedges = {ent.max_hedges!r} is beyond the {Hedge.MAX_HEDGES} hedges a request's entry "
+                                  "counts on the engine (Hedge.MAX_HEDGES)")
+    a.kind[i] = N.NODE_HEDGE
+    a.target[i] = target
+    _ensure(a, "hg_params", lambda: np.zeros((a.n, 4), np.int64))[i] = (_wrapper_delay_ns(what, "hedge_delay", ent.hedge_delay),
+                                                                        ent.max_hedges, -1, 0)
+
+
+def _lower_fallback(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
+    what = f"Fallback '{ent.name}'"
+    if ent._failure_predicate is not None:
+        raise UnsupportedTopology(f"{what}: failure_predicate= is a host callable (not lowered)")
+    if not isinstance(ent.fallback, Entity):
+        raise UnsupportedTopology(f"{what}: fallback= is a host callable, not an Entity (not lowered)")
+    primary = _hook_target(cx, what, ent, ent.primary, "primary")
+    fallback = _hook_target(cx, what, ent, ent.fallback, "fallback entity")
+    a.kind[i] = N.NODE_FALLBACK
+    a.target[i] = primary
+    _ensure(a, "hg_params", lambda: np.zeros((a.n, 4), np.int64))[i] = (
+        -1 if ent.timeout is None else _wrapper_delay_ns(what, "timeout", ent.timeout), 0, fallback, 0)
 
 
 def _lower_client(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
@@ -724,7 +771,7 @@ def _lower_sink(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
 _LOWER = ((Source, _lower_source), (Probe, _lower_probe), (Server, _lower_server), (NetworkLink, _lower_link),
           (LoadBalancer, _lower_load_balancer), (HealthChecker, _lower_health_checker), (AutoScaler, _lower_auto_scaler),
           (CanaryDeployer, _lower_canary_deployer), (RollingDeployer, _lower_rolling_deployer), ((Bulkhead, TimeoutWrapper), _lower_wrapper),
-          (Client, _lower_client), (_FLOWS, _lower_flow), (RateLimitedEntity, _lower_limiter), (RandomRouter, _lower_router))
+          (Hedge, _lower_hedge), (Fallback, _lower_fallback), (Client, _lower_client), (_FLOWS, _lower_flow), (RateLimitedEntity, _lower_limiter), (RandomRouter, _lower_router))
 
 
 def _assemble(cx: _Lowering) -> GeneralGraph:

@@ -7,7 +7,7 @@ import numpy as np
 from . import _native as N
 from .core.temporal import Duration, Instant
 from .entities import (QUEUE_POLICIES, AdaptiveLIFO, AutoScaler, BackendHealthState, BackendInfo, BatchProcessor, Bulkhead, CanaryDeployer,
-                       CanaryState, Client, CoDelQueue, ConsistentHash, ConveyorBelt, DeploymentState, GateController, HealthChecker,
+                       CanaryState, Client, CoDelQueue, ConsistentHash, ConveyorBelt, DeploymentState, Fallback, GateController, HealthChecker, Hedge,
                        IPHash, LoadBalancer, Network, NetworkLink, Probe, RandomRouter, RateLimitedEntity, RollingDeployer, RoundRobin,
                        ScalingEvent, Server, Source, TimeoutWrapper, WeightedRoundRobin)
 from .graph_engine import GeneralGraph, GraphEngine
@@ -257,6 +257,24 @@ def _write_timeout_wrapper(r: _Results, i: int, ent) -> None:
     ent._in_flight = {int(x): {} for x in w["in_flight_ids"]}
 
 
+def _write_hedge(r: _Results, i: int, ent) -> None:
+    w = r.engine.hedge(i)
+    (ent._total_requests, ent._primary_wins, ent._hedge_wins, ent._hedges_sent, ent._hedges_cancelled) = (
+        w["total_requests"], w["primary_wins"], w["hedge_wins"], w["hedges_sent"], w["hedges_cancelled"])
+    ent._next_request_id = w["next_request_id"]
+    ent._in_flight = {int(rid): {"start_time": Instant(int(t0)), "completed": bool(done), "hedges_sent": int(sent),
+                                 "responses_received": int(got)} for rid, t0, done, sent, got in w["entries"]}
+
+
+def _write_fallback(r: _Results, i: int, ent) -> None:
+    w = r.engine.hedge(i)
+    (ent._total_requests, ent._primary_successes, ent._primary_failures, ent._fallback_invocations, ent._fallback_successes,
+     ent._fallback_failures) = (w["total_requests"], w["primary_successes"], w["primary_failures"], w["fallback_invocations"],
+                                w["fallback_successes"], w["fallback_failures"])
+    ent._next_request_id = w["next_request_id"]
+    ent._in_flight = {int(rid): {"start_time": Instant(int(t0)), "state": "fallback" if st else "primary"} for rid, t0, st in w["entries"]}
+
+
 def _write_limiter(r: _Results, i: int, ent) -> None:
     st = r.stats["limiters"][i]
     ent._received, ent._forwarded, ent._queued, ent._dropped = (int(st[k]) for k in ("received", "forwarded", "queued", "dropped"))
@@ -306,6 +324,7 @@ _WRITE_BACK = ((Source, _write_source), (Server, _write_server), (NetworkLink, _
                (LoadBalancer, _write_load_balancer), (CanaryDeployer, _write_canary_deployer), (RollingDeployer, _write_rolling_deployer),
                (AutoScaler, _write_auto_scaler), (HealthChecker, _write_health_checker), (Bulkhead, _write_bulkhead),
                ((BatchProcessor, ConveyorBelt, GateController), _write_flow), (Client, _write_client), (TimeoutWrapper, _write_timeout_wrapper),
+               (Hedge, _write_hedge), (Fallback, _write_fallback),
                (RateLimitedEntity, _write_limiter), (Probe, _write_probe), (RandomRouter, _write_router))
 
 

@@ -198,6 +198,7 @@ typedef enum hs_probe_metric {
     HS_PROBE_CV_IN_TRANSIT = 14,   /* ConveyorBelt.items_in_transit */
     HS_PROBE_GT_QUEUE_DEPTH = 15,  /* GateController.queue_depth */
     HS_PROBE_AS_CURRENT_COUNT = 16,/* AutoScaler.current_count (general graphs only) */
+    HS_PROBE_HG_IN_FLIGHT = 17,/* Hedge.in_flight_count (general graphs only) */
     HS_PROBE_NONE = 255
 } hs_probe_metric;
 typedef enum hs_profile_kind { HS_PROF_CONSTANT = 0, HS_PROF_LINEAR_RAMP = 1, HS_PROF_SPIKE = 2 } hs_profile_kind;
@@ -767,7 +768,9 @@ typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK
                              HS_NODE_GATE = 14,
                              HS_NODE_AUTO_SCALER = 15,     /* AutoScaler: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_auto_scaler */
                              HS_NODE_ROLLING_DEPLOYER = 16,/* RollingDeployer: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_rolling_deployer */
-                             HS_NODE_CANARY_DEPLOYER = 17  /* CanaryDeployer: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_canary_deployer */
+                             HS_NODE_CANARY_DEPLOYER = 17, /* CanaryDeployer: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_canary_deployer */
+                             HS_NODE_HEDGE = 18,           /* Hedge: `target` = the entity it sends to; everything else: hs_graph_set_hedge */
+                             HS_NODE_FALLBACK = 19         /* Fallback: `target` = its primary; the fallback entity and the rest: hs_graph_set_fallback */
 } hs_node_kind;
 
 typedef struct hs_graph_config {
@@ -1210,6 +1213,57 @@ int hs_graph_set_canary_deployer(hs_graph *g, int32_t node, int32_t lb_node, int
                                  const double *evaluation_period, int32_t evaluator, double ev_max, double ev_multiplier, double interval_s);
 int hs_graph_get_canary_deployer(hs_graph *g, int32_t node, int64_t *state, double *traffic_pct, int32_t *baseline, int32_t *members,
                                  int32_t *weights, int32_t *weight_set, double *service_sum, int64_t *service_count, int64_t *events);
+/* Hedge and Fallback (components/resilience/hedge.py, fallback.py): the two wrappers that send a Request a SECOND time.  A graph that
+ * holds one runs an eleventh instantiation of the loop (it carries the code of all the others).  Seven more internal kinds, in this
+ * order -- a Request at a Hedge, its `_hg_response`, its `_hg_send_hedge`; a Request at a Fallback, its `_fb_primary_response`, its
+ * `_fb_timeout`, its `_fb_fallback_response` -- are aimed at the wrapper itself (dropped while it is crashed or paused); they count in
+ * hs_summary.events_processed, not in events_by_kind.
+ *   Hedge: a Request takes id ++_next_request_id, its entry is stored with a copy of the Request's context (created_at, the client
+ *     key), a NEW Event for `target` at `now` is constructed with the Hedge's hook, then `_hg_send_hedge` number 1 at now +
+ *     hedge_delay_ns.  `_hg_send_hedge`: an unknown id is a processed no-op; a completed entry counts hedges_cancelled; an entry with
+ *     hedges_sent >= max_hedges does nothing; otherwise a duplicate Request is built FROM THE ENTRY (a fresh Request of the pool) and,
+ *     while its number < max_hedges, the next `_hg_send_hedge`.  `_hg_response` carries is_hedge: responses_received += 1, the first
+ *     one decides primary_wins / hedge_wins, and the entry leaves once responses_received >= 1 + hedges_sent at that moment.
+ *   Fallback: a Request takes an id, its entry is stored in state "primary", a NEW Event for the primary is constructed with the hook,
+ *     then, with a timeout, `_fb_timeout` at now + timeout_ns.  `_fb_primary_response` in state "primary" deletes the entry
+ *     (primary_successes); `_fb_timeout` in state "primary" counts primary_failures and fallback_invocations, the state becomes
+ *     "fallback" and a NEW Event for the fallback entity is built from the entry with the `_fb_fallback_response` hook;
+ *     `_fb_fallback_response` in state "fallback" deletes the entry (fallback_successes).  Everything else is a processed no-op;
+ *     fallback_failures is never incremented by the reference.
+ * The hooks fire where a TimeoutWrapper's fire (above; twice behind a NetworkLink, never at a crashed or paused target: such an entry
+ * stays for ever).  The in-flight table of a wrapper lives in device memory of its own: open addressing on the id (ids ascend and are
+ * never reused), kept at most half full.
+ * Refused (HS_E_UNSUPPORTED): a target, primary or fallback entity that is, directly or through a chain of NetworkLinks, a LoadBalancer,
+ * Bulkhead, TimeoutWrapper, Client, Hedge or Fallback (two hooks on one Event) or a BatchProcessor, ConveyorBelt or GateController; a
+ * Bulkhead, TimeoutWrapper or Client whose target is a Hedge or a Fallback; max_hedges above HS_HEDGE_MAX_HEDGES.
+ *
+ * hs_graph_set_hedge / hs_graph_set_fallback: the delays in whole nanoseconds (the host evaluates Duration.from_seconds; timeout_ns < 0:
+ * None, the fallback entity is never invoked) and table_capacity, the entries the table holds at first (0: 256) -- a full table stops
+ * the launch in front of the Request, the host doubles it and the run goes on, nothing is ever dropped; beyond HS_HEDGE_MAX_IN_FLIGHT
+ * entries the run ends with HS_E_OVERFLOW naming the wrapper.  Before the first run (HS_E_STATE afterwards); every such node is
+ * configured before a run (HS_E_STATE otherwise). */
+#define HS_HEDGE_MAX_HEDGES 65535
+#define HS_HEDGE_MAX_IN_FLIGHT (1 << 20)
+#define HS_HEDGE_KINDS 7
+#define HS_HEDGE_COUNTERS 8
+#define HS_FALLBACK_COUNTERS 9
+int hs_graph_set_hedge(hs_graph *g, int32_t node, int64_t hedge_delay_ns, int32_t max_hedges, int32_t table_capacity);
+int hs_graph_set_fallback(hs_graph *g, int32_t node, int32_t fallback_node, int64_t timeout_ns, int32_t table_capacity);
+/* After a run, for `node` a Hedge (any output may be NULL):
+ *   counters[HS_HEDGE_COUNTERS]  total_requests, primary_wins, hedge_wins, hedges_sent, hedges_cancelled, _next_request_id,
+ *                     len(_in_flight), the table's capacity;
+ *   entries[5 * min(len(_in_flight), cap)]  per entry in flight, in no particular order: id, start_time ns, completed, hedges_sent,
+ *                     responses_received;
+ *   events[HS_HEDGE_KINDS]  the graph's Hedge request / response / send-hedge and Fallback request / primary-response / timeout /
+ *                     fallback-response Events: events_processed == sum(events_by_kind) + every other family's internal counts + sum(events).
+ * node = -1 with the two node outputs NULL: the event counts alone. */
+int hs_graph_get_hedge(hs_graph *g, int32_t node, int64_t *counters, int64_t *entries, int64_t cap, int64_t *events);
+/* ... for `node` a Fallback:
+ *   counters[HS_FALLBACK_COUNTERS]  total_requests, primary_successes, primary_failures, fallback_invocations, fallback_successes,
+ *                     fallback_failures, _next_request_id, len(_in_flight), the table's capacity;
+ *   entries[3 * min(len(_in_flight), cap)]  id, start_time ns, state (0 "primary", 1 "fallback");
+ *   events[HS_HEDGE_KINDS]  as above. */
+int hs_graph_get_fallback(hs_graph *g, int32_t node, int64_t *counters, int64_t *entries, int64_t cap, int64_t *events);
 /* Debug / tests only (the null stream, its own allocations): the compaction of a deployed LoadBalancer's member list on the device.
  * list[len] = slots in [0, n_slots) in insertion order, member[n_slots] = the membership word of every slot; the entries whose word is
  * 0 leave, the others keep their order: list[0 .. *out_len) afterwards.  wave = 0: the lone lane; 1: all 64 lanes (a ballot and a
