@@ -80,6 +80,9 @@ NODE_HEDGE, NODE_FALLBACK = 18, 19
 HEDGE_MAX_HEDGES, HEDGE_MAX_IN_FLIGHT = 65535, 1 << 20      # include/hs_engine.h HS_HEDGE_MAX_HEDGES / HS_HEDGE_MAX_IN_FLIGHT
 HEDGE_KINDS, HEDGE_COUNTERS, FALLBACK_COUNTERS = 7, 8, 9    # HS_HEDGE_KINDS / HS_HEDGE_COUNTERS / HS_FALLBACK_COUNTERS
 PROBE_NONE = 255
+# hs_graph_level: the levels of the single-heap loop (csrc/hs_graph.hip kLvPlain ... kLvHedge; a level carries the code of all below it)
+(GRAPH_LEVEL_PLAIN, GRAPH_LEVEL_FAULTS, GRAPH_LEVEL_HEALTH, GRAPH_LEVEL_RESILIENCE, GRAPH_LEVEL_CLIENT, GRAPH_LEVEL_FLOW, GRAPH_LEVEL_QUEUES,
+ GRAPH_LEVEL_LINK_FAULTS, GRAPH_LEVEL_SCALER, GRAPH_LEVEL_DEPLOY, GRAPH_LEVEL_HEDGE) = range(11)
 # hs_engine_run_path / hs_lb_run_path: which side of the host-side gates the last run landed on (include/hs_engine.h)
 RUN_ONE_LANE, RUN_ONE_LANE_UNI, RUN_WIDE, RUN_WAVE, RUN_TANDEM, RUN_SINGLE_HEAP = 1, 2, 4, 8, 16, 32
 RUN_F64_TIMES, RUN_NET_ASYNC, RUN_NET_ASYNC_UNI, RUN_NET_WINDOWED, RUN_NET_SEGMENTED = 64, 128, 256, 512, 1024
@@ -602,6 +605,8 @@ def lib():
     L.hs_graph_run_many.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]
     L.hs_graph_run_parts.restype = C.c_int
     L.hs_graph_run_parts.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]
+    L.hs_graph_level.restype = C.c_int
+    L.hs_graph_level.argtypes = [C.c_void_p, C.c_int]
     L.hs_graph_get_summary.restype = C.c_int
     L.hs_graph_get_summary.argtypes = [C.c_void_p, P(Summary)]
     L.hs_graph_get_stats.restype = C.c_int
@@ -656,4 +661,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_set_rolling_deployer", "hs_graph_get_rolling_deployer", "hs_debug_compact_members",
     "hs_graph_set_canary_deployer", "hs_graph_get_canary_deployer",
     "hs_graph_set_hedge", "hs_graph_set_fallback", "hs_graph_get_hedge", "hs_graph_get_fallback",
+    "hs_graph_level",
 )

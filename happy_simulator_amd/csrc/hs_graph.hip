@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <mutex>
 #include <cmath>
 #include <cstdio>
@@ -28,6 +29,7 @@
 #include <string>
 #include <vector>
 #include <type_traits>
+#include <utility>
 
 #include "../../include/hs_engine.h"
 #include "hs_device.hpp"
@@ -212,7 +214,30 @@ static_assert(kEvCnKinds <= 64, "kDropKindsDp is two words; s_by_kind is zeroed 
 // ... and all seven of a Hedge and a Fallback
 constexpr uint64_t kDropKindsHg = kDropKindsDp | (((1ull << HS_HEDGE_KINDS) - 1ull) << kEvHgReq);
 static_assert(kEvHgKinds <= 64, "kDropKindsHg is two words; s_by_kind is zeroed by one lane per kind");
-constexpr int kDefaultHedgeTable = 256;                  // entries a Hedge's / Fallback's table holds before it first grows
+// The levels of graph_loop.  A level carries all the code of the levels below it, and a graph (or a batch of graphs) runs at the lowest
+// level that dispatches all its kinds: the lone lane's loop is bound by its own instruction count and register allocation, so a graph
+// does not carry the code of a family it does not hold (the two fault tests per event were measurable).
+enum {
+    kLvPlain,          // Source, Server, Sink, Link, Router, LoadBalancer, Probe, RateLimitedEntity
+    kLvFaults,         // + fault Events (CrashNode / PauseNode)
+    kLvHealth,         // + a HealthChecker or an unhealthy backend
+    kLvResilience,     // + a Bulkhead or a TimeoutWrapper
+    kLvClient,         // + a Client
+    kLvFlow,           // + a BatchProcessor, a ConveyorBelt or a GateController
+    kLvQueues,         // + a Server with a LIFOQueue, an AdaptiveLIFO or a CoDelQueue (no kinds of its own)
+    kLvLinkFaults,     // + a link fault, InjectLatency / InjectPacketLoss (no kinds of its own)
+    kLvScaler,         // + an AutoScaler
+    kLvDeploy,         // + a RollingDeployer or a CanaryDeployer
+    kLvHedge,          // + a Hedge or a Fallback
+    kLevels
+};
+// ... the kinds a level dispatches (any other: kBadKind) ...
+constexpr uint32_t kLevelKinds[kLevels] = {kEvFaultOn, kEvHcCycle, kEvAllKinds, kEvResKinds, kEvCliKinds, kEvFlowKinds, kEvFlowKinds, kEvFlowKinds,
+                                           kEvAsKinds, kEvCnKinds, kEvHgKinds};
+// ... and those of them a crashed target drops (one word is tested below kLvFlow, two from there on)
+constexpr uint64_t kLevelDrop[kLevels] = {kDropKinds, kDropKinds, kDropKinds, kDropKindsRes, kDropKindsCli, kDropKindsFlow, kDropKindsFlow, kDropKindsFlow,
+                                          kDropKindsAs, kDropKindsDp, kDropKindsHg};
+constexpr int kDefaultHedgeTable = 256;                 // entries a Hedge's / Fallback's table holds before it first grows
 // One entry of a Hedge's or a Fallback's `_in_flight`: the id, start_time, the state and what a later duplicate of the Request is built
 // from -- the original Event's context as GRequest carries it (the first copy may long have been freed at a Sink).
 struct GHgEnt {                                // 40 bytes
@@ -485,8 +510,9 @@ __device__ __forceinline__ double uniform_at(uint64_t seed, uint64_t sid, uint64
 }
 
 // a Request-carrying Event aimed at `node`: which handler it lands in (Entity.handle_event of that class)
-template <bool R = false, bool CL = false, bool FL = false, bool HG = false>
+template <int L>
 __device__ __forceinline__ uint32_t arrival_kind(const GParam *P, int node) {
+    constexpr bool R = L >= kLvResilience, CL = L >= kLvClient, FL = L >= kLvFlow, HG = L >= kLvHedge;
     if constexpr (HG) {
         if (P[node].kind == HS_NODE_HEDGE) return kEvHgReq;
         if (P[node].kind == HS_NODE_FALLBACK) return kEvFbReq;
@@ -717,8 +743,9 @@ __device__ __forceinline__ int64_t ev_id(const GEvent &e) { return ((int64_t)(-2
 __device__ __forceinline__ int64_t req_id(const GRequest &q) { return __double_as_longlong(q.service_s); }
 // the `_bh_response` / `_tw_response` / `_client_response` kind of a hook's owner
 // (a Fallback's two hooks differ by the flag bit of the key that rode on the Request)
-template <bool CL, bool HG = false>
+template <int L>
 __device__ __forceinline__ uint32_t hook_resp_kind(uint8_t hk, [[maybe_unused]] int64_t key = 0) {
+    constexpr bool CL = L >= kLvClient, HG = L >= kLvHedge;
     if constexpr (HG) {
         if (hk == HS_NODE_HEDGE) return kEvHgResp;
         if (hk == HS_NODE_FALLBACK) return (key & kHgFlag) ? kEvFbFbResp : kEvFbPrimResp;
@@ -728,8 +755,9 @@ __device__ __forceinline__ uint32_t hook_resp_kind(uint8_t hk, [[maybe_unused]] 
     }
     return hk == HS_NODE_BULKHEAD ? kEvBhResp : kEvTwResp;
 }
-template <bool CL, bool HG = false>
+template <int L>
 __device__ __forceinline__ bool hook_has_id(uint8_t hk) {
+    constexpr bool CL = L >= kLvClient, HG = L >= kLvHedge;
     if constexpr (HG) {
         if (hk == HS_NODE_HEDGE || hk == HS_NODE_FALLBACK) return true;
     }
@@ -777,12 +805,7 @@ __device__ inline void hg_remove(const GHg &row, long long i) {
 
 // NL: graphs of up to NL nodes keep their nodes' parameters and state in LDS for the launch (the loop's dependent chain goes
 // through them several times per event: 64-cycle LDS round trips instead of L2's) -- `lnodes`: NL x (GParam + GState).
-// F: the graph has fault Events.  A graph without any runs the instantiation that holds none of their code (the lone lane's loop is
-// bound by its own instruction count and register allocation: the two tests per event were measurable).
-// HC: the graph (or one of a batch) has a HealthChecker or an unhealthy backend -- a third instantiation, so that the two above keep
-// their code: the fault-only loop is as sensitive to what it carries as the plain one.  HC implies F.
-// R: the graph (or one of a batch) has a Bulkhead or a TimeoutWrapper -- a fourth instantiation, for the same reason.  R implies HC.
-// CL: ... has a Client -- a fifth, for the same reason.  CL implies R.
+// L: the level (kLvPlain ... kLvHedge, above), which decides what code the instantiation carries.
 // A LoadBalancer's member list `hl` (`len` slots in insertion order) compacted by the membership words `mem` (by slot), order kept;
 // the new length.  On the lone lane ...
 __device__ inline int compact_members_lone(int32_t *hl, const uint8_t *mem, int len) {
@@ -807,25 +830,13 @@ __device__ inline int compact_members_wave(int32_t *hl, const uint8_t *mem, int 
     return w;
 }
 
-// FL: ... has a BatchProcessor, a ConveyorBelt or a GateController -- a sixth, for the same reason.  FL implies CL.
-// Q: ... has a Server with a LIFOQueue, an AdaptiveLIFO or a CoDelQueue -- a seventh, for the same reason.  Q implies FL.
-// LF: ... has a link fault (InjectLatency / InjectPacketLoss) -- an eighth, for the same reason.  LF implies Q.
-// AS: ... has an AutoScaler -- a ninth, for the same reason.  AS implies LF.
-template <int W, int NL, bool F = false, bool HC = false, bool R = false, bool CL = false, bool FL = false, bool Q = false, bool LF = false,
-          bool AS = false, bool DP = false, bool HG = false>
+template <int W, int NL, int L = kLvPlain>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
-    static_assert(F || !HC, "the health instantiation carries the fault code");
-    static_assert(HC || !R, "the resilience instantiation carries the fault and health code");
-    static_assert(R || !CL, "the client instantiation carries the fault, health and resilience code");
-    static_assert(CL || !FL, "the flow instantiation carries the fault, health, resilience and client code");
-    static_assert(FL || !Q, "the queue-policy instantiation carries the fault, health, resilience, client and flow code");
-    static_assert(Q || !LF, "the link-fault instantiation carries the code of all the others");
-    static_assert(LF || !AS, "the scaler instantiation carries the code of all the others");
-    static_assert(AS || !DP, "the deployer instantiation carries the code of all the others");
-    static_assert(DP || !HG, "the hedge instantiation carries the code of all the others");
-    constexpr uint32_t kKinds = HG ? kEvHgKinds : DP ? kEvCnKinds : AS ? kEvAsKinds : FL ? kEvFlowKinds : CL ? kEvCliKinds : R ? kEvResKinds : HC ? kEvAllKinds : F ? kEvHcCycle : kEvFaultOn;      // the kinds this instantiation dispatches (any other: kBadKind)
-    // (one word for the instantiations whose kinds fit in it, two for the flow instantiation's 39)
-    constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = HG ? kDropKindsHg : DP ? kDropKindsDp : AS ? kDropKindsAs : FL ? kDropKindsFlow : CL ? kDropKindsCli : R ? kDropKindsRes : kDropKinds;
+    constexpr bool F = L >= kLvFaults, HC = L >= kLvHealth, R = L >= kLvResilience, CL = L >= kLvClient, FL = L >= kLvFlow,
+                   Q = L >= kLvQueues, LF = L >= kLvLinkFaults, AS = L >= kLvScaler, DP = L >= kLvDeploy, HG = L >= kLvHedge;
+    constexpr uint32_t kKinds = kLevelKinds[L];            // the kinds this instantiation dispatches (any other: kBadKind)
+    // (one word for the instantiations whose kinds fit in it, two from the flow instantiation's 39 on)
+    constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = (std::conditional_t<FL, uint64_t, uint32_t>)kLevelDrop[L];
     constexpr int kPushes = R ? 3 : 2;         // heap entries one event constructs at most (R: a limiter's forward or poll + the hook's response)
     __shared__ unsigned long long s_by_kind[kKinds];
     __shared__ int s_want;                     // the LoadBalancer whose least-loaded selection the lone lane hands to the wavefront (-1: none)
@@ -959,7 +970,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             const int64_t t = c.sched_t[V.sched_done];
             GRequest q; q.created = t; q.idx = V.global_counter; q.service_s = 0.0; q.client = -1; q.next = -1; q.hook = -1; q.pre = 1;
             c.reqs[r] = q;
-            H.push(mk_pre(t, V.global_counter++, arrival_kind<R, CL, FL, HG>(c.P, node), node, r));
+            H.push(mk_pre(t, V.global_counter++, arrival_kind<L>(c.P, node), node, r));
             V.sched_done++;
         }
         cur = V.cur;
@@ -1148,7 +1159,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         GRequest rq; rq.created = t; rq.idx = idx_p; rq.service_s = 0.0; rq.client = (id << 32) | (int64_t)q; rq.next = -1; rq.hook = n; rq.pre = 0;
                         c.reqs[r] = rq;
                         const int be = c.rt_targets[lp.rt_off + q];
-                        H.push(mk(t, idx_p, arrival_kind<R, CL, FL, HG>(c.P, be), be, r));
+                        H.push(mk(t, idx_p, arrival_kind<L>(c.P, be), be, r));
                         GEvent te = mk(t + ns_from_seconds(p.lat_min), G++, kEvHcTimeout, n, -2 - q);
                         te.pad = (uint32_t)id << kPadIdShift;
                         H.push(te);
@@ -1297,7 +1308,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         GRequest q; q.created = en.created; q.idx = idx_p; q.service_s = __longlong_as_double(key); q.client = en.client;
                         q.next = -1; q.hook = n; q.pre = 0;
                         c.reqs[r] = q;
-                        H.push(mk(t, idx_p, arrival_kind<R, CL, FL, HG>(c.P, to), to, r));
+                        H.push(mk(t, idx_p, arrival_kind<L>(c.P, to), to, r));
                     };
                     // _forward_primary (hedge.py:176-217) / _forward_to_primary (fallback.py:179-248) up to the trigger / timeout: a new
                     // id, the entry with the original's context, the Request itself travels on as the NEW Event's
@@ -1310,7 +1321,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         hg_insert(row, en);                                        // (room: tested in front of the pop)
                         s.qlen += 1;
                         q.hook = n; q.service_s = __longlong_as_double(id);
-                        H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
+                        H.push(mk(t, G++, arrival_kind<L>(c.P, p.target), p.target, e.req));
                         return id;
                     };
                     const int64_t key = e.req >= 0 ? 0 : ev_id(e);
@@ -1574,7 +1585,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                             GRequest rq; rq.created = t; rq.idx = idx_p; rq.service_s = 0.0; rq.client = (int64_t)slot; rq.next = -1; rq.hook = n; rq.pre = 0;
                             c.reqs[r] = rq;
                             const int be = c.rt_targets[lp.rt_off + slot];
-                            H.push(mk(t, idx_p, arrival_kind<R, CL, FL, HG>(c.P, be), be, r));
+                            H.push(mk(t, idx_p, arrival_kind<L>(c.P, be), be, r));
                             H.push(mk(t + iv_ns, G++, kEvRdTimeout, n, -2 - slot));
                         }
                         break;
@@ -1631,8 +1642,8 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if (hook < 0) return;
                 if (!keep) c.reqs[r].hook = -1;
                 const uint8_t hk = c.P[hook].kind;
-                if (hook_has_id<CL, HG>(hk))
-                    H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(hk, req_id(c.reqs[r])), hook, req_id(c.reqs[r])));
+                if (hook_has_id<L>(hk))
+                    H.push(mk_id(t, G++, hook_resp_kind<L>(hk, req_id(c.reqs[r])), hook, req_id(c.reqs[r])));
                 else if (hk == HS_NODE_LB) H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
             };
             if constexpr (FL) {
@@ -1642,7 +1653,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     // GState: see hs_graph_get_flow.  No completion hook ever reaches one of them (a LoadBalancer's backends are Servers,
                     // a wrapper's or Client's target is refused), so a handler ends with the Events it constructs.
                     // A NEW Event for the downstream at `now` with the item's context (created_at survives), no hook:
-                    auto forward = [&](int r) { H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r)); };
+                    auto forward = [&](int r) { H.push(mk(t, G++, arrival_kind<L>(c.P, p.target), p.target, r)); };
                     // BatchProcessor._process_batch up to its yield (batch_processor.py:131-141) via Event._start_process: the buffer
                     // becomes the batch, the pending timeout is cancelled; one continuation is built and invoked at once, the pushed
                     // one is the second.  The batch's list and length travel in the entry: any number of batches is in process.
@@ -1748,7 +1759,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         if ((key >> kKeyAttemptShift) > 1) s.d += 1;
                         GRequest q; q.created = t; q.idx = 0; q.service_s = __longlong_as_double(key); q.client = -2 - key; q.next = -1; q.hook = n; q.pre = 0;
                         c.reqs[r] = q;
-                        H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r));
+                        H.push(mk(t, G++, arrival_kind<L>(c.P, p.target), p.target, r));
                         if (p.sub) H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvClTimeout, n, key));
                         continue;
                     }
@@ -1786,7 +1797,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         if (s.active > peaks[0]) peaks[0] = s.active;
                         tab[s.active - 1] = id;                                    // (active <= max_concurrent = rt_cnt)
                         c.reqs[r].hook = n; c.reqs[r].service_s = __longlong_as_double(id);
-                        H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r));
+                        H.push(mk(t, G++, arrival_kind<L>(c.P, p.target), p.target, r));
                     };
                     switch (e.kind) {
                     case kEvBhReq: {                                               // Bulkhead.handle_event (bulkhead.py:191-229)
@@ -1848,7 +1859,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                         tab[s.qlen] = id;                                          // (room: tested in front of the pop)
                         s.qlen += 1;
                         c.reqs[e.req].hook = n; c.reqs[e.req].service_s = __longlong_as_double(id);
-                        H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
+                        H.push(mk(t, G++, arrival_kind<L>(c.P, p.target), p.target, e.req));
                         H.push(mk_id(t + ns_from_seconds(p.lat_min), G++, kEvTwTimeout, n, id));
                     } break;
                     default: {                                                     // _handle_response / _handle_timeout (:222-295): whichever comes second finds nothing
@@ -1902,7 +1913,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                             H.push(re);
                         } else if (hook >= 0) {
                             const uint8_t hk = c.P[hook].kind;
-                            if (hook_has_id<CL, HG>(hk)) H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(hk, hook_id), hook, hook_id));
+                            if (hook_has_id<L>(hk)) H.push(mk_id(t, G++, hook_resp_kind<L>(hk, hook_id), hook, hook_id));
                             else H.push(mk(t, G++, HS_EV_LB_RESP, hook, -1));
                         }
                         continue;
@@ -1988,7 +1999,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 }
                 s.c += 1;                                                           // _generated_count (:159)
                 const int64_t a2 = next_arrival(c, n);
-                if (payload) H.push(mk(t, idx_p, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r));
+                if (payload) H.push(mk(t, idx_p, arrival_kind<L>(c.P, p.target), p.target, r));
                 if (a2 != kInfNs) H.push(mk(a2, G++, HS_EV_SOURCE, n, -1));       // RuntimeError: the source is exhausted (:176-180)
             } break;
             case HS_EV_ENQUEUE: {
@@ -2030,8 +2041,8 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 } else if (hook >= 0) {
                     if constexpr (R) {                                             // (a wrapper's hook: its id stayed on the Request)
                         const uint8_t hk = c.P[hook].kind;
-                        if (hook_has_id<CL, HG>(hk)) {
-                            H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(hk, req_id(c.reqs[e.req])), hook, req_id(c.reqs[e.req])));
+                        if (hook_has_id<L>(hk)) {
+                            H.push(mk_id(t, G++, hook_resp_kind<L>(hk, req_id(c.reqs[e.req])), hook, req_id(c.reqs[e.req])));
                             break;
                         }
                     }
@@ -2083,7 +2094,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 s.active = s.active > 0 ? s.active - 1 : 0;
                 s.c += 1; n_completed++;
                 s.total_service = __dadd_rn(s.total_service, c.reqs[e.req].service_s);
-                if (p.target >= 0) H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
+                if (p.target >= 0) H.push(mk(t, G++, arrival_kind<L>(c.P, p.target), p.target, e.req));
                 else { c.reqs[e.req].next = req_free; req_free = e.req; }
                 if (s.active < p.conc) H.push(mk(t, G++, HS_EV_POLL, n, -1));
             } break;
@@ -2104,11 +2115,11 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     const int hook = c.reqs[e.req].hook;                            //  its Event constructed behind the forward's)
                     const int64_t id = req_id(c.reqs[e.req]);
                     c.reqs[e.req].hook = -1;
-                    H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, tg), tg, e.req));
-                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(c.P[hook].kind, id), hook, id));
+                    H.push(mk(t, G++, arrival_kind<L>(c.P, tg), tg, e.req));
+                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<L>(c.P[hook].kind, id), hook, id));
                     break;
                 }
-                H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, tg), tg, e.req));
+                H.push(mk(t, G++, arrival_kind<L>(c.P, tg), tg, e.req));
             } break;
             case HS_EV_LINK: {
                 // NetworkLink.handle_event up to its yield (components/network/link.py:114-154, _calculate_delay :190-216)
@@ -2153,7 +2164,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
             case HS_EV_LINK_CONT:                                                   // transit over (link.py:156-189): a NEW Event for the egress
                 s.b += 1;
                 if (p.target >= 0) {
-                    H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
+                    H.push(mk(t, G++, arrival_kind<L>(c.P, p.target), p.target, e.req));
                     if constexpr (R) fire_hook(e.req, true);                        // ... and stays on the Event for the egress (link.py:181)
                 } else {
                     if constexpr (R) fire_hook(e.req, false);
@@ -2246,7 +2257,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 // a NEW Event for the backend with the same context (created_at survives) + the response hook (:398-431)
                 const int be = c.rt_targets[p.rt_off + slot];
                 c.reqs[e.req].hook = n;
-                H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, be), be, e.req));
+                H.push(mk(t, G++, arrival_kind<L>(c.P, be), be, e.req));
             } break;
             case HS_EV_LB_RESP:                                                     // LoadBalancer._handle_response (load_balancer.py:435-473)
                 if (s.d > 0) s.d -= 1;
@@ -2311,7 +2322,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if (lim_try_acquire(c, p, s, t)) {
                     // _forward (:164-178): a NEW Event for the downstream at `now` with a copy of the context, no completion hook
                     outcome = HS_LIMITER_FORWARDED;
-                    H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, e.req));
+                    H.push(mk(t, G++, arrival_kind<L>(c.P, p.target), p.target, e.req));
                 } else if (!(p.lim >= 0 && s.qlen >= p.lim)) {                     // FIFOQueue.push (queue_policy.py:94-98)
                     outcome = HS_LIMITER_QUEUED;
                     c.reqs[e.req].next = -1;
@@ -2332,7 +2343,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = outcome;
                 rec_n++;
                 if constexpr (R) {
-                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<CL, HG>(c.P[hook].kind, hook_id), hook, hook_id));
+                    if (hook >= 0) H.push(mk_id(t, G++, hook_resp_kind<L>(c.P[hook].kind, hook_id), hook, hook_id));
                 }
             } break;
             case kEvLimPoll: {
@@ -2349,7 +2360,7 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     s.qlen -= 1;
                     c.rec_node[rec_n] = n; c.rec_t[rec_n] = t; c.rec_cr[rec_n] = HS_LIMITER_DRAINED;
                     rec_n++;
-                    H.push(mk(t, G++, arrival_kind<R, CL, FL, HG>(c.P, p.target), p.target, r));
+                    H.push(mk(t, G++, arrival_kind<L>(c.P, p.target), p.target, r));
                     again = s.qlen > 0;
                 }
                 if (again) {
@@ -2495,69 +2506,11 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
     }
 }
 
-__global__ void __launch_bounds__(64) hs_graph_run(GCtl c) {
+template <int L>
+__global__ void __launch_bounds__(64) hs_graph_run_level(GCtl c) {
     __shared__ GEvent lheap[kLdsHeap];
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes>(c, lheap, lnodes);
-}
-__global__ void __launch_bounds__(64) hs_graph_run_faults(GCtl c) {           // ... of a graph with fault Events
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true>(c, lheap, lnodes);
-}
-
-__global__ void __launch_bounds__(64) hs_graph_run_health(GCtl c) {           // ... with a HealthChecker or an unhealthy backend
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true, true>(c, lheap, lnodes);
-}
-
-__global__ void __launch_bounds__(64) hs_graph_run_resilience(GCtl c) {       // ... with a Bulkhead or a TimeoutWrapper
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true, true, true>(c, lheap, lnodes);
-}
-
-__global__ void __launch_bounds__(64) hs_graph_run_client(GCtl c) {           // ... with a Client
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true>(c, lheap, lnodes);
-}
-
-__global__ void __launch_bounds__(64) hs_graph_run_flow(GCtl c) {             // ... with a BatchProcessor, a ConveyorBelt or a GateController
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true>(c, lheap, lnodes);
-}
-
-__global__ void __launch_bounds__(64) hs_graph_run_queues(GCtl c) {           // ... with a Server whose queue policy is not the FIFO
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true>(c, lheap, lnodes);
-}
-
-__global__ void __launch_bounds__(64) hs_graph_run_link_faults(GCtl c) {      // ... with an InjectLatency or an InjectPacketLoss
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true>(c, lheap, lnodes);
-}
-
-__global__ void __launch_bounds__(64) hs_graph_run_scaler(GCtl c) {           // ... with an AutoScaler
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
-}
-
-__global__ void __launch_bounds__(64) hs_graph_run_deploy(GCtl c) {           // ... with a RollingDeployer
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
-}
-
-__global__ void __launch_bounds__(64) hs_graph_run_hedge(GCtl c) {            // ... with a Hedge or a Fallback
-    __shared__ GEvent lheap[kLdsHeap];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodes * (sizeof(GParam) + sizeof(GState))];
-    graph_loop<kLdsHeap, kLdsNodes, true, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
+    graph_loop<kLdsHeap, kLdsNodes, L>(c, lheap, lnodes);
 }
 
 // hs_debug_compact_members: one list, one wavefront
@@ -2580,93 +2533,25 @@ __device__ __forceinline__ void batch_report(const GCtl &c, long long *stat) {
         o[3] = c.V->heap_len > 0 ? c.heap[0].t : 0;                // (the earliest pending event: hs_graph_run_parts elects across parts)
     }
 }
-__global__ void __launch_bounds__(64) hs_graph_run_batch(const GCtl *cs, long long *stat) {
+// (the batch runs at the highest level any of its handles needs: a handle of a lower level computes the same either way)
+template <int L>
+__global__ void __launch_bounds__(64) hs_graph_run_batch_level(const GCtl *cs, long long *stat) {
     __shared__ GEvent lheap[kLdsHeapBatch];
     __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
     const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch>(c, lheap, lnodes);
+    graph_loop<kLdsHeapBatch, kLdsNodesBatch, L>(c, lheap, lnodes);
     batch_report(c, stat);
 }
-// ... of a batch in which at least one handle has fault Events (a handle without any computes the same either way)
-__global__ void __launch_bounds__(64) hs_graph_run_batch_faults(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
-// ... of a batch in which at least one handle has health state
-__global__ void __launch_bounds__(64) hs_graph_run_batch_health(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
-// ... of a batch in which at least one handle has a wrapper
-__global__ void __launch_bounds__(64) hs_graph_run_batch_resilience(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
-// ... of a batch in which at least one handle has a Client
-__global__ void __launch_bounds__(64) hs_graph_run_batch_client(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
-// ... of a batch in which at least one handle has a flow entity
-__global__ void __launch_bounds__(64) hs_graph_run_batch_flow(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
-// ... of a batch in which at least one handle has a Server with a queue policy
-__global__ void __launch_bounds__(64) hs_graph_run_batch_queues(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
-// ... of a batch in which at least one handle has a link fault
-__global__ void __launch_bounds__(64) hs_graph_run_batch_link_faults(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
-// ... of a batch in which at least one handle has an AutoScaler
-__global__ void __launch_bounds__(64) hs_graph_run_batch_scaler(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
-// ... of a batch in which at least one handle has a RollingDeployer
-__global__ void __launch_bounds__(64) hs_graph_run_batch_deploy(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
-// ... of a batch in which at least one handle has a Hedge or a Fallback
-__global__ void __launch_bounds__(64) hs_graph_run_batch_hedge(const GCtl *cs, long long *stat) {
-    __shared__ GEvent lheap[kLdsHeapBatch];
-    __shared__ __attribute__((aligned(16))) char lnodes[kLdsNodesBatch * (sizeof(GParam) + sizeof(GState))];
-    const GCtl c = cs[blockIdx.x];
-    graph_loop<kLdsHeapBatch, kLdsNodesBatch, true, true, true, true, true, true, true, true, true, true>(c, lheap, lnodes);
-    batch_report(c, stat);
-}
+
+// One kernel of each form per level: these two tables are the only place that instantiates them.
+using LoneKernel = void (*)(GCtl);
+using BatchKernel = void (*)(const GCtl *, long long *);
+template <int... Ls>
+constexpr std::array<LoneKernel, sizeof...(Ls)> lone_kernels(std::integer_sequence<int, Ls...>) { return {{hs_graph_run_level<Ls>...}}; }
+template <int... Ls>
+constexpr std::array<BatchKernel, sizeof...(Ls)> batch_kernels(std::integer_sequence<int, Ls...>) { return {{hs_graph_run_batch_level<Ls>...}}; }
+constexpr auto kLoneKernels = lone_kernels(std::make_integer_sequence<int, kLevels>{});
+constexpr auto kBatchKernels = batch_kernels(std::make_integer_sequence<int, kLevels>{});
 
 }  // namespace graph
 }  // namespace hs
@@ -2759,6 +2644,7 @@ struct hs_graph {
     char *slab = nullptr; size_t slab_bytes = 0, slab_alloc = 0;   // every buffer of hs_graph_create in ONE allocation (a replica costs one hipMalloc / hipFree)
     double last_run_ms = 0.0;
     long long launches = 0;
+    int last_level = -1;                       // the level of the most recent launch the handle ran in (hs_graph_level)
     bool ran = false;
     long long pending_events = 0; int64_t earliest_ns = 0;   // after a batch launch: the heap's length and its top's time
     bool undecided = false;                    // a part run met a timestamp group only the whole Simulation orders (hs_graph_run_parts)
@@ -2817,6 +2703,27 @@ static int ensure_stream(hs_graph *g) {
     HS_HIP(g, hipEventCreate(&g->ev_a));
     HS_HIP(g, hipEventCreate(&g->ev_b));
     return HS_OK;
+}
+
+// The lowest level of graph_loop that dispatches every kind the graph holds.
+static int level_of(const hs_graph *g) {
+    if (g->n_hedges > 0) return kLvHedge;
+    if (g->n_deployers + g->n_canaries > 0) return kLvDeploy;
+    if (g->n_scalers > 0) return kLvScaler;
+    if (g->n_link_faults > 0) return kLvLinkFaults;
+    if (!g->qpol.empty()) return kLvQueues;
+    if (g->n_flows > 0) return kLvFlow;
+    if (g->n_clients > 0) return kLvClient;
+    if (g->n_wrappers > 0) return kLvResilience;
+    if (g->health) return kLvHealth;
+    if (!g->faults.empty()) return kLvFaults;
+    return kLvPlain;
+}
+static void launch_lone(int level, hipStream_t stream, const GCtl &ctl) {
+    hipLaunchKernelGGL(kLoneKernels[(size_t)level], dim3(1), dim3(64), 0, stream, ctl);
+}
+static void launch_batch(int level, unsigned blocks, hipStream_t stream, const GCtl *d_ctl, long long *d_stat) {
+    hipLaunchKernelGGL(kBatchKernels[(size_t)level], dim3(blocks), dim3(64), 0, stream, d_ctl, d_stat);
 }
 
 extern "C" {
@@ -4794,17 +4701,7 @@ int hs_graph_run_until(hs_graph *g, int64_t end_ns) {
     { const int rc = ensure_stream(g); if (rc) return rc; }
     HS_HIP(g, hipEventRecord(g->ev_a, g->stream));
     for (bool done = false; !done;) {
-        if (g->n_hedges > 0) hipLaunchKernelGGL(hs_graph_run_hedge, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else if (g->n_deployers + g->n_canaries > 0) hipLaunchKernelGGL(hs_graph_run_deploy, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, g->ctl);
-        else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, g->ctl);
+        launch_lone(g->last_level = level_of(g), g->stream, g->ctl);
         HS_HIP(g, hipGetLastError());
         HS_HIP(g, hipStreamSynchronize(g->stream));
         const int rc = after_launch(g, &done);
@@ -4852,27 +4749,10 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
             h_ctl.back().part = part;              // (the handles themselves never keep part semantics: no early return can leave it set)
         }
         if ((he = hipMemcpy(d_ctl, h_ctl.data(), h_ctl.size() * sizeof(GCtl), hipMemcpyHostToDevice)) != hipSuccess) break;
-        bool any_faults = false, any_health = false, any_wrappers = false, any_clients = false, any_flows = false, any_queues = false;
-        for (int i : pending) { any_faults |= !gs[i]->faults.empty(); any_health |= gs[i]->health; any_wrappers |= gs[i]->n_wrappers > 0; any_clients |= gs[i]->n_clients > 0; any_flows |= gs[i]->n_flows > 0; any_queues |= !gs[i]->qpol.empty(); }
-        bool any_link_faults = false;
-        for (int i : pending) any_link_faults |= gs[i]->n_link_faults > 0;
-        bool any_scalers = false;
-        for (int i : pending) any_scalers |= gs[i]->n_scalers > 0;
-        bool any_deployers = false;
-        for (int i : pending) any_deployers |= gs[i]->n_deployers + gs[i]->n_canaries > 0;
-        bool any_hedges = false;
-        for (int i : pending) any_hedges |= gs[i]->n_hedges > 0;
-        if (any_hedges) hipLaunchKernelGGL(hs_graph_run_batch_hedge, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else if (any_deployers) hipLaunchKernelGGL(hs_graph_run_batch_deploy, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else if (any_scalers) hipLaunchKernelGGL(hs_graph_run_batch_scaler, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else if (any_link_faults) hipLaunchKernelGGL(hs_graph_run_batch_link_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else if (any_queues) hipLaunchKernelGGL(hs_graph_run_batch_queues, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else if (any_flows) hipLaunchKernelGGL(hs_graph_run_batch_flow, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else if (any_clients) hipLaunchKernelGGL(hs_graph_run_batch_client, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else if (any_wrappers) hipLaunchKernelGGL(hs_graph_run_batch_resilience, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else if (any_health) hipLaunchKernelGGL(hs_graph_run_batch_health, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else if (!any_faults) hipLaunchKernelGGL(hs_graph_run_batch, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
-        else hipLaunchKernelGGL(hs_graph_run_batch_faults, dim3((unsigned)pending.size()), dim3(64), 0, g0->stream, (const GCtl *)d_ctl, d_stat);
+        int level = kLvPlain;                      // (the highest any pending handle needs: the others compute the same either way)
+        for (int i : pending) level = std::max(level, level_of(gs[i]));
+        for (int i : pending) gs[i]->last_level = level;
+        launch_batch(level, (unsigned)pending.size(), g0->stream, d_ctl, d_stat);
         if ((he = hipGetLastError()) != hipSuccess) break;
         if ((he = hipStreamSynchronize(g0->stream)) != hipSuccess) break;
         h_stat.resize((size_t)kBatchStat * pending.size());
@@ -4903,6 +4783,11 @@ static int run_batch(hs_graph *const *gs, int32_t n, int64_t end_ns, int part) {
 }
 
 int hs_graph_run_many(hs_graph *const *gs, int32_t n, int64_t end_ns) { return run_batch(gs, n, end_ns, 0); }
+
+int hs_graph_level(const hs_graph *g, int which) {
+    if (!g || (which != 0 && which != 1)) return -1;
+    return which == 0 ? level_of(g) : g->last_level;
+}
 
 int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
     {
@@ -4939,17 +4824,7 @@ int hs_graph_run_parts(hs_graph *const *gs, int32_t n, int64_t end_ns) {
         one.heap = g->ctl.heap; one.heap_cap = g->ctl.heap_cap; one.reqs = g->ctl.reqs; one.req_cap = g->ctl.req_cap;
         one.rec_node = g->ctl.rec_node; one.rec_t = g->ctl.rec_t; one.rec_cr = g->ctl.rec_cr; one.rec_cap = g->ctl.rec_cap;
         one.ticks = g->ctl.ticks; one.tick_cap = g->ctl.tick_cap; one.tick_count = g->ctl.tick_count; one.rs_tab = g->ctl.rs_tab;
-        if (g->n_hedges > 0) hipLaunchKernelGGL(hs_graph_run_hedge, dim3(1), dim3(64), 0, g->stream, one);
-        else if (g->n_deployers + g->n_canaries > 0) hipLaunchKernelGGL(hs_graph_run_deploy, dim3(1), dim3(64), 0, g->stream, one);
-        else if (g->n_scalers > 0) hipLaunchKernelGGL(hs_graph_run_scaler, dim3(1), dim3(64), 0, g->stream, one);
-        else if (g->n_link_faults > 0) hipLaunchKernelGGL(hs_graph_run_link_faults, dim3(1), dim3(64), 0, g->stream, one);
-        else if (!g->qpol.empty()) hipLaunchKernelGGL(hs_graph_run_queues, dim3(1), dim3(64), 0, g->stream, one);
-        else if (g->n_flows > 0) hipLaunchKernelGGL(hs_graph_run_flow, dim3(1), dim3(64), 0, g->stream, one);
-        else if (g->n_clients > 0) hipLaunchKernelGGL(hs_graph_run_client, dim3(1), dim3(64), 0, g->stream, one);
-        else if (g->n_wrappers > 0) hipLaunchKernelGGL(hs_graph_run_resilience, dim3(1), dim3(64), 0, g->stream, one);
-        else if (g->health) hipLaunchKernelGGL(hs_graph_run_health, dim3(1), dim3(64), 0, g->stream, one);
-        else if (g->faults.empty()) hipLaunchKernelGGL(hs_graph_run, dim3(1), dim3(64), 0, g->stream, one);
-        else hipLaunchKernelGGL(hs_graph_run_faults, dim3(1), dim3(64), 0, g->stream, one);
+        launch_lone(g->last_level = level_of(g), g->stream, one);
         HS_HIP(g0, hipGetLastError());
         HS_HIP(g0, hipStreamSynchronize(g->stream));
         bool done = false;

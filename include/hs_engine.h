@@ -1306,6 +1306,11 @@ int hs_graph_run_many(hs_graph *const *graphs, int32_t n, int64_t end_ns);
  * -- case (i) occurred, or two parts hold the earliest time: the caller repeats the run on one heap (the handles' state is then
  * meaningless); or a negative hs_status.  Call once per handle set (no later end). */
 int hs_graph_run_parts(hs_graph *const *parts, int32_t n, int64_t end_ns);
+/* Read-only: the level of the loop (csrc/hs_graph.hip kLvPlain ... kLvHedge: 0 plain, 1 faults, 2 health, 3 resilience, 4 client,
+ * 5 flow, 6 queue policies, 7 link faults, 8 scaler, 9 deployers, 10 hedge; a level carries the code of all below it).  which = 0: the
+ * lowest level that dispatches all the graph's kinds, the one a lone run takes; which = 1: the level of the most recent launch the
+ * handle ran in (a batch runs at the highest level of its handles), -1 before the first launch.  -1 for any other `which`. */
+int hs_graph_level(const hs_graph *g, int which);
 int hs_graph_get_summary(hs_graph *g, hs_summary *out);
 int hs_graph_get_stats(hs_graph *g, hs_graph_stats *out);
 /* Every Sink record of the run in processing order: (Sink node, completion ns, created_at ns).  Returns the number of

@@ -221,5 +221,7 @@ def test_the_side_by_side_kernels_lds_windows_are_the_sizes_the_gpu_tests_cross(
 
     text = open(os.path.join(N.CSRC, "hs_graph.hip")).read()
     assert "kLdsHeapBatch = 1024" in text and "kLdsNodesBatch = 48" in text
-    assert "graph_loop<kLdsHeapBatch, kLdsNodesBatch>" in text             # ... and it is these two the batch kernel is built with
+    batch = text[text.index("hs_graph_run_batch_level(const GCtl *cs"):]
+    batch = batch[:batch.index("\n}\n")]                                     # ... and it is these two every level of the batch kernel is built with
+    assert "graph_loop<kLdsHeapBatch, kLdsNodesBatch, L>" in batch
     assert "(long long)n * 4 + 1024);" in text                             # hs_graph_create: the smallest heap_cap of a handle

@@ -1,6 +1,6 @@
 """ON THE GPU BOX: the capacity experiment in ONE Simulation -- Source.poisson(40) -> LoadBalancer(LeastConnections) over one
 Server(Exp(0.05)), scaled by an AutoScaler(TargetUtilization(0.6), 1 .. 4 instances, evaluated every 0.5 s, cooldowns of 1 s and 2 s)
--> Sink per group -- the single-heap loop's scaler instantiation (csrc/hs_graph.hip hs_graph_run_batch_scaler) with the data-parallel
+-> Sink per group -- the single-heap loop's scaler instantiation (csrc/hs_graph.hip hs_graph_run_batch_level<kLvScaler>) with the data-parallel
 dimension a Simulation has: its parts (hs_graph_run_parts, up to 2 048 heaps side by side).  Prints one JSON line: events/s of the
 device and the device time; `wall_s` is Simulation.run() as a whole.  A demonstration: nothing else runs a scaler, so the loop's
 ~2.5 us per event and heap is the only figure it can be set against.

@@ -1,7 +1,7 @@
 """ON THE GPU BOX: rolling deployments in ONE Simulation -- Source.poisson(40) -> LoadBalancer(LeastConnections) over three
 Server(Exp(0.05)), replaced by a RollingDeployer(batch_size=1, health_check_interval=0.5, healthy_threshold=2, max_failures=3) whose
 deploy() is scheduled at 1 s -> Sink per group -- the single-heap loop's deployer instantiation (csrc/hs_graph.hip
-hs_graph_run_batch_deploy) with the data-parallel dimension a Simulation has: its parts (hs_graph_run_parts, up to 2 048 heaps side by
+hs_graph_run_batch_level<kLvDeploy>) with the data-parallel dimension a Simulation has: its parts (hs_graph_run_parts, up to 2 048 heaps side by
 side).  Prints one JSON line: events/s of the device and the device time; `wall_s` is Simulation.run() as a whole.  A demonstration:
 nothing else runs a deployer, so the loop's ~2.5 us per event and heap is the only figure it can be set against.
 

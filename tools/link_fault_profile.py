@@ -1,7 +1,7 @@
 """ON THE GPU BOX: the degraded-network experiment in ONE Simulation -- Source.poisson(60) -> Client(timeout 80 ms, FixedRetry(3, 50 ms)) ->
 NetworkLink(20 ms + Exp(10 ms)) -> Server(c = 2, Exp(0.01)) -> Sink per group, every link registered in one Network, with
 InjectLatency(+100 ms) from 2 s to 4 s and InjectPacketLoss(0.3) from 5 s to 7 s on every link -- the single-heap loop's link-fault
-instantiation (csrc/hs_graph.hip hs_graph_run_batch_link_faults) with the data-parallel dimension a Simulation has: its parts
+instantiation (csrc/hs_graph.hip hs_graph_run_batch_level<kLvLinkFaults>) with the data-parallel dimension a Simulation has: its parts
 (hs_graph_run_parts, up to 2 048 heaps side by side).  Prints one JSON line: events/s of the device and the device time; `wall_s` is
 Simulation.run() as a whole.  A demonstration: nothing else runs these faults, so the loop's ~2.5 us per event and heap is the only
 figure it can be set against.

@@ -1,6 +1,6 @@
 """ON THE GPU BOX: chains with queue policies in ONE Simulation -- Source.poisson(60) -> Server(c = 2, Exp(0.02), CoDelQueue(0.005, 0.02))
 -> Server(Exp(0.012), AdaptiveLIFO(4, capacity 32)) -> Server(Exp(0.01), LIFOQueue(16)) -> Sink -- the single-heap loop's queue-policy
-instantiation (csrc/hs_graph.hip hs_graph_run_batch_queues: a pop that takes the newest item, a pop that drops the items behind the one
+instantiation (csrc/hs_graph.hip hs_graph_run_batch_level<kLvQueues>: a pop that takes the newest item, a pop that drops the items behind the one
 it delivers) with the data-parallel dimension a Simulation has: its parts (hs_graph_run_parts, up to 2 048 heaps side by side).  Prints
 one JSON line: events/s of the device and the device time; `wall_s` is Simulation.run() as a whole.  A demonstration: nothing else
 runs these policies, so the loop's ~2.5 us per event and heap is the only figure it can be set against.
