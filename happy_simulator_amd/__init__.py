@@ -28,6 +28,7 @@ from .entities import (FixedWindowPolicy, LeakyBucketPolicy, RateLimitedEntity, 
 from .entities import BackendHealthState, HealthChecker, HealthCheckStats  # noqa: F401
 from .entities import Bulkhead, BulkheadStats, TimeoutStats, TimeoutWrapper  # noqa: F401
 from .entities import Fallback, FallbackStats, Hedge, HedgeStats  # noqa: F401
+from .entities import InventoryBuffer, InventoryStats, PooledCycleResource, PooledCycleStats  # noqa: F401
 from .entities import Client, ClientStats, DecorrelatedJitter, ExponentialBackoff, FixedRetry, NoRetry  # noqa: F401
 from .entities import (AdaptiveLIFO, AdaptiveLIFOStats, CoDelQueue, CoDelStats, DeadlineQueue, FairQueue, LIFOQueue, PriorityQueue,  # noqa: F401
                        REDQueue, WeightedFairQueue)

@@ -79,10 +79,16 @@ PROBE_HEDGE_METRICS = {"in_flight_count": 17}               # ... of a Hedge
 NODE_HEDGE, NODE_FALLBACK = 18, 19
 HEDGE_MAX_HEDGES, HEDGE_MAX_IN_FLIGHT = 65535, 1 << 20      # include/hs_engine.h HS_HEDGE_MAX_HEDGES / HS_HEDGE_MAX_IN_FLIGHT
 HEDGE_KINDS, HEDGE_COUNTERS, FALLBACK_COUNTERS = 7, 8, 9    # HS_HEDGE_KINDS / HS_HEDGE_COUNTERS / HS_FALLBACK_COUNTERS
+NODE_POOLED_CYCLE, NODE_INVENTORY = 20, 21
+# ... of a PooledCycleResource (available / active / queued) and an InventoryBuffer (stock)
+PROBE_STOCK_METRICS = {"available": 18, "active": 19, "queued": 20, "stock": 21}
+POOL_MAX_UNITS, INVENTORY_MAX = 1 << 20, 1 << 62             # include/hs_engine.h HS_POOL_MAX_UNITS / HS_INVENTORY_MAX
+INVENTORY_MAX_LEVEL = (1 << 63) - (1 << 48)                  # HS_INVENTORY_MAX_LEVEL: reorder_point + order_quantity
+STOCK_KINDS, POOL_COUNTERS, INVENTORY_COUNTERS = 4, 5, 6    # HS_STOCK_KINDS / HS_POOL_COUNTERS / HS_INVENTORY_COUNTERS
 PROBE_NONE = 255
-# hs_graph_level: the levels of the single-heap loop (csrc/hs_graph.hip kLvPlain ... kLvHedge; a level carries the code of all below it)
+# hs_graph_level: the levels of the single-heap loop (csrc/hs_graph.hip kLvPlain ... kLvStock; a level carries the code of all below it)
 (GRAPH_LEVEL_PLAIN, GRAPH_LEVEL_FAULTS, GRAPH_LEVEL_HEALTH, GRAPH_LEVEL_RESILIENCE, GRAPH_LEVEL_CLIENT, GRAPH_LEVEL_FLOW, GRAPH_LEVEL_QUEUES,
- GRAPH_LEVEL_LINK_FAULTS, GRAPH_LEVEL_SCALER, GRAPH_LEVEL_DEPLOY, GRAPH_LEVEL_HEDGE) = range(11)
+ GRAPH_LEVEL_LINK_FAULTS, GRAPH_LEVEL_SCALER, GRAPH_LEVEL_DEPLOY, GRAPH_LEVEL_HEDGE, GRAPH_LEVEL_STOCK) = range(12)
 # hs_engine_run_path / hs_lb_run_path: which side of the host-side gates the last run landed on (include/hs_engine.h)
 RUN_ONE_LANE, RUN_ONE_LANE_UNI, RUN_WIDE, RUN_WAVE, RUN_TANDEM, RUN_SINGLE_HEAP = 1, 2, 4, 8, 16, 32
 RUN_F64_TIMES, RUN_NET_ASYNC, RUN_NET_ASYNC_UNI, RUN_NET_WINDOWED, RUN_NET_SEGMENTED = 64, 128, 256, 512, 1024
@@ -585,6 +591,13 @@ def lib():
     for name in ("hs_graph_get_hedge", "hs_graph_get_fallback"):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.hs_graph_set_pool.restype = C.c_int
+    L.hs_graph_set_pool.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    L.hs_graph_set_inventory.restype = C.c_int
+    L.hs_graph_set_inventory.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int32]
+    for name in ("hs_graph_get_pool", "hs_graph_get_inventory"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.hs_debug_compact_members.restype = C.c_int
     L.hs_debug_compact_members.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.hs_debug_codel_next.restype = C.c_int
@@ -662,4 +675,5 @@ EXPORTED_SYMBOLS = (
     "hs_graph_set_canary_deployer", "hs_graph_get_canary_deployer",
     "hs_graph_set_hedge", "hs_graph_set_fallback", "hs_graph_get_hedge", "hs_graph_get_fallback",
     "hs_graph_level",
+    "hs_graph_set_pool", "hs_graph_set_inventory", "hs_graph_get_pool", "hs_graph_get_inventory",
 )

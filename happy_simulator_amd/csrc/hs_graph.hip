@@ -184,6 +184,12 @@ constexpr uint32_t kEvHgReq = kEvCnKinds, kEvHgResp = kEvCnKinds + 1, kEvHgSend 
 constexpr int kHgIdBits = 34, kHgFlagBit = 50;               // (a key's bits above the low 30 ride in GEvent::req: at most 31 of them)
 constexpr int64_t kHgIdMask = (1ll << kHgIdBits) - 1, kHgFlag = 1ll << kHgFlagBit;
 static_assert(HS_HEDGE_MAX_HEDGES < (1 << (kHgFlagBit - kHgIdBits)), "hedge_number fits between the id and the flag");
+// PooledCycleResource / InventoryBuffer (components/industrial/pooled_cycle.py, inventory.py): a Request at a pool, the continuation of
+// its cycle (it carries the Request); a consume Request at a buffer, its `_InventoryReplenish` (no Request) -- the last four kinds the
+// kind word holds (60 .. 63 of 64: the next family widens kDrop and s_by_kind first).  They count in events_processed and per graph
+// (GVars::st_by_kind).
+constexpr uint32_t kEvPcItem = kEvHgKinds, kEvPcCont = kEvHgKinds + 1, kEvIbItem = kEvHgKinds + 2, kEvIbReplenish = kEvHgKinds + 3,
+                   kEvStKinds = kEvHgKinds + HS_STOCK_KINDS;
 constexpr int kMaxFlowItems = HS_FLOW_MAX_ITEMS;            // batch_size / a bounded gate queue: a batch's length rides in 30 bits of GEvent::pad
 constexpr uint32_t kPadPre = 1u, kPadCancelled = 2u;
 constexpr int kPadIdShift = 2;                 // a check id in GEvent::pad (its low 30 bits: only the one pending id of a backend and ids
@@ -214,6 +220,9 @@ static_assert(kEvCnKinds <= 64, "kDropKindsDp is two words; s_by_kind is zeroed 
 // ... and all seven of a Hedge and a Fallback
 constexpr uint64_t kDropKindsHg = kDropKindsDp | (((1ull << HS_HEDGE_KINDS) - 1ull) << kEvHgReq);
 static_assert(kEvHgKinds <= 64, "kDropKindsHg is two words; s_by_kind is zeroed by one lane per kind");
+// ... and the three of a pool and a buffer that are aimed at the entity itself (the end of a cycle resumes a generator)
+constexpr uint64_t kDropKindsSt = kDropKindsHg | (1ull << kEvPcItem) | (1ull << kEvIbItem) | (1ull << kEvIbReplenish);
+static_assert(kEvStKinds <= 64, "kDropKindsSt is two words; s_by_kind is zeroed by one lane per kind");
 // The levels of graph_loop.  A level carries all the code of the levels below it, and a graph (or a batch of graphs) runs at the lowest
 // level that dispatches all its kinds: the lone lane's loop is bound by its own instruction count and register allocation, so a graph
 // does not carry the code of a family it does not hold (the two fault tests per event were measurable).
@@ -229,14 +238,21 @@ enum {
     kLvScaler,         // + an AutoScaler
     kLvDeploy,         // + a RollingDeployer or a CanaryDeployer
     kLvHedge,          // + a Hedge or a Fallback
+    kLvStock,          // + a PooledCycleResource or an InventoryBuffer
     kLevels
 };
 // ... the kinds a level dispatches (any other: kBadKind) ...
 constexpr uint32_t kLevelKinds[kLevels] = {kEvFaultOn, kEvHcCycle, kEvAllKinds, kEvResKinds, kEvCliKinds, kEvFlowKinds, kEvFlowKinds, kEvFlowKinds,
-                                           kEvAsKinds, kEvCnKinds, kEvHgKinds};
+                                           kEvAsKinds, kEvCnKinds, kEvHgKinds, kEvStKinds};
 // ... and those of them a crashed target drops (one word is tested below kLvFlow, two from there on)
 constexpr uint64_t kLevelDrop[kLevels] = {kDropKinds, kDropKinds, kDropKinds, kDropKindsRes, kDropKindsCli, kDropKindsFlow, kDropKindsFlow, kDropKindsFlow,
-                                          kDropKindsAs, kDropKindsDp, kDropKindsHg};
+                                          kDropKindsAs, kDropKindsDp, kDropKindsHg, kDropKindsSt};
+// GParam of a PooledCycleResource: conc = pool_size, lim = cycle_time in ns, rt_cnt = queue_capacity (0: unbounded), target = its
+// downstream (-1: none).  GState: a = completed, b = rejected, active = _active (_available = pool_size - _active: the two move
+// together), qhead / qtail / qlen = _queue through Request::next.
+// GParam of an InventoryBuffer: lim = reorder_point, stream_base = order_quantity, mean = lead_time in seconds, target = its downstream,
+// conc = its stockout_target (-1: none).  GState: a = _stock, b = stockouts, c = reorders, d = items_consumed,
+// svc_draws = items_replenished, active = _order_pending.
 constexpr int kDefaultHedgeTable = 256;                 // entries a Hedge's / Fallback's table holds before it first grows
 // One entry of a Hedge's or a Fallback's `_in_flight`: the id, start_time, the state and what a later duplicate of the Request is built
 // from -- the original Event's context as GRequest carries it (the first copy may long have been freed at a Sink).
@@ -389,6 +405,7 @@ struct GVars {                                 // device scalars
     int rd_coop_min;                           // a removal from a list of >= this many members is compacted by all 64 lanes (0: never)
     GHg *hg;                                   // the rows of the Hedges and Fallbacks (hs_graph_set_hedge / hs_graph_set_fallback; null: none)
     long long hg_by_kind[HS_HEDGE_KINDS];      // their Events by kind, kEvHgReq .. kEvFbFbResp (hs_graph_get_hedge)
+    long long st_by_kind[HS_STOCK_KINDS];      // the pools' and buffers' Events by kind, kEvPcItem .. kEvIbReplenish (hs_graph_get_pool)
 };
 
 struct GCtl {                                  // kernel argument
@@ -512,7 +529,11 @@ __device__ __forceinline__ double uniform_at(uint64_t seed, uint64_t sid, uint64
 // a Request-carrying Event aimed at `node`: which handler it lands in (Entity.handle_event of that class)
 template <int L>
 __device__ __forceinline__ uint32_t arrival_kind(const GParam *P, int node) {
-    constexpr bool R = L >= kLvResilience, CL = L >= kLvClient, FL = L >= kLvFlow, HG = L >= kLvHedge;
+    constexpr bool R = L >= kLvResilience, CL = L >= kLvClient, FL = L >= kLvFlow, HG = L >= kLvHedge, ST = L >= kLvStock;
+    if constexpr (ST) {
+        if (P[node].kind == HS_NODE_POOLED_CYCLE) return kEvPcItem;
+        if (P[node].kind == HS_NODE_INVENTORY) return kEvIbItem;
+    }
     if constexpr (HG) {
         if (P[node].kind == HS_NODE_HEDGE) return kEvHgReq;
         if (P[node].kind == HS_NODE_FALLBACK) return kEvFbReq;
@@ -805,7 +826,7 @@ __device__ inline void hg_remove(const GHg &row, long long i) {
 
 // NL: graphs of up to NL nodes keep their nodes' parameters and state in LDS for the launch (the loop's dependent chain goes
 // through them several times per event: 64-cycle LDS round trips instead of L2's) -- `lnodes`: NL x (GParam + GState).
-// L: the level (kLvPlain ... kLvHedge, above), which decides what code the instantiation carries.
+// L: the level (kLvPlain ... kLvStock, above), which decides what code the instantiation carries.
 // A LoadBalancer's member list `hl` (`len` slots in insertion order) compacted by the membership words `mem` (by slot), order kept;
 // the new length.  On the lone lane ...
 __device__ inline int compact_members_lone(int32_t *hl, const uint8_t *mem, int len) {
@@ -833,7 +854,8 @@ __device__ inline int compact_members_wave(int32_t *hl, const uint8_t *mem, int 
 template <int W, int NL, int L = kLvPlain>
 __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *lnodes) {
     constexpr bool F = L >= kLvFaults, HC = L >= kLvHealth, R = L >= kLvResilience, CL = L >= kLvClient, FL = L >= kLvFlow,
-                   Q = L >= kLvQueues, LF = L >= kLvLinkFaults, AS = L >= kLvScaler, DP = L >= kLvDeploy, HG = L >= kLvHedge;
+                   Q = L >= kLvQueues, LF = L >= kLvLinkFaults, AS = L >= kLvScaler, DP = L >= kLvDeploy, HG = L >= kLvHedge,
+                   ST = L >= kLvStock;
     constexpr uint32_t kKinds = kLevelKinds[L];            // the kinds this instantiation dispatches (any other: kBadKind)
     // (one word for the instantiations whose kinds fit in it, two from the flow instantiation's 39 on)
     constexpr std::conditional_t<FL, uint64_t, uint32_t> kDrop = (std::conditional_t<FL, uint64_t, uint32_t>)kLevelDrop[L];
@@ -1290,6 +1312,70 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                     }
                     H.push(mk(t + ns_from_seconds(p.mean), G++, kEvAsEval, n, -1));   // self.now + Duration.from_seconds(evaluation_interval)
                     polls_pending += 1;
+                    continue;
+                }
+            }
+            if constexpr (ST) {
+                if (e.kind >= kEvPcItem) {
+                    // PooledCycleResource.handle_event (pooled_cycle.py:120-141) / InventoryBuffer.handle_event (inventory.py:118-121).
+                    // No completion hook ever rides on an Event that reaches one of them (a wrapper's or Client's target is refused,
+                    // a LoadBalancer's backends are Servers), so a handler ends with the Events it constructs.
+                    // A NEW Event for `to` at `now` with the Request's context (created_at and a client key survive), no hook;
+                    // without a receiver the Request ends here:
+                    auto forward = [&](int to, int r) {
+                        if (to >= 0) H.push(mk(t, G++, arrival_kind<L>(c.P, to), to, r));
+                        else { c.reqs[r].next = req_free; req_free = r; }
+                    };
+                    switch (e.kind) {
+                    case kEvPcItem:
+                        if (s.active < p.conc) {                                    // _start_cycle up to its yield (:143-148) via
+                            s.active += 1;                                          // Event._start_process: one continuation is built and
+                            (void)G++;                                              // invoked at once, the pushed one is the second
+                            H.push(mk(t + p.lim, G++, kEvPcCont, n, e.req));
+                        } else if (p.rt_cnt > 0 && s.qlen >= p.rt_cnt) {            // the line is full (:125-133)
+                            s.b += 1;
+                            c.reqs[e.req].next = req_free; req_free = e.req;
+                        } else {                                                    // _queue.append (:135)
+                            c.reqs[e.req].next = -1;
+                            if (s.qtail >= 0) c.reqs[s.qtail].next = e.req; else s.qhead = e.req;
+                            s.qtail = e.req;
+                            s.qlen += 1;
+                        }
+                        break;
+                    case kEvPcCont:                                                 // behind the yield (:149-179): the unit returns, the
+                        s.active -= 1;                                              // Request travels on, then the head of the line is sent
+                        s.a += 1;                                                   // to the pool ITSELF as a new Event: it takes a fresh
+                        forward(p.target, e.req);                                   // sort index and goes through the heap
+                        if (s.qlen > 0 && s.active < p.conc) {
+                            const int r = s.qhead;
+                            s.qhead = c.reqs[r].next;
+                            if (s.qhead < 0) s.qtail = -1;
+                            s.qlen -= 1;
+                            c.reqs[r].next = -1;
+                            H.push(mk(t, G++, kEvPcItem, n, r));
+                        }
+                        break;
+                    case kEvIbItem:                                                 // _handle_consume (inventory.py:123-181), amount = 1
+                        if (s.a >= 1) {
+                            s.a -= 1;
+                            s.d += 1;
+                            forward(p.target, e.req);
+                        } else {
+                            s.b += 1;
+                            forward(p.conc, e.req);
+                        }
+                        if (s.a <= p.lim && !s.active) {                            // the reorder (:161-172), behind the forward:
+                            s.active = 1;                                           // Instant.from_seconds(now.to_seconds() + lead_time)
+                            s.c += 1;
+                            H.push(mk(ns_from_seconds(__dadd_rn(seconds_from_ns(t), p.mean)), G++, kEvIbReplenish, n, -1));
+                        }
+                        break;
+                    default:                                                        // _handle_replenish (:183-194)
+                        s.a += (int64_t)p.stream_base;
+                        s.svc_draws += p.stream_base;
+                        s.active = 0;
+                        break;
+                    }
                     continue;
                 }
             }
@@ -2304,6 +2390,12 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
                 if constexpr (HG) {                                                 // Hedge.in_flight_count
                     if (p.sub == HS_PROBE_HG_IN_FLIGHT) v = tg.qlen;
                 }
+                if constexpr (ST) {                                                 // PooledCycleResource.available / active / queued,
+                    if (p.sub == HS_PROBE_PC_AVAILABLE) v = (int64_t)c.P[p.target].conc - tg.active;     // InventoryBuffer.stock
+                    else if (p.sub == HS_PROBE_PC_ACTIVE) v = tg.active;
+                    else if (p.sub == HS_PROBE_PC_QUEUED) v = tg.qlen;
+                    else if (p.sub == HS_PROBE_IB_STOCK) v = tg.a;
+                }
                 if constexpr (FL) {                                                 // (the flow entities' metrics likewise)
                     if (p.sub == HS_PROBE_BP_BUFFER_DEPTH || p.sub == HS_PROBE_GT_QUEUE_DEPTH) v = tg.qlen;   // buffer_depth / queue_depth
                     else if (p.sub == HS_PROBE_CV_IN_TRANSIT) v = tg.active;        // ConveyorBelt.items_in_transit
@@ -2488,6 +2580,9 @@ __device__ __forceinline__ void graph_loop(const GCtl &c0, GEvent *lheap, char *
         if constexpr (HG) {
             for (int k = 0; k < HS_HEDGE_KINDS; ++k) V.hg_by_kind[k] += (long long)s_by_kind[kEvHgReq + k];
         }
+        if constexpr (ST) {
+            for (int k = 0; k < HS_STOCK_KINDS; ++k) V.st_by_kind[k] += (long long)s_by_kind[kEvPcItem + k];
+        }
         V.coop_selects = (c.coop_reset ? 0 : V.coop_selects) + n_coop;
         V.status = status;
     }
@@ -2633,6 +2728,7 @@ struct hs_graph {
     std::vector<GHg> hg_rows;                  // in node order (GParam::rt_off = the row)
     std::vector<int32_t> hg_node;              // the wrapper node of every row
     GHg *d_hg = nullptr;
+    int n_stock = 0;                           // PooledCycleResource / InventoryBuffer nodes: a graph that holds one runs at kLvStock
     int debug_flags = 0;                       // hs_debug_graph_flags
     // tick tables: one row per time-varying Source and per distinct Probe interval, computed up to `tick_horizon`
     std::vector<hs::TickRow> rows;
@@ -2707,6 +2803,7 @@ static int ensure_stream(hs_graph *g) {
 
 // The lowest level of graph_loop that dispatches every kind the graph holds.
 static int level_of(const hs_graph *g) {
+    if (g->n_stock > 0) return kLvStock;
     if (g->n_hedges > 0) return kLvHedge;
     if (g->n_deployers + g->n_canaries > 0) return kLvDeploy;
     if (g->n_scalers > 0) return kLvScaler;
@@ -2760,6 +2857,8 @@ static const char *hook_refused(int kind) {
         return "a LoadBalancer, Bulkhead, TimeoutWrapper, Client, Hedge or Fallback: two completion hooks on one Event are not lowered";
     case HS_NODE_BATCH_PROCESSOR: case HS_NODE_CONVEYOR: case HS_NODE_GATE:
         return "a BatchProcessor, ConveyorBelt or GateController: a completion hook on an item they hold is not lowered";
+    case HS_NODE_POOLED_CYCLE: case HS_NODE_INVENTORY:
+        return "a PooledCycleResource or an InventoryBuffer: a completion hook on an item they hold or forward is not lowered";
     default: return nullptr;
     }
 }
@@ -2779,7 +2878,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
     if (cfg->start_ns < 0)        // (the Sinks' merged records hold non-negative times)
         return fail(nullptr, HS_E_UNSUPPORTED, "start_time %lld ns is negative: not lowered", (long long)cfg->start_ns);
     bool has_wrr = false;
-    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER || k == HS_NODE_BULKHEAD || k == HS_NODE_TIMEOUT_WRAPPER || k == HS_NODE_CLIENT || k == HS_NODE_BATCH_PROCESSOR || k == HS_NODE_CONVEYOR || k == HS_NODE_GATE || k == HS_NODE_HEDGE || k == HS_NODE_FALLBACK; };
+    auto takes_requests = [&](int t) { const int k = nd->kind[t]; return k == HS_NODE_SERVER || k == HS_NODE_SINK || k == HS_NODE_LINK || k == HS_NODE_ROUTER || k == HS_NODE_LB || k == HS_NODE_RATE_LIMITER || k == HS_NODE_BULKHEAD || k == HS_NODE_TIMEOUT_WRAPPER || k == HS_NODE_CLIENT || k == HS_NODE_BATCH_PROCESSOR || k == HS_NODE_CONVEYOR || k == HS_NODE_GATE || k == HS_NODE_HEDGE || k == HS_NODE_FALLBACK || k == HS_NODE_POOLED_CYCLE || k == HS_NODE_INVENTORY; };
     int64_t kmax = 0;                                  // client ids any Source hands out: [0, kmax)
     for (int i = 0; i < n; ++i)
         if (nd->kind[i] == HS_NODE_SOURCE && nd->src_n_clients && nd->src_n_clients[i] > kmax) kmax = nd->src_n_clients[i];
@@ -2852,6 +2951,8 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
                             : p.sub == HS_PROBE_TW_IN_FLIGHT ? tk == HS_NODE_TIMEOUT_WRAPPER
                             : p.sub == HS_PROBE_CL_IN_FLIGHT ? tk == HS_NODE_CLIENT
                             : p.sub == HS_PROBE_HG_IN_FLIGHT ? tk == HS_NODE_HEDGE
+                            : (p.sub >= HS_PROBE_PC_AVAILABLE && p.sub <= HS_PROBE_PC_QUEUED) ? tk == HS_NODE_POOLED_CYCLE
+                            : p.sub == HS_PROBE_IB_STOCK ? tk == HS_NODE_INVENTORY
                             : p.sub == HS_PROBE_BP_BUFFER_DEPTH ? tk == HS_NODE_BATCH_PROCESSOR
                             : p.sub == HS_PROBE_CV_IN_TRANSIT ? tk == HS_NODE_CONVEYOR
                             : p.sub == HS_PROBE_GT_QUEUE_DEPTH ? tk == HS_NODE_GATE
@@ -2978,6 +3079,9 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             if (t >= 0 && (nd->kind[t] == HS_NODE_HEDGE || nd->kind[t] == HS_NODE_FALLBACK))
                 return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the target of a %s is (through %s) node %d, a Hedge or a Fallback: "
                             "two completion hooks on one Event are not lowered", i, nm, t == p.target ? "no link" : "its links", t);
+            if (t >= 0 && (nd->kind[t] == HS_NODE_POOLED_CYCLE || nd->kind[t] == HS_NODE_INVENTORY))
+                return fail(nullptr, HS_E_UNSUPPORTED, "node %d: the target of a %s is (through %s) node %d, %s", i, nm,
+                            t == p.target ? "no link" : "its links", t, hook_refused(nd->kind[t]));
             p.conc = 1; p.lim = 0; p.sub = 0; p.rt_off = 0; p.rt_cnt = 0;
         } break;
         case HS_NODE_HEDGE:
@@ -2999,6 +3103,13 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
             // BatchProcessor / ConveyorBelt / GateController (components/industrial/): the parameters come with hs_graph_set_flow
             if (p.target < 0) return fail(nullptr, HS_E_INVALID, "node %d: a BatchProcessor, ConveyorBelt or GateController needs a downstream", i);
             p.conc = 0; p.lim = 0; p.sub = 0; p.stream_base = 0; p.rt_off = 0; p.rt_cnt = 0;
+        } break;
+        case HS_NODE_POOLED_CYCLE:
+        case HS_NODE_INVENTORY: {
+            // PooledCycleResource / InventoryBuffer (components/industrial/pooled_cycle.py, inventory.py): a downstream is optional;
+            // the parameters come with hs_graph_set_pool / hs_graph_set_inventory
+            if (p.target >= 0 && !takes_requests(p.target)) return fail(nullptr, HS_E_INVALID, "node %d: its downstream %d takes no Requests", i, p.target);
+            p.conc = p.kind == HS_NODE_POOLED_CYCLE ? 1 : -1; p.lim = 0; p.sub = 0; p.mean = 0.0; p.stream_base = 0; p.rt_off = 0; p.rt_cnt = 0;
         } break;
         case HS_NODE_AUTO_SCALER: {
             // AutoScaler (auto_scaler.py:207-263); its LoadBalancer, policy and parameters: hs_graph_set_auto_scaler
@@ -3040,6 +3151,7 @@ int hs_graph_create(const hs_graph_config *cfg, const hs_graph_nodes *nd, hs_gra
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_BULKHEAD || P[(size_t)i].kind == HS_NODE_TIMEOUT_WRAPPER) g->n_wrappers++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_CLIENT) g->n_clients++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_HEDGE || P[(size_t)i].kind == HS_NODE_FALLBACK) g->n_hedges++;
+        for (int i = 0; i < n; ++i) if (P[(size_t)i].kind == HS_NODE_POOLED_CYCLE || P[(size_t)i].kind == HS_NODE_INVENTORY) g->n_stock++;
         for (int i = 0; i < n; ++i) if (P[(size_t)i].kind >= HS_NODE_BATCH_PROCESSOR && P[(size_t)i].kind <= HS_NODE_GATE) g->n_flows++;
         g->wrapper_set.assign((size_t)n, 0); g->tab_cap.assign((size_t)n, 0);
     }
@@ -3732,6 +3844,96 @@ int hs_graph_get_flow(hs_graph *g, int32_t node, int64_t *counters, int64_t *eve
     default: counters[0] = s.a; counters[1] = s.b; counters[2] = s.c; counters[3] = s.d; counters[4] = s.qlen; counters[5] = s.active; break;
     }
     return HS_OK;
+}
+
+int hs_graph_set_pool(hs_graph *g, int32_t node, int32_t pool_size, int64_t cycle_ns, int32_t queue_capacity) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_POOLED_CYCLE) return fail(g, HS_E_INVALID, "set_pool: node %d is not a PooledCycleResource", node);
+    if (g->ran || g->launches > 0) return fail(g, HS_E_STATE, "set_pool: a node is configured before the first run");
+    if (g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "set_pool: node %d is configured already", node);
+    if (pool_size <= 0) return fail(g, HS_E_INVALID, "pool_size must be > 0, got %d", pool_size);                                // pooled_cycle.py:61-62
+    if (cycle_ns < 0) return fail(g, HS_E_INVALID, "cycle_time must be >= 0, got %g", (double)cycle_ns / 1e9);                   // :63-64
+    if (cycle_ns > (1ll << 61)) return fail(g, HS_E_INVALID, "set_pool: a cycle_time beyond 2^61 ns");
+    if (pool_size > HS_POOL_MAX_UNITS) return fail(g, HS_E_UNSUPPORTED, "PooledCycleResource: pool_size = %d is beyond %d units", pool_size, HS_POOL_MAX_UNITS);
+    if (queue_capacity > HS_POOL_MAX_UNITS)
+        return fail(g, HS_E_UNSUPPORTED, "PooledCycleResource: queue_capacity = %d is beyond %d items (0: unbounded)", queue_capacity, HS_POOL_MAX_UNITS);
+    GParam &p = g->params[(size_t)node];
+    p.conc = pool_size; p.lim = cycle_ns; p.rt_cnt = queue_capacity > 0 ? queue_capacity : 0; p.rt_off = 0; p.sub = 0;
+    GState s0{};
+    s0.qhead = -1; s0.qtail = -1;
+    g->reach_s = std::max(g->reach_s, (double)cycle_ns / 1e9);
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    HS_HIP(g, hipMemcpy(g->ctl.S + node, &s0, sizeof s0, hipMemcpyHostToDevice));
+    g->wrapper_set[(size_t)node] = 1;
+    return HS_OK;
+}
+
+int hs_graph_set_inventory(hs_graph *g, int32_t node, int64_t initial_stock, int64_t reorder_point, int64_t order_quantity, double lead_time_s,
+                           int32_t stockout_node) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != HS_NODE_INVENTORY) return fail(g, HS_E_INVALID, "set_inventory: node %d is not an InventoryBuffer", node);
+    if (g->ran || g->launches > 0) return fail(g, HS_E_STATE, "set_inventory: a node is configured before the first run");
+    if (g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "set_inventory: node %d is configured already", node);
+    if (initial_stock < 0) return fail(g, HS_E_INVALID, "initial_stock must be >= 0, got %lld", (long long)initial_stock);       // inventory.py:73-78
+    if (reorder_point < 0) return fail(g, HS_E_INVALID, "reorder_point must be >= 0, got %lld", (long long)reorder_point);
+    if (order_quantity <= 0) return fail(g, HS_E_INVALID, "order_quantity must be > 0, got %lld", (long long)order_quantity);
+    if (initial_stock > HS_INVENTORY_MAX || reorder_point > HS_INVENTORY_MAX || order_quantity > HS_INVENTORY_MAX)
+        return fail(g, HS_E_UNSUPPORTED, "InventoryBuffer: a stock parameter beyond 2^62 is not lowered");
+    if (reorder_point + order_quantity > HS_INVENTORY_MAX_LEVEL)       // (each <= 2^62: the sum itself cannot wrap)
+        return fail(g, HS_E_UNSUPPORTED, "InventoryBuffer: reorder_point + order_quantity = %llu is beyond 2^63 - 2^48, the level a 64-bit stock holds",
+                    (unsigned long long)reorder_point + (unsigned long long)order_quantity);
+    if (!(lead_time_s >= 0.0) || !std::isfinite(lead_time_s) || lead_time_s > 2.0e9)
+        return fail(g, HS_E_UNSUPPORTED, "InventoryBuffer: lead_time = %g is not a finite number in [0, 2e9] s", lead_time_s);
+    if (stockout_node < -1 || stockout_node >= g->n) return fail(g, HS_E_INVALID, "set_inventory: stock-out node %d out of range", stockout_node);
+    if (stockout_node >= 0) {
+        const int k = g->params[(size_t)stockout_node].kind;
+        if (k == HS_NODE_SOURCE || k == HS_NODE_PROBE || k == HS_NODE_HEALTH_CHECKER || k == HS_NODE_AUTO_SCALER || k == HS_NODE_ROLLING_DEPLOYER || k == HS_NODE_CANARY_DEPLOYER)
+            return fail(g, HS_E_INVALID, "node %d: its stockout_target %d takes no Requests", node, stockout_node);
+    }
+    GParam &p = g->params[(size_t)node];
+    p.lim = reorder_point; p.stream_base = (uint64_t)order_quantity; p.mean = lead_time_s; p.conc = stockout_node; p.sub = 0; p.rt_off = 0; p.rt_cnt = 0;
+    GState s0{};
+    s0.qhead = -1; s0.qtail = -1;
+    s0.a = initial_stock;
+    g->reach_s = std::max(g->reach_s, lead_time_s);
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    HS_HIP(g, hipMemcpy(const_cast<GParam *>(g->ctl.P) + node, &p, sizeof p, hipMemcpyHostToDevice));
+    HS_HIP(g, hipMemcpy(g->ctl.S + node, &s0, sizeof s0, hipMemcpyHostToDevice));
+    g->wrapper_set[(size_t)node] = 1;
+    return HS_OK;
+}
+
+// hs_graph_get_pool / hs_graph_get_inventory
+static int get_stock_common(hs_graph *g, int32_t node, int kind, const char *what, int64_t *counters, int64_t *events) {
+    if (!g) return fail(g, HS_E_INVALID, "null handle");
+    HS_HIP(g, hipSetDevice(g->cfg.device));
+    if (events) {
+        GVars v;
+        HS_HIP(g, hipMemcpy(&v, g->ctl.V, sizeof v, hipMemcpyDeviceToHost));
+        for (int k = 0; k < HS_STOCK_KINDS; ++k) events[k] = v.st_by_kind[k];
+    }
+    if (node == -1 && !counters) return HS_OK;
+    if (node < 0 || node >= g->n || g->params[(size_t)node].kind != kind)
+        return fail(g, HS_E_INVALID, "%s: node %d is not %s", what, node, kind == HS_NODE_POOLED_CYCLE ? "a PooledCycleResource" : "an InventoryBuffer");
+    if (!g->wrapper_set[(size_t)node]) return fail(g, HS_E_STATE, "%s: node %d was never configured", what, node);
+    if (!counters) return HS_OK;
+    GState s{};
+    HS_HIP(g, hipMemcpy(&s, g->ctl.S + node, sizeof s, hipMemcpyDeviceToHost));
+    if (kind == HS_NODE_POOLED_CYCLE) {
+        counters[0] = (int64_t)g->params[(size_t)node].conc - s.active; counters[1] = s.active; counters[2] = s.qlen; counters[3] = s.a; counters[4] = s.b;
+    } else {
+        counters[0] = s.a; counters[1] = s.b; counters[2] = s.c; counters[3] = s.d; counters[4] = (int64_t)s.svc_draws; counters[5] = s.active;
+    }
+    return HS_OK;
+}
+
+int hs_graph_get_pool(hs_graph *g, int32_t node, int64_t *counters, int64_t *events) {
+    return get_stock_common(g, node, HS_NODE_POOLED_CYCLE, "get_pool", counters, events);
+}
+
+int hs_graph_get_inventory(hs_graph *g, int32_t node, int64_t *counters, int64_t *events) {
+    return get_stock_common(g, node, HS_NODE_INVENTORY, "get_inventory", counters, events);
 }
 
 int hs_graph_set_queue_policy(hs_graph *g, int32_t node, int32_t policy, int64_t capacity, int64_t threshold, double target_s, double interval_s) {
@@ -4489,6 +4691,12 @@ static int prepare_run(hs_graph *g, int64_t end_ns) {
         HS_HIP(g, hipMemcpy(g->d_qp, g->qpol.data(), g->qpol.size() * sizeof(GQueue), hipMemcpyHostToDevice));
         HS_HIP(g, hipMemcpy(reinterpret_cast<char *>(c.V) + offsetof(GVars, qp), &g->d_qp, sizeof g->d_qp, hipMemcpyHostToDevice));
     }
+    if (g->n_stock > 0)
+        for (int i = 0; i < g->n; ++i) {
+            const uint8_t k = g->params[(size_t)i].kind;
+            if ((k == HS_NODE_POOLED_CYCLE || k == HS_NODE_INVENTORY) && !g->wrapper_set[(size_t)i])
+                return fail(g, HS_E_STATE, "node %d: a PooledCycleResource / InventoryBuffer without its parameters (hs_graph_set_pool / hs_graph_set_inventory comes before the run)", i);
+        }
     if (g->n_flows > 0)
         for (int i = 0; i < g->n; ++i) {
             const uint8_t k = g->params[(size_t)i].kind;

@@ -2221,6 +2221,144 @@ class GateController(Entity):
         return []
 
 
+# ---- pools and stock -----------------------------------------------------------------------------
+# components/industrial/pooled_cycle.py, inventory.py: a pool of units with a fixed cycle and a waiting line, and an (s, Q) stock
+# counter with lead-time replenishment.  Both are deterministic; their handlers run on the device (csrc/hs_graph.hip kEvPcItem ..
+# kEvIbReplenish, the last four of the 64 kinds the loop's kind word holds).  Not mirrored from that package: PerishableInventory (its
+# spoilage sweep is a daemon chain over a list of batches), PreemptibleResource (callbacks and SimFuture grants), AppointmentScheduler
+# (it draws no-shows from the process-wide `random`, and would need a 65th kind).
+@dataclass(frozen=True)
+class PooledCycleStats:
+    """pooled_cycle.py:24-34."""
+
+    pool_size: int = 0
+    available: int = 0
+    active: int = 0
+    queued: int = 0
+    completed: int = 0
+    rejected: int = 0
+    utilization: float = 0.0
+
+
+class PooledCycleResource(Entity):
+    """`pool_size` identical units; a Request that finds one free holds it for `cycle_time` seconds and then goes on to `downstream`
+    (None: it ends there), one that finds none waits in a line -- unbounded with `queue_capacity = 0`, otherwise a Request that finds
+    the line full is rejected (pooled_cycle.py:37-179).  A unit that comes free sends the head of the line to the pool again as a new
+    Event of the same nanosecond: an arrival of that nanosecond that sorts ahead of it takes the unit, and the waiting Request queues
+    again at the back."""
+
+    MAX_POOL_SIZE = 1 << 20                   # include/hs_engine.h HS_POOL_MAX_UNITS (pool_size, and a bounded queue_capacity)
+
+    def __init__(self, name: str, pool_size: int, cycle_time: float, downstream: Entity | None = None, queue_capacity: int = 0):
+        if pool_size <= 0:                                                                # pooled_cycle.py:61-64
+            raise ValueError(f"pool_size must be > 0, got {pool_size}")
+        if cycle_time < 0:
+            raise ValueError(f"cycle_time must be >= 0, got {cycle_time}")
+        super().__init__(name)
+        self.pool_size = pool_size
+        self.cycle_time = cycle_time
+        self.downstream = downstream
+        self._queue_capacity = queue_capacity
+        self._available = pool_size
+        self._active = 0
+        self._queue: list = []                # after a run: one placeholder per waiting Request (the Requests live on the device)
+        self._completed = 0
+        self._rejected = 0
+
+    def downstream_entities(self) -> list[Entity]:
+        return [self.downstream] if self.downstream is not None else []
+
+    @property
+    def available(self) -> int:
+        return self._available
+
+    @property
+    def active(self) -> int:
+        return self._active
+
+    @property
+    def queued(self) -> int:
+        return len(self._queue)
+
+    @property
+    def completed(self) -> int:
+        return self._completed
+
+    @property
+    def rejected(self) -> int:
+        return self._rejected
+
+    @property
+    def utilization(self) -> float:
+        return 0.0 if self.pool_size == 0 else self._active / self.pool_size
+
+    @property
+    def stats(self) -> PooledCycleStats:
+        return PooledCycleStats(pool_size=self.pool_size, available=self._available, active=self._active, queued=len(self._queue),
+                                completed=self._completed, rejected=self._rejected, utilization=self.utilization)
+
+
+@dataclass(frozen=True)
+class InventoryStats:
+    """inventory.py:21-37."""
+
+    current_stock: int = 0
+    stockouts: int = 0
+    reorders: int = 0
+    items_consumed: int = 0
+    items_replenished: int = 0
+
+    @property
+    def fill_rate(self) -> float:
+        """The share of the demand that was met from stock (1.0 without any demand)."""
+        total = self.items_consumed + self.stockouts
+        return 1.0 if total == 0 else self.items_consumed / total
+
+
+class InventoryBuffer(Entity):
+    """A stock counter under an (s, Q) policy: every Request consumes one item and goes on to `downstream`; a Request that finds the
+    stock empty counts as a stock-out and goes to `stockout_target`.  Once the stock is at or below `reorder_point` and no order is
+    pending, `order_quantity` items are ordered and arrive `lead_time` seconds later (inventory.py:40-194).  `supplier` is kept and
+    listed among `downstream_entities()`; nothing is ever sent to it, as in the reference.  Stock and counters are 64-bit."""
+
+    MAX_STOCK = 1 << 62                       # include/hs_engine.h HS_INVENTORY_MAX (initial_stock, reorder_point, order_quantity)
+    MAX_LEVEL = (1 << 63) - (1 << 48)         # HS_INVENTORY_MAX_LEVEL: reorder_point + order_quantity, the level the stock can reach
+
+    def __init__(self, name: str, initial_stock: int = 100, reorder_point: int = 20, order_quantity: int = 50, lead_time: float = 5.0,
+                 supplier: Entity | None = None, downstream: Entity | None = None, stockout_target: Entity | None = None):
+        if initial_stock < 0:                                                             # inventory.py:73-78
+            raise ValueError(f"initial_stock must be >= 0, got {initial_stock}")
+        if reorder_point < 0:
+            raise ValueError(f"reorder_point must be >= 0, got {reorder_point}")
+        if order_quantity <= 0:
+            raise ValueError(f"order_quantity must be > 0, got {order_quantity}")
+        super().__init__(name)
+        self._stock = initial_stock
+        self.reorder_point = reorder_point
+        self.order_quantity = order_quantity
+        self.lead_time = lead_time
+        self.supplier = supplier
+        self.downstream = downstream
+        self.stockout_target = stockout_target
+        self._stockouts = 0
+        self._reorders = 0
+        self._items_consumed = 0
+        self._items_replenished = 0
+        self._order_pending = False
+
+    def downstream_entities(self) -> list[Entity]:
+        return [x for x in (self.downstream, self.supplier, self.stockout_target) if x is not None]
+
+    @property
+    def stock(self) -> int:
+        return self._stock
+
+    @property
+    def stats(self) -> InventoryStats:
+        return InventoryStats(current_stock=self._stock, stockouts=self._stockouts, reorders=self._reorders,
+                              items_consumed=self._items_consumed, items_replenished=self._items_replenished)
+
+
 # ---- auto scaling --------------------------------------------------------------------------------
 # components/deployment/auto_scaler.py.  Inside a Simulation the policies are evaluated on the device (csrc/hs_graph.hip kEvAsEval);
 # `evaluate` here is the reference's expression over host objects, for a policy used on its own.
@@ -2717,13 +2855,16 @@ class Probe(Entity):
     every `interval` seconds into a Data container.  Lowered metrics: Server.depth / active_requests / utilization / available_capacity / has_capacity /
     stats_accepted / stats_dropped / requests completed, Sink.events_received, Source.generated_count, RateLimitedEntity.queue_depth,
     Bulkhead.active_count / queue_depth / available_permits, TimeoutWrapper.in_flight_count, Client.in_flight_count,
-    BatchProcessor.buffer_depth, ConveyorBelt.items_in_transit, GateController.queue_depth."""
+    BatchProcessor.buffer_depth, ConveyorBelt.items_in_transit, GateController.queue_depth, PooledCycleResource.available / active /
+    queued, InventoryBuffer.stock."""
 
     _LOWERED = {"depth", "active_requests", "utilization", "available_capacity", "has_capacity", "stats_accepted", "stats_dropped",
                 "requests_completed", "_requests_completed", "events_received", "generated_count", "_generated_count", "queue_depth",
-                "active_count", "available_permits", "in_flight_count", "buffer_depth", "items_in_transit", "current_count"}
+                "active_count", "available_permits", "in_flight_count", "buffer_depth", "items_in_transit", "current_count",
+                "available", "active", "queued", "stock"}
     _ON_WRAPPER = {"active_count": Bulkhead, "available_permits": Bulkhead, "in_flight_count": (TimeoutWrapper, Client, Hedge),
-                   "buffer_depth": BatchProcessor, "items_in_transit": ConveyorBelt, "current_count": AutoScaler}
+                   "buffer_depth": BatchProcessor, "items_in_transit": ConveyorBelt, "current_count": AutoScaler,
+                   "available": PooledCycleResource, "active": PooledCycleResource, "queued": PooledCycleResource, "stock": InventoryBuffer}
     # Server attributes that are functions of `active_requests` and the (fixed) concurrency: the engine samples the integer,
     # the Data container applies the reference's expression (components/server/server.py:153-173,191-200, concurrency.py:117-131)
     _ON_ACTIVE = ("utilization", "available_capacity", "has_capacity")

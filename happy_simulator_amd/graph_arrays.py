@@ -107,6 +107,18 @@ class GraphArrays:
     def hg_params(self, value):
         self._hg_params = value
 
+    @property
+    def st_params(self):
+        """[n, 5] int64 (None: neither a pool nor a buffer; kept out of vars() like `rd_params`): POOLED_CYCLE nodes -- pool_size,
+        cycle_time in ns, queue_capacity (0: unbounded), 0, -1; INVENTORY nodes -- initial_stock, reorder_point, order_quantity, the
+        bits of lead_time (binary64 seconds), the node of the stockout_target (-1: none -- the node's second outgoing edge; the
+        downstream: `target`); set through hs_graph_set_pool / hs_graph_set_inventory."""
+        return getattr(self, "_st_params", None)
+
+    @st_params.setter
+    def st_params(self, value):
+        self._st_params = value
+
     # the families a graph has nodes of: what GraphEngine applies and reads, what the run's results hold
     has_deployers = property(lambda self: self._rd_params is not None)
     has_canaries = property(lambda self: self.cn_params is not None)
@@ -117,6 +129,7 @@ class GraphArrays:
     has_health = property(lambda self: self.hc_params is not None or self.lb_healthy is not None)
     has_wrappers = property(lambda self: self.wrap_params is not None)
     has_hedges = property(lambda self: self.hg_params is not None)
+    has_stock = property(lambda self: self.st_params is not None)
 
     def struct(self) -> N.GraphNodes:
         s = N.GraphNodes()
@@ -140,7 +153,7 @@ class GraphArrays:
 _PER_NODE = ("kind", "stream_base", "src_kind", "src_rate", "src_stop_after_ns", "concurrency", "lat_kind", "lat_mean_s", "link_lat_min_s",
              "link_loss_rate", "queue_cap", "src_profile_kind", "src_profile_params", "probe_metric", "probe_interval_s", "lb_strategy",
              "lb_vnodes", "src_n_clients", "lim_policy", "lim_params", "lim_count", "hc_params", "wrap_params", "cl_params", "flow_params",
-             "qp_params", "as_params", "rd_params", "hg_params")
+             "qp_params", "as_params", "rd_params", "hg_params", "st_params")
 
 # (a family's array, which of a part's nodes are of that family): a part without one drops the array and runs the loop it would run
 # alone (without a checker: no health state unless a flag says so, below)
@@ -151,7 +164,8 @@ _FAMILY_OF = (("hc_params", lambda b: b.kind == N.NODE_HEALTH_CHECKER),
               ("qp_params", lambda b: b.qp_params[:, 0] != N.QUEUE_FIFO),
               ("as_params", lambda b: b.kind == N.NODE_AUTO_SCALER),
               ("cl_params", lambda b: b.kind == N.NODE_CLIENT),
-              ("hg_params", lambda b: (b.kind == N.NODE_HEDGE) | (b.kind == N.NODE_FALLBACK)))
+              ("hg_params", lambda b: (b.kind == N.NODE_HEDGE) | (b.kind == N.NODE_FALLBACK)),
+              ("st_params", lambda b: (b.kind == N.NODE_POOLED_CYCLE) | (b.kind == N.NODE_INVENTORY)))
 
 
 def _offsets(blobs, dtype) -> np.ndarray:
@@ -179,6 +193,9 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
     if a.hg_params is not None:                        # a Fallback's second edge: its fallback entity
         fb = np.nonzero(a.kind == N.NODE_FALLBACK)[0]
         src, dst = np.concatenate([src, fb]), np.concatenate([dst, a.hg_params[fb, 2]])
+    if a.st_params is not None:                        # an InventoryBuffer's second edge: its stockout_target
+        ib = np.nonzero((a.kind == N.NODE_INVENTORY) & (a.st_params[:, 4] >= 0))[0]
+        src, dst = np.concatenate([src, ib]), np.concatenate([dst, a.st_params[ib, 4]])
     n_comp, label = connected_components(coo_matrix((np.ones(len(src), np.int8), (src, dst)), shape=(n, n)), directed=False)
     if n_comp < 2:
         return None
@@ -222,6 +239,9 @@ def split_parts(a: GraphArrays, max_parts: int = MAX_PARTS):
         if b.hg_params is not None:
             fb = b.kind == N.NODE_FALLBACK
             b.hg_params[fb, 2] = new_index[b.hg_params[fb, 2]]
+        if b.st_params is not None:
+            ib = (b.kind == N.NODE_INVENTORY) & (b.st_params[:, 4] >= 0)
+            b.st_params[ib, 4] = new_index[b.st_params[ib, 4]]
         for nm, of_family in _FAMILY_OF:
             if getattr(b, nm) is not None and not of_family(b).any():
                 setattr(b, nm, None)

@@ -126,6 +126,15 @@ class GraphEngine:
             else:
                 self._check(self._lib.hs_graph_set_fallback(self._h, int(i), fallback, delay_ns, self._table_capacity or cap))
 
+    def _apply_stock(self, a: GraphArrays) -> None:
+        for i in np.nonzero((a.kind == N.NODE_POOLED_CYCLE) | (a.kind == N.NODE_INVENTORY))[0]:
+            row = a.st_params[i]
+            if a.kind[i] == N.NODE_POOLED_CYCLE:
+                self._check(self._lib.hs_graph_set_pool(self._h, int(i), int(row[0]), int(row[1]), int(row[2])))
+            else:
+                self._check(self._lib.hs_graph_set_inventory(self._h, int(i), int(row[0]), int(row[1]), int(row[2]),
+                                                             float(row[3:4].view(np.float64)[0]), int(row[4])))
+
     def _apply_clients(self, a: GraphArrays) -> None:
         for i in np.nonzero(a.kind == N.NODE_CLIENT)[0]:
             timeout, cap = a.cl_params[i]
@@ -147,7 +156,7 @@ class GraphEngine:
     # before its scaler ...
     _APPLY = ((None, _apply_lb_weights), (None, _apply_limiters), ("has_health", _apply_health), ("has_scalers", _apply_scalers),
               ("has_deployers", _apply_rolling_deployers), ("has_canaries", _apply_canary_deployers), ("has_wrappers", _apply_wrappers),
-              ("has_hedges", _apply_hedges), ("has_clients", _apply_clients), ("has_flows", _apply_flows), ("has_queue_policies", _apply_queue_policies))
+              ("has_hedges", _apply_hedges), ("has_stock", _apply_stock), ("has_clients", _apply_clients), ("has_flows", _apply_flows), ("has_queue_policies", _apply_queue_policies))
 
     _QUEUE_NAMES = ("policy", "len", "enqueued", "dequeued_fifo", "dequeued_lifo", "dropped", "capacity_rejected", "switches", "flag",
                     "count", "last_count", "has_first_above", "first_above_ns", "has_drop_next", "drop_next_ns")
@@ -224,6 +233,23 @@ class GraphEngine:
         Events of the run."""
         events = np.zeros(N.HEDGE_KINDS, np.int64)
         self._check(self._lib.hs_graph_get_hedge(self._h, -1, None, None, 0, _ptr(events)))
+        return events
+
+    _POOL_NAMES = ("available", "active", "queued", "completed", "rejected")
+    _INVENTORY_NAMES = ("stock", "stockouts", "reorders", "items_consumed", "items_replenished", "order_pending")
+
+    def stock(self, node: int) -> dict:
+        """hs_graph_get_pool / hs_graph_get_inventory of a PooledCycleResource or InventoryBuffer node: its counters by name."""
+        pool = self.arrays.kind[node] == N.NODE_POOLED_CYCLE
+        get, names = (self._lib.hs_graph_get_pool, self._POOL_NAMES) if pool else (self._lib.hs_graph_get_inventory, self._INVENTORY_NAMES)
+        c = np.zeros(len(names), np.int64)
+        self._check(get(self._h, int(node), _ptr(c), None))
+        return {k: int(v) for k, v in zip(names, c)}
+
+    def stock_events(self) -> np.ndarray:
+        """The graph's pool Request / cycle end / consume Request / replenish Events of the run."""
+        events = np.zeros(N.STOCK_KINDS, np.int64)
+        self._check(self._lib.hs_graph_get_pool(self._h, -1, None, _ptr(events)))
         return events
 
     def wrapper(self, node: int) -> dict:
@@ -600,6 +626,7 @@ class PartRun:
 
     queue_policy, flow, client, wrapper = _of_node("queue_policy"), _of_node("flow"), _of_node("client"), _of_node("wrapper")
     hedge, hedge_events = _of_node("hedge"), _summed("hedge_events", _int64)
+    stock, stock_events = _of_node("stock"), _summed("stock_events", _int64)
     canary, deployer, scaler, health = _of_node("canary"), _of_node("deployer"), _of_node("scaler"), _of_node("health")
     health_events, wrapper_events = _summed("health_events", _int64), _summed("wrapper_events", _int64)
     client_events, flow_events = _summed("client_events", _int64), _summed("flow_events", _int64)

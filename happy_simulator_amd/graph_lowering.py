@@ -18,8 +18,9 @@ from .core.temporal import Duration
 from .entities import (LIMITER_POLICIES, METRIC_EVALUATORS, QUEUE_POLICIES, SCALING_POLICIES, AdaptiveLIFO, AutoScaler, BatchProcessor,
                        Bulkhead, CanaryDeployer, Client, ClientKeyEventProvider, CoDelQueue, ConsistentHash, ConstantLatency,
                        ConstantRateProfile, ConveyorBelt, Counter, DecorrelatedJitter, Entity, ExponentialBackoff, ExponentialLatency,
-                       Fallback, FIFOQueue, FixedRetry, GateController, HealthChecker, Hedge, IPHash, LatencyEvaluator, LatencyTracker, LeastConnections,
-                       LinearRampProfile, LoadBalancer, Network, NetworkLink, NoRetry, Probe, Random, RandomRouter, RateLimitedEntity,
+                       Fallback, FIFOQueue, FixedRetry, GateController, HealthChecker, Hedge, InventoryBuffer, IPHash, LatencyEvaluator, LatencyTracker,
+                       LeastConnections, LinearRampProfile, LoadBalancer, Network, NetworkLink, NoRetry, PooledCycleResource, Probe, Random, RandomRouter,
+                       RateLimitedEntity,
                        RollingDeployer, RoundRobin, Server, SimpleEventProvider, Sink, SlidingWindowPolicy, Source, StepScaling,
                        TargetUtilization, TimeoutWrapper, TokenBucketPolicy, WeightedLeastConnections, WeightedRoundRobin)
 from .graph_arrays import GraphArrays, _offsets
@@ -32,10 +33,12 @@ _STRATEGY_CODE = ((ConsistentHash, N.LB_CONSISTENT_HASH), (RoundRobin, N.LB_ROUN
 
 _SINKS = (Sink, Counter, LatencyTracker)
 _FLOWS = (BatchProcessor, ConveyorBelt, GateController)
+_STOCK = (PooledCycleResource, InventoryBuffer)
 _DEPLOYERS = (RollingDeployer, CanaryDeployer)
 _FLOW_METRIC_OF = {"buffer_depth": BatchProcessor, "items_in_transit": ConveyorBelt, "queue_depth": GateController}
+_STOCK_METRIC_OF = {"available": PooledCycleResource, "active": PooledCycleResource, "queued": PooledCycleResource, "stock": InventoryBuffer}
 _LOWERED = (Server, NetworkLink, RandomRouter, LoadBalancer, RateLimitedEntity, HealthChecker, Bulkhead, TimeoutWrapper, Client,
-            BatchProcessor, ConveyorBelt, GateController, AutoScaler, RollingDeployer, CanaryDeployer, Hedge, Fallback) + _SINKS
+            BatchProcessor, ConveyorBelt, GateController, AutoScaler, RollingDeployer, CanaryDeployer, Hedge, Fallback) + _STOCK + _SINKS
 _FIXED_LIST = (ConsistentHash, IPHash, Random)            # strategies whose selection over a changing backend list is not lowered
 
 
@@ -413,6 +416,8 @@ def _lower_probe(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
         codes = N.PROBE_HEDGE_METRICS
     elif isinstance(tgt, _FLOW_METRIC_OF.get(m, ())):
         codes = N.PROBE_FLOW_METRICS
+    elif isinstance(tgt, _STOCK_METRIC_OF.get(m, ())):
+        codes = N.PROBE_STOCK_METRICS
     else:
         if m not in N.PROBE_METRICS and not on_wrapper and not on_client:
             raise UnsupportedTopology(f"probe '{ent.name}': metric '{ent.metric}' is not sampled on the engine")
@@ -597,6 +602,9 @@ def _hook_target(cx: _Lowering, what: str, ent, tgt=None, role: str = "target") 
     if isinstance(end, (Hedge, Fallback)) or (isinstance(ent, (Hedge, Fallback)) and isinstance(end, (LoadBalancer, Bulkhead, TimeoutWrapper, Client))):
         raise UnsupportedTopology(f"{what}: its {role}{via} is the {type(end).__name__} '{end.name}' -- two completion hooks on one Event "
                                   "are not lowered (a follow-up)")
+    if isinstance(end, _STOCK):
+        raise UnsupportedTopology(f"{what}: its {role}{via} is the {type(end).__name__} '{end.name}' -- a completion hook on an item that "
+                                  "a PooledCycleResource or an InventoryBuffer holds or forwards is not lowered (a follow-up)")
     if isinstance(end, _FLOWS) and isinstance(ent, (Hedge, Fallback)):
         raise UnsupportedTopology(f"{what}: its {role}{via} is the {type(end).__name__} '{end.name}' -- a completion hook on an item that "
                                   "a BatchProcessor, ConveyorBelt or GateController holds is not lowered (a follow-up)")
@@ -718,6 +726,61 @@ def _lower_flow(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
         params[i] = (max(int(cap), 0), 0, int(ent._open_cycles), 1 if ent._is_open else 0)
 
 
+def _stock_int(what: str, name: str, value, least: int, most: int, limit: str) -> int:
+    """An integer parameter of a pool or a buffer within [least, most], or the refusal that names it."""
+    if type(value) is not int:
+        raise UnsupportedTopology(f"{what}: {name} must be an int, got {value!r}")
+    if not least <= value <= most:
+        raise UnsupportedTopology(f"{what}: {name} = {value} is beyond {limit}")
+    return value
+
+
+def _stock_seconds(what: str, name: str, value) -> float:
+    try:
+        ok = bool(np.isfinite(value)) and value >= 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise UnsupportedTopology(f"{what}: {name} = {value!r} is not a finite number >= 0")
+    return float(value)
+
+
+def _lower_stock(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
+    what = f"{type(ent).__name__} '{ent.name}'"
+    # (a buffer's `supplier` is a node like any entity of downstream_entities(), but nothing is ever sent to it)
+    for role, d in (("downstream", ent.downstream), ("stockout_target", getattr(ent, "stockout_target", None))):
+        if d is not None and _takes_no_requests(cx, d):
+            raise UnsupportedTopology(f"{what}: its {role} {type(d).__name__} '{getattr(d, 'name', d)}' takes no Requests")
+    params = _ensure(a, "st_params", lambda: np.zeros((a.n, 5), np.int64))
+    a.target[i] = -1 if ent.downstream is None else cx.node_of[id(ent.downstream)]
+    if isinstance(ent, PooledCycleResource):
+        units = f"the {PooledCycleResource.MAX_POOL_SIZE} the engine holds (PooledCycleResource.MAX_POOL_SIZE)"
+        size = _stock_int(what, "pool_size", ent.pool_size, 1, PooledCycleResource.MAX_POOL_SIZE, units)
+        cap = _stock_int(what, "queue_capacity", ent._queue_capacity, -(1 << 62), PooledCycleResource.MAX_POOL_SIZE, units + "; 0 is unbounded")
+        if len(ent._queue) or ent._active:
+            raise UnsupportedTopology(f"{what}: {len(ent._queue)} Requests wait and {ent._active} cycles run from an earlier run (not lowered)")
+        a.kind[i] = N.NODE_POOLED_CYCLE
+        # the generator's `yield cycle_time` is the number added to an Instant: int(cycle_time * 1e9) nanoseconds whatever `now` is
+        params[i] = (size, flow_delay_ns(_stock_seconds(what, "cycle_time", ent.cycle_time), what, "cycle_time"), max(cap, 0), 0, -1)
+    else:
+        limit = "2^62 (InventoryBuffer.MAX_STOCK)"
+        stock = _stock_int(what, "initial_stock", ent._stock, 0, InventoryBuffer.MAX_STOCK, limit)
+        point = _stock_int(what, "reorder_point", ent.reorder_point, 0, InventoryBuffer.MAX_STOCK, limit)
+        order = _stock_int(what, "order_quantity", ent.order_quantity, 1, InventoryBuffer.MAX_STOCK, limit)
+        if point + order > InventoryBuffer.MAX_LEVEL:
+            # the stock never passes max(initial_stock, reorder_point + order_quantity): beyond this a 64-bit counter would wrap
+            raise UnsupportedTopology(f"{what}: reorder_point + order_quantity = {point + order} is beyond 2^63 - 2^48, the level a 64-bit "
+                                      "stock holds (InventoryBuffer.MAX_LEVEL; the reference's integers are unbounded)")
+        lead = _stock_seconds(what, "lead_time", ent.lead_time)
+        if lead > 2.0e9:
+            raise UnsupportedTopology(f"{what}: lead_time = {lead!r} is beyond 2e9 s")
+        if ent._order_pending:
+            raise UnsupportedTopology(f"{what}: an order is pending from an earlier run (not lowered)")
+        a.kind[i] = N.NODE_INVENTORY
+        so = ent.stockout_target
+        params[i] = (stock, point, order, int(np.float64(lead).view(np.int64)), -1 if so is None else cx.node_of[id(so)])
+
+
 def _lower_limiter(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
     pol = ent.policy
     if type(pol) not in LIMITER_POLICIES:
@@ -771,7 +834,7 @@ def _lower_sink(cx: _Lowering, a: GraphArrays, i: int, ent) -> None:
 _LOWER = ((Source, _lower_source), (Probe, _lower_probe), (Server, _lower_server), (NetworkLink, _lower_link),
           (LoadBalancer, _lower_load_balancer), (HealthChecker, _lower_health_checker), (AutoScaler, _lower_auto_scaler),
           (CanaryDeployer, _lower_canary_deployer), (RollingDeployer, _lower_rolling_deployer), ((Bulkhead, TimeoutWrapper), _lower_wrapper),
-          (Hedge, _lower_hedge), (Fallback, _lower_fallback), (Client, _lower_client), (_FLOWS, _lower_flow), (RateLimitedEntity, _lower_limiter), (RandomRouter, _lower_router))
+          (Hedge, _lower_hedge), (Fallback, _lower_fallback), (Client, _lower_client), (_FLOWS, _lower_flow), (_STOCK, _lower_stock), (RateLimitedEntity, _lower_limiter), (RandomRouter, _lower_router))
 
 
 def _assemble(cx: _Lowering) -> GeneralGraph:

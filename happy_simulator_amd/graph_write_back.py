@@ -8,7 +8,7 @@ from . import _native as N
 from .core.temporal import Duration, Instant
 from .entities import (QUEUE_POLICIES, AdaptiveLIFO, AutoScaler, BackendHealthState, BackendInfo, BatchProcessor, Bulkhead, CanaryDeployer,
                        CanaryState, Client, CoDelQueue, ConsistentHash, ConveyorBelt, DeploymentState, Fallback, GateController, HealthChecker, Hedge,
-                       IPHash, LoadBalancer, Network, NetworkLink, Probe, RandomRouter, RateLimitedEntity, RollingDeployer, RoundRobin,
+                       InventoryBuffer, IPHash, LoadBalancer, Network, NetworkLink, PooledCycleResource, Probe, RandomRouter, RateLimitedEntity, RollingDeployer, RoundRobin,
                        ScalingEvent, Server, Source, TimeoutWrapper, WeightedRoundRobin)
 from .graph_engine import GeneralGraph, GraphEngine
 
@@ -275,6 +275,19 @@ def _write_fallback(r: _Results, i: int, ent) -> None:
     ent._in_flight = {int(rid): {"start_time": Instant(int(t0)), "state": "fallback" if st else "primary"} for rid, t0, st in w["entries"]}
 
 
+def _write_pool(r: _Results, i: int, ent) -> None:
+    w = r.engine.stock(i)
+    ent._available, ent._active, ent._completed, ent._rejected = w["available"], w["active"], w["completed"], w["rejected"]
+    ent._queue = [None] * w["queued"]                     # (the waiting Requests stay on the device: one placeholder each)
+
+
+def _write_inventory(r: _Results, i: int, ent) -> None:
+    w = r.engine.stock(i)
+    ent._stock, ent._stockouts, ent._reorders, ent._items_consumed, ent._items_replenished = (
+        w["stock"], w["stockouts"], w["reorders"], w["items_consumed"], w["items_replenished"])
+    ent._order_pending = bool(w["order_pending"])
+
+
 def _write_limiter(r: _Results, i: int, ent) -> None:
     st = r.stats["limiters"][i]
     ent._received, ent._forwarded, ent._queued, ent._dropped = (int(st[k]) for k in ("received", "forwarded", "queued", "dropped"))
@@ -324,7 +337,7 @@ _WRITE_BACK = ((Source, _write_source), (Server, _write_server), (NetworkLink, _
                (LoadBalancer, _write_load_balancer), (CanaryDeployer, _write_canary_deployer), (RollingDeployer, _write_rolling_deployer),
                (AutoScaler, _write_auto_scaler), (HealthChecker, _write_health_checker), (Bulkhead, _write_bulkhead),
                ((BatchProcessor, ConveyorBelt, GateController), _write_flow), (Client, _write_client), (TimeoutWrapper, _write_timeout_wrapper),
-               (Hedge, _write_hedge), (Fallback, _write_fallback),
+               (Hedge, _write_hedge), (Fallback, _write_fallback), (PooledCycleResource, _write_pool), (InventoryBuffer, _write_inventory),
                (RateLimitedEntity, _write_limiter), (Probe, _write_probe), (RandomRouter, _write_router))
 
 

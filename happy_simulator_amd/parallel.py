@@ -21,7 +21,7 @@ import numpy as np
 from . import _native as N
 from .core.temporal import Instant
 from .engine import StationArrays, StationEngine
-from .entities import CanaryDeployer, RollingDeployer, AutoScaler, BatchProcessor, Bulkhead, Client, ConveyorBelt, Fallback, FIFOQueue, GateController, HealthChecker, Hedge, Probe, Server, TimeoutWrapper
+from .entities import CanaryDeployer, RollingDeployer, AutoScaler, BatchProcessor, Bulkhead, Client, ConveyorBelt, Fallback, FIFOQueue, GateController, HealthChecker, Hedge, InventoryBuffer, PooledCycleResource, Probe, Server, TimeoutWrapper
 from .graph_engine import GeneralGraph, GraphEngine
 from .lowering import UnsupportedTopology, write_back, write_back_probes
 from .simulation import Simulation, entity_summaries
@@ -449,6 +449,9 @@ class ParallelSimulation:
                 if isinstance(ent, (Hedge, Fallback)):
                     raise UnsupportedTopology(f"partition '{p.name}': the {type(ent).__name__} '{ent.name}' on a ParallelSimulation partition "
                                               "is not lowered (Hedge and Fallback run on the single-heap loop: pass it to a Simulation)")
+                if isinstance(ent, (PooledCycleResource, InventoryBuffer)):
+                    raise UnsupportedTopology(f"partition '{p.name}': the {type(ent).__name__} '{ent.name}' on a ParallelSimulation partition "
+                                              "is not lowered (it runs on the single-heap loop: pass it to a Simulation)")
                 if isinstance(ent, (BatchProcessor, ConveyorBelt, GateController)):
                     raise UnsupportedTopology(f"partition '{p.name}': the {type(ent).__name__} '{ent.name}' on a ParallelSimulation partition "
                                               "is not lowered (it runs on the single-heap loop: pass it to a Simulation)")

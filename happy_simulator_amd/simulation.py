@@ -14,7 +14,7 @@ from .core.temporal import Instant
 from .engine import StationEngine
 from .graph_engine import (DEFAULT_MAX_EVENTS, MAX_PARTS, GeneralGraph, GraphEngine, PartRun, keyless_hazard, lower_general, split_parts,
                            write_back_general)
-from .entities import CanaryDeployer, RollingDeployer, AutoScaler, BatchProcessor, Bulkhead, Client, ConveyorBelt, Entity, Fallback, GateController, HealthChecker, Hedge, LoadBalancer, Network, Server, TimeoutWrapper
+from .entities import CanaryDeployer, RollingDeployer, AutoScaler, BatchProcessor, Bulkhead, Client, ConveyorBelt, Entity, Fallback, GateController, HealthChecker, Hedge, InventoryBuffer, LoadBalancer, Network, PooledCycleResource, Server, TimeoutWrapper
 from .faults import FaultSchedule, LinkFaultEvent
 from .lowering import (LazyRecords, LbGraph, LoweredGraph, UnsupportedTopology, attach_lb_probes, attach_probes, find_load_balancer, lower,
                        plain_probe_arrays, write_back_plain_probes,
@@ -33,6 +33,7 @@ LAZY_PROBES_MIN = 256      # plain-chain runs with more Probes than this leave t
 # retries, stations that hold Requests back and release them together.
 _NOT_ON_STATIONS = "the station, network and pipeline engines do not lower "
 _SINGLE_HEAP_ONLY = (
+    ((PooledCycleResource, InventoryBuffer), True, _NOT_ON_STATIONS + "PooledCycleResource or InventoryBuffer"),
     ((Hedge, Fallback), True, _NOT_ON_STATIONS + "Hedge or Fallback"),
     ((RollingDeployer, CanaryDeployer), False, _NOT_ON_STATIONS + "a RollingDeployer or a CanaryDeployer"),
     (AutoScaler, False, _NOT_ON_STATIONS + "an AutoScaler"),
@@ -51,6 +52,7 @@ _BY_KIND = (
     (("has_deployers", "has_canaries"), "_deployer_by_kind", "deployer_events"),   # the deployers' seven kinds
     (("has_deployers", "has_canaries"), "_canary_by_kind", "canary_events"),
     (("has_hedges",), "_hedge_by_kind", "hedge_events"),                     # Hedge request / response / send-hedge, Fallback's four
+    (("has_stock",), "_stock_by_kind", "stock_events"),                      # a pool's Request / cycle end, a buffer's consume / replenish
 )
 
 
@@ -465,6 +467,10 @@ class Simulation:
                                           "RateLimitedEntity of this Simulation are lowered")
             if ev.on_complete:
                 raise UnsupportedTopology(f"scheduled event {ev!r}: completion hooks are host Python (not lowered)")
+            if a.has_stock and (ev.event_type == "_InventoryReplenish" or "quantity" in ev.context):
+                # (an event_type and a context travel on with the Event: either may reach a buffer from anywhere)
+                raise UnsupportedTopology(f"scheduled event {ev!r}: a hand-made '_InventoryReplenish' Event and a 'quantity' in an Event's "
+                                          "context are not lowered next to an InventoryBuffer (a consume takes one item)")
             rid = None
             if a.kind[i] == N.NODE_AUTO_SCALER:
                 # the Event AutoScaler.start() returns: a daemon without a Request, at the Simulation's start
@@ -584,7 +590,7 @@ class Simulation:
             fe = eng.flow_events()
             self._flow_by_kind = fe[:N.FLOW_KINDS]
             self._events_cancelled += int(fe[N.FLOW_KINDS])
-        if (a.has_health or a.has_wrappers or a.has_clients or a.has_flows or a.has_queue_policies or a.has_hedges) and not self._faults:
+        if (a.has_health or a.has_wrappers or a.has_clients or a.has_flows or a.has_queue_policies or a.has_hedges or a.has_stock) and not self._faults:
             self._internal_by_kind = eng.faults()[1]
         if self._faults:
             crashed, internal, popped_cancelled = eng.faults()

@@ -199,6 +199,10 @@ typedef enum hs_probe_metric {
     HS_PROBE_GT_QUEUE_DEPTH = 15,  /* GateController.queue_depth */
     HS_PROBE_AS_CURRENT_COUNT = 16,/* AutoScaler.current_count (general graphs only) */
     HS_PROBE_HG_IN_FLIGHT = 17,/* Hedge.in_flight_count (general graphs only) */
+    HS_PROBE_PC_AVAILABLE = 18,/* PooledCycleResource.available (general graphs only, like the three below) */
+    HS_PROBE_PC_ACTIVE = 19,   /* PooledCycleResource.active */
+    HS_PROBE_PC_QUEUED = 20,   /* PooledCycleResource.queued */
+    HS_PROBE_IB_STOCK = 21,    /* InventoryBuffer.stock */
     HS_PROBE_NONE = 255
 } hs_probe_metric;
 typedef enum hs_profile_kind { HS_PROF_CONSTANT = 0, HS_PROF_LINEAR_RAMP = 1, HS_PROF_SPIKE = 2 } hs_profile_kind;
@@ -770,7 +774,9 @@ typedef enum hs_node_kind { HS_NODE_SOURCE = 0, HS_NODE_SERVER = 1, HS_NODE_SINK
                              HS_NODE_ROLLING_DEPLOYER = 16,/* RollingDeployer: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_rolling_deployer */
                              HS_NODE_CANARY_DEPLOYER = 17, /* CanaryDeployer: `target` = -1 or its LoadBalancer; everything else: hs_graph_set_canary_deployer */
                              HS_NODE_HEDGE = 18,           /* Hedge: `target` = the entity it sends to; everything else: hs_graph_set_hedge */
-                             HS_NODE_FALLBACK = 19         /* Fallback: `target` = its primary; the fallback entity and the rest: hs_graph_set_fallback */
+                             HS_NODE_FALLBACK = 19,        /* Fallback: `target` = its primary; the fallback entity and the rest: hs_graph_set_fallback */
+                             HS_NODE_POOLED_CYCLE = 20,    /* PooledCycleResource: `target` = its downstream or -1; everything else: hs_graph_set_pool */
+                             HS_NODE_INVENTORY = 21        /* InventoryBuffer: `target` = its downstream or -1; its stock-out target and the rest: hs_graph_set_inventory */
 } hs_node_kind;
 
 typedef struct hs_graph_config {
@@ -1264,6 +1270,48 @@ int hs_graph_get_hedge(hs_graph *g, int32_t node, int64_t *counters, int64_t *en
  *   entries[3 * min(len(_in_flight), cap)]  id, start_time ns, state (0 "primary", 1 "fallback");
  *   events[HS_HEDGE_KINDS]  as above. */
 int hs_graph_get_fallback(hs_graph *g, int32_t node, int64_t *counters, int64_t *entries, int64_t cap, int64_t *events);
+/* PooledCycleResource and InventoryBuffer (components/industrial/pooled_cycle.py, inventory.py) on HS_NODE_POOLED_CYCLE /
+ * HS_NODE_INVENTORY nodes: the twelfth level of the single-heap loop, four more internal Event kinds (60 .. 63 of the 64 the kind word
+ * holds): a Request at a pool, the end of a cycle (a generator's continuation: never dropped), a consume Request at a buffer, its
+ * `_InventoryReplenish`.  Neither draws a random number.
+ *   PooledCycleResource: a Request that finds a unit free takes it (available -= 1, active += 1) and its continuation is constructed
+ *     at now + cycle_ns; otherwise it is rejected when queue_capacity > 0 and the line is that long, or appended to the line
+ *     (queue_capacity = 0: unbounded).  The continuation releases the unit, counts `completed`, forwards the Request to `target` with
+ *     its context (no target: the Request ends there) and, when the line is not empty, re-sends its head to the pool ITSELF as a NEW
+ *     Event at `now`: it goes through the heap with a fresh sort index, so an arrival of the same nanosecond that sorts ahead of it
+ *     takes the unit and the re-sent Request queues again at the back; a crashed pool drops it like any arrival.
+ *   InventoryBuffer: a consume takes one item (stock -= 1, items_consumed += 1, a NEW Event for `target`) or counts a stock-out (a NEW
+ *     Event for the stock-out target); then, when stock <= reorder_point and no order is pending, `reorders` += 1 and
+ *     `_InventoryReplenish` is constructed at from_seconds(to_seconds(now) + lead_time_s) -- a binary64 sum of seconds, truncated to
+ *     nanoseconds --, behind the forward.  The replenish adds order_quantity and clears the pending flag; one that a crashed buffer
+ *     drops leaves the flag set for ever.
+ * No completion hook reaches either of them: refused (HS_E_UNSUPPORTED) as a LoadBalancer's backend and as the target, primary or
+ * fallback entity -- directly or through NetworkLinks -- of a Bulkhead, TimeoutWrapper, Client, Hedge or Fallback.
+ *
+ * hs_graph_set_pool: pool_size in [1, HS_POOL_MAX_UNITS], cycle_ns = int(cycle_time * 1e9) >= 0 (what `Instant + seconds` adds),
+ * queue_capacity in [0, HS_POOL_MAX_UNITS] (0: unbounded).  hs_graph_set_inventory: initial_stock, reorder_point >= 0 and
+ * order_quantity > 0, each at most HS_INVENTORY_MAX (2^62) and reorder_point + order_quantity at most HS_INVENTORY_MAX_LEVEL -- the stock
+ * never passes max(initial_stock, reorder_point + order_quantity), an order being placed only at or below the reorder point and one at a
+ * time, and items_replenished never passes that plus the items consumed, so both stay inside int64 for any run of fewer than 2^48
+ * Events (HS_E_UNSUPPORTED beyond: the reference's integers are unbounded) --, lead_time_s finite and >= 0, stockout_node = -1 or a node
+ * that takes Requests.  Before the first run (HS_E_STATE afterwards); every such node is configured before a run (HS_E_STATE otherwise). */
+#define HS_POOL_MAX_UNITS (1 << 20)
+#define HS_INVENTORY_MAX (1ll << 62)
+#define HS_INVENTORY_MAX_LEVEL 0x7fff000000000000ll   /* 2^63 - 2^48 */
+#define HS_STOCK_KINDS 4
+#define HS_POOL_COUNTERS 5
+#define HS_INVENTORY_COUNTERS 6
+int hs_graph_set_pool(hs_graph *g, int32_t node, int32_t pool_size, int64_t cycle_ns, int32_t queue_capacity);
+int hs_graph_set_inventory(hs_graph *g, int32_t node, int64_t initial_stock, int64_t reorder_point, int64_t order_quantity, double lead_time_s,
+                           int32_t stockout_node);
+/* After a run (any output may be NULL; node = -1 with `counters` NULL: the event counts alone):
+ *   hs_graph_get_pool       counters[HS_POOL_COUNTERS]  _available, _active, len(_queue), _completed, _rejected;
+ *   hs_graph_get_inventory  counters[HS_INVENTORY_COUNTERS]  _stock, _stockouts, _reorders, _items_consumed, _items_replenished,
+ *                           _order_pending;
+ *   events[HS_STOCK_KINDS]  the graph's pool Request / cycle end / consume Request / replenish Events: events_processed ==
+ *                           sum(events_by_kind) + every other family's internal counts + sum(events). */
+int hs_graph_get_pool(hs_graph *g, int32_t node, int64_t *counters, int64_t *events);
+int hs_graph_get_inventory(hs_graph *g, int32_t node, int64_t *counters, int64_t *events);
 /* Debug / tests only (the null stream, its own allocations): the compaction of a deployed LoadBalancer's member list on the device.
  * list[len] = slots in [0, n_slots) in insertion order, member[n_slots] = the membership word of every slot; the entries whose word is
  * 0 leave, the others keep their order: list[0 .. *out_len) afterwards.  wave = 0: the lone lane; 1: all 64 lanes (a ballot and a
@@ -1306,8 +1354,8 @@ int hs_graph_run_many(hs_graph *const *graphs, int32_t n, int64_t end_ns);
  * -- case (i) occurred, or two parts hold the earliest time: the caller repeats the run on one heap (the handles' state is then
  * meaningless); or a negative hs_status.  Call once per handle set (no later end). */
 int hs_graph_run_parts(hs_graph *const *parts, int32_t n, int64_t end_ns);
-/* Read-only: the level of the loop (csrc/hs_graph.hip kLvPlain ... kLvHedge: 0 plain, 1 faults, 2 health, 3 resilience, 4 client,
- * 5 flow, 6 queue policies, 7 link faults, 8 scaler, 9 deployers, 10 hedge; a level carries the code of all below it).  which = 0: the
+/* Read-only: the level of the loop (csrc/hs_graph.hip kLvPlain ... kLvStock: 0 plain, 1 faults, 2 health, 3 resilience, 4 client,
+ * 5 flow, 6 queue policies, 7 link faults, 8 scaler, 9 deployers, 10 hedge, 11 pools and stock; a level carries the code of all below it).  which = 0: the
  * lowest level that dispatches all the graph's kinds, the one a lone run takes; which = 1: the level of the most recent launch the
  * handle ran in (a batch runs at the highest level of its handles), -1 before the first launch.  -1 for any other `which`. */
 int hs_graph_level(const hs_graph *g, int which);
